@@ -2,7 +2,8 @@
 """bench.py -- env-steps/s of the batched Gobblet hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B | --boards-per-gpu B]
-                    [--mode collect|fused|step|step2] [--traj T] [--graph 0|1] [--no-obs] [--no-configs] [--no-cpu-baseline]
+                    [--mode collect|fused|step|step2] [--traj T] [--graph 0|1] [--no-obs] [--dump-outputs DIR]
+                    [--full [--no-configs] [--no-cpu-baseline]]
 
 One "step" = one lockstep ply of the benchmark pipeline over this rank's shard of boards -- masked-uniform
 sampling + raw_env.step + observe of the next mover, with EVERY ply's action, mask, obs, winner, reward, done and
@@ -24,10 +25,14 @@ board id, ply) so results do not depend on N.  No collective on the step path: R
 barriers, one MAX-reduce of the elapsed time and one all-gather of per-rank numbers; the barrier on both sides of the timed
 span is the node's own (LocalBarrier, --span-barrier).  --boards-per-gpu B fixes the per-GPU shard instead
 ("weak" scaling).  For N>1 launch with torchrun (the driver does), one rank per GPU.
-By default K timed plies that take more than one launch are replayed as one hipGraph whose kernel nodes take the
-ply index from a device-resident counter (gbl_rollout_at + gbl_counter_add); a timed run of ONE launch (the
-driver's 20 plies) is launched eagerly, with the ply index by value.  Either way the K plies are played once UNTIMED through the same code path
-first and the timed pass plays K fresh plies; --graph 0 launches eagerly always.
+By default K timed plies that take more than one launch are replayed as hipGraphs (of up to GRAPH_LAUNCHES launches each) whose
+kernel nodes take the ply index from a device-resident counter (gbl_rollout_at + gbl_counter_add); a timed run of ONE launch (the
+driver's 20 plies) is launched eagerly, with the ply index by value.  Either way the plies are played once UNTIMED through the same code
+path first (each graph replayed once; eagerly, the first GRAPH_LAUNCHES launches) and the timed pass plays K fresh plies; --graph 0
+launches eagerly always.
+A plain run does only that: set up, W warm-up plies, the rehearsal, the K timed plies, --dump-outputs, the line.  Everything else
+it can measure -- the sub-records of the other configs, the scaling prediction, the CPU baseline, four more passes of the timed
+plies, step2's per-kernel timing -- runs with --full only.
 
 Rank 0 prints ONE compact JSON line (< 4 kB; the task's bench contract) as the LAST line of stdout:
     the contract keys, `config` (a workload string + scalars), and two flat objects
@@ -37,9 +42,9 @@ Rank 0 prints ONE compact JSON line (< 4 kB; the task's bench contract) as the L
                     winner 1 + done 1 + to_move 1 = 178) and the state only once per launch (57 B per board);
                     `traffic` = HBM bytes per launch from the committed PMC passes of the same launch shape
     cpu_baseline -- the CPU oracle (a C port of the reference algorithm; kind "port") doing the same pipeline
-                    on the host cores, on a bounded sample (rank 0, N=1 only)
+                    on the host cores, on a bounded sample (rank 0, N=1 only, --full)
 The FULL record goes to --configs-out (default gpurun_out/bench_configs.json, named in config.configs_file) and to stderr:
-    configs      -- (N=1 only) the other sizes BASELINE.json names, each a short run with its own roofline:
+    configs      -- (N=1 only, --full) the other sizes BASELINE.json names, each a short run with its own roofline:
                     4 096 and 262 144 boards, the 131 072-board shard of C4 at 8 GPUs, 2^22 boards (beyond the
                     Infinity Cache), MASK_ONLY at 2^20, and config 5 (65 536 boards x depth-2 greedy)
     detail       -- per-rank kernel times and trajectory placements; cpu_baseline's greedy extras.
@@ -63,6 +68,10 @@ ALGO_BYTES_COLLECT_PLY, ALGO_BYTES_COLLECT_PLY_MASK_ONLY, ALGO_BYTES_COLLECT_LAU
 HBM_PEAK_GBPS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec
 SIMDS, CLOCK_GHZ = 1024, 2.4  # 256 CUs x 4 SIMDs; max shader clock (MI355X_MICROARCH.md)
 TOTAL_BOARDS = 1 << 20
+# launches per captured hipGraph of the timed plies: K plies beyond that replay the same graph again (and a second one for the
+# rest), so that capturing and the untimed rehearsal cost at most two such graphs however large --steps is
+GRAPH_LAUNCHES = 512
+DUMP_BOARDS = 65536  # --dump-outputs: boards sampled (~205 float32 values each, < 64 MB in all)
 COLLECT_KERNELS = {0: "k_collect", 1: "k_collect (plain stores)", 2: "k_collect2", 4: "k_collect3", 5: "k_collect5"}  # gbl_collect_variant()
 
 
@@ -116,7 +125,7 @@ def parse():
     ap.add_argument("--traj", type=int, default=0,
                     help="plies per launch in mode collect; 0 = by shard size (auto_traj: 1024 for <= 8192 boards per GPU ... 8 "
                          "at 2^20, 4 from 2^22), never more than --steps")
-    ap.add_argument("--graph", type=int, default=1, help="1: replay the K timed plies as one hipGraph; 0: eager launches")
+    ap.add_argument("--graph", type=int, default=1, help="1: replay the K timed plies as hipGraphs; 0: eager launches")
     ap.add_argument("--no-obs", action="store_true",
                     help="MASK_ONLY variant (BASELINE.md: 117 algorithmic bytes per env-step): no observation tensor")
     ap.add_argument("--placement", choices=["auto", "spread", "any"], default="auto",
@@ -135,6 +144,13 @@ def parse():
                          "memory (one node is the contract; ~1 us); dist = torch.distributed's (RCCL: an all-reduce + a "
                          "synchronize per barrier, which at 8 ranks lasts about as long as the shard's 20 plies)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the sub-records of the other BASELINE configs, the scaling "
+                         "prediction, the CPU baseline, four more passes of the timed plies and step2's per-kernel timing "
+                         "(--no-configs / --no-cpu-baseline still drop parts of it); off: set up, warm up, time the K plies, report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed plies, write what the last one computed as DIR/<name>.npy (float32) for a fixed, "
+                         f"seeded sample of at most {DUMP_BOARDS} of rank 0's boards (DIR/board_index.npy: their global ids)")
     return ap.parse_args()
 
 
@@ -785,8 +801,8 @@ def contract_record(args, p, roof, total, boards, world, K, W, elapsed, local_el
                    "launch": "hipGraph replay" if graphed else "eager launches",
                    # the dominant kernel's mean launch duration on the slowest / fastest rank (HIP events), timed pass
                    "kernel_us_max": max(per_rank_us), "kernel_us_min": min(per_rank_us),
-                   # the same K plies played FOUR MORE times behind the contract's pass (rank 0; mean launch duration of each
-                   # pass by HIP events): whether the one timed pass was luck shows here
+                   # (--full) the same K plies played FOUR MORE times behind the contract's pass (rank 0; mean launch duration
+                   # of each pass by HIP events): whether the one timed pass was luck shows here
                    "kernel_us_median_of_5": reps[len(reps) // 2] if reps else None,
                    "kernel_us_min_of_5": reps[0] if reps else None, "kernel_us_max_of_5": reps[-1] if reps else None,
                    # each rank's own span, from the synchronize behind the leading barrier to the synchronize behind its last
@@ -811,7 +827,7 @@ def contract_record(args, p, roof, total, boards, world, K, W, elapsed, local_el
                    "kernel_us_of_5_passes": repeats_us,
                    "sharding": f"contiguous board ranges, {world} shard(s), no collective on the step path",
                    "launch": ("hipGraph replay of the K plies' launches (device-resident ply index; one untimed warm replay of "
-                              "the same graph = K more untimed plies before the timed one)") if graphed else "eager"},
+                              "each graph before the timed one)") if graphed else "eager"},
     }
 
 
@@ -851,6 +867,35 @@ def compact_line(full, configs_path):
         text = json.dumps(line)
     assert len(text.encode()) <= COMPACT_LIMIT, "bench.py: the contract line outgrew the driver's tail"
     return text
+
+
+OUTPUT_NAMES = ("actions", "winner", "rewards", "done", "to_move", "action_mask", "observation")
+
+
+def output_sample(p, env_base, last_launch_plies):
+    """--dump-outputs: what the timed path's last ply handed its caller -- mode collect: that ply's slot of the trajectory arrays,
+    the other modes: the environment's output tensors -- and the board state after it, for a fixed, seeded sample of this shard's
+    boards (all of them up to DUMP_BOARDS), as float32 arrays on the host.  In mode step "actions" holds what that ply's launch
+    wrote over the action array: the NEXT ply's masked-random draw (gbl_step_ex), not the action just played."""
+    import numpy as np
+    torch, env, n = p.torch, p.env, p.boards
+    pick = np.arange(n) if n <= DUMP_BOARDS else np.sort(np.random.default_rng(0).choice(n, DUMP_BOARDS, replace=False))
+    idx = torch.from_numpy(pick).to(p.dev)
+    if p.traj is not None:
+        src = {k: p.traj[k][last_launch_plies - 1] for k in OUTPUT_NAMES if k in p.traj}
+    else:
+        src = {k: getattr(env, k) for k in OUTPUT_NAMES if getattr(env, k) is not None}
+    src["squares"] = env.squares
+    out = {k: v.index_select(0, idx).to(torch.float32).cpu().numpy() for k, v in src.items()}
+    out["board_index"] = (env_base + pick).astype(np.float64)
+    return out
+
+
+def write_outputs(outputs, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def emit(full, configs_out):
@@ -966,7 +1011,8 @@ def main():
     args.traj = auto_traj(boards, K, args.traj, no_obs=args.no_obs)
     p = Pipeline(G, torch, boards, env_base, dev, no_obs=args.no_obs, mode=args.mode, traj=args.traj,
                  placement=args.placement)
-    nlaunch = len(p.plan(K))
+    plan = p.plan(K)
+    nlaunch = len(plan)
     p.eager(W)  # warm-up plies (untimed): decorrelate game phases, warm caches / code objects
     torch.cuda.synchronize(dev)
     if dist is not None:
@@ -979,30 +1025,38 @@ def main():
     # no sooner and carries the counter node inside the timed span (131 072 boards x 20 plies: 90 vs 99 us of wall clock,
     # scripts/experiments/launch_overhead.py); several launches are replayed as one hipGraph.  Either way the K plies are played ONCE untimed
     # through the very same code path first (the first launch of an instantiated graph carries one-off costs, and so does the first
-    # pass of the host code: 30 us on a 560 us region), then timed.
+    # pass of the host code: 30 us on a 560 us region), then timed.  More than GRAPH_LAUNCHES launches are captured as one graph of
+    # that many, replayed back to back, plus one graph of the rest (the same launches in the same order); the rehearsal replays each
+    # graph once -- eagerly, the first GRAPH_LAUNCHES launches -- so that neither grows with K.
     use_graph = bool(args.graph) and nlaunch > 1
-    graph = p.capture(K) if use_graph else None
+    graphs = []  # [(graph, replays per pass)]
+    if use_graph:
+        chunk = sum(plies for _, plies in plan[:GRAPH_LAUNCHES])
+        replays, rest = divmod(K, chunk)
+        graphs = [(p.capture(chunk), replays)] + ([(p.capture(rest), 1)] if rest else [])
     ev = p.events(1 if use_graph else nlaunch)
     stream = p.nat.current_stream(dev)
 
     # eager gbl_collect launches take the ply index by value (what BatchedGobblet.collect does without device_ply()): the launch
     # that would move a device-resident index on is not needed, and not in the span (scripts/experiments/span_overhead.py: 7 of its 22 us)
-    by_value = graph is None and args.mode == "collect"
+    by_value = not graphs and args.mode == "collect"
 
-    def play_k():
-        if graph is not None:
+    def play_k(rehearsal=False):
+        if graphs:
             ev[0][0].record()
-            graph.replay()        # (its last node moves the device-resident ply index on)
+            for g, n in graphs:
+                for _ in range(1 if rehearsal else n):
+                    g.replay()    # (its last node moves the device-resident ply index on)
             ev[0][1].record()
         else:
-            for i, (off, plies) in enumerate(p.plan(K)):
+            launches = plan[:GRAPH_LAUNCHES] if rehearsal else plan
+            for i, (off, plies) in enumerate(launches):
                 p.enqueue(off, plies, stream, ev[i], by_value=by_value)
-
-    def bookkeeping():
-        if by_value:
-            p.played(K)           # (host arithmetic)
-        elif graph is None:       # eager, one ply per launch: the launch that moves the device-resident ply index on
-            p.advance(K, stream)
+            k = sum(plies for _, plies in launches)
+            if by_value:
+                p.played(k)       # (host arithmetic)
+            else:                 # eager, one ply per launch: the launch that moves the device-resident ply index on
+                p.advance(k, stream)
 
     span_barrier, lb = None, None
     args.span_barrier_used = None
@@ -1016,35 +1070,41 @@ def main():
             span_barrier, args.span_barrier_used = dist.barrier, "torch.distributed (%s)" % args.dist_backend
 
     def pass_kernel_us():         # mean launch duration of the dominant kernel over the pass just played (HIP events)
-        if graph is None:
+        if not graphs:
             return sum(a.elapsed_time(b) for a, b in ev) / nlaunch * 1e3
         return ev[0][0].elapsed_time(ev[0][1]) / nlaunch * 1e3
 
-    play_k()                      # untimed rehearsal: K more warm plies
-    bookkeeping()
+    play_k(rehearsal=True)        # untimed rehearsal: up to K more warm plies
     torch.cuda.synchronize(dev)
     if span_barrier is not None:
         span_barrier()            # (rehearsed too)
         span_barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    play_k()
-    bookkeeping()                 # (inside the timed region, as in the graph)
+    play_k()                      # (the eager form's bookkeeping inside the timed region, as in the graph)
     torch.cuda.synchronize(dev)
     local_elapsed = time.perf_counter() - t0  # this rank's own span (reported beside the contract's)
     if span_barrier is not None:
         span_barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0        # the contract's span: barrier + synchronize on both sides
+    # what the last timed ply computed, before anything else runs on these buffers (--full plays more plies into them)
+    outputs = output_sample(p, env_base, plan[-1][1]) if args.dump_outputs and rank == 0 else None
 
     # dominant-kernel time for the roofline: HIP events on the launch stream
-    plies_timed = K
-    if graph is None:
+    plies_timed, roof_note = K, None
+    if not graphs:
         kernel_s = sum(a.elapsed_time(b) for a, b in ev) / 1e3
         launches, timing = nlaunch, "HIP event pair around every launch of the dominant kernel"
     elif args.mode != "step2":
         kernel_s = ev[0][0].elapsed_time(ev[0][1]) / 1e3
         launches, timing = nlaunch, "HIP events around the graph replay of all launches (includes kernel boundaries)"
+    elif not args.full:
+        # two kernels per ply in the graph; timing gbl_step alone takes a pass of its own (--full)
+        kernel_s = ev[0][0].elapsed_time(ev[0][1]) / 1e3
+        launches, timing = nlaunch, "HIP events around the graph replay of all launches: k_sample + k_step per ply (--full: k_step alone)"
+        roof_note = ("two kernels per ply (k_sample 58 B + k_step 234 B algorithmic per board): the fraction is the whole ply's "
+                     "time against k_step's 234 bytes")   # (the compact line says so in roofline.kernel)
     else:
         # two kernels per ply in the graph: time gbl_step on its own with event pairs, eagerly, after the timed region
         plies_timed = launches = min(K, 64)
@@ -1056,11 +1116,10 @@ def main():
     mean_kernel_s = kernel_s / launches
     # the headline's timed sample may be ONE launch: play the same K plies four more times (rank 0 reports the spread)
     repeats_us = []
-    if args.mode != "step2":
+    if args.full and args.mode != "step2":
         repeats_us.append(pass_kernel_us())
         for _ in range(4):
             play_k()
-            bookkeeping()
             torch.cuda.synchronize(dev)
             repeats_us.append(pass_kernel_us())
     p.settle(stream)  # (plies launched with the index by value: the device-resident index catches up)
@@ -1089,11 +1148,14 @@ def main():
 
     if rank == 0:
         roof = p.kernel_roofline(kernel_s, plies_timed, launches, timing)
+        if roof_note:
+            roof["note"] = roof_note
+            roof["kernel"] = roof["kernel"].replace("k_step", "k_sample + k_step (whole ply)", 1)
         # (the counters were taken on launches of exactly T plies; the timed launches may end with a shorter one)
         attach_traffic(roof, p, min(args.traj, K) if args.mode == "collect" else 1)
-        full = contract_record(args, p, roof, total, boards, world, K, W, elapsed, local_elapsed, nlaunch, graph is not None,
+        full = contract_record(args, p, roof, total, boards, world, K, W, elapsed, local_elapsed, nlaunch, bool(graphs),
                                per_rank_us, per_rank_placement, dist is not None, repeats_us)
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             cfg = {}
             for name, (n, k, noobs, mode) in CONFIG_RECORDS.items():
                 cfg[name] = short_run(G, torch, dev, n, k, max(W, 64) if name == "headline_recipe_1048576" else W, no_obs=noobs,
@@ -1107,7 +1169,7 @@ def main():
             full["configs"] = cfg
             if args.mode == "collect" and not args.boards_per_gpu and total % 8 == 0:
                 full["scale_prediction"] = scale_prediction(G, torch, dev, total, K, W, full["value"], args.placement)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             full["cpu_baseline"] = cpu_baseline(boards, W, args.cpu_seconds)
             ref = full["cpu_baseline"].get("greedy_depth2")
             if ref and "configs" in full:
@@ -1118,6 +1180,8 @@ def main():
                 c5["legality_tests_per_s_equivalent"] = c5["value"] * ref["legality_tests_per_decision"]
                 c5["leaf_evaluations_per_s_equivalent"] = c5["value"] * ref["leaf_evaluations_per_decision"]
                 c5["cpu_port_decisions_per_s_1core"] = ref["decisions_per_s_1core"]
+        if outputs is not None:
+            write_outputs(outputs, args.dump_outputs)
         emit(full, args.configs_out)
     if lb is not None:
         lb.close()

@@ -19,13 +19,13 @@ done
 [ "$STAGE" = b ] || scripts/build_variant.sh stamps -DGBL_STAMPS -DGBL_AB_COLLECT_CFG >> $O/build_$STAGE.log 2>&1   # (diagnostic build for the phase stamps)
 bench_lines() {
 # stdout of bench.py is the compact contract line; the full record (sub-records, per-rank lists) goes to --configs-out
-python bench.py --configs-out $O/bench_default_full.json > $O/bench_default.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --configs-out $O/bench_driver_cmd_full.json > $O/bench_driver_cmd.json   # the driver's exact command
-python bench.py --mode fused --no-configs --no-cpu-baseline --configs-out $O/bench_single_ply_full.json > $O/bench_single_ply.json
-python bench.py --mode step --no-configs --no-cpu-baseline --configs-out $O/bench_stepmode_full.json > $O/bench_stepmode.json
-python bench.py --mode step2 --no-configs --no-cpu-baseline --configs-out $O/bench_step_two_launch_full.json > $O/bench_step_two_launch.json
-python bench.py --no-obs --no-configs --no-cpu-baseline --configs-out $O/bench_maskonly_full.json > $O/bench_maskonly.json
-python bench.py --boards 131072 --no-configs --no-cpu-baseline --configs-out $O/bench_c4_shard_131072_full.json > $O/bench_c4_shard_131072.json
+python bench.py --full --configs-out $O/bench_default_full.json > $O/bench_default.json
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --configs-out $O/bench_driver_cmd_full.json > $O/bench_driver_cmd.json   # the driver's command + --full
+python bench.py --mode fused --full --no-configs --no-cpu-baseline --configs-out $O/bench_single_ply_full.json > $O/bench_single_ply.json
+python bench.py --mode step --full --no-configs --no-cpu-baseline --configs-out $O/bench_stepmode_full.json > $O/bench_stepmode.json
+python bench.py --mode step2 --full --no-configs --no-cpu-baseline --configs-out $O/bench_step_two_launch_full.json > $O/bench_step_two_launch.json
+python bench.py --no-obs --full --no-configs --no-cpu-baseline --configs-out $O/bench_maskonly_full.json > $O/bench_maskonly.json
+python bench.py --boards 131072 --full --no-configs --no-cpu-baseline --configs-out $O/bench_c4_shard_131072_full.json > $O/bench_c4_shard_131072.json
 }
 if [ "$STAGE" = c ]; then
 # the bench lines once more, AFTER scripts/profile_collect.py has written profiles/pmc_traffic.json for these kernel sources
@@ -80,13 +80,13 @@ fi   # SHORT
 python scripts/soak_parity.py ${SOAK_SECONDS:-150} 3 > $O/soak_parity.txt 2>&1
 echo "bench lines done"
 # ---- kernel traces (durations) ------------------------------------------------------------------------------
-rocprofv3 --kernel-trace --stats -d $O/collect_stats -o p -- python3 bench.py --steps 320 --no-configs --no-cpu-baseline > $O/collect_stats.log 2>&1
-rocprofv3 --kernel-trace --stats -d $O/single_stats -o p -- python3 bench.py --mode fused --steps 300 --no-configs --no-cpu-baseline > $O/single_stats.log 2>&1
-rocprofv3 --kernel-trace --stats -d $O/step_stats -o p -- python3 bench.py --mode step --steps 300 --no-configs --no-cpu-baseline > $O/step_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/collect_stats -o p -- python3 bench.py --steps 320 --full --no-configs --no-cpu-baseline > $O/collect_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/single_stats -o p -- python3 bench.py --mode fused --steps 300 --full --no-configs --no-cpu-baseline > $O/single_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/step_stats -o p -- python3 bench.py --mode step --steps 300 --full --no-configs --no-cpu-baseline > $O/step_stats.log 2>&1
 rocprofv3 --kernel-trace -d $O/sweep_trace -o p -- python3 scripts/sweep_sizes.py --sizes 4096,16384,32768,65536,131072,262144,1048576 --modes full,mask,traj,trajmask --plies 128 --reps 2 > $O/sweep_trace.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/greedy_stats -o p -- python3 scripts/run_eager.py greedy 65536 20 > $O/greedy_stats.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/policy_stats -o p -- python3 scripts/run_eager.py policy 65536 8 16 > $O/policy_stats.log 2>&1
-rocprofv3 --kernel-trace --stats -d $O/driver_stats -o p -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/driver_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/driver_stats -o p -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-configs --no-cpu-baseline > $O/driver_stats.log 2>&1
 echo "kernel traces done"
 fi
 if [ "$STAGE" != a ]; then

@@ -111,3 +111,14 @@ def test_more_ranks_than_gpus_fails_fast_with_a_clear_message():
                                "--warmup", "5"], capture_output=True, text=True, timeout=120, env=env)
     assert launched.returncode != 0 and "2 rank(s) but this node has" in launched.stderr
     assert time.time() - t0 < 100
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` measures the headline alone: --full (other configs, CPU baseline, extra passes)
+    and --dump-outputs are off unless asked for."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and not a.no_configs and not a.no_cpu_baseline

@@ -1098,7 +1098,7 @@ def test_bench_script_runs_and_reports(G):
 
 
 def test_bench_driver_command_prints_a_compact_line(G):
-    """The driver's EXACT command -- python3 bench.py --gpus 1 --steps 20 --warmup 5, sub-records and CPU baseline ON -- must
+    """The driver's command with --full -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full, sub-records and CPU baseline ON -- must
     end stdout with ONE compact line (< 4 096 bytes: the driver keeps only the tail of stdout; round 3's 20 kB line came back
     `parsed: null`) that carries the contract's keys, a flat roofline with `frac` and `traffic`, and a flat cpu_baseline; the 18
     sub-records are in the file config.configs_file names.  And: the same command under a launcher with WORLD_SIZE=1 (how a
@@ -1108,7 +1108,7 @@ def test_bench_driver_command_prints_a_compact_line(G):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     import bench
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], capture_output=True,
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], capture_output=True,
                          text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     last = out.stdout.rstrip("\n").splitlines()[-1]
@@ -1144,6 +1144,41 @@ def test_bench_driver_command_prints_a_compact_line(G):
     assert e["config"]["workload"] == d["config"]["workload"] and e["roofline"]["kernel"] == d["roofline"]["kernel"]
     assert e["config"]["plies_per_launch"] == d["config"]["plies_per_launch"] and e["n_gpus"] == 1
     assert e["config"]["rccl_ranks"] == 0 and e["config"]["dist_backend"] is None  # (world 1: no process group, as in the bare form)
+
+
+def test_bench_plain_run_dumps_the_last_ply(G, tmp_path):
+    """A plain bench.py run (no --full) reports the headline alone, and --dump-outputs writes what its last timed ply computed:
+    equal to the oracle playing the same plies (W warm-up + the untimed rehearsal + K timed).  Mode collect in one eager launch,
+    in launches of 8 + 8 + 4 plies (the last, shorter launch's last slot), and at 131 072 boards (the seeded sample of 65 536);
+    mode fused with more launches than one graph holds (a graph replayed twice + a graph of the rest; the rehearsal replays each
+    once: 512 + 76 plies); mode step (the action array holds the NEXT ply's fused draw) and step2."""
+    import bench
+    cases = ((16384, 20, ["--mode", "collect"], 20), (16384, 20, ["--mode", "collect", "--traj", "8"], 20),
+             (131072, 20, ["--mode", "collect"], 20), (4096, 1100, ["--mode", "fused"], 588),
+             (16384, 20, ["--mode", "step"], 20), (16384, 20, ["--mode", "step2"], 20))
+    for i, (boards, steps, extra, rehearsal) in enumerate(cases):
+        out_dir = tmp_path / str(i)
+        lines, full, _ = _bench(["--boards", str(boards), "--steps", str(steps), "--warmup", "5", "--dump-outputs", str(out_dir), *extra])
+        d = json.loads(lines[-1])
+        assert d["steps"] == steps and abs(d["value"] - boards * steps / (d["ms_per_step"] * steps / 1e3)) / d["value"] < 1e-6
+        assert "cpu_baseline" not in d and "configs_compact" not in d and "scale_prediction" not in d and "configs" not in full
+        assert d["config"]["kernel_us_median_of_5"] is None                      # (the four extra passes are --full's)
+        if extra[1] == "step2":  # (a plain run times the whole ply in the graph, and its line says so)
+            assert d["roofline"]["kernel"].startswith("k_sample + k_step (whole ply)"), d["roofline"]["kernel"]
+        got = {f.stem: np.load(f) for f in out_dir.glob("*.npy")}
+        assert set(got) == {"actions", "winner", "rewards", "done", "to_move", "action_mask", "observation", "squares", "board_index"}
+        rows = min(boards, bench.DUMP_BOARDS)
+        assert all(a.dtype in (np.float32, np.float64) and a.shape[0] == rows for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        idx = got["board_index"].astype(np.int64)
+        assert np.array_equal(got["board_index"], idx) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < boards
+        s, tm, dn = oracle.batch_reset(boards)
+        last = 5 + rehearsal + steps - 1
+        o = oracle.batch_rollout(s, tm, dn, 0, 0, 0, last + 1, threads=4)
+        acts = oracle.batch_sample(o["mask"], 0, 0, last + 1) if extra[1] == "step" else o["actions"]
+        for name, exp in (("actions", acts), ("winner", o["winner"]), ("rewards", o["reward"]), ("action_mask", o["mask"]),
+                          ("observation", o["obs"]), ("squares", s), ("to_move", tm), ("done", dn)):
+            assert np.array_equal(got[name], exp[idx].astype(np.float32)), (extra, name)
 
 
 def test_bench_script_two_ranks_rehearsal(G):
