@@ -4,6 +4,7 @@
     BatchedBoard     the reference ``Board`` interface over N boards
     gobblet_v1       ``env() / raw_env()``: the reference's single-env AEC surface over the same engine
     GreedyGobbletPolicy  the reference's depth-1/2 lookahead policy, batched
+    MonteCarloGobbletPolicy  flat Monte-Carlo playouts per candidate action (strength tunable by the playout count)
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in
 ``include/gobblet_hip.h``); there is no CPU fallback.  Importing this package needs torch;
@@ -15,6 +16,7 @@ from ._native import GobbletHipError, build  # noqa: F401
 from .board import BatchedBoard  # noqa: F401
 from .vector_env import BatchedGobblet  # noqa: F401
 from .greedy_policy import GreedyGobbletPolicy  # noqa: F401
+from .playout_policy import MonteCarloGobbletPolicy  # noqa: F401
 from .random_policy import RandomAdmissiblePolicy  # noqa: F401
 from .sharding import make_shard, reduce_counters, shard_bounds  # noqa: F401
 

@@ -61,20 +61,20 @@ int fail(int code, const char *msg)
     return code;
 }
 
-int thread_count(int64_t n)
+int thread_count(int64_t n, int64_t grain)
 {
     int t = g_threads.load();
     if (t <= 0) t = (int)std::thread::hardware_concurrency();
     if (t <= 0) t = 1;
-    const int64_t by_work = (n + 2047) / 2048;  // a thread is worth starting for a few thousand boards
+    const int64_t by_work = (n + grain - 1) / grain;  // a thread is worth starting for a few thousand boards (one-ply work)
     return (int)std::max<int64_t>(1, std::min<int64_t>(t, by_work));
 }
 
-// f(b0, b1) over [0, n) in contiguous ranges, one per thread
+// f(b0, b1) over [0, n) in contiguous ranges, one per thread; grain = boards per thread below which fewer threads start
 template <typename F>
-void parallel_for(int64_t n, F f)
+void parallel_for(int64_t n, F f, int64_t grain = 2048)
 {
-    const int t = thread_count(n);
+    const int t = thread_count(n, grain);
     if (t == 1) {
         f((int64_t)0, n);
         return;
@@ -634,6 +634,47 @@ int gbl_cpu_greedy_act(const int8_t *state, const int8_t *to_move, const int8_t 
 {
     return gbl_cpu_greedy_act_at(state, to_move, mask, hist, depth, seed, env_base, call, nullptr, action_out, chosen_out, cand_mask_out,
                                  fallback_out, n, stream);
+}
+
+int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
+                           uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
+                           int32_t *action_out, int32_t *plies_out, int64_t n, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (playouts < 1 || playouts > 4096) return fail(GBL_ERR_ARG, "playouts must be in [1, 4096]");
+    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
+    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is playouts x ~30 whole games: every board is worth a thread)
+        for (int64_t b = b0; b < b1; ++b) {
+            uint32_t r[7];
+            load_row(state, b, r);
+            const Planes root = make_planes(r);
+            const int mover = to_move[b] != 0;
+            uint64_t cand = legal54(root, mover);
+            if (mask) cand &= read_mask(mask + b * kActions);
+            int32_t wins[kActions] = {}, losses[kActions] = {};
+            uint32_t plies = 0, best = 0;
+            for (int a = 0; a < kActions; ++a) {
+                if (!((cand >> a) & 1ull)) continue;
+                for (int k = 0; k < playouts; ++k) {
+                    const PlayoutEnd e = playout(root, mover, a, seed, playout_id(env_base + (uint64_t)b, (uint32_t)a, (uint32_t)k), call,
+                                                 (uint32_t)max_plies);
+                    wins[a] += e.outcome > 0;
+                    losses[a] += e.outcome < 0;
+                    plies += e.plies;
+                }
+                best = std::max(best, playout_key(wins[a], losses[a], a));
+            }
+            if (wins_out) memcpy(wins_out + b * kActions, wins, sizeof wins);
+            if (losses_out) memcpy(losses_out + b * kActions, losses, sizeof losses);
+            if (action_out) action_out[b] = playout_action_of(best);
+            if (plies_out) plies_out[b] = (int32_t)plies;
+        }
+    }, 1);
+    return GBL_OK;
 }
 
 int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *hist, int32_t *actions_traj, int8_t *winner_traj,

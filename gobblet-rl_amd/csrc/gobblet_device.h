@@ -933,8 +933,9 @@ __device__ __forceinline__ uint32_t kth_bit32(uint32_t w, uint32_t k)
 // (word ply & 3 of the block with counter ply >> 2): a kernel that plays several plies per launch
 // runs the generator once per four.
 // `stream` (counter word 3) separates the consumers of one (seed, board) pair: kStreamEnv = the masked-random
-// actions of gbl_sample / gbl_rollout, kStreamGreedy = the greedy policy's fallback draw (gbl_greedy_act).
-constexpr uint32_t kStreamEnv = 0u, kStreamGreedy = 1u;
+// actions of gbl_sample / gbl_rollout, kStreamGreedy = the greedy policy's fallback draw (gbl_greedy_act),
+// kStreamPlayout = the moves of the Monte-Carlo playouts (gbl_playout_values, keyed by a playout id, not a board id).
+constexpr uint32_t kStreamEnv = 0u, kStreamGreedy = 1u, kStreamPlayout = 2u;
 
 __device__ __forceinline__ Draw4 draw_block(uint64_t seed, uint64_t env_id, uint32_t ply, uint32_t stream = kStreamEnv)
 {
@@ -1064,6 +1065,64 @@ __device__ __forceinline__ uint64_t next_mask(const Planes &p, int mover, int dn
 {
     return (dn && !auto_reset) ? 0ull : legal54(p, mover);
 }
+
+// ---- gbl_playout_values: flat Monte-Carlo playouts -------------------------------------------
+// Playout k of action a on global board g draws from generator id playout_id(g, a, k) on stream kStreamPlayout, with
+// ply index (call << 8) | t for its ply t (t = 0 is the root move, t = 1 .. max_plies the masked-random plies).  The id
+// does not depend on the number of playouts, so the first k playouts of a board are the same for every K >= k.
+__device__ __forceinline__ uint64_t playout_id(uint64_t g, uint32_t a, uint32_t k) { return (g * kActions + a) * 65536ull + k; }
+__device__ __forceinline__ uint32_t playout_ply_index(uint32_t call, uint32_t t) { return (call << 8) | t; }
+
+// One ply of a playout: the root move a0 at t = 0, else the masked-uniform move of the side to move on generator word w
+// (draw_word of the block of ply index playout_ply_index(call, t)).  Returns the winner after the move, or kPlayoutStuck
+// when the side to move has no legal move (nothing is played; only outside the state contract).
+constexpr int kPlayoutStuck = 2;
+
+__device__ __forceinline__ int playout_ply(Planes &p, int &side, uint32_t t, int a0, uint32_t w)
+{
+    const int a = t == 0 ? a0 : pick54(legal54(p, side), w);
+    if (a < 0) return kPlayoutStuck;
+    move_planes(p, side, (uint32_t)a);
+    side ^= 1;
+    return winner_of(p);
+}
+
+// The end of a playout after ply t returned w: +1 / -1 = won / lost from the root mover's side, 0 = unfinished, and the
+// plies the playout played (its root move included).  done = false: the playout goes on with ply t + 1.
+struct PlayoutEnd {
+    bool done;
+    int outcome;
+    uint32_t plies;
+};
+
+__device__ __forceinline__ PlayoutEnd playout_end(int w, uint32_t t, int mover, uint32_t max_plies)
+{
+    if (w == kPlayoutStuck) return PlayoutEnd{true, 0, t};
+    if (w != 0) return PlayoutEnd{true, mover ? -w : w, t + 1};
+    return PlayoutEnd{t >= max_plies, 0, t + 1};
+}
+
+// One whole playout, ply after ply (the host flavour; the kernel interleaves the same plies with refills, k_playout)
+__device__ __forceinline__ PlayoutEnd playout(const Planes &root, int mover, int a, uint64_t seed, uint64_t pid, uint32_t call,
+                                              uint32_t max_plies)
+{
+    Planes p = root;
+    int side = mover;
+    Draw4 d{};
+    for (uint32_t t = 0;; ++t) {
+        if ((t & 3u) == 0) d = draw_block(seed, pid, playout_ply_index(call, t), kStreamPlayout);  // one block per four plies
+        const PlayoutEnd e = playout_end(playout_ply(p, side, t, a, draw_word(d, t)), t, mover, max_plies);
+        if (e.done) return e;
+    }
+}
+
+// gbl_playout_values' decision: the candidate with the largest wins - losses, the lowest index on ties, -1 if none.  playout_key is the
+// order key of a candidate (0 stands for a non-candidate): larger is better, the max over the 54 keys decides.
+__device__ __forceinline__ uint32_t playout_key(int wins, int losses, int a)
+{
+    return ((uint32_t)(wins - losses + 8192) << 6) | (uint32_t)(63 - a);  // |wins - losses| <= 4096
+}
+__device__ __forceinline__ int playout_action_of(uint32_t best_key) { return best_key ? 63 - (int)(best_key & 63u) : -1; }
 
 // 54 mask bytes (14 dwords, row_load order) -> 54 bits
 __device__ __forceinline__ uint64_t mask_bits(const uint32_t (&d)[14])

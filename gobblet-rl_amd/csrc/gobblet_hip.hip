@@ -1651,6 +1651,96 @@ __global__ __launch_bounds__(64) void k_validate(const int8_t *__restrict__ stat
     flags[L.b] = (int8_t)validate_row(r);
 }
 
+// gbl_playout_values: flat Monte-Carlo values.  One workgroup of W wavefronts per board (a grid-stride loop over boards).  The
+// root position stays in registers (lane c < 27 reads cell c, and three ballots are its planes); the (candidate rank, k) work
+// items are dealt round-robin to the 64 W lanes, item i = rank * K + k.  A lane plays its playout in quanta of four plies that
+// share one Philox block, and when the playout ends it adds the outcome to the workgroup's LDS counters and starts its next
+// item from the root at the next quantum (refill): a wavefront waits for its busiest LANE's sum of playouts, not for the
+// longest playout of every round.  The counters go out once per board.  kinv = ceil(2^32 / K): item / K without a divide
+// (item < 54 * 4096 = 2^17.8, so the product's error stays below 1 / K).
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_playout(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                                    const int8_t *__restrict__ mask, int32_t *__restrict__ wins_out,
+                                                    int32_t *__restrict__ losses_out, int32_t *__restrict__ action_out,
+                                                    int32_t *__restrict__ plies_out, int64_t n, uint64_t seed, uint64_t env_base,
+                                                    uint32_t call, uint32_t K, uint64_t kinv, uint32_t max_plies)
+{
+    __shared__ uint32_t s_win[kActions], s_loss[kActions], s_plies;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        for (uint32_t j = tid; j < (uint32_t)kActions; j += 64u * W) s_win[j] = s_loss[j] = 0u;
+        if (tid == 0) s_plies = 0u;
+        const int v = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
+        const Planes root{(uint32_t)__ballot(v != 0), (uint32_t)__ballot(v < 0), (uint32_t)__ballot(v & 1)};
+        const int mover = to_move[b] != 0;
+        uint64_t cand = legal54(root, mover);
+        if (mask) cand &= (uint64_t)__ballot(lane < (uint32_t)kActions && mask[b * kActions + lane] != 0);
+        const uint32_t total = (uint32_t)__popcll(cand) * K;
+        __syncthreads();  // (counters zeroed)
+
+        uint32_t item = tid, t = 0, plies = 0;
+        Planes p = root;
+        int side = mover, a = 0;
+        uint64_t pid = 0;
+        bool fresh = true;
+        while (item < total) {
+            if (fresh) {  // refill: the next item from the root
+                const uint32_t r = (uint32_t)(((uint64_t)item * kinv) >> 32);
+                a = (int)kth_bit64(cand, r);
+                pid = playout_id(env_base + (uint64_t)b, (uint32_t)a, item - r * K);
+                p = root;
+                side = mover;
+                t = 0;
+                fresh = false;
+            }
+            const Draw4 d = draw_block(seed, pid, playout_ply_index(call, t), kStreamPlayout);  // (t % 4 == 0 here)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (!fresh) {
+                    const PlayoutEnd e = playout_end(playout_ply(p, side, t, a, d.w[u]), t, mover, max_plies);
+                    ++t;
+                    if (e.done) {
+                        plies += e.plies;
+                        if (e.outcome > 0) atomicAdd(&s_win[a], 1u);
+                        if (e.outcome < 0) atomicAdd(&s_loss[a], 1u);
+                        item += 64u * W;
+                        fresh = true;
+                    }
+                }
+            }
+        }
+        if (plies) atomicAdd(&s_plies, plies);
+        __syncthreads();
+        if (tid < 64u) {  // wavefront 0: the rows out and the decision (max of the order keys over the wavefront)
+            const bool in = lane < (uint32_t)kActions;
+            const int w = in ? (int)s_win[lane] : 0, l = in ? (int)s_loss[lane] : 0;
+            if (wins_out && in) wins_out[b * kActions + lane] = w;
+            if (losses_out && in) losses_out[b * kActions + lane] = l;
+            uint32_t key = in && ((cand >> lane) & 1ull) ? playout_key(w, l, (int)lane) : 0u;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint32_t other = (uint32_t)__shfl_xor((int)key, o);
+                key = other > key ? other : key;
+            }
+            if (lane == 0) {
+                if (action_out) action_out[b] = playout_action_of(key);
+                if (plies_out) plies_out[b] = (int32_t)s_plies;
+            }
+        }
+        __syncthreads();  // (before the next board zeroes the counters)
+    }
+}
+
+// Wavefronts per board of k_playout: one where the batch alone fills the chip (16 384 boards are 16 wavefronts per SIMD), more
+// for smaller batches -- but never so many that a lane gets fewer than about four playouts of a typical 30-candidate board, or
+// the wavefront's time is its unluckiest lane's single long playout.
+int playout_waves(int64_t n, int playouts)
+{
+    int w = 1;
+    while (w < 8 && n * (2 * w) <= 16384 && 64 * (2 * w) * 4 <= 30 * playouts) w *= 2;
+    return w;
+}
+
 // gbl_greedy: one decision per board.  Each lane owns a board (depth-1 walk, order-dependent replay,
 // fallback test), but the depth-2 evaluations -- one moved + legal54 + outcomes54 per (board,
 // candidate) pair, ~95 % of the work -- are pooled over the tile: the boards' candidate lists are
@@ -3045,6 +3135,38 @@ int gbl_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8_t *
     launch_greedy(greedy_shape(depth, n), n, (hipStream_t)stream, state, to_move, mask, nullptr, depth, chosen_out,
                   cand_mask_out, fallback_out, hist, action_out, seed, env_base, call, call_dev);
     GBL_LAUNCHED("gbl_greedy_act");
+}
+
+
+int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
+                       uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
+                       int32_t *action_out, int32_t *plies_out, int64_t n, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (playouts < 1 || playouts > 4096) return fail(GBL_ERR_ARG, "playouts must be in [1, 4096]");
+    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
+    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    if ((reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) | reinterpret_cast<uintptr_t>(action_out) |
+         reinterpret_cast<uintptr_t>(plies_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "wins_out / losses_out / action_out / plies_out must be 4-byte aligned");
+    const uint32_t K = (uint32_t)playouts;
+    const uint64_t kinv = ((1ull << 32) + K - 1) / K;
+    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    const hipStream_t s = (hipStream_t)stream;
+#define GBL_PLAYOUT(W)                                                                                                          \
+    hipLaunchKernelGGL((k_playout<W>), grid, dim3(64 * W), 0, s, state, to_move, mask, wins_out, losses_out, action_out, plies_out, \
+                       n, seed, env_base, call, K, kinv, (uint32_t)max_plies)
+    switch (playout_waves(n, playouts)) {
+    case 8: GBL_PLAYOUT(8); break;
+    case 4: GBL_PLAYOUT(4); break;
+    case 2: GBL_PLAYOUT(2); break;
+    default: GBL_PLAYOUT(1); break;
+    }
+#undef GBL_PLAYOUT
+    GBL_LAUNCHED("gbl_playout_values");
 }
 
 }  // extern "C"

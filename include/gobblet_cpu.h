@@ -88,6 +88,9 @@ int gbl_cpu_greedy_act(const int8_t *state, const int8_t *to_move, const int8_t 
 int gbl_cpu_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8_t *mask, int8_t *hist, int depth,
                           uint64_t seed, uint64_t env_base, uint32_t call, const uint32_t *call_dev, int32_t *action_out,
                           int32_t *chosen_out, int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *stream);
+int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
+                           uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
+                           int32_t *action_out, int32_t *plies_out, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

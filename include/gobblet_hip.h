@@ -203,7 +203,8 @@ int gbl_board_eval(int8_t *state, const int8_t *agent_index, const int32_t *acti
  * consecutive plies of a board; k = (r * nlegal) >> 32; the k-th legal action
  * in ascending order (-1 if the mask is empty).  env id = env_base + b.
  * Counter word 3 separates the consumers of one (seed, board) pair: stream 0 here
- * and in gbl_rollout, stream 1 for the fallback draw of gbl_greedy_act. */
+ * and in gbl_rollout, stream 1 for the fallback draw of gbl_greedy_act, stream 2
+ * for the playouts of gbl_playout_values. */
 int gbl_sample(const int8_t *mask, int32_t *actions, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply,
                void *stream);
 
@@ -267,6 +268,24 @@ int gbl_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *action
 int gbl_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8_t *mask, int8_t *hist, int depth,
                       uint64_t seed, uint64_t env_base, uint32_t call, const uint32_t *call_dev, int32_t *action_out,
                       int32_t *chosen_out, int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *stream);
+
+/* Flat Monte-Carlo playout values (no counterpart in the reference: a stronger, tunable opponent than the greedy policy, and
+ * the leaf evaluator / value target of a tree search).  For every candidate action a of board b -- mask[b] & legal mask of
+ * the agent to move (mask NULL: the legal mask) -- and every k < playouts:
+ *   1. the mover plays a; a non-zero check_for_winner() decides the playout (a win, or a loss by uncovering an opponent's line);
+ *   2. else, for t = 1 .. max_plies, the side to move plays the gbl_sample rule over its legal mask with the generator word of
+ *      (seed, pid, ply index (call << 8) | t, stream 2), pid = ((env_base + b) * 54 + a) * 65536 + k, until the first non-zero
+ *      winner; max_plies plies without one, or no legal move, leave the playout unfinished.
+ * Outputs (each may be NULL; non-candidate entries are 0):
+ *   wins_out   int32[n][54] : playouts of a won by the mover       losses_out int32[n][54] : ... lost by the mover
+ *   action_out int32[n]     : the candidate with the largest wins - losses, the lowest index on ties; -1 without a candidate
+ *   plies_out  int32[n]     : plies played over all of b's playouts, the root moves included
+ * pid does not depend on `playouts`, so the counts are non-decreasing in it, and a shard (env_base) of a batch gets its
+ * boards' results.  1 <= playouts <= 4096, 0 <= max_plies <= 255, call < 2^24, env_base + n <= 2^42; states must be
+ * contract states (gbl_validate).  Allocates nothing. */
+int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
+                       uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
+                       int32_t *action_out, int32_t *plies_out, int64_t n, void *stream);
 
 /* Trajectory collection (K plies per launch with EVERY ply materialised).  `plies` masked-random
  * plies with auto-reset in ONE launch; ply t (t = 0 .. plies-1) of board b leaves in element

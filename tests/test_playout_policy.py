@@ -1,0 +1,303 @@
+"""gbl_playout_values / MonteCarloGobbletPolicy on the host flavour (no GPU): against a Python restatement of the contract
+(include/gobblet_hip.h) built from the oracle's board functions and its masked-uniform sampler, plus properties, argument
+limits and an arena against the masked-random player."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+
+import gobblet_rl_amd as G
+from gobblet_rl_amd import _native as nat
+
+STREAM_PLAYOUT = 2
+E40 = (1 << 40) - 20
+
+
+def _sampler():
+    """gbo_sample_action_stream on a handle of our own (the oracle package declares only the stream-0 form)."""
+    h = C.CDLL(oracle.build())
+    f = h.gbo_sample_action_stream
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_int8), C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
+    return f
+
+
+_SAMPLE = None
+
+
+def sample_stream(mask, seed, env_id, ply, stream):
+    global _SAMPLE
+    if _SAMPLE is None:
+        _SAMPLE = _sampler()
+    m = np.ascontiguousarray(mask, dtype=np.int8)
+    return int(_SAMPLE(m.ctypes.data_as(C.POINTER(C.c_int8)), seed, env_id, ply, stream))
+
+
+def restate(state, to_move, mask, K, M, seed, env_base, call):
+    """The contract, one playout at a time, on the oracle."""
+    n = len(state)
+    wins = np.zeros((n, 54), np.int32)
+    losses = np.zeros((n, 54), np.int32)
+    plies = np.zeros(n, np.int32)
+    action = np.full(n, -1, np.int32)
+    for b in range(n):
+        mover = int(to_move[b] != 0)
+        cand = oracle.legal_mask(state[b], mover) != 0
+        if mask is not None:
+            cand &= mask[b] != 0
+        best = None
+        for a in np.flatnonzero(cand):
+            for k in range(K):
+                pid = ((env_base + b) * 54 + int(a)) * 65536 + k
+                s = oracle.play_turn(state[b], mover, int(a))
+                w, side, t = oracle.check_for_winner(s), 1 - mover, 0
+                plies[b] += 1
+                while w == 0 and t < M:
+                    t += 1
+                    act = sample_stream(oracle.legal_mask(s, side), seed, pid, (call << 8) | t, STREAM_PLAYOUT)
+                    if act < 0:
+                        break
+                    s = oracle.play_turn(s, side, act)
+                    plies[b] += 1
+                    side = 1 - side
+                    w = oracle.check_for_winner(s)
+                mine = w if mover == 0 else -w
+                wins[b, a] += mine > 0
+                losses[b, a] += mine < 0
+            score = int(wins[b, a]) - int(losses[b, a])
+            if best is None or score > best:
+                best, action[b] = score, int(a)
+    return wins, losses, action, plies
+
+
+def run(lib, state, to_move, mask, K, M, seed, env_base, call):
+    """gbl_playout_values on host arrays through `lib` (the host flavour's raw handle): (wins, losses, action, plies)."""
+    n = len(state)
+    wins = np.full((n, 54), -7, np.int32)
+    losses = np.full((n, 54), -7, np.int32)
+    action = np.full(n, -7, np.int32)
+    plies = np.full(n, -7, np.int32)
+    st, tm = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(to_move, np.int8)
+    mk = None if mask is None else np.ascontiguousarray(mask, np.int8)
+    rc = lib.gbl_cpu_playout_values(st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, K, M, seed, env_base,
+                                    call, wins.ctypes.data, losses.ctypes.data, action.ctypes.data, plies.ctypes.data, n, None)
+    assert rc == 0, lib.gbl_cpu_last_error()
+    return wins, losses, action, plies
+
+
+def random_midgames(n, seed, min_plies=2, max_plies=14):
+    """Masked-random games stopped at a random ply, on boards nobody has won yet (both movers)."""
+    rng = np.random.default_rng(seed)
+    out_s, out_t = [], []
+    while len(out_s) < n:
+        s, side = np.zeros(27, np.int8), 0
+        for _ in range(int(rng.integers(min_plies, max_plies + 1))):
+            a = int(rng.choice(np.flatnonzero(oracle.legal_mask(s, side))))
+            s2 = oracle.play_turn(s, side, a)
+            if oracle.check_for_winner(s2) != 0:
+                break
+            s, side = s2, 1 - side
+        out_s.append(s)
+        out_t.append(side)
+    return np.array(out_s, np.int8), np.array(out_t, np.int8)
+
+
+def play(seq):
+    """The board after a sequence of actions from the empty board, players alternating from player_1; (state, mover)."""
+    s = np.zeros(27, np.int8)
+    for i, a in enumerate(seq):
+        assert oracle.legal_mask(s, i & 1)[a], (seq, i)
+        s = oracle.play_turn(s, i & 1, a)
+    return s, len(seq) & 1
+
+
+WIN_SEQ, WIN_ACTION = [0, 3, 10, 13], 20             # player_1 holds squares 0 and 1; piece 3 to square 2 completes the row
+UNCOVER_SEQ, UNCOVER_ACTION = [0, 5, 23, 12, 10, 22], 26  # player_1's piece 3 covers player_2's line 3-4-5; moving it uncovers it
+
+
+@pytest.fixture(scope="module")
+def cpu():
+    L = nat.cpu_raw()
+    L.gbl_cpu_set_threads(4)
+    yield L
+    L.gbl_cpu_set_threads(0)
+
+
+@pytest.fixture(scope="module")
+def boards(golden_dir):
+    g = np.load(golden_dir + "/greedy.npz")
+    st, tm = [np.zeros(27, np.int8)], [0]
+    keep = np.flatnonzero(oracle.batch_winner(g["squares"]) == 0)[:4]
+    st += list(g["squares"][keep])
+    tm += list(g["to_move"][keep])
+    ms, mt = random_midgames(7, seed=3)
+    st += list(ms)
+    tm += list(mt)
+    st, tm = np.array(st, np.int8), np.array(tm, np.int8)
+    assert len(st) == 12 and set(tm.tolist()) == {0, 1}
+    return st, tm
+
+
+@pytest.mark.parametrize("K,M,call,env_base", [
+    (1, 0, 0, 0), (1, 255, 5, E40), (7, 1, 0, E40), (7, 30, 5, 0), (7, 255, 0, 0), (64, 30, 5, E40), (64, 255, 0, 0)])
+def test_host_flavour_equals_restatement(cpu, boards, K, M, call, env_base):
+    st, tm = boards
+    if K == 64:  # (the restatement walks every ply through ctypes: a third of the boards at the largest K)
+        st, tm = st[::3], tm[::3]
+    got = run(cpu, st, tm, None, K, M, 9, env_base, call)
+    exp = restate(st, tm, None, K, M, 9, env_base, call)
+    for name, g, e in zip(("wins", "losses", "action", "plies"), got, exp):
+        assert np.array_equal(g, e), name
+
+
+def test_host_flavour_equals_restatement_with_mask(cpu, boards):
+    st, tm = boards
+    mask = (np.random.default_rng(2).random((len(st), 54)) < 0.4).astype(np.int8)
+    mask[0] = 0  # a board without a candidate
+    got = run(cpu, st, tm, mask, 5, 40, 1, 3, 2)
+    exp = restate(st, tm, mask, 5, 40, 1, 3, 2)
+    for name, g, e in zip(("wins", "losses", "action", "plies"), got, exp):
+        assert np.array_equal(g, e), name
+    assert got[2][0] == -1 and got[3][0] == 0
+
+
+@pytest.fixture(scope="module")
+def many():
+    env = G.BatchedGobblet(300, "cpu", auto_reset=True, seed=11)
+    env.rollout(37)
+    st, tm = env.squares.numpy().copy(), env.to_move.numpy().copy()
+    assert (oracle.batch_winner(st) == 0).all()
+    return st, tm
+
+
+def test_properties(cpu, many):
+    st, tm = many
+    n, K = len(st), 16
+    legal = oracle.batch_legal_mask(st, tm) != 0
+    mask = (np.random.default_rng(8).random((n, 54)) < 0.5).astype(np.int8)
+    w, l, a, p = run(cpu, st, tm, mask, K, 64, 4, 100, 1)
+    cand = legal & (mask != 0)
+    assert ((w + l) <= K).all() and (w >= 0).all() and (l >= 0).all()
+    assert (w[~cand] == 0).all() and (l[~cand] == 0).all()
+    has = cand.any(1)
+    assert (a[~has] == -1).all() and cand[np.flatnonzero(has), a[has]].all()
+    score = np.where(cand, w - l, -10 ** 6)
+    assert np.array_equal(a[has], np.argmax(score, 1)[has])  # (argmax: the first maximum, the lowest index)
+    assert (p[has] >= cand.sum(1)[has] * K).all() and (p[has] <= cand.sum(1)[has] * K * 65).all()
+    # more playouts: the first K are the same games
+    w2, l2, _, p2 = run(cpu, st, tm, mask, 2 * K, 64, 4, 100, 1)
+    assert (w2 >= w).all() and (l2 >= l).all() and (p2 >= p).all()
+    # sharding over env_base changes nothing
+    h = n // 3
+    parts = [run(cpu, st[i:j], tm[i:j], mask[i:j], K, 64, 4, 100 + i, 1) for i, j in ((0, h), (h, n))]
+    for k in range(4):
+        assert np.array_equal(np.concatenate([q[k] for q in parts]), (w, l, a, p)[k])
+    # M = 0: every playout of an action is its root move alone
+    w0, l0, _, p0 = run(cpu, st, tm, None, K, 0, 4, 100, 1)
+    assert np.isin(w0, (0, K)).all() and np.isin(l0, (0, K)).all() and np.array_equal(p0, legal.sum(1) * K)
+    # another call index plays other games
+    w5, l5, _, _ = run(cpu, st, tm, mask, K, 64, 4, 100, 5)
+    assert not np.array_equal(w5, w)
+
+
+def test_decided_root_moves(cpu):
+    (sw, mw), (su, mu) = play(WIN_SEQ), play(UNCOVER_SEQ)
+    assert oracle.check_for_winner(oracle.play_turn(sw, mw, WIN_ACTION)) == 1
+    assert oracle.check_for_winner(oracle.play_turn(su, mu, UNCOVER_ACTION)) == -1
+    K = 50
+    w, l, a, _ = run(cpu, np.array([sw, su]), np.array([mw, mu]), None, K, 64, 0, 0, 0)
+    assert w[0, WIN_ACTION] == K and l[0, WIN_ACTION] == 0 and a[0] == WIN_ACTION
+    assert l[1, UNCOVER_ACTION] == K and w[1, UNCOVER_ACTION] == 0 and a[1] != UNCOVER_ACTION
+
+
+@pytest.mark.parametrize("flavour", ["cpu", "hip"])
+def test_argument_limits(flavour):
+    if flavour == "cpu":
+        L = nat.cpu_raw()
+        f, err = L.gbl_cpu_playout_values, L.gbl_cpu_last_error
+    else:  # (the device entry point checks its arguments before any HIP call: no GPU needed)
+        L = nat.lib()
+        f, err = L.gbl_playout_values, L.gbl_last_error
+    st, tm = np.zeros((2, 27), np.int8), np.zeros(2, np.int8)
+    out = np.zeros(2, np.int32)
+
+    def call(K=4, M=8, call=0, env_base=0, n=1):
+        return f(st.ctypes.data, tm.ctypes.data, None, K, M, 0, env_base, call, None, None, out.ctypes.data, None, n, None)
+
+    for kw, word in (({"K": 0}, b"playouts"), ({"K": 4097}, b"playouts"), ({"M": -1}, b"max_plies"), ({"M": 256}, b"max_plies"),
+                     ({"call": 1 << 24}, b"call"), ({"env_base": (1 << 42) - 1, "n": 2}, b"2^42"),
+                     ({"env_base": 1 << 43}, b"2^42"), ({"n": -1}, b"n < 0")):
+        assert call(**kw) == nat.ERR_ARG, kw
+        assert word in err(), (kw, err())
+    assert f(None, tm.ctypes.data, None, 4, 8, 0, 0, 0, None, None, None, None, 1, None) == nat.ERR_ARG and b"state" in err()
+    assert call(n=0) == 0
+    if flavour == "cpu":
+        assert call(K=4096, M=255, call=(1 << 24) - 1, env_base=(1 << 42) - 1, n=1) == 0 and out[0] >= 0
+    with pytest.raises(ValueError):
+        G.MonteCarloGobbletPolicy(playouts=0, device="cpu")
+    with pytest.raises(ValueError):
+        G.MonteCarloGobbletPolicy(max_plies=256, device="cpu")
+
+
+def arena(policy, n, seed, opponent="random", max_plies=64):
+    """MonteCarloGobbletPolicy as player_1 against the masked-random player (BatchedGobblet.sample_actions, keyed by `seed`) or
+    depth-2 greedy, over n games in lockstep (finished games stay frozen).  Returns the number of games player_1 won."""
+    env = G.BatchedGobblet(n, policy.device, auto_reset=False, seed=seed)
+    other = G.GreedyGobbletPolicy(depth=2, seed=seed, device=policy.device) if opponent == "greedy" else None
+    for t in range(max_plies):
+        if bool(env.done.all()):
+            break
+        if t % 2 == 0:
+            a = policy.compute_actions_from_state(env.squares, env.to_move, env.action_mask)
+        elif other is not None:
+            a = other.compute_actions_from_state(env.squares, env.to_move, env.action_mask)
+        else:
+            a = env.sample_actions()
+        env.step(torch.where(env.done != 0, torch.zeros_like(a), a))
+    return int((env.winner == 1).sum())
+
+
+# measured: MC(64, max_plies 64, seed 0) as player_1 wins 255 of 256 games against the masked-random player (seed 7); the
+# masked-random player itself wins about 0.54 of its games as player_1
+ARENA_CPU_WINS = 255
+
+
+def test_policy_on_cpu_beats_random(cpu):
+    pol = G.MonteCarloGobbletPolicy(playouts=64, max_plies=64, seed=0, device="cpu")
+    wins = arena(pol, 256, seed=7)
+    assert wins >= 0.9 * 256  # (the floor, with a margin below the record)
+    assert wins == ARENA_CPU_WINS
+
+
+def test_policy_surface_on_cpu(cpu, many):
+    st, tm = many
+    st, tm = torch.from_numpy(st[:40]), torch.from_numpy(tm[:40])
+    obs = torch.from_numpy(np.stack([oracle.observe(s, int(m), int(m))["observation"] for s, m in zip(st.numpy(), tm.numpy())]))
+    mask = torch.from_numpy(oracle.batch_legal_mask(st.numpy(), tm.numpy()))
+    a = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu").compute_actions(obs, mask)
+    b = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu").compute_actions_from_state(st, tm)
+    assert a.dtype == torch.int32 and torch.equal(a, b)
+    pol = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu")
+    v = pol.action_values(st, tm)
+    exp_w, exp_l, exp_a, exp_p = run(nat.cpu_raw(), st.numpy(), tm.numpy(), None, 8, 64, 3, 0, 0)
+    assert torch.equal(pol.last_action, b) and np.array_equal(pol.last_wins.numpy(), exp_w)
+    assert np.array_equal(pol.last_losses.numpy(), exp_l) and np.array_equal(pol.last_plies.numpy(), exp_p)
+    legal = mask.numpy() != 0
+    assert np.array_equal(v.numpy()[legal], ((exp_w - exp_l) / 8.0).astype(np.float32)[legal]) and np.isneginf(v.numpy()[~legal]).all()
+    # the call index moves on once per call
+    assert pol._calls == 1
+    pol.compute_actions_from_state(st, tm)
+    assert pol._calls == 2
+    w1, _, _, _ = run(nat.cpu_raw(), st.numpy(), tm.numpy(), None, 8, 64, 3, 0, 1)
+    assert np.array_equal(pol.last_wins.numpy(), w1)
+    # single-observation and rllib / tianshou shapes
+    one = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu")
+    assert int(one.compute_action(obs[0].numpy(), mask[0].numpy())) == int(b[0])
+    r = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu").compute_actions_rllib(
+        {"observation": obs.numpy().reshape(40, -1), "action_mask": mask.numpy()})
+    assert [int(x) for x in r] == b.tolist()
+    f = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu").forward({"obs": {"obs": obs.numpy(), "mask": mask.numpy()}})
+    assert f["act"].dtype == np.int64 and f["act"].tolist() == b.tolist()
