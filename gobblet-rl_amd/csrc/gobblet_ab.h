@@ -26,11 +26,6 @@
 #endif
 #ifndef GBL_FORCE_COLLECT_NT
 #define GBL_FORCE_COLLECT_NT -1
-#define GBL_KNOB_COLLECT_STREAM_OR_PLAIN(M, O, D) GBL_COLLECT_KN(M, O, D, true)
-#else
-#define GBL_KNOB_COLLECT_STREAM_OR_PLAIN(M, O, D)   \
-    if (nt) GBL_COLLECT_KN(M, O, D, true);          \
-    else GBL_COLLECT_KN(M, O, D, false)
 #endif
 #ifndef GBL_FORCE_COLLECT_PAIR
 #define GBL_FORCE_COLLECT_PAIR -1
@@ -72,20 +67,9 @@ inline int collect_cfg_override() { return -1; }
 #endif
 
 #ifdef GBL_AB_COLLECT_CFG
-#define GBL_KNOB_SMALL_FORMS                                                                                                     \
-    GBL_SMALL_CFG(1, 2, false) /* (the product's form for 8 193 ... 16 384 boards until k_collect3's scalars left its player) */ \
-    GBL_SMALL_CFG(1, 1, false)                                                                                                   \
-    GBL_SMALL_CFG(4, 1, false)                                                                                                   \
-    GBL_SMALL_CFG(1, 4, false)                                                                                                   \
-    GBL_SMALL_CFG(1, 4, true)                                                                                                    \
-    GBL_SMALL_CFG(1, 2, true)                                                                                                    \
-    GBL_SMALL_CFG(1, 1, true)                                                                                                    \
-    GBL_SMALL_CFG(2, 2, true)                                                                                                    \
-    GBL_SMALL_CFG(2, 1, true)                                                                                                    \
-    GBL_SMALL_CFG(4, 1, true)                                                                                                    \
-    GBL_SMALL_CFG(4, 0, true)                                                                                                    \
-    GBL_SMALL_CFG(2, 0, true)                                                                                                    \
-    GBL_SMALL_CFG(1, 0, true)
+// (role-kernel forms as collect_variant codes 100 LA + 10 KO + MERGE; 120: the product's form for 8 193 ... 16 384 boards until
+//  k_collect3's scalars left its player)
+#define GBL_KNOB_SMALL_FORMS , 120, 110, 410, 140, 141, 121, 111, 221, 211, 411, 401, 201, 101
 #define GBL_KNOB_EXTRA_ENTRY_POINTS                                                                         \
     extern "C" int gbl_ab_collect_cfg(int cfg) /* (not part of the ABI: -1 = the library's own choice) */  \
     {                                                                                                       \

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include <stdlib.h>
 #include <string.h>
 
@@ -169,6 +170,19 @@ __device__ __forceinline__ bool lane_setup(Lane &L, int64_t n, int64_t ntiles)
     L.valid = L.lane < L.rows;
     L.b = L.tile * kTile + L.lane;
     return true;
+}
+
+// A wavefront's tallies of finished games and of each player's wins (ballot + popcount: wave-uniform) into the counters: one stripe
+// (its own 128-byte line) per tile mod GBL_COUNTER_STRIPES, so that the device-scope atomics of concurrently finishing waves go to
+// different lines.  (One lane calls it.)
+__device__ __forceinline__ void tally_flush(int64_t *counters, int64_t stripe, int boards, uint32_t plies, uint32_t games, uint32_t w1,
+                                            uint32_t w2)
+{
+    unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) + (size_t)(stripe % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
+    atomicAdd(c + 0, (unsigned long long)boards * plies);
+    if (games) atomicAdd(c + 1, (unsigned long long)games);
+    if (w1) atomicAdd(c + 2, (unsigned long long)w1);
+    if (w2) atomicAdd(c + 3, (unsigned long long)w2);
 }
 
 template <typename Between = NoWork>
@@ -603,8 +617,8 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_rollout(int8_t *__restrict_
             reinterpret_cast<uint16_t *>(reward_out)[L.b] = (uint16_t)((y.r0 & 0xFF) | ((y.r1 & 0xFF) << 8));
         if (turn) turn[L.b] = treset ? tcount : turn[L.b] + tcount;
     }
-    // Tallies: one stripe (its own 128-byte line) per tile mod GBL_COUNTER_STRIPES, so that the
-    // device-scope atomics of concurrently finishing waves go to different lines.
+    // Tallies (tally_flush spelled out: through the helper this kernel's code changes -- the scheduler orders its zero-initialisations
+    // differently)
     if (counters && L.lane == 0) {
         unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) +
                                 (size_t)(L.tile % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
@@ -710,14 +724,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GBL_KNOB_COL
         done[L.b] = (int8_t)dn;
         if (turn) turn[L.b] = treset ? tcount : turn[L.b] + tcount;
     }
-    if (counters && L.lane == 0) {
-        unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) +
-                                (size_t)(L.tile % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
-        atomicAdd(c + 0, (unsigned long long)L.rows * plies);
-        if (games) atomicAdd(c + 1, (unsigned long long)games);
-        if (w1) atomicAdd(c + 2, (unsigned long long)w1);
-        if (w2) atomicAdd(c + 3, (unsigned long long)w2);
-    }
+    if (counters && L.lane == 0) tally_flush(counters, L.tile, L.rows, plies, games, w1, w2);
     GBL_STAMP(1); GBL_STAMP(2); GBL_STAMP(3); GBL_STAMP(4);
     GBL_STAMP_DRAIN(5);
     GBL_STAMP_FLUSH(L.tile);
@@ -848,14 +855,7 @@ __global__ __launch_bounds__(128) void k_collect2(int8_t *__restrict__ state, in
         done[L.b] = (int8_t)dn;
         if (turn) turn[L.b] = treset ? tcount : turn[L.b] + tcount;
     }
-    if (counters && L.lane == 0) {
-        unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) +
-                                (size_t)(L.tile % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
-        atomicAdd(c + 0, (unsigned long long)L.rows * plies);
-        if (games) atomicAdd(c + 1, (unsigned long long)games);
-        if (w1) atomicAdd(c + 2, (unsigned long long)w1);
-        if (w2) atomicAdd(c + 3, (unsigned long long)w2);
-    }
+    if (counters && L.lane == 0) tally_flush(counters, L.tile, L.rows, plies, games, w1, w2);
 }
 
 // gbl_collect for batches that do NOT fill the chip: ROLE wavefronts that share NOTHING, and the game played REDUNDANTLY wherever
@@ -1111,14 +1111,7 @@ __device__ __forceinline__ void small_role(const SmallArgs &A, uint32_t *img, ui
             A.done[b] = (int8_t)dn;
             if (A.turn) A.turn[b] = treset ? tcount : A.turn[b] + tcount;
         }
-        if (A.counters && lane == 0) {
-            unsigned long long *c = reinterpret_cast<unsigned long long *>(A.counters) +
-                                    (size_t)((sub >> SH) % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
-            atomicAdd(c + 0, (unsigned long long)rows * plies);
-            if (games) atomicAdd(c + 1, (unsigned long long)games);
-            if (w1) atomicAdd(c + 2, (unsigned long long)w1);
-            if (w2) atomicAdd(c + 3, (unsigned long long)w2);
-        }
+        if (A.counters && lane == 0) tally_flush(A.counters, sub >> SH, rows, plies, games, w1, w2);
     }
 }
 
@@ -1303,14 +1296,7 @@ __global__ __launch_bounds__(64 * (1 + (WITH_MASK ? 1 : 0) + (WITH_OBS ? 1 : 0))
         done[b] = (int8_t)dn;
         if (turn) turn[b] = treset ? tcount : turn[b] + tcount;
     }
-    if (counters && lane == 0) {
-        unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) +
-                                (size_t)(tile % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
-        atomicAdd(c + 0, (unsigned long long)rows * plies);
-        if (games) atomicAdd(c + 1, (unsigned long long)games);
-        if (w1) atomicAdd(c + 2, (unsigned long long)w1);
-        if (w2) atomicAdd(c + 3, (unsigned long long)w2);
-    }
+    if (counters && lane == 0) tally_flush(counters, tile, rows, plies, games, w1, w2);
 }
 
 // wavefronts of a workgroup of the role kernel: the scalars wavefront, the mask wavefront unless merged, KO observation wavefronts
@@ -1474,14 +1460,7 @@ __global__ __launch_bounds__(64 * (WITH_OBS ? 4 : 2)) void k_collect5(
         }
         if (plies) sub_store<kActions, kPolicy, GB>(dst, vm, lane, mbytes & ~15);
         if (valid && j == 0 && turn) turn[b] = treset ? tcount : turn[b] + tcount;
-        if (counters && lane == 0) {
-            unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) +
-                                    (size_t)((group >> 1) % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
-            atomicAdd(c + 0, (unsigned long long)rows * plies);
-            if (games) atomicAdd(c + 1, (unsigned long long)games);
-            if (w1) atomicAdd(c + 2, (unsigned long long)w1);
-            if (w2) atomicAdd(c + 3, (unsigned long long)w2);
-        }
+        if (counters && lane == 0) tally_flush(counters, group >> 1, rows, plies, games, w1, w2);
         return;
     }
     if (role >= 2) {
@@ -2377,47 +2356,68 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 &&
             hp[2] = (uint16_t)((hp1 >> 8) & 0xFFFFu);
         }
     }
-    if (counters && L.lane == 0) {
-        unsigned long long *c = reinterpret_cast<unsigned long long *>(counters) +
-                                (size_t)(L.tile % GBL_COUNTER_STRIPES) * GBL_COUNTER_STRIDE;
-        atomicAdd(c + 0, (unsigned long long)L.rows * plies);
-        if (games) atomicAdd(c + 1, (unsigned long long)games);
-        if (w1) atomicAdd(c + 2, (unsigned long long)w1);
-        if (w2) atomicAdd(c + 3, (unsigned long long)w2);
-    }
+    if (counters && L.lane == 0) tally_flush(counters, L.tile, L.rows, plies, games, w1, w2);
 }
 
-// k_collect_small for a checked call (see gbl_collect_from); cfg = 100 LA + 10 KO + MERGE (collect_variant)
-// (the product build instantiates the forms collect_variant() can return; an experiment build a whole menu: gobblet_ab.h)
-bool launch_small(int cfg, int8_t *state, int8_t *to_move, int8_t *done, const int32_t *first_actions, int8_t *first_status, int32_t *actions_t, int8_t *winner_t,
-                  int8_t *reward_t, int8_t *done_t, int8_t *to_move_t, int8_t *mask_t, int8_t *obs_t, int64_t n, int64_t ply_stride,
-                  int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
-                  int illegal_mode, int64_t *counters, int32_t *turn, hipStream_t s)
+// Run-time flags as template arguments: f(std::bool_constant<b>...).  Every combination of the flags is instantiated: a caller keeps
+// out with `if constexpr` what it never launches.
+template <typename F>
+void with_flags(F &&f)
 {
-    const int la = cfg / 100;
-    const int64_t gb = kTile / la, ngroups = (n + gb - 1) / gb;
-#define GBL_SMALL_K(M, O, D, LA, KO, MG)                                                                                        \
-    hipLaunchKernelGGL((k_collect_small<M, O, D, LA, KO, MG>), dim3((uint32_t)ngroups), dim3(64 * small_waves<M, O, KO, MG>()), 0, s, \
-                       state, to_move, n, ngroups, seed, env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, actions_t,      \
-                       winner_t, reward_t, done_t, to_move_t, mask_t, obs_t, illegal_mode, counters, turn, first_actions, first_status)
-#define GBL_SMALL_D(M, O, LA, KO, MG)                           \
-    if (ply_dev) { GBL_SMALL_K(M, O, true, LA, KO, MG); }       \
-    else { GBL_SMALL_K(M, O, false, LA, KO, MG); }
-#define GBL_SMALL_CFG(LA, KO, MG)                                                                              \
-    if (cfg == 100 * LA + 10 * KO + (MG ? 1 : 0)) {                                                            \
-        if (mask_t && obs_t) { GBL_SMALL_D(true, true, LA, KO, MG); }                                          \
-        else if (mask_t) { GBL_SMALL_D(true, false, LA, KO, MG); }                                             \
-        else if (obs_t) { GBL_SMALL_D(false, true, LA, KO, MG); }                                              \
-        else { GBL_SMALL_D(false, false, LA, KO, MG); }                                                        \
-        return true;                                                                                           \
-    }
-    GBL_SMALL_CFG(2, 2, false)
-    GBL_SMALL_CFG(2, 1, false)
-    GBL_KNOB_SMALL_FORMS
-#undef GBL_SMALL_CFG
-#undef GBL_SMALL_D
-#undef GBL_SMALL_K
-    return false;
+    f();
+}
+template <typename F, typename... B>
+void with_flags(F &&f, bool b, B... rest)
+{
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// The arguments of the five collect kernels (k_collect, k_collect2, k_collect3, k_collect5, k_collect_small), in their order -- the
+// first 16 dwords arrive preloaded in SGPRs (see _native.py) -- except the count of tiles or groups, which is the launch's
+struct CollectArgs {
+    int8_t *state, *to_move;
+    int64_t n;
+    uint64_t seed, env_base;
+    const uint32_t *ply_dev;
+    uint32_t ply0, plies;
+    int8_t *done;
+    int64_t ply_stride, tile_stride;
+    int32_t *actions_t;
+    int8_t *winner_t, *reward_t, *done_t, *to_move_t, *mask_t, *obs_t;
+    int illegal_mode;
+    int64_t *counters;
+    int32_t *turn;
+    const int32_t *first_actions;
+    int8_t *first_status;
+};
+
+template <typename Kernel>
+void launch_collect(Kernel kernel, int64_t ngroups, uint32_t grid, int threads, hipStream_t s, const CollectArgs &a)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, a.state, a.to_move, a.n, ngroups, a.seed, a.env_base, a.ply_dev, a.ply0,
+                       a.plies, a.done, a.ply_stride, a.tile_stride, a.actions_t, a.winner_t, a.reward_t, a.done_t, a.to_move_t, a.mask_t,
+                       a.obs_t, a.illegal_mode, a.counters, a.turn, a.first_actions, a.first_status);
+}
+
+// The forms of the role kernel a build carries, as collect_variant's codes 100 LA + 10 KO + MERGE: the product's are the ones
+// collect_variant() can return; an experiment build carries a whole menu (gobblet_ab.h)
+using SmallForms = std::integer_sequence<int, 220, 210 GBL_KNOB_SMALL_FORMS>;
+
+template <int LA, int KO, bool MERGE>
+void launch_small_form(const CollectArgs &a, hipStream_t s)
+{
+    const int64_t gb = kTile / LA, ngroups = (a.n + gb - 1) / gb;
+    with_flags([&](auto M, auto O, auto D) {
+        launch_collect(k_collect_small<M, O, D, LA, KO, MERGE>, ngroups, (uint32_t)ngroups, 64 * small_waves<M, O, KO, MERGE>(), s, a);
+    }, a.mask_t != nullptr, a.obs_t != nullptr, a.ply_dev != nullptr);
+}
+
+// k_collect_small for a checked call (see gbl_collect_from) in form cfg; false: this build has no such form
+template <int... CFG>
+bool launch_small(std::integer_sequence<int, CFG...>, int cfg, const CollectArgs &a, hipStream_t s)
+{
+    return ((cfg == CFG && (launch_small_form<CFG / 100, (CFG / 10) % 10, (CFG % 10) != 0>(a, s), true)) || ...);
 }
 
 int greedy_shape(int depth, int64_t n);  // (defined with the greedy entry points below)
@@ -2447,6 +2447,30 @@ int policy_shape(int depth, int64_t n);
         if (e_ != hipSuccess) return hip_fail(e_, name);     \
         return GBL_OK;                                       \
     } while (0)
+
+// The trajectory arguments of gbl_collect_from_ex and gbl_collect_policy.  words: the addresses of the 4-byte element arrays OR-ed
+// together (a null one adds nothing), words_msg: the error that names them.
+static int check_traj(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride, const int8_t *state, const int8_t *mask_traj,
+                      const int8_t *obs_traj, const int8_t *reward_traj, uintptr_t words, const char *words_msg, const int32_t *turn,
+                      const int64_t *counters)
+{
+    {   // the (ply, tile) cells of 64 boards must start 16-byte aligned and must not overlap
+        const int64_t tiles = (n + kTile - 1) / kTile;
+        const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
+        const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
+        const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
+        if (!aligned || !(time_major || tile_major))
+            return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    }
+    GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(obs_traj, "obs_traj");
+    if (reward_traj && (reinterpret_cast<uintptr_t>(reward_traj) & 1u))
+        return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
+    if (words & 3u) return fail(GBL_ERR_ALIGN, words_msg);
+    if (turn && (reinterpret_cast<uintptr_t>(turn) & 3u)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
+    if (counters && (reinterpret_cast<uintptr_t>(counters) & 127u))
+        return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
+    return GBL_OK;
+}
 
 extern "C" {
 
@@ -2660,22 +2684,10 @@ int gbl_step_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *act
     const int nt = nt_policy(n);
     const bool ext = actions_out || done_out || to_move_out || status_out || next_actions_out;
     const StepExt X{actions_out, done_out, to_move_out, status_out, next_actions_out, seed, env_base, ply_dev, ply};
-#define GBL_STEP_I(M, O, NT, I)                                                                                          \
-    hipLaunchKernelGGL((k_step<M, O, NT, I>), dim3(g.grid), dim3(64 * kStepWaves), 0, s, state, to_move, done, actions, \
-                       n, g.ntiles, illegal_mode, auto_reset, winner_out, reward_out, mask_out, obs_out, turn, X)
-#define GBL_STEP_NT(M, O, NT)                                   \
-    if (ext) GBL_STEP_I(M, O, NT, true);                        \
-    else GBL_STEP_I(M, O, NT, false)
-#define GBL_STEP(M, O)                                          \
-    if (nt == 3) { GBL_STEP_NT(M, O, 3); }                      \
-    else { GBL_STEP_NT(M, O, 1); }
-    if (mask_out && obs_out) GBL_STEP(true, true)
-    else if (mask_out) GBL_STEP(true, false)
-    else if (obs_out) GBL_STEP(false, true)
-    else GBL_STEP(false, false)
-#undef GBL_STEP
-#undef GBL_STEP_NT
-#undef GBL_STEP_I
+    with_flags([&](auto M, auto O, auto NT3, auto EXT) {
+        hipLaunchKernelGGL((k_step<M, O, NT3 ? 3 : 1, EXT>), dim3(g.grid), dim3(64 * kStepWaves), 0, s, state, to_move, done, actions, n,
+                           g.ntiles, illegal_mode, auto_reset, winner_out, reward_out, mask_out, obs_out, turn, X);
+    }, mask_out != nullptr, obs_out != nullptr, nt == 3, ext);
     GBL_LAUNCHED("gbl_step");
 }
 
@@ -2733,27 +2745,11 @@ int gbl_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *action
     Geometry g = geometry(n, kStepWaves);
     hipStream_t s = (hipStream_t)stream;
     const int nt = nt_policy(n);
-#define GBL_ROLL_K(M, O, NT, D, ONE)                                                                                \
-    hipLaunchKernelGGL((k_rollout<M, O, NT, D, ONE>), dim3(g.grid), dim3(64 * kStepWaves), 0, s, state, to_move, n, \
-                       g.ntiles, seed, env_base, ply_dev, ply0, plies, done, actions_out, winner_out, reward_out,   \
-                       mask_out, obs_out, illegal_mode, counters, turn)
-#define GBL_ROLL_D(M, O, NT, D)                                 \
-    if (plies == 1) GBL_ROLL_K(M, O, NT, D, true);              \
-    else GBL_ROLL_K(M, O, NT, D, false)
-#define GBL_ROLL_NT(M, O, NT)                                   \
-    if (ply_dev) { GBL_ROLL_D(M, O, NT, true); }                \
-    else { GBL_ROLL_D(M, O, NT, false); }
-#define GBL_ROLL(M, O)                                          \
-    if (nt == 3) { GBL_ROLL_NT(M, O, 3); }                      \
-    else { GBL_ROLL_NT(M, O, 1); }
-    if (mask_out && obs_out) GBL_ROLL(true, true)
-    else if (mask_out) GBL_ROLL(true, false)
-    else if (obs_out) GBL_ROLL(false, true)
-    else GBL_ROLL(false, false)
-#undef GBL_ROLL
-#undef GBL_ROLL_NT
-#undef GBL_ROLL_D
-#undef GBL_ROLL_K
+    with_flags([&](auto M, auto O, auto NT3, auto D, auto ONE) {
+        hipLaunchKernelGGL((k_rollout<M, O, NT3 ? 3 : 1, D, ONE>), dim3(g.grid), dim3(64 * kStepWaves), 0, s, state, to_move, n, g.ntiles,
+                           seed, env_base, ply_dev, ply0, plies, done, actions_out, winner_out, reward_out, mask_out, obs_out, illegal_mode,
+                           counters, turn);
+    }, mask_out != nullptr, obs_out != nullptr, nt == 3, ply_dev != nullptr, plies == 1);
     GBL_LAUNCHED("gbl_rollout");  // (also gbl_rollout_at)
 }
 
@@ -2792,95 +2788,37 @@ int gbl_collect_from_ex(int8_t *state, int8_t *to_move, int8_t *done, const int3
     if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
         return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
     if (plies == 0) return GBL_OK;
-    {   // the (ply, tile) cells of 64 boards must start 16-byte aligned and must not overlap
-        const int64_t tiles = (n + kTile - 1) / kTile;
-        const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
-        const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
-        const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
-        if (!aligned || !(time_major || tile_major))
-            return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
-    }
-    GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(obs_traj, "obs_traj");
-    if (reward_traj && (reinterpret_cast<uintptr_t>(reward_traj) & 1u))
-        return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
-    if (actions_traj && (reinterpret_cast<uintptr_t>(actions_traj) & 3u))
-        return fail(GBL_ERR_ALIGN, "actions_traj must be 4-byte aligned");
-    if (turn && (reinterpret_cast<uintptr_t>(turn) & 3u)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
-    if (counters && (reinterpret_cast<uintptr_t>(counters) & 127u))
-        return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
-    Geometry g = geometry(n);
-    hipStream_t s = (hipStream_t)stream;
+    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
+                                 reinterpret_cast<uintptr_t>(actions_traj), "actions_traj must be 4-byte aligned", turn, counters))
+        return e;
+    const Geometry g = geometry(n);
+    const hipStream_t s = (hipStream_t)stream;
     const int variant = collect_variant(n, plies, mask_traj != nullptr, obs_traj != nullptr);
-    const bool pair = variant == GBL_COLLECT_PAIR;
-    [[maybe_unused]] const bool nt = variant != GBL_COLLECT_CACHED;
-    if (variant == GBL_COLLECT_TRIO) {
-#define GBL_TRIO_KH(M, O, D, H)                                                                                                   \
-    hipLaunchKernelGGL((k_collect3<M, O, D, H>), dim3((uint32_t)g.ntiles), dim3(64 * (1 + (M ? 1 : 0) + (O ? 1 : 0))), 0, s, state,   \
-                       to_move, n, g.ntiles, seed, env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, actions_traj,   \
-                       winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, illegal_mode, counters, turn,      \
-                       first_actions, first_status)
-#define GBL_TRIO_K(M, O, D)                                     \
-    if (g.ntiles <= kTrioHandMaxTiles) { GBL_TRIO_KH(M, O, D, true); } \
-    else { GBL_TRIO_KH(M, O, D, false); }
-#define GBL_TRIO(M, O)                                          \
-    if (ply_dev) { GBL_TRIO_K(M, O, true); }                    \
-    else { GBL_TRIO_K(M, O, false); }
-        if (mask_traj && obs_traj) { GBL_TRIO(true, true); }
-        else if (mask_traj) { GBL_TRIO(true, false); }
-        else { GBL_TRIO(false, true); }
-#undef GBL_TRIO
-#undef GBL_TRIO_K
-#undef GBL_TRIO_KH
-        GBL_LAUNCHED("gbl_collect");
-    }
-    if (variant == GBL_COLLECT_GROUP32) {
-        const int64_t ngroups = (n + kGroupBoards - 1) / kGroupBoards;
-#define GBL_G32_K(O, D)                                                                                                            \
-    hipLaunchKernelGGL((k_collect5<O, D>), dim3((uint32_t)ngroups), dim3(64 * (O ? 4 : 2)), 0, s, state, to_move, n, ngroups, seed,    \
-                       env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, actions_traj, winner_traj, reward_traj,      \
-                       done_traj, to_move_traj, mask_traj, obs_traj, illegal_mode, counters, turn, first_actions, first_status)
-        if (obs_traj) {
-            if (ply_dev) { GBL_G32_K(true, true); }
-            else { GBL_G32_K(true, false); }
-        } else {
-            if (ply_dev) { GBL_G32_K(false, true); }
-            else { GBL_G32_K(false, false); }
-        }
-#undef GBL_G32_K
-        GBL_LAUNCHED("gbl_collect");
-    }
+    const CollectArgs a{state,       to_move,     n,         seed,         env_base,  ply_dev,  ply0,     plies,
+                        done,        ply_stride,  tile_stride, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj,
+                        mask_traj,   obs_traj,    illegal_mode, counters,    turn,      first_actions, first_status};
     if (GBL_COLLECT_IS_ROLES(variant)) {
-        if (!launch_small(variant - GBL_COLLECT_ROLES(0, 0, 0), state, to_move, done, first_actions, first_status, actions_traj, winner_traj, reward_traj,
-                          done_traj, to_move_traj, mask_traj, obs_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies,
-                          illegal_mode, counters, turn, s))
+        if (!launch_small(SmallForms{}, variant - GBL_COLLECT_ROLES(0, 0, 0), a, s))
             return fail(GBL_ERR_ARG, "gbl_collect: this build has no such form of the role kernel");
         GBL_LAUNCHED("gbl_collect");
     }
-    // (the plain-store instantiation of k_collect exists in experiment builds only)
-#define GBL_COLLECT_K(M, O, D)                                  \
-    if (pair) GBL_COLLECT_K2(M, O, D);                          \
-    else GBL_KNOB_COLLECT_STREAM_OR_PLAIN(M, O, D)
-#define GBL_COLLECT_K2(M, O, D)                                                                                         \
-    hipLaunchKernelGGL((k_collect2<M, O, D>), dim3((uint32_t)g.ntiles), dim3(128), 0, s, state, to_move, n, g.ntiles, seed, \
-                       env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, actions_traj, winner_traj,        \
-                       reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, illegal_mode, counters, turn,         \
-                       first_actions, first_status)
-#define GBL_COLLECT_KN(M, O, D, N)                                                                                      \
-    hipLaunchKernelGGL((k_collect<M, O, D, N>), dim3(g.grid), dim3(64), 0, s, state, to_move, n, g.ntiles, seed, env_base, \
-                       ply_dev, ply0, plies, done, ply_stride, tile_stride, actions_traj, winner_traj, reward_traj,     \
-                       done_traj,                                                                                      \
-                       to_move_traj, mask_traj, obs_traj, illegal_mode, counters, turn, first_actions, first_status)
-#define GBL_COLLECT(M, O)                                       \
-    if (ply_dev) { GBL_COLLECT_K(M, O, true); }                 \
-    else { GBL_COLLECT_K(M, O, false); }
-    if (mask_traj && obs_traj) { GBL_COLLECT(true, true); }
-    else if (mask_traj) { GBL_COLLECT(true, false); }
-    else if (obs_traj) { GBL_COLLECT(false, true); }
-    else { GBL_COLLECT(false, false); }
-#undef GBL_COLLECT
-#undef GBL_COLLECT_K
-#undef GBL_COLLECT_KN
-#undef GBL_COLLECT_K2
+    with_flags([&](auto M, auto O, auto D) {
+        if (variant == GBL_COLLECT_TRIO) {
+            if constexpr (M || O) {  // (collect_variant sends no launch without rows to k_collect3)
+                with_flags([&](auto H) { launch_collect(k_collect3<M, O, D, H>, g.ntiles, (uint32_t)g.ntiles, 64 * (1 + M + O), s, a); },
+                           g.ntiles <= kTrioHandMaxTiles);
+            }
+        } else if (variant == GBL_COLLECT_GROUP32) {
+            const int64_t ngroups = (n + kGroupBoards - 1) / kGroupBoards;
+            launch_collect(k_collect5<O, D>, ngroups, (uint32_t)ngroups, 64 * (O ? 4 : 2), s, a);
+        } else if (variant == GBL_COLLECT_PAIR) {
+            launch_collect(k_collect2<M, O, D>, g.ntiles, (uint32_t)g.ntiles, 128, s, a);
+        } else if constexpr (knob::kForcedCollectNt < 0) {
+            launch_collect(k_collect<M, O, D, true>, g.ntiles, g.grid, 64, s, a);
+        } else {  // (the plain-store instantiation of k_collect exists in experiment builds only)
+            with_flags([&](auto NT) { launch_collect(k_collect<M, O, D, NT>, g.ntiles, g.grid, 64, s, a); }, variant != GBL_COLLECT_CACHED);
+        }
+    }, mask_traj != nullptr, obs_traj != nullptr, ply_dev != nullptr);
     GBL_LAUNCHED("gbl_collect");
 }
 
@@ -2900,23 +2838,12 @@ int gbl_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *his
     if (opening_plies < 0) return fail(GBL_ERR_ARG, "opening_plies < 0");
     if (opening_plies > 0 && !turn) return fail(GBL_ERR_ARG, "opening_plies > 0 needs the per-board turn counter (turn must not be NULL)");
     if (plies == 0) return GBL_OK;
-    {   // the (ply, tile) cells of 64 boards must start 16-byte aligned and must not overlap (as gbl_collect)
-        const int64_t tiles = (n + kTile - 1) / kTile;
-        const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
-        const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
-        const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
-        if (!aligned || !(time_major || tile_major))
-            return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
-    }
-    GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(obs_traj, "obs_traj"); GBL_ALIGNED(cand_traj, "cand_traj");
+    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
+                                 reinterpret_cast<uintptr_t>(actions_traj) | reinterpret_cast<uintptr_t>(chosen_traj),
+                                 "actions_traj / chosen_traj must be 4-byte aligned", turn, counters))
+        return e;
+    GBL_ALIGNED(cand_traj, "cand_traj");
     if (hist && (reinterpret_cast<uintptr_t>(hist) & 1u)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
-    if (reward_traj && (reinterpret_cast<uintptr_t>(reward_traj) & 1u))
-        return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
-    if ((actions_traj && (reinterpret_cast<uintptr_t>(actions_traj) & 3u)) || (chosen_traj && (reinterpret_cast<uintptr_t>(chosen_traj) & 3u)))
-        return fail(GBL_ERR_ALIGN, "actions_traj / chosen_traj must be 4-byte aligned");
-    if (turn && (reinterpret_cast<uintptr_t>(turn) & 3u)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
-    if (counters && (reinterpret_cast<uintptr_t>(counters) & 127u))
-        return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int depth = policy0 > policy1 ? policy0 : policy1;
     const int shape = policy_shape(depth, n);

@@ -34,9 +34,9 @@ inline int collect_cfg_override() { return -1; }  // a form picked at run time (
 // occupancy pins (see k_collect / k_collect_policy)
 #define GBL_KNOB_COLLECT_WAVES_PER_EU 4, 4
 #define GBL_KNOB_CP_WAVES_PER_EU 4
-// template instantiations only experiment builds carry: more forms of the role kernel, k_collect with plain stores, more block shapes
+// template instantiations only experiment builds carry: more forms of the role kernel (codes appended to SmallForms), more block shapes
+// (k_collect with plain stores: kForcedCollectNt >= 0)
 #define GBL_KNOB_SMALL_FORMS
-#define GBL_KNOB_COLLECT_STREAM_OR_PLAIN(M, O, D) GBL_COLLECT_KN(M, O, D, true)
 #define GBL_KNOB_CP_SHAPES
 #define GBL_KNOB_GREEDY_SHAPES
 #define GBL_KNOB_EXTRA_ENTRY_POINTS
