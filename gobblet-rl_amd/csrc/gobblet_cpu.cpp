@@ -677,6 +677,66 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
     return GBL_OK;
 }
 
+int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
+                        int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
+                        int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (iterations < 1 || iterations > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
+    if (playouts < 1 || playouts > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
+    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
+    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    const uint32_t P = (uint32_t)playouts;
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
+        std::vector<TreeNode> nodes((size_t)iterations + 1);
+        for (int64_t b = b0; b < b1; ++b) {
+            uint32_t r[7];
+            load_row(state, b, r);
+            const Planes root = make_planes(r);
+            const int mover = to_move[b] != 0;
+            const uint64_t g = env_base + (uint64_t)b;
+            uint64_t cand = legal54(root, mover);
+            if (mask) cand &= read_mask(mask + b * kActions);
+            nodes[0] = TreeNode{};
+            uint32_t count = 1, plies = 0;
+            for (uint32_t i = 0; cand && i < (uint32_t)iterations; ++i) {
+                TreeLeaf s = tree_select(nodes.data(), root, mover, cand, P, (uint32_t)explore);
+                const uint32_t parent = s.node;
+                uint32_t term = tree_term(nodes[s.node]), a = 0;
+                const bool grow = s.untried != 0;
+                if (grow) a = tree_expand_move(s.p, s.side, s.untried, draw32(seed, tree_pid(g, i, 0), playout_ply_index(call, 0), kStreamTree), term);
+                uint32_t wl = tree_decided(term, P);
+                for (uint32_t j = 0; term == kTreeOpen && j < P; ++j) {
+                    const PlayoutEnd e = tree_playout(s.p, s.side, seed, tree_pid(g, i, j), call, (uint32_t)max_plies);
+                    wl += e.outcome > 0 ? 1u : (e.outcome < 0 ? 1u << 16 : 0u);
+                    plies += e.plies;
+                }
+                if (grow) tree_link(nodes.data(), s.node = count++, parent, a, term);
+                tree_backup(nodes.data(), s.node, wl & 0xFFFFu, wl >> 16);
+            }
+            int32_t visits[kActions] = {}, wins[kActions] = {}, losses[kActions] = {};
+            uint64_t best = 0;
+            for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
+                const TreeNode &k = nodes[c];
+                const uint32_t a = tree_action(k);
+                visits[a] = k.n; wins[a] = (int32_t)tree_wins(k); losses[a] = (int32_t)tree_losses(k);
+                best = std::max(best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
+            }
+            if (visits_out) memcpy(visits_out + b * kActions, visits, sizeof visits);
+            if (wins_out) memcpy(wins_out + b * kActions, wins, sizeof wins);
+            if (losses_out) memcpy(losses_out + b * kActions, losses, sizeof losses);
+            if (action_out) action_out[b] = tree_action_of(best);
+            if (nodes_out) nodes_out[b] = (int32_t)count;
+            if (plies_out) plies_out[b] = (int32_t)plies;
+        }
+    }, 1);
+    return GBL_OK;
+}
+
 int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *hist, int32_t *actions_traj, int8_t *winner_traj,
                            int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                            int32_t *chosen_traj, int8_t *how_traj, int8_t *cand_traj, int64_t n, int64_t ply_stride,

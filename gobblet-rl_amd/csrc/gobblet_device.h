@@ -1844,4 +1844,161 @@ __device__ __forceinline__ GreedyResult greedy_decide(const Planes &p, int me, u
     return greedy_finish(h, prev3);
 }
 
+// ---- gbl_tree_search: leaf-parallel UCT, one tree per board (contract: include/gobblet_hip.h) --
+// Integer-only, so that k_tree, the host flavour and a restatement of the contract agree bit for bit.  The tree is an array of
+// 16-byte nodes (LDS in the kernel, a vector in the host flavour); node 0 is the root, 0 in a link stands for "none".  A node
+// holds no position: selection replays the actions from the root planes, one move_planes per level.
+constexpr uint32_t kStreamTree = 3u;  // generator stream of the search: the expansion draws and the leaves' playouts
+constexpr int kTreeMaxIterations = 1024, kTreeMaxPlayouts = 256, kTreeMaxExplore = 1024;
+// what the move INTO a node decided: nothing, a win / a loss of the side that made it, or a side to move without a legal action
+constexpr uint32_t kTreeOpen = 0u, kTreeWon = 1u, kTreeLost = 2u, kTreeStuck = 3u;
+
+struct TreeNode {
+    uint16_t parent, child, sibling, n;  // links (child = the newest child, sibling = the next older one); n <= 1024 visits
+    uint32_t w, l;                       // W | action << 24,  L | kTree* << 24   (W, L <= 1024 * 256 = 2^18)
+};
+static_assert(sizeof(TreeNode) == 16, "a tree node is 16 bytes");
+
+__device__ __forceinline__ uint32_t tree_action(const TreeNode &v) { return v.w >> 24; }
+__device__ __forceinline__ uint32_t tree_term(const TreeNode &v) { return v.l >> 24; }
+__device__ __forceinline__ uint32_t tree_wins(const TreeNode &v) { return v.w & 0xFFFFFFu; }
+__device__ __forceinline__ uint32_t tree_losses(const TreeNode &v) { return v.l & 0xFFFFFFu; }
+
+// generator id of playout j of iteration i of global board g (j = 0, word 0: the expansion draw).  Independent of the number of
+// iterations and of playouts: a longer search is a continuation of a shorter one.
+__device__ __forceinline__ uint64_t tree_pid(uint64_t g, uint32_t i, uint32_t j) { return (g * 1024ull + i) * 256ull + j; }
+
+// exact integer square root of x < 2^24
+__device__ __forceinline__ uint32_t tree_isqrt(uint32_t x)
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t b = 1u << 22; b; b >>= 2) {
+        const bool ge = x >= r + b;
+        x -= ge ? r + b : 0u;
+        r = (r >> 1) + (ge ? b : 0u);
+    }
+    return r;
+}
+
+// The selection key of a child (n visits, W wins, L losses of the side choosing) under a parent of np visits:
+//   ((W - L + n P) << 15) / (n P)  +  ((explore * isqrt((bitlen(np) << 20) / n)) >> 3)
+// The first quotient is taken in two base-2^8 steps of long division, which keeps every operand below 2^32 (W - L + n P <= 2^19).
+__device__ __forceinline__ uint32_t tree_key(uint32_t W, uint32_t L, uint32_t n, uint32_t P, uint32_t np, uint32_t explore)
+{
+    const uint32_t d = n * P, x = W + d - L;
+    const uint32_t hi = (x << 7) / d, rem = (x << 7) - hi * d;
+    const uint32_t mean = (hi << 8) + (rem << 8) / d;
+    const uint32_t bitlen = np ? 32u - (uint32_t)__builtin_clz(np) : 0u;
+    return mean + ((explore * tree_isqrt((bitlen << 20) / n)) >> 3);
+}
+// the order of the children of one node: the larger key, then the lower action (key < 2^20); 0 stands for "no child"
+__device__ __forceinline__ uint32_t tree_order_key(uint32_t key, uint32_t a) { return ((key + 1u) << 6) | (63u - a); }
+// the order of the root's children for the decision: visits, then W - L, then the lower action; 0 stands for "no child"
+__device__ __forceinline__ uint64_t tree_final_key(uint32_t n, uint32_t W, uint32_t L, uint32_t a)
+{
+    return ((uint64_t)n << 32) | (uint64_t)(((W + (1u << 18) - L) << 6) | (63u - a));
+}
+__device__ __forceinline__ int tree_action_of(uint64_t best_key) { return best_key ? 63 - (int)(best_key & 63u) : -1; }
+
+// Where an iteration's selection stopped: at `node`, whose position is p with `side` to move.  untried = its candidates without
+// a child (non-empty: the iteration expands one of them); 0: the node is terminal and is evaluated itself.
+struct TreeLeaf {
+    uint32_t node;
+    Planes p;
+    int side;
+    uint64_t untried;
+};
+
+// Step 1, one node after the other (the host flavour; k_tree walks the same rule with a lane per child).  rootcand != 0.
+__device__ __forceinline__ TreeLeaf tree_select(const TreeNode *nodes, const Planes &root, int mover, uint64_t rootcand, uint32_t P,
+                                                uint32_t explore)
+{
+    TreeLeaf s{0u, root, mover, 0ull};
+    uint64_t cand = rootcand;
+    for (;;) {
+        const TreeNode v = nodes[s.node];
+        if (tree_term(v)) return s;
+        uint64_t have = 0;
+        uint32_t best = 0, best_c = 0;
+        for (uint32_t c = v.child; c; c = nodes[c].sibling) {
+            const TreeNode k = nodes[c];
+            have |= 1ull << tree_action(k);
+            const uint32_t key = tree_order_key(tree_key(tree_wins(k), tree_losses(k), k.n, P, v.n, explore), tree_action(k));
+            if (key > best) best = key, best_c = c;
+        }
+        s.untried = cand & ~have;
+        if (s.untried) return s;
+        move_planes(s.p, s.side, tree_action(nodes[best_c]));
+        s.side ^= 1;
+        s.node = best_c;
+        cand = legal54(s.p, s.side);
+    }
+}
+
+// Step 2 without the bookkeeping: the gbl_sample rule over the untried candidates on generator word r, the move, and what it
+// decided (kTree*).  p / side become the new child's position.  Returns the action.
+__device__ __forceinline__ uint32_t tree_expand_move(Planes &p, int &side, uint64_t untried, uint32_t r, uint32_t &term)
+{
+    const uint32_t a = kth_bit64(untried, __umulhi(r, (uint32_t)__popcll(untried)));
+    const int by = side;
+    move_planes(p, side, a);
+    side ^= 1;
+    const int w = winner_of(p);
+    const int mine = by ? -w : w;
+    term = mine > 0 ? kTreeWon : (mine < 0 ? kTreeLost : (legal54(p, side) ? kTreeOpen : kTreeStuck));
+    return a;
+}
+
+// ... and the bookkeeping: node `at` becomes the newest child of `parent`
+__device__ __forceinline__ void tree_link(TreeNode *nodes, uint32_t at, uint32_t parent, uint32_t a, uint32_t term)
+{
+    nodes[at] = TreeNode{(uint16_t)parent, (uint16_t)0, nodes[parent].child, (uint16_t)0, a << 24, term << 24};
+    nodes[parent].child = (uint16_t)at;
+}
+
+// Step 3 of a leaf that the move into it decided: all P outcomes at once, as wins | losses << 16
+__device__ __forceinline__ uint32_t tree_decided(uint32_t term, uint32_t P)
+{
+    return term == kTreeWon ? P : (term == kTreeLost ? P << 16 : 0u);
+}
+
+// One ply of a leaf's playout: ply index t = 0 plays nothing (word 0 of a playout id belongs to the expansion), t >= 1 is
+// playout_ply.  The outcome counts for the side that moved INTO the leaf (1 - side0); PlayoutEnd.plies = masked-random plies played.
+__device__ __forceinline__ PlayoutEnd tree_playout_ply(Planes &p, int &side, int side0, uint32_t t, uint32_t word, uint32_t max_plies)
+{
+    const int w = t ? playout_ply(p, side, t, 0, word) : 0;
+    PlayoutEnd e = playout_end(w, t, 1 - side0, max_plies);
+    e.plies -= 1u;  // (playout_end counts a root move; here there is none)
+    return e;
+}
+
+// One whole playout of a leaf (the host flavour; k_tree deals the P playouts to its lanes)
+__device__ __forceinline__ PlayoutEnd tree_playout(const Planes &leaf, int side0, uint64_t seed, uint64_t pid, uint32_t call,
+                                                   uint32_t max_plies)
+{
+    Planes p = leaf;
+    int side = side0;
+    Draw4 d{};
+    for (uint32_t t = 0;; ++t) {
+        if ((t & 3u) == 0) d = draw_block(seed, pid, playout_ply_index(call, t), kStreamTree);
+        const PlayoutEnd e = tree_playout_ply(p, side, side0, t, draw_word(d, t), max_plies);
+        if (e.done) return e;
+    }
+}
+
+// Step 4: from the leaf to the root, the two counts swapping sides at every level; the root only counts visits
+__device__ __forceinline__ void tree_backup(TreeNode *nodes, uint32_t leaf, uint32_t wins, uint32_t losses)
+{
+    for (uint32_t v = leaf; v; v = nodes[v].parent) {
+        nodes[v].n += 1;
+        nodes[v].w += wins;
+        nodes[v].l += losses;
+        const uint32_t x = wins;
+        wins = losses;
+        losses = x;
+    }
+    nodes[0].n += 1;
+}
+
 }  // namespace gbl

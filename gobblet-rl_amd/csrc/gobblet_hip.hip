@@ -1720,6 +1720,175 @@ int playout_waves(int64_t n, int playouts)
     return w;
 }
 
+// gbl_tree_search: leaf-parallel UCT.  One workgroup of W wavefronts per board (a grid-stride loop over boards); the tree is an
+// array of 16-byte nodes in dynamic LDS, 16 (iterations + 1) bytes, and the root planes stay in registers as in k_playout.  An
+// iteration:
+//   select   every wavefront walks the same path (the tree is only read): the child list of a node once, with broadcast LDS reads
+//            -- lane a keeps the statistics of the child of action a -- then all lanes compute their key and a butterfly max picks
+//            the child; one move_planes per level replays the position;
+//   expand   the draw, the move and what it decided, in every lane alike (the node itself is written later, by thread 0);
+//   evaluate the P playouts of the leaf dealt to the 64 W lanes, in k_playout's four-ply quanta on one Philox block; wins | losses
+//            << 16 and the plies are summed over the wavefront by butterflies and, for W > 1, over the workgroup in LDS counters
+//            (two sets, used by alternate iterations, so that zeroing one never races with the adds of the next iteration);
+//   back up  thread 0 links the new node and walks to the root, between two barriers.
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_tree(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                                 const int8_t *__restrict__ mask, int32_t *__restrict__ visits_out,
+                                                 int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
+                                                 int32_t *__restrict__ action_out, int32_t *__restrict__ nodes_out,
+                                                 int32_t *__restrict__ plies_out, int64_t n, uint64_t seed, uint64_t env_base,
+                                                 uint32_t call, uint32_t iterations, uint32_t P, uint32_t max_plies, uint32_t explore)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    __shared__ uint32_t s_sum[2][2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        if (tid == 0) nodes[0] = TreeNode{};
+        if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
+        const int v0 = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
+        const Planes root{(uint32_t)__ballot(v0 != 0), (uint32_t)__ballot(v0 < 0), (uint32_t)__ballot(v0 & 1)};
+        const int mover = to_move[b] != 0;
+        uint64_t cand = legal54(root, mover);
+        if (mask) cand &= (uint64_t)__ballot(lane < (uint32_t)kActions && mask[b * kActions + lane] != 0);
+        const uint64_t g = env_base + (uint64_t)b;
+        __syncthreads();  // (root and counters zeroed)
+
+        uint32_t count = 1, plies_total = 0;
+        for (uint32_t i = 0; cand && i < iterations; ++i) {
+            // 1. select
+            uint32_t v = 0, term;
+            Planes p = root;
+            int side = mover;
+            uint64_t cd = cand, untried = 0;
+            for (;;) {
+                const TreeNode nv = nodes[v];
+                term = tree_term(nv);
+                if (term) break;
+                uint64_t have = 0;
+                uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
+                for (uint32_t c = nv.child; c;) {
+                    const TreeNode k = nodes[c];
+                    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)tree_action(k));
+                    have |= 1ull << a;
+                    if (lane == a) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
+                    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+                }
+                untried = cd & ~have;
+                if (untried) break;
+                uint32_t key = my_c ? tree_order_key(tree_key(my_w, my_l, my_n, P, nv.n, explore), lane) : 0u;
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    const uint32_t other = (uint32_t)__shfl_xor((int)key, o);
+                    key = other > key ? other : key;
+                }
+                const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
+                v = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a);
+                move_planes(p, side, a);
+                side ^= 1;
+                cd = legal54(p, side);
+            }
+            // 2. expand (the position and what the move decided; the node is linked below)
+            const bool grow = term == kTreeOpen;
+            uint32_t a_new = 0;
+            if (grow) a_new = tree_expand_move(p, side, untried, draw32(seed, tree_pid(g, i, 0), playout_ply_index(call, 0), kStreamTree), term);
+            // 3. evaluate
+            uint32_t wl = 0, pl = 0;
+            if (term == kTreeOpen) {
+                uint32_t j = tid, t = 0;
+                Planes q = p;
+                int s = side;
+                uint64_t pid = 0;
+                bool fresh = true;
+                while (j < P) {
+                    if (fresh) {
+                        pid = tree_pid(g, i, j);
+                        q = p;
+                        s = side;
+                        t = 0;
+                        fresh = false;
+                    }
+                    const Draw4 d = draw_block(seed, pid, playout_ply_index(call, t), kStreamTree);  // (t % 4 == 0 here)
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        if (!fresh) {
+                            const PlayoutEnd e = tree_playout_ply(q, s, side, t, d.w[u], max_plies);
+                            ++t;
+                            if (e.done) {
+                                pl += e.plies;
+                                wl += e.outcome > 0 ? 1u : (e.outcome < 0 ? 1u << 16 : 0u);
+                                j += 64u * W;
+                                fresh = true;
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    wl += (uint32_t)__shfl_xor((int)wl, o);
+                    pl += (uint32_t)__shfl_xor((int)pl, o);
+                }
+                if (W > 1 && lane == 0) {
+                    atomicAdd(&s_sum[i & 1u][0], wl);
+                    atomicAdd(&s_sum[i & 1u][1], pl);
+                }
+            }
+            __syncthreads();  // (every wavefront has read the tree; the sums are complete)
+            if (W > 1 && term == kTreeOpen) {
+                wl = s_sum[i & 1u][0];
+                pl = s_sum[i & 1u][1];
+            }
+            if (term != kTreeOpen) wl = tree_decided(term, P);
+            plies_total += pl;
+            // 4. back up
+            if (tid == 0) {
+                if (W > 1) s_sum[(i & 1u) ^ 1u][0] = s_sum[(i & 1u) ^ 1u][1] = 0u;  // (last read before the previous iteration's second barrier)
+                uint32_t leaf = v;
+                if (grow) tree_link(nodes, leaf = count, v, a_new, term);
+                tree_backup(nodes, leaf, wl & 0xFFFFu, wl >> 16);
+            }
+            count += grow ? 1u : 0u;
+            __syncthreads();  // (the tree is written)
+        }
+
+        if (tid < 64u) {  // wavefront 0: the root's children out, and the decision
+            uint32_t my_n = 0, my_w = 0, my_l = 0;
+            bool mine = false;
+            for (uint32_t c = nodes[0].child; c;) {
+                const TreeNode k = nodes[c];
+                if (lane == tree_action(k)) mine = true, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
+                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+            }
+            if (lane < (uint32_t)kActions) {
+                if (visits_out) visits_out[b * kActions + lane] = (int32_t)my_n;
+                if (wins_out) wins_out[b * kActions + lane] = (int32_t)my_w;
+                if (losses_out) losses_out[b * kActions + lane] = (int32_t)my_l;
+            }
+            uint64_t key = mine ? tree_final_key(my_n, my_w, my_l, lane) : 0ull;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint64_t other = (uint64_t)__shfl_xor((unsigned long long)key, o);
+                key = other > key ? other : key;
+            }
+            if (lane == 0) {
+                if (action_out) action_out[b] = tree_action_of(key);
+                if (nodes_out) nodes_out[b] = (int32_t)count;
+                if (plies_out) plies_out[b] = (int32_t)plies_total;
+            }
+        }
+        __syncthreads();  // (before the next board rewrites the root)
+    }
+}
+
+// Wavefronts per board of k_tree: a leaf has only `playouts` games to deal, so more than playouts / 64 wavefronts would idle, and
+// one is enough once the batch alone gives every SIMD eight wavefronts (8 192 boards).
+int tree_waves(int64_t n, int playouts)
+{
+    int w = 1;
+    while (w < 4 && n * (2 * w) <= 8192 && 64 * (2 * w) <= playouts) w *= 2;
+    return w;
+}
+
 // gbl_greedy: one decision per board.  Each lane owns a board (depth-1 walk, order-dependent replay,
 // fallback test), but the depth-2 evaluations -- one moved + legal54 + outcomes54 per (board,
 // candidate) pair, ~95 % of the work -- are pooled over the tile: the boards' candidate lists are
@@ -3094,6 +3263,38 @@ int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t 
     }
 #undef GBL_PLAYOUT
     GBL_LAUNCHED("gbl_playout_values");
+}
+
+int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
+                    int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
+                    int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (iterations < 1 || iterations > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
+    if (playouts < 1 || playouts > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
+    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
+    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    if ((reinterpret_cast<uintptr_t>(visits_out) | reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) |
+         reinterpret_cast<uintptr_t>(action_out) | reinterpret_cast<uintptr_t>(nodes_out) | reinterpret_cast<uintptr_t>(plies_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / plies_out must be 4-byte aligned");
+    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    const size_t lds = sizeof(TreeNode) * ((size_t)iterations + 1);  // the tree: one node per iteration and the root
+    const hipStream_t s = (hipStream_t)stream;
+#define GBL_TREE(W)                                                                                                               \
+    hipLaunchKernelGGL((k_tree<W>), grid, dim3(64 * W), lds, s, state, to_move, mask, visits_out, wins_out, losses_out, action_out, \
+                       nodes_out, plies_out, n, seed, env_base, call, (uint32_t)iterations, (uint32_t)playouts, (uint32_t)max_plies, \
+                       (uint32_t)explore)
+    switch (tree_waves(n, playouts)) {
+    case 4: GBL_TREE(4); break;
+    case 2: GBL_TREE(2); break;
+    default: GBL_TREE(1); break;
+    }
+#undef GBL_TREE
+    GBL_LAUNCHED("gbl_tree_search");
 }
 
 }  // extern "C"

@@ -91,6 +91,9 @@ int gbl_cpu_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8
 int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
                            uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
                            int32_t *action_out, int32_t *plies_out, int64_t n, void *stream);
+int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
+                        int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
+                        int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

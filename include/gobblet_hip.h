@@ -287,6 +287,45 @@ int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t 
                        uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
                        int32_t *action_out, int32_t *plies_out, int64_t n, void *stream);
 
+/* UCT tree search (no counterpart in the reference): leaf-parallel, one independent tree per board, `iterations` leaves of
+ * `playouts` masked-random playouts each.  Deterministic and integer-only (every operand below 2^64, every division an unsigned
+ * integer division of non-negative operands), so that the kernel, the host flavour and a restatement of this text agree bit for bit.
+ * Per board g = env_base + b with mover m = to_move[b], P = playouts:
+ *   Nodes.  Node 0 is the root (the given position, m to move); every other node is the position after its parent's side played
+ *     one action.  A node keeps n_v (iterations that went through it) and W_v, L_v (playout outcomes counted for the side that
+ *     moved INTO the node).  A node other than the root is terminal if check_for_winner() is non-zero after the move into it, or
+ *     if its side to move has no legal action.  The root's candidates are mask[b] & its legal mask (mask NULL: the legal mask);
+ *     every other node's candidates are its legal mask.  A root without a candidate: nothing is played, action_out = -1,
+ *     nodes_out = 1, everything else 0.
+ *   Iteration i = 0 .. iterations - 1:
+ *     1. Select.  Start at the root.  While the node is not terminal and every candidate has a child, go to the child c with the
+ *        largest key, the lowest action on ties:
+ *          key(c) = (((W_c - L_c + n_c P) << 15) / (n_c P)) + ((explore * isqrt((bitlen(n_p) << 20) / n_c)) >> 3)
+ *        p = the node being left, bitlen(x) = 32 - clz(x), isqrt = the exact integer square root.  The first term is the child's
+ *        mean outcome for the side choosing, 0 .. 65536; the second is UCB1's exploration term with the logarithm replaced by the
+ *        bit length; explore is in units of 1/256 of a full win.
+ *     2. Expand.  If the node reached is not terminal: one of its candidates without a child by the gbl_sample rule
+ *        (k = (r * count) >> 32, the k-th such action ascending), r = the generator word of (seed, pid(g, i, 0), ply index
+ *        (call << 8) | 0, stream 3), pid(g, i, j) = (g * 1024 + i) * 256 + j; the child is created.
+ *     3. Evaluate the leaf (the new child, or the terminal node selection stopped at).  Decided by check_for_winner(): all P
+ *        outcomes are that result, nothing is played.  Its side has no move: all P outcomes are unfinished.  Otherwise playout
+ *        j = 0 .. P - 1 starts from the leaf's position and plays, for t = 1 .. max_plies, the gbl_sample rule over the legal mask
+ *        of the side to move with the generator word of (seed, pid(g, i, j), (call << 8) | t, stream 3), until the first
+ *        non-zero winner; max_plies plies without one, or no legal move, leave it unfinished (neither a win nor a loss).
+ *     4. Back up.  From the leaf to the root: n_v += 1, W_v += wins, L_v += losses, wins and losses swapping at every level; the
+ *        root only counts n.
+ * Outputs (each may be NULL), for the root's child c of action a, from the root mover's side; 0 for every other action:
+ *   visits_out int32[n][54] = n_c      wins_out int32[n][54] = W_c      losses_out int32[n][54] = L_c
+ *   action_out int32[n] : the root's child with the largest n_c, then the larger W_c - L_c, then the lowest action; -1 without one
+ *   nodes_out  int32[n] : nodes created, the root included          plies_out int32[n] : masked-random plies played in all playouts
+ * pid does not depend on `iterations`: a search is the beginning of every longer one, so nodes_out and the sum of visits_out do
+ * not decrease with it, and a shard (env_base) of a batch gets its boards' results.  1 <= iterations <= 1024, 1 <= playouts <= 256,
+ * 0 <= max_plies <= 255, 0 <= explore <= 1024, call < 2^24, env_base + n <= 2^42; states must be contract states (gbl_validate).
+ * Allocates nothing; the tree lives in 16 (iterations + 1) bytes of LDS per workgroup. */
+int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
+                    int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
+                    int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream);
+
 /* Trajectory collection (K plies per launch with EVERY ply materialised).  `plies` masked-random
  * plies with auto-reset in ONE launch; ply t (t = 0 .. plies-1) of board b leaves in element
  *     cell(t, b) = t * ply_stride + (b / 64) * tile_stride + b % 64
