@@ -677,6 +677,46 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
     return GBL_OK;
 }
 
+// One board's search (the contract of gbl_tree_search, one iteration and one playout at a time): the root's children into visits /
+// wins / losses (zeroed here), the decision's order key (0: no child), the nodes created and the plies played.
+struct HostSearch {
+    int32_t visits[kActions], wins[kActions], losses[kActions];
+    uint64_t best;
+    uint32_t count, plies;
+};
+
+static void host_tree_search(std::vector<TreeNode> &nodes, const Planes &root, int mover, uint64_t cand, uint64_t g, uint32_t iterations,
+                             uint32_t P, uint32_t max_plies, uint32_t explore, uint64_t seed, uint32_t call, HostSearch &out)
+{
+    nodes[0] = TreeNode{};
+    uint32_t count = 1, plies = 0;
+    for (uint32_t i = 0; cand && i < iterations; ++i) {
+        TreeLeaf s = tree_select(nodes.data(), root, mover, cand, P, explore);
+        const uint32_t parent = s.node;
+        uint32_t term = tree_term(nodes[s.node]), a = 0;
+        const bool grow = s.untried != 0;
+        if (grow) a = tree_expand_move(s.p, s.side, s.untried, draw32(seed, tree_pid(g, i, 0), playout_ply_index(call, 0), kStreamTree), term);
+        uint32_t wl = tree_decided(term, P);
+        for (uint32_t j = 0; term == kTreeOpen && j < P; ++j) {
+            const PlayoutEnd e = tree_playout(s.p, s.side, seed, tree_pid(g, i, j), call, max_plies);
+            wl += e.outcome > 0 ? 1u : (e.outcome < 0 ? 1u << 16 : 0u);
+            plies += e.plies;
+        }
+        if (grow) tree_link(nodes.data(), s.node = count++, parent, a, term);
+        tree_backup(nodes.data(), s.node, wl & 0xFFFFu, wl >> 16);
+    }
+    memset(out.visits, 0, sizeof out.visits); memset(out.wins, 0, sizeof out.wins); memset(out.losses, 0, sizeof out.losses);
+    out.best = 0;
+    for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
+        const TreeNode &k = nodes[c];
+        const uint32_t a = tree_action(k);
+        out.visits[a] = k.n; out.wins[a] = (int32_t)tree_wins(k); out.losses[a] = (int32_t)tree_losses(k);
+        out.best = std::max(out.best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
+    }
+    out.count = count;
+    out.plies = plies;
+}
+
 int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
                         int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
                         int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *)
@@ -690,48 +730,24 @@ int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t
     if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
-    const uint32_t P = (uint32_t)playouts;
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)iterations + 1);
+        HostSearch h;
         for (int64_t b = b0; b < b1; ++b) {
             uint32_t r[7];
             load_row(state, b, r);
             const Planes root = make_planes(r);
             const int mover = to_move[b] != 0;
-            const uint64_t g = env_base + (uint64_t)b;
             uint64_t cand = legal54(root, mover);
             if (mask) cand &= read_mask(mask + b * kActions);
-            nodes[0] = TreeNode{};
-            uint32_t count = 1, plies = 0;
-            for (uint32_t i = 0; cand && i < (uint32_t)iterations; ++i) {
-                TreeLeaf s = tree_select(nodes.data(), root, mover, cand, P, (uint32_t)explore);
-                const uint32_t parent = s.node;
-                uint32_t term = tree_term(nodes[s.node]), a = 0;
-                const bool grow = s.untried != 0;
-                if (grow) a = tree_expand_move(s.p, s.side, s.untried, draw32(seed, tree_pid(g, i, 0), playout_ply_index(call, 0), kStreamTree), term);
-                uint32_t wl = tree_decided(term, P);
-                for (uint32_t j = 0; term == kTreeOpen && j < P; ++j) {
-                    const PlayoutEnd e = tree_playout(s.p, s.side, seed, tree_pid(g, i, j), call, (uint32_t)max_plies);
-                    wl += e.outcome > 0 ? 1u : (e.outcome < 0 ? 1u << 16 : 0u);
-                    plies += e.plies;
-                }
-                if (grow) tree_link(nodes.data(), s.node = count++, parent, a, term);
-                tree_backup(nodes.data(), s.node, wl & 0xFFFFu, wl >> 16);
-            }
-            int32_t visits[kActions] = {}, wins[kActions] = {}, losses[kActions] = {};
-            uint64_t best = 0;
-            for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
-                const TreeNode &k = nodes[c];
-                const uint32_t a = tree_action(k);
-                visits[a] = k.n; wins[a] = (int32_t)tree_wins(k); losses[a] = (int32_t)tree_losses(k);
-                best = std::max(best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
-            }
-            if (visits_out) memcpy(visits_out + b * kActions, visits, sizeof visits);
-            if (wins_out) memcpy(wins_out + b * kActions, wins, sizeof wins);
-            if (losses_out) memcpy(losses_out + b * kActions, losses, sizeof losses);
-            if (action_out) action_out[b] = tree_action_of(best);
-            if (nodes_out) nodes_out[b] = (int32_t)count;
-            if (plies_out) plies_out[b] = (int32_t)plies;
+            host_tree_search(nodes, root, mover, cand, env_base + (uint64_t)b, (uint32_t)iterations, (uint32_t)playouts, (uint32_t)max_plies,
+                             (uint32_t)explore, seed, call, h);
+            if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
+            if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
+            if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
+            if (action_out) action_out[b] = tree_action_of(h.best);
+            if (nodes_out) nodes_out[b] = (int32_t)h.count;
+            if (plies_out) plies_out[b] = (int32_t)h.plies;
         }
     }, 1);
     return GBL_OK;
@@ -812,6 +828,123 @@ int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t 
             }
         }
         add_tally(counters, tl);
+    });
+    return GBL_OK;
+}
+
+int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                           int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                           int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int64_t n, int64_t ply_stride,
+                           int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                           int policy0, int policy1, int iterations0, int iterations1, int playouts0, int playouts1, int max_plies,
+                           int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
+        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
+    if ((policy0 != GBL_POLICY_RANDOM && policy0 != GBL_POLICY_TREE) || (policy1 != GBL_POLICY_RANDOM && policy1 != GBL_POLICY_TREE))
+        return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE");
+    const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != GBL_POLICY_TREE) continue;
+        if (its[m] < 1 || its[m] > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
+        if (pls[m] < 1 || pls[m] > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
+    }
+    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (sample_plies < 0) return fail(GBL_ERR_ARG, "sample_plies < 0");
+    if (sample_plies > 0 && !turn) return fail(GBL_ERR_ARG, "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)");
+    if ((uint64_t)ply0 + plies > (1ull << 24)) return fail(GBL_ERR_ARG, "ply0 + plies must not exceed 2^24 (the search's call index)");
+    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (plies == 0) return GBL_OK;
+    if (!strides_ok(n, plies, ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    if (ply_dev) ply0 += *ply_dev;
+    const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
+        Tally tl;
+        std::vector<TreeNode> nodes((size_t)most + 1);
+        HostSearch h;
+        for (int64_t b = b0; b < b1; ++b) {
+            uint32_t r[7];
+            load_row(state, b, r);
+            Planes p = make_planes(r);
+            const HostRow row{reinterpret_cast<uint8_t *>(state) + b * kCells};
+            const uint64_t g = env_base + (uint64_t)b;
+            int mover = to_move[b] != 0, dn = 0, tabs = turn ? turn[b] : 0;
+            uint64_t legal = legal54(p, mover);
+            for (uint32_t t = 0; t < plies; ++t) {
+                const uint32_t q = ply0 + t;
+                const int who = mover;
+                const bool tree = pol[who] == GBL_POLICY_TREE;
+                int action, how = GBL_HOW_RANDOM, value = 0;
+                if (tree) {
+                    host_tree_search(nodes, p, who, legal, g, (uint32_t)its[who], (uint32_t)pls[who], (uint32_t)max_plies, (uint32_t)explore, seed,
+                                     q, h);
+                    const bool sampled = tabs < sample_plies;
+                    action = sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit)) : tree_action_of(h.best);
+                    how = sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
+                    for (int a = 0; a < kActions; ++a) value += h.wins[a] - h.losses[a];
+                } else {
+                    action = sample54(legal, seed, g, q);
+                }
+                const Ply y = play_ply(p, row, mover, legal, action, illegal_mode);
+                dn = y.terminal ? 1 : 0;
+                if (y.terminal) {
+                    p = Planes{0u, 0u, 0u};
+                    mover = 0;
+                    row.reset();
+                }
+                tabs = next_turn(tabs, y, 1);
+                tl.games += y.terminal; tl.w1 += y.winner == 1; tl.w2 += y.winner == -1;
+                legal = next_mask(p, mover, dn, 1);
+                const int64_t at = cell_of(b, t, ply_stride, tile_stride);
+                if (actions_traj) actions_traj[at] = action;
+                if (winner_traj) winner_traj[at] = (int8_t)y.winner;
+                if (reward_traj) { reward_traj[2 * at] = (int8_t)y.r0; reward_traj[2 * at + 1] = (int8_t)y.r1; }
+                if (done_traj) done_traj[at] = (int8_t)dn;
+                if (to_move_traj) to_move_traj[at] = (int8_t)mover;
+                if (visits_traj)
+                    for (int a = 0; a < kActions; ++a) visits_traj[at * kActions + a] = (int16_t)(tree ? h.visits[a] : 0);
+                if (value_traj) value_traj[at] = value;
+                if (nodes_traj) nodes_traj[at] = tree ? (int32_t)h.count : 0;
+                if (how_traj) how_traj[at] = (int8_t)how;
+                if (mover_traj) mover_traj[at] = (int8_t)who;
+                if (obs_traj) write_obs(obs_traj + at * kObs, p, mover);
+                if (mask_traj) write_mask(mask_traj + at * kActions, legal);
+            }
+            tl.plies += plies;
+            to_move[b] = (int8_t)mover;
+            done[b] = (int8_t)dn;
+            if (turn) turn[b] = tabs;
+        }
+        add_tally(counters, tl);
+    }, 1);
+    return GBL_OK;
+}
+
+int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
+                            int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *)
+{
+    GBL_CHECK_N(n);
+    GBL_NEED(done_traj, "done_traj"); GBL_NEED(reward_traj, "reward_traj"); GBL_NEED(mover_traj, "mover_traj"); GBL_NEED(z_traj, "z_traj");
+    if (plies > 32767u) return fail(GBL_ERR_ARG, "plies must not exceed 32767");
+    if (plies == 0) return GBL_OK;
+    if (!strides_ok(n, plies, ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    parallel_for(n, [=](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) {
+            int r0 = 0, r1 = 0, left = -1;  // the rewards of the nearest game end at or after t, and how far it is
+            for (uint32_t t = plies; t-- > 0;) {
+                const int64_t at = cell_of(b, t, ply_stride, tile_stride);
+                if (done_traj[at]) { r0 = reward_traj[2 * at]; r1 = reward_traj[2 * at + 1]; left = 0; }
+                else if (left >= 0) ++left;
+                z_traj[at] = (int8_t)(left < 0 ? GBL_Z_OPEN : (mover_traj[at] ? r1 : r0));
+                if (plies_left_traj) plies_left_traj[at] = (int16_t)left;
+            }
+        }
     });
     return GBL_OK;
 }

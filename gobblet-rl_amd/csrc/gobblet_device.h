@@ -2001,4 +2001,25 @@ __device__ __forceinline__ void tree_backup(TreeNode *nodes, uint32_t leaf, uint
     nodes[0].n += 1;
 }
 
+// ---- gbl_collect_search: whole games with the tree search on either side (contract: include/gobblet_hip.h) --
+constexpr int kPolicyTree = 4;                 // GBL_POLICY_TREE
+constexpr int kHowSearch = 3, kHowSearchSampled = 4;  // GBL_HOW_SEARCH / GBL_HOW_SEARCH_SAMPLED (0 = GBL_HOW_RANDOM)
+constexpr int kZOpen = -128;                   // GBL_Z_OPEN
+constexpr uint32_t kStreamVisit = 4u;          // generator stream of the visit-proportional draw of a game's first plies
+
+// The visit-proportional draw on generator word r: k = (r * S) >> 32 with S the sum of the visits, then the lowest action whose
+// running sum of visits exceeds k; -1 when nothing was visited.  (One action after the other: the host flavour; the kernel takes a
+// prefix sum over the lanes, k_collect_search.)
+__device__ __forceinline__ int visits_pick(const int32_t (&visits)[kActions], uint32_t r)
+{
+    uint32_t S = 0, run = 0;
+    for (int a = 0; a < kActions; ++a) S += (uint32_t)visits[a];
+    const uint32_t k = __umulhi(r, S);
+    for (int a = 0; a < kActions; ++a) {
+        run += (uint32_t)visits[a];
+        if (run > k) return a;
+    }
+    return -1;
+}
+
 }  // namespace gbl

@@ -1889,6 +1889,308 @@ int tree_waves(int64_t n, int playouts)
     return w;
 }
 
+// The iterations of one board's search for k_collect_search: k_tree's loop, word for word, as a function (on entry the root node and
+// the sums are zeroed and a barrier has passed; on return the tree is written and a barrier has passed; count, 1 on entry, and
+// plies_total, 0, count the nodes created and the masked-random plies played).  A COPY: with k_tree calling it the compiler orders
+// k_tree<W>'s operands and registers differently, and the existing kernels' code stays as measured.
+template <int W>
+__device__ __forceinline__ void tree_iterations(TreeNode *const nodes, uint32_t (&s_sum)[2][2], const Planes &root, const int mover,
+                                                const uint64_t cand, const uint64_t g, const uint64_t seed, const uint32_t call,
+                                                const uint32_t iterations, const uint32_t P, const uint32_t max_plies,
+                                                const uint32_t explore, const uint32_t tid, const uint32_t lane, uint32_t &count,
+                                                uint32_t &plies_total)
+{
+    for (uint32_t i = 0; cand && i < iterations; ++i) {
+        // 1. select
+        uint32_t v = 0, term;
+        Planes p = root;
+        int side = mover;
+        uint64_t cd = cand, untried = 0;
+        for (;;) {
+            const TreeNode nv = nodes[v];
+            term = tree_term(nv);
+            if (term) break;
+            uint64_t have = 0;
+            uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
+            for (uint32_t c = nv.child; c;) {
+                const TreeNode k = nodes[c];
+                const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)tree_action(k));
+                have |= 1ull << a;
+                if (lane == a) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
+                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+            }
+            untried = cd & ~have;
+            if (untried) break;
+            uint32_t key = my_c ? tree_order_key(tree_key(my_w, my_l, my_n, P, nv.n, explore), lane) : 0u;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint32_t other = (uint32_t)__shfl_xor((int)key, o);
+                key = other > key ? other : key;
+            }
+            const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
+            v = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a);
+            move_planes(p, side, a);
+            side ^= 1;
+            cd = legal54(p, side);
+        }
+        // 2. expand (the position and what the move decided; the node is linked below)
+        const bool grow = term == kTreeOpen;
+        uint32_t a_new = 0;
+        if (grow) a_new = tree_expand_move(p, side, untried, draw32(seed, tree_pid(g, i, 0), playout_ply_index(call, 0), kStreamTree), term);
+        // 3. evaluate
+        uint32_t wl = 0, pl = 0;
+        if (term == kTreeOpen) {
+            uint32_t j = tid, t = 0;
+            Planes q = p;
+            int s = side;
+            uint64_t pid = 0;
+            bool fresh = true;
+            while (j < P) {
+                if (fresh) {
+                    pid = tree_pid(g, i, j);
+                    q = p;
+                    s = side;
+                    t = 0;
+                    fresh = false;
+                }
+                const Draw4 d = draw_block(seed, pid, playout_ply_index(call, t), kStreamTree);  // (t % 4 == 0 here)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (!fresh) {
+                        const PlayoutEnd e = tree_playout_ply(q, s, side, t, d.w[u], max_plies);
+                        ++t;
+                        if (e.done) {
+                            pl += e.plies;
+                            wl += e.outcome > 0 ? 1u : (e.outcome < 0 ? 1u << 16 : 0u);
+                            j += 64u * W;
+                            fresh = true;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                wl += (uint32_t)__shfl_xor((int)wl, o);
+                pl += (uint32_t)__shfl_xor((int)pl, o);
+            }
+            if (W > 1 && lane == 0) {
+                atomicAdd(&s_sum[i & 1u][0], wl);
+                atomicAdd(&s_sum[i & 1u][1], pl);
+            }
+        }
+        __syncthreads();  // (every wavefront has read the tree; the sums are complete)
+        if (W > 1 && term == kTreeOpen) {
+            wl = s_sum[i & 1u][0];
+            pl = s_sum[i & 1u][1];
+        }
+        if (term != kTreeOpen) wl = tree_decided(term, P);
+        plies_total += pl;
+        // 4. back up
+        if (tid == 0) {
+            if (W > 1) s_sum[(i & 1u) ^ 1u][0] = s_sum[(i & 1u) ^ 1u][1] = 0u;  // (last read before the previous iteration's second barrier)
+            uint32_t leaf = v;
+            if (grow) tree_link(nodes, leaf = count, v, a_new, term);
+            tree_backup(nodes, leaf, wl & 0xFFFFu, wl >> 16);
+        }
+        count += grow ? 1u : 0u;
+        __syncthreads();  // (the tree is written)
+    }
+}
+
+// The root's child of action `lane` (every lane of a wavefront calls it; the tree is only read)
+struct TreeRootChild {
+    uint32_t n, w, l;
+    bool mine;
+};
+
+__device__ __forceinline__ TreeRootChild tree_root_child(const TreeNode *nodes, uint32_t lane)
+{
+    TreeRootChild r{0u, 0u, 0u, false};
+    for (uint32_t c = nodes[0].child; c;) {
+        const TreeNode k = nodes[c];
+        if (lane == tree_action(k)) r.mine = true, r.n = k.n, r.w = tree_wins(k), r.l = tree_losses(k);
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+    }
+    return r;
+}
+
+// gbl_collect_search: whole games with the tree search on either or both sides, every ply materialised.  One workgroup of W
+// wavefronts per board (a grid-stride loop over boards) with the ply loop INSIDE: a board whose search walks into decided nodes
+// and plays nothing goes on to its next ply while its neighbours still play iterations x playouts games -- no ply of any board
+// waits for the slowest board's search, and neither a second launch nor the action's round trip through HBM lies between a
+// search and its step.  Between two searches only the planes, the mover, the turn and the done flag are live, all wave-uniform
+// (every wavefront replays the same ply; wavefront 0 stores).  A tree side's ply:
+//   search   the root node is zeroed, then tree_iterations -- the tree in 16 (iterations + 1) bytes of dynamic LDS, rebuilt from
+//            an empty root on every ply (call q's search IS gbl_tree_search(call = q));
+//   decide   lane a reads the root's child of action a; butterflies give the decision's key and the value sum, a prefix sum over
+//            the lanes the visit-proportional draw of a game's first plies (stream kStreamVisit);
+//   step     play_ply / next_turn / next_mask on the planes; the state row is rebuilt from them once, after the last ply;
+//   store    the scalars from lane 0, the visits row from lanes 0..53, and the mask and observation rows built in LDS by
+//            mask_row_part<4> / obs_scatter_part<4> on lanes 0..3 and stored a byte per lane, all non-temporally.
+struct SearchTraj {
+    int32_t *actions;
+    int8_t *winner, *reward, *done, *to_move, *mask, *obs;
+    int16_t *visits;
+    int32_t *value, *nodes;
+    int8_t *how, *mover;
+};
+
+__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                           uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
+                                                           uint32_t plies, int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride,
+                                                           SearchTraj T, int policy0, int policy1, uint32_t iterations0, uint32_t iterations1,
+                                                           uint32_t playouts0, uint32_t playouts1, uint32_t max_plies, uint32_t explore,
+                                                           int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
+                                                           int32_t *__restrict__ turn)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    __shared__ uint32_t s_sum[2][2];
+    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (ply_dev) ply0 += *ply_dev;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        const int v0 = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
+        Planes p{(uint32_t)__ballot(v0 != 0), (uint32_t)__ballot(v0 < 0), (uint32_t)__ballot(v0 & 1)};
+        int mover = to_move[b] != 0, tabs = turn ? turn[b] : 0, dn = 0;
+        uint32_t games = 0, w1 = 0, w2 = 0;
+        const uint64_t g = env_base + (uint64_t)b;
+        const int64_t cell0 = (b >> 6) * tile_stride + (b & 63);
+        for (uint32_t t = 0; t < plies; ++t) {
+            const uint32_t q = ply0 + t;
+            const int who = mover;
+            const uint64_t legal = legal54(p, who);
+            const bool tree = (who ? policy1 : policy0) == kPolicyTree;
+            int action, how = 0, value = 0;
+            uint32_t my_n = 0, count = 0;
+            if (tree) {
+                if (tid == 0) nodes[0] = TreeNode{};
+                if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
+                __syncthreads();  // (root and counters zeroed)
+                uint32_t plies_total = 0;
+                count = 1;
+                tree_iterations<W>(nodes, s_sum, p, who, legal, g, seed, q, who ? iterations1 : iterations0, who ? playouts1 : playouts0,
+                                   max_plies, explore, tid, lane, count, plies_total);
+                const TreeRootChild c = tree_root_child(nodes, lane);
+                my_n = c.n;
+                uint64_t key = c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull;
+                value = (int)c.w - (int)c.l;
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    const uint64_t other = (uint64_t)__shfl_xor((unsigned long long)key, o);
+                    key = other > key ? other : key;
+                    value += __shfl_xor(value, o);
+                }
+                action = tree_action_of(key);
+                how = kHowSearch;
+                if (tabs < sample_plies) {  // the first plies of a game: in proportion to the visits
+                    uint32_t run = my_n;    // (the running sum of the visits through this lane's action)
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const uint32_t below = (uint32_t)__shfl_up((int)run, o);
+                        run += lane >= (uint32_t)o ? below : 0u;
+                    }
+                    const uint32_t S = (uint32_t)__builtin_amdgcn_readlane((int)run, 63);
+                    const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), S);
+                    const uint64_t over = (uint64_t)__ballot(run > k);
+                    action = over ? (int)__builtin_ctzll(over) : -1;
+                    how = kHowSearchSampled;
+                }
+                __syncthreads();  // (every wavefront has read the root's children before the next search rewrites the tree)
+            } else {
+                action = pick54(legal, draw32(seed, g, q));
+            }
+            action = uniform(action);
+            const Ply y = play_ply(p, NoRow{}, mover, legal, action, illegal_mode);
+            dn = uniform(y.terminal ? 1 : 0);
+            if (dn) {  // raw_env.reset, gobblet.py:275-290
+                p = Planes{0u, 0u, 0u};
+                mover = 0;
+            }
+            p = Planes{(uint32_t)uniform((int)p.nz), (uint32_t)uniform((int)p.neg), (uint32_t)uniform((int)p.odd)};
+            mover = uniform(mover);
+            tabs = uniform(next_turn(tabs, y, 1));
+            const int winner = uniform(y.winner);
+            games += (uint32_t)dn;
+            w1 += winner == 1;
+            w2 += winner == -1;
+            if (tid < 64u) {  // wavefront 0: the ply's outputs
+                const int64_t at = (int64_t)t * ply_stride + cell0;
+                if (lane == 0) {
+                    if (T.actions) T.actions[at] = action;
+                    if (T.winner) T.winner[at] = (int8_t)winner;
+                    if (T.reward) reinterpret_cast<uint16_t *>(T.reward)[at] = (uint16_t)((y.r0 & 0xFF) | ((y.r1 & 0xFF) << 8));
+                    if (T.done) T.done[at] = (int8_t)dn;
+                    if (T.to_move) T.to_move[at] = (int8_t)mover;
+                    if (T.value) T.value[at] = value;
+                    if (T.nodes) T.nodes[at] = (int32_t)count;
+                    if (T.how) T.how[at] = (int8_t)how;
+                    if (T.mover) T.mover[at] = (int8_t)who;
+                }
+                if (T.visits && lane < (uint32_t)kActions) __builtin_nontemporal_store((int16_t)my_n, T.visits + at * kActions + lane);
+                if (T.mask) {
+                    if (lane < 4u) mask_row_part<4>(reinterpret_cast<uint8_t *>(s_mask), next_mask(p, mover, dn, 1), (int)lane);
+                    wave_lds_fence();
+                    if (lane < (uint32_t)kActions)
+                        __builtin_nontemporal_store(reinterpret_cast<const int8_t *>(s_mask)[lane], T.mask + at * kActions + lane);
+                    wave_lds_fence();
+                }
+                if (T.obs) {
+                    if (lane < 32u) s_obs[lane] = 0u;
+                    wave_lds_fence();
+                    if (lane < 4u) obs_scatter_part<4>(reinterpret_cast<uint8_t *>(s_obs), p, mover, (int)lane);
+                    wave_lds_fence();
+                    const int8_t *row = reinterpret_cast<const int8_t *>(s_obs);
+                    __builtin_nontemporal_store(row[lane], T.obs + at * kObs + lane);
+                    if (lane + 64u < (uint32_t)kObs) __builtin_nontemporal_store(row[lane + 64u], T.obs + at * kObs + lane + 64u);
+                    wave_lds_fence();
+                }
+            }
+        }
+        if (tid < (uint32_t)kCells) {  // the state row from the planes (planes_to_row, a cell per lane)
+            const uint32_t nz = (p.nz >> tid) & 1u, ng = (p.neg >> tid) & nz, od = (p.odd >> tid) & nz;
+            const uint32_t v = nz * (tid >= 18u ? 6u : (tid >= 9u ? 4u : 2u)) - od;
+            state[b * kCells + tid] = (int8_t)(ng ? 0u - v : v);
+        }
+        if (tid == 0) {
+            to_move[b] = (int8_t)mover;
+            done[b] = (int8_t)dn;
+            if (turn) turn[b] = tabs;
+            if (counters) tally_flush(counters, b, 1, plies, games, w1, w2);
+        }
+    }
+}
+
+// gbl_outcome_targets: one reverse pass over the plies per board, a lane per board and a wavefront per tile of 64 boards -- in both
+// layouts the 64 lanes of a ply read and write consecutive elements.  A ply's loads do not depend on the pass's state (the reward
+// is read whether or not the game ended there), so the unrolled loop keeps several plies' loads in flight: 4 bytes in and up to 3
+// out per cell, memory-bound.
+__global__ __launch_bounds__(64) void k_outcome_targets(const int8_t *__restrict__ done_t, const int8_t *__restrict__ reward_t,
+                                                        const int8_t *__restrict__ mover_t, int8_t *__restrict__ z_t,
+                                                        int16_t *__restrict__ left_t, int64_t n, int64_t ntiles, int64_t ply_stride,
+                                                        int64_t tile_stride, uint32_t plies)
+{
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        if (tile * kTile + (int64_t)threadIdx.x >= n) continue;
+        const int64_t cell0 = tile * tile_stride + threadIdx.x;
+        uint32_t rw = 0;  // the two rewards of the nearest game end at or after t
+        int left = -1;    // ... and how many plies ahead it lies
+#pragma unroll 4
+        for (uint32_t t = plies; t-- > 0;) {
+            const int64_t at = (int64_t)t * ply_stride + cell0;
+            const int d = done_t[at], m = mover_t[at];
+            const uint32_t r = reinterpret_cast<const uint16_t *>(reward_t)[at];
+            left = d ? 0 : (left >= 0 ? left + 1 : left);
+            rw = d ? r : rw;
+            z_t[at] = (int8_t)(left < 0 ? kZOpen : (int)(int8_t)(m ? rw >> 8 : rw & 0xFFu));
+            if (left_t) left_t[at] = (int16_t)left;
+        }
+    }
+}
+
 // gbl_greedy: one decision per board.  Each lane owns a board (depth-1 walk, order-dependent replay,
 // fallback test), but the depth-2 evaluations -- one moved + legal54 + outcomes54 per (board,
 // candidate) pair, ~95 % of the work -- are pooled over the tile: the boards' candidate lists are
@@ -3295,6 +3597,75 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
     }
 #undef GBL_TREE
     GBL_LAUNCHED("gbl_tree_search");
+}
+
+int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                       int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                       int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int64_t n, int64_t ply_stride,
+                       int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                       int policy0, int policy1, int iterations0, int iterations1, int playouts0, int playouts1, int max_plies,
+                       int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
+        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
+    if ((policy0 != GBL_POLICY_RANDOM && policy0 != GBL_POLICY_TREE) || (policy1 != GBL_POLICY_RANDOM && policy1 != GBL_POLICY_TREE))
+        return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE");
+    const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
+    int most = 0, wide = 1;  // the larger tree and the larger leaf of the sides that search
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != GBL_POLICY_TREE) continue;
+        if (its[m] < 1 || its[m] > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
+        if (pls[m] < 1 || pls[m] > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
+        most = std::max(most, its[m]);
+        wide = std::max(wide, pls[m]);
+    }
+    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (sample_plies < 0) return fail(GBL_ERR_ARG, "sample_plies < 0");
+    if (sample_plies > 0 && !turn) return fail(GBL_ERR_ARG, "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)");
+    if ((uint64_t)ply0 + plies > (1ull << 24)) return fail(GBL_ERR_ARG, "ply0 + plies must not exceed 2^24 (the search's call index)");
+    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (plies == 0) return GBL_OK;
+    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
+                                 reinterpret_cast<uintptr_t>(actions_traj) | reinterpret_cast<uintptr_t>(value_traj) |
+                                     reinterpret_cast<uintptr_t>(nodes_traj),
+                                 "actions_traj / value_traj / nodes_traj must be 4-byte aligned", turn, counters))
+        return e;
+    if (reinterpret_cast<uintptr_t>(visits_traj) & 1u) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
+    const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                       nodes_traj, how_traj, mover_traj};
+    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    const size_t lds = sizeof(TreeNode) * ((size_t)most + 1);  // the tree: one node per iteration and the root
+    const hipStream_t s = (hipStream_t)stream;
+#define GBL_CS(W)                                                                                                                    \
+    hipLaunchKernelGGL((k_collect_search<W>), grid, dim3(64 * W), lds, s, state, to_move, n, seed, env_base, ply_dev, ply0, plies, done, \
+                       ply_stride, tile_stride, T, policy0, policy1, (uint32_t)iterations0, (uint32_t)iterations1, (uint32_t)playouts0,  \
+                       (uint32_t)playouts1, (uint32_t)max_plies, (uint32_t)explore, sample_plies, illegal_mode, counters, turn)
+    switch (tree_waves(n, wide)) {
+    case 4: GBL_CS(4); break;
+    case 2: GBL_CS(2); break;
+    default: GBL_CS(1); break;
+    }
+#undef GBL_CS
+    GBL_LAUNCHED("gbl_collect_search");
+}
+
+int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
+                        int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *stream)
+{
+    GBL_CHECK_N(n);
+    GBL_NEED(done_traj, "done_traj"); GBL_NEED(reward_traj, "reward_traj"); GBL_NEED(mover_traj, "mover_traj"); GBL_NEED(z_traj, "z_traj");
+    if (plies > 32767u) return fail(GBL_ERR_ARG, "plies must not exceed 32767");
+    if (plies == 0) return GBL_OK;
+    if (const int e = check_traj(n, plies, ply_stride, tile_stride, nullptr, nullptr, nullptr, reward_traj, 0, "", nullptr, nullptr)) return e;
+    if (reinterpret_cast<uintptr_t>(plies_left_traj) & 1u) return fail(GBL_ERR_ALIGN, "plies_left_traj must be 2-byte aligned");
+    const int64_t ntiles = (n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_outcome_targets, dim3((uint32_t)std::min<int64_t>(ntiles, 1 << 20)), dim3(64), 0, (hipStream_t)stream, done_traj,
+                       reward_traj, mover_traj, z_traj, plies_left_traj, n, ntiles, ply_stride, tile_stride, plies);
+    GBL_LAUNCHED("gbl_outcome_targets");
 }
 
 }  // extern "C"

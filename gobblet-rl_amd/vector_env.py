@@ -253,12 +253,17 @@ class BatchedGobblet:
 
     # -- trajectory collection: T plies per launch, every ply materialised -------------------------------------
     POLICIES = {"random": nat.POLICY_RANDOM, "greedy1": nat.POLICY_GREEDY1, "greedy": nat.POLICY_GREEDY2,
-                "greedy2": nat.POLICY_GREEDY2, "greedy3": nat.POLICY_GREEDY3}
+                "greedy2": nat.POLICY_GREEDY2, "greedy3": nat.POLICY_GREEDY3, "tree": nat.POLICY_TREE}
 
     def trajectory_buffers(self, plies: int, layout: str = "time", pad_boards: int | None = None,
                            placement: str = "auto", policy_outputs: bool = False, candidates: bool = False,
-                           far: bool | None = None) -> dict:
+                           far: bool | None = None, search_outputs: bool = False) -> dict:
         """Device tensors for ``collect``.
+
+        search_outputs: also "visits" (int16 (..., 54)), "value" / "nodes" (int32), "how" and "mover" (int8) for
+        ``collect(policies=(... "tree" ...), search=...)``: the root visit counts, value sum and node count of the search that
+        chose every ply's action, how it was arrived at (0 random, 3 the search's decision, 4 drawn in proportion to the visits)
+        and who played it.
 
         policy_outputs: also "chosen" (int32) and "how" (int8: 0 random ply, 1 greedy choice, 2 greedy fallback draw) for
         ``collect(policies=...)``; candidates: also "candidates" (int8 (..., 54): the greedy policy's ``actions_depth1``).
@@ -338,7 +343,9 @@ class BatchedGobblet:
                 placed["why"] = ("host memory" if dev.type != "cuda" else
                                  "arrays too small to probe" if self.observation is not None else "no observation stream")
         extra = ((("chosen", torch.int32, ()), ("how", torch.int8, ())) if policy_outputs else ()) + \
-                ((("candidates", torch.int8, (nat.ACTIONS,)),) if candidates else ())
+                ((("candidates", torch.int8, (nat.ACTIONS,)),) if candidates else ()) + \
+                ((("visits", torch.int16, (nat.ACTIONS,)), ("value", torch.int32, ()), ("nodes", torch.int32, ()),
+                  ("mover", torch.int8, ())) + ((("how", torch.int8, ()),) if not policy_outputs else ()) if search_outputs else ())
         for key, dtype, tail in (("actions", torch.int32, ()), ("winner", torch.int8, ()), ("rewards", torch.int8, (2,)),
                                  ("done", torch.int8, ()), ("to_move", torch.int8, ())) + extra:
             full[key] = torch.zeros(lead + tail, dtype=dtype, device=dev)
@@ -356,7 +363,8 @@ class BatchedGobblet:
         return v.reshape((v.shape[0] * 64,) + tuple(v.shape[2:]))[:n]
 
     def collect(self, plies: int, out: dict | None = None, count: bool = False, refresh: bool = True,
-                layout: str = "time", policies=None, opening_plies: int = 0, first_actions=None, first_status=None) -> dict:
+                layout: str = "time", policies=None, opening_plies: int = 0, first_actions=None, first_status=None,
+                search: dict | None = None) -> dict:
         """``plies`` masked-random plies with auto-reset in ONE launch (``gbl_collect``), EVERY ply materialised:
         entry t of the returned tensors -- "actions", "winner", "rewards", "done", "to_move", "action_mask",
         "observation", each (plies, N, ...) in the default time-major layout -- is what ``rollout(1)`` called ``plies``
@@ -389,21 +397,33 @@ class BatchedGobblet:
         and per-agent action history (``policy_hist``, int8 (N, 2, 3), kept across calls and across games like the
         reference's policy object; ``reset_policy_history()`` clears it).  ``opening_plies``: the first plies of every
         game are drawn at random by a greedy side too (tutorials/GreedyAgent/tutorial_greedy.py:34-41 uses 2; needs
-        ``track_turn=True``).  Buffers made with ``policy_outputs=True`` also receive "chosen" / "how" (/ "candidates")."""
+        ``track_turn=True``).  Buffers made with ``policy_outputs=True`` also receive "chosen" / "how" (/ "candidates").
+
+        A pair with "tree" (or a ``TreeSearchGobbletPolicy`` instance, which supplies its parameters) against "tree" or "random"
+        plays with the UCT tree search INSIDE the launch (``gbl_collect_search``): ``search=dict(iterations=, playouts=,
+        max_plies=, explore=, sample_plies=)`` -- ``iterations`` / ``playouts`` may each be a pair, one value per side;
+        ``sample_plies``: the first plies of every game (``turn < sample_plies``, needs ``track_turn=True``) are drawn in
+        proportion to the visits instead of taking the most visited action.  Ply t's search is exactly
+        ``gbl_tree_search(call = ply index)`` of the position.  The buffers (``trajectory_buffers(search_outputs=True)``) also
+        receive "visits" / "value" / "nodes" / "how" / "mover"; ``outcome_targets`` turns them into training targets.  The
+        greedy policies cannot be paired with "tree"."""
         if not self.auto_reset:
             raise ValueError("collect() plays with auto-reset; this environment was created with auto_reset=False")
         T = int(plies)
+        sp = self._search_params(policies, search)  # None unless a side plays the tree search
         if isinstance(out, str):
             if out != "fresh":
                 raise ValueError("out: a dict from trajectory_buffers(), None (the environment's staging buffers) or 'fresh'")
             # buffers of the caller's own: made (and placed) now, not kept by the environment, never overwritten by a later call
-            out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None, far=False)
+            out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
+                                          search_outputs=sp is not None, far=False)
         if out is None:
-            key = (T, layout, policies is not None)
+            key = (T, layout, policies is not None) + (("search",) if sp is not None else ())
             out = self._staging.pop(key, None)
             made = out is None
             if made:
-                out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None, far=False)
+                out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
+                                              search_outputs=sp is not None, far=False)
             # (buffers made inside a graph capture belong to the graph's private pool: not kept beyond it)
             capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
             if not (made and capturing):
@@ -426,7 +446,21 @@ class BatchedGobblet:
         first_status = self._i8_out(first_status, "first_status")
         if first_status is not None and fa is None:
             raise ValueError("first_status needs first_actions")
-        if policies is not None:
+        if sp is not None:
+            if sp["sample_plies"] and self.turn is None:
+                raise ValueError("sample_plies needs the per-board turn counter: create the environment with track_turn=True")
+            if opening_plies:
+                raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
+            nat.check(self._lib.gbl_collect_search(
+                self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
+                f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
+                f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
+                nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")), n,
+                out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T,
+                *sp["policies"], *sp["iterations"], *sp["playouts"], sp["max_plies"], sp["explore"], sp["sample_plies"],
+                self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream()),
+                "gbl_collect_search")
+        elif policies is not None:
             try:
                 p0, p1 = (self.POLICIES[x] if isinstance(x, str) else int(x) for x in policies)
             except (KeyError, ValueError, TypeError):
@@ -462,6 +496,69 @@ class BatchedGobblet:
         if self.observation is not None:
             self.observation.copy_(self._last_ply(out, "observation"))
         return out
+
+    def _search_params(self, policies, search):
+        """The arguments of ``gbl_collect_search`` when a side of ``policies`` plays the tree search, else None."""
+        from .tree_policy import TreeSearchGobbletPolicy
+        if policies is None or isinstance(policies, str):
+            if search is not None:
+                raise ValueError("search= belongs to policies with a 'tree' side")
+            return None
+        sides = list(policies)
+        trees = [isinstance(x, TreeSearchGobbletPolicy) or x == "tree" or (not isinstance(x, str) and x == nat.POLICY_TREE) for x in sides]
+        if len(sides) != 2 or not any(trees):
+            if search is not None:
+                raise ValueError("search= belongs to policies with a 'tree' side")
+            return None
+        kw = dict(iterations=256, playouts=16, max_plies=64, explore=16, sample_plies=0)  # TreeSearchGobbletPolicy's defaults
+        unknown = set(search or ()) - set(kw)
+        if unknown:
+            raise ValueError("search: unknown keys %s" % sorted(unknown))
+        kw.update(search or {})
+        pair = lambda v: tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v), int(v))  # noqa: E731
+        its, pls = list(pair(kw["iterations"])), list(pair(kw["playouts"]))
+        if len(its) != 2 or len(pls) != 2:
+            raise ValueError("search: iterations / playouts are a value or a pair, one value per side")
+        codes = []
+        for m, x in enumerate(sides):
+            if isinstance(x, TreeSearchGobbletPolicy):
+                its[m], pls[m] = x.iterations, x.playouts
+                if search is None or "max_plies" not in search:
+                    kw["max_plies"] = x.max_plies
+                if search is None or "explore" not in search:
+                    kw["explore"] = x.explore
+                codes.append(nat.POLICY_TREE)
+            elif trees[m]:
+                codes.append(nat.POLICY_TREE)
+            elif x == "random" or (not isinstance(x, str) and x == nat.POLICY_RANDOM):
+                codes.append(nat.POLICY_RANDOM)
+            else:
+                raise ValueError("policies: the tree search plays against 'tree' or 'random' (not %r)" % (x,))
+        for m in range(2):
+            if codes[m] == nat.POLICY_TREE and not (1 <= its[m] <= 1024 and 1 <= pls[m] <= 256):
+                raise ValueError("search: iterations must be in [1, 1024] and playouts in [1, 256]")
+        if not (0 <= int(kw["max_plies"]) <= 255 and 0 <= int(kw["explore"]) <= 1024 and int(kw["sample_plies"]) >= 0):
+            raise ValueError("search: max_plies must be in [0, 255], explore in [0, 1024], sample_plies >= 0")
+        return dict(policies=codes, iterations=its, playouts=pls, max_plies=int(kw["max_plies"]), explore=int(kw["explore"]),
+                    sample_plies=int(kw["sample_plies"]))
+
+    def outcome_targets(self, traj: dict) -> dict:
+        """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128
+        where the game does not end inside the window) and "plies_left" (int16: plies until that end, -1 likewise) to a
+        trajectory collected with ``search_outputs`` ("mover" is needed): the value targets of an AlphaZero-style trainer, one
+        launch of ``gbl_outcome_targets``.  Returns ``traj``."""
+        f, n = traj["_full"], self.num_envs
+        if "mover" not in f:
+            raise ValueError("outcome_targets needs the 'mover' entry: buffers from trajectory_buffers(search_outputs=True)")
+        if "z" not in f:
+            f["z"] = torch.full_like(f["done"], nat.Z_OPEN)
+            f["plies_left"] = torch.full(f["done"].shape, -1, dtype=torch.int16, device=f["done"].device)
+            for k in ("z", "plies_left"):
+                traj[k] = f[k][:, :n] if traj["_layout"] == "time" else f[k]
+        nat.check(self._lib.gbl_outcome_targets(f["done"].data_ptr(), f["rewards"].data_ptr(), f["mover"].data_ptr(),
+                                                f["z"].data_ptr(), f["plies_left"].data_ptr(), n, traj["_ply_stride"],
+                                                traj["_tile_stride"], traj["_plies"], self._stream()), "gbl_outcome_targets")
+        return traj
 
     def release_staging(self) -> None:
         """Drop the trajectory buffers ``collect()`` keeps for calls without ``out`` (their blocks go back to the driver

@@ -387,6 +387,52 @@ int gbl_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *his
                        const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, int opening_plies,
                        int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
 
+/* Search-driven self-play collection (no counterpart in the reference: the data generator of an AlphaZero-style trainer).
+ * gbl_collect with the mover's action chosen inside the launch by a per-side policy, and every ply's search kept:
+ *   policy0 / policy1  how player_1 / player_2 decide: GBL_POLICY_RANDOM or GBL_POLICY_TREE.  The greedy policies and flat
+ *                      Monte-Carlo are out of scope here (GBL_ERR_ARG); gbl_collect_policy in turn rejects GBL_POLICY_TREE.
+ * Per board g = env_base + b, for t = 0 .. plies-1, ply index q = ply0 + t (+ *ply_dev), mover m:
+ *   RANDOM  the gbl_sample rule on generator stream 0 with ply index q, exactly as gbl_collect.
+ *   TREE    the search is exactly gbl_tree_search(state, to_move, mask = NULL, iterations_m, playouts_m, max_plies, explore, seed,
+ *           env_base, call = q) of the board's current position (the same rule text, the same draws on stream 3), and the action
+ *           is that search's action_out -- except while turn[b] < sample_plies, where the action is drawn in proportion to the
+ *           visits: S = the sum of visits_out, r = the generator word of (seed, g, q, stream 4), k = (r * S) >> 32, and the
+ *           lowest action whose running sum of visits exceeds k.  sample_plies > 0 needs `turn`.  A root without a candidate gives
+ *           action -1, which is stepped as gbl_step steps an illegal action (per illegal_mode).
+ *   then    gbl_step with auto-reset and illegal_mode, as in gbl_collect.
+ * Ply t of board b leaves in cell(t, b) (see gbl_collect; both layouts) the seven arrays of gbl_collect, and (every pointer may be NULL)
+ *   visits_traj int16[cells][54]  visits_out of the search that chose the action of ply t; zeros where RANDOM moved
+ *   value_traj  int32[cells]      the sum over the actions of wins_out - losses_out of that search, from the mover's side (the games
+ *                                 behind it: S * playouts_m); 0 where RANDOM moved
+ *   nodes_traj  int32[cells]      that search's nodes_out; 0 where RANDOM moved
+ *   how_traj    int8 [cells]      GBL_HOW_RANDOM, GBL_HOW_SEARCH (the search's decision) or GBL_HOW_SEARCH_SAMPLED (the draw)
+ *   mover_traj  int8 [cells]      the agent who played ply t
+ * The limits of iterations / playouts / max_plies / explore / env_base are those of gbl_tree_search (a RANDOM side's pair is
+ * ignored), sample_plies >= 0, and ply0 + plies <= 2^24 because `call` has 24 bits (with ply_dev the caller
+ * keeps the sum below it).  state / to_move / done / turn / counters / ply_dev and the strides as gbl_collect; the state rows are
+ * rebuilt from bit planes on return (see the contract on `state` above).  Allocates nothing; the tree lives in
+ * 16 (max(iterations0, iterations1) + 1) bytes of LDS per workgroup and is rebuilt from an empty root on every ply. */
+#define GBL_POLICY_TREE 4
+#define GBL_HOW_SEARCH 3
+#define GBL_HOW_SEARCH_SAMPLED 4
+int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                       int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                       int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                       int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                       const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, int iterations0, int iterations1,
+                       int playouts0, int playouts1, int max_plies, int explore, int sample_plies, int illegal_mode,
+                       int64_t *counters, int32_t *turn, void *stream);
+
+/* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
+ * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:
+ *   z_traj          int8 [cells]  reward_traj[cell(e, b)][mover_traj[cell(t, b)]] -- the reward, not the winner, so that
+ *                                 GBL_ILLEGAL_TERMINATE's -1 comes out right; GBL_Z_OPEN where no game end lies in the window
+ *   plies_left_traj int16[cells]  e - t, or -1 where no game end lies in the window (may be NULL)
+ * done_traj / reward_traj / mover_traj / z_traj are required; strides and cells as gbl_collect; plies <= 32767. */
+#define GBL_Z_OPEN (-128)
+int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
+                        int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *stream);
+
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
  *   GBL_COLLECT_STREAM  k_collect,  one wavefront per tile of 64 boards, trajectory rows stored non-temporally
