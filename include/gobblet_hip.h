@@ -282,7 +282,9 @@ int gbl_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8_t *
  *   plies_out  int32[n]     : plies played over all of b's playouts, the root moves included
  * pid does not depend on `playouts`, so the counts are non-decreasing in it, and a shard (env_base) of a batch gets its
  * boards' results.  1 <= playouts <= 4096, 0 <= max_plies <= 255, call < 2^24, env_base + n <= 2^42; states must be
- * contract states (gbl_validate).  Allocates nothing. */
+ * contract states (gbl_validate).  state / to_move / mask are read a byte at a time and need NO alignment here (the
+ * 16-byte rule above is for the entry points that move whole rows); the outputs must be 4-byte aligned (GBL_ERR_ALIGN).
+ * to_move and mask count as set wherever they are non-zero.  Allocates nothing. */
 int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
                        uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
                        int32_t *action_out, int32_t *plies_out, int64_t n, void *stream);
@@ -321,6 +323,8 @@ int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t 
  * pid does not depend on `iterations`: a search is the beginning of every longer one, so nodes_out and the sum of visits_out do
  * not decrease with it, and a shard (env_base) of a batch gets its boards' results.  1 <= iterations <= 1024, 1 <= playouts <= 256,
  * 0 <= max_plies <= 255, 0 <= explore <= 1024, call < 2^24, env_base + n <= 2^42; states must be contract states (gbl_validate).
+ * state / to_move / mask are read a byte at a time and need NO alignment here (as gbl_playout_values); the outputs must be 4-byte
+ * aligned (GBL_ERR_ALIGN).  to_move and mask count as set wherever they are non-zero.
  * Allocates nothing; the tree lives in 16 (iterations + 1) bytes of LDS per workgroup. */
 int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
                     int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,

@@ -176,3 +176,55 @@ def greedy_vroot_rule(state, to_move, mask=None, cap=6):
     lib().emu_greedy_vroot_rule(_p(np.ascontiguousarray(state)), _p(np.ascontiguousarray(to_move)),
                                 _p(np.ascontiguousarray(mask)) if mask is not None else None, len(state), int(cap), _p(o))
     return tuple(int(x) for x in o)
+
+
+# ---- the integer helpers of gbl_tree_search / gbl_collect_search (gobblet_device.h), array in / array out ----
+def _u32(a):
+    return np.ascontiguousarray(a, np.uint32)
+
+
+def tree_isqrt(x):
+    x = _u32(x); out = np.zeros(len(x), np.uint32)
+    lib().emu_tree_isqrt(_p(x), _p(out), C.c_int64(len(x))); return out
+
+
+def tree_isqrt_range(x0, count):
+    """tree_isqrt of x0, x0 + 1, ..., x0 + count - 1."""
+    out = np.zeros(count, np.uint32)
+    lib().emu_tree_isqrt_range(C.c_uint32(x0), _p(out), C.c_int64(count)); return out
+
+
+def tree_key(W, L, n, P, n_parent, explore):
+    a = [_u32(v) for v in (W, L, n, P, n_parent, explore)]
+    out = np.zeros(len(a[0]), np.uint32)
+    assert all(len(v) == len(out) for v in a)
+    lib().emu_tree_key(*[_p(v) for v in a], _p(out), C.c_int64(len(out))); return out
+
+
+def tree_order_key(key, action):
+    key, action = _u32(key), _u32(action); out = np.zeros(len(key), np.uint32)
+    lib().emu_tree_order_key(_p(key), _p(action), _p(out), C.c_int64(len(key))); return out
+
+
+def tree_final_key(n, W, L, action):
+    a = [_u32(v) for v in (n, W, L, action)]
+    out = np.zeros(len(a[0]), np.uint64)
+    lib().emu_tree_final_key(*[_p(v) for v in a], _p(out), C.c_int64(len(out))); return out
+
+
+def tree_action_of(key):
+    key = np.ascontiguousarray(key, np.uint64); out = np.full(len(key), 77, np.int32)
+    lib().emu_tree_action_of(_p(key), _p(out), C.c_int64(len(key))); return out
+
+
+def visits_pick(visits, r):
+    """visits (m, 54) int32, r (m,) uint32 -> the drawn action per row (-1 where nothing was visited)."""
+    visits, r = np.ascontiguousarray(visits, np.int32), _u32(r)
+    assert visits.shape == (len(r), 54)
+    out = np.full(len(r), 77, np.int32)
+    lib().emu_visits_pick(_p(visits), _p(r), _p(out), C.c_int64(len(r))); return out
+
+
+def tree_pid(g, i, j):
+    g, i, j = np.ascontiguousarray(g, np.uint64), _u32(i), _u32(j); out = np.zeros(len(g), np.uint64)
+    lib().emu_tree_pid(_p(g), _p(i), _p(j), _p(out), C.c_int64(len(g))); return out

@@ -765,4 +765,51 @@ void emu_greedy(const int8_t *state, const int8_t *to_move, const int8_t *mask_i
     });
 }
 
+// ---- the integer helpers of gbl_tree_search / gbl_collect_search, array in / array out (tests/test_tree_arith.py) ----
+void emu_tree_isqrt(const uint32_t *x, uint32_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_isqrt(x[i]);
+}
+
+// tree_isqrt over the whole range [x0, x0 + n) without an input array
+void emu_tree_isqrt_range(uint32_t x0, uint32_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_isqrt(x0 + (uint32_t)i);
+}
+
+void emu_tree_key(const uint32_t *W, const uint32_t *L, const uint32_t *nv, const uint32_t *P, const uint32_t *np, const uint32_t *explore,
+                  uint32_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_key(W[i], L[i], nv[i], P[i], np[i], explore[i]);
+}
+
+void emu_tree_order_key(const uint32_t *key, const uint32_t *a, uint32_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_order_key(key[i], a[i]);
+}
+
+void emu_tree_final_key(const uint32_t *nv, const uint32_t *W, const uint32_t *L, const uint32_t *a, uint64_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_final_key(nv[i], W[i], L[i], a[i]);
+}
+
+void emu_tree_action_of(const uint64_t *key, int32_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_action_of(key[i]);
+}
+
+void emu_visits_pick(const int32_t *visits, const uint32_t *r, int32_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        int32_t row[kActions];
+        memcpy(row, visits + i * kActions, sizeof(row));
+        out[i] = visits_pick(row, r[i]);
+    }
+}
+
+void emu_tree_pid(const uint64_t *g, const uint32_t *it, const uint32_t *j, uint64_t *out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = tree_pid(g[i], it[i], j[i]);
+}
+
 }  // extern "C"
