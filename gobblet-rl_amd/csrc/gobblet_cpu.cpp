@@ -137,15 +137,6 @@ void add_tally(int64_t *counters, const Tally &t)  // (stripe 0: the totals are 
     c[0] += t.plies; c[1] += t.games; c[2] += t.w1; c[3] += t.w2;
 }
 
-bool strides_ok(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
-{
-    const int64_t tiles = (n + kTile - 1) / kTile;
-    const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
-    const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
-    const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
-    return aligned && (time_major || tile_major);
-}
-
 inline int64_t cell_of(int64_t b, uint32_t t, int64_t ply_stride, int64_t tile_stride)
 {
     return (int64_t)t * ply_stride + (b / kTile) * tile_stride + (b % kTile);
@@ -511,8 +502,7 @@ int gbl_cpu_collect_from_ex(int8_t *state, int8_t *to_move, int8_t *done, const 
     if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
         return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
     if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride))
-        return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     if (ply_dev) ply0 += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         Tally tl;
@@ -642,9 +632,9 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
     if (playouts < 1 || playouts > 4096) return fail(GBL_ERR_ARG, "playouts must be in [1, 4096]");
-    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (const char *why = playout_limits_error(max_plies)) return fail(GBL_ERR_ARG, why);
     if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is playouts x ~30 whole games: every board is worth a thread)
@@ -722,12 +712,10 @@ int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t
                         int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (iterations < 1 || iterations > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
-    if (playouts < 1 || playouts > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
-    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
-    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (const char *why = tree_budget_error(iterations, playouts)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
     if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
@@ -769,8 +757,7 @@ int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t 
     if (opening_plies < 0) return fail(GBL_ERR_ARG, "opening_plies < 0");
     if (opening_plies > 0 && !turn) return fail(GBL_ERR_ARG, "opening_plies > 0 needs the per-board turn counter (turn must not be NULL)");
     if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride))
-        return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     if (ply_dev) ply0 += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         Tally tl;
@@ -847,20 +834,17 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
     const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
     for (int m = 0; m < 2; ++m) {
         if (pol[m] != GBL_POLICY_TREE) continue;
-        if (its[m] < 1 || its[m] > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
-        if (pls[m] < 1 || pls[m] > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
+        if (const char *why = tree_budget_error(its[m], pls[m])) return fail(GBL_ERR_ARG, why);
     }
-    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
-    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
     if (sample_plies < 0) return fail(GBL_ERR_ARG, "sample_plies < 0");
     if (sample_plies > 0 && !turn) return fail(GBL_ERR_ARG, "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)");
     if ((uint64_t)ply0 + plies > (1ull << 24)) return fail(GBL_ERR_ARG, "ply0 + plies must not exceed 2^24 (the search's call index)");
-    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride))
-        return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     if (ply_dev) ply0 += *ply_dev;
     const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
@@ -932,8 +916,7 @@ int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, 
     GBL_NEED(done_traj, "done_traj"); GBL_NEED(reward_traj, "reward_traj"); GBL_NEED(mover_traj, "mover_traj"); GBL_NEED(z_traj, "z_traj");
     if (plies > 32767u) return fail(GBL_ERR_ARG, "plies must not exceed 32767");
     if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride))
-        return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) {
             int r0 = 0, r1 = 0, left = -1;  // the rewards of the nearest game end at or after t, and how far it is

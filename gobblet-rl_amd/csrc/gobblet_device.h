@@ -2022,4 +2022,36 @@ __device__ __forceinline__ int visits_pick(const int32_t (&visits)[kActions], ui
     return -1;
 }
 
+// ---- argument checks of the search entry points and the trajectory strides: host code, for both flavours of the ABI ----------
+// Each *_error returns the message of the first rule the arguments break, or nullptr; a flavour passes it to its own fail().
+inline const char *tree_budget_error(int iterations, int playouts)
+{
+    if (iterations < 1 || iterations > kTreeMaxIterations) return "iterations must be in [1, 1024]";
+    if (playouts < 1 || playouts > kTreeMaxPlayouts) return "playouts must be in [1, 256]";
+    return nullptr;
+}
+
+inline const char *playout_limits_error(int max_plies, int explore = 0)  // (gbl_playout_values has no explore)
+{
+    if (max_plies < 0 || max_plies > 255) return "max_plies must be in [0, 255]";
+    if (explore < 0 || explore > kTreeMaxExplore) return "explore must be in [0, 1024]";
+    return nullptr;
+}
+
+inline const char *env_range_error(uint64_t env_base, int64_t n)  // (n >= 0)
+{
+    return env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base ? "env_base + n must not exceed 2^42" : nullptr;
+}
+
+// The (ply, tile) cells of 64 boards of a trajectory must start 16-byte aligned and must not overlap.
+inline bool strides_ok(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
+{
+    const int64_t tiles = (n + kTile - 1) / kTile;
+    const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
+    const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
+    const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
+    return aligned && (time_major || tile_major);
+}
+constexpr const char *kStridesMessage = "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart";
+
 }  // namespace gbl

@@ -1630,6 +1630,43 @@ __global__ __launch_bounds__(64) void k_validate(const int8_t *__restrict__ stat
     flags[L.b] = (int8_t)validate_row(r);
 }
 
+// ---- the search kernels (k_playout, k_tree, k_collect_search): what they share ----------------------------------------------------
+__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+// Butterfly reductions over the wavefront: every lane returns with the full result.
+template <typename T>
+__device__ __forceinline__ T wave_max(T x)  // (T: uint32_t or uint64_t)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const T other = __shfl_xor(x, o);
+        x = other > x ? other : x;
+    }
+    return x;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x)  // (a signed sum goes through a cast: two's complement, the same bits)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o);
+    return x;
+}
+
+// Board b's planes in every lane: lane c < 27 reads cell c, and three ballots are the planes.
+__device__ __forceinline__ Planes board_planes(const int8_t *__restrict__ state, int64_t b, uint32_t lane)
+{
+    const int v = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
+    return Planes{(uint32_t)__ballot(v != 0), (uint32_t)__ballot(v < 0), (uint32_t)__ballot(v & 1)};
+}
+
+// ... and the candidates of its search: the mover's legal actions, less those whose byte of the board's `mask` row (optional) is zero
+__device__ __forceinline__ uint64_t board_candidates(const Planes &p, int mover, const int8_t *__restrict__ mask, int64_t b, uint32_t lane)
+{
+    uint64_t cand = legal54(p, mover);
+    if (mask) cand &= (uint64_t)__ballot(lane < (uint32_t)kActions && mask[b * kActions + lane] != 0);
+    return cand;
+}
+
 // gbl_playout_values: flat Monte-Carlo values.  One workgroup of W wavefronts per board (a grid-stride loop over boards).  The
 // root position stays in registers (lane c < 27 reads cell c, and three ballots are its planes); the (candidate rank, k) work
 // items are dealt round-robin to the 64 W lanes, item i = rank * K + k.  A lane plays its playout in quanta of four plies that
@@ -1649,11 +1686,9 @@ __global__ __launch_bounds__(64 * W) void k_playout(const int8_t *__restrict__ s
     for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
         for (uint32_t j = tid; j < (uint32_t)kActions; j += 64u * W) s_win[j] = s_loss[j] = 0u;
         if (tid == 0) s_plies = 0u;
-        const int v = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
-        const Planes root{(uint32_t)__ballot(v != 0), (uint32_t)__ballot(v < 0), (uint32_t)__ballot(v & 1)};
+        const Planes root = board_planes(state, b, lane);
         const int mover = to_move[b] != 0;
-        uint64_t cand = legal54(root, mover);
-        if (mask) cand &= (uint64_t)__ballot(lane < (uint32_t)kActions && mask[b * kActions + lane] != 0);
+        const uint64_t cand = board_candidates(root, mover, mask, b, lane);
         const uint32_t total = (uint32_t)__popcll(cand) * K;
         __syncthreads();  // (counters zeroed)
 
@@ -1695,12 +1730,7 @@ __global__ __launch_bounds__(64 * W) void k_playout(const int8_t *__restrict__ s
             const int w = in ? (int)s_win[lane] : 0, l = in ? (int)s_loss[lane] : 0;
             if (wins_out && in) wins_out[b * kActions + lane] = w;
             if (losses_out && in) losses_out[b * kActions + lane] = l;
-            uint32_t key = in && ((cand >> lane) & 1ull) ? playout_key(w, l, (int)lane) : 0u;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const uint32_t other = (uint32_t)__shfl_xor((int)key, o);
-                key = other > key ? other : key;
-            }
+            const uint32_t key = wave_max(in && ((cand >> lane) & 1ull) ? playout_key(w, l, (int)lane) : 0u);
             if (lane == 0) {
                 if (action_out) action_out[b] = playout_action_of(key);
                 if (plies_out) plies_out[b] = (int32_t)s_plies;
@@ -1720,9 +1750,9 @@ int playout_waves(int64_t n, int playouts)
     return w;
 }
 
-// gbl_tree_search: leaf-parallel UCT.  One workgroup of W wavefronts per board (a grid-stride loop over boards); the tree is an
-// array of 16-byte nodes in dynamic LDS, 16 (iterations + 1) bytes, and the root planes stay in registers as in k_playout.  An
-// iteration:
+// The iterations of one board's search, for k_tree and k_collect_search: every thread of the board's W wavefronts calls it.  On entry
+// the root node and the sums are zeroed and a barrier has passed; on return the tree is written and a barrier has passed.  count
+// (1 on entry) and plies_total (0) count the nodes created and the masked-random plies played.  An iteration:
 //   select   every wavefront walks the same path (the tree is only read): the child list of a node once, with broadcast LDS reads
 //            -- lane a keeps the statistics of the child of action a -- then all lanes compute their key and a butterfly max picks
 //            the child; one move_planes per level replays the position;
@@ -1731,168 +1761,6 @@ int playout_waves(int64_t n, int playouts)
 //            << 16 and the plies are summed over the wavefront by butterflies and, for W > 1, over the workgroup in LDS counters
 //            (two sets, used by alternate iterations, so that zeroing one never races with the adds of the next iteration);
 //   back up  thread 0 links the new node and walks to the root, between two barriers.
-template <int W>
-__global__ __launch_bounds__(64 * W) void k_tree(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
-                                                 const int8_t *__restrict__ mask, int32_t *__restrict__ visits_out,
-                                                 int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
-                                                 int32_t *__restrict__ action_out, int32_t *__restrict__ nodes_out,
-                                                 int32_t *__restrict__ plies_out, int64_t n, uint64_t seed, uint64_t env_base,
-                                                 uint32_t call, uint32_t iterations, uint32_t P, uint32_t max_plies, uint32_t explore)
-{
-    extern __shared__ uint4 s_tree[];
-    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
-    __shared__ uint32_t s_sum[2][2];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
-        if (tid == 0) nodes[0] = TreeNode{};
-        if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
-        const int v0 = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
-        const Planes root{(uint32_t)__ballot(v0 != 0), (uint32_t)__ballot(v0 < 0), (uint32_t)__ballot(v0 & 1)};
-        const int mover = to_move[b] != 0;
-        uint64_t cand = legal54(root, mover);
-        if (mask) cand &= (uint64_t)__ballot(lane < (uint32_t)kActions && mask[b * kActions + lane] != 0);
-        const uint64_t g = env_base + (uint64_t)b;
-        __syncthreads();  // (root and counters zeroed)
-
-        uint32_t count = 1, plies_total = 0;
-        for (uint32_t i = 0; cand && i < iterations; ++i) {
-            // 1. select
-            uint32_t v = 0, term;
-            Planes p = root;
-            int side = mover;
-            uint64_t cd = cand, untried = 0;
-            for (;;) {
-                const TreeNode nv = nodes[v];
-                term = tree_term(nv);
-                if (term) break;
-                uint64_t have = 0;
-                uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
-                for (uint32_t c = nv.child; c;) {
-                    const TreeNode k = nodes[c];
-                    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)tree_action(k));
-                    have |= 1ull << a;
-                    if (lane == a) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
-                    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
-                }
-                untried = cd & ~have;
-                if (untried) break;
-                uint32_t key = my_c ? tree_order_key(tree_key(my_w, my_l, my_n, P, nv.n, explore), lane) : 0u;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) {
-                    const uint32_t other = (uint32_t)__shfl_xor((int)key, o);
-                    key = other > key ? other : key;
-                }
-                const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
-                v = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a);
-                move_planes(p, side, a);
-                side ^= 1;
-                cd = legal54(p, side);
-            }
-            // 2. expand (the position and what the move decided; the node is linked below)
-            const bool grow = term == kTreeOpen;
-            uint32_t a_new = 0;
-            if (grow) a_new = tree_expand_move(p, side, untried, draw32(seed, tree_pid(g, i, 0), playout_ply_index(call, 0), kStreamTree), term);
-            // 3. evaluate
-            uint32_t wl = 0, pl = 0;
-            if (term == kTreeOpen) {
-                uint32_t j = tid, t = 0;
-                Planes q = p;
-                int s = side;
-                uint64_t pid = 0;
-                bool fresh = true;
-                while (j < P) {
-                    if (fresh) {
-                        pid = tree_pid(g, i, j);
-                        q = p;
-                        s = side;
-                        t = 0;
-                        fresh = false;
-                    }
-                    const Draw4 d = draw_block(seed, pid, playout_ply_index(call, t), kStreamTree);  // (t % 4 == 0 here)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (!fresh) {
-                            const PlayoutEnd e = tree_playout_ply(q, s, side, t, d.w[u], max_plies);
-                            ++t;
-                            if (e.done) {
-                                pl += e.plies;
-                                wl += e.outcome > 0 ? 1u : (e.outcome < 0 ? 1u << 16 : 0u);
-                                j += 64u * W;
-                                fresh = true;
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) {
-                    wl += (uint32_t)__shfl_xor((int)wl, o);
-                    pl += (uint32_t)__shfl_xor((int)pl, o);
-                }
-                if (W > 1 && lane == 0) {
-                    atomicAdd(&s_sum[i & 1u][0], wl);
-                    atomicAdd(&s_sum[i & 1u][1], pl);
-                }
-            }
-            __syncthreads();  // (every wavefront has read the tree; the sums are complete)
-            if (W > 1 && term == kTreeOpen) {
-                wl = s_sum[i & 1u][0];
-                pl = s_sum[i & 1u][1];
-            }
-            if (term != kTreeOpen) wl = tree_decided(term, P);
-            plies_total += pl;
-            // 4. back up
-            if (tid == 0) {
-                if (W > 1) s_sum[(i & 1u) ^ 1u][0] = s_sum[(i & 1u) ^ 1u][1] = 0u;  // (last read before the previous iteration's second barrier)
-                uint32_t leaf = v;
-                if (grow) tree_link(nodes, leaf = count, v, a_new, term);
-                tree_backup(nodes, leaf, wl & 0xFFFFu, wl >> 16);
-            }
-            count += grow ? 1u : 0u;
-            __syncthreads();  // (the tree is written)
-        }
-
-        if (tid < 64u) {  // wavefront 0: the root's children out, and the decision
-            uint32_t my_n = 0, my_w = 0, my_l = 0;
-            bool mine = false;
-            for (uint32_t c = nodes[0].child; c;) {
-                const TreeNode k = nodes[c];
-                if (lane == tree_action(k)) mine = true, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
-                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
-            }
-            if (lane < (uint32_t)kActions) {
-                if (visits_out) visits_out[b * kActions + lane] = (int32_t)my_n;
-                if (wins_out) wins_out[b * kActions + lane] = (int32_t)my_w;
-                if (losses_out) losses_out[b * kActions + lane] = (int32_t)my_l;
-            }
-            uint64_t key = mine ? tree_final_key(my_n, my_w, my_l, lane) : 0ull;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const uint64_t other = (uint64_t)__shfl_xor((unsigned long long)key, o);
-                key = other > key ? other : key;
-            }
-            if (lane == 0) {
-                if (action_out) action_out[b] = tree_action_of(key);
-                if (nodes_out) nodes_out[b] = (int32_t)count;
-                if (plies_out) plies_out[b] = (int32_t)plies_total;
-            }
-        }
-        __syncthreads();  // (before the next board rewrites the root)
-    }
-}
-
-// Wavefronts per board of k_tree: a leaf has only `playouts` games to deal, so more than playouts / 64 wavefronts would idle, and
-// one is enough once the batch alone gives every SIMD eight wavefronts (8 192 boards).
-int tree_waves(int64_t n, int playouts)
-{
-    int w = 1;
-    while (w < 4 && n * (2 * w) <= 8192 && 64 * (2 * w) <= playouts) w *= 2;
-    return w;
-}
-
-// The iterations of one board's search for k_collect_search: k_tree's loop, word for word, as a function (on entry the root node and
-// the sums are zeroed and a barrier has passed; on return the tree is written and a barrier has passed; count, 1 on entry, and
-// plies_total, 0, count the nodes created and the masked-random plies played).  A COPY: with k_tree calling it the compiler orders
-// k_tree<W>'s operands and registers differently, and the existing kernels' code stays as measured.
 template <int W>
 __device__ __forceinline__ void tree_iterations(TreeNode *const nodes, uint32_t (&s_sum)[2][2], const Planes &root, const int mover,
                                                 const uint64_t cand, const uint64_t g, const uint64_t seed, const uint32_t call,
@@ -1921,12 +1789,7 @@ __device__ __forceinline__ void tree_iterations(TreeNode *const nodes, uint32_t 
             }
             untried = cd & ~have;
             if (untried) break;
-            uint32_t key = my_c ? tree_order_key(tree_key(my_w, my_l, my_n, P, nv.n, explore), lane) : 0u;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const uint32_t other = (uint32_t)__shfl_xor((int)key, o);
-                key = other > key ? other : key;
-            }
+            const uint32_t key = wave_max(my_c ? tree_order_key(tree_key(my_w, my_l, my_n, P, nv.n, explore), lane) : 0u);
             const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
             v = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a);
             move_planes(p, side, a);
@@ -1968,11 +1831,8 @@ __device__ __forceinline__ void tree_iterations(TreeNode *const nodes, uint32_t 
                     }
                 }
             }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                wl += (uint32_t)__shfl_xor((int)wl, o);
-                pl += (uint32_t)__shfl_xor((int)pl, o);
-            }
+            wl = wave_sum(wl);
+            pl = wave_sum(pl);
             if (W > 1 && lane == 0) {
                 atomicAdd(&s_sum[i & 1u][0], wl);
                 atomicAdd(&s_sum[i & 1u][1], pl);
@@ -2014,6 +1874,58 @@ __device__ __forceinline__ TreeRootChild tree_root_child(const TreeNode *nodes, 
     return r;
 }
 
+// gbl_tree_search: leaf-parallel UCT.  One workgroup of W wavefronts per board (a grid-stride loop over boards); the tree is an
+// array of 16-byte nodes in dynamic LDS, 16 (iterations + 1) bytes, and the root planes stay in registers as in k_playout.  The
+// search is tree_iterations; wavefront 0 then writes the root's children out and decides.
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_tree(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                                 const int8_t *__restrict__ mask, int32_t *__restrict__ visits_out,
+                                                 int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
+                                                 int32_t *__restrict__ action_out, int32_t *__restrict__ nodes_out,
+                                                 int32_t *__restrict__ plies_out, int64_t n, uint64_t seed, uint64_t env_base,
+                                                 uint32_t call, uint32_t iterations, uint32_t P, uint32_t max_plies, uint32_t explore)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    __shared__ uint32_t s_sum[2][2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        if (tid == 0) nodes[0] = TreeNode{};
+        if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
+        const Planes root = board_planes(state, b, lane);
+        const int mover = to_move[b] != 0;
+        const uint64_t cand = board_candidates(root, mover, mask, b, lane);
+        __syncthreads();  // (root and counters zeroed)
+        uint32_t count = 1, plies_total = 0;
+        tree_iterations<W>(nodes, s_sum, root, mover, cand, env_base + (uint64_t)b, seed, call, iterations, P, max_plies, explore, tid, lane,
+                           count, plies_total);
+        if (tid < 64u) {  // wavefront 0: the root's children out, and the decision
+            const TreeRootChild c = tree_root_child(nodes, lane);
+            if (lane < (uint32_t)kActions) {
+                if (visits_out) visits_out[b * kActions + lane] = (int32_t)c.n;
+                if (wins_out) wins_out[b * kActions + lane] = (int32_t)c.w;
+                if (losses_out) losses_out[b * kActions + lane] = (int32_t)c.l;
+            }
+            const uint64_t key = wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull);
+            if (lane == 0) {
+                if (action_out) action_out[b] = tree_action_of(key);
+                if (nodes_out) nodes_out[b] = (int32_t)count;
+                if (plies_out) plies_out[b] = (int32_t)plies_total;
+            }
+        }
+        __syncthreads();  // (before the next board rewrites the root)
+    }
+}
+
+// Wavefronts per board of k_tree: a leaf has only `playouts` games to deal, so more than playouts / 64 wavefronts would idle, and
+// one is enough once the batch alone gives every SIMD eight wavefronts (8 192 boards).
+int tree_waves(int64_t n, int playouts)
+{
+    int w = 1;
+    while (w < 4 && n * (2 * w) <= 8192 && 64 * (2 * w) <= playouts) w *= 2;
+    return w;
+}
+
 // gbl_collect_search: whole games with the tree search on either or both sides, every ply materialised.  One workgroup of W
 // wavefronts per board (a grid-stride loop over boards) with the ply loop INSIDE: a board whose search walks into decided nodes
 // and plays nothing goes on to its next ply while its neighbours still play iterations x playouts games -- no ply of any board
@@ -2035,8 +1947,6 @@ struct SearchTraj {
     int8_t *how, *mover;
 };
 
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                            uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
@@ -2053,8 +1963,7 @@ __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (ply_dev) ply0 += *ply_dev;
     for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
-        const int v0 = lane < (uint32_t)kCells ? state[b * kCells + lane] : 0;
-        Planes p{(uint32_t)__ballot(v0 != 0), (uint32_t)__ballot(v0 < 0), (uint32_t)__ballot(v0 & 1)};
+        Planes p = board_planes(state, b, lane);
         int mover = to_move[b] != 0, tabs = turn ? turn[b] : 0, dn = 0;
         uint32_t games = 0, w1 = 0, w2 = 0;
         const uint64_t g = env_base + (uint64_t)b;
@@ -2076,15 +1985,8 @@ __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ 
                                    max_plies, explore, tid, lane, count, plies_total);
                 const TreeRootChild c = tree_root_child(nodes, lane);
                 my_n = c.n;
-                uint64_t key = c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull;
-                value = (int)c.w - (int)c.l;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) {
-                    const uint64_t other = (uint64_t)__shfl_xor((unsigned long long)key, o);
-                    key = other > key ? other : key;
-                    value += __shfl_xor(value, o);
-                }
-                action = tree_action_of(key);
+                value = (int)wave_sum(c.w - c.l);
+                action = tree_action_of(wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
                 how = kHowSearch;
                 if (tabs < sample_plies) {  // the first plies of a game: in proportion to the visits
                     uint32_t run = my_n;    // (the running sum of the visits through this lane's action)
@@ -2925,14 +2827,7 @@ static int check_traj(int64_t n, uint32_t plies, int64_t ply_stride, int64_t til
                       const int8_t *obs_traj, const int8_t *reward_traj, uintptr_t words, const char *words_msg, const int32_t *turn,
                       const int64_t *counters)
 {
-    {   // the (ply, tile) cells of 64 boards must start 16-byte aligned and must not overlap
-        const int64_t tiles = (n + kTile - 1) / kTile;
-        const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
-        const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
-        const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
-        if (!aligned || !(time_major || tile_major))
-            return fail(GBL_ERR_ARG, "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart");
-    }
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(obs_traj, "obs_traj");
     if (reward_traj && (reinterpret_cast<uintptr_t>(reward_traj) & 1u))
         return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
@@ -3542,9 +3437,9 @@ int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t 
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
     if (playouts < 1 || playouts > 4096) return fail(GBL_ERR_ARG, "playouts must be in [1, 4096]");
-    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
+    if (const char *why = playout_limits_error(max_plies)) return fail(GBL_ERR_ARG, why);
     if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     if ((reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) | reinterpret_cast<uintptr_t>(action_out) |
@@ -3572,12 +3467,10 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
                     int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (iterations < 1 || iterations > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
-    if (playouts < 1 || playouts > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
-    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
-    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (const char *why = tree_budget_error(iterations, playouts)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
     if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     if ((reinterpret_cast<uintptr_t>(visits_out) | reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) |
@@ -3615,17 +3508,15 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
     int most = 0, wide = 1;  // the larger tree and the larger leaf of the sides that search
     for (int m = 0; m < 2; ++m) {
         if (pol[m] != GBL_POLICY_TREE) continue;
-        if (its[m] < 1 || its[m] > kTreeMaxIterations) return fail(GBL_ERR_ARG, "iterations must be in [1, 1024]");
-        if (pls[m] < 1 || pls[m] > kTreeMaxPlayouts) return fail(GBL_ERR_ARG, "playouts must be in [1, 256]");
+        if (const char *why = tree_budget_error(its[m], pls[m])) return fail(GBL_ERR_ARG, why);
         most = std::max(most, its[m]);
         wide = std::max(wide, pls[m]);
     }
-    if (max_plies < 0 || max_plies > 255) return fail(GBL_ERR_ARG, "max_plies must be in [0, 255]");
-    if (explore < 0 || explore > kTreeMaxExplore) return fail(GBL_ERR_ARG, "explore must be in [0, 1024]");
+    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
     if (sample_plies < 0) return fail(GBL_ERR_ARG, "sample_plies < 0");
     if (sample_plies > 0 && !turn) return fail(GBL_ERR_ARG, "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)");
     if ((uint64_t)ply0 + plies > (1ull << 24)) return fail(GBL_ERR_ARG, "ply0 + plies must not exceed 2^24 (the search's call index)");
-    if (env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base) return fail(GBL_ERR_ARG, "env_base + n must not exceed 2^42");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;

@@ -166,3 +166,24 @@ def test_header_asks_no_alignment_of_the_search_inputs():
     for name in ("gbl_playout_values", "gbl_tree_search"):
         doc = text[:text.index("int %s(" % name)].rsplit("/*", 1)[1]
         assert "need NO alignment" in doc and "4-byte aligned" in doc and "non-zero" in doc, name
+
+
+# ---- the entry points' argument checks --------------------------------------------------------------------------------------------
+def test_argument_errors_replay_the_recorded_table(golden_dir):
+    """tests/golden/search_arg_errors.json: bad calls of gbl_playout_values, gbl_tree_search, gbl_collect_search and
+    gbl_outcome_targets (every single violation, and double ones that pin which check fires first and which checks precede the
+    n == 0 and plies == 0 returns) with the return code and the gbl_last_error text of either flavour, as recorded before the two
+    flavours shared their checks.  Every call returns before any device work (the pointers are numbers, never read); a case whose
+    "host" is null is an alignment rule, which only the device flavour has."""
+    import json
+    flavours = (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_"))
+    table = json.load(open(os.path.join(golden_dir, "search_arg_errors.json")))
+    assert len(table) > 120 and {c["fn"] for c in table} == {"playout_values", "tree_search", "collect_search", "outcome_targets"}
+    for c in table:
+        for flavour, lib, prefix in flavours:
+            if c[flavour] is None:
+                continue
+            rc, msg = c[flavour]
+            assert getattr(lib, prefix + c["fn"])(*c["args"]) == rc, (flavour, c["fn"], c["case"])
+            if rc:
+                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])
