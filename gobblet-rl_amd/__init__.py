@@ -6,6 +6,8 @@
     GreedyGobbletPolicy  the reference's depth-1/2 lookahead policy, batched
     MonteCarloGobbletPolicy  flat Monte-Carlo playouts per candidate action (strength tunable by the playout count)
     TreeSearchGobbletPolicy  UCT tree search per board on the same playouts (root visit distribution and values)
+    GobbletEvaluator  a small integer network (priors and value of a position) evaluated inside the kernels
+    EvaluatorTreeSearchGobbletPolicy  the tree search with that network in place of the playouts
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in
 ``include/gobblet_hip.h``); there is no CPU fallback.  Importing this package needs torch;
@@ -19,6 +21,7 @@ from .vector_env import BatchedGobblet  # noqa: F401
 from .greedy_policy import GreedyGobbletPolicy  # noqa: F401
 from .playout_policy import MonteCarloGobbletPolicy  # noqa: F401
 from .tree_policy import TreeSearchGobbletPolicy  # noqa: F401
+from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator  # noqa: F401
 from .random_policy import RandomAdmissiblePolicy  # noqa: F401
 from .sharding import make_shard, reduce_counters, shard_bounds  # noqa: F401
 

@@ -72,6 +72,8 @@ SIGNATURES = {
     "gbl_greedy_act_at": (_int, [_vp, _vp, _vp, _vp, _int, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_playout_values": (_int, [_vp, _vp, _vp, _int, _int, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_tree_search": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gbl_evaluate": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gbl_tree_search_eval": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_counter_add": (_int, [_vp, _u32, _vp]),
     "gbl_collect": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32,
                            _int, _vp, _vp, _vp]),
@@ -88,6 +90,12 @@ SIGNATURES = {
     "gbl_placement_probe": (_int, [_vp, _i64, _vp, _i64, _i64, _int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), _vp]),
 }
+
+
+class Evaluator(C.Structure):
+    """gbl_evaluator (include/gobblet_hip.h): a host struct of four pointers (device pointers for the HIP library) and four ints."""
+    _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp),
+                ("hidden", C.c_int32), ("shift1", C.c_int32), ("shift_p", C.c_int32), ("shift_v", C.c_int32)]
 
 
 class GobbletHipError(RuntimeError):

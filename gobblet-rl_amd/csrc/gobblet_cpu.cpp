@@ -741,6 +741,120 @@ int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t
     return GBL_OK;
 }
 
+// gbl_evaluator as the shared functions take it
+static inline EvalNet eval_net(const gbl_evaluator *ev)
+{
+    return EvalNet{ev->w1, ev->b1, ev->w2, ev->b2, ev->hidden, ev->shift1, ev->shift_p, ev->shift_v};
+}
+
+// One evaluation (the contract of gbl_evaluate): the outputs, the prior row over `cand` (zeros where it is empty) and q.
+static int32_t host_evaluate(const EvalNet &net, const Planes &p, int side, uint64_t cand, uint8_t *pri, int32_t (&o)[kEvalOutputs])
+{
+    uint32_t h4[kEvalMaxHidden / 4];
+    eval_hidden(net, p, side, h4);
+    eval_outputs(net, h4, o);
+    if (cand)
+        eval_priors(net, o, cand, pri);
+    else
+        memset(pri, 0, kActions);
+    return eval_value(net, o[kEvalValue]);
+}
+
+int gbl_cpu_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, uint8_t *priors_out,
+                     int32_t *value_out, int32_t *logits_out, int64_t n, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(priors_out, "priors_out"); GBL_NEED(value_out, "value_out");
+    if (const char *why = evaluator_pointers_error(ev)) return fail(GBL_ERR_ARG, why);
+    const EvalNet net = eval_net(ev);
+    parallel_for(n, [=](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) {
+            uint32_t r[7];
+            load_row(state, b, r);
+            const Planes p = make_planes(r);
+            const int mover = to_move[b] != 0;
+            uint64_t cand = legal54(p, mover);
+            if (mask) cand &= read_mask(mask + b * kActions);
+            int32_t o[kEvalOutputs];
+            value_out[b] = host_evaluate(net, p, mover, cand, priors_out + b * kActions, o);
+            if (logits_out) memcpy(logits_out + b * kEvalOutputs, o, sizeof o);
+        }
+    }, 256);
+    return GBL_OK;
+}
+
+// One board's evaluator-guided search (the contract of gbl_tree_search_eval, one iteration at a time): HostSearch as
+// host_tree_search, and the root's q; pri[0 .. 53] is the root's prior row.
+static int32_t host_tree_search_eval(std::vector<TreeNode> &nodes, std::vector<uint8_t> &pri, const EvalNet &net, const Planes &root,
+                                     int mover, uint64_t cand, uint32_t iterations, uint32_t explore, HostSearch &out)
+{
+    int32_t o[kEvalOutputs];
+    nodes[0] = TreeNode{};
+    const int32_t root_q = host_evaluate(net, root, mover, cand, pri.data(), o);
+    uint32_t count = 1;
+    for (uint32_t i = 0; cand && i < iterations; ++i) {
+        TreeEvalLeaf s = tree_eval_select(nodes.data(), pri.data(), root, mover, cand, explore);
+        uint32_t term = tree_term(nodes[s.node]);
+        if (s.expand) {
+            term = tree_move_into(s.p, s.side, s.a);
+            tree_link(nodes.data(), count, s.node, s.a, term);
+            s.node = count++;
+        }
+        uint32_t wl = tree_decided(term, kTreeEvalP);
+        if (s.expand && term == kTreeOpen)
+            wl = tree_eval_outcome(host_evaluate(net, s.p, s.side, legal54(s.p, s.side), pri.data() + (size_t)s.node * kEvalOutputs, o));
+        tree_backup(nodes.data(), s.node, wl & 0xFFFFu, wl >> 16);
+    }
+    memset(out.visits, 0, sizeof out.visits); memset(out.wins, 0, sizeof out.wins); memset(out.losses, 0, sizeof out.losses);
+    out.best = 0;
+    for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
+        const TreeNode &k = nodes[c];
+        const uint32_t a = tree_action(k);
+        out.visits[a] = k.n; out.wins[a] = (int32_t)tree_wins(k); out.losses[a] = (int32_t)tree_losses(k);
+        out.best = std::max(out.best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
+    }
+    out.count = count;
+    out.plies = 0;
+    return root_q;
+}
+
+int gbl_cpu_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                             int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                             int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_eval_budget_error(iterations, explore)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    if (const char *why = evaluator_pointers_error(ev)) return fail(GBL_ERR_ARG, why);
+    const EvalNet net = eval_net(ev);
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
+        std::vector<TreeNode> nodes((size_t)iterations + 1);
+        std::vector<uint8_t> pri(((size_t)iterations + 1) * kEvalOutputs);
+        HostSearch h;
+        for (int64_t b = b0; b < b1; ++b) {
+            uint32_t r[7];
+            load_row(state, b, r);
+            const Planes root = make_planes(r);
+            const int mover = to_move[b] != 0;
+            uint64_t cand = legal54(root, mover);
+            if (mask) cand &= read_mask(mask + b * kActions);
+            const int32_t q = host_tree_search_eval(nodes, pri, net, root, mover, cand, (uint32_t)iterations, (uint32_t)explore, h);
+            if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
+            if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
+            if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
+            if (action_out) action_out[b] = tree_action_of(h.best);
+            if (nodes_out) nodes_out[b] = (int32_t)h.count;
+            if (root_value_out) root_value_out[b] = q;
+            if (root_priors_out) memcpy(root_priors_out + b * kActions, pri.data(), kActions);
+        }
+    }, 1);
+    return GBL_OK;
+}
+
 int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *hist, int32_t *actions_traj, int8_t *winner_traj,
                            int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                            int32_t *chosen_traj, int8_t *how_traj, int8_t *cand_traj, int64_t n, int64_t ply_stride,

@@ -1938,15 +1938,20 @@ __device__ __forceinline__ TreeLeaf tree_select(const TreeNode *nodes, const Pla
 
 // Step 2 without the bookkeeping: the gbl_sample rule over the untried candidates on generator word r, the move, and what it
 // decided (kTree*).  p / side become the new child's position.  Returns the action.
-__device__ __forceinline__ uint32_t tree_expand_move(Planes &p, int &side, uint64_t untried, uint32_t r, uint32_t &term)
+__device__ __forceinline__ uint32_t tree_move_into(Planes &p, int &side, uint32_t a)  // the move, and what it decided (kTree*)
 {
-    const uint32_t a = kth_bit64(untried, __umulhi(r, (uint32_t)__popcll(untried)));
     const int by = side;
     move_planes(p, side, a);
     side ^= 1;
     const int w = winner_of(p);
     const int mine = by ? -w : w;
-    term = mine > 0 ? kTreeWon : (mine < 0 ? kTreeLost : (legal54(p, side) ? kTreeOpen : kTreeStuck));
+    return mine > 0 ? kTreeWon : (mine < 0 ? kTreeLost : (legal54(p, side) ? kTreeOpen : kTreeStuck));
+}
+
+__device__ __forceinline__ uint32_t tree_expand_move(Planes &p, int &side, uint64_t untried, uint32_t r, uint32_t &term)
+{
+    const uint32_t a = kth_bit64(untried, __umulhi(r, (uint32_t)__popcll(untried)));
+    term = tree_move_into(p, side, a);
     return a;
 }
 
@@ -2022,6 +2027,189 @@ __device__ __forceinline__ int visits_pick(const int32_t (&visits)[kActions], ui
     return -1;
 }
 
+// ---- gbl_evaluate / gbl_tree_search_eval: the integer network and the search it guides (contract: include/gobblet_hip.h) --
+// Every step is a function of one hidden-unit quad / one output / one action, so that the kernels give a lane each and the host
+// flavour runs them one after the other: the same arithmetic, bit for bit.  Every operand stays inside int32.
+constexpr int kEvalOutputs = 56, kEvalValue = 54;  // outputs 0..53: the action logits, 54: the value, 55: padding
+constexpr int kEvalMaxHidden = 256, kEvalMaxShift = 24;
+constexpr int kTreeEvalMaxIterations = 512;
+constexpr uint32_t kTreeEvalP = 128u;  // a network leaf counts as 128 games: q is in 1/128 of a win
+
+struct EvalNet {  // gbl_evaluator, as the kernels take it (by value)
+    const int8_t *w1;
+    const int32_t *b1;
+    const int8_t *w2;
+    const int32_t *b2;
+    int32_t hidden, shift1, shift_p, shift_v;
+};
+
+__device__ __forceinline__ uint32_t eval_load4(const int8_t *w)  // four weights as one dword (w is 4-byte aligned)
+{
+#ifndef GBL_HOST_EMU
+    return *reinterpret_cast<const uint32_t *>(w);
+#else
+    uint32_t x;
+    __builtin_memcpy(&x, w, 4);
+    return x;
+#endif
+}
+
+// acc + the dot product of four signed bytes with four signed bytes: v_dot4_i32_i8
+__device__ __forceinline__ int32_t eval_dot4(uint32_t a, uint32_t b, int32_t acc)
+{
+#ifndef GBL_HOST_EMU
+    return __builtin_amdgcn_sdot4((int)a, (int)b, acc, false);
+#else
+    for (int u = 0; u < 4; ++u) acc += (int32_t)(int8_t)(a >> (8 * u)) * (int32_t)(int8_t)(b >> (8 * u));
+    return acc;
+#endif
+}
+
+__device__ __forceinline__ int32_t eval_clamp(int32_t x, int32_t lo, int32_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// Layer 1, hidden units j0 .. j0 + 3 (j0 a multiple of 4) of position p as `side` observes it: the sum of the weight rows of the
+// set observation bytes (obs_scatter_row's rule: byte 13 pos + ch; at most 12 pieces, and the 9 bytes of channel 12 when player_2
+// observes), never a matrix product.  Returns h as four bytes, unit j0 lowest.
+__device__ __forceinline__ uint32_t eval_hidden4(const EvalNet &net, const Planes &p, int side, uint32_t j0)
+{
+    const uint32_t pos = p.nz & ~p.neg, ngv = p.nz & p.neg;
+    const uint32_t own = side ? ngv : pos, opp = side ? pos : ngv;
+    const uint32_t X[4] = {own & p.odd, own & ~p.odd, opp & p.odd, opp & ~p.odd};
+    const int8_t *col = net.w1 + j0;
+    int32_t acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = net.b1[j0 + u];
+    // Straight-line code, every load issued before the first sum needs one: a piece that is not on the board reads the row of
+    // square 8 of its own channel, channel 12 is read whoever observes, and the dword is dropped afterwards.
+    uint32_t rows[21];
+#pragma unroll
+    for (int ch = 0; ch < 12; ++ch) {
+        const int k = (ch % 6) / 2;
+        const uint32_t grp = (X[(ch < 6 ? 0 : 2) + (ch & 1)] >> (9 * k)) & 0x1FFu;
+        const uint32_t row = eval_load4(col + (13 * __builtin_ctz(grp | 0x100u) + ch) * net.hidden);
+        rows[ch] = grp ? row : 0u;
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        const uint32_t row = eval_load4(col + (13 * q + 12) * net.hidden);
+        rows[12 + q] = side ? row : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < 21; ++r) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] += (int32_t)(int8_t)(rows[r] >> (8 * u));
+    }
+    uint32_t h = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) h |= (uint32_t)eval_clamp(acc[u] >> net.shift1, 0, 127) << (8 * u);
+    return h;
+}
+
+// all H hidden units, into h4[H / 4] (the host flavour; the kernels give every quad a lane)
+__device__ __forceinline__ void eval_hidden(const EvalNet &net, const Planes &p, int side, uint32_t *h4)
+{
+    for (uint32_t j0 = 0; j0 < (uint32_t)net.hidden; j0 += 4) h4[j0 >> 2] = eval_hidden4(net, p, side, j0);
+}
+
+// Layer 2, output k < 56: b2_k + sum_j h_j w2(j, k), four hidden units per step (h <= 127, so both operands are signed bytes)
+__device__ __forceinline__ int32_t eval_output(const EvalNet &net, const uint32_t *h4, uint32_t k)
+{
+    int32_t o = net.b2[k];
+    const int8_t *w = net.w2 + 4u * k;
+    const int quads = net.hidden >> 2;
+#pragma unroll 8
+    for (int j = 0; j < quads; ++j) o = eval_dot4(eval_load4(w + j * 4 * kEvalOutputs), h4[j], o);
+    return o;
+}
+
+__device__ __forceinline__ void eval_outputs(const EvalNet &net, const uint32_t *h4, int32_t (&o)[kEvalOutputs])
+{
+    for (uint32_t k = 0; k < (uint32_t)kEvalOutputs; ++k) o[k] = eval_output(net, h4, k);
+}
+
+__device__ __forceinline__ int32_t eval_value(const EvalNet &net, int32_t o54) { return eval_clamp(o54 >> net.shift_v, -128, 128); }
+
+// 2^(-d / 16) in 1/65536, d = the distance of a logit below the largest one, capped at 255 (16 octaves)
+__device__ __forceinline__ uint32_t eval_exp2(int32_t lmax, int32_t l)
+{
+    constexpr uint32_t T[16] = {65536u, 62757u, 60097u, 57549u, 55109u, 52773u, 50535u, 48393u,
+                                46341u, 44376u, 42495u, 40693u, 38968u, 37316u, 35734u, 34219u};
+    const int32_t d = lmax - l < 255 ? lmax - l : 255;
+    return T[d & 15] >> (d >> 4);
+}
+__device__ __forceinline__ uint32_t eval_prior(uint32_t e, uint32_t sum) { return 1u + (e * 254u) / sum; }  // (sum >= e, sum > 0)
+
+// the prior row of a candidate set (the host flavour; the kernels take the maximum and the sum over the wavefront)
+__device__ __forceinline__ void eval_priors(const EvalNet &net, const int32_t (&o)[kEvalOutputs], uint64_t cand, uint8_t *pri)
+{
+    int32_t lmax = INT32_MIN;
+    for (int a = 0; a < kActions; ++a)
+        if (((cand >> a) & 1ull) && (o[a] >> net.shift_p) > lmax) lmax = o[a] >> net.shift_p;
+    uint32_t sum = 0;
+    for (int a = 0; a < kActions; ++a)
+        if ((cand >> a) & 1ull) sum += eval_exp2(lmax, o[a] >> net.shift_p);
+    for (int a = 0; a < kActions; ++a) pri[a] = (uint8_t)(((cand >> a) & 1ull) ? eval_prior(eval_exp2(lmax, o[a] >> net.shift_p), sum) : 0u);
+}
+
+// The selection key of candidate a with prior pi under a node of nv visits: the mean of its child (tree_key's first term; 32768
+// without a child, n = 0) plus ((explore pi isqrt(nv << 8)) >> 5) / (1 + n).  nv <= 512: the root of the isqrt stays below 2^24,
+// the product below 1024 * 255 * 363 < 2^27.
+__device__ __forceinline__ uint32_t tree_eval_key(bool child, uint32_t W, uint32_t L, uint32_t n, uint32_t nv, uint32_t pi, uint32_t explore)
+{
+    uint32_t mean = 32768u;
+    if (child) {
+        const uint32_t d = n * kTreeEvalP, x = W + d - L;
+        const uint32_t hi = (x << 7) / d, rem = (x << 7) - hi * d;
+        mean = (hi << 8) + (rem << 8) / d;
+    }
+    return mean + ((explore * pi * tree_isqrt(nv << 8)) >> 5) / (1u + (child ? n : 0u));
+}
+
+// the outcome of a network leaf for the side that moved INTO it, as wins | losses << 16 (q: for the side to move at the leaf)
+__device__ __forceinline__ uint32_t tree_eval_outcome(int32_t q) { return q < 0 ? (uint32_t)-q : (uint32_t)q << 16; }
+
+// Where an iteration's selection stopped: at `node` with position p, `side` to move.  expand: action `a` of the node has no child
+// and is the expansion; otherwise the node is terminal and is evaluated itself.
+struct TreeEvalLeaf {
+    uint32_t node;
+    Planes p;
+    int side;
+    bool expand;
+    uint32_t a;
+};
+
+// Selection, one node and one candidate after the other (the host flavour; k_tree_eval gives every action a lane).  pri: the prior
+// rows, kEvalOutputs bytes per node.  rootcand != 0.
+__device__ __forceinline__ TreeEvalLeaf tree_eval_select(const TreeNode *nodes, const uint8_t *pri, const Planes &root, int mover,
+                                                         uint64_t rootcand, uint32_t explore)
+{
+    TreeEvalLeaf s{0u, root, mover, false, 0u};
+    uint64_t cand = rootcand;
+    for (;;) {
+        const TreeNode v = nodes[s.node];
+        if (tree_term(v)) return s;
+        uint32_t of[kActions] = {};
+        for (uint32_t c = v.child; c; c = nodes[c].sibling) of[tree_action(nodes[c])] = c;
+        uint32_t best = 0;
+        for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+            if (!((cand >> a) & 1ull)) continue;
+            const TreeNode k = nodes[of[a]];  // (of[a] == 0: the root, not looked at)
+            const uint32_t key = tree_order_key(tree_eval_key(of[a] != 0, tree_wins(k), tree_losses(k), k.n, v.n,
+                                                              pri[s.node * kEvalOutputs + a], explore), a);
+            if (key > best) best = key;
+        }
+        s.a = 63u - (best & 63u);
+        if (!of[s.a]) {
+            s.expand = true;
+            return s;
+        }
+        move_planes(s.p, s.side, s.a);
+        s.side ^= 1;
+        s.node = of[s.a];
+        cand = legal54(s.p, s.side);
+    }
+}
+
 // ---- argument checks of the search entry points and the trajectory strides: host code, for both flavours of the ABI ----------
 // Each *_error returns the message of the first rule the arguments break, or nullptr; a flavour passes it to its own fail().
 inline const char *tree_budget_error(int iterations, int playouts)
@@ -2034,6 +2222,30 @@ inline const char *tree_budget_error(int iterations, int playouts)
 inline const char *playout_limits_error(int max_plies, int explore = 0)  // (gbl_playout_values has no explore)
 {
     if (max_plies < 0 || max_plies > 255) return "max_plies must be in [0, 255]";
+    if (explore < 0 || explore > kTreeMaxExplore) return "explore must be in [0, 1024]";
+    return nullptr;
+}
+
+// the checks of a gbl_evaluator's scalar fields (its four pointers are looked at after the n == 0 return)
+template <typename Ev>
+inline const char *evaluator_error(const Ev *ev)
+{
+    if (!ev) return "ev must not be NULL";
+    if (ev->hidden != 64 && ev->hidden != 128 && ev->hidden != 192 && ev->hidden != 256) return "hidden must be 64, 128, 192 or 256";
+    if (ev->shift1 < 0 || ev->shift1 > kEvalMaxShift || ev->shift_p < 0 || ev->shift_p > kEvalMaxShift || ev->shift_v < 0 ||
+        ev->shift_v > kEvalMaxShift)
+        return "shift1 / shift_p / shift_v must be in [0, 24]";
+    return nullptr;
+}
+template <typename Ev>
+inline const char *evaluator_pointers_error(const Ev *ev)
+{
+    return ev->w1 && ev->b1 && ev->w2 && ev->b2 ? nullptr : "the evaluator's w1 / b1 / w2 / b2 must not be NULL";
+}
+
+inline const char *tree_eval_budget_error(int iterations, int explore)
+{
+    if (iterations < 1 || iterations > kTreeEvalMaxIterations) return "iterations must be in [1, 512]";
     if (explore < 0 || explore > kTreeMaxExplore) return "explore must be in [0, 1024]";
     return nullptr;
 }

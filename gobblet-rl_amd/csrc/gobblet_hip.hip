@@ -1926,6 +1926,152 @@ int tree_waves(int64_t n, int playouts)
     return w;
 }
 
+// ---- the integer network (k_evaluate) and the search it guides (k_tree_eval): contract in include/gobblet_hip.h ---------------------
+__device__ __forceinline__ int32_t wave_max_signed(int32_t x)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int32_t other = __shfl_xor(x, o);
+        x = other > x ? other : x;
+    }
+    return x;
+}
+
+// One evaluation by a whole wavefront; every lane holds the same p / side / cand.
+//   layer 1   lane i < H / 4 owns hidden units 4 i .. 4 i + 3: a set observation byte is one coalesced dword per lane of its w1 row
+//             (the set bytes come straight from the planes: no observation row is built); the clamped bytes go to s_h, H bytes;
+//   layer 2   lane k < 56 owns output k: h as broadcast LDS dwords against its own [j / 4][k] dword of w2, one v_dot4_i32_i8 each;
+//   priors    the maximum and the sum over the candidates are wavefront butterflies; the value is lane 54's output.
+// Returns lane a's prior byte (0 for a lane outside cand), its output (0 for lanes >= 56) and q in every lane.
+struct WaveEval {
+    uint32_t pi;
+    int32_t o, q;
+};
+
+__device__ __forceinline__ WaveEval wave_evaluate(const EvalNet &net, const Planes &p, int side, uint64_t cand, uint32_t *s_h, uint32_t lane)
+{
+    if (4u * lane < (uint32_t)net.hidden) s_h[lane] = eval_hidden4(net, p, side, 4u * lane);
+    wave_lds_fence();
+    const int32_t o = lane < (uint32_t)kEvalOutputs ? eval_output(net, s_h, lane) : 0;
+    wave_lds_fence();  // (h is read before the next evaluation overwrites it)
+    const bool in = (cand >> lane) & 1ull;
+    const int32_t l = o >> net.shift_p;
+    const int32_t lmax = wave_max_signed(in ? l : INT32_MIN);
+    const uint32_t e = in ? eval_exp2(lmax, l) : 0u;
+    const uint32_t sum = wave_sum(e);
+    return WaveEval{in ? eval_prior(e, sum) : 0u, o, eval_value(net, __builtin_amdgcn_readlane(o, kEvalValue))};
+}
+
+// gbl_evaluate: the network alone.  One wavefront per board (a grid-stride loop over boards).
+__global__ __launch_bounds__(64) void k_evaluate(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                                 const int8_t *__restrict__ mask, const EvalNet net, uint8_t *__restrict__ priors_out,
+                                                 int32_t *__restrict__ value_out, int32_t *__restrict__ logits_out, int64_t n)
+{
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    const uint32_t lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        const Planes p = board_planes(state, b, lane);
+        const int mover = to_move[b] != 0;
+        const WaveEval r = wave_evaluate(net, p, mover, board_candidates(p, mover, mask, b, lane), s_h, lane);
+        if (lane < (uint32_t)kActions) priors_out[b * kActions + lane] = (uint8_t)r.pi;
+        if (logits_out && lane < (uint32_t)kEvalOutputs) logits_out[b * kEvalOutputs + lane] = r.o;
+        if (lane == 0) value_out[b] = r.q;
+    }
+}
+
+// gbl_tree_search_eval: k_tree's tree with a network leaf.  One wavefront per board (a grid-stride loop over boards), so the tree
+// needs no workgroup barrier: LDS traffic of one wavefront lands in order.  The tree is (iterations + 1) 16-byte nodes followed by
+// (iterations + 1) 56-byte prior rows in dynamic LDS; the root planes stay in registers.  An iteration:
+//   select   k_tree's walk -- the child list of a node once, lane a keeps the child of action a -- plus one byte of the node's prior
+//            row per lane; every lane computes its action's key, a butterfly max picks, one move_planes per level replays the position;
+//   expand   the move and what it decided in every lane alike; lane 0 links the node;
+//   evaluate wave_evaluate on the new child's position, its prior row stored beside the node;
+//   back up  lane 0 walks to the root.
+__global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                                  const int8_t *__restrict__ mask, const EvalNet net, int32_t *__restrict__ visits_out,
+                                                  int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
+                                                  int32_t *__restrict__ action_out, int32_t *__restrict__ nodes_out,
+                                                  int32_t *__restrict__ root_value_out, uint8_t *__restrict__ root_priors_out, int64_t n,
+                                                  uint32_t iterations, uint32_t explore)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + iterations + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    const uint32_t lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        const Planes root = board_planes(state, b, lane);
+        const int mover = to_move[b] != 0;
+        const uint64_t cand = board_candidates(root, mover, mask, b, lane);
+        if (lane == 0) nodes[0] = TreeNode{};
+        const WaveEval at_root = wave_evaluate(net, root, mover, cand, s_h, lane);
+        if (lane < (uint32_t)kEvalOutputs) pri[lane] = (uint8_t)at_root.pi;
+        wave_lds_fence();  // (the root is written)
+        uint32_t count = 1;
+        for (uint32_t i = 0; cand && i < iterations; ++i) {
+            // 1. select
+            uint32_t v = 0, term, a_new = 0;
+            Planes p = root;
+            int side = mover;
+            uint64_t cd = cand;
+            bool grow = false;
+            for (;;) {
+                const TreeNode nv = nodes[v];
+                term = tree_term(nv);
+                if (term) break;
+                uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
+                for (uint32_t c = nv.child; c;) {
+                    const TreeNode k = nodes[c];
+                    if (lane == tree_action(k)) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
+                    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+                }
+                const uint32_t pi = lane < (uint32_t)kEvalOutputs ? pri[v * kEvalOutputs + lane] : 0u;
+                const uint32_t key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my_c != 0, my_w, my_l, my_n, nv.n, pi, explore), lane) : 0u);
+                a_new = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
+                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a_new);
+                if (!c) {
+                    grow = true;
+                    break;
+                }
+                move_planes(p, side, a_new);
+                side ^= 1;
+                v = c;
+                cd = legal54(p, side);
+            }
+            // 2. expand and evaluate
+            uint32_t leaf = v;
+            if (grow) {
+                term = tree_move_into(p, side, a_new);
+                leaf = count++;
+                if (lane == 0) tree_link(nodes, leaf, v, a_new, term);
+            }
+            uint32_t wl = tree_decided(term, kTreeEvalP);
+            if (grow && term == kTreeOpen) {
+                const WaveEval r = wave_evaluate(net, p, side, legal54(p, side), s_h, lane);
+                if (lane < (uint32_t)kEvalOutputs) pri[leaf * kEvalOutputs + lane] = (uint8_t)r.pi;
+                wl = tree_eval_outcome(r.q);
+            }
+            // 3. back up
+            if (lane == 0) tree_backup(nodes, leaf, wl & 0xFFFFu, wl >> 16);
+            wave_lds_fence();  // (the tree is written)
+        }
+        const TreeRootChild c = tree_root_child(nodes, lane);
+        if (lane < (uint32_t)kActions) {
+            if (visits_out) visits_out[b * kActions + lane] = (int32_t)c.n;
+            if (wins_out) wins_out[b * kActions + lane] = (int32_t)c.w;
+            if (losses_out) losses_out[b * kActions + lane] = (int32_t)c.l;
+            if (root_priors_out) root_priors_out[b * kActions + lane] = (uint8_t)at_root.pi;
+        }
+        const uint64_t key = wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull);
+        if (lane == 0) {
+            if (action_out) action_out[b] = tree_action_of(key);
+            if (nodes_out) nodes_out[b] = (int32_t)count;
+            if (root_value_out) root_value_out[b] = at_root.q;
+        }
+        wave_lds_fence();  // (before the next board rewrites the root)
+    }
+}
+
 // gbl_collect_search: whole games with the tree search on either or both sides, every ply materialised.  One workgroup of W
 // wavefronts per board (a grid-stride loop over boards) with the ply loop INSIDE: a board whose search walks into decided nodes
 // and plays nothing goes on to its next ply while its neighbours still play iterations x playouts games -- no ply of any board
@@ -3490,6 +3636,54 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
     }
 #undef GBL_TREE
     GBL_LAUNCHED("gbl_tree_search");
+}
+
+// gbl_evaluator as the kernels take it, after the checks both entry points share; 0, or the error
+static int eval_net_of(const gbl_evaluator *ev, EvalNet &net)
+{
+    if (const char *why = evaluator_pointers_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (!aligned16(ev->w1) || !aligned16(ev->b1) || !aligned16(ev->w2) || !aligned16(ev->b2))
+        return fail(GBL_ERR_ALIGN, "the evaluator's w1 / b1 / w2 / b2 must be 16-byte aligned");
+    net = EvalNet{ev->w1, ev->b1, ev->w2, ev->b2, ev->hidden, ev->shift1, ev->shift_p, ev->shift_v};
+    return GBL_OK;
+}
+
+int gbl_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, uint8_t *priors_out,
+                 int32_t *value_out, int32_t *logits_out, int64_t n, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(priors_out, "priors_out"); GBL_NEED(value_out, "value_out");
+    EvalNet net;
+    if (const int e = eval_net_of(ev, net)) return e;
+    if ((reinterpret_cast<uintptr_t>(value_out) | reinterpret_cast<uintptr_t>(logits_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "value_out / logits_out must be 4-byte aligned");
+    hipLaunchKernelGGL(k_evaluate, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), 0, (hipStream_t)stream, state, to_move, mask, net,
+                       priors_out, value_out, logits_out, n);
+    GBL_LAUNCHED("gbl_evaluate");
+}
+
+int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                         int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                         int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_eval_budget_error(iterations, explore)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    EvalNet net;
+    if (const int e = eval_net_of(ev, net)) return e;
+    if ((reinterpret_cast<uintptr_t>(visits_out) | reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) |
+         reinterpret_cast<uintptr_t>(action_out) | reinterpret_cast<uintptr_t>(nodes_out) | reinterpret_cast<uintptr_t>(root_value_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / root_value_out must be 4-byte aligned");
+    // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations: below the 64 KB a kernel gets unasked)
+    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);
+    hipLaunchKernelGGL(k_tree_eval, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), lds, (hipStream_t)stream, state, to_move, mask,
+                       net, visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n,
+                       (uint32_t)iterations, (uint32_t)explore);
+    GBL_LAUNCHED("gbl_tree_search_eval");
 }
 
 int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,

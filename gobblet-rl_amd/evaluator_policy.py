@@ -1,0 +1,231 @@
+"""``GobbletEvaluator`` -- a small integer network (117 observation bytes -> H hidden units -> 54 action logits and a value) that
+the library evaluates INSIDE its kernels, and ``EvaluatorTreeSearchGobbletPolicy`` -- the tree search of ``TreeSearchGobbletPolicy``
+with that network in place of the masked-random playouts and with its priors steering the selection (``gbl_evaluate`` /
+``gbl_tree_search_eval``, include/gobblet_hip.h).  This is what a network trained on the ``(obs, pi, z)`` targets of
+``collect(..., search=...)`` / ``outcome_targets`` is used by: ``GobbletEvaluator.from_float`` quantises a float 117-H-55 MLP.
+
+The rule is integer-only: the kernel and the host flavour (``device="cpu"``) agree bit for bit, and the search draws nothing --
+no seed, no call index; two calls on the same boards give the same result.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+import math
+from typing import Any
+
+import numpy as np
+import torch
+
+from . import _native as nat
+
+HIDDEN_SIZES = (64, 128, 192, 256)
+OUTPUTS, VALUE = 56, 54
+MAX_SHIFT, MAX_B1, MAX_B2 = 24, 1 << 20, 1 << 24
+LOG2E_16 = 16.0 * math.log2(math.e)  # a natural-log logit in 1/16 of an octave
+
+
+def _pow2_at_most(x: float) -> float:
+    """The largest power of two s with s <= x (x > 0)."""
+    return 2.0 ** math.floor(math.log2(x))
+
+
+class GobbletEvaluator:
+    """The four integer tensors of a ``gbl_evaluator`` on one device: w1 int8 (117, H), b1 int32 (H,), w2 int8 (H / 4, 56, 4) with
+    element [j // 4, k, j % 4] = the weight of hidden unit j for output k, b2 int32 (56,), and the three shifts."""
+
+    def __init__(self, w1, b1, w2, b2, shift1: int, shift_p: int, shift_v: int, device="cpu") -> None:
+        self.device = torch.device(device)
+        w1, b1, w2, b2 = (torch.as_tensor(t) for t in (w1, b1, w2, b2))
+        hidden = int(w1.shape[-1])
+        if hidden not in HIDDEN_SIZES:
+            raise ValueError("hidden must be 64, 128, 192 or 256")
+        if tuple(w1.shape) != (nat.OBS_BYTES, hidden) or tuple(b1.shape) != (hidden,) or tuple(w2.shape) != (hidden // 4, OUTPUTS, 4) \
+                or tuple(b2.shape) != (OUTPUTS,):
+            raise ValueError("shapes: w1 (117, H), b1 (H,), w2 (H / 4, 56, 4), b2 (56,)")
+        for name, sh in (("shift1", shift1), ("shift_p", shift_p), ("shift_v", shift_v)):
+            if not 0 <= int(sh) <= MAX_SHIFT:
+                raise ValueError(f"{name} must be in [0, {MAX_SHIFT}]")
+        if int(b1.abs().max()) > MAX_B1 or int(b2.abs().max()) > MAX_B2:
+            raise ValueError("|b1| must not exceed 2^20 and |b2| must not exceed 2^24")
+        self.hidden, self.shift1, self.shift_p, self.shift_v = hidden, int(shift1), int(shift_p), int(shift_v)
+        # (fresh allocations: 16-byte aligned on either device)
+        self.w1 = w1.to(device=self.device, dtype=torch.int8).contiguous().clone()
+        self.b1 = b1.to(device=self.device, dtype=torch.int32).contiguous().clone()
+        self.w2 = w2.to(device=self.device, dtype=torch.int8).contiguous().clone()
+        self.b2 = b2.to(device=self.device, dtype=torch.int32).contiguous().clone()
+        self.scales: dict[str, float] = {}  # from_float: the power-of-two scales it chose
+        self._lib = nat.lib_for(self.device)
+
+    def to(self, device) -> "GobbletEvaluator":
+        ev = GobbletEvaluator(self.w1, self.b1, self.w2, self.b2, self.shift1, self.shift_p, self.shift_v, device=device)
+        ev.scales = dict(self.scales)
+        return ev
+
+    def as_struct(self) -> nat.Evaluator:
+        """The ``gbl_evaluator`` over this object's tensors (keep the object alive while the struct is in use)."""
+        return nat.Evaluator(self.w1.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(), self.b2.data_ptr(), self.hidden, self.shift1,
+                             self.shift_p, self.shift_v)
+
+    @staticmethod
+    def pack_w2(w2_jk) -> torch.Tensor:
+        """(H, 56) -> the (H / 4, 56, 4) layout of the ABI."""
+        w2_jk = torch.as_tensor(w2_jk)
+        h = w2_jk.shape[0]
+        return w2_jk.reshape(h // 4, 4, OUTPUTS).permute(0, 2, 1).contiguous()
+
+    @classmethod
+    def from_float(cls, w1, b1, w2, b2, hidden_max: float | None = None, natural_log: bool = True, device="cpu") -> "GobbletEvaluator":
+        """Quantise the float network  h = relu(x @ w1 + b1),  out = h @ w2 + b2  with w1 (117, H), b1 (H,), w2 (H, 55), b2 (55,):
+        out[:54] are the action logits of a softmax (natural-log if ``natural_log``, else already in 1/16 of an octave), out[54] is
+        the value, read as clip(out[54], -1, 1) of a win for the side to move.
+
+        Every scale is a power of two, the largest that keeps the rounded weights inside int8: ``scale1`` for w1 / b1;
+        ``scale_h`` = scale1 / 2^shift1 for the hidden units, with shift1 the smallest that keeps ``hidden_max`` (the largest hidden
+        activation to represent; default: the bound b1_j + the 21 largest positive weights of unit j) below 128; ``scale_p`` for
+        the policy columns after log2(e) * 16 has been folded into them, so that shift_p = log2(scale_p * scale_h) leaves the
+        logits in 1/16 of an octave; ``scale_v`` for the value column, shift_v = log2(scale_v * scale_h / 128).  They are kept in
+        ``.scales``.  Raises ValueError if a shift leaves 0 .. 24 or a bias its range."""
+        w1, b1, w2, b2 = (np.asarray(torch.as_tensor(t).detach().cpu(), np.float64) for t in (w1, b1, w2, b2))
+        hidden = w1.shape[1]
+        if w1.shape != (nat.OBS_BYTES, hidden) or b1.shape != (hidden,) or w2.shape != (hidden, 55) or b2.shape != (55,):
+            raise ValueError("shapes: w1 (117, H), b1 (H,), w2 (H, 55), b2 (55,)")
+        scale1 = _pow2_at_most(127.0 / max(float(np.abs(w1).max()), 1e-30))
+        if hidden_max is None:
+            hidden_max = float((b1 + np.sort(np.maximum(w1, 0.0), axis=0)[-21:].sum(0)).max())
+        shift1 = max(0, math.ceil(math.log2(max(hidden_max, 1e-30) * scale1 / 127.0)))
+        scale_h = scale1 / 2.0 ** shift1
+        fold = LOG2E_16 if natural_log else 1.0
+        wp, bp, wv, bv = w2[:, :54] * fold, b2[:54] * fold, w2[:, 54], b2[54]
+        scale_p = _pow2_at_most(127.0 / max(float(np.abs(wp).max()), 1e-30))
+        scale_v = _pow2_at_most(127.0 / max(float(np.abs(wv).max()), 1e-30))
+        shift_p, shift_v = round(math.log2(scale_p * scale_h)), round(math.log2(scale_v * scale_h / 128.0))
+        if shift_p > MAX_SHIFT:  # (tiny weights: a smaller scale loses nothing that the shift would not drop)
+            scale_p, shift_p = scale_p / 2.0 ** (shift_p - MAX_SHIFT), MAX_SHIFT
+        if shift_v > MAX_SHIFT:
+            scale_v, shift_v = scale_v / 2.0 ** (shift_v - MAX_SHIFT), MAX_SHIFT
+        if shift_p < 0 or shift_v < 0:
+            raise ValueError("the output weights are too large for the hidden scale: no shift in [0, 24] represents them")
+        q_w1 = np.clip(np.rint(w1 * scale1), -128, 127)
+        q_b1 = np.rint(b1 * scale1)
+        q_w2 = np.zeros((hidden, OUTPUTS))
+        q_w2[:, :54], q_w2[:, VALUE] = np.clip(np.rint(wp * scale_p), -128, 127), np.clip(np.rint(wv * scale_v), -128, 127)
+        q_b2 = np.zeros(OUTPUTS)
+        q_b2[:54], q_b2[VALUE] = np.rint(bp * scale_p * scale_h), np.rint(bv * scale_v * scale_h)
+        ev = cls(torch.from_numpy(q_w1.astype(np.int8)), torch.from_numpy(q_b1.astype(np.int64)),
+                 cls.pack_w2(torch.from_numpy(q_w2.astype(np.int8))), torch.from_numpy(q_b2.astype(np.int64)), shift1, shift_p, shift_v,
+                 device=device)
+        ev.scales = {"scale1": scale1, "scale_h": scale_h, "scale_p": scale_p, "scale_v": scale_v, "fold": fold}
+        return ev
+
+    def _on_device(self):
+        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
+
+    def evaluate_raw(self, state, to_move, mask=None, logits: bool = False):
+        """``gbl_evaluate``: (priors uint8 (N, 54), value int32 (N,), logits int32 (N, 56) or None)."""
+        state = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(-1, nat.CELLS).contiguous()
+        n = state.shape[0]
+        to_move = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.int8).reshape(n, nat.ACTIONS).contiguous()
+        pri = torch.empty((n, nat.ACTIONS), dtype=torch.uint8, device=self.device)
+        val = torch.empty(n, dtype=torch.int32, device=self.device)
+        log = torch.empty((n, OUTPUTS), dtype=torch.int32, device=self.device) if logits else None
+        ev = self.as_struct()
+        with self._on_device():
+            nat.check(self._lib.gbl_evaluate(state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), pri.data_ptr(),
+                                             val.data_ptr(), nat.ptr(log), n, nat.current_stream(self.device)), "gbl_evaluate")
+        return pri, val, log
+
+    def evaluate(self, state, to_move, mask=None):
+        """(priors float32 (N, 54) = pi / sum(pi), zeros where a board has no candidate; value float32 (N,) = q / 128)."""
+        pri, val, _ = self.evaluate_raw(state, to_move, mask)
+        pri = pri.to(torch.float32)
+        return pri / pri.sum(1, keepdim=True).clamp(min=1.0), val.to(torch.float32) / 128.0
+
+
+class EvaluatorTreeSearchGobbletPolicy:
+    def __init__(self, evaluator: GobbletEvaluator, iterations: int = 256, explore: int = 16, device=None, **kwargs: Any) -> None:
+        """iterations: network leaves per decision (1 .. 512); explore: weight of the prior term of the selection key (0 .. 1024;
+        the default is the best of the host-flavour sweep in profiles/r10/evaluator_policy.json); device: where the search runs
+        (default: the evaluator's; the evaluator is copied there if it lives elsewhere)."""
+        for name, val, lo, hi in (("iterations", iterations, 1, 512), ("explore", explore, 0, 1024)):
+            if not lo <= int(val) <= hi:
+                raise ValueError(f"{name} must be in [{lo}, {hi}]")
+        self.iterations, self.explore = int(iterations), int(explore)
+        self.device = torch.device(evaluator.device if device is None else device)
+        self.evaluator = evaluator if evaluator.device == self.device else evaluator.to(self.device)
+        self._lib = nat.lib_for(self.device)
+        # outputs of the last call (tensors on the device): int32 (N, 54) visits / wins / losses of the root's children from the
+        # mover's side (a leaf counts as 128 games), int32 (N,) nodes created, the decision and the root's q, uint8 (N, 54) the
+        # root's prior row
+        self.last_visits = self.last_wins = self.last_losses = self.last_nodes = self.last_action = None
+        self.last_root_value = self.last_root_priors = None
+
+    def _on_device(self):
+        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
+
+    def _run(self, state, to_move, mask) -> torch.Tensor:
+        state = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(-1, nat.CELLS).contiguous()
+        n = state.shape[0]
+        to_move = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.int8).reshape(n, nat.ACTIONS).contiguous()
+        visits = torch.empty((n, nat.ACTIONS), dtype=torch.int32, device=self.device)
+        wins, losses = torch.empty_like(visits), torch.empty_like(visits)
+        act = torch.empty(n, dtype=torch.int32, device=self.device)
+        nodes, rootv = torch.empty_like(act), torch.empty_like(act)
+        rootp = torch.empty((n, nat.ACTIONS), dtype=torch.uint8, device=self.device)
+        ev = self.evaluator.as_struct()
+        with self._on_device():
+            nat.check(self._lib.gbl_tree_search_eval(state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), self.iterations,
+                                                     self.explore, visits.data_ptr(), wins.data_ptr(), losses.data_ptr(), act.data_ptr(),
+                                                     nodes.data_ptr(), rootv.data_ptr(), rootp.data_ptr(), n,
+                                                     nat.current_stream(self.device)), "gbl_tree_search_eval")
+        self.last_visits, self.last_wins, self.last_losses = visits, wins, losses
+        self.last_nodes, self.last_action, self.last_root_value, self.last_root_priors = nodes, act, rootv, rootp
+        return act
+
+    def compute_actions_from_state(self, state, to_move, mask=None) -> torch.Tensor:
+        """The decision from ``squares`` (N,27) + ``to_move`` (N,): int32 (N,), -1 where a board has no candidate."""
+        return self._run(state, to_move, mask)
+
+    def visit_distribution(self, state, to_move, mask=None) -> torch.Tensor:
+        """float32 (N, 54): visits / iterations of every root action; 0 for non-candidates."""
+        self._run(state, to_move, mask)
+        return self.last_visits.to(torch.float32) / self.iterations
+
+    def action_values(self, state, to_move, mask=None) -> torch.Tensor:
+        """float32 (N, 54): (W - L) / (128 n) of every visited root action, -inf elsewhere."""
+        self._run(state, to_move, mask)
+        seen = self.last_visits > 0
+        vals = (self.last_wins - self.last_losses).to(torch.float32) / (self.last_visits.clamp(min=1) * 128).to(torch.float32)
+        return torch.where(seen, vals, torch.full_like(vals, float("-inf")))
+
+    def compute_actions(self, obs, mask=None) -> torch.Tensor:
+        """obs: int8 (N,3,3,13); mask: int8 (N,54) or None (the legal mask of the board)."""
+        obs = torch.as_tensor(obs).to(device=self.device, dtype=torch.int8).reshape(-1, 3, 3, 13).contiguous()
+        n = obs.shape[0]
+        state = torch.empty((n, nat.CELLS), dtype=torch.int8, device=self.device)
+        who = torch.empty(n, dtype=torch.int8, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.gbl_decode_obs(obs.data_ptr(), state.data_ptr(), who.data_ptr(), n, nat.current_stream(self.device)),
+                      "gbl_decode_obs")
+        return self._run(state, who, mask)
+
+    # -- reference-shaped entry points (as GreedyGobbletPolicy) ----------------------------------------------
+    def compute_action(self, obs, mask) -> np.ndarray:
+        return np.array(int(self.compute_actions(np.asarray(obs)[None], np.asarray(mask)[None])[0]))
+
+    def compute_actions_rllib(self, obs_batch):
+        observations = np.asarray(obs_batch["observation"])
+        observations = observations.reshape(observations.shape[0], 3, 3, -1)
+        return list(self.compute_actions(observations, np.asarray(obs_batch["action_mask"])).cpu().numpy())
+
+    def forward(self, batch, state=None, **kwargs):
+        """Tianshou-adapter shape: ``batch.obs.obs`` / ``batch.obs.mask`` (or dict keys "obs" / "mask") -> {"act": int64 (N,)}."""
+        ob = batch["obs"] if isinstance(batch, dict) else batch.obs
+        obs = ob["obs"] if isinstance(ob, dict) else ob.obs
+        mask = ob["mask"] if isinstance(ob, dict) else ob.mask
+        act = self.compute_actions(obs, torch.as_tensor(mask).to(torch.int8))
+        return {"act": act.to(torch.int64).cpu().numpy()}

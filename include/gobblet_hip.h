@@ -330,6 +330,78 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
                     int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
                     int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream);
 
+/* A small integer network that evaluates a position (no counterpart in the reference): 117 observation bytes -> H hidden units ->
+ * 54 action logits and a value.  The struct lives on the HOST; its four pointers are DEVICE pointers (host pointers in the host
+ * flavour), each 16-byte aligned (GBL_ERR_ALIGN), and the arrays are only read.
+ *   hidden  H, one of 64, 128, 192, 256
+ *   w1      int8  [117][H]       row f = the weights of observation byte f
+ *   b1      int32 [H]            |b1| <= 2^20
+ *   w2      int8  [H / 4][56][4] element [j / 4][k][j % 4] = the weight of hidden unit j for output k; outputs 0..53 are the action
+ *                                logits, 54 is the value, 55 is padding: o_55 follows the same rule and nothing reads it
+ *   b2      int32 [56]           |b2| <= 2^24
+ *   shift1, shift_p, shift_v     each in 0 .. 24
+ * The rule, for a position p with side s to move.  Integer-only: every shift is arithmetic (floor), every division an unsigned
+ * integer division, every operand stays inside int32, so that the kernels, the host flavour and a restatement of this text agree
+ * bit for bit.
+ *   x     = the 117 observation bytes of p as s observes it (gbl_observe with agent_sel = s); they are 0 or 1, at most 21 are 1
+ *   h_j   = clamp((b1_j + sum over f with x_f = 1 of w1[f][j]) >> shift1, 0, 127)                    j = 0 .. H - 1
+ *   o_k   = b2_k + sum over j of h_j * w2(j, k)                                                      k = 0 .. 55
+ *   value   q = clamp(o_54 >> shift_v, -128, 128), in 1/128 of a win for s
+ *   priors over a candidate set C of actions, C not empty:
+ *     l_a  = o_a >> shift_p                     (in 1/16 of an octave)
+ *     d_a  = min(max over C of l - l_a, 255)
+ *     e_a  = T[d_a & 15] >> (d_a >> 4),  T[k] = floor(65536 * 2^(-k / 16) + 0.5) =
+ *            65536 62757 60097 57549 55109 52773 50535 48393 46341 44376 42495 40693 38968 37316 35734 34219
+ *     pi_a = 1 + (e_a * 254) / (sum over C of e)    for a in C, a uint8 in 1 .. 255;  pi_a = 0 outside C */
+typedef struct {
+    const int8_t *w1;
+    const int32_t *b1;
+    const int8_t *w2;
+    const int32_t *b2;
+    int32_t hidden, shift1, shift_p, shift_v;
+} gbl_evaluator;
+
+/* The network alone, one evaluation per board from the side to move: C = mask[b] & the mover's legal mask (mask NULL: the legal
+ * mask).  Outputs:
+ *   priors_out uint8 [n][54] : pi over C; all zeros where C is empty        value_out int32[n] : q (also where C is empty)
+ *   logits_out int32 [n][56] : o_0 .. o_55 (may be NULL)
+ * state / to_move / mask are read a byte at a time and need NO alignment here (as gbl_tree_search); to_move and mask count as set
+ * wherever they are non-zero; value_out / logits_out must be 4-byte aligned (GBL_ERR_ALIGN).  Allocates nothing. */
+int gbl_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, uint8_t *priors_out,
+                 int32_t *value_out, int32_t *logits_out, int64_t n, void *stream);
+
+/* Evaluator-guided tree search: gbl_tree_search with the network above in place of the playouts, and with its priors steering the
+ * selection.  Deterministic and integer-only; it draws NOTHING -- there is no seed, no env_base and no call, two calls on the same
+ * boards give the same result, and a board's result does not depend on the batch it is in.  One launch is one decision: nothing
+ * persists between launches.  Per board with mover m = to_move[b], P = 128 throughout:
+ *   Nodes.  Nodes, what makes a node terminal, W / L / n and the root's candidates are those of gbl_tree_search.  Every node that is
+ *     not terminal also keeps the prior row pi over its own candidates, from the network's evaluation of the node's position (from
+ *     its side to move) at the moment the node is created; the root is created before iteration 0, and its q is root_value_out.
+ *     A root without a candidate: nothing is searched, action_out = -1, nodes_out = 1, the root's q is still written, everything
+ *     else is 0.
+ *   Iteration i = 0 .. iterations - 1:
+ *     1. Select.  Start at the root.  At a node v that is not terminal every candidate a of v gets
+ *          key(a) = mean + ((explore * pi_a * isqrt(n_v << 8)) >> 5) / (1 + n_c)
+ *        where, if a has a child c, mean = ((W_c - L_c + n_c P) << 15) / (n_c P) (gbl_tree_search's first term), and otherwise
+ *        mean = 32768 and n_c = 0.  Take the largest key, the lowest action on ties.  If that action has a child, go there and
+ *        repeat; if not, that action is the expansion.  A terminal node stops the selection and is evaluated itself.
+ *     2. Expand and evaluate.  The child is created.  Decided by check_for_winner() after the move: wins or losses = P, as in
+ *        gbl_tree_search.  Its side has no move: 0 and 0.  Otherwise the network evaluates the child's position from its side to
+ *        move, the child keeps that prior row (C = its legal mask), and for the side that moved INTO the child
+ *        wins = max(-q, 0), losses = max(q, 0).  A terminal node reached again counts its P or 0 / 0 again.
+ *     3. Back up.  As gbl_tree_search: n_v += 1, W_v += wins, L_v += losses from the leaf to the root, wins and losses swapping at
+ *        every level; the root only counts n.
+ * Outputs (each may be NULL): visits_out / wins_out / losses_out int32[n][54], action_out int32[n] (most visits, then the larger
+ * W - L, then the lowest action; -1 without a candidate) and nodes_out int32[n] as gbl_tree_search; root_value_out int32[n] = the
+ * root's q; root_priors_out uint8[n][54] = the root's prior row.
+ * 1 <= iterations <= 512, 0 <= explore <= 1024; the evaluator as above; states must be contract states (gbl_validate).
+ * state / to_move / mask are read a byte at a time and need NO alignment here; to_move and mask count as set wherever they are
+ * non-zero; the int32 outputs must be 4-byte aligned (GBL_ERR_ALIGN).
+ * Allocates nothing; the tree lives in 72 (iterations + 1) bytes of LDS per workgroup (16-byte nodes and 56-byte prior rows). */
+int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                         int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                         int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *stream);
+
 /* Trajectory collection (K plies per launch with EVERY ply materialised).  `plies` masked-random
  * plies with auto-reset in ONE launch; ply t (t = 0 .. plies-1) of board b leaves in element
  *     cell(t, b) = t * ply_stride + (b / 64) * tile_stride + b % 64
