@@ -5,6 +5,7 @@ of the evaluator that examples/example_train_evaluator.py trains.
 
     python scripts/bench_evaluator_policy.py [out.json]         on the GPU (default: profiles/r10/evaluator_policy.json)
     python scripts/bench_evaluator_policy.py --host [out.json]  the sweep and the arena alone, on the host flavour
+    python scripts/bench_evaluator_policy.py --timing [out.json]  the timing rows alone, on the GPU (the record's other sections stay)
 
 States: the stationary masked-random mix (BatchedGobblet(N, seed=11).rollout(64), as BASELINE config 5).  HIP-event times, one
 warm-up and 5 repetitions per point; the record keeps the median, and for the yardstick its minimum and maximum as well.  The
@@ -46,7 +47,7 @@ def event_ms(fn):
     return e0.elapsed_time(e1)
 
 
-def main(out_path):
+def main(out_path, with_sweep=True):
     env = G.BatchedGobblet(max(BOARDS), DEV, auto_reset=True, seed=11)
     env.rollout(64)
     torch.cuda.synchronize()
@@ -80,8 +81,9 @@ def main(out_path):
             print(evals[-1], flush=True)
     rec = {"metric": "gbl_tree_search_eval vs gbl_tree_search(iterations, 16 playouts), HIP-event ms per launch (median of %d)" % REPS,
            "device": torch.cuda.get_device_name(0), "rows": rows, "k_evaluate": evals}
-    rec.update(sweep(DEV, 256, (64, 256)))
-    merge(out_path, rec)
+    merge(out_path, rec)  # (the timing is kept even if the games below are cut short)
+    if with_sweep:
+        merge(out_path, sweep(DEV, 256, (64, 256)))
 
 
 def sweep(dev, games, arena_iterations):
@@ -111,8 +113,8 @@ def merge(out_path, sections):
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--host"]
+    args = [a for a in sys.argv[1:] if a not in ("--host", "--timing")]
     if "--host" in sys.argv[1:]:  # the sweep and the arena alone, on the host flavour (fewer games: it is the CPU playing them)
         merge(args[0] if args else DEFAULT_OUT, sweep("cpu", 128, (64,)))
     else:
-        main(args[0] if args else DEFAULT_OUT)
+        main(args[0] if args else DEFAULT_OUT, with_sweep="--timing" not in sys.argv[1:])

@@ -220,3 +220,186 @@ def run_search(lib, net, state, to_move, mask, iterations, explore):
 def same(got, exp, names):
     for name, g, e in zip(names, got, exp):
         assert g.dtype == e.dtype and np.array_equal(g, e), (name, np.argwhere(g != e)[:5])
+
+
+# ---- dial networks (H = 64): weight sets whose outputs are known in closed form ----------------------------------------------------
+DIAL_H = 64
+DIAL_DISTANCES = (0, 1, 15, 16, 17, 31, 32, 239, 240, 254, 255, 256, 1000)
+
+
+def _dial(b1=None, w2_jk=None, b2=None, shift1=0, shift_p=0, shift_v=0):
+    w2 = np.zeros((DIAL_H, 56), np.int8) if w2_jk is None else np.asarray(w2_jk, np.int8)
+    packed = np.ascontiguousarray(w2.reshape(DIAL_H // 4, 4, 56).transpose(0, 2, 1))
+    return Net(np.zeros((117, DIAL_H), np.int8), np.zeros(DIAL_H, np.int32) if b1 is None else np.asarray(b1, np.int32), packed,
+               np.zeros(56, np.int32) if b2 is None else np.asarray(b2, np.int32), shift1, shift_p, shift_v)
+
+
+def logit_dial(logits, shift_p=0, low_bits=0, o54=0, shift_v=0):
+    """w2 = 0: output k is b2[k] whatever the position.  b2[a] = (logits[a] << shift_p) + low_bits (0 <= low_bits < 2^shift_p: what
+    the floor must drop), so l_a = logits[a]; b2[54] = o54."""
+    assert 0 <= low_bits < (1 << shift_p) and len(logits) == 54
+    b2 = np.zeros(56, np.int64)
+    b2[:54] = (np.asarray(logits, np.int64) << shift_p) + low_bits
+    b2[54] = o54
+    assert np.abs(b2).max() <= 1 << 24
+    return _dial(b2=b2, shift_p=shift_p, shift_v=shift_v)
+
+
+def distance_dial(top, rotation, shift_p=0, low_bits=0, base=2000):
+    """A logit dial with the largest logit on action `top` and action a != top at distance DIAL_DISTANCES[(a + rotation) % 13] below
+    it: (net, the 54 distances)."""
+    dist = np.array([DIAL_DISTANCES[(a + rotation) % len(DIAL_DISTANCES)] for a in range(54)], np.int64)
+    dist[top] = 0
+    return logit_dial(base - dist, shift_p, low_bits), dist
+
+
+def value_dial(q_raw, shift_v, low_bits=0):
+    """o_54 >> shift_v = q_raw on every position."""
+    assert 0 <= low_bits < (1 << shift_v)
+    return logit_dial(np.zeros(54, np.int64), o54=(q_raw << shift_v) + low_bits, shift_v=shift_v)
+
+
+def hidden_dial(raw, shift1, low_bits=0):
+    """w1 = 0 and w2(j, k) = 1 for j == k < 54: logits_out[k] is hidden unit k, whose sum before the clamp is raw[k] (raw: 64 values;
+    b1_j = (raw[j] << shift1) + low_bits)."""
+    assert 0 <= low_bits < (1 << shift1) and len(raw) == DIAL_H
+    b1 = (np.asarray(raw, np.int64) << shift1) + low_bits
+    assert np.abs(b1).max() <= 1 << 20
+    w2 = np.zeros((DIAL_H, 56), np.int8)
+    w2[np.arange(54), np.arange(54)] = 1
+    return _dial(b1=b1, w2_jk=w2, shift1=shift1)
+
+
+def hidden_census(net, state, to_move):
+    """(units clamped at 0, units clamped at 127, units in between) over the boards: h = clamp(sum >> shift1, 0, 127) with the sum
+    >> shift1 <= 0, >= 127, or neither."""
+    pre = np.concatenate([hidden_sums(net, s, int(m != 0)) >> net.shift1 for s, m in zip(state, to_move)])
+    low, high = int((pre <= 0).sum()), int((pre >= 127).sum())
+    return low, high, len(pre) - low - high
+
+
+# ---- a float64 reference of the network and how far the integer rule may lie from it --------------------------------------------------
+def observations(state, to_move):
+    return np.stack([np.asarray(oracle.observe(s, int(m != 0), int(m != 0))["observation"], np.float64).reshape(117)
+                     for s, m in zip(state, to_move)])
+
+
+def float_mlp(x, w1, b1, w2, b2, cand, fold_ln2_16=None):
+    """The plain network: h = relu(x @ w1 + b1), out = h @ w2 + b2 (w2 (H, 55)), p = softmax of out[:54] over the candidates (base e;
+    base 2^(1/16) if the logits are already in 1/16 of an octave), v = clip(out[54], -1, 1).  Returns (pre-activations, p, v, out)."""
+    pre = x @ w1 + b1
+    out = np.maximum(pre, 0.0) @ w2 + b2
+    z = out[:, :54] * (1.0 if fold_ln2_16 is None else fold_ln2_16)
+    z = np.where(cand, z, -np.inf)
+    z = z - z.max(1, keepdims=True)
+    e = np.exp(z)
+    return pre, e / e.sum(1, keepdims=True), np.clip(out[:, 54], -1.0, 1.0), out
+
+
+def dequantised(ev):
+    """The float network that a from_float evaluator represents exactly: the integer weights over ev.scales, the fold undone."""
+    sc = ev.scales
+    w2q = ev.w2.cpu().numpy().transpose(0, 2, 1).reshape(ev.hidden, 56).astype(np.float64)
+    b2q = ev.b2.cpu().numpy().astype(np.float64)
+    w2 = np.concatenate([w2q[:, :54] / (sc["scale_p"] * sc["fold"]), w2q[:, 54:55] / sc["scale_v"]], 1)
+    b2 = np.concatenate([b2q[:54] / (sc["scale_p"] * sc["scale_h"] * sc["fold"]), b2q[54:55] / (sc["scale_v"] * sc["scale_h"])])
+    return ev.w1.cpu().numpy() / sc["scale1"], ev.b1.cpu().numpy() / sc["scale1"], w2, b2
+
+
+def prior_interval(p, cand, below, above):
+    """Where pi_a / sum(pi) of the integer rule may lie, given the float softmax p over the candidates `cand` (bool (N, 54)) and, per
+    action, how far the float logit L_a may lie from the integer one l_a in integer steps of 1/16 octave: -below_a <= L_a - l_a <=
+    above_a.  Three steps (derived in tests/test_evaluator_edges.py's docstring):
+      1. phat_a = 2^(l_a / 16) / sum: every weight 2^(L_c / 16) moves by a factor in [2^(-above_c / 16), 2^(below_c / 16)];
+      2. s_a = e_a / sum(e): every table entry is within 1.5 of 65536 * 2^(-d / 16) and sum(e) >= 65536, so |s_a - phat_a| <=
+         1.5 (1 + n) / 65536 with n candidates;
+      3. pi_a = 1 + floor(254 s_a) = 254 s_a + t_a, 0 < t_a <= 1: pi_a / sum(pi) lies in [254 s_a / (254 + n), s_a + 1 / 254].
+    Returns (lower, upper), zero outside the candidates."""
+    n = cand.sum(1, keepdims=True)
+    up_w, dn_w = np.where(cand, p * 2.0 ** (below / 16.0), 0.0), np.where(cand, p * 2.0 ** (-above / 16.0), 0.0)
+    hi = up_w / (up_w + (dn_w.sum(1, keepdims=True) - dn_w))
+    lo = dn_w / (dn_w + (up_w.sum(1, keepdims=True) - up_w))
+    gamma = 1.5 * (1 + n) / 65536.0
+    lower = np.maximum(lo - gamma, 0.0) * 254.0 / (254.0 + n)
+    upper = np.minimum(hi + gamma, 1.0) + 1.0 / 254.0
+    return np.where(cand, lower, 0.0), np.where(cand, upper, 0.0)
+
+
+def quantisation_bounds(ev, pre, w2, set_bytes, rounding):
+    """How far the integer rule of the from_float evaluator `ev` may lie from a float network with pre-activations `pre` (N, H) and
+    second layer `w2` (H, 55), from the float quantities alone.  rounding = False: the float network IS the dequantised one;
+    True: it is the one from_float was given, every weight and bias within half a unit of its scale.
+    With hs = relu(pre) * scale_h and rho = (set_bytes + 1) / 2 / 2^shift1 (0 without rounding), relu(hs) - h_j lies in [-rho, 1 + rho]
+    for every unit with hs > -rho and is 0 for the others; in units of the output's own integer step
+        L - o / 2^shift = (-eta_b + sum_j c_j (hs_j - h_j) - sum_j eta_j h_j) / 2^shift,  c = w2 * scale, |eta| <= 1/2 (0 without),
+    and the shift floors: L - l lies in [-below, above].  Returns (below (N, 54), above (N, 54), the bound on |q / 128 - v| (N,),
+    boards on which a unit could saturate at 127)."""
+    sc = ev.scales
+    hs = pre * sc["scale_h"]
+    rho = ((np.asarray(set_bytes, np.float64) + 1.0) / 2.0 / 2.0 ** ev.shift1)[:, None] if rounding else np.zeros((len(pre), 1))
+    live = (hs > -rho).astype(np.float64)
+    saturating = (hs + rho >= 128.0).any(1)
+    extra = (0.5 + 0.5 * (live * (np.maximum(hs, 0.0) + rho)).sum(1)) if rounding else np.zeros(len(pre))
+    c = np.concatenate([w2[:, :54] * sc["fold"] * sc["scale_p"], w2[:, 54:55] * sc["scale_v"]], 1)
+    pos, neg = np.maximum(c, 0.0), np.maximum(-c, 0.0)
+    up = (live * (1.0 + rho)) @ pos + (live * rho) @ neg + extra[:, None]  # L - o / 2^shift at most this, times 2^shift
+    dn = (live * (1.0 + rho)) @ neg + (live * rho) @ pos + extra[:, None]
+    above, below = up[:, :54] / 2.0 ** ev.shift_p + 1.0, dn[:, :54] / 2.0 ** ev.shift_p
+    v_bound = (np.maximum(up[:, 54], dn[:, 54]) / 2.0 ** ev.shift_v + 1.0) / 128.0
+    return below, above, v_bound, saturating
+
+
+def tv_bound(p, cand, below, above):
+    """A bound on the total variation between the float softmax p and pi / sum(pi), as the sum of three distances:
+      1. p to phat (the softmax of the integer logits): phat_a is proportional to p_a g_a with every g_a in [m, M] =
+         [2^(-max above / 16), 2^(max below / 16)]; the worst case is two points, (sqrt M - sqrt m) / (sqrt M + sqrt m);
+      2. phat to s = e / sum(e): half of sum_a 1.5 (1 + n phat_a) / 65536 = 1.5 n / 65536;
+      3. s to pi / sum(pi): with pi_a = 254 s_a + t_a, 0 < t_a <= 1 and t = sum(t), the distance is sum_a max(t_a - s_a t, 0) / (254 + t),
+         convex in every t_a, so largest at a corner: t_a = 1 on a set of k actions (the k with the smallest s), 0 elsewhere, which
+         gives sum over them of max(1 - k s_a, 0) / (254 + k); the largest over k, with s_a at its lower bound (prior_interval's).
+    Returns (N,)."""
+    out = np.zeros(len(p))
+    for b in range(len(p)):
+        c = cand[b]
+        n = int(c.sum())
+        span = (below[b, c].max() + above[b, c].max()) / 16.0 * math.log(2.0)
+        d1 = math.tanh(span / 4.0)
+        d2 = 1.5 * n / 65536.0
+        up_w, dn_w = p[b, c] * 2.0 ** (below[b, c] / 16.0), p[b, c] * 2.0 ** (-above[b, c] / 16.0)
+        s_lo = np.sort(np.maximum(dn_w / (dn_w + (up_w.sum() - up_w)) - 1.5 * (1 + n) / 65536.0, 0.0))
+        d3 = max(np.maximum(1.0 - k * s_lo[:k], 0.0).sum() / (254.0 + k) for k in range(1, n + 1))
+        out[b] = d1 + d2 + d3
+    return out
+
+
+def dial_boards(midgame, top):
+    """The positions the dial nets are read on: the empty board with either mover (54 candidates), a mid-game board, and the same
+    boards under masks that keep 27, 2 and 1 candidates (`top` among them wherever it is legal, then the legal actions after it).
+    Returns (state (9, 27), to_move (9,), mask (9, 54))."""
+    ms, mm = midgame
+    st = np.stack([np.zeros(27, np.int8), np.zeros(27, np.int8), ms] + [np.zeros(27, np.int8)] * 3 + [ms] * 3)
+    tm = np.array([0, 1, mm, 0, 1, 0, mm, mm, mm], np.int8)
+    mask = np.ones((9, 54), np.int8)
+    for b, keep in ((3, 27), (4, 2), (5, 1), (6, 27), (7, 2), (8, 1)):
+        legal = np.flatnonzero(oracle.legal_mask(st[b], int(tm[b])))
+        order = sorted(legal.tolist(), key=lambda a: ((a - top) % 54))  # top first if legal, then the legal actions after it
+        assert len(order) >= keep
+        mask[b] = 0
+        mask[b, order[:keep]] = 1
+    return np.ascontiguousarray(st), tm, mask
+
+
+def exact_priors(logit, cand):
+    """The header's sentence in exact integers, written out once more for the dial tests (no call into priors_of): (prior bytes,
+    {action: l_max - l_a before the cap})."""
+    acts = [int(a) for a in np.flatnonzero(cand)]
+    top = max(int(logit[a]) for a in acts)
+    raw = {a: top - int(logit[a]) for a in acts}
+    e = {}
+    for a in acts:
+        d = raw[a] if raw[a] < 255 else 255
+        e[a] = int(math.floor(65536 * 2.0 ** (-(d % 16) / 16) + 0.5)) // (2 ** (d // 16))
+    pi = np.zeros(54, np.uint8)
+    for a in acts:
+        pi[a] = 1 + (254 * e[a]) // sum(e.values())
+    return pi, raw

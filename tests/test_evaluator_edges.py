@@ -1,0 +1,309 @@
+"""The integer evaluator's edges on the host flavour (no GPU): dial networks whose outputs are known in closed form (every clamp, the
+prior table's index, octave shift and cap, the arithmetic floor of a negative sum), the shift triples the contract allows but no
+other test runs, a float64 reference of the network with derived bounds, and from_float's untested branches.
+
+The float comparison.  from_float keeps its power-of-two scales in ev.scales; scale_p * scale_h = 2^shift_p and
+scale_v * scale_h / 128 = 2^shift_v, so one integer logit step is 1/16 of an octave of the float softmax and one step of q is 1/128.
+  Hidden.  The integer sum of unit j is scale1 * (the float pre-activation) exactly for the dequantised weights, and within
+    (set bytes + 1) / 2 of it for the weights from_float was given (half a unit per rounded weight and bias; no weight is clipped,
+    because each scale keeps the largest magnitude at or below 127).  After >> shift1 and the clamp, relu(hs_j) - h_j lies in
+    [-rho, 1 + rho] (rho = (set bytes + 1) / 2^(shift1 + 1), 0 for the dequantised weights) as long as hs_j + rho < 128.
+  Output.  L_a - o_a / 2^shift_p = (-eta_b + sum_j c_ja (hs_j - h_j) - sum_j eta_ja h_j) / 2^shift_p with c = w2 * fold * scale_p and
+    |eta| <= 1/2 the roundings (0 for the dequantised weights); the final shift floors, which adds [0, 1).  That is the issue's
+    sum_j |w2q(j, a)| / 2^shift_p + 1 with the sign of each weight kept.  The value has the same form, and clip is 1-Lipschitz.
+  Priors.  tests/evaluator_restatement.py: prior_interval (per action) and tv_bound (total variation) carry the logit interval
+    through the table (every entry within 1.5 of 65536 * 2^(-d / 16)) and the byte 1 + floor(254 e / sum e).
+None of these bounds was fitted to the code under test: they are computed from the float network and the scales alone."""
+import numpy as np
+import pytest
+import torch
+
+import oracle
+
+import gobblet_rl_amd as G
+from gobblet_rl_amd import _native as nat
+from tests import evaluator_restatement as R
+from tests.test_playout_policy import random_midgames
+
+TOPS = (0, 26, 53)  # the largest logit on the first, a middle and the last lane of the wavefront butterfly
+SHIFT_TRIPLES = ((0, 0, 0), (3, 5, 12), (7, 0, 24), (1, 24, 0), (24, 24, 24))
+NARROW = {64: 0.0625, 256: 0.0625}  # comparison (b): the factor on uniform(-1, 1) / sqrt(H) at which the bounds reach 0.1
+
+
+@pytest.fixture(scope="module")
+def cpu():
+    L = nat.cpu_raw()
+    L.gbl_cpu_set_threads(4)
+    yield L
+    L.gbl_cpu_set_threads(0)
+
+
+@pytest.fixture(scope="module")
+def midgame():
+    ms, mt = random_midgames(8, seed=33, max_plies=12)
+    b = next(i for i in range(8) if oracle.check_for_winner(ms[i]) == 0 and (oracle.legal_mask(ms[i], int(mt[i])) != 0).sum() >= 27)
+    return ms[b].copy(), int(mt[b])
+
+
+@pytest.fixture(scope="module")
+def open_positions():
+    """60 open positions of both movers, 14 to 54 candidates."""
+    env = G.BatchedGobblet(120, "cpu", auto_reset=True, seed=11)
+    env.rollout(29)
+    st, tm = env.squares.numpy().copy(), env.to_move.numpy().copy()
+    keep = oracle.batch_winner(st) == 0
+    st, tm = np.ascontiguousarray(st[keep][:60]), np.ascontiguousarray(tm[keep][:60])
+    assert len(st) == 60 and 0.3 < tm.mean() < 0.7
+    return st, tm
+
+
+def three_flavours(cpu, net, st, tm, mask):
+    """(priors, value, logits) of the restatement, after asserting that the host flavour gives the same."""
+    exp = R.restate_evaluate(net, st, tm, mask)
+    R.same(R.run_evaluate(cpu, net, st, tm, mask), exp, R.EVAL_NAMES)
+    return exp
+
+
+def dial_cases():
+    """Every distance dial of the sweep: (top, rotation, shift_p, low_bits)."""
+    return [(top, rot, sp, low) for top in TOPS for rot in range(len(R.DIAL_DISTANCES)) for sp, low in ((0, 0), (4, 11))]
+
+
+def test_logit_dial_reaches_every_table_edge(cpu, midgame):
+    seen, bytes_of = set(), {}
+    for top, rot, sp, low in dial_cases():
+        net, dist = R.distance_dial(top, rot, sp, low)
+        st, tm, mask = R.dial_boards(midgame, top)
+        pri, val, log = three_flavours(cpu, net, st, tm, mask)
+        assert (val == 0).all() and np.array_equal(log[:, :54] >> sp, np.broadcast_to(2000 - dist, (len(st), 54)))
+        for b in range(len(st)):
+            cand = R.candidates(st[b], int(tm[b]), mask[b])
+            exp, raw = R.exact_priors(2000 - dist, cand)
+            assert np.array_equal(pri[b], exp), (top, rot, sp, b)
+            seen |= set(raw.values())
+            if len(raw) == 2 and top in raw:  # two candidates: the other one's byte is a function of its distance alone
+                (other,) = [a for a in raw if a != top]
+                bytes_of.setdefault(raw[other], set()).add(int(pri[b, other]))
+            if len(raw) == 1:
+                assert pri[b].max() == 255 and pri[b].sum() == 255
+    # every edge was reached, on a full root (54 candidates) and next to the top alone
+    assert seen >= set(R.DIAL_DISTANCES) and set(bytes_of) >= set(R.DIAL_DISTANCES) - {0}
+    assert all(len(v) == 1 for v in bytes_of.values())
+    byte = {d: next(iter(v)) for d, v in bytes_of.items()}
+    # d & 15 wraps and d >> 4 steps between 15 and 16, and between 31 and 32:  T[15] = 34219, then 65536 >> 1, 65536 >> 2
+    assert byte[1] == 1 + 254 * 62757 // (65536 + 62757) and byte[15] == 1 + 254 * 34219 // (65536 + 34219) == 88
+    assert byte[16] == 1 + 254 * 32768 // (65536 + 32768) == 85 and byte[17] == 1 + 254 * (62757 >> 1) // (65536 + (62757 >> 1))
+    assert byte[31] == 1 + 254 * (34219 >> 1) // (65536 + (34219 >> 1)) == 53 and byte[32] == 1 + 254 * 16384 // (65536 + 16384) == 51
+    # the cap: 255, 256 and 1000 read the same entry (an uncapped 1000 >> 4 would shift by 62)
+    assert byte[255] == byte[256] == byte[1000] == 1 and byte[239] == byte[240] == byte[254] == 1
+
+
+def test_full_root_shows_the_cap_in_the_top_byte(cpu):
+    """54 candidates, 53 of them 1000 below the top: each still counts e = T[15] >> 15 = 1, so the top's byte is
+    1 + 254 * 65536 // (65536 + 53) = 254; with the distance not capped (e = 0) it would be 255.  (A cap at 254 instead of 255 cannot
+    be told apart by any input: T[14] >> 15 = T[15] >> 15 = 1.)"""
+    st, tm = np.zeros((2, 27), np.int8), np.array([0, 1], np.int8)
+    for top in TOPS:
+        for far in (255, 256, 1000):
+            logit = np.full(54, -far, np.int64)
+            logit[top] = 0
+            pri, _, _ = three_flavours(cpu, R.logit_dial(logit), st, tm, None)
+            assert (pri[:, top] == 254).all() and pri.sum() == 2 * (254 + 53)
+    assert (34219 >> 15) == (35734 >> 15) == 1
+
+
+def test_widest_logits_of_the_contract(cpu, midgame):
+    """b2 = +-2^24 at shift_p = 0: the largest difference of two logits the contract allows, 2^25, is capped like 255."""
+    for top in TOPS:
+        logit = np.full(54, -(1 << 24), np.int64)
+        logit[top] = 1 << 24
+        logit[(top + 7) % 54] = 1 << 24  # a second action at the top: d = 0 twice
+        st, tm, mask = R.dial_boards(midgame, top)
+        pri, _, log = three_flavours(cpu, R.logit_dial(logit), st, tm, mask)
+        assert log[:, :54].max() == 1 << 24 and log[:, :54].min() == -(1 << 24)
+        for b in range(len(st)):
+            exp, raw = R.exact_priors(logit, R.candidates(st[b], int(tm[b]), mask[b]))
+            assert np.array_equal(pri[b], exp) and set(raw.values()) <= {0, 1 << 25}
+        assert pri[0, top] == pri[0, (top + 7) % 54] == 1 + 254 * 65536 // (2 * 65536 + 52) == 127
+
+
+def test_negative_sums_floor_under_the_largest_shift(cpu):
+    """-1 >> 24 = -1 (an arithmetic shift floors; a division or a logical shift would give 0 or 255): at shift_p = 24 the logits -1 and
+    0 are one step apart, and at shift_v = 24 o_54 = -1 is q = -1."""
+    st, tm = np.zeros((2, 27), np.int8), np.array([0, 1], np.int8)
+    b2 = np.zeros(56, np.int32)
+    b2[1::2] = -1
+    b2[54] = -1
+    net = R._dial(b2=b2, shift_p=24, shift_v=24)
+    mask = np.zeros((2, 54), np.int8)
+    mask[0], mask[1, :2] = 1, 1  # all 54 candidates; actions 0 (l = 0) and 1 (l = -1) alone
+    pri, val, log = three_flavours(cpu, net, st, tm, mask)
+    assert (val == -1).all() and (log[:, 1:54:2] == -1).all()
+    total = 27 * 65536 + 27 * 62757
+    assert (pri[0, 0::2] == 1 + 254 * 65536 // total).all() and (pri[0, 1::2] == 1 + 254 * 62757 // total).all()
+    assert pri[1, 0] == 1 + 254 * 65536 // (65536 + 62757) == 130 and pri[1, 1] == 1 + 254 * 62757 // (65536 + 62757) == 125
+    assert (three_flavours(cpu, R._dial(b2=b2 * 0 + np.eye(56, dtype=np.int32)[54] * ((1 << 24) - 1), shift_v=24), st, tm, None)[1] == 0).all()
+
+
+@pytest.mark.parametrize("shift_v", [0, 7])
+def test_value_dial_clamps_at_128_either_way(cpu, shift_v):
+    st, tm = np.zeros((2, 27), np.int8), np.array([0, 1], np.int8)
+    got = {}
+    for raw in (-129, -128, -127, -1, 0, 127, 128, 129):
+        for low in sorted({0, (1 << shift_v) - 1}):
+            _, val, log = three_flavours(cpu, R.value_dial(raw, shift_v, low), st, tm, None)
+            assert (log[:, 54] >> shift_v == raw).all() and val[0] == val[1]
+            got.setdefault(raw, set()).add(int(val[0]))
+    assert got == {-129: {-128}, -128: {-128}, -127: {-127}, -1: {-1}, 0: {0}, 127: {127}, 128: {128}, 129: {128}}
+
+
+@pytest.mark.parametrize("shift1", [0, 5, 13])
+def test_hidden_dial_clamps_at_0_and_127(cpu, shift1):
+    """(At shift1 = 13 the raw value 300 needs b1 = 300 * 2^13 > 2^20, which the contract refuses: 128 = 2^20 >> 13 is the largest.)"""
+    values = [v for v in (-2, -1, 0, 1, 126, 127, 128, 300) if abs(v) << shift1 <= 1 << 20]
+    assert len(values) == (7 if shift1 == 13 else 8)
+    st, tm = np.zeros((2, 27), np.int8), np.array([0, 1], np.int8)
+    for low in sorted({0, (1 << shift1) - 1}):
+        raw = np.array([values[j % len(values)] for j in range(64)])
+        use_low = np.where((np.abs(raw) << shift1) + low <= 1 << 20, low, 0)  # (128 at shift1 = 13 is 2^20 itself)
+        net = R.hidden_dial(raw, shift1)
+        net.b1 += use_low.astype(np.int32)
+        assert np.abs(net.b1).max() <= 1 << 20 and np.array_equal(net.b1.astype(np.int64) >> shift1, raw)
+        _, _, log = three_flavours(cpu, net, st, tm, None)
+        assert np.array_equal(log[:, :54], np.broadcast_to(np.clip(raw[:54], 0, 127), (2, 54)))
+        assert set(log[0, :54].tolist()) == {0, 1, 126, 127} and (log[:, 54:] == 0).all()
+
+
+def test_hidden_units_read_zero_at_shift_24(cpu):
+    st, tm = np.zeros((2, 27), np.int8), np.array([0, 1], np.int8)
+    for b1 in (1 << 20, -(1 << 20)):
+        net = R.hidden_dial(np.zeros(64, np.int64), 24)
+        net.b1[:] = b1
+        assert (three_flavours(cpu, net, st, tm, None)[2] == 0).all()
+
+
+def search_dial(top):
+    """One action 600 steps above the rest, q = 0 everywhere."""
+    logit = np.zeros(54, np.int64)
+    logit[top] = 600
+    return R.logit_dial(logit)
+
+
+def test_search_on_a_logit_dial_at_the_largest_key(cpu, midgame):
+    """explore = 1024, 512 iterations: under a root with one candidate (prior 255) the key's second term reaches
+    (1024 * 255 * isqrt(511 << 8)) >> 5, the largest its comment allows for."""
+    top = 26
+    st, tm, mask = R.dial_boards(midgame, top)
+    st, tm, mask = st[[5, 0]], tm[[5, 0]], mask[[5, 0]]  # one candidate; all 54
+    net = search_dial(top)
+    got = R.run_search(cpu, net, st, tm, mask, 512, 1024)
+    R.same(got, R.restate_search(net, st, tm, mask, 512, 1024), R.SEARCH_NAMES)
+    v, w, l, a, nd, rv, rp = got
+    assert rp[0].max() == 255 and (rp[0] > 0).sum() == 1 and v[0, top] == 512 and a[0] == top
+    assert (rp[1] > 0).sum() == 54 and rp[1, top] == 254 and v[1].sum() == 512 and (rv == 0).all()
+
+
+# ---- the shift sweep --------------------------------------------------------------------------------------------------------------
+# (clamped at 0, clamped at 127, in between) of the hidden units of random_net(hidden, 40 + hidden, ...) on the 60 open positions,
+# as the restatement counts them
+@pytest.mark.parametrize("hidden", [64, 256])
+@pytest.mark.parametrize("shifts", SHIFT_TRIPLES)
+def test_shift_sweep_evaluate_and_search(cpu, open_positions, hidden, shifts):
+    st, tm = open_positions
+    net = R.random_net(hidden, 40 + hidden, *shifts)
+    mask = (np.random.default_rng(7).random((len(st), 54)) < 0.5).astype(np.int8)
+    for mk in (None, mask):
+        three_flavours(cpu, net, st, tm, mk)
+    low, high, mid = R.hidden_census(net, st, tm)
+    total = 60 * hidden
+    print("shifts %s H %d: hidden units clamped at 0: %d, at 127: %d, in between: %d" % (shifts, hidden, low, high, mid))
+    assert low + high + mid == total
+    if shifts[0] == 0:  # sums of a few hundred either way: most units are clamped, low or high (49 + 33 % and 50 + 32 % of them)
+        assert low > 0.4 * total and high > 0.3 * total and 0 < mid < 0.2 * total
+    elif shifts[0] in (1, 3):  # all three kinds; after >> 3 a handful of units (4 and 5 of them) still reach 127
+        assert low > 0.4 * total and mid > 0.25 * total and high > 0
+    elif shifts[0] == 7:  # |sum| >> 7 never reaches 127
+        assert low > 0.4 * total and mid > 0.3 * total and high == 0
+    else:  # 24: |sum| < 2^21, so every unit reads 0 or -1 before the clamp
+        assert (low, high, mid) == (total, 0, 0)
+    if hidden == 64:
+        R.same(R.run_search(cpu, net, st[:6], tm[:6], mask[:6], 48, 16), R.restate_search(net, st[:6], tm[:6], mask[:6], 48, 16), R.SEARCH_NAMES)
+
+
+# ---- the float64 reference ----------------------------------------------------------------------------------------------------------
+def float_weights(hidden, seed, narrow=1.0):
+    """Off any grid.  A sparse first layer (8 % of uniform(-1, 1)) keeps from_float's default hidden_max -- the bound b1_j + the 21
+    largest positive weights of unit j -- near what positions reach, so that a hidden step is small against the activations; the
+    second layer is uniform(-1, 1) / sqrt(H) times `narrow`."""
+    rng = np.random.default_rng(seed)
+    w1 = rng.uniform(-1, 1, (117, hidden)) * (rng.random((117, hidden)) < 0.08)
+    return w1, rng.uniform(-0.5, 0.5, hidden), rng.uniform(-1, 1, (hidden, 55)) / np.sqrt(hidden) * narrow, rng.uniform(-1, 1, 55)
+
+
+def compare_with_float(ev, weights, st, tm, rounding, evaluate=None):
+    """The integer evaluator against the float network `weights`: asserts the per-action interval, the total variation and the
+    value against their bounds, and returns (tv bound, value bound, tv, value error) per board."""
+    cand = oracle.batch_legal_mask(st, tm) != 0
+    x = R.observations(st, tm)
+    pre, p, v, _ = R.float_mlp(x, *weights, cand)
+    below, above, v_bound, saturating = R.quantisation_bounds(ev, pre, weights[2], x.sum(1), rounding)
+    assert not saturating.any()  # (the share of boards excluded is 0 for these weights)
+    lower, upper = R.prior_interval(p, cand, below, above)
+    tv_b = R.tv_bound(p, cand, below, above)
+    pri, val = (ev.evaluate if evaluate is None else evaluate)(torch.from_numpy(st), torch.from_numpy(tm))
+    pri, val = pri.cpu().numpy().astype(np.float64), val.cpu().numpy().astype(np.float64)
+    tv, dv = 0.5 * np.abs(pri - p).sum(1), np.abs(val - v)
+    print("rounding %s H %d shifts (%d, %d, %d): tv %.4f max against bound %.4f median; |dv| %.4f max against %.4f median" %
+          (rounding, ev.hidden, ev.shift1, ev.shift_p, ev.shift_v, tv.max(), np.median(tv_b), dv.max(), np.median(v_bound)))
+    assert (pri >= lower - 1e-9).all() and (pri <= upper + 1e-9).all(), np.argwhere((pri < lower - 1e-9) | (pri > upper + 1e-9))[:5]
+    assert (tv <= tv_b + 1e-9).all() and (dv <= v_bound + 1e-9).all()
+    return tv_b, v_bound, tv, dv
+
+
+@pytest.mark.parametrize("hidden", [64, 256])
+def test_dequantised_weights_against_the_float_reference(open_positions, hidden):
+    """(a): the reference runs the integer weights over ev.scales; only the three floors and the prior table separate the two."""
+    st, tm = open_positions
+    for seed, narrow in ((1, 1.0), (2, NARROW[hidden])):
+        ev = G.GobbletEvaluator.from_float(*float_weights(hidden, seed, narrow))
+        compare_with_float(ev, R.dequantised(ev), st, tm, rounding=False)
+
+
+@pytest.mark.parametrize("hidden", [64, 256])
+def test_original_float_weights_against_the_float_reference(open_positions, hidden):
+    """(b): the reference runs the weights from_float was given (default hidden_max, natural_log, off any grid).  With the second
+    layer at uniform(-1, 1) / sqrt(H) the worst-case bounds do not reach 0.1 on any of the 60 positions (total variation bound:
+    median 0.26 at H = 64 and 0.41 at H = 256, value bound 0.35 and 0.62, against 0.04 and 0.04 measured: the bounds add |w2| over
+    every live unit, the errors add like a random walk), so the weights are narrowed, not the assertion: the second layer by
+    NARROW[H] = 1/16.  The share of positions with both bounds at most 0.1 is then 1.00 at H = 64 and 0.90 at H = 256 (about 0.05
+    of either bound is the byte 1 + floor(254 e / sum e) alone, which no weight narrows)."""
+    st, tm = open_positions
+    weights = float_weights(hidden, 3, NARROW[hidden])
+    ev = G.GobbletEvaluator.from_float(*weights)
+    assert ev.scales["fold"] == G.evaluator_policy.LOG2E_16
+    tv_b, v_b, _, _ = compare_with_float(ev, weights, st, tm, rounding=True)
+    share = float(((tv_b <= 0.1) & (v_b <= 0.1)).mean())
+    print("H %d: share of positions with both bounds at most 0.1: %.3f" % (hidden, share))
+    assert share >= 0.9
+
+
+def test_from_float_rescales_a_shift_above_24(open_positions):
+    """Output weights of 2^-22: the scale that fills int8 would need a shift near 40; from_float lowers the scales until it is 24."""
+    st, tm = open_positions
+    w1, b1, w2, b2 = float_weights(64, 4)
+    w2, b2 = w2 * 2.0 ** -22, b2 * 2.0 ** -8
+    ev = G.GobbletEvaluator.from_float(w1, b1, w2, b2)
+    assert (ev.shift_p, ev.shift_v) == (24, 24) and ev.scales["scale_p"] * ev.scales["scale_h"] == 2.0 ** 24
+    assert ev.scales["scale_v"] * ev.scales["scale_h"] == 2.0 ** 31
+    compare_with_float(ev, R.dequantised(ev), st, tm, rounding=False)
+    assert np.abs(ev.b2.numpy()[:54]).max() > 1000  # (the biases still spread the logits: the comparison is not of zeros)
+
+
+def test_from_float_refuses_a_negative_shift():
+    w1, b1, w2, b2 = float_weights(64, 5)
+    with pytest.raises(ValueError):
+        G.GobbletEvaluator.from_float(w1, b1, w2 * 2.0 ** 12, b2)  # the policy shift
+    big_v = w2.copy()
+    big_v[:, 54] *= 2.0 ** 16
+    with pytest.raises(ValueError):
+        G.GobbletEvaluator.from_float(w1, b1, big_v, b2)  # the value shift alone
