@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The loop closed end to end: tree-vs-tree self-play -> (obs, pi, z) targets -> a 117-H-55 MLP fitted in torch -> the integer
-evaluator -> the evaluator-guided search against the playout search at equal iterations:
-    python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G]"""
+evaluator -> the evaluator-guided search against the playout search at equal iterations; with --generations G > 1 the loop goes
+round: generation k collects with generation k - 1's evaluator on both sides INSIDE one launch (gbl_collect_search_eval), fits a
+new network and plays it against the old one, one launch per colour:
+    python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G] [--generations G]"""
 import argparse
 import os
 import sys
@@ -18,11 +20,38 @@ def collect_targets(device, boards, plies, iterations, seed=0):
     search = dict(iterations=iterations, playouts=8, max_plies=64, explore=16, sample_plies=4)
     traj = env.collect(plies, policies=("tree", "tree"), search=search)
     env.outcome_targets(traj)
+    return targets_of(traj, boards, plies)
+
+
+def targets_of(traj, boards, plies):
+    """(obs, pi, z) of the plies of finished games of a collected window with search outputs and outcome targets."""
     obs = traj["observation"][:-1].reshape(plies - 1, boards, 117)   # what the mover of ply t saw is slot t - 1
     visits, z = traj["visits"][1:].float(), traj["z"][1:]
     keep = (z != G._native.Z_OPEN) & (traj["done"][:-1] == 0) & (visits.sum(-1) > 0)  # (after a finished game slot t - 1 is a fresh board)
     pi = visits / visits.sum(-1, keepdim=True).clamp(min=1)
     return obs[keep].float().cpu(), pi[keep].cpu(), z[keep].float().cpu()
+
+
+def collect_targets_with(ev, device, boards, plies, iterations, seed=0):
+    """collect_targets with the evaluator-guided search of `ev` on both sides, the first four plies of every game drawn in proportion
+    to the visits: one launch for the whole window."""
+    env = G.BatchedGobblet(boards, device, auto_reset=True, seed=seed, track_turn=True)
+    traj = env.collect(plies, policies=("evaluator", "evaluator"), search=dict(evaluator=ev, iterations=iterations, sample_plies=4))
+    env.outcome_targets(traj)
+    return targets_of(traj, boards, plies)
+
+
+def arena_in_one_launch(new, old, device, games, plies, iterations, seed=7):
+    """`new` against `old`, half the boards' games with either colour, each half ONE launch with auto-reset: every board plays game
+    after game for `plies` plies and the wins are read from the counters.  (new wins, old wins, games finished)."""
+    wins, losses, finished = 0, 0, 0
+    for nets in ((new, old), (old, new)):
+        env = G.BatchedGobblet(max(games // 2, 1), device, auto_reset=True, seed=seed)
+        env.collect(plies, policies=("evaluator", "evaluator"), search=dict(evaluator=nets, iterations=iterations), count=True, refresh=False)
+        c = env.counters  # (plies, games finished, player_1 wins, player_2 wins)
+        w1, w2 = int(c[2]), int(c[3])
+        wins, losses, finished = wins + (w1 if nets[0] is new else w2), losses + (w2 if nets[0] is new else w1), finished + int(c[1])
+    return wins, losses, finished
 
 
 def fit(obs, pi, z, hidden, steps, seed=0):
@@ -80,8 +109,18 @@ if __name__ == "__main__":
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--iterations", type=int, default=64)
     ap.add_argument("--games", type=int, default=128)
+    ap.add_argument("--generations", type=int, default=1)
+    ap.add_argument("--selfplay-iterations", type=int, default=64, help="iterations of the evaluator search in generations >= 2")
     a = ap.parse_args()
     ev, samples, loss = train_evaluator(a.device, a.boards, a.plies, a.steps, a.hidden)
     print("trained on", samples, "plies; final loss", round(loss, 3), "; scales", ev.scales, "shifts", (ev.shift1, ev.shift_p, ev.shift_v))
     w, l, d = score(ev, a.device, a.iterations, a.games)
     print("evaluator search vs playout search at %d iterations: %d wins, %d losses, %d unfinished of %d games" % (a.iterations, w, l, d, w + l + d))
+    for gen in range(2, a.generations + 1):
+        obs, pi, z = collect_targets_with(ev, a.device, a.boards, a.plies, a.selfplay_iterations, seed=gen)
+        weights, hmax, loss = fit(obs, pi, z, a.hidden, a.steps, seed=gen)
+        new = G.GobbletEvaluator.from_float(*weights, hidden_max=hmax, device=a.device)
+        w, l, n = arena_in_one_launch(new, ev, a.device, a.games, a.plies, a.selfplay_iterations)
+        print("generation %d: trained on %d plies of generation %d's self-play, final loss %.3f; arena against generation %d at %d "
+              "iterations: %d wins, %d losses of %d finished games" % (gen, len(obs), gen - 1, loss, gen - 1, a.selfplay_iterations, w, l, n))
+        ev = new

@@ -34,6 +34,7 @@ ILLEGAL_NOOP, ILLEGAL_TERMINATE = 0, 1
 POLICY_RANDOM, POLICY_GREEDY1, POLICY_GREEDY2, POLICY_GREEDY3 = 0, 1, 2, 3  # gbl_collect_policy
 HOW_RANDOM, HOW_GREEDY, HOW_FALLBACK = 0, 1, 2
 POLICY_TREE, HOW_SEARCH, HOW_SEARCH_SAMPLED, Z_OPEN = 4, 3, 4, -128  # gbl_collect_search / gbl_outcome_targets
+POLICY_EVAL_TREE = 5  # gbl_collect_search_eval
 STATUS_ILLEGAL, STATUS_OUT_OF_RANGE = 1, 2  # gbl_step_ex / gbl_collect_from_ex status bits
 CELLS, ACTIONS, OBS_BYTES = 27, 54, 117
 COUNTER_STRIPES, COUNTER_STRIDE = 64, 16
@@ -82,6 +83,8 @@ SIGNATURES = {
     "gbl_collect_from_ex": (_int, [_vp] * 12 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _vp, _vp, _vp]),
     "gbl_collect_policy": (_int, [_vp] * 14 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _int, _int, _vp, _vp, _vp]),
     "gbl_collect_search": (_int, [_vp] * 15 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32] + [_int] * 10 + [_vp, _vp, _vp]),
+    "gbl_collect_search_eval": (_int, [_vp] * 17 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 5 +
+                                [_vp, _vp, _vp]),
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_collect_variant": (_int, [_i64, _u32, _int, _int]),
     "gbl_block_alloc": (_int, [_i64, C.POINTER(_vp)]),

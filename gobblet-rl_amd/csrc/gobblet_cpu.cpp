@@ -933,6 +933,96 @@ int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t 
     return GBL_OK;
 }
 
+// The boards [b0, b1) of a self-play window, for gbl_cpu_collect_search and gbl_cpu_collect_search_eval: per ply the mover's search
+// (`search(p, who, legal, g, q, h)`: false where the masked-random sampler moves, else it fills h and returns true), the decision
+// or the visit-proportional draw, the step with auto-reset and the ply's cell of every trajectory array.
+struct SelfplayTraj {
+    int32_t *actions;
+    int8_t *winner, *reward, *done, *to_move, *mask, *obs;
+    int16_t *visits;
+    int32_t *value, *nodes;
+    int8_t *how, *mover;
+    int32_t *root_value;  // (the evaluator search's two: NULL in gbl_cpu_collect_search)
+    uint8_t *priors;
+};
+
+struct SelfplaySearch {
+    HostSearch h;
+    int32_t root_q;
+    const uint8_t *priors;  // the root's prior row, or NULL
+};
+
+extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
+template <typename Search>
+static void selfplay_boards(int64_t b0, int64_t b1, int8_t *state, int8_t *to_move, int8_t *done, const SelfplayTraj &T, int64_t ply_stride,
+                            int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, uint32_t plies, int sample_plies,
+                            int illegal_mode, int64_t *counters, int32_t *turn, Search &&search)
+{
+    Tally tl;
+    SelfplaySearch S{};
+    HostSearch &h = S.h;
+    for (int64_t b = b0; b < b1; ++b) {
+        uint32_t r[7];
+        load_row(state, b, r);
+        Planes p = make_planes(r);
+        const HostRow row{reinterpret_cast<uint8_t *>(state) + b * kCells};
+        const uint64_t g = env_base + (uint64_t)b;
+        int mover = to_move[b] != 0, dn = 0, tabs = turn ? turn[b] : 0;
+        uint64_t legal = legal54(p, mover);
+        for (uint32_t t = 0; t < plies; ++t) {
+            const uint32_t q = ply0 + t;
+            const int who = mover;
+            S.root_q = 0;
+            S.priors = nullptr;
+            const bool tree = search(p, who, legal, g, q, S);
+            int action, how = GBL_HOW_RANDOM, value = 0;
+            if (tree) {
+                const bool sampled = tabs < sample_plies;
+                action = sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit)) : tree_action_of(h.best);
+                how = sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
+                for (int a = 0; a < kActions; ++a) value += h.wins[a] - h.losses[a];
+            } else {
+                action = sample54(legal, seed, g, q);
+            }
+            const Ply y = play_ply(p, row, mover, legal, action, illegal_mode);
+            dn = y.terminal ? 1 : 0;
+            if (y.terminal) {
+                p = Planes{0u, 0u, 0u};
+                mover = 0;
+                row.reset();
+            }
+            tabs = next_turn(tabs, y, 1);
+            tl.games += y.terminal; tl.w1 += y.winner == 1; tl.w2 += y.winner == -1;
+            legal = next_mask(p, mover, dn, 1);
+            const int64_t at = cell_of(b, t, ply_stride, tile_stride);
+            if (T.actions) T.actions[at] = action;
+            if (T.winner) T.winner[at] = (int8_t)y.winner;
+            if (T.reward) { T.reward[2 * at] = (int8_t)y.r0; T.reward[2 * at + 1] = (int8_t)y.r1; }
+            if (T.done) T.done[at] = (int8_t)dn;
+            if (T.to_move) T.to_move[at] = (int8_t)mover;
+            if (T.visits)
+                for (int a = 0; a < kActions; ++a) T.visits[at * kActions + a] = (int16_t)(tree ? h.visits[a] : 0);
+            if (T.value) T.value[at] = value;
+            if (T.nodes) T.nodes[at] = tree ? (int32_t)h.count : 0;
+            if (T.how) T.how[at] = (int8_t)how;
+            if (T.mover) T.mover[at] = (int8_t)who;
+            if (T.root_value) T.root_value[at] = S.root_q;
+            if (T.priors) {
+                if (S.priors) memcpy(T.priors + at * kActions, S.priors, kActions);
+                else memset(T.priors + at * kActions, 0, kActions);
+            }
+            if (T.obs) write_obs(T.obs + at * kObs, p, mover);
+            if (T.mask) write_mask(T.mask + at * kActions, legal);
+        }
+        tl.plies += plies;
+        to_move[b] = (int8_t)mover;
+        done[b] = (int8_t)dn;
+        if (turn) turn[b] = tabs;
+    }
+    add_tally(counters, tl);
+}
+}  // extern "C++"
+
 int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
                            int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
                            int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int64_t n, int64_t ply_stride,
@@ -941,8 +1031,7 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
                            int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
+    if (const char *why = illegal_mode_error(illegal_mode)) return fail(GBL_ERR_ARG, why);
     if ((policy0 != GBL_POLICY_RANDOM && policy0 != GBL_POLICY_TREE) || (policy1 != GBL_POLICY_RANDOM && policy1 != GBL_POLICY_TREE))
         return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE");
     const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
@@ -951,74 +1040,69 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
         if (const char *why = tree_budget_error(its[m], pls[m])) return fail(GBL_ERR_ARG, why);
     }
     if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
-    if (sample_plies < 0) return fail(GBL_ERR_ARG, "sample_plies < 0");
-    if (sample_plies > 0 && !turn) return fail(GBL_ERR_ARG, "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)");
-    if ((uint64_t)ply0 + plies > (1ull << 24)) return fail(GBL_ERR_ARG, "ply0 + plies must not exceed 2^24 (the search's call index)");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = selfplay_window_error(sample_plies, turn != nullptr, ply0, plies, env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;
     if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     if (ply_dev) ply0 += *ply_dev;
     const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
+    const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                         nodes_traj, how_traj, mover_traj, nullptr, nullptr};
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
-        Tally tl;
         std::vector<TreeNode> nodes((size_t)most + 1);
-        HostSearch h;
-        for (int64_t b = b0; b < b1; ++b) {
-            uint32_t r[7];
-            load_row(state, b, r);
-            Planes p = make_planes(r);
-            const HostRow row{reinterpret_cast<uint8_t *>(state) + b * kCells};
-            const uint64_t g = env_base + (uint64_t)b;
-            int mover = to_move[b] != 0, dn = 0, tabs = turn ? turn[b] : 0;
-            uint64_t legal = legal54(p, mover);
-            for (uint32_t t = 0; t < plies; ++t) {
-                const uint32_t q = ply0 + t;
-                const int who = mover;
-                const bool tree = pol[who] == GBL_POLICY_TREE;
-                int action, how = GBL_HOW_RANDOM, value = 0;
-                if (tree) {
-                    host_tree_search(nodes, p, who, legal, g, (uint32_t)its[who], (uint32_t)pls[who], (uint32_t)max_plies, (uint32_t)explore, seed,
-                                     q, h);
-                    const bool sampled = tabs < sample_plies;
-                    action = sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit)) : tree_action_of(h.best);
-                    how = sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
-                    for (int a = 0; a < kActions; ++a) value += h.wins[a] - h.losses[a];
-                } else {
-                    action = sample54(legal, seed, g, q);
-                }
-                const Ply y = play_ply(p, row, mover, legal, action, illegal_mode);
-                dn = y.terminal ? 1 : 0;
-                if (y.terminal) {
-                    p = Planes{0u, 0u, 0u};
-                    mover = 0;
-                    row.reset();
-                }
-                tabs = next_turn(tabs, y, 1);
-                tl.games += y.terminal; tl.w1 += y.winner == 1; tl.w2 += y.winner == -1;
-                legal = next_mask(p, mover, dn, 1);
-                const int64_t at = cell_of(b, t, ply_stride, tile_stride);
-                if (actions_traj) actions_traj[at] = action;
-                if (winner_traj) winner_traj[at] = (int8_t)y.winner;
-                if (reward_traj) { reward_traj[2 * at] = (int8_t)y.r0; reward_traj[2 * at + 1] = (int8_t)y.r1; }
-                if (done_traj) done_traj[at] = (int8_t)dn;
-                if (to_move_traj) to_move_traj[at] = (int8_t)mover;
-                if (visits_traj)
-                    for (int a = 0; a < kActions; ++a) visits_traj[at * kActions + a] = (int16_t)(tree ? h.visits[a] : 0);
-                if (value_traj) value_traj[at] = value;
-                if (nodes_traj) nodes_traj[at] = tree ? (int32_t)h.count : 0;
-                if (how_traj) how_traj[at] = (int8_t)how;
-                if (mover_traj) mover_traj[at] = (int8_t)who;
-                if (obs_traj) write_obs(obs_traj + at * kObs, p, mover);
-                if (mask_traj) write_mask(mask_traj + at * kActions, legal);
-            }
-            tl.plies += plies;
-            to_move[b] = (int8_t)mover;
-            done[b] = (int8_t)dn;
-            if (turn) turn[b] = tabs;
-        }
-        add_tally(counters, tl);
+        selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
+                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t g, uint32_t q, SelfplaySearch &S) {
+                            if (pol[who] != GBL_POLICY_TREE) return false;
+                            host_tree_search(nodes, p, who, legal, g, (uint32_t)its[who], (uint32_t)pls[who], (uint32_t)max_plies,
+                                             (uint32_t)explore, seed, q, S.h);
+                            return true;
+                        });
+    }, 1);
+    return GBL_OK;
+}
+
+int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                                int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
+                                uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
+                                int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                                int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = collect_eval_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, explore, sample_plies,
+                                             turn != nullptr, ply0, plies, env_base, n))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (plies == 0) return GBL_OK;
+    const gbl_evaluator *evs[2] = {ev0, ev1};
+    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
+    EvalNet nets[2] = {};
+    int most = 0;
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
+        if (const char *why = evaluator_pointers_error(evs[m])) return fail(GBL_ERR_ARG, why);
+        nets[m] = eval_net(evs[m]);
+        most = std::max(most, its[m]);
+    }
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    if (ply_dev) ply0 += *ply_dev;
+    const EvalNet net0 = nets[0], net1 = nets[1];
+    const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                         nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj};
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
+        std::vector<TreeNode> nodes((size_t)most + 1);
+        std::vector<uint8_t> pri(((size_t)most + 1) * kEvalOutputs);
+        selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
+                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t, uint32_t, SelfplaySearch &S) {
+                            if (pol[who] != GBL_POLICY_EVAL_TREE) return false;
+                            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, legal, (uint32_t)its[who],
+                                                             (uint32_t)explore, S.h);
+                            S.priors = pri.data();  // (the root's row; zeros where the root has no candidate)
+                            return true;
+                        });
     }, 1);
     return GBL_OK;
 }

@@ -2008,6 +2008,7 @@ __device__ __forceinline__ void tree_backup(TreeNode *nodes, uint32_t leaf, uint
 
 // ---- gbl_collect_search: whole games with the tree search on either side (contract: include/gobblet_hip.h) --
 constexpr int kPolicyTree = 4;                 // GBL_POLICY_TREE
+constexpr int kPolicyEvalTree = 5;             // GBL_POLICY_EVAL_TREE (gbl_collect_search_eval)
 constexpr int kHowSearch = 3, kHowSearchSampled = 4;  // GBL_HOW_SEARCH / GBL_HOW_SEARCH_SAMPLED (0 = GBL_HOW_RANDOM)
 constexpr int kZOpen = -128;                   // GBL_Z_OPEN
 constexpr uint32_t kStreamVisit = 4u;          // generator stream of the visit-proportional draw of a game's first plies
@@ -2253,6 +2254,40 @@ inline const char *tree_eval_budget_error(int iterations, int explore)
 inline const char *env_range_error(uint64_t env_base, int64_t n)  // (n >= 0)
 {
     return env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base ? "env_base + n must not exceed 2^42" : nullptr;
+}
+
+// what the two self-play entry points (gbl_collect_search, gbl_collect_search_eval) ask of the window: after the policies' own checks
+inline const char *selfplay_window_error(int sample_plies, bool has_turn, uint32_t ply0, uint32_t plies, uint64_t env_base, int64_t n)
+{
+    if (sample_plies < 0) return "sample_plies < 0";
+    if (sample_plies > 0 && !has_turn) return "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)";
+    if ((uint64_t)ply0 + plies > (1ull << 24)) return "ply0 + plies must not exceed 2^24 (the search's call index)";
+    return env_range_error(env_base, n);
+}
+
+inline const char *illegal_mode_error(int illegal_mode)
+{
+    return illegal_mode != 0 && illegal_mode != 1 ? "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE" : nullptr;
+}
+
+// gbl_collect_search_eval, everything that is looked at before a pointer is: the policies, the searching sides' evaluator and
+// budget (a RANDOM side's are not read), then the window.  (n >= 0)
+template <typename Ev>
+inline const char *collect_eval_error(int illegal_mode, int policy0, int policy1, const Ev *ev0, const Ev *ev1, int iterations0,
+                                      int iterations1, int explore, int sample_plies, bool has_turn, uint32_t ply0, uint32_t plies,
+                                      uint64_t env_base, int64_t n)
+{
+    if (const char *why = illegal_mode_error(illegal_mode)) return why;
+    if ((policy0 != 0 && policy0 != kPolicyEvalTree) || (policy1 != 0 && policy1 != kPolicyEvalTree))
+        return "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_EVAL_TREE";
+    const Ev *evs[2] = {ev0, ev1};
+    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != kPolicyEvalTree) continue;
+        if (const char *why = evaluator_error(evs[m])) return why;
+        if (const char *why = tree_eval_budget_error(its[m], explore)) return why;
+    }
+    return selfplay_window_error(sample_plies, has_turn, ply0, plies, env_base, n);
 }
 
 // The (ply, tile) cells of 64 boards of a trajectory must start 16-byte aligned and must not overlap.

@@ -1979,14 +1979,78 @@ __global__ __launch_bounds__(64) void k_evaluate(const int8_t *__restrict__ stat
     }
 }
 
-// gbl_tree_search_eval: k_tree's tree with a network leaf.  One wavefront per board (a grid-stride loop over boards), so the tree
-// needs no workgroup barrier: LDS traffic of one wavefront lands in order.  The tree is (iterations + 1) 16-byte nodes followed by
-// (iterations + 1) 56-byte prior rows in dynamic LDS; the root planes stay in registers.  An iteration:
+// The evaluator-guided search of one board, for k_tree_eval and k_collect_eval: every lane of the board's one wavefront calls it,
+// with the same root / mover / cand.  LDS traffic of one wavefront lands in order, so the tree needs no workgroup barrier, only
+// wave_lds_fence.  nodes: iterations + 1 nodes at least; pri: a 56-byte prior row per node.  On return the tree is written and
+// fenced, count is the nodes created (the root included), and the root's evaluation comes back: lane a's prior byte and q.  The
+// root is created before iteration 0; an iteration:
 //   select   k_tree's walk -- the child list of a node once, lane a keeps the child of action a -- plus one byte of the node's prior
 //            row per lane; every lane computes its action's key, a butterfly max picks, one move_planes per level replays the position;
 //   expand   the move and what it decided in every lane alike; lane 0 links the node;
 //   evaluate wave_evaluate on the new child's position, its prior row stored beside the node;
 //   back up  lane 0 walks to the root.
+__device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, uint8_t *const pri, uint32_t *const s_h, const EvalNet &net,
+                                                         const Planes &root, const int mover, const uint64_t cand, const uint32_t iterations,
+                                                         const uint32_t explore, const uint32_t lane, uint32_t &count)
+{
+    if (lane == 0) nodes[0] = TreeNode{};
+    const WaveEval at_root = wave_evaluate(net, root, mover, cand, s_h, lane);
+    if (lane < (uint32_t)kEvalOutputs) pri[lane] = (uint8_t)at_root.pi;
+    wave_lds_fence();  // (the root is written)
+    count = 1;
+    for (uint32_t i = 0; cand && i < iterations; ++i) {
+        // 1. select
+        uint32_t v = 0, term, a_new = 0;
+        Planes p = root;
+        int side = mover;
+        uint64_t cd = cand;
+        bool grow = false;
+        for (;;) {
+            const TreeNode nv = nodes[v];
+            term = tree_term(nv);
+            if (term) break;
+            uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
+            for (uint32_t c = nv.child; c;) {
+                const TreeNode k = nodes[c];
+                if (lane == tree_action(k)) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
+                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+            }
+            const uint32_t pi = lane < (uint32_t)kEvalOutputs ? pri[v * kEvalOutputs + lane] : 0u;
+            const uint32_t key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my_c != 0, my_w, my_l, my_n, nv.n, pi, explore), lane) : 0u);
+            a_new = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a_new);
+            if (!c) {
+                grow = true;
+                break;
+            }
+            move_planes(p, side, a_new);
+            side ^= 1;
+            v = c;
+            cd = legal54(p, side);
+        }
+        // 2. expand and evaluate
+        uint32_t leaf = v;
+        if (grow) {
+            term = tree_move_into(p, side, a_new);
+            leaf = count++;
+            if (lane == 0) tree_link(nodes, leaf, v, a_new, term);
+        }
+        uint32_t wl = tree_decided(term, kTreeEvalP);
+        if (grow && term == kTreeOpen) {
+            const WaveEval r = wave_evaluate(net, p, side, legal54(p, side), s_h, lane);
+            if (lane < (uint32_t)kEvalOutputs) pri[leaf * kEvalOutputs + lane] = (uint8_t)r.pi;
+            wl = tree_eval_outcome(r.q);
+        }
+        // 3. back up
+        if (lane == 0) tree_backup(nodes, leaf, wl & 0xFFFFu, wl >> 16);
+        wave_lds_fence();  // (the tree is written)
+    }
+    return at_root;
+}
+
+// gbl_tree_search_eval: k_tree's tree with a network leaf.  One wavefront per board (a grid-stride loop over boards).  The tree is
+// (iterations + 1) 16-byte nodes followed by (iterations + 1) 56-byte prior rows in dynamic LDS; the root planes stay in registers.
+// The search is tree_eval_iterations; the wavefront then writes the root's children out and decides.
 __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
                                                   const int8_t *__restrict__ mask, const EvalNet net, int32_t *__restrict__ visits_out,
                                                   int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
@@ -2003,58 +2067,8 @@ __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ sta
         const Planes root = board_planes(state, b, lane);
         const int mover = to_move[b] != 0;
         const uint64_t cand = board_candidates(root, mover, mask, b, lane);
-        if (lane == 0) nodes[0] = TreeNode{};
-        const WaveEval at_root = wave_evaluate(net, root, mover, cand, s_h, lane);
-        if (lane < (uint32_t)kEvalOutputs) pri[lane] = (uint8_t)at_root.pi;
-        wave_lds_fence();  // (the root is written)
-        uint32_t count = 1;
-        for (uint32_t i = 0; cand && i < iterations; ++i) {
-            // 1. select
-            uint32_t v = 0, term, a_new = 0;
-            Planes p = root;
-            int side = mover;
-            uint64_t cd = cand;
-            bool grow = false;
-            for (;;) {
-                const TreeNode nv = nodes[v];
-                term = tree_term(nv);
-                if (term) break;
-                uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
-                for (uint32_t c = nv.child; c;) {
-                    const TreeNode k = nodes[c];
-                    if (lane == tree_action(k)) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
-                    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
-                }
-                const uint32_t pi = lane < (uint32_t)kEvalOutputs ? pri[v * kEvalOutputs + lane] : 0u;
-                const uint32_t key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my_c != 0, my_w, my_l, my_n, nv.n, pi, explore), lane) : 0u);
-                a_new = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
-                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a_new);
-                if (!c) {
-                    grow = true;
-                    break;
-                }
-                move_planes(p, side, a_new);
-                side ^= 1;
-                v = c;
-                cd = legal54(p, side);
-            }
-            // 2. expand and evaluate
-            uint32_t leaf = v;
-            if (grow) {
-                term = tree_move_into(p, side, a_new);
-                leaf = count++;
-                if (lane == 0) tree_link(nodes, leaf, v, a_new, term);
-            }
-            uint32_t wl = tree_decided(term, kTreeEvalP);
-            if (grow && term == kTreeOpen) {
-                const WaveEval r = wave_evaluate(net, p, side, legal54(p, side), s_h, lane);
-                if (lane < (uint32_t)kEvalOutputs) pri[leaf * kEvalOutputs + lane] = (uint8_t)r.pi;
-                wl = tree_eval_outcome(r.q);
-            }
-            // 3. back up
-            if (lane == 0) tree_backup(nodes, leaf, wl & 0xFFFFu, wl >> 16);
-            wave_lds_fence();  // (the tree is written)
-        }
+        uint32_t count;
+        const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, net, root, mover, cand, iterations, explore, lane, count);
         const TreeRootChild c = tree_root_child(nodes, lane);
         if (lane < (uint32_t)kActions) {
             if (visits_out) visits_out[b * kActions + lane] = (int32_t)c.n;
@@ -2093,6 +2107,117 @@ struct SearchTraj {
     int8_t *how, *mover;
 };
 
+// What the two self-play kernels (k_collect_search, k_collect_eval) do between a search and the next one; wavefront 0's lanes call
+// search_decide and store_search_ply, every thread of the board's workgroup the other two.
+//
+// decide: lane a reads the root's child of action a; butterflies give the decision's key and the value sum; `sampled` (a game's
+// first plies): the visit-proportional draw on stream kStreamVisit, by a prefix sum of the visits over the lanes.
+struct SearchDecision {
+    int action, how, value;
+    uint32_t my_n;  // (the visits of this lane's action)
+};
+
+__device__ __forceinline__ SearchDecision search_decide(const TreeNode *nodes, uint32_t lane, bool sampled, uint64_t seed, uint64_t g, uint32_t q)
+{
+    const TreeRootChild c = tree_root_child(nodes, lane);
+    SearchDecision d{0, kHowSearch, (int)wave_sum(c.w - c.l), c.n};
+    d.action = tree_action_of(wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
+    if (sampled) {
+        uint32_t run = c.n;  // (the running sum of the visits through this lane's action)
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t below = (uint32_t)__shfl_up((int)run, o);
+            run += lane >= (uint32_t)o ? below : 0u;
+        }
+        const uint32_t S = (uint32_t)__builtin_amdgcn_readlane((int)run, 63);
+        const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), S);
+        const uint64_t over = (uint64_t)__ballot(run > k);
+        d.action = over ? (int)__builtin_ctzll(over) : -1;
+        d.how = kHowSearchSampled;
+    }
+    return d;
+}
+
+// step: play_ply / next_turn on the planes with auto-reset, everything left wave-uniform; the tallies of the board's games
+struct SearchBoard {
+    Planes p;
+    int mover, tabs, dn;
+    uint32_t games, w1, w2;
+};
+
+__device__ __forceinline__ Ply search_step(SearchBoard &B, uint64_t legal, int action, int illegal_mode, int &winner)
+{
+    const Ply y = play_ply(B.p, NoRow{}, B.mover, legal, action, illegal_mode);
+    B.dn = uniform(y.terminal ? 1 : 0);
+    if (B.dn) {  // raw_env.reset, gobblet.py:275-290
+        B.p = Planes{0u, 0u, 0u};
+        B.mover = 0;
+    }
+    B.p = Planes{(uint32_t)uniform((int)B.p.nz), (uint32_t)uniform((int)B.p.neg), (uint32_t)uniform((int)B.p.odd)};
+    B.mover = uniform(B.mover);
+    B.tabs = uniform(next_turn(B.tabs, y, 1));
+    winner = uniform(y.winner);
+    B.games += (uint32_t)B.dn;
+    B.w1 += winner == 1;
+    B.w2 += winner == -1;
+    return y;
+}
+
+// store: the scalars from lane 0, the visits row from lanes 0..53, and the mask and observation rows built in LDS by
+// mask_row_part<4> / obs_scatter_part<4> on lanes 0..3 and stored a byte per lane, all non-temporally.  B: the board AFTER the ply.
+__device__ __forceinline__ void store_search_ply(const SearchTraj &T, int64_t at, uint32_t lane, uint32_t *s_mask, uint32_t *s_obs,
+                                                 const SearchBoard &B, const Ply &y, int winner, int action, int value, uint32_t count,
+                                                 int how, int who, uint32_t my_n)
+{
+    if (lane == 0) {
+        if (T.actions) T.actions[at] = action;
+        if (T.winner) T.winner[at] = (int8_t)winner;
+        if (T.reward) reinterpret_cast<uint16_t *>(T.reward)[at] = (uint16_t)((y.r0 & 0xFF) | ((y.r1 & 0xFF) << 8));
+        if (T.done) T.done[at] = (int8_t)B.dn;
+        if (T.to_move) T.to_move[at] = (int8_t)B.mover;
+        if (T.value) T.value[at] = value;
+        if (T.nodes) T.nodes[at] = (int32_t)count;
+        if (T.how) T.how[at] = (int8_t)how;
+        if (T.mover) T.mover[at] = (int8_t)who;
+    }
+    if (T.visits && lane < (uint32_t)kActions) __builtin_nontemporal_store((int16_t)my_n, T.visits + at * kActions + lane);
+    if (T.mask) {
+        if (lane < 4u) mask_row_part<4>(reinterpret_cast<uint8_t *>(s_mask), next_mask(B.p, B.mover, B.dn, 1), (int)lane);
+        wave_lds_fence();
+        if (lane < (uint32_t)kActions)
+            __builtin_nontemporal_store(reinterpret_cast<const int8_t *>(s_mask)[lane], T.mask + at * kActions + lane);
+        wave_lds_fence();
+    }
+    if (T.obs) {
+        if (lane < 32u) s_obs[lane] = 0u;
+        wave_lds_fence();
+        if (lane < 4u) obs_scatter_part<4>(reinterpret_cast<uint8_t *>(s_obs), B.p, B.mover, (int)lane);
+        wave_lds_fence();
+        const int8_t *row = reinterpret_cast<const int8_t *>(s_obs);
+        __builtin_nontemporal_store(row[lane], T.obs + at * kObs + lane);
+        if (lane + 64u < (uint32_t)kObs) __builtin_nontemporal_store(row[lane + 64u], T.obs + at * kObs + lane + 64u);
+        wave_lds_fence();
+    }
+}
+
+// ... and after the last ply: the state row from the planes (planes_to_row, a cell per lane), the board's scalars and its tallies
+__device__ __forceinline__ void store_search_board(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int8_t *__restrict__ done,
+                                                   int32_t *__restrict__ turn, int64_t *__restrict__ counters, int64_t b, uint32_t tid,
+                                                   const SearchBoard &B, uint32_t plies)
+{
+    if (tid < (uint32_t)kCells) {
+        const uint32_t nz = (B.p.nz >> tid) & 1u, ng = (B.p.neg >> tid) & nz, od = (B.p.odd >> tid) & nz;
+        const uint32_t v = nz * (tid >= 18u ? 6u : (tid >= 9u ? 4u : 2u)) - od;
+        state[b * kCells + tid] = (int8_t)(ng ? 0u - v : v);
+    }
+    if (tid == 0) {
+        to_move[b] = (int8_t)B.mover;
+        done[b] = (int8_t)B.dn;
+        if (turn) turn[b] = B.tabs;
+        if (counters) tally_flush(counters, b, 1, plies, B.games, B.w1, B.w2);
+    }
+}
+
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                            uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
@@ -2109,106 +2234,98 @@ __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (ply_dev) ply0 += *ply_dev;
     for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
-        Planes p = board_planes(state, b, lane);
-        int mover = to_move[b] != 0, tabs = turn ? turn[b] : 0, dn = 0;
-        uint32_t games = 0, w1 = 0, w2 = 0;
+        SearchBoard B{board_planes(state, b, lane), to_move[b] != 0, turn ? turn[b] : 0, 0, 0u, 0u, 0u};
         const uint64_t g = env_base + (uint64_t)b;
         const int64_t cell0 = (b >> 6) * tile_stride + (b & 63);
         for (uint32_t t = 0; t < plies; ++t) {
             const uint32_t q = ply0 + t;
-            const int who = mover;
-            const uint64_t legal = legal54(p, who);
+            const int who = B.mover;
+            const uint64_t legal = legal54(B.p, who);
             const bool tree = (who ? policy1 : policy0) == kPolicyTree;
-            int action, how = 0, value = 0;
-            uint32_t my_n = 0, count = 0;
+            SearchDecision d{0, 0, 0, 0u};
+            uint32_t count = 0;
             if (tree) {
                 if (tid == 0) nodes[0] = TreeNode{};
                 if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
                 __syncthreads();  // (root and counters zeroed)
                 uint32_t plies_total = 0;
                 count = 1;
-                tree_iterations<W>(nodes, s_sum, p, who, legal, g, seed, q, who ? iterations1 : iterations0, who ? playouts1 : playouts0,
+                tree_iterations<W>(nodes, s_sum, B.p, who, legal, g, seed, q, who ? iterations1 : iterations0, who ? playouts1 : playouts0,
                                    max_plies, explore, tid, lane, count, plies_total);
-                const TreeRootChild c = tree_root_child(nodes, lane);
-                my_n = c.n;
-                value = (int)wave_sum(c.w - c.l);
-                action = tree_action_of(wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
-                how = kHowSearch;
-                if (tabs < sample_plies) {  // the first plies of a game: in proportion to the visits
-                    uint32_t run = my_n;    // (the running sum of the visits through this lane's action)
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const uint32_t below = (uint32_t)__shfl_up((int)run, o);
-                        run += lane >= (uint32_t)o ? below : 0u;
-                    }
-                    const uint32_t S = (uint32_t)__builtin_amdgcn_readlane((int)run, 63);
-                    const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), S);
-                    const uint64_t over = (uint64_t)__ballot(run > k);
-                    action = over ? (int)__builtin_ctzll(over) : -1;
-                    how = kHowSearchSampled;
-                }
+                d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
                 __syncthreads();  // (every wavefront has read the root's children before the next search rewrites the tree)
             } else {
-                action = pick54(legal, draw32(seed, g, q));
+                d.action = pick54(legal, draw32(seed, g, q));
             }
-            action = uniform(action);
-            const Ply y = play_ply(p, NoRow{}, mover, legal, action, illegal_mode);
-            dn = uniform(y.terminal ? 1 : 0);
-            if (dn) {  // raw_env.reset, gobblet.py:275-290
-                p = Planes{0u, 0u, 0u};
-                mover = 0;
+            const int action = uniform(d.action);
+            int winner;
+            const Ply y = search_step(B, legal, action, illegal_mode, winner);
+            if (tid < 64u)  // wavefront 0: the ply's outputs
+                store_search_ply(T, (int64_t)t * ply_stride + cell0, lane, s_mask, s_obs, B, y, winner, action, d.value, count, d.how, who, d.my_n);
+        }
+        store_search_board(state, to_move, done, turn, counters, b, tid, B, plies);
+    }
+}
+
+// gbl_collect_search_eval: k_collect_search with the evaluator-guided search: one wavefront per board (a grid-stride loop over
+// boards), the ply loop inside, the tree rebuilt from an empty root on every ply -- ply q's search IS gbl_tree_search_eval of the
+// position, because both kernels run tree_eval_iterations.  Dynamic LDS: (most + 1) nodes, then (most + 1) prior rows, most = the
+// larger budget of the sides that search; beside it s_h and the two row images.  One wavefront: no workgroup barrier anywhere.  The
+// mover picks its network and budget wave-uniformly (field by field: the two structs stay in SGPRs).  The decision, the step and
+// the stores are k_collect_search's; the root's q and its prior row -- a byte in every lane -- go out beside them.
+__device__ __forceinline__ EvalNet eval_net_pick(const EvalNet &a, const EvalNet &b, int second)
+{
+    return EvalNet{second ? b.w1 : a.w1, second ? b.b1 : a.b1, second ? b.w2 : a.w2, second ? b.b2 : a.b2, second ? b.hidden : a.hidden,
+                   second ? b.shift1 : a.shift1, second ? b.shift_p : a.shift_p, second ? b.shift_v : a.shift_v};
+}
+
+__global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                     uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
+                                                     int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
+                                                     int32_t *__restrict__ root_value_traj, uint8_t *__restrict__ priors_traj,
+                                                     const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
+                                                     uint32_t iterations1, uint32_t most, uint32_t explore, int sample_plies, int illegal_mode,
+                                                     int64_t *__restrict__ counters, int32_t *__restrict__ turn)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    const uint32_t lane = threadIdx.x;
+    if (ply_dev) ply0 += *ply_dev;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        SearchBoard B{board_planes(state, b, lane), to_move[b] != 0, turn ? turn[b] : 0, 0, 0u, 0u, 0u};
+        const uint64_t g = env_base + (uint64_t)b;
+        const int64_t cell0 = (b >> 6) * tile_stride + (b & 63);
+        for (uint32_t t = 0; t < plies; ++t) {
+            const uint32_t q = ply0 + t;
+            const int who = B.mover;
+            const uint64_t legal = legal54(B.p, who);
+            const bool search = (who ? policy1 : policy0) == kPolicyEvalTree;
+            SearchDecision d{0, 0, 0, 0u};
+            uint32_t count = 0, my_pi = 0;
+            int root_q = 0;
+            if (search) {
+                const EvalNet net = eval_net_pick(net0, net1, who);
+                const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, net, B.p, who, legal, who ? iterations1 : iterations0, explore,
+                                                              lane, count);
+                my_pi = at_root.pi;
+                root_q = at_root.q;
+                d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+                wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            } else {
+                d.action = pick54(legal, draw32(seed, g, q));
             }
-            p = Planes{(uint32_t)uniform((int)p.nz), (uint32_t)uniform((int)p.neg), (uint32_t)uniform((int)p.odd)};
-            mover = uniform(mover);
-            tabs = uniform(next_turn(tabs, y, 1));
-            const int winner = uniform(y.winner);
-            games += (uint32_t)dn;
-            w1 += winner == 1;
-            w2 += winner == -1;
-            if (tid < 64u) {  // wavefront 0: the ply's outputs
-                const int64_t at = (int64_t)t * ply_stride + cell0;
-                if (lane == 0) {
-                    if (T.actions) T.actions[at] = action;
-                    if (T.winner) T.winner[at] = (int8_t)winner;
-                    if (T.reward) reinterpret_cast<uint16_t *>(T.reward)[at] = (uint16_t)((y.r0 & 0xFF) | ((y.r1 & 0xFF) << 8));
-                    if (T.done) T.done[at] = (int8_t)dn;
-                    if (T.to_move) T.to_move[at] = (int8_t)mover;
-                    if (T.value) T.value[at] = value;
-                    if (T.nodes) T.nodes[at] = (int32_t)count;
-                    if (T.how) T.how[at] = (int8_t)how;
-                    if (T.mover) T.mover[at] = (int8_t)who;
-                }
-                if (T.visits && lane < (uint32_t)kActions) __builtin_nontemporal_store((int16_t)my_n, T.visits + at * kActions + lane);
-                if (T.mask) {
-                    if (lane < 4u) mask_row_part<4>(reinterpret_cast<uint8_t *>(s_mask), next_mask(p, mover, dn, 1), (int)lane);
-                    wave_lds_fence();
-                    if (lane < (uint32_t)kActions)
-                        __builtin_nontemporal_store(reinterpret_cast<const int8_t *>(s_mask)[lane], T.mask + at * kActions + lane);
-                    wave_lds_fence();
-                }
-                if (T.obs) {
-                    if (lane < 32u) s_obs[lane] = 0u;
-                    wave_lds_fence();
-                    if (lane < 4u) obs_scatter_part<4>(reinterpret_cast<uint8_t *>(s_obs), p, mover, (int)lane);
-                    wave_lds_fence();
-                    const int8_t *row = reinterpret_cast<const int8_t *>(s_obs);
-                    __builtin_nontemporal_store(row[lane], T.obs + at * kObs + lane);
-                    if (lane + 64u < (uint32_t)kObs) __builtin_nontemporal_store(row[lane + 64u], T.obs + at * kObs + lane + 64u);
-                    wave_lds_fence();
-                }
-            }
+            const int action = uniform(d.action);
+            int winner;
+            const Ply y = search_step(B, legal, action, illegal_mode, winner);
+            const int64_t at = (int64_t)t * ply_stride + cell0;
+            store_search_ply(T, at, lane, s_mask, s_obs, B, y, winner, action, d.value, count, d.how, who, d.my_n);
+            if (root_value_traj && lane == 0) root_value_traj[at] = root_q;
+            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)my_pi, priors_traj + at * kActions + lane);
         }
-        if (tid < (uint32_t)kCells) {  // the state row from the planes (planes_to_row, a cell per lane)
-            const uint32_t nz = (p.nz >> tid) & 1u, ng = (p.neg >> tid) & nz, od = (p.odd >> tid) & nz;
-            const uint32_t v = nz * (tid >= 18u ? 6u : (tid >= 9u ? 4u : 2u)) - od;
-            state[b * kCells + tid] = (int8_t)(ng ? 0u - v : v);
-        }
-        if (tid == 0) {
-            to_move[b] = (int8_t)mover;
-            done[b] = (int8_t)dn;
-            if (turn) turn[b] = tabs;
-            if (counters) tally_flush(counters, b, 1, plies, games, w1, w2);
-        }
+        store_search_board(state, to_move, done, turn, counters, b, lane, B, plies);
     }
 }
 
@@ -3694,8 +3811,7 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
                        int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
+    if (const char *why = illegal_mode_error(illegal_mode)) return fail(GBL_ERR_ARG, why);
     if ((policy0 != GBL_POLICY_RANDOM && policy0 != GBL_POLICY_TREE) || (policy1 != GBL_POLICY_RANDOM && policy1 != GBL_POLICY_TREE))
         return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE");
     const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
@@ -3707,10 +3823,7 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
         wide = std::max(wide, pls[m]);
     }
     if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
-    if (sample_plies < 0) return fail(GBL_ERR_ARG, "sample_plies < 0");
-    if (sample_plies > 0 && !turn) return fail(GBL_ERR_ARG, "sample_plies > 0 needs the per-board turn counter (turn must not be NULL)");
-    if ((uint64_t)ply0 + plies > (1ull << 24)) return fail(GBL_ERR_ARG, "ply0 + plies must not exceed 2^24 (the search's call index)");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = selfplay_window_error(sample_plies, turn != nullptr, ply0, plies, env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;
@@ -3736,6 +3849,47 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
     }
 #undef GBL_CS
     GBL_LAUNCHED("gbl_collect_search");
+}
+
+int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                            int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                            int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                            uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base,
+                            uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                            const gbl_evaluator *ev1, int iterations0, int iterations1, int explore, int sample_plies, int illegal_mode,
+                            int64_t *counters, int32_t *turn, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = collect_eval_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, explore, sample_plies,
+                                             turn != nullptr, ply0, plies, env_base, n))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (plies == 0) return GBL_OK;
+    const gbl_evaluator *evs[2] = {ev0, ev1};
+    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
+    EvalNet nets[2] = {};  // (a RANDOM side's stays empty: the kernel never reads it)
+    int most = 0;          // the larger tree of the sides that search
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
+        if (const int e = eval_net_of(evs[m], nets[m])) return e;
+        most = std::max(most, its[m]);
+    }
+    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
+                                 reinterpret_cast<uintptr_t>(actions_traj) | reinterpret_cast<uintptr_t>(value_traj) |
+                                     reinterpret_cast<uintptr_t>(nodes_traj) | reinterpret_cast<uintptr_t>(root_value_traj),
+                                 "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned", turn, counters))
+        return e;
+    if (reinterpret_cast<uintptr_t>(visits_traj) & 1u) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
+    const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                       nodes_traj, how_traj, mover_traj};
+    // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations, as gbl_tree_search_eval)
+    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)most + 1);
+    hipLaunchKernelGGL(k_collect_eval, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed,
+                       env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, T, root_value_traj, priors_traj, nets[0], nets[1], policy0,
+                       policy1, (uint32_t)iterations0, (uint32_t)iterations1, (uint32_t)most, (uint32_t)explore, sample_plies, illegal_mode,
+                       counters, turn);
+    GBL_LAUNCHED("gbl_collect_search_eval");
 }
 
 int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

@@ -17,6 +17,8 @@ Tensors (attributes, all on ``device``)
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _native as nat
@@ -253,12 +255,15 @@ class BatchedGobblet:
 
     # -- trajectory collection: T plies per launch, every ply materialised -------------------------------------
     POLICIES = {"random": nat.POLICY_RANDOM, "greedy1": nat.POLICY_GREEDY1, "greedy": nat.POLICY_GREEDY2,
-                "greedy2": nat.POLICY_GREEDY2, "greedy3": nat.POLICY_GREEDY3, "tree": nat.POLICY_TREE}
+                "greedy2": nat.POLICY_GREEDY2, "greedy3": nat.POLICY_GREEDY3, "tree": nat.POLICY_TREE, "evaluator": nat.POLICY_EVAL_TREE}
 
     def trajectory_buffers(self, plies: int, layout: str = "time", pad_boards: int | None = None,
                            placement: str = "auto", policy_outputs: bool = False, candidates: bool = False,
-                           far: bool | None = None, search_outputs: bool = False) -> dict:
+                           far: bool | None = None, search_outputs: bool = False, evaluator_outputs: bool = False) -> dict:
         """Device tensors for ``collect``.
+
+        evaluator_outputs (with ``search_outputs``): also "root_value" (int32: the root's q of every ply's evaluator-guided search,
+        in 1/128 of a win for the mover) and "priors" (uint8 (..., 54): the root's prior row) for ``collect`` with an evaluator side.
 
         search_outputs: also "visits" (int16 (..., 54)), "value" / "nodes" (int32), "how" and "mover" (int8) for
         ``collect(policies=(... "tree" ...), search=...)``: the root visit counts, value sum and node count of the search that
@@ -346,6 +351,10 @@ class BatchedGobblet:
                 ((("candidates", torch.int8, (nat.ACTIONS,)),) if candidates else ()) + \
                 ((("visits", torch.int16, (nat.ACTIONS,)), ("value", torch.int32, ()), ("nodes", torch.int32, ()),
                   ("mover", torch.int8, ())) + ((("how", torch.int8, ()),) if not policy_outputs else ()) if search_outputs else ())
+        if evaluator_outputs:
+            if not search_outputs:
+                raise ValueError("evaluator_outputs belongs to search_outputs=True")
+            extra += (("root_value", torch.int32, ()), ("priors", torch.uint8, (nat.ACTIONS,)))
         for key, dtype, tail in (("actions", torch.int32, ()), ("winner", torch.int8, ()), ("rewards", torch.int8, (2,)),
                                  ("done", torch.int8, ()), ("to_move", torch.int8, ())) + extra:
             full[key] = torch.zeros(lead + tail, dtype=dtype, device=dev)
@@ -406,24 +415,33 @@ class BatchedGobblet:
         proportion to the visits instead of taking the most visited action.  Ply t's search is exactly
         ``gbl_tree_search(call = ply index)`` of the position.  The buffers (``trajectory_buffers(search_outputs=True)``) also
         receive "visits" / "value" / "nodes" / "how" / "mover"; ``outcome_targets`` turns them into training targets.  The
-        greedy policies cannot be paired with "tree"."""
+        greedy policies cannot be paired with "tree".
+
+        A pair with "evaluator" (or an ``EvaluatorTreeSearchGobbletPolicy`` instance, which supplies its evaluator, iterations and
+        explore) against "evaluator" or "random" plays with the evaluator-guided search INSIDE the launch
+        (``gbl_collect_search_eval``): ``search=dict(evaluator=, iterations=, explore=, sample_plies=)`` -- ``evaluator`` and
+        ``iterations`` may each be a pair, one per side (two different networks: an arena); ``explore`` is one value.  Ply t's search
+        is exactly ``gbl_tree_search_eval`` of the position.  The buffers (``trajectory_buffers(search_outputs=True,
+        evaluator_outputs=True)``) receive the search entries and "root_value" / "priors".  An evaluator side cannot be paired with
+        "tree" or a greedy policy inside one launch: compose ``compute_actions_from_state`` + ``step_into`` per ply for that."""
         if not self.auto_reset:
             raise ValueError("collect() plays with auto-reset; this environment was created with auto_reset=False")
         T = int(plies)
-        sp = self._search_params(policies, search)  # None unless a side plays the tree search
+        ep = self._evaluator_params(policies, search)  # None unless a side plays the evaluator-guided search
+        sp = ep if ep is not None else self._search_params(policies, search)  # None unless a side plays a tree search
         if isinstance(out, str):
             if out != "fresh":
                 raise ValueError("out: a dict from trajectory_buffers(), None (the environment's staging buffers) or 'fresh'")
             # buffers of the caller's own: made (and placed) now, not kept by the environment, never overwritten by a later call
             out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                          search_outputs=sp is not None, far=False)
+                                          search_outputs=sp is not None, evaluator_outputs=ep is not None, far=False)
         if out is None:
-            key = (T, layout, policies is not None) + (("search",) if sp is not None else ())
+            key = (T, layout, policies is not None) + (("search",) if sp is not None else ()) + (("evaluator",) if ep is not None else ())
             out = self._staging.pop(key, None)
             made = out is None
             if made:
                 out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                              search_outputs=sp is not None, far=False)
+                                              search_outputs=sp is not None, evaluator_outputs=ep is not None, far=False)
             # (buffers made inside a graph capture belong to the graph's private pool: not kept beyond it)
             capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
             if not (made and capturing):
@@ -446,11 +464,24 @@ class BatchedGobblet:
         first_status = self._i8_out(first_status, "first_status")
         if first_status is not None and fa is None:
             raise ValueError("first_status needs first_actions")
-        if sp is not None:
+        if sp is not None:  # (either search)
             if sp["sample_plies"] and self.turn is None:
                 raise ValueError("sample_plies needs the per-board turn counter: create the environment with track_turn=True")
             if opening_plies:
                 raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
+        if ep is not None:
+            structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
+            nat.check(self._lib.gbl_collect_search_eval(
+                self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
+                f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
+                f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
+                nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")),
+                nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), n, out["_ply_stride"], out["_tile_stride"], self.seed,
+                self.env_base, self._ply, nat.ptr(self._ply_dev), T, *ep["policies"],
+                *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"], ep["explore"], ep["sample_plies"],
+                self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream()),
+                "gbl_collect_search_eval")
+        elif sp is not None:
             nat.check(self._lib.gbl_collect_search(
                 self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
                 f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
@@ -541,6 +572,69 @@ class BatchedGobblet:
             raise ValueError("search: max_plies must be in [0, 255], explore in [0, 1024], sample_plies >= 0")
         return dict(policies=codes, iterations=its, playouts=pls, max_plies=int(kw["max_plies"]), explore=int(kw["explore"]),
                     sample_plies=int(kw["sample_plies"]))
+
+    def _evaluator_params(self, policies, search):
+        """The arguments of ``gbl_collect_search_eval`` when a side of ``policies`` plays the evaluator-guided search, else None."""
+        from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator
+        from .tree_policy import TreeSearchGobbletPolicy
+        if policies is None or isinstance(policies, str):
+            return None
+        sides = list(policies)
+
+        def is_eval(x):
+            return isinstance(x, EvaluatorTreeSearchGobbletPolicy) or x == "evaluator" or \
+                (not isinstance(x, (str, TreeSearchGobbletPolicy)) and x == nat.POLICY_EVAL_TREE)
+        evs = [is_eval(x) for x in sides]
+        if len(sides) != 2 or not any(evs):
+            return None
+        kw = dict(evaluator=None, iterations=256, explore=None, sample_plies=0)  # EvaluatorTreeSearchGobbletPolicy's defaults
+        unknown = set(search or ()) - set(kw)
+        if unknown:
+            raise ValueError("search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies)" % sorted(unknown))
+        kw.update(search or {})
+        pair = lambda v: list(v) if isinstance(v, (tuple, list)) else [v, v]  # noqa: E731
+        its, nets = pair(kw["iterations"]), pair(kw["evaluator"])
+        if len(its) != 2 or len(nets) != 2:
+            raise ValueError("search: iterations / evaluator are a value or a pair, one per side")
+        codes, explores = [], []
+        for m, x in enumerate(sides):
+            if isinstance(x, EvaluatorTreeSearchGobbletPolicy):
+                its[m], nets[m] = x.iterations, x.evaluator
+                explores.append(x.explore)
+                codes.append(nat.POLICY_EVAL_TREE)
+            elif evs[m]:
+                codes.append(nat.POLICY_EVAL_TREE)
+            elif x == "random" or (not isinstance(x, (str, TreeSearchGobbletPolicy)) and x == nat.POLICY_RANDOM):
+                codes.append(nat.POLICY_RANDOM)
+                nets[m] = None
+            else:
+                raise ValueError("policies: the evaluator-guided search plays against 'evaluator' or 'random' inside one launch (not %r); "
+                                 "against the tree search or a greedy policy, compose the loop: the policy's "
+                                 "compute_actions_from_state + step_into per ply" % (x,))
+        if kw["explore"] is not None:
+            explore = int(kw["explore"])
+        elif explores:
+            if len(set(explores)) > 1:
+                raise ValueError("the two policy instances disagree on explore (%d, %d): one launch has one value; pass "
+                                 "search=dict(explore=...)" % tuple(explores))
+            explore = explores[0]
+        else:
+            explore = 16
+        for m in range(2):
+            if codes[m] != nat.POLICY_EVAL_TREE:
+                its[m] = 0
+                continue
+            if not isinstance(nets[m], GobbletEvaluator):
+                raise ValueError("search: an 'evaluator' side needs search=dict(evaluator=GobbletEvaluator ...)")
+            if nets[m].device != self.device:
+                raise ValueError("the evaluator lives on %s and the environment on %s: move it with evaluator.to(...)"
+                                 % (nets[m].device, self.device))
+            its[m] = int(its[m])
+            if not 1 <= its[m] <= 512:
+                raise ValueError("search: iterations must be in [1, 512]")
+        if not (0 <= explore <= 1024 and int(kw["sample_plies"]) >= 0):
+            raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
+        return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]))
 
     def outcome_targets(self, traj: dict) -> dict:
         """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128

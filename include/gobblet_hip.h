@@ -499,6 +499,46 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
                        int playouts0, int playouts1, int max_plies, int explore, int sample_plies, int illegal_mode,
                        int64_t *counters, int32_t *turn, void *stream);
 
+/* Evaluator-guided self-play collection (no counterpart in the reference): gbl_collect_search with gbl_tree_search_eval in place of
+ * the playout search -- the step an AlphaZero-style loop repeats, and, with two different networks, the arena that gates a new one.
+ *   policy0 / policy1  how player_1 / player_2 decide: GBL_POLICY_RANDOM or GBL_POLICY_EVAL_TREE.  GBL_POLICY_TREE and the greedy
+ *                      policies are out of scope here (GBL_ERR_ARG); gbl_collect_policy and gbl_collect_search in turn reject
+ *                      GBL_POLICY_EVAL_TREE.
+ *   ev0 / ev1          the networks of player_1 / player_2 (gbl_evaluator, above).  They may be the same struct and may have different
+ *                      `hidden`; NULL is allowed only for a RANDOM side.
+ * Per board g = env_base + b, for t = 0 .. plies-1, ply index q = ply0 + t (+ *ply_dev), mover m:
+ *   RANDOM     the gbl_sample rule on generator stream 0 with ply index q, exactly as gbl_collect_search.
+ *   EVAL_TREE  the search is exactly gbl_tree_search_eval(state, to_move, mask = NULL, ev_m, iterations_m, explore) of the board's
+ *              current position, and the action is that search's action_out -- except while turn[b] < sample_plies, where the action
+ *              is drawn in proportion to the visits by gbl_collect_search's rule: S = the sum of visits_out, r = the generator word of
+ *              (seed, g, q, stream 4), k = (r * S) >> 32, and the lowest action whose running sum of visits exceeds k.  The search
+ *              itself still draws nothing: seed, env_base and q matter only for RANDOM sides and that draw.  A root without a
+ *              candidate gives action -1, which is stepped as gbl_step steps an illegal action (per illegal_mode).
+ *   then       gbl_step with auto-reset and illegal_mode, as in gbl_collect.
+ * Ply t of board b leaves in cell(t, b) (see gbl_collect; both layouts) the seven arrays of gbl_collect, and (every pointer may be NULL)
+ *   visits_traj     int16[cells][54]  visits_out of the search that chose the action of ply t; zeros where RANDOM moved
+ *   value_traj      int32[cells]      the sum over the actions of wins_out - losses_out of that search, in 1/128 of a game, from the
+ *                                     mover's side; 0 where RANDOM moved
+ *   nodes_traj      int32[cells]      that search's nodes_out; 0 where RANDOM moved
+ *   how_traj        int8 [cells]      GBL_HOW_RANDOM, GBL_HOW_SEARCH or GBL_HOW_SEARCH_SAMPLED
+ *   mover_traj      int8 [cells]      the agent who played ply t
+ *   root_value_traj int32[cells]      that search's root_value_out (written also for a root without a candidate); 0 where RANDOM moved
+ *   priors_traj     uint8[cells][54]  that search's root_priors_out; zeros where RANDOM moved
+ * 1 <= iterations <= 512, 0 <= explore <= 1024 and the evaluator's rules are those of gbl_tree_search_eval (a RANDOM side's evaluator
+ * and iterations are ignored), sample_plies >= 0 (> 0 needs `turn`), ply0 + plies <= 2^24 and env_base + n <= 2^42 as
+ * gbl_collect_search.  state / to_move / done / turn / counters / ply_dev, the strides and the alignment rules as gbl_collect_search
+ * (root_value_traj 4-byte aligned; priors_traj needs none); the state rows are rebuilt from bit planes on return.  gbl_outcome_targets
+ * works on these trajectories unchanged.  Allocates nothing; the tree lives in 72 (max(iterations of the searching sides) + 1) bytes of
+ * LDS per workgroup and is rebuilt from an empty root on every ply: nothing persists from one ply's search to the next. */
+#define GBL_POLICY_EVAL_TREE 5
+int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                            int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                            int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                            int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
+                            uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
+                            int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                            int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
+
 /* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
  * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:
  *   z_traj          int8 [cells]  reward_traj[cell(e, b)][mover_traj[cell(t, b)]] -- the reward, not the winner, so that
