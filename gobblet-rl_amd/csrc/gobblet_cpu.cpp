@@ -626,6 +626,24 @@ int gbl_cpu_greedy_act(const int8_t *state, const int8_t *to_move, const int8_t 
                                  fallback_out, n, stream);
 }
 
+// Board b as the search entry points (gbl_cpu_playout_values, _tree_search, _evaluate, _tree_search_eval) take it: its planes, the
+// mover and the candidates -- the mover's legal actions, less those whose byte of the board's `mask` row (optional) is zero
+struct HostRoot {
+    Planes p;
+    int mover;
+    uint64_t cand;
+};
+
+static HostRoot host_root(const int8_t *state, const int8_t *to_move, const int8_t *mask, int64_t b)
+{
+    uint32_t r[7];
+    load_row(state, b, r);
+    HostRoot R{make_planes(r), to_move[b] != 0, 0};
+    R.cand = legal54(R.p, R.mover);
+    if (mask) R.cand &= read_mask(mask + b * kActions);
+    return R;
+}
+
 int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
                            uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
                            int32_t *action_out, int32_t *plies_out, int64_t n, void *)
@@ -639,18 +657,13 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is playouts x ~30 whole games: every board is worth a thread)
         for (int64_t b = b0; b < b1; ++b) {
-            uint32_t r[7];
-            load_row(state, b, r);
-            const Planes root = make_planes(r);
-            const int mover = to_move[b] != 0;
-            uint64_t cand = legal54(root, mover);
-            if (mask) cand &= read_mask(mask + b * kActions);
+            const HostRoot R = host_root(state, to_move, mask, b);
             int32_t wins[kActions] = {}, losses[kActions] = {};
             uint32_t plies = 0, best = 0;
             for (int a = 0; a < kActions; ++a) {
-                if (!((cand >> a) & 1ull)) continue;
+                if (!((R.cand >> a) & 1ull)) continue;
                 for (int k = 0; k < playouts; ++k) {
-                    const PlayoutEnd e = playout(root, mover, a, seed, playout_id(env_base + (uint64_t)b, (uint32_t)a, (uint32_t)k), call,
+                    const PlayoutEnd e = playout(R.p, R.mover, a, seed, playout_id(env_base + (uint64_t)b, (uint32_t)a, (uint32_t)k), call,
                                                  (uint32_t)max_plies);
                     wins[a] += e.outcome > 0;
                     losses[a] += e.outcome < 0;
@@ -675,6 +688,20 @@ struct HostSearch {
     uint32_t count, plies;
 };
 
+// The read-out of a finished search, for both host searches: the root's children into the three rows and the decision's key
+static void host_root_out(const std::vector<TreeNode> &nodes, uint32_t count, HostSearch &out)
+{
+    memset(out.visits, 0, sizeof out.visits); memset(out.wins, 0, sizeof out.wins); memset(out.losses, 0, sizeof out.losses);
+    out.best = 0;
+    for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
+        const TreeNode &k = nodes[c];
+        const uint32_t a = tree_action(k);
+        out.visits[a] = k.n; out.wins[a] = (int32_t)tree_wins(k); out.losses[a] = (int32_t)tree_losses(k);
+        out.best = std::max(out.best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
+    }
+    out.count = count;
+}
+
 static void host_tree_search(std::vector<TreeNode> &nodes, const Planes &root, int mover, uint64_t cand, uint64_t g, uint32_t iterations,
                              uint32_t P, uint32_t max_plies, uint32_t explore, uint64_t seed, uint32_t call, HostSearch &out)
 {
@@ -695,15 +722,7 @@ static void host_tree_search(std::vector<TreeNode> &nodes, const Planes &root, i
         if (grow) tree_link(nodes.data(), s.node = count++, parent, a, term);
         tree_backup(nodes.data(), s.node, wl & 0xFFFFu, wl >> 16);
     }
-    memset(out.visits, 0, sizeof out.visits); memset(out.wins, 0, sizeof out.wins); memset(out.losses, 0, sizeof out.losses);
-    out.best = 0;
-    for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
-        const TreeNode &k = nodes[c];
-        const uint32_t a = tree_action(k);
-        out.visits[a] = k.n; out.wins[a] = (int32_t)tree_wins(k); out.losses[a] = (int32_t)tree_losses(k);
-        out.best = std::max(out.best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
-    }
-    out.count = count;
+    host_root_out(nodes, count, out);
     out.plies = plies;
 }
 
@@ -722,13 +741,8 @@ int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t
         std::vector<TreeNode> nodes((size_t)iterations + 1);
         HostSearch h;
         for (int64_t b = b0; b < b1; ++b) {
-            uint32_t r[7];
-            load_row(state, b, r);
-            const Planes root = make_planes(r);
-            const int mover = to_move[b] != 0;
-            uint64_t cand = legal54(root, mover);
-            if (mask) cand &= read_mask(mask + b * kActions);
-            host_tree_search(nodes, root, mover, cand, env_base + (uint64_t)b, (uint32_t)iterations, (uint32_t)playouts, (uint32_t)max_plies,
+            const HostRoot R = host_root(state, to_move, mask, b);
+            host_tree_search(nodes, R.p, R.mover, R.cand, env_base + (uint64_t)b, (uint32_t)iterations, (uint32_t)playouts, (uint32_t)max_plies,
                              (uint32_t)explore, seed, call, h);
             if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
             if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
@@ -771,14 +785,9 @@ int gbl_cpu_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *m
     const EvalNet net = eval_net(ev);
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) {
-            uint32_t r[7];
-            load_row(state, b, r);
-            const Planes p = make_planes(r);
-            const int mover = to_move[b] != 0;
-            uint64_t cand = legal54(p, mover);
-            if (mask) cand &= read_mask(mask + b * kActions);
+            const HostRoot R = host_root(state, to_move, mask, b);
             int32_t o[kEvalOutputs];
-            value_out[b] = host_evaluate(net, p, mover, cand, priors_out + b * kActions, o);
+            value_out[b] = host_evaluate(net, R.p, R.mover, R.cand, priors_out + b * kActions, o);
             if (logits_out) memcpy(logits_out + b * kEvalOutputs, o, sizeof o);
         }
     }, 256);
@@ -807,15 +816,7 @@ static int32_t host_tree_search_eval(std::vector<TreeNode> &nodes, std::vector<u
             wl = tree_eval_outcome(host_evaluate(net, s.p, s.side, legal54(s.p, s.side), pri.data() + (size_t)s.node * kEvalOutputs, o));
         tree_backup(nodes.data(), s.node, wl & 0xFFFFu, wl >> 16);
     }
-    memset(out.visits, 0, sizeof out.visits); memset(out.wins, 0, sizeof out.wins); memset(out.losses, 0, sizeof out.losses);
-    out.best = 0;
-    for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
-        const TreeNode &k = nodes[c];
-        const uint32_t a = tree_action(k);
-        out.visits[a] = k.n; out.wins[a] = (int32_t)tree_wins(k); out.losses[a] = (int32_t)tree_losses(k);
-        out.best = std::max(out.best, tree_final_key(k.n, tree_wins(k), tree_losses(k), a));
-    }
-    out.count = count;
+    host_root_out(nodes, count, out);
     out.plies = 0;
     return root_q;
 }
@@ -836,13 +837,8 @@ int gbl_cpu_tree_search_eval(const int8_t *state, const int8_t *to_move, const i
         std::vector<uint8_t> pri(((size_t)iterations + 1) * kEvalOutputs);
         HostSearch h;
         for (int64_t b = b0; b < b1; ++b) {
-            uint32_t r[7];
-            load_row(state, b, r);
-            const Planes root = make_planes(r);
-            const int mover = to_move[b] != 0;
-            uint64_t cand = legal54(root, mover);
-            if (mask) cand &= read_mask(mask + b * kActions);
-            const int32_t q = host_tree_search_eval(nodes, pri, net, root, mover, cand, (uint32_t)iterations, (uint32_t)explore, h);
+            const HostRoot R = host_root(state, to_move, mask, b);
+            const int32_t q = host_tree_search_eval(nodes, pri, net, R.p, R.mover, R.cand, (uint32_t)iterations, (uint32_t)explore, h);
             if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
             if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
             if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
@@ -1031,16 +1027,10 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
                            int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = illegal_mode_error(illegal_mode)) return fail(GBL_ERR_ARG, why);
-    if ((policy0 != GBL_POLICY_RANDOM && policy0 != GBL_POLICY_TREE) || (policy1 != GBL_POLICY_RANDOM && policy1 != GBL_POLICY_TREE))
-        return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE");
+    if (const char *why = collect_search_error(illegal_mode, policy0, policy1, iterations0, iterations1, playouts0, playouts1, max_plies,
+                                               explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
+        return fail(GBL_ERR_ARG, why);
     const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
-    for (int m = 0; m < 2; ++m) {
-        if (pol[m] != GBL_POLICY_TREE) continue;
-        if (const char *why = tree_budget_error(its[m], pls[m])) return fail(GBL_ERR_ARG, why);
-    }
-    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
-    if (const char *why = selfplay_window_error(sample_plies, turn != nullptr, ply0, plies, env_base, n)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;

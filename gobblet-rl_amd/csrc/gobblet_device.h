@@ -2270,8 +2270,25 @@ inline const char *illegal_mode_error(int illegal_mode)
     return illegal_mode != 0 && illegal_mode != 1 ? "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE" : nullptr;
 }
 
-// gbl_collect_search_eval, everything that is looked at before a pointer is: the policies, the searching sides' evaluator and
-// budget (a RANDOM side's are not read), then the window.  (n >= 0)
+// gbl_collect_search, everything that is looked at before a pointer is: the policies, the searching sides' budgets (a RANDOM side's
+// are not read), the playout limits, then the window.  (n >= 0)
+inline const char *collect_search_error(int illegal_mode, int policy0, int policy1, int iterations0, int iterations1, int playouts0,
+                                        int playouts1, int max_plies, int explore, int sample_plies, bool has_turn, uint32_t ply0,
+                                        uint32_t plies, uint64_t env_base, int64_t n)
+{
+    if (const char *why = illegal_mode_error(illegal_mode)) return why;
+    if ((policy0 != 0 && policy0 != kPolicyTree) || (policy1 != 0 && policy1 != kPolicyTree))
+        return "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE";
+    if (policy0 == kPolicyTree)
+        if (const char *why = tree_budget_error(iterations0, playouts0)) return why;
+    if (policy1 == kPolicyTree)
+        if (const char *why = tree_budget_error(iterations1, playouts1)) return why;
+    if (const char *why = playout_limits_error(max_plies, explore)) return why;
+    return selfplay_window_error(sample_plies, has_turn, ply0, plies, env_base, n);
+}
+
+// gbl_collect_search_eval, the same: the policies, the searching sides' evaluator and budget (a RANDOM side's are not read), then the
+// window.  (n >= 0)
 template <typename Ev>
 inline const char *collect_eval_error(int illegal_mode, int policy0, int policy1, const Ev *ev0, const Ev *ev1, int iterations0,
                                       int iterations1, int explore, int sample_plies, bool has_turn, uint32_t ply0, uint32_t plies,

@@ -1635,7 +1635,7 @@ __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirs
 
 // Butterfly reductions over the wavefront: every lane returns with the full result.
 template <typename T>
-__device__ __forceinline__ T wave_max(T x)  // (T: uint32_t or uint64_t)
+__device__ __forceinline__ T wave_max(T x)  // (T: uint32_t, uint64_t or int32_t)
 {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -1750,12 +1750,34 @@ int playout_waves(int64_t n, int playouts)
     return w;
 }
 
+// The child list that starts at node `first` (0: empty), walked once by a whole wavefront; the tree is only read.  Lane a keeps the
+// child of action a: its index c (0: this lane's action has no child; the root is node 0 and nobody's child), its visits and its wins
+// / losses.  A lane without a child holds n = 1, w = l = 0: the selection keys divide by n in every lane before the lanes without a
+// child are dropped, so n is never 0; visits() is the count to report.  `first` is wave-uniform and the sibling index goes through
+// readfirstlane, so the loop is scalar and the reads broadcast.
+struct TreeChild {
+    uint32_t c, n, w, l;
+    __device__ __forceinline__ bool mine() const { return c != 0u; }
+    __device__ __forceinline__ uint32_t visits() const { return c ? n : 0u; }
+};
+
+__device__ __forceinline__ TreeChild tree_lane_child(const TreeNode *nodes, uint32_t first, uint32_t lane)
+{
+    TreeChild r{0u, 1u, 0u, 0u};
+    for (uint32_t c = first; c;) {
+        const TreeNode k = nodes[c];
+        if (lane == tree_action(k)) r = TreeChild{c, k.n, tree_wins(k), tree_losses(k)};
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+    }
+    return r;
+}
+
 // The iterations of one board's search, for k_tree and k_collect_search: every thread of the board's W wavefronts calls it.  On entry
 // the root node and the sums are zeroed and a barrier has passed; on return the tree is written and a barrier has passed.  count
 // (1 on entry) and plies_total (0) count the nodes created and the masked-random plies played.  An iteration:
-//   select   every wavefront walks the same path (the tree is only read): the child list of a node once, with broadcast LDS reads
-//            -- lane a keeps the statistics of the child of action a -- then all lanes compute their key and a butterfly max picks
-//            the child; one move_planes per level replays the position;
+//   select   every wavefront walks the same path (the tree is only read): the child list of a node once (tree_lane_child), a ballot
+//            of the lanes with a child says what is untried, then all lanes compute their key and a butterfly max picks the child;
+//            one move_planes per level replays the position;
 //   expand   the draw, the move and what it decided, in every lane alike (the node itself is written later, by thread 0);
 //   evaluate the P playouts of the leaf dealt to the 64 W lanes, in k_playout's four-ply quanta on one Philox block; wins | losses
 //            << 16 and the plies are summed over the wavefront by butterflies and, for W > 1, over the workgroup in LDS counters
@@ -1778,20 +1800,12 @@ __device__ __forceinline__ void tree_iterations(TreeNode *const nodes, uint32_t 
             const TreeNode nv = nodes[v];
             term = tree_term(nv);
             if (term) break;
-            uint64_t have = 0;
-            uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
-            for (uint32_t c = nv.child; c;) {
-                const TreeNode k = nodes[c];
-                const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)tree_action(k));
-                have |= 1ull << a;
-                if (lane == a) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
-                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
-            }
-            untried = cd & ~have;
+            const TreeChild my = tree_lane_child(nodes, nv.child, lane);
+            untried = cd & ~(uint64_t)__ballot(my.mine());
             if (untried) break;
-            const uint32_t key = wave_max(my_c ? tree_order_key(tree_key(my_w, my_l, my_n, P, nv.n, explore), lane) : 0u);
+            const uint32_t key = wave_max(my.mine() ? tree_order_key(tree_key(my.w, my.l, my.n, P, nv.n, explore), lane) : 0u);
             const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
-            v = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a);
+            v = (uint32_t)__builtin_amdgcn_readlane((int)my.c, (int)a);
             move_planes(p, side, a);
             side ^= 1;
             cd = legal54(p, side);
@@ -1857,26 +1871,23 @@ __device__ __forceinline__ void tree_iterations(TreeNode *const nodes, uint32_t 
     }
 }
 
-// The root's child of action `lane` (every lane of a wavefront calls it; the tree is only read)
-struct TreeRootChild {
-    uint32_t n, w, l;
-    bool mine;
-};
-
-__device__ __forceinline__ TreeRootChild tree_root_child(const TreeNode *nodes, uint32_t lane)
+// The read-out of a finished search, for k_tree and k_tree_eval (every lane of one wavefront calls it): board b's visits / wins /
+// losses rows (each optional) from lanes 0..53, zeros where the root has no child; returns the decision's key in every lane.
+__device__ __forceinline__ uint64_t tree_root_out(const TreeNode *nodes, uint32_t lane, int64_t b, int32_t *__restrict__ visits_out,
+                                                  int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out)
 {
-    TreeRootChild r{0u, 0u, 0u, false};
-    for (uint32_t c = nodes[0].child; c;) {
-        const TreeNode k = nodes[c];
-        if (lane == tree_action(k)) r.mine = true, r.n = k.n, r.w = tree_wins(k), r.l = tree_losses(k);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
+    const TreeChild c = tree_lane_child(nodes, nodes[0].child, lane);
+    if (lane < (uint32_t)kActions) {
+        if (visits_out) visits_out[b * kActions + lane] = (int32_t)c.visits();
+        if (wins_out) wins_out[b * kActions + lane] = (int32_t)c.w;
+        if (losses_out) losses_out[b * kActions + lane] = (int32_t)c.l;
     }
-    return r;
+    return wave_max(c.mine() ? tree_final_key(c.n, c.w, c.l, lane) : 0ull);
 }
 
 // gbl_tree_search: leaf-parallel UCT.  One workgroup of W wavefronts per board (a grid-stride loop over boards); the tree is an
 // array of 16-byte nodes in dynamic LDS, 16 (iterations + 1) bytes, and the root planes stay in registers as in k_playout.  The
-// search is tree_iterations; wavefront 0 then writes the root's children out and decides.
+// search is tree_iterations; wavefront 0 then writes the root's children out and decides (tree_root_out).
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_tree(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
                                                  const int8_t *__restrict__ mask, int32_t *__restrict__ visits_out,
@@ -1900,13 +1911,7 @@ __global__ __launch_bounds__(64 * W) void k_tree(const int8_t *__restrict__ stat
         tree_iterations<W>(nodes, s_sum, root, mover, cand, env_base + (uint64_t)b, seed, call, iterations, P, max_plies, explore, tid, lane,
                            count, plies_total);
         if (tid < 64u) {  // wavefront 0: the root's children out, and the decision
-            const TreeRootChild c = tree_root_child(nodes, lane);
-            if (lane < (uint32_t)kActions) {
-                if (visits_out) visits_out[b * kActions + lane] = (int32_t)c.n;
-                if (wins_out) wins_out[b * kActions + lane] = (int32_t)c.w;
-                if (losses_out) losses_out[b * kActions + lane] = (int32_t)c.l;
-            }
-            const uint64_t key = wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull);
+            const uint64_t key = tree_root_out(nodes, lane, b, visits_out, wins_out, losses_out);
             if (lane == 0) {
                 if (action_out) action_out[b] = tree_action_of(key);
                 if (nodes_out) nodes_out[b] = (int32_t)count;
@@ -1927,16 +1932,6 @@ int tree_waves(int64_t n, int playouts)
 }
 
 // ---- the integer network (k_evaluate) and the search it guides (k_tree_eval): contract in include/gobblet_hip.h ---------------------
-__device__ __forceinline__ int32_t wave_max_signed(int32_t x)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int32_t other = __shfl_xor(x, o);
-        x = other > x ? other : x;
-    }
-    return x;
-}
-
 // One evaluation by a whole wavefront; every lane holds the same p / side / cand.
 //   layer 1   lane i < H / 4 owns hidden units 4 i .. 4 i + 3: a set observation byte is one coalesced dword per lane of its w1 row
 //             (the set bytes come straight from the planes: no observation row is built); the clamped bytes go to s_h, H bytes;
@@ -1956,7 +1951,7 @@ __device__ __forceinline__ WaveEval wave_evaluate(const EvalNet &net, const Plan
     wave_lds_fence();  // (h is read before the next evaluation overwrites it)
     const bool in = (cand >> lane) & 1ull;
     const int32_t l = o >> net.shift_p;
-    const int32_t lmax = wave_max_signed(in ? l : INT32_MIN);
+    const int32_t lmax = wave_max<int32_t>(in ? l : INT32_MIN);
     const uint32_t e = in ? eval_exp2(lmax, l) : 0u;
     const uint32_t sum = wave_sum(e);
     return WaveEval{in ? eval_prior(e, sum) : 0u, o, eval_value(net, __builtin_amdgcn_readlane(o, kEvalValue))};
@@ -1984,7 +1979,7 @@ __global__ __launch_bounds__(64) void k_evaluate(const int8_t *__restrict__ stat
 // wave_lds_fence.  nodes: iterations + 1 nodes at least; pri: a 56-byte prior row per node.  On return the tree is written and
 // fenced, count is the nodes created (the root included), and the root's evaluation comes back: lane a's prior byte and q.  The
 // root is created before iteration 0; an iteration:
-//   select   k_tree's walk -- the child list of a node once, lane a keeps the child of action a -- plus one byte of the node's prior
+//   select   k_tree's walk -- the child list of a node once, tree_lane_child -- plus one byte of the node's prior
 //            row per lane; every lane computes its action's key, a butterfly max picks, one move_planes per level replays the position;
 //   expand   the move and what it decided in every lane alike; lane 0 links the node;
 //   evaluate wave_evaluate on the new child's position, its prior row stored beside the node;
@@ -2009,16 +2004,11 @@ __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, 
             const TreeNode nv = nodes[v];
             term = tree_term(nv);
             if (term) break;
-            uint32_t my_c = 0, my_n = 1, my_w = 0, my_l = 0;
-            for (uint32_t c = nv.child; c;) {
-                const TreeNode k = nodes[c];
-                if (lane == tree_action(k)) my_c = c, my_n = k.n, my_w = tree_wins(k), my_l = tree_losses(k);
-                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)k.sibling);
-            }
+            const TreeChild my = tree_lane_child(nodes, nv.child, lane);
             const uint32_t pi = lane < (uint32_t)kEvalOutputs ? pri[v * kEvalOutputs + lane] : 0u;
-            const uint32_t key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my_c != 0, my_w, my_l, my_n, nv.n, pi, explore), lane) : 0u);
+            const uint32_t key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my.mine(), my.w, my.l, my.n, nv.n, pi, explore), lane) : 0u);
             a_new = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
-            const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)my_c, (int)a_new);
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)my.c, (int)a_new);
             if (!c) {
                 grow = true;
                 break;
@@ -2050,7 +2040,7 @@ __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, 
 
 // gbl_tree_search_eval: k_tree's tree with a network leaf.  One wavefront per board (a grid-stride loop over boards).  The tree is
 // (iterations + 1) 16-byte nodes followed by (iterations + 1) 56-byte prior rows in dynamic LDS; the root planes stay in registers.
-// The search is tree_eval_iterations; the wavefront then writes the root's children out and decides.
+// The search is tree_eval_iterations; the wavefront then writes the root's children out and decides (tree_root_out).
 __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
                                                   const int8_t *__restrict__ mask, const EvalNet net, int32_t *__restrict__ visits_out,
                                                   int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
@@ -2069,14 +2059,8 @@ __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ sta
         const uint64_t cand = board_candidates(root, mover, mask, b, lane);
         uint32_t count;
         const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, net, root, mover, cand, iterations, explore, lane, count);
-        const TreeRootChild c = tree_root_child(nodes, lane);
-        if (lane < (uint32_t)kActions) {
-            if (visits_out) visits_out[b * kActions + lane] = (int32_t)c.n;
-            if (wins_out) wins_out[b * kActions + lane] = (int32_t)c.w;
-            if (losses_out) losses_out[b * kActions + lane] = (int32_t)c.l;
-            if (root_priors_out) root_priors_out[b * kActions + lane] = (uint8_t)at_root.pi;
-        }
-        const uint64_t key = wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull);
+        const uint64_t key = tree_root_out(nodes, lane, b, visits_out, wins_out, losses_out);
+        if (root_priors_out && lane < (uint32_t)kActions) root_priors_out[b * kActions + lane] = (uint8_t)at_root.pi;
         if (lane == 0) {
             if (action_out) action_out[b] = tree_action_of(key);
             if (nodes_out) nodes_out[b] = (int32_t)count;
@@ -2119,11 +2103,11 @@ struct SearchDecision {
 
 __device__ __forceinline__ SearchDecision search_decide(const TreeNode *nodes, uint32_t lane, bool sampled, uint64_t seed, uint64_t g, uint32_t q)
 {
-    const TreeRootChild c = tree_root_child(nodes, lane);
-    SearchDecision d{0, kHowSearch, (int)wave_sum(c.w - c.l), c.n};
-    d.action = tree_action_of(wave_max(c.mine ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
+    const TreeChild c = tree_lane_child(nodes, nodes[0].child, lane);
+    SearchDecision d{0, kHowSearch, (int)wave_sum(c.w - c.l), c.visits()};
+    d.action = tree_action_of(wave_max(c.mine() ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
     if (sampled) {
-        uint32_t run = c.n;  // (the running sum of the visits through this lane's action)
+        uint32_t run = c.visits();  // (the running sum of the visits through this lane's action)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const uint32_t below = (uint32_t)__shfl_up((int)run, o);
@@ -2218,6 +2202,51 @@ __device__ __forceinline__ void store_search_board(int8_t *__restrict__ state, i
     }
 }
 
+// What a ply's search leaves for the stores (all zero on a masked-random ply): the decision, the nodes created and, from the
+// evaluator-guided search alone, the root's q and this lane's byte of the root's prior row.
+struct SearchPly {
+    SearchDecision d;
+    uint32_t count, pi;
+    int root_q;
+};
+
+// The boards and plies of a self-play launch, for k_collect_search and k_collect_eval (every thread of the workgroup calls it; the
+// host flavour's selfplay_boards is the same loop).  search(B, who, legal, g, q, S): the mover's search of call q on board B -- false
+// where the masked-random sampler moves, else it fills S (the decision by search_decide) and returns after whatever keeps the next
+// search's writes to the tree behind this one's reads.  stored(at, S): wavefront 0, after the ply's cell `at` is written -- a
+// kernel's own extra trajectory arrays.  Both are lambdas of the calling kernel and are inlined here.
+template <typename Search, typename Stored>
+__device__ __forceinline__ void search_plies(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int8_t *__restrict__ done,
+                                             int32_t *__restrict__ turn, int64_t *__restrict__ counters, int64_t n, uint64_t seed,
+                                             uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
+                                             int64_t ply_stride, int64_t tile_stride, const SearchTraj &T, int illegal_mode, uint32_t *s_mask,
+                                             uint32_t *s_obs, Search &&search, Stored &&stored)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (ply_dev) ply0 += *ply_dev;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        SearchBoard B{board_planes(state, b, lane), to_move[b] != 0, turn ? turn[b] : 0, 0, 0u, 0u, 0u};
+        const uint64_t g = env_base + (uint64_t)b;
+        const int64_t cell0 = (b >> 6) * tile_stride + (b & 63);
+        for (uint32_t t = 0; t < plies; ++t) {
+            const uint32_t q = ply0 + t;
+            const int who = B.mover;
+            const uint64_t legal = legal54(B.p, who);
+            SearchPly S{};
+            if (!search(B, who, legal, g, q, S)) S.d.action = pick54(legal, draw32(seed, g, q));
+            const int action = uniform(S.d.action);
+            int winner;
+            const Ply y = search_step(B, legal, action, illegal_mode, winner);
+            if (tid < 64u) {  // wavefront 0: the ply's outputs
+                const int64_t at = (int64_t)t * ply_stride + cell0;
+                store_search_ply(T, at, lane, s_mask, s_obs, B, y, winner, action, S.d.value, S.count, S.d.how, who, S.d.my_n);
+                stored(at, S);
+            }
+        }
+        store_search_board(state, to_move, done, turn, counters, b, tid, B, plies);
+    }
+}
+
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                            uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
@@ -2232,47 +2261,31 @@ __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ 
     __shared__ uint32_t s_sum[2][2];
     __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    if (ply_dev) ply0 += *ply_dev;
-    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
-        SearchBoard B{board_planes(state, b, lane), to_move[b] != 0, turn ? turn[b] : 0, 0, 0u, 0u, 0u};
-        const uint64_t g = env_base + (uint64_t)b;
-        const int64_t cell0 = (b >> 6) * tile_stride + (b & 63);
-        for (uint32_t t = 0; t < plies; ++t) {
-            const uint32_t q = ply0 + t;
-            const int who = B.mover;
-            const uint64_t legal = legal54(B.p, who);
-            const bool tree = (who ? policy1 : policy0) == kPolicyTree;
-            SearchDecision d{0, 0, 0, 0u};
-            uint32_t count = 0;
-            if (tree) {
-                if (tid == 0) nodes[0] = TreeNode{};
-                if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
-                __syncthreads();  // (root and counters zeroed)
-                uint32_t plies_total = 0;
-                count = 1;
-                tree_iterations<W>(nodes, s_sum, B.p, who, legal, g, seed, q, who ? iterations1 : iterations0, who ? playouts1 : playouts0,
-                                   max_plies, explore, tid, lane, count, plies_total);
-                d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
-                __syncthreads();  // (every wavefront has read the root's children before the next search rewrites the tree)
-            } else {
-                d.action = pick54(legal, draw32(seed, g, q));
-            }
-            const int action = uniform(d.action);
-            int winner;
-            const Ply y = search_step(B, legal, action, illegal_mode, winner);
-            if (tid < 64u)  // wavefront 0: the ply's outputs
-                store_search_ply(T, (int64_t)t * ply_stride + cell0, lane, s_mask, s_obs, B, y, winner, action, d.value, count, d.how, who, d.my_n);
-        }
-        store_search_board(state, to_move, done, turn, counters, b, tid, B, plies);
-    }
+    search_plies(
+        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            if ((who ? policy1 : policy0) != kPolicyTree) return false;
+            if (tid == 0) nodes[0] = TreeNode{};
+            if (tid < 4u) (&s_sum[0][0])[tid] = 0u;
+            __syncthreads();  // (root and counters zeroed)
+            uint32_t plies_total = 0;
+            S.count = 1;
+            tree_iterations<W>(nodes, s_sum, B.p, who, legal, g, seed, q, who ? iterations1 : iterations0, who ? playouts1 : playouts0,
+                               max_plies, explore, tid, lane, S.count, plies_total);
+            S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+            __syncthreads();  // (every wavefront has read the root's children before the next search rewrites the tree)
+            return true;
+        },
+        [](int64_t, const SearchPly &) {});
 }
 
 // gbl_collect_search_eval: k_collect_search with the evaluator-guided search: one wavefront per board (a grid-stride loop over
-// boards), the ply loop inside, the tree rebuilt from an empty root on every ply -- ply q's search IS gbl_tree_search_eval of the
-// position, because both kernels run tree_eval_iterations.  Dynamic LDS: (most + 1) nodes, then (most + 1) prior rows, most = the
-// larger budget of the sides that search; beside it s_h and the two row images.  One wavefront: no workgroup barrier anywhere.  The
-// mover picks its network and budget wave-uniformly (field by field: the two structs stay in SGPRs).  The decision, the step and
-// the stores are k_collect_search's; the root's q and its prior row -- a byte in every lane -- go out beside them.
+// boards), the ply loop inside (search_plies), the tree rebuilt from an empty root on every ply -- ply q's search IS
+// gbl_tree_search_eval of the position, because both kernels run tree_eval_iterations.  Dynamic LDS: (most + 1) nodes, then (most + 1)
+// prior rows, most = the larger budget of the sides that search; beside it s_h and the two row images.  One wavefront: no workgroup
+// barrier anywhere, wave_lds_fence instead.  The mover picks its network and budget wave-uniformly (field by field: the two structs
+// stay in SGPRs).  The root's q and its prior row -- a byte in every lane -- go out beside the ply's cell, from this kernel's own
+// second lambda.
 __device__ __forceinline__ EvalNet eval_net_pick(const EvalNet &a, const EvalNet &b, int second)
 {
     return EvalNet{second ? b.w1 : a.w1, second ? b.b1 : a.b1, second ? b.w2 : a.w2, second ? b.b2 : a.b2, second ? b.hidden : a.hidden,
@@ -2293,40 +2306,22 @@ __global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state,
     __shared__ uint32_t s_h[kEvalMaxHidden / 4];
     __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
     const uint32_t lane = threadIdx.x;
-    if (ply_dev) ply0 += *ply_dev;
-    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
-        SearchBoard B{board_planes(state, b, lane), to_move[b] != 0, turn ? turn[b] : 0, 0, 0u, 0u, 0u};
-        const uint64_t g = env_base + (uint64_t)b;
-        const int64_t cell0 = (b >> 6) * tile_stride + (b & 63);
-        for (uint32_t t = 0; t < plies; ++t) {
-            const uint32_t q = ply0 + t;
-            const int who = B.mover;
-            const uint64_t legal = legal54(B.p, who);
-            const bool search = (who ? policy1 : policy0) == kPolicyEvalTree;
-            SearchDecision d{0, 0, 0, 0u};
-            uint32_t count = 0, my_pi = 0;
-            int root_q = 0;
-            if (search) {
-                const EvalNet net = eval_net_pick(net0, net1, who);
-                const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, net, B.p, who, legal, who ? iterations1 : iterations0, explore,
-                                                              lane, count);
-                my_pi = at_root.pi;
-                root_q = at_root.q;
-                d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
-                wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
-            } else {
-                d.action = pick54(legal, draw32(seed, g, q));
-            }
-            const int action = uniform(d.action);
-            int winner;
-            const Ply y = search_step(B, legal, action, illegal_mode, winner);
-            const int64_t at = (int64_t)t * ply_stride + cell0;
-            store_search_ply(T, at, lane, s_mask, s_obs, B, y, winner, action, d.value, count, d.how, who, d.my_n);
-            if (root_value_traj && lane == 0) root_value_traj[at] = root_q;
-            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)my_pi, priors_traj + at * kActions + lane);
-        }
-        store_search_board(state, to_move, done, turn, counters, b, lane, B, plies);
-    }
+    search_plies(
+        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            if ((who ? policy1 : policy0) != kPolicyEvalTree) return false;
+            const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
+                                                          who ? iterations1 : iterations0, explore, lane, S.count);
+            S.pi = at_root.pi;
+            S.root_q = at_root.q;
+            S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+            wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            return true;
+        },
+        [&](int64_t at, const SearchPly &S) {
+            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
+            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
+        });
 }
 
 // gbl_outcome_targets: one reverse pass over the plies per board, a lane per board and a wavefront per tile of 64 boards -- in both
@@ -3101,6 +3096,19 @@ static int check_traj(int64_t n, uint32_t plies, int64_t ply_stride, int64_t til
     return GBL_OK;
 }
 
+// The tail the two self-play entry points (gbl_collect_search, gbl_collect_search_eval) share, after their own checks: the
+// trajectory's strides and alignments.  T: the kernel's SearchTraj, built by the entry point from its arguments; more_words /
+// words_msg: the entry's own further 4-byte arrays (check_traj's `words`) and the message that names its whole list.
+static int check_search_traj(const SearchTraj &T, uintptr_t more_words, const char *words_msg, int64_t n, uint32_t plies, int64_t ply_stride,
+                             int64_t tile_stride, const int8_t *state, const int32_t *turn, const int64_t *counters)
+{
+    const uintptr_t words = more_words | reinterpret_cast<uintptr_t>(T.actions) | reinterpret_cast<uintptr_t>(T.value) |
+                            reinterpret_cast<uintptr_t>(T.nodes);
+    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, T.mask, T.obs, T.reward, words, words_msg, turn, counters)) return e;
+    if (reinterpret_cast<uintptr_t>(T.visits) & 1u) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
+    return GBL_OK;
+}
+
 extern "C" {
 
 
@@ -3811,30 +3819,20 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
                        int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = illegal_mode_error(illegal_mode)) return fail(GBL_ERR_ARG, why);
-    if ((policy0 != GBL_POLICY_RANDOM && policy0 != GBL_POLICY_TREE) || (policy1 != GBL_POLICY_RANDOM && policy1 != GBL_POLICY_TREE))
-        return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM or GBL_POLICY_TREE");
-    const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
-    int most = 0, wide = 1;  // the larger tree and the larger leaf of the sides that search
-    for (int m = 0; m < 2; ++m) {
-        if (pol[m] != GBL_POLICY_TREE) continue;
-        if (const char *why = tree_budget_error(its[m], pls[m])) return fail(GBL_ERR_ARG, why);
-        most = std::max(most, its[m]);
-        wide = std::max(wide, pls[m]);
-    }
-    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
-    if (const char *why = selfplay_window_error(sample_plies, turn != nullptr, ply0, plies, env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = collect_search_error(illegal_mode, policy0, policy1, iterations0, iterations1, playouts0, playouts1, max_plies,
+                                               explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
+        return fail(GBL_ERR_ARG, why);
+    // the larger tree and the larger leaf of the sides that search
+    const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
+    const int wide = std::max(1, std::max(policy0 == GBL_POLICY_TREE ? playouts0 : 0, policy1 == GBL_POLICY_TREE ? playouts1 : 0));
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;
-    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
-                                 reinterpret_cast<uintptr_t>(actions_traj) | reinterpret_cast<uintptr_t>(value_traj) |
-                                     reinterpret_cast<uintptr_t>(nodes_traj),
-                                 "actions_traj / value_traj / nodes_traj must be 4-byte aligned", turn, counters))
-        return e;
-    if (reinterpret_cast<uintptr_t>(visits_traj) & 1u) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
     const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
                        nodes_traj, how_traj, mover_traj};
+    if (const int e = check_search_traj(T, 0, "actions_traj / value_traj / nodes_traj must be 4-byte aligned", n, plies, ply_stride,
+                                        tile_stride, state, turn, counters))
+        return e;
     const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
     const size_t lds = sizeof(TreeNode) * ((size_t)most + 1);  // the tree: one node per iteration and the root
     const hipStream_t s = (hipStream_t)stream;
@@ -3875,17 +3873,16 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
         if (const int e = eval_net_of(evs[m], nets[m])) return e;
         most = std::max(most, its[m]);
     }
-    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
-                                 reinterpret_cast<uintptr_t>(actions_traj) | reinterpret_cast<uintptr_t>(value_traj) |
-                                     reinterpret_cast<uintptr_t>(nodes_traj) | reinterpret_cast<uintptr_t>(root_value_traj),
-                                 "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned", turn, counters))
-        return e;
-    if (reinterpret_cast<uintptr_t>(visits_traj) & 1u) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
     const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
                        nodes_traj, how_traj, mover_traj};
+    if (const int e = check_search_traj(T, reinterpret_cast<uintptr_t>(root_value_traj),
+                                        "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned", n, plies,
+                                        ply_stride, tile_stride, state, turn, counters))
+        return e;
+    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
     // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations, as gbl_tree_search_eval)
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)most + 1);
-    hipLaunchKernelGGL(k_collect_eval, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed,
+    hipLaunchKernelGGL(k_collect_eval, grid, dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed,
                        env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, T, root_value_traj, priors_traj, nets[0], nets[1], policy0,
                        policy1, (uint32_t)iterations0, (uint32_t)iterations1, (uint32_t)most, (uint32_t)explore, sample_plies, illegal_mode,
                        counters, turn);

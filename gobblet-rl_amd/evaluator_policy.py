@@ -9,7 +9,6 @@ no seed, no call index; two calls on the same boards give the same result.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import math
 from typing import Any
@@ -18,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._policy_base import _OnDevice, _TreeSearchPolicy
 
 HIDDEN_SIZES = (64, 128, 192, 256)
 OUTPUTS, VALUE = 56, 54
@@ -30,7 +30,7 @@ def _pow2_at_most(x: float) -> float:
     return 2.0 ** math.floor(math.log2(x))
 
 
-class GobbletEvaluator:
+class GobbletEvaluator(_OnDevice):
     """The four integer tensors of a ``gbl_evaluator`` on one device: w1 int8 (117, H), b1 int32 (H,), w2 int8 (H / 4, 56, 4) with
     element [j // 4, k, j % 4] = the weight of hidden unit j for output k, b2 int32 (56,), and the three shifts."""
 
@@ -118,23 +118,17 @@ class GobbletEvaluator:
         ev.scales = {"scale1": scale1, "scale_h": scale_h, "scale_p": scale_p, "scale_v": scale_v, "fold": fold}
         return ev
 
-    def _on_device(self):
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
-
     def evaluate_raw(self, state, to_move, mask=None, logits: bool = False):
         """``gbl_evaluate``: (priors uint8 (N, 54), value int32 (N,), logits int32 (N, 56) or None)."""
-        state = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(-1, nat.CELLS).contiguous()
+        state, to_move, mask = self._inputs(state, to_move, mask)
         n = state.shape[0]
-        to_move = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.int8).reshape(n, nat.ACTIONS).contiguous()
         pri = torch.empty((n, nat.ACTIONS), dtype=torch.uint8, device=self.device)
         val = torch.empty(n, dtype=torch.int32, device=self.device)
         log = torch.empty((n, OUTPUTS), dtype=torch.int32, device=self.device) if logits else None
         ev = self.as_struct()
         with self._on_device():
             nat.check(self._lib.gbl_evaluate(state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), pri.data_ptr(),
-                                             val.data_ptr(), nat.ptr(log), n, nat.current_stream(self.device)), "gbl_evaluate")
+                                             val.data_ptr(), nat.ptr(log), n, self._stream()), "gbl_evaluate")
         return pri, val, log
 
     def evaluate(self, state, to_move, mask=None):
@@ -144,7 +138,9 @@ class GobbletEvaluator:
         return pri / pri.sum(1, keepdim=True).clamp(min=1.0), val.to(torch.float32) / 128.0
 
 
-class EvaluatorTreeSearchGobbletPolicy:
+class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
+    _games_per_visit = 128  # (a network leaf counts as 128 games)
+
     def __init__(self, evaluator: GobbletEvaluator, iterations: int = 256, explore: int = 16, device=None, **kwargs: Any) -> None:
         """iterations: network leaves per decision (1 .. 512); explore: weight of the prior term of the selection key (0 .. 1024;
         the default is the best of the host-flavour sweep in profiles/r10/evaluator_policy.json); device: where the search runs
@@ -162,15 +158,8 @@ class EvaluatorTreeSearchGobbletPolicy:
         self.last_visits = self.last_wins = self.last_losses = self.last_nodes = self.last_action = None
         self.last_root_value = self.last_root_priors = None
 
-    def _on_device(self):
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
-
     def _run(self, state, to_move, mask) -> torch.Tensor:
-        state = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(-1, nat.CELLS).contiguous()
         n = state.shape[0]
-        to_move = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.int8).reshape(n, nat.ACTIONS).contiguous()
         visits = torch.empty((n, nat.ACTIONS), dtype=torch.int32, device=self.device)
         wins, losses = torch.empty_like(visits), torch.empty_like(visits)
         act = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -181,51 +170,8 @@ class EvaluatorTreeSearchGobbletPolicy:
             nat.check(self._lib.gbl_tree_search_eval(state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), self.iterations,
                                                      self.explore, visits.data_ptr(), wins.data_ptr(), losses.data_ptr(), act.data_ptr(),
                                                      nodes.data_ptr(), rootv.data_ptr(), rootp.data_ptr(), n,
-                                                     nat.current_stream(self.device)), "gbl_tree_search_eval")
+                                                     self._stream()), "gbl_tree_search_eval")
         self.last_visits, self.last_wins, self.last_losses = visits, wins, losses
         self.last_nodes, self.last_action, self.last_root_value, self.last_root_priors = nodes, act, rootv, rootp
         return act
 
-    def compute_actions_from_state(self, state, to_move, mask=None) -> torch.Tensor:
-        """The decision from ``squares`` (N,27) + ``to_move`` (N,): int32 (N,), -1 where a board has no candidate."""
-        return self._run(state, to_move, mask)
-
-    def visit_distribution(self, state, to_move, mask=None) -> torch.Tensor:
-        """float32 (N, 54): visits / iterations of every root action; 0 for non-candidates."""
-        self._run(state, to_move, mask)
-        return self.last_visits.to(torch.float32) / self.iterations
-
-    def action_values(self, state, to_move, mask=None) -> torch.Tensor:
-        """float32 (N, 54): (W - L) / (128 n) of every visited root action, -inf elsewhere."""
-        self._run(state, to_move, mask)
-        seen = self.last_visits > 0
-        vals = (self.last_wins - self.last_losses).to(torch.float32) / (self.last_visits.clamp(min=1) * 128).to(torch.float32)
-        return torch.where(seen, vals, torch.full_like(vals, float("-inf")))
-
-    def compute_actions(self, obs, mask=None) -> torch.Tensor:
-        """obs: int8 (N,3,3,13); mask: int8 (N,54) or None (the legal mask of the board)."""
-        obs = torch.as_tensor(obs).to(device=self.device, dtype=torch.int8).reshape(-1, 3, 3, 13).contiguous()
-        n = obs.shape[0]
-        state = torch.empty((n, nat.CELLS), dtype=torch.int8, device=self.device)
-        who = torch.empty(n, dtype=torch.int8, device=self.device)
-        with self._on_device():
-            nat.check(self._lib.gbl_decode_obs(obs.data_ptr(), state.data_ptr(), who.data_ptr(), n, nat.current_stream(self.device)),
-                      "gbl_decode_obs")
-        return self._run(state, who, mask)
-
-    # -- reference-shaped entry points (as GreedyGobbletPolicy) ----------------------------------------------
-    def compute_action(self, obs, mask) -> np.ndarray:
-        return np.array(int(self.compute_actions(np.asarray(obs)[None], np.asarray(mask)[None])[0]))
-
-    def compute_actions_rllib(self, obs_batch):
-        observations = np.asarray(obs_batch["observation"])
-        observations = observations.reshape(observations.shape[0], 3, 3, -1)
-        return list(self.compute_actions(observations, np.asarray(obs_batch["action_mask"])).cpu().numpy())
-
-    def forward(self, batch, state=None, **kwargs):
-        """Tianshou-adapter shape: ``batch.obs.obs`` / ``batch.obs.mask`` (or dict keys "obs" / "mask") -> {"act": int64 (N,)}."""
-        ob = batch["obs"] if isinstance(batch, dict) else batch.obs
-        obs = ob["obs"] if isinstance(ob, dict) else ob.obs
-        mask = ob["mask"] if isinstance(ob, dict) else ob.mask
-        act = self.compute_actions(obs, torch.as_tensor(mask).to(torch.int8))
-        return {"act": act.to(torch.int64).cpu().numpy()}

@@ -18,13 +18,13 @@ from __future__ import annotations
 
 from typing import Any, Optional
 
-import numpy as np
 import torch
 
 from . import _native as nat
+from ._policy_base import _ReferenceAdapters
 
 
-class GreedyGobbletPolicy:
+class GreedyGobbletPolicy(_ReferenceAdapters):
     def __init__(self, depth: Optional[int] = 2, seed: Optional[int] = 0, device="cuda:0", env_base: int = 0,
                  **kwargs: Any) -> None:
         """env_base: global index of board 0 of the batches this policy is handed (a shard of a larger batch passes
@@ -98,23 +98,7 @@ class GreedyGobbletPolicy:
         self._calls += 1
         return out
 
-    # -- reference-shaped single-observation entry points ------------------------------------------------
-    def compute_action(self, obs, mask) -> np.ndarray:  # greedy_policy.py:38-221
-        return np.array(int(self.compute_actions(np.asarray(obs)[None], np.asarray(mask)[None])[0]))
-
-    def compute_actions_rllib(self, obs_batch):  # greedy_policy.py:21-31
-        observations = np.asarray(obs_batch["observation"])
-        observations = observations.reshape(observations.shape[0], 3, 3, -1)
-        return list(self.compute_actions(observations, np.asarray(obs_batch["action_mask"])).cpu().numpy())
-
-    def forward(self, batch, state=None, **kwargs):
-        """Tianshou-adapter shape (greedy_policy_tianshou.py:63-84): ``batch.obs.obs`` / ``batch.obs.mask``
-        (or dict keys "obs" / "mask") for all environments at once -> {"act": int64 (N,)} on the host."""
-        ob = batch["obs"] if isinstance(batch, dict) else batch.obs
-        obs = ob["obs"] if isinstance(ob, dict) else ob.obs
-        mask = ob["mask"] if isinstance(ob, dict) else ob.mask
-        act = self.compute_actions(obs, torch.as_tensor(mask).to(torch.int8))
-        return {"act": act.to(torch.int64).cpu().numpy()}
+    # compute_action / compute_actions_rllib / forward: the reference-shaped entry points, _ReferenceAdapters
 
     def compute_action_tianshou(self, obs):  # greedy_policy.py:33-36
         mask = obs.mask

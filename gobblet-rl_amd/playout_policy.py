@@ -10,16 +10,15 @@ The surface mirrors ``GreedyGobbletPolicy`` (``compute_actions`` / ``compute_act
 """
 from __future__ import annotations
 
-import contextlib
 from typing import Any
 
-import numpy as np
 import torch
 
 from . import _native as nat
+from ._policy_base import _SearchPolicy
 
 
-class MonteCarloGobbletPolicy:
+class MonteCarloGobbletPolicy(_SearchPolicy):
     def __init__(self, playouts: int = 64, max_plies: int = 64, seed: int = 0, device="cuda:0", env_base: int = 0,
                  **kwargs: Any) -> None:
         """playouts: games per candidate action (1 .. 4096); max_plies: masked-random plies per game after the action (0 .. 255)
@@ -39,19 +38,8 @@ class MonteCarloGobbletPolicy:
         self.last_wins = self.last_losses = self.last_plies = None
         self.last_action = None  # int32 (N,): the decision of action_values()' playouts
 
-    def _stream(self):
-        return nat.current_stream(self.device)
-
-    def _on_device(self):
-        """Launches go to the policy's device (on its current stream), whichever device is current."""
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
-
     def _run(self, state: torch.Tensor, to_move: torch.Tensor, mask) -> torch.Tensor:
-        state = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(-1, nat.CELLS).contiguous()
         n = state.shape[0]
-        to_move = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.int8).reshape(n, nat.ACTIONS).contiguous()
         wins = torch.empty((n, nat.ACTIONS), dtype=torch.int32, device=self.device)
         losses = torch.empty_like(wins)
         act = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -65,52 +53,17 @@ class MonteCarloGobbletPolicy:
         self.last_wins, self.last_losses, self.last_plies = wins, losses, plies
         return act
 
-    def compute_actions_from_state(self, state: torch.Tensor, to_move: torch.Tensor, mask=None) -> torch.Tensor:
-        """The decision from ``squares`` (N,27) + ``to_move`` (N,): int32 (N,), -1 where a board has no candidate."""
-        return self._run(state, to_move, mask)
-
     def action_values(self, state: torch.Tensor, to_move: torch.Tensor, mask=None) -> torch.Tensor:
         """float32 (N, 54): (wins - losses) / playouts of every candidate action, -inf elsewhere (one call; the decision of the
         same playouts is left in ``last_action``)."""
-        self.last_action = self._run(state, to_move, mask)
+        st, tm, m8 = self._inputs(state, to_move, mask)
+        self.last_action = self._run(st, tm, m8)
         vals = (self.last_wins - self.last_losses).to(torch.float32) / self.playouts
-        n = vals.shape[0]
-        legal = torch.empty((n, nat.ACTIONS), dtype=torch.int8, device=self.device)
-        st = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(n, nat.CELLS).contiguous()
-        tm = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
+        legal = torch.empty_like(vals, dtype=torch.int8)
         with self._on_device():
-            nat.check(self._lib.gbl_legal_mask(st.data_ptr(), tm.data_ptr(), legal.data_ptr(), n, self._stream()),
+            nat.check(self._lib.gbl_legal_mask(st.data_ptr(), tm.data_ptr(), legal.data_ptr(), st.shape[0], self._stream()),
                       "gbl_legal_mask")
         cand = legal != 0
-        if mask is not None:
-            cand &= torch.as_tensor(mask).to(self.device).reshape(n, nat.ACTIONS) != 0
+        if m8 is not None:
+            cand &= m8 != 0
         return torch.where(cand, vals, torch.full_like(vals, float("-inf")))
-
-    def compute_actions(self, obs, mask=None) -> torch.Tensor:
-        """obs: int8 (N,3,3,13); mask: int8 (N,54) or None (the legal mask of the board)."""
-        obs = torch.as_tensor(obs).to(device=self.device, dtype=torch.int8).reshape(-1, 3, 3, 13).contiguous()
-        n = obs.shape[0]
-        state = torch.empty((n, nat.CELLS), dtype=torch.int8, device=self.device)
-        who = torch.empty(n, dtype=torch.int8, device=self.device)
-        with self._on_device():
-            nat.check(self._lib.gbl_decode_obs(obs.data_ptr(), state.data_ptr(), who.data_ptr(), n, self._stream()),
-                      "gbl_decode_obs")
-        return self._run(state, who, mask)
-
-    # -- reference-shaped entry points (as GreedyGobbletPolicy) ----------------------------------------------
-    def compute_action(self, obs, mask) -> np.ndarray:
-        return np.array(int(self.compute_actions(np.asarray(obs)[None], np.asarray(mask)[None])[0]))
-
-    def compute_actions_rllib(self, obs_batch):
-        observations = np.asarray(obs_batch["observation"])
-        observations = observations.reshape(observations.shape[0], 3, 3, -1)
-        return list(self.compute_actions(observations, np.asarray(obs_batch["action_mask"])).cpu().numpy())
-
-    def forward(self, batch, state=None, **kwargs):
-        """Tianshou-adapter shape: ``batch.obs.obs`` / ``batch.obs.mask`` (or dict keys "obs" / "mask") -> {"act": int64 (N,)}."""
-        ob = batch["obs"] if isinstance(batch, dict) else batch.obs
-        obs = ob["obs"] if isinstance(ob, dict) else ob.obs
-        mask = ob["mask"] if isinstance(ob, dict) else ob.mask
-        act = self.compute_actions(obs, torch.as_tensor(mask).to(torch.int8))
-        return {"act": act.to(torch.int64).cpu().numpy()}
-

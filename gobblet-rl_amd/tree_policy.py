@@ -11,16 +11,15 @@ as the whole batch would.  The search is integer-only: the kernel and the host f
 """
 from __future__ import annotations
 
-import contextlib
 from typing import Any
 
-import numpy as np
 import torch
 
 from . import _native as nat
+from ._policy_base import _TreeSearchPolicy
 
 
-class TreeSearchGobbletPolicy:
+class TreeSearchGobbletPolicy(_TreeSearchPolicy):
     def __init__(self, iterations: int = 256, playouts: int = 16, max_plies: int = 64, explore: int = 16, seed: int = 0,
                  device="cuda:0", env_base: int = 0, **kwargs: Any) -> None:
         """iterations: leaves per decision (1 .. 1024); playouts: games per leaf (1 .. 256); max_plies: masked-random plies per game
@@ -32,6 +31,7 @@ class TreeSearchGobbletPolicy:
             if not lo <= int(val) <= hi:
                 raise ValueError(f"{name} must be in [{lo}, {hi}]")
         self.iterations, self.playouts, self.max_plies, self.explore = int(iterations), int(playouts), int(max_plies), int(explore)
+        self._games_per_visit = self.playouts  # (a leaf is `playouts` games)
         self.seed = int(seed or 0)
         self.env_base = int(env_base)
         self.device = torch.device(device)
@@ -41,19 +41,8 @@ class TreeSearchGobbletPolicy:
         # mover's side, int32 (N,) nodes created and plies played, int32 (N,) the decision
         self.last_visits = self.last_wins = self.last_losses = self.last_nodes = self.last_plies = self.last_action = None
 
-    def _stream(self):
-        return nat.current_stream(self.device)
-
-    def _on_device(self):
-        """Launches go to the policy's device (on its current stream), whichever device is current."""
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
-
     def _run(self, state: torch.Tensor, to_move: torch.Tensor, mask) -> torch.Tensor:
-        state = torch.as_tensor(state).to(device=self.device, dtype=torch.int8).reshape(-1, nat.CELLS).contiguous()
         n = state.shape[0]
-        to_move = torch.as_tensor(to_move).to(device=self.device, dtype=torch.int8).reshape(n).contiguous()
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.int8).reshape(n, nat.ACTIONS).contiguous()
         visits = torch.empty((n, nat.ACTIONS), dtype=torch.int32, device=self.device)
         wins, losses = torch.empty_like(visits), torch.empty_like(visits)
         act = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -68,49 +57,3 @@ class TreeSearchGobbletPolicy:
         self.last_nodes, self.last_plies, self.last_action = nodes, plies, act
         return act
 
-    def compute_actions_from_state(self, state: torch.Tensor, to_move: torch.Tensor, mask=None) -> torch.Tensor:
-        """The decision from ``squares`` (N,27) + ``to_move`` (N,): int32 (N,), -1 where a board has no candidate."""
-        return self._run(state, to_move, mask)
-
-    def visit_distribution(self, state: torch.Tensor, to_move: torch.Tensor, mask=None) -> torch.Tensor:
-        """float32 (N, 54): visits / iterations of every root action -- the policy target of a trainer; 0 for non-candidates (one
-        call; the decision of the same search is left in ``last_action``)."""
-        self._run(state, to_move, mask)
-        return self.last_visits.to(torch.float32) / self.iterations
-
-    def action_values(self, state: torch.Tensor, to_move: torch.Tensor, mask=None) -> torch.Tensor:
-        """float32 (N, 54): (W - L) / (n * playouts) of every visited root action, -inf elsewhere (one call; the decision of the
-        same search is left in ``last_action``)."""
-        self._run(state, to_move, mask)
-        seen = self.last_visits > 0
-        games = (self.last_visits.clamp(min=1) * self.playouts).to(torch.float32)
-        vals = (self.last_wins - self.last_losses).to(torch.float32) / games
-        return torch.where(seen, vals, torch.full_like(vals, float("-inf")))
-
-    def compute_actions(self, obs, mask=None) -> torch.Tensor:
-        """obs: int8 (N,3,3,13); mask: int8 (N,54) or None (the legal mask of the board)."""
-        obs = torch.as_tensor(obs).to(device=self.device, dtype=torch.int8).reshape(-1, 3, 3, 13).contiguous()
-        n = obs.shape[0]
-        state = torch.empty((n, nat.CELLS), dtype=torch.int8, device=self.device)
-        who = torch.empty(n, dtype=torch.int8, device=self.device)
-        with self._on_device():
-            nat.check(self._lib.gbl_decode_obs(obs.data_ptr(), state.data_ptr(), who.data_ptr(), n, self._stream()),
-                      "gbl_decode_obs")
-        return self._run(state, who, mask)
-
-    # -- reference-shaped entry points (as GreedyGobbletPolicy) ----------------------------------------------
-    def compute_action(self, obs, mask) -> np.ndarray:
-        return np.array(int(self.compute_actions(np.asarray(obs)[None], np.asarray(mask)[None])[0]))
-
-    def compute_actions_rllib(self, obs_batch):
-        observations = np.asarray(obs_batch["observation"])
-        observations = observations.reshape(observations.shape[0], 3, 3, -1)
-        return list(self.compute_actions(observations, np.asarray(obs_batch["action_mask"])).cpu().numpy())
-
-    def forward(self, batch, state=None, **kwargs):
-        """Tianshou-adapter shape: ``batch.obs.obs`` / ``batch.obs.mask`` (or dict keys "obs" / "mask") -> {"act": int64 (N,)}."""
-        ob = batch["obs"] if isinstance(batch, dict) else batch.obs
-        obs = ob["obs"] if isinstance(ob, dict) else ob.obs
-        mask = ob["mask"] if isinstance(ob, dict) else ob.mask
-        act = self.compute_actions(obs, torch.as_tensor(mask).to(torch.int8))
-        return {"act": act.to(torch.int64).cpu().numpy()}

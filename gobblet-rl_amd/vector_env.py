@@ -469,28 +469,22 @@ class BatchedGobblet:
                 raise ValueError("sample_plies needs the per-board turn counter: create the environment with track_turn=True")
             if opening_plies:
                 raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
-        if ep is not None:
-            structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
-            nat.check(self._lib.gbl_collect_search_eval(
-                self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
-                f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
-                f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
-                nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")),
-                nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), n, out["_ply_stride"], out["_tile_stride"], self.seed,
-                self.env_base, self._ply, nat.ptr(self._ply_dev), T, *ep["policies"],
-                *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"], ep["explore"], ep["sample_plies"],
-                self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream()),
-                "gbl_collect_search_eval")
-        elif sp is not None:
-            nat.check(self._lib.gbl_collect_search(
-                self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
-                f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
-                f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
-                nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")), n,
-                out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T,
-                *sp["policies"], *sp["iterations"], *sp["playouts"], sp["max_plies"], sp["explore"], sp["sample_plies"],
-                self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream()),
-                "gbl_collect_search")
+            # what the two self-play entry points take alike: the boards and the 12 trajectory arrays, the window, and the tail
+            head = (self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
+                    f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
+                    f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
+                    nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")))
+            window = (n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T)
+            tail = (sp["sample_plies"], self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream())
+            if ep is not None:
+                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
+                nat.check(self._lib.gbl_collect_search_eval(
+                    *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), *window, *ep["policies"],
+                    *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"], ep["explore"], *tail),
+                    "gbl_collect_search_eval")
+            else:
+                nat.check(self._lib.gbl_collect_search(*head, *window, *sp["policies"], *sp["iterations"], *sp["playouts"], sp["max_plies"],
+                                                       sp["explore"], *tail), "gbl_collect_search")
         elif policies is not None:
             try:
                 p0, p1 = (self.POLICIES[x] if isinstance(x, str) else int(x) for x in policies)
@@ -528,6 +522,23 @@ class BatchedGobblet:
             self.observation.copy_(self._last_ply(out, "observation"))
         return out
 
+    @staticmethod
+    def _pair(v) -> list:
+        """A per-side setting of ``search=``: a value for both sides, or a pair."""
+        return list(v) if isinstance(v, (tuple, list)) else [v, v]
+
+    @staticmethod
+    def _is_random(x) -> bool:
+        return x == "random" or (not isinstance(x, str) and x == nat.POLICY_RANDOM)
+
+    @staticmethod
+    def _search_kw(defaults: dict, search, unknown_msg: str) -> dict:
+        """``defaults`` updated with ``search=``; a key it does not have is an error."""
+        unknown = set(search or ()) - set(defaults)
+        if unknown:
+            raise ValueError(unknown_msg % sorted(unknown))
+        return {**defaults, **(search or {})}
+
     def _search_params(self, policies, search):
         """The arguments of ``gbl_collect_search`` when a side of ``policies`` plays the tree search, else None."""
         from .tree_policy import TreeSearchGobbletPolicy
@@ -541,13 +552,9 @@ class BatchedGobblet:
             if search is not None:
                 raise ValueError("search= belongs to policies with a 'tree' side")
             return None
-        kw = dict(iterations=256, playouts=16, max_plies=64, explore=16, sample_plies=0)  # TreeSearchGobbletPolicy's defaults
-        unknown = set(search or ()) - set(kw)
-        if unknown:
-            raise ValueError("search: unknown keys %s" % sorted(unknown))
-        kw.update(search or {})
-        pair = lambda v: tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v), int(v))  # noqa: E731
-        its, pls = list(pair(kw["iterations"])), list(pair(kw["playouts"]))
+        kw = self._search_kw(dict(iterations=256, playouts=16, max_plies=64, explore=16, sample_plies=0),  # TreeSearchGobbletPolicy's defaults
+                             search, "search: unknown keys %s")
+        its, pls = ([int(x) for x in self._pair(kw[k])] for k in ("iterations", "playouts"))
         if len(its) != 2 or len(pls) != 2:
             raise ValueError("search: iterations / playouts are a value or a pair, one value per side")
         codes = []
@@ -561,7 +568,7 @@ class BatchedGobblet:
                 codes.append(nat.POLICY_TREE)
             elif trees[m]:
                 codes.append(nat.POLICY_TREE)
-            elif x == "random" or (not isinstance(x, str) and x == nat.POLICY_RANDOM):
+            elif self._is_random(x):
                 codes.append(nat.POLICY_RANDOM)
             else:
                 raise ValueError("policies: the tree search plays against 'tree' or 'random' (not %r)" % (x,))
@@ -587,13 +594,9 @@ class BatchedGobblet:
         evs = [is_eval(x) for x in sides]
         if len(sides) != 2 or not any(evs):
             return None
-        kw = dict(evaluator=None, iterations=256, explore=None, sample_plies=0)  # EvaluatorTreeSearchGobbletPolicy's defaults
-        unknown = set(search or ()) - set(kw)
-        if unknown:
-            raise ValueError("search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies)" % sorted(unknown))
-        kw.update(search or {})
-        pair = lambda v: list(v) if isinstance(v, (tuple, list)) else [v, v]  # noqa: E731
-        its, nets = pair(kw["iterations"]), pair(kw["evaluator"])
+        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0),  # EvaluatorTreeSearchGobbletPolicy's defaults
+                             search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies)")
+        its, nets = self._pair(kw["iterations"]), self._pair(kw["evaluator"])
         if len(its) != 2 or len(nets) != 2:
             raise ValueError("search: iterations / evaluator are a value or a pair, one per side")
         codes, explores = [], []
@@ -604,7 +607,7 @@ class BatchedGobblet:
                 codes.append(nat.POLICY_EVAL_TREE)
             elif evs[m]:
                 codes.append(nat.POLICY_EVAL_TREE)
-            elif x == "random" or (not isinstance(x, (str, TreeSearchGobbletPolicy)) and x == nat.POLICY_RANDOM):
+            elif self._is_random(x):
                 codes.append(nat.POLICY_RANDOM)
                 nets[m] = None
             else:

@@ -68,7 +68,8 @@ def main(out_path, with_sweep=True):
             y = float(np.median(t_yard))
             for h in HIDDEN:
                 e = float(np.median(t_eval[h]))
-                rows.append({"boards": n, "iterations": I, "hidden": h, "ms_per_launch": e, "yardstick_ms": y, "yardstick_min_ms": min(t_yard),
+                rows.append({"boards": n, "iterations": I, "hidden": h, "ms_per_launch": e, "ms_min": min(t_eval[h]), "ms_max": max(t_eval[h]),
+                             "yardstick_ms": y, "yardstick_min_ms": min(t_yard),
                              "yardstick_max_ms": max(t_yard), "ratio_to_yardstick": e / y,
                              "leaves_per_s": float(pols[h].last_nodes.sum()) / (e * 1e-3)})
                 print(rows[-1], flush=True)
@@ -76,8 +77,9 @@ def main(out_path, with_sweep=True):
             ev = random_evaluator(h)
             ev.evaluate_raw(st, tm)
             torch.cuda.synchronize()
-            ms = float(np.median([event_ms(lambda: ev.evaluate_raw(st, tm)) for _ in range(REPS)]))
-            evals.append({"boards": n, "hidden": h, "ms_per_launch": ms, "evaluations_per_s": n / (ms * 1e-3)})
+            times = [event_ms(lambda: ev.evaluate_raw(st, tm)) for _ in range(REPS)]
+            ms = float(np.median(times))
+            evals.append({"boards": n, "hidden": h, "ms_per_launch": ms, "ms_min": min(times), "ms_max": max(times), "evaluations_per_s": n / (ms * 1e-3)})
             print(evals[-1], flush=True)
     rec = {"metric": "gbl_tree_search_eval vs gbl_tree_search(iterations, 16 playouts), HIP-event ms per launch (median of %d)" % REPS,
            "device": torch.cuda.get_device_name(0), "rows": rows, "k_evaluate": evals}

@@ -51,7 +51,7 @@ def timed(fn, iters):
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
+    return times
 
 
 def time_tree(st, tm, I, P, explore, iters=5):
@@ -65,8 +65,8 @@ def time_tree(st, tm, I, P, explore, iters=5):
         nat.check(nat.lib().gbl_tree_search(st.data_ptr(), tm.data_ptr(), None, I, P, M, explore, 0, 0, call, v.data_ptr(), w.data_ptr(),
                                             l.data_ptr(), a.data_ptr(), nd.data_ptr(), p.data_ptr(), n, nat.current_stream(DEV)),
                   "gbl_tree_search")
-    ms = timed(go, iters)
-    return ms, int(p.sum()), float(nd.to(torch.float64).mean())
+    times = timed(go, iters)
+    return times, int(p.sum()), float(nd.to(torch.float64).mean())
 
 
 def time_playout(st, tm, K, iters=5):
@@ -79,8 +79,7 @@ def time_playout(st, tm, K, iters=5):
     def go(call):
         nat.check(nat.lib().gbl_playout_values(st.data_ptr(), tm.data_ptr(), None, K, M, 0, 0, call, w.data_ptr(), l.data_ptr(),
                                                a.data_ptr(), p.data_ptr(), n, nat.current_stream(DEV)), "gbl_playout_values")
-    ms = timed(go, iters)
-    return ms, int(p.sum())
+    return float(np.median(timed(go, iters))), int(p.sum())
 
 
 def tree_waves(n, P):  # the library's rule (csrc/gobblet_hip.hip tree_waves)
@@ -182,7 +181,8 @@ def main():
     if argv[:1] == ["--trace"]:
         n, I, P = (int(x) for x in argv[1:4])
         st, tm = states(n)
-        ms, plies, nodes = time_tree(st, tm, I, P, 128, 3)
+        times, plies, nodes = time_tree(st, tm, I, P, 128, 3)
+        ms = float(np.median(times))
         print(json.dumps({"boards": n, "iterations": I, "playouts": P, "ms": ms, "plies": plies}))
         return
     if argv[:1] == ["--host"]:
@@ -194,12 +194,13 @@ def main():
     for n in (4096, 65536):
         st, tm = states(n)
         for I, P in BUDGETS:
-            ms, plies, nodes = time_tree(st, tm, I, P, explore)
+            times, plies, nodes = time_tree(st, tm, I, P, explore)
+            ms = float(np.median(times))
             K = I * P // CANDIDATES
             pms, pplies = time_playout(st, tm, K, 3)
             rate, prate = plies / (ms / 1e3), pplies / (pms / 1e3)
             rows.append({"boards": n, "iterations": I, "playouts": P, "max_plies": M, "explore": explore,
-                         "waves_per_board": tree_waves(n, P), "ms_per_launch": ms, "decisions_per_s": n / (ms / 1e3),
+                         "waves_per_board": tree_waves(n, P), "ms_per_launch": ms, "ms_min": min(times), "ms_max": max(times), "decisions_per_s": n / (ms / 1e3),
                          "useful_plies_per_s": rate, "plies_per_decision": plies / n, "nodes_per_decision": nodes,
                          "playout_values_playouts": K, "playout_values_ms": pms, "playout_values_plies_per_s": prate,
                          "plies_per_s_vs_playout_values": rate / prate})
