@@ -8,6 +8,7 @@
     TreeSearchGobbletPolicy  UCT tree search per board on the same playouts (root visit distribution and values)
     GobbletEvaluator  a small integer network (priors and value of a position) evaluated inside the kernels
     EvaluatorTreeSearchGobbletPolicy  the tree search with that network in place of the playouts
+    SolverGobbletPolicy  the exact bounded-depth solver: proven wins and losses per action, optionally over another policy
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in
 ``include/gobblet_hip.h``); there is no CPU fallback.  Importing this package needs torch;
@@ -22,6 +23,7 @@ from .greedy_policy import GreedyGobbletPolicy  # noqa: F401
 from .playout_policy import MonteCarloGobbletPolicy  # noqa: F401
 from .tree_policy import TreeSearchGobbletPolicy  # noqa: F401
 from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator  # noqa: F401
+from .solver_policy import SolverGobbletPolicy  # noqa: F401
 from .random_policy import RandomAdmissiblePolicy  # noqa: F401
 from .sharding import make_shard, reduce_counters, shard_bounds  # noqa: F401
 

@@ -35,6 +35,7 @@ POLICY_RANDOM, POLICY_GREEDY1, POLICY_GREEDY2, POLICY_GREEDY3 = 0, 1, 2, 3  # gb
 HOW_RANDOM, HOW_GREEDY, HOW_FALLBACK = 0, 1, 2
 POLICY_TREE, HOW_SEARCH, HOW_SEARCH_SAMPLED, Z_OPEN = 4, 3, 4, -128  # gbl_collect_search / gbl_outcome_targets
 POLICY_EVAL_TREE = 5  # gbl_collect_search_eval
+SOLVE_MAX_DEPTH, SOLVE_NONE = 6, -128  # gbl_solve
 STATUS_ILLEGAL, STATUS_OUT_OF_RANGE = 1, 2  # gbl_step_ex / gbl_collect_from_ex status bits
 CELLS, ACTIONS, OBS_BYTES = 27, 54, 117
 COUNTER_STRIPES, COUNTER_STRIDE = 64, 16
@@ -75,6 +76,7 @@ SIGNATURES = {
     "gbl_tree_search": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_evaluate": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_tree_search_eval": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gbl_solve": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp]),
     "gbl_counter_add": (_int, [_vp, _u32, _vp]),
     "gbl_collect": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32,
                            _int, _vp, _vp, _vp]),

@@ -13,6 +13,7 @@
 //   -DGBL_AB_COLLECT_CFG          a menu of role-kernel forms in one library, picked at run time with gbl_ab_collect_cfg(cfg)
 //   -DGBL_FORCE_GREEDY_SHAPE=s    the greedy kernels' block shape (11, 14, 18, 26, 28, 48, 56)
 //   -DGBL_COLLECT_WAVES_PER_EU=a,b / -DGBL_CP_WAVES_PER_EU=n   occupancy pins of k_collect / k_collect_policy
+//   -DGBL_SOLVE_DEAL=0|1          k_solve's (action, reply) pairs dealt interleaved / off a counter in LDS
 #pragma once
 
 #ifndef GBL_X_GREEDY_SKIP
@@ -36,9 +37,13 @@
 #ifndef GBL_FORCE_GREEDY_SHAPE
 #define GBL_FORCE_GREEDY_SHAPE 0
 #endif
+#ifndef GBL_SOLVE_DEAL
+#define GBL_SOLVE_DEAL 0
+#endif
 
 namespace gbl {
 namespace knob {
+constexpr int kSolveDeal = GBL_SOLVE_DEAL;
 constexpr int kGreedySkip = GBL_X_GREEDY_SKIP;
 constexpr int kGreedyPairCap = GBL_X_GREEDY_PAIR_CAP;
 constexpr int kForcedNt = GBL_FORCE_NT;

@@ -680,6 +680,35 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
     return GBL_OK;
 }
 
+int gbl_cpu_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, int depth, int8_t *outcome_out, int8_t *value_out,
+                  int32_t *action_out, int64_t n, void *)
+{
+    int code = 0;
+    if (const char *why = solve_error(depth, n, state, to_move, action_out, code)) return fail(code ? GBL_ERR_ALIGN : GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole game tree: every board is worth a thread)
+        for (int64_t b = b0; b < b1; ++b) {
+            const HostRoot R = host_root(state, to_move, mask, b);
+            int8_t out[kActions];
+            uint32_t best = 0;
+            for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+                out[a] = (int8_t)kSolveNone;
+                if (!((R.cand >> a) & 1ull)) continue;
+                SolveRoot A = solve_root_action(R.p, R.mover, a, depth);
+                for (uint64_t l = A.deep; l; l &= l - 1)
+                    A.key = std::max(A.key, solve_reply(R.p, R.mover, a, (uint32_t)__builtin_ctzll(l), depth, A.key));
+                if (A.deep) A.c = solve_parent(solve_of_key(A.key));
+                out[a] = (int8_t)A.c;
+                best = std::max(best, solve_action_key(A.c, a));
+            }
+            if (outcome_out) memcpy(outcome_out + b * kActions, out, sizeof out);
+            if (value_out) value_out[b] = (int8_t)solve_value_of(best);
+            if (action_out) action_out[b] = solve_action_of(best);
+        }
+    }, 1);
+    return GBL_OK;
+}
+
 // One board's search (the contract of gbl_tree_search, one iteration and one playout at a time): the root's children into visits /
 // wins / losses (zeroed here), the decision's order key (0: no child), the nodes created and the plies played.
 struct HostSearch {

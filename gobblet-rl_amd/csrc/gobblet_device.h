@@ -2211,6 +2211,130 @@ __device__ __forceinline__ TreeEvalLeaf tree_eval_select(const TreeNode *nodes, 
     }
 }
 
+// ---- gbl_solve: the exact depth-bounded solver (contract: include/gobblet_hip.h) ----------------------------------------------
+// A result c is +k (the mover wins at ply k), -k (the mover has lost by ply k) or 0 (unproven); rank orders them: the shortest
+// win, then the unproven, then the longest loss.  A node's best result travels as an ORDER KEY, rank + 128 (1 .. 191; 0 = no
+// move yet, which reads back as V = 0), so that "the result of largest rank" is an unsigned max -- in a register, or an LDS
+// atomic where the lanes of a wavefront share a node.
+constexpr int kSolveMaxDepth = 6;  // GBL_SOLVE_MAX_DEPTH
+constexpr int kSolveNone = -128;   // GBL_SOLVE_NONE
+
+__device__ __forceinline__ int solve_rank(int c) { return c > 0 ? 64 - c : (c < 0 ? -64 - c : 0); }
+__device__ __forceinline__ uint32_t solve_key(int c) { return (uint32_t)(solve_rank(c) + 128); }
+__device__ __forceinline__ int solve_of_key(uint32_t key)  // V of the node whose best key this is (rank is its own inverse)
+{
+    return key ? solve_rank((int)key - 128) : 0;
+}
+// c(a) where nobody has won after a: from u = V of the position after a, for the other side
+__device__ __forceinline__ int solve_parent(int u) { return u == 0 ? 0 : (u > 0 ? -(u + 1) : 1 - u); }
+// c(a) where check_for_winner() = w after side s played a: s won, s lost at once (it uncovered a line), or 0 = nobody yet
+__device__ __forceinline__ int solve_now(int w, int s) { return w == 0 ? 0 : (w == (s ? -1 : 1) ? 1 : -1); }
+
+// The window cut every level shares.  A node's best order key so far is `best`; what is the deepest its NEXT quiet move need be
+// searched (plies below that move, at most `left`)?  A quiet move gives +2 at best (every answer of the other side loses at
+// once), so a best of +2 settles the node: 0.  A best of +k, k >= 3, is outranked by a +j with j < k alone, and a +j shows with
+// j - 1 plies below the move: k - 2 of them are enough.  A shallower search can only turn a result into 0 (a proven result is
+// the same at every depth that proves it), and 0 ranks below every win -- so the node's best key, the only thing kept, is that of
+// the full-width definition.  A best that is no win cuts nothing.
+__device__ __forceinline__ int solve_plies_needed(uint32_t best, int left)
+{
+    const int k = 192 - (int)best;  // best = solve_key(+k)
+    return k >= 2 && k - 2 < left ? k - 2 : left;
+}
+
+// V(p, s, r), 1 <= r <= MAXR: the recursion unrolled MAXR levels deep by the template parameter (every level inlined once: no call,
+// no stack), r the run-time bound that stops it earlier.  Two passes over a node's moves, which change no value:
+//   1. every move played and check_for_winner() read: a win at once ends the node (nothing ranks above +1); the moves after which
+//      nobody has won are the `quiet` ones;
+//   2. the quiet moves searched r - 1 plies deep, or as deep as solve_plies_needed() says once one of them wins.
+template <int MAXR>
+__device__ __forceinline__ int solve_value(const Planes &p, int s, int r)
+{
+    uint64_t quiet = 0;
+    uint32_t best = 0;
+    for (uint64_t l = legal54(p, s); l; l &= l - 1) {
+        const uint32_t a = (uint32_t)__builtin_ctzll(l);
+        Planes q = p;
+        move_planes(q, s, a);
+        const int c = solve_now(winner_of(q), s);
+        if (c > 0) return 1;
+        if (c < 0) best = solve_key(-1);
+        else quiet |= 1ull << a;
+    }
+    if (!quiet) return solve_of_key(best);
+    if (r <= 1) return 0;  // (a quiet move is unproven, which outranks every loss)
+    if constexpr (MAXR > 1) {
+        for (uint64_t l = quiet; l; l &= l - 1) {
+            Planes q = p;
+            move_planes(q, s, (uint32_t)__builtin_ctzll(l));
+            const int left = solve_plies_needed(best, r - 1);
+            if (left == 0) break;
+            const uint32_t k = solve_key(solve_parent(solve_value<MAXR - 1>(q, s ^ 1, left)));
+            best = k > best ? k : best;
+        }
+        return solve_of_key(best);
+    } else {
+        return 0;  // (r <= MAXR: not reached)
+    }
+}
+
+// The root's first two plies, which the kernel's lanes share and the host flavour walks in the same order.  Root action a of
+// `mover`, `depth` plies in all: c is final unless `deep` is non-empty.  Then nobody has won after a, no reply wins at once, and
+// `deep` holds the quiet replies, each worth solve_reply(); key is the best of the replies that lose at once (0: none).  When
+// every deep reply's key has been folded into key by max, c(a) = solve_parent(solve_of_key(key)).
+struct SolveRoot {
+    int c;
+    uint32_t key;
+    uint64_t deep;
+};
+
+__device__ __forceinline__ SolveRoot solve_root_action(const Planes &root, int mover, uint32_t a, int depth)
+{
+    Planes q = root;
+    move_planes(q, mover, a);
+    SolveRoot R{solve_now(winner_of(q), mover), 0u, 0ull};
+    if (R.c != 0 || depth == 1) return R;
+    const int other = mover ^ 1;
+    for (uint64_t l = legal54(q, other); l; l &= l - 1) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(l);
+        Planes t = q;
+        move_planes(t, other, b);
+        const int cb = solve_now(winner_of(t), other);
+        if (cb > 0) {  // the reply wins at once: a loses in two
+            R.c = -2;
+            R.deep = 0;
+            return R;
+        }
+        if (cb < 0) R.key = solve_key(-1);
+        else R.deep |= 1ull << b;
+    }
+    if (depth == 2 && R.deep) {  // the quiet replies are unproven
+        R.key = solve_key(0);
+        R.deep = 0;
+    }
+    if (!R.deep) R.c = solve_parent(solve_of_key(R.key));
+    return R;
+}
+
+// the order key of the quiet reply b to root action a (depth >= 3): the lane's serial part, depth - 2 plies from the root's mover.
+// `best` is the action's key so far (the max over its replies done): solve_plies_needed() cuts by it as inside solve_value, and a
+// reply that needs no ply returns 0, which changes no max.  An OLDER (smaller) best than the action has by now only costs work:
+// the cut is exact for every best the action has held.
+__device__ __forceinline__ uint32_t solve_reply(const Planes &root, int mover, uint32_t a, uint32_t b, int depth, uint32_t best)
+{
+    const int left = solve_plies_needed(best, depth - 2);
+    if (left == 0) return 0u;
+    Planes q = root;
+    move_planes(q, mover, a);
+    move_planes(q, mover ^ 1, b);
+    return solve_key(solve_parent(solve_value<kSolveMaxDepth - 2>(q, mover, left)));
+}
+
+// the decision over the root's 54 results: the key of candidate a with result c (0 stands for a non-candidate), the max decides
+__device__ __forceinline__ uint32_t solve_action_key(int c, uint32_t a) { return (solve_key(c) << 6) | (63u - a); }
+__device__ __forceinline__ int solve_action_of(uint32_t best) { return best ? 63 - (int)(best & 63u) : -1; }
+__device__ __forceinline__ int solve_value_of(uint32_t best) { return solve_of_key(best >> 6); }
+
 // ---- argument checks of the search entry points and the trajectory strides: host code, for both flavours of the ABI ----------
 // Each *_error returns the message of the first rule the arguments break, or nullptr; a flavour passes it to its own fail().
 inline const char *tree_budget_error(int iterations, int playouts)
@@ -2305,6 +2429,21 @@ inline const char *collect_eval_error(int illegal_mode, int policy0, int policy1
         if (const char *why = tree_eval_budget_error(its[m], explore)) return why;
     }
     return selfplay_window_error(sample_plies, has_turn, ply0, plies, env_base, n);
+}
+
+// gbl_solve: every check, in the order both flavours report them.  Returns the message (nullptr: none) and, in `code`, which error
+// it is (0 = GBL_ERR_ARG, 1 = GBL_ERR_ALIGN).  n == 0 passes whatever the pointers are: the caller returns GBL_OK before using them.
+inline const char *solve_error(int depth, int64_t n, const void *state, const void *to_move, const void *action_out, int &code)
+{
+    code = 0;
+    if (n < 0) return "n < 0";
+    if (depth < 1 || depth > kSolveMaxDepth) return "depth must be in [1, 6]";
+    if (n == 0) return nullptr;
+    if (!state) return "state must not be NULL";
+    if (!to_move) return "to_move must not be NULL";
+    code = 1;
+    if (reinterpret_cast<uintptr_t>(action_out) & 3u) return "action_out must be 4-byte aligned";
+    return nullptr;
 }
 
 // The (ply, tile) cells of 64 boards of a trajectory must start 16-byte aligned and must not overlap.

@@ -2351,6 +2351,71 @@ __global__ __launch_bounds__(64) void k_outcome_targets(const int8_t *__restrict
     }
 }
 
+// gbl_solve: the exact solver, one wavefront per board (a grid-stride loop over boards), three phases per board:
+//   1. lane a < 54 plays root action a and, unless that decides it, every reply once (solve_root_action): depths 1 and 2 end here,
+//      and so does every action with a reply that wins at once.  What is left of an action are its QUIET replies;
+//   2. the (root action, quiet reply) pairs of the whole board are laid back to back -- an exclusive scan of the lanes' counts --
+//      and dealt to the 64 lanes, each of which searches its pair's remaining depth - 2 plies serially in registers
+//      (solve_reply) and folds the result into the action's order key with an LDS max;
+//   3. lane a reads its action's key, the 54 result bytes go out one per lane, and a butterfly max decides.
+// DEAL picks how phase 2 hands the pairs out: 0 = lane l takes pairs l, l + 64, ...; 1 = a lane takes the next pair off a counter
+// in LDS whenever it is free.  Either way a lane's pairs come in ascending order, so the action of a pair is found by walking a
+// cursor over the scan.
+template <int DEAL>
+__global__ __launch_bounds__(64) void k_solve(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                              const int8_t *__restrict__ mask, int8_t *__restrict__ outcome_out,
+                                              int8_t *__restrict__ value_out, int32_t *__restrict__ action_out, int64_t n, int depth)
+{
+    __shared__ uint64_t s_deep[kActions];
+    __shared__ uint32_t s_start[kActions + 1], s_key[kActions], s_next;
+    const uint32_t lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        const Planes root = board_planes(state, b, lane);
+        const int mover = to_move[b] != 0;
+        const uint64_t cand = board_candidates(root, mover, mask, b, lane);
+        const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
+        SolveRoot A{kSolveNone, 0u, 0ull};
+        if (mine) A = solve_root_action(root, mover, lane, depth);
+        uint32_t total = 0;
+        if (depth > 2) {  // (wave-uniform)
+            uint32_t upto = (uint32_t)__popcll(A.deep);  // inclusive scan of the pairs per action
+#pragma unroll
+            for (uint32_t o = 1; o < 64u; o <<= 1) {
+                const uint32_t below = (uint32_t)__shfl_up((int)upto, o);
+                upto += lane >= o ? below : 0u;
+            }
+            total = (uint32_t)__shfl((int)upto, 63);
+            if (lane < (uint32_t)kActions) {
+                s_deep[lane] = A.deep;
+                s_key[lane] = A.key;
+                s_start[lane + 1] = upto;
+            }
+            if (lane == 0) {
+                s_start[0] = 0u;
+                s_next = 0u;
+            }
+            __syncthreads();
+            uint32_t a = 0;
+            for (uint32_t i = DEAL ? atomicAdd(&s_next, 1u) : lane; i < total; i = DEAL ? atomicAdd(&s_next, 1u) : i + 64u) {
+                while (s_start[a + 1] <= i) ++a;  // (s_start[54] = total > i: a stays below 54)
+                // s_key[a] is read plainly while other lanes atomicMax it: a stale value is one the action held earlier, which
+                // cuts less and gives the same key (solve_reply) -- it costs work, never the result
+                const uint32_t rb = kth_bit64(s_deep[a], i - s_start[a]);
+                atomicMax(&s_key[a], solve_reply(root, mover, a, rb, depth, s_key[a]));
+            }
+            __syncthreads();
+            if (A.deep) A.c = solve_parent(solve_of_key(s_key[lane]));
+        }
+        if (outcome_out && lane < (uint32_t)kActions) outcome_out[b * kActions + lane] = (int8_t)A.c;
+        const uint32_t best = wave_max(mine ? solve_action_key(A.c, lane) : 0u);
+        if (lane == 0) {
+            if (value_out) value_out[b] = (int8_t)solve_value_of(best);
+            if (action_out) action_out[b] = solve_action_of(best);
+        }
+        if (depth > 2) __syncthreads();  // (before the next board rewrites the LDS arrays)
+    }
+}
+
 // gbl_greedy: one decision per board.  Each lane owns a board (depth-1 walk, order-dependent replay,
 // fallback test), but the depth-2 evaluations -- one moved + legal54 + outcomes54 per (board,
 // candidate) pair, ~95 % of the work -- are pooled over the tile: the boards' candidate lists are
@@ -3761,6 +3826,18 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
     }
 #undef GBL_TREE
     GBL_LAUNCHED("gbl_tree_search");
+}
+
+int gbl_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, int depth, int8_t *outcome_out, int8_t *value_out,
+              int32_t *action_out, int64_t n, void *stream)
+{
+    int code = 0;
+    if (const char *why = solve_error(depth, n, state, to_move, action_out, code)) return fail(code ? GBL_ERR_ALIGN : GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    hipLaunchKernelGGL((k_solve<knob::kSolveDeal>), grid, dim3(64), 0, (hipStream_t)stream, state, to_move, mask, outcome_out, value_out,
+                       action_out, n, depth);
+    GBL_LAUNCHED("gbl_solve");
 }
 
 // gbl_evaluator as the kernels take it, after the checks both entry points share; 0, or the error

@@ -17,6 +17,7 @@ Tensors (attributes, all on ``device``)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -656,6 +657,23 @@ class BatchedGobblet:
                                                 f["z"].data_ptr(), f["plies_left"].data_ptr(), n, traj["_ply_stride"],
                                                 traj["_tile_stride"], traj["_plies"], self._stream()), "gbl_outcome_targets")
         return traj
+
+    def solve(self, depth: int = 4) -> dict:
+        """The exact ``depth``-ply verdict on the current boards, one launch of ``gbl_solve`` (include/gobblet_hip.h): "outcome" int8
+        (N, 54), the proven result of every legal action of the side to move (+k: wins at ply k, -k: has lost by ply k, 0: unproven,
+        ``nat.SOLVE_NONE`` = -128: not legal); "value" int8 (N,), the board's own result; "action" int32 (N,), the best action (the
+        shortest win, else the lowest unproven action, else the longest loss).  The boards are not touched."""
+        depth = int(depth)
+        if not 1 <= depth <= nat.SOLVE_MAX_DEPTH:
+            raise ValueError(f"solve: depth must be in [1, {nat.SOLVE_MAX_DEPTH}]")
+        n = self.num_envs
+        out = {"outcome": torch.empty((n, nat.ACTIONS), dtype=torch.int8, device=self.device),
+               "value": torch.empty(n, dtype=torch.int8, device=self.device),
+               "action": torch.empty(n, dtype=torch.int32, device=self.device)}
+        with torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext():  # (whichever device is current)
+            nat.check(self._lib.gbl_solve(self.squares.data_ptr(), self.to_move.data_ptr(), None, depth, out["outcome"].data_ptr(),
+                                          out["value"].data_ptr(), out["action"].data_ptr(), n, self._stream()), "gbl_solve")
+        return out
 
     def release_staging(self) -> None:
         """Drop the trajectory buffers ``collect()`` keeps for calls without ``out`` (their blocks go back to the driver

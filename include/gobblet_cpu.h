@@ -94,6 +94,8 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
 int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *mask, int iterations, int playouts, int max_plies,
                         int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
                         int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream);
+int gbl_cpu_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, int depth, int8_t *outcome_out, int8_t *value_out,
+                  int32_t *action_out, int64_t n, void *stream);
 int gbl_cpu_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, uint8_t *priors_out,
                      int32_t *value_out, int32_t *logits_out, int64_t n, void *stream);
 int gbl_cpu_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,

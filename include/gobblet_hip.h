@@ -402,6 +402,33 @@ int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_
                          int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
                          int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *stream);
 
+/* Exact bounded-depth solver (no counterpart in the reference): the full-width game tree of every board to `depth` plies, the proven
+ * result of every root action.  Integer-only and draws nothing: the kernel, the host flavour and a restatement of this text agree
+ * byte for byte.
+ *   Result of an action.  s = the side to move in a position, r >= 1 the plies left.  For a legal action a: play a, read
+ *     w = check_for_winner() (with the reference's last-line-decides rule where a move uncovers a line of the opponent).  Then
+ *       c(a) = +1  if w is s;          c(a) = -1  if w is the other side (a move that loses at once);
+ *       c(a) =  0  if w == 0 and r == 1;
+ *       otherwise, with u = V(position after a, other side, r - 1):  c(a) = 0 if u == 0, else -sign(u) * (|u| + 1).
+ *   Value of a position.  V(position, s, r) = 0 if s has no legal action; otherwise the c(a) of largest rank, where
+ *       rank(c) = 64 - c for c > 0,    rank(0) = 0,    rank(c) = -64 - c for c < 0:
+ *     the shortest forced win, then the unproven, then the longest forced loss.  +k reads "the mover wins at ply k against every
+ *     defence", -k "the mover has lost by ply k whatever they do", 0 "nothing is proven within r plies".
+ * The root's candidates are mask[b] & the legal mask of to_move[b] (mask NULL: the legal mask), as in gbl_playout_values; below the
+ * root the legal mask is used.  Outputs (each may be NULL):
+ *   outcome_out int8[n][54] : c(a) with r = depth for every candidate a, GBL_SOLVE_NONE for every other action
+ *   value_out   int8[n]     : the root's V; 0 without a candidate
+ *   action_out  int32[n]    : the candidate of largest rank, the lowest index on ties; -1 without a candidate
+ * An implementation may prune (a win in one ply ends a node; window cuts) only where every output byte stays that of the
+ * full-width definition above: the contract is the definition, not the traversal.
+ * 1 <= depth <= GBL_SOLVE_MAX_DEPTH; states must be contract states (gbl_validate).  state / to_move / mask are read a byte at a
+ * time and need NO alignment; action_out must be 4-byte aligned (GBL_ERR_ALIGN); to_move and mask count as set wherever they are
+ * non-zero.  n == 0 returns GBL_OK; n < 0 and null inputs GBL_ERR_ARG.  Allocates nothing. */
+#define GBL_SOLVE_MAX_DEPTH 6
+#define GBL_SOLVE_NONE (-128)
+int gbl_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, int depth, int8_t *outcome_out, int8_t *value_out,
+              int32_t *action_out, int64_t n, void *stream);
+
 /* Trajectory collection (K plies per launch with EVERY ply materialised).  `plies` masked-random
  * plies with auto-reset in ONE launch; ply t (t = 0 .. plies-1) of board b leaves in element
  *     cell(t, b) = t * ply_stride + (b / 64) * tile_stride + b % 64
