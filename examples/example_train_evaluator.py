@@ -3,7 +3,9 @@
 evaluator -> the evaluator-guided search against the playout search at equal iterations; with --generations G > 1 the loop goes
 round: generation k collects with generation k - 1's evaluator on both sides INSIDE one launch (gbl_collect_search_eval), fits a
 new network and plays it against the old one, one launch per colour:
-    python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G] [--generations G]"""
+    python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G] [--generations G]
+--augment square|all draws every Adam step's batch on the device under random board symmetries (BatchedGobblet.training_batch) and
+fits there; the default (none) keeps the whole window on the host as before."""
 import argparse
 import os
 import sys
@@ -73,6 +75,31 @@ def fit(obs, pi, z, hidden, steps, seed=0):
     return (l1.weight.detach().T, l1.bias.detach(), l2.weight.detach().T, l2.bias.detach()), hmax, float(loss.detach())
 
 
+def fit_augmented(env, traj, hidden, steps, augment, seed=0):
+    """fit() with every step's 1 024 rows drawn by env.training_batch(call=step) -- plies of finished games under random symmetries
+    ("square": the 8 of the square, "all": the 512) -- on the device the window lies on; nothing of the window crosses to the host."""
+    torch.manual_seed(seed)
+    dev = env.device
+    l1, l2 = torch.nn.Linear(117, hidden).to(dev), torch.nn.Linear(hidden, 55).to(dev)
+    opt = torch.optim.Adam(list(l1.parameters()) + list(l2.parameters()), lr=2e-3, weight_decay=1e-4)
+    loss, batch = torch.zeros(()), None
+    for step in range(steps):
+        batch = env.training_batch(traj, 1024, symmetries=augment, call=step, out=batch)
+        drawn = (batch["index"][:, 0] >= 0).float()  # (a sample that found no finished ply in its 16 attempts counts for nothing)
+        obs, visits, z = batch["observation"].float(), batch["visits"].float(), batch["z"].float() * drawn
+        pi = visits / visits.sum(-1, keepdim=True).clamp(min=1)
+        out = l2(torch.relu(l1(obs)))
+        per = -(pi * torch.log_softmax(out[:, :54], 1)).sum(1) + (out[:, 54].clamp(-1, 1) - z) ** 2 + 1e-2 * out[:, 54] ** 2
+        loss = (per * drawn).sum() / drawn.sum().clamp(min=1)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+    with torch.no_grad():
+        wide = env.training_batch(traj, 8192, symmetries=augment, call=steps)
+        hmax = float(torch.relu(l1(wide["observation"].float())).max())
+    return (l1.weight.detach().T, l1.bias.detach(), l2.weight.detach().T, l2.bias.detach()), hmax, float(loss.detach())
+
+
 def arena(first, second, n, device, seed=7, max_plies=64):
     """n games in lockstep, `first` as player_1 (finished games stay frozen): (player_1 wins, player_2 wins)."""
     env = G.BatchedGobblet(n, device, auto_reset=False, seed=seed)
@@ -84,7 +111,15 @@ def arena(first, second, n, device, seed=7, max_plies=64):
     return int((env.winner == 1).sum()), int((env.winner == -1).sum())
 
 
-def train_evaluator(device, boards=512, plies=48, steps=400, hidden=64, collect_iterations=64):
+def train_evaluator(device, boards=512, plies=48, steps=400, hidden=64, collect_iterations=64, augment="none"):
+    if augment != "none":
+        env = G.BatchedGobblet(boards, device, auto_reset=True, seed=0, track_turn=True)
+        traj = env.collect(plies, policies=("tree", "tree"), search=dict(iterations=collect_iterations, playouts=8, max_plies=64, explore=16,
+                                                                         sample_plies=4))
+        env.outcome_targets(traj)
+        weights, hmax, loss = fit_augmented(env, traj, hidden, steps, augment)
+        kept = int(((traj["z"][1:] != G._native.Z_OPEN) & (traj["done"][:-1] == 0) & (traj["visits"][1:].sum(-1, dtype=torch.int32) > 0)).sum())
+        return G.GobbletEvaluator.from_float(*weights, hidden_max=hmax, device=device), kept, loss
     obs, pi, z = collect_targets(device, boards, plies, collect_iterations)
     weights, hmax, loss = fit(obs, pi, z, hidden, steps)
     return G.GobbletEvaluator.from_float(*weights, hidden_max=hmax, device=device), len(obs), loss
@@ -111,8 +146,10 @@ if __name__ == "__main__":
     ap.add_argument("--games", type=int, default=128)
     ap.add_argument("--generations", type=int, default=1)
     ap.add_argument("--selfplay-iterations", type=int, default=64, help="iterations of the evaluator search in generations >= 2")
+    ap.add_argument("--augment", choices=("none", "square", "all"), default="none",
+                    help="draw every step's batch on the device under random board symmetries (generation 1)")
     a = ap.parse_args()
-    ev, samples, loss = train_evaluator(a.device, a.boards, a.plies, a.steps, a.hidden)
+    ev, samples, loss = train_evaluator(a.device, a.boards, a.plies, a.steps, a.hidden, augment=a.augment)
     print("trained on", samples, "plies; final loss", round(loss, 3), "; scales", ev.scales, "shifts", (ev.shift1, ev.shift_p, ev.shift_v))
     w, l, d = score(ev, a.device, a.iterations, a.games)
     print("evaluator search vs playout search at %d iterations: %d wins, %d losses, %d unfinished of %d games" % (a.iterations, w, l, d, w + l + d))

@@ -8,6 +8,7 @@
     TreeSearchGobbletPolicy  UCT tree search per board on the same playouts (root visit distribution and values)
     GobbletEvaluator  a small integer network (priors and value of a position) evaluated inside the kernels
     EvaluatorTreeSearchGobbletPolicy  the tree search with that network in place of the playouts
+    symmetry         the 512 board symmetries; BatchedGobblet.training_batch draws symmetry-augmented batches on the device
     SolverGobbletPolicy  the exact bounded-depth solver: proven wins and losses per action, optionally over another policy
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in
@@ -16,6 +17,7 @@ using it needs an MI355X.
 """
 from . import _native  # noqa: F401
 from . import gobblet_v1  # noqa: F401
+from . import symmetry  # noqa: F401
 from ._native import GobbletHipError, build  # noqa: F401
 from .board import BatchedBoard  # noqa: F401
 from .vector_env import BatchedGobblet  # noqa: F401
@@ -25,6 +27,7 @@ from .tree_policy import TreeSearchGobbletPolicy  # noqa: F401
 from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator  # noqa: F401
 from .solver_policy import SolverGobbletPolicy  # noqa: F401
 from .random_policy import RandomAdmissiblePolicy  # noqa: F401
+from .symmetry import N_SYMMETRIES  # noqa: F401
 from .sharding import make_shard, reduce_counters, shard_bounds  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1149,4 +1149,69 @@ int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, 
     return GBL_OK;
 }
 
+int gbl_cpu_symmetry_apply(const int16_t *sym, int sym_all, const int8_t *agent, const int8_t *state_in, int8_t *state_out,
+                           const int8_t *obs_in, int8_t *obs_out, const int8_t *mask_in, int8_t *mask_out, const int16_t *visits_in,
+                           int16_t *visits_out, const uint8_t *priors_in, uint8_t *priors_out, const int32_t *actions_in,
+                           int32_t *actions_out, int64_t n, void *)
+{
+    const SymRowsArg R{{state_in, obs_in, mask_in, visits_in, priors_in, actions_in},
+                       {state_out, obs_out, mask_out, visits_out, priors_out, actions_out}};
+    if (const char *why = symmetry_error(sym, sym_all, agent, R, n)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    parallel_for(n, [=](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) {
+            const Sym S = sym_of((uint32_t)(sym ? sym[b] : sym_all) & 511u);
+            const uint32_t m = agent && agent[b] != 0;
+            if (state_in) sym_state_row(state_in + b * kCells, state_out + b * kCells, S);
+            if (obs_in) sym_obs_row(obs_in + b * kObs, obs_out + b * kObs, S, m);
+            if (mask_in) sym_action_row(mask_in + b * kActions, mask_out + b * kActions, S, m);
+            if (visits_in) sym_action_row(visits_in + b * kActions, visits_out + b * kActions, S, m);
+            if (priors_in) sym_action_row(priors_in + b * kActions, priors_out + b * kActions, S, m);
+            if (actions_in) actions_out[b] = sym_action_any(S, m, actions_in[b]);
+        }
+    });
+    return GBL_OK;
+}
+
+int gbl_cpu_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                           const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                           int64_t tile_stride, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base, uint32_t call,
+                           int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out,
+                           void *)
+{
+    if (const char *why = batch_error(obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, n, plies, ply_stride, tile_stride,
+                                      batch, sym_mask, call, obs_out, mask_out, index_out))
+        return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    parallel_for(batch, [=](int64_t j0, int64_t j1) {
+        for (int64_t j = j0; j < j1; ++j) {
+            int64_t at = -1, prev = -1;
+            BatchDraw d{0u, 0u, 0};
+            for (uint32_t i = 0; i < (uint32_t)kBatchAttempts && at < 0; ++i) {
+                d = batch_draw(seed, sample_base + (uint64_t)j, call, i, plies, n);
+                const int64_t c = traj_cell(d.t, d.b, ply_stride, tile_stride), p = traj_cell((int64_t)d.t - 1, d.b, ply_stride, tile_stride);
+                if (batch_valid(z_traj, done_traj, visits_traj, c, p)) { at = c; prev = p; }
+            }
+            const bool ok = at >= 0;
+            const uint32_t code = ok ? d.sym & (uint32_t)sym_mask : 0u;
+            index_out[2 * j] = ok ? (int32_t)d.t : -1;
+            index_out[2 * j + 1] = ok ? (int32_t)d.b : -1;
+            if (z_out) z_out[j] = ok ? z_traj[at] : (int8_t)kZOpen;
+            if (sym_out) sym_out[j] = (int16_t)code;
+            if (!ok) {
+                if (obs_out) memset(obs_out + j * kObs, 0, kObs);
+                if (mask_out) memset(mask_out + j * kActions, 0, kActions);
+                if (visits_out) memset(visits_out + j * kActions, 0, 2 * kActions);
+                continue;
+            }
+            const Sym S = sym_of(code);
+            const uint32_t m = mover_traj[at] != 0;
+            if (obs_out) sym_obs_row(obs_traj + prev * kObs, obs_out + j * kObs, S, m);
+            if (mask_out) sym_action_row(mask_traj + prev * kActions, mask_out + j * kActions, S, m);
+            if (visits_out) sym_action_row(visits_traj + at * kActions, visits_out + j * kActions, S, m);
+        }
+    });
+    return GBL_OK;
+}
+
 }  // extern "C"

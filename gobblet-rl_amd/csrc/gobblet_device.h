@@ -2446,6 +2446,127 @@ inline const char *solve_error(int depth, int64_t n, const void *state, const vo
     return nullptr;
 }
 
+// ---- board symmetries (include/gobblet_hip.h, "Board symmetries"): gbl_symmetry_apply and gbl_training_batch ------------------------
+// One statement of the rule for the kernels and the host flavour.  Everything is in GATHER form -- "which input element lands in
+// output element k" -- so that a lane that owns a whole row runs it with constant k (the divisions fold away) and a wavefront that
+// fills a row cooperatively runs it with k = its lane.
+constexpr int kSymmetries = 512;         // GBL_SYMMETRIES
+constexpr int kBatchAttempts = 16;       // GBL_BATCH_ATTEMPTS
+constexpr uint32_t kStreamBatch = 5u;    // generator stream of gbl_training_batch's draws
+
+// sigma(p) from the header's (r, c) rule
+__device__ __forceinline__ uint32_t sym_sigma(uint32_t s, uint32_t p)
+{
+    uint32_t r = p / 3u, c = p % 3u;
+    c = (s & 4u) ? 2u - c : c;
+#pragma unroll
+    for (uint32_t i = 0; i < 3u; ++i) {
+        const bool turn = i < (s & 3u);
+        const uint32_t r2 = turn ? c : r, c2 = turn ? 2u - r : c;
+        r = r2; c = c2;
+    }
+    return 3u * r + c;
+}
+
+// A decoded symmetry: sigma and its inverse as nine nibbles each (nibble p = the image of p), and the six swap bits
+// (bit k: player_1's pair k, bit 3 + k: player_2's).
+struct Sym {
+    uint64_t fwd, inv;
+    uint32_t swaps;
+};
+
+__device__ __forceinline__ Sym sym_of(uint32_t s)
+{
+    Sym S{0ull, 0ull, (s >> 3) & 63u};
+#pragma unroll
+    for (uint32_t p = 0; p < 9u; ++p) {
+        const uint32_t q = sym_sigma(s, p);
+        S.fwd |= (uint64_t)q << (4u * p);
+        S.inv |= (uint64_t)p << (4u * q);
+    }
+    return S;
+}
+
+__device__ __forceinline__ uint32_t sym_pos(const Sym &S, uint32_t p) { return (uint32_t)(S.fwd >> (4u * p)) & 15u; }
+__device__ __forceinline__ uint32_t sym_pos_inv(const Sym &S, uint32_t p) { return (uint32_t)(S.inv >> (4u * p)) & 15u; }
+// tau_m on the piece INDEX i = piece - 1 in 0..5 (an involution: it is its own inverse)
+__device__ __forceinline__ uint32_t sym_piece(const Sym &S, uint32_t m, uint32_t i) { return i ^ ((S.swaps >> (3u * m + (i >> 1))) & 1u); }
+
+// A_m(a), a in [0, 54)
+__device__ __forceinline__ uint32_t sym_action(const Sym &S, uint32_t m, uint32_t a) { return 9u * sym_piece(S, m, a / 9u) + sym_pos(S, a % 9u); }
+// the action whose entry lands in entry k of an action-indexed row: A_m^-1(k)
+__device__ __forceinline__ uint32_t sym_action_src(const Sym &S, uint32_t m, uint32_t k) { return 9u * sym_piece(S, m, k / 9u) + sym_pos_inv(S, k % 9u); }
+// the observation byte that lands in byte k = 13 p + ch of agent m's observation row
+__device__ __forceinline__ uint32_t sym_obs_src(const Sym &S, uint32_t m, uint32_t k)
+{
+    const uint32_t p = k / 13u, ch = k % 13u;
+    const uint32_t from = ch < 6u ? sym_piece(S, m, ch) : ch < 12u ? 6u + sym_piece(S, m ^ 1u, ch - 6u) : 12u;
+    return 13u * sym_pos_inv(S, p) + from;
+}
+// the state cell that lands in cell k = 9 l + p, and what becomes of its value
+__device__ __forceinline__ uint32_t sym_state_src(const Sym &S, uint32_t k) { return 9u * (k / 9u) + sym_pos_inv(S, k % 9u); }
+__device__ __forceinline__ int8_t sym_value(const Sym &S, int8_t v)
+{
+    const int a = v < 0 ? -v : v;
+    if (a < 1 || a > 6) return v;
+    const int t = (int)sym_piece(S, v < 0 ? 1u : 0u, (uint32_t)(a - 1)) + 1;
+    return (int8_t)(v < 0 ? -t : t);
+}
+
+// Whole rows, for whoever owns one (a lane with its row in LDS; the host flavour with the row where it lives).  in != out.
+__device__ __forceinline__ void sym_state_row(const int8_t *in, int8_t *out, const Sym &S)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kCells; ++k) out[k] = sym_value(S, in[sym_state_src(S, k)]);
+}
+__device__ __forceinline__ void sym_obs_row(const int8_t *in, int8_t *out, const Sym &S, uint32_t m)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kObs; ++k) out[k] = in[sym_obs_src(S, m, k)];
+}
+template <typename T>
+__device__ __forceinline__ void sym_action_row(const T *in, T *out, const Sym &S, uint32_t m)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kActions; ++k) out[k] = in[sym_action_src(S, m, k)];
+}
+__device__ __forceinline__ int32_t sym_action_any(const Sym &S, uint32_t m, int32_t a)
+{
+    return a >= 0 && a < kActions ? (int32_t)sym_action(S, m, (uint32_t)a) : a;
+}
+
+// gbl_training_batch: element (t, b) of a trajectory array, and attempt i of sample `id` (the header's draw rule)
+__device__ __forceinline__ int64_t traj_cell(int64_t t, int64_t b, int64_t ply_stride, int64_t tile_stride)
+{
+    return t * ply_stride + (b >> 6) * tile_stride + (b & 63);
+}
+struct BatchDraw {
+    uint32_t t, sym;
+    int64_t b;
+};
+__device__ __forceinline__ BatchDraw batch_draw(uint64_t seed, uint64_t id, uint32_t call, uint32_t i, uint32_t plies, int64_t n)
+{
+    const Draw4 d = draw_block(seed, id, 4u * ((uint32_t)kBatchAttempts * call + i), kStreamBatch);
+    return BatchDraw{1u + __umulhi(d.w[0], plies - 1u), d.w[2], (int64_t)(((uint64_t)d.w[1] * (uint64_t)n) >> 32)};
+}
+// is cell `at` = (t, b), whose predecessor (t - 1, b) is `prev`, a training sample?  (visits rows: 4-byte aligned on the device)
+__device__ __forceinline__ bool batch_valid(const int8_t *z, const int8_t *done, const int16_t *visits, int64_t at, int64_t prev)
+{
+    if (z[at] == (int8_t)kZOpen || done[prev] != 0) return false;
+    int sum = 0;
+#ifndef GBL_HOST_EMU
+    const uint32_t *v = reinterpret_cast<const uint32_t *>(visits + at * kActions);
+#pragma unroll
+    for (int k = 0; k < kActions / 2; ++k) {
+        const uint32_t d = v[k];
+        sum += (int)(int16_t)(d & 0xFFFFu) + (int)(int16_t)(d >> 16);
+    }
+#else
+    for (int k = 0; k < kActions; ++k) sum += visits[at * kActions + k];
+#endif
+    return sum > 0;
+}
+
 // The (ply, tile) cells of 64 boards of a trajectory must start 16-byte aligned and must not overlap.
 inline bool strides_ok(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
 {
@@ -2456,5 +2577,57 @@ inline bool strides_ok(int64_t n, uint32_t plies, int64_t ply_stride, int64_t ti
     return aligned && (time_major || tile_major);
 }
 constexpr const char *kStridesMessage = "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart";
+
+// Argument checks of gbl_symmetry_apply, shared by both flavours (the device entry adds its alignment rules).  ok_zero: n == 0.
+struct SymRowsArg {
+    const void *in[6];  // state, obs, mask, visits, priors, actions
+    void *out[6];
+};
+inline const char *symmetry_error(const void *sym, int sym_all, const void *agent, const SymRowsArg &R, int64_t n)
+{
+    static const char *const pair_msg[6] = {"state_in and state_out go together", "obs_in and obs_out go together",
+                                            "mask_in and mask_out go together", "visits_in and visits_out go together",
+                                            "priors_in and priors_out go together", "actions_in and actions_out go together"};
+    static const char *const same_msg[6] = {"state_out must not be state_in: the transform is not in-place safe",
+                                            "obs_out must not be obs_in: the transform is not in-place safe",
+                                            "mask_out must not be mask_in: the transform is not in-place safe",
+                                            "visits_out must not be visits_in: the transform is not in-place safe",
+                                            "priors_out must not be priors_in: the transform is not in-place safe",
+                                            "actions_out must not be actions_in: the transform is not in-place safe"};
+    if (n < 0) return "n < 0";
+    if (!sym && (sym_all < 0 || sym_all >= kSymmetries)) return "sym_all must be in [0, 512)";
+    if (n == 0) return nullptr;
+    bool needs_agent = false;
+    for (int i = 0; i < 6; ++i) {
+        if (!R.in[i] != !R.out[i]) return pair_msg[i];
+        if (R.in[i] && R.in[i] == R.out[i]) return same_msg[i];
+        needs_agent |= i > 0 && R.in[i];
+    }
+    if (needs_agent && !agent) return "agent must not be NULL when obs, an action-indexed row or actions are given";
+    return nullptr;
+}
+
+// ... and of gbl_training_batch.
+inline const char *batch_error(const void *obs_traj, const void *mask_traj, const void *visits_traj, const void *z_traj,
+                               const void *done_traj, const void *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                               int64_t tile_stride, int64_t batch, int sym_mask, uint32_t call, const void *obs_out,
+                               const void *mask_out, const void *index_out)
+{
+    if (plies < 2u || plies > 32767u) return "plies must be in [2, 32767]";
+    if (batch < 0 || batch > ((int64_t)1 << 31)) return "batch must be in [0, 2^31]";
+    if (sym_mask < 0 || sym_mask >= kSymmetries) return "sym_mask must be in [0, 511]";
+    if (call >= (1u << 26)) return "call must be below 2^26";
+    if (batch == 0) return nullptr;
+    if (n < 1 || n > ((int64_t)1 << 31)) return "n must be in [1, 2^31]";
+    if (!visits_traj) return "visits_traj must not be NULL";
+    if (!z_traj) return "z_traj must not be NULL";
+    if (!done_traj) return "done_traj must not be NULL";
+    if (!mover_traj) return "mover_traj must not be NULL";
+    if (!index_out) return "index_out must not be NULL";
+    if (obs_out && !obs_traj) return "obs_out needs obs_traj";
+    if (mask_out && !mask_traj) return "mask_out needs mask_traj";
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return kStridesMessage;
+    return nullptr;
+}
 
 }  // namespace gbl

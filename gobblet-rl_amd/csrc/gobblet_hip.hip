@@ -2351,6 +2351,143 @@ __global__ __launch_bounds__(64) void k_outcome_targets(const int8_t *__restrict
     }
 }
 
+// gbl_symmetry_apply: a tile of 64 boards per wavefront, one row type after the other over the LDS-image path -- the tile's rows in
+// as 16-byte vectors, lane l permutes ITS row from the one image into the other (constant indices: the rule's divisions fold away,
+// what is left per byte is a nibble of sigma^-1 and an LDS byte each way), the tile out as 16-byte vectors.
+struct SymRows {
+    const int8_t *state_in, *obs_in, *mask_in;
+    const int16_t *visits_in;
+    const uint8_t *priors_in;
+    const int32_t *actions_in;
+    int8_t *state_out, *obs_out, *mask_out;
+    int16_t *visits_out;
+    uint8_t *priors_out;
+    int32_t *actions_out;
+};
+
+// one row type of the tile: `row(in, out)` moves the lane's ROWB bytes
+template <int ROWB, typename Row>
+__device__ __forceinline__ void sym_tile(const void *in, void *out, uint32_t *s_in, uint32_t *s_out, const Lane &L, Row row)
+{
+    tile_in<ROWB>(static_cast<const int8_t *>(in) + L.tile * (kTile * ROWB), s_in, L.lane, L.rows);
+    wave_lds_fence();
+    row(reinterpret_cast<const int8_t *>(s_in) + L.lane * ROWB, reinterpret_cast<int8_t *>(s_out) + L.lane * ROWB);
+    wave_lds_fence();
+    tile_out<ROWB, kStoreStream>(static_cast<int8_t *>(out) + L.tile * (kTile * ROWB), s_out, L.lane, L.rows);
+    wave_lds_fence();  // (the images are reused by the next row type)
+}
+
+__global__ __launch_bounds__(64) void k_symmetry_apply(const int16_t *__restrict__ sym, int sym_all, const int8_t *__restrict__ agent,
+                                                       SymRows R, int64_t n, int64_t ntiles)
+{
+    __shared__ uint32_t s_in[image_words<kObs>()];
+    __shared__ uint32_t s_out[image_words<kObs>()];
+    Lane L;
+    if (!lane_setup(L, n, ntiles)) return;
+    // (lanes past the end of a ragged last tile permute whatever the image holds with the identity: nothing of theirs is stored)
+    const Sym S = sym_of((uint32_t)(sym ? (L.valid ? (int)sym[L.b] : 0) : sym_all) & 511u);
+    const uint32_t m = agent && L.valid ? agent[L.b] != 0 : 0u;
+    if (R.state_in) sym_tile<kCells>(R.state_in, R.state_out, s_in, s_out, L, [&](const int8_t *i, int8_t *o) { sym_state_row(i, o, S); });
+    if (R.obs_in) sym_tile<kObs>(R.obs_in, R.obs_out, s_in, s_out, L, [&](const int8_t *i, int8_t *o) { sym_obs_row(i, o, S, m); });
+    if (R.mask_in) sym_tile<kActions>(R.mask_in, R.mask_out, s_in, s_out, L, [&](const int8_t *i, int8_t *o) { sym_action_row(i, o, S, m); });
+    if (R.priors_in) sym_tile<kActions>(R.priors_in, R.priors_out, s_in, s_out, L, [&](const int8_t *i, int8_t *o) { sym_action_row(i, o, S, m); });
+    if (R.visits_in)
+        sym_tile<2 * kActions>(R.visits_in, R.visits_out, s_in, s_out, L, [&](const int8_t *i, int8_t *o) {
+            sym_action_row(reinterpret_cast<const int16_t *>(i), reinterpret_cast<int16_t *>(o), S, m);
+        });
+    if (R.actions_in && L.valid) R.actions_out[L.b] = sym_action_any(S, m, R.actions_in[L.b]);
+}
+
+// gbl_training_batch: 64 samples per wavefront.
+//   1. Lane l draws sample l: up to 16 attempts of one generator block, two byte loads and the 27 dwords of the visits row each
+//      (the loop ends when every lane has its cell), then writes the sample's scalars and leaves its source cells, sigma^-1 and
+//      swap bits in LDS.
+//   2. Row type after row type, the 64 output rows are gathered into ONE LDS image, permuted on the way in: the wavefront walks
+//      the samples, lane k fetching the source element of output element k (and k + 64 of an observation row) of sample r -- k is the
+//      lane's own, so its cell and channel are computed once, and per sample what is left is a nibble of sigma^-1 and a swap bit.
+//      A row's 117 / 54 / 108 source bytes lie in one or two 128-byte lines; four samples' loads are in flight at a time.
+//   3. The image -- a contiguous tile of the output -- leaves as whole 16-byte vectors (tile_out, ragged last tile as elsewhere).
+struct BatchArgs {
+    const int8_t *obs, *mask;
+    const int16_t *visits;
+    const int8_t *z, *done, *mover;
+    int8_t *obs_out, *mask_out;
+    int16_t *visits_out;
+    int8_t *z_out;
+    int32_t *index_out;
+    int16_t *sym_out;
+    int64_t n, ply_stride, tile_stride, batch, ntiles;
+    uint64_t seed, sample_base;
+    uint32_t plies, call, sym_mask;
+};
+
+// rows `ROWS` of element type T and E elements: element k of sample r from src[cell_r * E + from(r, k)], zeros for a failed sample
+template <typename T, int E, typename From>
+__device__ __forceinline__ void batch_gather(const T *__restrict__ src, T *img, const int64_t *s_cell, int rows, uint32_t k, From from)
+{
+    if (k >= (uint32_t)E) return;
+#pragma unroll 4
+    for (int r = 0; r < rows; ++r) {
+        const int64_t c = s_cell[r];
+        const T v = src[(c >= 0 ? c : 0) * E + from(r, k)];  // (a failed sample reads cell 0 and drops it: no branch around the load)
+        img[r * E + (int)k] = c >= 0 ? v : (T)0;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_training_batch(BatchArgs A)
+{
+    __shared__ uint32_t s_img[image_words<kObs>()];
+    __shared__ int64_t s_at[kTile], s_prev[kTile];
+    __shared__ uint64_t s_inv[kTile];
+    __shared__ uint32_t s_sw[kTile];  // swap bits | mover << 6
+    Lane L;
+    if (!lane_setup(L, A.batch, A.ntiles)) return;
+    int64_t at = -1, prev = -1;
+    BatchDraw d{0u, 0u, 0};
+    if (L.valid) {
+        for (uint32_t i = 0; i < (uint32_t)kBatchAttempts && at < 0; ++i) {
+            d = batch_draw(A.seed, A.sample_base + (uint64_t)L.b, A.call, i, A.plies, A.n);
+            const int64_t c = traj_cell(d.t, d.b, A.ply_stride, A.tile_stride), p = c - A.ply_stride;
+            if (batch_valid(A.z, A.done, A.visits, c, p)) { at = c; prev = p; }
+        }
+    }
+    const bool ok = at >= 0;
+    const uint32_t code = ok ? d.sym & A.sym_mask : 0u;
+    const Sym S = sym_of(code);
+    const uint32_t m = ok ? A.mover[at] != 0 : 0u;
+    if (L.valid) {
+        A.index_out[2 * L.b] = ok ? (int32_t)d.t : -1;  // (two dword stores: index_out is only 4-byte aligned)
+        A.index_out[2 * L.b + 1] = ok ? (int32_t)d.b : -1;
+        if (A.z_out) A.z_out[L.b] = ok ? A.z[at] : (int8_t)kZOpen;
+        if (A.sym_out) A.sym_out[L.b] = (int16_t)code;
+    }
+    s_at[L.lane] = at; s_prev[L.lane] = prev; s_inv[L.lane] = S.inv; s_sw[L.lane] = S.swaps | (m << 6);
+    wave_lds_fence();
+    const uint32_t k = (uint32_t)L.lane;
+    const auto sym_r = [&](int r) { return Sym{0ull, s_inv[r], s_sw[r] & 63u}; };
+    if (A.obs_out) {
+        int8_t *img = reinterpret_cast<int8_t *>(s_img);
+        const auto from = [&](int r, uint32_t e) { return sym_obs_src(sym_r(r), s_sw[r] >> 6, e); };
+        batch_gather<int8_t, kObs>(A.obs, img, s_prev, L.rows, k, from);
+        batch_gather<int8_t, kObs>(A.obs, img, s_prev, L.rows, k + 64u, from);
+        wave_lds_fence();
+        tile_out<kObs, kStoreStream>(A.obs_out + L.tile * (kTile * kObs), s_img, L.lane, L.rows);
+        wave_lds_fence();
+    }
+    const auto from = [&](int r, uint32_t e) { return sym_action_src(sym_r(r), s_sw[r] >> 6, e); };
+    if (A.mask_out) {
+        batch_gather<int8_t, kActions>(A.mask, reinterpret_cast<int8_t *>(s_img), s_prev, L.rows, k, from);
+        wave_lds_fence();
+        tile_out<kActions, kStoreStream>(A.mask_out + L.tile * (kTile * kActions), s_img, L.lane, L.rows);
+        wave_lds_fence();
+    }
+    if (A.visits_out) {
+        batch_gather<int16_t, kActions>(A.visits, reinterpret_cast<int16_t *>(s_img), s_at, L.rows, k, from);
+        wave_lds_fence();
+        tile_out<2 * kActions, kStoreStream>(reinterpret_cast<int8_t *>(A.visits_out) + L.tile * (kTile * 2 * kActions), s_img, L.lane, L.rows);
+    }
+}
+
 // gbl_solve: the exact solver, one wavefront per board (a grid-stride loop over boards), three phases per board:
 //   1. lane a < 54 plays root action a and, unless that decides it, every reply once (solve_root_action): depths 1 and 2 end here,
 //      and so does every action with a reply that wins at once.  What is left of an action are its QUIET replies;
@@ -3979,6 +4116,49 @@ int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, cons
     hipLaunchKernelGGL(k_outcome_targets, dim3((uint32_t)std::min<int64_t>(ntiles, 1 << 20)), dim3(64), 0, (hipStream_t)stream, done_traj,
                        reward_traj, mover_traj, z_traj, plies_left_traj, n, ntiles, ply_stride, tile_stride, plies);
     GBL_LAUNCHED("gbl_outcome_targets");
+}
+
+int gbl_symmetry_apply(const int16_t *sym, int sym_all, const int8_t *agent, const int8_t *state_in, int8_t *state_out,
+                       const int8_t *obs_in, int8_t *obs_out, const int8_t *mask_in, int8_t *mask_out, const int16_t *visits_in,
+                       int16_t *visits_out, const uint8_t *priors_in, uint8_t *priors_out, const int32_t *actions_in,
+                       int32_t *actions_out, int64_t n, void *stream)
+{
+    const SymRowsArg Q{{state_in, obs_in, mask_in, visits_in, priors_in, actions_in},
+                       {state_out, obs_out, mask_out, visits_out, priors_out, actions_out}};
+    if (const char *why = symmetry_error(sym, sym_all, agent, Q, n)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_ALIGNED(state_in, "state_in"); GBL_ALIGNED(state_out, "state_out"); GBL_ALIGNED(obs_in, "obs_in"); GBL_ALIGNED(obs_out, "obs_out");
+    GBL_ALIGNED(mask_in, "mask_in"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_in, "visits_in");
+    GBL_ALIGNED(visits_out, "visits_out"); GBL_ALIGNED(priors_in, "priors_in"); GBL_ALIGNED(priors_out, "priors_out");
+    if ((reinterpret_cast<uintptr_t>(actions_in) | reinterpret_cast<uintptr_t>(actions_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "actions_in / actions_out must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sym) & 1u) return fail(GBL_ERR_ALIGN, "sym must be 2-byte aligned");
+    const Geometry g = geometry(n);
+    const SymRows R{state_in,  obs_in,  mask_in,  visits_in,  priors_in, actions_in,
+                    state_out, obs_out, mask_out, visits_out, priors_out, actions_out};
+    hipLaunchKernelGGL(k_symmetry_apply, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, sym, sym_all, agent, R, n, g.ntiles);
+    GBL_LAUNCHED("gbl_symmetry_apply");
+}
+
+int gbl_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                       const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                       int64_t tile_stride, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base, uint32_t call,
+                       int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out,
+                       void *stream)
+{
+    if (const char *why = batch_error(obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, n, plies, ply_stride, tile_stride,
+                                      batch, sym_mask, call, obs_out, mask_out, index_out))
+        return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    GBL_ALIGNED(obs_out, "obs_out"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_out, "visits_out");
+    if ((reinterpret_cast<uintptr_t>(visits_traj) | reinterpret_cast<uintptr_t>(index_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "visits_traj / index_out must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sym_out) & 1u) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
+    const Geometry g = geometry(batch);
+    const BatchArgs A{obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, obs_out, mask_out, visits_out, z_out, index_out, sym_out,
+                      n, ply_stride, tile_stride, batch, g.ntiles, seed, sample_base, plies, call, (uint32_t)sym_mask};
+    hipLaunchKernelGGL(k_training_batch, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_training_batch");
 }
 
 }  // extern "C"

@@ -675,6 +675,51 @@ class BatchedGobblet:
                                           out["value"].data_ptr(), out["action"].data_ptr(), n, self._stream()), "gbl_solve")
         return out
 
+    SYMMETRY_MASKS = {None: 0, "none": 0, "square": 7, "all": nat.SYMMETRIES - 1}
+
+    def training_batch(self, traj: dict, batch: int, symmetries="all", call: int = 0, seed=None, out: dict | None = None) -> dict:
+        """``batch`` training samples drawn on the device from a collected window with search outputs and outcome targets
+        (``collect(..., policies=(... "tree" / "evaluator" ...))`` + ``outcome_targets``), each under a random symmetry, one launch of
+        ``gbl_training_batch`` (include/gobblet_hip.h): "observation" int8 (batch, 117) -- what the mover of the drawn ply saw --,
+        "action_mask" int8 (batch, 54), "visits" int16 (batch, 54), "z" int8 (batch,), "index" int32 (batch, 2) = (ply, board) and
+        "sym" int16 (batch,).  A sample is a ply of a finished game whose search visited something (the plies
+        ``examples/example_train_evaluator.py`` keeps); ``symmetries``: "all" (the 512), "square" (the 8 of the square) or None.
+        The draws are keyed by (``seed`` -- the environment's by default --, sample index, ``call``): pass the step number as ``call``
+        for a fresh batch per step.  A sample that finds no such ply in 16 attempts (a window with hardly any) has index (-1, -1),
+        zero rows and z = ``nat.Z_OPEN``.  ``out``: a dict from an earlier call to write into."""
+        if symmetries not in self.SYMMETRY_MASKS:
+            raise ValueError("symmetries: 'all', 'square' or None")
+        f, batch, call = traj["_full"], int(batch), int(call)
+        if "z" not in f:
+            raise ValueError("training_batch needs the 'z' entry: call outcome_targets(traj) first")
+        if "visits" not in f or "mover" not in f:
+            raise ValueError("training_batch needs a window with search outputs ('visits', 'mover')")
+        if f["z"].device != self.device:
+            raise ValueError("the window lives on %s and the environment on %s" % (f["z"].device, self.device))
+        if batch < 0 or not 0 <= call < 1 << 26:
+            raise ValueError("training_batch: batch >= 0 and 0 <= call < 2^26")
+        if traj["_plies"] < 2:
+            raise ValueError("training_batch needs a window of at least 2 plies")
+        dev = self.device
+        spec = {"observation": ((batch, nat.OBS_BYTES), torch.int8), "action_mask": ((batch, nat.ACTIONS), torch.int8),
+                "visits": ((batch, nat.ACTIONS), torch.int16), "z": ((batch,), torch.int8), "index": ((batch, 2), torch.int32),
+                "sym": ((batch,), torch.int16)}
+        if "observation" not in f:
+            del spec["observation"]
+        if out is None:
+            out = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (shape, dtype) in spec.items()}
+        elif set(out) != set(spec) or any(tuple(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != dev
+                                          or not out[k].is_contiguous() for k, (shape, dtype) in spec.items()):
+            raise ValueError("out: the dict of an earlier training_batch call of this batch size on this window's device")
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():  # (whichever device is current)
+            nat.check(self._lib.gbl_training_batch(
+                nat.ptr(f.get("observation")), f["action_mask"].data_ptr(), f["visits"].data_ptr(), f["z"].data_ptr(),
+                f["done"].data_ptr(), f["mover"].data_ptr(), self.num_envs, traj["_plies"], traj["_ply_stride"], traj["_tile_stride"],
+                batch, self.SYMMETRY_MASKS[symmetries], self.seed if seed is None else int(seed), 0, call,
+                nat.ptr(out.get("observation")), out["action_mask"].data_ptr(), out["visits"].data_ptr(), out["z"].data_ptr(),
+                out["index"].data_ptr(), out["sym"].data_ptr(), self._stream()), "gbl_training_batch")
+        return out
+
     def release_staging(self) -> None:
         """Drop the trajectory buffers ``collect()`` keeps for calls without ``out`` (their blocks go back to the driver
         once the last tensor over them is gone; blocks parked during a graph capture are freed here too)."""

@@ -576,6 +576,66 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
 int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
                         int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *stream);
 
+/* Board symmetries (no counterpart in the reference: the augmentation step of an AlphaZero-style trainer).  A symmetry is an integer
+ * s in [0, GBL_SYMMETRIES): one of the 8 symmetries of the square acting on the 9 positions, times the exchange of the two equal-sized
+ * pieces of a colour (piece numbers 2k+1 <-> 2k+2), three independent swaps per colour: 8 x 8 x 8 = 512 elements.
+ *   Position map sigma.  Bits 0-1 = rot, bit 2 = flip.  For the cell (r, c) of position p = 3 r + c: if flip, c <- 2 - c; then rot
+ *     times (r, c) <- (c, 2 - r).  sigma(p) = 3 r + c of the result: the position a piece on p moves to.
+ *   Piece swaps.  Bit 3 + k (k = 0, 1, 2) swaps player_1's pieces 2k+1 <-> 2k+2, bit 6 + k those of player_2.  tau_m is the resulting
+ *     map on agent m's piece numbers 1..6 (m = 0: player_1).
+ *   State row (27 B).  out[9 l + sigma(p)] = sign(v) * tau_m(|v|) for v = in[9 l + p] with |v| in 1..6, m the owner (v > 0: player_1);
+ *     every other byte value (0, and what no contract state holds) is moved unchanged.
+ *   An action of agent m.  a = 9 (piece - 1) + p  |->  A_m(a) = 9 (tau_m(piece) - 1) + sigma(p); actions outside [0, 54) pass unchanged.
+ *   Action-indexed rows (mask int8[54], visits int16[54], priors uint8[54]; candidate sets and solver outcomes are such rows too):
+ *     out[A_m(a)] = in[a].
+ *   Observation row (117 B, byte 13 p + ch) as seen by agent m: channels 0-5 (the viewer's pieces, channel = piece - 1) are permuted by
+ *     tau_m, channels 6-11 (the other side's) by tau_(1-m), channel 12 stays; cells move by sigma.
+ *   z, values, rewards, winners and done do not change.
+ * What is symmetric.  The legal mask, the observation and a step commute with every element.  The piece swaps are symmetries of
+ * check_for_winner() everywhere.  The square's symmetries are too, EXCEPT on boards where both colours hold a line at once (a lift
+ * uncovered the other side's line): there the reference's "last matching line decides" (board.py:183-194) makes the order of the
+ * lines count, and a reflection or rotation changes that order.  Such boards are about 0.04 % of masked-random play.
+ *
+ * gbl_symmetry_apply: for n boards, the image under sym[b] (const int16_t[n]; only its low 9 bits are read) of whichever rows are
+ * given -- or under sym_all, in [0, 512), for every board when sym is NULL.  Every _in / _out pair is optional (both NULL) but goes
+ * together; agent (int8[n], non-zero = player_2: whose view / whose actions) is required as soon as anything but the state pair is
+ * given.  The transform is a permutation and NOT in-place safe: an _out equal to its _in is GBL_ERR_ARG.  state / obs / mask /
+ * visits / priors buffers must be 16-byte aligned, actions 4-byte aligned (GBL_ERR_ALIGN).  One launch; allocates nothing. */
+#define GBL_SYMMETRIES 512
+int gbl_symmetry_apply(const int16_t *sym, int sym_all, const int8_t *agent, const int8_t *state_in, int8_t *state_out,
+                       const int8_t *obs_in, int8_t *obs_out, const int8_t *mask_in, int8_t *mask_out, const int16_t *visits_in,
+                       int16_t *visits_out, const uint8_t *priors_in, uint8_t *priors_out, const int32_t *actions_in,
+                       int32_t *actions_out, int64_t n, void *stream);
+
+/* Symmetry-augmented training batches drawn on the device from a collected window with outcome targets (gbl_collect_search /
+ * gbl_collect_search_eval + gbl_outcome_targets; strides and cell(t, b) as gbl_collect, both layouts).
+ *   Valid cells.  Cell (t, b), 1 <= t < plies, is valid iff z_traj[cell(t, b)] != GBL_Z_OPEN, done_traj[cell(t - 1, b)] == 0 (slot
+ *     t - 1 holds what the mover of ply t saw, unless a game ended there) and the 54 visits of cell(t, b) sum to more than 0.
+ *   Draw of sample j (j = 0 .. batch - 1).  For attempt i = 0 .. GBL_BATCH_ATTEMPTS - 1: (w0, w1, w2, w3) = the block
+ *     Philox4x32-10(ctr = (id_lo, id_hi, 16 call + i, 5), key = (seed_lo, seed_hi)) with id = sample_base + j -- the gbl_sample
+ *     generator with ply index 4 (16 call + i) + w on stream 5 --, t = 1 + ((w0 * (plies - 1)) >> 32), b = (w1 * n) >> 32.  The first
+ *     attempt whose cell (t, b) is valid is taken; its symmetry is s = w2 & sym_mask (sym_mask in [0, 511]: 0 = none, 7 = the square
+ *     only, 511 = the whole group).  The draw of sample j depends on (seed, sample_base + j, call) alone: not on batch, not on the
+ *     launch.  call < 2^26.  A sample is not exactly uniform over the valid cells of a window only in that it may fail: with a valid
+ *     share v of the cells, with probability (1 - v)^16.
+ *   Outputs, row j (all optional but index_out), with m = mover_traj[cell(t, b)] != 0 the agent:
+ *     obs_out    int8 [batch][117] the image of obs_traj[cell(t - 1, b)]       (needs obs_traj)
+ *     mask_out   int8 [batch][54]  the image of mask_traj[cell(t - 1, b)]      (needs mask_traj)
+ *     visits_out int16[batch][54]  the image of visits_traj[cell(t, b)]
+ *     z_out      int8 [batch]      z_traj[cell(t, b)]
+ *     index_out  int32[batch][2]   (t, b)                    sym_out int16[batch]  s
+ *     A sample without a valid attempt: zero rows, z = GBL_Z_OPEN, index (-1, -1), sym 0.
+ * Argument errors: plies < 2 or > 32767, batch < 0 or > 2^31, sym_mask outside [0, 511], call >= 2^26, and with batch > 0: n < 1 or n > 2^31,
+ * a missing required pointer, and gbl_collect's stride rules.  batch == 0 returns GBL_OK after the scalar checks.  visits_traj and
+ * index_out must be 4-byte aligned, sym_out 2-byte, obs_out / mask_out / visits_out 16-byte (GBL_ERR_ALIGN); the window's byte arrays
+ * need no alignment.  One launch, one wavefront per 64 samples; allocates nothing, no atomics. */
+#define GBL_BATCH_ATTEMPTS 16
+int gbl_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                       const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                       int64_t tile_stride, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base, uint32_t call,
+                       int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out,
+                       void *stream);
+
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
  *   GBL_COLLECT_STREAM  k_collect,  one wavefront per tile of 64 boards, trajectory rows stored non-temporally
