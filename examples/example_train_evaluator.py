@@ -34,11 +34,13 @@ def targets_of(traj, boards, plies):
     return obs[keep].float().cpu(), pi[keep].cpu(), z[keep].float().cpu()
 
 
-def collect_targets_with(ev, device, boards, plies, iterations, seed=0):
+def collect_targets_with(ev, device, boards, plies, iterations, seed=0, solve_depth=0):
     """collect_targets with the evaluator-guided search of `ev` on both sides, the first four plies of every game drawn in proportion
-    to the visits: one launch for the whole window."""
+    to the visits: one launch for the whole window.  solve_depth > 0: the exact solver in front of every search (a proven win is
+    taken, a proven loss avoided, and such a ply's policy target is one-hot)."""
     env = G.BatchedGobblet(boards, device, auto_reset=True, seed=seed, track_turn=True)
-    traj = env.collect(plies, policies=("evaluator", "evaluator"), search=dict(evaluator=ev, iterations=iterations, sample_plies=4))
+    traj = env.collect(plies, policies=("evaluator", "evaluator"),
+                       search=dict(evaluator=ev, iterations=iterations, sample_plies=4, solve_depth=solve_depth))
     env.outcome_targets(traj)
     return targets_of(traj, boards, plies)
 
@@ -146,6 +148,8 @@ if __name__ == "__main__":
     ap.add_argument("--games", type=int, default=128)
     ap.add_argument("--generations", type=int, default=1)
     ap.add_argument("--selfplay-iterations", type=int, default=64, help="iterations of the evaluator search in generations >= 2")
+    ap.add_argument("--solve-depth", type=int, default=0,
+                    help="guard the self-play of generations >= 2 with the exact solver at this depth (0: none)")
     ap.add_argument("--augment", choices=("none", "square", "all"), default="none",
                     help="draw every step's batch on the device under random board symmetries (generation 1)")
     a = ap.parse_args()
@@ -154,7 +158,7 @@ if __name__ == "__main__":
     w, l, d = score(ev, a.device, a.iterations, a.games)
     print("evaluator search vs playout search at %d iterations: %d wins, %d losses, %d unfinished of %d games" % (a.iterations, w, l, d, w + l + d))
     for gen in range(2, a.generations + 1):
-        obs, pi, z = collect_targets_with(ev, a.device, a.boards, a.plies, a.selfplay_iterations, seed=gen)
+        obs, pi, z = collect_targets_with(ev, a.device, a.boards, a.plies, a.selfplay_iterations, seed=gen, solve_depth=a.solve_depth)
         weights, hmax, loss = fit(obs, pi, z, a.hidden, a.steps, seed=gen)
         new = G.GobbletEvaluator.from_float(*weights, hidden_max=hmax, device=a.device)
         w, l, n = arena_in_one_launch(new, ev, a.device, a.games, a.plies, a.selfplay_iterations)

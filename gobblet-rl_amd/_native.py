@@ -36,6 +36,7 @@ HOW_RANDOM, HOW_GREEDY, HOW_FALLBACK = 0, 1, 2
 POLICY_TREE, HOW_SEARCH, HOW_SEARCH_SAMPLED, Z_OPEN = 4, 3, 4, -128  # gbl_collect_search / gbl_outcome_targets
 POLICY_EVAL_TREE = 5  # gbl_collect_search_eval
 SOLVE_MAX_DEPTH, SOLVE_NONE = 6, -128  # gbl_solve
+HOW_PROVEN = 5  # gbl_collect_search_solve
 SYMMETRIES, BATCH_ATTEMPTS = 512, 16  # gbl_symmetry_apply / gbl_training_batch
 STATUS_ILLEGAL, STATUS_OUT_OF_RANGE = 1, 2  # gbl_step_ex / gbl_collect_from_ex status bits
 CELLS, ACTIONS, OBS_BYTES = 27, 54, 117
@@ -88,6 +89,8 @@ SIGNATURES = {
     "gbl_collect_search": (_int, [_vp] * 15 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32] + [_int] * 10 + [_vp, _vp, _vp]),
     "gbl_collect_search_eval": (_int, [_vp] * 17 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 5 +
                                 [_vp, _vp, _vp]),
+    "gbl_collect_search_solve": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 7 +
+                                 [_vp, _vp, _vp]),
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_symmetry_apply": (_int, [_vp, _int, _vp] + [_vp] * 12 + [_i64, _vp]),
     "gbl_training_batch": (_int, [_vp] * 6 + [_i64, _u32, _i64, _i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),

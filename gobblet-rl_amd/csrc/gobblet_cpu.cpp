@@ -680,6 +680,24 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
     return GBL_OK;
 }
 
+// One board's solve (the contract of gbl_solve): the 54 result bytes into out, the decision's key back (solve_action_of /
+// solve_value_of read it)
+static uint32_t host_solve(const Planes &p, int mover, uint64_t cand, int depth, int8_t (&out)[kActions])
+{
+    uint32_t best = 0;
+    for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+        out[a] = (int8_t)kSolveNone;
+        if (!((cand >> a) & 1ull)) continue;
+        SolveRoot A = solve_root_action(p, mover, a, depth);
+        for (uint64_t l = A.deep; l; l &= l - 1)
+            A.key = std::max(A.key, solve_reply(p, mover, a, (uint32_t)__builtin_ctzll(l), depth, A.key));
+        if (A.deep) A.c = solve_parent(solve_of_key(A.key));
+        out[a] = (int8_t)A.c;
+        best = std::max(best, solve_action_key(A.c, a));
+    }
+    return best;
+}
+
 int gbl_cpu_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, int depth, int8_t *outcome_out, int8_t *value_out,
                   int32_t *action_out, int64_t n, void *)
 {
@@ -690,17 +708,7 @@ int gbl_cpu_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask
         for (int64_t b = b0; b < b1; ++b) {
             const HostRoot R = host_root(state, to_move, mask, b);
             int8_t out[kActions];
-            uint32_t best = 0;
-            for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
-                out[a] = (int8_t)kSolveNone;
-                if (!((R.cand >> a) & 1ull)) continue;
-                SolveRoot A = solve_root_action(R.p, R.mover, a, depth);
-                for (uint64_t l = A.deep; l; l &= l - 1)
-                    A.key = std::max(A.key, solve_reply(R.p, R.mover, a, (uint32_t)__builtin_ctzll(l), depth, A.key));
-                if (A.deep) A.c = solve_parent(solve_of_key(A.key));
-                out[a] = (int8_t)A.c;
-                best = std::max(best, solve_action_key(A.c, a));
-            }
+            const uint32_t best = host_solve(R.p, R.mover, R.cand, depth, out);
             if (outcome_out) memcpy(outcome_out + b * kActions, out, sizeof out);
             if (value_out) value_out[b] = (int8_t)solve_value_of(best);
             if (action_out) action_out[b] = solve_action_of(best);
@@ -969,12 +977,18 @@ struct SelfplayTraj {
     int8_t *how, *mover;
     int32_t *root_value;  // (the evaluator search's two: NULL in gbl_cpu_collect_search)
     uint8_t *priors;
+    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_cpu_collect_search_solve)
 };
 
 struct SelfplaySearch {
     HostSearch h;
     int32_t root_q;
     const uint8_t *priors;  // the root's prior row, or NULL
+    // gbl_cpu_collect_search_solve's guard: the solver's V and, where it is not 0, its action -- h then holds the one-hot row and
+    // the value, and nothing is decided or drawn from it; `solved`: outcome holds the solver's row
+    int proven, proven_action;
+    bool solved;
+    int8_t outcome[kActions];
 };
 
 extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
@@ -999,12 +1013,14 @@ static void selfplay_boards(int64_t b0, int64_t b1, int8_t *state, int8_t *to_mo
             const int who = mover;
             S.root_q = 0;
             S.priors = nullptr;
+            S.proven = 0;
+            S.solved = false;
             const bool tree = search(p, who, legal, g, q, S);
             int action, how = GBL_HOW_RANDOM, value = 0;
             if (tree) {
-                const bool sampled = tabs < sample_plies;
-                action = sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit)) : tree_action_of(h.best);
-                how = sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
+                const bool sampled = !S.proven && tabs < sample_plies;
+                action = S.proven ? S.proven_action : sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit)) : tree_action_of(h.best);
+                how = S.proven ? GBL_HOW_PROVEN : sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
                 for (int a = 0; a < kActions; ++a) value += h.wins[a] - h.losses[a];
             } else {
                 action = sample54(legal, seed, g, q);
@@ -1036,6 +1052,11 @@ static void selfplay_boards(int64_t b0, int64_t b1, int8_t *state, int8_t *to_mo
                 if (S.priors) memcpy(T.priors + at * kActions, S.priors, kActions);
                 else memset(T.priors + at * kActions, 0, kActions);
             }
+            if (T.outcome) {
+                if (S.solved) memcpy(T.outcome + at * kActions, S.outcome, kActions);
+                else memset(T.outcome + at * kActions, kSolveNone, kActions);
+            }
+            if (T.proven) T.proven[at] = (int8_t)S.proven;
             if (T.obs) write_obs(T.obs + at * kObs, p, mover);
             if (T.mask) write_mask(T.mask + at * kActions, legal);
         }
@@ -1067,7 +1088,7 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
     if (ply_dev) ply0 += *ply_dev;
     const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
     const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                         nodes_traj, how_traj, mover_traj, nullptr, nullptr};
+                         nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr};
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)most + 1);
         selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
@@ -1110,7 +1131,7 @@ int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, in
     if (ply_dev) ply0 += *ply_dev;
     const EvalNet net0 = nets[0], net1 = nets[1];
     const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                         nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj};
+                         nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr};
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)most + 1);
         std::vector<uint8_t> pri(((size_t)most + 1) * kEvalOutputs);
@@ -1118,6 +1139,67 @@ int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, in
                         counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t, uint32_t, SelfplaySearch &S) {
                             if (pol[who] != GBL_POLICY_EVAL_TREE) return false;
                             S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, legal, (uint32_t)its[who],
+                                                             (uint32_t)explore, S.h);
+                            S.priors = pri.data();  // (the root's row; zeros where the root has no candidate)
+                            return true;
+                        });
+    }, 1);
+    return GBL_OK;
+}
+
+int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                 int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                 int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                                 int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                                 int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                                 const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
+                                 int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = collect_solve_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, solve_depth0, solve_depth1,
+                                              explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (plies == 0) return GBL_OK;
+    const gbl_evaluator *evs[2] = {ev0, ev1};
+    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1}, deps[2] = {solve_depth0, solve_depth1};
+    EvalNet nets[2] = {};
+    int most = 0;
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
+        if (const char *why = evaluator_pointers_error(evs[m])) return fail(GBL_ERR_ARG, why);
+        nets[m] = eval_net(evs[m]);
+        most = std::max(most, its[m]);
+    }
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    if (ply_dev) ply0 += *ply_dev;
+    const EvalNet net0 = nets[0], net1 = nets[1];
+    const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                         nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj};
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a solve and a whole search: every board is worth a thread)
+        std::vector<TreeNode> nodes((size_t)most + 1);
+        std::vector<uint8_t> pri(((size_t)most + 1) * kEvalOutputs);
+        selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
+                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t, uint32_t, SelfplaySearch &S) {
+                            if (pol[who] != GBL_POLICY_EVAL_TREE) return false;
+                            uint64_t cand = legal;
+                            if (deps[who] > 0 && legal) {
+                                const uint32_t best = host_solve(p, who, legal, deps[who], S.outcome);
+                                S.solved = true;
+                                S.proven = solve_value_of(best);
+                                if (S.proven) {  // the one-hot row and the value of a proven root: no search
+                                    S.proven_action = solve_action_of(best);
+                                    S.h = HostSearch{};
+                                    S.h.visits[S.proven_action] = its[who];
+                                    (S.proven > 0 ? S.h.wins : S.h.losses)[S.proven_action] = 128 * its[who];
+                                    return true;
+                                }
+                                cand = 0;
+                                for (int a = 0; a < kActions; ++a) cand |= (uint64_t)(S.outcome[a] == 0) << a;
+                            }
+                            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, (uint32_t)its[who],
                                                              (uint32_t)explore, S.h);
                             S.priors = pri.data();  // (the root's row; zeros where the root has no candidate)
                             return true;

@@ -2010,6 +2010,7 @@ __device__ __forceinline__ void tree_backup(TreeNode *nodes, uint32_t leaf, uint
 constexpr int kPolicyTree = 4;                 // GBL_POLICY_TREE
 constexpr int kPolicyEvalTree = 5;             // GBL_POLICY_EVAL_TREE (gbl_collect_search_eval)
 constexpr int kHowSearch = 3, kHowSearchSampled = 4;  // GBL_HOW_SEARCH / GBL_HOW_SEARCH_SAMPLED (0 = GBL_HOW_RANDOM)
+constexpr int kHowProven = 5;                  // GBL_HOW_PROVEN (gbl_collect_search_solve)
 constexpr int kZOpen = -128;                   // GBL_Z_OPEN
 constexpr uint32_t kStreamVisit = 4u;          // generator stream of the visit-proportional draw of a game's first plies
 
@@ -2429,6 +2430,21 @@ inline const char *collect_eval_error(int illegal_mode, int policy0, int policy1
         if (const char *why = tree_eval_budget_error(its[m], explore)) return why;
     }
     return selfplay_window_error(sample_plies, has_turn, ply0, plies, env_base, n);
+}
+
+// gbl_collect_search_solve: collect_eval_error, then the guarded sides' depths (a RANDOM side's is not read; 0 = no guard).  (n >= 0)
+template <typename Ev>
+inline const char *collect_solve_error(int illegal_mode, int policy0, int policy1, const Ev *ev0, const Ev *ev1, int iterations0,
+                                       int iterations1, int solve_depth0, int solve_depth1, int explore, int sample_plies, bool has_turn,
+                                       uint32_t ply0, uint32_t plies, uint64_t env_base, int64_t n)
+{
+    if (const char *why = collect_eval_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, explore, sample_plies,
+                                             has_turn, ply0, plies, env_base, n))
+        return why;
+    if ((policy0 == kPolicyEvalTree && (solve_depth0 < 0 || solve_depth0 > kSolveMaxDepth)) ||
+        (policy1 == kPolicyEvalTree && (solve_depth1 < 0 || solve_depth1 > kSolveMaxDepth)))
+        return "solve_depth0 / solve_depth1 must be in [0, 6]";
+    return nullptr;
 }
 
 // gbl_solve: every check, in the order both flavours report them.  Returns the message (nullptr: none) and, in `code`, which error

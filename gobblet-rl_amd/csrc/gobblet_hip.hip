@@ -2498,59 +2498,147 @@ __global__ __launch_bounds__(64) void k_training_batch(BatchArgs A)
 // DEAL picks how phase 2 hands the pairs out: 0 = lane l takes pairs l, l + 64, ...; 1 = a lane takes the next pair off a counter
 // in LDS whenever it is free.  Either way a lane's pairs come in ascending order, so the action of a pair is found by walking a
 // cursor over the scan.
+// The three phases live in solve_board, which gbl_collect_search_solve's kernel runs too.
+//
+// The solver's LDS of one board's wavefront: the quiet replies and the order key per root action, the scan, the deal's counter
+struct SolveLds {
+    uint64_t deep[kActions];
+    uint32_t start[kActions + 1], key[kActions], next;
+};
+
+// Orders a wavefront's accesses to SolveLds between the phases.  BLOCK: __syncthreads(), k_solve's own; else wave_lds_fence() --
+// a kernel with trajectory stores in flight must not wait for them here (see pool_fence).
+template <bool BLOCK>
+__device__ __forceinline__ void solve_fence()
+{
+    if (BLOCK)
+        __syncthreads();
+    else
+        wave_lds_fence();
+}
+
+// One board's solve; every lane of the board's one wavefront calls it with the same root / mover / cand / depth.  Returns the
+// decision's key (solve_action_of / solve_value_of read it) in every lane and leaves in c lane a's result byte (kSolveNone for a
+// non-candidate).  At depth > 2 the caller passes solve_fence<BLOCK>() before the next call rewrites L.
+template <int DEAL, bool BLOCK>
+__device__ __forceinline__ uint32_t solve_board(SolveLds &L, const Planes &root, int mover, uint64_t cand, int depth, uint32_t lane, int &c)
+{
+    const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
+    SolveRoot A{kSolveNone, 0u, 0ull};
+    if (mine) A = solve_root_action(root, mover, lane, depth);
+    if (depth > 2) {  // (wave-uniform)
+        uint32_t upto = (uint32_t)__popcll(A.deep);  // inclusive scan of the pairs per action
+#pragma unroll
+        for (uint32_t o = 1; o < 64u; o <<= 1) {
+            const uint32_t below = (uint32_t)__shfl_up((int)upto, o);
+            upto += lane >= o ? below : 0u;
+        }
+        const uint32_t total = (uint32_t)__shfl((int)upto, 63);
+        if (lane < (uint32_t)kActions) {
+            L.deep[lane] = A.deep;
+            L.key[lane] = A.key;
+            L.start[lane + 1] = upto;
+        }
+        if (lane == 0) {
+            L.start[0] = 0u;
+            L.next = 0u;
+        }
+        solve_fence<BLOCK>();
+        uint32_t a = 0;
+        for (uint32_t i = DEAL ? atomicAdd(&L.next, 1u) : lane; i < total; i = DEAL ? atomicAdd(&L.next, 1u) : i + 64u) {
+            while (L.start[a + 1] <= i) ++a;  // (start[54] = total > i: a stays below 54)
+            // key[a] is read plainly while other lanes atomicMax it: a stale value is one the action held earlier, which
+            // cuts less and gives the same key (solve_reply) -- it costs work, never the result
+            const uint32_t rb = kth_bit64(L.deep[a], i - L.start[a]);
+            atomicMax(&L.key[a], solve_reply(root, mover, a, rb, depth, L.key[a]));
+        }
+        solve_fence<BLOCK>();
+        if (A.deep) A.c = solve_parent(solve_of_key(L.key[lane]));
+    }
+    c = A.c;
+    return wave_max(mine ? solve_action_key(A.c, lane) : 0u);
+}
+
 template <int DEAL>
 __global__ __launch_bounds__(64) void k_solve(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
                                               const int8_t *__restrict__ mask, int8_t *__restrict__ outcome_out,
                                               int8_t *__restrict__ value_out, int32_t *__restrict__ action_out, int64_t n, int depth)
 {
-    __shared__ uint64_t s_deep[kActions];
-    __shared__ uint32_t s_start[kActions + 1], s_key[kActions], s_next;
+    __shared__ SolveLds s_solve;
     const uint32_t lane = threadIdx.x;
     for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
         const Planes root = board_planes(state, b, lane);
         const int mover = to_move[b] != 0;
-        const uint64_t cand = board_candidates(root, mover, mask, b, lane);
-        const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
-        SolveRoot A{kSolveNone, 0u, 0ull};
-        if (mine) A = solve_root_action(root, mover, lane, depth);
-        uint32_t total = 0;
-        if (depth > 2) {  // (wave-uniform)
-            uint32_t upto = (uint32_t)__popcll(A.deep);  // inclusive scan of the pairs per action
-#pragma unroll
-            for (uint32_t o = 1; o < 64u; o <<= 1) {
-                const uint32_t below = (uint32_t)__shfl_up((int)upto, o);
-                upto += lane >= o ? below : 0u;
-            }
-            total = (uint32_t)__shfl((int)upto, 63);
-            if (lane < (uint32_t)kActions) {
-                s_deep[lane] = A.deep;
-                s_key[lane] = A.key;
-                s_start[lane + 1] = upto;
-            }
-            if (lane == 0) {
-                s_start[0] = 0u;
-                s_next = 0u;
-            }
-            __syncthreads();
-            uint32_t a = 0;
-            for (uint32_t i = DEAL ? atomicAdd(&s_next, 1u) : lane; i < total; i = DEAL ? atomicAdd(&s_next, 1u) : i + 64u) {
-                while (s_start[a + 1] <= i) ++a;  // (s_start[54] = total > i: a stays below 54)
-                // s_key[a] is read plainly while other lanes atomicMax it: a stale value is one the action held earlier, which
-                // cuts less and gives the same key (solve_reply) -- it costs work, never the result
-                const uint32_t rb = kth_bit64(s_deep[a], i - s_start[a]);
-                atomicMax(&s_key[a], solve_reply(root, mover, a, rb, depth, s_key[a]));
-            }
-            __syncthreads();
-            if (A.deep) A.c = solve_parent(solve_of_key(s_key[lane]));
-        }
-        if (outcome_out && lane < (uint32_t)kActions) outcome_out[b * kActions + lane] = (int8_t)A.c;
-        const uint32_t best = wave_max(mine ? solve_action_key(A.c, lane) : 0u);
+        int c;
+        const uint32_t best = solve_board<DEAL, true>(s_solve, root, mover, board_candidates(root, mover, mask, b, lane), depth, lane, c);
+        if (outcome_out && lane < (uint32_t)kActions) outcome_out[b * kActions + lane] = (int8_t)c;
         if (lane == 0) {
             if (value_out) value_out[b] = (int8_t)solve_value_of(best);
             if (action_out) action_out[b] = solve_action_of(best);
         }
-        if (depth > 2) __syncthreads();  // (before the next board rewrites the LDS arrays)
+        if (depth > 2) solve_fence<true>();  // (before the next board rewrites the LDS arrays)
     }
+}
+
+// gbl_collect_search_solve: k_collect_eval with the exact solver in front of every search of a guarded side (solve_depth_m > 0).
+// One wavefront per board (a grid-stride loop over boards), the ply loop inside (search_plies).  A guarded ply runs solve_board
+// on the live planes.  A proven root (V != 0) plays the solver's action and searches nothing; an unproven root searches exactly as
+// k_tree_eval does under the mask C = the actions of outcome 0 (tree_eval_iterations with cand = C, then search_decide).  The
+// solver's LDS stands beside the tree's, and its fences are wave_lds_fence: the ply's trajectory stores stay in flight over the
+// next decision.  The solver's registers are dead before the tree's come alive.  The outcome byte of every lane and V go out
+// from the second lambda, beside the root's q and the prior byte.
+__global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                      uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
+                                                      int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
+                                                      int32_t *__restrict__ root_value_traj, uint8_t *__restrict__ priors_traj,
+                                                      int8_t *__restrict__ outcome_traj, int8_t *__restrict__ proven_traj,
+                                                      const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
+                                                      uint32_t iterations1, int solve_depth0, int solve_depth1, uint32_t most, uint32_t explore,
+                                                      int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
+                                                      int32_t *__restrict__ turn)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    __shared__ SolveLds s_solve;
+    const uint32_t lane = threadIdx.x;
+    int my_c = kSolveNone, proven = 0;  // the ply's outcome byte of this lane and V, from the first lambda to the second
+    search_plies(
+        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            my_c = kSolveNone;
+            proven = 0;
+            if ((who ? policy1 : policy0) != kPolicyEvalTree) return false;
+            const uint32_t its = who ? iterations1 : iterations0;
+            const int depth = who ? solve_depth1 : solve_depth0;
+            uint64_t cand = legal;
+            if (depth > 0 && legal) {  // (wave-uniform)
+                const uint32_t best = solve_board<knob::kSolveDeal, false>(s_solve, B.p, who, legal, depth, lane, my_c);
+                if (depth > 2) solve_fence<false>();  // (before the next ply's solve rewrites the LDS arrays)
+                proven = uniform(solve_value_of(best));
+                if (proven) {
+                    const int a = uniform(solve_action_of(best));
+                    S.d = SearchDecision{a, kHowProven, (proven > 0 ? 128 : -128) * (int)its, lane == (uint32_t)a ? its : 0u};
+                    return true;
+                }
+                cand = (uint64_t)__ballot(my_c == 0);
+            }
+            const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its, explore, lane,
+                                                          S.count);
+            S.pi = at_root.pi;
+            S.root_q = at_root.q;
+            S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+            wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            return true;
+        },
+        [&](int64_t at, const SearchPly &S) {
+            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
+            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
+            if (outcome_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((int8_t)my_c, outcome_traj + at * kActions + lane);
+            if (proven_traj && lane == 0) proven_traj[at] = (int8_t)proven;
+        });
 }
 
 // gbl_greedy: one decision per board.  Each lane owns a board (depth-1 walk, order-dependent replay,
@@ -4101,6 +4189,47 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
                        policy1, (uint32_t)iterations0, (uint32_t)iterations1, (uint32_t)most, (uint32_t)explore, sample_plies, illegal_mode,
                        counters, turn);
     GBL_LAUNCHED("gbl_collect_search_eval");
+}
+
+int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                             int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                             int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                             uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                             int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                             int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                             int solve_depth0, int solve_depth1, int explore, int sample_plies, int illegal_mode, int64_t *counters,
+                             int32_t *turn, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = collect_solve_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, solve_depth0, solve_depth1,
+                                              explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (plies == 0) return GBL_OK;
+    const gbl_evaluator *evs[2] = {ev0, ev1};
+    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
+    EvalNet nets[2] = {};  // (a RANDOM side's stays empty: the kernel never reads it)
+    int most = 0;          // the larger tree of the sides that search
+    for (int m = 0; m < 2; ++m) {
+        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
+        if (const int e = eval_net_of(evs[m], nets[m])) return e;
+        most = std::max(most, its[m]);
+    }
+    const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                       nodes_traj, how_traj, mover_traj};
+    if (const int e = check_search_traj(T, reinterpret_cast<uintptr_t>(root_value_traj),
+                                        "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned", n, plies,
+                                        ply_stride, tile_stride, state, turn, counters))
+        return e;
+    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    // the tree as gbl_collect_search_eval; the solver's arrays are static LDS beside it
+    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)most + 1);
+    hipLaunchKernelGGL(k_collect_solve, grid, dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed, env_base, ply_dev, ply0, plies, done,
+                       ply_stride, tile_stride, T, root_value_traj, priors_traj, outcome_traj, proven_traj, nets[0], nets[1], policy0, policy1,
+                       (uint32_t)iterations0, (uint32_t)iterations1, solve_depth0, solve_depth1, (uint32_t)most, (uint32_t)explore,
+                       sample_plies, illegal_mode, counters, turn);
+    GBL_LAUNCHED("gbl_collect_search_solve");
 }
 
 int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

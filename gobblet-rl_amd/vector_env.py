@@ -260,8 +260,13 @@ class BatchedGobblet:
 
     def trajectory_buffers(self, plies: int, layout: str = "time", pad_boards: int | None = None,
                            placement: str = "auto", policy_outputs: bool = False, candidates: bool = False,
-                           far: bool | None = None, search_outputs: bool = False, evaluator_outputs: bool = False) -> dict:
+                           far: bool | None = None, search_outputs: bool = False, evaluator_outputs: bool = False,
+                           solver_outputs: bool = False) -> dict:
         """Device tensors for ``collect``.
+
+        solver_outputs (with ``evaluator_outputs``): also "outcomes" (int8 (..., 54): the solver's result of every action of the ply's
+        position, ``nat.SOLVE_NONE`` where nothing was solved) and "proven" (int8: the position's own result) for ``collect`` with
+        ``search=dict(solve_depth=...)``.
 
         evaluator_outputs (with ``search_outputs``): also "root_value" (int32: the root's q of every ply's evaluator-guided search,
         in 1/128 of a win for the mover) and "priors" (uint8 (..., 54): the root's prior row) for ``collect`` with an evaluator side.
@@ -356,6 +361,10 @@ class BatchedGobblet:
             if not search_outputs:
                 raise ValueError("evaluator_outputs belongs to search_outputs=True")
             extra += (("root_value", torch.int32, ()), ("priors", torch.uint8, (nat.ACTIONS,)))
+        if solver_outputs:
+            if not evaluator_outputs:
+                raise ValueError("solver_outputs belongs to evaluator_outputs=True")
+            extra += (("outcomes", torch.int8, (nat.ACTIONS,)), ("proven", torch.int8, ()))
         for key, dtype, tail in (("actions", torch.int32, ()), ("winner", torch.int8, ()), ("rewards", torch.int8, (2,)),
                                  ("done", torch.int8, ()), ("to_move", torch.int8, ())) + extra:
             full[key] = torch.zeros(lead + tail, dtype=dtype, device=dev)
@@ -424,25 +433,35 @@ class BatchedGobblet:
         ``iterations`` may each be a pair, one per side (two different networks: an arena); ``explore`` is one value.  Ply t's search
         is exactly ``gbl_tree_search_eval`` of the position.  The buffers (``trajectory_buffers(search_outputs=True,
         evaluator_outputs=True)``) receive the search entries and "root_value" / "priors".  An evaluator side cannot be paired with
-        "tree" or a greedy policy inside one launch: compose ``compute_actions_from_state`` + ``step_into`` per ply for that."""
+        "tree" or a greedy policy inside one launch: compose ``compute_actions_from_state`` + ``step_into`` per ply for that.
+
+        ``search=dict(..., solve_depth=d)`` (an int, or a pair, one per side; 0 or absent: none) puts the exact solver in front of
+        every search of an evaluator side, still inside the one launch (``gbl_collect_search_solve``): a root the solver proves
+        (a forced win, or nothing but forced losses) plays the solver's action, "how" = ``nat.HOW_PROVEN``, with a one-hot visits
+        row; every other root is searched over its unproven actions only.  The buffers (``solver_outputs=True``) also receive
+        "outcomes" / "proven"; ``outcome_targets`` and ``training_batch`` take the result as it is."""
         if not self.auto_reset:
             raise ValueError("collect() plays with auto-reset; this environment was created with auto_reset=False")
         T = int(plies)
         ep = self._evaluator_params(policies, search)  # None unless a side plays the evaluator-guided search
         sp = ep if ep is not None else self._search_params(policies, search)  # None unless a side plays a tree search
+        guarded = ep is not None and any(ep["solve_depth"])  # (the solver in front of an evaluator side's searches)
         if isinstance(out, str):
             if out != "fresh":
                 raise ValueError("out: a dict from trajectory_buffers(), None (the environment's staging buffers) or 'fresh'")
             # buffers of the caller's own: made (and placed) now, not kept by the environment, never overwritten by a later call
             out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                          search_outputs=sp is not None, evaluator_outputs=ep is not None, far=False)
+                                          search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
+                                          far=False)
         if out is None:
-            key = (T, layout, policies is not None) + (("search",) if sp is not None else ()) + (("evaluator",) if ep is not None else ())
+            key = (T, layout, policies is not None) + (("search",) if sp is not None else ()) + (("evaluator",) if ep is not None else ()) + \
+                (("solver",) if guarded else ())
             out = self._staging.pop(key, None)
             made = out is None
             if made:
                 out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                              search_outputs=sp is not None, evaluator_outputs=ep is not None, far=False)
+                                              search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
+                                              far=False)
             # (buffers made inside a graph capture belong to the graph's private pool: not kept beyond it)
             capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
             if not (made and capturing):
@@ -477,7 +496,13 @@ class BatchedGobblet:
                     nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")))
             window = (n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T)
             tail = (sp["sample_plies"], self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream())
-            if ep is not None:
+            if guarded:
+                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
+                nat.check(self._lib.gbl_collect_search_solve(
+                    *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), nat.ptr(f.get("outcomes")), nat.ptr(f.get("proven")),
+                    *window, *ep["policies"], *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
+                    *ep["solve_depth"], ep["explore"], *tail), "gbl_collect_search_solve")
+            elif ep is not None:
                 structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
                 nat.check(self._lib.gbl_collect_search_eval(
                     *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), *window, *ep["policies"],
@@ -595,11 +620,12 @@ class BatchedGobblet:
         evs = [is_eval(x) for x in sides]
         if len(sides) != 2 or not any(evs):
             return None
-        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0),  # EvaluatorTreeSearchGobbletPolicy's defaults
-                             search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies)")
-        its, nets = self._pair(kw["iterations"]), self._pair(kw["evaluator"])
-        if len(its) != 2 or len(nets) != 2:
-            raise ValueError("search: iterations / evaluator are a value or a pair, one per side")
+        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0),  # EvaluatorTreeSearchGobbletPolicy's defaults
+                             search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies / "
+                             "solve_depth)")
+        its, nets, deps = self._pair(kw["iterations"]), self._pair(kw["evaluator"]), self._pair(kw["solve_depth"])
+        if len(its) != 2 or len(nets) != 2 or len(deps) != 2:
+            raise ValueError("search: iterations / evaluator / solve_depth are a value or a pair, one per side")
         codes, explores = [], []
         for m, x in enumerate(sides):
             if isinstance(x, EvaluatorTreeSearchGobbletPolicy):
@@ -626,8 +652,11 @@ class BatchedGobblet:
             explore = 16
         for m in range(2):
             if codes[m] != nat.POLICY_EVAL_TREE:
-                its[m] = 0
+                its[m] = deps[m] = 0
                 continue
+            deps[m] = int(deps[m] or 0)
+            if not 0 <= deps[m] <= nat.SOLVE_MAX_DEPTH:
+                raise ValueError(f"search: solve_depth must be in [0, {nat.SOLVE_MAX_DEPTH}]")
             if not isinstance(nets[m], GobbletEvaluator):
                 raise ValueError("search: an 'evaluator' side needs search=dict(evaluator=GobbletEvaluator ...)")
             if nets[m].device != self.device:
@@ -638,7 +667,8 @@ class BatchedGobblet:
                 raise ValueError("search: iterations must be in [1, 512]")
         if not (0 <= explore <= 1024 and int(kw["sample_plies"]) >= 0):
             raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
-        return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]))
+        return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
+                    solve_depth=deps)
 
     def outcome_targets(self, traj: dict) -> dict:
         """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128

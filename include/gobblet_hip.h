@@ -566,6 +566,41 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
                             int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
                             int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
 
+/* Solver-guarded evaluator self-play (no counterpart in the reference): gbl_collect_search_eval with gbl_solve in front of every
+ * search, inside the same launch -- a side that is guarded never passes over a win the solver proves and never steps into a loss it
+ * proves beside an unproven move.  Everything is as gbl_collect_search_eval (policies GBL_POLICY_RANDOM / GBL_POLICY_EVAL_TREE, ev0 /
+ * ev1, the window, the strides, the twelve arrays and root_value_traj / priors_traj), with
+ *   solve_depth0 / solve_depth1  the guard's depth for player_1 / player_2: 0 = no guard, else 1 .. GBL_SOLVE_MAX_DEPTH.  A RANDOM
+ *                                side's depth is ignored, as its evaluator and iterations are.
+ * The one exception to gbl_collect_search_eval's rule is the ply of a mover m with policy EVAL_TREE and solve_depth_m = d > 0:
+ *   solve     (outcome, V, a*) = gbl_solve(state, to_move, mask = NULL, depth = d) of the board's current position: the same rule text.
+ *   proven    V != 0 (the root holds a forced win, or every candidate is a forced loss): the action is a* -- the shortest win, else
+ *             the longest loss, the lowest index on ties.  No search runs and nothing is drawn, also while turn[b] < sample_plies.
+ *             how = GBL_HOW_PROVEN; the visits row holds iterations_m at a* and 0 elsewhere (visits / sum is one-hot, and
+ *             gbl_training_batch keeps the ply); value = sign(V) * 128 * iterations_m; nodes = 0, root_value = 0, the prior row zeros.
+ *   unproven  V == 0 and at least one outcome is 0.  With C = the actions whose outcome is 0, the search is exactly
+ *             gbl_tree_search_eval(state, to_move, mask = C, ev_m, iterations_m, explore); the action is its action_out or, while
+ *             turn[b] < sample_plies, the visit-proportional draw on stream 4; how, visits, value, nodes, root_value and priors are
+ *             what gbl_collect_search_eval writes for that search.
+ *   a root without a candidate: as EVAL_TREE in gbl_collect_search_eval (action -1, stepped per illegal_mode).
+ * Two more arrays per cell (either may be NULL):
+ *   outcome_traj int8[cells][54]  the solver's outcome_out row of ply t's position
+ *   proven_traj  int8[cells]      the solver's V
+ * On plies of a RANDOM side, of a side with depth 0 and of a root without a candidate the outcome row is all GBL_SOLVE_NONE and V is 0.
+ * With both depths 0 every shared array is that of gbl_collect_search_eval, bit for bit.  A depth outside 0 .. GBL_SOLVE_MAX_DEPTH on
+ * an EVAL_TREE side is GBL_ERR_ARG; every other limit, the alignment rules (outcome_traj / proven_traj need none) and the LDS of the
+ * tree as gbl_collect_search_eval, beside which the solver keeps 872 bytes.  gbl_outcome_targets and gbl_training_batch work on these
+ * trajectories unchanged.  Allocates nothing. */
+#define GBL_HOW_PROVEN 5
+int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                             int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                             int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                             int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                             int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                             const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                             const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
+                             int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
+
 /* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
  * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:
  *   z_traj          int8 [cells]  reward_traj[cell(e, b)][mover_traj[cell(t, b)]] -- the reward, not the winner, so that
