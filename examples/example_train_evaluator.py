@@ -5,7 +5,9 @@ round: generation k collects with generation k - 1's evaluator on both sides INS
 new network and plays it against the old one, one launch per colour:
     python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G] [--generations G]
 --augment square|all draws every Adam step's batch on the device under random board symmetries (BatchedGobblet.training_batch) and
-fits there; the default (none) keeps the whole window on the host as before."""
+fits there; the default (none) keeps the whole window on the host as before.  --fit device (with --augment) runs every Adam step on
+the device too: BatchedGobblet.fit with a GobbletTrainer, two launches of gbl_train_step per step instead of torch's few dozen, and the
+same bits from the same seed on every run; the default (torch) keeps the recorded runs reproducible."""
 import argparse
 import os
 import sys
@@ -102,6 +104,13 @@ def fit_augmented(env, traj, hidden, steps, augment, seed=0):
     return (l1.weight.detach().T, l1.bias.detach(), l2.weight.detach().T, l2.bias.detach()), hmax, float(loss.detach())
 
 
+def fit_on_device(env, traj, hidden, steps, augment, seed=0):
+    """fit_augmented with the whole step on the device: the batch draw and gbl_train_step, nothing of the fit in torch."""
+    trainer = G.GobbletTrainer(hidden=hidden, device=env.device, seed=seed)
+    stats = env.fit(traj, trainer, steps, batch=1024, symmetries=augment)
+    return trainer.evaluator(), float(stats[-1, 0] + stats[-1, 1])
+
+
 def arena(first, second, n, device, seed=7, max_plies=64):
     """n games in lockstep, `first` as player_1 (finished games stay frozen): (player_1 wins, player_2 wins)."""
     env = G.BatchedGobblet(n, device, auto_reset=False, seed=seed)
@@ -113,14 +122,17 @@ def arena(first, second, n, device, seed=7, max_plies=64):
     return int((env.winner == 1).sum()), int((env.winner == -1).sum())
 
 
-def train_evaluator(device, boards=512, plies=48, steps=400, hidden=64, collect_iterations=64, augment="none"):
+def train_evaluator(device, boards=512, plies=48, steps=400, hidden=64, collect_iterations=64, augment="none", fit_with="torch"):
     if augment != "none":
         env = G.BatchedGobblet(boards, device, auto_reset=True, seed=0, track_turn=True)
         traj = env.collect(plies, policies=("tree", "tree"), search=dict(iterations=collect_iterations, playouts=8, max_plies=64, explore=16,
                                                                          sample_plies=4))
         env.outcome_targets(traj)
-        weights, hmax, loss = fit_augmented(env, traj, hidden, steps, augment)
         kept = int(((traj["z"][1:] != G._native.Z_OPEN) & (traj["done"][:-1] == 0) & (traj["visits"][1:].sum(-1, dtype=torch.int32) > 0)).sum())
+        if fit_with == "device":
+            ev, loss = fit_on_device(env, traj, hidden, steps, augment)
+            return ev, kept, loss
+        weights, hmax, loss = fit_augmented(env, traj, hidden, steps, augment)
         return G.GobbletEvaluator.from_float(*weights, hidden_max=hmax, device=device), kept, loss
     obs, pi, z = collect_targets(device, boards, plies, collect_iterations)
     weights, hmax, loss = fit(obs, pi, z, hidden, steps)
@@ -152,8 +164,12 @@ if __name__ == "__main__":
                     help="guard the self-play of generations >= 2 with the exact solver at this depth (0: none)")
     ap.add_argument("--augment", choices=("none", "square", "all"), default="none",
                     help="draw every step's batch on the device under random board symmetries (generation 1)")
+    ap.add_argument("--fit", choices=("torch", "device"), default="torch",
+                    help="device: every Adam step of generation 1 is gbl_train_step (needs --augment square or all)")
     a = ap.parse_args()
-    ev, samples, loss = train_evaluator(a.device, a.boards, a.plies, a.steps, a.hidden, augment=a.augment)
+    if a.fit == "device" and a.augment == "none":
+        ap.error("--fit device draws its batches on the device: pass --augment square or all")
+    ev, samples, loss = train_evaluator(a.device, a.boards, a.plies, a.steps, a.hidden, augment=a.augment, fit_with=a.fit)
     print("trained on", samples, "plies; final loss", round(loss, 3), "; scales", ev.scales, "shifts", (ev.shift1, ev.shift_p, ev.shift_v))
     w, l, d = score(ev, a.device, a.iterations, a.games)
     print("evaluator search vs playout search at %d iterations: %d wins, %d losses, %d unfinished of %d games" % (a.iterations, w, l, d, w + l + d))

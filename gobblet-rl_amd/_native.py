@@ -94,6 +94,8 @@ SIGNATURES = {
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_symmetry_apply": (_int, [_vp, _int, _vp] + [_vp] * 12 + [_i64, _vp]),
     "gbl_training_batch": (_int, [_vp] * 6 + [_i64, _u32, _i64, _i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),
+    "gbl_train_workspace_bytes": (_i64, [_i64, _int]),
+    "gbl_train_step": (_int, [_vp] * 4 + [_i64, _int] + [_vp] * 7 + [_i64, _vp]),
     "gbl_collect_variant": (_int, [_i64, _u32, _int, _int]),
     "gbl_block_alloc": (_int, [_i64, C.POINTER(_vp)]),
     "gbl_block_free": (_int, [_vp]),
@@ -107,6 +109,11 @@ class Evaluator(C.Structure):
     """gbl_evaluator (include/gobblet_hip.h): a host struct of four pointers (device pointers for the HIP library) and four ints."""
     _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp),
                 ("hidden", C.c_int32), ("shift1", C.c_int32), ("shift_p", C.c_int32), ("shift_v", C.c_int32)]
+
+
+class TrainHyper(C.Structure):
+    """gbl_train_hyper (include/gobblet_hip.h): eight floats on the HOST, read when gbl_train_step is called."""
+    _fields_ = [(k, C.c_float) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "value_reg", "bias1", "bias2")]
 
 
 class GobbletHipError(RuntimeError):
@@ -216,10 +223,11 @@ def current_stream(device):
 CPU_LIB_PATH = os.path.join(CSRC, "libgobblet_cpu.so")
 CPU_SOURCES = [os.path.join(CSRC, "gobblet_cpu.cpp"), os.path.join(CSRC, "gobblet_device.h"),
                os.path.join(_HERE, "..", "include", "gobblet_cpu.h"), os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
-CPU_CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", "-Wno-attributes"] + \
+# -ffp-contract=off: gbl_cpu_train_step's float rule is single IEEE operations (include/gobblet_hip.h); everything else here is integer code
+CPU_CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"] + \
                 (["-mpopcnt"] if platform.machine() in ("x86_64", "AMD64") else [])
 _NO_HOST_FLAVOUR = ("gbl_pinned_alloc", "gbl_pinned_free", "gbl_block_alloc", "gbl_block_free", "gbl_device_memory",
-                    "gbl_placement_probe", "gbl_collect_variant")
+                    "gbl_placement_probe", "gbl_collect_variant", "gbl_train_workspace_bytes")
 CPU_SIGNATURES = {"gbl_cpu_" + k[4:]: v for k, v in SIGNATURES.items() if k not in _NO_HOST_FLAVOUR}
 CPU_SIGNATURES["gbl_cpu_set_threads"] = (_int, [_int])
 

@@ -1297,3 +1297,166 @@ int gbl_cpu_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, cons
 }
 
 }  // extern "C"
+
+// gbl_cpu_train_step: the header's rule row by row and element by element -- the same scalar pieces (gobblet_device.h: train_exp,
+// train_log, train_value, train_policy, train_gradient, train_adam) in the same order as the kernels; the rows, and then the
+// parameter segments, are dealt over the threads, which changes no sum's order.
+namespace {
+
+struct HostTrain {
+    const int8_t *obs, *mask;
+    const int16_t *visits;
+    const int8_t *z;
+    const float *params;
+    float *h, *dh, *dout, *row;
+    int H;
+    TrainHyper hy;
+};
+
+void train_row(const HostTrain &A, int64_t r)
+{
+    GBL_FP_STRICT
+    const int H = A.H;
+    float *rh = A.h + r * H, *rdh = A.dh + r * H, *rdo = A.dout + r * kTrainDoStride, *rst = A.row + r * kTrainRowStats;
+    const float *w1 = A.params, *b1 = w1 + kObs * H, *w2 = b1 + H, *b2 = w2 + H * kTrainOutputs;
+    bool in_c[kActions];
+    int S = 0, first = -1;
+    for (int a = 0; a < kActions; ++a) {
+        in_c[a] = !A.mask || A.mask[r * kActions + a] != 0;
+        if (in_c[a]) S += A.visits[r * kActions + a];
+        if (in_c[a] && first < 0) first = a;
+    }
+    const int z = A.z[r];
+    if (z == kZOpen || S <= 0) {
+        std::fill(rh, rh + H, 0.0f); std::fill(rdh, rdh + H, 0.0f);
+        std::fill(rdo, rdo + kTrainDoStride, 0.0f); std::fill(rst, rst + kTrainRowStats, 0.0f);
+        return;
+    }
+    float pre[256], o[kTrainOutputs], d[kActions], e[kActions], term[kActions];
+    for (int j = 0; j < H; ++j) pre[j] = b1[j];
+    for (int f = 0; f < kObs; ++f)
+        if (A.obs[r * kObs + f] != 0)
+            for (int j = 0; j < H; ++j) pre[j] = pre[j] + w1[f * H + j];
+    float top = 0.0f;
+    for (int j = 0; j < H; ++j) {
+        rh[j] = pre[j] > 0.0f ? pre[j] : 0.0f;
+        top = train_float_bits(rh[j]) > train_float_bits(top) ? rh[j] : top;
+    }
+    for (int k = 0; k < kTrainOutputs; ++k) o[k] = b2[k];
+    for (int j = 0; j < H; ++j)
+        for (int k = 0; k < kTrainOutputs; ++k) o[k] = o[k] + rh[j] * w2[j * kTrainOutputs + k];
+    float mx = o[first];
+    for (int a = first + 1; a < kActions; ++a)
+        if (in_c[a]) mx = o[a] > mx ? o[a] : mx;
+    float s = 0.0f;
+    for (int a = 0; a < kActions; ++a) {
+        if (!in_c[a]) continue;
+        d[a] = o[a] - mx;
+        e[a] = train_exp(d[a]);
+        s = s + e[a];
+    }
+    const float L = train_log(s);
+    float lp = 0.0f, lv, dv;
+    for (int a = 0; a < kActions; ++a) {
+        rdo[a] = 0.0f;
+        if (!in_c[a]) continue;
+        train_policy(e[a], s, d[a], L, A.visits[r * kActions + a], S, rdo[a], term[a]);
+        lp = lp + term[a];
+    }
+    train_value(o[kActions], z, A.hy.value_reg, lv, dv);
+    rdo[kActions] = dv;
+    rdo[kTrainOutputs] = 0.0f;
+    for (int j = 0; j < H; ++j) {
+        float acc = 0.0f;
+        for (int k = 0; k < kTrainOutputs; ++k) acc = acc + rdo[k] * w2[j * kTrainOutputs + k];
+        rdh[j] = pre[j] > 0.0f ? acc : 0.0f;
+    }
+    rst[0] = lp; rst[1] = lv; rst[2] = top; rst[3] = 1.0f;
+}
+
+// SUM of the header over `len` neighbouring elements at once: term(r, acc) adds row r's terms to the chunk's accumulators
+template <typename Term>
+void train_sum(int64_t B, int len, float *total, Term term)
+{
+    GBL_FP_STRICT
+    float acc[256];
+    std::fill(total, total + len, 0.0f);
+    for (int64_t r0 = 0; r0 < B; r0 += kTrainChunk) {
+        std::fill(acc, acc + len, 0.0f);
+        for (int64_t r = r0; r < std::min<int64_t>(B, r0 + kTrainChunk); ++r) term(r, acc);
+        for (int i = 0; i < len; ++i) total[i] = total[i] + acc[i];
+    }
+}
+
+}  // namespace
+
+extern "C" int gbl_cpu_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                                  float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out,
+                                  float *stats_out, void *workspace, int64_t workspace_bytes, void *)
+{
+    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    GBL_FP_STRICT
+    const int H = hidden;
+    const int64_t B = batch;
+    float *ws = static_cast<float *>(workspace);
+    const HostTrain A{obs, mask, visits, z, params, ws, ws + B * H, ws + 2 * B * H, ws + 2 * B * H + B * kTrainDoStride, H,
+                      TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
+                                 hyper->bias2}};
+    parallel_for(B, [=](int64_t r0, int64_t r1) {
+        for (int64_t r = r0; r < r1; ++r) train_row(A, r);
+    }, 64);
+    int N = 0;
+    for (int64_t r = 0; r < B; ++r) N += A.row[r * kTrainRowStats + 3] != 0.0f;
+    const float M = (float)(N > 0 ? N : 1);
+    // the segments of the parameter vector: the 117 rows of w1, b1, the H rows of w2, b2 -- each `len` neighbouring elements
+    const int at_b1 = kObs * H, at_w2 = at_b1 + H, at_b2 = at_w2 + kTrainOutputs * H;
+    parallel_for(kObs + 1 + H + 1, [=](int64_t s0, int64_t s1) {
+        GBL_FP_STRICT
+        float G[256];
+        for (int64_t seg = s0; seg < s1; ++seg) {
+            int at, len;
+            if (seg < kObs) {
+                const int f = (int)seg;
+                at = f * H; len = H;
+                train_sum(B, len, G, [&](int64_t r, float *acc) {
+                    if (A.obs[r * kObs + f] == 0) return;
+                    for (int j = 0; j < H; ++j) acc[j] = acc[j] + A.dh[r * H + j];
+                });
+            } else if (seg == kObs) {
+                at = at_b1; len = H;
+                train_sum(B, len, G, [&](int64_t r, float *acc) {
+                    for (int j = 0; j < H; ++j) acc[j] = acc[j] + A.dh[r * H + j];
+                });
+            } else if (seg <= kObs + H) {
+                const int j = (int)seg - kObs - 1;
+                at = at_w2 + j * kTrainOutputs; len = kTrainOutputs;
+                train_sum(B, len, G, [&](int64_t r, float *acc) {
+                    for (int k = 0; k < kTrainOutputs; ++k) acc[k] = acc[k] + A.h[r * H + j] * A.dout[r * kTrainDoStride + k];
+                });
+            } else {
+                at = at_b2; len = kTrainOutputs;
+                train_sum(B, len, G, [&](int64_t r, float *acc) {
+                    for (int k = 0; k < kTrainOutputs; ++k) acc[k] = acc[k] + A.dout[r * kTrainDoStride + k];
+                });
+            }
+            for (int i = 0; i < len; ++i) {
+                const float g = train_gradient(G[i], M, params[at + i], A.hy);
+                train_adam(g, params[at + i], adam_m[at + i], adam_v[at + i], A.hy);
+                if (grad_out) grad_out[at + i] = g;
+            }
+        }
+    }, 8);
+    float sums[2], top = 0.0f;
+    train_sum(B, 2, sums, [&](int64_t r, float *acc) {
+        GBL_FP_STRICT
+        acc[0] = acc[0] + A.row[r * kTrainRowStats];
+        acc[1] = acc[1] + A.row[r * kTrainRowStats + 1];
+    });
+    for (int64_t r = 0; r < B; ++r) {
+        const float t = A.row[r * kTrainRowStats + 2];
+        top = train_float_bits(t) > train_float_bits(top) ? t : top;
+    }
+    stats_out[0] = sums[0] / M; stats_out[1] = sums[1] / M; stats_out[2] = (float)N; stats_out[3] = top;
+    return GBL_OK;
+}

@@ -2646,4 +2646,142 @@ inline const char *batch_error(const void *obs_traj, const void *mask_traj, cons
     return nullptr;
 }
 
+// ---- gbl_train_step (include/gobblet_hip.h, "One Adam step of the FLOAT network"): the scalar pieces of the bit-defined rule ----------
+// Shared by k_train_rows / k_train_reduce_adam and the host flavour.  Every function that does float arithmetic for the rule opens
+// with GBL_FP_STRICT, and so do the two kernels and the host flavour's own loops (train_row, train_sum, gbl_cpu_train_step): hipcc
+// (and clang++ as a host compiler) must not contract a multiply and an add into an fma there -- the rule is single operations; g++
+// takes the same from -ffp-contract=off (CPU_CXX_FLAGS).  HIPCC_FLAGS stay as they are.
+#ifdef GBL_HOST_EMU
+#ifndef __host__
+#define __host__
+#endif
+#endif
+#define GBL_FP_STRICT _Pragma("clang fp contract(off)")
+
+constexpr int kTrainOutputs = 55;     // o_0 .. o_53: the action logits, o_54: the value
+constexpr int kTrainDoStride = 56;    // the workspace's do rows (element 55 is padding, written as 0)
+constexpr int kTrainRowStats = 4;     // the workspace's per-row record: lp, lv, the row's largest h, counted (1.0 / 0.0)
+constexpr int kTrainChunk = 64;       // rows per chunk of the row sums
+constexpr int64_t kTrainMaxBatch = 65536;
+
+struct TrainHyper {  // gbl_train_hyper, as the kernels take it (by value)
+    float lr, beta1, beta2, eps, weight_decay, value_reg, bias1, bias2;
+};
+
+inline bool train_hidden_ok(int h) { return h == 64 || h == 128 || h == 192 || h == 256; }
+constexpr int train_param_count(int h) { return (kObs + 1 + kTrainOutputs) * h + kTrainOutputs; }
+// floats of workspace: h [B][H], dh [B][H], do [B][56], the row records [B][4]
+inline int64_t train_workspace_bytes(int64_t batch, int hidden)
+{
+    if (batch < 1 || batch > kTrainMaxBatch || !train_hidden_ok(hidden)) return 0;
+    return 4 * batch * (2 * (int64_t)hidden + kTrainDoStride + kTrainRowStats);
+}
+
+inline const char *train_error(const void *obs, const void *visits, const void *z, int64_t batch, int hidden, const void *params,
+                               const void *adam_m, const void *adam_v, const void *hyper, const void *stats_out, const void *workspace,
+                               int64_t workspace_bytes)
+{
+    if (!train_hidden_ok(hidden)) return "hidden must be 64, 128, 192 or 256";
+    if (batch < 1 || batch > kTrainMaxBatch) return "batch must be in [1, 65536]";
+    if (!obs) return "obs must not be NULL";
+    if (!visits) return "visits must not be NULL";
+    if (!z) return "z must not be NULL";
+    if (!params) return "params must not be NULL";
+    if (!adam_m || !adam_v) return "adam_m / adam_v must not be NULL";
+    if (!hyper) return "hyper must not be NULL";
+    if (!stats_out) return "stats_out must not be NULL";
+    if (!workspace) return "workspace must not be NULL";
+    if (workspace_bytes < train_workspace_bytes(batch, hidden)) return "workspace_bytes is below gbl_train_workspace_bytes";
+    return nullptr;
+}
+
+__host__ __device__ __forceinline__ float train_bits_float(uint32_t u) { return __builtin_bit_cast(float, u); }
+__host__ __device__ __forceinline__ uint32_t train_float_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
+
+constexpr float kTrainLog2e = 0x1.715476p+0f, kTrainLn2Hi = 0x1.62e4p-1f, kTrainLn2Lo = 0x1.7f7d1cp-20f;
+
+// EXP of the header: x <= 0 (a NaN or anything below -110 is taken as -110, whose result is 0)
+__host__ __device__ __forceinline__ float train_exp(float x)
+{
+    GBL_FP_STRICT
+    x = x >= -110.0f ? x : -110.0f;
+    x = x <= 0.0f ? x : 0.0f;
+    const float t = x * kTrainLog2e;
+    const int32_t n = (int32_t)(t - 0.5f);
+    const float fn = (float)n;
+    const float r = (x - fn * kTrainLn2Hi) - fn * kTrainLn2Lo;
+    float q = 0x1.a01a02p-13f;
+    q = q * r; q = q + 0x1.6c16c2p-10f;
+    q = q * r; q = q + 0x1.111112p-7f;
+    q = q * r; q = q + 0x1.555556p-5f;
+    q = q * r; q = q + 0x1.555556p-3f;
+    q = q * r; q = q + 0x1p-1f;
+    float y = r * r;
+    y = y * q;
+    y = y + r;
+    y = y + 1.0f;
+    const int32_t n1 = n >> 1, n2 = n - n1;
+    y = y * train_bits_float((uint32_t)(n1 + 127) << 23);
+    return y * train_bits_float((uint32_t)(n2 + 127) << 23);
+}
+
+// LOG of the header: s >= 1 and finite (anything else gives an unspecified float, never a fault)
+__host__ __device__ __forceinline__ float train_log(float s)
+{
+    GBL_FP_STRICT
+    const uint32_t u = train_float_bits(s);
+    int32_t e = (int32_t)(u >> 23) - 127;
+    const uint32_t mant = u & 0x7FFFFFu;
+    const bool upper = mant > 0x3504F3u;
+    e += upper ? 1 : 0;
+    const float w = train_bits_float(mant | (upper ? 0x3F000000u : 0x3F800000u));
+    const float f = w - 1.0f;
+    const float q = f / (2.0f + f);
+    const float y = q * q;
+    float R = 0x1.c71c72p-3f;
+    R = R * y; R = R + 0x1.24924ap-2f;
+    R = R * y; R = R + 0x1.99999ap-2f;
+    R = R * y; R = R + 0x1.555556p-1f;
+    R = R * y;
+    const float hf = (0.5f * f) * f;
+    const float T = q * (hf + R);
+    const float dk = (float)e;
+    return (((T + dk * kTrainLn2Lo) - hf) + f) + dk * kTrainLn2Hi;
+}
+
+// the value column of a counted row: the loss term lv and do_54
+__host__ __device__ __forceinline__ void train_value(float v, int z, float value_reg, float &lv, float &dv)
+{
+    GBL_FP_STRICT
+    const float c = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
+    const float u = c - (float)z;
+    lv = u * u + value_reg * (v * v);
+    dv = 2.0f * (v > -1.0f && v < 1.0f ? u : 0.0f) + 2.0f * (value_reg * v);
+}
+
+// one action of a counted row's candidate set: do_a and its term of the policy loss
+__host__ __device__ __forceinline__ void train_policy(float e, float s, float d, float L, int visits, int S, float &da, float &term)
+{
+    GBL_FP_STRICT
+    const float t = (float)visits / (float)S;
+    da = e / s - t;
+    term = t * (L - d);
+}
+
+// g of the header from a row sum, and Adam on one element
+__host__ __device__ __forceinline__ float train_gradient(float G, float M, float theta, const TrainHyper &hy)
+{
+    GBL_FP_STRICT
+    return G / M + hy.weight_decay * theta;
+}
+
+__host__ __device__ __forceinline__ void train_adam(float g, float &theta, float &m, float &v, const TrainHyper &hy)
+{
+    GBL_FP_STRICT
+    m = hy.beta1 * m + (1.0f - hy.beta1) * g;
+    v = hy.beta2 * v + (1.0f - hy.beta2) * (g * g);
+    const float root = __builtin_sqrtf(v / hy.bias2);  // (correctly rounded on either side: hipcc's default for fp32 divide and sqrt)
+    theta = theta - (hy.lr * (m / hy.bias1)) / (root + hy.eps);
+}
+
 }  // namespace gbl

@@ -2488,6 +2488,248 @@ __global__ __launch_bounds__(64) void k_training_batch(BatchArgs A)
     }
 }
 
+// gbl_train_step: the float trainer's Adam step in two launches, bit-defined by the header (every float operation below is the
+// header's, in its order; GBL_FP_STRICT keeps hipcc from fusing them).
+//   k_train_rows          one wavefront per row (four per workgroup, rows dealt grid-stride), w2 staged in LDS once per workgroup:
+//                         forward, softmax, losses, do and dh of the row, left in the workspace.
+//   k_train_reduce_adam   64 parameter elements per workgroup, one per lane; its 16 wavefronts take the 64-row chunks round robin,
+//                         wavefront 0 adds the chunk sums in ascending order, forms g and applies Adam.  The last workgroup's spare
+//                         lanes reduce the loss terms and the hidden maximum for stats_out.
+struct TrainArgs {
+    const int8_t *obs, *mask;
+    const int16_t *visits;
+    const int8_t *z;
+    float *params, *adam_m, *adam_v, *grad_out, *stats_out;
+    float *ws_h, *ws_dh, *ws_do, *ws_row;
+    int64_t batch;
+    int hidden;
+    TrainHyper hy;
+};
+
+constexpr int kTrainRowWaves = 4;                       // wavefronts (rows in flight) per workgroup of k_train_rows
+constexpr int kTrainRowScratch = 4 * kTrainDoStride;    // per wavefront beside h: o, e, the loss terms, do
+constexpr int kTrainReduceWaves = 16;
+
+inline size_t train_rows_lds(int hidden)
+{
+    return sizeof(float) * ((size_t)hidden * kTrainOutputs + kTrainRowWaves * ((size_t)hidden + kTrainRowScratch));
+}
+
+// the set bits of a wavefront-uniform mask in ascending order
+template <typename F>
+__device__ __forceinline__ void each_bit(uint64_t bits, F f)
+{
+    while (bits) {
+        f(__builtin_ctzll(bits));
+        bits &= bits - 1;
+    }
+}
+
+template <int U>  // U = H / 64: hidden units per lane
+__global__ __launch_bounds__(64 * kTrainRowWaves) void k_train_rows(TrainArgs A)
+{
+    GBL_FP_STRICT
+    constexpr int H = 64 * U;
+    extern __shared__ __align__(16) float s_train[];  // w2 [H][55]; then per wavefront h [H], o / e / terms / do [56] each
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    float *w2s = s_train;
+    float *sh = s_train + H * kTrainOutputs + wave * (H + kTrainRowScratch);
+    float *so = sh + H, *se = so + kTrainDoStride, *st = se + kTrainDoStride, *sd = st + kTrainDoStride;
+    const float *__restrict__ w1 = A.params, *__restrict__ b1 = w1 + kObs * H, *__restrict__ w2 = b1 + H,
+                *__restrict__ b2 = w2 + H * kTrainOutputs;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(H * kTrainOutputs); i += 64u * kTrainRowWaves) w2s[i] = w2[i];
+    __syncthreads();  // (the only rendezvous: from here the wavefronts share nothing but the read-only w2)
+    for (int64_t r = (int64_t)blockIdx.x * kTrainRowWaves + wave; r < A.batch; r += (int64_t)gridDim.x * kTrainRowWaves) {
+        float *rh = A.ws_h + r * H, *rdh = A.ws_dh + r * H, *rdo = A.ws_do + r * kTrainDoStride, *rst = A.ws_row + r * kTrainRowStats;
+        const bool action = lane < (uint32_t)kActions;
+        const bool in_c = action && (!A.mask || A.mask[r * kActions + lane] != 0);
+        const uint64_t cand = __ballot(in_c);
+        const int vis = in_c ? (int)A.visits[r * kActions + lane] : 0;
+        const int S = (int)wave_sum((uint32_t)vis);
+        const int z = A.z[r];
+        if (z == kZOpen || S <= 0) {  // (uniform) an uncounted row: zeros everywhere
+#pragma unroll
+            for (int u = 0; u < U; ++u) rh[lane + 64 * u] = rdh[lane + 64 * u] = 0.0f;
+            if (lane < (uint32_t)kTrainDoStride) rdo[lane] = 0.0f;
+            if (lane < (uint32_t)kTrainRowStats) rst[lane] = 0.0f;
+            continue;
+        }
+        // layer 1: the w1 rows of the set bytes, ascending
+        const uint64_t set0 = __ballot(A.obs[r * kObs + lane] != 0);
+        const uint64_t set1 = __ballot(lane + 64u < (uint32_t)kObs && A.obs[r * kObs + (lane + 64u < (uint32_t)kObs ? lane + 64u : 0u)] != 0);
+        float pre[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) pre[u] = b1[lane + 64 * u];
+        each_bit(set0, [&](int f) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) pre[u] = pre[u] + w1[f * H + lane + 64 * u];
+        });
+        each_bit(set1, [&](int f) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) pre[u] = pre[u] + w1[(f + 64) * H + lane + 64 * u];
+        });
+        uint32_t top = 0u;  // (the bits of non-negative floats order as the floats do)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float h = pre[u] > 0.0f ? pre[u] : 0.0f;
+            sh[lane + 64 * u] = rh[lane + 64 * u] = h;
+            top = train_float_bits(h) > top ? train_float_bits(h) : top;
+        }
+        top = wave_max(top);
+        wave_lds_fence();
+        // layer 2: lane k owns o_k
+        float o = 0.0f;
+        if (lane < (uint32_t)kTrainOutputs) {
+            o = b2[lane];
+            for (int j = 0; j < H; ++j) o = o + sh[j] * w2s[j * kTrainOutputs + lane];
+        }
+        if (lane < (uint32_t)kTrainDoStride) so[lane] = o;
+        wave_lds_fence();
+        // the softmax over C: every lane walks the candidates in ascending order (the sums have ONE order), lane a keeps its own e_a
+        float mx = so[__builtin_ctzll(cand)];
+        each_bit(cand & (cand - 1), [&](int a) {
+            const float v = so[a];
+            mx = v > mx ? v : mx;
+        });
+        const float d = o - mx;
+        const float e = in_c ? train_exp(d) : 0.0f;
+        if (lane < (uint32_t)kTrainDoStride) se[lane] = e;
+        wave_lds_fence();
+        float s = 0.0f;
+        each_bit(cand, [&](int a) { s = s + se[a]; });
+        const float L = train_log(s);
+        float g = 0.0f, term = 0.0f, lv = 0.0f;
+        if (in_c) train_policy(e, s, d, L, vis, S, g, term);
+        if (lane == (uint32_t)kActions) train_value(o, z, A.hy.value_reg, lv, g);
+        if (lane < (uint32_t)kTrainDoStride) {
+            st[lane] = term;
+            sd[lane] = g;
+            rdo[lane] = g;
+        }
+        wave_lds_fence();
+        float lp = 0.0f;
+        each_bit(cand, [&](int a) { lp = lp + st[a]; });
+        if (lane == 0u) {
+            rst[0] = lp;
+            rst[2] = train_bits_float(top);
+            rst[3] = 1.0f;
+        }
+        if (lane == (uint32_t)kActions) rst[1] = lv;
+        // backward through layer 2: lane j owns dh_j
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = (int)lane + 64 * u;
+            float acc = 0.0f;
+            for (int k = 0; k < kTrainOutputs; ++k) acc = acc + sd[k] * w2s[j * kTrainOutputs + k];
+            rdh[j] = pre[u] > 0.0f ? acc : 0.0f;
+        }
+        wave_lds_fence();  // (every lane has read this row's LDS before the next row overwrites it)
+    }
+}
+
+// rows [r0, r1) of one chunk, ascending, for the lane's element.  KIND 0: an element of w1 (x points at the rows' byte f);
+// 1: a plain column (b1, b2, the loss terms); 2: an element of w2 (a product of two columns)
+template <int KIND>
+__device__ __forceinline__ float train_chunk_sum(const float *__restrict__ a, int64_t stride_a, const float *__restrict__ b,
+                                                 const int8_t *__restrict__ x, int64_t r0, int64_t r1)
+{
+    GBL_FP_STRICT
+    float acc = 0.0f;
+#pragma unroll 8
+    for (int64_t r = r0; r < r1; ++r) {
+        if (KIND == 0) {
+            if (x[r * kObs] != 0) acc = acc + a[r * stride_a];
+        } else if (KIND == 1) {
+            acc = acc + a[r * stride_a];
+        } else {
+            acc = acc + a[r * stride_a] * b[r * kTrainDoStride];
+        }
+    }
+    return acc;
+}
+
+// the larger of two non-negative floats, on their bits (which order as the floats do)
+__device__ __forceinline__ float train_max(float a, float b) { return train_float_bits(b) > train_float_bits(a) ? b : a; }
+
+__global__ __launch_bounds__(64 * kTrainReduceWaves) void k_train_reduce_adam(TrainArgs A)
+{
+    GBL_FP_STRICT
+    __shared__ float s_part[kTrainReduceWaves][64];
+    __shared__ int s_count[kTrainReduceWaves];
+    const int H = A.hidden, P = train_param_count(H);
+    const int64_t B = A.batch;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int first = (int)blockIdx.x * 64, e = first + (int)lane;  // this workgroup's elements; first is a multiple of 64
+    // N, the counted rows (an integer count: any order)
+    int mine = 0;
+    for (int64_t r = threadIdx.x; r < B; r += 64 * kTrainReduceWaves) mine += A.ws_row[r * kTrainRowStats + 3] != 0.0f;
+    mine = (int)wave_sum((uint32_t)mine);
+    if (lane == 0u) s_count[wave] = mine;
+    __syncthreads();
+    int N = 0;
+#pragma unroll
+    for (int w = 0; w < kTrainReduceWaves; ++w) N += s_count[w];
+    // what this lane sums.  The regions w1 / b1 / w2 begin at multiples of 64 elements (H is one), so a workgroup lies in ONE
+    // region -- except the last, which holds b2 and, in its spare lanes, the two loss terms and the hidden maximum
+    const int at_b1 = kObs * H, at_w2 = at_b1 + H, at_b2 = at_w2 + kTrainOutputs * H;
+    const int region = first < at_b1 ? 0 : first < at_w2 ? 1 : first < at_b2 ? 2 : 3;  // (uniform)
+    const float *a = A.ws_row, *b = A.ws_do;
+    const int8_t *x = A.obs;
+    int64_t stride = 0;  // (a spare lane past the statistics sums the first row's lp with stride 0 and drops it)
+    if (region == 0) {
+        const int f = first / H;
+        x = A.obs + f; a = A.ws_dh + (e - f * H); stride = H;
+    } else if (region == 1) {
+        a = A.ws_dh + (e - at_b1); stride = H;
+    } else if (region == 2) {
+        const int j = (e - at_w2) / kTrainOutputs, k = (e - at_w2) - j * kTrainOutputs;
+        a = A.ws_h + j; b = A.ws_do + k; stride = H;
+    } else if (e < P) {
+        a = A.ws_do + (e - at_b2); stride = kTrainDoStride;
+    } else if (e < P + 3) {
+        a = A.ws_row + (e - P); stride = kTrainRowStats;
+    }
+    const bool is_max = e == P + 2;
+    const int64_t chunks = (B + kTrainChunk - 1) / kTrainChunk;
+    float total = 0.0f;
+    for (int64_t c0 = 0; c0 < chunks; c0 += kTrainReduceWaves) {
+        const int64_t c = c0 + wave, r0 = c * kTrainChunk, r1 = r0 + kTrainChunk < B ? r0 + kTrainChunk : B;
+        float acc = 0.0f;
+        if (c < chunks) {
+            if (region == 0) acc = train_chunk_sum<0>(a, stride, b, x, r0, r1);
+            else if (region == 1) acc = train_chunk_sum<1>(a, stride, b, x, r0, r1);
+            else if (region == 2) acc = train_chunk_sum<2>(a, stride, b, x, r0, r1);
+            else if (!is_max) acc = train_chunk_sum<1>(a, stride, b, x, r0, r1);
+            else
+                for (int64_t r = r0; r < r1; ++r) acc = train_max(acc, a[r * stride]);
+        }
+        s_part[wave][lane] = acc;
+        __syncthreads();
+        if (wave == 0u) {
+            const int live = chunks - c0 < kTrainReduceWaves ? (int)(chunks - c0) : kTrainReduceWaves;
+            for (int w = 0; w < live; ++w) {
+                const float p = s_part[w][lane];
+                total = is_max ? train_max(total, p) : total + p;
+            }
+        }
+        __syncthreads();  // (wavefront 0 has read the chunk sums before the next round overwrites them)
+    }
+    if (wave != 0u) return;
+    const float M = (float)(N > 0 ? N : 1);
+    if (e < P) {
+        float theta = A.params[e], m = A.adam_m[e], v = A.adam_v[e];
+        const float g = train_gradient(total, M, theta, A.hy);
+        train_adam(g, theta, m, v, A.hy);
+        A.params[e] = theta; A.adam_m[e] = m; A.adam_v[e] = v;
+        if (A.grad_out) A.grad_out[e] = g;
+    } else if (e < P + 2) {
+        A.stats_out[e - P] = total / M;
+    } else if (is_max) {
+        A.stats_out[2] = (float)N;
+        A.stats_out[3] = total;
+    }
+}
+
 // gbl_solve: the exact solver, one wavefront per board (a grid-stride loop over boards), three phases per board:
 //   1. lane a < 54 plays root action a and, unless that decides it, every reply once (solve_root_action): depths 1 and 2 end here,
 //      and so does every action with a reply that wins at once.  What is left of an action are its QUIET replies;
@@ -4288,6 +4530,40 @@ int gbl_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const in
                       n, ply_stride, tile_stride, batch, g.ntiles, seed, sample_base, plies, call, (uint32_t)sym_mask};
     hipLaunchKernelGGL(k_training_batch, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
     GBL_LAUNCHED("gbl_training_batch");
+}
+
+int64_t gbl_train_workspace_bytes(int64_t batch, int hidden) { return train_workspace_bytes(batch, hidden); }
+
+int gbl_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                   float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
+                   void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    GBL_ALIGNED(obs, "obs"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(visits, "visits"); GBL_ALIGNED(params, "params");
+    GBL_ALIGNED(adam_m, "adam_m"); GBL_ALIGNED(adam_v, "adam_v"); GBL_ALIGNED(grad_out, "grad_out"); GBL_ALIGNED(stats_out, "stats_out");
+    GBL_ALIGNED(workspace, "workspace");
+    float *ws = static_cast<float *>(workspace);
+    const TrainArgs A{obs, mask, visits, z, params, adam_m, adam_v, grad_out, stats_out,
+                      ws, ws + batch * hidden, ws + 2 * batch * hidden, ws + 2 * batch * hidden + batch * kTrainDoStride, batch, hidden,
+                      TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
+                                 hyper->bias2}};
+    // as many workgroups as stay resident on 256 CUs, at most one per four rows: 4 / 4 / 3 / 2 per CU at H = 64 / 128 / 192 / 256, the
+    // smaller of what the registers allow (127 / 127 / 168 / 212 VGPRs: 4 / 4 / 3 / 2 wavefronts per SIMD, a workgroup being one wavefront on
+    // each SIMD) and what the LDS allows (w2 and four rows' scratch: 18 / 33 / 48 / 63 KB of 160)
+    const int units = hidden / 64;
+    const int64_t resident = 256 * (int64_t)(units <= 2 ? 4 : units == 3 ? 3 : 2);
+    const dim3 rows_grid((uint32_t)std::min<int64_t>((batch + kTrainRowWaves - 1) / kTrainRowWaves, resident)), rows_block(64 * kTrainRowWaves);
+    const size_t lds = train_rows_lds(hidden);
+    hipStream_t s = (hipStream_t)stream;
+    if (units == 1) hipLaunchKernelGGL(k_train_rows<1>, rows_grid, rows_block, lds, s, A);
+    else if (units == 2) hipLaunchKernelGGL(k_train_rows<2>, rows_grid, rows_block, lds, s, A);
+    else if (units == 3) hipLaunchKernelGGL(k_train_rows<3>, rows_grid, rows_block, lds, s, A);
+    else hipLaunchKernelGGL(k_train_rows<4>, rows_grid, rows_block, lds, s, A);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_train_step");
+    const uint32_t tiles = (uint32_t)((train_param_count(hidden) + 3 + 63) / 64);  // (+ 3: the statistics' lanes)
+    hipLaunchKernelGGL(k_train_reduce_adam, dim3(tiles), dim3(64 * kTrainReduceWaves), 0, s, A);
+    GBL_LAUNCHED("gbl_train_step");
 }
 
 }  // extern "C"

@@ -671,6 +671,62 @@ int gbl_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const in
                        int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out,
                        void *stream);
 
+/* One Adam step of the FLOAT network that GobbletEvaluator.from_float quantises (no counterpart in the reference), on a batch shaped
+ * as gbl_training_batch writes it:  h = relu(x w1 + b1),  o = h w2 + b2.  The rule is BIT-DEFINED: every operation below is ONE
+ * IEEE-754 binary32 multiply, add, subtract, divide or square root, correctly rounded (no fused multiply-add, no reciprocal or
+ * rsqrt approximation, denormals kept), in the order written, so that the kernels, the host flavour and a numpy-float32 restatement
+ * of this text agree bit for bit.  Two launches, no atomics, allocates nothing.
+ *   Inputs.  obs int8 [B][117], a byte counts as 1 wherever it is non-zero; mask int8 [B][54] (NULL: all 54 actions), C_r = {a :
+ *     mask[r][a] != 0}; visits int16 [B][54]; z int8 [B].  1 <= B <= 65 536.  S_r = the integer sum of visits[r][a] over C_r.  Row r
+ *     COUNTS iff z[r] != GBL_Z_OPEN and S_r > 0 (a sample gbl_training_batch could not draw counts for nothing).  An uncounted row
+ *     has h = dh = do = 0 and both loss terms 0 below.  N = the number of counted rows, M = max(N, 1) as a float.
+ *   Parameters.  params float [P], P = 117 H + H + 55 H + 55, in the order w1[117][H], b1[H], w2[H][55], b2[55] (from_float's
+ *     shapes); adam_m and adam_v float [P] alike.  H is 64, 128, 192 or 256.
+ *   Forward of a counted row (ascending means: an accumulator that starts with the first value named and takes one add per term).
+ *     pre_j = b1_j, then + w1[f][j] for every f with x_f = 1, f ascending            h_j = pre_j > 0 ? pre_j : 0
+ *     o_k   = b2_k, then + h_j * w2[j][k] for j = 0 .. H - 1 ascending               k = 0 .. 54
+ *     mx    = o_a of the first a in C, then for the other a in C ascending: mx = o_a > mx ? o_a : mx
+ *     d_a   = o_a - mx,  e_a = EXP(d_a)  (a in C);   s = 0, then + e_a for a in C ascending;   L = LOG(s)
+ *     t_a   = float(visits_a) / float(S),  p_a = e_a / s
+ *     policy loss  lp = 0, then + t_a * (L - d_a) for a in C ascending               (the log-sum form of -sum t log p)
+ *     v = o_54,  c = v < -1 ? -1 : (v > 1 ? 1 : v),  u = c - float(z)
+ *     value loss   lv = u * u + value_reg * (v * v)
+ *   Backward.  do_a = p_a - t_a (a in C), 0 for the other a < 54;  do_54 = 2 * (-1 < v < 1 ? u : 0) + 2 * (value_reg * v);
+ *     dh_j = pre_j > 0 ? (0, then + do_k * w2[j][k] for k = 0 .. 54 ascending) : 0.
+ *   Row sums.  Rows are summed in CHUNKS of 64: chunk c holds rows 64 c .. min(64 c + 63, B - 1).  SUM(term) = 0, then + the chunk
+ *     sums for c ascending, each chunk sum = 0, then + term_r for its rows ascending.
+ *       G(w1[f][j]) = SUM(dh_j of the rows with x_f = 1; the other rows add nothing)     G(b1_j) = SUM(dh_j)
+ *       G(w2[j][k]) = SUM(h_j * do_k)                                                    G(b2_k) = SUM(do_k)
+ *     gradient  g = G / M + weight_decay * theta        (torch Adam's L2 form)
+ *   Adam, per element, with hy = *hyper:
+ *     m' = beta1 * m + (1 - beta1) * g        v' = beta2 * v + (1 - beta2) * (g * g)        (1 - beta is one float subtraction)
+ *     theta' = theta - (lr * (m' / bias1)) / (sqrt(v' / bias2) + eps)
+ *     The caller computes bias1 = 1 - beta1^t and bias2 = 1 - beta2^t (t = 1, 2, ... the step) in double and passes them as floats.
+ *   EXP(x), x <= 0:  x = max(x, -110);  n = int(x * LOG2E - 0.5) (the cast truncates);  r = (x - n * LN2_HI) - n * LN2_LO;
+ *     q = C7, then q = q * r + C_i for i = 6 .. 2 (two operations each);  y = ((r * r) * q + r) + 1;  n1 = n >> 1, n2 = n - n1;
+ *     EXP = (y * 2^n1) * 2^n2, the powers of two built from their exponent bits.  LOG2E = 0x1.715476p+0, LN2_HI = 0x1.62e4p-1,
+ *     LN2_LO = 0x1.7f7d1cp-20, C2 .. C7 = 0x1p-1 0x1.555556p-3 0x1.555556p-5 0x1.111112p-7 0x1.6c16c2p-10 0x1.a01a02p-13.
+ *   LOG(s), s >= 1 (here s <= 54):  s = 2^e * w with the mantissa w in [1, 2); if w's 23 mantissa bits exceed 0x3504f3 (sqrt 2)
+ *     then w = w / 2, e = e + 1 (on the bits);  f = w - 1,  q = f / (2 + f),  y = q * q;
+ *     R = D4, then R = R * y + D_i for i = 3 .. 1, then R = R * y;  hf = (0.5 * f) * f;  T = q * (hf + R);
+ *     LOG = (((T + e * LN2_LO) - hf) + f) + e * LN2_HI.  D1 .. D4 = 0x1.555556p-1 0x1.99999ap-2 0x1.24924ap-2 0x1.c71c72p-3.
+ *     (Measured over 2^20 evenly spaced arguments and the range edges, and asserted as the bound by tests/test_train_step.py:
+ *      EXP is within 0.99491 ulp on [-104, 0], LOG within 0.74746 ulp on [1, 54].)
+ *   Outputs.  params, adam_m, adam_v updated in place; grad_out float [P] (may be NULL): g;  stats_out float [4]: SUM(lp) / M,
+ *     SUM(lv) / M, float(N), and the largest h_j over the counted rows (0 without one: what from_float takes as hidden_max).
+ *   Workspace.  The caller supplies gbl_train_workspace_bytes bytes (4 B (2 H + 60); it holds h, dh, do and the loss terms of
+ *     every row between the two launches); that function returns 0 for a batch or hidden out of range and launches nothing.
+ * Argument errors (GBL_ERR_ARG): hidden or batch out of range, a missing pointer (all but mask and grad_out are required), a
+ * workspace_bytes that is too small.  GBL_ERR_ALIGN: obs, mask, visits, the float arrays and the workspace must be 16-byte
+ * aligned (the host flavour asks no alignment). */
+typedef struct {
+    float lr, beta1, beta2, eps, weight_decay, value_reg, bias1, bias2;
+} gbl_train_hyper;
+int64_t gbl_train_workspace_bytes(int64_t batch, int hidden);
+int gbl_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                   float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
  *   GBL_COLLECT_STREAM  k_collect,  one wavefront per tile of 64 boards, trajectory rows stored non-temporally
