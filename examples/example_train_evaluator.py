@@ -3,7 +3,7 @@
 evaluator -> the evaluator-guided search against the playout search at equal iterations; with --generations G > 1 the loop goes
 round: generation k collects with generation k - 1's evaluator on both sides INSIDE one launch (gbl_collect_search_eval), fits a
 new network and plays it against the old one, one launch per colour:
-    python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G] [--generations G]
+    python examples/example_train_evaluator.py [device] [--boards N] [--plies T] [--steps S] [--hidden H] [--games G] [--generations G] [--noise X]
 --augment square|all draws every Adam step's batch on the device under random board symmetries (BatchedGobblet.training_batch) and
 fits there; the default (none) keeps the whole window on the host as before.  --fit device (with --augment) runs every Adam step on
 the device too: BatchedGobblet.fit with a GobbletTrainer, two launches of gbl_train_step per step instead of torch's few dozen, and the
@@ -36,13 +36,14 @@ def targets_of(traj, boards, plies):
     return obs[keep].float().cpu(), pi[keep].cpu(), z[keep].float().cpu()
 
 
-def collect_targets_with(ev, device, boards, plies, iterations, seed=0, solve_depth=0):
+def collect_targets_with(ev, device, boards, plies, iterations, seed=0, solve_depth=0, noise=0.0):
     """collect_targets with the evaluator-guided search of `ev` on both sides, the first four plies of every game drawn in proportion
     to the visits: one launch for the whole window.  solve_depth > 0: the exact solver in front of every search (a proven win is
-    taken, a proven loss avoided, and such a ply's policy target is one-hot)."""
+    taken, a proven loss avoided, and such a ply's policy target is one-hot).  noise > 0: that share of a random row is mixed into
+    the root's priors of every search, so that the search also looks at what the network rates low (the arena never does this)."""
     env = G.BatchedGobblet(boards, device, auto_reset=True, seed=seed, track_turn=True)
     traj = env.collect(plies, policies=("evaluator", "evaluator"),
-                       search=dict(evaluator=ev, iterations=iterations, sample_plies=4, solve_depth=solve_depth))
+                       search=dict(evaluator=ev, iterations=iterations, sample_plies=4, solve_depth=solve_depth, noise=noise))
     env.outcome_targets(traj)
     return targets_of(traj, boards, plies)
 
@@ -162,6 +163,8 @@ if __name__ == "__main__":
     ap.add_argument("--selfplay-iterations", type=int, default=64, help="iterations of the evaluator search in generations >= 2")
     ap.add_argument("--solve-depth", type=int, default=0,
                     help="guard the self-play of generations >= 2 with the exact solver at this depth (0: none)")
+    ap.add_argument("--noise", type=float, default=0.0,
+                    help="share in [0, 1] of root exploration noise in the self-play of generations >= 2 (0: none; never in the arena)")
     ap.add_argument("--augment", choices=("none", "square", "all"), default="none",
                     help="draw every step's batch on the device under random board symmetries (generation 1)")
     ap.add_argument("--fit", choices=("torch", "device"), default="torch",
@@ -174,7 +177,8 @@ if __name__ == "__main__":
     w, l, d = score(ev, a.device, a.iterations, a.games)
     print("evaluator search vs playout search at %d iterations: %d wins, %d losses, %d unfinished of %d games" % (a.iterations, w, l, d, w + l + d))
     for gen in range(2, a.generations + 1):
-        obs, pi, z = collect_targets_with(ev, a.device, a.boards, a.plies, a.selfplay_iterations, seed=gen, solve_depth=a.solve_depth)
+        obs, pi, z = collect_targets_with(ev, a.device, a.boards, a.plies, a.selfplay_iterations, seed=gen, solve_depth=a.solve_depth,
+                                          noise=a.noise)
         weights, hmax, loss = fit(obs, pi, z, a.hidden, a.steps, seed=gen)
         new = G.GobbletEvaluator.from_float(*weights, hidden_max=hmax, device=a.device)
         w, l, n = arena_in_one_launch(new, ev, a.device, a.games, a.plies, a.selfplay_iterations)

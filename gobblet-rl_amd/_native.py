@@ -37,6 +37,7 @@ POLICY_TREE, HOW_SEARCH, HOW_SEARCH_SAMPLED, Z_OPEN = 4, 3, 4, -128  # gbl_colle
 POLICY_EVAL_TREE = 5  # gbl_collect_search_eval
 SOLVE_MAX_DEPTH, SOLVE_NONE = 6, -128  # gbl_solve
 HOW_PROVEN = 5  # gbl_collect_search_solve
+STREAM_NOISE, NOISE_MAX_WEIGHT = 6, 256  # gbl_tree_search_eval_noise / gbl_collect_search_noise
 SYMMETRIES, BATCH_ATTEMPTS = 512, 16  # gbl_symmetry_apply / gbl_training_batch
 STATUS_ILLEGAL, STATUS_OUT_OF_RANGE = 1, 2  # gbl_step_ex / gbl_collect_from_ex status bits
 CELLS, ACTIONS, OBS_BYTES = 27, 54, 117
@@ -78,6 +79,7 @@ SIGNATURES = {
     "gbl_tree_search": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_evaluate": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_tree_search_eval": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gbl_tree_search_eval_noise": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _u64, _u64, _u32] + [_vp] * 8 + [_i64, _vp]),
     "gbl_solve": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp]),
     "gbl_counter_add": (_int, [_vp, _u32, _vp]),
     "gbl_collect": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32,
@@ -90,6 +92,8 @@ SIGNATURES = {
     "gbl_collect_search_eval": (_int, [_vp] * 17 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 5 +
                                 [_vp, _vp, _vp]),
     "gbl_collect_search_solve": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 7 +
+                                 [_vp, _vp, _vp]),
+    "gbl_collect_search_noise": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
                                  [_vp, _vp, _vp]),
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_symmetry_apply": (_int, [_vp, _int, _vp] + [_vp] * 12 + [_i64, _vp]),

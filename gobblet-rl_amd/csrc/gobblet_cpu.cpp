@@ -832,13 +832,23 @@ int gbl_cpu_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *m
 }
 
 // One board's evaluator-guided search (the contract of gbl_tree_search_eval, one iteration at a time): HostSearch as
-// host_tree_search, and the root's q; pri[0 .. 53] is the root's prior row.
+// host_tree_search, and the root's q; pri[0 .. 53] is the row the root keeps (pi' where there is noise, else the network's row).
+struct HostNoise {  // the root noise of one search (w == 0: none); root_pi: where the network's row goes (NULL: nowhere)
+    uint32_t w;
+    uint64_t seed, g;
+    uint32_t q;
+    uint8_t *root_pi;
+};
+
 static int32_t host_tree_search_eval(std::vector<TreeNode> &nodes, std::vector<uint8_t> &pri, const EvalNet &net, const Planes &root,
-                                     int mover, uint64_t cand, uint32_t iterations, uint32_t explore, HostSearch &out)
+                                     int mover, uint64_t cand, uint32_t iterations, uint32_t explore, HostSearch &out,
+                                     const HostNoise &noise = HostNoise{})
 {
     int32_t o[kEvalOutputs];
     nodes[0] = TreeNode{};
     const int32_t root_q = host_evaluate(net, root, mover, cand, pri.data(), o);
+    if (noise.root_pi) memcpy(noise.root_pi, pri.data(), kActions);
+    if (noise.w && cand) noise_priors(noise.seed, noise.g, noise.q, noise.w, cand, pri.data(), pri.data());
     uint32_t count = 1;
     for (uint32_t i = 0; cand && i < iterations; ++i) {
         TreeEvalLeaf s = tree_eval_select(nodes.data(), pri.data(), root, mover, cand, explore);
@@ -858,9 +868,10 @@ static int32_t host_tree_search_eval(std::vector<TreeNode> &nodes, std::vector<u
     return root_q;
 }
 
-int gbl_cpu_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
-                             int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
-                             int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *)
+static int host_tree_search_eval_run(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                                     int explore, int noise, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out,
+                                     int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
+                                     int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
     if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
@@ -875,17 +886,40 @@ int gbl_cpu_tree_search_eval(const int8_t *state, const int8_t *to_move, const i
         HostSearch h;
         for (int64_t b = b0; b < b1; ++b) {
             const HostRoot R = host_root(state, to_move, mask, b);
-            const int32_t q = host_tree_search_eval(nodes, pri, net, R.p, R.mover, R.cand, (uint32_t)iterations, (uint32_t)explore, h);
+            const int32_t q = host_tree_search_eval(nodes, pri, net, R.p, R.mover, R.cand, (uint32_t)iterations, (uint32_t)explore, h,
+                                                    HostNoise{(uint32_t)noise, seed, env_base + (uint64_t)b, call,
+                                                              root_priors_out ? root_priors_out + b * kActions : nullptr});
             if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
             if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
             if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
             if (action_out) action_out[b] = tree_action_of(h.best);
             if (nodes_out) nodes_out[b] = (int32_t)h.count;
             if (root_value_out) root_value_out[b] = q;
-            if (root_priors_out) memcpy(root_priors_out + b * kActions, pri.data(), kActions);
+            if (root_mixed_out) memcpy(root_mixed_out + b * kActions, pri.data(), kActions);
         }
     }, 1);
     return GBL_OK;
+}
+
+int gbl_cpu_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                             int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                             int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *)
+{
+    return host_tree_search_eval_run(state, to_move, mask, ev, iterations, explore, 0, 0, 0, 0, visits_out, wins_out, losses_out, action_out,
+                                     nodes_out, root_value_out, root_priors_out, nullptr, n);
+}
+
+int gbl_cpu_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                                   int explore, int noise, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out,
+                                   int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
+                                   int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = noise_error(noise)) return fail(GBL_ERR_ARG, why);
+    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    return host_tree_search_eval_run(state, to_move, mask, ev, iterations, explore, noise, seed, env_base, call, visits_out, wins_out,
+                                     losses_out, action_out, nodes_out, root_value_out, root_priors_out, root_mixed_out, n);
 }
 
 int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *hist, int32_t *actions_traj, int8_t *winner_traj,
@@ -1147,24 +1181,27 @@ int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, in
     return GBL_OK;
 }
 
-int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+static int host_collect_solve_run(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                  int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                                  int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
                                  int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
                                  int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
                                  const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
-                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
-                                 int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
+                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1,
+                                 int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
     if (const char *why = collect_solve_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, solve_depth0, solve_depth1,
                                               explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
         return fail(GBL_ERR_ARG, why);
+    if ((policy0 == GBL_POLICY_EVAL_TREE && noise_error(noise0)) || (policy1 == GBL_POLICY_EVAL_TREE && noise_error(noise1)))
+        return fail(GBL_ERR_ARG, "noise0 / noise1 must be in [0, 256]");
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;
     const gbl_evaluator *evs[2] = {ev0, ev1};
-    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1}, deps[2] = {solve_depth0, solve_depth1};
+    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1}, deps[2] = {solve_depth0, solve_depth1},
+              nz[2] = {noise0, noise1};
     EvalNet nets[2] = {};
     int most = 0;
     for (int m = 0; m < 2; ++m) {
@@ -1181,8 +1218,9 @@ int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, i
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a solve and a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)most + 1);
         std::vector<uint8_t> pri(((size_t)most + 1) * kEvalOutputs);
+        uint8_t root_pi[kActions];
         selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
-                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t, uint32_t, SelfplaySearch &S) {
+                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t g, uint32_t q, SelfplaySearch &S) {
                             if (pol[who] != GBL_POLICY_EVAL_TREE) return false;
                             uint64_t cand = legal;
                             if (deps[who] > 0 && legal) {
@@ -1200,12 +1238,43 @@ int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, i
                                 for (int a = 0; a < kActions; ++a) cand |= (uint64_t)(S.outcome[a] == 0) << a;
                             }
                             S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, (uint32_t)its[who],
-                                                             (uint32_t)explore, S.h);
-                            S.priors = pri.data();  // (the root's row; zeros where the root has no candidate)
+                                                             (uint32_t)explore, S.h, HostNoise{(uint32_t)nz[who], seed, g, q, root_pi});
+                            S.priors = root_pi;  // (the network's row; zeros where the root has no candidate)
                             return true;
                         });
     }, 1);
     return GBL_OK;
+}
+
+int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                 int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                 int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                                 int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                                 int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                                 const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
+                                 int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
+{
+    return host_collect_solve_run(state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj,
+                                  obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj,
+                                  proven_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1,
+                                  iterations0, iterations1, solve_depth0, solve_depth1, 0, 0, explore, sample_plies, illegal_mode, counters, turn);
+}
+
+int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                 int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                 int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                                 int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                                 int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                                 const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1,
+                                 int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
+                                 void *)
+{
+    return host_collect_solve_run(state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj,
+                                  obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj,
+                                  proven_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1,
+                                  iterations0, iterations1, solve_depth0, solve_depth1, noise0, noise1, explore, sample_plies, illegal_mode, counters, turn);
 }
 
 int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

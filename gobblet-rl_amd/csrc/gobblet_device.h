@@ -2153,6 +2153,39 @@ __device__ __forceinline__ void eval_priors(const EvalNet &net, const int32_t (&
     for (int a = 0; a < kActions; ++a) pri[a] = (uint8_t)(((cand >> a) & 1ull) ? eval_prior(eval_exp2(lmax, o[a] >> net.shift_p), sum) : 0u);
 }
 
+// ---- root noise (include/gobblet_hip.h, "Root noise"): one statement for the kernels and the host flavour ---------------------
+// The noise row is the prior rule itself (eval_exp2 / eval_prior) over logits l_a = -(r_a >> 24), r_a a generator word of its own
+// stream.  The kernels give every action a lane and take the maximum and the sum over the wavefront; the host flavour runs
+// noise_priors.
+constexpr uint32_t kStreamNoise = 6u;  // generator stream of the root noise
+constexpr int kNoiseMaxWeight = 256;
+
+// l_a: minus the top byte of the word of (seed, g, ply index 64 q + a) -- one Philox block serves four actions
+__device__ __forceinline__ int32_t noise_logit(uint64_t seed, uint64_t g, uint32_t q, uint32_t a)
+{
+    return -(int32_t)(draw32(seed, g, 64u * q + a, kStreamNoise) >> 24);
+}
+
+__device__ __forceinline__ uint32_t noise_mix(uint32_t pi, uint32_t nu, uint32_t w) { return (pi * (256u - w) + nu * w + 128u) >> 8; }
+
+// pri: the root's prior row pi over cand (cand != 0, 0 < w <= 256); mixed: pi' (may be pri itself)
+__device__ __forceinline__ void noise_priors(uint64_t seed, uint64_t g, uint32_t q, uint32_t w, uint64_t cand, const uint8_t *pri, uint8_t *mixed)
+{
+    int32_t l[kActions], lmax = INT32_MIN;
+    uint32_t sum = 0;
+    for (int a = 0; a < kActions; ++a) {
+        if (!((cand >> a) & 1ull)) continue;
+        l[a] = noise_logit(seed, g, q, (uint32_t)a);
+        if (l[a] > lmax) lmax = l[a];
+    }
+    for (int a = 0; a < kActions; ++a)
+        if ((cand >> a) & 1ull) sum += eval_exp2(lmax, l[a]);
+    for (int a = 0; a < kActions; ++a)
+        mixed[a] = (uint8_t)(((cand >> a) & 1ull) ? noise_mix(pri[a], eval_prior(eval_exp2(lmax, l[a]), sum), w) : 0u);
+}
+
+inline const char *noise_error(int noise) { return noise < 0 || noise > kNoiseMaxWeight ? "the noise weight must be in [0, 256]" : nullptr; }
+
 // The selection key of candidate a with prior pi under a node of nv visits: the mean of its child (tree_key's first term; 32768
 // without a child, n = 0) plus ((explore pi isqrt(nv << 8)) >> 5) / (1 + n).  nv <= 512: the root of the isqrt stays below 2^24,
 // the product below 1024 * 255 * 363 < 2^27.

@@ -1984,13 +1984,33 @@ __global__ __launch_bounds__(64) void k_evaluate(const int8_t *__restrict__ stat
 //   expand   the move and what it decided in every lane alike; lane 0 links the node;
 //   evaluate wave_evaluate on the new child's position, its prior row stored beside the node;
 //   back up  lane 0 walks to the root.
+// noise: the root noise of this search (w == 0: none, nothing is drawn); NOISE = false compiles it out, so that the kernels without
+// it are the code they were.  mixed: lane a's byte of the row the root keeps -- pi' where there is noise, the network's byte
+// otherwise; the returned pi is the network's either way.
+struct RootNoise {
+    uint32_t w;
+    uint64_t seed, g;
+    uint32_t q;
+};
+
+template <bool NOISE>
 __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, uint8_t *const pri, uint32_t *const s_h, const EvalNet &net,
                                                          const Planes &root, const int mover, const uint64_t cand, const uint32_t iterations,
-                                                         const uint32_t explore, const uint32_t lane, uint32_t &count)
+                                                         const uint32_t explore, const uint32_t lane, uint32_t &count, const RootNoise &noise,
+                                                         uint32_t &mixed)
 {
     if (lane == 0) nodes[0] = TreeNode{};
     const WaveEval at_root = wave_evaluate(net, root, mover, cand, s_h, lane);
-    if (lane < (uint32_t)kEvalOutputs) pri[lane] = (uint8_t)at_root.pi;
+    mixed = at_root.pi;
+    if (NOISE && noise.w && cand) {  // (wave-uniform) the root's row alone: lane a draws its word, the noise row is the prior rule over the words
+        const bool in = (cand >> lane) & 1ull;
+        const int32_t l = noise_logit(noise.seed, noise.g, noise.q, lane);
+        const int32_t lmax = wave_max<int32_t>(in ? l : INT32_MIN);
+        const uint32_t e = in ? eval_exp2(lmax, l) : 0u;
+        const uint32_t sum = wave_sum(e);
+        mixed = in ? noise_mix(at_root.pi, eval_prior(e, sum), noise.w) : 0u;
+    }
+    if (lane < (uint32_t)kEvalOutputs) pri[lane] = (uint8_t)mixed;
     wave_lds_fence();  // (the root is written)
     count = 1;
     for (uint32_t i = 0; cand && i < iterations; ++i) {
@@ -2041,12 +2061,14 @@ __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, 
 // gbl_tree_search_eval: k_tree's tree with a network leaf.  One wavefront per board (a grid-stride loop over boards).  The tree is
 // (iterations + 1) 16-byte nodes followed by (iterations + 1) 56-byte prior rows in dynamic LDS; the root planes stay in registers.
 // The search is tree_eval_iterations; the wavefront then writes the root's children out and decides (tree_root_out).
+template <bool NOISE>
 __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
                                                   const int8_t *__restrict__ mask, const EvalNet net, int32_t *__restrict__ visits_out,
                                                   int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
                                                   int32_t *__restrict__ action_out, int32_t *__restrict__ nodes_out,
                                                   int32_t *__restrict__ root_value_out, uint8_t *__restrict__ root_priors_out, int64_t n,
-                                                  uint32_t iterations, uint32_t explore)
+                                                  uint32_t iterations, uint32_t explore, uint8_t *__restrict__ root_mixed_out, uint32_t noise,
+                                                  uint64_t seed, uint64_t env_base, uint32_t call)
 {
     extern __shared__ uint4 s_tree[];
     TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
@@ -2057,10 +2079,12 @@ __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ sta
         const Planes root = board_planes(state, b, lane);
         const int mover = to_move[b] != 0;
         const uint64_t cand = board_candidates(root, mover, mask, b, lane);
-        uint32_t count;
-        const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, net, root, mover, cand, iterations, explore, lane, count);
+        uint32_t count, mixed;
+        const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, net, root, mover, cand, iterations, explore, lane, count,
+                                                             RootNoise{noise, seed, env_base + (uint64_t)b, call}, mixed);
         const uint64_t key = tree_root_out(nodes, lane, b, visits_out, wins_out, losses_out);
         if (root_priors_out && lane < (uint32_t)kActions) root_priors_out[b * kActions + lane] = (uint8_t)at_root.pi;
+        if (NOISE && root_mixed_out && lane < (uint32_t)kActions) root_mixed_out[b * kActions + lane] = (uint8_t)mixed;
         if (lane == 0) {
             if (action_out) action_out[b] = tree_action_of(key);
             if (nodes_out) nodes_out[b] = (int32_t)count;
@@ -2310,8 +2334,9 @@ __global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state,
         state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
         [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
             if ((who ? policy1 : policy0) != kPolicyEvalTree) return false;
-            const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
-                                                          who ? iterations1 : iterations0, explore, lane, S.count);
+            uint32_t mixed;  // (no noise here: the network's byte)
+            const WaveEval at_root = tree_eval_iterations<false>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
+                                                                 who ? iterations1 : iterations0, explore, lane, S.count, RootNoise{}, mixed);
             S.pi = at_root.pi;
             S.root_q = at_root.q;
             S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
@@ -2829,6 +2854,7 @@ __global__ __launch_bounds__(64) void k_solve(const int8_t *__restrict__ state, 
 // solver's LDS stands beside the tree's, and its fences are wave_lds_fence: the ply's trajectory stores stay in flight over the
 // next decision.  The solver's registers are dead before the tree's come alive.  The outcome byte of every lane and V go out
 // from the second lambda, beside the root's q and the prior byte.
+template <bool NOISE>
 __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                       uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
                                                       int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
@@ -2837,7 +2863,7 @@ __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state
                                                       const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
                                                       uint32_t iterations1, int solve_depth0, int solve_depth1, uint32_t most, uint32_t explore,
                                                       int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
-                                                      int32_t *__restrict__ turn)
+                                                      int32_t *__restrict__ turn, uint32_t noise0, uint32_t noise1)
 {
     extern __shared__ uint4 s_tree[];
     TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
@@ -2867,8 +2893,9 @@ __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state
                 }
                 cand = (uint64_t)__ballot(my_c == 0);
             }
-            const WaveEval at_root = tree_eval_iterations(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its, explore, lane,
-                                                          S.count);
+            uint32_t mixed;  // (the root's own row; the trajectory keeps the network's)
+            const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its, explore,
+                                                                 lane, S.count, RootNoise{who ? noise1 : noise0, seed, g, q}, mixed);
             S.pi = at_root.pi;
             S.root_q = at_root.q;
             S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
@@ -4333,9 +4360,11 @@ int gbl_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask,
     GBL_LAUNCHED("gbl_evaluate");
 }
 
-int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
-                         int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
-                         int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *stream)
+// gbl_tree_search_eval and gbl_tree_search_eval_noise: one kernel in two instantiations, with and without the noise's code
+static int tree_search_eval_launch(const char *name, const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev,
+                                   int iterations, int explore, int noise, uint64_t seed, uint64_t env_base, uint32_t call,
+                                   int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
+                                   int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
     if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
@@ -4349,10 +4378,39 @@ int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_
         return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / root_value_out must be 4-byte aligned");
     // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations: below the 64 KB a kernel gets unasked)
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);
-    hipLaunchKernelGGL(k_tree_eval, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), lds, (hipStream_t)stream, state, to_move, mask,
-                       net, visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n,
-                       (uint32_t)iterations, (uint32_t)explore);
-    GBL_LAUNCHED("gbl_tree_search_eval");
+    // (k_tree_eval<false> is the kernel without the noise's code; a caller who asks for root_mixed_out at weight 0 gets the <true> one)
+#define GBL_TE(NOISE)                                                                                                                   \
+    hipLaunchKernelGGL(k_tree_eval<NOISE>, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), lds, (hipStream_t)stream, state, to_move, \
+                       mask, net, visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n,              \
+                       (uint32_t)iterations, (uint32_t)explore, root_mixed_out, (uint32_t)noise, seed, env_base, call)
+    if (noise || root_mixed_out)
+        GBL_TE(true);
+    else
+        GBL_TE(false);
+#undef GBL_TE
+    GBL_LAUNCHED(name);
+}
+
+int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                         int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                         int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *stream)
+{
+    return tree_search_eval_launch("gbl_tree_search_eval", state, to_move, mask, ev, iterations, explore, 0, 0, 0, 0, visits_out, wins_out,
+                                   losses_out, action_out, nodes_out, root_value_out, root_priors_out, nullptr, n, stream);
+}
+
+int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                               int explore, int noise, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out,
+                               int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *root_value_out,
+                               uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream)
+{
+    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
+    if (const char *why = noise_error(noise)) return fail(GBL_ERR_ARG, why);
+    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
+    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    return tree_search_eval_launch("gbl_tree_search_eval_noise", state, to_move, mask, ev, iterations, explore, noise, seed, env_base, call,
+                                   visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, root_mixed_out,
+                                   n, stream);
 }
 
 int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
@@ -4433,19 +4491,22 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
     GBL_LAUNCHED("gbl_collect_search_eval");
 }
 
-int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
-                             int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+// gbl_collect_search_solve and gbl_collect_search_noise: one kernel in two instantiations, with and without the noise's code
+static int collect_solve_launch(const char *name, int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                             int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
                              int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
                              uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
                              int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
                              int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
-                             int solve_depth0, int solve_depth1, int explore, int sample_plies, int illegal_mode, int64_t *counters,
-                             int32_t *turn, void *stream)
+                             int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
+                             int64_t *counters, int32_t *turn, void *stream)
 {
     if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
     if (const char *why = collect_solve_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, solve_depth0, solve_depth1,
                                               explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
         return fail(GBL_ERR_ARG, why);
+    if ((policy0 == GBL_POLICY_EVAL_TREE && noise_error(noise0)) || (policy1 == GBL_POLICY_EVAL_TREE && noise_error(noise1)))
+        return fail(GBL_ERR_ARG, "noise0 / noise1 must be in [0, 256]");
     if (n == 0) return GBL_OK;
     GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
     if (plies == 0) return GBL_OK;
@@ -4467,11 +4528,51 @@ int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32
     const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
     // the tree as gbl_collect_search_eval; the solver's arrays are static LDS beside it
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)most + 1);
-    hipLaunchKernelGGL(k_collect_solve, grid, dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed, env_base, ply_dev, ply0, plies, done,
-                       ply_stride, tile_stride, T, root_value_traj, priors_traj, outcome_traj, proven_traj, nets[0], nets[1], policy0, policy1,
-                       (uint32_t)iterations0, (uint32_t)iterations1, solve_depth0, solve_depth1, (uint32_t)most, (uint32_t)explore,
-                       sample_plies, illegal_mode, counters, turn);
-    GBL_LAUNCHED("gbl_collect_search_solve");
+    const uint32_t w0 = policy0 == GBL_POLICY_EVAL_TREE ? (uint32_t)noise0 : 0u, w1 = policy1 == GBL_POLICY_EVAL_TREE ? (uint32_t)noise1 : 0u;
+    // (k_collect_solve<false> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked)
+#define GBL_CSV(NOISE)                                                                                                                    \
+    hipLaunchKernelGGL(k_collect_solve<NOISE>, grid, dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed, env_base, ply_dev, ply0,   \
+                       plies, done, ply_stride, tile_stride, T, root_value_traj, priors_traj, outcome_traj, proven_traj, nets[0], nets[1],   \
+                       policy0, policy1, (uint32_t)iterations0, (uint32_t)iterations1, solve_depth0, solve_depth1, (uint32_t)most,           \
+                       (uint32_t)explore, sample_plies, illegal_mode, counters, turn, w0, w1)
+    if (w0 | w1)
+        GBL_CSV(true);
+    else
+        GBL_CSV(false);
+#undef GBL_CSV
+    GBL_LAUNCHED(name);
+}
+
+int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                             int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                             int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                             uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                             int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                             int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                             int solve_depth0, int solve_depth1, int explore, int sample_plies, int illegal_mode, int64_t *counters,
+                             int32_t *turn, void *stream)
+{
+    return collect_solve_launch("gbl_collect_search_solve", state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj,
+                                to_move_traj, mask_traj, obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj,
+                                priors_traj, outcome_traj, proven_traj, n,
+                                ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1, iterations0, iterations1,
+                                solve_depth0, solve_depth1, 0, 0, explore, sample_plies, illegal_mode, counters, turn, stream);
+}
+
+int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                             int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                             int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                             uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                             int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                             int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                             int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
+                             int64_t *counters, int32_t *turn, void *stream)
+{
+    return collect_solve_launch("gbl_collect_search_noise", state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj,
+                                to_move_traj, mask_traj, obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj,
+                                priors_traj, outcome_traj, proven_traj, n,
+                                ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1, iterations0, iterations1,
+                                solve_depth0, solve_depth1, noise0, noise1, explore, sample_plies, illegal_mode, counters, turn, stream);
 }
 
 int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

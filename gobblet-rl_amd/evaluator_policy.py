@@ -5,7 +5,9 @@ with that network in place of the masked-random playouts and with its priors ste
 ``collect(..., search=...)`` / ``outcome_targets`` is used by: ``GobbletEvaluator.from_float`` quantises a float 117-H-55 MLP.
 
 The rule is integer-only: the kernel and the host flavour (``device="cpu"``) agree bit for bit, and the search draws nothing --
-no seed, no call index; two calls on the same boards give the same result.
+no seed, no call index; two calls on the same boards give the same result -- unless it is asked for root noise (``noise=``,
+``gbl_tree_search_eval_noise``): a random row keyed by (seed, board id, call) mixed into the root's prior row, the exploration of
+self-play.  ``root_noise`` restates that row in torch for the consumers of a trajectory.
 """
 from __future__ import annotations
 
@@ -141,22 +143,29 @@ class GobbletEvaluator(_OnDevice):
 class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
     _games_per_visit = 128  # (a network leaf counts as 128 games)
 
-    def __init__(self, evaluator: GobbletEvaluator, iterations: int = 256, explore: int = 16, device=None, **kwargs: Any) -> None:
+    def __init__(self, evaluator: GobbletEvaluator, iterations: int = 256, explore: int = 16, noise: float = 0.0, seed: int = 0,
+                 env_base: int = 0, device=None, **kwargs: Any) -> None:
         """iterations: network leaves per decision (1 .. 512); explore: weight of the prior term of the selection key (0 .. 1024;
         the default is the best of the host-flavour sweep in profiles/r10/evaluator_policy.json); device: where the search runs
-        (default: the evaluator's; the evaluator is copied there if it lives elsewhere)."""
+        (default: the evaluator's; the evaluator is copied there if it lives elsewhere).
+
+        noise: the share in [0, 1] of a random row mixed into the ROOT's prior row, once per search (``gbl_tree_search_eval_noise``;
+        the weight of the ABI is round(256 * noise)).  The row of board b of call k is keyed by (seed, env_base + b, k): ``call``
+        counts up once per ``compute_actions_from_state``.  With noise 0 the policy draws nothing."""
         for name, val, lo, hi in (("iterations", iterations, 1, 512), ("explore", explore, 0, 1024)):
             if not lo <= int(val) <= hi:
                 raise ValueError(f"{name} must be in [{lo}, {hi}]")
         self.iterations, self.explore = int(iterations), int(explore)
+        self.noise = noise_weight(noise)
+        self.seed, self.env_base, self.call = int(seed), int(env_base), 0
         self.device = torch.device(evaluator.device if device is None else device)
         self.evaluator = evaluator if evaluator.device == self.device else evaluator.to(self.device)
         self._lib = nat.lib_for(self.device)
         # outputs of the last call (tensors on the device): int32 (N, 54) visits / wins / losses of the root's children from the
         # mover's side (a leaf counts as 128 games), int32 (N,) nodes created, the decision and the root's q, uint8 (N, 54) the
-        # root's prior row
+        # root's prior row as the network gives it, and as the root keeps it (the same row without noise)
         self.last_visits = self.last_wins = self.last_losses = self.last_nodes = self.last_action = None
-        self.last_root_value = self.last_root_priors = None
+        self.last_root_value = self.last_root_priors = self.last_root_mixed = None
 
     def _run(self, state, to_move, mask) -> torch.Tensor:
         n = state.shape[0]
@@ -165,13 +174,79 @@ class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
         act = torch.empty(n, dtype=torch.int32, device=self.device)
         nodes, rootv = torch.empty_like(act), torch.empty_like(act)
         rootp = torch.empty((n, nat.ACTIONS), dtype=torch.uint8, device=self.device)
+        mixed = rootp
         ev = self.evaluator.as_struct()
         with self._on_device():
-            nat.check(self._lib.gbl_tree_search_eval(state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), self.iterations,
-                                                     self.explore, visits.data_ptr(), wins.data_ptr(), losses.data_ptr(), act.data_ptr(),
-                                                     nodes.data_ptr(), rootv.data_ptr(), rootp.data_ptr(), n,
-                                                     self._stream()), "gbl_tree_search_eval")
+            if self.noise:
+                mixed = torch.empty_like(rootp)
+                nat.check(self._lib.gbl_tree_search_eval_noise(
+                    state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), self.iterations, self.explore, self.noise,
+                    self.seed, self.env_base, self.call, visits.data_ptr(), wins.data_ptr(), losses.data_ptr(), act.data_ptr(),
+                    nodes.data_ptr(), rootv.data_ptr(), rootp.data_ptr(), mixed.data_ptr(), n, self._stream()),
+                    "gbl_tree_search_eval_noise")
+                self.call += 1
+            else:
+                nat.check(self._lib.gbl_tree_search_eval(state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev),
+                                                         self.iterations, self.explore, visits.data_ptr(), wins.data_ptr(),
+                                                         losses.data_ptr(), act.data_ptr(), nodes.data_ptr(), rootv.data_ptr(),
+                                                         rootp.data_ptr(), n, self._stream()), "gbl_tree_search_eval")
         self.last_visits, self.last_wins, self.last_losses = visits, wins, losses
         self.last_nodes, self.last_action, self.last_root_value, self.last_root_priors = nodes, act, rootv, rootp
+        self.last_root_mixed = mixed
         return act
 
+
+def noise_weight(noise) -> int:
+    """The ABI's weight 0 .. 256 of a noise share in [0, 1]."""
+    if not 0.0 <= float(noise) <= 1.0:
+        raise ValueError("noise must be in [0, 1]")
+    return int(round(256.0 * float(noise)))
+
+
+# ---- the root noise restated in torch (include/gobblet_hip.h, "Root noise"): a convenience for consumers, not a kernel -----------
+_EXP2_16 = (65536, 62757, 60097, 57549, 55109, 52773, 50535, 48393, 46341, 44376, 42495, 40693, 38968, 37316, 35734, 34219)
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def _philox4x32_10(c, k0: int, k1: int):
+    """Philox4x32-10 on int64 tensors that hold 32-bit words: c = [c0, c1, c2, c3] -> the four output words."""
+    def mulhilo(m: int, x):
+        lo, hi = x & 0xFFFF, x >> 16          # (x * m in two halves: every product stays below 2^63)
+        ml, mh = m & 0xFFFF, m >> 16
+        ll, lh, hl, hh = lo * ml, lo * mh, hi * ml, hi * mh
+        mid = (ll >> 16) + (lh & 0xFFFF) + (hl & 0xFFFF)
+        return (hh + (lh >> 16) + (hl >> 16) + (mid >> 16)) & _M32, ((mid << 16) | (ll & 0xFFFF)) & _M32
+    c0, c1, c2, c3 = c
+    for _ in range(10):
+        hi0, lo0 = mulhilo(_PHILOX_M0, c0)
+        hi1, lo1 = mulhilo(_PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def root_noise(seed: int, board_ids, ply, candidates) -> torch.Tensor:
+    """uint8 (N, 54): the noise rows nu of ``gbl_tree_search_eval_noise`` / ``gbl_collect_search_noise`` for boards ``board_ids``
+    (N,) (= env_base + b) at call / ply index ``ply`` (an int or (N,)) over the candidate sets ``candidates`` (N, 54), non-zero =
+    candidate -- the legal mask of an unguarded side, the outcome-0 actions of a guarded one.  A consumer of a trajectory rebuilds
+    the row the root kept from "priors":  pi' = (pi * (256 - w) + nu * w + 128) >> 8.  On the device of ``candidates``."""
+    cand = torch.as_tensor(candidates)
+    dev = cand.device
+    cand = cand.reshape(-1, nat.ACTIONS) != 0
+    n = cand.shape[0]
+    g = torch.as_tensor(board_ids, device=dev).to(torch.int64).reshape(-1).expand(n)
+    q = torch.as_tensor(ply, device=dev).to(torch.int64).reshape(-1).expand(n)
+    a = torch.arange(nat.ACTIONS, device=dev, dtype=torch.int64)
+    idx = (64 * q)[:, None] + a[None, :]                      # the ply index 64 q + a
+    blk = idx[:, 0::4] >> 2                                   # one block per four actions: (N, 14)
+    zero = torch.zeros_like(blk)
+    words = _philox4x32_10([(g & _M32)[:, None] + zero, (g >> 32)[:, None] + zero, blk, zero + nat.STREAM_NOISE],
+                           int(seed) & _M32, (int(seed) >> 32) & _M32)
+    r = torch.stack(words, dim=2).reshape(n, 56)[:, :nat.ACTIONS] >> 24
+    rmin = torch.where(cand, r, torch.full_like(r, 255)).min(1, keepdim=True).values
+    d = (r - rmin).clamp(min=0)
+    e = torch.tensor(_EXP2_16, device=dev, dtype=torch.int64)[d & 15] >> (d >> 4)
+    e = torch.where(cand, e, torch.zeros_like(e))
+    nu = 1 + (e * 254) // e.sum(1, keepdim=True).clamp(min=1)
+    return torch.where(cand, nu, torch.zeros_like(nu)).to(torch.uint8)

@@ -439,7 +439,12 @@ class BatchedGobblet:
         every search of an evaluator side, still inside the one launch (``gbl_collect_search_solve``): a root the solver proves
         (a forced win, or nothing but forced losses) plays the solver's action, "how" = ``nat.HOW_PROVEN``, with a one-hot visits
         row; every other root is searched over its unproven actions only.  The buffers (``solver_outputs=True``) also receive
-        "outcomes" / "proven"; ``outcome_targets`` and ``training_batch`` take the result as it is."""
+        "outcomes" / "proven"; ``outcome_targets`` and ``training_batch`` take the result as it is.
+
+        ``search=dict(..., noise=x)`` (a share in [0, 1], or a pair, one per side; 0 or absent: none; a policy instance brings its
+        own) mixes a random row into the ROOT's prior row of every search of an evaluator side, keyed by (seed, board id, ply)
+        (``gbl_collect_search_noise``): the exploration of self-play.  An arena passes no noise, or noises one side only.  "priors"
+        stays the network's row; ``root_noise`` recomputes the random one."""
         if not self.auto_reset:
             raise ValueError("collect() plays with auto-reset; this environment was created with auto_reset=False")
         T = int(plies)
@@ -496,7 +501,13 @@ class BatchedGobblet:
                     nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")))
             window = (n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T)
             tail = (sp["sample_plies"], self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream())
-            if guarded:
+            if ep is not None and any(ep["noise"]):  # (root noise on a side: the guarded kernel, whatever the depths)
+                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
+                nat.check(self._lib.gbl_collect_search_noise(
+                    *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), nat.ptr(f.get("outcomes")), nat.ptr(f.get("proven")),
+                    *window, *ep["policies"], *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
+                    *ep["solve_depth"], *ep["noise"], ep["explore"], *tail), "gbl_collect_search_noise")
+            elif guarded:
                 structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
                 nat.check(self._lib.gbl_collect_search_solve(
                     *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), nat.ptr(f.get("outcomes")), nat.ptr(f.get("proven")),
@@ -607,7 +618,8 @@ class BatchedGobblet:
                     sample_plies=int(kw["sample_plies"]))
 
     def _evaluator_params(self, policies, search):
-        """The arguments of ``gbl_collect_search_eval`` when a side of ``policies`` plays the evaluator-guided search, else None."""
+        """The arguments of ``gbl_collect_search_eval`` / ``_solve`` / ``_noise`` when a side of ``policies`` plays the evaluator-guided
+        search, else None."""
         from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator
         from .tree_policy import TreeSearchGobbletPolicy
         if policies is None or isinstance(policies, str):
@@ -620,16 +632,18 @@ class BatchedGobblet:
         evs = [is_eval(x) for x in sides]
         if len(sides) != 2 or not any(evs):
             return None
-        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0),  # EvaluatorTreeSearchGobbletPolicy's defaults
+        from .evaluator_policy import noise_weight
+        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0, noise=0.0),  # EvaluatorTreeSearchGobbletPolicy's defaults
                              search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies / "
-                             "solve_depth)")
-        its, nets, deps = self._pair(kw["iterations"]), self._pair(kw["evaluator"]), self._pair(kw["solve_depth"])
-        if len(its) != 2 or len(nets) != 2 or len(deps) != 2:
-            raise ValueError("search: iterations / evaluator / solve_depth are a value or a pair, one per side")
+                             "solve_depth / noise)")
+        its, nets, deps, nzs = self._pair(kw["iterations"]), self._pair(kw["evaluator"]), self._pair(kw["solve_depth"]), self._pair(kw["noise"])
+        if len(its) != 2 or len(nets) != 2 or len(deps) != 2 or len(nzs) != 2:
+            raise ValueError("search: iterations / evaluator / solve_depth / noise are a value or a pair, one per side")
+        nzs = [noise_weight(x or 0.0) for x in nzs]  # (shares in [0, 1] -> the ABI's weights 0 .. 256)
         codes, explores = [], []
         for m, x in enumerate(sides):
             if isinstance(x, EvaluatorTreeSearchGobbletPolicy):
-                its[m], nets[m] = x.iterations, x.evaluator
+                its[m], nets[m], nzs[m] = x.iterations, x.evaluator, x.noise
                 explores.append(x.explore)
                 codes.append(nat.POLICY_EVAL_TREE)
             elif evs[m]:
@@ -652,7 +666,7 @@ class BatchedGobblet:
             explore = 16
         for m in range(2):
             if codes[m] != nat.POLICY_EVAL_TREE:
-                its[m] = deps[m] = 0
+                its[m] = deps[m] = nzs[m] = 0
                 continue
             deps[m] = int(deps[m] or 0)
             if not 0 <= deps[m] <= nat.SOLVE_MAX_DEPTH:
@@ -668,7 +682,7 @@ class BatchedGobblet:
         if not (0 <= explore <= 1024 and int(kw["sample_plies"]) >= 0):
             raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
         return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
-                    solve_depth=deps)
+                    solve_depth=deps, noise=nzs)
 
     def outcome_targets(self, traj: dict) -> dict:
         """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128

@@ -402,6 +402,31 @@ int gbl_tree_search_eval(const int8_t *state, const int8_t *to_move, const int8_
                          int explore, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
                          int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, int64_t n, void *stream);
 
+/* Root noise: gbl_tree_search_eval with a random row mixed into the ROOT's prior row, once per search (the exploration of a self-play
+ * search).  Integer-only, drawn inside the launch, and keyed by (seed, board id, call) alone: a board's result does not depend on the
+ * batch or the shard it is in.  Parameters: the weight w = `noise` in 0 .. 256, seed, the board id g = env_base + b and q = call.
+ * C is the root's candidate set and pi the root's prior row, exactly as gbl_tree_search_eval computes them.
+ *   w == 0   nothing is drawn and the search is gbl_tree_search_eval, bit for bit.
+ *   w > 0    Draw.  For every a in C, r_a = the generator word of (seed, g, ply index 64 q + a, stream 6): gbl_sample's generator,
+ *              the Philox block with counter (g_lo, g_hi, (64 q + a) >> 2, 6), word a & 3 -- one block serves four actions.  Stream 6
+ *              is the noise's own; streams 0 .. 5 belong to the other consumers of a (seed, board) pair.
+ *            Noise row.  nu = the prior rule of gbl_evaluator over C with l_a = -(r_a >> 24):
+ *              d_a = (r_a >> 24) - min over C of (r >> 24),  e_a = T[d_a & 15] >> (d_a >> 4),  nu_a = 1 + (e_a * 254) / (sum over C of e),
+ *              and nu_a = 0 outside C.  The e_a are log-uniform over 16 octaves.
+ *            Mix.  pi'_a = (pi_a * (256 - w) + nu_a * w + 128) >> 8 for a in C, 0 outside; it stays in 1 .. 255, and w = 256 gives nu.
+ *            The root node keeps pi' as its prior row, so that the selection at the root uses pi'.  Every other node keeps its
+ *            network row.  Everything else is gbl_tree_search_eval's text unchanged: the iterations, the keys, the back-up,
+ *            action_out.  The root's q is not touched.  A root without a candidate draws nothing.
+ * Outputs: those of gbl_tree_search_eval -- root_priors_out stays the network's row pi -- and root_mixed_out uint8[n][54] (may be
+ * NULL) = pi', which equals pi where noise == 0.
+ * `call` travels by value: a replayed graph repeats its noise, as it repeats gbl_training_batch's draws.
+ * noise outside 0 .. 256, call >= 2^24 (the ply index 64 q + a fits 32 bits) and env_base + n > 2^42 are GBL_ERR_ARG; every other
+ * limit, the alignment rules and the LDS as gbl_tree_search_eval.  Allocates nothing. */
+int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                               int explore, int noise, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out,
+                               int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *root_value_out,
+                               uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream);
+
 /* Exact bounded-depth solver (no counterpart in the reference): the full-width game tree of every board to `depth` plies, the proven
  * result of every root action.  Integer-only and draws nothing: the kernel, the host flavour and a restatement of this text agree
  * byte for byte.
@@ -600,6 +625,23 @@ int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32
                              const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
                              const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
                              int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
+
+/* Self-play with root noise: gbl_collect_search_solve with one noise weight per side, noise0 / noise1 in 0 .. 256 for player_1 /
+ * player_2.  A side's weight is ignored unless that side is EVAL_TREE.  The ply q of a mover m is gbl_collect_search_solve's text with
+ * the search replaced by gbl_tree_search_eval_noise(..., noise_m, seed, env_base, call = q) over the same candidate set: the legal
+ * mask where the side is unguarded, the actions of outcome 0 where it is guarded.  A proven ply searches nothing and draws nothing.
+ * The arrays are gbl_collect_search_solve's; priors_traj stays the network's row pi (nu is a function of (seed, g, q, C): a consumer
+ * recomputes it).  With both weights 0 every array is gbl_collect_search_solve's, bit for bit.  The noise moves with *ply_dev as every
+ * other draw of the window does.  A weight outside 0 .. 256 on an EVAL_TREE side is GBL_ERR_ARG; everything else as
+ * gbl_collect_search_solve.  Allocates nothing. */
+int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                             int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                             int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                             int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                             int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                             const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                             const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int noise0,
+                             int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
 
 /* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
  * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:
