@@ -1000,20 +1000,9 @@ int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t 
     return GBL_OK;
 }
 
-// The boards [b0, b1) of a self-play window, for gbl_cpu_collect_search and gbl_cpu_collect_search_eval: per ply the mover's search
-// (`search(p, who, legal, g, q, h)`: false where the masked-random sampler moves, else it fills h and returns true), the decision
-// or the visit-proportional draw, the step with auto-reset and the ply's cell of every trajectory array.
-struct SelfplayTraj {
-    int32_t *actions;
-    int8_t *winner, *reward, *done, *to_move, *mask, *obs;
-    int16_t *visits;
-    int32_t *value, *nodes;
-    int8_t *how, *mover;
-    int32_t *root_value;  // (the evaluator search's two: NULL in gbl_cpu_collect_search)
-    uint8_t *priors;
-    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_cpu_collect_search_solve)
-};
-
+// The boards [b0, b1) of a self-play window (c: the call, gobblet_device.h's SelfplayCall; ply0: with *ply_dev added): per ply the
+// mover's search (`search(p, who, legal, g, q, S)`: false where the masked-random sampler moves, else it fills S and returns true),
+// the decision or the visit-proportional draw, the step with auto-reset and the ply's cell of every trajectory array.
 struct SelfplaySearch {
     HostSearch h;
     int32_t root_q;
@@ -1027,10 +1016,15 @@ struct SelfplaySearch {
 
 extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
 template <typename Search>
-static void selfplay_boards(int64_t b0, int64_t b1, int8_t *state, int8_t *to_move, int8_t *done, const SelfplayTraj &T, int64_t ply_stride,
-                            int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, uint32_t plies, int sample_plies,
-                            int illegal_mode, int64_t *counters, int32_t *turn, Search &&search)
+static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evaluator> &c, uint32_t ply0, Search &&search)
 {
+    int8_t *const state = c.state, *const to_move = c.to_move, *const done = c.done;
+    const SelfplayTraj &T = c.traj;
+    const int64_t ply_stride = c.ply_stride, tile_stride = c.tile_stride;
+    const uint64_t seed = c.seed, env_base = c.env_base;
+    const uint32_t plies = c.plies;
+    const int sample_plies = c.sample_plies, illegal_mode = c.illegal_mode;
+    int32_t *const turn = c.turn;
     Tally tl;
     SelfplaySearch S{};
     HostSearch &h = S.h;
@@ -1099,9 +1093,61 @@ static void selfplay_boards(int64_t b0, int64_t b1, int8_t *state, int8_t *to_mo
         done[b] = (int8_t)dn;
         if (turn) turn[b] = tabs;
     }
-    add_tally(counters, tl);
+    add_tally(c.counters, tl);
 }
 }  // extern "C++"
+
+// The four self-play entry points behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
+// over the threads.  gbl_cpu_collect_search_eval is the guarded loop with depths and weights 0 and no outcome / proven arrays.
+static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
+{
+    EvalNet nets[2] = {};
+    int most = 0;  // the larger tree of the sides that search
+    const int go = selfplay_prologue(c, most, [](const char *why) { return fail(GBL_ERR_ARG, why); }, [&](int m) {
+        if (const char *why = evaluator_pointers_error(c.ev[m])) return fail(GBL_ERR_ARG, why);
+        nets[m] = eval_net(c.ev[m]);
+        return GBL_OK;
+    });
+    if (go <= 0) return go;
+    if (!strides_ok(c.n, c.plies, c.ply_stride, c.tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    const uint32_t ply0 = c.ply0 + (c.ply_dev ? *c.ply_dev : 0u);
+    const bool uct = c.run == kRunSearch;
+    const EvalNet net0 = nets[0], net1 = nets[1];
+    parallel_for(c.n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a solve and a whole search: every board is worth a thread)
+        std::vector<TreeNode> nodes((size_t)most + 1);
+        std::vector<uint8_t> pri(uct ? 0 : ((size_t)most + 1) * kEvalOutputs);
+        uint8_t root_pi[kActions];
+        selfplay_boards(b0, b1, c, ply0, [&](const Planes &p, int who, uint64_t legal, uint64_t g, uint32_t q, SelfplaySearch &S) {
+            if (c.policy[who] != (uct ? GBL_POLICY_TREE : GBL_POLICY_EVAL_TREE)) return false;
+            const uint32_t its = (uint32_t)c.iterations[who];
+            if (uct) {
+                host_tree_search(nodes, p, who, legal, g, its, (uint32_t)c.playouts[who], (uint32_t)c.max_plies, (uint32_t)c.explore, c.seed, q,
+                                 S.h);
+                return true;
+            }
+            uint64_t cand = legal;
+            if (c.solve_depth[who] > 0 && legal) {
+                const uint32_t best = host_solve(p, who, legal, c.solve_depth[who], S.outcome);
+                S.solved = true;
+                S.proven = solve_value_of(best);
+                if (S.proven) {  // the one-hot row and the value of a proven root: no search
+                    S.proven_action = solve_action_of(best);
+                    S.h = HostSearch{};
+                    S.h.visits[S.proven_action] = (int)its;
+                    (S.proven > 0 ? S.h.wins : S.h.losses)[S.proven_action] = 128 * (int)its;
+                    return true;
+                }
+                cand = 0;
+                for (int a = 0; a < kActions; ++a) cand |= (uint64_t)(S.outcome[a] == 0) << a;
+            }
+            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, its, (uint32_t)c.explore, S.h,
+                                             HostNoise{(uint32_t)c.noise[who], c.seed, g, q, root_pi});
+            S.priors = root_pi;  // (the network's row; zeros where the root has no candidate)
+            return true;
+        });
+    }, 1);
+    return GBL_OK;
+}
 
 int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
                            int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
@@ -1110,30 +1156,12 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
                            int policy0, int policy1, int iterations0, int iterations1, int playouts0, int playouts1, int max_plies,
                            int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = collect_search_error(illegal_mode, policy0, policy1, iterations0, iterations1, playouts0, playouts1, max_plies,
-                                               explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
-        return fail(GBL_ERR_ARG, why);
-    const int its[2] = {iterations0, iterations1}, pls[2] = {playouts0, playouts1}, pol[2] = {policy0, policy1};
-    if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
-    if (ply_dev) ply0 += *ply_dev;
-    const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
-    const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                         nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr};
-    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
-        std::vector<TreeNode> nodes((size_t)most + 1);
-        selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
-                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t g, uint32_t q, SelfplaySearch &S) {
-                            if (pol[who] != GBL_POLICY_TREE) return false;
-                            host_tree_search(nodes, p, who, legal, g, (uint32_t)its[who], (uint32_t)pls[who], (uint32_t)max_plies,
-                                             (uint32_t)explore, seed, q, S.h);
-                            return true;
-                        });
-    }, 1);
-    return GBL_OK;
+    return host_selfplay_run({kRunSearch, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {nullptr, nullptr},
+                            {iterations0, iterations1}, {playouts0, playouts1}, {0, 0}, {0, 0}, max_plies, explore, sample_plies, illegal_mode,
+                            counters, turn});
 }
 
 int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
@@ -1144,106 +1172,12 @@ int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, in
                                 int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
                                 int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = collect_eval_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, explore, sample_plies,
-                                             turn != nullptr, ply0, plies, env_base, n))
-        return fail(GBL_ERR_ARG, why);
-    if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (plies == 0) return GBL_OK;
-    const gbl_evaluator *evs[2] = {ev0, ev1};
-    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
-    EvalNet nets[2] = {};
-    int most = 0;
-    for (int m = 0; m < 2; ++m) {
-        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
-        if (const char *why = evaluator_pointers_error(evs[m])) return fail(GBL_ERR_ARG, why);
-        nets[m] = eval_net(evs[m]);
-        most = std::max(most, its[m]);
-    }
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
-    if (ply_dev) ply0 += *ply_dev;
-    const EvalNet net0 = nets[0], net1 = nets[1];
-    const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                         nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr};
-    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a whole search: every board is worth a thread)
-        std::vector<TreeNode> nodes((size_t)most + 1);
-        std::vector<uint8_t> pri(((size_t)most + 1) * kEvalOutputs);
-        selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
-                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t, uint32_t, SelfplaySearch &S) {
-                            if (pol[who] != GBL_POLICY_EVAL_TREE) return false;
-                            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, legal, (uint32_t)its[who],
-                                                             (uint32_t)explore, S.h);
-                            S.priors = pri.data();  // (the root's row; zeros where the root has no candidate)
-                            return true;
-                        });
-    }, 1);
-    return GBL_OK;
-}
-
-static int host_collect_solve_run(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                                 int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                                 int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
-                                 int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
-                                 int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
-                                 const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
-                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1,
-                                 int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn)
-{
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = collect_solve_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, solve_depth0, solve_depth1,
-                                              explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
-        return fail(GBL_ERR_ARG, why);
-    if ((policy0 == GBL_POLICY_EVAL_TREE && noise_error(noise0)) || (policy1 == GBL_POLICY_EVAL_TREE && noise_error(noise1)))
-        return fail(GBL_ERR_ARG, "noise0 / noise1 must be in [0, 256]");
-    if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (plies == 0) return GBL_OK;
-    const gbl_evaluator *evs[2] = {ev0, ev1};
-    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1}, deps[2] = {solve_depth0, solve_depth1},
-              nz[2] = {noise0, noise1};
-    EvalNet nets[2] = {};
-    int most = 0;
-    for (int m = 0; m < 2; ++m) {
-        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
-        if (const char *why = evaluator_pointers_error(evs[m])) return fail(GBL_ERR_ARG, why);
-        nets[m] = eval_net(evs[m]);
-        most = std::max(most, its[m]);
-    }
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
-    if (ply_dev) ply0 += *ply_dev;
-    const EvalNet net0 = nets[0], net1 = nets[1];
-    const SelfplayTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                         nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj};
-    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a solve and a whole search: every board is worth a thread)
-        std::vector<TreeNode> nodes((size_t)most + 1);
-        std::vector<uint8_t> pri(((size_t)most + 1) * kEvalOutputs);
-        uint8_t root_pi[kActions];
-        selfplay_boards(b0, b1, state, to_move, done, T, ply_stride, tile_stride, seed, env_base, ply0, plies, sample_plies, illegal_mode,
-                        counters, turn, [&](const Planes &p, int who, uint64_t legal, uint64_t g, uint32_t q, SelfplaySearch &S) {
-                            if (pol[who] != GBL_POLICY_EVAL_TREE) return false;
-                            uint64_t cand = legal;
-                            if (deps[who] > 0 && legal) {
-                                const uint32_t best = host_solve(p, who, legal, deps[who], S.outcome);
-                                S.solved = true;
-                                S.proven = solve_value_of(best);
-                                if (S.proven) {  // the one-hot row and the value of a proven root: no search
-                                    S.proven_action = solve_action_of(best);
-                                    S.h = HostSearch{};
-                                    S.h.visits[S.proven_action] = its[who];
-                                    (S.proven > 0 ? S.h.wins : S.h.losses)[S.proven_action] = 128 * its[who];
-                                    return true;
-                                }
-                                cand = 0;
-                                for (int a = 0; a < kActions; ++a) cand |= (uint64_t)(S.outcome[a] == 0) << a;
-                            }
-                            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, (uint32_t)its[who],
-                                                             (uint32_t)explore, S.h, HostNoise{(uint32_t)nz[who], seed, g, q, root_pi});
-                            S.priors = root_pi;  // (the network's row; zeros where the root has no candidate)
-                            return true;
-                        });
-    }, 1);
-    return GBL_OK;
+    return host_selfplay_run({kRunEval, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn});
 }
 
 int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
@@ -1255,10 +1189,12 @@ int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, i
                                  const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
                                  int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
 {
-    return host_collect_solve_run(state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj,
-                                  obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj,
-                                  proven_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1,
-                                  iterations0, iterations1, solve_depth0, solve_depth1, 0, 0, explore, sample_plies, illegal_mode, counters, turn);
+    return host_selfplay_run({kRunSolve, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {0, 0}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn});
 }
 
 int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
@@ -1271,10 +1207,12 @@ int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, i
                                  int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
                                  void *)
 {
-    return host_collect_solve_run(state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj,
-                                  obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj,
-                                  proven_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1,
-                                  iterations0, iterations1, solve_depth0, solve_depth1, noise0, noise1, explore, sample_plies, illegal_mode, counters, turn);
+    return host_selfplay_run({kRunSolve, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn});
 }
 
 int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

@@ -2480,6 +2480,76 @@ inline const char *collect_solve_error(int illegal_mode, int policy0, int policy
     return nullptr;
 }
 
+// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve and _noise, and the checks both flavours make of them ----
+// The 16 trajectory arrays (any may be NULL).
+struct SelfplayTraj {
+    int32_t *actions;
+    int8_t *winner, *reward, *done, *to_move, *mask, *obs;
+    int16_t *visits;
+    int32_t *value, *nodes;
+    int8_t *how, *mover;
+    int32_t *root_value;  // (the evaluator search's two: NULL in gbl_collect_search)
+    uint8_t *priors;
+    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_collect_search_solve / _noise)
+};
+
+enum SelfplayRun { kRunSearch, kRunEval, kRunSolve };  // gbl_collect_search; gbl_collect_search_eval; _solve and _noise
+
+// The union of the four entry points' arguments; an entry point fills it (0 / NULL for what it does not have) and calls its flavour's
+// one runner.  [0] is player_1's, [1] player_2's.  Ev: gbl_evaluator.
+template <typename Ev>
+struct SelfplayCall {
+    SelfplayRun run;
+    int8_t *state, *to_move, *done;
+    SelfplayTraj traj;
+    int64_t n, ply_stride, tile_stride;
+    uint64_t seed, env_base;
+    uint32_t ply0;
+    const uint32_t *ply_dev;
+    uint32_t plies;
+    int policy[2];
+    const Ev *ev[2];
+    int iterations[2], playouts[2], solve_depth[2], noise[2];
+    int max_plies, explore, sample_plies, illegal_mode;
+    int64_t *counters;
+    int32_t *turn;
+};
+
+// Everything both flavours look at, in the order they report it: n < 0, the entry point's *_error, the searching sides' noise
+// weights, n == 0, the three board arrays, plies == 0, then per searching side `side(m)` -- the flavour's own look at evaluator m
+// (its pointers; on the device their alignment too), which returns 0 or what its fail() returned.  Returns a flavour's error
+// code (< 0; fail(message) makes a GBL_ERR_ARG of a message), 0 where there is nothing to do (GBL_OK), or 1: the flavour goes on
+// with the strides (and its alignments) and runs.  most: the larger tree of the sides that search.
+template <typename Ev, typename Fail, typename Side>
+inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, Side &&side)
+{
+    const bool uct = c.run == kRunSearch;
+    const int searching = uct ? kPolicyTree : kPolicyEvalTree;
+    if (c.n < 0) return fail("n < 0");
+    const char *why = uct ? collect_search_error(c.illegal_mode, c.policy[0], c.policy[1], c.iterations[0], c.iterations[1], c.playouts[0],
+                                                 c.playouts[1], c.max_plies, c.explore, c.sample_plies, c.turn != nullptr, c.ply0, c.plies,
+                                                 c.env_base, c.n)
+                          : collect_solve_error(c.illegal_mode, c.policy[0], c.policy[1], c.ev[0], c.ev[1], c.iterations[0], c.iterations[1],
+                                                c.solve_depth[0], c.solve_depth[1], c.explore, c.sample_plies, c.turn != nullptr, c.ply0,
+                                                c.plies, c.env_base, c.n);
+    if (why) return fail(why);
+    if (!uct && ((c.policy[0] == searching && noise_error(c.noise[0])) || (c.policy[1] == searching && noise_error(c.noise[1]))))
+        return fail("noise0 / noise1 must be in [0, 256]");
+    if (c.n == 0) return 0;
+    if (!c.state) return fail("state must not be NULL");
+    if (!c.to_move) return fail("to_move must not be NULL");
+    if (!c.done) return fail("done must not be NULL");
+    if (c.plies == 0) return 0;
+    most = 0;
+    for (int m = 0; m < 2; ++m) {
+        if (c.policy[m] != searching) continue;  // (a RANDOM side's evaluator and budget are not read)
+        if (!uct)
+            if (const int e = side(m)) return e;
+        most = c.iterations[m] > most ? c.iterations[m] : most;
+    }
+    return 1;
+}
+
 // gbl_solve: every check, in the order both flavours report them.  Returns the message (nullptr: none) and, in `code`, which error
 // it is (0 = GBL_ERR_ARG, 1 = GBL_ERR_ALIGN).  n == 0 passes whatever the pointers are: the caller returns GBL_OK before using them.
 inline const char *solve_error(int depth, int64_t n, const void *state, const void *to_move, const void *action_out, int &code)

@@ -4413,6 +4413,64 @@ int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const
                                    n, stream);
 }
 
+// The four self-play entry points between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
+// evaluators as the kernels take them, the trajectory's strides and alignments, the grid, the tree's LDS and the entry's own kernel.
+static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &c, void *stream)
+{
+    EvalNet nets[2] = {};  // (a RANDOM side's stays empty: the kernel never reads it)
+    int most = 0;          // the larger tree of the sides that search
+    const int go = selfplay_prologue(c, most, [](const char *why) { return fail(GBL_ERR_ARG, why); },
+                                     [&](int m) { return eval_net_of(c.ev[m], nets[m]); });
+    if (go <= 0) return go;
+    const bool uct = c.run == kRunSearch;
+    const SelfplayTraj &t = c.traj;
+    const SearchTraj T{t.actions, t.winner, t.reward, t.done, t.to_move, t.mask, t.obs, t.visits, t.value, t.nodes, t.how, t.mover};
+    if (const int e = check_search_traj(T, reinterpret_cast<uintptr_t>(t.root_value),
+                                        uct ? "actions_traj / value_traj / nodes_traj must be 4-byte aligned"
+                                            : "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned",
+                                        c.n, c.plies, c.ply_stride, c.tile_stride, c.state, c.turn, c.counters))
+        return e;
+    const dim3 grid((uint32_t)std::min<int64_t>(c.n, 1 << 20));
+    const hipStream_t s = (hipStream_t)stream;
+    const uint32_t its0 = (uint32_t)c.iterations[0], its1 = (uint32_t)c.iterations[1], explore = (uint32_t)c.explore;
+    // the tree: one node per iteration and the root; with an evaluator a prior row beside each (36.9 KB at 512 iterations, as
+    // gbl_tree_search_eval; the solver's arrays are static LDS beside it)
+    const size_t lds = (sizeof(TreeNode) + (uct ? 0 : kEvalOutputs)) * ((size_t)most + 1);
+    if (uct) {
+        // the larger leaf of the sides that search
+        const int wide = std::max(1, std::max(c.policy[0] == GBL_POLICY_TREE ? c.playouts[0] : 0, c.policy[1] == GBL_POLICY_TREE ? c.playouts[1] : 0));
+#define GBL_CS(W)                                                                                                                         \
+    hipLaunchKernelGGL((k_collect_search<W>), grid, dim3(64 * W), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,    \
+                       c.plies, c.done, c.ply_stride, c.tile_stride, T, c.policy[0], c.policy[1], its0, its1, (uint32_t)c.playouts[0],       \
+                       (uint32_t)c.playouts[1], (uint32_t)c.max_plies, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn)
+        switch (tree_waves(c.n, wide)) {
+        case 4: GBL_CS(4); break;
+        case 2: GBL_CS(2); break;
+        default: GBL_CS(1); break;
+        }
+#undef GBL_CS
+    } else if (c.run == kRunEval) {
+        hipLaunchKernelGGL(k_collect_eval, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
+                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1], its0,
+                           its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn);
+    } else {
+        const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
+                       w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
+        // (k_collect_solve<false> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked)
+#define GBL_CSV(NOISE)                                                                                                                    \
+    hipLaunchKernelGGL(k_collect_solve<NOISE>, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,       \
+                       c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1],       \
+                       c.policy[0], c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies,    \
+                       c.illegal_mode, c.counters, c.turn, w0, w1)
+        if (w0 | w1)
+            GBL_CSV(true);
+        else
+            GBL_CSV(false);
+#undef GBL_CSV
+    }
+    GBL_LAUNCHED(name);
+}
+
 int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
                        int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
                        int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int64_t n, int64_t ply_stride,
@@ -4420,35 +4478,14 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
                        int policy0, int policy1, int iterations0, int iterations1, int playouts0, int playouts1, int max_plies,
                        int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = collect_search_error(illegal_mode, policy0, policy1, iterations0, iterations1, playouts0, playouts1, max_plies,
-                                               explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
-        return fail(GBL_ERR_ARG, why);
-    // the larger tree and the larger leaf of the sides that search
-    const int most = std::max(policy0 == GBL_POLICY_TREE ? iterations0 : 0, policy1 == GBL_POLICY_TREE ? iterations1 : 0);
-    const int wide = std::max(1, std::max(policy0 == GBL_POLICY_TREE ? playouts0 : 0, policy1 == GBL_POLICY_TREE ? playouts1 : 0));
-    if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (plies == 0) return GBL_OK;
-    const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                       nodes_traj, how_traj, mover_traj};
-    if (const int e = check_search_traj(T, 0, "actions_traj / value_traj / nodes_traj must be 4-byte aligned", n, plies, ply_stride,
-                                        tile_stride, state, turn, counters))
-        return e;
-    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
-    const size_t lds = sizeof(TreeNode) * ((size_t)most + 1);  // the tree: one node per iteration and the root
-    const hipStream_t s = (hipStream_t)stream;
-#define GBL_CS(W)                                                                                                                    \
-    hipLaunchKernelGGL((k_collect_search<W>), grid, dim3(64 * W), lds, s, state, to_move, n, seed, env_base, ply_dev, ply0, plies, done, \
-                       ply_stride, tile_stride, T, policy0, policy1, (uint32_t)iterations0, (uint32_t)iterations1, (uint32_t)playouts0,  \
-                       (uint32_t)playouts1, (uint32_t)max_plies, (uint32_t)explore, sample_plies, illegal_mode, counters, turn)
-    switch (tree_waves(n, wide)) {
-    case 4: GBL_CS(4); break;
-    case 2: GBL_CS(2); break;
-    default: GBL_CS(1); break;
-    }
-#undef GBL_CS
-    GBL_LAUNCHED("gbl_collect_search");
+    return selfplay_launch("gbl_collect_search",
+                           {kRunSearch, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {nullptr, nullptr},
+                            {iterations0, iterations1}, {playouts0, playouts1}, {0, 0}, {0, 0}, max_plies, explore, sample_plies, illegal_mode,
+                            counters, turn},
+                           stream);
 }
 
 int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
@@ -4459,88 +4496,14 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
                             const gbl_evaluator *ev1, int iterations0, int iterations1, int explore, int sample_plies, int illegal_mode,
                             int64_t *counters, int32_t *turn, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = collect_eval_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, explore, sample_plies,
-                                             turn != nullptr, ply0, plies, env_base, n))
-        return fail(GBL_ERR_ARG, why);
-    if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (plies == 0) return GBL_OK;
-    const gbl_evaluator *evs[2] = {ev0, ev1};
-    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
-    EvalNet nets[2] = {};  // (a RANDOM side's stays empty: the kernel never reads it)
-    int most = 0;          // the larger tree of the sides that search
-    for (int m = 0; m < 2; ++m) {
-        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
-        if (const int e = eval_net_of(evs[m], nets[m])) return e;
-        most = std::max(most, its[m]);
-    }
-    const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                       nodes_traj, how_traj, mover_traj};
-    if (const int e = check_search_traj(T, reinterpret_cast<uintptr_t>(root_value_traj),
-                                        "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned", n, plies,
-                                        ply_stride, tile_stride, state, turn, counters))
-        return e;
-    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
-    // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations, as gbl_tree_search_eval)
-    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)most + 1);
-    hipLaunchKernelGGL(k_collect_eval, grid, dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed,
-                       env_base, ply_dev, ply0, plies, done, ply_stride, tile_stride, T, root_value_traj, priors_traj, nets[0], nets[1], policy0,
-                       policy1, (uint32_t)iterations0, (uint32_t)iterations1, (uint32_t)most, (uint32_t)explore, sample_plies, illegal_mode,
-                       counters, turn);
-    GBL_LAUNCHED("gbl_collect_search_eval");
-}
-
-// gbl_collect_search_solve and gbl_collect_search_noise: one kernel in two instantiations, with and without the noise's code
-static int collect_solve_launch(const char *name, int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                             int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
-                             int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
-                             uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
-                             int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
-                             int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
-                             int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
-                             int64_t *counters, int32_t *turn, void *stream)
-{
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = collect_solve_error(illegal_mode, policy0, policy1, ev0, ev1, iterations0, iterations1, solve_depth0, solve_depth1,
-                                              explore, sample_plies, turn != nullptr, ply0, plies, env_base, n))
-        return fail(GBL_ERR_ARG, why);
-    if ((policy0 == GBL_POLICY_EVAL_TREE && noise_error(noise0)) || (policy1 == GBL_POLICY_EVAL_TREE && noise_error(noise1)))
-        return fail(GBL_ERR_ARG, "noise0 / noise1 must be in [0, 256]");
-    if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (plies == 0) return GBL_OK;
-    const gbl_evaluator *evs[2] = {ev0, ev1};
-    const int its[2] = {iterations0, iterations1}, pol[2] = {policy0, policy1};
-    EvalNet nets[2] = {};  // (a RANDOM side's stays empty: the kernel never reads it)
-    int most = 0;          // the larger tree of the sides that search
-    for (int m = 0; m < 2; ++m) {
-        if (pol[m] != GBL_POLICY_EVAL_TREE) continue;
-        if (const int e = eval_net_of(evs[m], nets[m])) return e;
-        most = std::max(most, its[m]);
-    }
-    const SearchTraj T{actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                       nodes_traj, how_traj, mover_traj};
-    if (const int e = check_search_traj(T, reinterpret_cast<uintptr_t>(root_value_traj),
-                                        "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned", n, plies,
-                                        ply_stride, tile_stride, state, turn, counters))
-        return e;
-    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
-    // the tree as gbl_collect_search_eval; the solver's arrays are static LDS beside it
-    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)most + 1);
-    const uint32_t w0 = policy0 == GBL_POLICY_EVAL_TREE ? (uint32_t)noise0 : 0u, w1 = policy1 == GBL_POLICY_EVAL_TREE ? (uint32_t)noise1 : 0u;
-    // (k_collect_solve<false> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked)
-#define GBL_CSV(NOISE)                                                                                                                    \
-    hipLaunchKernelGGL(k_collect_solve<NOISE>, grid, dim3(64), lds, (hipStream_t)stream, state, to_move, n, seed, env_base, ply_dev, ply0,   \
-                       plies, done, ply_stride, tile_stride, T, root_value_traj, priors_traj, outcome_traj, proven_traj, nets[0], nets[1],   \
-                       policy0, policy1, (uint32_t)iterations0, (uint32_t)iterations1, solve_depth0, solve_depth1, (uint32_t)most,           \
-                       (uint32_t)explore, sample_plies, illegal_mode, counters, turn, w0, w1)
-    if (w0 | w1)
-        GBL_CSV(true);
-    else
-        GBL_CSV(false);
-#undef GBL_CSV
-    GBL_LAUNCHED(name);
+    return selfplay_launch("gbl_collect_search_eval",
+                           {kRunEval, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn},
+                           stream);
 }
 
 int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
@@ -4552,11 +4515,14 @@ int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32
                              int solve_depth0, int solve_depth1, int explore, int sample_plies, int illegal_mode, int64_t *counters,
                              int32_t *turn, void *stream)
 {
-    return collect_solve_launch("gbl_collect_search_solve", state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj,
-                                to_move_traj, mask_traj, obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj,
-                                priors_traj, outcome_traj, proven_traj, n,
-                                ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1, iterations0, iterations1,
-                                solve_depth0, solve_depth1, 0, 0, explore, sample_plies, illegal_mode, counters, turn, stream);
+    return selfplay_launch("gbl_collect_search_solve",
+                           {kRunSolve, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {0, 0}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn},
+                           stream);
 }
 
 int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
@@ -4568,11 +4534,14 @@ int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32
                              int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
                              int64_t *counters, int32_t *turn, void *stream)
 {
-    return collect_solve_launch("gbl_collect_search_noise", state, to_move, done, actions_traj, winner_traj, reward_traj, done_traj,
-                                to_move_traj, mask_traj, obs_traj, visits_traj, value_traj, nodes_traj, how_traj, mover_traj, root_value_traj,
-                                priors_traj, outcome_traj, proven_traj, n,
-                                ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, ev0, ev1, iterations0, iterations1,
-                                solve_depth0, solve_depth1, noise0, noise1, explore, sample_plies, illegal_mode, counters, turn, stream);
+    return selfplay_launch("gbl_collect_search_noise",
+                           {kRunSolve, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn},
+                           stream);
 }
 
 int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

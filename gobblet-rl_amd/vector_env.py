@@ -451,22 +451,21 @@ class BatchedGobblet:
         ep = self._evaluator_params(policies, search)  # None unless a side plays the evaluator-guided search
         sp = ep if ep is not None else self._search_params(policies, search)  # None unless a side plays a tree search
         guarded = ep is not None and any(ep["solve_depth"])  # (the solver in front of an evaluator side's searches)
+        def fresh():  # buffers for this call's entry point, made (and placed) now
+            return self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
+                                           search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
+                                           far=False)
         if isinstance(out, str):
             if out != "fresh":
                 raise ValueError("out: a dict from trajectory_buffers(), None (the environment's staging buffers) or 'fresh'")
-            # buffers of the caller's own: made (and placed) now, not kept by the environment, never overwritten by a later call
-            out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                          search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
-                                          far=False)
+            out = fresh()  # the caller's own: not kept by the environment, never overwritten by a later call
         if out is None:
             key = (T, layout, policies is not None) + (("search",) if sp is not None else ()) + (("evaluator",) if ep is not None else ()) + \
                 (("solver",) if guarded else ())
             out = self._staging.pop(key, None)
             made = out is None
             if made:
-                out = self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                              search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
-                                              far=False)
+                out = fresh()
             # (buffers made inside a graph capture belong to the graph's private pool: not kept beyond it)
             capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
             if not (made and capturing):
@@ -494,34 +493,25 @@ class BatchedGobblet:
                 raise ValueError("sample_plies needs the per-board turn counter: create the environment with track_turn=True")
             if opening_plies:
                 raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
-            # what the two self-play entry points take alike: the boards and the 12 trajectory arrays, the window, and the tail
-            head = (self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
+            # one argument list for the four self-play entry points: any noise weight -> _noise (the guarded kernel, whatever the
+            # depths), else any solve depth -> _solve, else an evaluator side -> _eval, else the UCT search
+            entry = "gbl_collect_search" + ("" if ep is None else "_noise" if any(ep["noise"]) else "_solve" if guarded else "_eval")
+            args = [self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
                     f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
                     f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
-                    nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover")))
-            window = (n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T)
-            tail = (sp["sample_plies"], self.illegal_mode, self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream())
-            if ep is not None and any(ep["noise"]):  # (root noise on a side: the guarded kernel, whatever the depths)
-                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
-                nat.check(self._lib.gbl_collect_search_noise(
-                    *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), nat.ptr(f.get("outcomes")), nat.ptr(f.get("proven")),
-                    *window, *ep["policies"], *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
-                    *ep["solve_depth"], *ep["noise"], ep["explore"], *tail), "gbl_collect_search_noise")
-            elif guarded:
-                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
-                nat.check(self._lib.gbl_collect_search_solve(
-                    *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), nat.ptr(f.get("outcomes")), nat.ptr(f.get("proven")),
-                    *window, *ep["policies"], *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
-                    *ep["solve_depth"], ep["explore"], *tail), "gbl_collect_search_solve")
-            elif ep is not None:
-                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
-                nat.check(self._lib.gbl_collect_search_eval(
-                    *head, nat.ptr(f.get("root_value")), nat.ptr(f.get("priors")), *window, *ep["policies"],
-                    *[None if st is None else C.addressof(st) for st in structs], *ep["iterations"], ep["explore"], *tail),
-                    "gbl_collect_search_eval")
+                    nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover"))]
+            if ep is None:
+                sides = [*sp["iterations"], *sp["playouts"], sp["max_plies"]]
             else:
-                nat.check(self._lib.gbl_collect_search(*head, *window, *sp["policies"], *sp["iterations"], *sp["playouts"], sp["max_plies"],
-                                                       sp["explore"], *tail), "gbl_collect_search")
+                solver, noise = not entry.endswith("_eval"), entry.endswith("_noise")
+                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
+                args += [nat.ptr(f.get(k)) for k in ("root_value", "priors") + (("outcomes", "proven") if solver else ())]
+                sides = [*[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
+                         *(ep["solve_depth"] if solver else ()), *(ep["noise"] if noise else ())]
+            nat.check(getattr(self._lib, entry)(
+                *args, n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T,
+                *sp["policies"], *sides, sp["explore"], sp["sample_plies"], self.illegal_mode,
+                self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream()), entry)
         elif policies is not None:
             try:
                 p0, p1 = (self.POLICIES[x] if isinstance(x, str) else int(x) for x in policies)

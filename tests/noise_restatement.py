@@ -147,9 +147,3 @@ def restate_collect_noise(st, tm, turn, T, pols, nets, its, deps, noise, X, samp
                      ("proven", proven)):
             out[k].append(v)
     return {k: np.stack(v) for k, v in out.items()}, st, tm, dn, turn
-
-
-def with_noise(f, noise):
-    """gbl(_cpu)_collect_search_noise under the argument list of gbl(_cpu)_collect_search_solve (tests/test_selfplay_solve.py's
-    solve_call): the two weights go in after the 35 arguments that end with solve_depth1."""
-    return lambda *a: f(*a[:35], int(noise[0]), int(noise[1]), *a[35:])

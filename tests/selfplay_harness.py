@@ -1,0 +1,148 @@
+"""What the tests of the four self-play entry points (gbl_collect_search, _eval, _solve, _noise; either flavour) share: the output
+tables, the trajectory geometry, ONE argument list, one runner on host arrays and one on the device (every output filled with -7 /
+99 first: nothing outside the cells may be written), the comparison, and the evaluator helpers.  A plain module: no fixtures."""
+import ctypes as C
+
+import numpy as np
+
+import gobblet_rl_amd as G
+from gobblet_rl_amd import _native as nat
+
+DEV = "cuda:0"
+PAD = 16     # elements of -7 / 99 kept before and after every output on the device (16: the rows keep their 16-byte alignment)
+SCALARS = (("actions", np.int32, ()), ("winner", np.int8, ()), ("rewards", np.int8, (2,)), ("done", np.int8, ()),
+           ("to_move", np.int8, ()), ("action_mask", np.int8, (54,)), ("observation", np.int8, (117,)), ("visits", np.int16, (54,)),
+           ("value", np.int32, ()), ("nodes", np.int32, ()), ("how", np.int8, ()), ("mover", np.int8, ()))
+EVAL_NAMES = SCALARS + (("root_value", np.int32, ()), ("priors", np.uint8, (54,)))
+SOLVE_NAMES = EVAL_NAMES + (("outcomes", np.int8, (54,)), ("proven", np.int8, ()))
+NAMES = {"search": SCALARS, "eval": EVAL_NAMES, "solve": SOLVE_NAMES, "noise": SOLVE_NAMES}  # entry point -> its outputs, in ABI order
+CODES = {"random": nat.POLICY_RANDOM, "tree": nat.POLICY_TREE, "eval": nat.POLICY_EVAL_TREE}
+
+
+def strides(n, T, layout):
+    tiles = -(-n // 64)
+    if layout == "time":
+        slot = tiles * 64 + 64  # (a padded slot: the stride is not the board count)
+        return slot, 64, T * slot
+    return 64, 64 * T, tiles * T * 64
+
+
+def cells(n, T, layout):
+    ps, ts, _ = strides(n, T, layout)
+    b = np.arange(n)
+    return np.arange(T)[:, None] * ps + (b // 64) * ts + b % 64  # (T, n)
+
+
+def call_args(entry, ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, X, sample_plies, illegal_mode, counters, tn, stream,
+              its=(0, 0), pls=(0, 0), M=0, evs=(None, None), deps=(0, 0), noise=(0, 0)):
+    """The argument list of gbl(_cpu)_collect_search ("search"), _eval, _solve or _noise; ptr(x) turns an array (or None) into a
+    pointer, evs are gbl_evaluator structs (or None)."""
+    if entry == "search":
+        sides = [its[0], its[1], pls[0], pls[1], M]
+    else:
+        sides = [*[None if e is None else C.addressof(e) for e in evs], its[0], its[1]] + \
+            ([deps[0], deps[1]] if entry != "eval" else []) + ([int(noise[0]), int(noise[1])] if entry == "noise" else [])
+    return [ptr(st), ptr(tm), ptr(dn), *[ptr(traj.get(k)) for k, _, _ in NAMES[entry]], n, ps, ts, seed, env_base, ply0, ptr(pd), T,
+            CODES[pols[0]], CODES[pols[1]], *sides, X, sample_plies, illegal_mode, ptr(counters), ptr(tn), stream]
+
+
+def _run(entry, f, ok, put, get, ptr, pad, stream, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0,
+         ply_dev, keep, counters, nets, **sides):
+    n = len(st)
+    ps, ts, total = strides(n, T, layout)
+    keep = [k for k, _, _ in NAMES[entry]] if keep is None else keep
+    full = {k: put(np.full((total + 2 * pad,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in NAMES[entry] if k in keep}
+    traj = {k: v[pad:] for k, v in full.items()}
+    st, tm, dn = put(np.ascontiguousarray(st, np.int8)), put(np.ascontiguousarray(tm, np.int8)), put(np.full(n, 5, np.int8))
+    tn = None if turn is None else put(np.ascontiguousarray(turn, np.int32))
+    pd = None if ply_dev is None else put(np.array([ply_dev], np.int32))
+    evs = [None if net is None else net.struct() for net in nets]  # (alive until the call has returned)
+    ok(f(*call_args(entry, ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, X, sample_plies, illegal_mode, counters, tn,
+                    stream, evs=evs, **sides)))
+    at = cells(n, T, layout)
+    untouched = np.ones(total + 2 * pad, bool)
+    untouched[at.ravel() + pad] = False
+    host = {k: get(v) for k, v in full.items()}
+    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
+        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
+    return {k: v[pad:][at] for k, v in host.items()}, get(st), get(tm), get(dn), None if tn is None else get(tn)
+
+
+def host_collect(entry, f, err, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None,
+                 counters=None, nets=(None, None), **sides):
+    """`f` = gbl_cpu_collect_search* of `entry` on host arrays; only the outputs named in `keep` are given (None: all); sides: its=,
+    pls=, M=, deps=, noise=; nets: restatement Nets.  Returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
+    def ok(rc):
+        assert rc == 0, err()
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+    return _run(entry, f, ok, np.array, lambda a: a, ptr, 0, None, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base,
+                ply0, ply_dev, keep, counters, nets, **sides)
+
+
+def device_collect(entry, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None,
+                   nets=(None, None), **sides):
+    """gbl_collect_search* of `entry` on the device, every output between canaries; nets: DeviceNets; the same return value as
+    host_collect."""
+    import torch
+    name = "gbl_collect_search" + ("" if entry == "search" else "_" + entry)
+
+    def get(t):
+        torch.cuda.synchronize()
+        return t.cpu().numpy()
+    return _run(entry, getattr(nat.lib(), name), lambda rc: nat.check(rc, name), lambda a: torch.from_numpy(a).to(DEV), get, nat.ptr, PAD,
+                nat.current_stream(DEV), st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, None,
+                nets, **sides)
+
+
+def same(got, exp):
+    for k in got[0]:
+        assert got[0][k].dtype == exp[0][k].dtype and np.array_equal(got[0][k], exp[0][k]), (k, np.argwhere(got[0][k] != exp[0][k])[:5])
+    for name, g, e in zip(("state", "to_move", "done", "turn"), got[1:], exp[1:]):
+        if g is not None:
+            assert np.array_equal(g, e), name
+
+
+class DeviceNet:
+    """A restatement Net with its four arrays on the device."""
+
+    def __init__(self, net):
+        import torch
+        self.net = net
+        self.arrays = [torch.from_numpy(a).to(DEV) for a in (net.w1, net.b1, net.w2, net.b2)]
+        assert all(a.data_ptr() % 16 == 0 for a in self.arrays)
+
+    def struct(self):
+        return self.net.struct(self.arrays)
+
+
+def _evaluator(net, device="cpu"):
+    return G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, net.shift1, net.shift_p, net.shift_v, device=device)
+
+
+def recorded_call(lib, prefix, case):
+    """One case of a tests/golden/*_arg_errors.json table whose argument lists hold evaluators: every "ev" is the next evaluator of
+    case["evs"], given as its eight fields (or null); every pointer is a number that is never read (all calls return before any
+    work).  Returns the return code."""
+    evs = [None if e is None else nat.Evaluator(*e) for e in case["evs"]]
+    it = iter(evs)
+    args = []
+    for x in case["args"]:
+        if x == "ev":
+            e = next(it)
+            x = None if e is None else C.addressof(e)
+        args.append(x)
+    return getattr(lib, prefix + case["fn"])(*args)
+
+
+def replay_arg_errors(table):
+    """Every case of such a table on both flavours: the recorded return code and, for an error, the recorded message."""
+    for c in table:
+        for flavour, lib, prefix in (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_")):
+            if c[flavour] is None:  # (an alignment rule: only the device flavour has it)
+                continue
+            rc, msg = c[flavour]
+            assert recorded_call(lib, prefix, c) == rc, (flavour, c["fn"], c["case"])
+            if rc:
+                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])

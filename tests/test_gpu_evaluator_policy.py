@@ -10,6 +10,7 @@ import torch
 
 import oracle
 from tests import evaluator_restatement as R
+from tests.selfplay_harness import DeviceNet
 from tests.test_playout_policy import UNCOVER_SEQ, WIN_SEQ, play
 
 pytestmark = pytest.mark.gpu
@@ -39,18 +40,6 @@ def c5(G):
     (sw, mw), (su, mu) = play(WIN_SEQ), play(UNCOVER_SEQ)  # boards 1 and 2: roots one move from a decided game
     st[1], tm[1], st[2], tm[2] = sw, mw, su, mu
     return st, tm
-
-
-class DeviceNet:
-    """A restatement Net with its four arrays on the device."""
-
-    def __init__(self, net):
-        self.net = net
-        self.arrays = [torch.from_numpy(a).to(DEV) for a in (net.w1, net.b1, net.w2, net.b2)]
-        assert all(a.data_ptr() % 16 == 0 for a in self.arrays)
-
-    def struct(self):
-        return self.net.struct(self.arrays)
 
 
 def guarded(n, width, dtype, fill):

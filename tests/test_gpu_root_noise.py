@@ -13,15 +13,13 @@ import oracle
 
 from tests import evaluator_restatement as R
 from tests import noise_restatement as N
-from tests.test_selfplay_eval import same
-from tests.test_selfplay_search import cells, strides
-from tests.test_selfplay_solve import EXPLORE, NAMES, collect_solve, fixture_boards, smoke_net, solve_call
+from tests import selfplay_harness as H
+from tests.selfplay_harness import DEV, PAD, DeviceNet, _evaluator, same
+from tests.test_selfplay_solve import EXPLORE, collect_solve, fixture_boards, smoke_net
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 THREADS = 16
-PAD = 16     # elements of -7 / 99 kept before and after every output (16: the rows keep their 16-byte alignment)
 SEED, ENV_BASE, CALL = 0x1234567890ABCDEF, (1 << 40) + 3, (1 << 24) - 1
 
 
@@ -37,18 +35,6 @@ def G():
 @pytest.fixture(scope="module")
 def c5(G):
     return fixture_boards(256, DEV)
-
-
-class DeviceNet:
-    """A restatement Net with its four arrays on the device."""
-
-    def __init__(self, net):
-        self.net = net
-        self.arrays = [torch.from_numpy(a).to(DEV) for a in (net.w1, net.b1, net.w2, net.b2)]
-        assert all(a.data_ptr() % 16 == 0 for a in self.arrays)
-
-    def struct(self):
-        return self.net.struct(self.arrays)
 
 
 def device_search_noise(G, dnet, st, tm, mask, iterations, explore, w, seed, env_base, call, keep=N.NOISE_SEARCH_NAMES):
@@ -126,37 +112,13 @@ def test_masked_roots_and_null_outputs(G, c5):
 # ---- self-play -----------------------------------------------------------------------------------------------------------------------
 def host_collect(G, noise, *args, **kw):
     cpu = G._native.cpu_raw()
-    f = cpu.gbl_cpu_collect_search_solve if noise is None else N.with_noise(cpu.gbl_cpu_collect_search_noise, noise)
-    return collect_solve(f, cpu.gbl_cpu_last_error, *args, **kw)
+    f = cpu.gbl_cpu_collect_search_solve if noise is None else cpu.gbl_cpu_collect_search_noise
+    return collect_solve(f, cpu.gbl_cpu_last_error, *args, noise=noise, **kw)
 
 
-def device_collect(G, noise, st, tm, turn, T_, pols, dnets, its, deps, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None,
-                   keep=None):
-    """gbl_collect_search_noise (noise None: gbl_collect_search_solve) on the device, every output between canaries; the same
-    return value as collect_solve."""
-    nat = G._native
-    n = len(st)
-    ps, ts, total = strides(n, T_, layout)
-    keep = [k for k, _, _ in NAMES] if keep is None else keep
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
-    full = {k: dev(np.full((total + 2 * PAD,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in NAMES if k in keep}
-    traj = {k: v[PAD:] for k, v in full.items()}
-    d_st, d_tm, d_dn = dev(st.astype(np.int8)), dev(tm.astype(np.int8)), dev(np.full(n, 5, np.int8))
-    d_tn = None if turn is None else dev(turn.astype(np.int32))
-    d_pd = None if ply_dev is None else dev(np.array([ply_dev], np.int32))
-    evs = [None if d is None else d.struct() for d in dnets]
-    f = nat.lib().gbl_collect_search_solve if noise is None else N.with_noise(nat.lib().gbl_collect_search_noise, noise)
-    nat.check(solve_call(f, traj, d_st, d_tm, d_dn, d_tn, d_pd, n, ps, ts, seed, env_base, ply0, T_, pols, evs, its, deps, X, sample_plies,
-                         illegal_mode, None, nat.current_stream(DEV), nat.ptr), "gbl_collect_search_noise")
-    torch.cuda.synchronize()
-    at = cells(n, T_, layout)
-    untouched = np.ones(total + 2 * PAD, bool)
-    untouched[at.ravel() + PAD] = False
-    host = {k: v.cpu().numpy() for k, v in full.items()}
-    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
-    return ({k: v[PAD:][at] for k, v in host.items()}, d_st.cpu().numpy(), d_tm.cpu().numpy(), d_dn.cpu().numpy(),
-            None if d_tn is None else d_tn.cpu().numpy())
+# gbl_collect_search_noise (noise None: gbl_collect_search_solve) on the device, every output between canaries (H.device_collect)
+device_collect = lambda G, noise, st, tm, turn, T_, pols, dnets, its, deps, X, *a, **kw: H.device_collect(  # noqa: E731
+    "solve" if noise is None else "noise", st, tm, turn, T_, pols, X, *a, nets=dnets, its=its, deps=deps, noise=noise or (0, 0), **kw)
 
 
 @pytest.fixture(scope="module")
@@ -186,10 +148,6 @@ def test_k_collect_noise_equals_host_flavour(G, c5, nets, n):
     same(device_collect(G, (999, 128), *args[:5], (None, dn[1]), *args[6:]), host_collect(G, (-5, 128), *args[:5], (None, hn[1]), *args[6:]))
 
 
-def _evaluator(G, net, device):
-    return G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, net.shift1, net.shift_p, net.shift_v, device=device)
-
-
 KEYS = ("actions", "visits", "value", "nodes", "how", "mover", "root_value", "priors", "outcomes", "proven", "observation", "done")
 
 
@@ -199,7 +157,7 @@ def test_graph_capture_and_replay(G):
     n, T_, seed = 130, 3, 7
     net = smoke_net()
     kw = lambda d: dict(policies=("evaluator", "evaluator"),  # noqa: E731
-                        search=dict(evaluator=_evaluator(G, net, d), iterations=8, solve_depth=(2, 0), sample_plies=2, noise=(0.25, 1.0)))
+                        search=dict(evaluator=_evaluator(net, d), iterations=8, solve_depth=(2, 0), sample_plies=2, noise=(0.25, 1.0)))
     env = G.BatchedGobblet(n, DEV, auto_reset=True, seed=seed, track_turn=True)
     env.rollout(20)
     env.device_ply()

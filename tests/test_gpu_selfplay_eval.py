@@ -3,7 +3,6 @@ contract, bit for bit and with canaries around every output; against the compose
 the device; a batch beyond the grid cap; a graph capture with the weights refreshed in place; NULL optional outputs; and
 BatchedGobblet.collect with two policy instances.  (k_collect_eval has one instantiation -- one wavefront per board -- so the
 batch sizes are those of cell()'s tile edge: 1, 3, 63, 64, 65 and 257 boards.)"""
-import ctypes as C
 import os
 import sys
 
@@ -13,17 +12,16 @@ import torch
 
 import oracle
 from tests import evaluator_restatement as R
-from tests.test_selfplay_eval import CODES, NAMES, collect_eval, restate_collect, same
-from tests.test_selfplay_search import cells, strides
+from tests import selfplay_harness as H
+from tests.selfplay_harness import DEV, DeviceNet, same
+from tests.test_selfplay_eval import collect_eval, restate_collect
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-DEV = "cuda:0"
 THREADS = 16
 GRID_CAP = 1 << 20
-PAD = 16     # elements of -7 / 99 kept before and after every output (16: the rows keep their 16-byte alignment)
 
 
 @pytest.fixture(scope="module")
@@ -45,50 +43,13 @@ def c5(G):
     return st, tm, turn
 
 
-class DeviceNet:
-    """A restatement Net with its four arrays on the device."""
-
-    def __init__(self, net):
-        self.net = net
-        self.arrays = [torch.from_numpy(a).to(DEV) for a in (net.w1, net.b1, net.w2, net.b2)]
-        assert all(a.data_ptr() % 16 == 0 for a in self.arrays)
-
-    def struct(self):
-        return self.net.struct(self.arrays)
-
-
 def host_collect(G, *args, **kw):
     cpu = G._native.cpu_raw()
     return collect_eval(cpu.gbl_cpu_collect_search_eval, cpu.gbl_cpu_last_error, *args, **kw)
 
 
-def device_collect(G, st, tm, turn, T, pols, dnets, its, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None):
-    """gbl_collect_search_eval on the device, every output between canaries; the same return value as collect_eval."""
-    nat = G._native
-    n = len(st)
-    ps, ts, total = strides(n, T, layout)
-    keep = [k for k, _, _ in NAMES] if keep is None else keep
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
-    # (the canaries sit in front of cell 0 and behind the last cell; 16 elements keep the rows' 16-byte alignment)
-    pad = PAD
-    traj = {k: dev(np.full((total + 2 * pad,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in NAMES if k in keep}
-    d_st, d_tm, d_dn = dev(st.astype(np.int8)), dev(tm.astype(np.int8)), dev(np.full(n, 5, np.int8))
-    d_tn = None if turn is None else dev(turn.astype(np.int32))
-    d_pd = None if ply_dev is None else dev(np.array([ply_dev], np.int32))
-    evs = [None if d is None else d.struct() for d in dnets]
-    nat.check(nat.lib().gbl_collect_search_eval(
-        d_st.data_ptr(), d_tm.data_ptr(), d_dn.data_ptr(), *[traj[k][pad:].data_ptr() if k in traj else None for k, _, _ in NAMES], n, ps, ts,
-        seed, env_base, ply0, nat.ptr(d_pd), T, CODES[pols[0]], CODES[pols[1]], *[None if e is None else C.addressof(e) for e in evs],
-        its[0], its[1], X, sample_plies, illegal_mode, None, nat.ptr(d_tn), nat.current_stream(DEV)), "gbl_collect_search_eval")
-    torch.cuda.synchronize()
-    at = cells(n, T, layout)
-    untouched = np.ones(total + 2 * pad, bool)
-    untouched[at.ravel() + pad] = False
-    host = {k: v.cpu().numpy() for k, v in traj.items()}
-    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
-    return ({k: v[pad:][at] for k, v in host.items()}, d_st.cpu().numpy(), d_tm.cpu().numpy(), d_dn.cpu().numpy(),
-            None if d_tn is None else d_tn.cpu().numpy())
+# gbl_collect_search_eval on the device, every output between canaries (H.device_collect), under collect_eval's argument order
+device_collect = lambda G, st, tm, turn, T, pols, dnets, its, X, *a, **kw: H.device_collect("eval", st, tm, turn, T, pols, X, *a, nets=dnets, its=its, **kw)  # noqa: E731
 
 
 def pair(h0, h1):

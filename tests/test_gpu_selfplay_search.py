@@ -12,13 +12,14 @@ import pytest
 import torch
 
 import oracle
-from tests.test_selfplay_search import CODES, GRID, SCALARS, cells, collect, restate_collect, same, strides
+from tests import selfplay_harness as H
+from tests.selfplay_harness import DEV, same
+from tests.test_selfplay_search import GRID, collect, restate_collect
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-DEV = "cuda:0"
 THREADS = 16
 
 
@@ -41,28 +42,8 @@ def c5(G):
     return st, tm, turn
 
 
-def device_collect(G, st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None):
-    """gbl_collect_search on the device; the same return value as tests.test_selfplay_search.collect."""
-    nat = G._native
-    n = len(st)
-    ps, ts, total = strides(n, T, layout)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
-    traj = {k: dev(np.full((total,) + tail, -7, dt)) for k, dt, tail in SCALARS}
-    d_st, d_tm, d_dn = dev(st.astype(np.int8)), dev(tm.astype(np.int8)), dev(np.full(n, 5, np.int8))
-    d_tn = None if turn is None else dev(turn.astype(np.int32))
-    d_pd = None if ply_dev is None else dev(np.array([ply_dev], np.int32))
-    nat.check(nat.lib().gbl_collect_search(d_st.data_ptr(), d_tm.data_ptr(), d_dn.data_ptr(), *[traj[k].data_ptr() for k, _, _ in SCALARS], n,
-                                           ps, ts, seed, env_base, ply0, nat.ptr(d_pd), T, CODES[pols[0]], CODES[pols[1]], its[0], its[1],
-                                           pls[0], pls[1], M, X, sample_plies, illegal_mode, None, nat.ptr(d_tn), nat.current_stream(DEV)),
-              "gbl_collect_search")
-    torch.cuda.synchronize()
-    at = cells(n, T, layout)
-    untouched = np.ones(total, bool)
-    untouched[at.ravel()] = False
-    host = {k: v.cpu().numpy() for k, v in traj.items()}
-    assert all((v[untouched] == -7).all() for v in host.values())  # (nothing outside the cells is written)
-    return ({k: v[at] for k, v in host.items()}, d_st.cpu().numpy(), d_tm.cpu().numpy(), d_dn.cpu().numpy(),
-            None if d_tn is None else d_tn.cpu().numpy())
+# gbl_collect_search on the device (H.device_collect) under the argument order of tests.test_selfplay_search.collect
+device_collect = lambda G, st, tm, turn, T, pols, its, pls, M, X, *a: H.device_collect("search", st, tm, turn, T, pols, X, *a, its=its, pls=pls, M=M)  # noqa: E731
 
 
 @pytest.mark.parametrize("pols,its,pls,sample_plies,illegal_mode,ply_dev", GRID)

@@ -3,7 +3,6 @@ elements around every output, at the batch sizes of cell()'s tile edge; depth 4 
 test); 512 iterations beside the solver's LDS arrays; against the Python restatement of the contract; NULL optional outputs; a batch
 beyond the grid cap; a graph capture and replay; BatchedGobblet.collect(solve_depth=) against the same on "cpu"; and the two
 performance guards of the record profiles/r16/selfplay_solve.json."""
-import ctypes as C
 import json
 import os
 import sys
@@ -14,18 +13,15 @@ import torch
 
 from tests import evaluator_restatement as R
 from tests import solver_restatement as SR
-from tests.test_selfplay_eval import same
-from tests.test_selfplay_search import cells, strides
-from tests.test_selfplay_solve import (CASES, EXPLORE, NAMES, T, WINDOW, collect_solve, fixture_boards, restated_six, six_boards, smoke_net,
-                                       solve_call)
+from tests import selfplay_harness as H
+from tests.selfplay_harness import DEV, DeviceNet, _evaluator, same
+from tests.test_selfplay_solve import CASES, EXPLORE, T, WINDOW, collect_solve, fixture_boards, restated_six, six_boards, smoke_net
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 THREADS = 16
 GRID_CAP = 1 << 20
-PAD = 16     # elements of -7 / 99 kept before and after every output (16: the rows keep their 16-byte alignment)
 
 
 @pytest.fixture(scope="module")
@@ -42,18 +38,6 @@ def c5(G):
     return fixture_boards(65536, DEV)
 
 
-class DeviceNet:
-    """A restatement Net with its four arrays on the device."""
-
-    def __init__(self, net):
-        self.net = net
-        self.arrays = [torch.from_numpy(a).to(DEV) for a in (net.w1, net.b1, net.w2, net.b2)]
-        assert all(a.data_ptr() % 16 == 0 for a in self.arrays)
-
-    def struct(self):
-        return self.net.struct(self.arrays)
-
-
 @pytest.fixture(scope="module")
 def nets(G):
     """(host nets, device nets): smoke()'s network and a second one of another width."""
@@ -66,31 +50,8 @@ def host_collect(G, *args, **kw):
     return collect_solve(cpu.gbl_cpu_collect_search_solve, cpu.gbl_cpu_last_error, *args, **kw)
 
 
-def device_collect(G, st, tm, turn, T_, pols, dnets, its, deps, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None,
-                   keep=None):
-    """gbl_collect_search_solve on the device, every output between canaries; the same return value as collect_solve."""
-    nat = G._native
-    n = len(st)
-    ps, ts, total = strides(n, T_, layout)
-    keep = [k for k, _, _ in NAMES] if keep is None else keep
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
-    full = {k: dev(np.full((total + 2 * PAD,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in NAMES if k in keep}
-    traj = {k: v[PAD:] for k, v in full.items()}
-    d_st, d_tm, d_dn = dev(st.astype(np.int8)), dev(tm.astype(np.int8)), dev(np.full(n, 5, np.int8))
-    d_tn = None if turn is None else dev(turn.astype(np.int32))
-    d_pd = None if ply_dev is None else dev(np.array([ply_dev], np.int32))
-    evs = [None if d is None else d.struct() for d in dnets]
-    nat.check(solve_call(nat.lib().gbl_collect_search_solve, traj, d_st, d_tm, d_dn, d_tn, d_pd, n, ps, ts, seed, env_base, ply0, T_, pols, evs,
-                         its, deps, X, sample_plies, illegal_mode, None, nat.current_stream(DEV), nat.ptr), "gbl_collect_search_solve")
-    torch.cuda.synchronize()
-    at = cells(n, T_, layout)
-    untouched = np.ones(total + 2 * PAD, bool)
-    untouched[at.ravel() + PAD] = False
-    host = {k: v.cpu().numpy() for k, v in full.items()}
-    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
-    return ({k: v[PAD:][at] for k, v in host.items()}, d_st.cpu().numpy(), d_tm.cpu().numpy(), d_dn.cpu().numpy(),
-            None if d_tn is None else d_tn.cpu().numpy())
+# gbl_collect_search_solve on the device, every output between canaries (H.device_collect), under collect_solve's argument order
+device_collect = lambda G, st, tm, turn, T_, pols, dnets, its, deps, X, *a, **kw: H.device_collect("solve", st, tm, turn, T_, pols, X, *a, nets=dnets, its=its, deps=deps, **kw)  # noqa: E731
 
 
 @pytest.mark.parametrize("n", [1, 3, 63, 64, 65, 257])
@@ -174,10 +135,6 @@ def test_beyond_the_grid_cap(G, c5, nets):
     assert np.array_equal(got[1], np.resize(head[1], (n, 27))) and np.array_equal(got[4], np.resize(head[4], n))
 
 
-def _evaluator(G, net, device):
-    return G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, net.shift1, net.shift_p, net.shift_v, device=device)
-
-
 KEYS = ("actions", "visits", "value", "nodes", "how", "mover", "root_value", "priors", "outcomes", "proven", "observation", "done")
 
 
@@ -185,7 +142,7 @@ def test_graph_capture_and_replay(G):
     """One captured guarded launch with ply_dev, replayed twice (gbl_counter_add advances the ply inside the graph): the same as two
     eager launches."""
     n, T_, seed = 300, 3, 7
-    ev = _evaluator(G, smoke_net(), DEV)
+    ev = _evaluator(smoke_net(), DEV)
     kw = dict(policies=("evaluator", "evaluator"), search=dict(evaluator=ev, iterations=8, solve_depth=(2, 3), sample_plies=2))
     env = G.BatchedGobblet(n, DEV, auto_reset=True, seed=seed, track_turn=True)
     env.rollout(20)
@@ -223,7 +180,7 @@ def test_collect_with_solve_depth_equals_cpu(G):
         env = G.BatchedGobblet(200, d, auto_reset=True, seed=11, env_base=3, track_turn=True)
         env.rollout(30)
         out = env.collect(4, policies=("evaluator", "evaluator"), count=True,
-                          search=dict(evaluator=_evaluator(G, net, d), iterations=(8, 5), solve_depth=(3, 2), sample_plies=40, explore=24))
+                          search=dict(evaluator=_evaluator(net, d), iterations=(8, 5), solve_depth=(3, 2), sample_plies=40, explore=24))
         env.outcome_targets(out)
         outs.append((out, env))
     torch.cuda.synchronize()

@@ -2,7 +2,6 @@
 the header text (tests/noise_restatement.py) -- the noise row, the mix, the search, the self-play loop -- plus the identities the
 contract states (w = 0, explore = 0, a board alone, a shard), the diversity the noise is there for, the recorded argument errors of
 both flavours and the Python surface on device="cpu"."""
-import ctypes as C
 import json
 import os
 
@@ -17,8 +16,8 @@ from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import noise_restatement as N
 from tests import solver_restatement as SR
+from tests.selfplay_harness import _evaluator, replay_arg_errors, same
 from tests.test_playout_policy import random_midgames
-from tests.test_selfplay_eval import same
 from tests.test_selfplay_solve import EXPLORE, collect_solve, fixture_boards, smoke_net
 
 SEED, ENV_BASE = 0xFEDCBA9876543210, (1 << 41) + 77
@@ -198,10 +197,9 @@ def test_selfplay_equals_composed_loop_and_restatement(cpu, sample_plies, deps, 
     st, tm, turn = five_boards()
     nets, its, T = (smoke_net(), R.random_net(128, 77)), (8, 5), 6
     plies, s, tn = composed_loop(cpu, st, tm, turn, T, nets, its, deps, noise, EXPLORE, sample_plies, 9, ENV_BASE, 8)
-    f = N.with_noise(cpu.gbl_cpu_collect_search_noise, noise)
     for layout, ply_dev in (("time", None), ("tile", 3)):
-        got = collect_solve(f, cpu.gbl_cpu_last_error, st, tm, turn, T, ("eval", "eval"), nets, its, deps, EXPLORE, sample_plies,
-                            nat.ILLEGAL_NOOP, layout, 9, ENV_BASE, 8 - (ply_dev or 0), ply_dev)
+        got = collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, st, tm, turn, T, ("eval", "eval"), nets, its, deps,
+                            EXPLORE, sample_plies, nat.ILLEGAL_NOOP, layout, 9, ENV_BASE, 8 - (ply_dev or 0), ply_dev, noise=noise)
         for t, ply in enumerate(plies):
             for k, v in ply.items():
                 assert np.array_equal(got[0][k][t], v), (layout, t, k)
@@ -224,10 +222,10 @@ def test_selfplay_identities(cpu):
         args = (st, tm, turn, 4, pols, use, its, deps, EXPLORE, 2, nat.ILLEGAL_TERMINATE, "tile", 3, 17, 4)
         plain = collect_solve(cpu.gbl_cpu_collect_search_solve, cpu.gbl_cpu_last_error, *args)
         # weights (0, 0): gbl_cpu_collect_search_solve on every array
-        same(collect_solve(N.with_noise(cpu.gbl_cpu_collect_search_noise, (0, 0)), cpu.gbl_cpu_last_error, *args), plain)
+        same(collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, *args, noise=(0, 0)), plain)
         if pols[0] == "random":  # a RANDOM side ignores its weight, whatever it is
-            a = collect_solve(N.with_noise(cpu.gbl_cpu_collect_search_noise, (0, 64)), cpu.gbl_cpu_last_error, *args)
-            b = collect_solve(N.with_noise(cpu.gbl_cpu_collect_search_noise, (999, 64)), cpu.gbl_cpu_last_error, *args)
+            a = collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, *args, noise=(0, 64))
+            b = collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, *args, noise=(999, 64))
             same(a, b)
             assert not np.array_equal(a[0]["visits"], plain[0]["visits"])
 
@@ -243,9 +241,9 @@ def test_noise_makes_the_games_differ(cpu):
     st, tm, turn = np.zeros((n, 27), np.int8), np.zeros(n, np.int8), np.zeros(n, np.int32)
     net = R.random_net(64, DIVERSE_NET_SEED)
     args = (st, tm, turn, T, ("eval", "eval"), (net, net), (8, 8), (0, 0), 16, 0, nat.ILLEGAL_NOOP, "time", 1, 0, 0)
-    plain = collect_solve(N.with_noise(cpu.gbl_cpu_collect_search_noise, (0, 0)), cpu.gbl_cpu_last_error, *args)[0]["actions"].T
+    plain = collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, *args, noise=(0, 0))[0]["actions"].T
     assert len({tuple(r) for r in plain}) == 1
-    noisy = collect_solve(N.with_noise(cpu.gbl_cpu_collect_search_noise, (64, 64)), cpu.gbl_cpu_last_error, *args)[0]["actions"].T
+    noisy = collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, *args, noise=(64, 64))[0]["actions"].T
     assert len({tuple(r) for r in noisy}) == DIVERSE_SEQUENCES >= 8
     k = 12  # the first boards once more against the restatement itself (a board's game depends on its id alone)
     exp = N.restate_collect_noise(st[:k], tm[:k], turn[:k], T, ("eval", "eval"), (net, net), (8, 8), (0, 0), (64, 64), 16, 0, nat.ILLEGAL_NOOP,
@@ -254,39 +252,13 @@ def test_noise_makes_the_games_differ(cpu):
 
 
 # ---- the recorded argument errors ---------------------------------------------------------------------------------------------------------
-def _call(lib, prefix, case):
-    """One case of tests/golden/noise_arg_errors.json: every "ev" of the argument list is the next evaluator of `evs`, given as its
-    eight fields (or null); every pointer is a number that is never read (all calls return before any work)."""
-    evs = [None if e is None else nat.Evaluator(*e) for e in case["evs"]]
-    it = iter(evs)
-    args = []
-    for x in case["args"]:
-        if x == "ev":
-            e = next(it)
-            x = None if e is None else C.addressof(e)
-        args.append(x)
-    return getattr(lib, prefix + case["fn"])(*args)
-
-
 def test_argument_errors_replay_the_recorded_table(golden_dir):
-    flavours = (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_"))
     table = json.load(open(os.path.join(golden_dir, "noise_arg_errors.json")))
     assert len(table) >= 20 and {c["fn"] for c in table} == {"tree_search_eval_noise", "collect_search_noise"}
-    for c in table:
-        for flavour, lib, prefix in flavours:
-            if c[flavour] is None:  # (an alignment rule: only the device flavour has it)
-                continue
-            rc, msg = c[flavour]
-            assert _call(lib, prefix, c) == rc, (flavour, c["fn"], c["case"])
-            if rc:
-                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])
+    replay_arg_errors(table)
 
 
 # ---- the Python surface on device="cpu" ----------------------------------------------------------------------------------------------------
-def _evaluator(net):
-    return G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, net.shift1, net.shift_p, net.shift_v)
-
-
 class Counting:
     """A library handle that counts the calls of every entry point it hands out."""
 
@@ -373,9 +345,9 @@ def test_collect_noise(cpu):
     assert set(env3._lib.calls) == {"gbl_collect_search_noise"} and not torch.equal(both["visits"], plain["visits"])
     ref = G.BatchedGobblet(40, "cpu", auto_reset=True, seed=11, env_base=3, track_turn=True)
     ref.rollout(30)
-    raw = collect_solve(N.with_noise(cpu.gbl_cpu_collect_search_noise, (64, 64)), cpu.gbl_cpu_last_error, ref.squares.numpy(),
-                        ref.to_move.numpy(), ref.turn.numpy(), 4, ("eval", "eval"), (net, net), (8, 8), (0, 0), 24, 40, nat.ILLEGAL_NOOP, "time",
-                        11, 3, 30)[0]
+    raw = collect_solve(cpu.gbl_cpu_collect_search_noise, cpu.gbl_cpu_last_error, ref.squares.numpy(), ref.to_move.numpy(),
+                        ref.turn.numpy(), 4, ("eval", "eval"), (net, net), (8, 8), (0, 0), 24, 40, nat.ILLEGAL_NOOP, "time", 11, 3, 30,
+                        noise=(64, 64))[0]
     for k in ("actions", "visits", "value", "nodes", "how", "root_value", "priors"):
         assert np.array_equal(both[k].numpy(), raw[k]), k
     # a pair: one side only (an arena noises one side, or none)

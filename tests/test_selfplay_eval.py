@@ -25,13 +25,10 @@ import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests.positions import terminal_roots
+from tests.selfplay_harness import EVAL_NAMES as NAMES, _evaluator, host_collect, same
 from tests.test_playout_policy import WIN_SEQ, UNCOVER_SEQ, play, random_midgames, sample_stream
-from tests.test_selfplay_search import STREAM_VISIT, cells, strides, targets_numpy, visits_draw, word
+from tests.test_selfplay_search import STREAM_VISIT, targets_numpy, visits_draw, word
 
-NAMES = (("actions", np.int32, ()), ("winner", np.int8, ()), ("rewards", np.int8, (2,)), ("done", np.int8, ()), ("to_move", np.int8, ()),
-         ("action_mask", np.int8, (54,)), ("observation", np.int8, (117,)), ("visits", np.int16, (54,)), ("value", np.int32, ()),
-         ("nodes", np.int32, ()), ("how", np.int8, ()), ("mover", np.int8, ()), ("root_value", np.int32, ()), ("priors", np.uint8, (54,)))
-CODES = {"random": nat.POLICY_RANDOM, "eval": nat.POLICY_EVAL_TREE}
 SEARCH_ONLY = ("visits", "value", "nodes", "root_value", "priors")
 
 
@@ -39,25 +36,8 @@ def collect_eval(f, err, st, tm, turn, T, pols, nets, its, X, sample_plies, ille
                  keep=None, counters=None):
     """gbl(_cpu)_collect_search_eval on host arrays; only the outputs named in `keep` are given (None: all).  Returns
     ({name: (T, n, ...)}, state, to_move, done, turn)."""
-    n = len(st)
-    ps, ts, total = strides(n, T, layout)
-    keep = [k for k, _, _ in NAMES] if keep is None else keep
-    traj = {k: np.full((total,) + tail, 99 if dt == np.uint8 else -7, dt) for k, dt, tail in NAMES if k in keep}
-    st, tm, dn = np.ascontiguousarray(st, np.int8).copy(), np.ascontiguousarray(tm, np.int8).copy(), np.full(n, 5, np.int8)
-    tn = None if turn is None else np.ascontiguousarray(turn, np.int32).copy()
-    pd = None if ply_dev is None else np.array([ply_dev], np.uint32)
-    evs = [None if net is None else net.struct() for net in nets]
-    rc = f(st.ctypes.data, tm.ctypes.data, dn.ctypes.data, *[traj[k].ctypes.data if k in traj else None for k, _, _ in NAMES], n, ps, ts,
-           seed, env_base, ply0, None if pd is None else pd.ctypes.data, T, CODES[pols[0]], CODES[pols[1]],
-           *[None if e is None else C.addressof(e) for e in evs], its[0], its[1], X, sample_plies, illegal_mode,
-           None if counters is None else counters.ctypes.data, None if tn is None else tn.ctypes.data, None)
-    assert rc == 0, err()
-    at = cells(n, T, layout)
-    untouched = np.ones(total, bool)
-    untouched[at] = False
-    for k, v in traj.items():  # (nothing outside the cells is written)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), k
-    return {k: v[at] for k, v in traj.items()}, st, tm, dn, tn
+    return host_collect("eval", f, err, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep,
+                        counters, nets=nets, its=its)
 
 
 def restate_collect(st, tm, turn, T, pols, nets, its, X, sample_plies, illegal_mode, seed, env_base, ply0):
@@ -89,14 +69,6 @@ def restate_collect(st, tm, turn, T, pols, nets, its, X, sample_plies, illegal_m
                      ("nodes", nodes), ("how", how), ("mover", mover), ("root_value", rootv), ("priors", pri)):
             out[k].append(v)
     return {k: np.stack(v) for k, v in out.items()}, st, tm, dn, turn
-
-
-def same(got, exp):
-    for k in got[0]:
-        assert got[0][k].dtype == exp[0][k].dtype and np.array_equal(got[0][k], exp[0][k]), (k, np.argwhere(got[0][k] != exp[0][k])[:5])
-    for name, g, e in zip(("state", "to_move", "done", "turn"), got[1:], exp[1:]):
-        if g is not None:
-            assert np.array_equal(g, e), name
 
 
 @pytest.fixture(scope="module")
@@ -343,10 +315,6 @@ def test_argument_limits():
 
 
 # ---- the Python surface on device="cpu" -------------------------------------------------------------------------------------------
-def _evaluator(net, device="cpu"):
-    return G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, net.shift1, net.shift_p, net.shift_v, device=device)
-
-
 def test_python_surface_on_cpu(cpu, nets):
     ev0, ev1 = _evaluator(nets[0]), _evaluator(nets[1])
     env = G.BatchedGobblet(70, "cpu", auto_reset=True, seed=4, env_base=3, track_turn=True)

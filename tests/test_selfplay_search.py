@@ -10,15 +10,12 @@ import oracle
 
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
+from tests.selfplay_harness import CODES, SCALARS, cells, host_collect, replay_arg_errors, same, strides  # noqa: F401  (re-exported)
 from tests.test_playout_policy import random_midgames, sample_stream
 from tests.test_tree_policy import restate
 
 STREAM_VISIT = 4
 M32 = 0xFFFFFFFF
-SCALARS = (("actions", np.int32, ()), ("winner", np.int8, ()), ("rewards", np.int8, (2,)), ("done", np.int8, ()),
-           ("to_move", np.int8, ()), ("action_mask", np.int8, (54,)), ("observation", np.int8, (117,)), ("visits", np.int16, (54,)),
-           ("value", np.int32, ()), ("nodes", np.int32, ()), ("how", np.int8, ()), ("mover", np.int8, ()))
-CODES = {"random": nat.POLICY_RANDOM, "tree": nat.POLICY_TREE}
 
 
 def word(seed, env_id, ply, stream):
@@ -34,36 +31,10 @@ def visits_draw(visits, r):
     return int(over[0]) if len(over) else -1
 
 
-def strides(n, T, layout):
-    tiles = -(-n // 64)
-    if layout == "time":
-        slot = tiles * 64 + 64  # (a padded slot: the stride is not the board count)
-        return slot, 64, T * slot
-    return 64, 64 * T, tiles * T * 64
-
-
-def cells(n, T, layout):
-    ps, ts, _ = strides(n, T, layout)
-    b = np.arange(n)
-    return np.arange(T)[:, None] * ps + (b // 64) * ts + b % 64  # (T, n)
-
-
-def collect(lib, st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None,
-            device=False, count=False):
-    """gbl(_cpu)_collect_search on host arrays through `lib`; returns ({name: (T, n, ...)}, state, to_move, done, turn[, tallies])."""
-    n = len(st)
-    ps, ts, total = strides(n, T, layout)
-    traj = {k: np.full((total,) + tail, -7, dt) for k, dt, tail in SCALARS}
-    st, tm, dn = np.ascontiguousarray(st, np.int8).copy(), np.ascontiguousarray(tm, np.int8).copy(), np.full(n, 5, np.int8)
-    tn = None if turn is None else np.ascontiguousarray(turn, np.int32).copy()
-    pd = None if ply_dev is None else np.array([ply_dev], np.uint32)
-    f = lib.gbl_cpu_collect_search
-    rc = f(st.ctypes.data, tm.ctypes.data, dn.ctypes.data, *[traj[k].ctypes.data for k, _, _ in SCALARS], n, ps, ts, seed, env_base, ply0,
-           None if pd is None else pd.ctypes.data, T, CODES[pols[0]], CODES[pols[1]], its[0], its[1], pls[0], pls[1], M, X, sample_plies,
-           illegal_mode, None, None if tn is None else tn.ctypes.data, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    at = cells(n, T, layout)
-    return {k: v[at] for k, v in traj.items()}, st, tm, dn, tn
+def collect(lib, st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None):
+    """gbl_cpu_collect_search on host arrays through `lib`; returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
+    return host_collect("search", lib.gbl_cpu_collect_search, lib.gbl_cpu_last_error, st, tm, turn, T, pols, X, sample_plies, illegal_mode,
+                        layout, seed, env_base, ply0, ply_dev, its=its, pls=pls, M=M)
 
 
 def restate_collect(st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, seed, env_base, ply0):
@@ -94,14 +65,6 @@ def restate_collect(st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal
                      ("nodes", nodes), ("how", how), ("mover", mover)):
             out[k].append(v)
     return {k: np.stack(v) for k, v in out.items()}, st, tm, dn, turn
-
-
-def same(got, exp):
-    for k in exp[0]:
-        assert np.array_equal(got[0][k], exp[0][k]), (k, np.argwhere(got[0][k] != exp[0][k])[:5])
-    for name, g, e in zip(("state", "to_move", "done", "turn"), got[1:], exp[1:]):
-        if g is not None:
-            assert np.array_equal(g, e), name
 
 
 @pytest.fixture(scope="module")
@@ -207,18 +170,12 @@ def test_sharding(cpu, many):
 def test_tallies_and_null_outputs(cpu, many):
     st, tm, turn = many
     n, T_ = len(st), 6
-    ps, ts, total = strides(n, T_, "time")
-    s, m, d = st.copy(), tm.copy(), np.zeros(n, np.int8)
     counters = np.zeros((nat.COUNTER_STRIPES, nat.COUNTER_STRIDE), np.int64)
-    done = np.zeros(total, np.int8)
-    winner = np.zeros(total, np.int8)
-    rc = cpu.gbl_cpu_collect_search(s.ctypes.data, m.ctypes.data, d.ctypes.data, None, winner.ctypes.data, None, done.ctypes.data,
-                                    *[None] * 8, n, ps, ts, 1, 0, 0, None, T_, nat.POLICY_TREE, nat.POLICY_RANDOM, 16, 0, 4, 0, 30, 64, 0,
-                                    nat.ILLEGAL_NOOP, counters.ctypes.data, None, None)
-    assert rc == 0, cpu.gbl_cpu_last_error()
-    at = cells(n, T_, "time")
+    tr, *_ = host_collect("search", cpu.gbl_cpu_collect_search, cpu.gbl_cpu_last_error, st, tm, None, T_, ("tree", "random"), 64, 0,
+                          nat.ILLEGAL_NOOP, "time", 1, 0, 0, keep=("winner", "done"), counters=counters, its=(16, 0), pls=(4, 0), M=30)
     tot = counters.sum(0)
-    assert tot[0] == n * T_ and tot[1] == done[at].sum() and tot[2] == (winner[at] == 1).sum() and tot[3] == (winner[at] == -1).sum()
+    assert set(tr) == {"winner", "done"}
+    assert tot[0] == n * T_ and tot[1] == tr["done"].sum() and tot[2] == (tr["winner"] == 1).sum() and tot[3] == (tr["winner"] == -1).sum()
 
 
 # ---- gbl_outcome_targets ----------------------------------------------------------------------------------------------------
@@ -280,6 +237,19 @@ def test_outcome_targets(cpu, many, layout):
 
 
 # ---- argument limits ----------------------------------------------------------------------------------------------------------
+def test_argument_precedence_replays_the_recorded_table(golden_dir):
+    """tests/golden/selfplay_arg_errors.json (scripts/record_selfplay_arg_errors.py): for each of the four self-play entry points
+    and both flavours every check alone, every adjacent pair of checks broken together (the earlier one answers), a clean call and
+    the n == 0 / plies == 0 returns in front of arguments a later check refuses -- code and message as recorded."""
+    import json
+    import os
+    table = json.load(open(os.path.join(golden_dir, "selfplay_arg_errors.json")))
+    per_fn = {fn: sum(c["fn"] == fn for c in table) for fn in ("collect_search", "collect_search_eval", "collect_search_solve", "collect_search_noise")}
+    assert sum(per_fn.values()) == len(table) and min(per_fn.values()) >= 50, per_fn
+    assert sum(c["host"] is None for c in table) >= 40 and sum(c["device"][0] == 0 for c in table) >= 12
+    replay_arg_errors(table)
+
+
 @pytest.mark.parametrize("flavour", ["cpu", "hip"])
 def test_argument_limits(flavour):
     if flavour == "cpu":

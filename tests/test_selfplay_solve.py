@@ -20,11 +20,11 @@ import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import solver_restatement as SR
+from tests.selfplay_harness import SOLVE_NAMES as NAMES, host_collect, same
 from tests.test_playout_policy import sample_stream
-from tests.test_selfplay_eval import CODES, NAMES as EVAL_NAMES, collect_eval, same
-from tests.test_selfplay_search import STREAM_VISIT, cells, strides, visits_draw, word
+from tests.test_selfplay_eval import collect_eval
+from tests.test_selfplay_search import STREAM_VISIT, visits_draw, word
 
-NAMES = EVAL_NAMES + (("outcomes", np.int8, (54,)), ("proven", np.int8, ()))
 EXPLORE = 48
 
 
@@ -51,35 +51,12 @@ def six_boards(c5):
     return st, tm, turn
 
 
-def solve_call(f, traj, st, tm, dn, tn, pd, n, ps, ts, seed, env_base, ply0, T, pols, evs, its, deps, X, sample_plies, illegal_mode, counters,
-               stream, ptr):
-    """The argument list of gbl(_cpu)_collect_search_solve; ptr(x) turns an array (or None) into a pointer."""
-    return f(ptr(st), ptr(tm), ptr(dn), *[ptr(traj.get(k)) for k, _, _ in NAMES], n, ps, ts, seed, env_base, ply0, ptr(pd), T, CODES[pols[0]],
-             CODES[pols[1]], *[None if e is None else C.addressof(e) for e in evs], its[0], its[1], deps[0], deps[1], X, sample_plies,
-             illegal_mode, ptr(counters), ptr(tn), stream)
-
-
 def collect_solve(f, err, st, tm, turn, T, pols, nets, its, deps, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None,
-                  keep=None):
-    """gbl_cpu_collect_search_solve on host arrays, as tests/test_selfplay_eval.py's collect_eval: ({name: (T, n, ...)}, state, to_move,
-    done, turn); nothing outside the cells may be written."""
-    n = len(st)
-    ps, ts, total = strides(n, T, layout)
-    keep = [k for k, _, _ in NAMES] if keep is None else keep
-    traj = {k: np.full((total,) + tail, 99 if dt == np.uint8 else -7, dt) for k, dt, tail in NAMES if k in keep}
-    st, tm, dn = np.ascontiguousarray(st, np.int8).copy(), np.ascontiguousarray(tm, np.int8).copy(), np.full(n, 5, np.int8)
-    tn = None if turn is None else np.ascontiguousarray(turn, np.int32).copy()
-    pd = None if ply_dev is None else np.array([ply_dev], np.uint32)
-    evs = [None if net is None else net.struct() for net in nets]
-    rc = solve_call(f, traj, st, tm, dn, tn, pd, n, ps, ts, seed, env_base, ply0, T, pols, evs, its, deps, X, sample_plies, illegal_mode, None,
-                    None, lambda a: None if a is None else a.ctypes.data)
-    assert rc == 0, err()
-    at = cells(n, T, layout)
-    untouched = np.ones(total, bool)
-    untouched[at] = False
-    for k, v in traj.items():
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), k
-    return {k: v[at] for k, v in traj.items()}, st, tm, dn, tn
+                  keep=None, noise=None):
+    """gbl_cpu_collect_search_solve (with `noise`, a pair of weights: gbl_cpu_collect_search_noise) on host arrays, as
+    tests/test_selfplay_eval.py's collect_eval: ({name: (T, n, ...)}, state, to_move, done, turn)."""
+    return host_collect("solve" if noise is None else "noise", f, err, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed,
+                        env_base, ply0, ply_dev, keep, nets=nets, its=its, deps=deps, noise=noise or (0, 0))
 
 
 @functools.lru_cache(maxsize=None)
