@@ -648,13 +648,8 @@ int gbl_cpu_playout_values(const int8_t *state, const int8_t *to_move, const int
                            uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
                            int32_t *action_out, int32_t *plies_out, int64_t n, void *)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (playouts < 1 || playouts > 4096) return fail(GBL_ERR_ARG, "playouts must be in [1, 4096]");
-    if (const char *why = playout_limits_error(max_plies)) return fail(GBL_ERR_ARG, why);
-    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = playout_values_error(playouts, max_plies, call, env_base, n, state, to_move)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is playouts x ~30 whole games: every board is worth a thread)
         for (int64_t b = b0; b < b1; ++b) {
             const HostRoot R = host_root(state, to_move, mask, b);
@@ -739,6 +734,17 @@ static void host_root_out(const std::vector<TreeNode> &nodes, uint32_t count, Ho
     out.count = count;
 }
 
+// ... and its write-out into board b's rows of an entry point's outputs, each only if its pointer is given
+static void host_search_out(const HostSearch &h, int64_t b, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                            int32_t *nodes_out)
+{
+    if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
+    if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
+    if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
+    if (action_out) action_out[b] = tree_action_of(h.best);
+    if (nodes_out) nodes_out[b] = (int32_t)h.count;
+}
+
 static void host_tree_search(std::vector<TreeNode> &nodes, const Planes &root, int mover, uint64_t cand, uint64_t g, uint32_t iterations,
                              uint32_t P, uint32_t max_plies, uint32_t explore, uint64_t seed, uint32_t call, HostSearch &out)
 {
@@ -767,13 +773,9 @@ int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t
                         int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
                         int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = tree_budget_error(iterations, playouts)) return fail(GBL_ERR_ARG, why);
-    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
-    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_search_error(iterations, playouts, max_plies, explore, call, env_base, n, state, to_move))
+        return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)iterations + 1);
         HostSearch h;
@@ -781,11 +783,7 @@ int gbl_cpu_tree_search(const int8_t *state, const int8_t *to_move, const int8_t
             const HostRoot R = host_root(state, to_move, mask, b);
             host_tree_search(nodes, R.p, R.mover, R.cand, env_base + (uint64_t)b, (uint32_t)iterations, (uint32_t)playouts, (uint32_t)max_plies,
                              (uint32_t)explore, seed, call, h);
-            if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
-            if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
-            if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
-            if (action_out) action_out[b] = tree_action_of(h.best);
-            if (nodes_out) nodes_out[b] = (int32_t)h.count;
+            host_search_out(h, b, visits_out, wins_out, losses_out, action_out, nodes_out);
             if (plies_out) plies_out[b] = (int32_t)h.plies;
         }
     }, 1);
@@ -814,11 +812,8 @@ static int32_t host_evaluate(const EvalNet &net, const Planes &p, int side, uint
 int gbl_cpu_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, uint8_t *priors_out,
                      int32_t *value_out, int32_t *logits_out, int64_t n, void *)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = evaluate_error(ev, n, state, to_move, priors_out, value_out)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(priors_out, "priors_out"); GBL_NEED(value_out, "value_out");
-    if (const char *why = evaluator_pointers_error(ev)) return fail(GBL_ERR_ARG, why);
     const EvalNet net = eval_net(ev);
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) {
@@ -873,12 +868,8 @@ static int host_tree_search_eval_run(const int8_t *state, const int8_t *to_move,
                                      int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
                                      int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
-    if (const char *why = tree_eval_budget_error(iterations, explore)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_search_eval_error(ev, iterations, explore, n, state, to_move)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
-    if (const char *why = evaluator_pointers_error(ev)) return fail(GBL_ERR_ARG, why);
     const EvalNet net = eval_net(ev);
     parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)iterations + 1);
@@ -889,11 +880,7 @@ static int host_tree_search_eval_run(const int8_t *state, const int8_t *to_move,
             const int32_t q = host_tree_search_eval(nodes, pri, net, R.p, R.mover, R.cand, (uint32_t)iterations, (uint32_t)explore, h,
                                                     HostNoise{(uint32_t)noise, seed, env_base + (uint64_t)b, call,
                                                               root_priors_out ? root_priors_out + b * kActions : nullptr});
-            if (visits_out) memcpy(visits_out + b * kActions, h.visits, sizeof h.visits);
-            if (wins_out) memcpy(wins_out + b * kActions, h.wins, sizeof h.wins);
-            if (losses_out) memcpy(losses_out + b * kActions, h.losses, sizeof h.losses);
-            if (action_out) action_out[b] = tree_action_of(h.best);
-            if (nodes_out) nodes_out[b] = (int32_t)h.count;
+            host_search_out(h, b, visits_out, wins_out, losses_out, action_out, nodes_out);
             if (root_value_out) root_value_out[b] = q;
             if (root_mixed_out) memcpy(root_mixed_out + b * kActions, pri.data(), kActions);
         }
@@ -914,10 +901,7 @@ int gbl_cpu_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, c
                                    int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
                                    int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = noise_error(noise)) return fail(GBL_ERR_ARG, why);
-    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_search_noise_error(noise, call, env_base, n)) return fail(GBL_ERR_ARG, why);
     return host_tree_search_eval_run(state, to_move, mask, ev, iterations, explore, noise, seed, env_base, call, visits_out, wins_out,
                                      losses_out, action_out, nodes_out, root_value_out, root_priors_out, root_mixed_out, n);
 }

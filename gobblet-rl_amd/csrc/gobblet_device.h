@@ -2565,6 +2565,70 @@ inline const char *solve_error(int depth, int64_t n, const void *state, const vo
     return nullptr;
 }
 
+// The other single-decision entry points, likewise: what BOTH flavours look at, in the order they report it (every one a
+// GBL_ERR_ARG; n == 0 passes whatever the pointers are).  The device flavour's alignment rules follow there, after these.
+inline const char *call_env_error(uint32_t call, uint64_t env_base, int64_t n)  // (n >= 0)
+{
+    return call >= (1u << 24) ? "call must be below 2^24" : env_range_error(env_base, n);
+}
+
+inline const char *boards_error(const void *state, const void *to_move)
+{
+    return !state ? "state must not be NULL" : !to_move ? "to_move must not be NULL" : nullptr;
+}
+
+inline const char *playout_values_error(int playouts, int max_plies, uint32_t call, uint64_t env_base, int64_t n, const void *state,
+                                        const void *to_move)
+{
+    if (n < 0) return "n < 0";
+    if (playouts < 1 || playouts > 4096) return "playouts must be in [1, 4096]";
+    if (const char *why = playout_limits_error(max_plies)) return why;
+    if (const char *why = call_env_error(call, env_base, n)) return why;
+    return n == 0 ? nullptr : boards_error(state, to_move);
+}
+
+inline const char *tree_search_error(int iterations, int playouts, int max_plies, int explore, uint32_t call, uint64_t env_base, int64_t n,
+                                     const void *state, const void *to_move)
+{
+    if (n < 0) return "n < 0";
+    if (const char *why = tree_budget_error(iterations, playouts)) return why;
+    if (const char *why = playout_limits_error(max_plies, explore)) return why;
+    if (const char *why = call_env_error(call, env_base, n)) return why;
+    return n == 0 ? nullptr : boards_error(state, to_move);
+}
+
+template <typename Ev>
+inline const char *evaluate_error(const Ev *ev, int64_t n, const void *state, const void *to_move, const void *priors_out,
+                                  const void *value_out)
+{
+    if (n < 0) return "n < 0";
+    if (const char *why = evaluator_error(ev)) return why;
+    if (n == 0) return nullptr;
+    if (const char *why = boards_error(state, to_move)) return why;
+    if (!priors_out) return "priors_out must not be NULL";
+    if (!value_out) return "value_out must not be NULL";
+    return evaluator_pointers_error(ev);
+}
+
+template <typename Ev>
+inline const char *tree_search_eval_error(const Ev *ev, int iterations, int explore, int64_t n, const void *state, const void *to_move)
+{
+    if (n < 0) return "n < 0";
+    if (const char *why = evaluator_error(ev)) return why;
+    if (const char *why = tree_eval_budget_error(iterations, explore)) return why;
+    if (n == 0) return nullptr;
+    if (const char *why = boards_error(state, to_move)) return why;
+    return evaluator_pointers_error(ev);
+}
+
+// gbl_tree_search_eval_noise's own four, in front of tree_search_eval_error
+inline const char *tree_search_noise_error(int noise, uint32_t call, uint64_t env_base, int64_t n)
+{
+    if (n < 0) return "n < 0";
+    if (const char *why = noise_error(noise)) return why;
+    return call_env_error(call, env_base, n);
+}
+
 // ---- board symmetries (include/gobblet_hip.h, "Board symmetries"): gbl_symmetry_apply and gbl_training_batch ------------------------
 // One statement of the rule for the kernels and the host flavour.  Everything is in GATHER form -- "which input element lands in
 // output element k" -- so that a lane that owns a whole row runs it with constant k (the divisions fold away) and a wavefront that

@@ -3668,6 +3668,13 @@ static int check_search_traj(const SearchTraj &T, uintptr_t more_words, const ch
     return GBL_OK;
 }
 
+// the grid of the one-workgroup-a-board kernels: they stride over what is beyond the cap
+static inline dim3 board_grid(int64_t n) { return dim3((uint32_t)std::min<int64_t>(n, 1 << 20)); }
+
+// whether any of the pointers (NULL included) is off a 4-byte boundary
+template <typename... P>
+static inline bool off_dword(const P *...p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 3u) != 0; }
+
 extern "C" {
 
 
@@ -4260,24 +4267,17 @@ int gbl_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8_t *
     GBL_LAUNCHED("gbl_greedy_act");
 }
 
-
 int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t *mask, int playouts, int max_plies,
                        uint64_t seed, uint64_t env_base, uint32_t call, int32_t *wins_out, int32_t *losses_out,
                        int32_t *action_out, int32_t *plies_out, int64_t n, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (playouts < 1 || playouts > 4096) return fail(GBL_ERR_ARG, "playouts must be in [1, 4096]");
-    if (const char *why = playout_limits_error(max_plies)) return fail(GBL_ERR_ARG, why);
-    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = playout_values_error(playouts, max_plies, call, env_base, n, state, to_move)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
-    if ((reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) | reinterpret_cast<uintptr_t>(action_out) |
-         reinterpret_cast<uintptr_t>(plies_out)) & 3u)
+    if (off_dword(wins_out, losses_out, action_out, plies_out))
         return fail(GBL_ERR_ALIGN, "wins_out / losses_out / action_out / plies_out must be 4-byte aligned");
     const uint32_t K = (uint32_t)playouts;
     const uint64_t kinv = ((1ull << 32) + K - 1) / K;
-    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    const dim3 grid = board_grid(n);
     const hipStream_t s = (hipStream_t)stream;
 #define GBL_PLAYOUT(W)                                                                                                          \
     hipLaunchKernelGGL((k_playout<W>), grid, dim3(64 * W), 0, s, state, to_move, mask, wins_out, losses_out, action_out, plies_out, \
@@ -4296,17 +4296,12 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
                     int explore, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out,
                     int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *plies_out, int64_t n, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = tree_budget_error(iterations, playouts)) return fail(GBL_ERR_ARG, why);
-    if (const char *why = playout_limits_error(max_plies, explore)) return fail(GBL_ERR_ARG, why);
-    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_search_error(iterations, playouts, max_plies, explore, call, env_base, n, state, to_move))
+        return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
-    if ((reinterpret_cast<uintptr_t>(visits_out) | reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) |
-         reinterpret_cast<uintptr_t>(action_out) | reinterpret_cast<uintptr_t>(nodes_out) | reinterpret_cast<uintptr_t>(plies_out)) & 3u)
+    if (off_dword(visits_out, wins_out, losses_out, action_out, nodes_out, plies_out))
         return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / plies_out must be 4-byte aligned");
-    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
+    const dim3 grid = board_grid(n);
     const size_t lds = sizeof(TreeNode) * ((size_t)iterations + 1);  // the tree: one node per iteration and the root
     const hipStream_t s = (hipStream_t)stream;
 #define GBL_TREE(W)                                                                                                               \
@@ -4328,8 +4323,7 @@ int gbl_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, in
     int code = 0;
     if (const char *why = solve_error(depth, n, state, to_move, action_out, code)) return fail(code ? GBL_ERR_ALIGN : GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    const dim3 grid((uint32_t)std::min<int64_t>(n, 1 << 20));
-    hipLaunchKernelGGL((k_solve<knob::kSolveDeal>), grid, dim3(64), 0, (hipStream_t)stream, state, to_move, mask, outcome_out, value_out,
+    hipLaunchKernelGGL((k_solve<knob::kSolveDeal>), board_grid(n), dim3(64), 0, (hipStream_t)stream, state, to_move, mask, outcome_out, value_out,
                        action_out, n, depth);
     GBL_LAUNCHED("gbl_solve");
 }
@@ -4347,16 +4341,13 @@ static int eval_net_of(const gbl_evaluator *ev, EvalNet &net)
 int gbl_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, uint8_t *priors_out,
                  int32_t *value_out, int32_t *logits_out, int64_t n, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = evaluate_error(ev, n, state, to_move, priors_out, value_out)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(priors_out, "priors_out"); GBL_NEED(value_out, "value_out");
     EvalNet net;
     if (const int e = eval_net_of(ev, net)) return e;
-    if ((reinterpret_cast<uintptr_t>(value_out) | reinterpret_cast<uintptr_t>(logits_out)) & 3u)
-        return fail(GBL_ERR_ALIGN, "value_out / logits_out must be 4-byte aligned");
-    hipLaunchKernelGGL(k_evaluate, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), 0, (hipStream_t)stream, state, to_move, mask, net,
-                       priors_out, value_out, logits_out, n);
+    if (off_dword(value_out, logits_out)) return fail(GBL_ERR_ALIGN, "value_out / logits_out must be 4-byte aligned");
+    hipLaunchKernelGGL(k_evaluate, board_grid(n), dim3(64), 0, (hipStream_t)stream, state, to_move, mask, net, priors_out, value_out,
+                       logits_out, n);
     GBL_LAUNCHED("gbl_evaluate");
 }
 
@@ -4366,23 +4357,19 @@ static int tree_search_eval_launch(const char *name, const int8_t *state, const 
                                    int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
                                    int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = evaluator_error(ev)) return fail(GBL_ERR_ARG, why);
-    if (const char *why = tree_eval_budget_error(iterations, explore)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_search_eval_error(ev, iterations, explore, n, state, to_move)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
     EvalNet net;
     if (const int e = eval_net_of(ev, net)) return e;
-    if ((reinterpret_cast<uintptr_t>(visits_out) | reinterpret_cast<uintptr_t>(wins_out) | reinterpret_cast<uintptr_t>(losses_out) |
-         reinterpret_cast<uintptr_t>(action_out) | reinterpret_cast<uintptr_t>(nodes_out) | reinterpret_cast<uintptr_t>(root_value_out)) & 3u)
+    if (off_dword(visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out))
         return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / root_value_out must be 4-byte aligned");
     // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations: below the 64 KB a kernel gets unasked)
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);
     // (k_tree_eval<false> is the kernel without the noise's code; a caller who asks for root_mixed_out at weight 0 gets the <true> one)
 #define GBL_TE(NOISE)                                                                                                                   \
-    hipLaunchKernelGGL(k_tree_eval<NOISE>, dim3((uint32_t)std::min<int64_t>(n, 1 << 20)), dim3(64), lds, (hipStream_t)stream, state, to_move, \
-                       mask, net, visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n,              \
-                       (uint32_t)iterations, (uint32_t)explore, root_mixed_out, (uint32_t)noise, seed, env_base, call)
+    hipLaunchKernelGGL(k_tree_eval<NOISE>, board_grid(n), dim3(64), lds, (hipStream_t)stream, state, to_move, mask, net, visits_out,    \
+                       wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n, (uint32_t)iterations,           \
+                       (uint32_t)explore, root_mixed_out, (uint32_t)noise, seed, env_base, call)
     if (noise || root_mixed_out)
         GBL_TE(true);
     else
@@ -4404,10 +4391,7 @@ int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const
                                int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *root_value_out,
                                uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream)
 {
-    if (n < 0) return fail(GBL_ERR_ARG, "n < 0");
-    if (const char *why = noise_error(noise)) return fail(GBL_ERR_ARG, why);
-    if (call >= (1u << 24)) return fail(GBL_ERR_ARG, "call must be below 2^24");
-    if (const char *why = env_range_error(env_base, n)) return fail(GBL_ERR_ARG, why);
+    if (const char *why = tree_search_noise_error(noise, call, env_base, n)) return fail(GBL_ERR_ARG, why);
     return tree_search_eval_launch("gbl_tree_search_eval_noise", state, to_move, mask, ev, iterations, explore, noise, seed, env_base, call,
                                    visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, root_mixed_out,
                                    n, stream);

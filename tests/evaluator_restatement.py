@@ -1,7 +1,6 @@
 """A Python restatement of the gbl_evaluator / gbl_evaluate / gbl_tree_search_eval text of include/gobblet_hip.h on the oracle's
-board functions (test infrastructure; written from the header, not from the device code), the seeded weight sets the evaluator
-tests share, and the ctypes plumbing to run either flavour on host arrays."""
-import ctypes as C
+board functions (test infrastructure; written from the header, not from the device code) and the seeded weight sets the evaluator
+tests share."""
 import math
 
 import numpy as np
@@ -12,8 +11,6 @@ from gobblet_rl_amd import _native as nat
 
 P = 128
 T = [int(math.floor(65536 * 2.0 ** (-k / 16) + 0.5)) for k in range(16)]
-EVAL_NAMES = ("priors", "value", "logits")
-SEARCH_NAMES = ("visits", "wins", "losses", "action", "nodes", "root_value", "root_priors")
 
 
 class Net:
@@ -183,43 +180,6 @@ def restate_search(net, state, to_move, mask, iterations, explore):
             visits[b, a], wins[b, a], losses[b, a] = c.n, c.W, c.L
         action[b] = max(sorted(root.children), key=lambda a: (root.children[a].n, root.children[a].W - root.children[a].L, -a))
     return visits, wins, losses, action, nodes, rootv, rootp
-
-
-# ---- either flavour on host arrays ---------------------------------------------------------------------------------------------------
-def _in(state, to_move, mask):
-    st, tm = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(to_move, np.int8)
-    mk = None if mask is None else np.ascontiguousarray(mask, np.int8)
-    return st, tm, mk
-
-
-def run_evaluate(lib, net, state, to_move, mask=None, logits=True):
-    """gbl_cpu_evaluate through the host flavour's raw handle: (priors, value, logits)."""
-    st, tm, mk = _in(state, to_move, mask)
-    n = len(st)
-    pri, val = np.full((n, 54), 99, np.uint8), np.full(n, -7, np.int32)
-    log = np.full((n, 56), -7, np.int32) if logits else None
-    ev = net.struct()
-    rc = lib.gbl_cpu_evaluate(st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, C.addressof(ev), pri.ctypes.data,
-                              val.ctypes.data, None if log is None else log.ctypes.data, n, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    return pri, val, log
-
-
-def run_search(lib, net, state, to_move, mask, iterations, explore):
-    """gbl_cpu_tree_search_eval through the host flavour's raw handle: the seven outputs."""
-    st, tm, mk = _in(state, to_move, mask)
-    n = len(st)
-    out = [np.full((n, 54), -7, np.int32) for _ in range(3)] + [np.full(n, -7, np.int32) for _ in range(3)] + [np.full((n, 54), 99, np.uint8)]
-    ev = net.struct()
-    rc = lib.gbl_cpu_tree_search_eval(st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, C.addressof(ev), iterations,
-                                      explore, *[o.ctypes.data for o in out], n, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    return tuple(out)
-
-
-def same(got, exp, names):
-    for name, g, e in zip(names, got, exp):
-        assert g.dtype == e.dtype and np.array_equal(g, e), (name, np.argwhere(g != e)[:5])
 
 
 # ---- dial networks (H = 64): weight sets whose outputs are known in closed form ----------------------------------------------------

@@ -2,7 +2,6 @@
 alone (include/gobblet_hip.h, "Root noise"), for tests/test_root_noise.py and tests/test_gpu_root_noise.py.  The generator is the
 oracle's Philox block, as tests/test_selfplay_search.py::word uses it; the search around the root row is
 tests/evaluator_restatement.py's restate_search, imported and left as it is."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -13,7 +12,6 @@ from tests import evaluator_restatement as R
 M32 = 0xFFFFFFFF
 STREAM_NOISE = 6
 T = (65536, 62757, 60097, 57549, 55109, 52773, 50535, 48393, 46341, 44376, 42495, 40693, 38968, 37316, 35734, 34219)
-NOISE_SEARCH_NAMES = R.SEARCH_NAMES + ("root_mixed",)
 
 
 @functools.lru_cache(maxsize=64)
@@ -85,20 +83,6 @@ def restate_search_noise(net, state, to_move, mask, iterations, explore, w, seed
         pi = R.restate_evaluate(net, state[b:b + 1], to_move[b:b + 1], None if mask is None else mask[b:b + 1])[0]
         outs.append(got[:6] + (pi, mixed))
     return tuple(np.concatenate([o[k] for o in outs]) for k in range(8))
-
-
-def run_search_noise(lib, net, state, to_move, mask, iterations, explore, w, seed, env_base, call, prefix="gbl_cpu_", mixed=True):
-    """gbl_cpu_tree_search_eval_noise through the host flavour's raw handle: the eight outputs (root_mixed None if not asked for)."""
-    st, tm, mk = R._in(state, to_move, mask)
-    n = len(st)
-    out = [np.full((n, 54), -7, np.int32) for _ in range(3)] + [np.full(n, -7, np.int32) for _ in range(3)] + \
-        [np.full((n, 54), 99, np.uint8), np.full((n, 54), 99, np.uint8) if mixed else None]
-    ev = net.struct()
-    rc = getattr(lib, prefix + "tree_search_eval_noise")(
-        st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, C.addressof(ev), iterations, explore, w, seed, env_base, call,
-        *[None if o is None else o.ctypes.data for o in out], n, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    return tuple(out)
 
 
 def restate_collect_noise(st, tm, turn, T, pols, nets, its, deps, noise, X, sample_plies, illegal_mode, seed, env_base, ply0):

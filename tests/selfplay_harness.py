@@ -7,9 +7,9 @@ import numpy as np
 
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
+from tests.search_harness import DEV, PAD
+from tests.search_harness import same as same_arrays
 
-DEV = "cuda:0"
-PAD = 16     # elements of -7 / 99 kept before and after every output on the device (16: the rows keep their 16-byte alignment)
 SCALARS = (("actions", np.int32, ()), ("winner", np.int8, ()), ("rewards", np.int8, (2,)), ("done", np.int8, ()),
            ("to_move", np.int8, ()), ("action_mask", np.int8, (54,)), ("observation", np.int8, (117,)), ("visits", np.int16, (54,)),
            ("value", np.int32, ()), ("nodes", np.int32, ()), ("how", np.int8, ()), ("mover", np.int8, ()))
@@ -82,9 +82,9 @@ def host_collect(entry, f, err, st, tm, turn, T, pols, X, sample_plies, illegal_
 
 
 def device_collect(entry, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None,
-                   nets=(None, None), **sides):
-    """gbl_collect_search* of `entry` on the device, every output between canaries; nets: DeviceNets; the same return value as
-    host_collect."""
+                   counters=None, nets=(None, None), **sides):
+    """gbl_collect_search* of `entry` on the device, every output between canaries; nets: DeviceNets; counters: a device tensor; the
+    same return value as host_collect."""
     import torch
     name = "gbl_collect_search" + ("" if entry == "search" else "_" + entry)
 
@@ -92,13 +92,12 @@ def device_collect(entry, st, tm, turn, T, pols, X, sample_plies, illegal_mode, 
         torch.cuda.synchronize()
         return t.cpu().numpy()
     return _run(entry, getattr(nat.lib(), name), lambda rc: nat.check(rc, name), lambda a: torch.from_numpy(a).to(DEV), get, nat.ptr, PAD,
-                nat.current_stream(DEV), st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, None,
+                nat.current_stream(DEV), st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters,
                 nets, **sides)
 
 
 def same(got, exp):
-    for k in got[0]:
-        assert got[0][k].dtype == exp[0][k].dtype and np.array_equal(got[0][k], exp[0][k]), (k, np.argwhere(got[0][k] != exp[0][k])[:5])
+    same_arrays(got[0], exp[0])
     for name, g, e in zip(("state", "to_move", "done", "turn"), got[1:], exp[1:]):
         if g is not None:
             assert np.array_equal(g, e), name
@@ -119,30 +118,3 @@ class DeviceNet:
 
 def _evaluator(net, device="cpu"):
     return G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, net.shift1, net.shift_p, net.shift_v, device=device)
-
-
-def recorded_call(lib, prefix, case):
-    """One case of a tests/golden/*_arg_errors.json table whose argument lists hold evaluators: every "ev" is the next evaluator of
-    case["evs"], given as its eight fields (or null); every pointer is a number that is never read (all calls return before any
-    work).  Returns the return code."""
-    evs = [None if e is None else nat.Evaluator(*e) for e in case["evs"]]
-    it = iter(evs)
-    args = []
-    for x in case["args"]:
-        if x == "ev":
-            e = next(it)
-            x = None if e is None else C.addressof(e)
-        args.append(x)
-    return getattr(lib, prefix + case["fn"])(*args)
-
-
-def replay_arg_errors(table):
-    """Every case of such a table on both flavours: the recorded return code and, for an error, the recorded message."""
-    for c in table:
-        for flavour, lib, prefix in (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_")):
-            if c[flavour] is None:  # (an alignment rule: only the device flavour has it)
-                continue
-            rc, msg = c[flavour]
-            assert recorded_call(lib, prefix, c) == rc, (flavour, c["fn"], c["case"])
-            if rc:
-                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])

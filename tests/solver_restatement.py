@@ -1,6 +1,6 @@
 """The contract of gbl_solve (include/gobblet_hip.h) restated as a plain full-width recursion over the oracle's play_turn,
 check_for_winner and legal_mask: no pruning, no code shared with the library (test infrastructure; slow on purpose).  Also the
-position sets the CPU and the GPU tests of the solver share, and the call through a library handle."""
+position sets the CPU and the GPU tests of the solver share."""
 import functools
 
 import numpy as np
@@ -8,7 +8,6 @@ import numpy as np
 import oracle
 
 NONE, MAX_DEPTH = -128, 6
-NAMES = ("outcome", "value", "action")
 
 
 def rank(c):
@@ -59,23 +58,6 @@ def solve(state, to_move, mask, depth):
                 best, act[b] = c, a
         val[b] = 0 if best is None else best
     return outcome, val, act
-
-
-def run(lib, state, to_move, mask, depth, prefix="gbl_cpu_"):
-    """gbl_solve on host arrays through the host flavour's raw handle: (outcome, value, action), pre-filled with junk."""
-    st, tm = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(to_move, np.int8)
-    mk = None if mask is None else np.ascontiguousarray(mask, np.int8)
-    n = len(st)
-    out = np.full((n, 54), 77, np.int8), np.full(n, 77, np.int8), np.full(n, -7, np.int32)
-    rc = getattr(lib, prefix + "solve")(st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, depth,
-                                        *[o.ctypes.data for o in out], n, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    return out
-
-
-def same(got, exp):
-    for name, g, e in zip(NAMES, got, exp):
-        assert g.dtype == e.dtype and np.array_equal(g, e), (name, np.argwhere(g != e)[:5])
 
 
 def play(seq, first=0):

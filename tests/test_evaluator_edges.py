@@ -23,6 +23,7 @@ import oracle
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
+from tests.search_harness import run, same
 from tests.test_playout_policy import random_midgames
 
 TOPS = (0, 26, 53)  # the largest logit on the first, a middle and the last lane of the wavefront butterfly
@@ -60,7 +61,7 @@ def open_positions():
 def three_flavours(cpu, net, st, tm, mask):
     """(priors, value, logits) of the restatement, after asserting that the host flavour gives the same."""
     exp = R.restate_evaluate(net, st, tm, mask)
-    R.same(R.run_evaluate(cpu, net, st, tm, mask), exp, R.EVAL_NAMES)
+    same(run("evaluate", "cpu", st, tm, mask, (), net), exp)
     return exp
 
 
@@ -196,9 +197,9 @@ def test_search_on_a_logit_dial_at_the_largest_key(cpu, midgame):
     st, tm, mask = R.dial_boards(midgame, top)
     st, tm, mask = st[[5, 0]], tm[[5, 0]], mask[[5, 0]]  # one candidate; all 54
     net = search_dial(top)
-    got = R.run_search(cpu, net, st, tm, mask, 512, 1024)
-    R.same(got, R.restate_search(net, st, tm, mask, 512, 1024), R.SEARCH_NAMES)
-    v, w, l, a, nd, rv, rp = got
+    got = run("tree_search_eval", "cpu", st, tm, mask, (512, 1024), net)
+    same(got, R.restate_search(net, st, tm, mask, 512, 1024))
+    v, w, l, a, nd, rv, rp = got.values()
     assert rp[0].max() == 255 and (rp[0] > 0).sum() == 1 and v[0, top] == 512 and a[0] == top
     assert (rp[1] > 0).sum() == 54 and rp[1, top] == 254 and v[1].sum() == 512 and (rv == 0).all()
 
@@ -227,7 +228,7 @@ def test_shift_sweep_evaluate_and_search(cpu, open_positions, hidden, shifts):
     else:  # 24: |sum| < 2^21, so every unit reads 0 or -1 before the clamp
         assert (low, high, mid) == (total, 0, 0)
     if hidden == 64:
-        R.same(R.run_search(cpu, net, st[:6], tm[:6], mask[:6], 48, 16), R.restate_search(net, st[:6], tm[:6], mask[:6], 48, 16), R.SEARCH_NAMES)
+        same(run("tree_search_eval", "cpu", st[:6], tm[:6], mask[:6], (48, 16), net), R.restate_search(net, st[:6], tm[:6], mask[:6], 48, 16))
 
 
 # ---- the float64 reference ----------------------------------------------------------------------------------------------------------

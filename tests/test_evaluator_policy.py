@@ -1,7 +1,6 @@
 """gbl_evaluate / gbl_tree_search_eval / GobbletEvaluator / EvaluatorTreeSearchGobbletPolicy on the host flavour (no GPU): against
 the Python restatement of the header text (tests/evaluator_restatement.py), plus properties, tactics with the zero evaluator, the
 recorded argument errors and the quantiser."""
-import ctypes as C
 import json
 import math
 import os
@@ -16,6 +15,7 @@ import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests.positions import terminal_roots
+from tests.search_harness import replay_arg_errors, run, same
 from tests.test_playout_policy import UNCOVER_ACTION, UNCOVER_SEQ, WIN_ACTION, WIN_SEQ, play, random_midgames
 from tests.test_tree_policy import threat_positions, winning_moves
 
@@ -53,11 +53,11 @@ def test_evaluate_equals_restatement(cpu, positions, hidden):
     mask[4] = 0  # a board without a candidate
     for kind, net in nets(hidden).items():
         exp = R.restate_evaluate(net, st, tm)
-        R.same(R.run_evaluate(cpu, net, st, tm), exp, R.EVAL_NAMES)
-        got = R.run_evaluate(cpu, net, st, tm, mask)
-        R.same(got, R.restate_evaluate(net, st, tm, mask), R.EVAL_NAMES)
-        assert not got[0][4].any() and got[1][4] == exp[1][4]  # no candidate: zero priors, the value all the same
-        assert np.array_equal(R.run_evaluate(cpu, net, st, tm, logits=False)[0], exp[0]), kind
+        same(run("evaluate", "cpu", st, tm, None, (), net), exp)
+        got = run("evaluate", "cpu", st, tm, mask, (), net)
+        same(got, R.restate_evaluate(net, st, tm, mask))
+        assert not got["priors"][4].any() and got["value"][4] == exp[1][4]  # no candidate: zero priors, the value all the same
+        assert np.array_equal(run("evaluate", "cpu", st, tm, None, (), net, keep=("priors", "value"))["priors"], exp[0]), kind
         legal = oracle.batch_legal_mask(st, tm) != 0
         assert ((exp[0] > 0) == legal).all()
         if kind == "zero":  # uniform priors, value 0
@@ -95,7 +95,7 @@ def test_search_equals_restatement(cpu, positions, iterations, explore):
         if iterations == 512 and hidden != 64:
             continue
         net = nets(hidden)[kind]
-        R.same(R.run_search(cpu, net, st, tm, None, iterations, explore), R.restate_search(net, st, tm, None, iterations, explore), R.SEARCH_NAMES)
+        same(run("tree_search_eval", "cpu", st, tm, None, (iterations, explore), net), R.restate_search(net, st, tm, None, iterations, explore))
 
 
 def test_search_equals_restatement_with_masked_roots(cpu, positions):
@@ -108,9 +108,9 @@ def test_search_equals_restatement_with_masked_roots(cpu, positions):
     mask[8] = 0
     mask[8, WIN_ACTION] = 1
     net = R.random_net(192, 2)
-    got = R.run_search(cpu, net, st, tm, mask, 48, DEFAULT_EXPLORE)
-    R.same(got, R.restate_search(net, st, tm, mask, 48, DEFAULT_EXPLORE), R.SEARCH_NAMES)
-    v, w, l, a, nd, rv, rp = got
+    got = run("tree_search_eval", "cpu", st, tm, mask, (48, DEFAULT_EXPLORE), net)
+    same(got, R.restate_search(net, st, tm, mask, 48, DEFAULT_EXPLORE))
+    v, w, l, a, nd, rv, rp = got.values()
     assert a[0] == -1 and nd[0] == 1 and not v[0].any() and not w[0].any() and not l[0].any() and not rp[0].any()
     assert rv[0] == R.restate_evaluate(net, st[:1], tm[:1])[1][0]  # the root's value is written all the same
     assert v[1].sum() == 48 and (v[1] > 0).sum() == 1 and rp[1].max() == 255
@@ -133,7 +133,8 @@ def test_properties(cpu, many):
     legal = oracle.batch_legal_mask(st, tm) != 0
     mask = (np.random.default_rng(8).random((n, 54)) < 0.5).astype(np.int8)
     mask[5] = 0
-    v, w, l, a, nd, rv, rp = got = R.run_search(cpu, net, st, tm, mask, I, DEFAULT_EXPLORE)
+    got = run("tree_search_eval", "cpu", st, tm, mask, (I, DEFAULT_EXPLORE), net)
+    v, w, l, a, nd, rv, rp = got.values()
     cand = legal & (mask != 0)
     has = cand.any(1)
     assert has.sum() > n - 5 and not has[5]
@@ -142,9 +143,10 @@ def test_properties(cpu, many):
     assert (w >= 0).all() and (l >= 0).all() and ((w + l) <= v * 128).all()
     assert (nd <= I + 1).all() and (nd[has] >= 2).all() and (nd[~has] == 1).all() and (a[~has] == -1).all()
     assert (np.abs(rv) <= 128).all()
-    R.same(R.run_search(cpu, net, st, tm, mask, I, DEFAULT_EXPLORE), got, R.SEARCH_NAMES)  # two calls, one result
+    same(run("tree_search_eval", "cpu", st, tm, mask, (I, DEFAULT_EXPLORE), net), got)  # two calls, one result
     for b in (0, 5, 17, n - 1):  # a board alone is the board in the batch
-        R.same(R.run_search(cpu, net, st[b:b + 1], tm[b:b + 1], mask[b:b + 1], I, DEFAULT_EXPLORE), [x[b:b + 1] for x in got], R.SEARCH_NAMES)
+        alone = run("tree_search_eval", "cpu", st[b:b + 1], tm[b:b + 1], mask[b:b + 1], (I, DEFAULT_EXPLORE), net)
+        same(alone, {k: x[b:b + 1] for k, x in got.items()})
 
 
 def test_zero_evaluator_plays_the_immediate_win(cpu):
@@ -166,26 +168,10 @@ def test_zero_evaluator_plays_the_immediate_win(cpu):
 
 
 # ---- the recorded argument errors ------------------------------------------------------------------------------------------------------
-def _call(lib, prefix, case):
-    """One case of tests/golden/evaluator_arg_errors.json: the evaluator is given as its eight fields (or null), every pointer is a
-    number that is never read (all calls return before any device work)."""
-    ev = None if case["ev"] is None else nat.Evaluator(*case["ev"])
-    args = [C.addressof(ev) if x == "ev" and ev is not None else (None if x == "ev" else x) for x in case["args"]]
-    return getattr(lib, prefix + case["fn"])(*args)
-
-
 def test_argument_errors_replay_the_recorded_table(golden_dir):
-    flavours = (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_"))
     table = json.load(open(os.path.join(golden_dir, "evaluator_arg_errors.json")))
     assert len(table) >= 40 and {c["fn"] for c in table} == {"evaluate", "tree_search_eval"}
-    for c in table:
-        for flavour, lib, prefix in flavours:
-            if c[flavour] is None:  # (an alignment rule: only the device flavour has it)
-                continue
-            rc, msg = c[flavour]
-            assert _call(lib, prefix, c) == rc, (flavour, c["fn"], c["case"])
-            if rc:
-                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])
+    replay_arg_errors(table)
     for kw in ({"iterations": 0}, {"iterations": 513}, {"explore": -1}, {"explore": 1025}):
         with pytest.raises(ValueError):
             G.EvaluatorTreeSearchGobbletPolicy(G.GobbletEvaluator.from_float(*float_net(64, 1)), **kw)
@@ -262,25 +248,25 @@ def test_policy_surface_on_cpu(cpu, many):
     assert pri.dtype == torch.float32 and np.allclose(pri.numpy(), exp_p / exp_p.sum(1, keepdims=True), rtol=1e-6, atol=0)
     assert np.array_equal(val.numpy(), (exp_v / 128.0).astype(np.float32))
     kw = dict(iterations=24, explore=96)
-    exp = R.run_search(cpu, net, st, tm, None, 24, 96)
+    exp = run("tree_search_eval", "cpu", st, tm, None, (24, 96), net)
     obs = torch.from_numpy(np.stack([oracle.observe(x, int(m), int(m))["observation"] for x, m in zip(st, tm)]))
     mask = torch.from_numpy(oracle.batch_legal_mask(st, tm))
     pol = G.EvaluatorTreeSearchGobbletPolicy(ev, **kw)
     a = pol.compute_actions(obs, mask)
-    assert a.dtype == torch.int32 and np.array_equal(a.numpy(), exp[3])
+    assert a.dtype == torch.int32 and np.array_equal(a.numpy(), exp["action"])
     vals = pol.action_values(st, tm)
     last = (pol.last_visits, pol.last_wins, pol.last_losses, pol.last_action, pol.last_nodes, pol.last_root_value, pol.last_root_priors)
-    R.same([t.numpy() for t in last], exp, R.SEARCH_NAMES)
-    seen = exp[0] > 0
-    assert np.array_equal(vals.numpy()[seen], ((exp[1] - exp[2])[seen] / (exp[0][seen] * 128.0)).astype(np.float32))
+    same(exp, [t.numpy() for t in last])
+    seen = exp["visits"] > 0
+    assert np.array_equal(vals.numpy()[seen], ((exp["wins"] - exp["losses"])[seen] / (exp["visits"][seen] * 128.0)).astype(np.float32))
     assert np.isneginf(vals.numpy()[~seen]).all()
     dist = pol.visit_distribution(st, tm)
-    assert np.allclose(dist.numpy(), exp[0] / 24.0, rtol=1e-6, atol=0) and np.allclose(dist.sum(1).numpy(), 1.0)
-    assert int(pol.compute_action(obs[0].numpy(), mask[0].numpy())) == int(exp[3][0])
+    assert np.allclose(dist.numpy(), exp["visits"] / 24.0, rtol=1e-6, atol=0) and np.allclose(dist.sum(1).numpy(), 1.0)
+    assert int(pol.compute_action(obs[0].numpy(), mask[0].numpy())) == int(exp["action"][0])
     r = pol.compute_actions_rllib({"observation": obs.numpy().reshape(30, -1), "action_mask": mask.numpy()})
-    assert [int(x) for x in r] == exp[3].tolist()
+    assert [int(x) for x in r] == exp["action"].tolist()
     f = pol.forward({"obs": {"obs": obs.numpy(), "mask": mask.numpy()}})
-    assert f["act"].dtype == np.int64 and f["act"].tolist() == exp[3].tolist()
+    assert f["act"].dtype == np.int64 and f["act"].tolist() == exp["action"].tolist()
     for bad in (dict(shift1=25), dict(shift_p=-1)):
         with pytest.raises(ValueError):
             G.GobbletEvaluator(net.w1, net.b1, net.w2, net.b2, **{**dict(shift1=0, shift_p=0, shift_v=0), **bad})

@@ -2,15 +2,15 @@
 k_evaluate and k_tree_eval with canaried outputs at 1, 3 and 65 boards, the float64 reference once more through the device, the two
 entry points replayed from a captured graph with weights and boards refreshed in place.  (No performance guard yet: a guard's ceiling
 is read from a device record of scripts/bench_evaluator_policy.py, and profiles/r10/evaluator_policy.json has no timing rows.)"""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from tests import evaluator_restatement as R
 from tests.test_evaluator_edges import SHIFT_TRIPLES, TOPS, compare_with_float, dial_cases, float_weights, midgame, search_dial  # noqa: F401
-from tests.test_gpu_evaluator_policy import DEV, DeviceNet, G, c5, device_evaluate, device_search, host_search, same_dict  # noqa: F401
+from tests.search_harness import DEV, Call, G, run, same  # noqa: F401  (G: the fixture)
+from tests.selfplay_harness import DeviceNet
+from tests.test_gpu_evaluator_policy import c5  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +20,12 @@ SIZES = (1, 3, 65)
 def on_device_equals_both(G, net, st, tm, mask, sizes=SIZES):
     """k_evaluate at every size (the boards repeated) against the restatement and the host flavour of the boards themselves."""
     exp = R.restate_evaluate(net, st, tm, mask)
-    R.same(R.run_evaluate(G._native.cpu_raw(), net, st, tm, mask), exp, R.EVAL_NAMES)
+    same(run("evaluate", "cpu", st, tm, mask, (), net), exp)
     dnet = DeviceNet(net)
     for n in sizes:
         idx = np.arange(n) % len(st)
-        got = device_evaluate(G, dnet, st[idx], tm[idx], None if mask is None else mask[idx])
-        R.same(got, [e[idx] for e in exp], R.EVAL_NAMES)
+        got = run("evaluate", DEV, st[idx], tm[idx], None if mask is None else mask[idx], (), dnet)
+        same(got, [e[idx] for e in exp])
     return exp
 
 
@@ -73,12 +73,12 @@ def test_search_on_a_logit_dial_on_device(G, midgame):
     st, tm, mask = R.dial_boards(midgame, top)
     st, tm, mask = st[[5, 0]], tm[[5, 0]], mask[[5, 0]]
     net = search_dial(top)
-    exp = host_search(G, net, st, tm, mask, 512, 1024)
-    same_dict(exp, dict(zip(R.SEARCH_NAMES, R.restate_search(net, st, tm, mask, 512, 1024))))
+    exp = run("tree_search_eval", "cpu", st, tm, mask, (512, 1024), net)
+    same(exp, R.restate_search(net, st, tm, mask, 512, 1024))
     dnet = DeviceNet(net)
     for n in SIZES:
         idx = np.arange(n) % 2
-        same_dict(device_search(G, dnet, st[idx], tm[idx], mask[idx], 512, 1024), {k: v[idx] for k, v in exp.items()})
+        same(run("tree_search_eval", DEV, st[idx], tm[idx], mask[idx], (512, 1024), dnet), {k: v[idx] for k, v in exp.items()})
     assert exp["root_priors"][0].max() == 255 and exp["visits"][0, top] == 512
 
 
@@ -95,10 +95,10 @@ def test_shift_sweep_on_device(G, c5, hidden, shifts):
     # |sum| <= 300 + 21 * 128 = 2988: >> 24 leaves 0 or -1, >> 7 at most 23; unshifted, sums of a few hundred reach 127
     assert (low == 65 * hidden) == (shifts[0] == 24) and (mid > 0) == (shifts[0] != 24)
     assert high == 0 if shifts[0] >= 7 else (high > 0 or shifts[0] == 3)
-    got = device_search(G, DeviceNet(net), st, tm, mask, 48, 16)
-    same_dict(got, host_search(G, net, st, tm, mask, 48, 16))
+    got = run("tree_search_eval", DEV, st, tm, mask, (48, 16), DeviceNet(net))
+    same(got, run("tree_search_eval", "cpu", st, tm, mask, (48, 16), net))
     if hidden == 64:
-        same_dict(got, dict(zip(R.SEARCH_NAMES, R.restate_search(net, st, tm, mask, 48, 16))))
+        same(got, R.restate_search(net, st, tm, mask, 48, 16))
 
 
 def test_dequantised_weights_against_the_float_reference_on_device(G, c5):
@@ -114,39 +114,30 @@ def test_dequantised_weights_against_the_float_reference_on_device(G, c5):
 class Session:
     """The two entry points on fixed device tensors: what a training loop keeps between weight refreshes."""
 
-    def __init__(self, G, net, n, iterations, explore):
-        self.nat, self.n, self.iterations, self.explore = G._native, n, iterations, explore
-        self.net = net
+    def __init__(self, net, iterations, explore):
+        self.net, self.params = net, (iterations, explore)
         self.arrays = [torch.empty_like(torch.from_numpy(a), device=DEV) for a in (net.w1, net.b1, net.w2, net.b2)]
-        self.st, self.tm = torch.zeros((n, 27), dtype=torch.int8, device=DEV), torch.zeros(n, dtype=torch.int8, device=DEV)
-        self.eval_out = [torch.zeros((n, 54), dtype=torch.uint8, device=DEV), torch.zeros(n, dtype=torch.int32, device=DEV),
-                         torch.zeros((n, 56), dtype=torch.int32, device=DEV)]
-        self.search_out = [torch.zeros((n, 54), dtype=torch.int32, device=DEV) for _ in range(3)] + \
-                          [torch.zeros(n, dtype=torch.int32, device=DEV) for _ in range(3)] + [torch.zeros((n, 54), dtype=torch.uint8, device=DEV)]
+        self.calls = [Call("evaluate", DEV, self), Call("tree_search_eval", DEV, self)]
+
+    def struct(self):
+        return self.net.struct(self.arrays)
 
     def load(self, net, st, tm):
-        """copy_ into the SAME tensors, on the current stream (the shifts are launch arguments: a refreshed network keeps them)."""
+        """copy_ into the SAME tensors, on the current stream (the shifts are launch arguments: a refreshed network keeps them);
+        every output is filled anew."""
         assert (net.shift1, net.shift_p, net.shift_v, net.hidden) == (self.net.shift1, self.net.shift_p, self.net.shift_v, self.net.hidden)
         for dst, src in zip(self.arrays, (net.w1, net.b1, net.w2, net.b2)):
             dst.copy_(torch.from_numpy(src), non_blocking=False)
-        self.st.copy_(torch.from_numpy(st))
-        self.tm.copy_(torch.from_numpy(tm))
+        for call in self.calls:
+            call.load(st, tm)
 
     def launch(self):
-        nat, ev, s = self.nat, self.net.struct(self.arrays), self.nat.current_stream(DEV)
-        nat.check(nat.lib().gbl_evaluate(self.st.data_ptr(), self.tm.data_ptr(), None, C.addressof(ev), *[t.data_ptr() for t in self.eval_out],
-                                         self.n, s), "gbl_evaluate")
-        nat.check(nat.lib().gbl_tree_search_eval(self.st.data_ptr(), self.tm.data_ptr(), None, C.addressof(ev), self.iterations, self.explore,
-                                                 *[t.data_ptr() for t in self.search_out], self.n, s), "gbl_tree_search_eval")
+        self.calls[0].launch()
+        self.calls[1].launch(self.params)
 
-    def check(self, G, net, st, tm):
-        cpu = G._native.cpu_raw()
-        R.same([t.cpu().numpy() for t in self.eval_out], R.run_evaluate(cpu, net, st, tm), R.EVAL_NAMES)
-        R.same([t.cpu().numpy() for t in self.search_out], R.run_search(cpu, net, st, tm, None, self.iterations, self.explore), R.SEARCH_NAMES)
-
-    def clear(self):
-        for t in self.eval_out + self.search_out:
-            t.fill_(77)
+    def check(self, net, st, tm):
+        same(self.calls[0].results(), run("evaluate", "cpu", st, tm, None, (), net))
+        same(self.calls[1].results(), run("tree_search_eval", "cpu", st, tm, None, self.params, net))
 
 
 def test_graph_replay_with_weights_and_boards_refreshed_in_place(G, c5):
@@ -156,7 +147,7 @@ def test_graph_replay_with_weights_and_boards_refreshed_in_place(G, c5):
     n, I = 65, 16
     nets = [R.random_net(64, s, 3, 5, 12) for s in (71, 72)]
     boards = [(np.ascontiguousarray(c5[0][o:o + n]), np.ascontiguousarray(c5[1][o:o + n])) for o in (0, 300)]
-    ses = Session(G, nets[0], n, I, 16)
+    ses = Session(nets[0], I, 16)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -167,15 +158,13 @@ def test_graph_replay_with_weights_and_boards_refreshed_in_place(G, c5):
             ses.launch()
         for net, (st, tm) in zip(nets, boards):
             ses.load(net, st, tm)
-            ses.clear()
             g.replay()
             side.synchronize()
-            ses.check(G, net, st, tm)
+            ses.check(net, st, tm)
         # uncaptured, inputs produced on the side stream: the second network on the first boards
         ses.load(nets[1], *boards[0])
-        ses.clear()
         ses.launch()
         side.synchronize()
-        ses.check(G, nets[1], *boards[0])
+        ses.check(nets[1], *boards[0])
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()

@@ -10,50 +10,17 @@ import pytest
 import torch
 
 import oracle
-from tests.test_playout_policy import arena, restate, run
+from tests.search_harness import DEV, Call, G, midgame_boards, run, same  # noqa: F401  (G: the fixture)
+from tests.test_playout_policy import arena, restate
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-THREADS = 16
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
 
 
 @pytest.fixture(scope="module")
 def c5(G):
-    env = G.BatchedGobblet(65536, DEV, auto_reset=True, seed=11)
-    env.rollout(64)
-    torch.cuda.synchronize()
-    st, tm = env.squares.cpu().numpy().copy(), env.to_move.cpu().numpy().copy()
-    assert (oracle.batch_winner(st) == 0).all() and 0.3 < tm.mean() < 0.7
-    return st, tm
-
-
-def device_run(G, st, tm, mask, K, M, seed, env_base, call):
-    nat = G._native
-    n = len(st)
-    d_st, d_tm = torch.from_numpy(np.ascontiguousarray(st)).to(DEV), torch.from_numpy(np.ascontiguousarray(tm)).to(DEV)
-    d_mk = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask)).to(DEV)
-    w = torch.full((n, 54), -7, dtype=torch.int32, device=DEV)
-    l, a, p = torch.full_like(w, -7), torch.full((n,), -7, dtype=torch.int32, device=DEV), torch.full((n,), -7, dtype=torch.int32, device=DEV)
-    nat.check(nat.lib().gbl_playout_values(d_st.data_ptr(), d_tm.data_ptr(), nat.ptr(d_mk), K, M, seed, env_base, call, w.data_ptr(),
-                                           l.data_ptr(), a.data_ptr(), p.data_ptr(), n, nat.current_stream(DEV)), "gbl_playout_values")
-    torch.cuda.synchronize()
-    return w.cpu().numpy(), l.cpu().numpy(), a.cpu().numpy(), p.cpu().numpy()
-
-
-def same(got, exp):
-    for name, g, e in zip(("wins", "losses", "action", "plies"), got, exp):
-        assert np.array_equal(g, e), (name, np.argwhere(g != e)[:5])
+    return midgame_boards()
 
 
 @pytest.mark.parametrize("K,M,call,env_base", [(7, 30, 5, (1 << 40) - 20), (3, 255, 0, 0), (5, 0, 2, 11)])
@@ -62,22 +29,20 @@ def test_device_equals_restatement(G, c5, K, M, call, env_base):
     st = np.concatenate([np.zeros((1, 27), np.int8), st])
     tm = np.concatenate([np.zeros(1, np.int8), tm])
     mask = None if K != 3 else (np.random.default_rng(1).random((len(st), 54)) < 0.5).astype(np.int8)
-    same(device_run(G, st, tm, mask, K, M, 9, env_base, call), restate(st, tm, mask, K, M, 9, env_base, call))
+    same(run("playout_values", DEV, st, tm, mask, (K, M, 9, env_base, call)), restate(st, tm, mask, K, M, 9, env_base, call))
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 4096])
 def test_device_equals_host_flavour(G, c5, n):
     st, tm = c5[0][:n], c5[1][:n]
-    cpu = G._native.cpu_raw()
-    same(device_run(G, st, tm, None, 64, 64, 3, 17, 4), run(cpu, st, tm, None, 64, 64, 3, 17, 4))
+    same(run("playout_values", DEV, st, tm, None, (64, 64, 3, 17, 4)), run("playout_values", "cpu", st, tm, None, (64, 64, 3, 17, 4)))
     mask = (np.random.default_rng(n).random((n, 54)) < 0.3).astype(np.int8)
-    same(device_run(G, st, tm, mask, 64, 64, 3, 17, 4), run(cpu, st, tm, mask, 64, 64, 3, 17, 4))
+    same(run("playout_values", DEV, st, tm, mask, (64, 64, 3, 17, 4)), run("playout_values", "cpu", st, tm, mask, (64, 64, 3, 17, 4)))
 
 
 def test_device_equals_host_flavour_config5_full_size(G, c5):
     st, tm = c5
-    cpu = G._native.cpu_raw()
-    same(device_run(G, st, tm, None, 4, 64, 0, 0, 0), run(cpu, st, tm, None, 4, 64, 0, 0, 0))
+    same(run("playout_values", DEV, st, tm, None, (4, 64, 0, 0, 0)), run("playout_values", "cpu", st, tm, None, (4, 64, 0, 0, 0)))
 
 
 def test_arena_device_equals_host_flavour(G):
@@ -93,9 +58,9 @@ def test_policy_on_device(G, c5):
     st, tm = torch.from_numpy(c5[0][:256]).to(DEV), torch.from_numpy(c5[1][:256]).to(DEV)
     pol = G.MonteCarloGobbletPolicy(playouts=32, seed=5, device=DEV)
     v = pol.action_values(st, tm)
-    exp = run(G._native.cpu_raw(), c5[0][:256], c5[1][:256], None, 32, 64, 5, 0, 0)
-    assert pol.last_wins.device.type == "cuda" and np.array_equal(pol.last_wins.cpu().numpy(), exp[0])
-    assert np.array_equal(pol.last_action.cpu().numpy(), exp[2]) and np.array_equal(pol.last_plies.cpu().numpy(), exp[3])
+    exp = run("playout_values", "cpu", c5[0][:256], c5[1][:256], None, (32, 64, 5, 0, 0))
+    assert pol.last_wins.device.type == "cuda" and np.array_equal(pol.last_wins.cpu().numpy(), exp["wins"])
+    assert np.array_equal(pol.last_action.cpu().numpy(), exp["action"]) and np.array_equal(pol.last_plies.cpu().numpy(), exp["plies"])
     assert torch.isfinite(v).sum() == int((oracle.batch_legal_mask(c5[0][:256], c5[1][:256]) != 0).sum())
 
 
@@ -106,14 +71,10 @@ RECORD = os.path.join(ROOT, "profiles", "r07", "playout_policy.json")
 @pytest.mark.parametrize("n,K", [(4096, 64), (65536, 64), (65536, 16)])
 def test_playout_perf_guard(G, c5, n, K):
     rec = {(r["boards"], r["playouts"]): r for r in json.load(open(RECORD))["rows"]}[(n, K)]
-    nat = G._native
-    st, tm = torch.from_numpy(c5[0][:n]).to(DEV), torch.from_numpy(c5[1][:n]).to(DEV)
-    w = torch.empty((n, 54), dtype=torch.int32, device=DEV)
-    l, a, p = torch.empty_like(w), torch.empty(n, dtype=torch.int32, device=DEV), torch.empty(n, dtype=torch.int32, device=DEV)
+    launch = Call("playout_values", DEV).load(c5[0][:n], c5[1][:n]).launch
 
     def go(call):
-        nat.check(nat.lib().gbl_playout_values(st.data_ptr(), tm.data_ptr(), None, K, 64, 0, 0, call, w.data_ptr(), l.data_ptr(),
-                                               a.data_ptr(), p.data_ptr(), n, nat.current_stream(DEV)), "gbl_playout_values")
+        launch((K, 64, 0, 0, call))
     go(0)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -9,20 +9,13 @@ import pytest
 import torch
 
 import oracle
+from tests.search_harness import G  # noqa: F401  (G: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 THREADS = 16
 POL = {"random": 0, "greedy1": 1, "greedy": 2, "greedy2": 2, "greedy3": 3}
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    return g
 
 
 def npy(x):

@@ -3,8 +3,6 @@ and between canaries; NULL optional outputs; weights (0, 0) against gbl_collect_
 replay of collect(..., noise=) with the ply on the device.  The launches go through the launchers of gbl_tree_search_eval and
 gbl_collect_search_solve (one grid rule, covered beyond its cap by tests/test_gpu_evaluator_policy.py and
 tests/test_gpu_selfplay_solve.py), so no case beyond the grid cap is repeated here."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -12,66 +10,20 @@ import torch
 import oracle
 
 from tests import evaluator_restatement as R
-from tests import noise_restatement as N
 from tests import selfplay_harness as H
-from tests.selfplay_harness import DEV, PAD, DeviceNet, _evaluator, same
+from tests.search_harness import DEV, G, run  # noqa: F401  (G: the fixture)
+from tests.search_harness import same as same_arrays
+from tests.selfplay_harness import DeviceNet, _evaluator, same
 from tests.test_selfplay_solve import EXPLORE, collect_solve, fixture_boards, smoke_net
 
 pytestmark = pytest.mark.gpu
 
-THREADS = 16
 SEED, ENV_BASE, CALL = 0x1234567890ABCDEF, (1 << 40) + 3, (1 << 24) - 1
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
 
 
 @pytest.fixture(scope="module")
 def c5(G):
     return fixture_boards(256, DEV)
-
-
-def device_search_noise(G, dnet, st, tm, mask, iterations, explore, w, seed, env_base, call, keep=N.NOISE_SEARCH_NAMES):
-    """gbl_tree_search_eval_noise with only the outputs named in `keep` given, each between canary rows: {name: array}."""
-    nat = G._native
-    n = len(st)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
-    d_st, d_tm, d_mk = dev(st), dev(tm), None if mask is None else dev(mask)
-    outs = {}
-    for k in N.NOISE_SEARCH_NAMES:
-        if k not in keep:
-            continue
-        wide, byte = k in ("visits", "wins", "losses", "root_priors", "root_mixed"), k in ("root_priors", "root_mixed")
-        shape = (n + 2 * PAD, 54) if wide else (n + 2 * PAD,)
-        outs[k] = torch.full(shape, 99 if byte else -7, dtype=torch.uint8 if byte else torch.int32, device=DEV)
-    ev = dnet.struct()
-    nat.check(nat.lib().gbl_tree_search_eval_noise(d_st.data_ptr(), d_tm.data_ptr(), nat.ptr(d_mk), C.addressof(ev), iterations, explore, w,
-                                                   seed, env_base, call,
-                                                   *[outs[k][PAD:].data_ptr() if k in outs else None for k in N.NOISE_SEARCH_NAMES], n,
-                                                   nat.current_stream(DEV)), "gbl_tree_search_eval_noise")
-    torch.cuda.synchronize()
-    got = {}
-    for k, t in outs.items():
-        a = t.cpu().numpy()
-        fill = 99 if a.dtype == np.uint8 else -7
-        assert (a[:PAD] == fill).all() and (a[PAD + n:] == fill).all(), "output %s was written outside its rows" % k
-        got[k] = a[PAD:PAD + n]
-    return got
-
-
-def host_search_noise(G, net, *args):
-    return dict(zip(N.NOISE_SEARCH_NAMES, N.run_search_noise(G._native.cpu_raw(), net, *args)))
-
-
-def same_dict(got, exp):
-    for k in got:
-        assert got[k].dtype == exp[k].dtype and np.array_equal(got[k], exp[k]), (k, np.argwhere(got[k] != exp[k])[:5])
 
 
 @pytest.mark.parametrize("iterations", [1, 8, 64])
@@ -82,9 +34,9 @@ def test_k_tree_eval_noise_equals_host_flavour(G, c5, hidden, iterations):
     for n in (1, 5, 65):
         st, tm = c5[0][:n], c5[1][:n]
         for w in (0, 1, 64, 256):
-            args = (st, tm, None, iterations, EXPLORE, w, SEED, ENV_BASE, CALL if w != 64 else 0)
-            got = device_search_noise(G, dnet, *args)
-            same_dict(got, host_search_noise(G, net, *args))
+            args = (st, tm, None, (iterations, EXPLORE, w, SEED, ENV_BASE, CALL if w != 64 else 0))
+            got = run("tree_search_eval_noise", DEV, *args, dnet)
+            same_arrays(got, run("tree_search_eval_noise", "cpu", *args, net))
             if w == 0:
                 assert np.array_equal(got["root_mixed"], got["root_priors"])
 
@@ -98,15 +50,15 @@ def test_masked_roots_and_null_outputs(G, c5):
     mask[0] = 0  # no candidate: nothing is drawn, the rows stay zeros
     mask[1] = 0
     mask[1, np.flatnonzero(legal[1])[3]] = 1  # one candidate: nu = 255, and so is pi
-    args = (st, tm, mask, 24, EXPLORE, 128, SEED, 7, 5)
-    full = device_search_noise(G, dnet, *args)
-    same_dict(full, host_search_noise(G, net, *args))
+    args = (st, tm, mask, (24, EXPLORE, 128, SEED, 7, 5))
+    full = run("tree_search_eval_noise", DEV, *args, dnet)
+    same_arrays(full, run("tree_search_eval_noise", "cpu", *args, net))
     assert not full["root_mixed"][0].any() and full["action"][0] == -1 and full["nodes"][0] == 1
     assert full["root_mixed"][1].max() == 255 and (full["root_mixed"][1] > 0).sum() == 1
     for keep in (("action",), ("root_mixed",), ("visits", "root_priors"), ("wins", "losses", "nodes", "root_value"), ()):
-        got = device_search_noise(G, dnet, *args, keep=keep)
+        got = run("tree_search_eval_noise", DEV, *args, dnet, keep)
         assert set(got) == set(keep)
-        same_dict(got, full)
+        same_arrays(got, full)
 
 
 # ---- self-play -----------------------------------------------------------------------------------------------------------------------

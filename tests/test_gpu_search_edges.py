@@ -8,59 +8,33 @@ import pytest
 import torch
 
 import oracle
-from tests import test_gpu_playout_policy as GP
 from tests import test_playout_policy as PP
+from tests.search_harness import DEV, PLAYOUT_NAMES, G, midgame_boards, run, same  # noqa: F401  (G: the fixture)
+from tests.search_harness import TREE_NAMES as NAMES
 from tests.test_gpu_selfplay_search import device_collect
-from tests.test_gpu_tree_policy import device_run, same
 from tests.test_search_edges import (EXPLORES, I_MAX, M_MAX, PLAYOUT_BYTES, TREE_BYTES, byte_value_boards, check_saturated_collect,
                                      check_saturated_tree, saturated_boards, saturated_collect_args)
 from tests.test_search_edges import CALL as SAT_CALL
 from tests.test_search_edges import ENV_BASE as SAT_ENV_BASE
 from tests.test_search_edges import SEED as SAT_SEED
-from tests.test_selfplay_search import CODES, SCALARS, cells, collect, strides, targets_numpy
+from tests.test_selfplay_search import SCALARS, cells, collect, strides, targets_numpy
 from tests.test_selfplay_search import same as same_collect
-from tests.test_tree_policy import NAMES, restate, run
+from tests.test_tree_policy import restate
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-THREADS = 16
 GRID_CAP = 1 << 20  # the kernels' largest grid: board b of a larger batch is served by workgroup b % 2^20 on its trip b / 2^20
-PLAYOUT_NAMES = ("wins", "losses", "action", "plies")
 TRAJ = [k for k, _, _ in SCALARS]
 
 
 @pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
-
-
-@pytest.fixture(scope="module")
 def c5(G):
-    """The 65 536 midgame boards of the other GPU modules, with their turn counters."""
-    env = G.BatchedGobblet(65536, DEV, auto_reset=True, seed=11, track_turn=True)
-    env.rollout(64)
-    torch.cuda.synchronize()
-    st, tm, turn = env.squares.cpu().numpy().copy(), env.to_move.cpu().numpy().copy(), env.turn.cpu().numpy().copy()
-    assert (oracle.batch_winner(st) == 0).all() and 0.3 < tm.mean() < 0.7
-    return st, tm, turn
+    return midgame_boards(turn=True)
 
 
 def to(device, a):
     """A copy of `a` on `device` (a copy on the host too: the host flavour writes its in/out arguments in place)."""
     return torch.from_numpy(np.array(a)).to(device)
-
-
-def entry(G, device, name):
-    """(entry point, stream) of gbl_<name> for the device flavour or, with device "cpu", the host flavour."""
-    nat = G._native
-    if device == "cpu":
-        return getattr(nat.cpu_raw(), "gbl_cpu_" + name), None
-    return getattr(nat.lib(), "gbl_" + name), nat.current_stream(device)
 
 
 # ---- B1: k_outcome_targets against the definition --------------------------------------------------------------------------------
@@ -145,30 +119,6 @@ def test_outcome_targets_at_the_ply_limit(G, layout):
 
 
 # ---- B2: gbl_collect_search's tallies and NULL outputs ----------------------------------------------------------------------------
-def collect_some(G, device, st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, keep=TRAJ,
-                 counters=None):
-    """gbl_collect_search of either flavour with only the trajectory arrays named in `keep` given (the others NULL), and optionally
-    tallies.  Returns ({name: (T, n, ...)}, state, to_move, done, turn) like tests.test_selfplay_search.collect."""
-    nat = G._native
-    f, stream = entry(G, device, "collect_search")
-    n = len(st)
-    ps, ts, total = strides(n, T, layout)
-    traj = {k: to(device, np.full((total,) + tail, -7, dt)) for k, dt, tail in SCALARS if k in keep}
-    d_st, d_tm, d_dn = to(device, np.asarray(st, np.int8)), to(device, np.asarray(tm, np.int8)), to(device, np.full(n, 5, np.int8))
-    d_tn = None if turn is None else to(device, np.asarray(turn, np.int32))
-    rc = f(d_st.data_ptr(), d_tm.data_ptr(), d_dn.data_ptr(), *[nat.ptr(traj.get(k)) for k in TRAJ], n, ps, ts, seed, env_base, ply0, None, T,
-           CODES[pols[0]], CODES[pols[1]], its[0], its[1], pls[0], pls[1], M, X, sample_plies, illegal_mode, nat.ptr(counters), nat.ptr(d_tn), stream)
-    assert rc == 0, (nat.lib().gbl_last_error(), nat.cpu_raw().gbl_cpu_last_error())
-    if device != "cpu":
-        torch.cuda.synchronize()
-    at = cells(n, T, layout)
-    untouched = np.ones(total, bool)
-    untouched[at.ravel()] = False
-    host = {k: v.cpu().numpy() for k, v in traj.items()}
-    assert all((v[untouched] == -7).all() for v in host.values())  # (nothing outside the cells is written)
-    return ({k: v[at] for k, v in host.items()}, d_st.cpu().numpy(), d_tm.cpu().numpy(), d_dn.cpu().numpy(), None if d_tn is None else d_tn.cpu().numpy())
-
-
 def tallies_of(tr, n, T):
     """What the four tallies of a launch must be, from its recorded trajectory."""
     return [n * T, int((tr["done"] != 0).sum()), int((tr["winner"] == 1).sum()), int((tr["winner"] == -1).sum())]
@@ -188,7 +138,7 @@ def test_collect_search_tallies_and_two_outputs(G, c5, n):
             full = device_collect(G, st, tm, turn, *args)
             same_collect(full, host)
             counters = torch.zeros((nat.COUNTER_STRIPES, nat.COUNTER_STRIDE), dtype=torch.int64, device=DEV)
-            some = collect_some(G, DEV, st, tm, turn, *args, keep=("winner", "done"), counters=counters)
+            some = device_collect(G, st, tm, turn, *args, keep=("winner", "done"), counters=counters)
             assert set(some[0]) == {"winner", "done"}
             for k in some[0]:
                 assert np.array_equal(some[0][k], full[0][k]) and np.array_equal(some[0][k], host[0][k]), (layout, pols, k)
@@ -199,7 +149,7 @@ def test_collect_search_tallies_and_two_outputs(G, c5, n):
             assert c.sum(0)[:4].tolist() == first and not c[:, 4:].any(), (layout, pols, c.sum(0), first)
             # a second launch on the same counters (another seed: other games) adds its own tallies
             args2 = args[:-3] + (4, 17, 4)
-            again = collect_some(G, DEV, st, tm, turn, *args2, keep=("winner", "done"), counters=counters)
+            again = device_collect(G, st, tm, turn, *args2, keep=("winner", "done"), counters=counters)
             second = tallies_of(again[0], n, T)
             assert counters.cpu().numpy().sum(0)[:4].tolist() == [a + b for a, b in zip(first, second)], (layout, pols)
             finished += first[1] + second[1]
@@ -214,7 +164,7 @@ def test_collect_search_each_output_null_in_turn(G, c5):
     full = device_collect(G, st, tm, turn, *args)
     for missing in TRAJ:
         keep = [k for k in TRAJ if k != missing]
-        got = collect_some(G, DEV, st, tm, turn, *args, keep=keep)
+        got = device_collect(G, st, tm, turn, *args, keep=keep)
         assert set(got[0]) == set(keep)
         for k in keep:
             assert np.array_equal(got[0][k], full[0][k]), (missing, k)
@@ -242,7 +192,7 @@ def test_saturated_tree_equals_restatement(G, playouts):
     st, tm, mask, _ = saturated_boards()
     assert G._native.lib() is not None
     for explore in EXPLORES:
-        got = device_run(G, st, tm, mask, I_MAX, playouts, M_MAX, explore, SAT_SEED, SAT_ENV_BASE, SAT_CALL)
+        got = run("tree_search", DEV, st, tm, mask, (I_MAX, playouts, M_MAX, explore, SAT_SEED, SAT_ENV_BASE, SAT_CALL))
         check_saturated_tree(got, explore, playouts)
 
 
@@ -261,33 +211,18 @@ def test_saturated_open_children_equal_host_flavour(G, c5):
     mask = np.zeros((4, 54), np.int8)
     for b in range(4):
         mask[b, rng.choice(np.flatnonzero(legal[b]), 2, replace=False)] = 1
-    cpu = G._native.cpu_raw()
     args = (I_MAX, 256, M_MAX, 16, 2, SAT_ENV_BASE - 1, SAT_CALL)
-    got = device_run(G, st, tm, mask, *args)
-    same(got, run(cpu, st, tm, mask, *args))
-    v, w, l = got[:3]
+    got = run("tree_search", DEV, st, tm, mask, args)
+    same(got, run("tree_search", "cpu", st, tm, mask, args))
+    v, w, l = got["visits"], got["wins"], got["losses"]
     assert ((v > 0).sum(1) == 2).all() and (v.sum(1) == I_MAX).all() and (w + l <= v * 256).all() and (w + l).sum() > 4 * 128 * 256
     pargs = (4096, M_MAX, 2, SAT_ENV_BASE - 1, SAT_CALL)
-    gotp = GP.device_run(G, st, tm, mask, *pargs)
-    GP.same(gotp, PP.run(cpu, st, tm, mask, *pargs))
-    assert ((gotp[0] + gotp[1]) <= 4096).all() and (gotp[0] + gotp[1]).sum() > 4 * 4096
+    gotp = run("playout_values", DEV, st, tm, mask, pargs)
+    same(gotp, run("playout_values", "cpu", st, tm, mask, pargs))
+    assert ((gotp["wins"] + gotp["losses"]) <= 4096).all() and (gotp["wins"] + gotp["losses"]).sum() > 4 * 4096
 
 
 # ---- B4: more boards than the grid cap --------------------------------------------------------------------------------------------
-def search_some(G, device, name, names, st, tm, mask, params, keep):
-    """gbl_tree_search / gbl_playout_values of either flavour with only the outputs named in `keep` given: {name: array}."""
-    nat = G._native
-    f, stream = entry(G, device, name)
-    n = len(st)
-    out = {k: torch.full((n, 54) if k in ("visits", "wins", "losses") else (n,), -7, dtype=torch.int32, device=device) for k in names if k in keep}
-    d_st, d_tm, d_mk = to(device, st), to(device, tm), None if mask is None else to(device, mask)
-    rc = f(d_st.data_ptr(), d_tm.data_ptr(), nat.ptr(d_mk), *params, *[nat.ptr(out.get(k)) for k in names], n, stream)
-    assert rc == 0, (nat.lib().gbl_last_error(), nat.cpu_raw().gbl_cpu_last_error())
-    if device != "cpu":
-        torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
 @pytest.fixture(scope="module")
 def beyond(c5):
     """2^20 + 65 boards: the grid-stride loops' second trip runs on 65 workgroups."""
@@ -297,31 +232,29 @@ def beyond(c5):
     return st, tm
 
 
-def check_beyond(G, name, names, beyond, params, keep):
+def check_beyond(name, beyond, params, keep):
     """Whole arrays against the host flavour, and the second trip's boards against a launch of their own at env_base + 2^20
     (a second trip that keeps anything of the first -- its tree's links, its counters, its board ids -- differs from it)."""
     st, tm = beyond
     seed_at = {"tree_search": 4, "playout_values": 2}[name]  # (params: ..., seed, env_base, call)
     assert params[seed_at + 1] == 5
-    got = search_some(G, DEV, name, names, st, tm, None, params, keep)
-    exp = search_some(G, "cpu", name, names, st, tm, None, params, keep)
+    got = run(name, DEV, st, tm, None, params, keep=keep)
     assert set(got) == set(keep)
-    for k in keep:
-        assert np.array_equal(got[k], exp[k]), (k, np.argwhere(got[k] != exp[k])[:5])
+    same(got, run(name, "cpu", st, tm, None, params, keep=keep))
     tail_params = params[:seed_at + 1] + (5 + GRID_CAP,) + params[seed_at + 2:]
-    tail = search_some(G, DEV, name, names, st[GRID_CAP:], tm[GRID_CAP:], None, tail_params, names)
+    tail = run(name, DEV, st[GRID_CAP:], tm[GRID_CAP:], None, tail_params)
     for k in keep:
         assert np.array_equal(got[k][GRID_CAP:], tail[k]), k
     return got
 
 
 def test_tree_search_beyond_the_grid_cap(G, beyond):
-    got = check_beyond(G, "tree_search", NAMES, beyond, (2, 1, 2, 16, 7, 5, 3), ("visits", "action", "nodes", "plies"))
+    got = check_beyond("tree_search", beyond, (2, 1, 2, 16, 7, 5, 3), ("visits", "action", "nodes", "plies"))
     assert (got["visits"].sum(1) == 2).all() and (got["nodes"] >= 2).all() and (got["nodes"] <= 3).all()
 
 
 def test_playout_values_beyond_the_grid_cap(G, beyond):
-    got = check_beyond(G, "playout_values", PLAYOUT_NAMES, beyond, (1, 2, 7, 5, 3), ("wins", "action", "plies"))
+    got = check_beyond("playout_values", beyond, (1, 2, 7, 5, 3), ("wins", "action", "plies"))
     assert (got["wins"] >= 0).all() and (got["wins"] <= 1).all()
 
 
@@ -330,9 +263,9 @@ def test_collect_search_beyond_the_grid_cap(G, beyond):
     st, tm = beyond
     args = (2, ("tree", "random"), (2, 2), (1, 1), 2, 16, 0, nat.ILLEGAL_NOOP, "time", 7, 5, 3)
     keep = ("actions", "done")
-    got = collect_some(G, DEV, st, tm, None, *args, keep=keep)
-    exp = collect_some(G, "cpu", st, tm, None, *args, keep=keep)
-    tail = collect_some(G, DEV, st[GRID_CAP:], tm[GRID_CAP:], None, *args[:-2], 5 + GRID_CAP, 3, keep=keep)
+    got = device_collect(G, st, tm, None, *args, keep=keep)
+    exp = collect(nat.cpu_raw(), st, tm, None, *args, keep=keep)
+    tail = device_collect(G, st[GRID_CAP:], tm[GRID_CAP:], None, *args[:-2], 5 + GRID_CAP, 3, keep=keep)
     for k in keep:
         assert np.array_equal(got[0][k], exp[0][k]), (k, np.argwhere(got[0][k] != exp[0][k])[:5])
         assert np.array_equal(got[0][k][:, GRID_CAP:], tail[0][k]), k
@@ -341,73 +274,35 @@ def test_collect_search_beyond_the_grid_cap(G, beyond):
 
 
 # ---- B5: canaries, unaligned inputs, byte values --------------------------------------------------------------------------------------
-GUARD = 0x5A
-
-
-def guarded(device_bytes_before, array):
-    """`array` copied into a guard-filled device buffer, `device_bytes_before` bytes in; (the view, the whole buffer as bytes)."""
-    raw = np.ascontiguousarray(array).view(np.uint8).ravel()
-    buf = torch.full((device_bytes_before + raw.size + 256,), GUARD, dtype=torch.uint8, device=DEV)
-    buf[device_bytes_before:device_bytes_before + raw.size] = torch.from_numpy(raw.copy()).to(DEV)
-    return buf[device_bytes_before:device_bytes_before + raw.size], buf
-
-
-def guards_intact(buf, before, size):
-    b = buf.cpu().numpy()
-    return (b[:before] == GUARD).all() and (b[before + size:] == GUARD).all() and len(b) == before + size + 256
-
-
-def canary_run(G, name, names, st, tm, mask, params):
-    """The entry point with every output a view 4 bytes into a guard-filled buffer and state / to_move / mask views at odd byte
-    offsets: the outputs, after checking every guard byte and that the inputs are as given."""
-    nat = G._native
-    f, stream = entry(G, DEV, name)
-    n = len(st)
-    ins = [guarded(off, a) for off, a in ((1, st), (3, tm), (5, mask))]
-    assert all(v.data_ptr() % 2 == 1 for v, _ in ins)
-    shapes = {k: (n, 54) if k in ("visits", "wins", "losses") else (n,) for k in names}
-    outs = {k: guarded(4, np.full(shapes[k], -7, np.int32)) for k in names}
-    assert all(v.data_ptr() % 8 == 4 for v, _ in outs.values())
-    nat.check(f(*[v.data_ptr() for v, _ in ins], *params, *[outs[k][0].data_ptr() for k in names], n, stream), name)
-    torch.cuda.synchronize()
-    for (v, buf), off, a in zip(ins, (1, 3, 5), (st, tm, mask)):
-        assert guards_intact(buf, off, a.size) and np.array_equal(v.cpu().numpy().view(np.int8).reshape(a.shape), a), name
-    for k in names:
-        assert guards_intact(outs[k][1], 4, 4 * int(np.prod(shapes[k]))), (name, k)
-    return tuple(outs[k][0].cpu().numpy().view(np.int32).reshape(shapes[k]) for k in names)
-
-
 @pytest.mark.parametrize("n", [1, 65, 257])
 def test_search_outputs_stay_inside_their_arrays(G, c5, n):
     st, tm = np.array(c5[0][:n]), np.array(c5[1][:n])
     mask = (np.random.default_rng(n).random((n, 54)) < 0.5).astype(np.int8)
     targs = (40, 6, 30, 64, 3, 17, 4)
-    same(canary_run(G, "tree_search", NAMES, st, tm, mask, targs), device_run(G, st, tm, mask, *targs))
+    same(run("tree_search", DEV, st, tm, mask, targs, misaligned=True), run("tree_search", DEV, st, tm, mask, targs))
     pargs = (8, 30, 3, 17, 4)
-    GP.same(canary_run(G, "playout_values", PLAYOUT_NAMES, st, tm, mask, pargs), GP.device_run(G, st, tm, mask, *pargs))
+    same(run("playout_values", DEV, st, tm, mask, pargs, misaligned=True), run("playout_values", DEV, st, tm, mask, pargs))
 
 
 def test_each_search_output_null_in_turn(G, c5):
     n = 65
     st, tm = c5[0][:n], c5[1][:n]
     mask = (np.random.default_rng(n).random((n, 54)) < 0.5).astype(np.int8)
-    for name, names, params, plain in (("tree_search", NAMES, (40, 6, 30, 64, 3, 17, 4), device_run),
-                                       ("playout_values", PLAYOUT_NAMES, (8, 30, 3, 17, 4), GP.device_run)):
-        full = dict(zip(names, plain(G, st, tm, mask, *params)))
+    for name, names, params in (("tree_search", NAMES, (40, 6, 30, 64, 3, 17, 4)), ("playout_values", PLAYOUT_NAMES, (8, 30, 3, 17, 4))):
+        full = run(name, DEV, st, tm, mask, params)
         for missing in names:
             keep = [k for k in names if k != missing]
-            got = search_some(G, DEV, name, names, st, tm, mask, params, keep)
+            got = run(name, DEV, st, tm, mask, params, keep=keep)
             assert set(got) == set(keep)
-            for k in keep:
-                assert np.array_equal(got[k], full[k]), (name, missing, k)
+            same(got, full)
 
 
 def test_nonzero_bytes_are_set_bytes_on_the_device(G):
     """to_move and mask bytes of -128, -1, 2 and 127 are read as set: the 0 / 1 inputs' result, which is the restatement's."""
     st, tm, mask, tm2, mask2 = byte_value_boards()
     exp = restate(st, tm, mask, *TREE_BYTES)
-    same(device_run(G, st, tm, mask, *TREE_BYTES), exp)
-    same(device_run(G, st, tm2, mask2, *TREE_BYTES), exp)
+    same(run("tree_search", DEV, st, tm, mask, TREE_BYTES), exp)
+    same(run("tree_search", DEV, st, tm2, mask2, TREE_BYTES), exp)
     exp = PP.restate(st, tm, mask, *PLAYOUT_BYTES)
-    GP.same(GP.device_run(G, st, tm, mask, *PLAYOUT_BYTES), exp)
-    GP.same(GP.device_run(G, st, tm2, mask2, *PLAYOUT_BYTES), exp)
+    same(run("playout_values", DEV, st, tm, mask, PLAYOUT_BYTES), exp)
+    same(run("playout_values", DEV, st, tm2, mask2, PLAYOUT_BYTES), exp)

@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
 from tests import evaluator_restatement as R
 from tests import selfplay_harness as H
+from tests.search_harness import G, midgame_boards  # noqa: F401  (G: the fixture)
 from tests.selfplay_harness import DEV, DeviceNet, same
 from tests.test_selfplay_eval import collect_eval, restate_collect
 
@@ -20,27 +20,12 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-THREADS = 16
 GRID_CAP = 1 << 20
 
 
 @pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
-
-
-@pytest.fixture(scope="module")
 def c5(G):
-    env = G.BatchedGobblet(65536, DEV, auto_reset=True, seed=11, track_turn=True)
-    env.rollout(64)
-    torch.cuda.synchronize()
-    st, tm, turn = env.squares.cpu().numpy().copy(), env.to_move.cpu().numpy().copy(), env.turn.cpu().numpy().copy()
-    assert (oracle.batch_winner(st) == 0).all() and 0.3 < tm.mean() < 0.7
-    return st, tm, turn
+    return midgame_boards(turn=True)
 
 
 def host_collect(G, *args, **kw):

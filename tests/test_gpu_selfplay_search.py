@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
 from tests import selfplay_harness as H
+from tests.search_harness import G, midgame_boards  # noqa: F401  (G: the fixture)
 from tests.selfplay_harness import DEV, same
 from tests.test_selfplay_search import GRID, collect, restate_collect
 
@@ -20,30 +20,16 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-THREADS = 16
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
 
 
 @pytest.fixture(scope="module")
 def c5(G):
-    env = G.BatchedGobblet(65536, DEV, auto_reset=True, seed=11, track_turn=True)
-    env.rollout(64)
-    torch.cuda.synchronize()
-    st, tm, turn = env.squares.cpu().numpy().copy(), env.to_move.cpu().numpy().copy(), env.turn.cpu().numpy().copy()
-    assert (oracle.batch_winner(st) == 0).all() and 0.3 < tm.mean() < 0.7
-    return st, tm, turn
+    return midgame_boards(turn=True)
 
 
 # gbl_collect_search on the device (H.device_collect) under the argument order of tests.test_selfplay_search.collect
-device_collect = lambda G, st, tm, turn, T, pols, its, pls, M, X, *a: H.device_collect("search", st, tm, turn, T, pols, X, *a, its=its, pls=pls, M=M)  # noqa: E731
+device_collect = lambda G, st, tm, turn, T, pols, its, pls, M, X, *a, **kw: H.device_collect(  # noqa: E731
+    "search", st, tm, turn, T, pols, X, *a, its=its, pls=pls, M=M, **kw)
 
 
 @pytest.mark.parametrize("pols,its,pls,sample_plies,illegal_mode,ply_dev", GRID)

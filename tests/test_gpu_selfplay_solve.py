@@ -14,23 +14,14 @@ import torch
 from tests import evaluator_restatement as R
 from tests import solver_restatement as SR
 from tests import selfplay_harness as H
+from tests.search_harness import G, run  # noqa: F401  (G: the fixture)
 from tests.selfplay_harness import DEV, DeviceNet, _evaluator, same
 from tests.test_selfplay_solve import CASES, EXPLORE, T, WINDOW, collect_solve, fixture_boards, restated_six, six_boards, smoke_net
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-THREADS = 16
 GRID_CAP = 1 << 20
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
 
 
 @pytest.fixture(scope="module")
@@ -85,8 +76,8 @@ def test_512_iterations_beside_the_solver(G, c5, nets):
     """The LDS limit of the tree (36.9 KB) beside the solver's arrays: 3 boards, 2 plies, depth 2."""
     hn, dn = nets
     # boards whose first roots are unproven at depth 2, so that the 512 iterations run
-    out = SR.run(G._native.cpu_raw(), c5[0][:64], c5[1][:64], None, 2)
-    pick = np.flatnonzero(out[1] == 0)[:3]
+    out = run("solve", "cpu", c5[0][:64], c5[1][:64], None, (2,))
+    pick = np.flatnonzero(out["value"] == 0)[:3]
     st, tm, turn = c5[0][pick], c5[1][pick], c5[2][pick]
     args = (2, ("eval", "eval"), None, (512, 512), (2, 2), 64, 0, 0, "time", 1, 0, 0)
     got = device_collect(G, st, tm, turn, *args[:2], dn, *args[3:])

@@ -8,22 +8,10 @@ import pytest
 import torch
 
 from tests import solver_restatement as R
+from tests.search_harness import DEV, SOLVE_NAMES, Call, G, run, same  # noqa: F401  (G: the fixture)
 from tests.solver_restatement import DEEP, hand_built, sample
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-THREADS = 16
-JUNK8, JUNK32 = 0x5A, 0x5A5A5A5A
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
 
 
 @functools.lru_cache(maxsize=None)
@@ -45,69 +33,22 @@ def masks(n):
     return m
 
 
-class Buffers:
-    """Device inputs at odd addresses and outputs with guard bytes on both sides."""
-
-    def __init__(self, n, with_mask, stream=None):
-        self.n = n
-        self.st = torch.zeros(n * 27 + 3, dtype=torch.int8, device=DEV)
-        self.tm = torch.zeros(n + 1, dtype=torch.int8, device=DEV)
-        self.mk = torch.zeros(n * 54 + 1, dtype=torch.int8, device=DEV) if with_mask else None
-        self.out = torch.full((n * 54 + 14,), JUNK8, dtype=torch.int8, device=DEV)
-        self.val = torch.full((n + 14,), JUNK8, dtype=torch.int8, device=DEV)
-        self.act = torch.full((n + 8,), JUNK32, dtype=torch.int32, device=DEV)
-
-    def load(self, st, tm, mask=None):
-        self.st[3:].copy_(torch.from_numpy(st.reshape(-1)))
-        self.tm[1:].copy_(torch.from_numpy(tm))
-        if self.mk is not None:
-            self.mk[1:].copy_(torch.from_numpy(mask.reshape(-1)))
-        self.out.fill_(JUNK8)
-        self.val.fill_(JUNK8)
-        self.act.fill_(JUNK32)
-
-    def launch(self, G, depth, skip=None):
-        nat = G._native
-        ptrs = [self.out.data_ptr() + 7, self.val.data_ptr() + 7, self.act.data_ptr() + 16]
-        ptrs = [None if i == skip else p for i, p in enumerate(ptrs)]
-        nat.check(nat.lib().gbl_solve(self.st.data_ptr() + 3, self.tm.data_ptr() + 1, None if self.mk is None else self.mk.data_ptr() + 1,
-                                      depth, *ptrs, self.n, nat.current_stream(DEV)), "gbl_solve")
-
-    def results(self):
-        out, val, act = self.out.cpu().numpy(), self.val.cpu().numpy(), self.act.cpu().numpy()
-        assert (out[:7] == JUNK8).all() and (out[-7:] == JUNK8).all() and (val[:7] == JUNK8).all() and (val[-7:] == JUNK8).all()
-        assert (act[:4] == JUNK32).all() and (act[-4:] == JUNK32).all()
-        return out[7:-7].reshape(self.n, 54), val[7:-7], act[4:-4]
-
-
-def host(G, st, tm, mask, depth):
-    return R.run(G._native.cpu_raw(), st, tm, mask, depth)
-
-
 @pytest.mark.parametrize("with_mask", [False, True])
 @pytest.mark.parametrize("n", [1, 3, 65])
 def test_device_equals_host_flavour(G, n, with_mask):
     st, tm = (a[:n] for a in boards65())
     mask = masks(n) if with_mask else None
-    buf = Buffers(n, with_mask)
     for depth in (1, 2, 3, 4):
-        buf.load(st, tm, mask)
-        buf.launch(G, depth)
-        torch.cuda.synchronize()
-        R.same(buf.results(), host(G, st, tm, mask, depth))
+        same(run("solve", DEV, st, tm, mask, (depth,), misaligned=True), run("solve", "cpu", st, tm, mask, (depth,)))
 
 
 @pytest.mark.parametrize("depth", [5, 6])
 def test_deep_searches_of_late_positions(G, depth):
     pool = R.rollout_positions(120, seed=3)
     st, tm = (np.ascontiguousarray(a[np.array(DEEP)]) for a in pool)
-    buf = Buffers(3, False)
-    buf.load(st, tm)
-    buf.launch(G, depth)
-    torch.cuda.synchronize()
-    exp = host(G, st, tm, None, depth)
-    R.same(buf.results(), exp)
-    assert (np.abs(exp[1]) == depth).any() or depth == 5 and (exp[1] == 5).any()
+    exp = run("solve", "cpu", st, tm, None, (depth,))
+    same(run("solve", DEV, st, tm, None, (depth,), misaligned=True), exp)
+    assert (np.abs(exp["value"]) == depth).any() or depth == 5 and (exp["value"] == 5).any()
 
 
 def test_zugzwang_boards(G):
@@ -118,58 +59,53 @@ def test_zugzwang_boards(G):
     only = np.zeros((3, 54), np.int8)
     only[0, R.ZUG_ROOT_ACTION] = only[1, R.ZUG_WIN_IN_2] = only[1, R.ZUG_WIN_IN_3] = only[2, R.ZUG_DEEP_ACTIONS[0]] = 1
     for mask in (None, only):
-        buf = Buffers(3, mask is not None)
         for depth in (3, 4, 5, 6):
-            buf.load(st, tm, mask)
-            buf.launch(G, depth)
-            torch.cuda.synchronize()
-            exp = host(G, st, tm, mask, depth)
-            R.same(buf.results(), exp)
-    assert exp[0][0, R.ZUG_ROOT_ACTION] == -3 and exp[0][1, R.ZUG_WIN_IN_2] == 2 and exp[0][2, R.ZUG_DEEP_ACTIONS[0]] == 4
+            exp = run("solve", "cpu", st, tm, mask, (depth,))
+            same(run("solve", DEV, st, tm, mask, (depth,), misaligned=True), exp)
+    out = exp["outcome"]
+    assert out[0, R.ZUG_ROOT_ACTION] == -3 and out[1, R.ZUG_WIN_IN_2] == 2 and out[2, R.ZUG_DEEP_ACTIONS[0]] == 4
 
 
 def test_null_outputs_and_a_side_stream(G):
     st, tm = (a[:3] for a in boards65())
-    exp = host(G, st, tm, None, 3)
-    buf = Buffers(3, False)
+    exp = run("solve", "cpu", st, tm, None, (3,))
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        for skip in (0, 1, 2):
-            buf.load(st, tm)
-            buf.launch(G, 3, skip=skip)
+        for skip in SOLVE_NAMES:
+            call = Call("solve", DEV, keep=[k for k in SOLVE_NAMES if k != skip], misaligned=True).load(st, tm)
+            call.launch((3,))
             side.synchronize()
-            for i, (g, e) in enumerate(zip(buf.results(), exp)):
-                if i == skip:
-                    assert (g == (JUNK8 if i < 2 else JUNK32)).all()
-                else:
-                    assert np.array_equal(g, e)
+            got = call.results()
+            assert skip not in got and len(got) == 2
+            same(got, exp)
     torch.cuda.current_stream().wait_stream(side)
 
 
 def test_replay_from_a_captured_graph(G):
     st, tm = boards65()
     sets = [(st[:33], tm[:33]), (np.ascontiguousarray(st[32:]), np.ascontiguousarray(tm[32:]))]
-    buf = Buffers(33, False)
+    call = Call("solve", DEV, misaligned=True)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        buf.load(*sets[0])
-        buf.launch(G, 3)  # warm-up on the side stream
+        call.load(*sets[0])
+        call.launch((3,))  # warm-up on the side stream
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            buf.launch(G, 3)
+            call.launch((3,))
         for s, t in sets:
-            buf.load(s, t)  # in place: the captured launch holds these addresses
+            call.load(s, t)  # in place: the captured launch holds these addresses
             g.replay()
             side.synchronize()
-            R.same(buf.results(), host(G, s, t, None, 3))
+            same(call.results(), run("solve", "cpu", s, t, None, (3,)))
     torch.cuda.current_stream().wait_stream(side)
 
 
 def test_argument_errors(G):
     nat = G._native
     L = nat.lib()
+    solve = L.gbl_solve
     st, tm = (torch.from_numpy(a).to(DEV) for a in hand_built())
     out = torch.zeros((2, 54), dtype=torch.int8, device=DEV)
     val = torch.zeros(2, dtype=torch.int8, device=DEV)
@@ -177,7 +113,7 @@ def test_argument_errors(G):
     odd = act.data_ptr() + 1
 
     def call(state, to_move, depth, action, n):
-        rc = L.gbl_solve(state, to_move, None, depth, out.data_ptr(), val.data_ptr(), action, n, None)
+        rc = solve(state, to_move, None, depth, out.data_ptr(), val.data_ptr(), action, n, None)
         return rc, L.gbl_last_error().decode()
     assert call(None, None, 0, odd, -1) == (nat.ERR_ARG, "n < 0")
     assert call(None, None, 0, odd, 0) == (nat.ERR_ARG, "depth must be in [1, 6]")

@@ -13,7 +13,6 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 
 
 @pytest.mark.parametrize("depth", [4])
@@ -21,19 +20,15 @@ def test_solve_4096_boards_within_the_record(depth):
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     import bench_solver
-    from gobblet_rl_amd import _native as nat
+    from tests.search_harness import DEV, Call
     with open(os.path.join(ROOT, "profiles", "r14", "solver.json")) as f:
         rows = json.load(f)["timing_libgobblet_hip.so"]
     record = next(r["device"]["median_ms"] for r in rows if r["boards"] == 4096 and r["depth"] == depth)
     n = 4096
-    st, tm = bench_solver.states(n)
-    out = torch.empty((n, 54), dtype=torch.int8, device=DEV)
-    val = torch.empty(n, dtype=torch.int8, device=DEV)
-    act = torch.empty(n, dtype=torch.int32, device=DEV)
+    launch = Call("solve", DEV).load(*(t.cpu().numpy() for t in bench_solver.states(n))).launch
 
     def go():
-        nat.check(nat.lib().gbl_solve(st.data_ptr(), tm.data_ptr(), None, depth, out.data_ptr(), val.data_ptr(), act.data_ptr(), n,
-                                      nat.current_stream(DEV)), "gbl_solve")
+        launch((depth,))
     ms = bench_solver.timed(go, iters=3)["median_ms"]  # (one warm-up, three repetitions)
     print("gbl_solve 4096 boards depth %d: %.4f ms (record %.4f)" % (depth, ms, record))
     assert ms <= 1.15 * record, (ms, record)

@@ -11,22 +11,13 @@ import pytest
 import torch
 
 from tests import symmetry_restatement as R
+from tests.search_harness import G, replay_arg_errors  # noqa: F401  (G: the fixture)
 from tests.test_symmetry import random_rows
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 GUARD, JUNK = 64, 0x5A
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(16)
-    yield g
-    g._native.cpu_raw().gbl_cpu_set_threads(0)
 
 
 class Guarded:
@@ -158,13 +149,7 @@ def test_training_batch_edge_windows(G):
 
 
 def test_argument_errors_replay_the_recorded_table(G, golden_dir):
-    lib = G._native.lib()
-    table = json.load(open(os.path.join(golden_dir, "batch_arg_errors.json")))
-    for c in table:
-        rc, msg = c["device"]
-        assert getattr(lib, "gbl_" + c["fn"])(*c["args"]) == rc, (c["fn"], c["case"])
-        if rc:
-            assert lib.gbl_last_error().decode() == msg, (c["fn"], c["case"])
+    replay_arg_errors(json.load(open(os.path.join(golden_dir, "batch_arg_errors.json"))), flavours=("device",))
     torch.cuda.synchronize()
 
 

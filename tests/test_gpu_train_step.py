@@ -11,20 +11,11 @@ import torch
 from tests import train_restatement as R
 from tests.test_gpu_symmetry import DEV, GUARD, Guarded, dev
 from tests.test_train_step import SHAPES
+from tests.search_harness import G  # noqa: F401  (G: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(16)
-    yield g
-    g._native.cpu_raw().gbl_cpu_set_threads(0)
 
 
 def guarded(a):

@@ -9,52 +9,18 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
+from tests.search_harness import DEV, Call, G, midgame_boards, run, same  # noqa: F401  (G: the fixture)
 from tests.test_playout_policy import arena
-from tests.test_tree_policy import NAMES, restate, run
+from tests.test_tree_policy import restate
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-THREADS = 16
-
-
-@pytest.fixture(scope="module")
-def G():
-    import gobblet_rl_amd as g
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    g._native.lib()
-    g._native.cpu_raw().gbl_cpu_set_threads(THREADS)
-    return g
 
 
 @pytest.fixture(scope="module")
 def c5(G):
-    env = G.BatchedGobblet(65536, DEV, auto_reset=True, seed=11)
-    env.rollout(64)
-    torch.cuda.synchronize()
-    st, tm = env.squares.cpu().numpy().copy(), env.to_move.cpu().numpy().copy()
-    assert (oracle.batch_winner(st) == 0).all() and 0.3 < tm.mean() < 0.7
-    return st, tm
-
-
-def device_run(G, st, tm, mask, I, P, M, X, seed, env_base, call):
-    nat = G._native
-    n = len(st)
-    d_st, d_tm = torch.from_numpy(np.ascontiguousarray(st)).to(DEV), torch.from_numpy(np.ascontiguousarray(tm)).to(DEV)
-    d_mk = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask)).to(DEV)
-    out = [torch.full((n, 54), -7, dtype=torch.int32, device=DEV) for _ in range(3)]
-    out += [torch.full((n,), -7, dtype=torch.int32, device=DEV) for _ in range(3)]
-    nat.check(nat.lib().gbl_tree_search(d_st.data_ptr(), d_tm.data_ptr(), nat.ptr(d_mk), I, P, M, X, seed, env_base, call,
-                                        *[o.data_ptr() for o in out], n, nat.current_stream(DEV)), "gbl_tree_search")
-    torch.cuda.synchronize()
-    return tuple(o.cpu().numpy() for o in out)
-
-
-def same(got, exp):
-    for name, g, e in zip(NAMES, got, exp):
-        assert np.array_equal(g, e), (name, np.argwhere(g != e)[:5])
+    return midgame_boards()
 
 
 @pytest.mark.parametrize("I,P,M,X,call,env_base", [(64, 4, 30, 128, 5, (1 << 40) - 20), (40, 3, 255, 0, 0, 0), (30, 130, 6, 1024, 2, 11)])
@@ -66,7 +32,7 @@ def test_device_equals_restatement(G, c5, I, P, M, X, call, env_base):
     if P == 3:
         mask = (np.random.default_rng(1).random((len(st), 54)) < 0.5).astype(np.int8)
         mask[2] = 0  # a board without a candidate
-    same(device_run(G, st, tm, mask, I, P, M, X, 9, env_base, call), restate(st, tm, mask, I, P, M, X, 9, env_base, call))
+    same(run("tree_search", DEV, st, tm, mask, (I, P, M, X, 9, env_base, call)), restate(st, tm, mask, I, P, M, X, 9, env_base, call))
 
 
 # (iterations, playouts): 256 playouts run k_tree<4> up to 1 024 boards, <2> up to 2 048 and <1> beyond; 600 iterations are a
@@ -74,18 +40,16 @@ def test_device_equals_restatement(G, c5, I, P, M, X, call, env_base):
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 2000, 4096])
 def test_device_equals_host_flavour(G, c5, n):
     st, tm = c5[0][:n], c5[1][:n]
-    cpu = G._native.cpu_raw()
-    same(device_run(G, st, tm, None, 40, 256, 64, 128, 3, 17, 4), run(cpu, st, tm, None, 40, 256, 64, 128, 3, 17, 4))
+    same(run("tree_search", DEV, st, tm, None, (40, 256, 64, 128, 3, 17, 4)), run("tree_search", "cpu", st, tm, None, (40, 256, 64, 128, 3, 17, 4)))
     mask = (np.random.default_rng(n).random((n, 54)) < 0.3).astype(np.int8)
-    same(device_run(G, st, tm, mask, 600, 6, 64, 64, 3, 17, 4), run(cpu, st, tm, mask, 600, 6, 64, 64, 3, 17, 4))
+    same(run("tree_search", DEV, st, tm, mask, (600, 6, 64, 64, 3, 17, 4)), run("tree_search", "cpu", st, tm, mask, (600, 6, 64, 64, 3, 17, 4)))
     if n <= 65:  # the largest tree
-        same(device_run(G, st, tm, None, 1024, 2, 20, 256, 1, 0, 0), run(cpu, st, tm, None, 1024, 2, 20, 256, 1, 0, 0))
+        same(run("tree_search", DEV, st, tm, None, (1024, 2, 20, 256, 1, 0, 0)), run("tree_search", "cpu", st, tm, None, (1024, 2, 20, 256, 1, 0, 0)))
 
 
 def test_device_equals_host_flavour_config5_full_size(G, c5):
     st, tm = c5
-    cpu = G._native.cpu_raw()
-    same(device_run(G, st, tm, None, 48, 4, 64, 128, 0, 0, 0), run(cpu, st, tm, None, 48, 4, 64, 128, 0, 0, 0))
+    same(run("tree_search", DEV, st, tm, None, (48, 4, 64, 128, 0, 0, 0)), run("tree_search", "cpu", st, tm, None, (48, 4, 64, 128, 0, 0, 0)))
 
 
 def test_arena_device_equals_host_flavour(G):
@@ -102,15 +66,15 @@ def test_policy_on_device(G, c5):
     st, tm = torch.from_numpy(c5[0][:256]).to(DEV), torch.from_numpy(c5[1][:256]).to(DEV)
     pol = G.TreeSearchGobbletPolicy(iterations=100, playouts=8, seed=5, device=DEV)
     val = pol.action_values(st, tm)
-    exp = run(G._native.cpu_raw(), c5[0][:256], c5[1][:256], None, 100, 8, 64, pol.explore, 5, 0, 0)
+    exp = run("tree_search", "cpu", c5[0][:256], c5[1][:256], None, (100, 8, 64, pol.explore, 5, 0, 0))
     last = (pol.last_visits, pol.last_wins, pol.last_losses, pol.last_action, pol.last_nodes, pol.last_plies)
     assert all(t.device.type == "cuda" for t in last) and val.device.type == "cuda"
-    same([t.cpu().numpy() for t in last], exp)
-    assert int(torch.isfinite(val).sum()) == int((exp[0] > 0).sum())
+    same(exp, [t.cpu().numpy() for t in last])
+    assert int(torch.isfinite(val).sum()) == int((exp["visits"] > 0).sum())
     dist = pol.visit_distribution(st, tm)
-    exp1 = run(G._native.cpu_raw(), c5[0][:256], c5[1][:256], None, 100, 8, 64, pol.explore, 5, 0, 1)
-    assert dist.device.type == "cuda" and np.array_equal(pol.last_visits.cpu().numpy(), exp1[0])
-    assert np.allclose(dist.cpu().numpy(), exp1[0] / 100.0, rtol=1e-6, atol=0)  # (one float32 division: 2^-24 relative)
+    exp1 = run("tree_search", "cpu", c5[0][:256], c5[1][:256], None, (100, 8, 64, pol.explore, 5, 0, 1))
+    assert dist.device.type == "cuda" and np.array_equal(pol.last_visits.cpu().numpy(), exp1["visits"])
+    assert np.allclose(dist.cpu().numpy(), exp1["visits"] / 100.0, rtol=1e-6, atol=0)  # (one float32 division: 2^-24 relative)
 
 
 # ceilings: the committed record + 15 % (boxes differ by a few percent; HIP-event medians)
@@ -120,14 +84,10 @@ RECORD = os.path.join(ROOT, "profiles", "r08", "tree_policy.json")
 @pytest.mark.parametrize("n,I,P", [(4096, 256, 16), (65536, 64, 16), (65536, 256, 64)])
 def test_tree_perf_guard(G, c5, n, I, P):
     rec = {(r["boards"], r["iterations"], r["playouts"]): r for r in json.load(open(RECORD))["rows"]}[(n, I, P)]
-    nat = G._native
-    st, tm = torch.from_numpy(c5[0][:n]).to(DEV), torch.from_numpy(c5[1][:n]).to(DEV)
-    out = [torch.empty((n, 54), dtype=torch.int32, device=DEV) for _ in range(3)]
-    out += [torch.empty(n, dtype=torch.int32, device=DEV) for _ in range(3)]
+    launch = Call("tree_search", DEV).load(c5[0][:n], c5[1][:n]).launch
 
     def go(call):
-        nat.check(nat.lib().gbl_tree_search(st.data_ptr(), tm.data_ptr(), None, I, P, 64, rec["explore"], 0, 0, call,
-                                            *[o.data_ptr() for o in out], n, nat.current_stream(DEV)), "gbl_tree_search")
+        launch((I, P, 64, rec["explore"], 0, 0, call))
     go(0)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -11,6 +11,7 @@ import oracle
 
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
+from tests.search_harness import PLAYOUT_NAMES, run, same
 
 STREAM_PLAYOUT = 2
 E40 = (1 << 40) - 20
@@ -73,21 +74,6 @@ def restate(state, to_move, mask, K, M, seed, env_base, call):
     return wins, losses, action, plies
 
 
-def run(lib, state, to_move, mask, K, M, seed, env_base, call):
-    """gbl_playout_values on host arrays through `lib` (the host flavour's raw handle): (wins, losses, action, plies)."""
-    n = len(state)
-    wins = np.full((n, 54), -7, np.int32)
-    losses = np.full((n, 54), -7, np.int32)
-    action = np.full(n, -7, np.int32)
-    plies = np.full(n, -7, np.int32)
-    st, tm = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(to_move, np.int8)
-    mk = None if mask is None else np.ascontiguousarray(mask, np.int8)
-    rc = lib.gbl_cpu_playout_values(st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, K, M, seed, env_base,
-                                    call, wins.ctypes.data, losses.ctypes.data, action.ctypes.data, plies.ctypes.data, n, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    return wins, losses, action, plies
-
-
 def random_midgames(n, seed, min_plies=2, max_plies=14):
     """Masked-random games stopped at a random ply, on boards nobody has won yet (both movers)."""
     rng = np.random.default_rng(seed)
@@ -147,21 +133,17 @@ def test_host_flavour_equals_restatement(cpu, boards, K, M, call, env_base):
     st, tm = boards
     if K == 64:  # (the restatement walks every ply through ctypes: a third of the boards at the largest K)
         st, tm = st[::3], tm[::3]
-    got = run(cpu, st, tm, None, K, M, 9, env_base, call)
-    exp = restate(st, tm, None, K, M, 9, env_base, call)
-    for name, g, e in zip(("wins", "losses", "action", "plies"), got, exp):
-        assert np.array_equal(g, e), name
+    got = run("playout_values", "cpu", st, tm, None, (K, M, 9, env_base, call))
+    same(got, restate(st, tm, None, K, M, 9, env_base, call))
 
 
 def test_host_flavour_equals_restatement_with_mask(cpu, boards):
     st, tm = boards
     mask = (np.random.default_rng(2).random((len(st), 54)) < 0.4).astype(np.int8)
     mask[0] = 0  # a board without a candidate
-    got = run(cpu, st, tm, mask, 5, 40, 1, 3, 2)
-    exp = restate(st, tm, mask, 5, 40, 1, 3, 2)
-    for name, g, e in zip(("wins", "losses", "action", "plies"), got, exp):
-        assert np.array_equal(g, e), name
-    assert got[2][0] == -1 and got[3][0] == 0
+    got = run("playout_values", "cpu", st, tm, mask, (5, 40, 1, 3, 2))
+    same(got, restate(st, tm, mask, 5, 40, 1, 3, 2))
+    assert got["action"][0] == -1 and got["plies"][0] == 0
 
 
 @pytest.fixture(scope="module")
@@ -178,7 +160,7 @@ def test_properties(cpu, many):
     n, K = len(st), 16
     legal = oracle.batch_legal_mask(st, tm) != 0
     mask = (np.random.default_rng(8).random((n, 54)) < 0.5).astype(np.int8)
-    w, l, a, p = run(cpu, st, tm, mask, K, 64, 4, 100, 1)
+    w, l, a, p = run("playout_values", "cpu", st, tm, mask, (K, 64, 4, 100, 1)).values()
     cand = legal & (mask != 0)
     assert ((w + l) <= K).all() and (w >= 0).all() and (l >= 0).all()
     assert (w[~cand] == 0).all() and (l[~cand] == 0).all()
@@ -188,18 +170,18 @@ def test_properties(cpu, many):
     assert np.array_equal(a[has], np.argmax(score, 1)[has])  # (argmax: the first maximum, the lowest index)
     assert (p[has] >= cand.sum(1)[has] * K).all() and (p[has] <= cand.sum(1)[has] * K * 65).all()
     # more playouts: the first K are the same games
-    w2, l2, _, p2 = run(cpu, st, tm, mask, 2 * K, 64, 4, 100, 1)
+    w2, l2, _, p2 = run("playout_values", "cpu", st, tm, mask, (2 * K, 64, 4, 100, 1)).values()
     assert (w2 >= w).all() and (l2 >= l).all() and (p2 >= p).all()
     # sharding over env_base changes nothing
     h = n // 3
-    parts = [run(cpu, st[i:j], tm[i:j], mask[i:j], K, 64, 4, 100 + i, 1) for i, j in ((0, h), (h, n))]
-    for k in range(4):
-        assert np.array_equal(np.concatenate([q[k] for q in parts]), (w, l, a, p)[k])
+    parts = [run("playout_values", "cpu", st[i:j], tm[i:j], mask[i:j], (K, 64, 4, 100 + i, 1)) for i, j in ((0, h), (h, n))]
+    for k, whole in zip(PLAYOUT_NAMES, (w, l, a, p)):
+        assert np.array_equal(np.concatenate([q[k] for q in parts]), whole), k
     # M = 0: every playout of an action is its root move alone
-    w0, l0, _, p0 = run(cpu, st, tm, None, K, 0, 4, 100, 1)
+    w0, l0, _, p0 = run("playout_values", "cpu", st, tm, None, (K, 0, 4, 100, 1)).values()
     assert np.isin(w0, (0, K)).all() and np.isin(l0, (0, K)).all() and np.array_equal(p0, legal.sum(1) * K)
     # another call index plays other games
-    w5, l5, _, _ = run(cpu, st, tm, mask, K, 64, 4, 100, 5)
+    w5, l5, _, _ = run("playout_values", "cpu", st, tm, mask, (K, 64, 4, 100, 5)).values()
     assert not np.array_equal(w5, w)
 
 
@@ -208,7 +190,7 @@ def test_decided_root_moves(cpu):
     assert oracle.check_for_winner(oracle.play_turn(sw, mw, WIN_ACTION)) == 1
     assert oracle.check_for_winner(oracle.play_turn(su, mu, UNCOVER_ACTION)) == -1
     K = 50
-    w, l, a, _ = run(cpu, np.array([sw, su]), np.array([mw, mu]), None, K, 64, 0, 0, 0)
+    w, l, a, _ = run("playout_values", "cpu", np.array([sw, su]), np.array([mw, mu]), None, (K, 64, 0, 0, 0)).values()
     assert w[0, WIN_ACTION] == K and l[0, WIN_ACTION] == 0 and a[0] == WIN_ACTION
     assert l[1, UNCOVER_ACTION] == K and w[1, UNCOVER_ACTION] == 0 and a[1] != UNCOVER_ACTION
 
@@ -282,7 +264,7 @@ def test_policy_surface_on_cpu(cpu, many):
     assert a.dtype == torch.int32 and torch.equal(a, b)
     pol = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu")
     v = pol.action_values(st, tm)
-    exp_w, exp_l, exp_a, exp_p = run(nat.cpu_raw(), st.numpy(), tm.numpy(), None, 8, 64, 3, 0, 0)
+    exp_w, exp_l, exp_a, exp_p = run("playout_values", "cpu", st.numpy(), tm.numpy(), None, (8, 64, 3, 0, 0)).values()
     assert torch.equal(pol.last_action, b) and np.array_equal(pol.last_wins.numpy(), exp_w)
     assert np.array_equal(pol.last_losses.numpy(), exp_l) and np.array_equal(pol.last_plies.numpy(), exp_p)
     legal = mask.numpy() != 0
@@ -291,7 +273,7 @@ def test_policy_surface_on_cpu(cpu, many):
     assert pol._calls == 1
     pol.compute_actions_from_state(st, tm)
     assert pol._calls == 2
-    w1, _, _, _ = run(nat.cpu_raw(), st.numpy(), tm.numpy(), None, 8, 64, 3, 0, 1)
+    w1, _, _, _ = run("playout_values", "cpu", st.numpy(), tm.numpy(), None, (8, 64, 3, 0, 1)).values()
     assert np.array_equal(pol.last_wins.numpy(), w1)
     # single-observation and rllib / tianshou shapes
     one = G.MonteCarloGobbletPolicy(playouts=8, seed=3, device="cpu")

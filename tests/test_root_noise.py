@@ -16,7 +16,9 @@ from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import noise_restatement as N
 from tests import solver_restatement as SR
-from tests.selfplay_harness import _evaluator, replay_arg_errors, same
+from tests.search_harness import SEARCH_NAMES, replay_arg_errors, run
+from tests.search_harness import same as same_arrays
+from tests.selfplay_harness import _evaluator, same
 from tests.test_playout_policy import random_midgames
 from tests.test_selfplay_solve import EXPLORE, collect_solve, fixture_boards, smoke_net
 
@@ -57,7 +59,7 @@ def test_noise_row_equals_restatement(cpu, size):
     mask = row_masks(size, n, np.random.default_rng(size))
     for i, q in enumerate(ROW_CALLS):
         base = ENV_BASE if i & 1 else i * 1000
-        nu = N.run_search_noise(cpu, net, st, tm, mask, 1, 0, 256, SEED, base, q)[7]  # (w = 256: pi' is nu itself)
+        nu = run("tree_search_eval_noise", "cpu", st, tm, mask, (1, 0, 256, SEED, base, q), net)["root_mixed"]  # (w = 256: pi' is nu itself)
         exp = np.stack([N.noise_row(SEED, base + b, q, mask[b] != 0) for b in range(n)])
         assert np.array_equal(nu, exp), (size, q)
         total = nu.astype(np.int64).sum(1)
@@ -73,15 +75,15 @@ def test_mix_equals_restatement(cpu, midgames, w):
     st, tm = midgames
     for hidden in (64, 256):
         net = R.random_net(hidden, 5 + hidden)
-        got = N.run_search_noise(cpu, net, st, tm, None, 1, EXPLORE, w, SEED, ENV_BASE, 9)
+        got = run("tree_search_eval_noise", "cpu", st, tm, None, (1, EXPLORE, w, SEED, ENV_BASE, 9), net)
         pi = R.restate_evaluate(net, st, tm)[0]
-        assert np.array_equal(got[6], pi)  # root_priors_out stays the network's row
+        assert np.array_equal(got["root_priors"], pi)  # root_priors_out stays the network's row
         for b in range(len(st)):
             cand = oracle.legal_mask(st[b], int(tm[b])) != 0
             nu = N.noise_row(SEED, ENV_BASE + b, 9, cand)
-            assert np.array_equal(got[7][b], N.mix(pi[b], nu, w, cand)), (w, b)
+            assert np.array_equal(got["root_mixed"][b], N.mix(pi[b], nu, w, cand)), (w, b)
             if w == 256:
-                assert np.array_equal(got[7][b], nu)
+                assert np.array_equal(got["root_mixed"][b], nu)
 
 
 def test_mix_stays_a_prior_byte():
@@ -103,10 +105,10 @@ def test_search_equals_restatement(cpu, midgames, hidden, iterations):
     mask[1] = 0
     mask[1, np.flatnonzero(legal[1])[3]] = 1  # one candidate
     for w, msk in ((64, None), (256, None), (128, mask)):
-        args = (net, st, tm, msk, iterations, EXPLORE, w, SEED, ENV_BASE, 5)
-        got = N.run_search_noise(cpu, *args)
-        R.same(got, N.restate_search_noise(*args), N.NOISE_SEARCH_NAMES)
-    v, w_, l, a, nd, rv, rp, rm = got
+        params = (iterations, EXPLORE, w, SEED, ENV_BASE, 5)
+        got = run("tree_search_eval_noise", "cpu", st, tm, msk, params, net)
+        same_arrays(got, N.restate_search_noise(net, st, tm, msk, *params))
+    v, w_, l, a, nd, rv, rp, rm = got.values()
     assert a[0] == -1 and nd[0] == 1 and not v[0].any() and not rp[0].any() and not rm[0].any()
     assert v[1].sum() == iterations and rp[1].max() == 255 and rm[1].max() == 255 and (rm[1] > 0).sum() == 1
 
@@ -115,32 +117,34 @@ def test_identities(cpu):
     st, tm, _ = fixture_boards(40)
     net = smoke_net()
     I = 24
-    plain = R.run_search(cpu, net, st, tm, None, I, EXPLORE)
+    plain = run("tree_search_eval", "cpu", st, tm, None, (I, EXPLORE), net)
     # w = 0 is gbl_cpu_tree_search_eval on every shared output, and root_mixed_out is the network's row
-    got = N.run_search_noise(cpu, net, st, tm, None, I, EXPLORE, 0, SEED, ENV_BASE, 3)
-    R.same(got[:7], plain, R.SEARCH_NAMES)
-    assert np.array_equal(got[7], plain[6])
+    got = run("tree_search_eval_noise", "cpu", st, tm, None, (I, EXPLORE, 0, SEED, ENV_BASE, 3), net)
+    same_arrays(plain, got)
+    assert np.array_equal(got["root_mixed"], plain["root_priors"])
     # explore = 0: the prior never enters the key, so only root_mixed_out differs
-    flat = R.run_search(cpu, net, st, tm, None, I, 0)
-    got0 = N.run_search_noise(cpu, net, st, tm, None, I, 0, 200, SEED, ENV_BASE, 3)
-    R.same(got0[:7], flat, R.SEARCH_NAMES)
-    assert not np.array_equal(got0[7], flat[6])
+    flat = run("tree_search_eval", "cpu", st, tm, None, (I, 0), net)
+    got0 = run("tree_search_eval_noise", "cpu", st, tm, None, (I, 0, 200, SEED, ENV_BASE, 3), net)
+    same_arrays(flat, got0)
+    assert not np.array_equal(got0["root_mixed"], flat["root_priors"])
     # the noise changes what the search looks at
-    noisy = N.run_search_noise(cpu, net, st, tm, None, I, EXPLORE, 128, SEED, ENV_BASE, 3)
-    assert np.array_equal(noisy[6], plain[6]) and np.array_equal(noisy[5], plain[5]) and not np.array_equal(noisy[0], plain[0])
+    noisy = run("tree_search_eval_noise", "cpu", st, tm, None, (I, EXPLORE, 128, SEED, ENV_BASE, 3), net)
+    assert np.array_equal(noisy["root_priors"], plain["root_priors"]) and np.array_equal(noisy["root_value"], plain["root_value"])
+    assert not np.array_equal(noisy["visits"], plain["visits"])
     # NULL for root_mixed_out (and every output is optional, as in gbl_tree_search_eval)
-    R.same(N.run_search_noise(cpu, net, st, tm, None, I, EXPLORE, 128, SEED, ENV_BASE, 3, mixed=False)[:7], noisy[:7], R.SEARCH_NAMES)
+    same_arrays(run("tree_search_eval_noise", "cpu", st, tm, None, (I, EXPLORE, 128, SEED, ENV_BASE, 3), net, keep=SEARCH_NAMES), noisy)
     # a board alone is the board in the batch; board k + b of a batch at env_base 0 is board b of the shard at env_base k
     for b in (0, 7, 39):
-        alone = N.run_search_noise(cpu, net, st[b:b + 1], tm[b:b + 1], None, I, EXPLORE, 128, SEED, ENV_BASE + b, 3)
-        R.same(alone, [x[b:b + 1] for x in noisy], N.NOISE_SEARCH_NAMES)
-    whole = N.run_search_noise(cpu, net, st, tm, None, I, EXPLORE, 128, SEED, 0, 3)
-    shard = N.run_search_noise(cpu, net, st[16:], tm[16:], None, I, EXPLORE, 128, SEED, 16, 3)
-    R.same(shard, [x[16:] for x in whole], N.NOISE_SEARCH_NAMES)
+        alone = run("tree_search_eval_noise", "cpu", st[b:b + 1], tm[b:b + 1], None, (I, EXPLORE, 128, SEED, ENV_BASE + b, 3), net)
+        same_arrays(alone, {k: x[b:b + 1] for k, x in noisy.items()})
+    whole = run("tree_search_eval_noise", "cpu", st, tm, None, (I, EXPLORE, 128, SEED, 0, 3), net)
+    shard = run("tree_search_eval_noise", "cpu", st[16:], tm[16:], None, (I, EXPLORE, 128, SEED, 16, 3), net)
+    same_arrays(shard, {k: x[16:] for k, x in whole.items()})
     # the call index and the seed both move the row
-    other = N.run_search_noise(cpu, net, st, tm, None, I, EXPLORE, 128, SEED, ENV_BASE, 4)
-    assert not np.array_equal(other[7], noisy[7])
-    assert not np.array_equal(N.run_search_noise(cpu, net, st, tm, None, I, EXPLORE, 128, SEED + 1, ENV_BASE, 3)[7], noisy[7])
+    other = run("tree_search_eval_noise", "cpu", st, tm, None, (I, EXPLORE, 128, SEED, ENV_BASE, 4), net)
+    assert not np.array_equal(other["root_mixed"], noisy["root_mixed"])
+    other = run("tree_search_eval_noise", "cpu", st, tm, None, (I, EXPLORE, 128, SEED + 1, ENV_BASE, 3), net)
+    assert not np.array_equal(other["root_mixed"], noisy["root_mixed"])
 
 
 # ---- self-play ----------------------------------------------------------------------------------------------------------------------------
@@ -165,15 +169,15 @@ def composed_loop(cpu, st, tm, turn, T, nets, its, deps, noise, X, sample_plies,
             mv = int(m[b])
             mask = None
             if deps[mv] > 0:
-                o, V, a_star = SR.run(cpu, s[b:b + 1], m[b:b + 1], None, deps[mv])
+                o, V, a_star = run("solve", "cpu", s[b:b + 1], m[b:b + 1], None, (deps[mv],)).values()
                 outcome[b], proven[b] = o[0], V[0]
                 if V[0] != 0:
                     act[b], how[b], vis[b, a_star[0]] = a_star[0], nat.HOW_PROVEN, its[mv]
                     val[b] = (1 if V[0] > 0 else -1) * 128 * its[mv]
                     continue
                 mask = (o == 0).astype(np.int8)
-            v, w, l, a, nd, rq, rp, _ = N.run_search_noise(cpu, nets[mv], s[b:b + 1], m[b:b + 1], mask, its[mv], X, noise[mv], seed,
-                                                           env_base + b, q)
+            v, w, l, a, nd, rq, rp, _ = run("tree_search_eval_noise", "cpu", s[b:b + 1], m[b:b + 1], mask,
+                                            (its[mv], X, noise[mv], seed, env_base + b, q), nets[mv]).values()
             vis[b], val[b], nod[b], rv[b], pri[b] = v[0], (w[0] - l[0]).sum(), nd[0], rq[0], rp[0]
             if tn[b] < sample_plies:
                 act[b], how[b] = visits_draw(v[0], N.word(seed, env_base + b, q, STREAM_VISIT)), nat.HOW_SEARCH_SAMPLED
@@ -283,9 +287,9 @@ def test_policy_noise(cpu):
     pol._lib = Counting(pol._lib)
     for call in range(2):  # `call` counts up once per compute_actions_from_state
         a = pol.compute_actions_from_state(torch.from_numpy(st), torch.from_numpy(tm)).numpy()
-        exp = N.run_search_noise(cpu, net, st, tm, None, 16, EXPLORE, 64, 5, 100, call)
-        assert np.array_equal(a, exp[3]) and np.array_equal(pol.last_visits.numpy(), exp[0])
-        assert np.array_equal(pol.last_root_priors.numpy(), exp[6]) and np.array_equal(pol.last_root_mixed.numpy(), exp[7])
+        exp = run("tree_search_eval_noise", "cpu", st, tm, None, (16, EXPLORE, 64, 5, 100, call), net)
+        assert np.array_equal(a, exp["action"]) and np.array_equal(pol.last_visits.numpy(), exp["visits"])
+        assert np.array_equal(pol.last_root_priors.numpy(), exp["root_priors"]) and np.array_equal(pol.last_root_mixed.numpy(), exp["root_mixed"])
         assert pol.call == call + 1
         # G.root_noise rebuilds the row the root kept from the network's row
         nu = G.root_noise(5, 100 + np.arange(30), call, oracle.batch_legal_mask(st, tm))
@@ -298,7 +302,8 @@ def test_policy_noise(cpu):
     quiet._lib = Counting(quiet._lib)
     a = quiet.compute_actions_from_state(torch.from_numpy(st), torch.from_numpy(tm)).numpy()
     assert quiet._lib.calls == {"gbl_tree_search_eval": 1} and quiet.call == 0
-    assert np.array_equal(a, R.run_search(cpu, net, st, tm, None, 16, EXPLORE)[3]) and quiet.last_root_mixed is quiet.last_root_priors
+    assert np.array_equal(a, run("tree_search_eval", "cpu", st, tm, None, (16, EXPLORE), net)["action"])
+    assert quiet.last_root_mixed is quiet.last_root_priors
     for bad in (-0.1, 1.5):
         with pytest.raises(ValueError):
             G.EvaluatorTreeSearchGobbletPolicy(ev, noise=bad)
@@ -311,7 +316,7 @@ def test_root_noise_equals_root_mixed_out(cpu):
     mask = (np.random.default_rng(2).random((n, 54)) < 0.3).astype(np.int8)
     mask[3] = 0
     for seed, base, q in ((SEED, ENV_BASE, (1 << 24) - 1), (1, 0, 0), (2 ** 64 - 1, (1 << 42) - n, 77)):
-        exp = N.run_search_noise(cpu, R.zero_net(64), st, tm, mask, 1, 0, 256, seed, base, q)[7]
+        exp = run("tree_search_eval_noise", "cpu", st, tm, mask, (1, 0, 256, seed, base, q), R.zero_net(64))["root_mixed"]
         got = G.root_noise(seed, base + np.arange(n), q, torch.from_numpy(mask))
         assert np.array_equal(got.numpy(), exp)
     per_board = G.root_noise(1, np.arange(n), np.arange(n) % 5, mask)  # a ply per board

@@ -10,10 +10,11 @@ import pytest
 import oracle
 
 from gobblet_rl_amd import _native as nat
+from tests.search_harness import replay_arg_errors, run, same
 from tests.test_playout_policy import UNCOVER_ACTION, UNCOVER_SEQ, WIN_ACTION, WIN_SEQ, play
 from tests.test_selfplay_search import collect, restate_collect
 from tests.test_selfplay_search import same as same_collect
-from tests.test_tree_policy import restate, run, same
+from tests.test_tree_policy import restate
 
 I_MAX, P_MAX, M_MAX = 1024, 256, 255
 FULL = I_MAX * P_MAX  # 2^18: every game of every iteration
@@ -53,7 +54,7 @@ def check_saturated_tree(got, explore, playouts=P_MAX):
     """The outputs of a (1024, playouts, 255, explore) search of saturated_boards(): the restatement's, and the counts that follow
     from the rule text alone."""
     same(got, saturated_tree_expectation(explore, playouts))
-    v, w, l, a, nd, p = got
+    v, w, l, a, nd, p = got.values()
     full = I_MAX * playouts
     other = saturated_boards()[3]
     assert v[0, WIN_ACTION] == I_MAX and w[0, WIN_ACTION] == full and l[0, WIN_ACTION] == 0 and a[0] == WIN_ACTION and nd[0] == 2 and p[0] == 0
@@ -76,7 +77,7 @@ def cpu():
 def test_tree_host_flavour_equals_restatement_at_the_largest_budget(cpu, explore):
     st, tm, mask, _ = saturated_boards()
     assert FULL == 1 << 18
-    check_saturated_tree(run(cpu, st, tm, mask, I_MAX, P_MAX, M_MAX, explore, SEED, ENV_BASE, CALL), explore)
+    check_saturated_tree(run("tree_search", "cpu", st, tm, mask, (I_MAX, P_MAX, M_MAX, explore, SEED, ENV_BASE, CALL)), explore)
 
 
 # gbl_collect_search takes no root mask, so its searches of these positions see every legal move, and a restatement of 1024 x 256
@@ -149,12 +150,12 @@ def test_nonzero_bytes_are_set_bytes(cpu):
     from tests import test_playout_policy as PP
     st, tm, mask, tm2, mask2 = byte_value_boards()
     exp = restate(st, tm, mask, *TREE_BYTES)
-    same(restate(st, tm2, mask2, *TREE_BYTES), exp)
-    same(run(cpu, st, tm, mask, *TREE_BYTES), exp)
-    same(run(cpu, st, tm2, mask2, *TREE_BYTES), exp)
-    exp = PP.restate(st, tm, mask, *PLAYOUT_BYTES)
-    for got in (PP.restate(st, tm2, mask2, *PLAYOUT_BYTES), PP.run(cpu, st, tm, mask, *PLAYOUT_BYTES), PP.run(cpu, st, tm2, mask2, *PLAYOUT_BYTES)):
-        assert all(np.array_equal(g, e) for g, e in zip(got, exp))
+    for entry, exp, twin in (("tree_search", exp, restate(st, tm2, mask2, *TREE_BYTES)),
+                             ("playout_values", PP.restate(st, tm, mask, *PLAYOUT_BYTES), PP.restate(st, tm2, mask2, *PLAYOUT_BYTES))):
+        params = TREE_BYTES if entry == "tree_search" else PLAYOUT_BYTES
+        for got in (run(entry, "cpu", st, tm, mask, params), run(entry, "cpu", st, tm2, mask2, params)):
+            same(got, exp)
+            same(got, twin)
 
 
 # ---- the header's word on alignment ----------------------------------------------------------------------------------------------
@@ -176,14 +177,6 @@ def test_argument_errors_replay_the_recorded_table(golden_dir):
     flavours shared their checks.  Every call returns before any device work (the pointers are numbers, never read); a case whose
     "host" is null is an alignment rule, which only the device flavour has."""
     import json
-    flavours = (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_"))
     table = json.load(open(os.path.join(golden_dir, "search_arg_errors.json")))
     assert len(table) > 120 and {c["fn"] for c in table} == {"playout_values", "tree_search", "collect_search", "outcome_targets"}
-    for c in table:
-        for flavour, lib, prefix in flavours:
-            if c[flavour] is None:
-                continue
-            rc, msg = c[flavour]
-            assert getattr(lib, prefix + c["fn"])(*c["args"]) == rc, (flavour, c["fn"], c["case"])
-            if rc:
-                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])
+    replay_arg_errors(table)

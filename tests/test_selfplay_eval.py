@@ -25,6 +25,7 @@ import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests.positions import terminal_roots
+from tests.search_harness import run
 from tests.selfplay_harness import EVAL_NAMES as NAMES, _evaluator, host_collect, same
 from tests.test_playout_policy import WIN_SEQ, UNCOVER_SEQ, play, random_midgames, sample_stream
 from tests.test_selfplay_search import STREAM_VISIT, targets_numpy, visits_draw, word
@@ -156,7 +157,7 @@ def test_host_flavour_equals_composition(cpu, many, nets):
         for side in (0, 1):
             idx = np.flatnonzero(m == side)
             if len(idx):
-                v, w, l, a, nd, q, p = R.run_search(cpu, nets[side], s[idx], m[idx], None, its[side], X)
+                v, w, l, a, nd, q, p = run("tree_search_eval", "cpu", s[idx], m[idx], None, (its[side], X), nets[side]).values()
                 act[idx], vis[idx], val[idx], nod[idx], rv[idx], pri[idx] = a, v, (w - l).sum(1), nd, q, p
         win, rew = np.zeros(n, np.int8), np.zeros((n, 2), np.int8)
         mask, obs = np.zeros((n, 54), np.int8), np.zeros((n, 117), np.int8)

@@ -10,7 +10,8 @@ import oracle
 
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
-from tests.selfplay_harness import CODES, SCALARS, cells, host_collect, replay_arg_errors, same, strides  # noqa: F401  (re-exported)
+from tests.search_harness import replay_arg_errors, run
+from tests.selfplay_harness import CODES, SCALARS, cells, host_collect, same, strides  # noqa: F401  (re-exported)
 from tests.test_playout_policy import random_midgames, sample_stream
 from tests.test_tree_policy import restate
 
@@ -31,10 +32,10 @@ def visits_draw(visits, r):
     return int(over[0]) if len(over) else -1
 
 
-def collect(lib, st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None):
+def collect(lib, st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None):
     """gbl_cpu_collect_search on host arrays through `lib`; returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
     return host_collect("search", lib.gbl_cpu_collect_search, lib.gbl_cpu_last_error, st, tm, turn, T, pols, X, sample_plies, illegal_mode,
-                        layout, seed, env_base, ply0, ply_dev, its=its, pls=pls, M=M)
+                        layout, seed, env_base, ply0, ply_dev, keep, its=its, pls=pls, M=M)
 
 
 def restate_collect(st, tm, turn, T, pols, its, pls, M, X, sample_plies, illegal_mode, seed, env_base, ply0):
@@ -146,7 +147,7 @@ def test_properties(cpu, many):
     # ply 0 of (tree, tree) IS gbl_tree_search(call = ply0) on the entry position, decision included
     from tests.test_tree_policy import run
     tr, *_ = collect(cpu, st, tm, turn, 1, ("tree", "tree"), (24, 24), (4, 4), 40, 64, 0, nat.ILLEGAL_NOOP, "time", 3, 100, 6)
-    v, w, l, a, nd, _ = run(cpu, st, tm, None, 24, 4, 40, 64, 3, 100, 6)
+    v, w, l, a, nd, _ = run("tree_search", "cpu", st, tm, None, (24, 4, 40, 64, 3, 100, 6)).values()
     assert np.array_equal(tr["visits"][0], v) and np.array_equal(tr["actions"][0], a) and np.array_equal(tr["nodes"][0], nd)
     assert np.array_equal(tr["value"][0], (w - l).sum(1))
     # arg-max of the visits under tree_final_key's order wherever the search decided

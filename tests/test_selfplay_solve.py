@@ -20,6 +20,7 @@ import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import solver_restatement as SR
+from tests.search_harness import midgame_boards, run
 from tests.selfplay_harness import SOLVE_NAMES as NAMES, host_collect, same
 from tests.test_playout_policy import sample_stream
 from tests.test_selfplay_eval import collect_eval
@@ -36,11 +37,7 @@ def smoke_net():
 
 
 def fixture_boards(n, device="cpu"):
-    env = G.BatchedGobblet(n, device, auto_reset=True, seed=11, track_turn=True)
-    env.rollout(64)
-    st, tm, turn = env.squares.cpu().numpy().copy(), env.to_move.cpu().numpy().copy(), env.turn.cpu().numpy().copy()
-    assert (oracle.batch_winner(st) == 0).all()
-    return st, tm, turn
+    return midgame_boards(n, device, turn=True)
 
 
 def six_boards(c5):
@@ -167,7 +164,7 @@ def composed_loop(cpu, net, st, tm, turn, T_, its, depth, X):
     s, m, d, tn = st.copy(), tm.copy(), np.zeros(n, np.int8), turn.copy()
     plies, tally = [], np.zeros(3, np.int64)
     for _ in range(T_):
-        outcome, V, a_star = SR.run(cpu, s, m, None, depth)
+        outcome, V, a_star = run("solve", "cpu", s, m, None, (depth,)).values()
         act, vis, val, nod = a_star.copy(), np.zeros((n, 54), np.int16), np.zeros(n, np.int32), np.zeros(n, np.int32)
         rv, pri, how = np.zeros(n, np.int32), np.zeros((n, 54), np.uint8), np.full(n, nat.HOW_PROVEN, np.int8)
         won, lost = V > 0, V < 0
@@ -177,7 +174,7 @@ def composed_loop(cpu, net, st, tm, turn, T_, its, depth, X):
         if len(idx):
             C_ = (outcome[idx] == 0).astype(np.int8)
             assert C_.any(1).all()
-            v, w, l, a, nd, q, p = R.run_search(cpu, net, s[idx], m[idx], C_, its, X)
+            v, w, l, a, nd, q, p = run("tree_search_eval", "cpu", s[idx], m[idx], C_, (its, X), net).values()
             act[idx], vis[idx], val[idx], nod[idx], rv[idx], pri[idx], how[idx] = a, v, (w - l).sum(1), nd, q, p, nat.HOW_SEARCH
         tally += (won.sum(), lost.sum(), len(idx))
         win, rew = np.zeros(n, np.int8), np.zeros((n, 2), np.int8)
@@ -236,7 +233,7 @@ def guard_property(cpu, tr, st, tm, deps):
             idx = np.flatnonzero((m != 0) == bool(side))
             if not deps[side] or not len(idx):
                 continue
-            outcome = SR.run(cpu, s[idx], m[idx], None, deps[side])[0].astype(np.int64)
+            outcome = run("solve", "cpu", s[idx], m[idx], None, (deps[side],))["outcome"].astype(np.int64)
             a = tr["actions"][t][idx]
             played = outcome[np.arange(len(idx)), a]
             assert (played != SR.NONE).all()

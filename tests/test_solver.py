@@ -12,6 +12,7 @@ import oracle
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import solver_restatement as R
+from tests.search_harness import run, same
 from tests.solver_restatement import DEEP, UNCOVER_ACTION, WIN_ACTION, hand_built, late, sample
 
 NONE = R.NONE
@@ -45,22 +46,22 @@ def cpu():
 @pytest.mark.parametrize("depth", [1, 2])
 def test_host_flavour_equals_restatement(cpu, depth):
     st, tm = sample()
-    R.same(R.run(cpu, st, tm, None, depth), expected("sample", depth))
+    same(run("solve", "cpu", st, tm, None, (depth,)), expected("sample", depth))
 
 
 def test_host_flavour_equals_restatement_depth_3(cpu):
     st, tm = sample()
-    R.same(R.run(cpu, st[d3_rows()], tm[d3_rows()], None, 3), expected("d3", 3))
+    same(run("solve", "cpu", st[d3_rows()], tm[d3_rows()], None, (3,)), expected("d3", 3))
 
 
 def test_host_flavour_equals_restatement_on_late_positions(cpu):
     st, tm = late()
-    R.same(R.run(cpu, st, tm, None, 4), expected("late", 4))
+    same(run("solve", "cpu", st, tm, None, (4,)), expected("late", 4))
 
 
 def test_host_flavour_equals_restatement_at_depth_5(cpu):
     st, tm = late(DEEP[:1])
-    R.same(R.run(cpu, st, tm, None, 5), expected("deep", 5))
+    same(run("solve", "cpu", st, tm, None, (5,)), expected("deep", 5))
 
 
 def test_the_sample_reaches_every_kind_of_result():
@@ -90,14 +91,14 @@ def test_a_win_in_two_by_zugzwang_beside_a_win_in_three(cpu):
     assert node[1][0] == 2 and node[2][0] == R.ZUG_WIN_IN_2
     for depth in (3, 4):
         exp = R.solve(st, tm, None, depth)
-        R.same(R.run(cpu, st, tm, None, depth), exp)
+        same(run("solve", "cpu", st, tm, None, (depth,)), exp)
     assert exp[0][0, R.ZUG_ROOT_ACTION] == -3  # (depth 4) player_2 answers with the win in 2, not the win in 3
     only = np.zeros((1, 54), np.int8)          # depth 5 in pure Python: the one root action that leads to the node
     only[0, R.ZUG_DEEP_ACTIONS[0]] = 1
     exp = R.solve(st[2:], tm[2:], only, 5)
     assert exp[0][0, R.ZUG_DEEP_ACTIONS[0]] == 4 and exp[1][0] == 4
-    R.same(R.run(cpu, st[2:], tm[2:], only, 5), exp)
-    R.same(R.run(cpu, st[:1], tm[:1], None, 5), R.solve(st[:1], tm[:1], None, 5))
+    same(run("solve", "cpu", st[2:], tm[2:], only, (5,)), exp)
+    same(run("solve", "cpu", st[:1], tm[:1], None, (5,)), R.solve(st[:1], tm[:1], None, 5))
 
 
 def test_a_mask_changes_the_best_move(cpu):
@@ -109,8 +110,8 @@ def test_a_mask_changes_the_best_move(cpu):
     held = R.solve(st, tm, mask, 3)
     assert free[1][0] == 1 and free[2][0] != held[2][0] and held[2][0] >= 0 and held[1][0] != 1
     assert (held[0][free[0] == 1] == NONE).all()
-    R.same(R.run(cpu, st, tm, mask, 3), held)
-    R.same(R.run(cpu, st, tm, None, 3), free)
+    same(run("solve", "cpu", st, tm, mask, (3,)), held)
+    same(run("solve", "cpu", st, tm, None, (3,)), free)
 
 
 def test_masks_on_the_sample(cpu):
@@ -118,7 +119,7 @@ def test_masks_on_the_sample(cpu):
     mask = (np.random.default_rng(2).random((len(st), 54)) < 0.5).astype(np.int8) * np.int8(-3)  # (set = non-zero)
     mask[3] = 0
     for depth in (1, 2):
-        R.same(R.run(cpu, st, tm, mask, depth), R.solve(st, tm, mask, depth))
+        same(run("solve", "cpu", st, tm, mask, (depth,)), R.solve(st, tm, mask, depth))
 
 
 @functools.lru_cache(maxsize=None)
@@ -129,12 +130,12 @@ def property_positions():
 @pytest.fixture(scope="module")
 def by_depth(cpu):
     st, tm = property_positions()
-    return {d: R.run(cpu, st, tm, None, d) for d in (1, 2, 3, 4)}
+    return {d: run("solve", "cpu", st, tm, None, (d,)) for d in (1, 2, 3, 4)}
 
 
 def test_a_proven_result_stays_at_the_next_depth(by_depth):
     for d in (1, 2, 3):
-        lo, hi = by_depth[d][0], by_depth[d + 1][0]
+        lo, hi = by_depth[d]["outcome"], by_depth[d + 1]["outcome"]
         proven = (lo != 0) & (lo != NONE)
         assert proven.any() and np.array_equal(lo[proven], hi[proven])
         assert np.array_equal(lo == NONE, hi == NONE)
@@ -144,7 +145,8 @@ def test_a_proven_result_stays_at_the_next_depth(by_depth):
 def test_value_is_the_outcome_at_the_action_and_non_candidates_are_none(by_depth):
     st, tm = property_positions()
     legal = oracle.batch_legal_mask(np.ascontiguousarray(st), np.ascontiguousarray(tm)) != 0
-    for d, (out, val, act) in by_depth.items():
+    for d, got in by_depth.items():
+        out, val, act = got.values()
         assert (act >= 0).all() and np.array_equal(val, out[np.arange(len(out)), act])
         assert np.array_equal(out == NONE, ~legal)
         ranks = np.vectorize(R.rank)(np.where(legal, out, 0).astype(int))
@@ -154,7 +156,7 @@ def test_value_is_the_outcome_at_the_action_and_non_candidates_are_none(by_depth
 
 def test_depth_1_marks_the_moves_that_end_the_game(cpu, by_depth):
     st, tm = property_positions()
-    out = by_depth[1][0]
+    out = by_depth[1]["outcome"]
     rows, acts = np.nonzero(out != NONE)
     after = np.ascontiguousarray([oracle.play_turn(st[b], int(tm[b]), int(a)) for b, a in zip(rows, acts)], np.int8)
     win = np.full(len(after), 77, np.int8)
@@ -166,14 +168,15 @@ def test_depth_1_marks_the_moves_that_end_the_game(cpu, by_depth):
 
 def test_a_root_without_a_candidate(cpu):
     st, tm = sample()
-    out, val, act = R.run(cpu, st, tm, np.zeros((len(st), 54), np.int8), 3)
+    out, val, act = run("solve", "cpu", st, tm, np.zeros((len(st), 54), np.int8), (3,)).values()
     assert (out == NONE).all() and (val == 0).all() and (act == -1).all()
 
 
 def call(cpu, state, to_move, mask, depth, outcome, value, action, n):
     p = [None if a is None else (a if isinstance(a, int) else a.ctypes.data) for a in (state, to_move, mask)]
     o = [None if a is None else (a if isinstance(a, int) else a.ctypes.data) for a in (outcome, value, action)]
-    rc = cpu.gbl_cpu_solve(p[0], p[1], p[2], depth, o[0], o[1], o[2], n, None)
+    solve = cpu.gbl_cpu_solve
+    rc = solve(p[0], p[1], p[2], depth, o[0], o[1], o[2], n, None)
     return rc, cpu.gbl_cpu_last_error().decode()
 
 
@@ -271,7 +274,7 @@ def test_batched_env_solve_on_the_host_flavour(cpu):
     env.squares.copy_(torch.from_numpy(st.copy()))
     env.to_move.copy_(torch.from_numpy(tm.copy()))
     got = env.solve(2)
-    R.same((got["outcome"].numpy(), got["value"].numpy(), got["action"].numpy()), expected("sample", 2))
+    same({k: v.numpy() for k, v in got.items()}, expected("sample", 2))
     for depth in (0, 7):
         with pytest.raises(ValueError, match="depth must be in"):
             env.solve(depth)

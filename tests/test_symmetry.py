@@ -14,6 +14,7 @@ import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from gobblet_rl_amd import symmetry as S
 from tests import solver_restatement as SR
+from tests.search_harness import replay_arg_errors, run
 from tests import symmetry_restatement as R
 
 LINES = ((0, 1, 2), (3, 4, 5), (6, 7, 8), (0, 3, 6), (1, 4, 7), (2, 5, 8), (0, 4, 8), (2, 4, 6))
@@ -195,11 +196,11 @@ def test_solver_commutes_with_the_piece_swaps(cpu):
     parts = [SR.rollout_positions(10), SR.zugzwang(), SR.hand_built()]
     st, tm = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
     assert len(st) == 256
-    out, val, _ = SR.run(cpu, st, tm, None, 3)
+    out, val, _ = run("solve", "cpu", st, tm, None, (3,)).values()
     codes = ((np.arange(256) * 29 + 1) % 64).astype(np.int16) << 3   # every swap pattern, four boards each
     assert len(set(codes.tolist())) == 64 and (codes & 7 == 0).all()
     g_st = R.run_apply(cpu, codes, None, state=st)["state"]
-    g_out, g_val, g_act = SR.run(cpu, g_st, tm, None, 3)
+    g_out, g_val, g_act = run("solve", "cpu", g_st, tm, None, (3,)).values()
     assert np.array_equal(g_out, R.run_apply(cpu, codes, tm, mask=out)["mask"]) and np.array_equal(g_val, val)
     assert (g_out != out).any() and (out[256 - 4] == 2).any()   # (ZUG_NODE's win in two is there)
     has = g_act >= 0
@@ -326,14 +327,6 @@ def test_batch_argument_errors_replay_the_recorded_table(golden_dir):
     """tests/golden/batch_arg_errors.json: bad calls of gbl_symmetry_apply and gbl_training_batch with the return code and the
     gbl_last_error text of either flavour.  Every call returns before any device work (the pointers are numbers, never read); a case
     whose "host" is null is an alignment rule, which only the device flavour has."""
-    flavours = (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_"))
     table = json.load(open(os.path.join(golden_dir, "batch_arg_errors.json")))
     assert len(table) > 40 and {c["fn"] for c in table} == {"symmetry_apply", "training_batch"}
-    for c in table:
-        for flavour, lib, prefix in flavours:
-            if c[flavour] is None:
-                continue
-            rc, msg = c[flavour]
-            assert getattr(lib, prefix + c["fn"])(*c["args"]) == rc, (flavour, c["fn"], c["case"])
-            if rc:
-                assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["fn"], c["case"])
+    replay_arg_errors(table)

@@ -12,6 +12,7 @@ import torch
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
 from tests import train_restatement as R
+from tests.search_harness import replay_arg_errors
 from tests.test_evaluator_edges import compare_with_float, open_positions  # noqa: F401  (a helper and a fixture, reused as they are)
 
 F = np.float32
@@ -300,17 +301,11 @@ def test_the_trainer_starts_as_torch_linear_does():
 def test_argument_errors_replay_the_recorded_table(golden_dir):
     """tests/golden/train_arg_errors.json as the other *_arg_errors.json tables: every call returns before any work (the pointers are
     numbers, never read); a case whose "host" is null is an alignment rule, which only the device flavour has."""
-    flavours = (("device", nat.lib(), "gbl_"), ("host", nat.cpu_raw(), "gbl_cpu_"))
     table = json.load(open(os.path.join(golden_dir, "train_arg_errors.json")))
     assert len(table) > 25 and {c["fn"] for c in table} == {"train_step"}
     assert {c["device"][0] for c in table} == {nat.ERR_ARG, nat.ERR_ALIGN}
-    for c in table:
-        for flavour, lib, prefix in flavours:
-            if c[flavour] is None:
-                continue
-            rc, msg = c[flavour]
-            assert getattr(lib, prefix + c["fn"])(*c["args"]) == rc, (flavour, c["case"])
-            assert getattr(lib, prefix + "last_error")().decode() == msg, (flavour, c["case"])
+    assert all(c[f] is None or c[f][0] != nat.OK for c in table for f in ("device", "host"))  # (so the message is compared for every case)
+    replay_arg_errors(table)
 
 
 def test_workspace_bytes_is_positive_and_monotone():

@@ -11,11 +11,11 @@ import oracle
 
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
+from tests.search_harness import TREE_NAMES as NAMES, run, same
 from tests.test_playout_policy import (E40, UNCOVER_ACTION, UNCOVER_SEQ, WIN_ACTION, WIN_SEQ, arena, play, random_midgames,
                                        sample_stream)
 
 STREAM_TREE = 3
-NAMES = ("visits", "wins", "losses", "action", "nodes", "plies")
 
 
 def pid(g, i, j):
@@ -94,23 +94,6 @@ def restate(state, to_move, mask, I, P, M, X, seed, env_base, call):
     return visits, wins, losses, action, nodes, plies
 
 
-def run(lib, state, to_move, mask, I, P, M, X, seed, env_base, call):
-    """gbl_tree_search on host arrays through `lib` (the host flavour's raw handle): the six outputs."""
-    n = len(state)
-    out = [np.full((n, 54), -7, np.int32) for _ in range(3)] + [np.full(n, -7, np.int32) for _ in range(3)]
-    st, tm = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(to_move, np.int8)
-    mk = None if mask is None else np.ascontiguousarray(mask, np.int8)
-    rc = lib.gbl_cpu_tree_search(st.ctypes.data, tm.ctypes.data, None if mk is None else mk.ctypes.data, I, P, M, X, seed, env_base,
-                                 call, *[o.ctypes.data for o in out], n, None)
-    assert rc == 0, lib.gbl_cpu_last_error()
-    return tuple(out)
-
-
-def same(got, exp):
-    for name, g, e in zip(NAMES, got, exp):
-        assert np.array_equal(g, e), (name, np.argwhere(g != e)[:5])
-
-
 @pytest.fixture(scope="module")
 def cpu():
     L = nat.cpu_raw()
@@ -141,16 +124,16 @@ def test_host_flavour_equals_restatement(cpu, boards, I, P, M, X, call, env_base
     st, tm = boards
     if I == 200:  # (the restatement walks every ply through ctypes: a third of the boards at the largest budget)
         st, tm = st[::3], tm[::3]
-    same(run(cpu, st, tm, None, I, P, M, X, 9, env_base, call), restate(st, tm, None, I, P, M, X, 9, env_base, call))
+    same(run("tree_search", "cpu", st, tm, None, (I, P, M, X, 9, env_base, call)), restate(st, tm, None, I, P, M, X, 9, env_base, call))
 
 
 def test_host_flavour_equals_restatement_with_mask(cpu, boards):
     st, tm = boards
     mask = (np.random.default_rng(2).random((len(st), 54)) < 0.4).astype(np.int8)
     mask[0] = 0  # a board without a candidate
-    got = run(cpu, st, tm, mask, 48, 5, 40, 128, 1, 3, 2)
+    got = run("tree_search", "cpu", st, tm, mask, (48, 5, 40, 128, 1, 3, 2))
     same(got, restate(st, tm, mask, 48, 5, 40, 128, 1, 3, 2))
-    assert got[3][0] == -1 and got[4][0] == 1 and got[5][0] == 0 and not got[0][0].any()
+    assert got["action"][0] == -1 and got["nodes"][0] == 1 and got["plies"][0] == 0 and not got["visits"][0].any()
 
 
 @pytest.fixture(scope="module")
@@ -175,7 +158,7 @@ def test_properties(cpu, many):
     mask = (np.random.default_rng(8).random((n, 54)) < 0.5).astype(np.int8)
     mask[5] = 0
     args = (P, 64, 128, 4)
-    v, w, l, a, nd, p = run(cpu, st, tm, mask, I, *args, 100, 1)
+    v, w, l, a, nd, p = run("tree_search", "cpu", st, tm, mask, (I, *args, 100, 1)).values()
     cand = legal & (mask != 0)
     has = cand.any(1)
     assert has.sum() > 290 and not has[5]
@@ -187,27 +170,27 @@ def test_properties(cpu, many):
     assert (p <= I * P * 64).all()
     # no more iterations than candidates: every root child is visited at most once, and every iteration made a node
     few = int(cand.sum(1)[has].min())
-    v1, _, _, _, nd1, _ = run(cpu, st, tm, mask, few, *args, 100, 1)
+    v1, _, _, _, nd1, _ = run("tree_search", "cpu", st, tm, mask, (few, *args, 100, 1)).values()
     assert np.isin(v1, (0, 1)).all() and (nd1[has] == few + 1).all()
     # a search is the beginning of every longer one
-    v2, _, _, _, nd2, p2 = run(cpu, st, tm, mask, 2 * I, *args, 100, 1)
+    v2, _, _, _, nd2, p2 = run("tree_search", "cpu", st, tm, mask, (2 * I, *args, 100, 1)).values()
     assert (nd2 >= nd).all() and (p2 >= p).all() and (v2.sum(1)[has] == 2 * I).all()
     assert (v2 >= v).all()  # (n_c of a root child only grows)
     # sharding over env_base changes nothing
     h = n // 3
-    parts = [run(cpu, st[i:j], tm[i:j], mask[i:j], I, *args, 100 + i, 1) for i, j in ((0, h), (h, n))]
-    for k in range(6):
-        assert np.array_equal(np.concatenate([q[k] for q in parts]), (v, w, l, a, nd, p)[k]), NAMES[k]
+    parts = [run("tree_search", "cpu", st[i:j], tm[i:j], mask[i:j], (I, *args, 100 + i, 1)) for i, j in ((0, h), (h, n))]
+    for k, whole in zip(NAMES, (v, w, l, a, nd, p)):
+        assert np.array_equal(np.concatenate([q[k] for q in parts]), whole), k
     # another call index searches otherwise; the same call twice gives the same
-    v5 = run(cpu, st, tm, mask, I, *args, 100, 5)[0]
+    v5 = run("tree_search", "cpu", st, tm, mask, (I, *args, 100, 5))["visits"]
     assert not np.array_equal(v5, v)
-    same(run(cpu, st, tm, mask, I, *args, 100, 1), (v, w, l, a, nd, p))
+    same(run("tree_search", "cpu", st, tm, mask, (I, *args, 100, 1)), (v, w, l, a, nd, p))
 
 
 def test_decided_root_moves(cpu):
     (sw, mw), (su, mu) = play(WIN_SEQ), play(UNCOVER_SEQ)
     I, P = 128, 8
-    v, w, l, a, _, _ = run(cpu, np.array([sw, su]), np.array([mw, mu]), None, I, P, 64, 128, 0, 0, 0)
+    v, w, l, a, _, _ = run("tree_search", "cpu", np.array([sw, su]), np.array([mw, mu]), None, (I, P, 64, 128, 0, 0, 0)).values()
     assert a[0] == WIN_ACTION and v[0, WIN_ACTION] > 0 and w[0, WIN_ACTION] == v[0, WIN_ACTION] * P and l[0, WIN_ACTION] == 0
     assert a[1] != UNCOVER_ACTION and l[1, UNCOVER_ACTION] == v[1, UNCOVER_ACTION] * P and w[1, UNCOVER_ACTION] == 0
 
@@ -298,22 +281,22 @@ def test_policy_surface_on_cpu(cpu, many):
     a = G.TreeSearchGobbletPolicy(**kw).compute_actions(obs, mask)
     b = G.TreeSearchGobbletPolicy(**kw).compute_actions_from_state(st, tm)
     assert a.dtype == torch.int32 and torch.equal(a, b)
-    exp = run(nat.cpu_raw(), st.numpy(), tm.numpy(), None, 40, 4, 64, 96, 3, 0, 0)
-    assert np.array_equal(b.numpy(), exp[3])
+    exp = run("tree_search", "cpu", st.numpy(), tm.numpy(), None, (40, 4, 64, 96, 3, 0, 0))
+    assert np.array_equal(b.numpy(), exp["action"])
     pol = G.TreeSearchGobbletPolicy(**kw)
     val = pol.action_values(st, tm)
     last = (pol.last_visits, pol.last_wins, pol.last_losses, pol.last_action, pol.last_nodes, pol.last_plies)
-    same([t.numpy() for t in last], exp)
-    seen = exp[0] > 0
-    assert np.array_equal(val.numpy()[seen], ((exp[1] - exp[2])[seen] / (exp[0][seen] * 4.0)).astype(np.float32))
+    same(exp, [t.numpy() for t in last])
+    seen = exp["visits"] > 0
+    assert np.array_equal(val.numpy()[seen], ((exp["wins"] - exp["losses"])[seen] / (exp["visits"][seen] * 4.0)).astype(np.float32))
     assert np.isneginf(val.numpy()[~seen]).all()
     # the call index moves on once per call
     assert pol._calls == 1
     dist = pol.visit_distribution(st, tm)
     assert pol._calls == 2
-    exp1 = run(nat.cpu_raw(), st.numpy(), tm.numpy(), None, 40, 4, 64, 96, 3, 0, 1)
-    assert dist.dtype == torch.float32 and np.array_equal(pol.last_visits.numpy(), exp1[0])
-    assert np.allclose(dist.numpy(), exp1[0] / 40.0, rtol=1e-6, atol=0)  # (one float32 division: 2^-24 relative)
+    exp1 = run("tree_search", "cpu", st.numpy(), tm.numpy(), None, (40, 4, 64, 96, 3, 0, 1))
+    assert dist.dtype == torch.float32 and np.array_equal(pol.last_visits.numpy(), exp1["visits"])
+    assert np.allclose(dist.numpy(), exp1["visits"] / 40.0, rtol=1e-6, atol=0)  # (one float32 division: 2^-24 relative)
     assert np.allclose(dist.sum(1).numpy(), 1.0) and (dist.numpy()[mask.numpy() == 0] == 0).all()
     none = pol.visit_distribution(st[:2], tm[:2], torch.zeros((2, 54), dtype=torch.int8))  # boards without a candidate
     assert not none.any() and (pol.last_action == -1).all()
