@@ -1287,6 +1287,89 @@ int gbl_cpu_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, cons
     return GBL_OK;
 }
 
+// The header's enumeration as it reads: the cells in ascending (t, b), counted once and then walked again with their ranks (one
+// thread: the order is the rule).  The workspace is checked like the device flavour's and not used.
+int gbl_cpu_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                          const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                          int64_t tile_stride, int32_t tag, int8_t *ring_obs, int16_t *ring_visits, int8_t *ring_meta, int64_t capacity,
+                          uint64_t *ring_state, void *workspace, size_t workspace_bytes, void *)
+{
+    if (const char *why = replay_append_error(obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, n, plies, ply_stride,
+                                              tile_stride, ring_obs, ring_visits, ring_meta, capacity, ring_state, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    const auto valid = [=](uint32_t t, int64_t b) {
+        return batch_valid(z_traj, done_traj, visits_traj, traj_cell(t, b, ply_stride, tile_stride), traj_cell((int64_t)t - 1, b, ply_stride, tile_stride));
+    };
+    uint64_t K = 0, R = 0;
+    for (uint32_t t = 1; t < plies; ++t)
+        for (int64_t b = 0; b < n; ++b) K += valid(t, b);
+    const uint64_t T0 = ring_state[0], cap = (uint64_t)capacity;
+    for (uint32_t t = 1; t < plies; ++t) {
+        for (int64_t b = 0; b < n; ++b) {
+            if (!valid(t, b)) continue;
+            const uint64_t r = R++;
+            if (!replay_kept(r, K, cap)) continue;
+            const int64_t slot = replay_slot(T0, r, cap), at = traj_cell(t, b, ply_stride, tile_stride),
+                          prev = traj_cell((int64_t)t - 1, b, ply_stride, tile_stride);
+            if (ring_obs) {
+                int8_t *o = ring_obs + slot * kReplayObsPitch;
+                memcpy(o, obs_traj + prev * kObs, kObs);
+                memset(o + kObs, 0, kReplayObsPitch - kObs);
+            }
+            int16_t *v = ring_visits + slot * kReplayVisitsPitch;
+            memcpy(v, visits_traj + at * kActions, 2 * kActions);
+            memset(v + kActions, 0, 2 * (kReplayVisitsPitch - kActions));
+            int8_t *m = ring_meta + slot * kReplayMetaPitch;
+            memcpy(m, mask_traj + prev * kActions, kActions);
+            m[kReplayMetaZ] = z_traj[at];
+            m[kReplayMetaMover] = (int8_t)(mover_traj[at] != 0);
+            for (int i = 0; i < 4; ++i) m[kReplayMetaTag + i] = (int8_t)((uint32_t)tag >> (8 * i));
+            memset(m + kReplayMetaTag + 4, 0, kReplayMetaPitch - kReplayMetaTag - 4);
+        }
+    }
+    ring_state[0] = T0 + K;
+    ring_state[1] = K;
+    return GBL_OK;
+}
+
+int gbl_cpu_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                         const uint64_t *ring_state, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
+                         uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
+                         int16_t *sym_out, void *)
+{
+    if (const char *why = replay_batch_error(ring_obs, ring_visits, ring_meta, capacity, ring_state, recent, batch, sym_mask, call, obs_out,
+                                             index_out))
+        return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    const uint64_t total = ring_state[0];
+    parallel_for(batch, [=](int64_t j0, int64_t j1) {
+        for (int64_t j = j0; j < j1; ++j) {
+            const ReplayDraw d = replay_draw(seed, sample_base + (uint64_t)j, call, total, (uint64_t)capacity, recent);
+            const bool ok = d.slot >= 0;
+            const uint32_t code = ok ? d.sym & (uint32_t)sym_mask : 0u;
+            const int8_t *meta = ring_meta + (ok ? d.slot : 0) * kReplayMetaPitch;
+            int32_t tag = -1;
+            if (ok) memcpy(&tag, meta + kReplayMetaTag, 4);
+            index_out[2 * j] = ok ? (int32_t)d.slot : -1;
+            index_out[2 * j + 1] = tag;
+            if (z_out) z_out[j] = ok ? meta[kReplayMetaZ] : (int8_t)kZOpen;
+            if (sym_out) sym_out[j] = (int16_t)code;
+            if (!ok) {
+                if (obs_out) memset(obs_out + j * kObs, 0, kObs);
+                if (mask_out) memset(mask_out + j * kActions, 0, kActions);
+                if (visits_out) memset(visits_out + j * kActions, 0, 2 * kActions);
+                continue;
+            }
+            const Sym S = sym_of(code);
+            const uint32_t m = meta[kReplayMetaMover] != 0;
+            if (obs_out) sym_obs_row(ring_obs + d.slot * kReplayObsPitch, obs_out + j * kObs, S, m);
+            if (mask_out) sym_action_row(meta, mask_out + j * kActions, S, m);
+            if (visits_out) sym_action_row(ring_visits + d.slot * kReplayVisitsPitch, visits_out + j * kActions, S, m);
+        }
+    });
+    return GBL_OK;
+}
+
 }  // extern "C"
 
 // gbl_cpu_train_step: the header's rule row by row and element by element -- the same scalar pieces (gobblet_device.h: train_exp,

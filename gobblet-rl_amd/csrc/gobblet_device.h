@@ -2813,6 +2813,83 @@ inline const char *batch_error(const void *obs_traj, const void *mask_traj, cons
     return nullptr;
 }
 
+// ---- replay buffer (include/gobblet_hip.h, "Replay buffer"): the rule's pieces, shared by the kernels and the host flavour ------------
+constexpr int kReplayObsPitch = 128;    // GBL_REPLAY_OBS_PITCH (bytes)
+constexpr int kReplayVisitsPitch = 64;  // GBL_REPLAY_VISITS_PITCH (int16 elements)
+constexpr int kReplayMetaPitch = 64;    // GBL_REPLAY_META_PITCH (bytes)
+constexpr int kReplayMetaZ = 54, kReplayMetaMover = 55, kReplayMetaTag = 56;  // GBL_REPLAY_META_*
+constexpr uint32_t kStreamReplay = 7u;  // generator stream of gbl_replay_batch's draws
+constexpr int64_t kReplayMaxCapacity = 0x7FFFFFFF;
+constexpr int kReplayWsHead = 4;        // the workspace's first uint64s: T0, K, two of padding; then the chunks' ballots, then their bases
+
+// chunk c = (t - 1) * tiles + tile holds the cells (t, 64 tile .. 64 tile + 63): ascending c, then ascending lane, is ascending (t, b)
+inline int64_t replay_chunks(int64_t n, uint32_t plies) { return ((int64_t)plies - 1) * ((n + kTile - 1) / kTile); }
+inline bool replay_window_ok(int64_t n, uint32_t plies) { return plies >= 2u && plies <= 32767u && n >= 1 && n <= ((int64_t)1 << 31); }
+inline uint64_t replay_workspace_bytes(int64_t n, uint32_t plies)
+{
+    return replay_window_ok(n, plies) ? 8u * ((uint64_t)kReplayWsHead + 2u * (uint64_t)replay_chunks(n, plies)) : 0u;
+}
+// the cell of rank R of an append of K rows onto T0: is it written at all, and where
+__device__ __forceinline__ bool replay_kept(uint64_t R, uint64_t K, uint64_t capacity) { return K - R <= capacity; }
+__device__ __forceinline__ uint32_t replay_slot(uint64_t T0, uint64_t R, uint64_t capacity) { return (uint32_t)((T0 + R) % capacity); }
+
+// sample `id` of gbl_replay_batch on a ring that has taken `total` rows: its slot (-1: the ring is empty) and its symmetry word
+struct ReplayDraw {
+    int64_t slot;
+    uint32_t sym;
+};
+__device__ __forceinline__ ReplayDraw replay_draw(uint64_t seed, uint64_t id, uint32_t call, uint64_t total, uint64_t capacity, int64_t recent)
+{
+    const Draw4 d = draw_block(seed, id, 4u * ((uint32_t)kBatchAttempts * call), kStreamReplay);  // (batch_draw's attempt 0, another stream)
+    const uint64_t live = total < capacity ? total : capacity;
+    if (live == 0) return ReplayDraw{-1, 0u};
+    const uint64_t span = recent > 0 && (uint64_t)recent < live ? (uint64_t)recent : live;
+    const uint64_t age = __umulhi(d.w[0], (uint32_t)span), newest = (total - 1u) % capacity;
+    return ReplayDraw{(int64_t)(newest >= age ? newest - age : newest + capacity - age), d.w[2]};
+}
+
+inline const char *replay_append_error(const void *obs_traj, const void *mask_traj, const void *visits_traj, const void *z_traj,
+                                       const void *done_traj, const void *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                                       int64_t tile_stride, const void *ring_obs, const void *ring_visits, const void *ring_meta,
+                                       int64_t capacity, const void *ring_state, const void *workspace, uint64_t workspace_bytes)
+{
+    if (plies < 2u || plies > 32767u) return "plies must be in [2, 32767]";
+    if (n < 1 || n > ((int64_t)1 << 31)) return "n must be in [1, 2^31]";
+    if (capacity < 1 || capacity > kReplayMaxCapacity) return "capacity must be in [1, 2^31 - 1]";
+    if (!mask_traj) return "mask_traj must not be NULL";
+    if (!visits_traj) return "visits_traj must not be NULL";
+    if (!z_traj) return "z_traj must not be NULL";
+    if (!done_traj) return "done_traj must not be NULL";
+    if (!mover_traj) return "mover_traj must not be NULL";
+    if (!ring_visits) return "ring_visits must not be NULL";
+    if (!ring_meta) return "ring_meta must not be NULL";
+    if (!ring_state) return "ring_state must not be NULL";
+    if (!workspace) return "workspace must not be NULL";
+    if (!ring_obs != !obs_traj) return "ring_obs and obs_traj go together";
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return kStridesMessage;
+    if (workspace_bytes < replay_workspace_bytes(n, plies)) return "workspace_bytes is below gbl_replay_workspace_bytes";
+    return nullptr;
+}
+
+// (ok_zero: batch == 0 returns GBL_OK after the scalar checks)
+inline const char *replay_batch_error(const void *ring_obs, const void *ring_visits, const void *ring_meta, int64_t capacity,
+                                      const void *ring_state, int64_t recent, int64_t batch, int sym_mask, uint32_t call,
+                                      const void *obs_out, const void *index_out)
+{
+    if (capacity < 1 || capacity > kReplayMaxCapacity) return "capacity must be in [1, 2^31 - 1]";
+    if (batch < 0 || batch > ((int64_t)1 << 31)) return "batch must be in [0, 2^31]";
+    if (sym_mask < 0 || sym_mask >= kSymmetries) return "sym_mask must be in [0, 511]";
+    if (call >= (1u << 26)) return "call must be below 2^26";
+    if (recent < 0) return "recent must not be negative";
+    if (batch == 0) return nullptr;
+    if (!ring_visits) return "ring_visits must not be NULL";
+    if (!ring_meta) return "ring_meta must not be NULL";
+    if (!ring_state) return "ring_state must not be NULL";
+    if (!index_out) return "index_out must not be NULL";
+    if (obs_out && !ring_obs) return "obs_out needs ring_obs";
+    return nullptr;
+}
+
 // ---- gbl_train_step (include/gobblet_hip.h, "One Adam step of the FLOAT network"): the scalar pieces of the bit-defined rule ----------
 // Shared by k_train_rows / k_train_reduce_adam and the host flavour.  Every function that does float arithmetic for the rule opens
 // with GBL_FP_STRICT, and so do the two kernels and the host flavour's own loops (train_row, train_sum, gbl_cpu_train_step): hipcc

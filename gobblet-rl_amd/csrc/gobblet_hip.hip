@@ -2446,16 +2446,50 @@ struct BatchArgs {
     uint32_t plies, call, sym_mask;
 };
 
-// rows `ROWS` of element type T and E elements: element k of sample r from src[cell_r * E + from(r, k)], zeros for a failed sample
-template <typename T, int E, typename From>
+// rows `ROWS` of element type T and E elements: element k of sample r from src[cell_r * PITCH + from(r, k)], zeros for a failed sample
+// (PITCH: the source's row pitch in elements -- E in a trajectory array, a whole line in the replay ring)
+template <typename T, int E, int PITCH, typename From>
 __device__ __forceinline__ void batch_gather(const T *__restrict__ src, T *img, const int64_t *s_cell, int rows, uint32_t k, From from)
 {
     if (k >= (uint32_t)E) return;
 #pragma unroll 4
     for (int r = 0; r < rows; ++r) {
         const int64_t c = s_cell[r];
-        const T v = src[(c >= 0 ? c : 0) * E + from(r, k)];  // (a failed sample reads cell 0 and drops it: no branch around the load)
+        const T v = src[(c >= 0 ? c : 0) * PITCH + from(r, k)];  // (a failed sample reads cell 0 and drops it: no branch around the load)
         img[r * E + (int)k] = c >= 0 ? v : (T)0;
+    }
+}
+
+// Phases 2 and 3 of a batch kernel (k_training_batch, k_replay_batch): the 64 output rows of each type gathered into the one LDS image
+// under the samples' symmetries (s_inv, s_sw = swap bits | mover << 6) and stored as a tile.  s_prev / s_at: the source rows of the
+// observation and the mask / of the visits (-1: a failed sample); the pitches are the sources' row pitches in elements.
+template <int OBS_PITCH, int MASK_PITCH, int VISITS_PITCH>
+__device__ __forceinline__ void batch_rows(const int8_t *__restrict__ obs, const int8_t *__restrict__ mask, const int16_t *__restrict__ visits,
+                                           int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, uint32_t *s_img, const int64_t *s_at,
+                                           const int64_t *s_prev, const uint64_t *s_inv, const uint32_t *s_sw, const Lane &L)
+{
+    const uint32_t k = (uint32_t)L.lane;
+    const auto sym_r = [&](int r) { return Sym{0ull, s_inv[r], s_sw[r] & 63u}; };
+    if (obs_out) {
+        int8_t *img = reinterpret_cast<int8_t *>(s_img);
+        const auto from = [&](int r, uint32_t e) { return sym_obs_src(sym_r(r), s_sw[r] >> 6, e); };
+        batch_gather<int8_t, kObs, OBS_PITCH>(obs, img, s_prev, L.rows, k, from);
+        batch_gather<int8_t, kObs, OBS_PITCH>(obs, img, s_prev, L.rows, k + 64u, from);
+        wave_lds_fence();
+        tile_out<kObs, kStoreStream>(obs_out + L.tile * (kTile * kObs), s_img, L.lane, L.rows);
+        wave_lds_fence();
+    }
+    const auto from = [&](int r, uint32_t e) { return sym_action_src(sym_r(r), s_sw[r] >> 6, e); };
+    if (mask_out) {
+        batch_gather<int8_t, kActions, MASK_PITCH>(mask, reinterpret_cast<int8_t *>(s_img), s_prev, L.rows, k, from);
+        wave_lds_fence();
+        tile_out<kActions, kStoreStream>(mask_out + L.tile * (kTile * kActions), s_img, L.lane, L.rows);
+        wave_lds_fence();
+    }
+    if (visits_out) {
+        batch_gather<int16_t, kActions, VISITS_PITCH>(visits, reinterpret_cast<int16_t *>(s_img), s_at, L.rows, k, from);
+        wave_lds_fence();
+        tile_out<2 * kActions, kStoreStream>(reinterpret_cast<int8_t *>(visits_out) + L.tile * (kTile * 2 * kActions), s_img, L.lane, L.rows);
     }
 }
 
@@ -2488,29 +2522,217 @@ __global__ __launch_bounds__(64) void k_training_batch(BatchArgs A)
     }
     s_at[L.lane] = at; s_prev[L.lane] = prev; s_inv[L.lane] = S.inv; s_sw[L.lane] = S.swaps | (m << 6);
     wave_lds_fence();
-    const uint32_t k = (uint32_t)L.lane;
-    const auto sym_r = [&](int r) { return Sym{0ull, s_inv[r], s_sw[r] & 63u}; };
-    if (A.obs_out) {
-        int8_t *img = reinterpret_cast<int8_t *>(s_img);
-        const auto from = [&](int r, uint32_t e) { return sym_obs_src(sym_r(r), s_sw[r] >> 6, e); };
-        batch_gather<int8_t, kObs>(A.obs, img, s_prev, L.rows, k, from);
-        batch_gather<int8_t, kObs>(A.obs, img, s_prev, L.rows, k + 64u, from);
-        wave_lds_fence();
-        tile_out<kObs, kStoreStream>(A.obs_out + L.tile * (kTile * kObs), s_img, L.lane, L.rows);
-        wave_lds_fence();
+    batch_rows<kObs, kActions, kActions>(A.obs, A.mask, A.visits, A.obs_out, A.mask_out, A.visits_out, s_img, s_at, s_prev, s_inv, s_sw, L);
+}
+
+// ---- replay buffer (include/gobblet_hip.h, "Replay buffer") -----------------------------------------------------------------------
+// gbl_replay_append in three launches, the result a function of the inputs alone (no atomics, no waiting between workgroups):
+//   k_replay_count    one wavefront per chunk (the 64 boards of one tile at one ply; chunks in ascending (t, tile) and lanes in ascending
+//                     board are the header's order): lane l tests cell l, the chunk's BALLOT goes to the workspace -- the scatter reads
+//                     the 8 bytes back instead of the chunk's z, done and visits a second time.
+//   k_replay_scan     one workgroup: every thread sums the popcounts of a contiguous stretch of chunks, the workgroup scans the 1 024
+//                     sums in LDS, every thread walks its stretch again and leaves each chunk's first rank; the last thread leaves T0
+//                     and K for the scatter and writes the new ring_state.
+//   k_replay_scatter  one wavefront per chunk: a lane's rank inside the chunk is mbcnt of the ballot; row type after row type the
+//                     chunk's source tile comes in as 16-byte vectors (tile_in), the valid rows are closed up and padded to the ring's
+//                     pitch in a second LDS image, dword by dword, and leave as whole 16-byte vectors, each to the slot of its row
+//                     (the wrap of the ring and the K - capacity cut are per row; no two rows that are written share a slot).
+struct ReplayAppendArgs {
+    const int8_t *obs, *mask;
+    const int16_t *visits;
+    const int8_t *z, *done, *mover;
+    int8_t *ring_obs;
+    int16_t *ring_visits;
+    int8_t *ring_meta;
+    uint64_t *state, *ws;
+    int64_t n, ply_stride, tile_stride, ntiles, chunks;
+    uint64_t capacity;
+    int32_t tag;
+};
+
+constexpr int kReplayScanThreads = 1024;
+constexpr int64_t kReplayMaxGrid = (int64_t)1 << 18;  // (more chunks than that: the wavefronts stride over them)
+
+__global__ __launch_bounds__(64) void k_replay_count(ReplayAppendArgs A)
+{
+    const int lane = threadIdx.x;
+    uint64_t *ballots = A.ws + kReplayWsHead;
+    for (int64_t c = blockIdx.x; c < A.chunks; c += gridDim.x) {
+        const int64_t t = 1 + c / A.ntiles, tile = c % A.ntiles;
+        const int64_t at = t * A.ply_stride + tile * A.tile_stride + lane;
+        const bool ok = tile * kTile + lane < A.n && batch_valid(A.z, A.done, A.visits, at, at - A.ply_stride);
+        const uint64_t votes = __ballot(ok);
+        if (lane == 0) ballots[c] = votes;
     }
-    const auto from = [&](int r, uint32_t e) { return sym_action_src(sym_r(r), s_sw[r] >> 6, e); };
-    if (A.mask_out) {
-        batch_gather<int8_t, kActions>(A.mask, reinterpret_cast<int8_t *>(s_img), s_prev, L.rows, k, from);
-        wave_lds_fence();
-        tile_out<kActions, kStoreStream>(A.mask_out + L.tile * (kTile * kActions), s_img, L.lane, L.rows);
-        wave_lds_fence();
+}
+
+__global__ __launch_bounds__(kReplayScanThreads) void k_replay_scan(ReplayAppendArgs A)
+{
+    __shared__ uint64_t s_sum[2][kReplayScanThreads];
+    const int tid = threadIdx.x;
+    const uint64_t *ballots = A.ws + kReplayWsHead;
+    uint64_t *bases = A.ws + kReplayWsHead + A.chunks;
+    const int64_t per = (A.chunks + kReplayScanThreads - 1) / kReplayScanThreads;
+    const int64_t c0 = std::min<int64_t>(tid * per, A.chunks), c1 = std::min<int64_t>(c0 + per, A.chunks);
+    uint64_t mine = 0;
+    for (int64_t c = c0; c < c1; ++c) mine += (uint64_t)__popcll(ballots[c]);
+    s_sum[0][tid] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < kReplayScanThreads; d <<= 1) {  // (Hillis-Steele over the two halves of s_sum: one barrier per step)
+        s_sum[cur ^ 1][tid] = s_sum[cur][tid] + (tid >= d ? s_sum[cur][tid - d] : 0ull);
+        __syncthreads();
+        cur ^= 1;
     }
-    if (A.visits_out) {
-        batch_gather<int16_t, kActions>(A.visits, reinterpret_cast<int16_t *>(s_img), s_at, L.rows, k, from);
-        wave_lds_fence();
-        tile_out<2 * kActions, kStoreStream>(reinterpret_cast<int8_t *>(A.visits_out) + L.tile * (kTile * 2 * kActions), s_img, L.lane, L.rows);
+    const uint64_t upto = s_sum[cur][tid];
+    uint64_t base = upto - mine;
+    for (int64_t c = c0; c < c1; ++c) {
+        bases[c] = base;
+        base += (uint64_t)__popcll(ballots[c]);
     }
+    if (tid == kReplayScanThreads - 1) {
+        const uint64_t T0 = A.state[0];
+        A.ws[0] = T0; A.ws[1] = upto;
+        A.state[0] = T0 + upto; A.state[1] = upto;
+    }
+}
+
+// close the chunk's valid rows up: dword q of the image `dst` of cnt rows of PITCHB bytes = the bytes of row s_from[q / (PITCHB / 4)] of
+// `src` (rows of ROWB bytes, at any byte offset: two dwords and an alignbyte), zeros from byte ROWB on
+template <int ROWB, int PITCHB>
+__device__ __forceinline__ void replay_pack(const uint32_t *src, uint32_t *dst, const uint8_t *s_from, int cnt, int lane)
+{
+    constexpr int DW = PITCHB / 4;
+    for (int q = lane; q < cnt * DW; q += 64) {
+        const int r = q / DW, d = q % DW;
+        const int o = (int)s_from[r] * ROWB + 4 * d, left = ROWB - 4 * d;  // (left: bytes of the row from this dword on)
+        uint32_t v = 0u;
+        if (left > 0) {
+            v = __builtin_amdgcn_alignbyte(src[(o >> 2) + 1], src[o >> 2], (uint32_t)o & 3u);  // (the + 1 stays inside the image's slack)
+            if (left < 4) v &= (1u << (8 * left)) - 1u;
+        }
+        dst[q] = v;
+    }
+}
+
+// the closed-up image out: 16-byte vector q belongs to row q / (PITCHB / 16), which goes to slot s_slot[row] (-1: under the cut)
+template <int PITCHB>
+__device__ __forceinline__ void replay_store(int8_t *__restrict__ ring, const uint32_t *dst, const int32_t *s_slot, int cnt, int lane)
+{
+    constexpr int VEC = PITCHB / 16;
+    const uint4 *lv = reinterpret_cast<const uint4 *>(dst);
+    for (int q = lane; q < cnt * VEC; q += 64) {
+        const int32_t slot = s_slot[q / VEC];
+        if (slot >= 0) *reinterpret_cast<uint4 *>(ring + (int64_t)slot * PITCHB + (q % VEC) * 16) = lv[q];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_replay_scatter(ReplayAppendArgs A)
+{
+    __shared__ uint32_t s_src[image_words<kObs>()];
+    __shared__ __attribute__((aligned(16))) uint32_t s_dst[kTile * kReplayObsPitch / 4];
+    __shared__ int32_t s_slot[kTile];
+    __shared__ uint8_t s_from[kTile];
+    const int lane = threadIdx.x;
+    const uint64_t *ballots = A.ws + kReplayWsHead, *bases = A.ws + kReplayWsHead + A.chunks;
+    const uint64_t T0 = A.ws[0], K = A.ws[1];
+    for (int64_t c = blockIdx.x; c < A.chunks; c += gridDim.x) {
+        const uint64_t votes = ballots[c];
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)votes), hi = __builtin_amdgcn_readfirstlane((uint32_t)(votes >> 32));
+        const int cnt = __popc(lo) + __popc(hi);
+        if (cnt == 0) continue;
+        const uint64_t R0 = bases[c];
+        if (!replay_kept(R0 + (uint64_t)(cnt - 1), K, A.capacity)) continue;  // (the whole chunk lies under the cut)
+        const int64_t t = 1 + c / A.ntiles, tile = c % A.ntiles;
+        const int64_t left = A.n - tile * kTile, at0 = t * A.ply_stride + tile * A.tile_stride, prev0 = at0 - A.ply_stride;
+        const int rows = left < kTile ? (int)left : kTile;
+        const bool ok = ((lane < 32 ? lo : hi) >> (lane & 31)) & 1u;
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+        int8_t z = 0, mv = 0;
+        if (ok) {
+            z = A.z[at0 + lane];
+            mv = (int8_t)(A.mover[at0 + lane] != 0);
+            s_from[rank] = (uint8_t)lane;
+        }
+        if (lane < cnt) {
+            const uint64_t R = R0 + (uint64_t)lane;
+            s_slot[lane] = replay_kept(R, K, A.capacity) ? (int32_t)replay_slot(T0, R, A.capacity) : -1;
+        }
+        wave_lds_fence();
+        if (A.ring_obs) {
+            tile_in<kObs>(A.obs + prev0 * kObs, s_src, lane, rows);
+            wave_lds_fence();
+            replay_pack<kObs, kReplayObsPitch>(s_src, s_dst, s_from, cnt, lane);
+            wave_lds_fence();
+            replay_store<kReplayObsPitch>(A.ring_obs, s_dst, s_slot, cnt, lane);
+            wave_lds_fence();
+        }
+        tile_in<2 * kActions>(reinterpret_cast<const int8_t *>(A.visits) + at0 * (2 * kActions), s_src, lane, rows);
+        wave_lds_fence();
+        replay_pack<2 * kActions, 2 * kReplayVisitsPitch>(s_src, s_dst, s_from, cnt, lane);
+        wave_lds_fence();
+        replay_store<2 * kReplayVisitsPitch>(reinterpret_cast<int8_t *>(A.ring_visits), s_dst, s_slot, cnt, lane);
+        wave_lds_fence();
+        tile_in<kActions>(A.mask + prev0 * kActions, s_src, lane, rows);
+        wave_lds_fence();
+        replay_pack<kActions, kReplayMetaPitch>(s_src, s_dst, s_from, cnt, lane);
+        wave_lds_fence();
+        if (ok) {  // the row's own scalars, over the zeros the pack left behind the mask
+            int8_t *row = reinterpret_cast<int8_t *>(s_dst) + rank * kReplayMetaPitch;
+            row[kReplayMetaZ] = z;
+            row[kReplayMetaMover] = mv;
+            s_dst[(rank * kReplayMetaPitch + kReplayMetaTag) / 4] = (uint32_t)A.tag;
+        }
+        wave_lds_fence();
+        replay_store<kReplayMetaPitch>(A.ring_meta, s_dst, s_slot, cnt, lane);
+        wave_lds_fence();  // (the next chunk rebuilds s_from, s_slot and the images)
+    }
+}
+
+// gbl_replay_batch: k_training_batch with a one-shot phase 1 -- lane l draws sample l's slot from the ring's state (no attempt loop:
+// every live row is a sample) and reads the row's z, mover and tag as one 16-byte vector of its meta row -- and the same phases 2 and 3
+// (batch_rows) over the ring's pitches: a sample's three source rows are one 128-byte line each (the meta row half of one).
+struct ReplayBatchArgs {
+    const int8_t *ring_obs;
+    const int16_t *ring_visits;
+    const int8_t *ring_meta;
+    const uint64_t *state;
+    int8_t *obs_out, *mask_out;
+    int16_t *visits_out;
+    int8_t *z_out;
+    int32_t *index_out;
+    int16_t *sym_out;
+    int64_t batch, ntiles, recent;
+    uint64_t capacity, seed, sample_base;
+    uint32_t call, sym_mask;
+};
+
+__global__ __launch_bounds__(64) void k_replay_batch(ReplayBatchArgs A)
+{
+    __shared__ uint32_t s_img[image_words<kObs>()];
+    __shared__ int64_t s_row[kTile];
+    __shared__ uint64_t s_inv[kTile];
+    __shared__ uint32_t s_sw[kTile];  // swap bits | mover << 6
+    Lane L;
+    if (!lane_setup(L, A.batch, A.ntiles)) return;
+    ReplayDraw d{-1, 0u};
+    if (L.valid) d = replay_draw(A.seed, A.sample_base + (uint64_t)L.b, A.call, A.state[0], A.capacity, A.recent);
+    const bool ok = d.slot >= 0;
+    const uint32_t code = ok ? d.sym & A.sym_mask : 0u;
+    const Sym S = sym_of(code);
+    uint4 tail{0u, 0u, 0u, 0u};  // bytes 48 .. 63 of the meta row: z and the mover in .y's upper half, the tag in .z
+    if (ok) tail = *reinterpret_cast<const uint4 *>(A.ring_meta + d.slot * kReplayMetaPitch + 48);
+    const uint32_t m = (tail.y >> 24) != 0u;
+    if (L.valid) {
+        A.index_out[2 * L.b] = ok ? (int32_t)d.slot : -1;  // (two dword stores: index_out is only 4-byte aligned)
+        A.index_out[2 * L.b + 1] = ok ? (int32_t)tail.z : -1;
+        if (A.z_out) A.z_out[L.b] = ok ? (int8_t)(tail.y >> 16) : (int8_t)kZOpen;
+        if (A.sym_out) A.sym_out[L.b] = (int16_t)code;
+    }
+    s_row[L.lane] = d.slot; s_inv[L.lane] = S.inv; s_sw[L.lane] = S.swaps | (m << 6);
+    wave_lds_fence();
+    batch_rows<kReplayObsPitch, kReplayMetaPitch, kReplayVisitsPitch>(A.ring_obs, A.ring_meta, A.ring_visits, A.obs_out, A.mask_out,
+                                                                      A.visits_out, s_img, s_row, s_row, s_inv, s_sw, L);
 }
 
 // gbl_train_step: the float trainer's Adam step in two launches, bit-defined by the header (every float operation below is the
@@ -4584,6 +4806,55 @@ int gbl_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const in
                       n, ply_stride, tile_stride, batch, g.ntiles, seed, sample_base, plies, call, (uint32_t)sym_mask};
     hipLaunchKernelGGL(k_training_batch, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
     GBL_LAUNCHED("gbl_training_batch");
+}
+
+size_t gbl_replay_workspace_bytes(int64_t n, uint32_t plies) { return (size_t)replay_workspace_bytes(n, plies); }
+
+int gbl_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                      const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                      int64_t tile_stride, int32_t tag, int8_t *ring_obs, int16_t *ring_visits, int8_t *ring_meta, int64_t capacity,
+                      uint64_t *ring_state, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (const char *why = replay_append_error(obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, n, plies, ply_stride,
+                                              tile_stride, ring_obs, ring_visits, ring_meta, capacity, ring_state, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    if ((reinterpret_cast<uintptr_t>(ring_obs) | reinterpret_cast<uintptr_t>(ring_visits) | reinterpret_cast<uintptr_t>(ring_meta)) & 127u)
+        return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
+    GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(workspace, "workspace");
+    GBL_ALIGNED(obs_traj, "obs_traj"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(visits_traj, "visits_traj");
+    const int64_t ntiles = (n + kTile - 1) / kTile, chunks = replay_chunks(n, plies);
+    const ReplayAppendArgs A{obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, ring_obs, ring_visits, ring_meta, ring_state,
+                             static_cast<uint64_t *>(workspace), n, ply_stride, tile_stride, ntiles, chunks, (uint64_t)capacity, tag};
+    const dim3 grid((uint32_t)std::min<int64_t>(chunks, kReplayMaxGrid));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_replay_count, grid, dim3(64), 0, s, A);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_append");
+    hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(kReplayScanThreads), 0, s, A);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_append");
+    hipLaunchKernelGGL(k_replay_scatter, grid, dim3(64), 0, s, A);
+    GBL_LAUNCHED("gbl_replay_append");
+}
+
+int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                     const uint64_t *ring_state, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
+                     uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
+                     int16_t *sym_out, void *stream)
+{
+    if (const char *why = replay_batch_error(ring_obs, ring_visits, ring_meta, capacity, ring_state, recent, batch, sym_mask, call, obs_out,
+                                             index_out))
+        return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    if ((reinterpret_cast<uintptr_t>(ring_obs) | reinterpret_cast<uintptr_t>(ring_visits) | reinterpret_cast<uintptr_t>(ring_meta)) & 127u)
+        return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
+    GBL_ALIGNED(ring_state, "ring_state");
+    GBL_ALIGNED(obs_out, "obs_out"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_out, "visits_out");
+    if (reinterpret_cast<uintptr_t>(index_out) & 3u) return fail(GBL_ERR_ALIGN, "index_out must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sym_out) & 1u) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
+    const Geometry g = geometry(batch);
+    const ReplayBatchArgs A{ring_obs, ring_visits, ring_meta, ring_state, obs_out, mask_out, visits_out, z_out, index_out, sym_out,
+                            batch, g.ntiles, recent, (uint64_t)capacity, seed, sample_base, call, (uint32_t)sym_mask};
+    hipLaunchKernelGGL(k_replay_batch, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_replay_batch");
 }
 
 int64_t gbl_train_workspace_bytes(int64_t batch, int hidden) { return train_workspace_bytes(batch, hidden); }

@@ -8,7 +8,9 @@
  *   - all pointers are HOST pointers; the `stream` argument is ignored (calls are synchronous) and no alignment is asked of buffers;
  *   - the *_at forms read *ply_dev / *call_dev from host memory; `counters` accumulates into its first stripe;
  *   - the device-memory helpers (gbl_pinned_alloc / _free, gbl_block_alloc / _free, gbl_device_memory, gbl_placement_probe,
- *     gbl_collect_variant) have no host flavour; gbl_train_workspace_bytes is the same function for both (it launches nothing);
+ *     gbl_collect_variant) have no host flavour; gbl_train_workspace_bytes and gbl_replay_workspace_bytes are the same functions for both (they
+ *     launch nothing);
+ *   - gbl_cpu_replay_append checks its workspace like the device flavour and does not use it; ring_state is host memory;
  *   - gbl_cpu_set_threads(t): boards are dealt over t std::threads (0 = the hardware's; the library reads no environment).
  * It is a flavour a caller ASKS for (device="cpu" in the Python layer; BASELINE config 1 "on CPU"), never a fallback of the HIP
  * path, and it is test-independent of oracle/: tests/test_cpu_twin.py compares it with the oracle like the GPU tests do. */
@@ -151,6 +153,14 @@ int gbl_cpu_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, cons
 int gbl_cpu_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
                        float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
                        void *workspace, int64_t workspace_bytes, void *stream);
+int gbl_cpu_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                          const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                          int64_t tile_stride, int32_t tag, int8_t *ring_obs, int16_t *ring_visits, int8_t *ring_meta, int64_t capacity,
+                          uint64_t *ring_state, void *workspace, size_t workspace_bytes, void *stream);
+int gbl_cpu_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                         const uint64_t *ring_state, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
+                         uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
+                         int16_t *sym_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@
 #ifndef GOBBLET_HIP_H
 #define GOBBLET_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -768,6 +769,65 @@ int64_t gbl_train_workspace_bytes(int64_t batch, int hidden);
 int gbl_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
                    float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
                    void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Replay buffer (no counterpart in the reference: the memory of an AlphaZero-style loop across collected windows).  A ring of
+ * `capacity` compacted training rows in device memory, 1 <= capacity <= 2^31 - 1, in three arrays whose rows are whole 128-byte
+ * lines (or half of one), so that a drawn row costs one line per array:
+ *   ring_obs    int8 [capacity][GBL_REPLAY_OBS_PITCH]     bytes 0 .. 116: obs_traj[cell(t - 1, b)], what the mover saw; 117 .. 127: zero.
+ *                                                         Optional: NULL is a buffer without observations.
+ *   ring_visits int16[capacity][GBL_REPLAY_VISITS_PITCH]  elements 0 .. 53: visits_traj[cell(t, b)]; 54 .. 63: zero.
+ *   ring_meta   int8 [capacity][GBL_REPLAY_META_PITCH]    bytes 0 .. 53: mask_traj[cell(t - 1, b)]; byte GBL_REPLAY_META_Z: z_traj[cell(t, b)];
+ *                                                         byte GBL_REPLAY_META_MOVER: 1 where mover_traj[cell(t, b)] is non-zero, else 0;
+ *                                                         bytes GBL_REPLAY_META_TAG .. + 3: tag, int32 little endian; 60 .. 63: zero.
+ *   ring_state  uint64[2] in device memory.  state[0] = the number of rows ever appended: the newest row is in slot
+ *     (state[0] - 1) mod capacity and the buffer holds live = min(state[0], capacity) rows.  state[1] = the number of rows the last
+ *     append added (its K below).  A fresh buffer is all zeros.  The counters live on the device: append and draw never wait for the
+ *     host, the stream alone orders them.
+ * The three ring arrays must be 128-byte aligned, ring_state and the workspace 16-byte (GBL_ERR_ALIGN).
+ *
+ * gbl_replay_append: the valid cells of a window (exactly gbl_training_batch's valid cells, window arguments as there, both layouts),
+ * enumerated in ascending (t, b), t outer; K their number, r = 0 .. K - 1 the rank of a cell.  With T0 = state[0] before the call the
+ * cell of rank r goes to slot (T0 + r) mod capacity; ranks r < K - capacity are not written at all (a window that alone overflows
+ * the ring leaves its last `capacity` rows); afterwards state = (T0 + K, K).  Padding bytes are written as zero -- a ring is
+ * comparable byte for byte -- and nothing outside the written slots is touched.  Three launches on the caller's stream, no atomics and
+ * no waiting between workgroups: a count (one wavefront per chunk = the 64 boards of one tile at one ply, (plies - 1) * ceil(n / 64)
+ * chunks, a ballot each), an exclusive scan of the chunk counts by one workgroup, which also writes the new state, and a scatter (one
+ * wavefront per chunk closes its valid rows up and stores them as whole 16-byte vectors).  Ranks are 64-bit.
+ *   Workspace.  The caller supplies gbl_replay_workspace_bytes bytes: 32 + 16 per chunk (T0 and K, and per chunk its ballot and the
+ *     rank of its first valid cell); that function returns 0 for n outside [1, 2^31] or plies outside [2, 32767] and launches nothing.
+ *   Argument errors (GBL_ERR_ARG): plies outside [2, 32767], n outside [1, 2^31], capacity out of range, a missing pointer (all but
+ *     obs_traj and ring_obs are required), ring_obs without obs_traj or obs_traj without ring_obs, gbl_collect's stride rules, a
+ *     workspace_bytes that is too small.  GBL_ERR_ALIGN: the rules above, and obs_traj / mask_traj / visits_traj 16-byte aligned (whole
+ *     tiles are read as 16-byte vectors).
+ *
+ * gbl_replay_batch: `batch` rows drawn exactly uniformly from the newest rows of the ring, each under a random symmetry.  Sample j:
+ *   (w0, w1, w2, w3) = the block Philox4x32-10(ctr = (id_lo, id_hi, 16 call, 7), key = (seed_lo, seed_hi)) with id = sample_base + j --
+ *     the generator of gbl_training_batch's attempt 0 on stream 7; there is no attempt loop.  call < 2^26.
+ *   live = min(state[0], capacity);  span = recent > 0 ? min(recent, live) : live;  age = (w0 * span) >> 32 -- uniform over the span up
+ *     to the multiplication's bias: no age is more likely than another by more than span / 2^32;
+ *   slot = (state[0] - 1 - age) mod capacity -- `recent` means the newest `recent` rows --;  s = w2 & sym_mask.
+ *   Outputs as gbl_training_batch's (dtypes, shapes, alignment rules; all optional but index_out): the images under s of the row's
+ *     observation (needs ring_obs), mask and visits with the row's mover as the agent, z_out = the row's z, index_out[j] = (slot, tag),
+ *     sym_out = s.  With live == 0 every sample is gbl_training_batch's failed sample: zero rows, z = GBL_Z_OPEN, index (-1, -1), sym 0.
+ *   The draw of sample j depends on (seed, sample_base + j, call), recent and the ring's state alone: not on batch, not on the launch.
+ *   Argument errors (GBL_ERR_ARG): capacity out of range, batch < 0 or > 2^31, sym_mask outside [0, 511], call >= 2^26, recent < 0, and
+ *     with batch > 0: a missing ring_visits, ring_meta, ring_state or index_out, obs_out without ring_obs.  batch == 0 returns GBL_OK
+ *     after the scalar checks.  One launch, one wavefront per 64 samples; allocates nothing, no atomics. */
+#define GBL_REPLAY_OBS_PITCH 128   /* bytes per ring_obs row */
+#define GBL_REPLAY_VISITS_PITCH 64 /* int16 elements per ring_visits row (128 bytes) */
+#define GBL_REPLAY_META_PITCH 64   /* bytes per ring_meta row */
+#define GBL_REPLAY_META_Z 54
+#define GBL_REPLAY_META_MOVER 55
+#define GBL_REPLAY_META_TAG 56
+size_t gbl_replay_workspace_bytes(int64_t n, uint32_t plies);
+int gbl_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
+                      const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
+                      int64_t tile_stride, int32_t tag, int8_t *ring_obs, int16_t *ring_visits, int8_t *ring_meta, int64_t capacity,
+                      uint64_t *ring_state, void *workspace, size_t workspace_bytes, void *stream);
+int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                     const uint64_t *ring_state, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
+                     uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
+                     int16_t *sym_out, void *stream);
 
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.

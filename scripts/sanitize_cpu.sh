@@ -10,6 +10,10 @@ g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -Wno-
     -o $T/emu.so tests/emu/emu_device.cpp
 g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -Wno-unknown-pragmas -Wno-attributes -shared -fPIC -pthread \
     -o $T/cpu.so gobblet-rl_amd/csrc/gobblet_cpu.cpp
+# the replay buffer's host entry points as a stand-alone program (nothing of it is loaded into python)
+g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wno-unknown-pragmas -Wno-attributes \
+    -pthread -o $T/replay_main scripts/sanitize_replay_main.cpp gobblet-rl_amd/csrc/gobblet_cpu.cpp
+$T/replay_main
 python -c "import oracle; oracle.lib(); from tests import emu; emu.lib(); import gobblet_rl_amd as G; G._native.build_cpu()"   # make sure the normal builds exist
 C=gobblet-rl_amd/csrc/libgobblet_cpu.so
 cp oracle/libgobblet_oracle.so $T/oracle.bak; cp tests/emu/libgobblet_emu.so $T/emu.bak; cp $C $T/cpu.bak
