@@ -12,6 +12,7 @@
     SolverGobbletPolicy  the exact bounded-depth solver: proven wins and losses per action, optionally over another policy
     GobbletTrainer   the float network behind GobbletEvaluator.from_float and its Adam step on the device (BatchedGobblet.fit)
     ReplayBuffer     a ring of compacted training rows on the device: windows appended, exact symmetry-augmented draws, fit
+    Tablebase        the game solved outright, one byte per position: retrograde sweeps and probes; TablebaseGobbletPolicy plays from it
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in
 ``include/gobblet_hip.h``); there is no CPU fallback.  Importing this package needs torch;
@@ -30,6 +31,7 @@ from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator
 from .solver_policy import SolverGobbletPolicy  # noqa: F401
 from .trainer import GobbletTrainer  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401
+from .tablebase import Tablebase, TablebaseGobbletPolicy  # noqa: F401
 from .random_policy import RandomAdmissiblePolicy  # noqa: F401
 from .symmetry import N_SYMMETRIES  # noqa: F401
 from .sharding import make_shard, reduce_counters, shard_bounds  # noqa: F401

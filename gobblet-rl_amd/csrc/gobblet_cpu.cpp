@@ -1370,6 +1370,117 @@ int gbl_cpu_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, con
     return GBL_OK;
 }
 
+// The tablebase (include/gobblet_hip.h, "Exact tablebase"): the header's rule position by position, with the shared pieces of
+// gobblet_device.h.  aux, table and decided are host memory.
+int gbl_cpu_tb_prepare(const int32_t *inventory, void *aux, void *)
+{
+    if (const char *why = tb_inventory_error(inventory)) return fail(GBL_ERR_ARG, why);
+    if (!aux) return fail(GBL_ERR_ARG, "aux must not be NULL");
+    uint8_t *b = static_cast<uint8_t *>(aux);
+    memset(b, 0, kTbAuxBytes);
+    uint16_t *rank2 = reinterpret_cast<uint16_t *>(b + kTbAuxRank2), *inv2 = reinterpret_cast<uint16_t *>(b + kTbAuxInv2),
+             *inv1 = reinterpret_cast<uint16_t *>(b + kTbAuxInv1), *tern = reinterpret_cast<uint16_t *>(b + kTbAuxTern);
+    uint8_t *rank1 = b + kTbAuxRank1;
+    uint32_t n2 = 0, n1 = 0;
+    for (uint32_t t = 0; t < kTbTernary; ++t) {
+        const uint32_t f = tb_admissible(t);
+        rank2[t] = (f & 1u) ? (uint16_t)n2 : (uint16_t)0xFFFFu;
+        rank1[t] = (f >> 16) ? (uint8_t)n1 : (uint8_t)0xFFu;
+        if (f & 1u) inv2[n2++] = (uint16_t)t;
+        if (f >> 16) inv1[n1++] = (uint16_t)t;
+    }
+    for (uint32_t cells = 0; cells < 512u; ++cells) tern[cells] = (uint16_t)tb_tern_of(cells);
+    return GBL_OK;
+}
+
+int gbl_cpu_tb_sweep(const int32_t *inventory, const void *aux, const int8_t *table, int8_t *out, int64_t first, int64_t count, int k,
+                     uint64_t *decided, void *)
+{
+    if (const char *why = tb_sweep_error(inventory, aux, table, out, first, count, k, decided)) return fail(GBL_ERR_ARG, why);
+    if (count == 0) return GBL_OK;
+    const TbAux A = tb_aux(aux);
+    const TbShape S = tb_shape(inventory);
+    std::atomic<uint64_t> wrote{0};
+    std::atomic<uint64_t> *const total = &wrote;
+    parallel_for(count, [=](int64_t j0, int64_t j1) {
+        uint64_t mine = 0;
+        for (int64_t j = j0; j < j1; ++j) {
+            if (k > 0 && out[j] != 0) continue;
+            const TbPos p = tb_position_of(A, S, (uint32_t)(first + j));
+            const int v = k == 0 ? (tb_winner(p.own, p.oth) != 0 ? kTbTerminal : 0) : tb_sweep_value(A, S, p, k, table);
+            if (k == 0) out[j] = (int8_t)v;
+            else if (v == k || v == -k) out[j] = (int8_t)v;
+            else continue;
+            mine += v != 0;
+        }
+        total->fetch_add(mine);
+    });
+    *decided += wrote.load();
+    return GBL_OK;
+}
+
+int gbl_cpu_tb_index(const int32_t *inventory, const void *aux, const int8_t *state, const int8_t *to_move, int64_t *index_out, int64_t n,
+                     void *)
+{
+    if (const char *why = tb_rows_error(inventory, aux, n, state, "state must not be NULL", to_move, "to_move must not be NULL", index_out,
+                                        "index_out must not be NULL"))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    const TbAux A = tb_aux(aux);
+    const TbShape S = tb_shape(inventory);
+    parallel_for(n, [=](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) {
+            uint32_t r[7];
+            load_row(state, b, r);
+            index_out[b] = tb_board_index(A, S, make_planes(r), to_move[b] != 0);
+        }
+    });
+    return GBL_OK;
+}
+
+int gbl_cpu_tb_position(const int32_t *inventory, const void *aux, const int64_t *index, int8_t *state_out, int64_t n, void *)
+{
+    if (const char *why = tb_rows_error(inventory, aux, n, index, "index must not be NULL", state_out, "state_out must not be NULL", state_out, ""))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    const TbAux A = tb_aux(aux);
+    const TbShape S = tb_shape(inventory);
+    parallel_for(n, [=](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) tb_row_of(A, S, index[b], state_out + b * kCells);
+    });
+    return GBL_OK;
+}
+
+int gbl_cpu_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *state, const int8_t *to_move,
+                     const int8_t *mask, int8_t *outcome_out, int8_t *value_out, int32_t *action_out, int64_t n, void *)
+{
+    if (const char *why = tb_rows_error(inventory, aux, n, table, "table must not be NULL", state, "state must not be NULL", to_move,
+                                        "to_move must not be NULL"))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    if (reinterpret_cast<uintptr_t>(action_out) & 3u) return fail(GBL_ERR_ALIGN, "action_out must be 4-byte aligned");
+    const TbAux A = tb_aux(aux);
+    const TbShape S = tb_shape(inventory);
+    parallel_for(n, [=](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) {
+            const HostRoot R = host_root(state, to_move, mask, b);
+            const uint64_t cand = tb_board_index(A, S, R.p, R.mover) < 0 ? 0ull : R.cand & tb_piece_actions(S);
+            uint32_t best = 0;
+            for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+                int c = kSolveNone;
+                if ((cand >> a) & 1ull) {
+                    c = tb_probe_action(A, S, table, R.p, R.mover, a);
+                    best = std::max(best, tb_action_key(c, a));
+                }
+                if (outcome_out) outcome_out[b * kActions + a] = (int8_t)c;
+            }
+            if (value_out) value_out[b] = (int8_t)tb_value_of(best);
+            if (action_out) action_out[b] = tb_action_of(best);
+        }
+    });
+    return GBL_OK;
+}
+
 }  // extern "C"
 
 // gbl_cpu_train_step: the header's rule row by row and element by element -- the same scalar pieces (gobblet_device.h: train_exp,

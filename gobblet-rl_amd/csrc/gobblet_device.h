@@ -2890,6 +2890,276 @@ inline const char *replay_batch_error(const void *ring_obs, const void *ring_vis
     return nullptr;
 }
 
+// ---- tablebase (include/gobblet_hip.h, "Exact tablebase"): the rule's pieces, shared by the kernels and the host flavour ---------------
+// A position is two 27-bit cell sets, the mover's (`own`) and the other side's (`oth`), level k in bits 9k .. 9k + 8.  Its index comes
+// from three table look-ups (one per level: the rank of the level's ternary number), its successors from bit arithmetic on the
+// two sets; only the level a piece moves on changes its code, so a successor's index costs ONE look-up.
+constexpr int kTbTerminal = -128;       // GBL_TB_TERMINAL
+constexpr int kTbMaxSweep = 126;        // GBL_TB_MAX_SWEEP
+constexpr uint32_t kTbTernary = 19683;  // 3^9 level configurations
+constexpr uint32_t kTbLevels2 = 1423, kTbLevels1 = 91;
+// `aux` in bytes: rank2 uint16[19683] | inv2 uint16[1423] | inv1 uint16[91] | tern uint16[512] | rank1 uint8[19683], each on a 4-byte boundary
+constexpr uint32_t kTbAuxRank2 = 0, kTbAuxInv2 = 39368, kTbAuxInv1 = 42216, kTbAuxTern = 42400, kTbAuxRank1 = 43424;
+constexpr uint32_t kTbAuxBytes = 63120;  // GBL_TB_AUX_BYTES
+constexpr uint32_t kTbNoRank = 0xFFFFFFFFu;
+
+struct TbAux {
+    const uint16_t *rank2, *inv2, *inv1, *tern;
+    const uint8_t *rank1;
+};
+__device__ __forceinline__ TbAux tb_aux(const void *base)
+{
+    const uint8_t *b = static_cast<const uint8_t *>(base);
+    return TbAux{reinterpret_cast<const uint16_t *>(b + kTbAuxRank2), reinterpret_cast<const uint16_t *>(b + kTbAuxInv2),
+                 reinterpret_cast<const uint16_t *>(b + kTbAuxInv1), reinterpret_cast<const uint16_t *>(b + kTbAuxTern), b + kTbAuxRank1};
+}
+
+// the inventory as the kernels take it: c_k, L_k and the index strides (all below 2^32: 1 423^3 = 2 881 473 967)
+struct TbShape {
+    uint32_t c[3], L[3];
+    uint64_t positions;
+};
+inline uint32_t tb_levels(int c) { return c == 0 ? 1u : (c == 1 ? kTbLevels1 : kTbLevels2); }
+inline TbShape tb_shape(const int32_t *inventory)
+{
+    TbShape S;
+    for (int k = 0; k < 3; ++k) {
+        S.c[k] = (uint32_t)inventory[k];
+        S.L[k] = tb_levels(inventory[k]);
+    }
+    S.positions = (uint64_t)S.L[0] * S.L[1] * S.L[2];
+    return S;
+}
+
+// what a ternary level number is worth to the two rank tables: bit 0 = admissible for c = 2, bit 16 = for c = 1 (packed for the scan)
+__device__ __forceinline__ uint32_t tb_admissible(uint32_t t)
+{
+    uint32_t n1 = 0, n2 = 0;
+#pragma unroll
+    for (int pos = 0; pos < 9; ++pos) {
+        const uint32_t d = t % 3u;
+        t /= 3u;
+        n1 += d == 1u;
+        n2 += d == 2u;
+    }
+    return (uint32_t)(n1 <= 2u && n2 <= 2u) | ((uint32_t)(n1 <= 1u && n2 <= 1u) << 16);
+}
+__device__ __forceinline__ uint32_t tb_tern_of(uint32_t cells)  // sum of 3^pos over a 9-bit cell set
+{
+    uint32_t t = 0, w = 1;
+#pragma unroll
+    for (int pos = 0; pos < 9; ++pos, w *= 3u) t += ((cells >> pos) & 1u) * w;
+    return t;
+}
+
+// code of one level (kTbNoRank: more cells of a colour than c) and back
+__device__ __forceinline__ uint32_t tb_code(const TbAux &A, uint32_t c, uint32_t own9, uint32_t oth9)
+{
+    const uint32_t t = (uint32_t)A.tern[own9] + 2u * (uint32_t)A.tern[oth9];
+    if (c == 2u) {
+        const uint32_t r = A.rank2[t];
+        return r == 0xFFFFu ? kTbNoRank : r;
+    }
+    if (c == 1u) {
+        const uint32_t r = A.rank1[t];
+        return r == 0xFFu ? kTbNoRank : r;
+    }
+    return t == 0u ? 0u : kTbNoRank;
+}
+struct TbPos {
+    uint32_t own, oth;
+};
+__device__ __forceinline__ void tb_level_cells(const TbAux &A, uint32_t c, uint32_t code, int level, TbPos &p)
+{
+    uint32_t t = c == 2u ? A.inv2[code] : (c == 1u ? A.inv1[code] : 0u);
+#pragma unroll
+    for (int pos = 0; pos < 9; ++pos) {
+        const uint32_t d = t % 3u;
+        t /= 3u;
+        p.own |= (uint32_t)(d == 1u) << (9 * level + pos);
+        p.oth |= (uint32_t)(d == 2u) << (9 * level + pos);
+    }
+}
+__device__ __forceinline__ TbPos tb_position_of(const TbAux &A, const TbShape &S, uint32_t index)
+{
+    TbPos p{0u, 0u};
+    const uint32_t upper = index / S.L[0];
+    tb_level_cells(A, S.c[0], index - upper * S.L[0], 0, p);
+    const uint32_t top = upper / S.L[1];
+    tb_level_cells(A, S.c[1], upper - top * S.L[1], 1, p);
+    tb_level_cells(A, S.c[2], top, 2, p);
+    return p;
+}
+// the index of (own, oth), or -1
+__device__ __forceinline__ int64_t tb_index_of(const TbAux &A, const TbShape &S, const TbPos &p)
+{
+    const uint32_t c0 = tb_code(A, S.c[0], p.own & 0x1FFu, p.oth & 0x1FFu), c1 = tb_code(A, S.c[1], (p.own >> 9) & 0x1FFu, (p.oth >> 9) & 0x1FFu),
+                   c2 = tb_code(A, S.c[2], (p.own >> 18) & 0x1FFu, (p.oth >> 18) & 0x1FFu);
+    if ((c0 | c1 | c2) == kTbNoRank) return -1;  // (a code is below 1 423: only kTbNoRank sets every bit)
+    return (int64_t)(((uint64_t)c2 * S.L[1] + c1) * S.L[0] + c0);
+}
+// check_for_winner() of (own, oth): +1 the mover's colour, -1 the other, 0 no line (a line cannot match both colours)
+__device__ __forceinline__ int tb_winner(uint32_t own, uint32_t oth)
+{
+    return winner_from_matches(line_matches_of(own, own | oth), line_matches_of(oth, own | oth));
+}
+
+// the header's rank on results up to +-126, as an order key: 1 .. 255, 0 = no move yet (reads back as V = 0)
+__device__ __forceinline__ uint32_t tb_key(int c) { return (uint32_t)((c > 0 ? 128 - c : (c < 0 ? -128 - c : 0)) + 128); }
+__device__ __forceinline__ int tb_of_key(uint32_t key)
+{
+    const int r = (int)key - 128;
+    return key == 0u ? 0 : (r > 0 ? 128 - r : (r < 0 ? -128 - r : 0));
+}
+__device__ __forceinline__ uint32_t tb_action_key(int c, uint32_t a) { return (tb_key(c) << 6) | (63u - a); }
+__device__ __forceinline__ int tb_action_of(uint32_t best) { return best ? 63 - (int)(best & 63u) : -1; }
+__device__ __forceinline__ int tb_value_of(uint32_t best) { return tb_of_key(best >> 6); }
+// c(a) from the byte u of the position after a; `proven`: the largest |u| that counts (k - 1 in sweep k, 127 in a probe)
+__device__ __forceinline__ int tb_parent(int u, int proven)
+{
+    const int au = u < 0 ? -u : u;
+    return au >= 1 && au <= proven ? solve_parent(u) : 0;  // (GBL_TB_TERMINAL reads 128: never proven)
+}
+
+// Sweep k >= 1 at one position whose byte is still 0: V as the header defines it.  The moves: level after level, source after source
+// (bit 9 of `from` = the reserve), destination after destination.  A c(a) == k > 0 ends the walk: on the table of sweeps 0 .. k - 1
+// nothing of this position ranks above +k (a +j, j < k, would have been written in sweep j).
+__device__ __forceinline__ int tb_sweep_value(const TbAux &A, const TbShape &S, const TbPos &p, int k, const int8_t *table)
+{
+    const uint32_t stride[3] = {1u, S.L[0], S.L[0] * S.L[1]};
+    uint32_t swapped[3], total = 0;  // the level codes as the other side sees them
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        swapped[l] = tb_code(A, S.c[l], (p.oth >> (9 * l)) & 0x1FFu, (p.own >> (9 * l)) & 0x1FFu) * stride[l];
+        total += swapped[l];
+    }
+    const uint32_t occ = p.own | p.oth;
+    uint32_t best = 0;
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        if (S.c[l] == 0u) continue;
+        uint32_t above = 0;
+#pragma unroll
+        for (int j = l + 1; j < 3; ++j) above |= (occ >> (9 * j)) & 0x1FFu;
+        const uint32_t own_l = (p.own >> (9 * l)) & 0x1FFu;
+        const uint32_t dest = ~(above | (occ >> (9 * l))) & 0x1FFu;
+        if (!dest) continue;
+        const uint32_t from = (own_l & ~above) | ((uint32_t)__popc(own_l) < S.c[l] ? 0x200u : 0u);
+        const uint32_t base = total - swapped[l], oth_tern = A.tern[(p.oth >> (9 * l)) & 0x1FFu];
+        for (uint32_t f = from; f; f &= f - 1u) {
+            const uint32_t kept = own_l & ~(f & (0u - f));  // (the reserve's bit 9 clears nothing)
+            for (uint32_t d = dest; d; d &= d - 1u) {
+                const uint32_t now = kept | (d & (0u - d));
+                const int w = tb_winner((p.own & ~(0x1FFu << (9 * l))) | (now << (9 * l)), p.oth);
+                int c = w;
+                if (w == 0 && k > 1) {
+                    const uint32_t t = oth_tern + 2u * (uint32_t)A.tern[now];  // the level as the other side sees it: admissible by construction
+                    const uint32_t code = S.c[l] == 2u ? (uint32_t)A.rank2[t] : (uint32_t)A.rank1[t];
+                    c = tb_parent(table[base + code * stride[l]], k - 1);
+                }
+                if (c > 0 && c == k) return k;
+                const uint32_t key = tb_key(c);
+                best = key > best ? key : best;
+            }
+        }
+    }
+    return tb_of_key(best);
+}
+
+// a concrete board's planes as `viewer` (0 / 1) sees them, and whether it is a state of the inventory (only pieces that exist)
+__device__ __forceinline__ TbPos tb_view(const Planes &p, int viewer)
+{
+    const uint32_t pos = p.nz & ~p.neg & 0x7FFFFFFu, neg = p.nz & p.neg & 0x7FFFFFFu;
+    return viewer ? TbPos{neg, pos} : TbPos{pos, neg};
+}
+__device__ __forceinline__ bool tb_pieces_exist(const Planes &p, const TbShape &S)
+{
+    bool ok = true;
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        const uint32_t cells = (p.nz >> (9 * l)) & 0x1FFu, even = cells & ~(p.odd >> (9 * l));  // (piece 2l + 2 is the even one)
+        ok = ok && (S.c[l] == 2u || (S.c[l] == 1u ? even == 0u : cells == 0u));
+    }
+    return ok;
+}
+__device__ __forceinline__ int64_t tb_board_index(const TbAux &A, const TbShape &S, const Planes &p, int viewer)
+{
+    return tb_pieces_exist(p, S) ? tb_index_of(A, S, tb_view(p, viewer)) : -1;
+}
+// the actions of the pieces the inventory has: piece number 2l + 1 + j exists for j < c_l
+__device__ __forceinline__ uint64_t tb_piece_actions(const TbShape &S)
+{
+    uint64_t m = 0;
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+        for (uint32_t j = 0; j < S.c[l]; ++j) m |= 0x1FFull << (9u * (2u * (uint32_t)l + j));
+    return m;
+}
+// the probe's c(a) for a candidate a of `mover` on the concrete board p (a state of the inventory)
+__device__ __forceinline__ int tb_probe_action(const TbAux &A, const TbShape &S, const int8_t *table, const Planes &p, int mover, uint32_t a)
+{
+    Planes q = p;
+    move_planes(q, mover, a);
+    const int now = solve_now(winner_of(q), mover);
+    if (now != 0) return now;
+    const int64_t child = tb_index_of(A, S, tb_view(q, mover ^ 1));
+    return child < 0 ? 0 : tb_parent(table[child], 127);
+}
+// position `index` as a contract row with player_1 to move: own cells positive, the lowest piece number on the lowest cell
+__device__ __forceinline__ void tb_row_of(const TbAux &A, const TbShape &S, int64_t index, int8_t *row)
+{
+    if (index < 0 || (uint64_t)index >= S.positions) {
+        for (int i = 0; i < kCells; ++i) row[i] = (int8_t)kTbTerminal;
+        return;
+    }
+    const TbPos p = tb_position_of(A, S, (uint32_t)index);
+    for (int l = 0; l < 3; ++l) {
+        int own = 0, oth = 0;
+        for (int pos = 0; pos < 9; ++pos) {
+            const int cell = 9 * l + pos;
+            row[cell] = ((p.own >> cell) & 1u) ? (int8_t)(2 * l + 1 + own++) : (((p.oth >> cell) & 1u) ? (int8_t)-(2 * l + 1 + oth++) : (int8_t)0);
+        }
+    }
+}
+
+// Each *_error returns the message of the first rule the arguments break, or nullptr (all GBL_ERR_ARG; the device flavour's alignment
+// rules follow there)
+inline const char *tb_inventory_error(const int32_t *inventory)
+{
+    if (!inventory) return "inventory must not be NULL";
+    for (int k = 0; k < 3; ++k)
+        if (inventory[k] < 0 || inventory[k] > 2) return "inventory entries must be in [0, 2]";
+    return nullptr;
+}
+inline const char *tb_sweep_error(const int32_t *inventory, const void *aux, const void *table, const void *out, int64_t first, int64_t count,
+                                  int k, const void *decided)
+{
+    if (const char *why = tb_inventory_error(inventory)) return why;
+    if (k < 0 || k > kTbMaxSweep) return "k must be in [0, 126]";
+    const uint64_t positions = tb_shape(inventory).positions;
+    if (first < 0 || count < 0 || (uint64_t)first > positions || (uint64_t)count > positions - (uint64_t)first)
+        return "first / count must lie inside the universe";
+    if (count == 0) return nullptr;
+    if (!aux) return "aux must not be NULL";
+    if (!out) return "out must not be NULL";
+    if (!decided) return "decided must not be NULL";
+    if (k >= 2 && !table) return "table must not be NULL for k >= 2";
+    return nullptr;
+}
+// (n == 0 passes whatever the pointers are: the caller returns GBL_OK before using them)
+inline const char *tb_rows_error(const int32_t *inventory, const void *aux, int64_t n, const void *a, const char *a_msg, const void *b,
+                                 const char *b_msg, const void *c, const char *c_msg)
+{
+    if (const char *why = tb_inventory_error(inventory)) return why;
+    if (n < 0) return "n < 0";
+    if (n == 0) return nullptr;
+    if (!aux) return "aux must not be NULL";
+    if (!a) return a_msg;
+    if (!b) return b_msg;
+    if (!c) return c_msg;
+    return nullptr;
+}
+
 // ---- gbl_train_step (include/gobblet_hip.h, "One Adam step of the FLOAT network"): the scalar pieces of the bit-defined rule ----------
 // Shared by k_train_rows / k_train_reduce_adam and the host flavour.  Every function that does float arithmetic for the rule opens
 // with GBL_FP_STRICT, and so do the two kernels and the host flavour's own loops (train_row, train_sum, gbl_cpu_train_step): hipcc

@@ -2735,6 +2735,139 @@ __global__ __launch_bounds__(64) void k_replay_batch(ReplayBatchArgs A)
                                                                       A.visits_out, s_img, s_row, s_row, s_inv, s_sw, L);
 }
 
+// ---- tablebase (include/gobblet_hip.h, "Exact tablebase") ---------------------------------------------------------------------------
+// k_tb_prepare   one workgroup fills `aux`: every thread classifies a stretch of the 19 683 ternary level numbers, the workgroup scans
+//                the counts (both rank tables at once, packed into one word), every thread writes its stretch's ranks and inverses.
+// k_tb_sweep     one lane per position, grid-stride; the whole of `aux` (61.6 KB) in LDS, loaded once per workgroup.  A lane whose byte
+//                is already decided does nothing; the others walk their moves (tb_sweep_value): integer work that diverges from lane to
+//                lane and one byte load per quiet move from anywhere in the table.  Only bytes that change are stored.  The count of
+//                stores goes out as one atomic per wavefront.  Indices are below 2^32; the range counter and every offset are 64-bit.
+// k_tb_probe     one wavefront per board, lane a < 54 per action (board_planes / board_candidates as k_solve); the three look-ups of
+//                an action's successor go to `aux` in global memory (a board is too little work to stage 61.6 KB for).
+// k_tb_index / k_tb_position   one lane per board.
+constexpr int kTbThreads = 1024;
+constexpr int kTbSweepGroups = 512;
+constexpr int kTbPrepareSpan = (kTbTernary + kTbThreads - 1) / kTbThreads;  // level numbers per thread of k_tb_prepare
+
+__global__ __launch_bounds__(kTbThreads) void k_tb_prepare(uint8_t *aux)
+{
+    __shared__ uint32_t s_sum[2][kTbThreads];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t t0 = std::min(tid * (uint32_t)kTbPrepareSpan, kTbTernary), t1 = std::min(t0 + (uint32_t)kTbPrepareSpan, kTbTernary);
+    uint32_t mine = 0;
+    for (uint32_t t = t0; t < t1; ++t) mine += tb_admissible(t);
+    s_sum[0][tid] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < kTbThreads; d <<= 1) {  // (Hillis-Steele over the two halves of s_sum, as k_replay_scan; neither half-word carries: 1 423 and 91)
+        s_sum[cur ^ 1][tid] = s_sum[cur][tid] + (tid >= (uint32_t)d ? s_sum[cur][tid - d] : 0u);
+        __syncthreads();
+        cur ^= 1;
+    }
+    uint32_t base = s_sum[cur][tid] - mine;
+    uint16_t *rank2 = reinterpret_cast<uint16_t *>(aux + kTbAuxRank2), *inv2 = reinterpret_cast<uint16_t *>(aux + kTbAuxInv2),
+             *inv1 = reinterpret_cast<uint16_t *>(aux + kTbAuxInv1), *tern = reinterpret_cast<uint16_t *>(aux + kTbAuxTern);
+    uint8_t *rank1 = aux + kTbAuxRank1;
+    for (uint32_t t = t0; t < t1; ++t) {
+        const uint32_t f = tb_admissible(t), r2 = base & 0xFFFFu, r1 = base >> 16;
+        rank2[t] = (f & 1u) ? (uint16_t)r2 : (uint16_t)0xFFFFu;
+        rank1[t] = (f >> 16) ? (uint8_t)r1 : (uint8_t)0xFFu;
+        if (f & 1u) inv2[r2] = (uint16_t)t;
+        if (f >> 16) inv1[r1] = (uint16_t)t;
+        base += f;
+    }
+    if (tid < 512u) tern[tid] = (uint16_t)tb_tern_of(tid);
+    // the padding between the tables, so that `aux` is comparable byte for byte
+    if (tid == 0) {
+        rank2[kTbTernary] = 0; inv2[kTbLevels2] = 0; inv1[kTbLevels1] = 0;
+        for (uint32_t i = kTbAuxRank1 + kTbTernary; i < kTbAuxBytes; ++i) aux[i] = 0;
+    }
+}
+
+struct TbSweepArgs {
+    const uint32_t *aux;
+    const int8_t *table;
+    int8_t *out;  // (may alias table: no __restrict__ on either)
+    unsigned long long *decided;
+    uint64_t first, count;
+    TbShape S;
+    int k;
+};
+
+__global__ __launch_bounds__(kTbThreads) void k_tb_sweep(TbSweepArgs a)
+{
+    __shared__ uint32_t s_aux[kTbAuxBytes / 4];
+    for (uint32_t i = threadIdx.x; i < kTbAuxBytes / 4; i += kTbThreads) s_aux[i] = a.aux[i];
+    __syncthreads();
+    const TbAux A = tb_aux(s_aux);
+    const uint64_t step = (uint64_t)gridDim.x * kTbThreads;
+    uint32_t wrote = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * kTbThreads + threadIdx.x; j < a.count; j += step) {
+        if (a.k > 0 && a.out[j] != 0) continue;
+        const TbPos p = tb_position_of(A, a.S, (uint32_t)(a.first + j));
+        if (a.k == 0) {
+            const int v = tb_winner(p.own, p.oth) != 0 ? kTbTerminal : 0;
+            a.out[j] = (int8_t)v;
+            wrote += v != 0;
+        } else {
+            const int v = tb_sweep_value(A, a.S, p, a.k, a.table);
+            if (v == a.k || v == -a.k) {
+                a.out[j] = (int8_t)v;
+                ++wrote;
+            }
+        }
+    }
+    const uint32_t sum = wave_sum(wrote);
+    if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(a.decided, (unsigned long long)sum);
+}
+
+__global__ __launch_bounds__(64) void k_tb_probe(const uint8_t *__restrict__ aux, const int8_t *__restrict__ table, const int8_t *__restrict__ state,
+                                                 const int8_t *__restrict__ to_move, const int8_t *__restrict__ mask,
+                                                 int8_t *__restrict__ outcome_out, int8_t *__restrict__ value_out, int32_t *__restrict__ action_out,
+                                                 int64_t n, TbShape S)
+{
+    const TbAux A = tb_aux(aux);
+    const uint32_t lane = threadIdx.x;
+    const uint64_t pieces = tb_piece_actions(S);
+    for (int64_t b = blockIdx.x; b < n; b += gridDim.x) {
+        const Planes root = board_planes(state, b, lane);
+        const int mover = to_move[b] != 0;
+        uint64_t cand = board_candidates(root, mover, mask, b, lane) & pieces;
+        if (tb_board_index(A, S, root, mover) < 0) cand = 0;
+        const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
+        const int c = mine ? tb_probe_action(A, S, table, root, mover, lane) : kSolveNone;
+        const uint32_t best = wave_max(mine ? tb_action_key(c, lane) : 0u);
+        if (outcome_out && lane < (uint32_t)kActions) outcome_out[b * kActions + lane] = (int8_t)c;
+        if (lane == 0) {
+            if (value_out) value_out[b] = (int8_t)tb_value_of(best);
+            if (action_out) action_out[b] = tb_action_of(best);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tb_index(const uint8_t *__restrict__ aux, const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
+                                                  int64_t *__restrict__ index_out, int64_t n, TbShape S)
+{
+    const TbAux A = tb_aux(aux);
+    for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < n; b += (int64_t)gridDim.x * 256) {
+        Planes p{0u, 0u, 0u};
+        for (int cell = 0; cell < kCells; ++cell) {
+            const int v = state[b * kCells + cell];
+            p.nz |= (uint32_t)(v != 0) << cell;
+            p.neg |= (uint32_t)(v < 0) << cell;
+            p.odd |= (uint32_t)(v & 1) << cell;
+        }
+        index_out[b] = tb_board_index(A, S, p, to_move[b] != 0);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tb_position(const uint8_t *__restrict__ aux, const int64_t *__restrict__ index, int8_t *__restrict__ state_out,
+                                                     int64_t n, TbShape S)
+{
+    const TbAux A = tb_aux(aux);
+    for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < n; b += (int64_t)gridDim.x * 256) tb_row_of(A, S, index[b], state_out + b * kCells);
+}
+
 // gbl_train_step: the float trainer's Adam step in two launches, bit-defined by the header (every float operation below is the
 // header's, in its order; GBL_FP_STRICT keeps hipcc from fusing them).
 //   k_train_rows          one wavefront per row (four per workgroup, rows dealt grid-stride), w2 staged in LDS once per workgroup:
@@ -4855,6 +4988,84 @@ int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const i
                             batch, g.ntiles, recent, (uint64_t)capacity, seed, sample_base, call, (uint32_t)sym_mask};
     hipLaunchKernelGGL(k_replay_batch, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
     GBL_LAUNCHED("gbl_replay_batch");
+}
+
+int gbl_tb_layout(const int32_t *inventory, int64_t *out)
+{
+    if (const char *why = tb_inventory_error(inventory)) return fail(GBL_ERR_ARG, why);
+    GBL_NEED(out, "out");
+    const TbShape S = tb_shape(inventory);
+    out[0] = (int64_t)S.positions;
+    for (int k = 0; k < 3; ++k) out[1 + k] = S.L[k];
+    out[4] = kTbAuxBytes;
+    return GBL_OK;
+}
+
+int gbl_tb_prepare(const int32_t *inventory, void *aux, void *stream)
+{
+    if (const char *why = tb_inventory_error(inventory)) return fail(GBL_ERR_ARG, why);
+    GBL_NEED(aux, "aux");
+    GBL_ALIGNED(aux, "aux");
+    hipLaunchKernelGGL(k_tb_prepare, dim3(1), dim3(kTbThreads), 0, (hipStream_t)stream, static_cast<uint8_t *>(aux));
+    GBL_LAUNCHED("gbl_tb_prepare");
+}
+
+int gbl_tb_sweep(const int32_t *inventory, const void *aux, const int8_t *table, int8_t *out, int64_t first, int64_t count, int k,
+                 uint64_t *decided, void *stream)
+{
+    if (const char *why = tb_sweep_error(inventory, aux, table, out, first, count, k, decided)) return fail(GBL_ERR_ARG, why);
+    if (count == 0) return GBL_OK;
+    GBL_ALIGNED(aux, "aux");
+    if (reinterpret_cast<uintptr_t>(decided) & 7u) return fail(GBL_ERR_ALIGN, "decided must be 8-byte aligned");
+    const TbSweepArgs A{static_cast<const uint32_t *>(aux), table, out, reinterpret_cast<unsigned long long *>(decided), (uint64_t)first,
+                        (uint64_t)count, tb_shape(inventory), k};
+    // two workgroups per compute unit hold their tables at once (61.6 KB each of 160 KB): no more workgroups than that on 256 CUs, each striding
+    const int64_t groups = std::min<int64_t>((count + kTbThreads - 1) / kTbThreads, kTbSweepGroups);
+    hipLaunchKernelGGL(k_tb_sweep, dim3((uint32_t)groups), dim3(kTbThreads), 0, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_tb_sweep");
+}
+
+int gbl_tb_index(const int32_t *inventory, const void *aux, const int8_t *state, const int8_t *to_move, int64_t *index_out, int64_t n,
+                 void *stream)
+{
+    if (const char *why = tb_rows_error(inventory, aux, n, state, "state must not be NULL", to_move, "to_move must not be NULL", index_out,
+                                        "index_out must not be NULL"))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_ALIGNED(aux, "aux");
+    if (reinterpret_cast<uintptr_t>(index_out) & 7u) return fail(GBL_ERR_ALIGN, "index_out must be 8-byte aligned");
+    const int64_t groups = std::min<int64_t>((n + 255) / 256, (int64_t)1 << 20);
+    hipLaunchKernelGGL(k_tb_index, dim3((uint32_t)groups), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), state, to_move,
+                       index_out, n, tb_shape(inventory));
+    GBL_LAUNCHED("gbl_tb_index");
+}
+
+int gbl_tb_position(const int32_t *inventory, const void *aux, const int64_t *index, int8_t *state_out, int64_t n, void *stream)
+{
+    if (const char *why = tb_rows_error(inventory, aux, n, index, "index must not be NULL", state_out, "state_out must not be NULL", state_out, ""))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_ALIGNED(aux, "aux");
+    if (reinterpret_cast<uintptr_t>(index) & 7u) return fail(GBL_ERR_ALIGN, "index must be 8-byte aligned");
+    const int64_t groups = std::min<int64_t>((n + 255) / 256, (int64_t)1 << 20);
+    hipLaunchKernelGGL(k_tb_position, dim3((uint32_t)groups), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), index,
+                       state_out, n, tb_shape(inventory));
+    GBL_LAUNCHED("gbl_tb_position");
+}
+
+int gbl_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *state, const int8_t *to_move,
+                 const int8_t *mask, int8_t *outcome_out, int8_t *value_out, int32_t *action_out, int64_t n, void *stream)
+{
+    if (const char *why = tb_rows_error(inventory, aux, n, table, "table must not be NULL", state, "state must not be NULL", to_move,
+                                        "to_move must not be NULL"))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    GBL_ALIGNED(aux, "aux");
+    if (reinterpret_cast<uintptr_t>(action_out) & 3u) return fail(GBL_ERR_ALIGN, "action_out must be 4-byte aligned");
+    const int64_t groups = std::min<int64_t>(n, (int64_t)1 << 20);
+    hipLaunchKernelGGL(k_tb_probe, dim3((uint32_t)groups), dim3(64), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), table, state, to_move,
+                       mask, outcome_out, value_out, action_out, n, tb_shape(inventory));
+    GBL_LAUNCHED("gbl_tb_probe");
 }
 
 int64_t gbl_train_workspace_bytes(int64_t batch, int hidden) { return train_workspace_bytes(batch, hidden); }

@@ -709,6 +709,13 @@ class BatchedGobblet:
                                           out["value"].data_ptr(), out["action"].data_ptr(), n, self._stream()), "gbl_solve")
         return out
 
+    def tablebase(self, tb) -> dict:
+        """The true verdict on the current boards from a ``Tablebase`` on this device (one launch of ``gbl_tb_probe``): ``solve``'s dict
+        without a depth bound -- on a complete table 0 is a draw.  The boards are not touched."""
+        if tb.device != self.device:
+            raise ValueError("tablebase: the table lives on %s and the boards on %s" % (tb.device, self.device))
+        return tb.probe(self.squares, self.to_move)
+
     SYMMETRY_MASKS = {None: 0, "none": 0, "square": 7, "all": nat.SYMMETRIES - 1}
 
     def training_batch(self, traj: dict, batch: int, symmetries="all", call: int = 0, seed=None, out: dict | None = None) -> dict:

@@ -8,8 +8,9 @@
  *   - all pointers are HOST pointers; the `stream` argument is ignored (calls are synchronous) and no alignment is asked of buffers;
  *   - the *_at forms read *ply_dev / *call_dev from host memory; `counters` accumulates into its first stripe;
  *   - the device-memory helpers (gbl_pinned_alloc / _free, gbl_block_alloc / _free, gbl_device_memory, gbl_placement_probe,
- *     gbl_collect_variant) have no host flavour; gbl_train_workspace_bytes and gbl_replay_workspace_bytes are the same functions for both (they
- *     launch nothing);
+ *     gbl_collect_variant) have no host flavour; gbl_train_workspace_bytes, gbl_replay_workspace_bytes and gbl_tb_layout are the same functions for
+ *     both (they launch nothing);
+ *   - the gbl_cpu_tb_* entry points take `aux`, `table` and `decided` in host memory;
  *   - gbl_cpu_replay_append checks its workspace like the device flavour and does not use it; ring_state is host memory;
  *   - gbl_cpu_set_threads(t): boards are dealt over t std::threads (0 = the hardware's; the library reads no environment).
  * It is a flavour a caller ASKS for (device="cpu" in the Python layer; BASELINE config 1 "on CPU"), never a fallback of the HIP
@@ -161,6 +162,14 @@ int gbl_cpu_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, con
                          const uint64_t *ring_state, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
                          uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
                          int16_t *sym_out, void *stream);
+int gbl_cpu_tb_prepare(const int32_t *inventory, void *aux, void *stream);
+int gbl_cpu_tb_sweep(const int32_t *inventory, const void *aux, const int8_t *table, int8_t *out, int64_t first, int64_t count, int k,
+                     uint64_t *decided, void *stream);
+int gbl_cpu_tb_index(const int32_t *inventory, const void *aux, const int8_t *state, const int8_t *to_move, int64_t *index_out, int64_t n,
+                     void *stream);
+int gbl_cpu_tb_position(const int32_t *inventory, const void *aux, const int64_t *index, int8_t *state_out, int64_t n, void *stream);
+int gbl_cpu_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *state, const int8_t *to_move,
+                     const int8_t *mask, int8_t *outcome_out, int8_t *value_out, int32_t *action_out, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

@@ -829,6 +829,73 @@ int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const i
                      uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
                      int16_t *sym_out, void *stream);
 
+/* Exact tablebase (no counterpart in the reference: the game solved outright, one byte per position).  Integer-only and draws nothing:
+ * the kernels, the host flavour and a restatement of this text agree byte for byte.
+ *   Inventory.  inventory[3] (int32 on the HOST, read at the call) gives c_k in 0 .. 2, each player's number of pieces of size k.  The
+ *     reference's game is (2, 2, 2).  The pieces 2k+1 .. 2k+c_k exist; a smaller inventory is the same rules with fewer pieces.  A state
+ *     of an inventory holds only pieces that exist.
+ *   Position.  Pieces of equal size are interchangeable and the rules treat the two colours alike (check_for_winner compares the two
+ *     colours' lines in the same way), so a position is stored as the side to move sees it: three levels of nine cells, each cell
+ *     t = 0 empty, 1 own (the mover's), 2 other; at most c_k own and at most c_k other cells on level k.  A concrete board with
+ *     player_2 to move is looked up with the colours swapped.
+ *   Index.  code_k = the rank of level k's configuration, in ascending order of sum over pos of t_pos * 3^pos, among the admissible
+ *     ones; there are L_k = 1 / 91 / 1 423 of them for c_k = 0 / 1 / 2.  index = (code_2 * L_1 + code_1) * L_0 + code_0, and
+ *     positions = L_0 * L_1 * L_2 (2 881 473 967 for (2, 2, 2): an index needs 32 bits, a signed 32-bit number does not hold it).
+ *   Moves of the mover.  A piece of size k may go to any cell that holds no piece of level >= k of either colour.  It comes from the
+ *     reserve (fewer than c_k own cells on level k) or from an own cell of level k with nothing on a level above it; the source cell
+ *     becomes empty.  This is Board.is_legal / play_turn (board.py:82-132) on interchangeable pieces.  After the move
+ *     check_for_winner() is read with the reference's last-line-decides rule, as gbl_solve reads it.
+ *   Byte.  int8 per position: GBL_TB_TERMINAL where the position already holds a line of either colour (nobody moves from it);
+ *     otherwise gbl_solve's V -- +k the mover wins at ply k, -k the mover has lost by ply k, 0 nothing proven (also a mover without a
+ *     move).  Here k goes to 126, so "largest rank" is taken with rank(c) = 128 - c for c > 0, 0 for 0, -128 - c for c < 0: the
+ *     order of gbl_solve's rank (the shortest win, the unproven, the longest loss) on the wider range.
+ *   Sweeps.  Sweep 0 writes GBL_TB_TERMINAL or 0 into every byte of its range.  Sweep k >= 1 looks at every byte of its range that is
+ *     still 0 and computes gbl_solve's c(a) for every move a: +1 / -1 where the move decides at once, otherwise from u = the byte of
+ *     the position after a as the other side sees it, where u counts as proven only if 1 <= |u| <= k - 1 (so that a sweep in place
+ *     does not depend on the order in which positions are visited) and as 0 otherwise.  V = the c(a) of largest rank; the sweep
+ *     writes V where |V| == k and nothing elsewhere.
+ *   Invariant.  After sweeps 0 .. k over the whole universe every non-terminal byte equals V(position, mover, r = k) of gbl_solve's
+ *     text (a non-zero V is the same at every depth that proves it).  A sweep that decides nothing is the fixed point V(., ., infinity).
+ *     k stops at 126: a byte never holds +-127, and a caller whose next sweep would be 127 reports an error instead of wrapping.
+ *
+ * gbl_tb_layout: out[0] = positions, out[1 .. 3] = L_0, L_1, L_2, out[4] = GBL_TB_AUX_BYTES.  Launches nothing; one function for
+ *   both flavours.
+ * gbl_tb_prepare: fills the caller's `aux` (GBL_TB_AUX_BYTES bytes, the same for every inventory): the rank of each of the 3^9 = 19 683
+ *   level configurations for c = 2 (uint16) and c = 1 (uint8), the inverse tables, and the 512 sums of 3^pos over a 9-bit cell set.
+ *   The sweep kernel keeps all of it in LDS.
+ * gbl_tb_sweep: sweep k over the positions [first, first + count): byte i of the universe is out[i - first].  `table` is the whole
+ *   universe (positions bytes) for the look-ups of u; it is not read for k <= 1 and may be NULL there.  out == table + first is the
+ *   sweep in place; out and table may alias in any way.  For k >= 1 `out` must hold the range's bytes after sweeps 0 .. k - 1 and
+ *   `table` the universe after sweeps 0 .. k - 1 (bytes of sweep k itself may already be there).  The number of non-zero bytes the call
+ *   wrote is ADDED to *decided (uint64 in device memory, 8-byte aligned; the caller zeroes it), so that a sweep cut into slices
+ *   counts in one place.  0 <= k <= GBL_TB_MAX_SWEEP; count == 0 returns GBL_OK after the scalar checks.
+ * gbl_tb_index: index_out int64[n] = the index of board b as to_move[b] sees it, or -1 where the board holds a piece the inventory
+ *   lacks or more cells of one colour on a level than c_k.
+ * gbl_tb_position: state_out int8[n][27] = position index[b] as a contract state with player_1 to move: own cells positive, on
+ *   each level the lowest piece number on the lowest cell.  gbl_tb_index of it with to_move = 0 is index[b].  An index outside
+ *   [0, positions) gives a row of 27 bytes GBL_TB_TERMINAL.
+ * gbl_tb_probe: gbl_solve's three outputs with r = infinity, read from `table`: for every candidate a -- mask[b] & the legal mask of
+ *   to_move[b] (mask NULL: the legal mask), less the actions of pieces the inventory lacks -- c(a) as in a sweep with every non-zero,
+ *   non-terminal byte counted as proven.  outcome_out int8[n][54] (GBL_SOLVE_NONE for every other action), value_out int8[n] = the
+ *   c(a) of largest rank (0 without a candidate), action_out int32[n] = that candidate, the lowest index on ties (-1 without one);
+ *   each may be NULL.  A board gbl_tb_index gives -1 for has no candidate.  On a table that is not complete a 0 reads "not proven by
+ *   the sweeps done".  One wavefront per board; state / to_move / mask are read a byte at a time and need no alignment.
+ * Argument errors (GBL_ERR_ARG): a missing pointer, an inventory entry outside [0, 2], k outside [0, GBL_TB_MAX_SWEEP], a range that
+ *   leaves the universe, table == NULL with k >= 2, n < 0.  GBL_ERR_ALIGN (device flavour): aux 16-byte, decided and the int64 arrays
+ *   8-byte, action_out 4-byte aligned.  n == 0 returns GBL_OK after the scalar checks.  Nothing here allocates. */
+#define GBL_TB_TERMINAL (-128)
+#define GBL_TB_MAX_SWEEP 126
+#define GBL_TB_AUX_BYTES 63120
+int gbl_tb_layout(const int32_t *inventory, int64_t *out);
+int gbl_tb_prepare(const int32_t *inventory, void *aux, void *stream);
+int gbl_tb_sweep(const int32_t *inventory, const void *aux, const int8_t *table, int8_t *out, int64_t first, int64_t count, int k,
+                 uint64_t *decided, void *stream);
+int gbl_tb_index(const int32_t *inventory, const void *aux, const int8_t *state, const int8_t *to_move, int64_t *index_out, int64_t n,
+                 void *stream);
+int gbl_tb_position(const int32_t *inventory, const void *aux, const int64_t *index, int8_t *state_out, int64_t n, void *stream);
+int gbl_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *state, const int8_t *to_move,
+                 const int8_t *mask, int8_t *outcome_out, int8_t *value_out, int32_t *action_out, int64_t n, void *stream);
+
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
  *   GBL_COLLECT_STREAM  k_collect,  one wavefront per tile of 64 boards, trajectory rows stored non-temporally

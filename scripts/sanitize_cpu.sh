@@ -14,6 +14,10 @@ g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-poin
 g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wno-unknown-pragmas -Wno-attributes \
     -pthread -o $T/replay_main scripts/sanitize_replay_main.cpp gobblet-rl_amd/csrc/gobblet_cpu.cpp
 $T/replay_main
+# the tablebase's host entry points likewise
+g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wno-unknown-pragmas -Wno-attributes \
+    -pthread -o $T/tablebase_main scripts/sanitize_tablebase_main.cpp gobblet-rl_amd/csrc/gobblet_cpu.cpp
+$T/tablebase_main
 python -c "import oracle; oracle.lib(); from tests import emu; emu.lib(); import gobblet_rl_amd as G; G._native.build_cpu()"   # make sure the normal builds exist
 C=gobblet-rl_amd/csrc/libgobblet_cpu.so
 cp oracle/libgobblet_oracle.so $T/oracle.bak; cp tests/emu/libgobblet_emu.so $T/emu.bak; cp $C $T/cpu.bak
