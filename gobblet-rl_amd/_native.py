@@ -42,6 +42,7 @@ SYMMETRIES, BATCH_ATTEMPTS = 512, 16  # gbl_symmetry_apply / gbl_training_batch
 REPLAY_OBS_PITCH, REPLAY_VISITS_PITCH, REPLAY_META_PITCH = 128, 64, 64  # gbl_replay_append / gbl_replay_batch: the ring's row pitches
 REPLAY_META_Z, REPLAY_META_MOVER, REPLAY_META_TAG, STREAM_REPLAY = 54, 55, 56, 7
 TB_TERMINAL, TB_MAX_SWEEP, TB_AUX_BYTES = -128, 126, 63120  # gbl_tb_*
+TB_TARGET_MODES, TB_TARGET_MAX_COUNT = {"result": 0, "shortest": 1}, 600  # gbl_tb_targets
 STATUS_ILLEGAL, STATUS_OUT_OF_RANGE = 1, 2  # gbl_step_ex / gbl_collect_from_ex status bits
 CELLS, ACTIONS, OBS_BYTES = 27, 54, 117
 COUNTER_STRIPES, COUNTER_STRIDE = 64, 16
@@ -110,6 +111,7 @@ SIGNATURES = {
     "gbl_tb_index": (_int, [_vp] * 5 + [_i64, _vp]),
     "gbl_tb_position": (_int, [_vp] * 4 + [_i64, _vp]),
     "gbl_tb_probe": (_int, [_vp] * 9 + [_i64, _vp]),
+    "gbl_tb_targets": (_int, [_vp] * 4 + [_i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int] + [_vp] * 3 + [_i64, _vp]),
     "gbl_train_workspace_bytes": (_i64, [_i64, _int]),
     "gbl_train_step": (_int, [_vp] * 4 + [_i64, _int] + [_vp] * 7 + [_i64, _vp]),
     "gbl_collect_variant": (_int, [_i64, _u32, _int, _int]),

@@ -1481,6 +1481,67 @@ int gbl_cpu_tb_probe(const int32_t *inventory, const void *aux, const int8_t *ta
     return GBL_OK;
 }
 
+// Tablebase targets (include/gobblet_hip.h, "Tablebase targets"): decode_obs_row, the probe's loop and the rule's scalar pieces, row by
+// row.  The visits rows go through memcpy: the host flavour asks no alignment of them.
+int gbl_cpu_tb_targets(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                       int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                       int8_t *z_out, int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out,
+                       int64_t n, void *)
+{
+    bool empty;
+    if (const char *why = tb_targets_error(inventory, aux, table, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
+                                           z_out, z_pitch, mode, count, value_out, outcome_out, census_out, n, &empty))
+        return fail(GBL_ERR_ARG, why);
+    if (empty) return GBL_OK;
+    const TbAux A = tb_aux(aux);
+    const TbShape S = tb_shape(inventory);
+    const char *vin = reinterpret_cast<const char *>(visits_in);
+    char *vout = reinterpret_cast<char *>(visits_out);
+    parallel_for(n, [=](int64_t r0, int64_t r1) {
+        for (int64_t r = r0; r < r1; ++r) {
+            const int z_old = z_in ? (int)z_in[r * z_pitch] : 0;
+            int8_t c[kActions];
+            memset(c, kSolveNone, sizeof c);
+            int value = 0, census = -1;
+            const bool skipped = z_in && z_old == kZOpen;
+            if (!skipped) {
+                uint32_t d[30], row[7];
+                d[29] = 0;
+                memcpy(d, obs + r * obs_pitch, kObs);
+                const int mover = decode_obs_row(d, row) != 0;
+                const Planes p = make_planes(row);
+                uint64_t cand = legal54(p, mover) & tb_piece_actions(S);
+                if (mask) cand &= read_mask(mask + r * mask_pitch);
+                if (tb_board_index(A, S, p, mover) < 0) cand = 0;
+                uint32_t best = 0;
+                for (uint32_t a = 0; a < (uint32_t)kActions; ++a)
+                    if ((cand >> a) & 1ull) {
+                        c[a] = (int8_t)tb_probe_action(A, S, table, p, mover, a);
+                        best = std::max(best, tb_action_key(c[a], a));
+                    }
+                value = tb_value_of(best);
+                int16_t old[kActions], now[kActions];
+                if (visits_in) memcpy(old, vin + r * visits_pitch * 2, sizeof old);  // (read before the row is written: it may be the same row)
+                uint64_t keeps = 0;
+                uint32_t top = 0;
+                for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+                    const bool mine = (cand >> a) & 1ull;
+                    keeps |= (uint64_t)(mine && tb_target_keeps(c[a], value, kTbTargetResult)) << a;
+                    now[a] = (int16_t)(best && mine && tb_target_keeps(c[a], value, mode) ? count : 0);
+                    if (visits_in) top = std::max(top, tb_visit_key(old[a], a));
+                }
+                if (best) census = tb_census(top, keeps, z_in != nullptr, z_old, tb_sign(value));
+                if (visits_out) memcpy(vout + r * visits_pitch * 2, now, sizeof now);
+                z_out[r * z_pitch] = (int8_t)(best ? tb_sign(value) : kZOpen);
+            }
+            if (value_out) value_out[r] = (int8_t)value;
+            if (outcome_out) memcpy(outcome_out + r * kActions, c, sizeof c);
+            if (census_out) census_out[r] = (int8_t)census;
+        }
+    });
+    return GBL_OK;
+}
+
 }  // extern "C"
 
 // gbl_cpu_train_step: the header's rule row by row and element by element -- the same scalar pieces (gobblet_device.h: train_exp,

@@ -3160,6 +3160,89 @@ inline const char *tb_rows_error(const int32_t *inventory, const void *aux, int6
     return nullptr;
 }
 
+// ---- tablebase targets (include/gobblet_hip.h, "Tablebase targets"): the scalar pieces of the rule, shared by k_tb_targets and the host flavour
+constexpr int kTbTargetResult = 0, kTbTargetShortest = 1;  // GBL_TB_TARGET_RESULT / _SHORTEST
+constexpr int kTbTargetMaxCount = 600;
+__device__ __forceinline__ int tb_sign(int c) { return (c > 0) - (c < 0); }
+// whether a candidate's result BYTE c (the probe's outcome byte) belongs to the set O of a row of value `value`: R (mode 0, the result
+// kept) or S (mode 1, c == value).  A c(a) of +-128 -- from a table byte of +-127, which no sweep writes -- reads GBL_SOLVE_NONE as a byte
+// (its order key is a draw's either way): such a candidate counts for the probe's value and action and belongs to neither set.
+__device__ __forceinline__ bool tb_target_keeps(int c, int value, int mode)
+{
+    return c != kSolveNone && (mode == kTbTargetShortest ? c == value : tb_sign(c) == tb_sign(value));
+}
+// the order key of an old visit count (0: not positive); the largest key is the argmax, the lowest index on ties
+__device__ __forceinline__ uint32_t tb_visit_key(int v, uint32_t a) { return v > 0 ? ((uint32_t)v << 6) | (63u - a) : 0u; }
+// a labelled row's census byte: `top` the largest tb_visit_key of the old visits (0 without visits_in), `keeps` the set R as bits
+__device__ __forceinline__ int tb_census(uint32_t top, uint64_t keeps, bool has_z, int z_old, int z_new)
+{
+    const int kept = top ? (int)((keeps >> (63u - (top & 63u))) & 1ull) : 4;
+    return kept | (has_z && z_old == z_new ? 2 : 0);
+}
+
+// one pitched array of a gbl_tb_targets call, in bytes: rows of `row` bytes, `pitch` bytes apart
+struct TbSpan {
+    uintptr_t base;
+    uint64_t pitch, row;
+};
+inline TbSpan tb_span(const void *p, int64_t pitch, int64_t row, int64_t elem)
+{
+    return TbSpan{reinterpret_cast<uintptr_t>(p), (uint64_t)(pitch * elem), (uint64_t)(row * elem)};
+}
+// whether two arrays of n rows share a byte.  Arrays whose extents intersect must have one byte pitch (then the rows interleave, as
+// z does with the mask in ring_meta, and the test is exact); with two pitches an intersection of the extents counts as an overlap.
+inline bool tb_spans_overlap(const TbSpan &a, const TbSpan &b, int64_t n)
+{
+    if (!a.base || !b.base) return false;
+    const uint64_t ea = (uint64_t)(n - 1) * a.pitch + a.row, eb = (uint64_t)(n - 1) * b.pitch + b.row;
+    if (a.base + ea <= b.base || b.base + eb <= a.base) return false;
+    if (n == 1) return true;
+    if (a.pitch != b.pitch) return true;
+    const uint64_t d = b.base >= a.base ? (b.base - a.base) % a.pitch : (a.pitch - (a.base - b.base) % a.pitch) % a.pitch;
+    return d < a.row || d + b.row > a.pitch;
+}
+
+// the message of the first rule a gbl_tb_targets call breaks, or nullptr; *empty = the call has nothing to do (n == 0 after the scalar checks)
+inline const char *tb_targets_error(const int32_t *inventory, const void *aux, const void *table, const void *obs, int64_t obs_pitch,
+                                    const void *mask, int64_t mask_pitch, const void *visits_in, const void *visits_out, int64_t visits_pitch,
+                                    const void *z_in, const void *z_out, int64_t z_pitch, int mode, int count, const void *value_out,
+                                    const void *outcome_out, const void *census_out, int64_t n, bool *empty)
+{
+    *empty = false;
+    if (const char *why = tb_inventory_error(inventory)) return why;
+    if (n < 0) return "n < 0";
+    if (mode != kTbTargetResult && mode != kTbTargetShortest) return "mode must be GBL_TB_TARGET_RESULT or GBL_TB_TARGET_SHORTEST";
+    if (count < 1 || count > kTbTargetMaxCount) return "count must be in [1, 600]";
+    if (obs_pitch < kObs) return "obs_pitch must be at least 117";
+    if (mask && mask_pitch < kActions) return "mask_pitch must be at least 54";
+    if ((visits_in || visits_out) && visits_pitch < kActions) return "visits_pitch must be at least 54";
+    if (z_pitch < 1) return "z_pitch must be at least 1";
+    if (n == 0) {
+        *empty = true;
+        return nullptr;
+    }
+    if (!aux) return "aux must not be NULL";
+    if (!table) return "table must not be NULL";
+    if (!obs) return "obs must not be NULL";
+    if (!z_out) return "z_out must not be NULL";
+    // every output against every input; visits_in == visits_out and z_in == z_out are the in-place forms
+    const TbSpan in[6] = {tb_span(obs, obs_pitch, kObs, 1), tb_span(mask, mask_pitch, kActions, 1),
+                          tb_span(visits_in == visits_out ? nullptr : visits_in, visits_pitch, kActions, 2),
+                          tb_span(z_in == z_out ? nullptr : z_in, z_pitch, 1, 1),
+                          tb_span(aux, 0, kTbAuxBytes, 1), tb_span(table, 0, (int64_t)tb_shape(inventory).positions, 1)};
+    const TbSpan out[5] = {tb_span(visits_out, visits_pitch, kActions, 2), tb_span(z_out, z_pitch, 1, 1), tb_span(value_out, 1, 1, 1),
+                           tb_span(outcome_out, kActions, kActions, 1), tb_span(census_out, 1, 1, 1)};
+    for (int o = 0; o < 5; ++o)
+        for (int i = 0; i < 6; ++i) {
+            // (aux and table are single rows whatever n is; an in-place pair is still checked against the other inputs)
+            const bool one = i >= 4;
+            if (one ? tb_spans_overlap(TbSpan{out[o].base, 0, (uint64_t)(n - 1) * out[o].pitch + out[o].row}, in[i], 1)
+                    : tb_spans_overlap(in[i], out[o], n))
+                return "an output overlaps an input (only visits_in == visits_out and z_in == z_out may alias)";
+        }
+    return nullptr;
+}
+
 // ---- gbl_train_step (include/gobblet_hip.h, "One Adam step of the FLOAT network"): the scalar pieces of the bit-defined rule ----------
 // Shared by k_train_rows / k_train_reduce_adam and the host flavour.  Every function that does float arithmetic for the rule opens
 // with GBL_FP_STRICT, and so do the two kernels and the host flavour's own loops (train_row, train_sum, gbl_cpu_train_step): hipcc

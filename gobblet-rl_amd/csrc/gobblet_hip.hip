@@ -2868,6 +2868,83 @@ __global__ __launch_bounds__(256) void k_tb_position(const uint8_t *__restrict__
     for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < n; b += (int64_t)gridDim.x * 256) tb_row_of(A, S, index[b], state_out + b * kCells);
 }
 
+// ---- tablebase targets (include/gobblet_hip.h, "Tablebase targets") -------------------------------------------------------------------
+// k_tb_targets   one wavefront per row (four per workgroup, rows dealt grid-stride), lane a < 54 per action, as k_tb_probe.  The board
+//                never exists as a state row: lane c < 27 reads the four observation bytes that make cell c (two pairs of neighbours),
+//                lanes 27 .. 35 the nine agent bytes, and five ballots are the mover and the planes (decode_obs_row's arithmetic per
+//                cell, so any 117 bytes decode alike).  The byte loads go to at most two lines of the row; nothing is staged in LDS.
+//                R, S, the old visits' argmax and the census are ballots and butterfly reductions.  Every row is read (its old z and
+//                visits too) before any of its bytes is written, so visits_out / z_out may be visits_in / z_in.
+constexpr int kTbTargetWaves = 4;
+constexpr int kTbTargetGroups = 4096;  // the grid's cap: 16 384 rows in flight, the rest by the stride
+
+struct TbTargetArgs {
+    const uint8_t *aux;
+    const int8_t *table, *obs, *mask;
+    const int16_t *visits_in;  // (may be visits_out, and z_in z_out: no __restrict__ anywhere here)
+    int16_t *visits_out;
+    const int8_t *z_in;
+    int8_t *z_out, *value_out, *outcome_out, *census_out;
+    int64_t obs_pitch, mask_pitch, visits_pitch, z_pitch, n;
+    TbShape S;
+    int mode, count;
+};
+
+// the planes and the mover of one observation row, in every lane
+__device__ __forceinline__ Planes obs_planes(const int8_t *o, uint32_t lane, int &mover)
+{
+    int v = 0, agent = 0;
+    if (lane < (uint32_t)kCells) {
+        const uint32_t k = (lane * 57u) >> 9, q = lane - 9u * k;  // (lane / 9 for lane < 64)
+        const int8_t *c = o + 13u * q + 2u * k;
+        const int lo = 2 * (int)k + 1;
+        const int bp = lo * c[0] + (lo + 1) * c[1], bo = lo * c[6] + (lo + 1) * c[7];  // greedy_policy.py:44-56
+        v = bp > bo ? bp : -bo;                                                      // :57
+    } else if (lane < (uint32_t)kCells + 9u) {
+        agent = o[13u * (lane - (uint32_t)kCells) + 12u];
+    }
+    const uint64_t one = __ballot(agent > 0), more = __ballot(agent > 1);  // obs[..., 12].max() over 0: > 0 moves second, == 1 negates (:67-68)
+    mover = one != 0ull;
+    if (one != 0ull && more == 0ull) v = -v;
+    return Planes{(uint32_t)__ballot((v & 0xFF) != 0), (uint32_t)__ballot((v & 0x80) != 0), (uint32_t)__ballot(v & 1)};
+}
+
+__global__ __launch_bounds__(64 * kTbTargetWaves) void k_tb_targets(TbTargetArgs a)
+{
+    const TbAux A = tb_aux(a.aux);
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool act = lane < (uint32_t)kActions;
+    const uint64_t pieces = tb_piece_actions(a.S);
+    const int64_t step = (int64_t)gridDim.x * kTbTargetWaves;
+    for (int64_t r = (int64_t)blockIdx.x * kTbTargetWaves + uniform((int)(threadIdx.x >> 6)); r < a.n; r += step) {
+        const int z_old = a.z_in ? uniform((int)a.z_in[r * a.z_pitch]) : 0;
+        int c = kSolveNone, value = 0, census = -1;
+        if (!(a.z_in && z_old == kZOpen)) {  // (uniform) a skipped row writes neither visits nor z
+            int mover;
+            const Planes root = obs_planes(a.obs + r * a.obs_pitch, lane, mover);
+            uint64_t cand = board_candidates(root, mover, a.mask ? a.mask + r * a.mask_pitch : nullptr, 0, lane) & pieces;
+            if (tb_board_index(A, a.S, root, mover) < 0) cand = 0;
+            const bool mine = act && ((cand >> lane) & 1ull);
+            if (mine) c = (int)(int8_t)tb_probe_action(A, a.S, a.table, root, mover, lane);  // (the outcome byte: see tb_target_keeps)
+            const uint32_t best = wave_max(mine ? tb_action_key(c, lane) : 0u);
+            value = tb_value_of(best);
+            const int sign = tb_sign(value);
+            if (a.census_out && best) {
+                const int old = a.visits_in && act ? (int)a.visits_in[r * a.visits_pitch + lane] : 0;
+                const uint32_t top = wave_max(tb_visit_key(old, lane));
+                census = tb_census(top, __ballot(mine && tb_target_keeps(c, value, kTbTargetResult)), a.z_in != nullptr, z_old, sign);
+            }
+            if (a.visits_out && act) a.visits_out[r * a.visits_pitch + lane] = (int16_t)(best && mine && tb_target_keeps(c, value, a.mode) ? a.count : 0);
+            if (lane == 0) a.z_out[r * a.z_pitch] = (int8_t)(best ? sign : kZOpen);
+        }
+        if (a.outcome_out && act) a.outcome_out[r * kActions + lane] = (int8_t)c;
+        if (lane == 0) {
+            if (a.value_out) a.value_out[r] = (int8_t)value;
+            if (a.census_out) a.census_out[r] = (int8_t)census;
+        }
+    }
+}
+
 // gbl_train_step: the float trainer's Adam step in two launches, bit-defined by the header (every float operation below is the
 // header's, in its order; GBL_FP_STRICT keeps hipcc from fusing them).
 //   k_train_rows          one wavefront per row (four per workgroup, rows dealt grid-stride), w2 staged in LDS once per workgroup:
@@ -5066,6 +5143,25 @@ int gbl_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table,
     hipLaunchKernelGGL(k_tb_probe, dim3((uint32_t)groups), dim3(64), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), table, state, to_move,
                        mask, outcome_out, value_out, action_out, n, tb_shape(inventory));
     GBL_LAUNCHED("gbl_tb_probe");
+}
+
+int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                   int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int8_t *z_out,
+                   int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out, int64_t n, void *stream)
+{
+    bool empty;
+    if (const char *why = tb_targets_error(inventory, aux, table, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
+                                           z_out, z_pitch, mode, count, value_out, outcome_out, census_out, n, &empty))
+        return fail(GBL_ERR_ARG, why);
+    if (empty) return GBL_OK;
+    GBL_ALIGNED(aux, "aux");
+    if (reinterpret_cast<uintptr_t>(visits_in) & 1u) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(visits_out) & 1u) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
+    const TbTargetArgs A{static_cast<const uint8_t *>(aux), table, obs, mask, visits_in, visits_out, z_in, z_out, value_out, outcome_out,
+                         census_out, obs_pitch, mask_pitch, visits_pitch, z_pitch, n, tb_shape(inventory), mode, count};
+    const int64_t groups = std::min<int64_t>((n + kTbTargetWaves - 1) / kTbTargetWaves, kTbTargetGroups);
+    hipLaunchKernelGGL(k_tb_targets, dim3((uint32_t)groups), dim3(64 * kTbTargetWaves), 0, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_tb_targets");
 }
 
 int64_t gbl_train_workspace_bytes(int64_t batch, int hidden) { return train_workspace_bytes(batch, hidden); }

@@ -132,17 +132,32 @@ class ReplayBuffer(_OnDevice):
                 out["sym"].data_ptr(), self._stream()), "gbl_replay_batch")
         return out
 
+    def relabel(self, tb, mode: str = "result", count: int = 1, census: bool = False, allow_incomplete: bool = False):
+        """Exact targets for the ring's live rows, in place: one launch of ``gbl_tb_targets`` over the ring's own arrays through their
+        pitches (``Tablebase.targets`` has the rule).  The live rows are every slot once the ring has wrapped and the first ``total``
+        slots before, so a slot never written stays zero; mover bytes, tags and padding are not touched.  Returns the census, int8
+        (live rows,) in slot order, when asked.  Reads ``total`` from the device."""
+        if self._obs is None:
+            raise ValueError("relabel needs a buffer with observations")
+        if tb.device != self.device:
+            raise ValueError("relabel: the table lives on %s and the buffer on %s" % (tb.device, self.device))
+        return tb._targets(self.size, self._obs.data_ptr(), nat.REPLAY_OBS_PITCH, self._meta.data_ptr(), nat.REPLAY_META_PITCH,
+                           self._visits.data_ptr(), nat.REPLAY_VISITS_PITCH, self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH,
+                           mode, count, census, None, allow_incomplete)
+
     def fit(self, trainer, steps: int, batch: int = 1024, symmetries="all", first_call: int = 0, recent: int | None = None,
-            seed: int = 0) -> torch.Tensor:
+            seed: int = 0, targets=None) -> torch.Tensor:
         """``steps`` Adam steps of ``trainer`` (a ``GobbletTrainer`` on this buffer's device): step i draws ``batch(batch, symmetries,
         call=first_call + i, recent=recent)`` into one reused buffer and hands it to ``trainer.step``; nothing crosses to the host.
-        Returns the steps' statistics, float32 (steps, 4) on the device, as ``BatchedGobblet.fit`` does."""
+        ``targets``: a ``Tablebase`` on this device -- every drawn batch goes through ``targets.targets`` first (one more launch per
+        step: the fit learns from the exact labels).  Returns the steps' statistics, float32 (steps, 4) on the device, as
+        ``BatchedGobblet.fit`` does."""
         if torch.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the buffer on %s" % (trainer.device, self.device))
         buf, stats = None, []
         for i in range(int(steps)):
             buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf)
-            stats.append(trainer.step(buf))
+            stats.append(trainer.step(buf if targets is None else targets.targets(dict(buf))))
         return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
 
     def state_dict(self) -> dict:

@@ -105,6 +105,46 @@ class Tablebase(_OnDevice):
         """int8 (N,): the table's bytes at ``indices`` (``nat.TB_TERMINAL`` where the position already holds a line)."""
         return self.table[torch.as_tensor(indices).to(device=self.device, dtype=torch.int64).reshape(-1)]
 
+    # ---- exact training targets -------------------------------------------------------------------------------------------------
+    def _targets(self, n, obs, obs_pitch, mask, mask_pitch, visits, visits_pitch, z, z_pitch, mode, count, census, value, allow_incomplete):
+        """One launch of ``gbl_tb_targets`` in place on ``n`` pitched rows (data pointers); returns the census tensor or None."""
+        if mode not in nat.TB_TARGET_MODES:
+            raise ValueError("mode: 'result' or 'shortest'")
+        if not 1 <= int(count) <= nat.TB_TARGET_MAX_COUNT:
+            raise ValueError("count must be in [1, %d]" % nat.TB_TARGET_MAX_COUNT)
+        if not self.complete and not allow_incomplete:
+            raise ValueError("the table is not complete: a 0 would read 'not proven yet' (allow_incomplete=True to label with it anyway)")
+        tally = torch.empty(n, dtype=torch.int8, device=self.device) if census else None
+        with self._on_device():
+            nat.check(self._lib.gbl_tb_targets(self._inv, self._aux.data_ptr(), self.table.data_ptr(), obs, obs_pitch, mask, mask_pitch, visits,
+                                               visits, visits_pitch, z, z, z_pitch, nat.TB_TARGET_MODES[mode], int(count), nat.ptr(value), None,
+                                               nat.ptr(tally), n, self._stream()), "gbl_tb_targets")
+        return tally
+
+    def targets(self, batch: dict, mode: str = "result", count: int = 1, census: bool = False, allow_incomplete: bool = False) -> dict:
+        """Exact targets for the dict ``BatchedGobblet.training_batch`` / ``ReplayBuffer.batch`` return, one launch of ``gbl_tb_targets``:
+        "visits" and "z" are overwritten IN PLACE -- ``count`` on every candidate that keeps the true result (``mode`` "result") or
+        that is a shortest win, a draw or a longest loss ("shortest"), z = the true sign; a failed sample stays as it is, a row the
+        table cannot label gets zero visits and z = ``nat.Z_OPEN``.  Adds "tb_value" int8 (N,) and, with ``census``, "census" int8 (N,)
+        (include/gobblet_hip.h, "Tablebase targets": bit 0 the old visits' argmax kept the result, bit 1 the old z was the true sign,
+        bit 2 there were no old visits; -1 for a row without a label).  Returns the dict."""
+        if "observation" not in batch:
+            raise ValueError("targets needs the 'observation' entry: a window or a buffer with observations")
+        obs, mask, visits, z = batch["observation"], batch.get("action_mask"), batch["visits"], batch["z"]
+        n = int(z.shape[0])
+        spec = (("observation", obs, (n, nat.OBS_BYTES), torch.int8), ("action_mask", mask, (n, nat.ACTIONS), torch.int8),
+                ("visits", visits, (n, nat.ACTIONS), torch.int16), ("z", z, (n,), torch.int8))
+        for name, t, shape, dtype in spec:
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"targets: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        value = torch.empty(n, dtype=torch.int8, device=self.device)
+        tally = self._targets(n, obs.data_ptr(), nat.OBS_BYTES, nat.ptr(mask), nat.ACTIONS, visits.data_ptr(), nat.ACTIONS, z.data_ptr(), 1,
+                              mode, count, census, value, allow_incomplete)
+        batch["tb_value"] = value
+        if census:
+            batch["census"] = tally
+        return batch
+
     # ---- files: a header and the raw bytes (never part of the repository: the full table is 2.9 GB) -------------------------------
     def save(self, path) -> None:
         head = json.dumps({"inventory": list(self.inventory), "positions": self.positions, "sweeps": self.sweeps, "complete": self.complete,

@@ -761,18 +761,19 @@ class BatchedGobblet:
                 out["index"].data_ptr(), out["sym"].data_ptr(), self._stream()), "gbl_training_batch")
         return out
 
-    def fit(self, traj: dict, trainer, steps: int, batch: int = 1024, symmetries="all", first_call: int = 0) -> torch.Tensor:
+    def fit(self, traj: dict, trainer, steps: int, batch: int = 1024, symmetries="all", first_call: int = 0, targets=None) -> torch.Tensor:
         """``steps`` Adam steps of ``trainer`` (a ``GobbletTrainer`` on this environment's device) on the window ``traj``: step i
         draws ``training_batch(traj, batch, symmetries, call=first_call + i)`` into one reused buffer and hands it to
         ``trainer.step`` -- four launches per step on the current stream (the draw, gbl_train_step's two, the trainer's running hidden
-        maximum), nothing crosses to the host.  Returns the steps'
+        maximum), nothing crosses to the host.  ``targets``: a ``Tablebase`` on this device -- every drawn batch goes through
+        ``targets.targets`` first (one more launch per step: the fit learns from the exact labels).  Returns the steps'
         statistics, float32 (steps, 4) on the device (see ``GobbletTrainer.step``)."""
         if torch.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the environment on %s" % (trainer.device, self.device))
         buf, stats = None, []
         for i in range(int(steps)):
             buf = self.training_batch(traj, batch, symmetries=symmetries, call=int(first_call) + i, out=buf)
-            stats.append(trainer.step(buf))
+            stats.append(trainer.step(buf if targets is None else targets.targets(dict(buf))))
         return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
 
     def release_staging(self) -> None:

@@ -170,6 +170,10 @@ int gbl_cpu_tb_index(const int32_t *inventory, const void *aux, const int8_t *st
 int gbl_cpu_tb_position(const int32_t *inventory, const void *aux, const int64_t *index, int8_t *state_out, int64_t n, void *stream);
 int gbl_cpu_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *state, const int8_t *to_move,
                      const int8_t *mask, int8_t *outcome_out, int8_t *value_out, int32_t *action_out, int64_t n, void *stream);
+int gbl_cpu_tb_targets(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                       int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                       int8_t *z_out, int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out,
+                       int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

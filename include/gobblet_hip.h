@@ -896,6 +896,44 @@ int gbl_tb_position(const int32_t *inventory, const void *aux, const int64_t *in
 int gbl_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *state, const int8_t *to_move,
                  const int8_t *mask, int8_t *outcome_out, int8_t *value_out, int32_t *action_out, int64_t n, void *stream);
 
+/* Tablebase targets (no counterpart in the reference): exact training targets for rows in the shape gbl_training_batch and
+ * gbl_replay_batch write, or for the replay ring's own rows in place, and a census of the targets they replace.  One launch, no
+ * allocation, no atomics; integer-only, so the kernel, the host flavour and a restatement of this text agree byte for byte.
+ *   Rows.  n rows; row r of each pitched array lies at base + r * pitch, pitches in ELEMENTS of the array's type: obs int8 (117 per
+ *     row), mask int8 (54), visits_in / visits_out int16 (54, one pitch for both), z_in / z_out int8 (1, one pitch for both).  A drawn
+ *     batch has the pitches 117 / 54 / 54 / 1; the ring has ring_obs at GBL_REPLAY_OBS_PITCH, ring_meta (the mask) at
+ *     GBL_REPLAY_META_PITCH, ring_visits at GBL_REPLAY_VISITS_PITCH and z = ring_meta + GBL_REPLAY_META_Z at GBL_REPLAY_META_PITCH.
+ *     Bytes of a pitched row beyond its 117 / 54 / 54 / 1 elements are neither read into the rule nor written.
+ *   Skipped rows.  z_in is optional; a row whose z_in byte is GBL_Z_OPEN (the failed sample of both samplers) is skipped: no byte of
+ *     its visits_out or z_out row is written.
+ *   The rule.  (state, to_move) = gbl_decode_obs of the row's 117 bytes; (outcome[54], value, action) = gbl_tb_probe of that board
+ *     with the row's mask bytes as candidates (mask NULL: the legal mask).  A row with action == -1 is UNLABELLED (no candidate, a
+ *     board that is no state of the inventory, a mask that removes every move): visits_out = 54 zeros, z_out = GBL_Z_OPEN, so that
+ *     gbl_train_step counts it for nothing.  Otherwise, with sign(x) in {-1, 0, +1}: R = the candidates a with
+ *     sign(c(a)) == sign(value) (they keep the result), S = those with c(a) == value (the shortest wins, the draws, the longest
+ *     losses); O = R for mode GBL_TB_TARGET_RESULT, S for GBL_TB_TARGET_SHORTEST; visits_out[a] = count for a in O and 0 for the other
+ *     actions (1 <= count <= 600: a row's sum fits an int16); z_out = sign(value).  visits_out may be NULL.  c(a) is the probe's
+ *     outcome BYTE: a table byte of +-127 (no sweep writes one) gives a c(a) of -+128, which reads GBL_SOLVE_NONE there; such a
+ *     candidate counts for value and action as in the probe (it ranks like a 0) and belongs to neither set.
+ *   Dense outputs (each optional, row r at r * 1 / 54 / 1): value_out int8[n] = value (0 for a skipped or unlabelled row); outcome_out
+ *     int8[n][54] = the probe's row (54 times GBL_SOLVE_NONE for a skipped row); census_out int8[n] = -1 for a skipped or unlabelled
+ *     row, otherwise bit 0: visits_in is given, the row's 54 old visits are not all <= 0 and their argmax (the lowest index on ties)
+ *     lies in R; bit 1: z_in is given and the old z equals the new z; bit 2: the old visits were all <= 0, or visits_in is NULL.
+ *   Aliasing.  visits_in == visits_out and z_in == z_out are the in-place forms: a row is read completely before it is written.  Any
+ *     other byte an output shares with an input (obs, mask, visits_in, z_in, aux, table) is GBL_ERR_ARG.  Two arrays whose extents
+ *     intersect must have the same pitch in bytes (their rows interleave, as z and the mask do in ring_meta); with different
+ *     pitches intersecting extents count as an overlap.
+ *   Errors, in this order (GBL_ERR_ARG): the inventory, n < 0, mode, count, a pitch smaller than its row (obs; mask if given; visits
+ *     if either is given; z); n == 0 returns GBL_OK here; then a missing aux, table, obs or z_out; then the overlaps.
+ *     GBL_ERR_ALIGN (device flavour only): aux 16-byte, visits_in / visits_out 2-byte; the byte arrays need no alignment (a batch's
+ *     observation rows are 117 bytes apart).
+ *   On a table that is not complete a 0 reads "not proven by the sweeps done", as in the probe. */
+#define GBL_TB_TARGET_RESULT 0
+#define GBL_TB_TARGET_SHORTEST 1
+int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *table, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                   int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int8_t *z_out,
+                   int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out, int64_t n, void *stream);
+
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
  *   GBL_COLLECT_STREAM  k_collect,  one wavefront per tile of 64 boards, trajectory rows stored non-temporally
