@@ -996,6 +996,11 @@ struct SelfplaySearch {
     int proven, proven_action;
     bool solved;
     int8_t outcome[kActions];
+    // gbl_cpu_collect_search_tb: `judged`: tb_outcome / tb_value hold the table's verdict of the position; `table`: the mover plays from
+    // it -- h holds its visits row and value, tb_action the probe's a*
+    bool judged, table;
+    int tb_value, tb_action;
+    int8_t tb_outcome[kActions];
 };
 
 extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
@@ -1027,12 +1032,17 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
             S.priors = nullptr;
             S.proven = 0;
             S.solved = false;
+            S.judged = S.table = false;
             const bool tree = search(p, who, legal, g, q, S);
             int action, how = GBL_HOW_RANDOM, value = 0;
             if (tree) {
                 const bool sampled = !S.proven && tabs < sample_plies;
-                action = S.proven ? S.proven_action : sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit)) : tree_action_of(h.best);
-                how = S.proven ? GBL_HOW_PROVEN : sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
+                action = S.proven ? S.proven_action
+                         : sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit))
+                                   : S.table ? S.tb_action : tree_action_of(h.best);
+                how = S.proven ? GBL_HOW_PROVEN
+                      : S.table ? (sampled ? GBL_HOW_TABLE_SAMPLED : GBL_HOW_TABLE)
+                                : sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
                 for (int a = 0; a < kActions; ++a) value += h.wins[a] - h.losses[a];
             } else {
                 action = sample54(legal, seed, g, q);
@@ -1069,6 +1079,12 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
                 else memset(T.outcome + at * kActions, kSolveNone, kActions);
             }
             if (T.proven) T.proven[at] = (int8_t)S.proven;
+            if (T.tb_outcome) {
+                if (S.judged) memcpy(T.tb_outcome + at * kActions, S.tb_outcome, kActions);
+                else memset(T.tb_outcome + at * kActions, kSolveNone, kActions);
+            }
+            if (T.tb_value) T.tb_value[at] = (int8_t)(S.judged ? S.tb_value : 0);
+            if (T.tb_played) T.tb_played[at] = S.judged && action >= 0 ? S.tb_outcome[action] : (int8_t)kSolveNone;
             if (T.obs) write_obs(T.obs + at * kObs, p, mover);
             if (T.mask) write_mask(T.mask + at * kActions, legal);
         }
@@ -1081,8 +1097,9 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
 }
 }  // extern "C++"
 
-// The four self-play entry points behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
-// over the threads.  gbl_cpu_collect_search_eval is the guarded loop with depths and weights 0 and no outcome / proven arrays.
+// The five self-play entry points behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
+// over the threads.  gbl_cpu_collect_search_eval is the guarded loop with depths and weights 0 and no outcome / proven arrays;
+// gbl_cpu_collect_search_tb is it with the probe in front of every ply that is judged or played from the table.
 static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
 {
     EvalNet nets[2] = {};
@@ -1097,11 +1114,39 @@ static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
     const uint32_t ply0 = c.ply0 + (c.ply_dev ? *c.ply_dev : 0u);
     const bool uct = c.run == kRunSearch;
     const EvalNet net0 = nets[0], net1 = nets[1];
+    const bool reads_table = selfplay_reads_table(c);
+    const bool judge = reads_table && (c.traj.tb_outcome || c.traj.tb_value || c.traj.tb_played);
+    const TbAux A = reads_table ? tb_aux(c.aux) : TbAux{};
+    const TbShape tbs = reads_table ? tb_shape(c.inventory) : TbShape{};
     parallel_for(c.n, [=](int64_t b0, int64_t b1) {  // (a ply of a board is a solve and a whole search: every board is worth a thread)
         std::vector<TreeNode> nodes((size_t)most + 1);
         std::vector<uint8_t> pri(uct ? 0 : ((size_t)most + 1) * kEvalOutputs);
         uint8_t root_pi[kActions];
         selfplay_boards(b0, b1, c, ply0, [&](const Planes &p, int who, uint64_t legal, uint64_t g, uint32_t q, SelfplaySearch &S) {
+            const bool plays_table = c.policy[who] == GBL_POLICY_TABLEBASE;  // (kRunTb alone admits the policy)
+            if (judge || plays_table) {  // the verdict: gbl_tb_probe(mask = NULL) of the position, as its mover sees it
+                const uint64_t cand = tb_board_index(A, tbs, p, who) < 0 ? 0ull : legal & tb_piece_actions(tbs);
+                uint32_t best = 0;
+                memset(S.tb_outcome, kSolveNone, kActions);
+                for (uint32_t a = 0; a < (uint32_t)kActions; ++a)
+                    if ((cand >> a) & 1ull) {
+                        S.tb_outcome[a] = (int8_t)tb_probe_action(A, tbs, c.table, p, who, a);
+                        best = std::max(best, tb_action_key(S.tb_outcome[a], a));
+                    }
+                S.judged = true;
+                S.tb_value = tb_value_of(best);
+                S.tb_action = tb_action_of(best);
+                if (plays_table && best) {  // count on every action of O; nothing is searched
+                    S.table = true;
+                    S.h = HostSearch{};
+                    for (uint32_t a = 0; a < (uint32_t)kActions; ++a)
+                        if (((cand >> a) & 1ull) && tb_target_keeps(S.tb_outcome[a], S.tb_value, c.tb_mode)) {
+                            S.h.visits[a] = c.tb_count;
+                            (S.tb_value > 0 ? S.h.wins : S.h.losses)[a] = S.tb_value ? 128 * c.tb_count : 0;
+                        }
+                    return true;
+                }
+            }
             if (c.policy[who] != (uct ? GBL_POLICY_TREE : GBL_POLICY_EVAL_TREE)) return false;
             const uint32_t its = (uint32_t)c.iterations[who];
             if (uct) {
@@ -1142,10 +1187,10 @@ int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t
 {
     return host_selfplay_run({kRunSearch, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr},
+                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {nullptr, nullptr},
                             {iterations0, iterations1}, {playouts0, playouts1}, {0, 0}, {0, 0}, max_plies, explore, sample_plies, illegal_mode,
-                            counters, turn});
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
 }
 
 int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
@@ -1158,10 +1203,10 @@ int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, in
 {
     return host_selfplay_run({kRunEval, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr},
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn});
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
 }
 
 int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
@@ -1175,10 +1220,10 @@ int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, i
 {
     return host_selfplay_run({kRunSolve, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn});
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
 }
 
 int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
@@ -1193,10 +1238,29 @@ int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, i
 {
     return host_selfplay_run({kRunSolve, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn});
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
+}
+
+int gbl_cpu_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                              int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                              int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                              uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                              int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                              int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                              int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
+                              int64_t *counters, int32_t *turn, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode,
+                              int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *)
+{
+    return host_selfplay_run({kRunTb, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, tb_outcome_traj,
+                             tb_value_traj, tb_played_traj},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn, inventory, aux, table, tb_mode, tb_count});
 }
 
 int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,

@@ -2011,6 +2011,10 @@ constexpr int kPolicyTree = 4;                 // GBL_POLICY_TREE
 constexpr int kPolicyEvalTree = 5;             // GBL_POLICY_EVAL_TREE (gbl_collect_search_eval)
 constexpr int kHowSearch = 3, kHowSearchSampled = 4;  // GBL_HOW_SEARCH / GBL_HOW_SEARCH_SAMPLED (0 = GBL_HOW_RANDOM)
 constexpr int kHowProven = 5;                  // GBL_HOW_PROVEN (gbl_collect_search_solve)
+constexpr int kPolicyTablebase = 6;            // GBL_POLICY_TABLEBASE (gbl_collect_search_tb)
+constexpr int kHowTable = 6, kHowTableSampled = 7;  // GBL_HOW_TABLE / GBL_HOW_TABLE_SAMPLED
+constexpr int kTbTargetResult = 0, kTbTargetShortest = 1;  // GBL_TB_TARGET_RESULT / _SHORTEST (gbl_tb_targets, gbl_collect_search_tb)
+constexpr int kTbTargetMaxCount = 600;
 constexpr int kZOpen = -128;                   // GBL_Z_OPEN
 constexpr uint32_t kStreamVisit = 4u;          // generator stream of the visit-proportional draw of a game's first plies
 
@@ -2480,8 +2484,8 @@ inline const char *collect_solve_error(int illegal_mode, int policy0, int policy
     return nullptr;
 }
 
-// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve and _noise, and the checks both flavours make of them ----
-// The 16 trajectory arrays (any may be NULL).
+// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise and _tb, and the checks both flavours make of them ----
+// The 19 trajectory arrays (any may be NULL).
 struct SelfplayTraj {
     int32_t *actions;
     int8_t *winner, *reward, *done, *to_move, *mask, *obs;
@@ -2490,12 +2494,13 @@ struct SelfplayTraj {
     int8_t *how, *mover;
     int32_t *root_value;  // (the evaluator search's two: NULL in gbl_collect_search)
     uint8_t *priors;
-    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_collect_search_solve / _noise)
+    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_collect_search_solve / _noise / _tb)
+    int8_t *tb_outcome, *tb_value, *tb_played;  // (the table's verdict of every ply: NULL but in gbl_collect_search_tb)
 };
 
-enum SelfplayRun { kRunSearch, kRunEval, kRunSolve };  // gbl_collect_search; gbl_collect_search_eval; _solve and _noise
+enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval; _solve and _noise; _tb
 
-// The union of the four entry points' arguments; an entry point fills it (0 / NULL for what it does not have) and calls its flavour's
+// The union of the five entry points' arguments; an entry point fills it (0 / NULL for what it does not have) and calls its flavour's
 // one runner.  [0] is player_1's, [1] player_2's.  Ev: gbl_evaluator.
 template <typename Ev>
 struct SelfplayCall {
@@ -2513,10 +2518,55 @@ struct SelfplayCall {
     int max_plies, explore, sample_plies, illegal_mode;
     int64_t *counters;
     int32_t *turn;
+    // gbl_collect_search_tb's own (0 / NULL elsewhere): the table as gbl_tb_probe takes it, gbl_tb_targets' mode and count
+    const int32_t *inventory;
+    const void *aux;
+    const int8_t *table;
+    int tb_mode, tb_count;
 };
 
+// (the tablebase entry points' look at an inventory: "Exact tablebase" below)
+inline const char *tb_inventory_error(const int32_t *inventory)
+{
+    if (!inventory) return "inventory must not be NULL";
+    for (int k = 0; k < 3; ++k)
+        if (inventory[k] < 0 || inventory[k] > 2) return "inventory entries must be in [0, 2]";
+    return nullptr;
+}
+
+// whether a gbl_collect_search_tb call reads the table at all: a side plays from it, or a judge array is given
+template <typename Ev>
+inline bool selfplay_reads_table(const SelfplayCall<Ev> &c)
+{
+    return c.run == kRunTb && (c.policy[0] == kPolicyTablebase || c.policy[1] == kPolicyTablebase || c.traj.tb_outcome || c.traj.tb_value ||
+                               c.traj.tb_played);
+}
+
+// gbl_collect_search_tb, everything that is looked at before a pointer to boards is: the illegal mode, the policies (three here), then
+// collect_solve_error with a TABLEBASE side read as a RANDOM one (its evaluator, budget and depth are not read), then the table's
+// mode and count and, where the call reads the table, the inventory.  (n >= 0)
+template <typename Ev>
+inline const char *collect_tb_error(const SelfplayCall<Ev> &c)
+{
+    if (const char *why = illegal_mode_error(c.illegal_mode)) return why;
+    int pol[2];
+    for (int m = 0; m < 2; ++m) {
+        if (c.policy[m] != 0 && c.policy[m] != kPolicyEvalTree && c.policy[m] != kPolicyTablebase)
+            return "policy0 / policy1: GBL_POLICY_RANDOM, GBL_POLICY_EVAL_TREE or GBL_POLICY_TABLEBASE";
+        pol[m] = c.policy[m] == kPolicyTablebase ? 0 : c.policy[m];
+    }
+    if (const char *why = collect_solve_error(c.illegal_mode, pol[0], pol[1], c.ev[0], c.ev[1], c.iterations[0], c.iterations[1],
+                                              c.solve_depth[0], c.solve_depth[1], c.explore, c.sample_plies, c.turn != nullptr, c.ply0, c.plies,
+                                              c.env_base, c.n))
+        return why;
+    if (c.tb_mode != kTbTargetResult && c.tb_mode != kTbTargetShortest) return "tb_mode must be GBL_TB_TARGET_RESULT or GBL_TB_TARGET_SHORTEST";
+    if (c.tb_count < 1 || c.tb_count > kTbTargetMaxCount) return "tb_count must be in [1, 600]";
+    return selfplay_reads_table(c) ? tb_inventory_error(c.inventory) : nullptr;
+}
+
 // Everything both flavours look at, in the order they report it: n < 0, the entry point's *_error, the searching sides' noise
-// weights, n == 0, the three board arrays, plies == 0, then per searching side `side(m)` -- the flavour's own look at evaluator m
+// weights, n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
+// per searching side `side(m)` -- the flavour's own look at evaluator m
 // (its pointers; on the device their alignment too), which returns 0 or what its fail() returned.  Returns a flavour's error
 // code (< 0; fail(message) makes a GBL_ERR_ARG of a message), 0 where there is nothing to do (GBL_OK), or 1: the flavour goes on
 // with the strides (and its alignments) and runs.  most: the larger tree of the sides that search.
@@ -2529,6 +2579,7 @@ inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, 
     const char *why = uct ? collect_search_error(c.illegal_mode, c.policy[0], c.policy[1], c.iterations[0], c.iterations[1], c.playouts[0],
                                                  c.playouts[1], c.max_plies, c.explore, c.sample_plies, c.turn != nullptr, c.ply0, c.plies,
                                                  c.env_base, c.n)
+                      : c.run == kRunTb ? collect_tb_error(c)
                           : collect_solve_error(c.illegal_mode, c.policy[0], c.policy[1], c.ev[0], c.ev[1], c.iterations[0], c.iterations[1],
                                                 c.solve_depth[0], c.solve_depth[1], c.explore, c.sample_plies, c.turn != nullptr, c.ply0,
                                                 c.plies, c.env_base, c.n);
@@ -2539,6 +2590,10 @@ inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, 
     if (!c.state) return fail("state must not be NULL");
     if (!c.to_move) return fail("to_move must not be NULL");
     if (!c.done) return fail("done must not be NULL");
+    if (selfplay_reads_table(c)) {
+        if (!c.aux) return fail("aux must not be NULL");
+        if (!c.table) return fail("table must not be NULL");
+    }
     if (c.plies == 0) return 0;
     most = 0;
     for (int m = 0; m < 2; ++m) {
@@ -3124,13 +3179,6 @@ __device__ __forceinline__ void tb_row_of(const TbAux &A, const TbShape &S, int6
 
 // Each *_error returns the message of the first rule the arguments break, or nullptr (all GBL_ERR_ARG; the device flavour's alignment
 // rules follow there)
-inline const char *tb_inventory_error(const int32_t *inventory)
-{
-    if (!inventory) return "inventory must not be NULL";
-    for (int k = 0; k < 3; ++k)
-        if (inventory[k] < 0 || inventory[k] > 2) return "inventory entries must be in [0, 2]";
-    return nullptr;
-}
 inline const char *tb_sweep_error(const int32_t *inventory, const void *aux, const void *table, const void *out, int64_t first, int64_t count,
                                   int k, const void *decided)
 {
@@ -3161,8 +3209,6 @@ inline const char *tb_rows_error(const int32_t *inventory, const void *aux, int6
 }
 
 // ---- tablebase targets (include/gobblet_hip.h, "Tablebase targets"): the scalar pieces of the rule, shared by k_tb_targets and the host flavour
-constexpr int kTbTargetResult = 0, kTbTargetShortest = 1;  // GBL_TB_TARGET_RESULT / _SHORTEST
-constexpr int kTbTargetMaxCount = 600;
 __device__ __forceinline__ int tb_sign(int c) { return (c > 0) - (c < 0); }
 // whether a candidate's result BYTE c (the probe's outcome byte) belongs to the set O of a row of value `value`: R (mode 0, the result
 // kept) or S (mode 1, c == value).  A c(a) of +-128 -- from a table byte of +-127, which no sweep writes -- reads GBL_SOLVE_NONE as a byte
@@ -3171,6 +3217,8 @@ __device__ __forceinline__ bool tb_target_keeps(int c, int value, int mode)
 {
     return c != kSolveNone && (mode == kTbTargetShortest ? c == value : tb_sign(c) == tb_sign(value));
 }
+// a TABLEBASE mover's ply in gbl_collect_search_tb: its value from the probe's V and the sum of its visits row (count on every action of O)
+__device__ __forceinline__ int tb_play_value(int value, int sum) { return tb_sign(value) * 128 * sum; }
 // the order key of an old visit count (0: not positive); the largest key is the argmax, the lowest index on ties
 __device__ __forceinline__ uint32_t tb_visit_key(int v, uint32_t a) { return v > 0 ? ((uint32_t)v << 6) | (63u - a) : 0u; }
 // a labelled row's census byte: `top` the largest tb_visit_key of the old visits (0 without visits_in), `keeps` the set R as bits

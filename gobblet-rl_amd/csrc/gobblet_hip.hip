@@ -3342,6 +3342,116 @@ __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state
         });
 }
 
+// gbl_collect_search_tb: k_collect_solve with the tablebase's probe in front of every ply that is judged or played from the table.
+// The probe is k_tb_probe's on the live planes: lane a < 54 takes action a, its successor's three look-ups go to `aux` in global
+// memory and one byte comes from anywhere in the table (a 64-bit offset); a butterfly gives V and a*.  A TABLEBASE mover's ply is done
+// there -- the set O is a ballot, its visits row a count in O's lanes, the sampled draw search_decide's rule on that row (the running
+// sum through lane a is count times the members of O up to a) -- and neither the solver nor the tree runs; on a board the table does
+// not hold the masked-random sampler moves.  The lane's outcome byte and V stay for the second lambda, which stores the three judge
+// arrays beside k_collect_solve's four (the played action's byte comes from its lane by a shuffle).  SEARCH = false is the launch
+// without an EVAL_TREE side: the solver and the tree are compiled out, and with them their registers -- such a ply is a chain of
+// dependent look-ups that only more resident wavefronts hide.
+struct TbPlay {
+    const uint8_t *aux;
+    const int8_t *table;
+    TbShape S;
+    int mode, count, judge;  // judge: a judge array is given, every ply is probed
+    int8_t *outcome, *value, *played;
+};
+
+template <bool NOISE, bool SEARCH>
+__global__ __launch_bounds__(64) void k_collect_tb(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                   uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
+                                                   int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
+                                                   int32_t *__restrict__ root_value_traj, uint8_t *__restrict__ priors_traj,
+                                                   int8_t *__restrict__ outcome_traj, int8_t *__restrict__ proven_traj,
+                                                   const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
+                                                   uint32_t iterations1, int solve_depth0, int solve_depth1, uint32_t most, uint32_t explore,
+                                                   int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
+                                                   int32_t *__restrict__ turn, uint32_t noise0, uint32_t noise1, const TbPlay tb)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    __shared__ SolveLds s_solve;
+    const uint32_t lane = threadIdx.x;
+    int my_c = kSolveNone, proven = 0;  // the ply's outcome byte of this lane and V, from the first lambda to the second
+    int tb_c = kSolveNone, tb_v = 0;    // ... and the table's
+    search_plies(
+        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            my_c = kSolveNone;
+            proven = 0;
+            tb_c = kSolveNone;
+            tb_v = 0;
+            const int policy = who ? policy1 : policy0;
+            if (tb.judge || policy == kPolicyTablebase) {  // (wave-uniform) the verdict: k_tb_probe of the live planes, no mask
+                const TbAux A = tb_aux(tb.aux);
+                uint64_t cand = legal & tb_piece_actions(tb.S);
+                if (tb_board_index(A, tb.S, B.p, who) < 0) cand = 0;
+                const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
+                if (mine) tb_c = (int)(int8_t)tb_probe_action(A, tb.S, tb.table, B.p, who, lane);  // (the outcome byte: see tb_target_keeps)
+                const uint32_t best = wave_max(mine ? tb_action_key(tb_c, lane) : 0u);
+                tb_v = uniform(tb_value_of(best));
+                if (policy == kPolicyTablebase && best) {
+                    const bool keep = mine && tb_target_keeps(tb_c, tb_v, tb.mode);
+                    const uint64_t kept = (uint64_t)__ballot(keep);
+                    const uint32_t sum = (uint32_t)tb.count * (uint32_t)__popcll(kept);
+                    S.d = SearchDecision{uniform(tb_action_of(best)), kHowTable, tb_play_value(tb_v, (int)sum), keep ? (uint32_t)tb.count : 0u};
+                    if (B.tabs < sample_plies) {
+                        const uint32_t run = (uint32_t)tb.count * (uint32_t)__popcll(kept & ((2ull << lane) - 1ull));
+                        const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), sum);
+                        const uint64_t over = (uint64_t)__ballot(run > k);
+                        S.d.action = over ? (int)__builtin_ctzll(over) : -1;
+                        S.d.how = kHowTableSampled;
+                    }
+                    return true;
+                }
+            }
+            if (!SEARCH || policy != kPolicyEvalTree) return false;
+            if constexpr (SEARCH) {
+                const uint32_t its = who ? iterations1 : iterations0;
+                const int depth = who ? solve_depth1 : solve_depth0;
+                uint64_t cand = legal;
+                if (depth > 0 && legal) {  // (wave-uniform)
+                    const uint32_t best = solve_board<knob::kSolveDeal, false>(s_solve, B.p, who, legal, depth, lane, my_c);
+                    if (depth > 2) solve_fence<false>();  // (before the next ply's solve rewrites the LDS arrays)
+                    proven = uniform(solve_value_of(best));
+                    if (proven) {
+                        const int a = uniform(solve_action_of(best));
+                        S.d = SearchDecision{a, kHowProven, (proven > 0 ? 128 : -128) * (int)its, lane == (uint32_t)a ? its : 0u};
+                        return true;
+                    }
+                    cand = (uint64_t)__ballot(my_c == 0);
+                }
+                uint32_t mixed;  // (the root's own row; the trajectory keeps the network's)
+                const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its,
+                                                                     explore, lane, S.count, RootNoise{who ? noise1 : noise0, seed, g, q}, mixed);
+                S.pi = at_root.pi;
+                S.root_q = at_root.q;
+                S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+                wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            }
+            return true;
+        },
+        [&](int64_t at, const SearchPly &S) {
+            const bool act = lane < (uint32_t)kActions;
+            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
+            if (priors_traj && act) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
+            if (outcome_traj && act) __builtin_nontemporal_store((int8_t)my_c, outcome_traj + at * kActions + lane);
+            if (proven_traj && lane == 0) proven_traj[at] = (int8_t)proven;
+            if (tb.outcome && act) __builtin_nontemporal_store((int8_t)tb_c, tb.outcome + at * kActions + lane);
+            if (tb.value && lane == 0) tb.value[at] = (int8_t)tb_v;
+            if (tb.played) {
+                const int a = uniform(S.d.action);  // (the action the ply played: search_plies steps with the same)
+                const int c = __shfl(tb_c, a < 0 ? 0 : a);
+                if (lane == 0) tb.played[at] = (int8_t)(a < 0 ? kSolveNone : c);
+            }
+        });
+}
+
 // gbl_greedy: one decision per board.  Each lane owns a board (depth-1 walk, order-dependent replay,
 // fallback test), but the depth-2 evaluations -- one moved + legal54 + outcomes54 per (board,
 // candidate) pair, ~95 % of the work -- are pooled over the tile: the boards' candidate lists are
@@ -4829,7 +4939,7 @@ int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const
                                    n, stream);
 }
 
-// The four self-play entry points between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
+// The five self-play entry points between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
 // evaluators as the kernels take them, the trajectory's strides and alignments, the grid, the tree's LDS and the entry's own kernel.
 static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &c, void *stream)
 {
@@ -4846,6 +4956,8 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
                                             : "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned",
                                         c.n, c.plies, c.ply_stride, c.tile_stride, c.state, c.turn, c.counters))
         return e;
+    const bool reads_table = selfplay_reads_table(c);
+    if (reads_table) GBL_ALIGNED(c.aux, "aux");
     const dim3 grid((uint32_t)std::min<int64_t>(c.n, 1 << 20));
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t its0 = (uint32_t)c.iterations[0], its1 = (uint32_t)c.iterations[1], explore = (uint32_t)c.explore;
@@ -4869,6 +4981,24 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
         hipLaunchKernelGGL(k_collect_eval, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
                            c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1], its0,
                            its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn);
+    } else if (c.run == kRunTb) {
+        const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
+                       w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
+        // (a call that never reads the table passes an empty one: no ply probes)
+        const TbPlay tb{static_cast<const uint8_t *>(c.aux), c.table, reads_table ? tb_shape(c.inventory) : TbShape{}, c.tb_mode, c.tb_count,
+                        (t.tb_outcome || t.tb_value || t.tb_played) ? 1 : 0, t.tb_outcome, t.tb_value, t.tb_played};
+#define GBL_CTB(NOISE, SEARCH)                                                                                                            \
+    hipLaunchKernelGGL((k_collect_tb<NOISE, SEARCH>), grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,          \
+                       c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1],       \
+                       c.policy[0], c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies,    \
+                       c.illegal_mode, c.counters, c.turn, w0, w1, tb)
+        if (most == 0)  // (no side searches: the instantiation without the solver and the tree)
+            GBL_CTB(false, false);
+        else if (w0 | w1)
+            GBL_CTB(true, true);
+        else
+            GBL_CTB(false, true);
+#undef GBL_CTB
     } else {
         const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
                        w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
@@ -4897,10 +5027,10 @@ int gbl_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
     return selfplay_launch("gbl_collect_search",
                            {kRunSearch, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr},
+                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {nullptr, nullptr},
                             {iterations0, iterations1}, {playouts0, playouts1}, {0, 0}, {0, 0}, max_plies, explore, sample_plies, illegal_mode,
-                            counters, turn},
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0},
                            stream);
 }
 
@@ -4915,10 +5045,10 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
     return selfplay_launch("gbl_collect_search_eval",
                            {kRunEval, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr},
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn},
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0},
                            stream);
 }
 
@@ -4934,10 +5064,10 @@ int gbl_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32
     return selfplay_launch("gbl_collect_search_solve",
                            {kRunSolve, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn},
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0},
                            stream);
 }
 
@@ -4953,10 +5083,31 @@ int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32
     return selfplay_launch("gbl_collect_search_noise",
                            {kRunSolve, state, to_move, done,
                             {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj},
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn},
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0},
+                           stream);
+}
+
+int gbl_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                          int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                          int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                          uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                          int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                          int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                          int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
+                          int64_t *counters, int32_t *turn, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode,
+                          int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *stream)
+{
+    return selfplay_launch("gbl_collect_search_tb",
+                           {kRunTb, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, tb_outcome_traj,
+                             tb_value_traj, tb_played_traj},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn, inventory, aux, table, tb_mode, tb_count},
                            stream);
 }
 

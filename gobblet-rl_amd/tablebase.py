@@ -145,6 +145,40 @@ class Tablebase(_OnDevice):
             batch["census"] = tally
         return batch
 
+    # ---- the verdict of a collected window -----------------------------------------------------------------------------------------
+    REGRET_CLASSES = ("kept", "win_to_draw", "win_to_loss", "draw_to_loss", "no_verdict")
+
+    def judge(self, traj: dict, boards: int | None = None) -> dict:
+        """What a window collected with ``search=dict(tablebase=..., judge=True)`` did with the truth (torch only, on the trajectory's
+        device).  Adds to ``traj``: "z_exact" int8 per cell, the sign of "tb_value" (``nat.Z_OPEN`` where the table holds no verdict:
+        the outcome row is all ``nat.SOLVE_NONE``), and "regret" int8 per cell: 0 the played action kept the result, 1 a win became a
+        draw, 2 a win became a loss, 3 a draw became a loss, -1 no verdict (also an action that was no candidate).  Returns the counts
+        of each class per side: ``{"player_1": {"kept": ..., "win_to_draw": ..., "win_to_loss": ..., "draw_to_loss": ...,
+        "no_verdict": ...}, "player_2": {...}}``, by "mover".  ``boards``: in the "tile" layout the number of boards of the window
+        (cells past it in the last tile were never written and are not counted)."""
+        for k in ("tb_outcomes", "tb_value", "tb_played", "mover"):
+            if k not in traj:
+                raise ValueError("judge needs the %r entry: buffers from trajectory_buffers(tablebase_outputs=True)" % k)
+        value, played, mover = traj["tb_value"], traj["tb_played"], traj["mover"]
+        none = (traj["tb_outcomes"] == nat.SOLVE_NONE).all(-1)
+        sv, sp = torch.sign(value.to(torch.int16)), torch.sign(played.to(torch.int16))
+        regret = torch.zeros_like(value)
+        regret[(sv == 1) & (sp == 0)] = 1
+        regret[(sv == 1) & (sp == -1)] = 2
+        regret[(sv == 0) & (sp == -1)] = 3
+        regret[none | (played == nat.SOLVE_NONE)] = -1
+        traj["z_exact"] = torch.where(none, torch.full_like(value, nat.Z_OPEN), sv.to(torch.int8))
+        traj["regret"] = regret
+        counted = torch.ones_like(none)
+        if boards is not None and traj.get("_layout") == "tile":
+            tiles, plies = value.shape[0], value.shape[1]
+            counted = (torch.arange(tiles * 64, device=value.device).reshape(tiles, 1, 64) < int(boards)).expand(tiles, plies, 64)
+        out = {}
+        for m, name in enumerate(("player_1", "player_2")):
+            mine = counted & (mover == m)
+            out[name] = {c: int((mine & (regret == (k if k < 4 else -1))).sum()) for k, c in enumerate(self.REGRET_CLASSES)}
+        return out
+
     # ---- files: a header and the raw bytes (never part of the repository: the full table is 2.9 GB) -------------------------------
     def save(self, path) -> None:
         head = json.dumps({"inventory": list(self.inventory), "positions": self.positions, "sweeps": self.sweeps, "complete": self.complete,

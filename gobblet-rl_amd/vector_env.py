@@ -256,13 +256,18 @@ class BatchedGobblet:
 
     # -- trajectory collection: T plies per launch, every ply materialised -------------------------------------
     POLICIES = {"random": nat.POLICY_RANDOM, "greedy1": nat.POLICY_GREEDY1, "greedy": nat.POLICY_GREEDY2,
-                "greedy2": nat.POLICY_GREEDY2, "greedy3": nat.POLICY_GREEDY3, "tree": nat.POLICY_TREE, "evaluator": nat.POLICY_EVAL_TREE}
+                "greedy2": nat.POLICY_GREEDY2, "greedy3": nat.POLICY_GREEDY3, "tree": nat.POLICY_TREE, "evaluator": nat.POLICY_EVAL_TREE,
+                "tablebase": nat.POLICY_TABLEBASE}
 
     def trajectory_buffers(self, plies: int, layout: str = "time", pad_boards: int | None = None,
                            placement: str = "auto", policy_outputs: bool = False, candidates: bool = False,
                            far: bool | None = None, search_outputs: bool = False, evaluator_outputs: bool = False,
-                           solver_outputs: bool = False) -> dict:
+                           solver_outputs: bool = False, tablebase_outputs: bool = False) -> dict:
         """Device tensors for ``collect``.
+
+        tablebase_outputs (with ``evaluator_outputs``): also "tb_outcomes" (int8 (..., 54): the table's result of every action of the
+        ply's position, ``nat.SOLVE_NONE`` where the table holds no verdict), "tb_value" (int8: the position's own result) and
+        "tb_played" (int8: the result of the action the ply played) for ``collect`` with ``search=dict(tablebase=..., judge=True)``.
 
         solver_outputs (with ``evaluator_outputs``): also "outcomes" (int8 (..., 54): the solver's result of every action of the ply's
         position, ``nat.SOLVE_NONE`` where nothing was solved) and "proven" (int8: the position's own result) for ``collect`` with
@@ -365,6 +370,10 @@ class BatchedGobblet:
             if not evaluator_outputs:
                 raise ValueError("solver_outputs belongs to evaluator_outputs=True")
             extra += (("outcomes", torch.int8, (nat.ACTIONS,)), ("proven", torch.int8, ()))
+        if tablebase_outputs:
+            if not evaluator_outputs:
+                raise ValueError("tablebase_outputs belongs to evaluator_outputs=True")
+            extra += (("tb_outcomes", torch.int8, (nat.ACTIONS,)), ("tb_value", torch.int8, ()), ("tb_played", torch.int8, ()))
         for key, dtype, tail in (("actions", torch.int32, ()), ("winner", torch.int8, ()), ("rewards", torch.int8, (2,)),
                                  ("done", torch.int8, ()), ("to_move", torch.int8, ())) + extra:
             full[key] = torch.zeros(lead + tail, dtype=dtype, device=dev)
@@ -444,24 +453,36 @@ class BatchedGobblet:
         ``search=dict(..., noise=x)`` (a share in [0, 1], or a pair, one per side; 0 or absent: none; a policy instance brings its
         own) mixes a random row into the ROOT's prior row of every search of an evaluator side, keyed by (seed, board id, ply)
         (``gbl_collect_search_noise``): the exploration of self-play.  An arena passes no noise, or noises one side only.  "priors"
-        stays the network's row; ``root_noise`` recomputes the random one."""
+        stays the network's row; ``root_noise`` recomputes the random one.
+
+        A side "tablebase" (or a ``TablebaseGobbletPolicy`` instance, which supplies its table) plays from the exact table INSIDE the
+        launch (``gbl_collect_search_tb``), against "tablebase", "evaluator" or "random": ``search=dict(..., tablebase=tb,
+        tb_mode="result" | "shortest", tb_count=1, judge=False, allow_incomplete=False)``.  Its ply takes the probe's action
+        ("how" = ``nat.HOW_TABLE``) or, while ``turn < sample_plies``, one of the set ``tb_mode`` names at random
+        (``nat.HOW_TABLE_SAMPLED``); its visits row holds ``tb_count`` on that set -- ``Tablebase.targets``' label, written as the game
+        is played; on a board the table does not hold it moves as "random".  ``judge=True`` (with or without a table side) also
+        writes the table's verdict of EVERY ply into buffers made with ``tablebase_outputs=True``: "tb_outcomes" / "tb_value" /
+        "tb_played"; ``Tablebase.judge`` turns them into exact value targets and a census of the results thrown away.  Calls
+        without a table side and without ``judge`` keep their entry points."""
         if not self.auto_reset:
             raise ValueError("collect() plays with auto-reset; this environment was created with auto_reset=False")
         T = int(plies)
-        ep = self._evaluator_params(policies, search)  # None unless a side plays the evaluator-guided search
+        tp = self._tablebase_params(policies, search)  # None unless a side plays from the table or the table judges
+        ep = tp["ep"] if tp is not None else self._evaluator_params(policies, search)  # None unless a side plays the evaluator-guided search
         sp = ep if ep is not None else self._search_params(policies, search)  # None unless a side plays a tree search
         guarded = ep is not None and any(ep["solve_depth"])  # (the solver in front of an evaluator side's searches)
+        judged = tp is not None and tp["judge"]
         def fresh():  # buffers for this call's entry point, made (and placed) now
             return self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
                                            search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
-                                           far=False)
+                                           tablebase_outputs=judged, far=False)
         if isinstance(out, str):
             if out != "fresh":
                 raise ValueError("out: a dict from trajectory_buffers(), None (the environment's staging buffers) or 'fresh'")
             out = fresh()  # the caller's own: not kept by the environment, never overwritten by a later call
         if out is None:
             key = (T, layout, policies is not None) + (("search",) if sp is not None else ()) + (("evaluator",) if ep is not None else ()) + \
-                (("solver",) if guarded else ())
+                (("solver",) if guarded else ()) + (("tablebase",) if judged else ())
             out = self._staging.pop(key, None)
             made = out is None
             if made:
@@ -495,7 +516,11 @@ class BatchedGobblet:
                 raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
             # one argument list for the four self-play entry points: any noise weight -> _noise (the guarded kernel, whatever the
             # depths), else any solve depth -> _solve, else an evaluator side -> _eval, else the UCT search
-            entry = "gbl_collect_search" + ("" if ep is None else "_noise" if any(ep["noise"]) else "_solve" if guarded else "_eval")
+            # a table side or the judge -> _tb (the noise entry point's list, then the table's)
+            entry = "gbl_collect_search" + ("_tb" if tp is not None else "" if ep is None else "_noise" if any(ep["noise"]) else
+                                            "_solve" if guarded else "_eval")
+            if judged and "tb_value" not in f:
+                raise ValueError("judge=True needs buffers from trajectory_buffers(tablebase_outputs=True)")
             args = [self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
                     f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
                     f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
@@ -503,7 +528,7 @@ class BatchedGobblet:
             if ep is None:
                 sides = [*sp["iterations"], *sp["playouts"], sp["max_plies"]]
             else:
-                solver, noise = not entry.endswith("_eval"), entry.endswith("_noise")
+                solver, noise = not entry.endswith("_eval"), entry.endswith(("_noise", "_tb"))
                 structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
                 args += [nat.ptr(f.get(k)) for k in ("root_value", "priors") + (("outcomes", "proven") if solver else ())]
                 sides = [*[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
@@ -511,7 +536,10 @@ class BatchedGobblet:
             nat.check(getattr(self._lib, entry)(
                 *args, n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T,
                 *sp["policies"], *sides, sp["explore"], sp["sample_plies"], self.illegal_mode,
-                self._counters.data_ptr() if count else None, nat.ptr(self.turn), self._stream()), entry)
+                self._counters.data_ptr() if count else None, nat.ptr(self.turn),
+                *(() if tp is None else (tp["inventory"], tp["aux"], tp["table"], tp["mode"], tp["count"],
+                                         *(nat.ptr(f.get(k)) if judged else None for k in ("tb_outcomes", "tb_value", "tb_played")))),
+                self._stream()), entry)
         elif policies is not None:
             try:
                 p0, p1 = (self.POLICIES[x] if isinstance(x, str) else int(x) for x in policies)
@@ -673,6 +701,58 @@ class BatchedGobblet:
             raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
         return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
                     solve_depth=deps, noise=nzs)
+
+    def _tablebase_params(self, policies, search):
+        """The table's arguments of ``gbl_collect_search_tb`` and, under "ep", the rest of the call as ``_evaluator_params`` returns it
+        (a table side stands there with its own policy code); None unless a side of ``policies`` plays from the table or
+        ``search=dict(judge=True)``."""
+        from .tablebase import Tablebase, TablebaseGobbletPolicy
+        if policies is None or isinstance(policies, str):
+            return None
+        sides = list(policies)
+
+        def is_tb(x):
+            return isinstance(x, TablebaseGobbletPolicy) or x == "tablebase" or \
+                (isinstance(x, int) and not isinstance(x, bool) and x == nat.POLICY_TABLEBASE)
+        tbs = [is_tb(x) for x in sides]
+        judge = bool((search or {}).get("judge", False))
+        if len(sides) != 2 or not (any(tbs) or judge):
+            if (search or {}).get("tablebase") is not None:
+                raise ValueError("search: tablebase= belongs to a pair of policies with a 'tablebase' side, or to judge=True")
+            return None
+        rest = {k: v for k, v in (search or {}).items() if k not in ("tablebase", "tb_mode", "tb_count", "judge", "allow_incomplete")}
+        kw = {**dict(tablebase=None, tb_mode="result", tb_count=1, allow_incomplete=False), **{k: v for k, v in (search or {}).items() if k not in rest}}
+        tb = kw["tablebase"]
+        for x in sides:
+            if isinstance(x, TablebaseGobbletPolicy):
+                if tb is not None and tb is not x.tb:
+                    raise ValueError("one launch reads one table: the policy instance's and search=dict(tablebase=...) differ")
+                tb = x.tb
+        if not isinstance(tb, Tablebase):
+            raise ValueError("search: a 'tablebase' side (or judge=True) needs search=dict(tablebase=Tablebase ...)")
+        if tb.device != self.device:
+            raise ValueError("the table lives on %s and the environment on %s" % (tb.device, self.device))
+        if not tb.complete and not kw["allow_incomplete"]:
+            raise ValueError("the table is not complete: a 0 would read 'not proven yet' (allow_incomplete=True to play from it anyway)")
+        if kw["tb_mode"] not in nat.TB_TARGET_MODES:
+            raise ValueError("search: tb_mode is 'result' or 'shortest'")
+        if not 1 <= int(kw["tb_count"]) <= nat.TB_TARGET_MAX_COUNT:
+            raise ValueError("search: tb_count must be in [1, %d]" % nat.TB_TARGET_MAX_COUNT)
+        others = ["random" if t else x for t, x in zip(tbs, sides)]
+        ep = self._evaluator_params(others, rest or None)
+        if ep is None:  # no evaluator side: the table against itself or against "random"
+            if not all(self._is_random(x) for x in others):
+                raise ValueError("policies: the table plays against 'tablebase', 'evaluator' or 'random' inside one launch (not %r)" % (sides,))
+            unknown = set(rest) - {"sample_plies", "evaluator", "iterations", "explore", "solve_depth", "noise"}
+            if unknown:
+                raise ValueError("search: unknown keys %s" % sorted(unknown))
+            if int(rest.get("sample_plies", 0)) < 0:
+                raise ValueError("search: sample_plies >= 0")
+            ep = dict(policies=[nat.POLICY_RANDOM] * 2, evaluators=[None, None], iterations=[0, 0], explore=16,
+                      sample_plies=int(rest.get("sample_plies", 0)), solve_depth=[0, 0], noise=[0, 0])
+        ep["policies"] = [nat.POLICY_TABLEBASE if t else c for t, c in zip(tbs, ep["policies"])]
+        return dict(ep=ep, judge=judge, tb=tb, inventory=tb._inv, aux=tb._aux.data_ptr(), table=tb.table.data_ptr(),
+                    mode=nat.TB_TARGET_MODES[kw["tb_mode"]], count=int(kw["tb_count"]))
 
     def outcome_targets(self, traj: dict) -> dict:
         """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128

@@ -934,6 +934,48 @@ int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *tabl
                    int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int8_t *z_out,
                    int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out, int64_t n, void *stream);
 
+/* Self-play with the tablebase (no counterpart in the reference): gbl_collect_search_noise with the exact table inside the launch, as a
+ * third policy for either side and as a judge of every ply.  The arguments are gbl_collect_search_noise's, then
+ *   inventory / aux / table   as gbl_tb_probe takes them (the table complete or not: a 0 reads "not proven by the sweeps done")
+ *   tb_mode / tb_count        gbl_tb_targets' mode (the set O) and count, 1 .. 600
+ *   tb_outcome_traj int8[cells][54] / tb_value_traj int8[cells] / tb_played_traj int8[cells]   the judge arrays (each may be NULL, none
+ *                             needs an alignment)
+ * A side's policy is GBL_POLICY_RANDOM, GBL_POLICY_EVAL_TREE or GBL_POLICY_TABLEBASE.  The rule is gbl_collect_search_noise's text with
+ * two additions.
+ *   The verdict of a ply.  Where a judge array is given or the ply's mover is TABLEBASE: (outcome[54], V, a*) = gbl_tb_probe(inventory,
+ *     aux, table, state, to_move, mask = NULL) of the position before the move, as its mover sees it.  tb_outcome_traj[cell] = the outcome
+ *     row (54 times GBL_SOLVE_NONE where the board is no state of the inventory or has no candidate); tb_value_traj[cell] = V;
+ *     tb_played_traj[cell] = outcome[action] of the action the ply played, GBL_SOLVE_NONE where that action is -1 or no candidate.  The
+ *     cell is outcome_traj's: ply t's cell describes ply t's position and mover.
+ *   A TABLEBASE mover, a* >= 0.  With R, S and O as gbl_tb_targets defines them from (outcome, V, tb_mode): the visits row holds
+ *     tb_count on O and 0 elsewhere; value = sign(V) * 128 * (the row's sum); nodes = 0, root_value = 0, the prior row zeros, the
+ *     solver's outcome row GBL_SOLVE_NONE and proven 0.  The action is a* with how = GBL_HOW_TABLE or, while turn[b] < sample_plies,
+ *     the visit-proportional draw over that row on stream 4 (gbl_collect_search's rule: k = (r * sum) >> 32, the first action whose
+ *     running sum exceeds k, -1 on an empty row) with how = GBL_HOW_TABLE_SAMPLED: uniform over O.  Nothing else is drawn.  A c(a)
+ *     of -+128 counts for V and a* and belongs to neither set, as in gbl_tb_targets.
+ *   A TABLEBASE mover, a* == -1 (a board outside the inventory, a root without a candidate): exactly a RANDOM side's ply -- the
+ *     masked-random draw, how = GBL_HOW_RANDOM, a zero visits row.
+ * An EVAL_TREE side keeps its guard, noise, iterations and evaluator; a TABLEBASE side's are not read, as a RANDOM side's.  With no
+ * TABLEBASE side and the three judge arrays NULL every array is gbl_collect_search_noise's, bit for bit, and inventory / aux / table may
+ * be NULL.  Errors: gbl_collect_search_noise's order, with (GBL_ERR_ARG) a policy outside the three where it reports a policy, then
+ * after its depth check tb_mode, tb_count and -- only where a side is TABLEBASE or a judge array is given -- the inventory (NULL, an
+ * entry outside 0 .. 2), all before the noise weights; a missing aux, then a missing table, after the three board arrays.  The device
+ * flavour asks aux to be 16-byte aligned (GBL_ERR_ALIGN, with the other alignment rules, which are gbl_collect_search_noise's).
+ * Nothing about the table's completeness is checked.  Every offset into the table is 64-bit.  gbl_outcome_targets, gbl_training_batch
+ * and gbl_replay_append work on these trajectories unchanged.  Allocates nothing. */
+#define GBL_POLICY_TABLEBASE 6
+#define GBL_HOW_TABLE 6
+#define GBL_HOW_TABLE_SAMPLED 7
+int gbl_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                          int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                          int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                          uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                          int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                          int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                          int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
+                          int64_t *counters, int32_t *turn, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode,
+                          int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *stream);
+
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
  *   GBL_COLLECT_STREAM  k_collect,  one wavefront per tile of 64 boards, trajectory rows stored non-temporally
