@@ -42,6 +42,7 @@ POLICY_TABLEBASE, HOW_TABLE, HOW_TABLE_SAMPLED = 6, 6, 7  # gbl_collect_search_t
 SYMMETRIES, BATCH_ATTEMPTS = 512, 16  # gbl_symmetry_apply / gbl_training_batch
 REPLAY_OBS_PITCH, REPLAY_VISITS_PITCH, REPLAY_META_PITCH = 128, 64, 64  # gbl_replay_append / gbl_replay_batch: the ring's row pitches
 REPLAY_META_Z, REPLAY_META_MOVER, REPLAY_META_TAG, STREAM_REPLAY = 54, 55, 56, 7
+STREAM_REPLAY_PRIO = 8  # gbl_replay_batch_prio's draws
 TB_TERMINAL, TB_MAX_SWEEP, TB_AUX_BYTES = -128, 126, 63120  # gbl_tb_*
 TB_TARGET_MODES, TB_TARGET_MAX_COUNT = {"result": 0, "shortest": 1}, 600  # gbl_tb_targets
 STATUS_ILLEGAL, STATUS_OUT_OF_RANGE = 1, 2  # gbl_step_ex / gbl_collect_from_ex status bits
@@ -108,6 +109,11 @@ SIGNATURES = {
     "gbl_replay_workspace_bytes": (C.c_size_t, [_i64, _u32]),
     "gbl_replay_append": (_int, [_vp] * 6 + [_i64, _u32, _i64, _i64, C.c_int32] + [_vp] * 3 + [_i64, _vp, _vp, C.c_size_t, _vp]),
     "gbl_replay_batch": (_int, [_vp] * 3 + [_i64, _vp, _i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),
+    "gbl_replay_prio_index_bytes": (C.c_size_t, [_i64]),
+    "gbl_replay_prio_append": (_int, [_vp] * 4 + [C.c_int32, _i64, _u32, _i64, _i64, _vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "gbl_replay_prio_update": (_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "gbl_replay_prio_index": (_int, [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "gbl_replay_batch_prio": (_int, [_vp] * 3 + [_i64] + [_vp] * 5 + [_i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),
     "gbl_tb_layout": (_int, [_vp, _vp]),
     "gbl_tb_prepare": (_int, [_vp, _vp, _vp]),
     "gbl_tb_sweep": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp]),
@@ -248,7 +254,8 @@ CPU_SOURCES = [os.path.join(CSRC, "gobblet_cpu.cpp"), os.path.join(CSRC, "gobble
 CPU_CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"] + \
                 (["-mpopcnt"] if platform.machine() in ("x86_64", "AMD64") else [])
 _NO_HOST_FLAVOUR = ("gbl_pinned_alloc", "gbl_pinned_free", "gbl_block_alloc", "gbl_block_free", "gbl_device_memory",
-                    "gbl_placement_probe", "gbl_collect_variant", "gbl_train_workspace_bytes", "gbl_replay_workspace_bytes", "gbl_tb_layout")
+                    "gbl_placement_probe", "gbl_collect_variant", "gbl_train_workspace_bytes", "gbl_replay_workspace_bytes", "gbl_replay_prio_index_bytes",
+                    "gbl_tb_layout")
 CPU_SIGNATURES = {"gbl_cpu_" + k[4:]: v for k, v in SIGNATURES.items() if k not in _NO_HOST_FLAVOUR}
 CPU_SIGNATURES["gbl_cpu_set_threads"] = (_int, [_int])
 

@@ -1434,6 +1434,107 @@ int gbl_cpu_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, con
     return GBL_OK;
 }
 
+// Prioritised replay as the header's paragraph reads.  The append's cells are enumerated again (the workspace is checked and not used);
+// the index has the device flavour's layout, built by one walk over the slots; a draw is replay_prio_span and replay_prio_draw, the pieces
+// the kernel uses.
+int gbl_cpu_replay_prio_append(const int16_t *visits_traj, const int8_t *z_traj, const int8_t *done_traj, const int32_t *prio_traj, int32_t value,
+                               int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride, int32_t *ring_prio, int64_t capacity,
+                               const uint64_t *ring_state, const void *workspace, size_t workspace_bytes, void *)
+{
+    if (const char *why = replay_prio_append_error(visits_traj, z_traj, done_traj, n, plies, ply_stride, tile_stride, ring_prio, capacity,
+                                                   ring_state, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    const uint64_t K = ring_state[1], T0 = ring_state[0] - K, cap = (uint64_t)capacity;
+    uint64_t R = 0;
+    for (uint32_t t = 1; t < plies; ++t) {
+        for (int64_t b = 0; b < n; ++b) {
+            const int64_t at = traj_cell(t, b, ply_stride, tile_stride);
+            if (!batch_valid(z_traj, done_traj, visits_traj, at, traj_cell((int64_t)t - 1, b, ply_stride, tile_stride))) continue;
+            const uint64_t r = R++;
+            if (replay_kept(r, K, cap)) ring_prio[replay_slot(T0, r, cap)] = prio_traj ? prio_traj[at] : value;
+        }
+    }
+    return GBL_OK;
+}
+
+int gbl_cpu_replay_prio_update(const int32_t *index, const int32_t *values, int64_t batch, int32_t *ring_prio, int64_t capacity, void *)
+{
+    if (const char *why = replay_prio_update_error(index, values, batch, ring_prio, capacity)) return fail(GBL_ERR_ARG, why);
+    const auto named = [=](int64_t j) { return index[2 * j] >= 0 && (int64_t)index[2 * j] < capacity; };
+    for (int64_t j = 0; j < batch; ++j)
+        if (named(j)) ring_prio[index[2 * j]] = INT32_MIN;
+    for (int64_t j = 0; j < batch; ++j)
+        if (named(j)) ring_prio[index[2 * j]] = std::max(ring_prio[index[2 * j]], values[j]);
+    return GBL_OK;
+}
+
+int gbl_cpu_replay_prio_index(const int32_t *ring_prio, int64_t capacity, const uint64_t *ring_state, void *prio_index, size_t index_bytes, void *)
+{
+    if (const char *why = replay_prio_index_error(ring_prio, capacity, ring_state, prio_index, index_bytes)) return fail(GBL_ERR_ARG, why);
+    uint64_t *index = static_cast<uint64_t *>(prio_index);
+    const uint64_t total = ring_state[0], cap = (uint64_t)capacity, live = std::min(total, cap);
+    const uint64_t leaves = replay_prio_leaves(cap), blocks = replay_prio_blocks(cap);
+    uint64_t *base = index + kReplayPrioHead, *local = base + blocks + 1u;
+    uint64_t acc = 0, in_block = 0;
+    for (uint64_t L = 0; L < leaves; ++L) {
+        if (L % kReplayBlockLeaves == 0) {
+            base[L / kReplayBlockLeaves] = acc;
+            in_block = 0;
+        }
+        local[L] = in_block;
+        uint64_t leaf = 0;
+        for (uint64_t s = L * kReplayLeaf; s < std::min((L + 1) * kReplayLeaf, live); ++s) leaf += replay_weight(ring_prio[s]);
+        acc += leaf;
+        in_block += leaf;
+    }
+    base[blocks] = acc;
+    index[0] = total;
+    index[1] = acc;
+    return GBL_OK;
+}
+
+int gbl_cpu_replay_batch_prio(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                              const uint64_t *ring_state, const int32_t *ring_prio, const void *prio_index, int32_t *prio_out,
+                              uint64_t *total_out, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
+                              uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
+                              int16_t *sym_out, void *)
+{
+    if (const char *why = replay_batch_prio_error(ring_obs, ring_visits, ring_meta, capacity, ring_state, ring_prio, prio_index, recent, batch,
+                                                  sym_mask, call, obs_out, index_out))
+        return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    const uint64_t *index = static_cast<const uint64_t *>(prio_index);
+    const ReplayPrioSpan P = replay_prio_span(ring_prio, index, ring_state[0], (uint64_t)capacity, recent);
+    if (total_out) { total_out[0] = P.W; total_out[1] = P.span; }
+    parallel_for(batch, [=](int64_t j0, int64_t j1) {
+        for (int64_t j = j0; j < j1; ++j) {
+            const ReplayPrioDraw d = replay_prio_draw(seed, sample_base + (uint64_t)j, call, P, (uint64_t)capacity, ring_prio, index);
+            const bool ok = d.slot >= 0;
+            const uint32_t code = ok ? d.sym & (uint32_t)sym_mask : 0u;
+            const int8_t *meta = ring_meta + (ok ? d.slot : 0) * kReplayMetaPitch;
+            int32_t tag = -1;
+            if (ok) memcpy(&tag, meta + kReplayMetaTag, 4);
+            index_out[2 * j] = ok ? (int32_t)d.slot : -1;
+            index_out[2 * j + 1] = tag;
+            if (prio_out) prio_out[j] = (int32_t)d.weight;
+            if (z_out) z_out[j] = ok ? meta[kReplayMetaZ] : (int8_t)kZOpen;
+            if (sym_out) sym_out[j] = (int16_t)code;
+            if (!ok) {
+                if (obs_out) memset(obs_out + j * kObs, 0, kObs);
+                if (mask_out) memset(mask_out + j * kActions, 0, kActions);
+                if (visits_out) memset(visits_out + j * kActions, 0, 2 * kActions);
+                continue;
+            }
+            const Sym S = sym_of(code);
+            const uint32_t m = meta[kReplayMetaMover] != 0;
+            if (obs_out) sym_obs_row(ring_obs + d.slot * kReplayObsPitch, obs_out + j * kObs, S, m);
+            if (mask_out) sym_action_row(meta, mask_out + j * kActions, S, m);
+            if (visits_out) sym_action_row(ring_visits + d.slot * kReplayVisitsPitch, visits_out + j * kActions, S, m);
+        }
+    });
+    return GBL_OK;
+}
+
 // The tablebase (include/gobblet_hip.h, "Exact tablebase"): the header's rule position by position, with the shared pieces of
 // gobblet_device.h.  aux, table and decided are host memory.
 int gbl_cpu_tb_prepare(const int32_t *inventory, void *aux, void *)

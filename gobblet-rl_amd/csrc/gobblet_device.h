@@ -2945,6 +2945,202 @@ inline const char *replay_batch_error(const void *ring_obs, const void *ring_vis
     return nullptr;
 }
 
+// ---- prioritised replay (include/gobblet_hip.h, "Replay buffer", the priorities' paragraph) -----------------------------------------
+// A leaf is 32 consecutive slots (one 128-byte line of ring_prio), a block 64 consecutive leaves (2 048 slots).  prio_index in uint64s:
+//   [0] the ring_state[0] it was built for, [1] the weight of all live rows,
+//   base[0 .. nblocks]   base[b] = the weight of the live slots of blocks 0 .. b - 1,
+//   local[0 .. nleaves)  local[L] = the weight of the live slots of the leaves of L's block that lie before L.
+// Two levels so that the build is two short launches: every block's local prefix by a workgroup of its own, then one scan over the blocks.
+constexpr uint32_t kStreamReplayPrio = 8u;  // generator stream of gbl_replay_batch_prio's draws
+constexpr int kReplayLeaf = 32, kReplayBlockLeaves = 64, kReplayPrioHead = 2;
+constexpr uint64_t replay_prio_leaves(uint64_t capacity) { return (capacity + kReplayLeaf - 1) / kReplayLeaf; }
+constexpr uint64_t replay_prio_blocks(uint64_t capacity) { return (replay_prio_leaves(capacity) + kReplayBlockLeaves - 1) / kReplayBlockLeaves; }
+inline uint64_t replay_prio_index_bytes(int64_t capacity)
+{
+    if (capacity < 1 || capacity > kReplayMaxCapacity) return 0u;
+    return 8u * (kReplayPrioHead + replay_prio_blocks((uint64_t)capacity) + 1u + replay_prio_leaves((uint64_t)capacity));
+}
+__device__ __forceinline__ uint64_t replay_weight(int32_t p) { return p > 0 ? (uint64_t)p : 0u; }
+// floor(a b / 2^64) from the four 32 x 32 products (plain C++: the same text serves the kernels, the host flavour and the emulation)
+__device__ __forceinline__ uint64_t replay_mulhi64(uint64_t a, uint64_t b)
+{
+    const uint64_t a0 = (uint32_t)a, a1 = a >> 32, b0 = (uint32_t)b, b1 = b >> 32;
+    const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const uint64_t mid = (p00 >> 32) + (uint32_t)p01 + (uint32_t)p10;
+    return p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+}
+
+struct ReplayPrioIndex {
+    const uint64_t *base, *local;
+    uint64_t leaves, blocks;
+};
+__device__ __forceinline__ ReplayPrioIndex replay_prio_view(const uint64_t *index, uint64_t capacity)
+{
+    const uint64_t blocks = replay_prio_blocks(capacity);
+    return ReplayPrioIndex{index + kReplayPrioHead, index + kReplayPrioHead + blocks + 1u, replay_prio_leaves(capacity), blocks};
+}
+
+// the 32 entries of the leaf that starts at slot s as weights, 0 for slots that are not live: a whole leaf comes in as eight 16-byte
+// vectors (independent loads: one trip to memory), the ragged last leaf of the array entry by entry
+__device__ __forceinline__ void replay_leaf_weights(const int32_t *__restrict__ prio, uint64_t s, uint64_t capacity, uint64_t live, uint32_t w[kReplayLeaf])
+{
+    if (s + kReplayLeaf <= capacity) {
+        const uint4 *v = reinterpret_cast<const uint4 *>(prio + s);
+#pragma unroll
+        for (int i = 0; i < kReplayLeaf / 4; ++i) {
+            const uint4 p = v[i];
+            w[4 * i] = p.x; w[4 * i + 1] = p.y; w[4 * i + 2] = p.z; w[4 * i + 3] = p.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < kReplayLeaf; ++i) w[i] = s + i < capacity ? (uint32_t)prio[s + i] : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < kReplayLeaf; ++i) w[i] = s + i < live ? (uint32_t)replay_weight((int32_t)w[i]) : 0u;
+}
+
+// the weight of the live slots below slot x (x <= capacity): the block's base, the leaf's local prefix and at most 31 entries of the leaf
+__device__ __forceinline__ uint64_t replay_prio_prefix(const int32_t *__restrict__ prio, const ReplayPrioIndex &I, uint64_t x, uint64_t capacity,
+                                                       uint64_t live)
+{
+    const uint64_t leaf = x / kReplayLeaf;
+    if (leaf == I.leaves) return I.base[I.blocks];  // (x == capacity, a multiple of 32)
+    uint64_t acc = I.base[leaf / kReplayBlockLeaves] + I.local[leaf];
+    const uint32_t k = (uint32_t)(x % kReplayLeaf);
+    if (k == 0) return acc;
+    uint32_t w[kReplayLeaf];
+    replay_leaf_weights(prio, leaf * kReplayLeaf, capacity, live, w);
+#pragma unroll
+    for (int i = 0; i < kReplayLeaf - 1; ++i) acc += (uint32_t)i < k ? w[i] : 0u;
+    return acc;
+}
+
+// what is the same for every sample of a launch: the span, its weight W (0: every sample fails), and where the span's order starts in
+// the ring's prefix -- the span is the slots [first, capacity) and then [0, ...) when it crosses the ring's end: the prefix value `base` of
+// its first slot and the weight `head` of its first range (W when it does not cross).
+struct ReplayPrioSpan {
+    uint64_t live, span, W, base, head;
+};
+__device__ __forceinline__ ReplayPrioSpan replay_prio_span(const int32_t *__restrict__ prio, const uint64_t *__restrict__ index, uint64_t total,
+                                                           uint64_t capacity, int64_t recent)
+{
+    const uint64_t live = total < capacity ? total : capacity;
+    const uint64_t span = recent > 0 && (uint64_t)recent < live ? (uint64_t)recent : live;
+    ReplayPrioSpan P{live, span, 0u, 0u, 0u};
+    if (live == 0 || index[0] != total) return P;
+    const ReplayPrioIndex I = replay_prio_view(index, capacity);
+    if (span == live) {  // (every live row: the build left the sum)
+        P.W = index[1];
+        const uint64_t first = total < capacity ? 0u : total % capacity;
+        P.base = first ? replay_prio_prefix(prio, I, first, capacity, live) : 0u;
+        P.head = P.W - P.base;
+        return P;
+    }
+    const uint64_t first = (total - span) % capacity;
+    P.base = replay_prio_prefix(prio, I, first, capacity, live);
+    if (first + span <= capacity) {
+        P.head = P.W = replay_prio_prefix(prio, I, first + span, capacity, live) - P.base;
+    } else {
+        P.head = index[1] - P.base;  // (the ring has wrapped: the first range runs to the ring's end)
+        P.W = P.head + replay_prio_prefix(prio, I, first + span - capacity, capacity, live);
+    }
+    return P;
+}
+
+// sample `id` of gbl_replay_batch_prio: the slot (-1: a failed sample), its weight and its symmetry word.  With a fresh index the target is
+// below the ring's whole weight and the walk ends inside the leaf; with a stale one the slot is still inside [0, capacity).
+struct ReplayPrioDraw {
+    int64_t slot;
+    uint32_t weight, sym;
+};
+__device__ __forceinline__ ReplayPrioDraw replay_prio_draw(uint64_t seed, uint64_t id, uint32_t call, const ReplayPrioSpan &P, uint64_t capacity,
+                                                           const int32_t *__restrict__ prio, const uint64_t *__restrict__ index)
+{
+    const Draw4 d = draw_block(seed, id, 4u * ((uint32_t)kBatchAttempts * call), kStreamReplayPrio);
+    if (P.W == 0) return ReplayPrioDraw{-1, 0u, 0u};
+    const uint64_t r = replay_mulhi64(((uint64_t)d.w[0] << 32) | d.w[1], P.W);
+    const uint64_t target = r < P.head ? P.base + r : r - P.head;  // (in the ring's own prefix: the slot is the first whose prefix passes it)
+    const ReplayPrioIndex I = replay_prio_view(index, capacity);
+    uint64_t lo = 0, hi = I.blocks;  // the last block whose base does not pass the target ...
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (I.base[mid] <= target) lo = mid; else hi = mid;
+    }
+    const uint64_t in_block = target - I.base[lo];
+    hi = (lo + 1u) * kReplayBlockLeaves < I.leaves ? (lo + 1u) * kReplayBlockLeaves : I.leaves;
+    lo *= kReplayBlockLeaves;  // ... and in it the last leaf whose local prefix does not
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (I.local[mid] <= in_block) lo = mid; else hi = mid;
+    }
+    const uint64_t s = lo * kReplayLeaf, in_leaf = in_block - I.local[lo];
+    uint32_t w[kReplayLeaf];
+    replay_leaf_weights(prio, s, capacity, P.live, w);
+    uint64_t acc = 0;
+    uint32_t at = 0, weight = w[0];  // (a stale index may pass no entry: the leaf's first slot, inside [0, capacity))
+    bool found = false;
+#pragma unroll
+    for (int i = 0; i < kReplayLeaf; ++i) {
+        acc += w[i];
+        if (!found && acc > in_leaf) { found = true; at = (uint32_t)i; weight = w[i]; }
+    }
+    return ReplayPrioDraw{(int64_t)(s + at), weight, d.w[2]};
+}
+
+inline const char *replay_prio_append_error(const void *visits_traj, const void *z_traj, const void *done_traj, int64_t n, uint32_t plies,
+                                            int64_t ply_stride, int64_t tile_stride, const void *ring_prio, int64_t capacity,
+                                            const void *ring_state, const void *workspace, uint64_t workspace_bytes)
+{
+    if (plies < 2u || plies > 32767u) return "plies must be in [2, 32767]";
+    if (n < 1 || n > ((int64_t)1 << 31)) return "n must be in [1, 2^31]";
+    if (capacity < 1 || capacity > kReplayMaxCapacity) return "capacity must be in [1, 2^31 - 1]";
+    if (!visits_traj) return "visits_traj must not be NULL";
+    if (!z_traj) return "z_traj must not be NULL";
+    if (!done_traj) return "done_traj must not be NULL";
+    if (!ring_prio) return "ring_prio must not be NULL";
+    if (!ring_state) return "ring_state must not be NULL";
+    if (!workspace) return "workspace must not be NULL";
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return kStridesMessage;
+    if (workspace_bytes < replay_workspace_bytes(n, plies)) return "workspace_bytes is below gbl_replay_workspace_bytes";
+    return nullptr;
+}
+
+// (batch == 0 returns GBL_OK after the scalar checks)
+inline const char *replay_prio_update_error(const void *index, const void *values, int64_t batch, const void *ring_prio, int64_t capacity)
+{
+    if (capacity < 1 || capacity > kReplayMaxCapacity) return "capacity must be in [1, 2^31 - 1]";
+    if (batch < 0 || batch > ((int64_t)1 << 31)) return "batch must be in [0, 2^31]";
+    if (batch == 0) return nullptr;
+    if (!index) return "index must not be NULL";
+    if (!values) return "values must not be NULL";
+    if (!ring_prio) return "ring_prio must not be NULL";
+    return nullptr;
+}
+
+inline const char *replay_prio_index_error(const void *ring_prio, int64_t capacity, const void *ring_state, const void *prio_index,
+                                           uint64_t index_bytes)
+{
+    if (capacity < 1 || capacity > kReplayMaxCapacity) return "capacity must be in [1, 2^31 - 1]";
+    if (!ring_prio) return "ring_prio must not be NULL";
+    if (!ring_state) return "ring_state must not be NULL";
+    if (!prio_index) return "prio_index must not be NULL";
+    if (index_bytes < replay_prio_index_bytes(capacity)) return "index_bytes is below gbl_replay_prio_index_bytes";
+    return nullptr;
+}
+
+// gbl_replay_batch's checks, and with batch > 0 the two blocks of the priorities
+inline const char *replay_batch_prio_error(const void *ring_obs, const void *ring_visits, const void *ring_meta, int64_t capacity,
+                                           const void *ring_state, const void *ring_prio, const void *prio_index, int64_t recent, int64_t batch,
+                                           int sym_mask, uint32_t call, const void *obs_out, const void *index_out)
+{
+    if (const char *why = replay_batch_error(ring_obs, ring_visits, ring_meta, capacity, ring_state, recent, batch, sym_mask, call, obs_out, index_out))
+        return why;
+    if (batch == 0) return nullptr;
+    if (!ring_prio) return "ring_prio must not be NULL";
+    if (!prio_index) return "prio_index must not be NULL";
+    return nullptr;
+}
+
 // ---- tablebase (include/gobblet_hip.h, "Exact tablebase"): the rule's pieces, shared by the kernels and the host flavour ---------------
 // A position is two 27-bit cell sets, the mover's (`own`) and the other side's (`oth`), level k in bits 9k .. 9k + 8.  Its index comes
 // from three table look-ups (one per level: the rank of the level's ternary number), its successors from bit arithmetic on the

@@ -2735,6 +2735,169 @@ __global__ __launch_bounds__(64) void k_replay_batch(ReplayBatchArgs A)
                                                                       A.visits_out, s_img, s_row, s_row, s_inv, s_sw, L);
 }
 
+// ---- prioritised replay (include/gobblet_hip.h, "Replay buffer", the priorities' paragraph) ------------------------------------------
+//   k_replay_prio_append  one wavefront per chunk, as k_replay_scatter: the chunk's ballot and first rank come from the workspace the
+//                         append of this window left, a lane's rank is mbcnt of the ballot, and a kept row's priority is one dword store.
+//   k_replay_prio_update  PASS 0 stores INT32_MIN to every named slot, PASS 1 applies atomicMax: two launches, so every maximum starts
+//                         from INT32_MIN whatever the order of the lanes.
+//   k_replay_prio_leaves  one workgroup of 512 threads per block of 64 leaves (8 KB of ring_prio): thread v reads the block's 16-byte vector
+//                         v (8 lanes per 128-byte line = leaf), counts only slots that are live, three shuffles leave the leaf's weight
+//                         with the line's first lane; the first wavefront scans the 64 weights by shuffles and stores the block's
+//                         local prefix and, into base[block + 1], its weight.
+//   k_replay_prio_scan    k_replay_scan's form over the blocks' weights, in place: base becomes the exclusive prefix (one block per
+//                         thread up to 2^21 slots); the last thread writes the header (the ring_state[0] the index is for, the whole weight).
+//   k_replay_batch_prio   k_replay_batch with another phase 1: the span's weight and origin (replay_prio_span: the same scalar work in
+//                         every lane, on lines the whole grid shares), then per lane the two binary searches and one leaf, which
+//                         comes in as eight independent 16-byte loads (replay_prio_draw).
+struct ReplayPrioAppendArgs {
+    const int32_t *prio_traj;
+    int32_t *ring_prio;
+    const uint64_t *ws;
+    int64_t ply_stride, tile_stride, ntiles, chunks;
+    uint64_t capacity;
+    int32_t value;
+};
+
+__global__ __launch_bounds__(64) void k_replay_prio_append(ReplayPrioAppendArgs A)
+{
+    const int lane = threadIdx.x;
+    const uint64_t *ballots = A.ws + kReplayWsHead, *bases = A.ws + kReplayWsHead + A.chunks;
+    const uint64_t T0 = A.ws[0], K = A.ws[1];
+    for (int64_t c = blockIdx.x; c < A.chunks; c += gridDim.x) {
+        const uint64_t votes = ballots[c];
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)votes), hi = __builtin_amdgcn_readfirstlane((uint32_t)(votes >> 32));
+        const bool ok = ((lane < 32 ? lo : hi) >> (lane & 31)) & 1u;
+        if (!ok) continue;
+        const uint64_t R = bases[c] + (uint64_t)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+        if (!replay_kept(R, K, A.capacity)) continue;
+        const int64_t at = (1 + c / A.ntiles) * A.ply_stride + (c % A.ntiles) * A.tile_stride + lane;
+        A.ring_prio[replay_slot(T0, R, A.capacity)] = A.prio_traj ? A.prio_traj[at] : A.value;
+    }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void k_replay_prio_update(const int32_t *__restrict__ index, const int32_t *__restrict__ values, int64_t batch,
+                                                            int32_t *ring_prio, int64_t capacity)
+{
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < batch; j += (int64_t)gridDim.x * 256) {
+        const int32_t slot = index[2 * j];
+        if (slot < 0 || (int64_t)slot >= capacity) continue;
+        if (PASS == 0) ring_prio[slot] = INT32_MIN;
+        else atomicMax(ring_prio + slot, values[j]);
+    }
+}
+
+struct ReplayPrioIndexArgs {
+    const int32_t *ring_prio;
+    const uint64_t *state;
+    uint64_t *index;
+    uint64_t capacity, leaves, blocks;
+};
+
+constexpr int kReplayLeafThreads = kReplayBlockLeaves * 8;  // a 16-byte vector per thread: 8 threads per leaf
+
+__global__ __launch_bounds__(kReplayLeafThreads) void k_replay_prio_leaves(ReplayPrioIndexArgs A)
+{
+    __shared__ uint64_t s_leaf[kReplayBlockLeaves];
+    const int tid = threadIdx.x;
+    const uint64_t total = A.state[0], live = total < A.capacity ? total : A.capacity;
+    uint64_t *base = A.index + kReplayPrioHead, *local = base + A.blocks + 1u;
+    for (uint64_t b = blockIdx.x; b < A.blocks; b += gridDim.x) {
+        const uint64_t s = 4u * (b * kReplayLeafThreads + (uint64_t)tid);
+        uint64_t sum = 0;
+        if (s + 4u <= live) {
+            const uint4 p = *reinterpret_cast<const uint4 *>(A.ring_prio + s);
+            sum = replay_weight((int32_t)p.x) + replay_weight((int32_t)p.y) + replay_weight((int32_t)p.z) + replay_weight((int32_t)p.w);
+        } else {
+            for (uint64_t i = s; i < live; ++i) sum += replay_weight(A.ring_prio[i]);  // (the last live vector, dword by dword; none behind it)
+        }
+        sum += __shfl_xor(sum, 1);
+        sum += __shfl_xor(sum, 2);
+        sum += __shfl_xor(sum, 4);
+        if ((tid & 7) == 0) s_leaf[tid >> 3] = sum;
+        __syncthreads();
+        if (tid < kReplayBlockLeaves) {  // the first wavefront: an inclusive scan of the 64 weights by shuffles
+            const uint64_t mine = s_leaf[tid];
+            uint64_t upto = mine;
+            for (int d = 1; d < kReplayBlockLeaves; d <<= 1) {
+                const uint64_t before = __shfl_up(upto, d);
+                if (tid >= d) upto += before;
+            }
+            const uint64_t leaf = b * kReplayBlockLeaves + (uint64_t)tid;
+            if (leaf < A.leaves) local[leaf] = upto - mine;
+            if (tid == kReplayBlockLeaves - 1) base[b + 1u] = upto;
+        }
+        __syncthreads();  // (the next block overwrites s_leaf)
+    }
+}
+
+__global__ __launch_bounds__(kReplayScanThreads) void k_replay_prio_scan(ReplayPrioIndexArgs A)
+{
+    __shared__ uint64_t s_sum[2][kReplayScanThreads];
+    const int tid = threadIdx.x;
+    uint64_t *base = A.index + kReplayPrioHead;
+    const uint64_t per = (A.blocks + kReplayScanThreads - 1) / kReplayScanThreads;
+    const uint64_t c0 = std::min<uint64_t>(tid * per, A.blocks), c1 = std::min<uint64_t>(c0 + per, A.blocks);
+    uint64_t mine = 0;
+    for (uint64_t c = c0; c < c1; ++c) mine += base[c + 1];
+    s_sum[0][tid] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < kReplayScanThreads; d <<= 1) {  // (Hillis-Steele over the two halves of s_sum: one barrier per step)
+        s_sum[cur ^ 1][tid] = s_sum[cur][tid] + (tid >= d ? s_sum[cur][tid - d] : 0ull);
+        __syncthreads();
+        cur ^= 1;
+    }
+    const uint64_t upto = s_sum[cur][tid];
+    uint64_t acc = upto - mine;
+    for (uint64_t c = c0; c < c1; ++c) {  // (a block's weight becomes the prefix behind it; base[c0] belongs to the thread before)
+        acc += base[c + 1];
+        base[c + 1] = acc;
+    }
+    if (tid == 0) base[0] = 0;
+    if (tid == kReplayScanThreads - 1) { A.index[0] = A.state[0]; A.index[1] = upto; }
+}
+
+struct ReplayBatchPrioArgs {
+    ReplayBatchArgs B;
+    const int32_t *ring_prio;
+    const uint64_t *index;
+    int32_t *prio_out;
+    uint64_t *total_out;
+};
+
+__global__ __launch_bounds__(64) void k_replay_batch_prio(ReplayBatchPrioArgs P)
+{
+    __shared__ uint32_t s_img[image_words<kObs>()];
+    __shared__ int64_t s_row[kTile];
+    __shared__ uint64_t s_inv[kTile];
+    __shared__ uint32_t s_sw[kTile];  // swap bits | mover << 6
+    const ReplayBatchArgs &A = P.B;
+    Lane L;
+    if (!lane_setup(L, A.batch, A.ntiles)) return;
+    const ReplayPrioSpan span = replay_prio_span(P.ring_prio, P.index, A.state[0], A.capacity, A.recent);
+    if (P.total_out && blockIdx.x == 0 && L.lane == 0) { P.total_out[0] = span.W; P.total_out[1] = span.span; }
+    ReplayPrioDraw d{-1, 0u, 0u};
+    if (L.valid) d = replay_prio_draw(A.seed, A.sample_base + (uint64_t)L.b, A.call, span, A.capacity, P.ring_prio, P.index);
+    const bool ok = d.slot >= 0;
+    const uint32_t code = ok ? d.sym & A.sym_mask : 0u;
+    const Sym S = sym_of(code);
+    uint4 tail{0u, 0u, 0u, 0u};  // bytes 48 .. 63 of the meta row: z and the mover in .y's upper half, the tag in .z
+    if (ok) tail = *reinterpret_cast<const uint4 *>(A.ring_meta + d.slot * kReplayMetaPitch + 48);
+    const uint32_t m = (tail.y >> 24) != 0u;
+    if (L.valid) {
+        A.index_out[2 * L.b] = ok ? (int32_t)d.slot : -1;  // (two dword stores: index_out is only 4-byte aligned)
+        A.index_out[2 * L.b + 1] = ok ? (int32_t)tail.z : -1;
+        if (P.prio_out) P.prio_out[L.b] = (int32_t)d.weight;
+        if (A.z_out) A.z_out[L.b] = ok ? (int8_t)(tail.y >> 16) : (int8_t)kZOpen;
+        if (A.sym_out) A.sym_out[L.b] = (int16_t)code;
+    }
+    s_row[L.lane] = d.slot; s_inv[L.lane] = S.inv; s_sw[L.lane] = S.swaps | (m << 6);
+    wave_lds_fence();
+    batch_rows<kReplayObsPitch, kReplayMetaPitch, kReplayVisitsPitch>(A.ring_obs, A.ring_meta, A.ring_visits, A.obs_out, A.mask_out,
+                                                                      A.visits_out, s_img, s_row, s_row, s_inv, s_sw, L);
+}
+
 // ---- tablebase (include/gobblet_hip.h, "Exact tablebase") ---------------------------------------------------------------------------
 // k_tb_prepare   one workgroup fills `aux`: every thread classifies a stretch of the 19 683 ternary level numbers, the workgroup scans
 //                the counts (both rank tables at once, packed into one word), every thread writes its stretch's ranks and inverses.
@@ -5216,6 +5379,81 @@ int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const i
                             batch, g.ntiles, recent, (uint64_t)capacity, seed, sample_base, call, (uint32_t)sym_mask};
     hipLaunchKernelGGL(k_replay_batch, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
     GBL_LAUNCHED("gbl_replay_batch");
+}
+
+size_t gbl_replay_prio_index_bytes(int64_t capacity) { return (size_t)replay_prio_index_bytes(capacity); }
+
+int gbl_replay_prio_append(const int16_t *visits_traj, const int8_t *z_traj, const int8_t *done_traj, const int32_t *prio_traj, int32_t value,
+                           int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride, int32_t *ring_prio, int64_t capacity,
+                           const uint64_t *ring_state, const void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (const char *why = replay_prio_append_error(visits_traj, z_traj, done_traj, n, plies, ply_stride, tile_stride, ring_prio, capacity,
+                                                   ring_state, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(workspace, "workspace");
+    if (reinterpret_cast<uintptr_t>(prio_traj) & 3u) return fail(GBL_ERR_ALIGN, "prio_traj must be 4-byte aligned");
+    const int64_t ntiles = (n + kTile - 1) / kTile, chunks = replay_chunks(n, plies);
+    const ReplayPrioAppendArgs A{prio_traj, ring_prio, static_cast<const uint64_t *>(workspace), ply_stride, tile_stride, ntiles, chunks,
+                                 (uint64_t)capacity, value};
+    hipLaunchKernelGGL(k_replay_prio_append, dim3((uint32_t)std::min<int64_t>(chunks, kReplayMaxGrid)), dim3(64), 0, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_replay_prio_append");
+}
+
+int gbl_replay_prio_update(const int32_t *index, const int32_t *values, int64_t batch, int32_t *ring_prio, int64_t capacity, void *stream)
+{
+    if (const char *why = replay_prio_update_error(index, values, batch, ring_prio, capacity)) return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(values)) & 3u)
+        return fail(GBL_ERR_ALIGN, "index / values must be 4-byte aligned");
+    const dim3 grid((uint32_t)std::min<int64_t>((batch + 255) / 256, kReplayMaxGrid));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_replay_prio_update<0>, grid, dim3(256), 0, s, index, values, batch, ring_prio, capacity);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_prio_update");
+    hipLaunchKernelGGL(k_replay_prio_update<1>, grid, dim3(256), 0, s, index, values, batch, ring_prio, capacity);
+    GBL_LAUNCHED("gbl_replay_prio_update");
+}
+
+int gbl_replay_prio_index(const int32_t *ring_prio, int64_t capacity, const uint64_t *ring_state, void *prio_index, size_t index_bytes,
+                          void *stream)
+{
+    if (const char *why = replay_prio_index_error(ring_prio, capacity, ring_state, prio_index, index_bytes)) return fail(GBL_ERR_ARG, why);
+    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(prio_index, "prio_index");
+    const uint64_t leaves = replay_prio_leaves((uint64_t)capacity), blocks = replay_prio_blocks((uint64_t)capacity);
+    const ReplayPrioIndexArgs A{ring_prio, ring_state, static_cast<uint64_t *>(prio_index), (uint64_t)capacity, leaves, blocks};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_replay_prio_leaves, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 16)), dim3(kReplayLeafThreads), 0, s, A);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_prio_index");
+    hipLaunchKernelGGL(k_replay_prio_scan, dim3(1), dim3(kReplayScanThreads), 0, s, A);
+    GBL_LAUNCHED("gbl_replay_prio_index");
+}
+
+int gbl_replay_batch_prio(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                          const uint64_t *ring_state, const int32_t *ring_prio, const void *prio_index, int32_t *prio_out, uint64_t *total_out,
+                          int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base, uint32_t call, int8_t *obs_out,
+                          int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out, void *stream)
+{
+    if (const char *why = replay_batch_prio_error(ring_obs, ring_visits, ring_meta, capacity, ring_state, ring_prio, prio_index, recent, batch,
+                                                  sym_mask, call, obs_out, index_out))
+        return fail(GBL_ERR_ARG, why);
+    if (batch == 0) return GBL_OK;
+    if ((reinterpret_cast<uintptr_t>(ring_obs) | reinterpret_cast<uintptr_t>(ring_visits) | reinterpret_cast<uintptr_t>(ring_meta)) & 127u)
+        return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
+    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(prio_index, "prio_index");
+    GBL_ALIGNED(obs_out, "obs_out"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_out, "visits_out");
+    if ((reinterpret_cast<uintptr_t>(index_out) | reinterpret_cast<uintptr_t>(prio_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "index_out / prio_out must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(total_out) & 7u) return fail(GBL_ERR_ALIGN, "total_out must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sym_out) & 1u) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
+    const Geometry g = geometry(batch);
+    const ReplayBatchPrioArgs A{{ring_obs, ring_visits, ring_meta, ring_state, obs_out, mask_out, visits_out, z_out, index_out, sym_out,
+                                 batch, g.ntiles, recent, (uint64_t)capacity, seed, sample_base, call, (uint32_t)sym_mask},
+                                ring_prio, static_cast<const uint64_t *>(prio_index), prio_out, total_out};
+    hipLaunchKernelGGL(k_replay_batch_prio, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_replay_batch_prio");
 }
 
 int gbl_tb_layout(const int32_t *inventory, int64_t *out)

@@ -2,7 +2,10 @@
 "Replay buffer": three arrays of whole 128-byte lines and two counters that live on the device).  ``append`` compacts a collected
 window's valid cells into it (``gbl_replay_append``: three launches, nothing waits for the host), ``batch`` draws exactly uniformly
 from its newest rows under random symmetries (``gbl_replay_batch``, the dict ``GobbletTrainer.step`` takes) and ``fit`` is the loop of
-the two -- on the GPU and, with device="cpu", in the host flavour alike."""
+the two -- on the GPU and, with device="cpu", in the host flavour alike.  With ``prioritized=True`` the buffer also owns a priority per
+row and the index of their prefix sums: ``append`` sets the new rows' priorities, ``set_priority`` / ``set_all_priority`` change them,
+``batch(prioritized=True)`` draws with probability proportional to them (``gbl_replay_batch_prio``, one launch, after a rebuild of the index
+on the same stream when anything changed since the last one)."""
 from __future__ import annotations
 
 import torch
@@ -23,8 +26,9 @@ def _lines(nbytes: int, device) -> torch.Tensor:
 
 
 class ReplayBuffer(_OnDevice):
-    def __init__(self, capacity: int, device="cuda:0", observations: bool = True) -> None:
-        """A ring of ``capacity`` rows (320 bytes each, 192 without observations), empty."""
+    def __init__(self, capacity: int, device="cuda:0", observations: bool = True, prioritized: bool = False) -> None:
+        """A ring of ``capacity`` rows (320 bytes each, 192 without observations), empty.  ``prioritized``: 4 more bytes per row for its
+        priority (all zeros: a row is drawn by priority only once it has been given one) and the index, 8 bytes per 32 rows."""
         capacity = int(capacity)
         if not 1 <= capacity <= MAX_CAPACITY:
             raise ValueError("capacity must be in [1, 2^31 - 1]")
@@ -36,6 +40,12 @@ class ReplayBuffer(_OnDevice):
         self._meta = _lines(capacity * nat.REPLAY_META_PITCH, dev).view(torch.int8).view(capacity, nat.REPLAY_META_PITCH)
         self._state = torch.zeros(2, dtype=torch.int64, device=dev)  # (the ABI's uint64[2]: rows ever appended, rows of the last append)
         self._workspace = None
+        self.prioritized = bool(prioritized)
+        if self.prioritized:
+            self._prio = _lines(4 * capacity, dev).view(torch.int32)
+            self._index = _lines(nat.lib().gbl_replay_prio_index_bytes(capacity), dev).view(torch.int64)
+            self._index_current = False  # (host bookkeeping alone: append and every priority write clear it, a prioritised draw rebuilds)
+            self._cells = None
 
     # ---- the ring, for inspection: views without the padding (slot order, not age order) ------------------------------------------
     @property
@@ -63,6 +73,17 @@ class ReplayBuffer(_OnDevice):
         return self._meta.view(torch.int32)[:, nat.REPLAY_META_TAG // 4]
 
     @property
+    def priority(self):
+        """int32 (capacity,), slot order; a row's weight is max(priority, 0).  A view: write through ``set_priority`` /
+        ``set_all_priority``, which know that the index is stale afterwards."""
+        self._need_priorities("priority")
+        return self._prio
+
+    def _need_priorities(self, what: str) -> None:
+        if not self.prioritized:
+            raise ValueError("%s needs ReplayBuffer(..., prioritized=True)" % what)
+
+    @property
     def total(self) -> int:
         """Rows ever appended.  Reads the device."""
         return int(self._state[0])
@@ -72,10 +93,14 @@ class ReplayBuffer(_OnDevice):
         """Rows the buffer holds: min(total, capacity).  Reads the device."""
         return min(self.total, self.capacity)
 
-    def append(self, env: BatchedGobblet, traj: dict, tag: int = 0) -> None:
+    def append(self, env: BatchedGobblet, traj: dict, tag: int = 0, priority=1) -> None:
         """The valid cells of the window ``traj`` of ``env`` (a window with search outputs and ``outcome_targets``: the cells
         ``training_batch`` draws from) go into the ring in ascending (ply, board), overwriting the oldest rows; ``tag`` (an int32, the
-        generation for instance) is stored with every row and comes back in a batch's "index".  Waits for nothing."""
+        generation for instance) is stored with every row and comes back in a batch's "index".  Waits for nothing.
+        ``priority`` (a prioritised buffer only): the new rows' priority, an int or an integer tensor per cell shaped like ``traj["z"]``
+        (one more launch, ``gbl_replay_prio_append``).  A row takes the value of the cell its visits come from: ply t's cell, which is
+        also the cell of ``Tablebase.judge``'s "regret" and "z_exact" (the judge arrays describe ply t's position and mover, as "visits"
+        does), so ``priority=table[traj["regret"].long() + 1]`` with a small weight table is the intended use."""
         f = traj["_full"]
         if "z" not in f:
             raise ValueError("append needs the 'z' entry: call outcome_targets(traj) first")
@@ -89,6 +114,19 @@ class ReplayBuffer(_OnDevice):
             raise ValueError("append: the buffer keeps observations and the window has none")
         if not -1 << 31 <= int(tag) < 1 << 31:
             raise ValueError("append: tag must fit an int32")
+        prio_traj = None
+        if self.prioritized:
+            if isinstance(priority, torch.Tensor):
+                if priority.shape != traj["z"].shape or priority.is_floating_point() or priority.device != self.device:
+                    raise ValueError("append: priority must be an int or an integer tensor shaped like traj['z'] on the buffer's device")
+                if self._cells is None or self._cells.shape != f["z"].shape:
+                    self._cells = torch.zeros(f["z"].shape, dtype=torch.int32, device=self.device)
+                (self._cells[:, :env.num_envs] if traj["_layout"] == "time" else self._cells).copy_(priority)
+                prio_traj, priority = self._cells, 0
+            elif not -1 << 31 <= int(priority) < 1 << 31:
+                raise ValueError("append: priority must fit an int32")
+        elif isinstance(priority, torch.Tensor) or int(priority) != 1:
+            self._need_priorities("append(priority=...)")
         n, plies = env.num_envs, traj["_plies"]
         need = nat.lib().gbl_replay_workspace_bytes(n, plies)  # (one function for both flavours: it launches nothing and needs no GPU)
         if self._workspace is None or self._workspace.numel() < need:
@@ -99,13 +137,62 @@ class ReplayBuffer(_OnDevice):
                 f["z"].data_ptr(), f["done"].data_ptr(), f["mover"].data_ptr(), n, plies, traj["_ply_stride"], traj["_tile_stride"],
                 int(tag), nat.ptr(self._obs), self._visits.data_ptr(), self._meta.data_ptr(), self.capacity, self._state.data_ptr(),
                 self._workspace.data_ptr(), self._workspace.numel(), self._stream()), "gbl_replay_append")
+            if self.prioritized:
+                self._index_current = False
+                nat.check(self._lib.gbl_replay_prio_append(
+                    f["visits"].data_ptr(), f["z"].data_ptr(), f["done"].data_ptr(), nat.ptr(prio_traj), int(priority), n, plies,
+                    traj["_ply_stride"], traj["_tile_stride"], self._prio.data_ptr(), self.capacity, self._state.data_ptr(),
+                    self._workspace.data_ptr(), self._workspace.numel(), self._stream()), "gbl_replay_prio_append")
 
-    def batch(self, batch: int, symmetries="all", call: int = 0, seed: int = 0, recent: int | None = None, out: dict | None = None) -> dict:
+    def set_priority(self, index: torch.Tensor, values: torch.Tensor) -> None:
+        """The rows a batch drew get new priorities (``gbl_replay_prio_update``): ``index`` is the batch's "index" (int32 (batch, 2); only
+        the slots are read, failed samples are skipped), ``values`` int32 (batch,).  A slot drawn more than once gets the largest of its
+        values; the old priority is replaced."""
+        self._need_priorities("set_priority")
+        if index.dtype != torch.int32 or index.dim() != 2 or index.shape[1] != 2 or not index.is_contiguous() or index.device != self.device:
+            raise ValueError("set_priority: index is a batch's 'index', int32 (batch, 2) on the buffer's device")
+        values = values.to(torch.int32).contiguous()
+        if values.shape != (index.shape[0],) or values.device != self.device:
+            raise ValueError("set_priority: values must be (batch,) on the buffer's device")
+        self._index_current = False
+        with self._on_device():
+            nat.check(self._lib.gbl_replay_prio_update(index.data_ptr(), values.data_ptr(), index.shape[0], self._prio.data_ptr(), self.capacity,
+                                                       self._stream()), "gbl_replay_prio_update")
+
+    def set_all_priority(self, values: torch.Tensor) -> None:
+        """Priorities for the first ``len(values)`` slots, in slot order (a torch copy): the census of ``relabel(..., census=True)``
+        mapped through a weight table, for instance."""
+        self._need_priorities("set_all_priority")
+        if values.dim() != 1 or values.shape[0] > self.capacity or values.is_floating_point():
+            raise ValueError("set_all_priority: an integer tensor of at most capacity entries, in slot order")
+        self._index_current = False
+        self._prio[:values.shape[0]].copy_(values)
+
+    def _rebuild_index(self) -> None:
+        if not self._index_current:
+            nat.check(self._lib.gbl_replay_prio_index(self._prio.data_ptr(), self.capacity, self._state.data_ptr(), self._index.data_ptr(),
+                                                      self._index.numel() * 8, self._stream()), "gbl_replay_prio_index")
+            self._index_current = True
+
+    @staticmethod
+    def importance_weights(batch: dict, beta: float = 1.0) -> torch.Tensor:
+        """The importance weights of a prioritised batch, float32 (batch,) in torch: with p = priority / W the probability a row was drawn
+        with and span the number of rows it was drawn from, (1 / (span p))^beta = (W / (span priority))^beta, divided by the largest of
+        them; 0 for a failed sample."""
+        w, total = batch["priority"].to(torch.float64), batch["prio_total"].to(torch.float64)
+        raw = torch.where(w > 0, (total[0] / (total[1] * w.clamp(min=1))) ** float(beta), torch.zeros_like(w))
+        return (raw / raw.max().clamp(min=torch.finfo(torch.float64).tiny)).to(torch.float32)
+
+    def batch(self, batch: int, symmetries="all", call: int = 0, seed: int = 0, recent: int | None = None, out: dict | None = None,
+              prioritized: bool = False) -> dict:
         """``batch`` rows drawn exactly uniformly from the newest ``recent`` rows (None: from all the buffer holds), each under a random
         symmetry, one launch of ``gbl_replay_batch``: the keys of ``BatchedGobblet.training_batch`` -- "observation" (a buffer with
         observations), "action_mask", "visits", "z", "sym" -- with "index" int32 (batch, 2) = (slot, tag).  The draws are keyed by
         (``seed``, sample index, ``call``).  An empty buffer gives ``training_batch``'s failed samples (index (-1, -1), zero rows,
-        z = ``nat.Z_OPEN``).  ``out``: a dict from an earlier call to write into."""
+        z = ``nat.Z_OPEN``).  ``out``: a dict from an earlier call to write into.
+        ``prioritized=True`` (a prioritised buffer): a row is drawn with probability priority / W instead, W the sum over the rows drawn
+        from (``gbl_replay_batch_prio``; keyed alike on its own generator stream); the dict also holds "priority" int32 (batch,), the
+        drawn rows' weights, and "prio_total" int64 (2,) = (W, the number of rows drawn from).  With W = 0 every sample is failed."""
         if symmetries not in BatchedGobblet.SYMMETRY_MASKS:
             raise ValueError("symmetries: 'all', 'square' or None")
         batch, call, recent = int(batch), int(call), 0 if recent is None else int(recent)
@@ -119,12 +206,24 @@ class ReplayBuffer(_OnDevice):
                 "sym": ((batch,), torch.int16)}
         if not self.observations:
             del spec["observation"]
+        if prioritized:
+            self._need_priorities("batch(prioritized=True)")
+            spec.update(priority=((batch,), torch.int32), prio_total=((2,), torch.int64))
         if out is None:
             out = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (shape, dtype) in spec.items()}
         elif set(out) != set(spec) or any(tuple(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != dev
                                           or not out[k].is_contiguous() for k, (shape, dtype) in spec.items()):
             raise ValueError("out: the dict of an earlier batch call of this batch size on this buffer")
         with self._on_device():
+            if prioritized:
+                self._rebuild_index()
+                nat.check(self._lib.gbl_replay_batch_prio(
+                    nat.ptr(self._obs), self._visits.data_ptr(), self._meta.data_ptr(), self.capacity, self._state.data_ptr(),
+                    self._prio.data_ptr(), self._index.data_ptr(), out["priority"].data_ptr(), out["prio_total"].data_ptr(), recent, batch,
+                    BatchedGobblet.SYMMETRY_MASKS[symmetries], int(seed), 0, call, nat.ptr(out.get("observation")),
+                    out["action_mask"].data_ptr(), out["visits"].data_ptr(), out["z"].data_ptr(), out["index"].data_ptr(),
+                    out["sym"].data_ptr(), self._stream()), "gbl_replay_batch_prio")
+                return out
             nat.check(self._lib.gbl_replay_batch(
                 nat.ptr(self._obs), self._visits.data_ptr(), self._meta.data_ptr(), self.capacity, self._state.data_ptr(), recent, batch,
                 BatchedGobblet.SYMMETRY_MASKS[symmetries], int(seed), 0, call, nat.ptr(out.get("observation")),
@@ -146,21 +245,26 @@ class ReplayBuffer(_OnDevice):
                            mode, count, census, None, allow_incomplete)
 
     def fit(self, trainer, steps: int, batch: int = 1024, symmetries="all", first_call: int = 0, recent: int | None = None,
-            seed: int = 0, targets=None) -> torch.Tensor:
+            seed: int = 0, targets=None, prioritized: bool = False) -> torch.Tensor:
         """``steps`` Adam steps of ``trainer`` (a ``GobbletTrainer`` on this buffer's device): step i draws ``batch(batch, symmetries,
         call=first_call + i, recent=recent)`` into one reused buffer and hands it to ``trainer.step``; nothing crosses to the host.
         ``targets``: a ``Tablebase`` on this device -- every drawn batch goes through ``targets.targets`` first (one more launch per
         step: the fit learns from the exact labels).  Returns the steps' statistics, float32 (steps, 4) on the device, as
-        ``BatchedGobblet.fit`` does."""
+        ``BatchedGobblet.fit`` does.  ``prioritized``: the batches are ``batch(..., prioritized=True)``'s."""
         if torch.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the buffer on %s" % (trainer.device, self.device))
         buf, stats = None, []
         for i in range(int(steps)):
-            buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf)
+            buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=prioritized)
             stats.append(trainer.step(buf if targets is None else targets.targets(dict(buf))))
         return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
 
     def state_dict(self) -> dict:
+        if self.prioritized:
+            return {**self._ring_state_dict(), "priority": self._prio.clone()}
+        return self._ring_state_dict()
+
+    def _ring_state_dict(self) -> dict:
         return {"capacity": self.capacity, "observations": self.observations, "state": self._state.clone(), "visits": self._visits.clone(),
                 "meta": self._meta.clone(), "obs": None if self._obs is None else self._obs.clone()}
 
@@ -173,3 +277,8 @@ class ReplayBuffer(_OnDevice):
         self._meta.copy_(state["meta"])
         if self._obs is not None:
             self._obs.copy_(state["obs"])
+        if self.prioritized:
+            if "priority" not in state:
+                raise ValueError("load_state_dict: the state is of a buffer without priorities")
+            self._prio.copy_(state["priority"])
+            self._index_current = False

@@ -171,6 +171,19 @@ int gbl_cpu_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, con
                          const uint64_t *ring_state, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
                          uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
                          int16_t *sym_out, void *stream);
+/* (gbl_replay_prio_index_bytes is one function for both flavours; gbl_cpu_replay_prio_append enumerates the window's cells again and
+ * does not use the workspace) */
+int gbl_cpu_replay_prio_append(const int16_t *visits_traj, const int8_t *z_traj, const int8_t *done_traj, const int32_t *prio_traj, int32_t value,
+                               int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride, int32_t *ring_prio, int64_t capacity,
+                               const uint64_t *ring_state, const void *workspace, size_t workspace_bytes, void *stream);
+int gbl_cpu_replay_prio_update(const int32_t *index, const int32_t *values, int64_t batch, int32_t *ring_prio, int64_t capacity, void *stream);
+int gbl_cpu_replay_prio_index(const int32_t *ring_prio, int64_t capacity, const uint64_t *ring_state, void *prio_index, size_t index_bytes,
+                              void *stream);
+int gbl_cpu_replay_batch_prio(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                              const uint64_t *ring_state, const int32_t *ring_prio, const void *prio_index, int32_t *prio_out,
+                              uint64_t *total_out, int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base,
+                              uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
+                              int16_t *sym_out, void *stream);
 int gbl_cpu_tb_prepare(const int32_t *inventory, void *aux, void *stream);
 int gbl_cpu_tb_sweep(const int32_t *inventory, const void *aux, const int8_t *table, int8_t *out, int64_t first, int64_t count, int k,
                      uint64_t *decided, void *stream);

@@ -829,6 +829,64 @@ int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const i
                      uint32_t call, int8_t *obs_out, int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out,
                      int16_t *sym_out, void *stream);
 
+/* Prioritised replay: a priority per ring row and draws with probability proportional to it.  Nothing above changes: the priorities
+ * live in a fourth array, and every function here is exact and bit-defined -- kernels, host flavour and a numpy restatement of this text
+ * (tests/replay_prio_restatement.py) agree bit for bit.
+ *   ring_prio   int32 [capacity], 128-byte aligned, in slot order.  The weight of a row is w = max(ring_prio[slot], 0): a negative entry
+ *     counts as 0.  A fresh buffer is all zeros.
+ *   prio_index  a block the caller owns, gbl_replay_prio_index_bytes(capacity) bytes (0 for a capacity out of range), 16-byte aligned,
+ *     opaque except for its first two uint64: the ring_state[0] it was built for, and the sum of w over all live rows.
+ *
+ * gbl_replay_prio_append sets the priorities of the rows that the gbl_replay_append just before it wrote.  PRECONDITION: it follows that
+ *   append with the same window arguments (visits_traj, z_traj, done_traj, n, plies, the two strides), the same capacity and ring_state
+ *   and the same workspace, untouched since.  With K = state[1] and T0 = state[0] - K the valid cell of rank r gets prio_traj[cell(t, b)]
+ *   (int32, indexed as z_traj is: it belongs with visits_traj[cell(t, b)]) or, where prio_traj is NULL, the scalar `value`, at slot
+ *   (T0 + r) mod capacity; ranks under the cut (r < K - capacity) are not written, and no other slot is touched.  The device flavour reads
+ *   the chunks' ballots, their first ranks, T0 and K from the workspace (one launch, one wavefront per chunk, ranks by mbcnt) and only
+ *   checks the window's three arrays for NULL; the host flavour enumerates the cells again and ignores the workspace.
+ * gbl_replay_prio_update sets the priorities of drawn rows: for index int32 [batch][2] (the index_out of a draw) and values int32 [batch],
+ *   every slot s named by some index[j][0] gets the maximum of values[j] over the j that name it; the old value is replaced, not kept.
+ *   Entries whose slot is outside [0, capacity) are skipped (the failed sample's -1 is one).  Two launches on the caller's stream -- the
+ *   first stores INT32_MIN to every named slot, the second applies atomicMax -- so the result does not depend on scheduling.  A value
+ *   stored negative reads as weight 0.
+ * gbl_replay_prio_index builds prio_index from ring_prio and ring_state.  Slots that are not live (slot >= state[0] on a ring that has
+ *   not wrapped) count 0 whatever they hold.  Two launches (the prefix sums inside every block of 2 048 slots, a workgroup per block, and
+ *   a scan over the blocks by one workgroup), no atomics and no waiting between workgroups.
+ * gbl_replay_batch_prio: gbl_replay_batch with a weighted draw.  Sample j:
+ *   (w0, w1, w2, w3) = gbl_replay_batch's Philox block on stream 8 (ctr = (id_lo, id_hi, 16 call, 8)); total = state[0], live and span as
+ *     there.  The span's rows from oldest to newest are q = 0 .. span - 1 at slot(q) = (total - span + q) mod capacity.
+ *   W = sum of w(q);  u = (w0 << 32) | w1;  r = floor(u W / 2^64) (the high half of a 64 x 64 product);
+ *   q* = the smallest q with w(0) + .. + w(q) > r;  the sample's slot is slot(q*), its symmetry s = w2 & sym_mask.
+ *   A row of weight 0 is never drawn; a row's probability is w / W up to one count in 2^64.
+ *   Outputs: every output of gbl_replay_batch as there (index_out = (slot, tag)), prio_out[j] = w(q*) (int32 [batch], optional) and
+ *     total_out = (W, span) (uint64 [2], optional, 8-byte aligned, written once per launch).
+ *   Every sample is gbl_replay_batch's failed sample (zero rows, z = GBL_Z_OPEN, index (-1, -1), sym 0, prio_out 0) when live == 0, when
+ *     W == 0, or when the index's first word is not state[0] (an append happened after the build); then total_out = (0, span).
+ *   With an index that is stale only because priorities changed since the build the draw is unspecified, but it still returns a slot
+ *     inside [0, capacity) and reads nothing outside the four arrays and the index.
+ *   The draw of sample j depends on (seed, sample_base + j, call), recent, the ring's state and the priorities alone.
+ *   Sizes: W < 2^62 (any ring of int32 priorities); all sums are uint64.
+ *   Argument errors: gbl_replay_batch's, in its order (batch == 0 returns GBL_OK after the scalar checks and writes nothing, total_out
+ *     included); then with batch > 0 a missing ring_prio or prio_index (GBL_ERR_ARG).  The other
+ *     three: capacity out of range, (batch out of range,) a missing pointer, the window's rules of gbl_replay_append, a workspace_bytes or
+ *     index_bytes that is too small (GBL_ERR_ARG).  GBL_ERR_ALIGN: ring_prio 128-byte, ring_state / workspace / prio_index 16-byte,
+ *     index / values / prio_traj / prio_out 4-byte, total_out 8-byte.
+ *   Measured (one MI355X, profiles/r25/replay_prio.json; a ring of 2^21 slots, batch 65 536): the index build plus the draw
+ *     92.5 us against 111.4 us for torch.cumsum + torch.searchsorted + gbl_replay_batch; the draw alone 85.1 us against gbl_replay_batch's
+ *     75.4 us; the build alone 11.0 us; gbl_replay_prio_append adds 2.9 us to a 34.5 us append.  NOT MEASURED: whether prioritising
+ *     helps a fit. */
+size_t gbl_replay_prio_index_bytes(int64_t capacity);
+int gbl_replay_prio_append(const int16_t *visits_traj, const int8_t *z_traj, const int8_t *done_traj, const int32_t *prio_traj, int32_t value,
+                           int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride, int32_t *ring_prio, int64_t capacity,
+                           const uint64_t *ring_state, const void *workspace, size_t workspace_bytes, void *stream);
+int gbl_replay_prio_update(const int32_t *index, const int32_t *values, int64_t batch, int32_t *ring_prio, int64_t capacity, void *stream);
+int gbl_replay_prio_index(const int32_t *ring_prio, int64_t capacity, const uint64_t *ring_state, void *prio_index, size_t index_bytes,
+                          void *stream);
+int gbl_replay_batch_prio(const int8_t *ring_obs, const int16_t *ring_visits, const int8_t *ring_meta, int64_t capacity,
+                          const uint64_t *ring_state, const int32_t *ring_prio, const void *prio_index, int32_t *prio_out, uint64_t *total_out,
+                          int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base, uint32_t call, int8_t *obs_out,
+                          int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out, void *stream);
+
 /* Exact tablebase (no counterpart in the reference: the game solved outright, one byte per position).  Integer-only and draws nothing:
  * the kernels, the host flavour and a restatement of this text agree byte for byte.
  *   Inventory.  inventory[3] (int32 on the HOST, read at the call) gives c_k in 0 .. 2, each player's number of pieces of size k.  The

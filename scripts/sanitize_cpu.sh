@@ -14,6 +14,10 @@ g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-poin
 g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wno-unknown-pragmas -Wno-attributes \
     -pthread -o $T/replay_main scripts/sanitize_replay_main.cpp gobblet-rl_amd/csrc/gobblet_cpu.cpp
 $T/replay_main
+# the prioritised replay's host entry points likewise
+g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wno-unknown-pragmas -Wno-attributes \
+    -pthread -o $T/replay_prio_main scripts/sanitize_replay_prio_main.cpp gobblet-rl_amd/csrc/gobblet_cpu.cpp
+$T/replay_prio_main
 # the tablebase's host entry points likewise
 g++ -O1 -g -std=c++17 -mpopcnt -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wno-unknown-pragmas -Wno-attributes \
     -pthread -o $T/tablebase_main scripts/sanitize_tablebase_main.cpp gobblet-rl_amd/csrc/gobblet_cpu.cpp
