@@ -123,6 +123,8 @@ SIGNATURES = {
     "gbl_tb_targets": (_int, [_vp] * 4 + [_i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int] + [_vp] * 3 + [_i64, _vp]),
     "gbl_train_workspace_bytes": (_i64, [_i64, _int]),
     "gbl_train_step": (_int, [_vp] * 4 + [_i64, _int] + [_vp] * 7 + [_i64, _vp]),
+    "gbl_train_step_weighted": (_int, [_vp] * 4 + [_i64, _int] + [_vp] * 7 + [C.c_float, C.c_int32, C.c_int32] + [_vp] * 3 + [_i64, _vp]),
+    "gbl_replay_importance": (_int, [_vp, _i64, C.c_float, _vp, _vp]),
     "gbl_collect_variant": (_int, [_i64, _u32, _int, _int]),
     "gbl_block_alloc": (_int, [_i64, C.POINTER(_vp)]),
     "gbl_block_free": (_int, [_vp]),

@@ -14,6 +14,7 @@
 //   -DGBL_FORCE_GREEDY_SHAPE=s    the greedy kernels' block shape (11, 14, 18, 26, 28, 48, 56)
 //   -DGBL_COLLECT_WAVES_PER_EU=a,b / -DGBL_CP_WAVES_PER_EU=n   occupancy pins of k_collect / k_collect_policy
 //   -DGBL_SOLVE_DEAL=0|1          k_solve's (action, reply) pairs dealt interleaved / off a counter in LDS
+//   -DGBL_IMPORTANCE_ONE_GROUP=1  gbl_replay_importance launches ONE workgroup, which walks the batch twice (scripts/bench_train_weighted.py)
 #pragma once
 
 #ifndef GBL_X_GREEDY_SKIP
@@ -40,10 +41,14 @@
 #ifndef GBL_SOLVE_DEAL
 #define GBL_SOLVE_DEAL 0
 #endif
+#ifndef GBL_IMPORTANCE_ONE_GROUP
+#define GBL_IMPORTANCE_ONE_GROUP 0
+#endif
 
 namespace gbl {
 namespace knob {
 constexpr int kSolveDeal = GBL_SOLVE_DEAL;
+constexpr int kImportanceOneGroup = GBL_IMPORTANCE_ONE_GROUP;
 constexpr int kGreedySkip = GBL_X_GREEDY_SKIP;
 constexpr int kGreedyPairCap = GBL_X_GREEDY_PAIR_CAP;
 constexpr int kForcedNt = GBL_FORCE_NT;

@@ -1722,8 +1722,15 @@ struct HostTrain {
     float *h, *dh, *dout, *row;
     int H;
     TrainHyper hy;
+    // gbl_cpu_train_step_weighted alone (EX): the rows' weights and the two per-row outputs
+    const float *row_weight;
+    float *row_loss_out;
+    int32_t *prio_out;
+    float prio_scale;
+    int32_t prio_floor, prio_cap;
 };
 
+template <bool EX>
 void train_row(const HostTrain &A, int64_t r)
 {
     GBL_FP_STRICT
@@ -1741,6 +1748,8 @@ void train_row(const HostTrain &A, int64_t r)
     if (z == kZOpen || S <= 0) {
         std::fill(rh, rh + H, 0.0f); std::fill(rdh, rdh + H, 0.0f);
         std::fill(rdo, rdo + kTrainDoStride, 0.0f); std::fill(rst, rst + kTrainRowStats, 0.0f);
+        if (EX && A.row_loss_out) A.row_loss_out[2 * r] = A.row_loss_out[2 * r + 1] = 0.0f;
+        if (EX && A.prio_out) A.prio_out[r] = 0;
         return;
     }
     float pre[256], o[kTrainOutputs], d[kActions], e[kActions], term[kActions];
@@ -1777,12 +1786,21 @@ void train_row(const HostTrain &A, int64_t r)
     train_value(o[kActions], z, A.hy.value_reg, lv, dv);
     rdo[kActions] = dv;
     rdo[kTrainOutputs] = 0.0f;
+    const float ww = EX && A.row_weight ? train_weight(A.row_weight[r]) : 1.0f;
+    if (EX)
+        for (int k = 0; k < kTrainOutputs; ++k) rdo[k] = ww * rdo[k];
     for (int j = 0; j < H; ++j) {
         float acc = 0.0f;
         for (int k = 0; k < kTrainOutputs; ++k) acc = acc + rdo[k] * w2[j * kTrainOutputs + k];
         rdh[j] = pre[j] > 0.0f ? acc : 0.0f;
     }
-    rst[0] = lp; rst[1] = lv; rst[2] = top; rst[3] = 1.0f;
+    if (EX) {
+        if (A.row_loss_out) { A.row_loss_out[2 * r] = lp; A.row_loss_out[2 * r + 1] = lv; }
+        if (A.prio_out) A.prio_out[r] = train_priority(lp, lv, A.prio_scale, A.prio_floor, A.prio_cap);
+        rst[0] = ww * lp; rst[1] = ww * lv; rst[2] = top; rst[3] = 1.0f;
+    } else {
+        rst[0] = lp; rst[1] = lv; rst[2] = top; rst[3] = 1.0f;
+    }
 }
 
 // SUM of the header over `len` neighbouring elements at once: term(r, acc) adds row r's terms to the chunk's accumulators
@@ -1799,23 +1817,14 @@ void train_sum(int64_t B, int len, float *total, Term term)
     }
 }
 
-}  // namespace
-
-extern "C" int gbl_cpu_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
-                                  float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out,
-                                  float *stats_out, void *workspace, int64_t workspace_bytes, void *)
+// the step after the argument checks, for both entry points: the rows (EX: weighted, with the per-row outputs), then the row sums and Adam
+template <bool EX>
+int train_step_host(const HostTrain &A, int64_t B, float *params, float *adam_m, float *adam_v, float *grad_out, float *stats_out)
 {
-    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
-        return fail(GBL_ERR_ARG, why);
     GBL_FP_STRICT
-    const int H = hidden;
-    const int64_t B = batch;
-    float *ws = static_cast<float *>(workspace);
-    const HostTrain A{obs, mask, visits, z, params, ws, ws + B * H, ws + 2 * B * H, ws + 2 * B * H + B * kTrainDoStride, H,
-                      TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
-                                 hyper->bias2}};
+    const int H = A.H;
     parallel_for(B, [=](int64_t r0, int64_t r1) {
-        for (int64_t r = r0; r < r1; ++r) train_row(A, r);
+        for (int64_t r = r0; r < r1; ++r) train_row<EX>(A, r);
     }, 64);
     int N = 0;
     for (int64_t r = 0; r < B; ++r) N += A.row[r * kTrainRowStats + 3] != 0.0f;
@@ -1869,5 +1878,54 @@ extern "C" int gbl_cpu_train_step(const int8_t *obs, const int8_t *mask, const i
         top = train_float_bits(t) > train_float_bits(top) ? t : top;
     }
     stats_out[0] = sums[0] / M; stats_out[1] = sums[1] / M; stats_out[2] = (float)N; stats_out[3] = top;
+    return GBL_OK;
+}
+
+HostTrain host_train(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t B, int H, const float *params,
+                     const gbl_train_hyper *hyper, void *workspace)
+{
+    float *ws = static_cast<float *>(workspace);
+    return HostTrain{obs, mask, visits, z, params, ws, ws + B * H, ws + 2 * B * H, ws + 2 * B * H + B * kTrainDoStride, H,
+                     TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
+                                hyper->bias2},
+                     nullptr, nullptr, nullptr, 0.0f, 0, 0};
+}
+
+}  // namespace
+
+extern "C" int gbl_cpu_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                                  float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out,
+                                  float *stats_out, void *workspace, int64_t workspace_bytes, void *)
+{
+    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    return train_step_host<false>(host_train(obs, mask, visits, z, batch, hidden, params, hyper, workspace), batch, params, adam_m, adam_v,
+                                  grad_out, stats_out);
+}
+
+// gbl_cpu_train_step_weighted: the same step with the rows' weights folded into do and the loss terms, and the two per-row outputs
+extern "C" int gbl_cpu_train_step_weighted(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch,
+                                           int hidden, float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper,
+                                           const float *row_weight, float *row_loss_out, int32_t *prio_out, float prio_scale,
+                                           int32_t prio_floor, int32_t prio_cap, float *grad_out, float *stats_out, void *workspace,
+                                           int64_t workspace_bytes, void *)
+{
+    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    if (const char *why = train_weighted_error(prio_out, prio_scale, prio_floor, prio_cap)) return fail(GBL_ERR_ARG, why);
+    HostTrain A = host_train(obs, mask, visits, z, batch, hidden, params, hyper, workspace);
+    A.row_weight = row_weight; A.row_loss_out = row_loss_out; A.prio_out = prio_out;
+    A.prio_scale = prio_scale; A.prio_floor = prio_floor; A.prio_cap = prio_cap;
+    return train_step_host<true>(A, batch, params, adam_m, adam_v, grad_out, stats_out);
+}
+
+// gbl_cpu_replay_importance: the header's rule, the integer minimum first
+extern "C" int gbl_cpu_replay_importance(const int32_t *prio, int64_t batch, float beta, float *weights_out, void *)
+{
+    if (const char *why = replay_importance_error(prio, batch, beta, weights_out)) return fail(GBL_ERR_ARG, why);
+    int32_t wmin = INT32_MAX;
+    for (int64_t j = 0; j < batch; ++j)
+        if (prio[j] > 0 && prio[j] < wmin) wmin = prio[j];
+    for (int64_t j = 0; j < batch; ++j) weights_out[j] = importance_weight(prio[j], wmin, beta);
     return GBL_OK;
 }

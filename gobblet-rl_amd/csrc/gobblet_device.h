@@ -3625,4 +3625,54 @@ __host__ __device__ __forceinline__ void train_adam(float g, float &theta, float
     theta = theta - (hy.lr * (m / hy.bias1)) / (root + hy.eps);
 }
 
+// ---- gbl_train_step_weighted / gbl_replay_importance (include/gobblet_hip.h): the scalar pieces they add to the rule above -------------
+constexpr float kTrainFltMax = 0x1.fffffep+127f;
+constexpr int32_t kTrainPrioTop = 1 << 30;  // the most a loss can add to prio_floor
+constexpr int64_t kImportanceMaxBatch = 65536;
+
+// the effective weight ww of a row: a NaN, a negative, a zero and +inf all count 0
+// (on the bits, which order as the positive floats do, so that a wavefront-uniform weight stays in the kernel's scalar registers:
+// 0 < w <= FLT_MAX exactly where 0 < bits <= 0x7F7FFFFF as an int32 -- denormals included, -0 and every NaN excluded)
+__host__ __device__ __forceinline__ uint32_t train_weight_bits(uint32_t u) { return (int32_t)u > 0 && (int32_t)u <= 0x7F7FFFFF ? u : 0u; }
+__host__ __device__ __forceinline__ float train_weight(float w) { return train_bits_float(train_weight_bits(train_float_bits(w))); }
+
+// prio_out of a counted row from its two unweighted loss terms
+__host__ __device__ __forceinline__ int32_t train_priority(float lp, float lv, float scale, int32_t floor, int32_t cap)
+{
+    GBL_FP_STRICT
+    float q = lp + lv;
+    q = q * scale;
+    const int32_t k = !(q > 0.0f) ? 0 : q >= 0x1p30f ? kTrainPrioTop : (int32_t)q;
+    const int64_t p = (int64_t)floor + k;
+    return (int32_t)(p < (int64_t)cap ? p : (int64_t)cap);
+}
+
+// what gbl_train_step_weighted checks after train_error (and, on the device, after gbl_train_step's alignment rules)
+inline const char *train_weighted_error(const void *prio_out, float prio_scale, int32_t prio_floor, int32_t prio_cap)
+{
+    if (!prio_out) return nullptr;
+    if (!(prio_scale >= 0.0f && prio_scale <= kTrainFltMax)) return "prio_scale must be finite and >= 0";
+    if (prio_floor < 0 || prio_floor > prio_cap) return "prio_floor and prio_cap must satisfy 0 <= prio_floor <= prio_cap";
+    return nullptr;
+}
+
+// the importance weight of a drawn row of priority p in a batch whose smallest positive priority is wmin (p > 0: wmin >= 1)
+__host__ __device__ __forceinline__ float importance_weight(int32_t p, int32_t wmin, float beta)
+{
+    GBL_FP_STRICT
+    if (p <= 0) return 0.0f;
+    const float ratio = (float)p / (float)wmin;
+    const float x = beta * train_log(ratio);
+    return train_exp(-x);
+}
+
+inline const char *replay_importance_error(const void *prio, int64_t batch, float beta, const void *weights_out)
+{
+    if (batch < 1 || batch > kImportanceMaxBatch) return "batch must be in [1, 65536]";
+    if (!(beta >= 0.0f && beta <= 1.0f)) return "beta must be in [0, 1]";
+    if (!prio) return "prio must not be NULL";
+    if (!weights_out) return "weights_out must not be NULL";
+    return nullptr;
+}
+
 }  // namespace gbl

@@ -3145,8 +3145,22 @@ __device__ __forceinline__ void each_bit(uint64_t bits, F f)
     }
 }
 
-template <int U>  // U = H / 64: hidden units per lane
-__global__ __launch_bounds__(64 * kTrainRowWaves) void k_train_rows(TrainArgs A)
+// gbl_train_step_weighted's rows kernel takes the step's arguments and, behind them, the rows' weights and the two per-row outputs
+struct TrainExArgs : TrainArgs {
+    const float *row_weight;
+    float *row_loss_out;
+    int32_t *prio_out;
+    float prio_scale;
+    int32_t prio_floor, prio_cap;
+};
+
+// EX = false: gbl_train_step's kernel.  EX = true: gbl_train_step_weighted's -- the row's weight ww, wavefront-uniform and held in a scalar
+// register, is folded into the stores of do and of the loss terms, and the lanes that hold lp and lv write the two per-row outputs
+// (EX asks the compiler for 4 / 4 / 2 / 2 wavefronts per SIMD by name: without that <2, true> lands at 131 VGPRs, just past the step
+// from 4 to 3.  <3, true> does not fit gbl_train_step's 168 -- asked for 3 wavefronts it spills two registers -- and runs 2 per SIMD)
+template <int U, bool EX = false>  // U = H / 64: hidden units per lane
+__global__ __launch_bounds__(64 * kTrainRowWaves) __attribute__((amdgpu_waves_per_eu(EX ? (U <= 2 ? 4 : 2) : 1)))
+void k_train_rows(std::conditional_t<EX, TrainExArgs, TrainArgs> A)
 {
     GBL_FP_STRICT
     constexpr int H = 64 * U;
@@ -3161,6 +3175,8 @@ __global__ __launch_bounds__(64 * kTrainRowWaves) void k_train_rows(TrainArgs A)
     __syncthreads();  // (the only rendezvous: from here the wavefronts share nothing but the read-only w2)
     for (int64_t r = (int64_t)blockIdx.x * kTrainRowWaves + wave; r < A.batch; r += (int64_t)gridDim.x * kTrainRowWaves) {
         float *rh = A.ws_h + r * H, *rdh = A.ws_dh + r * H, *rdo = A.ws_do + r * kTrainDoStride, *rst = A.ws_row + r * kTrainRowStats;
+        // (EX: the row as a scalar -- r < 2^16 --, so that the addresses of the row's weight and of its two outputs cost no vector registers)
+        const int64_t rs = EX ? (int64_t)__builtin_amdgcn_readfirstlane((int)r) : r;
         const bool action = lane < (uint32_t)kActions;
         const bool in_c = action && (!A.mask || A.mask[r * kActions + lane] != 0);
         const uint64_t cand = __ballot(in_c);
@@ -3172,7 +3188,16 @@ __global__ __launch_bounds__(64 * kTrainRowWaves) void k_train_rows(TrainArgs A)
             for (int u = 0; u < U; ++u) rh[lane + 64 * u] = rdh[lane + 64 * u] = 0.0f;
             if (lane < (uint32_t)kTrainDoStride) rdo[lane] = 0.0f;
             if (lane < (uint32_t)kTrainRowStats) rst[lane] = 0.0f;
+            if constexpr (EX) {
+                if (A.row_loss_out && lane < 2u) A.row_loss_out[2 * rs + lane] = 0.0f;
+                if (A.prio_out && lane == 0u) A.prio_out[rs] = 0;
+            }
             continue;
+        }
+        float ww = 1.0f;  // (uniform: one scalar load per row)
+        if constexpr (EX) {
+            if (A.row_weight)
+                ww = train_bits_float(train_weight_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)train_float_bits(A.row_weight[rs]))));
         }
         // layer 1: the w1 rows of the set bytes, ascending
         const uint64_t set0 = __ballot(A.obs[r * kObs + lane] != 0);
@@ -3223,18 +3248,23 @@ __global__ __launch_bounds__(64 * kTrainRowWaves) void k_train_rows(TrainArgs A)
         if (lane == (uint32_t)kActions) train_value(o, z, A.hy.value_reg, lv, g);
         if (lane < (uint32_t)kTrainDoStride) {
             st[lane] = term;
-            sd[lane] = g;
-            rdo[lane] = g;
+            sd[lane] = EX ? ww * g : g;
+            rdo[lane] = EX ? ww * g : g;
         }
         wave_lds_fence();
         float lp = 0.0f;
         each_bit(cand, [&](int a) { lp = lp + st[a]; });
         if (lane == 0u) {
-            rst[0] = lp;
+            rst[0] = EX ? ww * lp : lp;
             rst[2] = train_bits_float(top);
             rst[3] = 1.0f;
         }
-        if (lane == (uint32_t)kActions) rst[1] = lv;
+        if (lane == (uint32_t)kActions) rst[1] = EX ? ww * lv : lv;
+        if constexpr (EX) {  // the unweighted loss terms, from the lanes that hold them: lane 0 has lp, lane 54 has lp and lv
+            if (A.row_loss_out && lane == 0u) A.row_loss_out[2 * rs] = lp;
+            if (A.row_loss_out && lane == (uint32_t)kActions) A.row_loss_out[2 * rs + 1] = lv;
+            if (A.prio_out && lane == (uint32_t)kActions) A.prio_out[rs] = train_priority(lp, lv, A.prio_scale, A.prio_floor, A.prio_cap);
+        }
         // backward through layer 2: lane j owns dh_j
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -3348,6 +3378,30 @@ __global__ __launch_bounds__(64 * kTrainReduceWaves) void k_train_reduce_adam(Tr
         A.stats_out[2] = (float)N;
         A.stats_out[3] = total;
     }
+}
+
+// gbl_replay_importance: one launch, every workgroup finds the batch's smallest positive priority itself (an integer minimum over an
+// array of at most 256 KB that stays in L2: any order), then weighs its own 256 entries.  No atomics, no waiting between workgroups.
+constexpr int kImportanceThreads = 256;
+
+__global__ __launch_bounds__(kImportanceThreads) void k_replay_importance(const int32_t *__restrict__ prio, int64_t batch, float beta,
+                                                                          float *__restrict__ weights_out)
+{
+    GBL_FP_STRICT
+    __shared__ uint32_t s_min[kImportanceThreads / 64];
+    uint32_t mine = 0x7FFFFFFFu;
+    for (int64_t j = threadIdx.x; j < batch; j += kImportanceThreads) {
+        const int32_t p = prio[j];
+        mine = p > 0 && (uint32_t)p < mine ? (uint32_t)p : mine;
+    }
+    mine = ~wave_max(~mine);
+    if ((threadIdx.x & 63u) == 0u) s_min[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    uint32_t wmin = s_min[0];
+#pragma unroll
+    for (int w = 1; w < kImportanceThreads / 64; ++w) wmin = s_min[w] < wmin ? s_min[w] : wmin;
+    for (int64_t j = (int64_t)blockIdx.x * kImportanceThreads + threadIdx.x; j < batch; j += (int64_t)gridDim.x * kImportanceThreads)
+        weights_out[j] = importance_weight(prio[j], (int32_t)wmin, beta);
 }
 
 // gbl_solve: the exact solver, one wavefront per board (a grid-stride loop over boards), three phases per board:
@@ -5585,6 +5639,53 @@ int gbl_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits,
     const uint32_t tiles = (uint32_t)((train_param_count(hidden) + 3 + 63) / 64);  // (+ 3: the statistics' lanes)
     hipLaunchKernelGGL(k_train_reduce_adam, dim3(tiles), dim3(64 * kTrainReduceWaves), 0, s, A);
     GBL_LAUNCHED("gbl_train_step");
+}
+
+int gbl_train_step_weighted(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                            float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, const float *row_weight,
+                            float *row_loss_out, int32_t *prio_out, float prio_scale, int32_t prio_floor, int32_t prio_cap, float *grad_out,
+                            float *stats_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    GBL_ALIGNED(obs, "obs"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(visits, "visits"); GBL_ALIGNED(params, "params");
+    GBL_ALIGNED(adam_m, "adam_m"); GBL_ALIGNED(adam_v, "adam_v"); GBL_ALIGNED(grad_out, "grad_out"); GBL_ALIGNED(stats_out, "stats_out");
+    GBL_ALIGNED(workspace, "workspace");
+    if (const char *why = train_weighted_error(prio_out, prio_scale, prio_floor, prio_cap)) return fail(GBL_ERR_ARG, why);
+    if ((reinterpret_cast<uintptr_t>(row_weight) | reinterpret_cast<uintptr_t>(row_loss_out) | reinterpret_cast<uintptr_t>(prio_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "row_weight / row_loss_out / prio_out must be 4-byte aligned");
+    float *ws = static_cast<float *>(workspace);
+    const TrainExArgs X{{obs, mask, visits, z, params, adam_m, adam_v, grad_out, stats_out,
+                         ws, ws + batch * hidden, ws + 2 * batch * hidden, ws + 2 * batch * hidden + batch * kTrainDoStride, batch, hidden,
+                         TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
+                                    hyper->bias2}},
+                        row_weight, row_loss_out, prio_out, prio_scale, prio_floor, prio_cap};
+    // gbl_train_step's launch shape, with the weighted instantiations' 4 / 4 / 2 / 2 wavefronts per SIMD
+    const int units = hidden / 64;
+    const int64_t resident = 256 * (int64_t)(units <= 2 ? 4 : 2);
+    const dim3 rows_grid((uint32_t)std::min<int64_t>((batch + kTrainRowWaves - 1) / kTrainRowWaves, resident)), rows_block(64 * kTrainRowWaves);
+    const size_t lds = train_rows_lds(hidden);
+    hipStream_t s = (hipStream_t)stream;
+    if (units == 1) hipLaunchKernelGGL((k_train_rows<1, true>), rows_grid, rows_block, lds, s, X);
+    else if (units == 2) hipLaunchKernelGGL((k_train_rows<2, true>), rows_grid, rows_block, lds, s, X);
+    else if (units == 3) hipLaunchKernelGGL((k_train_rows<3, true>), rows_grid, rows_block, lds, s, X);
+    else hipLaunchKernelGGL((k_train_rows<4, true>), rows_grid, rows_block, lds, s, X);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_train_step_weighted");
+    const uint32_t tiles = (uint32_t)((train_param_count(hidden) + 3 + 63) / 64);  // (+ 3: the statistics' lanes)
+    hipLaunchKernelGGL(k_train_reduce_adam, dim3(tiles), dim3(64 * kTrainReduceWaves), 0, s, static_cast<const TrainArgs &>(X));
+    GBL_LAUNCHED("gbl_train_step_weighted");
+}
+
+int gbl_replay_importance(const int32_t *prio, int64_t batch, float beta, float *weights_out, void *stream)
+{
+    if (const char *why = replay_importance_error(prio, batch, beta, weights_out)) return fail(GBL_ERR_ARG, why);
+    if ((reinterpret_cast<uintptr_t>(prio) | reinterpret_cast<uintptr_t>(weights_out)) & 3u)
+        return fail(GBL_ERR_ALIGN, "prio / weights_out must be 4-byte aligned");
+    // (the kernel's loops stride by the grid: one workgroup that walks the batch twice is the same kernel on a grid of 1, the experiment
+    // builds' other form -- measured slower from batch 1 024 on: DESIGN.md 5.24)
+    const dim3 grid(knob::kImportanceOneGroup ? 1u : (uint32_t)((batch + kImportanceThreads - 1) / kImportanceThreads));
+    hipLaunchKernelGGL(k_replay_importance, grid, dim3(kImportanceThreads), 0, (hipStream_t)stream, prio, batch, beta, weights_out);
+    GBL_LAUNCHED("gbl_replay_importance");
 }
 
 }  // extern "C"

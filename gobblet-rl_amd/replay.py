@@ -183,6 +183,26 @@ class ReplayBuffer(_OnDevice):
         raw = torch.where(w > 0, (total[0] / (total[1] * w.clamp(min=1))) ** float(beta), torch.zeros_like(w))
         return (raw / raw.max().clamp(min=torch.finfo(torch.float64).tiny)).to(torch.float32)
 
+    def batch_weights(self, batch: dict, beta: float, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The importance weights of a prioritised batch dict on the device, float32 (batch,): one launch of ``gbl_replay_importance``
+        (bit-defined; (smallest drawn priority / priority)^beta, 0 for a failed sample -- ``importance_weights`` within rounding), what
+        ``GobbletTrainer.step(weights=...)`` takes.  ``out``: the tensor of an earlier call to write into."""
+        self._need_priorities("batch_weights")
+        if "priority" not in batch:
+            raise ValueError("batch_weights: the dict of batch(..., prioritized=True)")
+        prio = batch["priority"]
+        beta = float(beta)
+        if not 0.0 <= beta <= 1.0:
+            raise ValueError("batch_weights: beta must be in [0, 1]")
+        if out is None:
+            out = torch.empty(prio.shape[0], dtype=torch.float32, device=self.device)
+        elif out.shape != prio.shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out: the tensor of an earlier batch_weights call of this batch size on this buffer")
+        with self._on_device():
+            nat.check(self._lib.gbl_replay_importance(prio.data_ptr(), prio.shape[0], beta, out.data_ptr(), self._stream()),
+                      "gbl_replay_importance")
+        return out
+
     def batch(self, batch: int, symmetries="all", call: int = 0, seed: int = 0, recent: int | None = None, out: dict | None = None,
               prioritized: bool = False) -> dict:
         """``batch`` rows drawn exactly uniformly from the newest ``recent`` rows (None: from all the buffer holds), each under a random
@@ -245,15 +265,37 @@ class ReplayBuffer(_OnDevice):
                            mode, count, census, None, allow_incomplete)
 
     def fit(self, trainer, steps: int, batch: int = 1024, symmetries="all", first_call: int = 0, recent: int | None = None,
-            seed: int = 0, targets=None, prioritized: bool = False) -> torch.Tensor:
+            seed: int = 0, targets=None, prioritized: bool = False, beta=None, priority: dict | None = None) -> torch.Tensor:
         """``steps`` Adam steps of ``trainer`` (a ``GobbletTrainer`` on this buffer's device): step i draws ``batch(batch, symmetries,
         call=first_call + i, recent=recent)`` into one reused buffer and hands it to ``trainer.step``; nothing crosses to the host.
         ``targets``: a ``Tablebase`` on this device -- every drawn batch goes through ``targets.targets`` first (one more launch per
         step: the fit learns from the exact labels).  Returns the steps' statistics, float32 (steps, 4) on the device, as
-        ``BatchedGobblet.fit`` does.  ``prioritized``: the batches are ``batch(..., prioritized=True)``'s."""
+        ``BatchedGobblet.fit`` does.  ``prioritized``: the batches are ``batch(..., prioritized=True)``'s.
+        ``beta`` and ``priority`` (both need ``prioritized=True``) close the loop of prioritised replay.  ``beta``: a float, or a
+        (start, end) pair annealed linearly over the steps (computed on the host in double) -- every batch's rows count with their
+        ``batch_weights(buf, beta)`` in the step.  ``priority``: ``dict(scale=, floor=1, cap=)`` -- after every step the drawn rows get
+        ``trainer.last_priority`` (``set_priority``), so the next draw rebuilds the index from the trainer's own losses.  A full step
+        is then nine launches on one stream, and the host reads nothing: index build 2, draw 1, weights 1, step 2, the trainer's
+        running maximum 1, priority update 2 (``targets`` adds its one, before the weights)."""
         if torch.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the buffer on %s" % (trainer.device, self.device))
+        if (beta is not None or priority is not None) and not prioritized:
+            raise ValueError("fit: beta= and priority= need prioritized=True")
         buf, stats = None, []
+        if beta is not None or priority is not None:
+            steps = int(steps)
+            ends = (float(beta[0]), float(beta[1])) if isinstance(beta, (tuple, list)) else None
+            weights = None
+            for i in range(steps):
+                buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=True)
+                rows = buf if targets is None else targets.targets(dict(buf))
+                if beta is not None:
+                    b = float(beta) if ends is None else ends[0] + (ends[1] - ends[0]) * (i / (steps - 1) if steps > 1 else 0.0)
+                    weights = self.batch_weights(buf, b, out=weights)
+                stats.append(trainer.step(rows, weights=weights, priority=priority))
+                if priority is not None:
+                    self.set_priority(buf["index"], trainer.last_priority)
+            return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
         for i in range(int(steps)):
             buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=prioritized)
             stats.append(trainer.step(buf if targets is None else targets.targets(dict(buf))))

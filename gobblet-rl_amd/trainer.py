@@ -45,12 +45,19 @@ class GobbletTrainer(_OnDevice):
         self.hidden_max = torch.zeros((), dtype=torch.float32, device=self.device)  # the largest hidden activation any step has seen
         self.t = 0
         self._workspace = None
+        self.last_row_loss = None  # float32 (B, 2): the rows' unweighted (policy, value) losses of the last weighted step
+        self.last_priority = None  # int32 (B,): the priorities the last step(priority=...) made of them
 
-    def step(self, batch: dict) -> torch.Tensor:
+    def step(self, batch: dict, weights: torch.Tensor | None = None, priority: dict | None = None) -> torch.Tensor:
         """One Adam step on the dict ``BatchedGobblet.training_batch`` returns ("observation", "action_mask", "visits", "z"; without
         "action_mask" every action is a candidate).  Returns float32 (4,) on the device: the mean policy loss, the mean value loss
         (with its value_reg term), the number of rows that counted and the largest hidden activation over them; nothing waits for the
-        device."""
+        device.
+        ``weights`` (float32 (B,) on the trainer's device) and ``priority`` (``dict(scale=, floor=1, cap=)``): with either the step is
+        ``gbl_train_step_weighted``'s -- row r's loss and gradient count ``weights[r]`` times (the means stay over the counted rows),
+        ``last_row_loss`` holds the rows' unweighted losses and, with ``priority``, ``last_priority`` holds
+        min(floor + int((policy loss + value loss) * scale), cap) per counted row and 0 for the others: what
+        ``ReplayBuffer.set_priority`` takes.  Both are buffers the next such step overwrites."""
         if "observation" not in batch:
             raise ValueError("step needs the 'observation' entry: a window collected with observations")
         obs, mask, visits, z = batch["observation"], batch.get("action_mask"), batch["visits"], batch["z"]
@@ -62,6 +69,7 @@ class GobbletTrainer(_OnDevice):
         for name, t, shape, dtype in spec:
             if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
                 raise ValueError(f"step: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        extra = None if weights is None and priority is None else self._weighted_arguments(n, weights, priority)
         need = nat.lib().gbl_train_workspace_bytes(n, self.hidden)  # (one function for both flavours: it launches nothing and needs no GPU)
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -69,6 +77,15 @@ class GobbletTrainer(_OnDevice):
         b1, b2 = self.betas
         hyper = nat.TrainHyper(self.lr, b1, b2, self.eps, self.weight_decay, self.value_reg, 1.0 - b1 ** self.t, 1.0 - b2 ** self.t)
         stats = torch.empty(4, dtype=torch.float32, device=self.device)
+        if extra is not None:
+            with self._on_device():
+                nat.check(self._lib.gbl_train_step_weighted(
+                    obs.data_ptr(), nat.ptr(mask), visits.data_ptr(), z.data_ptr(), n, self.hidden, self.params.data_ptr(), self.m.data_ptr(),
+                    self.v.data_ptr(), C.addressof(hyper), nat.ptr(weights), self.last_row_loss.data_ptr(),
+                    None if priority is None else self.last_priority.data_ptr(), *extra, self.last_grad.data_ptr(), stats.data_ptr(),
+                    self._workspace.data_ptr(), self._workspace.numel(), self._stream()), "gbl_train_step_weighted")
+                torch.maximum(self.hidden_max, stats[3], out=self.hidden_max)
+            return stats
         with self._on_device():
             nat.check(self._lib.gbl_train_step(obs.data_ptr(), nat.ptr(mask), visits.data_ptr(), z.data_ptr(), n, self.hidden,
                                                self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), C.addressof(hyper),
@@ -76,6 +93,24 @@ class GobbletTrainer(_OnDevice):
                                                self._workspace.numel(), self._stream()), "gbl_train_step")
             torch.maximum(self.hidden_max, stats[3], out=self.hidden_max)
         return stats
+
+    def _weighted_arguments(self, n, weights, priority):
+        """Checks ``step``'s two optional arguments, sizes the two reused output buffers and returns (scale, floor, cap)."""
+        if weights is not None and (tuple(weights.shape) != (n,) or weights.dtype != torch.float32 or weights.device != self.device
+                                    or not weights.is_contiguous()):
+            raise ValueError(f"step: weights must be a contiguous float32 tensor of shape ({n},) on {self.device}")
+        scale, floor, cap = 0.0, 0, 0
+        if priority is not None:
+            if set(priority) - {"scale", "floor", "cap"} or "scale" not in priority or "cap" not in priority:
+                raise ValueError("step: priority is dict(scale=, floor=1, cap=)")
+            scale, floor, cap = float(priority["scale"]), int(priority.get("floor", 1)), int(priority["cap"])
+            if not (0.0 <= scale < float("inf")) or not 0 <= floor <= cap < 1 << 31:
+                raise ValueError("step: priority needs a finite scale >= 0 and 0 <= floor <= cap < 2^31")
+            if self.last_priority is None or self.last_priority.shape[0] != n:
+                self.last_priority = torch.empty(n, dtype=torch.int32, device=self.device)
+        if self.last_row_loss is None or self.last_row_loss.shape[0] != n:
+            self.last_row_loss = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        return scale, floor, cap
 
     def weights(self):
         """(w1 (117, H), b1 (H,), w2 (H, 55), b2 (55,)): views of the parameter vector in ``from_float``'s shapes."""

@@ -163,6 +163,11 @@ int gbl_cpu_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, cons
 int gbl_cpu_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
                        float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
                        void *workspace, int64_t workspace_bytes, void *stream);
+int gbl_cpu_train_step_weighted(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                                float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, const float *row_weight,
+                                float *row_loss_out, int32_t *prio_out, float prio_scale, int32_t prio_floor, int32_t prio_cap, float *grad_out,
+                                float *stats_out, void *workspace, int64_t workspace_bytes, void *stream);
+int gbl_cpu_replay_importance(const int32_t *prio, int64_t batch, float beta, float *weights_out, void *stream);
 int gbl_cpu_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int16_t *visits_traj, const int8_t *z_traj,
                           const int8_t *done_traj, const int8_t *mover_traj, int64_t n, uint32_t plies, int64_t ply_stride,
                           int64_t tile_stride, int32_t tag, int8_t *ring_obs, int16_t *ring_visits, int8_t *ring_meta, int64_t capacity,

@@ -770,6 +770,34 @@ int gbl_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits,
                    float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
                    void *workspace, int64_t workspace_bytes, void *stream);
 
+/* gbl_train_step with a weight per row, and with the rows' own losses handed out: the step of a prioritised fit (a row drawn with
+ * probability priority / W counts with its importance weight, and its loss becomes its next priority).  Everything is gbl_train_step's --
+ * inputs, parameters, workspace, stats_out's layout, the two launches, every operation ONE binary32 operation in the order written -- with
+ * these additions:
+ *   row_weight float [B] (NULL: every weight is 1).  The effective weight  ww_r = (row_weight[r] > 0 && row_weight[r] <= FLT_MAX) ?
+ *     row_weight[r] : 0  -- a NaN, a negative, a zero and +inf all count 0.
+ *   Which rows count, N and M = max(N, 1) are UNCHANGED: a row of weight 0 still counts in N and in the hidden maximum (the "mean of
+ *     w * loss over the batch" form).
+ *   Forward, lp, lv and do_k of a counted row as above.  Then  do'_k = ww_r * do_k  for k = 0 .. 54, one multiply each; do' takes do's
+ *     place: dh_j is formed from do', G(w2[j][k]) = SUM(h_j * do'_k), G(b2_k) = SUM(do'_k).  The row's loss terms enter their sums as
+ *     ww_r * lp and ww_r * lv (one multiply each), so stats_out = SUM(ww lp) / M, SUM(ww lv) / M, float(N), the hidden maximum.
+ *   row_loss_out float [B][2] (may be NULL): (lp, lv) UNWEIGHTED; (0, 0) for an uncounted row.
+ *   prio_out int32 [B] (may be NULL): 0 for an uncounted row; otherwise  q = (lp + lv) * prio_scale (one add, then one multiply);
+ *     k = 0 if !(q > 0), k = 2^30 if q >= 0x1p30, else k = (int32)q (the cast truncates);  prio_out = min((int64)prio_floor + k, prio_cap).
+ *     The map is linear in the loss.  prio_scale, prio_floor and prio_cap are read only when prio_out is given.
+ *   By construction: with row_weight NULL or every weight exactly 1.0f all five outputs of gbl_train_step come out bit for bit (1.0f * x
+ *     is x, denormals included), and row_loss_out and prio_out do not depend on the weights.
+ * Errors: gbl_train_step's in its order (alignment rules included); then GBL_ERR_ARG unless prio_scale is finite and >= 0, GBL_ERR_ARG
+ * unless 0 <= prio_floor <= prio_cap (both only with prio_out); then GBL_ERR_ALIGN unless row_weight, row_loss_out and prio_out are
+ * 4-byte aligned (device flavour only).
+ * The rows kernel is a second instantiation of gbl_train_step's (the weight sits in a scalar register and is folded into the stores of
+ * do and of the loss terms; the two outputs are written by the lanes that hold lp and lv: no third launch, no atomics); the second
+ * launch is gbl_train_step's own.  Measured: DESIGN.md 5.24, profiles/r26/train_weighted.json. */
+int gbl_train_step_weighted(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                            float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, const float *row_weight,
+                            float *row_loss_out, int32_t *prio_out, float prio_scale, int32_t prio_floor, int32_t prio_cap, float *grad_out,
+                            float *stats_out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Replay buffer (no counterpart in the reference: the memory of an AlphaZero-style loop across collected windows).  A ring of
  * `capacity` compacted training rows in device memory, 1 <= capacity <= 2^31 - 1, in three arrays whose rows are whole 128-byte
  * lines (or half of one), so that a drawn row costs one line per array:
@@ -886,6 +914,20 @@ int gbl_replay_batch_prio(const int8_t *ring_obs, const int16_t *ring_visits, co
                           const uint64_t *ring_state, const int32_t *ring_prio, const void *prio_index, int32_t *prio_out, uint64_t *total_out,
                           int64_t recent, int64_t batch, int sym_mask, uint64_t seed, uint64_t sample_base, uint32_t call, int8_t *obs_out,
                           int8_t *mask_out, int16_t *visits_out, int8_t *z_out, int32_t *index_out, int16_t *sym_out, void *stream);
+
+/* The importance weights of a prioritised draw, bit-defined: prio int32 [batch] is the prio_out of a gbl_replay_batch_prio, weights_out
+ * float [batch] what gbl_train_step_weighted takes as row_weight.  The usual weight (W / (span w_j))^beta divided by the batch's largest
+ * needs only the batch, W and span cancel:
+ *   wmin = the smallest prio[j] > 0 (an integer minimum: any order);
+ *   weights_out[j] = prio[j] > 0 ? EXP(-(beta * LOG(float(prio[j]) / float(wmin)))) : 0;   every weight is 0 if no entry is positive.
+ * EXP and LOG are gbl_train_step's above, one conversion, one divide, one multiply and one negation around them.  The row at wmin gets
+ * exactly 1.0f; the LOG argument lies in [1, 2^31], where LOG is within 0.74746 ulp (measured over 2^20 evenly spaced arguments of
+ * [1, 2^31] and the range edges -- 0.60622 ulp -- and over the 2^20 of [1, 54] above, whose maximum it is; asserted as the bound by
+ * tests/test_train_weighted.py).  Against float64 (wmin / w)^beta the weights are within 2^-19 relative (measured 1.04e-6).
+ * 1 <= batch <= 65 536 and 0 <= beta <= 1 (a NaN beta included: GBL_ERR_ARG), then a missing pointer (GBL_ERR_ARG); prio and weights_out
+ * 4-byte aligned (GBL_ERR_ALIGN, device flavour).  One launch, no atomics, no waiting between workgroups: every workgroup finds the
+ * minimum over the (L2-resident, at most 256 KB) array itself. */
+int gbl_replay_importance(const int32_t *prio, int64_t batch, float beta, float *weights_out, void *stream);
 
 /* Exact tablebase (no counterpart in the reference: the game solved outright, one byte per position).  Integer-only and draws nothing:
  * the kernels, the host flavour and a restatement of this text agree byte for byte.
