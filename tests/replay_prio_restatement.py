@@ -19,6 +19,43 @@ def weights(prio):
     return np.maximum(prio.astype(np.int64), 0)
 
 
+def wide_priorities(capacity, total, seed=0):
+    """Live rows within 1 000 of 2^31 - 1, about a fifth of them 0 and about 15 % negated (weight 0); garbage where the ring is not live.
+    More than two live rows with weight pass 2^32, more than 512 pass 2^40.  (One byte per row decides its kind: a ring of 2^27 rows is
+    made in a second.)"""
+    rng = np.random.default_rng(seed + capacity)
+    p = np.int32((1 << 31) - 1) - rng.integers(0, 1000, capacity, dtype=np.int32)
+    sign = np.ones(256, np.int32)
+    sign[:51], sign[51:89] = 0, -1
+    p *= sign[np.frombuffer(rng.bytes(capacity), np.uint8)]
+    live = min(total, capacity)
+    p[live:] = rng.integers(-1 << 31, 1 << 31, capacity - live, dtype=np.int64).astype(np.int32)
+    return p
+
+
+def index_layout(prio, capacity, total):
+    """The index as csrc/gobblet_device.h lays it out, in numpy int64 from the weights of the live slots: [0] = total, [1] = W, then
+    base[0 .. blocks] (the exclusive cumsum of the weights of the blocks of 64 leaves) and local[0 .. leaves) (the exclusive cumsum of the
+    leaves' weights inside each block); a leaf is 32 slots.  This is the layout the two flavours of the library share, not the ABI: the
+    header keeps the index opaque."""
+    live = min(total, capacity)
+    leaves = -(-capacity // 32)
+    blocks = -(-leaves // 64)
+    w = np.maximum(prio, 0)
+    w[live:] = 0
+    full = capacity // 32
+    leaf = np.zeros(blocks * 64, np.int64)
+    leaf[:full] = w[:full * 32].reshape(full, 32).sum(axis=1, dtype=np.int64)
+    if full < leaves:
+        leaf[full] = w[full * 32:].sum(dtype=np.int64)
+    group = leaf.reshape(blocks, 64)
+    local = (np.cumsum(group, axis=1) - group).reshape(-1)[:leaves]
+    base = np.concatenate([[0], np.cumsum(group.sum(axis=1))])
+    words = np.concatenate([[total, base[-1]], base, local])
+    assert words.dtype == np.int64 and (words >= 0).all() and 8 * len(words) == index_bytes(capacity)
+    return words.astype(np.uint64)
+
+
 def index_bytes(capacity):
     """What the library asks for; only the size function is contract."""
     import gobblet_rl_amd._native as nat

@@ -2,7 +2,9 @@
 host flavour bit for bit (which tests/test_replay_prio.py holds to the restatement of the header), every array read back through guard
 bytes.  Shapes: rings of one slot, of a ragged second leaf, of more leaves than a wavefront sums at once, and of more leaves than the
 scan's workgroup has threads; batches of one row, a tile less one, a tile, a tile and a row, and 65 tiles and a row; windows whose
-boards are no multiple of 64 in both layouts, with the cut; updates that all name one slot and that name 4 096 different ones."""
+boards are no multiple of 64 in both layouts, with the cut; updates that all name one slot and that name 4 096 different ones.  The draw
+grid and the largest ring run a second time with priorities near 2^31 - 1 (W beyond 2^32, 2^40 and 2^50), and the device index is
+compared with the host flavour's in every word.  (Counters and byte offsets past 32 bits: tests/test_gpu_replay_wide.py.)"""
 import json
 import os
 
@@ -69,12 +71,13 @@ def host_batch(cpu, host, prio, batch, sym_mask, call, recent, index=None):
     return P.run_batch(cpu, host, prio, index, batch, sym_mask, SEED, BASE, call, recent)
 
 
-@pytest.mark.parametrize("capacity", [1, 33, 4097])
-def test_draw_equals_host_flavour(G, capacity):
+def draw_grid(G, capacity, priorities, floor=0):
+    """Draws of every batch size on a ring not yet wrapped and on a wrapped one, over everything and over a span that reaches back across
+    slot 0, and the whole index word for word, device against host flavour; every draw's W is above `floor`."""
     lib, cpu = G._native.lib(), G._native.cpu_raw()
     for total in sorted({max(2 * capacity // 3, 1), 2 * capacity + capacity // 2 + 1}):   # not yet wrapped (full at one slot), wrapped mid-ring
         host = ring_at(capacity, total)
-        prio = random_priorities(capacity, total)
+        prio = priorities(capacity, total)
         if capacity == 1:
             prio[0] = 3
         ring, dprio = DeviceRing(host), Guarded(prio)
@@ -85,11 +88,35 @@ def test_draw_equals_host_flavour(G, capacity):
             for batch in (1, 63, 64, 65, 4161):
                 got = device_batch(lib, ring, dprio, index, batch, 511, 3, recent)
                 P.same_batch(got, host_batch(cpu, host, prio, batch, 511, 3, recent, hindex))
-                assert int(got["total"][0]) > 0
+                assert int(got["total"][0]) > floor
         words = index.read()
         assert words[0] == hindex[0] == total and words[1] == hindex[1]
+        assert words.dtype == hindex.dtype and np.array_equal(words, hindex), np.argwhere(words != hindex)[:5]   # every word, not only those a draw read
         assert np.array_equal(dprio.read(), prio)
         R.same_ring(ring.read(), host)   # (a draw writes nothing into the ring)
+
+
+@pytest.mark.parametrize("capacity", [1, 33, 4097])
+def test_draw_equals_host_flavour(G, capacity):
+    draw_grid(G, capacity, random_priorities)
+
+
+@pytest.mark.parametrize("capacity,floor", [(33, 1 << 32), (4097, 1 << 40)])
+def test_draw_with_weights_beyond_32_bits_equals_host_flavour(G, capacity, floor):
+    """The same grid with live priorities within 1 000 of 2^31 - 1 (P.wide_priorities): every W passes 2^32 (2^40 on the larger ring), so
+    the upper halves of the index's words, of the sums in its two kernels, of the product in replay_mulhi64 and of both binary searches'
+    comparisons are not zero on the device."""
+    draw_grid(G, capacity, P.wide_priorities, floor)
+
+
+def slot_marked_ring(capacity, total):
+    """A ring without observations, zeros but for what tells the slots apart (random rows would take seconds to make)."""
+    host = R.new_ring(capacity, observations=False)
+    slot = np.arange(capacity)
+    host["visits"][:, 0], host["visits"][:, 53], host["meta"][:, 7], host["meta"][:, R.META_Z] = slot & 0x7FFF, slot >> 15, slot & 1, slot % 3 - 1
+    host["meta"][:, R.META_TAG:R.META_TAG + 4] = slot.astype("<i4").view(np.int8).reshape(-1, 4)
+    host["state"][0] = total
+    return host
 
 
 def test_a_ring_of_more_leaves_than_the_scan_has_threads(G):
@@ -99,11 +126,7 @@ def test_a_ring_of_more_leaves_than_the_scan_has_threads(G):
     lib, cpu = G._native.lib(), G._native.cpu_raw()
     capacity = (1 << 21) + 33
     total = 3 * capacity + 1000
-    host = R.new_ring(capacity, observations=False)   # (zeros but for what tells the slots apart: random rows would take seconds to make)
-    slot = np.arange(capacity)
-    host["visits"][:, 0], host["visits"][:, 53], host["meta"][:, 7], host["meta"][:, R.META_Z] = slot & 0x7FFF, slot >> 15, slot & 1, slot % 3 - 1
-    host["meta"][:, R.META_TAG:R.META_TAG + 4] = slot.astype("<i4").view(np.int8).reshape(-1, 4)
-    host["state"][0] = total
+    host = slot_marked_ring(capacity, total)
     prio = random_priorities(capacity, total)
     ring, dprio = DeviceRing(host), Guarded(prio)
     hindex = P.run_index(cpu, host, prio)
@@ -126,6 +149,30 @@ def test_a_ring_of_more_leaves_than_the_scan_has_threads(G):
     got = device_batch(lib, ring, dprio, device_index(lib, ring, dprio), 65, 7, 2, 40)
     P.same_batch(got, host_batch(cpu, host, prio, 65, 7, 2, 40))
     assert got["total"][1] == 40 and (got["index"][:, 0] < capacity - 1).all()
+
+
+def test_the_large_ring_with_weights_beyond_32_bits(G):
+    """The ring above (2^21 + 33 slots, wrapped) with P.wide_priorities: W is about 2^51, the blocks' bases pass 2^32 from the second block
+    on and a leaf's local prefix from its block's second leaf on.  The whole index and 4 161 draws at three spans against the host flavour;
+    prio_out is the weight of the drawn slot."""
+    lib, cpu = G._native.lib(), G._native.cpu_raw()
+    capacity = (1 << 21) + 33
+    total = 3 * capacity + 1000
+    host = slot_marked_ring(capacity, total)
+    prio = P.wide_priorities(capacity, total)
+    ring, dprio = DeviceRing(host), Guarded(prio)
+    hindex = P.run_index(cpu, host, prio)
+    index = device_index(lib, ring, dprio)
+    for recent in (0, 5000, capacity - 7):
+        got = device_batch(lib, ring, dprio, index, 4161, 511, 1, recent)
+        P.same_batch(got, host_batch(cpu, host, prio, 4161, 511, 1, recent, hindex))
+        drawn = got["index"][:, 0]
+        assert (drawn >= 0).all() and np.array_equal(got["prio"], P.weights(prio[drawn]).astype(np.int32)) and (got["prio"] > 0).all()
+        assert int(got["total"][0]) > (1 << 50 if recent != 5000 else 1 << 42)
+    words = index.read()
+    assert words.dtype == hindex.dtype and np.array_equal(words, hindex), np.argwhere(words != hindex)[:5]
+    assert int(words[1]) == int(P.weights(prio).sum()) > 1 << 50
+    assert np.array_equal(dprio.read(), prio)
 
 
 def test_failed_samples_without_weight_and_with_a_stale_index(G):

@@ -110,6 +110,27 @@ def test_batch_host_flavour_equals_restatement(cpu, capacity, times):
     assert not np.array_equal(b["index"], R.run_batch(cpu, ring, 64, 511, SEED + 1, BASE, 0, 0)["index"])
 
 
+@pytest.mark.parametrize("capacity", [33, 1000])
+def test_batch_of_a_ring_that_has_taken_more_than_2_to_the_32_rows(cpu, capacity):
+    """ring_state[0] is a uint64 count of rows ever appended: the newest slot is (total - 1) mod capacity in 64 bits.  None of the three
+    totals gives the same slot when it is cut to 32 bits first (asserted), and one `recent` reaches back across slot 0."""
+    crossed = False
+    for total in ((1 << 32) + 5, 3 * (1 << 32) + capacity // 2, (1 << 40) + 3):
+        ring = R.new_ring(capacity, junk=capacity)
+        ring["meta"][:, R.META_MOVER] &= 1
+        ring["state"][0] = total
+        newest = (total - 1) % capacity
+        assert newest != ((total - 1) & 0xFFFFFFFF) % capacity
+        for recent in (0, 7, capacity - 1):
+            exp = R.batch(ring, 65, 511, SEED, BASE, 3, recent)
+            R.same_batch(R.run_batch(cpu, ring, 65, 511, SEED, BASE, 3, recent), exp)
+            span = recent if recent else capacity
+            age = (newest - exp["index"][:, 0]) % capacity
+            assert age.max() < span and (span > 7 or set(age.tolist()) == set(range(span)))
+            crossed |= recent > newest + 1 and bool((exp["index"][:, 0] > newest).any())
+    assert crossed
+
+
 def test_batch_of_an_empty_buffer_and_of_one_without_observations(cpu):
     empty = R.new_ring(50, junk=2)
     got = R.run_batch(cpu, empty, 65, 511, 1, 0, 0, 0)

@@ -1,7 +1,9 @@
 """Prioritised replay, host flavour (no GPU): gbl_cpu_replay_prio_append, _update, _index and gbl_cpu_replay_batch_prio against the numpy
 restatement of the header's paragraph (tests/replay_prio_restatement.py), bit for bit and every output; the frequencies of the draw on a
-small ring; ReplayBuffer(prioritized=True) on the host flavour (the stale-index bookkeeping, importance weights, fit against the
-hand-written loop, state_dict; an unprioritised buffer as before) and the recorded argument errors of both flavours."""
+small ring; draws of a ring that has taken more than 2^32 rows, the index word for word against its layout, and a ring far along against
+a small ring translated (what the device tests past 32 bits rest on); ReplayBuffer(prioritized=True) on the host flavour (the stale-index
+bookkeeping, importance weights, fit against the hand-written loop, state_dict; an unprioritised buffer as before) and the recorded
+argument errors of both flavours."""
 import json
 import os
 
@@ -120,6 +122,94 @@ def test_weights_beyond_32_bits(cpu):
     for recent in (0, 4500):
         exp, _ = draw_both(cpu, ring, prio, 300, 7, 1, recent)
         assert int(exp["total"][0]) > 1 << 42 and len(set(exp["index"][:, 0].tolist())) > 250 and (exp["prio"] > (1 << 31) - 1002).all()
+
+
+@pytest.mark.parametrize("capacity", [33, 1000])
+def test_draw_of_a_ring_that_has_taken_more_than_2_to_the_32_rows(cpu, capacity):
+    """state[0] beyond 2^32 (the span's first slot is (total - span) mod capacity in 64 bits) with weights near 2^31 - 1, about 30 % of
+    them 0: W passes 2^32, so r = floor(u W / 2^64) needs every one of the four partial products.  `recent` = 7 and capacity - 1: prefixes
+    that end inside a leaf, one span that crosses slot 0."""
+    crossed = False
+    for total in ((1 << 32) + 5, 3 * (1 << 32) + capacity // 2, (1 << 40) + 3):
+        ring = ring_at(capacity, total)
+        rng = np.random.default_rng(capacity + total % 1000)
+        prio = ((1 << 31) - 1 - rng.integers(0, 1000, capacity)).astype(np.int32)
+        prio[rng.random(capacity) < 0.3] = 0
+        for recent in (0, 7, capacity - 1):
+            exp, _ = draw_both(cpu, ring, prio, 65, 511, 3, recent)
+            span = recent if recent else capacity
+            slots = [(total - span + q) % capacity for q in range(span)]
+            assert total % capacity != (total & 0xFFFFFFFF) % capacity
+            W = int(P.weights(prio[slots]).sum())
+            assert exp["total"].tolist() == [W, span] and (W > 1 << 32 or recent == 7)
+            drawn = exp["index"][:, 0]
+            assert set(drawn.tolist()) <= set(slots) and np.array_equal(exp["prio"], prio[drawn]) and (exp["prio"] > 0).all()
+            crossed |= slots[0] > slots[-1]
+    assert crossed
+
+
+def test_a_ring_far_along_is_a_small_ring_translated(cpu):
+    """What tests/test_gpu_replay_wide.py rests on, here on the host flavour: a window of K rows appended at state[0] = T0 >= 2^33 leaves in
+    slot (T0 + r) mod capacity what it leaves in slot r of a ring of exactly K slots appended at 0 -- rows and priorities --, the uniform
+    draw over the newest K rows and the weighted draws (every other priority 0) are the small ring's with the slots translated.  Mid-ring
+    and across the ring's end."""
+    w = R.real_window("time")
+    K, capacity = R.count_valid(w), 1097
+    rng = np.random.default_rng(7)
+    per_cell = ((1 << 31) - 1 - rng.integers(0, 1000, w["z"].shape[0])).astype(np.int32)
+    per_cell[rng.random(len(per_cell)) < 0.25] = 0
+    small, sprio = R.new_ring(K), np.zeros(K, np.int32)
+    R.run_append(cpu, small, w, 9)
+    P.run_prio_append(cpu, small, sprio, w, per_cell, 0)
+    sindex = P.run_index(cpu, small, sprio)
+    for m, first in (((1 << 33) // capacity + 1, 400), ((1 << 52) // capacity + 3, capacity - K // 2)):
+        T0 = m * capacity + first
+        assert T0 >= 1 << 33 and T0 % capacity == first and T0 % capacity != (T0 & 0xFFFFFFFF) % capacity
+        ring, prio = R.new_ring(capacity), np.zeros(capacity, np.int32)
+        ring["state"][0] = T0
+        R.run_append(cpu, ring, w, 9)
+        P.run_prio_append(cpu, ring, prio, w, per_cell, 0)
+        slots = (T0 + np.arange(K)) % capacity
+        assert ring["state"].tolist() == [T0 + K, K] and np.array_equal(prio[slots], sprio) and np.count_nonzero(prio) == np.count_nonzero(sprio)
+        for k in ("obs", "visits", "meta"):
+            assert np.array_equal(ring[k][slots], small[k]) and np.count_nonzero(ring[k]) == np.count_nonzero(small[k]), k
+        index = P.run_index(cpu, ring, prio)
+        exp = R.run_batch(cpu, small, 130, 511, SEED, BASE, 3, 0)
+        exp["index"][:, 0] = (T0 + exp["index"][:, 0].astype(np.int64)) % capacity
+        R.same_batch(R.run_batch(cpu, ring, 130, 511, SEED, BASE, 3, K), exp)
+        exp = P.run_batch(cpu, small, sprio, sindex, 130, 511, SEED, BASE, 3, 0)
+        exp["index"][:, 0] = (T0 + exp["index"][:, 0].astype(np.int64)) % capacity
+        for recent in (0, K, K + 50):
+            exp["total"][1] = recent if recent else capacity
+            P.same_batch(P.run_batch(cpu, ring, prio, index, 130, 511, SEED, BASE, 3, recent), exp)
+
+
+@pytest.mark.parametrize("capacity", [1, 33, 4097, (1 << 27) + 3 * 2048 + 33])
+def test_index_of_the_host_flavour_word_for_word(cpu, capacity):
+    """Every word of the host flavour's index against P.index_layout: the layout that the two flavours share (csrc/gobblet_cpu.cpp builds
+    the device flavour's, csrc/gobblet_device.h states it), NOT the ABI -- the header keeps the index opaque, and only the library reads
+    it.  The device tests compare the kernels' index with this one word for word, so this closes the chain for the words no draw happens
+    to read.  The last capacity has more blocks than the leaves kernel has workgroups and a ragged last leaf of one slot; W is about
+    2^57.5 there.  At that size the states are those of the device test (tests/test_gpu_replay_wide.py): wrapped, and capacity - 1 and
+    capacity - 3 with the LARGEST weight in every slot that is not live, so an index that counted one of them differs."""
+    big = capacity > 1 << 27
+    totals = (3 * capacity + 1000, capacity - 1, capacity - 3) if big else (3 * capacity + 1000, max(2 * capacity // 3, 1))
+    prio = None
+    for total in totals:   # wrapped; not wrapped, garbage behind the live rows
+        if big and prio is not None:   # (one array at this size: making it is what costs)
+            prio[total:] = (1 << 31) - 1
+            assert (prio[capacity - 5:] > 0).all()   # live and dead entries of the last vectors alike
+        else:
+            prio = P.wide_priorities(capacity, total)
+        if capacity == 1:
+            prio[0] = (1 << 31) - 1
+        ring = {"capacity": capacity, "state": np.array([total, 0], np.uint64)}
+        got = P.run_index(cpu, ring, prio)
+        exp = P.index_layout(prio, capacity, total)
+        assert got.dtype == exp.dtype and np.array_equal(got, exp), np.argwhere(got != exp)[:5]
+        assert int(got[1]) == int(np.maximum(prio[:min(total, capacity)], 0).sum(dtype=np.int64)) > 0
+        if big:
+            assert int(got[1]) > 1 << 57 and len(got) == 2 + 65540 + 1 + 4194498
 
 
 def test_every_optional_output_null_in_turn_and_a_ring_without_observations(cpu):
