@@ -11,7 +11,8 @@
     symmetry         the 512 board symmetries; BatchedGobblet.training_batch draws symmetry-augmented batches on the device
     SolverGobbletPolicy  the exact bounded-depth solver: proven wins and losses per action, optionally over another policy
     GobbletTrainer   the float network behind GobbletEvaluator.from_float and its Adam step on the device (BatchedGobblet.fit)
-    ReplayBuffer     a ring of compacted training rows on the device: windows appended, exact symmetry-augmented draws, fit
+    ReplayBuffer     a ring of compacted training rows on the device: windows appended, exact symmetry-augmented draws, fit;
+                     ReplayBuffer.reanalyse / GobbletEvaluator.reanalyse: stored rows' visits from the current network's search
     Tablebase        the game solved outright, one byte per position: retrograde sweeps and probes; TablebaseGobbletPolicy plays from it
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in

@@ -15,6 +15,7 @@
 //   -DGBL_COLLECT_WAVES_PER_EU=a,b / -DGBL_CP_WAVES_PER_EU=n   occupancy pins of k_collect / k_collect_policy
 //   -DGBL_SOLVE_DEAL=0|1          k_solve's (action, reply) pairs dealt interleaved / off a counter in LDS
 //   -DGBL_IMPORTANCE_ONE_GROUP=1  gbl_replay_importance launches ONE workgroup, which walks the batch twice (scripts/bench_train_weighted.py)
+//   -DGBL_REANALYSE_GROUPS=n      gbl_reanalyse's grid cap (scripts/bench_reanalyse.py ring)
 #pragma once
 
 #ifndef GBL_X_GREEDY_SKIP
@@ -44,11 +45,15 @@
 #ifndef GBL_IMPORTANCE_ONE_GROUP
 #define GBL_IMPORTANCE_ONE_GROUP 0
 #endif
+#ifndef GBL_REANALYSE_GROUPS
+#define GBL_REANALYSE_GROUPS (1 << 20)
+#endif
 
 namespace gbl {
 namespace knob {
 constexpr int kSolveDeal = GBL_SOLVE_DEAL;
 constexpr int kImportanceOneGroup = GBL_IMPORTANCE_ONE_GROUP;
+constexpr int kReanalyseGroups = GBL_REANALYSE_GROUPS;
 constexpr int kGreedySkip = GBL_X_GREEDY_SKIP;
 constexpr int kGreedyPairCap = GBL_X_GREEDY_PAIR_CAP;
 constexpr int kForcedNt = GBL_FORCE_NT;

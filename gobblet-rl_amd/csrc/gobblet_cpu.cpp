@@ -1707,6 +1707,71 @@ int gbl_cpu_tb_targets(const int32_t *inventory, const void *aux, const int8_t *
     return GBL_OK;
 }
 
+// Reanalysis (include/gobblet_hip.h, "Reanalysis"): decode_obs_row, host_tree_search_eval and the rule's scalar pieces, row by row.  The
+// visits rows go through memcpy: the host flavour asks no alignment of them.
+int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                      int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                      int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
+                      int32_t *drift_out, int8_t *census_out, int64_t n, void *)
+{
+    bool empty;
+    if (const char *why = reanalyse_error(ev, iterations, explore, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
+                                          z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n, &empty))
+        return fail(GBL_ERR_ARG, why);
+    if (empty) return GBL_OK;
+    const EvalNet net = eval_net(ev);
+    const char *vin = reinterpret_cast<const char *>(visits_in);
+    char *vout = reinterpret_cast<char *>(visits_out);
+    parallel_for(n, [=](int64_t r0, int64_t r1) {  // (a row is a whole search: every row is worth a thread)
+        std::vector<TreeNode> nodes((size_t)iterations + 1);
+        std::vector<uint8_t> pri(((size_t)iterations + 1) * kEvalOutputs);
+        HostSearch h;
+        for (int64_t r = r0; r < r1; ++r) {
+            const int z_old = z_in ? (int)z_in[r * z_pitch] : 0;
+            int q = 0, action = -1, drift = -1, census = -1, count = 0;
+            uint8_t pi[kActions] = {};
+            if (!(z_in && z_old == kZOpen)) {
+                uint32_t d[30], row[7];
+                d[29] = 0;
+                memcpy(d, obs + r * obs_pitch, kObs);
+                const int mover = decode_obs_row(d, row) != 0;
+                const Planes p = make_planes(row);
+                uint64_t cand = legal54(p, mover);
+                if (mask) cand &= read_mask(mask + r * mask_pitch);
+                q = host_tree_search_eval(nodes, pri, net, p, mover, cand, (uint32_t)iterations, (uint32_t)explore, h, HostNoise{0, 0, 0, 0, pi});
+                action = tree_action_of(h.best);
+                count = (int)h.count;
+                int16_t old[kActions] = {}, now[kActions];
+                if (visits_in) memcpy(old, vin + r * visits_pitch * 2, sizeof old);  // (read before the row is written: it may be the same row)
+                uint32_t So = 0, Sn = 0, diff = 0, top_old = 0, top_new = 0;
+                for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+                    now[a] = (int16_t)h.visits[a];
+                    So += (uint32_t)std::max<int>(old[a], 0);
+                    Sn += (uint32_t)h.visits[a];
+                }
+                for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+                    const uint32_t x = (uint32_t)std::max<int>(old[a], 0) * Sn, y = (uint32_t)h.visits[a] * So;
+                    diff += x > y ? x - y : y - x;
+                    top_old = std::max(top_old, tb_visit_key(old[a], a));
+                    top_new = std::max(top_new, tb_visit_key(now[a], a));
+                }
+                if (cand) {
+                    drift = reanalyse_drift(visits_in != nullptr, So, Sn, diff);
+                    census = reanalyse_census(top_old, top_new, z_in != nullptr, z_old, q);
+                }
+                if (visits_out) memcpy(vout + r * visits_pitch * 2, now, sizeof now);
+            }
+            if (root_value_out) root_value_out[r] = q;
+            if (root_priors_out) memcpy(root_priors_out + r * kActions, pi, sizeof pi);
+            if (action_out) action_out[r] = action;
+            if (nodes_out) nodes_out[r] = count;
+            if (drift_out) drift_out[r] = drift;
+            if (census_out) census_out[r] = (int8_t)census;
+        }
+    }, 1);
+    return GBL_OK;
+}
+
 }  // extern "C"
 
 // gbl_cpu_train_step: the header's rule row by row and element by element -- the same scalar pieces (gobblet_device.h: train_exp,

@@ -3487,6 +3487,66 @@ inline const char *tb_targets_error(const int32_t *inventory, const void *aux, c
     return nullptr;
 }
 
+// ---- reanalysis (include/gobblet_hip.h, "Reanalysis"): the scalar pieces of the rule, shared by k_reanalyse and the host flavour ------
+// the drift of a row with a candidate: diff = sum over a of |o_a Sn - n_a So| (at most 2 So Sn <= 2 * 54 * 32767 * 512 < 2^32, so the
+// sum and the divisor fit 32 bits and the product by 1024 fits 64); has_old: visits_in is given
+__device__ __forceinline__ int reanalyse_drift(bool has_old, uint32_t So, uint32_t Sn, uint32_t diff)
+{
+    if (!has_old) return -1;
+    if (!So) return 1024;
+    return (int)((1024ull * (uint64_t)diff) / (2ull * (uint64_t)So * (uint64_t)Sn));
+}
+// the census byte of a row with a candidate: `top_old` / `top_new` the largest tb_visit_key of the old visits (0: none positive, or no
+// visits_in) and of the new ones (never 0: every iteration visits a child of the root); tb_census with the new argmax as the only kept action
+__device__ __forceinline__ int reanalyse_census(uint32_t top_old, uint32_t top_new, bool has_z, int z_old, int root_q)
+{
+    return tb_census(top_old, 1ull << (63u - (top_new & 63u)), has_z, z_old, tb_sign(root_q));
+}
+
+// the message of the first rule a gbl_reanalyse call breaks, or nullptr; *empty = the call has nothing to do (n == 0 after the scalar checks)
+template <typename Ev>
+inline const char *reanalyse_error(const Ev *ev, int iterations, int explore, const void *obs, int64_t obs_pitch, const void *mask,
+                                   int64_t mask_pitch, const void *visits_in, const void *visits_out, int64_t visits_pitch, const void *z_in,
+                                   int64_t z_pitch, const void *root_value_out, const void *root_priors_out, const void *action_out,
+                                   const void *nodes_out, const void *drift_out, const void *census_out, int64_t n, bool *empty)
+{
+    *empty = false;
+    if (const char *why = evaluator_error(ev)) return why;
+    if (const char *why = tree_eval_budget_error(iterations, explore)) return why;
+    if (n < 0) return "n < 0";
+    if (obs_pitch < kObs) return "obs_pitch must be at least 117";
+    if (mask && mask_pitch < kActions) return "mask_pitch must be at least 54";
+    if ((visits_in || visits_out) && visits_pitch < kActions) return "visits_pitch must be at least 54";
+    if (z_in && z_pitch < 1) return "z_pitch must be at least 1";
+    if (n == 0) {
+        *empty = true;
+        return nullptr;
+    }
+    if (const char *why = evaluator_pointers_error(ev)) return why;
+    if (!obs) return "obs must not be NULL";
+    if (!visits_out && !root_value_out && !root_priors_out && !action_out && !nodes_out && !drift_out && !census_out)
+        return "at least one output must be given";
+    // every output against every input; visits_in == visits_out is the in-place form (that one pair is let through: the other outputs
+    // are still checked against visits_in).  The evaluator's arrays are single rows.
+    const int64_t H = ev->hidden;
+    const TbSpan in[8] = {tb_span(obs, obs_pitch, kObs, 1), tb_span(mask, mask_pitch, kActions, 1),
+                          tb_span(visits_in, visits_pitch, kActions, 2), tb_span(z_in, z_pitch, 1, 1),
+                          tb_span(ev->w1, 0, (int64_t)kObs * H, 1), tb_span(ev->b1, 0, H, 4), tb_span(ev->w2, 0, H * kEvalOutputs, 1),
+                          tb_span(ev->b2, 0, kEvalOutputs, 4)};
+    const TbSpan out[7] = {tb_span(visits_out, visits_pitch, kActions, 2), tb_span(root_value_out, 1, 1, 4),
+                           tb_span(root_priors_out, kActions, kActions, 1), tb_span(action_out, 1, 1, 4), tb_span(nodes_out, 1, 1, 4),
+                           tb_span(drift_out, 1, 1, 4), tb_span(census_out, 1, 1, 1)};
+    for (int o = 0; o < 7; ++o)
+        for (int i = 0; i < 8; ++i) {
+            if (o == 0 && i == 2 && visits_in == visits_out) continue;
+            const bool one = i >= 4;
+            if (one ? tb_spans_overlap(TbSpan{out[o].base, 0, (uint64_t)(n - 1) * out[o].pitch + out[o].row}, in[i], 1)
+                    : tb_spans_overlap(in[i], out[o], n))
+                return "an output overlaps an input (only visits_in == visits_out may alias)";
+        }
+    return nullptr;
+}
+
 // ---- gbl_train_step (include/gobblet_hip.h, "One Adam step of the FLOAT network"): the scalar pieces of the bit-defined rule ----------
 // Shared by k_train_rows / k_train_reduce_adam and the host flavour.  Every function that does float arithmetic for the rule opens
 // with GBL_FP_STRICT, and so do the two kernels and the host flavour's own loops (train_row, train_sum, gbl_cpu_train_step): hipcc

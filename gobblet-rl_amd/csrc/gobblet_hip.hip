@@ -3108,6 +3108,76 @@ __global__ __launch_bounds__(64 * kTbTargetWaves) void k_tb_targets(TbTargetArgs
     }
 }
 
+// ---- reanalysis (include/gobblet_hip.h, "Reanalysis") ---------------------------------------------------------------------------------
+// k_reanalyse    k_tree_eval's geometry over pitched rows: one wavefront per row, one wavefront per workgroup, a grid-stride loop over the
+//                rows, the tree in (iterations + 1) 16-byte nodes and 56-byte prior rows of dynamic LDS beside s_h.  The board never
+//                exists as a state row (obs_planes, as k_tb_targets); the search is tree_eval_iterations<false>, the code k_tree_eval
+//                and k_collect_eval run.  Lane a then holds the root's child of action a (tree_lane_child): the decision, the two
+//                argmaxes and the sums So, Sn and sum |o_a Sn - n_a So| are butterflies, the division is one per row.  The old visits
+//                are read before the new ones are stored, so visits_out may be visits_in.
+struct ReanalyseArgs {
+    EvalNet net;
+    const int8_t *obs, *mask;
+    const int16_t *visits_in;  // (may be visits_out: no __restrict__ here)
+    int16_t *visits_out;
+    const int8_t *z_in;
+    int32_t *root_value_out;
+    uint8_t *root_priors_out;
+    int32_t *action_out, *nodes_out, *drift_out;
+    int8_t *census_out;
+    int64_t obs_pitch, mask_pitch, visits_pitch, z_pitch, n;
+    uint32_t iterations, explore;
+};
+
+__global__ __launch_bounds__(64) void k_reanalyse(ReanalyseArgs a)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + a.iterations + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    const uint32_t lane = threadIdx.x;
+    const bool act = lane < (uint32_t)kActions;
+    for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
+        const int z_old = a.z_in ? uniform((int)a.z_in[r * a.z_pitch]) : 0;
+        int q = 0, action = -1, drift = -1, census = -1;
+        uint32_t count = 0, pi = 0;
+        if (!(a.z_in && z_old == kZOpen)) {  // (uniform) a skipped row writes no visits
+            int mover;
+            const Planes root = obs_planes(a.obs + r * a.obs_pitch, lane, mover);
+            const uint64_t cand = board_candidates(root, mover, a.mask ? a.mask + r * a.mask_pitch : nullptr, 0, lane);
+            uint32_t mixed;
+            const WaveEval at_root = tree_eval_iterations<false>(nodes, pri, s_h, a.net, root, mover, cand, a.iterations, a.explore, lane, count,
+                                                                 RootNoise{}, mixed);
+            const TreeChild c = tree_lane_child(nodes, nodes[0].child, lane);
+            const uint32_t now = c.visits();
+            action = tree_action_of(wave_max(c.mine() ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
+            q = at_root.q;
+            pi = at_root.pi;
+            if (cand && (a.drift_out || a.census_out)) {  // (uniform)
+                const uint32_t old = a.visits_in && act ? (uint32_t)max((int)a.visits_in[r * a.visits_pitch + lane], 0) : 0u;
+                const uint32_t So = wave_sum(old), Sn = wave_sum(now);
+                if (a.drift_out) {
+                    const uint32_t x = old * Sn, y = now * So;
+                    drift = reanalyse_drift(a.visits_in != nullptr, So, Sn, wave_sum(x > y ? x - y : y - x));
+                }
+                if (a.census_out)
+                    census = reanalyse_census(wave_max(tb_visit_key((int)old, lane)), wave_max(tb_visit_key((int)now, lane)), a.z_in != nullptr,
+                                              z_old, q);
+            }
+            if (a.visits_out && act) a.visits_out[r * a.visits_pitch + lane] = (int16_t)now;
+            wave_lds_fence();  // (before the next row rewrites the root)
+        }
+        if (a.root_priors_out && act) a.root_priors_out[r * kActions + lane] = (uint8_t)pi;
+        if (lane == 0) {
+            if (a.root_value_out) a.root_value_out[r] = q;
+            if (a.action_out) a.action_out[r] = action;
+            if (a.nodes_out) a.nodes_out[r] = (int32_t)count;
+            if (a.drift_out) a.drift_out[r] = drift;
+            if (a.census_out) a.census_out[r] = (int8_t)census;
+        }
+    }
+}
+
 // gbl_train_step: the float trainer's Adam step in two launches, bit-defined by the header (every float operation below is the
 // header's, in its order; GBL_FP_STRICT keeps hipcc from fusing them).
 //   k_train_rows          one wavefront per row (four per workgroup, rows dealt grid-stride), w2 staged in LDS once per workgroup:
@@ -5605,6 +5675,31 @@ int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *tabl
     const int64_t groups = std::min<int64_t>((n + kTbTargetWaves - 1) / kTbTargetWaves, kTbTargetGroups);
     hipLaunchKernelGGL(k_tb_targets, dim3((uint32_t)groups), dim3(64 * kTbTargetWaves), 0, (hipStream_t)stream, A);
     GBL_LAUNCHED("gbl_tb_targets");
+}
+
+int gbl_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                  int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int64_t z_pitch,
+                  int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out, int32_t *drift_out,
+                  int8_t *census_out, int64_t n, void *stream)
+{
+    bool empty;
+    if (const char *why = reanalyse_error(ev, iterations, explore, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
+                                          z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n, &empty))
+        return fail(GBL_ERR_ARG, why);
+    if (empty) return GBL_OK;
+    EvalNet net;
+    if (const int e = eval_net_of(ev, net)) return e;
+    if (reinterpret_cast<uintptr_t>(visits_in) & 1u) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(visits_out) & 1u) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
+    if (off_dword(root_value_out, action_out, nodes_out, drift_out))
+        return fail(GBL_ERR_ALIGN, "root_value_out / action_out / nodes_out / drift_out must be 4-byte aligned");
+    const ReanalyseArgs A{net, obs, mask, visits_in, visits_out, z_in, root_value_out, root_priors_out, action_out, nodes_out, drift_out,
+                          census_out, obs_pitch, mask_pitch, visits_pitch, z_pitch, n, (uint32_t)iterations, (uint32_t)explore};
+    // the tree as gbl_tree_search_eval's: a node and a prior row per iteration, and the root's
+    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);
+    const int64_t groups = std::min<int64_t>(n, knob::kReanalyseGroups);
+    hipLaunchKernelGGL(k_reanalyse, dim3((uint32_t)groups), dim3(64), lds, (hipStream_t)stream, A);
+    GBL_LAUNCHED("gbl_reanalyse");
 }
 
 int64_t gbl_train_workspace_bytes(int64_t batch, int hidden) { return train_workspace_bytes(batch, hidden); }

@@ -15,7 +15,7 @@
 #if defined(GBL_X_GREEDY_SKIP) || defined(GBL_FORCE_NT) || defined(GBL_FORCE_COLLECT_NT) || defined(GBL_FORCE_COLLECT_PAIR) || \
     defined(GBL_FORCE_COLLECT_SMALL) || defined(GBL_AB_COLLECT_CFG) || defined(GBL_FORCE_GREEDY_SHAPE) ||                     \
     defined(GBL_COLLECT_WAVES_PER_EU) || defined(GBL_CP_WAVES_PER_EU) || defined(GBL_X_GREEDY_PAIR_CAP) || defined(GBL_SOLVE_DEAL) || \
-    defined(GBL_IMPORTANCE_ONE_GROUP)
+    defined(GBL_IMPORTANCE_ONE_GROUP) || defined(GBL_REANALYSE_GROUPS)
 #error "experiment knobs need -DGBL_AB_BUILD (csrc/gobblet_ab.h): the product build has none"
 #endif
 
@@ -31,6 +31,7 @@ constexpr int kForcedGreedyShape = 0;     // the greedy kernels' block shape for
 inline int collect_cfg_override() { return -1; }  // a form picked at run time (gbl_ab_collect_cfg): none
 constexpr int kSolveDeal = 0;             // how k_solve deals its (action, reply) pairs: 0 = interleaved, 1 = off an LDS counter
 constexpr int kImportanceOneGroup = 0;    // gbl_replay_importance's launch: 0 = a grid whose workgroups each find the minimum, 1 = one workgroup
+constexpr int kReanalyseGroups = 1 << 20; // gbl_reanalyse's grid cap, k_tree_eval's: a workgroup per row up to 2^20 rows (a smaller grid was measured slower), the rest by the stride
 }  // namespace knob
 }  // namespace gbl
 

@@ -139,6 +139,51 @@ class GobbletEvaluator(_OnDevice):
         pri = pri.to(torch.float32)
         return pri / pri.sum(1, keepdim=True).clamp(min=1.0), val.to(torch.float32) / 128.0
 
+    # ---- reanalysis: fresh search targets for stored rows ---------------------------------------------------------------------------
+    def _reanalyse(self, n, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z, z_pitch, iterations, explore, census,
+                   root_value=None):
+        """One launch of ``gbl_reanalyse`` on ``n`` pitched rows (data pointers); returns (drift int32 (n,), census int8 (n,) or None)."""
+        for name, val, lo, hi in (("iterations", iterations, 1, 512), ("explore", explore, 0, 1024)):
+            if not lo <= int(val) <= hi:
+                raise ValueError(f"{name} must be in [{lo}, {hi}]")
+        drift = torch.empty(n, dtype=torch.int32, device=self.device)
+        tally = torch.empty(n, dtype=torch.int8, device=self.device) if census else None
+        ev = self.as_struct()
+        with self._on_device():
+            nat.check(self._lib.gbl_reanalyse(C.addressof(ev), int(iterations), int(explore), obs, obs_pitch, mask, mask_pitch, visits_in,
+                                              visits_out, visits_pitch, z, z_pitch, nat.ptr(root_value), None, None, None, drift.data_ptr(),
+                                              nat.ptr(tally), n, self._stream()), "gbl_reanalyse")
+        return drift, tally
+
+    def reanalyse(self, batch: dict, iterations: int = 64, explore: int = 16, census: bool = False, out: torch.Tensor | None = None) -> dict:
+        """This network's search run again on the rows of the dict ``BatchedGobblet.training_batch`` / ``ReplayBuffer.batch`` return, one
+        launch of ``gbl_reanalyse``: returns a copy of the dict whose "visits" are the new search's visit counts (``gbl_tree_search_eval``
+        with ``iterations`` and ``explore`` on the position each observation holds, under the row's mask; no noise, no solver guard) in a
+        fresh tensor -- or in ``out``, an int16 (N, 54) tensor; ``out=batch["visits"]`` is the in-place form.  "z" stays the game's
+        outcome; a failed sample (z = ``nat.Z_OPEN``) keeps its row, a row without a candidate gets zeros.  Adds "root_value" int32 (N,),
+        the root's q in 1/128 of a win for the mover, "drift" int32 (N,), the total variation between the old and the new visit shares
+        in 1/1024 (1024: the old row had nothing positive; -1: a skipped row or one without a candidate) and, with ``census``, "census"
+        int8 (N,) (include/gobblet_hip.h, "Reanalysis": bit 0 the old argmax is the new one, bit 1 the sign of the root's q equals z,
+        bit 2 there were no old visits; -1 where drift is)."""
+        if "observation" not in batch:
+            raise ValueError("reanalyse needs the 'observation' entry: a window or a buffer with observations")
+        obs, mask, visits, z = batch["observation"], batch.get("action_mask"), batch["visits"], batch["z"]
+        n = int(z.shape[0])
+        spec = (("observation", obs, (n, nat.OBS_BYTES), torch.int8), ("action_mask", mask, (n, nat.ACTIONS), torch.int8),
+                ("visits", visits, (n, nat.ACTIONS), torch.int16), ("z", z, (n,), torch.int8), ("out", out, (n, nat.ACTIONS), torch.int16))
+        for name, t, shape, dtype in spec:
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"reanalyse: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        if out is None:
+            out = visits.clone()  # (a skipped row keeps what it held)
+        value = torch.empty(n, dtype=torch.int32, device=self.device)
+        drift, tally = self._reanalyse(n, obs.data_ptr(), nat.OBS_BYTES, nat.ptr(mask), nat.ACTIONS, visits.data_ptr(), out.data_ptr(),
+                                       nat.ACTIONS, z.data_ptr(), 1, iterations, explore, census, value)
+        fresh = dict(batch, visits=out, root_value=value, drift=drift)
+        if census:
+            fresh["census"] = tally
+        return fresh
+
 
 class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
     _games_per_visit = 128  # (a network leaf counts as 128 games)

@@ -264,8 +264,37 @@ class ReplayBuffer(_OnDevice):
                            self._visits.data_ptr(), nat.REPLAY_VISITS_PITCH, self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH,
                            mode, count, census, None, allow_incomplete)
 
+    def reanalyse(self, evaluator, iterations: int = 64, explore: int = 16, census: bool = False, prioritize: dict | None = None) -> dict:
+        """Fresh search targets for the ring's live rows, in place: one launch of ``gbl_reanalyse`` over the ring's own arrays through
+        their pitches -- the visits of every live row become the visit counts of ``evaluator``'s search (``GobbletEvaluator.reanalyse``
+        has the rule) on the position the row's observation holds.  The live rows are ``relabel``'s: every slot once the ring has
+        wrapped and the first ``total`` slots before; z, mover bytes, tags, masks, observations and padding are not touched.  Returns
+        ``dict(drift=int32 (live rows,), census=int8 (live rows,) or None)`` in slot order.  ``prioritize=dict(floor=1, scale=1)`` (a
+        prioritised buffer): every live row's priority becomes ``floor + scale * max(drift, 0)`` on the device (``set_priority``'s
+        path), so rows whose targets moved furthest are drawn first.  Reads ``total`` from the device, nothing else."""
+        if self._obs is None:
+            raise ValueError("reanalyse needs a buffer with observations")
+        if torch.device(evaluator.device) != self.device:
+            raise ValueError("reanalyse: the evaluator lives on %s and the buffer on %s" % (evaluator.device, self.device))
+        if prioritize is not None:
+            self._need_priorities("reanalyse(prioritize=...)")
+            if set(prioritize) - {"floor", "scale"}:
+                raise ValueError("reanalyse: prioritize=dict(floor=1, scale=1)")
+            floor, scale = int(prioritize.get("floor", 1)), int(prioritize.get("scale", 1))
+            if floor < 0 or scale < 0 or floor + scale * 1024 >= 1 << 31:
+                raise ValueError("reanalyse: floor and scale must be >= 0 and floor + 1024 * scale must fit an int32")
+        live = self.size
+        drift, tally = evaluator._reanalyse(live, self._obs.data_ptr(), nat.REPLAY_OBS_PITCH, self._meta.data_ptr(), nat.REPLAY_META_PITCH,
+                                            self._visits.data_ptr(), self._visits.data_ptr(), nat.REPLAY_VISITS_PITCH,
+                                            self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH, iterations, explore, census)
+        if prioritize is not None and live:
+            slots = torch.arange(live, dtype=torch.int32, device=self.device)
+            self.set_priority(torch.stack([slots, torch.zeros_like(slots)], dim=1).contiguous(), floor + scale * drift.clamp(min=0))
+        return dict(drift=drift, census=tally)
+
     def fit(self, trainer, steps: int, batch: int = 1024, symmetries="all", first_call: int = 0, recent: int | None = None,
-            seed: int = 0, targets=None, prioritized: bool = False, beta=None, priority: dict | None = None) -> torch.Tensor:
+            seed: int = 0, targets=None, prioritized: bool = False, beta=None, priority: dict | None = None,
+            reanalyse: dict | None = None) -> torch.Tensor:
         """``steps`` Adam steps of ``trainer`` (a ``GobbletTrainer`` on this buffer's device): step i draws ``batch(batch, symmetries,
         call=first_call + i, recent=recent)`` into one reused buffer and hands it to ``trainer.step``; nothing crosses to the host.
         ``targets``: a ``Tablebase`` on this device -- every drawn batch goes through ``targets.targets`` first (one more launch per
@@ -276,11 +305,36 @@ class ReplayBuffer(_OnDevice):
         ``batch_weights(buf, beta)`` in the step.  ``priority``: ``dict(scale=, floor=1, cap=)`` -- after every step the drawn rows get
         ``trainer.last_priority`` (``set_priority``), so the next draw rebuilds the index from the trainer's own losses.  A full step
         is then nine launches on one stream, and the host reads nothing: index build 2, draw 1, weights 1, step 2, the trainer's
-        running maximum 1, priority update 2 (``targets`` adds its one, before the weights)."""
+        running maximum 1, priority update 2 (``targets`` adds its one, before the weights).
+        ``reanalyse``: ``dict(evaluator=, iterations=64, explore=16)`` with a ``GobbletEvaluator`` on this device -- every drawn batch goes
+        through ``evaluator.reanalyse`` first (one more launch per step, ``gbl_reanalyse``, in ``targets``' place: the two exclude each
+        other): the step learns from the visit counts of that network's search instead of the stored ones, z stays the game's outcome.
+        It composes with ``prioritized``, ``beta`` and ``priority``.  The drawn row is a symmetric image of the stored one, which is sound
+        because the search commutes with the symmetries -- with ``gbl_symmetry_apply``'s caveat: check_for_winner's last-line-decides
+        rule is not symmetric on boards where a move leaves lines of both colours, so under the squares' symmetries a search that
+        reaches such a board may differ from the image of the stored row's search (``symmetries=None`` avoids it)."""
         if torch.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the buffer on %s" % (trainer.device, self.device))
         if (beta is not None or priority is not None) and not prioritized:
             raise ValueError("fit: beta= and priority= need prioritized=True")
+        if reanalyse is not None:
+            if targets is not None:
+                raise ValueError("fit: targets= and reanalyse= exclude each other")
+            unknown = set(reanalyse) - {"evaluator", "iterations", "explore"}
+            if unknown or "evaluator" not in reanalyse:
+                raise ValueError("fit: reanalyse=dict(evaluator=, iterations=64, explore=16)")
+            if torch.device(reanalyse["evaluator"].device) != self.device:
+                raise ValueError("fit: the evaluator lives on %s and the buffer on %s" % (reanalyse["evaluator"].device, self.device))
+            fresh = torch.zeros((int(batch), nat.ACTIONS), dtype=torch.int16, device=self.device)  # (reused: a skipped row counts for nothing)
+
+            def relabelled(rows):
+                return reanalyse["evaluator"].reanalyse(rows, reanalyse.get("iterations", 64), reanalyse.get("explore", 16), out=fresh)
+        elif targets is not None:
+            def relabelled(rows):
+                return targets.targets(dict(rows))
+        else:
+            def relabelled(rows):
+                return rows
         buf, stats = None, []
         if beta is not None or priority is not None:
             steps = int(steps)
@@ -288,7 +342,7 @@ class ReplayBuffer(_OnDevice):
             weights = None
             for i in range(steps):
                 buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=True)
-                rows = buf if targets is None else targets.targets(dict(buf))
+                rows = relabelled(buf)
                 if beta is not None:
                     b = float(beta) if ends is None else ends[0] + (ends[1] - ends[0]) * (i / (steps - 1) if steps > 1 else 0.0)
                     weights = self.batch_weights(buf, b, out=weights)
@@ -298,7 +352,7 @@ class ReplayBuffer(_OnDevice):
             return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
         for i in range(int(steps)):
             buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=prioritized)
-            stats.append(trainer.step(buf if targets is None else targets.targets(dict(buf))))
+            stats.append(trainer.step(relabelled(buf)))
         return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
 
     def state_dict(self) -> dict:

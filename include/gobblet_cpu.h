@@ -201,6 +201,10 @@ int gbl_cpu_tb_targets(const int32_t *inventory, const void *aux, const int8_t *
                        int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
                        int8_t *z_out, int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out,
                        int64_t n, void *stream);
+int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                      int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                      int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
+                      int32_t *drift_out, int8_t *census_out, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

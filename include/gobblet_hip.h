@@ -1034,6 +1034,50 @@ int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *tabl
                    int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int8_t *z_out,
                    int64_t z_pitch, int mode, int count, int8_t *value_out, int8_t *outcome_out, int8_t *census_out, int64_t n, void *stream);
 
+/* Reanalysis (no counterpart in the reference): fresh search targets for stored rows -- the learned-network counterpart of the tablebase
+ * targets above.  The evaluator's search runs again on the position a row's observation holds, and the row's visits become that search's;
+ * rows in the shape gbl_training_batch and gbl_replay_batch write, or the replay ring's own rows in place.  One launch, no allocation, no
+ * atomics, nothing drawn: the same rows and the same network give the same bytes.  Integer-only, so the kernel, the host flavour and a
+ * restatement of this text agree byte for byte.
+ *   Rows.  As gbl_tb_targets: n rows, row r of each pitched array at base + r * pitch, pitches in ELEMENTS of the array's type: obs int8
+ *     (117 per row), mask int8 (54), visits_in / visits_out int16 (54, one pitch for both), z_in int8 (1).  A drawn batch has the pitches
+ *     117 / 54 / 54 / 1; the ring has ring_obs at GBL_REPLAY_OBS_PITCH, ring_meta (the mask) at GBL_REPLAY_META_PITCH, ring_visits at
+ *     GBL_REPLAY_VISITS_PITCH and z = ring_meta + GBL_REPLAY_META_Z at GBL_REPLAY_META_PITCH.  Bytes of a pitched row beyond its
+ *     117 / 54 / 54 / 1 elements are neither read nor written.
+ *   Skipped rows.  z_in is optional; a row whose z_in byte is GBL_Z_OPEN (the failed sample of both samplers) is skipped: no byte of
+ *     its visits_out row is written.  z is never written: the value target stays the game's outcome, and an int8 z cannot carry a
+ *     fractional root value.
+ *   The rule.  (state, to_move) = gbl_decode_obs of the row's 117 bytes; C = the row's mask bytes & the mover's legal mask (mask NULL:
+ *     the legal mask).  The search is gbl_tree_search_eval's text unchanged on that board with ev, iterations and explore and the
+ *     candidate set C: no root noise, no solver guard.  visits_out[a] = (int16) n_c of the root's child of action a, 0 for the other
+ *     actions (iterations <= 512 keeps it inside an int16).  A row with C empty gets 54 zeros, so that gbl_train_step counts it for
+ *     nothing.  visits_out may be NULL (the dense outputs alone).
+ *   Dense outputs (each optional, row r at r * 1 / 54 / 1 / 1 / 1 / 1): root_value_out int32[n], root_priors_out uint8[n][54],
+ *     action_out int32[n] and nodes_out int32[n] are gbl_tree_search_eval's (a row with C empty: the root's q, zeros, -1, 1); a skipped
+ *     row holds 0 / zeros / -1 / 0.
+ *     drift_out int32[n]: the total variation between the old and the new visit shares, in 1/1024.  With o_a = max(visits_in[a], 0),
+ *     So = sum of o_a, n_a = the new visits and Sn = sum of n_a:
+ *         drift = (1024 * sum over a of |o_a * Sn - n_a * So|) / (2 * So * Sn)      an unsigned 64-bit division (floor)
+ *     and drift = 1024 where So == 0 < Sn.  So <= 54 * 32767 and Sn <= 512, so every term, the sum (at most 2 So Sn < 2^32) and the
+ *     divisor fit 32 bits, and the product by 1024 fits 64.  drift = -1 for a skipped row, a row with C empty, or visits_in NULL.
+ *     census_out int8[n]: -1 for a skipped row or a row with C empty, otherwise bit 0: visits_in is given, the row's 54 old visits are
+ *     not all <= 0 and their argmax (the largest, the lowest index on ties) is the argmax of the new visits row by the same rule;
+ *     bit 1: z_in is given, z is -1, 0 or +1 and sign(the root's q) == z; bit 2: the old visits were all <= 0, or visits_in is NULL.
+ *   Aliasing.  visits_in == visits_out is the in-place form: a row is read completely before any of it is written.  Any other byte an
+ *     output shares with an input (obs, mask, visits_in, z_in, the evaluator's w1 / b1 / w2 / b2) is GBL_ERR_ARG.  Two arrays whose
+ *     extents intersect must have the same pitch in bytes (their rows interleave, as z and the mask do in ring_meta); with different
+ *     pitches intersecting extents count as an overlap.
+ *   Errors, in this order (GBL_ERR_ARG): the evaluator (NULL, hidden, the shifts), iterations (1 .. 512), explore (0 .. 1024), n < 0, a
+ *     pitch smaller than its row (obs; mask if given; visits if either is given; z if given); n == 0 returns GBL_OK here; then the
+ *     evaluator's four pointers, a missing obs, no output at all; then the overlaps.  GBL_ERR_ALIGN (device flavour only): the
+ *     evaluator's arrays 16-byte, visits_in / visits_out 2-byte, root_value_out / action_out / nodes_out / drift_out 4-byte; the byte
+ *     arrays need no alignment (a batch's observation rows are 117 bytes apart).
+ *   The tree lives in 72 (iterations + 1) bytes of LDS per workgroup, as gbl_tree_search_eval's. */
+int gbl_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                  int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int64_t z_pitch,
+                  int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out, int32_t *drift_out,
+                  int8_t *census_out, int64_t n, void *stream);
+
 /* Self-play with the tablebase (no counterpart in the reference): gbl_collect_search_noise with the exact table inside the launch, as a
  * third policy for either side and as a judge of every ply.  The arguments are gbl_collect_search_noise's, then
  *   inventory / aux / table   as gbl_tb_probe takes them (the table complete or not: a 0 reads "not proven by the sweeps done")
