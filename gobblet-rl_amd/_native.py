@@ -39,6 +39,7 @@ SOLVE_MAX_DEPTH, SOLVE_NONE = 6, -128  # gbl_solve
 HOW_PROVEN = 5  # gbl_collect_search_solve
 STREAM_NOISE, NOISE_MAX_WEIGHT = 6, 256  # gbl_tree_search_eval_noise / gbl_collect_search_noise
 POLICY_TABLEBASE, HOW_TABLE, HOW_TABLE_SAMPLED = 6, 6, 7  # gbl_collect_search_tb
+HOW_FAST, HOW_FAST_SAMPLED, STREAM_CAP, CAP_FULL_SHARE = 8, 9, 9, 256  # gbl_collect_search_cap
 SYMMETRIES, BATCH_ATTEMPTS = 512, 16  # gbl_symmetry_apply / gbl_training_batch
 REPLAY_OBS_PITCH, REPLAY_VISITS_PITCH, REPLAY_META_PITCH = 128, 64, 64  # gbl_replay_append / gbl_replay_batch: the ring's row pitches
 REPLAY_META_Z, REPLAY_META_MOVER, REPLAY_META_TAG, STREAM_REPLAY = 54, 55, 56, 7
@@ -101,6 +102,8 @@ SIGNATURES = {
                                  [_vp, _vp, _vp]),
     "gbl_collect_search_noise": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
                                  [_vp, _vp, _vp]),
+    "gbl_collect_search_cap": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
+                               [_vp, _vp] + [_int] * 4 + [_vp]),
     "gbl_collect_search_tb": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
                               [_vp, _vp] + [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp] + [_vp]),
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),

@@ -1001,6 +1001,8 @@ struct SelfplaySearch {
     bool judged, table;
     int tb_value, tb_action;
     int8_t tb_outcome[kActions];
+    // gbl_cpu_collect_search_cap: the ply is a fast one -- h holds the small search, whose visits row is not recorded
+    bool fast;
 };
 
 extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
@@ -1033,6 +1035,7 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
             S.proven = 0;
             S.solved = false;
             S.judged = S.table = false;
+            S.fast = false;
             const bool tree = search(p, who, legal, g, q, S);
             int action, how = GBL_HOW_RANDOM, value = 0;
             if (tree) {
@@ -1042,6 +1045,7 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
                                    : S.table ? S.tb_action : tree_action_of(h.best);
                 how = S.proven ? GBL_HOW_PROVEN
                       : S.table ? (sampled ? GBL_HOW_TABLE_SAMPLED : GBL_HOW_TABLE)
+                      : S.fast  ? (sampled ? GBL_HOW_FAST_SAMPLED : GBL_HOW_FAST)
                                 : sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
                 for (int a = 0; a < kActions; ++a) value += h.wins[a] - h.losses[a];
             } else {
@@ -1064,7 +1068,7 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
             if (T.done) T.done[at] = (int8_t)dn;
             if (T.to_move) T.to_move[at] = (int8_t)mover;
             if (T.visits)
-                for (int a = 0; a < kActions; ++a) T.visits[at * kActions + a] = (int16_t)(tree ? h.visits[a] : 0);
+                for (int a = 0; a < kActions; ++a) T.visits[at * kActions + a] = (int16_t)(tree && !S.fast ? h.visits[a] : 0);
             if (T.value) T.value[at] = value;
             if (T.nodes) T.nodes[at] = tree ? (int32_t)h.count : 0;
             if (T.how) T.how[at] = (int8_t)how;
@@ -1169,8 +1173,11 @@ static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
                 cand = 0;
                 for (int a = 0; a < kActions; ++a) cand |= (uint64_t)(S.outcome[a] == 0) << a;
             }
-            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, its, (uint32_t)c.explore, S.h,
-                                             HostNoise{(uint32_t)c.noise[who], c.seed, g, q, root_pi});
+            // (the playout cap's draw, after the guard: a proven ply takes none)
+            const CapPly cp = cap_ply(c.seed, g, q, (uint32_t)selfplay_share(c, who), its, (uint32_t)c.fast[who], (uint32_t)c.noise[who]);
+            S.fast = cp.fast;
+            S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, cp.its, (uint32_t)c.explore, S.h,
+                                             HostNoise{cp.noise, c.seed, g, q, root_pi});
             S.priors = root_pi;  // (the network's row; zeros where the root has no candidate)
             return true;
         });
@@ -1242,6 +1249,24 @@ int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, i
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
                             counters, turn, nullptr, nullptr, nullptr, 0, 0});
+}
+
+int gbl_cpu_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                               int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                               int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                               int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                               const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                               const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1,
+                               int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
+                               int fast_iterations0, int fast_iterations1, int full_share0, int full_share1, void *)
+{
+    return host_selfplay_run({kRunSolve, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0, 1, {fast_iterations0, fast_iterations1}, {full_share0, full_share1}});
 }
 
 int gbl_cpu_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,

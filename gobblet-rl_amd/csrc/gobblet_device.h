@@ -2190,6 +2190,38 @@ __device__ __forceinline__ void noise_priors(uint64_t seed, uint64_t g, uint32_t
 
 inline const char *noise_error(int noise) { return noise < 0 || noise > kNoiseMaxWeight ? "the noise weight must be in [0, 256]" : nullptr; }
 
+// ---- playout cap (include/gobblet_hip.h, gbl_collect_search_cap): one statement for the kernel and the host flavour -----------------
+// Ply q of board g is FULL iff the top byte of its word on the cap's own stream lies below the mover's share (in 1/256); a full ply
+// searches with the side's budget and noise weight, a fast one with the fast budget and weight 0 (no noise: nothing of it is drawn).
+// A share of 256 draws nothing.  Every argument is the same in all lanes of a board's wavefront, and so is the result.
+constexpr uint32_t kStreamCap = 9u;  // generator stream of the playout cap's draw
+constexpr int kCapFullShare = 256;
+constexpr int kHowFast = 8, kHowFastSampled = 9;  // GBL_HOW_FAST / GBL_HOW_FAST_SAMPLED
+
+struct CapPly {
+    bool fast;
+    uint32_t its, noise;
+};
+
+__device__ __forceinline__ bool cap_full(uint64_t seed, uint64_t g, uint32_t q, uint32_t share)
+{
+    return share >= (uint32_t)kCapFullShare || (draw32(seed, g, q, kStreamCap) >> 24) < share;
+}
+
+__device__ __forceinline__ CapPly cap_ply(uint64_t seed, uint64_t g, uint32_t q, uint32_t share, uint32_t iterations, uint32_t fast_iterations,
+                                          uint32_t noise)
+{
+    const bool full = cap_full(seed, g, q, share);
+    return CapPly{!full, full ? iterations : fast_iterations, full ? noise : 0u};
+}
+
+// a side's share and fast budget, where they are read (an EVAL_TREE side; the budget where the share is below 256)
+inline const char *cap_share_error(int share) { return share < 0 || share > kCapFullShare ? "full_share0 / full_share1 must be in [0, 256]" : nullptr; }
+inline const char *cap_fast_error(int fast_iterations, int iterations)
+{
+    return fast_iterations < 1 || fast_iterations > iterations ? "fast_iterations0 / fast_iterations1 must be in [1, iterations]" : nullptr;
+}
+
 // The selection key of candidate a with prior pi under a node of nv visits: the mean of its child (tree_key's first term; 32768
 // without a child, n = 0) plus ((explore pi isqrt(nv << 8)) >> 5) / (1 + n).  nv <= 512: the root of the isqrt stays below 2^24,
 // the product below 1024 * 255 * 363 < 2^27.
@@ -2523,7 +2555,17 @@ struct SelfplayCall {
     const void *aux;
     const int8_t *table;
     int tb_mode, tb_count;
+    // gbl_collect_search_cap's own (cap = 0 elsewhere: neither array is read)
+    int cap;
+    int fast[2], share[2];
 };
+
+// the share of full plies that side m's plies are drawn against: 256 (nothing is drawn) without a cap or for a side that does not search
+template <typename Ev>
+inline int selfplay_share(const SelfplayCall<Ev> &c, int m)
+{
+    return c.cap && c.policy[m] == kPolicyEvalTree ? c.share[m] : kCapFullShare;
+}
 
 // (the tablebase entry points' look at an inventory: "Exact tablebase" below)
 inline const char *tb_inventory_error(const int32_t *inventory)
@@ -2565,7 +2607,7 @@ inline const char *collect_tb_error(const SelfplayCall<Ev> &c)
 }
 
 // Everything both flavours look at, in the order they report it: n < 0, the entry point's *_error, the searching sides' noise
-// weights, n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
+// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
 // per searching side `side(m)` -- the flavour's own look at evaluator m
 // (its pointers; on the device their alignment too), which returns 0 or what its fail() returned.  Returns a flavour's error
 // code (< 0; fail(message) makes a GBL_ERR_ARG of a message), 0 where there is nothing to do (GBL_OK), or 1: the flavour goes on
@@ -2586,6 +2628,14 @@ inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, 
     if (why) return fail(why);
     if (!uct && ((c.policy[0] == searching && noise_error(c.noise[0])) || (c.policy[1] == searching && noise_error(c.noise[1]))))
         return fail("noise0 / noise1 must be in [0, 256]");
+    if (c.cap) {  // gbl_collect_search_cap: the searching sides' shares, then the fast budgets that are read
+        for (int m = 0; m < 2; ++m)
+            if (c.policy[m] == searching)
+                if (const char *bad = cap_share_error(c.share[m])) return fail(bad);
+        for (int m = 0; m < 2; ++m)
+            if (c.policy[m] == searching && c.share[m] < kCapFullShare)
+                if (const char *bad = cap_fast_error(c.fast[m], c.iterations[m])) return fail(bad);
+    }
     if (c.n == 0) return 0;
     if (!c.state) return fail("state must not be NULL");
     if (!c.to_move) return fail("to_move must not be NULL");

@@ -3573,7 +3573,10 @@ __global__ __launch_bounds__(64) void k_solve(const int8_t *__restrict__ state, 
 // solver's LDS stands beside the tree's, and its fences are wave_lds_fence: the ply's trajectory stores stay in flight over the
 // next decision.  The solver's registers are dead before the tree's come alive.  The outcome byte of every lane and V go out
 // from the second lambda, beside the root's q and the prior byte.
-template <bool NOISE>
+// CAP (gbl_collect_search_cap): the ply that goes on to search first takes its budget and noise weight from cap_ply -- one generator
+// word of the board's own stream, wave-uniform, so a budget that differs between plies and boards costs no divergence -- and a fast
+// ply leaves a zero visits row and its own `how` codes.  CAP = false compiles all of it out: the kernels without it are the code they were.
+template <bool NOISE, bool CAP>
 __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                       uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
                                                       int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
@@ -3582,7 +3585,8 @@ __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state
                                                       const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
                                                       uint32_t iterations1, int solve_depth0, int solve_depth1, uint32_t most, uint32_t explore,
                                                       int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
-                                                      int32_t *__restrict__ turn, uint32_t noise0, uint32_t noise1)
+                                                      int32_t *__restrict__ turn, uint32_t noise0, uint32_t noise1, uint32_t fast0,
+                                                      uint32_t fast1, uint32_t share0, uint32_t share1)
 {
     extern __shared__ uint4 s_tree[];
     TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
@@ -3612,12 +3616,21 @@ __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state
                 }
                 cand = (uint64_t)__ballot(my_c == 0);
             }
+            CapPly cp{false, its, who ? noise1 : noise0};
+            if (CAP) {  // the ply's budget and weight, after the guard: one generator word, the same in every lane
+                cp = cap_ply(seed, g, q, who ? share1 : share0, its, who ? fast1 : fast0, cp.noise);
+                cp = CapPly{uniform((int)cp.fast) != 0, (uint32_t)uniform((int)cp.its), (uint32_t)uniform((int)cp.noise)};
+            }
             uint32_t mixed;  // (the root's own row; the trajectory keeps the network's)
-            const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its, explore,
-                                                                 lane, S.count, RootNoise{who ? noise1 : noise0, seed, g, q}, mixed);
+            const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, cp.its,
+                                                                 explore, lane, S.count, RootNoise{cp.noise, seed, g, q}, mixed);
             S.pi = at_root.pi;
             S.root_q = at_root.q;
             S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+            if (CAP && cp.fast) {  // (kHowSearch -> kHowFast, kHowSearchSampled -> kHowFastSampled; no policy target)
+                S.d.how += kHowFast - kHowSearch;
+                S.d.my_n = 0u;
+            }
             wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
             return true;
         },
@@ -5289,16 +5302,23 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     } else {
         const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
                        w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
-        // (k_collect_solve<false> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked)
-#define GBL_CSV(NOISE)                                                                                                                    \
-    hipLaunchKernelGGL(k_collect_solve<NOISE>, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,       \
+        const uint32_t sh0 = (uint32_t)selfplay_share(c, 0), sh1 = (uint32_t)selfplay_share(c, 1);
+        // (k_collect_solve<false, ...> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked; and
+        // <..., false> the one without the cap's: both shares 256 run it)
+#define GBL_CSV(NOISE, CAP)                                                                                                               \
+    hipLaunchKernelGGL((k_collect_solve<NOISE, CAP>), grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, \
                        c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1],       \
                        c.policy[0], c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies,    \
-                       c.illegal_mode, c.counters, c.turn, w0, w1)
-        if (w0 | w1)
-            GBL_CSV(true);
+                       c.illegal_mode, c.counters, c.turn, w0, w1, (uint32_t)c.fast[0], (uint32_t)c.fast[1], sh0, sh1)
+        const bool cap = sh0 < (uint32_t)kCapFullShare || sh1 < (uint32_t)kCapFullShare;
+        if (cap && (w0 | w1))
+            GBL_CSV(true, true);
+        else if (cap)
+            GBL_CSV(false, true);
+        else if (w0 | w1)
+            GBL_CSV(true, false);
         else
-            GBL_CSV(false);
+            GBL_CSV(false, false);
 #undef GBL_CSV
     }
     GBL_LAUNCHED(name);
@@ -5374,6 +5394,26 @@ int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
                             counters, turn, nullptr, nullptr, nullptr, 0, 0},
+                           stream);
+}
+
+int gbl_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                           int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                           int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                           uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
+                           int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
+                           int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                           int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
+                           int64_t *counters, int32_t *turn, int fast_iterations0, int fast_iterations1, int full_share0,
+                           int full_share1, void *stream)
+{
+    return selfplay_launch("gbl_collect_search_cap",
+                           {kRunSolve, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                           nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0, 1, {fast_iterations0, fast_iterations1}, {full_share0, full_share1}},
                            stream);
 }
 

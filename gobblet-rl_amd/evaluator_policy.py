@@ -295,3 +295,26 @@ def root_noise(seed: int, board_ids, ply, candidates) -> torch.Tensor:
     e = torch.where(cand, e, torch.zeros_like(e))
     nu = 1 + (e * 254) // e.sum(1, keepdim=True).clamp(min=1)
     return torch.where(cand, nu, torch.zeros_like(nu)).to(torch.uint8)
+
+
+# ---- the playout cap's draw restated in torch (include/gobblet_hip.h, gbl_collect_search_cap): a convenience, not a kernel ----------
+def cap_share(full) -> int:
+    """The ABI's share 0 .. 256 of full plies for a share in [0, 1]."""
+    if not 0.0 <= float(full) <= 1.0:
+        raise ValueError("cap: full must be in [0, 1]")
+    return int(round(256.0 * float(full)))
+
+
+def cap_full(seed: int, board_ids, ply_indices, full) -> torch.Tensor:
+    """bool: which plies of ``gbl_collect_search_cap`` are FULL for a side whose share of full plies is ``full`` (in [0, 1], as
+    ``collect(search=dict(cap=dict(full=...)))`` takes it).  ``board_ids`` (= env_base + b) and ``ply_indices`` broadcast against
+    each other: ``cap_full(seed, ids[None, :], plies[:, None], 0.25)`` has a time-major trajectory's shape.  The draw alone: a ply
+    of a side that does not search, and a ply the solver proves, takes none.  On the device of ``board_ids``."""
+    share = cap_share(full)
+    g = torch.as_tensor(board_ids)
+    dev = g.device
+    g, q = torch.broadcast_tensors(g.to(torch.int64), torch.as_tensor(ply_indices, device=dev).to(torch.int64))
+    zero = torch.zeros_like(g)
+    words = _philox4x32_10([g & _M32, g >> 32, q >> 2, zero + nat.STREAM_CAP], int(seed) & _M32, (int(seed) >> 32) & _M32)
+    r = torch.stack(words, dim=-1).gather(-1, (q & 3)[..., None])[..., 0]
+    return (r >> 24) < share

@@ -278,7 +278,8 @@ class BatchedGobblet:
 
         search_outputs: also "visits" (int16 (..., 54)), "value" / "nodes" (int32), "how" and "mover" (int8) for
         ``collect(policies=(... "tree" ...), search=...)``: the root visit counts, value sum and node count of the search that
-        chose every ply's action, how it was arrived at (0 random, 3 the search's decision, 4 drawn in proportion to the visits)
+        chose every ply's action, how it was arrived at (0 random, 3 the search's decision, 4 drawn in proportion to the visits;
+        with ``search=dict(cap=...)`` 8 a fast ply's decision and 9 its draw, ``nat.HOW_FAST`` / ``nat.HOW_FAST_SAMPLED``: no visits row)
         and who played it.
 
         policy_outputs: also "chosen" (int32) and "how" (int8: 0 random ply, 1 greedy choice, 2 greedy fallback draw) for
@@ -455,6 +456,14 @@ class BatchedGobblet:
         (``gbl_collect_search_noise``): the exploration of self-play.  An arena passes no noise, or noises one side only.  "priors"
         stays the network's row; ``root_noise`` recomputes the random one.
 
+        ``search=dict(..., cap=dict(fast_iterations=16, full=0.25))`` (either value may be a pair, one per side; ``full`` a share in
+        [0, 1]) is playout-cap randomisation of an evaluator side (``gbl_collect_search_cap``): a ply is FULL with probability
+        ``full`` -- the search above, a policy target -- and FAST otherwise: ``fast_iterations`` iterations without noise pick the
+        move, "how" = ``nat.HOW_FAST`` / ``nat.HOW_FAST_SAMPLED``, and the visits row is ZERO, so that ``training_batch`` and the
+        replay buffer drop the ply as they drop a "random" one, while its game's result still labels the full plies.  A ply the
+        solver proves stays ``nat.HOW_PROVEN`` whatever the draw; ``cap_full`` recomputes the draws.  An absent ``cap``, or
+        ``full=1``, keeps the entry points above.  Not with a "tablebase" side or ``judge=True``.
+
         A side "tablebase" (or a ``TablebaseGobbletPolicy`` instance, which supplies its table) plays from the exact table INSIDE the
         launch (``gbl_collect_search_tb``), against "tablebase", "evaluator" or "random": ``search=dict(..., tablebase=tb,
         tb_mode="result" | "shortest", tb_count=1, judge=False, allow_incomplete=False)``.  Its ply takes the probe's action
@@ -516,9 +525,11 @@ class BatchedGobblet:
                 raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
             # one argument list for the four self-play entry points: any noise weight -> _noise (the guarded kernel, whatever the
             # depths), else any solve depth -> _solve, else an evaluator side -> _eval, else the UCT search
-            # a table side or the judge -> _tb (the noise entry point's list, then the table's)
-            entry = "gbl_collect_search" + ("_tb" if tp is not None else "" if ep is None else "_noise" if any(ep["noise"]) else
-                                            "_solve" if guarded else "_eval")
+            # a table side or the judge -> _tb (the noise entry point's list, then the table's); a playout cap -> _cap (that list,
+            # then the cap's)
+            cap = None if ep is None else ep.get("cap")
+            entry = "gbl_collect_search" + ("_tb" if tp is not None else "" if ep is None else "_cap" if cap is not None else
+                                            "_noise" if any(ep["noise"]) else "_solve" if guarded else "_eval")
             if judged and "tb_value" not in f:
                 raise ValueError("judge=True needs buffers from trajectory_buffers(tablebase_outputs=True)")
             args = [self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
@@ -528,7 +539,7 @@ class BatchedGobblet:
             if ep is None:
                 sides = [*sp["iterations"], *sp["playouts"], sp["max_plies"]]
             else:
-                solver, noise = not entry.endswith("_eval"), entry.endswith(("_noise", "_tb"))
+                solver, noise = not entry.endswith("_eval"), entry.endswith(("_noise", "_tb", "_cap"))
                 structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
                 args += [nat.ptr(f.get(k)) for k in ("root_value", "priors") + (("outcomes", "proven") if solver else ())]
                 sides = [*[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
@@ -539,6 +550,7 @@ class BatchedGobblet:
                 self._counters.data_ptr() if count else None, nat.ptr(self.turn),
                 *(() if tp is None else (tp["inventory"], tp["aux"], tp["table"], tp["mode"], tp["count"],
                                          *(nat.ptr(f.get(k)) if judged else None for k in ("tb_outcomes", "tb_value", "tb_played")))),
+                *(() if cap is None or tp is not None else (*cap["fast_iterations"], *cap["share"])),
                 self._stream()), entry)
         elif policies is not None:
             try:
@@ -651,9 +663,9 @@ class BatchedGobblet:
         if len(sides) != 2 or not any(evs):
             return None
         from .evaluator_policy import noise_weight
-        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0, noise=0.0),  # EvaluatorTreeSearchGobbletPolicy's defaults
+        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0, noise=0.0, cap=None),  # EvaluatorTreeSearchGobbletPolicy's defaults
                              search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies / "
-                             "solve_depth / noise)")
+                             "solve_depth / noise / cap)")
         its, nets, deps, nzs = self._pair(kw["iterations"]), self._pair(kw["evaluator"]), self._pair(kw["solve_depth"]), self._pair(kw["noise"])
         if len(its) != 2 or len(nets) != 2 or len(deps) != 2 or len(nzs) != 2:
             raise ValueError("search: iterations / evaluator / solve_depth / noise are a value or a pair, one per side")
@@ -700,7 +712,32 @@ class BatchedGobblet:
         if not (0 <= explore <= 1024 and int(kw["sample_plies"]) >= 0):
             raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
         return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
-                    solve_depth=deps, noise=nzs)
+                    solve_depth=deps, noise=nzs, cap=self._cap_params(kw["cap"], codes, its))
+
+    def _cap_params(self, cap, codes, its):
+        """``search=dict(cap=dict(fast_iterations=, full=))`` as ``gbl_collect_search_cap`` takes it -- a fast budget and a share
+        0 .. 256 per side -- or None where no evaluator side is capped (an absent ``cap``, ``full=1``): the call keeps its entry point."""
+        from .evaluator_policy import cap_share
+        if cap is None:
+            return None
+        if not isinstance(cap, dict) or set(cap) - {"fast_iterations", "full"}:
+            raise ValueError("search: cap is a dict of fast_iterations / full")
+        fast, full = self._pair(cap.get("fast_iterations", 16)), self._pair(cap.get("full", 0.25))
+        if len(fast) != 2 or len(full) != 2:
+            raise ValueError("search: cap's fast_iterations / full are a value or a pair, one per side")
+        shares = [cap_share(x) for x in full]
+        for m in range(2):
+            if codes[m] != nat.POLICY_EVAL_TREE:
+                fast[m], shares[m] = 0, nat.CAP_FULL_SHARE
+            elif shares[m] < nat.CAP_FULL_SHARE:
+                fast[m] = int(fast[m])
+                if not 1 <= fast[m] <= its[m]:
+                    raise ValueError("search: cap's fast_iterations must be in [1, iterations]")
+            else:
+                fast[m] = 0
+        if all(x == nat.CAP_FULL_SHARE for x in shares):
+            return None
+        return dict(fast_iterations=fast, share=shares)
 
     def _tablebase_params(self, policies, search):
         """The table's arguments of ``gbl_collect_search_tb`` and, under "ep", the rest of the call as ``_evaluator_params`` returns it
@@ -738,18 +775,20 @@ class BatchedGobblet:
             raise ValueError("search: tb_mode is 'result' or 'shortest'")
         if not 1 <= int(kw["tb_count"]) <= nat.TB_TARGET_MAX_COUNT:
             raise ValueError("search: tb_count must be in [1, %d]" % nat.TB_TARGET_MAX_COUNT)
+        if rest.get("cap") is not None:
+            raise ValueError("search: cap does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no playout cap)")
         others = ["random" if t else x for t, x in zip(tbs, sides)]
         ep = self._evaluator_params(others, rest or None)
         if ep is None:  # no evaluator side: the table against itself or against "random"
             if not all(self._is_random(x) for x in others):
                 raise ValueError("policies: the table plays against 'tablebase', 'evaluator' or 'random' inside one launch (not %r)" % (sides,))
-            unknown = set(rest) - {"sample_plies", "evaluator", "iterations", "explore", "solve_depth", "noise"}
+            unknown = set(rest) - {"sample_plies", "evaluator", "iterations", "explore", "solve_depth", "noise", "cap"}
             if unknown:
                 raise ValueError("search: unknown keys %s" % sorted(unknown))
             if int(rest.get("sample_plies", 0)) < 0:
                 raise ValueError("search: sample_plies >= 0")
             ep = dict(policies=[nat.POLICY_RANDOM] * 2, evaluators=[None, None], iterations=[0, 0], explore=16,
-                      sample_plies=int(rest.get("sample_plies", 0)), solve_depth=[0, 0], noise=[0, 0])
+                      sample_plies=int(rest.get("sample_plies", 0)), solve_depth=[0, 0], noise=[0, 0], cap=None)
         ep["policies"] = [nat.POLICY_TABLEBASE if t else c for t, c in zip(tbs, ep["policies"])]
         return dict(ep=ep, judge=judge, tb=tb, inventory=tb._inv, aux=tb._aux.data_ptr(), table=tb.table.data_ptr(),
                     mode=nat.TB_TARGET_MODES[kw["tb_mode"]], count=int(kw["tb_count"]))

@@ -644,6 +644,43 @@ int gbl_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32
                              const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int noise0,
                              int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream);
 
+/* Self-play with playout-cap randomisation (no counterpart in the reference): gbl_collect_search_noise with a random share of an
+ * EVAL_TREE side's plies searched in full and the rest played from a small search that leaves no policy target.
+ *   full_share0 / full_share1          the share of full plies of player_1 / player_2, in 0 .. 256, in 1/256: 256 = every ply is full,
+ *                                      0 = every ply is fast
+ *   fast_iterations0 / fast_iterations1  the budget of a fast ply, 1 <= fast_iterations_m <= iterations_m (the LDS tree stays sized
+ *                                      by iterations)
+ * Both are read only for an EVAL_TREE side, and fast_iterations_m only where full_share_m < 256.  The rule is
+ * gbl_collect_search_noise's text with one addition, for ply q of an EVAL_TREE mover m with full_share_m < 256 on board
+ * g = env_base + b:
+ *   draw      r = the generator word of (seed, g, ply index q, stream 9) -- gbl_sample's generator: counter (g_lo, g_hi, q >> 2, 9),
+ *             word q & 3; stream 9 is the cap's own.  The ply is FULL iff (r >> 24) < full_share_m.  The draw moves with *ply_dev as
+ *             every other draw of the window does.
+ *   full ply  exactly gbl_collect_search_noise's ply.
+ *   fast ply  the solver guard runs as before; a proven root is gbl_collect_search_solve's proven ply, unchanged (GBL_HOW_PROVEN, the
+ *             one-hot row at iterations_m, nothing drawn).  Otherwise the search is exactly gbl_tree_search_eval(state, to_move,
+ *             mask = C, ev_m, fast_iterations_m, explore) -- no noise -- with C the legal mask, or the actions of outcome 0 under a
+ *             guard.  The action is its action_out or, while turn[b] < sample_plies, the visit-proportional draw on stream 4 over that
+ *             search's visits.  how = GBL_HOW_FAST or GBL_HOW_FAST_SAMPLED; the visits row holds 54 ZEROS (gbl_training_batch,
+ *             gbl_replay_append and gbl_train_step drop the cell: a fast ply is no policy target); value, nodes, root_value and
+ *             priors are what that search wrote; outcome / proven as on a full ply.
+ *   a root without a candidate behaves as before.
+ * With both shares 256 every array is gbl_collect_search_noise's, bit for bit.  A board's window depends on (seed, g, the ply
+ * indices) alone, not on the batch or the shard.  Errors are gbl_collect_search_noise's in its order; after its noise check comes
+ * GBL_ERR_ARG for a share outside 0 .. 256 on an EVAL_TREE side, then for a fast_iterations outside 1 .. iterations_m where it is
+ * read.  gbl_outcome_targets, gbl_training_batch and gbl_replay_append work on these trajectories unchanged.  Allocates nothing. */
+#define GBL_HOW_FAST 8
+#define GBL_HOW_FAST_SAMPLED 9
+int gbl_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                           int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                           int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                           int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                           int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                           const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                           const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int noise0,
+                           int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
+                           int fast_iterations0, int fast_iterations1, int full_share0, int full_share1, void *stream);
+
 /* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
  * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:
  *   z_traj          int8 [cells]  reward_traj[cell(e, b)][mover_traj[cell(t, b)]] -- the reward, not the winner, so that
