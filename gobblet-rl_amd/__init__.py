@@ -28,7 +28,7 @@ from .vector_env import BatchedGobblet  # noqa: F401
 from .greedy_policy import GreedyGobbletPolicy  # noqa: F401
 from .playout_policy import MonteCarloGobbletPolicy  # noqa: F401
 from .tree_policy import TreeSearchGobbletPolicy  # noqa: F401
-from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator, cap_full, root_noise  # noqa: F401
+from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator, cap_full, gumbel_row, root_noise  # noqa: F401
 from .solver_policy import SolverGobbletPolicy  # noqa: F401
 from .trainer import GobbletTrainer  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401

@@ -40,6 +40,7 @@ HOW_PROVEN = 5  # gbl_collect_search_solve
 STREAM_NOISE, NOISE_MAX_WEIGHT = 6, 256  # gbl_tree_search_eval_noise / gbl_collect_search_noise
 POLICY_TABLEBASE, HOW_TABLE, HOW_TABLE_SAMPLED = 6, 6, 7  # gbl_collect_search_tb
 HOW_FAST, HOW_FAST_SAMPLED, STREAM_CAP, CAP_FULL_SHARE = 8, 9, 9, 256  # gbl_collect_search_cap
+HOW_GUMBEL, STREAM_GUMBEL = 10, 10  # gbl_tree_search_gumbel / gbl_collect_search_gumbel
 SYMMETRIES, BATCH_ATTEMPTS = 512, 16  # gbl_symmetry_apply / gbl_training_batch
 REPLAY_OBS_PITCH, REPLAY_VISITS_PITCH, REPLAY_META_PITCH = 128, 64, 64  # gbl_replay_append / gbl_replay_batch: the ring's row pitches
 REPLAY_META_Z, REPLAY_META_MOVER, REPLAY_META_TAG, STREAM_REPLAY = 54, 55, 56, 7
@@ -87,6 +88,7 @@ SIGNATURES = {
     "gbl_evaluate": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_tree_search_eval": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gbl_tree_search_eval_noise": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _u64, _u64, _u32] + [_vp] * 8 + [_i64, _vp]),
+    "gbl_tree_search_gumbel": (_int, [_vp, _vp, _vp, _vp] + [_int] * 6 + [_u64, _u64, _u32] + [_vp] * 9 + [_i64, _vp]),
     "gbl_solve": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp]),
     "gbl_counter_add": (_int, [_vp, _u32, _vp]),
     "gbl_collect": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32,
@@ -104,6 +106,8 @@ SIGNATURES = {
                                  [_vp, _vp, _vp]),
     "gbl_collect_search_cap": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
                                [_vp, _vp] + [_int] * 4 + [_vp]),
+    "gbl_collect_search_gumbel": (_int, [_vp] * 17 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 5 +
+                                  [_vp, _vp] + [_int] * 5 + [_vp]),
     "gbl_collect_search_tb": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
                               [_vp, _vp] + [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp] + [_vp]),
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
@@ -254,7 +258,7 @@ def current_stream(device):
 # A flavour the caller ASKS for (device="cpu": BASELINE config 1 "on CPU", bench.py's CPU twin), never a fallback of the HIP
 # path: a "cuda" device without the HIP library still raises.  Built with g++ from the same device header.
 CPU_LIB_PATH = os.path.join(CSRC, "libgobblet_cpu.so")
-CPU_SOURCES = [os.path.join(CSRC, "gobblet_cpu.cpp"), os.path.join(CSRC, "gobblet_device.h"),
+CPU_SOURCES = [os.path.join(CSRC, "gobblet_cpu.cpp"), os.path.join(CSRC, "gobblet_device.h"), os.path.join(CSRC, "gobblet_knobs.h"),
                os.path.join(_HERE, "..", "include", "gobblet_cpu.h"), os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
 # -ffp-contract=off: gbl_cpu_train_step's float rule is single IEEE operations (include/gobblet_hip.h); everything else here is integer code
 CPU_CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"] + \

@@ -835,18 +835,32 @@ struct HostNoise {  // the root noise of one search (w == 0: none); root_pi: whe
     uint8_t *root_pi;
 };
 
+// The Gumbel root rule of one search (G.considered == 0: none, the root selects by its keys): in, the rule's arguments and the
+// generator's (seed, g, q); out, the decision, the target row and the g row (zeros outside the candidates).
+struct HostGumbel {
+    GumbelArgs G;
+    uint64_t seed, g;
+    uint32_t q;
+    int action;
+    uint8_t target[kActions];
+    int16_t gum[kActions];
+};
+
 static int32_t host_tree_search_eval(std::vector<TreeNode> &nodes, std::vector<uint8_t> &pri, const EvalNet &net, const Planes &root,
                                      int mover, uint64_t cand, uint32_t iterations, uint32_t explore, HostSearch &out,
-                                     const HostNoise &noise = HostNoise{})
+                                     const HostNoise &noise = HostNoise{}, HostGumbel *gumbel = nullptr)
 {
     int32_t o[kEvalOutputs];
     nodes[0] = TreeNode{};
     const int32_t root_q = host_evaluate(net, root, mover, cand, pri.data(), o);
     if (noise.root_pi) memcpy(noise.root_pi, pri.data(), kActions);
     if (noise.w && cand) noise_priors(noise.seed, noise.g, noise.q, noise.w, cand, pri.data(), pri.data());
+    GumbelRoot R;
+    const bool rule = gumbel && gumbel->G.considered && cand;
+    if (rule) gumbel_root_init(R, gumbel->G, iterations, gumbel->seed, gumbel->g, gumbel->q, cand, o, net.shift_p, root_q);
     uint32_t count = 1;
     for (uint32_t i = 0; cand && i < iterations; ++i) {
-        TreeEvalLeaf s = tree_eval_select(nodes.data(), pri.data(), root, mover, cand, explore);
+        TreeEvalLeaf s = tree_eval_select(nodes.data(), pri.data(), root, mover, cand, explore, rule ? gumbel_root_select(R, nodes.data()) : -1);
         uint32_t term = tree_term(nodes[s.node]);
         if (s.expand) {
             term = tree_move_into(s.p, s.side, s.a);
@@ -860,6 +874,15 @@ static int32_t host_tree_search_eval(std::vector<TreeNode> &nodes, std::vector<u
     }
     host_root_out(nodes, count, out);
     out.plies = 0;
+    if (gumbel) {
+        gumbel->action = -1;
+        memset(gumbel->target, 0, sizeof gumbel->target);
+        memset(gumbel->gum, 0, sizeof gumbel->gum);
+        if (rule) {
+            gumbel->action = gumbel_root_finish(R, nodes.data(), gumbel->target);
+            for (int a = 0; a < kActions; ++a) gumbel->gum[a] = (int16_t)R.gum[a];
+        }
+    }
     return root_q;
 }
 
@@ -904,6 +927,38 @@ int gbl_cpu_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, c
     if (const char *why = tree_search_noise_error(noise, call, env_base, n)) return fail(GBL_ERR_ARG, why);
     return host_tree_search_eval_run(state, to_move, mask, ev, iterations, explore, noise, seed, env_base, call, visits_out, wins_out,
                                      losses_out, action_out, nodes_out, root_value_out, root_priors_out, root_mixed_out, n);
+}
+
+int gbl_cpu_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                               int explore, int considered, int gumbel_noise, int visit_offset, int scale, uint64_t seed,
+                               uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out,
+                               int32_t *action_out, int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out,
+                               uint8_t *target_out, int16_t *gumbel_out, int64_t n, void *)
+{
+    if (const char *why = tree_search_gumbel_error(ev, iterations, explore, considered, gumbel_noise, visit_offset, scale, call, env_base, n,
+                                                   state, to_move))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    const EvalNet net = eval_net(ev);
+    const GumbelArgs G{(uint32_t)considered, (uint32_t)gumbel_noise, (uint32_t)visit_offset, (uint32_t)scale};
+    parallel_for(n, [=](int64_t b0, int64_t b1) {  // (a board is a whole search: every board is worth a thread)
+        std::vector<TreeNode> nodes((size_t)iterations + 1);
+        std::vector<uint8_t> pri(((size_t)iterations + 1) * kEvalOutputs);
+        HostSearch h;
+        HostGumbel gb{G, seed, 0, call, -1, {}, {}};
+        for (int64_t b = b0; b < b1; ++b) {
+            const HostRoot R = host_root(state, to_move, mask, b);
+            gb.g = env_base + (uint64_t)b;
+            const int32_t q = host_tree_search_eval(nodes, pri, net, R.p, R.mover, R.cand, (uint32_t)iterations, (uint32_t)explore, h,
+                                                    HostNoise{0, 0, 0, 0, root_priors_out ? root_priors_out + b * kActions : nullptr}, &gb);
+            host_search_out(h, b, visits_out, wins_out, losses_out, nullptr, nodes_out);
+            if (action_out) action_out[b] = gb.action;
+            if (root_value_out) root_value_out[b] = q;
+            if (target_out) memcpy(target_out + b * kActions, gb.target, sizeof gb.target);
+            if (gumbel_out) memcpy(gumbel_out + b * kActions, gb.gum, sizeof gb.gum);
+        }
+    }, 1);
+    return GBL_OK;
 }
 
 int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *hist, int32_t *actions_traj, int8_t *winner_traj,
@@ -1003,6 +1058,10 @@ struct SelfplaySearch {
     int8_t tb_outcome[kActions];
     // gbl_cpu_collect_search_cap: the ply is a fast one -- h holds the small search, whose visits row is not recorded
     bool fast;
+    // gbl_cpu_collect_search_gumbel: the mover follows the Gumbel root rule -- gb holds its decision and the target row, which is recorded
+    // in the visits row's place; nothing is drawn from the visits
+    bool gumbel;
+    HostGumbel gb;
 };
 
 extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
@@ -1036,14 +1095,17 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
             S.solved = false;
             S.judged = S.table = false;
             S.fast = false;
+            S.gumbel = false;
             const bool tree = search(p, who, legal, g, q, S);
             int action, how = GBL_HOW_RANDOM, value = 0;
             if (tree) {
-                const bool sampled = !S.proven && tabs < sample_plies;
+                const bool sampled = !S.proven && !S.gumbel && tabs < sample_plies;
                 action = S.proven ? S.proven_action
+                         : S.gumbel ? S.gb.action
                          : sampled ? visits_pick(h.visits, draw32(seed, g, q, kStreamVisit))
                                    : S.table ? S.tb_action : tree_action_of(h.best);
                 how = S.proven ? GBL_HOW_PROVEN
+                      : S.gumbel ? GBL_HOW_GUMBEL
                       : S.table ? (sampled ? GBL_HOW_TABLE_SAMPLED : GBL_HOW_TABLE)
                       : S.fast  ? (sampled ? GBL_HOW_FAST_SAMPLED : GBL_HOW_FAST)
                                 : sampled ? GBL_HOW_SEARCH_SAMPLED : GBL_HOW_SEARCH;
@@ -1068,7 +1130,8 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
             if (T.done) T.done[at] = (int8_t)dn;
             if (T.to_move) T.to_move[at] = (int8_t)mover;
             if (T.visits)
-                for (int a = 0; a < kActions; ++a) T.visits[at * kActions + a] = (int16_t)(tree && !S.fast ? h.visits[a] : 0);
+                for (int a = 0; a < kActions; ++a)
+                    T.visits[at * kActions + a] = (int16_t)(S.gumbel ? S.gb.target[a] : tree && !S.fast ? h.visits[a] : 0);
             if (T.value) T.value[at] = value;
             if (T.nodes) T.nodes[at] = tree ? (int32_t)h.count : 0;
             if (T.how) T.how[at] = (int8_t)how;
@@ -1101,7 +1164,7 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
 }
 }  // extern "C++"
 
-// The five self-play entry points behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
+// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb) behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
 // over the threads.  gbl_cpu_collect_search_eval is the guarded loop with depths and weights 0 and no outcome / proven arrays;
 // gbl_cpu_collect_search_tb is it with the probe in front of every ply that is judged or played from the table.
 static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
@@ -1176,8 +1239,11 @@ static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
             // (the playout cap's draw, after the guard: a proven ply takes none)
             const CapPly cp = cap_ply(c.seed, g, q, (uint32_t)selfplay_share(c, who), its, (uint32_t)c.fast[who], (uint32_t)c.noise[who]);
             S.fast = cp.fast;
+            S.gumbel = selfplay_considered(c, who) != 0;
+            S.gb = HostGumbel{GumbelArgs{(uint32_t)selfplay_considered(c, who), (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale},
+                              c.seed, g, q, -1, {}, {}};
             S.root_q = host_tree_search_eval(nodes, pri, who ? net1 : net0, p, who, cand, cp.its, (uint32_t)c.explore, S.h,
-                                             HostNoise{cp.noise, c.seed, g, q, root_pi});
+                                             HostNoise{cp.noise, c.seed, g, q, root_pi}, S.gumbel ? &S.gb : nullptr);
             S.priors = root_pi;  // (the network's row; zeros where the root has no candidate)
             return true;
         });
@@ -1214,6 +1280,24 @@ int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, in
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
                             counters, turn, nullptr, nullptr, nullptr, 0, 0});
+}
+
+int gbl_cpu_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                  int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                  int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                                  int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
+                                  uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
+                                  int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                                  int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, int considered0,
+                                  int considered1, int gumbel_noise, int visit_offset, int scale, void *)
+{
+    return host_selfplay_run({kRunEval, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr, nullptr, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0, 0, {0, 0}, {0, 0}, 1, {considered0, considered1}, gumbel_noise,
+                            visit_offset, scale});
 }
 
 int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,

@@ -25,6 +25,8 @@
 #endif
 #include <stdint.h>
 
+#include "gobblet_knobs.h"  // (kGumbelTable)
+
 namespace gbl {
 
 constexpr int kTile = 64;   // boards per wavefront
@@ -2225,14 +2227,16 @@ inline const char *cap_fast_error(int fast_iterations, int iterations)
 // The selection key of candidate a with prior pi under a node of nv visits: the mean of its child (tree_key's first term; 32768
 // without a child, n = 0) plus ((explore pi isqrt(nv << 8)) >> 5) / (1 + n).  nv <= 512: the root of the isqrt stays below 2^24,
 // the product below 1024 * 255 * 363 < 2^27.
+__device__ __forceinline__ uint32_t tree_eval_mean(uint32_t W, uint32_t L, uint32_t n)  // (n >= 1) 0 .. 65536, for the side that moved into the child
+{
+    const uint32_t d = n * kTreeEvalP, x = W + d - L;
+    const uint32_t hi = (x << 7) / d, rem = (x << 7) - hi * d;
+    return (hi << 8) + (rem << 8) / d;
+}
+
 __device__ __forceinline__ uint32_t tree_eval_key(bool child, uint32_t W, uint32_t L, uint32_t n, uint32_t nv, uint32_t pi, uint32_t explore)
 {
-    uint32_t mean = 32768u;
-    if (child) {
-        const uint32_t d = n * kTreeEvalP, x = W + d - L;
-        const uint32_t hi = (x << 7) / d, rem = (x << 7) - hi * d;
-        mean = (hi << 8) + (rem << 8) / d;
-    }
+    const uint32_t mean = child ? tree_eval_mean(W, L, n) : 32768u;
     return mean + ((explore * pi * tree_isqrt(nv << 8)) >> 5) / (1u + (child ? n : 0u));
 }
 
@@ -2250,9 +2254,10 @@ struct TreeEvalLeaf {
 };
 
 // Selection, one node and one candidate after the other (the host flavour; k_tree_eval gives every action a lane).  pri: the prior
-// rows, kEvalOutputs bytes per node.  rootcand != 0.
+// rows, kEvalOutputs bytes per node.  rootcand != 0.  root_action >= 0: the root takes that action whatever its keys say (the Gumbel
+// root rule picks it, gumbel_root_select); below the root nothing changes.
 __device__ __forceinline__ TreeEvalLeaf tree_eval_select(const TreeNode *nodes, const uint8_t *pri, const Planes &root, int mover,
-                                                         uint64_t rootcand, uint32_t explore)
+                                                         uint64_t rootcand, uint32_t explore, int root_action = -1)
 {
     TreeEvalLeaf s{0u, root, mover, false, 0u};
     uint64_t cand = rootcand;
@@ -2269,7 +2274,7 @@ __device__ __forceinline__ TreeEvalLeaf tree_eval_select(const TreeNode *nodes, 
                                                               pri[s.node * kEvalOutputs + a], explore), a);
             if (key > best) best = key;
         }
-        s.a = 63u - (best & 63u);
+        s.a = s.node == 0u && root_action >= 0 ? (uint32_t)root_action : 63u - (best & 63u);
         if (!of[s.a]) {
             s.expand = true;
             return s;
@@ -2279,6 +2284,184 @@ __device__ __forceinline__ TreeEvalLeaf tree_eval_select(const TreeNode *nodes, 
         s.node = of[s.a];
         cand = legal54(s.p, s.side);
     }
+}
+
+// ---- Gumbel root search (include/gobblet_hip.h, "Gumbel root search"): one statement for the kernels and the host flavour ---------
+// The scalar pieces -- the draw, the root logit, the completed value, sigma, the schedule and the three order keys -- are functions of
+// one action, so that the kernels give every action a lane (the considered set A is a ballot mask, "the k largest" a count over the
+// set bits) and the host flavour runs them one after the other (GumbelRoot below).
+constexpr uint32_t kStreamGumbel = 10u;  // generator stream of the Gumbel row
+constexpr int kGumbelMaxConsidered = 54, kGumbelMaxOffset = 255, kGumbelMaxScale = 64;
+constexpr int kHowGumbel = 10;  // GBL_HOW_GUMBEL
+
+struct GumbelArgs {  // considered == 0: the side searches by gbl_tree_search_eval's rule (gbl_collect_search_gumbel alone admits it)
+    uint32_t considered, noise, visit_offset, scale;
+};
+
+// g_a: the table at the top byte of the word of (seed, g, ply index 64 q + a) -- one Philox block serves four actions
+__device__ __forceinline__ int32_t gumbel_draw(uint64_t seed, uint64_t g, uint32_t q, uint32_t a)
+{
+    return kGumbelTable[draw32(seed, g, 64u * q + a, kStreamGumbel) >> 24];
+}
+
+// the root logit: minus the distance below the largest one, the prior rule's own cap
+__device__ __forceinline__ int32_t gumbel_logit(int32_t lmax, int32_t l) { return -(lmax - l < 255 ? lmax - l : 255); }
+
+// the completed value of an action: its child's mean, else the root's q on the same 0 .. 65536 scale
+__device__ __forceinline__ uint32_t gumbel_mean(bool child, uint32_t W, uint32_t L, uint32_t n, int32_t q_root)
+{
+    return child ? tree_eval_mean(W, L, n) : (uint32_t)(32768 + 256 * q_root);
+}
+
+// sigma: (767 * 64 * 65536 < 2^32)
+__device__ __forceinline__ int32_t gumbel_sigma(const GumbelArgs &G, uint32_t maxN, uint32_t mean)
+{
+    return (int32_t)(((G.visit_offset + maxN) * G.scale * mean) >> 16);
+}
+
+__device__ __forceinline__ uint32_t gumbel_phases(uint32_t m)  // max(1, ceil(log2 m)), m >= 1
+{
+    uint32_t p = 0;
+    while ((1u << p) < m) ++p;
+    return p ? p : 1u;
+}
+__device__ __forceinline__ uint32_t gumbel_step(uint32_t iterations, uint32_t P, uint32_t k)
+{
+    const uint32_t s = iterations / (P * k);
+    return s ? s : 1u;
+}
+__device__ __forceinline__ uint32_t gumbel_kept(uint32_t k) { return k <= 4u ? 2u : (k + 1u) >> 1; }  // max(2, ceil(k / 2)), k > 2
+
+// The order keys, each a max: 0 stands for an action outside the set.  s = g + l (>= -42 - 255) or g + l + sigma (< 2^16 - 512).
+//   rank: the larger s, then the lower action -- the considered set and the halving
+//   pick: the fewest visits (n <= 512), then the larger g + l, then the lower action -- the root's selection
+//   final: the most visits, then the larger g + l + sigma, then the lower action -- the decision
+__device__ __forceinline__ uint32_t gumbel_rank_key(int32_t s, uint32_t a) { return ((uint32_t)(s + 512) << 6) | (63u - a); }
+__device__ __forceinline__ uint32_t gumbel_pick_key(uint32_t n, int32_t gl, uint32_t a) { return ((512u - n) << 16) | gumbel_rank_key(gl, a); }
+__device__ __forceinline__ uint32_t gumbel_final_key(uint32_t n, int32_t s, uint32_t a) { return (n << 22) | gumbel_rank_key(s, a); }
+__device__ __forceinline__ int gumbel_action_of(uint32_t key) { return key ? 63 - (int)(key & 63u) : -1; }
+
+// the k actions of A with the largest keys (the keys differ: each holds its action)
+__device__ __forceinline__ uint64_t gumbel_keep(const uint32_t (&key)[kActions], uint64_t A, uint32_t k)
+{
+    uint64_t kept = 0;
+    for (uint64_t i = A; i; i &= i - 1) {
+        const int a = __builtin_ctzll(i);
+        uint32_t above = 0;
+        for (uint64_t j = A; j; j &= j - 1) above += key[__builtin_ctzll(j)] > key[a];
+        if (above < k) kept |= 1ull << a;
+    }
+    return kept;
+}
+
+// One root's rule, one action after the other (the host flavour; the kernels keep gum / gl in a lane each and A, T wave-uniform).
+struct GumbelRoot {
+    GumbelArgs G;
+    uint32_t iterations, P, T;
+    int32_t q_root;
+    uint64_t cand, A;
+    int32_t gum[kActions], gl[kActions];
+};
+
+// the root's children as the rule reads them: n_a (0 without a child) and mean_a; returns maxN
+__device__ __forceinline__ uint32_t gumbel_children(const GumbelRoot &R, const TreeNode *nodes, uint32_t (&n)[kActions], uint32_t (&mean)[kActions])
+{
+    uint32_t maxN = 0;
+    for (int a = 0; a < kActions; ++a) {
+        n[a] = 0;
+        mean[a] = gumbel_mean(false, 0u, 0u, 1u, R.q_root);
+    }
+    for (uint32_t c = nodes[0].child; c; c = nodes[c].sibling) {
+        const TreeNode &k = nodes[c];
+        const uint32_t a = tree_action(k);
+        n[a] = k.n;
+        mean[a] = gumbel_mean(true, tree_wins(k), tree_losses(k), k.n, R.q_root);
+        maxN = k.n > maxN ? k.n : maxN;
+    }
+    return maxN;
+}
+
+// o: the root evaluation's outputs; cand != 0
+__device__ __forceinline__ void gumbel_root_init(GumbelRoot &R, const GumbelArgs &G, uint32_t iterations, uint64_t seed, uint64_t g, uint32_t q,
+                                                 uint64_t cand, const int32_t (&o)[kEvalOutputs], int32_t shift_p, int32_t q_root)
+{
+    R.G = G;
+    R.iterations = iterations;
+    R.q_root = q_root;
+    R.cand = cand;
+    int32_t lmax = INT32_MIN;
+    for (int a = 0; a < kActions; ++a)
+        if (((cand >> a) & 1ull) && (o[a] >> shift_p) > lmax) lmax = o[a] >> shift_p;
+    uint32_t key[kActions];
+    for (int a = 0; a < kActions; ++a) {
+        const bool in = (cand >> a) & 1ull;
+        R.gum[a] = in && G.noise ? gumbel_draw(seed, g, q, (uint32_t)a) : 0;
+        R.gl[a] = in ? R.gum[a] + gumbel_logit(lmax, o[a] >> shift_p) : 0;
+        key[a] = in ? gumbel_rank_key(R.gl[a], (uint32_t)a) : 0u;
+    }
+    const uint32_t c = (uint32_t)__builtin_popcountll(cand), m = G.considered < c ? G.considered : c;
+    R.A = gumbel_keep(key, cand, m);
+    R.P = gumbel_phases(m);
+    R.T = gumbel_step(iterations, R.P, m);
+}
+
+// before an iteration's selection: halve where the schedule says so, then the root's action
+__device__ __forceinline__ int gumbel_root_select(GumbelRoot &R, const TreeNode *nodes)
+{
+    uint32_t n[kActions], mean[kActions], key[kActions] = {};
+    const uint32_t maxN = gumbel_children(R, nodes, n, mean);
+    const uint32_t size = (uint32_t)__builtin_popcountll(R.A);
+    bool due = size > 2u;
+    for (uint64_t i = R.A; i; i &= i - 1) due = due && n[__builtin_ctzll(i)] >= R.T;
+    if (due) {
+        for (uint64_t i = R.A; i; i &= i - 1) {
+            const int a = __builtin_ctzll(i);
+            key[a] = gumbel_rank_key(R.gl[a] + gumbel_sigma(R.G, maxN, mean[a]), (uint32_t)a);
+        }
+        R.A = gumbel_keep(key, R.A, gumbel_kept(size));
+        R.T += gumbel_step(R.iterations, R.P, (uint32_t)__builtin_popcountll(R.A));
+    }
+    uint32_t best = 0;
+    for (uint64_t i = R.A; i; i &= i - 1) {
+        const int a = __builtin_ctzll(i);
+        const uint32_t k = gumbel_pick_key(n[a], R.gl[a], (uint32_t)a);
+        best = k > best ? k : best;
+    }
+    return gumbel_action_of(best);
+}
+
+// after the last iteration: the decision, and the target row (54 bytes; may be NULL)
+__device__ __forceinline__ int gumbel_root_finish(const GumbelRoot &R, const TreeNode *nodes, uint8_t *target)
+{
+    uint32_t n[kActions], mean[kActions];
+    const uint32_t maxN = gumbel_children(R, nodes, n, mean);
+    uint32_t best = 0, sum = 0;
+    int32_t t[kActions], tmax = INT32_MIN;
+    for (int a = 0; a < kActions; ++a) {
+        if (!((R.cand >> a) & 1ull)) continue;
+        const int32_t sigma = gumbel_sigma(R.G, maxN, mean[a]);
+        t[a] = R.gl[a] - R.gum[a] + sigma;
+        tmax = t[a] > tmax ? t[a] : tmax;
+        if ((R.A >> a) & 1ull) {
+            const uint32_t k = gumbel_final_key(n[a], R.gl[a] + sigma, (uint32_t)a);
+            best = k > best ? k : best;
+        }
+    }
+    if (target) {
+        for (int a = 0; a < kActions; ++a)
+            if ((R.cand >> a) & 1ull) sum += eval_exp2(tmax, t[a]);
+        for (int a = 0; a < kActions; ++a) target[a] = (uint8_t)(((R.cand >> a) & 1ull) ? eval_prior(eval_exp2(tmax, t[a]), sum) : 0u);
+    }
+    return gumbel_action_of(best);
+}
+
+inline const char *gumbel_error(int considered, int gumbel_noise, int visit_offset, int scale, int least = 1)
+{
+    if (considered < least || considered > kGumbelMaxConsidered) return least ? "considered must be in [1, 54]" : "considered0 / considered1 must be in [0, 54]";
+    if (gumbel_noise != 0 && gumbel_noise != 1) return "gumbel_noise must be 0 or 1";
+    if (visit_offset < 0 || visit_offset > kGumbelMaxOffset) return "visit_offset must be in [0, 255]";
+    if (scale < 0 || scale > kGumbelMaxScale) return "scale must be in [0, 64]";
+    return nullptr;
 }
 
 // ---- gbl_solve: the exact depth-bounded solver (contract: include/gobblet_hip.h) ----------------------------------------------
@@ -2516,7 +2699,7 @@ inline const char *collect_solve_error(int illegal_mode, int policy0, int policy
     return nullptr;
 }
 
-// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise and _tb, and the checks both flavours make of them ----
+// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise, _cap, _gumbel and _tb, and the checks both flavours make of them ----
 // The 19 trajectory arrays (any may be NULL).
 struct SelfplayTraj {
     int32_t *actions;
@@ -2558,7 +2741,18 @@ struct SelfplayCall {
     // gbl_collect_search_cap's own (cap = 0 elsewhere: neither array is read)
     int cap;
     int fast[2], share[2];
+    // gbl_collect_search_gumbel's own (gumbel = 0 elsewhere: none is read)
+    int gumbel;
+    int considered[2];
+    int gumbel_noise, visit_offset, scale;
 };
+
+// how many actions side m's Gumbel root rule considers: 0 (the side searches by gbl_tree_search_eval's rule, or does not search) elsewhere
+template <typename Ev>
+inline int selfplay_considered(const SelfplayCall<Ev> &c, int m)
+{
+    return c.gumbel && c.policy[m] == kPolicyEvalTree ? c.considered[m] : 0;
+}
 
 // the share of full plies that side m's plies are drawn against: 256 (nothing is drawn) without a cap or for a side that does not search
 template <typename Ev>
@@ -2607,7 +2801,8 @@ inline const char *collect_tb_error(const SelfplayCall<Ev> &c)
 }
 
 // Everything both flavours look at, in the order they report it: n < 0, the entry point's *_error, the searching sides' noise
-// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
+// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) (gbl_collect_search_gumbel: their `considered`, then the
+// rule's three where a side follows it,) n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
 // per searching side `side(m)` -- the flavour's own look at evaluator m
 // (its pointers; on the device their alignment too), which returns 0 or what its fail() returned.  Returns a flavour's error
 // code (< 0; fail(message) makes a GBL_ERR_ARG of a message), 0 where there is nothing to do (GBL_OK), or 1: the flavour goes on
@@ -2635,6 +2830,13 @@ inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, 
         for (int m = 0; m < 2; ++m)
             if (c.policy[m] == searching && c.share[m] < kCapFullShare)
                 if (const char *bad = cap_fast_error(c.fast[m], c.iterations[m])) return fail(bad);
+    }
+    if (c.gumbel) {  // gbl_collect_search_gumbel: the searching sides' considered, then the rule's three where a side follows it
+        for (int m = 0; m < 2; ++m)
+            if (c.policy[m] == searching)
+                if (const char *bad = gumbel_error(c.considered[m], 0, 0, 0, 0)) return fail(bad);
+        if (selfplay_considered(c, 0) || selfplay_considered(c, 1))
+            if (const char *bad = gumbel_error(kGumbelMaxConsidered, c.gumbel_noise, c.visit_offset, c.scale)) return fail(bad);
     }
     if (c.n == 0) return 0;
     if (!c.state) return fail("state must not be NULL");
@@ -2732,6 +2934,17 @@ inline const char *tree_search_noise_error(int noise, uint32_t call, uint64_t en
     if (n < 0) return "n < 0";
     if (const char *why = noise_error(noise)) return why;
     return call_env_error(call, env_base, n);
+}
+
+// gbl_tree_search_gumbel: gbl_tree_search_eval_noise's errors in their order (the noise weight apart), then the rule's four
+template <typename Ev>
+inline const char *tree_search_gumbel_error(const Ev *ev, int iterations, int explore, int considered, int gumbel_noise, int visit_offset,
+                                            int scale, uint32_t call, uint64_t env_base, int64_t n, const void *state, const void *to_move)
+{
+    if (const char *why = tree_search_noise_error(0, call, env_base, n)) return why;
+    if (const char *why = tree_search_eval_error(ev, iterations, explore, n < 0 ? n : 0, state, to_move)) return why;
+    if (const char *why = gumbel_error(considered, gumbel_noise, visit_offset, scale)) return why;
+    return tree_search_eval_error(ev, iterations, explore, n, state, to_move);
 }
 
 // ---- board symmetries (include/gobblet_hip.h, "Board symmetries"): gbl_symmetry_apply and gbl_training_batch ------------------------

@@ -1993,11 +1993,53 @@ struct RootNoise {
     uint32_t q;
 };
 
-template <bool NOISE>
+// The Gumbel root rule of one search (include/gobblet_hip.h, "Gumbel root search"; GUMBEL = false compiles it out, and G.considered == 0
+// is a side that searches by the keys).  The wavefront's whole state: lane a keeps g_a and g_a + l_a, the considered set A is a ballot
+// mask, and the schedule's phase count and target are wave-uniform locals of tree_eval_iterations -- no LDS.
+struct WaveGumbel {
+    GumbelArgs G;
+    uint64_t seed, g;
+    uint32_t q;
+    int32_t gum, gl;  // (out) this lane's g_a and g_a + l_a; 0 outside the candidates
+    uint64_t A;       // (out) the considered set after the last halving; 0 where the rule did not run
+};
+
+// the k lanes of A with the largest keys, as a mask (the keys differ; key == 0 outside A): a lane counts the keys above its own
+__device__ __forceinline__ uint64_t wave_gumbel_keep(uint32_t key, uint64_t A, uint32_t k)
+{
+    uint32_t above = 0;
+    for (uint64_t i = A; i; i &= i - 1) {
+        const int j = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(i));
+        above += (uint32_t)__builtin_amdgcn_readlane((int)key, j) > key ? 1u : 0u;
+    }
+    return (uint64_t)__ballot(key != 0u && above < k);
+}
+
+// after the last iteration (the rule ran: gb.A != 0): the decision in every lane, and lane a's byte of the target row.  c: the lane's
+// root child, as tree_lane_child gives it.
+struct GumbelOut {
+    int action;
+    uint32_t target;
+};
+
+__device__ __forceinline__ GumbelOut wave_gumbel_finish(const WaveGumbel &gb, const TreeChild &c, uint64_t cand, int32_t q_root, uint32_t lane)
+{
+    const bool in = (cand >> lane) & 1ull, in_a = (gb.A >> lane) & 1ull;
+    const uint32_t max_n = wave_max(c.visits());
+    const int32_t sigma = gumbel_sigma(gb.G, max_n, gumbel_mean(c.mine(), c.w, c.l, c.n, q_root));
+    const int32_t t = gb.gl - gb.gum + sigma;
+    const int32_t tmax = wave_max<int32_t>(in ? t : INT32_MIN);
+    const uint32_t e = in ? eval_exp2(tmax, t) : 0u;
+    const uint32_t sum = wave_sum(e);
+    const uint32_t key = wave_max(in_a ? gumbel_final_key(c.visits(), gb.gl + sigma, lane) : 0u);
+    return GumbelOut{gumbel_action_of(key), in ? eval_prior(e, sum) : 0u};
+}
+
+template <bool NOISE, bool GUMBEL = false>
 __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, uint8_t *const pri, uint32_t *const s_h, const EvalNet &net,
                                                          const Planes &root, const int mover, const uint64_t cand, const uint32_t iterations,
                                                          const uint32_t explore, const uint32_t lane, uint32_t &count, const RootNoise &noise,
-                                                         uint32_t &mixed)
+                                                         uint32_t &mixed, WaveGumbel *const gb = nullptr)
 {
     if (lane == 0) nodes[0] = TreeNode{};
     const WaveEval at_root = wave_evaluate(net, root, mover, cand, s_h, lane);
@@ -2013,6 +2055,24 @@ __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, 
     if (lane < (uint32_t)kEvalOutputs) pri[lane] = (uint8_t)mixed;
     wave_lds_fence();  // (the root is written)
     count = 1;
+    bool rule = false;          // (wave-uniform) the root follows the Gumbel rule
+    uint32_t phases = 1, T = 0;  // the schedule: P and the visit target of the next halving
+    if constexpr (GUMBEL) {
+        rule = gb->G.considered != 0u && cand != 0ull;
+        gb->gum = gb->gl = 0;
+        gb->A = 0ull;
+        if (rule) {
+            const bool in = (cand >> lane) & 1ull;
+            const int32_t l = at_root.o >> net.shift_p;
+            const int32_t lmax = wave_max<int32_t>(in ? l : INT32_MIN);
+            if (gb->G.noise) gb->gum = in ? gumbel_draw(gb->seed, gb->g, gb->q, lane) : 0;
+            gb->gl = in ? gb->gum + gumbel_logit(lmax, l) : 0;
+            const uint32_t c = (uint32_t)__popcll(cand), m = gb->G.considered < c ? gb->G.considered : c;
+            gb->A = wave_gumbel_keep(in ? gumbel_rank_key(gb->gl, lane) : 0u, cand, m);
+            phases = gumbel_phases(m);
+            T = gumbel_step(iterations, phases, m);
+        }
+    }
     for (uint32_t i = 0; cand && i < iterations; ++i) {
         // 1. select
         uint32_t v = 0, term, a_new = 0;
@@ -2026,7 +2086,21 @@ __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, 
             if (term) break;
             const TreeChild my = tree_lane_child(nodes, nv.child, lane);
             const uint32_t pi = lane < (uint32_t)kEvalOutputs ? pri[v * kEvalOutputs + lane] : 0u;
-            const uint32_t key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my.mine(), my.w, my.l, my.n, nv.n, pi, explore), lane) : 0u);
+            uint32_t key;
+            if (GUMBEL && rule && v == 0u) {  // the root: halve where the schedule says so, then the least visited action of A
+                uint64_t A = gb->A;
+                const bool in_a = (A >> lane) & 1ull;
+                const uint32_t size = (uint32_t)__popcll(A);
+                if (size > 2u && !__ballot(in_a && my.visits() < T)) {
+                    const int32_t sigma = gumbel_sigma(gb->G, wave_max(my.visits()), gumbel_mean(my.mine(), my.w, my.l, my.n, at_root.q));
+                    A = wave_gumbel_keep(in_a ? gumbel_rank_key(gb->gl + sigma, lane) : 0u, A, gumbel_kept(size));
+                    gb->A = A;
+                    T += gumbel_step(iterations, phases, (uint32_t)__popcll(A));
+                }
+                key = wave_max(((A >> lane) & 1ull) ? gumbel_pick_key(my.visits(), gb->gl, lane) : 0u);
+            } else {
+                key = wave_max(((cd >> lane) & 1ull) ? tree_order_key(tree_eval_key(my.mine(), my.w, my.l, my.n, nv.n, pi, explore), lane) : 0u);
+            }
             a_new = (uint32_t)__builtin_amdgcn_readfirstlane((int)(63u - (key & 63u)));
             const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)my.c, (int)a_new);
             if (!c) {
@@ -2061,14 +2135,22 @@ __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, 
 // gbl_tree_search_eval: k_tree's tree with a network leaf.  One wavefront per board (a grid-stride loop over boards).  The tree is
 // (iterations + 1) 16-byte nodes followed by (iterations + 1) 56-byte prior rows in dynamic LDS; the root planes stay in registers.
 // The search is tree_eval_iterations; the wavefront then writes the root's children out and decides (tree_root_out).
-template <bool NOISE>
+// GUMBEL: gbl_tree_search_gumbel -- the root follows the Gumbel rule (tree_eval_iterations<.., true>), the decision and the target row
+// come from wave_gumbel_finish on the root's children that tree_root_out has just read out.
+struct GumbelOutputs {  // (empty in the instantiations without the rule)
+    uint8_t *target;
+    int16_t *gumbel;
+    GumbelArgs G;
+};
+
+template <bool NOISE, bool GUMBEL = false>
 __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ state, const int8_t *__restrict__ to_move,
                                                   const int8_t *__restrict__ mask, const EvalNet net, int32_t *__restrict__ visits_out,
                                                   int32_t *__restrict__ wins_out, int32_t *__restrict__ losses_out,
                                                   int32_t *__restrict__ action_out, int32_t *__restrict__ nodes_out,
                                                   int32_t *__restrict__ root_value_out, uint8_t *__restrict__ root_priors_out, int64_t n,
                                                   uint32_t iterations, uint32_t explore, uint8_t *__restrict__ root_mixed_out, uint32_t noise,
-                                                  uint64_t seed, uint64_t env_base, uint32_t call)
+                                                  uint64_t seed, uint64_t env_base, uint32_t call, const GumbelOutputs gum)
 {
     extern __shared__ uint4 s_tree[];
     TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
@@ -2080,13 +2162,24 @@ __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ sta
         const int mover = to_move[b] != 0;
         const uint64_t cand = board_candidates(root, mover, mask, b, lane);
         uint32_t count, mixed;
-        const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, net, root, mover, cand, iterations, explore, lane, count,
-                                                             RootNoise{noise, seed, env_base + (uint64_t)b, call}, mixed);
+        WaveGumbel gb{gum.G, seed, env_base + (uint64_t)b, call, 0, 0, 0ull};
+        const WaveEval at_root = tree_eval_iterations<NOISE, GUMBEL>(nodes, pri, s_h, net, root, mover, cand, iterations, explore, lane, count,
+                                                                     RootNoise{noise, seed, env_base + (uint64_t)b, call}, mixed, &gb);
         const uint64_t key = tree_root_out(nodes, lane, b, visits_out, wins_out, losses_out);
+        int action = GUMBEL ? -1 : tree_action_of(key);
+        if constexpr (GUMBEL) {
+            GumbelOut out{-1, 0u};
+            if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), cand, at_root.q, lane);
+            action = out.action;
+            if (lane < (uint32_t)kActions) {
+                if (gum.target) gum.target[b * kActions + lane] = (uint8_t)out.target;
+                if (gum.gumbel) gum.gumbel[b * kActions + lane] = (int16_t)gb.gum;
+            }
+        }
         if (root_priors_out && lane < (uint32_t)kActions) root_priors_out[b * kActions + lane] = (uint8_t)at_root.pi;
         if (NOISE && root_mixed_out && lane < (uint32_t)kActions) root_mixed_out[b * kActions + lane] = (uint8_t)mixed;
         if (lane == 0) {
-            if (action_out) action_out[b] = tree_action_of(key);
+            if (action_out) action_out[b] = action;
             if (nodes_out) nodes_out[b] = (int32_t)count;
             if (root_value_out) root_value_out[b] = at_root.q;
         }
@@ -2316,13 +2409,18 @@ __device__ __forceinline__ EvalNet eval_net_pick(const EvalNet &a, const EvalNet
                    second ? b.shift1 : a.shift1, second ? b.shift_p : a.shift_p, second ? b.shift_v : a.shift_v};
 }
 
+// GUMBEL: gbl_collect_search_gumbel -- a side with considered_m > 0 searches by the Gumbel root rule with call = the ply index: its
+// action is the rule's decision (never the visit-proportional draw), how = GBL_HOW_GUMBEL and the visits row holds the target bytes.
+// gum.G's considered is not read: the two sides' own travel beside it.
+template <bool GUMBEL>
 __global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                      uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
                                                      int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
                                                      int32_t *__restrict__ root_value_traj, uint8_t *__restrict__ priors_traj,
                                                      const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
                                                      uint32_t iterations1, uint32_t most, uint32_t explore, int sample_plies, int illegal_mode,
-                                                     int64_t *__restrict__ counters, int32_t *__restrict__ turn)
+                                                     int64_t *__restrict__ counters, int32_t *__restrict__ turn, const GumbelArgs gum,
+                                                     uint32_t considered0, uint32_t considered1)
 {
     extern __shared__ uint4 s_tree[];
     TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
@@ -2335,11 +2433,23 @@ __global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state,
         [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
             if ((who ? policy1 : policy0) != kPolicyEvalTree) return false;
             uint32_t mixed;  // (no noise here: the network's byte)
-            const WaveEval at_root = tree_eval_iterations<false>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
-                                                                 who ? iterations1 : iterations0, explore, lane, S.count, RootNoise{}, mixed);
+            WaveGumbel gb{GumbelArgs{who ? considered1 : considered0, gum.noise, gum.visit_offset, gum.scale}, seed, g, q, 0, 0, 0ull};
+            const WaveEval at_root = tree_eval_iterations<false, GUMBEL>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
+                                                                         who ? iterations1 : iterations0, explore, lane, S.count, RootNoise{},
+                                                                         mixed, &gb);
             S.pi = at_root.pi;
             S.root_q = at_root.q;
-            S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
+            const bool rule = GUMBEL && gb.G.considered != 0u;  // (wave-uniform) a Gumbel side's ply
+            S.d = search_decide(nodes, lane, !rule && B.tabs < sample_plies, seed, g, q);
+            if constexpr (GUMBEL) {
+                if (rule) {
+                    GumbelOut out{-1, 0u};
+                    if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), legal, at_root.q, lane);
+                    S.d.action = out.action;
+                    S.d.how = kHowGumbel;
+                    S.d.my_n = out.target;
+                }
+            }
             wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
             return true;
         },
@@ -5211,7 +5321,7 @@ static int tree_search_eval_launch(const char *name, const int8_t *state, const 
 #define GBL_TE(NOISE)                                                                                                                   \
     hipLaunchKernelGGL(k_tree_eval<NOISE>, board_grid(n), dim3(64), lds, (hipStream_t)stream, state, to_move, mask, net, visits_out,    \
                        wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n, (uint32_t)iterations,           \
-                       (uint32_t)explore, root_mixed_out, (uint32_t)noise, seed, env_base, call)
+                       (uint32_t)explore, root_mixed_out, (uint32_t)noise, seed, env_base, call, GumbelOutputs{})
     if (noise || root_mixed_out)
         GBL_TE(true);
     else
@@ -5239,7 +5349,32 @@ int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const
                                    n, stream);
 }
 
-// The five self-play entry points between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
+// gbl_tree_search_gumbel: k_tree_eval's instantiation with the Gumbel root rule and without the noise's code
+int gbl_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                           int explore, int considered, int gumbel_noise, int visit_offset, int scale, uint64_t seed, uint64_t env_base,
+                           uint32_t call, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                           int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *target_out, int16_t *gumbel_out,
+                           int64_t n, void *stream)
+{
+    if (const char *why = tree_search_gumbel_error(ev, iterations, explore, considered, gumbel_noise, visit_offset, scale, call, env_base, n,
+                                                   state, to_move))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
+    EvalNet net;
+    if (const int e = eval_net_of(ev, net)) return e;
+    if (off_dword(visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out))
+        return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / root_value_out must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(gumbel_out) & 1u) return fail(GBL_ERR_ALIGN, "gumbel_out must be 2-byte aligned");
+    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);  // (the tree of gbl_tree_search_eval: the rule adds none)
+    hipLaunchKernelGGL((k_tree_eval<false, true>), board_grid(n), dim3(64), lds, (hipStream_t)stream, state, to_move, mask, net, visits_out,
+                       wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n, (uint32_t)iterations,
+                       (uint32_t)explore, (uint8_t *)nullptr, 0u, seed, env_base, call,
+                       GumbelOutputs{target_out, gumbel_out,
+                                     GumbelArgs{(uint32_t)considered, (uint32_t)gumbel_noise, (uint32_t)visit_offset, (uint32_t)scale}});
+    GBL_LAUNCHED("gbl_tree_search_gumbel");
+}
+
+// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb) between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
 // evaluators as the kernels take them, the trajectory's strides and alignments, the grid, the tree's LDS and the entry's own kernel.
 static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &c, void *stream)
 {
@@ -5278,9 +5413,18 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
         }
 #undef GBL_CS
     } else if (c.run == kRunEval) {
-        hipLaunchKernelGGL(k_collect_eval, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
-                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1], its0,
-                           its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn);
+        const uint32_t m0 = (uint32_t)selfplay_considered(c, 0), m1 = (uint32_t)selfplay_considered(c, 1);
+        const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
+        // (k_collect_eval<false> is the kernel without the rule's code: gbl_collect_search_eval, and gbl_collect_search_gumbel with no Gumbel side)
+#define GBL_CE(GUMBEL)                                                                                                                    \
+    hipLaunchKernelGGL(k_collect_eval<GUMBEL>, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,       \
+                       c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1],  \
+                       its0, its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn, gum, m0, m1)
+        if (m0 | m1)
+            GBL_CE(true);
+        else
+            GBL_CE(false);
+#undef GBL_CE
     } else if (c.run == kRunTb) {
         const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
                        w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
@@ -5356,6 +5500,26 @@ int gbl_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_
                             n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
                             {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
                             counters, turn, nullptr, nullptr, nullptr, 0, 0},
+                           stream);
+}
+
+int gbl_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                              int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                              int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                              uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base,
+                              uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                              const gbl_evaluator *ev1, int iterations0, int iterations1, int explore, int sample_plies, int illegal_mode,
+                              int64_t *counters, int32_t *turn, int considered0, int considered1, int gumbel_noise, int visit_offset,
+                              int scale, void *stream)
+{
+    return selfplay_launch("gbl_collect_search_gumbel",
+                           {kRunEval, state, to_move, done,
+                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
+                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr, nullptr, nullptr, nullptr},
+                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
+                            {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
+                            counters, turn, nullptr, nullptr, nullptr, 0, 0, 0, {0, 0}, {0, 0}, 1, {considered0, considered1}, gumbel_noise,
+                            visit_offset, scale},
                            stream);
 }
 

@@ -46,3 +46,27 @@ constexpr int kReanalyseGroups = 1 << 20; // gbl_reanalyse's grid cap, k_tree_ev
 #define GBL_KNOB_EXTRA_ENTRY_POINTS
 
 #endif  // GBL_AB_BUILD
+
+// The Gumbel root rule's table (include/gobblet_hip.h, "Gumbel root search"): GT[k] = round(-ln(-ln((k + 1/2) / 256)) * 16 / ln 2), a
+// standard Gumbel variate at the midpoint of the k-th of 256 equal slices of (0, 1), in the logits' unit of 1/16 of an octave.  A
+// table of the RULE, not a knob: every build carries the same 256 numbers, and the header prints them.
+namespace gbl {
+constexpr int16_t kGumbelTable[256] = {
+    -42, -38, -35, -34, -32, -31, -30, -29, -28, -28, -27, -26, -26, -25, -24, -24,
+    -23, -23, -22, -22, -21, -21, -21, -20, -20, -19, -19, -19, -18, -18, -17, -17,
+    -17, -16, -16, -16, -15, -15, -15, -14, -14, -14, -14, -13, -13, -13, -12, -12,
+    -12, -11, -11, -11, -11, -10, -10, -10, -10, -9, -9, -9, -8, -8, -8, -8,
+    -7, -7, -7, -7, -6, -6, -6, -6, -5, -5, -5, -5, -4, -4, -4, -4,
+    -3, -3, -3, -3, -2, -2, -2, -2, -1, -1, -1, -1, 0, 0, 0, 0,
+    1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4,
+    5, 5, 5, 5, 6, 6, 6, 6, 7, 7, 7, 7, 8, 8, 8, 8,
+    9, 9, 9, 9, 10, 10, 10, 10, 11, 11, 11, 12, 12, 12, 12, 13,
+    13, 13, 13, 14, 14, 14, 15, 15, 15, 15, 16, 16, 16, 17, 17, 17,
+    18, 18, 18, 19, 19, 19, 19, 20, 20, 20, 21, 21, 21, 22, 22, 22,
+    23, 23, 24, 24, 24, 25, 25, 25, 26, 26, 27, 27, 27, 28, 28, 29,
+    29, 29, 30, 30, 31, 31, 32, 32, 33, 33, 33, 34, 34, 35, 35, 36,
+    37, 37, 38, 38, 39, 39, 40, 41, 41, 42, 43, 43, 44, 45, 45, 46,
+    47, 48, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 59, 60, 61, 63,
+    64, 66, 67, 69, 71, 73, 76, 78, 81, 84, 88, 93, 99, 107, 119, 144
+};
+}  // namespace gbl

@@ -189,19 +189,30 @@ class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
     _games_per_visit = 128  # (a network leaf counts as 128 games)
 
     def __init__(self, evaluator: GobbletEvaluator, iterations: int = 256, explore: int = 16, noise: float = 0.0, seed: int = 0,
-                 env_base: int = 0, device=None, **kwargs: Any) -> None:
+                 env_base: int = 0, device=None, gumbel: dict | None = None, **kwargs: Any) -> None:
         """iterations: network leaves per decision (1 .. 512); explore: weight of the prior term of the selection key (0 .. 1024;
         the default is the best of the host-flavour sweep in profiles/r10/evaluator_policy.json); device: where the search runs
         (default: the evaluator's; the evaluator is copied there if it lives elsewhere).
 
         noise: the share in [0, 1] of a random row mixed into the ROOT's prior row, once per search (``gbl_tree_search_eval_noise``;
         the weight of the ABI is round(256 * noise)).  The row of board b of call k is keyed by (seed, env_base + b, k): ``call``
-        counts up once per ``compute_actions_from_state``.  With noise 0 the policy draws nothing."""
+        counts up once per ``compute_actions_from_state``.  With noise 0 the policy draws nothing.
+
+        gumbel: ``dict(considered=16, noise=True, visit_offset=50, scale=23)`` (any key may be left out) makes the ROOT follow the
+        Gumbel rule (``gbl_tree_search_gumbel``), the search for small budgets such as ``iterations=16``: Gumbel noise once per root
+        (keyed like the root noise; ``noise=False``: none, the policy draws nothing), the ``considered`` (1 .. 54) best actions by
+        noise + logit, sequential halving over them, the decision among the survivors.  ``visit_offset`` (0 .. 255) and ``scale``
+        (0 .. 64, in 1/16 of an octave per unit of value) are the paper's c_visit and c_scale; the defaults are its 50 and 1.0 nat.
+        ``last_target`` is then the completed-Q improved policy, uint8 (N, 54), and ``last_gumbel`` the noise, int16 (N, 54).  Not
+        together with ``noise``."""
         for name, val, lo, hi in (("iterations", iterations, 1, 512), ("explore", explore, 0, 1024)):
             if not lo <= int(val) <= hi:
                 raise ValueError(f"{name} must be in [{lo}, {hi}]")
         self.iterations, self.explore = int(iterations), int(explore)
         self.noise = noise_weight(noise)
+        self.gumbel = None if gumbel is None else gumbel_args(gumbel)
+        if self.gumbel is not None and self.noise:
+            raise ValueError("gumbel does not go with noise: the Gumbel row is the search's exploration")
         self.seed, self.env_base, self.call = int(seed), int(env_base), 0
         self.device = torch.device(evaluator.device if device is None else device)
         self.evaluator = evaluator if evaluator.device == self.device else evaluator.to(self.device)
@@ -211,6 +222,7 @@ class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
         # root's prior row as the network gives it, and as the root keeps it (the same row without noise)
         self.last_visits = self.last_wins = self.last_losses = self.last_nodes = self.last_action = None
         self.last_root_value = self.last_root_priors = self.last_root_mixed = None
+        self.last_target = self.last_gumbel = None  # (gumbel=: the target row uint8 (N, 54) and the noise int16 (N, 54))
 
     def _run(self, state, to_move, mask) -> torch.Tensor:
         n = state.shape[0]
@@ -221,8 +233,18 @@ class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
         rootp = torch.empty((n, nat.ACTIONS), dtype=torch.uint8, device=self.device)
         mixed = rootp
         ev = self.evaluator.as_struct()
+        target = gum = None
         with self._on_device():
-            if self.noise:
+            if self.gumbel is not None:
+                target, gum = torch.empty_like(rootp), torch.empty((n, nat.ACTIONS), dtype=torch.int16, device=self.device)
+                g = self.gumbel
+                nat.check(self._lib.gbl_tree_search_gumbel(
+                    state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), self.iterations, self.explore, g["considered"],
+                    g["noise"], g["visit_offset"], g["scale"], self.seed, self.env_base, self.call, visits.data_ptr(), wins.data_ptr(),
+                    losses.data_ptr(), act.data_ptr(), nodes.data_ptr(), rootv.data_ptr(), rootp.data_ptr(), target.data_ptr(),
+                    gum.data_ptr(), n, self._stream()), "gbl_tree_search_gumbel")
+                self.call += 1
+            elif self.noise:
                 mixed = torch.empty_like(rootp)
                 nat.check(self._lib.gbl_tree_search_eval_noise(
                     state.data_ptr(), to_move.data_ptr(), nat.ptr(mask), C.addressof(ev), self.iterations, self.explore, self.noise,
@@ -238,6 +260,7 @@ class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
         self.last_visits, self.last_wins, self.last_losses = visits, wins, losses
         self.last_nodes, self.last_action, self.last_root_value, self.last_root_priors = nodes, act, rootv, rootp
         self.last_root_mixed = mixed
+        self.last_target, self.last_gumbel = target, gum
         return act
 
 
@@ -318,3 +341,44 @@ def cap_full(seed: int, board_ids, ply_indices, full) -> torch.Tensor:
     words = _philox4x32_10([g & _M32, g >> 32, q >> 2, zero + nat.STREAM_CAP], int(seed) & _M32, (int(seed) >> 32) & _M32)
     r = torch.stack(words, dim=-1).gather(-1, (q & 3)[..., None])[..., 0]
     return (r >> 24) < share
+
+
+# ---- the Gumbel root rule's arguments and its noise restated in torch (include/gobblet_hip.h, "Gumbel root search") ------------------
+GUMBEL_DEFAULTS = dict(considered=16, noise=True, visit_offset=50, scale=23)
+# GT[k] = round(-ln(-ln((k + 1/2) / 256)) * 16 / ln 2): a standard Gumbel variate in 1/16 of an octave (csrc/gobblet_knobs.h holds the numbers)
+GUMBEL_TABLE = tuple(int(x) for x in np.rint(-np.log(-np.log((np.arange(256) + 0.5) / 256.0)) * 16.0 / math.log(2.0)))
+
+
+def gumbel_args(gumbel: dict) -> dict:
+    """``gumbel=dict(...)`` with the defaults filled in, as the ABI takes it: considered 1 .. 54, noise 0 / 1, visit_offset 0 .. 255,
+    scale 0 .. 64."""
+    if not isinstance(gumbel, dict) or set(gumbel) - set(GUMBEL_DEFAULTS):
+        raise ValueError("gumbel is a dict of considered / noise / visit_offset / scale")
+    kw = {**GUMBEL_DEFAULTS, **gumbel}
+    out = {"noise": int(bool(kw["noise"]))}
+    if kw["noise"] not in (0, 1, False, True):
+        raise ValueError("gumbel: noise is True or False")
+    for name, lo, hi in (("considered", 1, 54), ("visit_offset", 0, 255), ("scale", 0, 64)):
+        v = kw[name]
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"gumbel: {name} must be an integer in [{lo}, {hi}]")
+        out[name] = int(v)
+    return out
+
+
+def gumbel_row(seed: int, board_ids, ply) -> torch.Tensor:
+    """int16 (N, 54): the Gumbel values g of ``gbl_tree_search_gumbel`` / ``gbl_collect_search_gumbel`` (with noise) for boards
+    ``board_ids`` (N,) (= env_base + b) at call / ply index ``ply`` (an int or (N,)), for EVERY action: the entry points write them for
+    the root's candidates and 0 elsewhere.  On the device of ``board_ids``."""
+    g = torch.as_tensor(board_ids)
+    dev = g.device
+    g = g.to(torch.int64).reshape(-1)
+    n = g.shape[0]
+    q = torch.as_tensor(ply, device=dev).to(torch.int64).reshape(-1).expand(n)
+    a = torch.arange(nat.ACTIONS, device=dev, dtype=torch.int64)
+    blk = ((64 * q)[:, None] + a[None, 0::4]) >> 2            # one block per four actions: (N, 14)
+    zero = torch.zeros_like(blk)
+    words = _philox4x32_10([(g & _M32)[:, None] + zero, (g >> 32)[:, None] + zero, blk, zero + nat.STREAM_GUMBEL],
+                           int(seed) & _M32, (int(seed) >> 32) & _M32)
+    r = torch.stack(words, dim=2).reshape(n, 56)[:, :nat.ACTIONS] >> 24
+    return torch.tensor(GUMBEL_TABLE, device=dev, dtype=torch.int16)[r]

@@ -464,6 +464,14 @@ class BatchedGobblet:
         solver proves stays ``nat.HOW_PROVEN`` whatever the draw; ``cap_full`` recomputes the draws.  An absent ``cap``, or
         ``full=1``, keeps the entry points above.  Not with a "tablebase" side or ``judge=True``.
 
+        ``search=dict(..., gumbel=dict(considered=16, noise=True, visit_offset=50, scale=23))`` (``considered`` may be a pair, one per
+        side; 0: that side keeps the search above) is the Gumbel root search of an evaluator side (``gbl_collect_search_gumbel``), made
+        for small budgets such as ``iterations=16``: Gumbel noise once per root, the ``considered`` best actions by noise + logit, the
+        budget spent on them by sequential halving, and the completed-Q improved policy as the target -- "visits" holds that row (1 ..
+        255 on the candidates), so EVERY ply of such a side is a policy target for ``training_batch`` / ``ReplayBuffer.append``.
+        "how" is ``nat.HOW_GUMBEL``; ``sample_plies`` is not read for such a side (the noise is its exploration); ``gumbel_row``
+        recomputes the noise.  Not with ``solve_depth``, ``noise``, ``cap``, a "tablebase" side or ``judge=True``.
+
         A side "tablebase" (or a ``TablebaseGobbletPolicy`` instance, which supplies its table) plays from the exact table INSIDE the
         launch (``gbl_collect_search_tb``), against "tablebase", "evaluator" or "random": ``search=dict(..., tablebase=tb,
         tb_mode="result" | "shortest", tb_count=1, judge=False, allow_incomplete=False)``.  Its ply takes the probe's action
@@ -528,7 +536,9 @@ class BatchedGobblet:
             # a table side or the judge -> _tb (the noise entry point's list, then the table's); a playout cap -> _cap (that list,
             # then the cap's)
             cap = None if ep is None else ep.get("cap")
-            entry = "gbl_collect_search" + ("_tb" if tp is not None else "" if ep is None else "_cap" if cap is not None else
+            gum = None if ep is None else ep.get("gumbel")  # the Gumbel root rule -> _gumbel (the _eval list, then the rule's five)
+            entry = "gbl_collect_search" + ("_tb" if tp is not None else "" if ep is None else "_gumbel" if gum is not None else
+                                            "_cap" if cap is not None else
                                             "_noise" if any(ep["noise"]) else "_solve" if guarded else "_eval")
             if judged and "tb_value" not in f:
                 raise ValueError("judge=True needs buffers from trajectory_buffers(tablebase_outputs=True)")
@@ -539,7 +549,7 @@ class BatchedGobblet:
             if ep is None:
                 sides = [*sp["iterations"], *sp["playouts"], sp["max_plies"]]
             else:
-                solver, noise = not entry.endswith("_eval"), entry.endswith(("_noise", "_tb", "_cap"))
+                solver, noise = not entry.endswith(("_eval", "_gumbel")), entry.endswith(("_noise", "_tb", "_cap"))
                 structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
                 args += [nat.ptr(f.get(k)) for k in ("root_value", "priors") + (("outcomes", "proven") if solver else ())]
                 sides = [*[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
@@ -551,6 +561,7 @@ class BatchedGobblet:
                 *(() if tp is None else (tp["inventory"], tp["aux"], tp["table"], tp["mode"], tp["count"],
                                          *(nat.ptr(f.get(k)) if judged else None for k in ("tb_outcomes", "tb_value", "tb_played")))),
                 *(() if cap is None or tp is not None else (*cap["fast_iterations"], *cap["share"])),
+                *(() if gum is None else (*gum["considered"], gum["noise"], gum["visit_offset"], gum["scale"])),
                 self._stream()), entry)
         elif policies is not None:
             try:
@@ -663,9 +674,10 @@ class BatchedGobblet:
         if len(sides) != 2 or not any(evs):
             return None
         from .evaluator_policy import noise_weight
-        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0, noise=0.0, cap=None),  # EvaluatorTreeSearchGobbletPolicy's defaults
+        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0, noise=0.0, cap=None,
+                                  gumbel=None),  # EvaluatorTreeSearchGobbletPolicy's defaults
                              search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies / "
-                             "solve_depth / noise / cap)")
+                             "solve_depth / noise / cap / gumbel)")
         its, nets, deps, nzs = self._pair(kw["iterations"]), self._pair(kw["evaluator"]), self._pair(kw["solve_depth"]), self._pair(kw["noise"])
         if len(its) != 2 or len(nets) != 2 or len(deps) != 2 or len(nzs) != 2:
             raise ValueError("search: iterations / evaluator / solve_depth / noise are a value or a pair, one per side")
@@ -673,6 +685,9 @@ class BatchedGobblet:
         codes, explores = [], []
         for m, x in enumerate(sides):
             if isinstance(x, EvaluatorTreeSearchGobbletPolicy):
+                if x.gumbel is not None:
+                    raise ValueError("a policy instance with gumbel= does not bring its rule into collect(): pass 'evaluator' sides and "
+                                     "search=dict(gumbel=...)")
                 its[m], nets[m], nzs[m] = x.iterations, x.evaluator, x.noise
                 explores.append(x.explore)
                 codes.append(nat.POLICY_EVAL_TREE)
@@ -711,8 +726,34 @@ class BatchedGobblet:
                 raise ValueError("search: iterations must be in [1, 512]")
         if not (0 <= explore <= 1024 and int(kw["sample_plies"]) >= 0):
             raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
+        gumbel = self._gumbel_params(kw["gumbel"], codes)
+        if gumbel is not None and (any(deps) or any(nzs) or kw["cap"] is not None):
+            raise ValueError("search: gumbel does not go with solve_depth, noise or cap (gbl_collect_search_gumbel has none of them)")
         return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
-                    solve_depth=deps, noise=nzs, cap=self._cap_params(kw["cap"], codes, its))
+                    solve_depth=deps, noise=nzs, cap=self._cap_params(kw["cap"], codes, its), gumbel=gumbel)
+
+    def _gumbel_params(self, gumbel, codes):
+        """``search=dict(gumbel=dict(considered=, noise=, visit_offset=, scale=))`` as ``gbl_collect_search_gumbel`` takes it --
+        ``considered`` per side (0: that side keeps the search above), the rest for both -- or None where no evaluator side follows
+        the rule (an absent ``gumbel``, ``considered=0``): the call keeps its entry point."""
+        from .evaluator_policy import gumbel_args
+        if gumbel is None:
+            return None
+        if not isinstance(gumbel, dict):
+            raise ValueError("search: gumbel is a dict of considered / noise / visit_offset / scale")
+        considered = self._pair(gumbel.get("considered", 16))
+        if len(considered) != 2:
+            raise ValueError("search: gumbel's considered is a value or a pair, one per side")
+        rest = gumbel_args(dict(gumbel, considered=1))
+        for m in range(2):
+            if codes[m] != nat.POLICY_EVAL_TREE:
+                considered[m] = 0
+            elif isinstance(considered[m], bool) or not 0 <= int(considered[m]) <= 54:
+                raise ValueError("search: gumbel's considered must be in [0, 54]")
+            considered[m] = int(considered[m])
+        if not any(considered):
+            return None
+        return dict(considered=considered, noise=rest["noise"], visit_offset=rest["visit_offset"], scale=rest["scale"])
 
     def _cap_params(self, cap, codes, its):
         """``search=dict(cap=dict(fast_iterations=, full=))`` as ``gbl_collect_search_cap`` takes it -- a fast budget and a share
@@ -777,12 +818,14 @@ class BatchedGobblet:
             raise ValueError("search: tb_count must be in [1, %d]" % nat.TB_TARGET_MAX_COUNT)
         if rest.get("cap") is not None:
             raise ValueError("search: cap does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no playout cap)")
+        if rest.get("gumbel") is not None:
+            raise ValueError("search: gumbel does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no Gumbel rule)")
         others = ["random" if t else x for t, x in zip(tbs, sides)]
         ep = self._evaluator_params(others, rest or None)
         if ep is None:  # no evaluator side: the table against itself or against "random"
             if not all(self._is_random(x) for x in others):
                 raise ValueError("policies: the table plays against 'tablebase', 'evaluator' or 'random' inside one launch (not %r)" % (sides,))
-            unknown = set(rest) - {"sample_plies", "evaluator", "iterations", "explore", "solve_depth", "noise", "cap"}
+            unknown = set(rest) - {"sample_plies", "evaluator", "iterations", "explore", "solve_depth", "noise", "cap", "gumbel"}
             if unknown:
                 raise ValueError("search: unknown keys %s" % sorted(unknown))
             if int(rest.get("sample_plies", 0)) < 0:

@@ -108,6 +108,11 @@ int gbl_cpu_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, c
                                    int explore, int noise, uint64_t seed, uint64_t env_base, uint32_t call, int32_t *visits_out,
                                    int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out,
                                    int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream);
+int gbl_cpu_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                               int explore, int considered, int gumbel_noise, int visit_offset, int scale, uint64_t seed,
+                               uint64_t env_base, uint32_t call, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out,
+                               int32_t *action_out, int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out,
+                               uint8_t *target_out, int16_t *gumbel_out, int64_t n, void *stream);
 int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                            int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                            int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
@@ -148,6 +153,14 @@ int gbl_cpu_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int
                                const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int noise0,
                                int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
                                int fast_iterations0, int fast_iterations1, int full_share0, int full_share1, void *stream);
+int gbl_cpu_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                  int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                  int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                                  int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
+                                  uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
+                                  int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                                  int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, int considered0,
+                                  int considered1, int gumbel_noise, int visit_offset, int scale, void *stream);
 int gbl_cpu_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
                               int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
                               int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,

@@ -428,6 +428,56 @@ int gbl_tree_search_eval_noise(const int8_t *state, const int8_t *to_move, const
                                int32_t *wins_out, int32_t *losses_out, int32_t *action_out, int32_t *nodes_out, int32_t *root_value_out,
                                uint8_t *root_priors_out, uint8_t *root_mixed_out, int64_t n, void *stream);
 
+/* Gumbel root search (no counterpart in the reference): gbl_tree_search_eval with the ROOT's selection, decision and policy target
+ * replaced by the root rule of "Policy improvement by planning with Gumbel" (Danihelka, Guez, Schrittwieser, Silver, ICLR 2022) --
+ * Gumbel noise once per root, the top-m actions by g + logit, the budget spent on them by sequential halving, and the completed-Q
+ * improved policy as a dense target -- in integers, so that the kernel, the host flavour and a restatement of this text agree byte
+ * for byte.  It is made for small budgets: 8 .. 16 iterations over up to 54 candidates.
+ * Parameters: gbl_tree_search_eval's, plus `considered` in 1 .. 54, `gumbel_noise` in {0, 1}, `visit_offset` in 0 .. 255, `scale` in
+ * 0 .. 64, and seed, the board id g = env_base + b and q = call as in gbl_tree_search_eval_noise.  C is the root's candidate set, o
+ * the root evaluation's outputs and q_root its value, exactly as gbl_tree_search_eval computes them.  Everything below is for a in C.
+ *   Gumbel row.  gumbel_noise == 0: g_a = 0 and nothing is drawn.  gumbel_noise == 1: g_a = GT[r_a >> 24], r_a = the generator word
+ *     of (seed, g, ply index 64 q + a, stream 10) -- gbl_sample's generator, the Philox block with counter (g_lo, g_hi, (64 q + a) >> 2,
+ *     10), word a & 3; stream 10 is the rule's own.  GT[k] = round(-ln(-ln((k + 1/2) / 256)) * 16 / ln 2), k = 0 .. 255: a standard Gumbel
+ *     variate in the logits' unit of 1/16 of an octave (no entry lies within 0.003 of a rounding tie):
+ *     -42 -38 -35 -34 -32 -31 -30 -29 -28 -28 -27 -26 -26 -25 -24 -24 -23 -23 -22 -22 -21 -21 -21 -20 -20 -19 -19 -19 -18 -18 -17 -17
+ *     -17 -16 -16 -16 -15 -15 -15 -14 -14 -14 -14 -13 -13 -13 -12 -12 -12 -11 -11 -11 -11 -10 -10 -10 -10 -9 -9 -9 -8 -8 -8 -8
+ *     -7 -7 -7 -7 -6 -6 -6 -6 -5 -5 -5 -5 -4 -4 -4 -4 -3 -3 -3 -3 -2 -2 -2 -2 -1 -1 -1 -1 0 0 0 0
+ *     1 1 1 1 2 2 2 2 3 3 3 3 4 4 4 4 5 5 5 5 6 6 6 6 7 7 7 7 8 8 8 8
+ *     9 9 9 9 10 10 10 10 11 11 11 12 12 12 12 13 13 13 13 14 14 14 15 15 15 15 16 16 16 17 17 17
+ *     18 18 18 19 19 19 19 20 20 20 21 21 21 22 22 22 23 23 24 24 24 25 25 25 26 26 27 27 27 28 28 29
+ *     29 29 30 30 31 31 32 32 33 33 33 34 34 35 35 36 37 37 38 38 39 39 40 41 41 42 43 43 44 45 45 46
+ *     47 48 48 49 50 51 52 53 54 55 56 57 59 60 61 63 64 66 67 69 71 73 76 78 81 84 88 93 99 107 119 144
+ *   Root logits.  l_a = o_a >> shift_p;  L_a = -min(max over C of l - l_a, 255) -- the prior rule's own cap.
+ *   Completed value.  mean_a = ((W_c - L_c + n_c P) << 15) / (n_c P) of the root's child c of a (the selection key's first term, 0 ..
+ *     65536, for the root's mover) if a has one, else mean_a = 32768 + 256 q_root.  maxN = the largest n among the root's children
+ *     (0 without one).  sigma_a = ((visit_offset + maxN) * scale * mean_a) >> 16, inside uint32 (767 * 64 * 65536 < 2^32).
+ *   Considered set.  m = min(considered, |C|); A = the m actions of C with the largest g_a + L_a, ties to the lower action;
+ *     P = max(1, ceil(log2 m)); the visit target starts at T = max(1, iterations div (P m)).
+ *   Iteration i = 0 .. iterations - 1.  Before its selection: if |A| > 2 and every action of A has a root child with n >= T, HALVE --
+ *     keep the max(2, ceil(|A| / 2)) actions of A with the largest g_a + L_a + sigma_a (sigma evaluated now), ties to the lower
+ *     action, then T += max(1, iterations div (P |A|)) with the new |A|.  At most one halving per iteration; none once |A| <= 2.
+ *     Select: at the ROOT take the action of A with the fewest visits (0 without a child), ties to the larger g_a + L_a, then to the
+ *     lower action.  Everywhere below the root, and for expansion, evaluation and back-up, the text of gbl_tree_search_eval holds
+ *     unchanged.  The search stops after `iterations`, wherever the schedule stands.
+ *   Decision.  Among A: the most visits, then the largest g_a + L_a + sigma_a at the end, then the lowest action.
+ *   Target row.  t_a = L_a + sigma_a (no g; sigma at the end, an unvisited action through the root's value);
+ *     target_a = 1 + (e_a * 254) / (sum over C of e), e_a = T[d & 15] >> (d >> 4) with d = min(max over C of t - t_a, 255): the prior
+ *     rule over t, a byte in 1 .. 255; 0 outside C.
+ *   A root without a candidate: nothing is drawn or searched, action_out = -1, the target and the Gumbel row are zeros, the rest as
+ *     gbl_tree_search_eval.
+ * Outputs (each may be NULL): those of gbl_tree_search_eval -- visits_out / wins_out / losses_out are the raw counts of the root's
+ * children, action_out the decision above -- and target_out uint8[n][54], gumbel_out int16[n][54] = g_a (0 outside C; 2-byte aligned).
+ * The rule keeps two registers per lane and A as a mask: the LDS is gbl_tree_search_eval's.
+ * Errors, in this order: n < 0, call >= 2^24, env_base + n > 2^42, the evaluator's fields, iterations, explore (all as
+ * gbl_tree_search_eval_noise), then considered, gumbel_noise, visit_offset, scale out of range (GBL_ERR_ARG); with n == 0 the call
+ * returns here; then the pointers and alignments of gbl_tree_search_eval.  Allocates nothing. */
+int gbl_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int8_t *mask, const gbl_evaluator *ev, int iterations,
+                           int explore, int considered, int gumbel_noise, int visit_offset, int scale, uint64_t seed, uint64_t env_base,
+                           uint32_t call, int32_t *visits_out, int32_t *wins_out, int32_t *losses_out, int32_t *action_out,
+                           int32_t *nodes_out, int32_t *root_value_out, uint8_t *root_priors_out, uint8_t *target_out, int16_t *gumbel_out,
+                           int64_t n, void *stream);
+
 /* Exact bounded-depth solver (no counterpart in the reference): the full-width game tree of every board to `depth` plies, the proven
  * result of every root action.  Integer-only and draws nothing: the kernel, the host flavour and a restatement of this text agree
  * byte for byte.
@@ -680,6 +730,33 @@ int gbl_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t
                            const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int noise0,
                            int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
                            int fast_iterations0, int fast_iterations1, int full_share0, int full_share1, void *stream);
+
+/* Self-play with the Gumbel root search: gbl_collect_search_eval with one `considered` per side, considered0 / considered1 in 0 .. 54
+ * for player_1 / player_2, and gumbel_noise / visit_offset / scale for both.  A side's value is ignored unless that side is EVAL_TREE;
+ * considered_m == 0 means that side searches exactly as in gbl_collect_search_eval, and with both 0 every array is
+ * gbl_collect_search_eval's, bit for bit (gumbel_noise, visit_offset and scale are then not read).  The ply q of an EVAL_TREE mover m
+ * with considered_m > 0 is
+ *   search   gbl_tree_search_gumbel(state, to_move, mask = NULL, ev_m, iterations_m, explore, considered_m, gumbel_noise,
+ *            visit_offset, scale, seed, env_base, call = q) of the board's current position.
+ *   action   that search's action_out.  sample_plies is not read for this side: the Gumbel row is its exploration.
+ *   how      GBL_HOW_GUMBEL.
+ *   visits   visits_traj holds the TARGET row target_out, an int16 in 1 .. 255 on C and 0 elsewhere: gbl_outcome_targets,
+ *            gbl_training_batch, gbl_replay_append and gbl_train_step read it unchanged as visits / sum.
+ *   value, nodes, root_value and priors are what gbl_collect_search_eval writes for a search (value from the raw wins and losses).
+ *   a root without a candidate: action -1, stepped per illegal_mode, the row zeros, how = GBL_HOW_GUMBEL.
+ * The Gumbel row moves with *ply_dev as every other draw of the window does; a consumer recomputes it from (seed, g, q).  Errors are
+ * gbl_collect_search_eval's in its order; after them (before the n == 0 return) GBL_ERR_ARG for a considered outside 0 .. 54 on an
+ * EVAL_TREE side, then, where a side follows the rule, for gumbel_noise, visit_offset, scale out of range.  The solver guard, root
+ * noise, the playout cap and the tablebase are not combined with the rule.  Allocates nothing; the LDS is gbl_collect_search_eval's. */
+#define GBL_HOW_GUMBEL 10
+int gbl_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                              int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                              int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                              int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
+                              uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
+                              int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
+                              int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, int considered0,
+                              int considered1, int gumbel_noise, int visit_offset, int scale, void *stream);
 
 /* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
  * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:

@@ -1,0 +1,562 @@
+"""The Gumbel root search on the host flavour (no GPU): gbl_cpu_tree_search_gumbel and gbl_cpu_collect_search_gumbel against the
+restatement of the header text (tests/gumbel_restatement.py), byte for byte -- and, so that a wrong rule cannot agree with itself,
+checks that do not rest on the restatement: the table against its formula, the schedule's visit counts worked out from the rule's text
+by hand, the Gumbel-max property against the exact distribution of the table, dial networks whose searches are known in closed form,
+the target row's edges, the consumers of a window, the argument errors of both flavours in their order and the Python surface."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+
+import gobblet_rl_amd as G
+from gobblet_rl_amd import _native as nat
+from tests import evaluator_restatement as R
+from tests import gumbel_restatement as GR
+from tests import solver_restatement as SR
+from tests.gumbel_harness import GUMBEL_NAMES, PAIRS, call_args, host_collect_gumbel, rule_boards
+from tests.search_harness import run
+from tests.search_harness import same as same_arrays
+from tests.selfplay_harness import _evaluator, host_collect, same
+from tests.test_selfplay_solve import EXPLORE, fixture_boards, smoke_net
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED, ENV_BASE = 0xFEDCBA9876543210, (1 << 41) + 77
+GUMBEL = "tree_search_gumbel"
+
+
+@pytest.fixture(scope="module")
+def cpu():
+    L = nat.cpu_raw()
+    L.gbl_cpu_set_threads(8)
+    yield L
+    L.gbl_cpu_set_threads(0)
+
+
+@pytest.fixture(scope="module")
+def roots():
+    """130 roots (state, to_move, mask, {candidates: board}): 54, 27, 2, 1 and 0 candidates among them."""
+    st, tm, _ = fixture_boards(120)
+    return rule_boards((st, tm))
+
+
+@pytest.fixture(scope="module")
+def nets():
+    return smoke_net(), R.random_net(128, 77)
+
+
+def formula():
+    return -np.log(-np.log((np.arange(256) + 0.5) / 256.0)) * 16.0 / math.log(2.0)
+
+
+# ---- 1. the table --------------------------------------------------------------------------------------------------------------------------
+def test_the_table_is_its_formula():
+    x = formula()
+    assert np.abs(x - np.floor(x) - 0.5).min() > 1e-3  # no entry lies within 10^-3 of a rounding tie: numpy.rint pins it
+    exp = np.rint(x).astype(np.int64)
+    knobs = open(os.path.join(ROOT, "gobblet-rl_amd", "csrc", "gobblet_knobs.h")).read()
+    body = re.search(r"kGumbelTable\[256\] = \{(.*?)\};", knobs, re.S).group(1)
+    assert np.array_equal(np.array([int(v) for v in body.replace("\n", " ").split(",")]), exp)
+    header = re.sub(r"\n \*", " ", open(os.path.join(ROOT, "include", "gobblet_hip.h")).read())
+    printed = re.search(r"rounding tie\):((?:\s+-?\d+){256})\s", header).group(1)
+    assert np.array_equal(np.array([int(v) for v in printed.split()]), exp)
+    assert tuple(exp) == GR.GT == G.evaluator_policy.GUMBEL_TABLE
+    assert exp[:4].tolist() == [-42, -38, -35, -34] and exp[-4:].tolist() == [99, 107, 119, 144] and (np.diff(exp) >= 0).all()
+
+
+def test_every_table_entry_comes_out_of_the_entry_point(cpu):
+    """gumbel_out over 4 096 empty boards holds GT at the top byte of the oracle's Philox word, and every one of the 256 entries shows."""
+    n = 4096
+    st, tm = np.zeros((n, 27), np.int8), np.zeros(n, np.int8)
+    got = run(GUMBEL, "cpu", st, tm, None, (1, 0, 54, 1, 0, 0, SEED, ENV_BASE, 9), R.zero_net(64), keep=("gumbel",))["gumbel"]
+    top = np.array([[GR.word(SEED, ENV_BASE + b, 64 * 9 + a, GR.STREAM_GUMBEL) >> 24 for a in range(54)] for b in range(0, n, 64)])
+    assert np.array_equal(got[::64], np.rint(formula()).astype(np.int16)[top])
+    assert len(np.unique(top)) == 256
+    assert np.array_equal(got, G.gumbel_row(SEED, ENV_BASE + torch.arange(n), 9).numpy())
+
+
+# ---- 2. the restatement --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pair", PAIRS)
+@pytest.mark.parametrize("k", [0, 1])
+def test_host_flavour_equals_restatement(cpu, roots, nets, k, pair):
+    st, tm, mask, where = roots
+    considered, iterations = pair
+    for noise in (0, 1):
+        for scale in (0, 23):
+            params = (iterations, EXPLORE, considered, noise, 50, scale, SEED, ENV_BASE, 5)
+            got = run(GUMBEL, "cpu", st, tm, mask, params, nets[k])
+            same_arrays(got, GR.restate_search_gumbel(nets[k], st, tm, mask, *params))
+    assert tuple(got) == GUMBEL_NAMES
+    none, one = where[0], where[1]
+    assert got["action"][none] == -1 and got["nodes"][none] == 1 and not got["target"][none].any() and not got["gumbel"][none].any()
+    assert got["visits"][one].sum() == iterations and got["target"][one].max() == 255 and (got["target"][one] > 0).sum() == 1
+    cand = (oracle.batch_legal_mask(st, tm) != 0) & (mask != 0)
+    assert ((got["target"] > 0) == cand).all() and ((got["gumbel"] != 0) <= cand).all()
+    # every output is optional
+    same_arrays(run(GUMBEL, "cpu", st[:9], tm[:9], mask[:9], params, nets[k], keep=("action", "gumbel")),
+                {x: got[x][:9] for x in ("action", "gumbel")})
+
+
+# ---- 3. the schedule, from the rule's text alone ---------------------------------------------------------------------------------------------
+SCHEDULE = {(4, 16): [6, 6, 2, 2], (16, 64): [15, 15, 7, 7, 3, 3, 3, 3] + [1] * 8, (3, 8): [4, 3, 1], (2, 8): [4, 4], (1, 8): [8]}
+
+
+@pytest.mark.parametrize("pair", sorted(SCHEDULE))
+def test_the_sorted_root_visits_depend_on_the_schedule_alone(cpu, roots, nets, pair):
+    st, tm, mask, _ = roots
+    considered, iterations = pair
+    enough = ((oracle.batch_legal_mask(st, tm) != 0) & (mask != 0)).sum(1) >= considered
+    assert enough.sum() > 100
+    for noise, scale, k in ((1, 23, 0), (0, 0, 1), (1, 64, 1)):
+        got = run(GUMBEL, "cpu", st, tm, mask, (iterations, EXPLORE, considered, noise, 50, scale, SEED, ENV_BASE, 2), nets[k], keep=("visits",))
+        rows = -np.sort(-got["visits"][enough], axis=1)[:, :considered]
+        assert (rows == np.array(SCHEDULE[pair])).all() and (got["visits"].sum(1)[enough] == iterations).all()
+
+
+def test_more_considered_than_candidates(cpu, roots, nets):
+    """(54, 16) on a 27-candidate root: m = 27, P = 5, T = 1 -- sixteen actions get one visit each and nothing is ever halved."""
+    st, tm, mask, where = roots
+    b = where[27]
+    got = run(GUMBEL, "cpu", st[b:b + 1], tm[b:b + 1], mask[b:b + 1], (16, EXPLORE, 54, 1, 50, 23, SEED, ENV_BASE, 2), nets[0])
+    assert sorted(got["visits"][0][got["visits"][0] > 0].tolist()) == [1] * 16
+
+
+# ---- 4. the Gumbel-max property -------------------------------------------------------------------------------------------------------------
+def test_gumbel_max_property(cpu):
+    """scale 0, considered 54, noise on, the empty board under 4 096 board ids: sigma is 0, so the decision is argmax(g + L) (the lowest
+    action on ties), a sample of softmax(L ln 2 / 16) as far as a 256-entry table can make one.  The exact law of that argmax follows
+    from the table by enumeration; the counts lie within 5 binomial standard deviations of it, action by action.  L stays within two
+    octaves, so that no action is rare enough for the normal bound to be the wrong one."""
+    n = 4096
+    logits = -((7 * np.arange(54)) % 33).astype(np.int64)  # L_a = logits[a]: the largest is 0
+    net = R.logit_dial(logits + 500, shift_p=3, low_bits=5)
+    st, tm = np.zeros((n, 27), np.int8), np.zeros(n, np.int8)
+    got = run(GUMBEL, "cpu", st, tm, None, (8, EXPLORE, 54, 1, 50, 0, SEED, ENV_BASE, 11), net, keep=("action", "gumbel", "target"))
+    g = G.gumbel_row(SEED, ENV_BASE + torch.arange(n), 11).numpy().astype(np.int64)
+    assert np.array_equal(got["gumbel"], g)
+    assert np.array_equal(got["action"], np.argmax(g + logits[None, :], axis=1))  # (numpy's argmax takes the first of equals)
+    # the exact distribution: P(a) = sum over k of 1/256 * prod over b != a of P(g_b + L_b < GT[k] + L_a, or <= for b > a)
+    gt = np.sort(np.rint(formula()).astype(np.int64))
+    p = np.zeros(54)
+    for a in range(54):
+        v = gt + logits[a]
+        below = np.ones(256)
+        for b in range(54):
+            if b != a:
+                below *= np.searchsorted(gt, v - logits[b], side="left" if b < a else "right") / 256.0
+        p[a] = below.mean()
+    assert abs(p.sum() - 1.0) < 1e-12 and p.min() > 0.004
+    counts = np.bincount(got["action"], minlength=54)
+    sd = np.sqrt(n * p * (1.0 - p))
+    assert (np.abs(counts - n * p) <= 5.0 * sd).all(), np.abs(counts - n * p) / sd
+    soft = 2.0 ** (logits / 16.0)
+    soft /= soft.sum()
+    print("total variation, exact law of the table's argmax against the float softmax: %.5f" % (0.5 * np.abs(p - soft).sum()))
+    # scale 0: the target row is the prior row itself (sigma = 0, t = L)
+    assert np.array_equal(got["target"][0], R.exact_priors(logits, np.ones(54, bool))[0])
+
+
+# ---- 5. dial networks ------------------------------------------------------------------------------------------------------------------------
+def test_an_action_that_wins_at_once_is_decided_whenever_it_is_considered(cpu):
+    """Flat logits and value 0: every leaf's mean is 32768 but a won child's 65536, so sigma lifts an action that wins at once over every
+    Gumbel value ((50 + maxN) * 23 / 2 > 575, the g's span 186).  The position has four such actions (any piece onto square 2); one is
+    in A iff its g is among the 16 largest (the lower action on ties).  A winner is decided whenever one is considered, the considered
+    winners -- and nobody else -- carry the largest target byte, and a winner outside A goes through the root's value like the rest."""
+    n = 512
+    s, m = SR.play(SR.WIN_SEQ)
+    st, tm = np.repeat(s[None], n, 0), np.full(n, m, np.int8)
+    got = run(GUMBEL, "cpu", st, tm, None, (16, EXPLORE, 16, 1, 50, 23, SEED, ENV_BASE, 3), R.zero_net(64))
+    legal = np.flatnonzero(oracle.legal_mask(s, m)).tolist()
+    mine = 1 if m == 0 else -1
+    winners = {a for a in legal if oracle.check_for_winner(oracle.play_turn(s, m, a)) == mine}
+    assert SR.WIN_ACTION in winners and len(winners) == 4
+    g = G.gumbel_row(SEED, ENV_BASE + torch.arange(n), 3).numpy().astype(np.int64)
+    some = 0
+    for b in range(n):
+        considered = winners & set(sorted(legal, key=lambda a: (-g[b, a], a))[:16])
+        assert (int(got["action"][b]) in winners) == bool(considered), b
+        if considered:
+            some += 1
+            row = got["target"][b]
+            assert int(got["action"][b]) in considered and set(np.flatnonzero(row == row.max()).tolist()) == considered
+            assert all(got["wins"][b, a] == 128 * got["visits"][b, a] > 0 for a in considered)
+    assert n // 10 < some < n - n // 10  # (both cases occur)
+
+
+@pytest.mark.parametrize("top", [0, 17, 53])
+def test_one_considered_action_without_noise_takes_every_iteration(cpu, top):
+    net, _ = R.distance_dial(top, rotation=top)
+    st, tm, mask = R.dial_boards(SR.play(SR.UNCOVER_SEQ), top)
+    got = run(GUMBEL, "cpu", st, tm, mask, (12, EXPLORE, 1, 0, 50, 23, 0, 0, 0), net)
+    for b in range(len(st)):
+        cand = (oracle.legal_mask(st[b], int(tm[b])) != 0) & (mask[b] != 0)
+        high = max(int(net.b2[a]) for a in np.flatnonzero(cand))  # (shift_p = 0: l_a = b2[a]; the dial has actions AT the top logit and distances that cap at 255: ties to the lower action)
+        best = min(np.flatnonzero(cand), key=lambda a: (min(high - int(net.b2[a]), 255), a))
+        assert got["visits"][b, best] == 12 and got["visits"][b].sum() == 12 and got["action"][b] == best
+        assert not got["gumbel"][b].any()
+
+
+# ---- 6. the target row's edges ------------------------------------------------------------------------------------------------------------------
+def exact_target(L, sigma):
+    """The header's sentence once more in exact integers, from {a: L_a} and {a: sigma_a}."""
+    t = {a: L[a] + sigma[a] for a in L}
+    top = max(t.values())
+    e = {}
+    for a in t:
+        d = min(top - t[a], 255)
+        e[a] = int(math.floor(65536 * 2.0 ** (-(d % 16) / 16) + 0.5)) // (2 ** (d // 16))
+    row = np.zeros(54, np.uint8)
+    for a in t:
+        row[a] = 1 + (254 * e[a]) // sum(e.values())
+    return row
+
+
+@pytest.mark.parametrize("q_raw", [-128, -37, 0, 90, 128])
+def test_an_unvisited_action_uses_the_root_value(cpu, q_raw):
+    """considered = 1 on the empty board: one child is visited, 53 actions go through the root's q.  The visited child's mean comes from
+    the raw wins / losses / visits the entry point writes, by the header's formula."""
+    logits = -(np.arange(54) % 7).astype(np.int64) * 5
+    net = R.logit_dial(logits + 100, o54=q_raw << 2, shift_v=2)
+    st, tm = np.zeros((1, 27), np.int8), np.zeros(1, np.int8)
+    for vo, scale in ((50, 23), (0, 64), (255, 1)):
+        got = run(GUMBEL, "cpu", st, tm, None, (6, EXPLORE, 1, 0, vo, scale, 0, 0, 0), net)
+        assert got["root_value"][0] == q_raw and got["visits"][0, 0] == 6 and got["visits"][0].sum() == 6
+        W, Lo = int(got["wins"][0, 0]), int(got["losses"][0, 0])
+        mean = {a: 32768 + 256 * q_raw for a in range(54)}
+        mean[0] = ((W - Lo + 6 * 128) << 15) // (6 * 128)
+        sigma = {a: ((vo + 6) * scale * mean[a]) >> 16 for a in range(54)}
+        assert np.array_equal(got["target"][0], exact_target({a: int(logits[a]) for a in range(54)}, sigma)), (vo, scale)
+
+
+def test_sigma_at_its_largest_stays_inside_uint32(cpu):
+    """visit_offset 255, scale 64, 512 iterations under one considered action that wins at once: (255 + 512) * 64 * 65536 = 3 217 031 168,
+    above 2^31 and below 2^32; sigma = 49 088, every other action lies more than 255 below and keeps the floor byte."""
+    s, m = SR.play(SR.WIN_SEQ)
+    logits = np.zeros(54, np.int64)
+    logits[SR.WIN_ACTION] = 9
+    got = run(GUMBEL, "cpu", s[None], np.array([m], np.int8), None, (512, EXPLORE, 1, 0, 255, 64, 0, 0, 0), R.logit_dial(logits))
+    assert got["visits"][0, SR.WIN_ACTION] == 512 and got["wins"][0, SR.WIN_ACTION] == 512 * 128 and got["action"][0] == SR.WIN_ACTION
+    legal = np.flatnonzero(oracle.legal_mask(s, m))
+    sigma = {int(a): (767 * 64 * 32768) >> 16 for a in legal}
+    sigma[SR.WIN_ACTION] = (767 * 64 * 65536) >> 16
+    assert sigma[SR.WIN_ACTION] == 49088 and 767 * 64 * 65536 >= 1 << 31
+    row = exact_target({int(a): int(logits[a]) - 9 for a in legal}, sigma)
+    assert np.array_equal(got["target"][0], row) and row[SR.WIN_ACTION] == 254 and (row[legal] >= 1).all()
+
+
+# ---- 7. self-play -------------------------------------------------------------------------------------------------------------------------------
+T = 6
+
+
+@pytest.fixture(scope="module")
+def boards():
+    """130 boards: 40 empty, then the midgame fixture, some inside the sampled plies."""
+    st, tm, turn = fixture_boards(90)
+    return (np.ascontiguousarray(np.concatenate([np.zeros((40, 27), np.int8), st])), np.concatenate([np.zeros(40, np.int8), tm]),
+            np.concatenate([np.zeros(40, np.int32), turn % 6]).astype(np.int32))
+
+
+def composed_loop(cpu, st, tm, turn, T_, pols, nets, its, considered, noise, vo, scale, X, sample_plies, seed, env_base, ply0):
+    """gbl_cpu_tree_search_gumbel (a Gumbel side) or gbl_cpu_tree_search_eval and the stream-4 draw (a PUCT side) or the stream-0 sample (a
+    RANDOM side), then gbl_cpu_step_into, ply by ply."""
+    from tests.test_playout_policy import sample_stream
+    from tests.test_selfplay_search import STREAM_VISIT, visits_draw
+    n = len(st)
+    s, m, d, tn = st.copy(), tm.copy(), np.zeros(n, np.int8), turn.astype(np.int32).copy()
+    plies = []
+    for t in range(T_):
+        q = ply0 + t
+        act, vis, val, nod = np.zeros(n, np.int32), np.zeros((n, 54), np.int16), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        rv, pri, how = np.zeros(n, np.int32), np.zeros((n, 54), np.uint8), np.zeros(n, np.int8)
+        legal = oracle.batch_legal_mask(s, m)
+        for side in (0, 1):
+            idx = np.flatnonzero(m == side)
+            if not len(idx):
+                continue
+            if pols[side] != "eval":
+                for b in idx:
+                    act[b] = sample_stream(legal[b], seed, env_base + int(b), q, 0)
+                continue
+            for b in idx:  # (a board at a time: the call's env_base is the board's id)
+                if considered[side] > 0:
+                    o = run(GUMBEL, "cpu", s[b:b + 1], m[b:b + 1], None,
+                            (its[side], X, considered[side], noise, vo, scale, seed, env_base + int(b), q), nets[side])
+                    vis[b], act[b], how[b] = o["target"][0], o["action"][0], nat.HOW_GUMBEL
+                else:
+                    o = run("tree_search_eval", "cpu", s[b:b + 1], m[b:b + 1], None, (its[side], X), nets[side])
+                    vis[b] = o["visits"][0]
+                    if tn[b] < sample_plies:
+                        act[b], how[b] = visits_draw(o["visits"][0], GR.word(seed, env_base + int(b), q, STREAM_VISIT)), nat.HOW_SEARCH_SAMPLED
+                    else:
+                        act[b], how[b] = o["action"][0], nat.HOW_SEARCH
+                val[b], nod[b], rv[b], pri[b] = (o["wins"][0] - o["losses"][0]).sum(), o["nodes"][0], o["root_value"][0], o["root_priors"][0]
+        mover = m.copy()
+        win, rew = np.zeros(n, np.int8), np.zeros((n, 2), np.int8)
+        mask_, obs = np.zeros((n, 54), np.int8), np.zeros((n, 117), np.int8)
+        rc = cpu.gbl_cpu_step_into(s.ctypes.data, m.ctypes.data, d.ctypes.data, act.ctypes.data, win.ctypes.data, rew.ctypes.data,
+                                   mask_.ctypes.data, obs.ctypes.data, tn.ctypes.data, None, None, None, n, nat.ILLEGAL_NOOP, 1, None)
+        assert rc == 0, cpu.gbl_cpu_last_error()
+        plies.append(dict(actions=act, winner=win, rewards=rew, done=d.copy(), to_move=m.copy(), action_mask=mask_, observation=obs,
+                          visits=vis, value=val, nodes=nod, how=how, mover=mover, root_value=rv, priors=pri))
+    return {k: np.stack([p[k] for p in plies]) for k in plies[0]}, s, m, d, tn
+
+
+@pytest.mark.parametrize("case", [(("eval", "eval"), (16, 0), "time"), (("eval", "eval"), (0, 4), "tile"), (("eval", "random"), (3, 0), "tile"),
+                                  (("random", "eval"), (7, 54), "time")])
+def test_window_equals_composed_loop(cpu, nets, boards, case):
+    pols, considered, layout = case
+    st, tm, turn = boards
+    kw = dict(noise=1, visit_offset=50, scale=23, X=EXPLORE, sample_plies=4, seed=SEED, env_base=ENV_BASE, ply0=3)
+    use = tuple(x if p == "eval" else None for x, p in zip(nets, pols))
+    got = host_collect_gumbel(st, tm, turn, T, pols, use, (8, 16), considered, layout=layout, **kw)
+    exp = composed_loop(cpu, st, tm, turn, T, pols, nets, (8, 16), considered, 1, 50, 23, EXPLORE, 4, SEED, ENV_BASE, 3)
+    same(got, exp)
+    how = got[0]["how"]
+    assert (how == nat.HOW_GUMBEL).any() and set(np.unique(how).tolist()) <= {0, 3, 4, 10}
+
+
+def test_window_equals_restatement(cpu, nets):
+    """... and the oracle's own loop on a few boards (the step, the masks and the observations are then not the library's either)."""
+    st, tm, turn = fixture_boards(6)
+    turn = turn % 4
+    for pols, considered in ((("eval", "eval"), (5, 0)), (("eval", "random"), (16, 0))):
+        use = tuple(x if p == "eval" else None for x, p in zip(nets, pols))
+        got = host_collect_gumbel(st, tm, turn, 4, pols, use, (8, 12), considered, noise=1, scale=23, X=EXPLORE, sample_plies=2, seed=SEED,
+                                  env_base=ENV_BASE, ply0=8)
+        same(got, GR.restate_collect_gumbel(st, tm, turn, 4, pols, nets, (8, 12), considered, 1, 50, 23, EXPLORE, 2, nat.ILLEGAL_NOOP, SEED,
+                                            ENV_BASE, 8))
+
+
+def test_shards_ply_dev_and_the_identity(cpu, nets, boards):
+    st, tm, turn = boards
+    kw = dict(noise=1, scale=23, X=EXPLORE, sample_plies=4, seed=SEED)
+    whole = host_collect_gumbel(st, tm, turn, T, ("eval", "eval"), nets, (8, 16), (16, 4), ply0=3, **kw)
+    halves = [host_collect_gumbel(st[a:b], tm[a:b], turn[a:b], T, ("eval", "eval"), nets, (8, 16), (16, 4), env_base=a, ply0=3, **kw)
+              for a, b in ((0, 65), (65, 130))]
+    for k, v in whole[0].items():
+        assert np.array_equal(v, np.concatenate([h[0][k] for h in halves], axis=1)), k
+    for i in (1, 2, 3, 4):
+        assert np.array_equal(whole[i], np.concatenate([h[i] for h in halves]))
+    same(host_collect_gumbel(st, tm, turn, T, ("eval", "eval"), nets, (8, 16), (16, 4), ply0=0, ply_dev=3, **kw), whole)
+    other = host_collect_gumbel(st, tm, turn, T, ("eval", "eval"), nets, (8, 16), (16, 4), ply0=4, **kw)
+    assert not np.array_equal(other[0]["visits"], whole[0]["visits"])  # (the Gumbel row moves with the ply index)
+    quiet = host_collect_gumbel(st, tm, turn, T, ("eval", "eval"), nets, (8, 16), (16, 4), ply0=4, **dict(kw, noise=0))
+    assert np.array_equal(quiet[0]["visits"], host_collect_gumbel(st, tm, turn, T, ("eval", "eval"), nets, (8, 16), (16, 4), ply0=9,
+                                                                  **dict(kw, noise=0))[0]["visits"])  # (without noise nothing is drawn)
+    # (0, 0) is gbl_cpu_collect_search_eval bit for bit, whatever the rule's three say; so is a RANDOM side's considered
+    L = nat.cpu_raw()
+    for layout in ("time", "tile"):
+        plain = host_collect("eval", L.gbl_cpu_collect_search_eval, L.gbl_cpu_last_error, st, tm, turn, T, ("eval", "eval"), EXPLORE, 4,
+                             nat.ILLEGAL_NOOP, layout, SEED, 0, 3, nets=nets, its=(8, 16))
+        same(host_collect_gumbel(st, tm, turn, T, ("eval", "eval"), nets, (8, 16), (0, 0), noise=5, visit_offset=-3, scale=999, X=EXPLORE,
+                                 sample_plies=4, seed=SEED, ply0=3, layout=layout), plain)
+    plain = host_collect("eval", L.gbl_cpu_collect_search_eval, L.gbl_cpu_last_error, st, tm, turn, T, ("random", "eval"), EXPLORE, 4,
+                         nat.ILLEGAL_NOOP, "time", SEED, 0, 3, nets=(None, nets[1]), its=(0, 16))
+    same(host_collect_gumbel(st, tm, turn, T, ("random", "eval"), (None, nets[1]), (0, 16), (33, 0), X=EXPLORE, sample_plies=4, seed=SEED,
+                             ply0=3), plain)
+
+
+# ---- 8. the consumers take the window as it is --------------------------------------------------------------------------------------------------
+def test_outcome_targets_replay_and_train_step_take_a_gumbel_window(cpu, nets):
+    n, plies = 130, 8
+    ev = tuple(_evaluator(x) for x in nets)
+    env = G.BatchedGobblet(n, "cpu", auto_reset=True, seed=11, track_turn=True)
+    env.rollout(40)
+    tr = env.collect(plies, policies=("evaluator", "random"), out="fresh",
+                     search=dict(evaluator=ev, iterations=16, explore=EXPLORE, gumbel=dict(considered=16)))
+    env.outcome_targets(tr)
+    how, z, done = tr["how"].numpy(), tr["z"].numpy(), tr["done"].numpy()
+    assert set(np.unique(how).tolist()) == {nat.HOW_RANDOM, nat.HOW_GUMBEL}
+    valid = np.zeros_like(how, bool)
+    valid[1:] = (z[1:] != nat.Z_OPEN) & (done[:-1] == 0)
+    keep = valid & (how == nat.HOW_GUMBEL)  # the kept rows are exactly the valid cells whose how is 10: every searched ply is a row
+    K = int(keep.sum())
+    assert K > 100 and (valid & (how == nat.HOW_RANDOM)).sum() > 100
+    rows = tr["visits"].numpy()
+    assert (rows[how == nat.HOW_GUMBEL].sum(1) >= 255).all() and not rows[how == nat.HOW_RANDOM].any()
+    buf = G.ReplayBuffer(2048, "cpu")
+    buf.append(env, tr, tag=3)
+    assert buf.total == K
+    at = np.argwhere(keep)
+    tt, bb = at[:, 0], at[:, 1]
+    assert np.array_equal(buf.visits[:K].numpy(), rows[tt, bb]) and np.array_equal(buf.z[:K].numpy(), z[tt, bb])
+    drawn = buf.batch(256, symmetries=None, call=1, seed=5)
+    slot = drawn["index"][:, 0].numpy()
+    assert (slot >= 0).all() and np.array_equal(drawn["visits"].numpy(), rows[tt[slot], bb[slot]])
+    trainer = G.GobbletTrainer(64, "cpu", seed=1)
+    stats = trainer.step(drawn)
+    assert int(stats[2]) == 256 and np.isfinite(stats.numpy()).all() and float(stats[0]) > 0.0
+    tb = env.training_batch(tr, 256, symmetries=None, call=2)
+    t_, b_ = tb["index"][:, 0].numpy(), tb["index"][:, 1].numpy()
+    ok = t_ >= 0
+    assert ok.sum() > 64 and keep[t_[ok], b_[ok]].all()
+
+
+# ---- 9. the argument errors, in the stated order --------------------------------------------------------------------------------------------------
+def _search_call(f, net, n=0, state=0, to_move=0, ev=True, iterations=8, explore=16, considered=16, noise=1, vo=50, scale=23, call=0,
+                 env_base=0):
+    import ctypes as C
+    e = net.struct()
+    return f(state or None, to_move or None, None, C.addressof(e) if ev else None, iterations, explore, considered, noise, vo, scale, 1,
+             env_base, call, *[None] * 9, n, None)
+
+
+SEARCH_CASES = [  # (name, overrides, message or None: GBL_OK) -- gbl_tree_search_eval_noise's errors in their order, then the rule's four
+    ("n < 0", dict(n=-1, call=1 << 24, considered=0), b"n < 0"),
+    ("call", dict(call=1 << 24, iterations=0, considered=0), b"call must be below 2^24"),
+    ("env_base", dict(env_base=(1 << 42) + 1, iterations=0), b"env_base + n must not exceed 2^42"),
+    ("ev", dict(ev=False, considered=0), b"ev must not be NULL"),
+    ("iterations before the rule", dict(iterations=513, considered=0), b"iterations must be in [1, 512]"),
+    ("explore before the rule", dict(explore=1025, scale=65), b"explore must be in [0, 1024]"),
+    ("considered 0", dict(considered=0, noise=2), b"considered must be in [1, 54]"),
+    ("considered 55", dict(considered=55, vo=-1), b"considered must be in [1, 54]"),
+    ("gumbel_noise", dict(noise=2, vo=256, scale=65), b"gumbel_noise must be 0 or 1"),
+    ("visit_offset", dict(vo=256, scale=65), b"visit_offset must be in [0, 255]"),
+    ("visit_offset -1", dict(vo=-1), b"visit_offset must be in [0, 255]"),
+    ("scale", dict(scale=65), b"scale must be in [0, 64]"),
+    ("scale -1", dict(scale=-1), b"scale must be in [0, 64]"),
+    ("the rule comes before the pointers", dict(n=1, scale=65), b"scale must be in [0, 64]"),
+    ("state", dict(n=1), b"state must not be NULL"),
+    ("to_move", dict(n=1, state=64), b"to_move must not be NULL"),
+    ("the ends of the ranges", dict(considered=54, noise=0, vo=255, scale=64, iterations=512), None),
+    ("the other ends", dict(considered=1, vo=0, scale=0, iterations=1), None),
+]
+CONSIDERED_MSG = b"considered0 / considered1 must be in [0, 54]"
+COLLECT_CASES = [
+    ("considered -1", dict(considered=(-1, 4)), CONSIDERED_MSG),
+    ("considered 55", dict(considered=(0, 55)), CONSIDERED_MSG),
+    ("an earlier check comes first", dict(its=(0, 5), considered=(55, 0)), b"iterations must be in [1, 512]"),
+    ("considered before the rule's three", dict(considered=(55, 4), noise=2), CONSIDERED_MSG),
+    ("gumbel_noise", dict(noise=2, vo=256), b"gumbel_noise must be 0 or 1"),
+    ("visit_offset", dict(vo=256, scale=65), b"visit_offset must be in [0, 255]"),
+    ("scale", dict(scale=65), b"scale must be in [0, 64]"),
+    ("no Gumbel side reads the three", dict(considered=(0, 0), noise=2, vo=-1, scale=65), None),
+    ("a RANDOM side's considered is not read", dict(pols=("random", "eval"), considered=(-5, 4)), None),
+    ("... nor does it make the three read", dict(pols=("eval", "random"), considered=(0, 9), scale=99), None),
+    ("the ends of the ranges", dict(considered=(54, 1), noise=0, vo=255, scale=64), None),
+]
+
+
+@pytest.mark.parametrize("flavour", ["host", "device"])
+def test_argument_errors(flavour):
+    lib, prefix = (nat.cpu_raw(), "gbl_cpu_") if flavour == "host" else (nat.lib(), "gbl_")
+    err = getattr(lib, prefix + "last_error")
+    net = smoke_net()
+    f = getattr(lib, prefix + "tree_search_gumbel")
+    for name, over, msg in SEARCH_CASES:  # (every case returns before a board is read or a kernel launched)
+        rc = _search_call(f, net, **over)
+        if msg is None:
+            assert rc == nat.OK, (name, err())
+        else:
+            assert rc == nat.ERR_ARG and err() == msg, (name, rc, err())
+    f = getattr(lib, prefix + "collect_search_gumbel")
+    for name, over, msg in COLLECT_CASES:
+        kw = dict(pols=("eval", "eval"), its=(8, 5), considered=(16, 4), noise=1, vo=50, scale=23)
+        kw.update(over)
+        evs = [net.struct() if p == "eval" else None for p in kw["pols"]]
+        # n = 0: every check of the arguments runs, and nothing is read or launched
+        rc = f(*call_args(lambda a: a, None, None, None, {}, 0, 64, 64, 1, 0, 0, None, 4, kw["pols"], evs, kw["its"], 16, 0, nat.ILLEGAL_NOOP,
+                          None, None, kw["considered"], kw["noise"], kw["vo"], kw["scale"], None))
+        if msg is None:
+            assert rc == nat.OK, (name, err())
+        else:
+            assert rc == nat.ERR_ARG and err() == msg, (name, rc, err())
+
+
+# ---- 10. the Python surface on device="cpu" --------------------------------------------------------------------------------------------------------
+def test_policy_surface(cpu, nets, roots):
+    st, tm, mask, _ = roots
+    ev = _evaluator(nets[0])
+    pol = G.EvaluatorTreeSearchGobbletPolicy(ev, iterations=16, explore=EXPLORE, gumbel=dict(considered=5, scale=40), seed=SEED, env_base=ENV_BASE)
+    assert pol.gumbel == dict(considered=5, noise=1, visit_offset=50, scale=40)
+    t = [torch.from_numpy(x) for x in (st, tm, mask)]
+    for call in (0, 1):
+        act = pol._run(*t)
+        exp = run(GUMBEL, "cpu", st, tm, mask, (16, EXPLORE, 5, 1, 50, 40, SEED, ENV_BASE, call), nets[0])
+        for k, v in (("visits", pol.last_visits), ("action", act), ("root_value", pol.last_root_value), ("target", pol.last_target),
+                     ("gumbel", pol.last_gumbel), ("root_priors", pol.last_root_priors)):
+            assert np.array_equal(v.numpy(), exp[k]), (call, k)
+    assert pol.call == 2
+    cand = torch.from_numpy((oracle.batch_legal_mask(st, tm) != 0) & (mask != 0))
+    row = G.gumbel_row(SEED, ENV_BASE + torch.arange(len(st)), 1)
+    assert row.dtype == torch.int16 and torch.equal(torch.where(cand, row, torch.zeros_like(row)), pol.last_gumbel)
+    assert G.EvaluatorTreeSearchGobbletPolicy(ev, iterations=16, gumbel={}).gumbel == dict(considered=16, noise=1, visit_offset=50, scale=23)
+    plain = G.EvaluatorTreeSearchGobbletPolicy(ev, iterations=16)
+    plain._run(*t)
+    assert plain.gumbel is None and plain.last_target is None and plain.last_gumbel is None
+    for bad in (dict(considered=0), dict(considered=55), dict(considered=2.5), dict(noise=2), dict(visit_offset=256), dict(visit_offset=-1),
+                dict(scale=65), dict(scale=-1), dict(temperature=1), 16, (16, True)):
+        with pytest.raises(ValueError):
+            G.EvaluatorTreeSearchGobbletPolicy(ev, iterations=16, gumbel=bad)
+    with pytest.raises(ValueError, match="noise"):
+        G.EvaluatorTreeSearchGobbletPolicy(ev, iterations=16, gumbel={}, noise=0.25)
+    assert nat.HOW_GUMBEL == 10 and nat.STREAM_GUMBEL == 10
+
+
+class Counting:
+    """A library handle that counts the calls of every entry point it hands out."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*a):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            return fn(*a)
+        return call
+
+
+def _collect(n, policies, search, seed=11, **kw):
+    env = G.BatchedGobblet(n, "cpu", auto_reset=True, seed=seed, env_base=3, track_turn=True)
+    env.rollout(30)
+    env._lib = Counting(env._lib)
+    return env.collect(4, policies=policies, search=search, out="fresh", **kw), env
+
+
+def test_collect_surface(cpu, nets):
+    net = nets[0]
+    ev = _evaluator(net)
+    base = dict(evaluator=ev, iterations=8, sample_plies=32, explore=24)
+    plain, env0 = _collect(40, ("evaluator", "evaluator"), dict(base))
+    assert set(env0._lib.calls) == {"gbl_collect_search_eval"}  # no gumbel: today's entry point
+    for considered in (0, (0, 0)):  # considered 0 keeps it too
+        one, env1 = _collect(40, ("evaluator", "evaluator"), dict(base, gumbel=dict(considered=considered)))
+        assert set(env1._lib.calls) == {"gbl_collect_search_eval"} and all(torch.equal(one[k], plain[k]) for k in ("actions", "visits", "how"))
+    got, env2 = _collect(40, ("evaluator", "evaluator"), dict(base, gumbel=dict(considered=(5, 0), scale=40, noise=True)))
+    assert set(env2._lib.calls) == {"gbl_collect_search_gumbel"}
+    ref = G.BatchedGobblet(40, "cpu", auto_reset=True, seed=11, env_base=3, track_turn=True)
+    ref.rollout(30)
+    raw = host_collect_gumbel(ref.squares.numpy(), ref.to_move.numpy(), ref.turn.numpy(), 4, ("eval", "eval"), (net, net), (8, 8), (5, 0),
+                              noise=1, visit_offset=50, scale=40, X=24, sample_plies=32, seed=11, env_base=3, ply0=30)[0]
+    for k in ("actions", "visits", "value", "nodes", "how", "root_value", "priors"):
+        assert np.array_equal(got[k].numpy(), raw[k]), k
+    how, mover = got["how"], got["mover"]
+    assert (how[mover == 0] == nat.HOW_GUMBEL).all() and (how[mover == 1] != nat.HOW_GUMBEL).all()
+    d, env3 = _collect(40, ("evaluator", "random"), dict(evaluator=ev, iterations=16, gumbel={}))  # the defaults
+    assert set(env3._lib.calls) == {"gbl_collect_search_gumbel"} and set(np.unique(d["how"].numpy())) == {0, 10}
+    r, env4 = _collect(40, ("random", "evaluator"), dict(base, gumbel=dict(considered=(99, 0))))  # a random side's value is dropped
+    assert set(env4._lib.calls) == {"gbl_collect_search_eval"}
+    for bad in (dict(considered=-1), dict(considered=55), dict(considered=(1, 2, 3)), dict(noise=3), dict(visit_offset=256), dict(scale=65),
+                dict(budget=3), 16, (16, 23)):
+        with pytest.raises(ValueError):
+            _collect(8, ("evaluator", "evaluator"), dict(base, gumbel=bad))
+    for other in (dict(solve_depth=2), dict(noise=0.25), dict(cap=dict(fast_iterations=2, full=0.25))):
+        with pytest.raises(ValueError, match="gumbel"):
+            _collect(8, ("evaluator", "evaluator"), dict(base, gumbel={}, **other))
+    with pytest.raises(ValueError):  # no evaluator side: the key is unknown
+        _collect(8, ("tree", "tree"), dict(iterations=8, playouts=2, gumbel={}))
+    with pytest.raises(ValueError, match="gumbel"):  # a policy instance does not carry the rule into collect()
+        _collect(8, (G.EvaluatorTreeSearchGobbletPolicy(ev, iterations=8, gumbel={}), "random"), None)
+    tb = G.Tablebase((1, 0, 0), "cpu")
+    tb.build()
+    env = G.BatchedGobblet(8, "cpu", auto_reset=True, seed=1, track_turn=True)
+    with pytest.raises(ValueError, match="gumbel"):
+        env.collect(3, policies=("tablebase", "evaluator"), search=dict(tablebase=tb, evaluator=ev, iterations=8, gumbel={}))
+    with pytest.raises(ValueError, match="gumbel"):
+        env.collect(3, policies=("evaluator", "evaluator"), search=dict(tablebase=tb, judge=True, evaluator=ev, iterations=8, gumbel={}))
