@@ -7,7 +7,7 @@ import numpy as np
 
 from gobblet_rl_amd import _native as nat
 from tests.search_harness import DEV, PAD
-from tests.selfplay_harness import CODES, SOLVE_NAMES, cells, strides
+from tests.selfplay_harness import CODES, SOLVE_NAMES, Compact, geometry
 
 FULL = 256  # the share at which every ply is full
 
@@ -22,29 +22,23 @@ def call_args(ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pol
 
 
 def _run(f, ok, put, get, ptr, pad, stream, st, tm, turn, T, pols, nets, its, deps, noise, fast, share, X, sample_plies, illegal_mode, layout,
-         seed, env_base, ply0, ply_dev, keep, counters):
+         seed, env_base, ply0, ply_dev, keep, counters, strides=None, store=None):
     n = len(st)
-    ps, ts, total = strides(n, T, layout)
+    ps, ts, total, at = geometry(n, T, layout, strides)
+    store = Compact(put, get, pad) if store is None else store
     keep = [k for k, _, _ in SOLVE_NAMES] if keep is None else keep
-    full = {k: put(np.full((total + 2 * pad,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in SOLVE_NAMES if k in keep}
-    traj = {k: v[pad:] for k, v in full.items()}
+    traj = {k: store.array(k, dt, tail, total) for k, dt, tail in SOLVE_NAMES if k in keep}
     st, tm, dn = put(np.ascontiguousarray(st, np.int8)), put(np.ascontiguousarray(tm, np.int8)), put(np.full(n, 5, np.int8))
     tn = None if turn is None else put(np.ascontiguousarray(turn, np.int32))
     pd = None if ply_dev is None else put(np.array([ply_dev], np.int32))
     evs = [None if net is None else net.struct() for net in nets]  # (alive until the call has returned)
     ok(f(*call_args(ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, evs, its, deps, noise, X, sample_plies, illegal_mode,
                     counters, tn, fast, share, stream)))
-    at = cells(n, T, layout)
-    untouched = np.ones(total + 2 * pad, bool)
-    untouched[at.ravel() + pad] = False
-    host = {k: get(v) for k, v in full.items()}
-    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
-    return {k: v[pad:][at] for k, v in host.items()}, get(st), get(tm), get(dn), None if tn is None else get(tn)
+    return store.cells(at, total), get(st), get(tm), get(dn), None if tn is None else get(tn)
 
 
 def host_collect_cap(st, tm, turn, T, pols, nets, its, fast, share, deps=(0, 0), noise=(0, 0), X=16, sample_plies=0,
-                     illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, keep=None, counters=None):
+                     illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, keep=None, counters=None, strides=None, store=None):
     """gbl_cpu_collect_search_cap on host arrays; nets: restatement Nets; only the outputs named in `keep` are given (None: all).
     Returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
     L = nat.cpu_raw()
@@ -55,11 +49,11 @@ def host_collect_cap(st, tm, turn, T, pols, nets, its, fast, share, deps=(0, 0),
     def ptr(a):
         return None if a is None else a.ctypes.data
     return _run(L.gbl_cpu_collect_search_cap, ok, np.array, lambda a: a, ptr, 0, None, st, tm, turn, T, pols, nets, its, deps, noise, fast,
-                share, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters)
+                share, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters, strides, store)
 
 
 def device_collect_cap(st, tm, turn, T, pols, nets, its, fast, share, deps=(0, 0), noise=(0, 0), X=16, sample_plies=0,
-                       illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, keep=None, counters=None):
+                       illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, keep=None, counters=None, strides=None, store=None):
     """gbl_collect_search_cap on the device, every output between canaries; nets: DeviceNets."""
     import torch
 
@@ -68,4 +62,4 @@ def device_collect_cap(st, tm, turn, T, pols, nets, its, fast, share, deps=(0, 0
         return t.cpu().numpy()
     return _run(nat.lib().gbl_collect_search_cap, lambda rc: nat.check(rc, "gbl_collect_search_cap"), lambda a: torch.from_numpy(a).to(DEV),
                 get, nat.ptr, PAD, nat.current_stream(DEV), st, tm, turn, T, pols, nets, its, deps, noise, fast, share, X, sample_plies,
-                illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters)
+                illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters, strides, store)

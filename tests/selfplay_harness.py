@@ -33,6 +33,39 @@ def cells(n, T, layout):
     return np.arange(T)[:, None] * ps + (b // 64) * ts + b % 64  # (T, n)
 
 
+def geometry(n, T, layout, override=None):
+    """(ply_stride, tile_stride, the cells an array must have, cell(t, b) as (T, n)) of the compact layout, or of
+    override = (ply_stride, tile_stride), in cells."""
+    ps, ts, total = strides(n, T, layout)
+    if override is not None:
+        ps, ts = override
+        total = (T - 1) * ps + (-(-n // 64) - 1) * ts + 64
+    b = np.arange(n)
+    return ps, ts, total, np.arange(T)[:, None] * ps + (b // 64) * ts + b % 64
+
+
+class Compact:
+    """Where a runner keeps its trajectory outputs: an array each, filled with -7 / 99, `pad` rows of the same on either side.  A test
+    with a geometry of its own brings another store of the same two methods (tests/test_gpu_far_offsets.py)."""
+
+    def __init__(self, put, get, pad):
+        self.put, self.get, self.pad, self.full = put, get, pad, {}
+
+    def array(self, k, dt, tail, total):
+        """The array of output k, from its cell 0."""
+        self.full[k] = self.put(np.full((total + 2 * self.pad,) + tail, 99 if dt == np.uint8 else -7, dt))
+        return self.full[k][self.pad:]
+
+    def cells(self, at, total):
+        """{k: (T, n, ...)} on the host, after checking that nothing outside the cells is written, the canaries on either side included."""
+        untouched = np.ones(total + 2 * self.pad, bool)
+        untouched[at.ravel() + self.pad] = False
+        host = {k: self.get(v) for k, v in self.full.items()}
+        for k, v in host.items():
+            assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
+        return {k: v[self.pad:][at] for k, v in host.items()}
+
+
 def call_args(entry, ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, X, sample_plies, illegal_mode, counters, tn, stream,
               its=(0, 0), pls=(0, 0), M=0, evs=(None, None), deps=(0, 0), noise=(0, 0)):
     """The argument list of gbl(_cpu)_collect_search ("search"), _eval, _solve or _noise; ptr(x) turns an array (or None) into a
@@ -47,25 +80,21 @@ def call_args(entry, ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd,
 
 
 def _run(entry, f, ok, put, get, ptr, pad, stream, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0,
-         ply_dev, keep, counters, nets, **sides):
+         ply_dev, keep, counters, nets, strides=None, store=None, **sides):
+    """strides: (ply_stride, tile_stride) in place of the compact ones of `layout`; store: where the outputs live (a Compact of this
+    runner's put / get / pad unless the caller brings one)."""
     n = len(st)
-    ps, ts, total = strides(n, T, layout)
+    ps, ts, total, at = geometry(n, T, layout, strides)
+    store = Compact(put, get, pad) if store is None else store
     keep = [k for k, _, _ in NAMES[entry]] if keep is None else keep
-    full = {k: put(np.full((total + 2 * pad,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in NAMES[entry] if k in keep}
-    traj = {k: v[pad:] for k, v in full.items()}
+    traj = {k: store.array(k, dt, tail, total) for k, dt, tail in NAMES[entry] if k in keep}
     st, tm, dn = put(np.ascontiguousarray(st, np.int8)), put(np.ascontiguousarray(tm, np.int8)), put(np.full(n, 5, np.int8))
     tn = None if turn is None else put(np.ascontiguousarray(turn, np.int32))
     pd = None if ply_dev is None else put(np.array([ply_dev], np.int32))
     evs = [None if net is None else net.struct() for net in nets]  # (alive until the call has returned)
     ok(f(*call_args(entry, ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, X, sample_plies, illegal_mode, counters, tn,
                     stream, evs=evs, **sides)))
-    at = cells(n, T, layout)
-    untouched = np.ones(total + 2 * pad, bool)
-    untouched[at.ravel() + pad] = False
-    host = {k: get(v) for k, v in full.items()}
-    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
-    return {k: v[pad:][at] for k, v in host.items()}, get(st), get(tm), get(dn), None if tn is None else get(tn)
+    return store.cells(at, total), get(st), get(tm), get(dn), None if tn is None else get(tn)
 
 
 def host_collect(entry, f, err, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None,

@@ -9,7 +9,7 @@ from gobblet_rl_amd import _native as nat
 from tests import tablebase_harness as TH
 from tests import tb_targets_harness as TT
 from tests.search_harness import DEV, PAD
-from tests.selfplay_harness import SOLVE_NAMES, cells, strides
+from tests.selfplay_harness import SOLVE_NAMES, Compact, geometry
 
 JUDGE_NAMES = (("tb_outcomes", np.int8, (54,)), ("tb_value", np.int8, ()), ("tb_played", np.int8, ()))
 TB_NAMES = SOLVE_NAMES + JUDGE_NAMES
@@ -35,30 +35,24 @@ def call_args(ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pol
 
 
 def _run(f, ok, put, get, ptr, pad, stream, tb, st, tm, turn, T, pols, nets, its, deps, noise, X, sample_plies, illegal_mode, layout, seed,
-         env_base, ply0, ply_dev, mode, count, keep, counters):
+         env_base, ply0, ply_dev, mode, count, keep, counters, strides=None, store=None):
     n = len(st)
-    ps, ts, total = strides(n, T, layout)
+    ps, ts, total, at = geometry(n, T, layout, strides)
+    store = Compact(put, get, pad) if store is None else store
     keep = [k for k, _, _ in TB_NAMES] if keep is None else keep
-    full = {k: put(np.full((total + 2 * pad,) + tail, 99 if dt == np.uint8 else -7, dt)) for k, dt, tail in TB_NAMES if k in keep}
-    traj = {k: v[pad:] for k, v in full.items()}
+    traj = {k: store.array(k, dt, tail, total) for k, dt, tail in TB_NAMES if k in keep}
     st, tm, dn = put(np.ascontiguousarray(st, np.int8)), put(np.ascontiguousarray(tm, np.int8)), put(np.full(n, 5, np.int8))
     tn = None if turn is None else put(np.ascontiguousarray(turn, np.int32))
     pd = None if ply_dev is None else put(np.array([ply_dev], np.int32))
     evs = [None if net is None else net.struct() for net in nets]  # (alive until the call has returned)
     ok(f(*call_args(ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, evs, its, deps, noise, X, sample_plies, illegal_mode,
                     counters, tn, tb, mode, count, stream)))
-    at = cells(n, T, layout)
-    untouched = np.ones(total + 2 * pad, bool)
-    untouched[at.ravel() + pad] = False
-    host = {k: get(v) for k, v in full.items()}
-    for k, v in host.items():  # (nothing outside the cells is written, the canaries on either side included)
-        assert (v[untouched] == (99 if v.dtype == np.uint8 else -7)).all(), "output %s was written outside its cells" % k
-    return {k: v[pad:][at] for k, v in host.items()}, get(st), get(tm), get(dn), None if tn is None else get(tn)
+    return store.cells(at, total), get(st), get(tm), get(dn), None if tn is None else get(tn)
 
 
 def host_collect_tb(tb, st, tm, turn, T, pols, nets=(None, None), its=(0, 0), deps=(0, 0), noise=(0, 0), X=16, sample_plies=0,
                     illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, mode=0, count=1, keep=None,
-                    counters=None):
+                    counters=None, strides=None, store=None):
     """gbl_cpu_collect_search_tb on host arrays; nets: restatement Nets; only the outputs named in `keep` are given (None: all).
     Returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
     L = nat.cpu_raw()
@@ -69,12 +63,12 @@ def host_collect_tb(tb, st, tm, turn, T, pols, nets=(None, None), its=(0, 0), de
     def ptr(a):
         return None if a is None else a.ctypes.data
     return _run(L.gbl_cpu_collect_search_tb, ok, np.array, lambda a: a, ptr, 0, None, tb, st, tm, turn, T, pols, nets, its, deps, noise, X,
-                sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, mode, count, keep, counters)
+                sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, mode, count, keep, counters, strides, store)
 
 
 def device_collect_tb(tb, st, tm, turn, T, pols, nets=(None, None), its=(0, 0), deps=(0, 0), noise=(0, 0), X=16, sample_plies=0,
                       illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, mode=0, count=1, keep=None,
-                      counters=None):
+                      counters=None, strides=None, store=None):
     """gbl_collect_search_tb on the device, every output between canaries; tb: a Table of device tensors; nets: DeviceNets."""
     import torch
 
@@ -83,7 +77,7 @@ def device_collect_tb(tb, st, tm, turn, T, pols, nets=(None, None), its=(0, 0), 
         return t.cpu().numpy()
     return _run(nat.lib().gbl_collect_search_tb, lambda rc: nat.check(rc, "gbl_collect_search_tb"), lambda a: torch.from_numpy(a).to(DEV), get,
                 nat.ptr, PAD, nat.current_stream(DEV), tb, st, tm, turn, T, pols, nets, its, deps, noise, X, sample_plies, illegal_mode, layout,
-                seed, env_base, ply0, ply_dev, mode, count, keep, counters)
+                seed, env_base, ply0, ply_dev, mode, count, keep, counters, strides, store)
 
 
 def start_boards(host, n_positions, n_random, n_fresh, seed):

@@ -2,7 +2,8 @@
 for byte and between canaries (the host flavour is pinned to the restatement of the header's text in tests/test_gumbel_search.py);
 (0, 0) against gbl_collect_search_eval on the device; and one graph capture and replay of collect(..., gumbel=) with the ply on the
 device.  The shapes are the smallest at which the kernel can still go wrong: a single board, a ragged second tile and a ragged third;
-roots of 54, 27, 2, 1 and 0 candidates under a mask; every schedule of tests/gumbel_harness.py::PAIRS but the long one -- a considered
+roots of 54, 27, 2, 1 and 0 candidates under a mask; every schedule of tests/gumbel_harness.py::PAIRS but the long one (that one, and
+the longer ones of LONG_PAIRS, in tests/test_gpu_gumbel_long.py) -- a considered
 set of one, of two (never halved), of three and five (odd halvings), of sixteen at one visit each, and of more than the candidates."""
 import numpy as np
 import pytest

@@ -18,7 +18,8 @@ from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import gumbel_restatement as GR
 from tests import solver_restatement as SR
-from tests.gumbel_harness import GUMBEL_NAMES, PAIRS, call_args, host_collect_gumbel, rule_boards
+from tests.gumbel_harness import (GUMBEL_NAMES, LONG_PAIRS, PAIRS, call_args, host_collect_gumbel, root_value_edge_case, rule_boards,
+                                  sigma_edge_case, winning_action_case)
 from tests.search_harness import run
 from tests.search_harness import same as same_arrays
 from tests.selfplay_harness import _evaluator, host_collect, same
@@ -101,8 +102,37 @@ def test_host_flavour_equals_restatement(cpu, roots, nets, k, pair):
                 {x: got[x][:9] for x in ("action", "gumbel")})
 
 
+@pytest.mark.parametrize("pair", LONG_PAIRS)
+@pytest.mark.parametrize("k", [0, 1])
+def test_host_flavour_equals_restatement_on_long_schedules(cpu, roots, nets, k, pair):
+    """The chains of three and four halvings, on the roots that keep the restatement to a few seconds: the two empty boards, eight
+    midgames and the eight rows under masks (27, 2, 1 and 0 candidates, twice)."""
+    st, tm, mask = (np.ascontiguousarray(np.concatenate([x[:10], x[-8:]])) for x in roots[:3])
+    considered, iterations = pair
+    for noise in (0, 1):
+        for scale in (0, 23, 64):
+            params = (iterations, EXPLORE, considered, noise, 50, scale, SEED, ENV_BASE, 5)
+            got = run(GUMBEL, "cpu", st, tm, mask, params, nets[k])
+            same_arrays(got, GR.restate_search_gumbel(nets[k], st, tm, mask, *params))
+    assert got["visits"][0].sum() == iterations and (got["visits"][0] > 0).sum() == min(considered, 54)
+
+
 # ---- 3. the schedule, from the rule's text alone ---------------------------------------------------------------------------------------------
 SCHEDULE = {(4, 16): [6, 6, 2, 2], (16, 64): [15, 15, 7, 7, 3, 3, 3, 3] + [1] * 8, (3, 8): [4, 3, 1], (2, 8): [4, 4], (1, 8): [8]}
+# The long ones, by hand (P: the phases; "k x s": every one of the k actions of A gets s more visits, until all stand at the target T):
+#   (54, 512)  P = 6, T = 512 div 324 = 1: 54 x 1 = 54 iterations; to 27, T = 1 + 512 div 162 = 4: 27 x 3 (135 spent); to 14,
+#              T = 4 + 512 div 84 = 10: 14 x 6 (219); to 7, T = 10 + 512 div 42 = 22: 7 x 12 (303); to 4, T = 22 + 512 div 24 = 43: 4 x 21
+#              (387); to 2 (max(2, .)): the 125 left go to the fewer visits in turn, 43 + 63 and 43 + 62.
+#   (27, 200)  P = 5, T = 200 div 135 = 1: 27; to 14, T = 1 + 200 div 70 = 3: 14 x 2 (55); to 7, T = 3 + 200 div 35 = 8: 7 x 5 (90); to 4,
+#              T = 8 + 200 div 20 = 18: 4 x 10 (130); to 2: 70 left, 18 + 35 each.
+#   (32, 256)  P = 5, T = 256 div 160 = 1: 32; to 16, T = 1 + 256 div 80 = 4: 16 x 3 (80); to 8, T = 4 + 256 div 40 = 10: 8 x 6 (128); to 4,
+#              T = 10 + 256 div 20 = 22: 4 x 12 (176); to 2: 80 left, 22 + 40 each.
+#   (7, 96)    P = 3, T = 96 div 21 = 4: 7 x 4 = 28; to 4, T = 4 + 96 div 12 = 12: 4 x 8 (60); to 2: 36 left, 12 + 18 each.
+SCHEDULE.update({(54, 512): [106, 105, 43, 43, 22, 22, 22] + [10] * 7 + [4] * 13 + [1] * 27,
+                 (27, 200): [53, 53, 18, 18, 8, 8, 8] + [3] * 7 + [1] * 13,
+                 (32, 256): [62, 62, 22, 22] + [10] * 4 + [4] * 8 + [1] * 16,
+                 (7, 96): [30, 30, 12, 12, 4, 4, 4]})
+assert set(LONG_PAIRS) <= set(SCHEDULE) and all(sum(row) == pair[1] and len(row) == pair[0] for pair, row in SCHEDULE.items())
 
 
 @pytest.mark.parametrize("pair", sorted(SCHEDULE))
@@ -110,11 +140,30 @@ def test_the_sorted_root_visits_depend_on_the_schedule_alone(cpu, roots, nets, p
     st, tm, mask, _ = roots
     considered, iterations = pair
     enough = ((oracle.batch_legal_mask(st, tm) != 0) & (mask != 0)).sum(1) >= considered
-    assert enough.sum() > 100
-    for noise, scale, k in ((1, 23, 0), (0, 0, 1), (1, 64, 1)):
-        got = run(GUMBEL, "cpu", st, tm, mask, (iterations, EXPLORE, considered, noise, 50, scale, SEED, ENV_BASE, 2), nets[k], keep=("visits",))
-        rows = -np.sort(-got["visits"][enough], axis=1)[:, :considered]
-        assert (rows == np.array(SCHEDULE[pair])).all() and (got["visits"].sum(1)[enough] == iterations).all()
+    launches = [(st, tm, mask, ENV_BASE, enough)]
+    if pair in LONG_PAIRS:  # few of the roots have so many candidates: 64 more on the empty board, either mover, under four values of env_base
+        launches += [(np.zeros((16, 27), np.int8), (np.arange(16) % 2).astype(np.int8), None, base, np.ones(16, bool))
+                     for base in (0, 1 << 20, (1 << 41) + 7, (1 << 42) - 16)]
+        assert enough.sum() >= 2 and sum(x[4].sum() for x in launches) >= 64 + 2
+    else:
+        assert enough.sum() > 100
+    for st, tm, mask, base, enough in launches:
+        for noise, scale, k in ((1, 23, 0), (0, 0, 1), (1, 64, 1)):
+            got = run(GUMBEL, "cpu", st, tm, mask, (iterations, EXPLORE, considered, noise, 50, scale, SEED, base, 2), nets[k], keep=("visits",))
+            rows = -np.sort(-got["visits"][enough], axis=1)[:, :considered]
+            assert (rows == np.array(SCHEDULE[pair])).all() and (got["visits"].sum(1)[enough] == iterations).all()
+
+
+@pytest.mark.parametrize("pair", LONG_PAIRS + ((16, 64),))
+def test_the_long_schedules_end_on_two_actions(cpu, roots, nets, pair):
+    """What tests/test_gpu_gumbel_long.py asserts of the kernel holds of its reference alone: on at least 100 of the 130 roots exactly
+    two actions end above iterations // 8 visits (the roots of one or no candidate cannot, nor can every masked one)."""
+    st, tm, mask, _ = roots
+    considered, iterations = pair
+    for noise, scale in ((0, 0), (1, 23), (1, 64)):
+        for k in (0, 1):
+            got = run(GUMBEL, "cpu", st, tm, mask, (iterations, EXPLORE, considered, noise, 50, scale, SEED, ENV_BASE, 5), nets[k], keep=("visits",))
+            assert len(st) == 130 and ((got["visits"] > iterations // 8).sum(1) == 2).sum() >= 100, (noise, scale, k)
 
 
 def test_more_considered_than_candidates(cpu, roots, nets):
@@ -162,29 +211,10 @@ def test_gumbel_max_property(cpu):
 
 # ---- 5. dial networks ------------------------------------------------------------------------------------------------------------------------
 def test_an_action_that_wins_at_once_is_decided_whenever_it_is_considered(cpu):
-    """Flat logits and value 0: every leaf's mean is 32768 but a won child's 65536, so sigma lifts an action that wins at once over every
-    Gumbel value ((50 + maxN) * 23 / 2 > 575, the g's span 186).  The position has four such actions (any piece onto square 2); one is
-    in A iff its g is among the 16 largest (the lower action on ties).  A winner is decided whenever one is considered, the considered
-    winners -- and nobody else -- carry the largest target byte, and a winner outside A goes through the root's value like the rest."""
-    n = 512
-    s, m = SR.play(SR.WIN_SEQ)
-    st, tm = np.repeat(s[None], n, 0), np.full(n, m, np.int8)
-    got = run(GUMBEL, "cpu", st, tm, None, (16, EXPLORE, 16, 1, 50, 23, SEED, ENV_BASE, 3), R.zero_net(64))
-    legal = np.flatnonzero(oracle.legal_mask(s, m)).tolist()
-    mine = 1 if m == 0 else -1
-    winners = {a for a in legal if oracle.check_for_winner(oracle.play_turn(s, m, a)) == mine}
-    assert SR.WIN_ACTION in winners and len(winners) == 4
-    g = G.gumbel_row(SEED, ENV_BASE + torch.arange(n), 3).numpy().astype(np.int64)
-    some = 0
-    for b in range(n):
-        considered = winners & set(sorted(legal, key=lambda a: (-g[b, a], a))[:16])
-        assert (int(got["action"][b]) in winners) == bool(considered), b
-        if considered:
-            some += 1
-            row = got["target"][b]
-            assert int(got["action"][b]) in considered and set(np.flatnonzero(row == row.max()).tolist()) == considered
-            assert all(got["wins"][b, a] == 128 * got["visits"][b, a] > 0 for a in considered)
-    assert n // 10 < some < n - n // 10  # (both cases occur)
+    """tests/gumbel_harness.py::winning_action_case on the host flavour: a winner is decided whenever one is considered, the considered
+    winners -- and nobody else -- carry the largest target byte."""
+    (st, tm), mask, net, params, expect = winning_action_case(SEED, ENV_BASE)
+    expect(run(GUMBEL, "cpu", st, tm, mask, params, net))
 
 
 @pytest.mark.parametrize("top", [0, 17, 53])
@@ -201,51 +231,19 @@ def test_one_considered_action_without_noise_takes_every_iteration(cpu, top):
 
 
 # ---- 6. the target row's edges ------------------------------------------------------------------------------------------------------------------
-def exact_target(L, sigma):
-    """The header's sentence once more in exact integers, from {a: L_a} and {a: sigma_a}."""
-    t = {a: L[a] + sigma[a] for a in L}
-    top = max(t.values())
-    e = {}
-    for a in t:
-        d = min(top - t[a], 255)
-        e[a] = int(math.floor(65536 * 2.0 ** (-(d % 16) / 16) + 0.5)) // (2 ** (d // 16))
-    row = np.zeros(54, np.uint8)
-    for a in t:
-        row[a] = 1 + (254 * e[a]) // sum(e.values())
-    return row
-
-
 @pytest.mark.parametrize("q_raw", [-128, -37, 0, 90, 128])
 def test_an_unvisited_action_uses_the_root_value(cpu, q_raw):
-    """considered = 1 on the empty board: one child is visited, 53 actions go through the root's q.  The visited child's mean comes from
-    the raw wins / losses / visits the entry point writes, by the header's formula."""
-    logits = -(np.arange(54) % 7).astype(np.int64) * 5
-    net = R.logit_dial(logits + 100, o54=q_raw << 2, shift_v=2)
-    st, tm = np.zeros((1, 27), np.int8), np.zeros(1, np.int8)
+    """tests/gumbel_harness.py::root_value_edge_case on the host flavour: considered = 1 on the empty board, 53 actions go through the
+    root's q."""
     for vo, scale in ((50, 23), (0, 64), (255, 1)):
-        got = run(GUMBEL, "cpu", st, tm, None, (6, EXPLORE, 1, 0, vo, scale, 0, 0, 0), net)
-        assert got["root_value"][0] == q_raw and got["visits"][0, 0] == 6 and got["visits"][0].sum() == 6
-        W, Lo = int(got["wins"][0, 0]), int(got["losses"][0, 0])
-        mean = {a: 32768 + 256 * q_raw for a in range(54)}
-        mean[0] = ((W - Lo + 6 * 128) << 15) // (6 * 128)
-        sigma = {a: ((vo + 6) * scale * mean[a]) >> 16 for a in range(54)}
-        assert np.array_equal(got["target"][0], exact_target({a: int(logits[a]) for a in range(54)}, sigma)), (vo, scale)
+        (st, tm), mask, net, params, expect = root_value_edge_case(q_raw, vo, scale)
+        expect(run(GUMBEL, "cpu", st, tm, mask, params, net))
 
 
 def test_sigma_at_its_largest_stays_inside_uint32(cpu):
-    """visit_offset 255, scale 64, 512 iterations under one considered action that wins at once: (255 + 512) * 64 * 65536 = 3 217 031 168,
-    above 2^31 and below 2^32; sigma = 49 088, every other action lies more than 255 below and keeps the floor byte."""
-    s, m = SR.play(SR.WIN_SEQ)
-    logits = np.zeros(54, np.int64)
-    logits[SR.WIN_ACTION] = 9
-    got = run(GUMBEL, "cpu", s[None], np.array([m], np.int8), None, (512, EXPLORE, 1, 0, 255, 64, 0, 0, 0), R.logit_dial(logits))
-    assert got["visits"][0, SR.WIN_ACTION] == 512 and got["wins"][0, SR.WIN_ACTION] == 512 * 128 and got["action"][0] == SR.WIN_ACTION
-    legal = np.flatnonzero(oracle.legal_mask(s, m))
-    sigma = {int(a): (767 * 64 * 32768) >> 16 for a in legal}
-    sigma[SR.WIN_ACTION] = (767 * 64 * 65536) >> 16
-    assert sigma[SR.WIN_ACTION] == 49088 and 767 * 64 * 65536 >= 1 << 31
-    row = exact_target({int(a): int(logits[a]) - 9 for a in legal}, sigma)
-    assert np.array_equal(got["target"][0], row) and row[SR.WIN_ACTION] == 254 and (row[legal] >= 1).all()
+    """tests/gumbel_harness.py::sigma_edge_case on the host flavour: sigma = 49 088 from a product above 2^31, the floor byte elsewhere."""
+    (st, tm), mask, net, params, expect = sigma_edge_case()
+    expect(run(GUMBEL, "cpu", st, tm, mask, params, net))
 
 
 # ---- 7. self-play -------------------------------------------------------------------------------------------------------------------------------
