@@ -13,6 +13,7 @@
     GobbletTrainer   the float network behind GobbletEvaluator.from_float and its Adam step on the device (BatchedGobblet.fit)
     ReplayBuffer     a ring of compacted training rows on the device: windows appended, exact symmetry-augmented draws, fit;
                      ReplayBuffer.reanalyse / GobbletEvaluator.reanalyse: stored rows' visits from the current network's search
+                     (gumbel=dict(...): the Gumbel root search's target rows, from 16 iterations)
     Tablebase        the game solved outright, one byte per position: retrograde sweeps and probes; TablebaseGobbletPolicy plays from it
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in

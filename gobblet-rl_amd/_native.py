@@ -129,6 +129,7 @@ SIGNATURES = {
     "gbl_tb_probe": (_int, [_vp] * 9 + [_i64, _vp]),
     "gbl_tb_targets": (_int, [_vp] * 4 + [_i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int] + [_vp] * 3 + [_i64, _vp]),
     "gbl_reanalyse": (_int, [_vp, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _vp]),
+    "gbl_reanalyse_gumbel": (_int, [_vp] + [_int] * 6 + [_u64, _u64, _u32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7 + [_i64, _vp]),
     "gbl_train_workspace_bytes": (_i64, [_i64, _int]),
     "gbl_train_step": (_int, [_vp] * 4 + [_i64, _int] + [_vp] * 7 + [_i64, _vp]),
     "gbl_train_step_weighted": (_int, [_vp] * 4 + [_i64, _int] + [_vp] * 7 + [C.c_float, C.c_int32, C.c_int32] + [_vp] * 3 + [_i64, _vp]),

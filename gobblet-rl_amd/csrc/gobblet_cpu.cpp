@@ -1817,28 +1817,36 @@ int gbl_cpu_tb_targets(const int32_t *inventory, const void *aux, const int8_t *
 }
 
 // Reanalysis (include/gobblet_hip.h, "Reanalysis"): decode_obs_row, host_tree_search_eval and the rule's scalar pieces, row by row.  The
-// visits rows go through memcpy: the host flavour asks no alignment of them.
-int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
-                      int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
-                      int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
-                      int32_t *drift_out, int8_t *census_out, int64_t n, void *)
+// visits rows go through memcpy: the host flavour asks no alignment of them.  gum: gbl_cpu_reanalyse_gumbel's arguments (nullptr:
+// gbl_cpu_reanalyse) -- the root follows the Gumbel rule (GumbelRoot, board id env_base + r), the row's new entries are the target bytes
+// and the drift's sum is 64-bit.
+static int host_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const ReanalyseGumbelCheck *gum, uint64_t seed,
+                          const int8_t *obs, int64_t obs_pitch, const int8_t *mask, int64_t mask_pitch, const int16_t *visits_in,
+                          int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int64_t z_pitch, int32_t *root_value_out,
+                          uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out, int32_t *drift_out, int8_t *census_out, int64_t n)
 {
     bool empty;
     if (const char *why = reanalyse_error(ev, iterations, explore, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
-                                          z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n, &empty))
+                                          z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n, &empty, gum))
         return fail(GBL_ERR_ARG, why);
     if (empty) return GBL_OK;
     const EvalNet net = eval_net(ev);
     const char *vin = reinterpret_cast<const char *>(visits_in);
     char *vout = reinterpret_cast<char *>(visits_out);
+    const bool rule = gum != nullptr;
+    const ReanalyseGumbelCheck g = rule ? *gum : ReanalyseGumbelCheck{};
+    char *const gout = reinterpret_cast<char *>(const_cast<void *>(g.gumbel_out));
     parallel_for(n, [=](int64_t r0, int64_t r1) {  // (a row is a whole search: every row is worth a thread)
         std::vector<TreeNode> nodes((size_t)iterations + 1);
         std::vector<uint8_t> pri(((size_t)iterations + 1) * kEvalOutputs);
         HostSearch h;
+        HostGumbel gb{GumbelArgs{(uint32_t)g.considered, (uint32_t)g.gumbel_noise, (uint32_t)g.visit_offset, (uint32_t)g.scale}, seed, 0, g.call,
+                      -1, {}, {}};
         for (int64_t r = r0; r < r1; ++r) {
             const int z_old = z_in ? (int)z_in[r * z_pitch] : 0;
             int q = 0, action = -1, drift = -1, census = -1, count = 0;
             uint8_t pi[kActions] = {};
+            memset(gb.gum, 0, sizeof gb.gum);
             if (!(z_in && z_old == kZOpen)) {
                 uint32_t d[30], row[7];
                 d[29] = 0;
@@ -1847,25 +1855,28 @@ int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, cons
                 const Planes p = make_planes(row);
                 uint64_t cand = legal54(p, mover);
                 if (mask) cand &= read_mask(mask + r * mask_pitch);
-                q = host_tree_search_eval(nodes, pri, net, p, mover, cand, (uint32_t)iterations, (uint32_t)explore, h, HostNoise{0, 0, 0, 0, pi});
-                action = tree_action_of(h.best);
+                gb.g = g.env_base + (uint64_t)r;
+                q = host_tree_search_eval(nodes, pri, net, p, mover, cand, (uint32_t)iterations, (uint32_t)explore, h, HostNoise{0, 0, 0, 0, pi},
+                                          rule ? &gb : nullptr);
+                action = rule ? gb.action : tree_action_of(h.best);
                 count = (int)h.count;
                 int16_t old[kActions] = {}, now[kActions];
                 if (visits_in) memcpy(old, vin + r * visits_pitch * 2, sizeof old);  // (read before the row is written: it may be the same row)
-                uint32_t So = 0, Sn = 0, diff = 0, top_old = 0, top_new = 0;
+                uint32_t So = 0, Sn = 0, top_old = 0, top_new = 0;
+                uint64_t diff = 0;
                 for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
-                    now[a] = (int16_t)h.visits[a];
+                    now[a] = (int16_t)(rule ? (uint32_t)gb.target[a] : h.visits[a]);
                     So += (uint32_t)std::max<int>(old[a], 0);
-                    Sn += (uint32_t)h.visits[a];
+                    Sn += (uint32_t)now[a];
                 }
                 for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
-                    const uint32_t x = (uint32_t)std::max<int>(old[a], 0) * Sn, y = (uint32_t)h.visits[a] * So;
+                    const uint32_t x = (uint32_t)std::max<int>(old[a], 0) * Sn, y = (uint32_t)now[a] * So;
                     diff += x > y ? x - y : y - x;
                     top_old = std::max(top_old, tb_visit_key(old[a], a));
                     top_new = std::max(top_new, tb_visit_key(now[a], a));
                 }
                 if (cand) {
-                    drift = reanalyse_drift(visits_in != nullptr, So, Sn, diff);
+                    drift = rule ? reanalyse_drift64(visits_in != nullptr, So, Sn, diff) : reanalyse_drift(visits_in != nullptr, So, Sn, (uint32_t)diff);
                     census = reanalyse_census(top_old, top_new, z_in != nullptr, z_old, q);
                 }
                 if (visits_out) memcpy(vout + r * visits_pitch * 2, now, sizeof now);
@@ -1876,9 +1887,30 @@ int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, cons
             if (nodes_out) nodes_out[r] = count;
             if (drift_out) drift_out[r] = drift;
             if (census_out) census_out[r] = (int8_t)census;
+            if (gout) memcpy(gout + r * kActions * 2, gb.gum, sizeof gb.gum);
         }
     }, 1);
     return GBL_OK;
+}
+
+int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                      int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                      int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
+                      int32_t *drift_out, int8_t *census_out, int64_t n, void *)
+{
+    return host_reanalyse(ev, iterations, explore, nullptr, 0, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in, z_pitch,
+                          root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n);
+}
+
+int gbl_cpu_reanalyse_gumbel(const gbl_evaluator *ev, int iterations, int explore, int considered, int gumbel_noise, int visit_offset,
+                             int scale, uint64_t seed, uint64_t env_base, uint32_t call, const int8_t *obs, int64_t obs_pitch,
+                             const int8_t *mask, int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch,
+                             const int8_t *z_in, int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out,
+                             int32_t *nodes_out, int32_t *drift_out, int8_t *census_out, int16_t *gumbel_out, int64_t n, void *)
+{
+    const ReanalyseGumbelCheck check{considered, gumbel_noise, visit_offset, scale, env_base, call, gumbel_out};
+    return host_reanalyse(ev, iterations, explore, &check, seed, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
+                          z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n);
 }
 
 }  // extern "C"

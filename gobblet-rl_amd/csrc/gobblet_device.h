@@ -3759,6 +3759,14 @@ __device__ __forceinline__ int reanalyse_drift(bool has_old, uint32_t So, uint32
     if (!So) return 1024;
     return (int)((1024ull * (uint64_t)diff) / (2ull * (uint64_t)So * (uint64_t)Sn));
 }
+// gbl_reanalyse_gumbel's drift: the same quotient over the target bytes, Sn <= 54 * 255 -- single terms still fit 32 bits (at most
+// 32767 * 13770), their sum (at most 2 So Sn, about 4.9e10) does not: diff and the divisor are 64-bit, the product by 1024 (5e13) fits
+__device__ __forceinline__ int reanalyse_drift64(bool has_old, uint32_t So, uint32_t Sn, uint64_t diff)
+{
+    if (!has_old) return -1;
+    if (!So) return 1024;
+    return (int)((1024ull * diff) / (2ull * (uint64_t)So * (uint64_t)Sn));
+}
 // the census byte of a row with a candidate: `top_old` / `top_new` the largest tb_visit_key of the old visits (0: none positive, or no
 // visits_in) and of the new ones (never 0: every iteration visits a child of the root); tb_census with the new argmax as the only kept action
 __device__ __forceinline__ int reanalyse_census(uint32_t top_old, uint32_t top_new, bool has_z, int z_old, int root_q)
@@ -3766,17 +3774,32 @@ __device__ __forceinline__ int reanalyse_census(uint32_t top_old, uint32_t top_n
     return tb_census(top_old, 1ull << (63u - (top_new & 63u)), has_z, z_old, tb_sign(root_q));
 }
 
-// the message of the first rule a gbl_reanalyse call breaks, or nullptr; *empty = the call has nothing to do (n == 0 after the scalar checks)
+// the message of the first rule a gbl_reanalyse call breaks, or nullptr; *empty = the call has nothing to do (n == 0 after the scalar checks).
+// gum: gbl_reanalyse_gumbel's own arguments (nullptr: gbl_reanalyse) -- call in front of n < 0, the board ids and the rule's four behind
+// it, and gumbel_out among the outputs.
+struct ReanalyseGumbelCheck {
+    int considered, gumbel_noise, visit_offset, scale;
+    uint64_t env_base;
+    uint32_t call;
+    const void *gumbel_out;
+};
 template <typename Ev>
 inline const char *reanalyse_error(const Ev *ev, int iterations, int explore, const void *obs, int64_t obs_pitch, const void *mask,
                                    int64_t mask_pitch, const void *visits_in, const void *visits_out, int64_t visits_pitch, const void *z_in,
                                    int64_t z_pitch, const void *root_value_out, const void *root_priors_out, const void *action_out,
-                                   const void *nodes_out, const void *drift_out, const void *census_out, int64_t n, bool *empty)
+                                   const void *nodes_out, const void *drift_out, const void *census_out, int64_t n, bool *empty,
+                                   const ReanalyseGumbelCheck *gum = nullptr)
 {
     *empty = false;
+    const void *gumbel_out = gum ? gum->gumbel_out : nullptr;
     if (const char *why = evaluator_error(ev)) return why;
     if (const char *why = tree_eval_budget_error(iterations, explore)) return why;
+    if (gum && gum->call >= (1u << 24)) return "call must be below 2^24";
     if (n < 0) return "n < 0";
+    if (gum) {
+        if (const char *why = env_range_error(gum->env_base, n)) return why;
+        if (const char *why = gumbel_error(gum->considered, gum->gumbel_noise, gum->visit_offset, gum->scale)) return why;
+    }
     if (obs_pitch < kObs) return "obs_pitch must be at least 117";
     if (mask && mask_pitch < kActions) return "mask_pitch must be at least 54";
     if ((visits_in || visits_out) && visits_pitch < kActions) return "visits_pitch must be at least 54";
@@ -3787,7 +3810,7 @@ inline const char *reanalyse_error(const Ev *ev, int iterations, int explore, co
     }
     if (const char *why = evaluator_pointers_error(ev)) return why;
     if (!obs) return "obs must not be NULL";
-    if (!visits_out && !root_value_out && !root_priors_out && !action_out && !nodes_out && !drift_out && !census_out)
+    if (!visits_out && !root_value_out && !root_priors_out && !action_out && !nodes_out && !drift_out && !census_out && !gumbel_out)
         return "at least one output must be given";
     // every output against every input; visits_in == visits_out is the in-place form (that one pair is let through: the other outputs
     // are still checked against visits_in).  The evaluator's arrays are single rows.
@@ -3796,10 +3819,10 @@ inline const char *reanalyse_error(const Ev *ev, int iterations, int explore, co
                           tb_span(visits_in, visits_pitch, kActions, 2), tb_span(z_in, z_pitch, 1, 1),
                           tb_span(ev->w1, 0, (int64_t)kObs * H, 1), tb_span(ev->b1, 0, H, 4), tb_span(ev->w2, 0, H * kEvalOutputs, 1),
                           tb_span(ev->b2, 0, kEvalOutputs, 4)};
-    const TbSpan out[7] = {tb_span(visits_out, visits_pitch, kActions, 2), tb_span(root_value_out, 1, 1, 4),
+    const TbSpan out[8] = {tb_span(visits_out, visits_pitch, kActions, 2), tb_span(root_value_out, 1, 1, 4),
                            tb_span(root_priors_out, kActions, kActions, 1), tb_span(action_out, 1, 1, 4), tb_span(nodes_out, 1, 1, 4),
-                           tb_span(drift_out, 1, 1, 4), tb_span(census_out, 1, 1, 1)};
-    for (int o = 0; o < 7; ++o)
+                           tb_span(drift_out, 1, 1, 4), tb_span(census_out, 1, 1, 1), tb_span(gumbel_out, kActions, kActions, 2)};
+    for (int o = 0; o < 8; ++o)
         for (int i = 0; i < 8; ++i) {
             if (o == 0 && i == 2 && visits_in == visits_out) continue;
             const bool one = i >= 4;

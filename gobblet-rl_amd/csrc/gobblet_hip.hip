@@ -3239,7 +3239,19 @@ struct ReanalyseArgs {
     uint32_t iterations, explore;
 };
 
-__global__ __launch_bounds__(64) void k_reanalyse(ReanalyseArgs a)
+// GUMBEL: gbl_reanalyse_gumbel -- the root follows the Gumbel rule (tree_eval_iterations<false, true>, board id env_base + r), the
+// decision and the row's new bytes come from wave_gumbel_finish on the same read-out: lane a stores its target byte where the other form
+// stores its child's visits.  Sn can now reach 54 * 255, so the sum of the |o_a Sn - n_a So| (each still below 2^29) is taken in two
+// 16-bit halves and the drift in 64 bits (reanalyse_drift64); nothing else differs.  The other form's arguments stay as they were.
+struct ReanalyseGumbelArgs : ReanalyseArgs {
+    GumbelArgs G;
+    uint64_t seed, env_base;
+    uint32_t call;
+    int16_t *gumbel_out;
+};
+
+template <bool GUMBEL>
+__global__ __launch_bounds__(64) void k_reanalyse(const std::conditional_t<GUMBEL, ReanalyseGumbelArgs, ReanalyseArgs> a)
 {
     extern __shared__ uint4 s_tree[];
     TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
@@ -3250,25 +3262,41 @@ __global__ __launch_bounds__(64) void k_reanalyse(ReanalyseArgs a)
     for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
         const int z_old = a.z_in ? uniform((int)a.z_in[r * a.z_pitch]) : 0;
         int q = 0, action = -1, drift = -1, census = -1;
+        [[maybe_unused]] int gum = 0;
         uint32_t count = 0, pi = 0;
         if (!(a.z_in && z_old == kZOpen)) {  // (uniform) a skipped row writes no visits
             int mover;
             const Planes root = obs_planes(a.obs + r * a.obs_pitch, lane, mover);
             const uint64_t cand = board_candidates(root, mover, a.mask ? a.mask + r * a.mask_pitch : nullptr, 0, lane);
-            uint32_t mixed;
-            const WaveEval at_root = tree_eval_iterations<false>(nodes, pri, s_h, a.net, root, mover, cand, a.iterations, a.explore, lane, count,
-                                                                 RootNoise{}, mixed);
-            const TreeChild c = tree_lane_child(nodes, nodes[0].child, lane);
-            const uint32_t now = c.visits();
-            action = tree_action_of(wave_max(c.mine() ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
+            uint32_t mixed, now;
+            WaveEval at_root;
+            if constexpr (GUMBEL) {
+                WaveGumbel gb{a.G, a.seed, a.env_base + (uint64_t)r, a.call, 0, 0, 0ull};
+                at_root = tree_eval_iterations<false, true>(nodes, pri, s_h, a.net, root, mover, cand, a.iterations, a.explore, lane, count,
+                                                            RootNoise{}, mixed, &gb);
+                GumbelOut out{-1, 0u};
+                if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), cand, at_root.q, lane);
+                now = out.target;
+                action = out.action;
+                gum = gb.gum;
+            } else {
+                at_root = tree_eval_iterations<false>(nodes, pri, s_h, a.net, root, mover, cand, a.iterations, a.explore, lane, count, RootNoise{},
+                                                      mixed);
+                const TreeChild c = tree_lane_child(nodes, nodes[0].child, lane);
+                now = c.visits();
+                action = tree_action_of(wave_max(c.mine() ? tree_final_key(c.n, c.w, c.l, lane) : 0ull));
+            }
             q = at_root.q;
             pi = at_root.pi;
             if (cand && (a.drift_out || a.census_out)) {  // (uniform)
                 const uint32_t old = a.visits_in && act ? (uint32_t)max((int)a.visits_in[r * a.visits_pitch + lane], 0) : 0u;
                 const uint32_t So = wave_sum(old), Sn = wave_sum(now);
                 if (a.drift_out) {
-                    const uint32_t x = old * Sn, y = now * So;
-                    drift = reanalyse_drift(a.visits_in != nullptr, So, Sn, wave_sum(x > y ? x - y : y - x));
+                    const uint32_t x = old * Sn, y = now * So, d = x > y ? x - y : y - x;
+                    if constexpr (GUMBEL)
+                        drift = reanalyse_drift64(a.visits_in != nullptr, So, Sn, ((uint64_t)wave_sum(d >> 16) << 16) + wave_sum(d & 0xFFFFu));
+                    else
+                        drift = reanalyse_drift(a.visits_in != nullptr, So, Sn, wave_sum(d));
                 }
                 if (a.census_out)
                     census = reanalyse_census(wave_max(tb_visit_key((int)old, lane)), wave_max(tb_visit_key((int)now, lane)), a.z_in != nullptr,
@@ -3278,6 +3306,8 @@ __global__ __launch_bounds__(64) void k_reanalyse(ReanalyseArgs a)
             wave_lds_fence();  // (before the next row rewrites the root)
         }
         if (a.root_priors_out && act) a.root_priors_out[r * kActions + lane] = (uint8_t)pi;
+        if constexpr (GUMBEL)
+            if (a.gumbel_out && act) a.gumbel_out[r * kActions + lane] = (int16_t)gum;
         if (lane == 0) {
             if (a.root_value_out) a.root_value_out[r] = q;
             if (a.action_out) a.action_out[r] = action;
@@ -5881,6 +5911,28 @@ int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *tabl
     GBL_LAUNCHED("gbl_tb_targets");
 }
 
+}  // extern "C"
+
+// what gbl_reanalyse and gbl_reanalyse_gumbel do once their arguments have passed reanalyse_error: the network, the alignments, the launch
+template <bool GUMBEL, typename Args>
+static int reanalyse_launch(const gbl_evaluator *ev, Args A, void *stream, const char *what)
+{
+    if (const int e = eval_net_of(ev, A.net)) return e;
+    if (reinterpret_cast<uintptr_t>(A.visits_in) & 1u) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(A.visits_out) & 1u) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
+    if (off_dword(A.root_value_out, A.action_out, A.nodes_out, A.drift_out))
+        return fail(GBL_ERR_ALIGN, "root_value_out / action_out / nodes_out / drift_out must be 4-byte aligned");
+    if constexpr (GUMBEL)
+        if (reinterpret_cast<uintptr_t>(A.gumbel_out) & 1u) return fail(GBL_ERR_ALIGN, "gumbel_out must be 2-byte aligned");
+    // the tree as gbl_tree_search_eval's: a node and a prior row per iteration, and the root's (the rule keeps no LDS)
+    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)A.iterations + 1);
+    const int64_t groups = std::min<int64_t>(A.n, knob::kReanalyseGroups);
+    hipLaunchKernelGGL(k_reanalyse<GUMBEL>, dim3((uint32_t)groups), dim3(64), lds, (hipStream_t)stream, A);
+    GBL_LAUNCHED(what);
+}
+
+extern "C" {
+
 int gbl_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
                   int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in, int64_t z_pitch,
                   int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out, int32_t *drift_out,
@@ -5891,19 +5943,31 @@ int gbl_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const in
                                           z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n, &empty))
         return fail(GBL_ERR_ARG, why);
     if (empty) return GBL_OK;
-    EvalNet net;
-    if (const int e = eval_net_of(ev, net)) return e;
-    if (reinterpret_cast<uintptr_t>(visits_in) & 1u) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(visits_out) & 1u) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
-    if (off_dword(root_value_out, action_out, nodes_out, drift_out))
-        return fail(GBL_ERR_ALIGN, "root_value_out / action_out / nodes_out / drift_out must be 4-byte aligned");
-    const ReanalyseArgs A{net, obs, mask, visits_in, visits_out, z_in, root_value_out, root_priors_out, action_out, nodes_out, drift_out,
-                          census_out, obs_pitch, mask_pitch, visits_pitch, z_pitch, n, (uint32_t)iterations, (uint32_t)explore};
-    // the tree as gbl_tree_search_eval's: a node and a prior row per iteration, and the root's
-    const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);
-    const int64_t groups = std::min<int64_t>(n, knob::kReanalyseGroups);
-    hipLaunchKernelGGL(k_reanalyse, dim3((uint32_t)groups), dim3(64), lds, (hipStream_t)stream, A);
-    GBL_LAUNCHED("gbl_reanalyse");
+    return reanalyse_launch<false>(ev, ReanalyseArgs{EvalNet{}, obs, mask, visits_in, visits_out, z_in, root_value_out, root_priors_out, action_out,
+                                                     nodes_out, drift_out, census_out, obs_pitch, mask_pitch, visits_pitch, z_pitch, n,
+                                                     (uint32_t)iterations, (uint32_t)explore},
+                                   stream, "gbl_reanalyse");
+}
+
+int gbl_reanalyse_gumbel(const gbl_evaluator *ev, int iterations, int explore, int considered, int gumbel_noise, int visit_offset, int scale,
+                         uint64_t seed, uint64_t env_base, uint32_t call, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                         int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                         int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
+                         int32_t *drift_out, int8_t *census_out, int16_t *gumbel_out, int64_t n, void *stream)
+{
+    bool empty;
+    const ReanalyseGumbelCheck check{considered, gumbel_noise, visit_offset, scale, env_base, call, gumbel_out};
+    if (const char *why = reanalyse_error(ev, iterations, explore, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z_in,
+                                          z_pitch, root_value_out, root_priors_out, action_out, nodes_out, drift_out, census_out, n, &empty,
+                                          &check))
+        return fail(GBL_ERR_ARG, why);
+    if (empty) return GBL_OK;
+    return reanalyse_launch<true>(
+        ev, ReanalyseGumbelArgs{{EvalNet{}, obs, mask, visits_in, visits_out, z_in, root_value_out, root_priors_out, action_out, nodes_out,
+                                 drift_out, census_out, obs_pitch, mask_pitch, visits_pitch, z_pitch, n, (uint32_t)iterations, (uint32_t)explore},
+                                GumbelArgs{(uint32_t)considered, (uint32_t)gumbel_noise, (uint32_t)visit_offset, (uint32_t)scale},
+                                seed, env_base, call, gumbel_out},
+        stream, "gbl_reanalyse_gumbel");
 }
 
 int64_t gbl_train_workspace_bytes(int64_t batch, int hidden) { return train_workspace_bytes(batch, hidden); }

@@ -141,21 +141,35 @@ class GobbletEvaluator(_OnDevice):
 
     # ---- reanalysis: fresh search targets for stored rows ---------------------------------------------------------------------------
     def _reanalyse(self, n, obs, obs_pitch, mask, mask_pitch, visits_in, visits_out, visits_pitch, z, z_pitch, iterations, explore, census,
-                   root_value=None):
-        """One launch of ``gbl_reanalyse`` on ``n`` pitched rows (data pointers); returns (drift int32 (n,), census int8 (n,) or None)."""
+                   root_value=None, gumbel=None, seed=0, env_base=0, call=0, gumbel_out=None):
+        """One launch of ``gbl_reanalyse`` -- with ``gumbel`` (``gumbel_args``' dict) of ``gbl_reanalyse_gumbel`` -- on ``n`` pitched rows
+        (data pointers); returns (drift int32 (n,), census int8 (n,) or None)."""
         for name, val, lo, hi in (("iterations", iterations, 1, 512), ("explore", explore, 0, 1024)):
             if not lo <= int(val) <= hi:
                 raise ValueError(f"{name} must be in [{lo}, {hi}]")
+        if gumbel is not None:
+            if not 0 <= int(call) < 1 << 24:
+                raise ValueError("call must be in [0, 2^24)")
+            if int(env_base) < 0 or int(env_base) + n > 1 << 42:
+                raise ValueError("env_base + the rows must not exceed 2^42")
         drift = torch.empty(n, dtype=torch.int32, device=self.device)
         tally = torch.empty(n, dtype=torch.int8, device=self.device) if census else None
         ev = self.as_struct()
         with self._on_device():
-            nat.check(self._lib.gbl_reanalyse(C.addressof(ev), int(iterations), int(explore), obs, obs_pitch, mask, mask_pitch, visits_in,
-                                              visits_out, visits_pitch, z, z_pitch, nat.ptr(root_value), None, None, None, drift.data_ptr(),
-                                              nat.ptr(tally), n, self._stream()), "gbl_reanalyse")
+            if gumbel is not None:
+                nat.check(self._lib.gbl_reanalyse_gumbel(
+                    C.addressof(ev), int(iterations), int(explore), gumbel["considered"], gumbel["noise"], gumbel["visit_offset"],
+                    gumbel["scale"], int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_base), int(call), obs, obs_pitch, mask, mask_pitch, visits_in,
+                    visits_out, visits_pitch, z, z_pitch, nat.ptr(root_value), None, None, None, drift.data_ptr(), nat.ptr(tally),
+                    nat.ptr(gumbel_out), n, self._stream()), "gbl_reanalyse_gumbel")
+            else:
+                nat.check(self._lib.gbl_reanalyse(C.addressof(ev), int(iterations), int(explore), obs, obs_pitch, mask, mask_pitch, visits_in,
+                                                  visits_out, visits_pitch, z, z_pitch, nat.ptr(root_value), None, None, None, drift.data_ptr(),
+                                                  nat.ptr(tally), n, self._stream()), "gbl_reanalyse")
         return drift, tally
 
-    def reanalyse(self, batch: dict, iterations: int = 64, explore: int = 16, census: bool = False, out: torch.Tensor | None = None) -> dict:
+    def reanalyse(self, batch: dict, iterations: int = 64, explore: int = 16, census: bool = False, out: torch.Tensor | None = None,
+                  gumbel: dict | None = None, seed: int = 0, call: int = 0, env_base: int = 0) -> dict:
         """This network's search run again on the rows of the dict ``BatchedGobblet.training_batch`` / ``ReplayBuffer.batch`` return, one
         launch of ``gbl_reanalyse``: returns a copy of the dict whose "visits" are the new search's visit counts (``gbl_tree_search_eval``
         with ``iterations`` and ``explore`` on the position each observation holds, under the row's mask; no noise, no solver guard) in a
@@ -164,9 +178,17 @@ class GobbletEvaluator(_OnDevice):
         the root's q in 1/128 of a win for the mover, "drift" int32 (N,), the total variation between the old and the new visit shares
         in 1/1024 (1024: the old row had nothing positive; -1: a skipped row or one without a candidate) and, with ``census``, "census"
         int8 (N,) (include/gobblet_hip.h, "Reanalysis": bit 0 the old argmax is the new one, bit 1 the sign of the root's q equals z,
-        bit 2 there were no old visits; -1 where drift is)."""
+        bit 2 there were no old visits; -1 where drift is).
+
+        gumbel: ``dict(considered=16, noise=True, visit_offset=50, scale=23)`` (``EvaluatorTreeSearchGobbletPolicy``'s keys, defaults and
+        checks) makes it one launch of ``gbl_reanalyse_gumbel``: the search is the Gumbel root search, made for budgets such as
+        ``iterations=16``, and "visits" become its target rows -- the completed-Q policy, 1 .. 255 on every candidate, what
+        ``collect(search=dict(gumbel=...))`` stores.  The noise of row r is keyed by (``seed``, ``env_base`` + r, ``call``);
+        ``noise=False`` draws nothing.  Adds "gumbel" int16 (N, 54), the noise g.  "drift" and "census" compare the old row with the
+        target row."""
         if "observation" not in batch:
             raise ValueError("reanalyse needs the 'observation' entry: a window or a buffer with observations")
+        rule = None if gumbel is None else gumbel_args(gumbel)
         obs, mask, visits, z = batch["observation"], batch.get("action_mask"), batch["visits"], batch["z"]
         n = int(z.shape[0])
         spec = (("observation", obs, (n, nat.OBS_BYTES), torch.int8), ("action_mask", mask, (n, nat.ACTIONS), torch.int8),
@@ -177,11 +199,14 @@ class GobbletEvaluator(_OnDevice):
         if out is None:
             out = visits.clone()  # (a skipped row keeps what it held)
         value = torch.empty(n, dtype=torch.int32, device=self.device)
+        noise = None if rule is None else torch.empty((n, nat.ACTIONS), dtype=torch.int16, device=self.device)
         drift, tally = self._reanalyse(n, obs.data_ptr(), nat.OBS_BYTES, nat.ptr(mask), nat.ACTIONS, visits.data_ptr(), out.data_ptr(),
-                                       nat.ACTIONS, z.data_ptr(), 1, iterations, explore, census, value)
+                                       nat.ACTIONS, z.data_ptr(), 1, iterations, explore, census, value, rule, seed, env_base, call, noise)
         fresh = dict(batch, visits=out, root_value=value, drift=drift)
         if census:
             fresh["census"] = tally
+        if rule is not None:
+            fresh["gumbel"] = noise
         return fresh
 
 

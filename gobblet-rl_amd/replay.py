@@ -12,6 +12,7 @@ import torch
 
 from . import _native as nat
 from ._policy_base import _OnDevice
+from .evaluator_policy import gumbel_args
 from .vector_env import BatchedGobblet
 
 MAX_CAPACITY = (1 << 31) - 1
@@ -264,16 +265,22 @@ class ReplayBuffer(_OnDevice):
                            self._visits.data_ptr(), nat.REPLAY_VISITS_PITCH, self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH,
                            mode, count, census, None, allow_incomplete)
 
-    def reanalyse(self, evaluator, iterations: int = 64, explore: int = 16, census: bool = False, prioritize: dict | None = None) -> dict:
+    def reanalyse(self, evaluator, iterations: int = 64, explore: int = 16, census: bool = False, prioritize: dict | None = None,
+                  gumbel: dict | None = None, seed: int = 0, call: int = 0) -> dict:
         """Fresh search targets for the ring's live rows, in place: one launch of ``gbl_reanalyse`` over the ring's own arrays through
         their pitches -- the visits of every live row become the visit counts of ``evaluator``'s search (``GobbletEvaluator.reanalyse``
         has the rule) on the position the row's observation holds.  The live rows are ``relabel``'s: every slot once the ring has
         wrapped and the first ``total`` slots before; z, mover bytes, tags, masks, observations and padding are not touched.  Returns
         ``dict(drift=int32 (live rows,), census=int8 (live rows,) or None)`` in slot order.  ``prioritize=dict(floor=1, scale=1)`` (a
         prioritised buffer): every live row's priority becomes ``floor + scale * max(drift, 0)`` on the device (``set_priority``'s
-        path), so rows whose targets moved furthest are drawn first.  Reads ``total`` from the device, nothing else."""
+        path), so rows whose targets moved furthest are drawn first.  Reads ``total`` from the device, nothing else.
+        ``gumbel=dict(considered=16, noise=True, visit_offset=50, scale=23)``: one launch of ``gbl_reanalyse_gumbel`` instead -- the
+        rows become the Gumbel root search's target rows (``GobbletEvaluator.reanalyse`` has the rule), the kind of row a ring filled by
+        ``collect(search=dict(gumbel=...))`` holds; the noise of a row is keyed by (``seed``, its slot, ``call``).  ``prioritize`` works
+        unchanged on the new drift."""
         if self._obs is None:
             raise ValueError("reanalyse needs a buffer with observations")
+        rule = None if gumbel is None else gumbel_args(gumbel)
         if torch.device(evaluator.device) != self.device:
             raise ValueError("reanalyse: the evaluator lives on %s and the buffer on %s" % (evaluator.device, self.device))
         if prioritize is not None:
@@ -286,7 +293,8 @@ class ReplayBuffer(_OnDevice):
         live = self.size
         drift, tally = evaluator._reanalyse(live, self._obs.data_ptr(), nat.REPLAY_OBS_PITCH, self._meta.data_ptr(), nat.REPLAY_META_PITCH,
                                             self._visits.data_ptr(), self._visits.data_ptr(), nat.REPLAY_VISITS_PITCH,
-                                            self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH, iterations, explore, census)
+                                            self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH, iterations, explore, census,
+                                            None, rule, seed, 0, call)
         if prioritize is not None and live:
             slots = torch.arange(live, dtype=torch.int32, device=self.device)
             self.set_priority(torch.stack([slots, torch.zeros_like(slots)], dim=1).contiguous(), floor + scale * drift.clamp(min=0))
@@ -309,7 +317,10 @@ class ReplayBuffer(_OnDevice):
         ``reanalyse``: ``dict(evaluator=, iterations=64, explore=16)`` with a ``GobbletEvaluator`` on this device -- every drawn batch goes
         through ``evaluator.reanalyse`` first (one more launch per step, ``gbl_reanalyse``, in ``targets``' place: the two exclude each
         other): the step learns from the visit counts of that network's search instead of the stored ones, z stays the game's outcome.
-        It composes with ``prioritized``, ``beta`` and ``priority``.  The drawn row is a symmetric image of the stored one, which is sound
+        It composes with ``prioritized``, ``beta`` and ``priority``.  With ``gumbel=dict(considered=16, noise=True, visit_offset=50,
+        scale=23)`` in the dict (and ``seed=0``) the launch is ``gbl_reanalyse_gumbel``'s: the step learns from the Gumbel root search's
+        target rows, made for ``iterations=16`` or fewer; step i's noise is keyed by (seed, the row's place in the batch,
+        ``first_call + i``), so every step's noise is fresh.  The drawn row is a symmetric image of the stored one, which is sound
         because the search commutes with the symmetries -- with ``gbl_symmetry_apply``'s caveat: check_for_winner's last-line-decides
         rule is not symmetric on boards where a move leaves lines of both colours, so under the squares' symmetries a search that
         reaches such a board may differ from the image of the stored row's search (``symmetries=None`` avoids it)."""
@@ -320,20 +331,22 @@ class ReplayBuffer(_OnDevice):
         if reanalyse is not None:
             if targets is not None:
                 raise ValueError("fit: targets= and reanalyse= exclude each other")
-            unknown = set(reanalyse) - {"evaluator", "iterations", "explore"}
-            if unknown or "evaluator" not in reanalyse:
-                raise ValueError("fit: reanalyse=dict(evaluator=, iterations=64, explore=16)")
+            unknown = set(reanalyse) - {"evaluator", "iterations", "explore", "gumbel", "seed"}
+            if unknown or "evaluator" not in reanalyse or ("seed" in reanalyse and reanalyse.get("gumbel") is None):
+                raise ValueError("fit: reanalyse=dict(evaluator=, iterations=64, explore=16, gumbel=None, seed=0) (seed goes with gumbel)")
+            rule = None if reanalyse.get("gumbel") is None else gumbel_args(reanalyse["gumbel"])
             if torch.device(reanalyse["evaluator"].device) != self.device:
                 raise ValueError("fit: the evaluator lives on %s and the buffer on %s" % (reanalyse["evaluator"].device, self.device))
             fresh = torch.zeros((int(batch), nat.ACTIONS), dtype=torch.int16, device=self.device)  # (reused: a skipped row counts for nothing)
 
-            def relabelled(rows):
-                return reanalyse["evaluator"].reanalyse(rows, reanalyse.get("iterations", 64), reanalyse.get("explore", 16), out=fresh)
+            def relabelled(rows, i):
+                return reanalyse["evaluator"].reanalyse(rows, reanalyse.get("iterations", 64), reanalyse.get("explore", 16), out=fresh, gumbel=rule,
+                                                        seed=reanalyse.get("seed", 0), call=int(first_call) + i)
         elif targets is not None:
-            def relabelled(rows):
+            def relabelled(rows, i):
                 return targets.targets(dict(rows))
         else:
-            def relabelled(rows):
+            def relabelled(rows, i):
                 return rows
         buf, stats = None, []
         if beta is not None or priority is not None:
@@ -342,7 +355,7 @@ class ReplayBuffer(_OnDevice):
             weights = None
             for i in range(steps):
                 buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=True)
-                rows = relabelled(buf)
+                rows = relabelled(buf, i)
                 if beta is not None:
                     b = float(beta) if ends is None else ends[0] + (ends[1] - ends[0]) * (i / (steps - 1) if steps > 1 else 0.0)
                     weights = self.batch_weights(buf, b, out=weights)
@@ -352,7 +365,7 @@ class ReplayBuffer(_OnDevice):
             return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
         for i in range(int(steps)):
             buf = self.batch(batch, symmetries=symmetries, call=int(first_call) + i, seed=seed, recent=recent, out=buf, prioritized=prioritized)
-            stats.append(trainer.step(relabelled(buf)))
+            stats.append(trainer.step(relabelled(buf, i)))
         return torch.stack(stats) if stats else torch.zeros((0, 4), dtype=torch.float32, device=self.device)
 
     def state_dict(self) -> dict:

@@ -227,6 +227,11 @@ int gbl_cpu_reanalyse(const gbl_evaluator *ev, int iterations, int explore, cons
                       int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
                       int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
                       int32_t *drift_out, int8_t *census_out, int64_t n, void *stream);
+int gbl_cpu_reanalyse_gumbel(const gbl_evaluator *ev, int iterations, int explore, int considered, int gumbel_noise, int visit_offset,
+                             int scale, uint64_t seed, uint64_t env_base, uint32_t call, const int8_t *obs, int64_t obs_pitch,
+                             const int8_t *mask, int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch,
+                             const int8_t *z_in, int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out,
+                             int32_t *nodes_out, int32_t *drift_out, int8_t *census_out, int16_t *gumbel_out, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

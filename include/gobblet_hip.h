@@ -1192,6 +1192,42 @@ int gbl_reanalyse(const gbl_evaluator *ev, int iterations, int explore, const in
                   int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out, int32_t *drift_out,
                   int8_t *census_out, int64_t n, void *stream);
 
+/* Reanalysis with the Gumbel root rule (no counterpart in the reference): gbl_reanalyse with gbl_tree_search_gumbel's search in the place
+ * of gbl_tree_search_eval's, so that a stored row's visits become the rule's TARGET ROW -- the completed-Q policy, a byte in 1 .. 255 on
+ * every candidate, the kind of row gbl_collect_search_gumbel stores -- from a budget of 8 .. 16 iterations.  One launch, no allocation, no
+ * atomics.  Integer-only, so the kernel, the host flavour and a restatement of this text agree byte for byte.
+ *   Rows, skipped rows, aliasing.  gbl_reanalyse's text unchanged: the pitches in ELEMENTS, a row whose z_in byte is GBL_Z_OPEN writes no
+ *     byte of its visits_out row, visits_in == visits_out is the in-place form, and every other byte an output shares with an input is
+ *     GBL_ERR_ARG; gumbel_out is one of the outputs there.
+ *   The search.  (state, to_move) = gbl_decode_obs of the row's 117 bytes; C = the row's mask bytes & the mover's legal mask (mask NULL:
+ *     the legal mask).  Then gbl_tree_search_gumbel's text unchanged on that board with the candidate set C, with ev, iterations, explore,
+ *     considered, gumbel_noise, visit_offset, scale and seed, the board id g = env_base + r (r the row's index in THIS call) and q = call.
+ *     With gumbel_noise == 0 nothing is drawn: the same rows and the same network give the same bytes.
+ *   visits_out[a] = (int16) target_a, the rule's target byte: 1 .. 255 on C, 0 elsewhere -- what gbl_collect_search_gumbel stores and
+ *     gbl_train_step reads unchanged.  A row with C empty gets 54 zeros.  visits_out may be NULL.
+ *   Dense outputs (each optional).  root_value_out, root_priors_out and nodes_out are the search's; action_out is the rule's DECISION
+ *     (with noise the sampled action); gumbel_out int16[n][54] = g_a (0 outside C, and all 0 without noise; 2-byte aligned).  A row with C
+ *     empty holds the root's q, zeros, 1, -1 and a zero Gumbel row; a skipped row 0, zeros, 0, -1 and a zero Gumbel row.
+ *     drift_out: gbl_reanalyse's formula with n_a = the new target bytes:
+ *         drift = (1024 * sum over a of |o_a * Sn - n_a * So|) / (2 * So * Sn)      an unsigned 64-bit division (floor)
+ *     and drift = 1024 where So == 0 (Sn >= 1 on a row with a candidate); -1 for a skipped row, a row with C empty or visits_in NULL.
+ *     Now Sn <= 54 * 255 = 13 770 and So <= 54 * 32 767: a single term o_a * Sn or n_a * So still fits 32 bits (at most 451 201 590),
+ *     but the sum can reach 2 So Sn, about 4.9e10, and does NOT: the sum and the divisor are unsigned 64-bit, and the product by 1024
+ *     (about 5e13) fits 64.  (That is the bytes' own range.  The target rule's bytes of one row sum to at most |C| + 254 <= 308, so a
+ *     row this entry point writes keeps the sum below 2^32; the arithmetic does not rest on it.)
+ *     census_out: gbl_reanalyse's byte; in bit 0 "the argmax of the new row" is the largest target byte, the lowest index on ties -- not
+ *     action_out.
+ *   Errors, in this order (GBL_ERR_ARG): the evaluator, iterations and explore as gbl_reanalyse; call >= 2^24; n < 0; env_base + n > 2^42;
+ *     considered outside 1 .. 54 (0 is no value here: that search is gbl_reanalyse), gumbel_noise, visit_offset and scale out of range as
+ *     gbl_tree_search_gumbel; a pitch smaller than its row; n == 0 returns GBL_OK here; then gbl_reanalyse's pointer and overlap checks
+ *     (gumbel_out counts as an output in both).  GBL_ERR_ALIGN (device flavour only): gbl_reanalyse's, then gumbel_out 2-byte.
+ *   The tree lives in 72 (iterations + 1) bytes of LDS per workgroup as before: the rule keeps two registers per lane. */
+int gbl_reanalyse_gumbel(const gbl_evaluator *ev, int iterations, int explore, int considered, int gumbel_noise, int visit_offset, int scale,
+                         uint64_t seed, uint64_t env_base, uint32_t call, const int8_t *obs, int64_t obs_pitch, const int8_t *mask,
+                         int64_t mask_pitch, const int16_t *visits_in, int16_t *visits_out, int64_t visits_pitch, const int8_t *z_in,
+                         int64_t z_pitch, int32_t *root_value_out, uint8_t *root_priors_out, int32_t *action_out, int32_t *nodes_out,
+                         int32_t *drift_out, int8_t *census_out, int16_t *gumbel_out, int64_t n, void *stream);
+
 /* Self-play with the tablebase (no counterpart in the reference): gbl_collect_search_noise with the exact table inside the launch, as a
  * third policy for either side and as a judge of every ply.  The arguments are gbl_collect_search_noise's, then
  *   inventory / aux / table   as gbl_tb_probe takes them (the table complete or not: a 0 reads "not proven by the sweeps done")
