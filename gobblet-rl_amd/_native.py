@@ -22,7 +22,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libgobblet_hip.so")
 _FOREIGN = False  # use_library() was called: LIB_PATH is somebody's own build, never rebuilt from here
 SOURCES = [os.path.join(CSRC, "gobblet_hip.hip"), os.path.join(CSRC, "gobblet_device.h"), os.path.join(CSRC, "gobblet_diag.h"),
-           os.path.join(CSRC, "gobblet_knobs.h"), os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
+           os.path.join(CSRC, "gobblet_knobs.h"), os.path.join(CSRC, "gobblet_selfplay_entries.inc"),
+           os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
 # -amdgpu-kernarg-preload-count: the first 16 dwords of a kernel's arguments arrive in SGPRs with the wave
 # launch (the kernels order their arguments for that), so a wavefront's first loads do not wait for a
 # kernel-argument fetch; firmware without the feature runs the compiler's fallback prologue
@@ -55,8 +56,62 @@ REC_BYTES = 432
 REC_FIELDS = {"squares": (0, 27), "winner": (28, 1), "flat": (32, 9), "covered": (44, 27), "mask0": (72, 54),
               "mask1": (128, 54), "obs0": (184, 117), "obs1": (304, 117)}
 
-# every symbol include/gobblet_hip.h declares: (name, restype, argtypes)
 _vp, _i64, _u64, _u32, _int = C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_int
+
+
+def _args(ctype, *names):
+    return tuple((name, ctype) for name in names)
+
+
+# The self-play family's argument lists, BY NAME, from the blocks include/gobblet_hip.h builds its seven declarations of:
+# symbol -> ((parameter name, ctype), ...) in the ABI's order.  SIGNATURES below, selfplay_call(), collect(), the tests' harness and
+# scripts/record_selfplay_arg_errors.py all take the order from here; tests/test_abi_and_host.py holds it against the header.
+_BOARDS = _args(_vp, "state", "to_move", "done")
+_TRAJ = _args(_vp, "actions_traj", "winner_traj", "reward_traj", "done_traj", "to_move_traj", "mask_traj", "obs_traj", "visits_traj",
+              "value_traj", "nodes_traj", "how_traj", "mover_traj")
+_TRAJ_EVAL = _TRAJ + _args(_vp, "root_value_traj", "priors_traj")   # (the evaluator search's two)
+_TRAJ_SOLVE = _TRAJ_EVAL + _args(_vp, "outcome_traj", "proven_traj")  # (the guard's two)
+_WINDOW = (("n", _i64), ("ply_stride", _i64), ("tile_stride", _i64), ("seed", _u64), ("env_base", _u64), ("ply0", _u32), ("ply_dev", _vp),
+           ("plies", _u32), ("policy0", _int), ("policy1", _int))
+_SIDES_EVAL = _args(_vp, "ev0", "ev1") + _args(_int, "iterations0", "iterations1")
+_SIDES_SOLVE = _SIDES_EVAL + _args(_int, "solve_depth0", "solve_depth1")
+_SIDES_NOISE = _SIDES_SOLVE + _args(_int, "noise0", "noise1")
+_TAIL = _args(_int, "explore", "sample_plies", "illegal_mode") + _args(_vp, "counters", "turn")
+_STREAM = _args(_vp, "stream")
+SELFPLAY_ARGS = {
+    "gbl_collect_search": _BOARDS + _TRAJ + _WINDOW + _args(_int, "iterations0", "iterations1", "playouts0", "playouts1", "max_plies") +
+                          _TAIL + _STREAM,
+    "gbl_collect_search_eval": _BOARDS + _TRAJ_EVAL + _WINDOW + _SIDES_EVAL + _TAIL + _STREAM,
+    "gbl_collect_search_solve": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_SOLVE + _TAIL + _STREAM,
+    "gbl_collect_search_noise": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_NOISE + _TAIL + _STREAM,
+    "gbl_collect_search_cap": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_NOISE + _TAIL +
+                              _args(_int, "fast_iterations0", "fast_iterations1", "full_share0", "full_share1") + _STREAM,
+    "gbl_collect_search_gumbel": _BOARDS + _TRAJ_EVAL + _WINDOW + _SIDES_EVAL + _TAIL +
+                                 _args(_int, "considered0", "considered1", "gumbel_noise", "visit_offset", "scale") + _STREAM,
+    "gbl_collect_search_tb": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_NOISE + _TAIL + _args(_vp, "inventory", "aux", "table") +
+                             _args(_int, "tb_mode", "tb_count") + _args(_vp, "tb_outcome_traj", "tb_value_traj", "tb_played_traj") + _STREAM,
+}
+
+
+def selfplay_args(entry: str, **named) -> list:
+    """The values of ``named`` in the order ``entry`` takes them (``SELFPLAY_ARGS``).  A missing or an unknown name is a TypeError;
+    nothing is defaulted and nothing converted."""
+    names = [name for name, _ in SELFPLAY_ARGS[entry]]
+    for name in names:
+        if name not in named:
+            raise TypeError(f"{entry}: missing argument {name!r}")
+    for name in named:
+        if name not in names:
+            raise TypeError(f"{entry} has no argument {name!r}")
+    return [named[name] for name in names]
+
+
+def selfplay_call(lib, entry: str, **named):
+    """``lib.<entry>`` of the self-play family with its arguments given by name."""
+    return getattr(lib, entry)(*selfplay_args(entry, **named))
+
+
+# every symbol include/gobblet_hip.h declares: (name, restype, argtypes)
 SIGNATURES = {
     "gbl_layout_info": (_int, [C.POINTER(C.c_int32)]),
     "gbl_last_error": (C.c_char_p, []),
@@ -97,19 +152,7 @@ SIGNATURES = {
                                 _int, _vp, _vp, _vp]),
     "gbl_collect_from_ex": (_int, [_vp] * 12 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _vp, _vp, _vp]),
     "gbl_collect_policy": (_int, [_vp] * 14 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _int, _int, _vp, _vp, _vp]),
-    "gbl_collect_search": (_int, [_vp] * 15 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32] + [_int] * 10 + [_vp, _vp, _vp]),
-    "gbl_collect_search_eval": (_int, [_vp] * 17 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 5 +
-                                [_vp, _vp, _vp]),
-    "gbl_collect_search_solve": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 7 +
-                                 [_vp, _vp, _vp]),
-    "gbl_collect_search_noise": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
-                                 [_vp, _vp, _vp]),
-    "gbl_collect_search_cap": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
-                               [_vp, _vp] + [_int] * 4 + [_vp]),
-    "gbl_collect_search_gumbel": (_int, [_vp] * 17 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 5 +
-                                  [_vp, _vp] + [_int] * 5 + [_vp]),
-    "gbl_collect_search_tb": (_int, [_vp] * 19 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _vp, _vp] + [_int] * 9 +
-                              [_vp, _vp] + [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp] + [_vp]),
+    **{entry: (_int, [ctype for _, ctype in args]) for entry, args in SELFPLAY_ARGS.items()},
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_symmetry_apply": (_int, [_vp, _int, _vp] + [_vp] * 12 + [_i64, _vp]),
     "gbl_training_batch": (_int, [_vp] * 6 + [_i64, _u32, _i64, _i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),
@@ -260,7 +303,8 @@ def current_stream(device):
 # path: a "cuda" device without the HIP library still raises.  Built with g++ from the same device header.
 CPU_LIB_PATH = os.path.join(CSRC, "libgobblet_cpu.so")
 CPU_SOURCES = [os.path.join(CSRC, "gobblet_cpu.cpp"), os.path.join(CSRC, "gobblet_device.h"), os.path.join(CSRC, "gobblet_knobs.h"),
-               os.path.join(_HERE, "..", "include", "gobblet_cpu.h"), os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
+               os.path.join(CSRC, "gobblet_selfplay_entries.inc"), os.path.join(_HERE, "..", "include", "gobblet_cpu.h"),
+               os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
 # -ffp-contract=off: gbl_cpu_train_step's float rule is single IEEE operations (include/gobblet_hip.h); everything else here is integer code
 CPU_CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"] + \
                 (["-mpopcnt"] if platform.machine() in ("x86_64", "AMD64") else [])

@@ -1251,126 +1251,12 @@ static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
     return GBL_OK;
 }
 
-int gbl_cpu_collect_search(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
-                           int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
-                           int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int64_t n, int64_t ply_stride,
-                           int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
-                           int policy0, int policy1, int iterations0, int iterations1, int playouts0, int playouts1, int max_plies,
-                           int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
-{
-    return host_selfplay_run({kRunSearch, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {nullptr, nullptr},
-                            {iterations0, iterations1}, {playouts0, playouts1}, {0, 0}, {0, 0}, max_plies, explore, sample_plies, illegal_mode,
-                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
-}
-
-int gbl_cpu_collect_search_eval(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                                int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                                int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
-                                int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
-                                uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
-                                int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
-                                int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
-{
-    return host_selfplay_run({kRunEval, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr, nullptr, nullptr, nullptr},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
-                            {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
-}
-
-int gbl_cpu_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                                  int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                                  int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
-                                  int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride,
-                                  uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0,
-                                  int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
-                                  int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, int considered0,
-                                  int considered1, int gumbel_noise, int visit_offset, int scale, void *)
-{
-    return host_selfplay_run({kRunEval, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, nullptr, nullptr, nullptr, nullptr, nullptr},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
-                            {iterations0, iterations1}, {0, 0}, {0, 0}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn, nullptr, nullptr, nullptr, 0, 0, 0, {0, 0}, {0, 0}, 1, {considered0, considered1}, gumbel_noise,
-                            visit_offset, scale});
-}
-
-int gbl_cpu_collect_search_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                                 int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                                 int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
-                                 int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
-                                 int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
-                                 const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
-                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
-                                 int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
-{
-    return host_selfplay_run({kRunSolve, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
-                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {0, 0}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
-}
-
-int gbl_cpu_collect_search_noise(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                                 int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                                 int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
-                                 int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
-                                 int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
-                                 const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
-                                 const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1,
-                                 int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
-                                 void *)
-{
-    return host_selfplay_run({kRunSolve, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
-                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn, nullptr, nullptr, nullptr, 0, 0});
-}
-
-int gbl_cpu_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                               int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
-                               int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
-                               int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
-                               const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
-                               const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1,
-                               int noise0, int noise1, int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn,
-                               int fast_iterations0, int fast_iterations1, int full_share0, int full_share1, void *)
-{
-    return host_selfplay_run({kRunSolve, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, nullptr, nullptr, nullptr},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
-                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn, nullptr, nullptr, nullptr, 0, 0, 1, {fast_iterations0, fast_iterations1}, {full_share0, full_share1}});
-}
-
-int gbl_cpu_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
-                              int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
-                              int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
-                              uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n, int64_t ply_stride,
-                              int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
-                              int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
-                              int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
-                              int64_t *counters, int32_t *turn, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode,
-                              int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *)
-{
-    return host_selfplay_run({kRunTb, state, to_move, done,
-                            {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj,
-                             nodes_traj, how_traj, mover_traj, root_value_traj, priors_traj, outcome_traj, proven_traj, tb_outcome_traj,
-                             tb_value_traj, tb_played_traj},
-                            n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, {policy0, policy1}, {ev0, ev1},
-                            {iterations0, iterations1}, {0, 0}, {solve_depth0, solve_depth1}, {noise0, noise1}, 0, explore, sample_plies, illegal_mode,
-                            counters, turn, inventory, aux, table, tb_mode, tb_count});
-}
+// the seven entry points themselves: one text for both flavours (the host flavour's calls are synchronous: `stream` is not read)
+#define GBL_SELFPLAY_SYMBOL(fn) gbl_cpu_##fn
+#define GBL_SELFPLAY_RUN(name, call, stream) ((void)(stream), host_selfplay_run(call))
+#include "gobblet_selfplay_entries.inc"
+#undef GBL_SELFPLAY_SYMBOL
+#undef GBL_SELFPLAY_RUN
 
 int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
                             int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *)

@@ -2709,14 +2709,14 @@ struct SelfplayTraj {
     int8_t *how, *mover;
     int32_t *root_value;  // (the evaluator search's two: NULL in gbl_collect_search)
     uint8_t *priors;
-    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_collect_search_solve / _noise / _tb)
+    int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_collect_search_solve / _noise / _cap / _tb)
     int8_t *tb_outcome, *tb_value, *tb_played;  // (the table's verdict of every ply: NULL but in gbl_collect_search_tb)
 };
 
-enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval; _solve and _noise; _tb
+enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval and _gumbel; _solve, _noise and _cap; _tb
 
-// The union of the five entry points' arguments; an entry point fills it (0 / NULL for what it does not have) and calls its flavour's
-// one runner.  [0] is player_1's, [1] player_2's.  Ev: gbl_evaluator.
+// The union of the seven entry points' arguments; an entry point (gobblet_selfplay_entries.inc, one text for both flavours) fills it,
+// leaving 0 / NULL what it does not have, and calls its flavour's one runner.  [0] is player_1's, [1] player_2's.  Ev: gbl_evaluator.
 template <typename Ev>
 struct SelfplayCall {
     SelfplayRun run;

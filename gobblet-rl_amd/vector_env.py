@@ -18,11 +18,11 @@ Tensors (attributes, all on ``device``)
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 
 import torch
 
 from . import _native as nat
+from . import _selfplay
 from . import placement as _placement
 from .board import BatchedBoard, _as_i32
 
@@ -484,22 +484,17 @@ class BatchedGobblet:
         if not self.auto_reset:
             raise ValueError("collect() plays with auto-reset; this environment was created with auto_reset=False")
         T = int(plies)
-        tp = self._tablebase_params(policies, search)  # None unless a side plays from the table or the table judges
-        ep = tp["ep"] if tp is not None else self._evaluator_params(policies, search)  # None unless a side plays the evaluator-guided search
-        sp = ep if ep is not None else self._search_params(policies, search)  # None unless a side plays a tree search
-        guarded = ep is not None and any(ep["solve_depth"])  # (the solver in front of an evaluator side's searches)
-        judged = tp is not None and tp["judge"]
+        plan = _selfplay.plan(policies, search, self.device)  # the entry point (None: no side searches), its buffers, its named arguments
+        entry, named = plan.entry, plan.named
         def fresh():  # buffers for this call's entry point, made (and placed) now
-            return self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and sp is None,
-                                           search_outputs=sp is not None, evaluator_outputs=ep is not None, solver_outputs=guarded,
-                                           tablebase_outputs=judged, far=False)
+            return self.trajectory_buffers(T, layout=layout, policy_outputs=policies is not None and entry is None, **plan.outputs, far=False)
         if isinstance(out, str):
             if out != "fresh":
                 raise ValueError("out: a dict from trajectory_buffers(), None (the environment's staging buffers) or 'fresh'")
             out = fresh()  # the caller's own: not kept by the environment, never overwritten by a later call
         if out is None:
-            key = (T, layout, policies is not None) + (("search",) if sp is not None else ()) + (("evaluator",) if ep is not None else ()) + \
-                (("solver",) if guarded else ()) + (("tablebase",) if judged else ())
+            # (... "search", "evaluator", "solver", "tablebase": the output groups of the plan)
+            key = (T, layout, policies is not None) + tuple(k[:-len("_outputs")] for k, on in plan.outputs.items() if on)
             out = self._staging.pop(key, None)
             made = out is None
             if made:
@@ -526,43 +521,22 @@ class BatchedGobblet:
         first_status = self._i8_out(first_status, "first_status")
         if first_status is not None and fa is None:
             raise ValueError("first_status needs first_actions")
-        if sp is not None:  # (either search)
-            if sp["sample_plies"] and self.turn is None:
+        if entry is not None:  # (a member of the self-play family: either search, the table)
+            if named["sample_plies"] and self.turn is None:
                 raise ValueError("sample_plies needs the per-board turn counter: create the environment with track_turn=True")
             if opening_plies:
                 raise ValueError("opening_plies belongs to the greedy policies; the tree search has sample_plies")
-            # one argument list for the four self-play entry points: any noise weight -> _noise (the guarded kernel, whatever the
-            # depths), else any solve depth -> _solve, else an evaluator side -> _eval, else the UCT search
-            # a table side or the judge -> _tb (the noise entry point's list, then the table's); a playout cap -> _cap (that list,
-            # then the cap's)
-            cap = None if ep is None else ep.get("cap")
-            gum = None if ep is None else ep.get("gumbel")  # the Gumbel root rule -> _gumbel (the _eval list, then the rule's five)
-            entry = "gbl_collect_search" + ("_tb" if tp is not None else "" if ep is None else "_gumbel" if gum is not None else
-                                            "_cap" if cap is not None else
-                                            "_noise" if any(ep["noise"]) else "_solve" if guarded else "_eval")
-            if judged and "tb_value" not in f:
+            if plan.outputs["tablebase_outputs"] and "tb_value" not in f:
                 raise ValueError("judge=True needs buffers from trajectory_buffers(tablebase_outputs=True)")
-            args = [self.squares.data_ptr(), self.to_move.data_ptr(), self.done.data_ptr(), f["actions"].data_ptr(),
-                    f["winner"].data_ptr(), f["rewards"].data_ptr(), f["done"].data_ptr(), f["to_move"].data_ptr(),
-                    f["action_mask"].data_ptr(), f["observation"].data_ptr() if "observation" in f else None, nat.ptr(f.get("visits")),
-                    nat.ptr(f.get("value")), nat.ptr(f.get("nodes")), nat.ptr(f.get("how")), nat.ptr(f.get("mover"))]
-            if ep is None:
-                sides = [*sp["iterations"], *sp["playouts"], sp["max_plies"]]
-            else:
-                solver, noise = not entry.endswith(("_eval", "_gumbel")), entry.endswith(("_noise", "_tb", "_cap"))
-                structs = [None if e is None else e.as_struct() for e in ep["evaluators"]]  # (alive until the call has returned)
-                args += [nat.ptr(f.get(k)) for k in ("root_value", "priors") + (("outcomes", "proven") if solver else ())]
-                sides = [*[None if st is None else C.addressof(st) for st in structs], *ep["iterations"],
-                         *(ep["solve_depth"] if solver else ()), *(ep["noise"] if noise else ())]
-            nat.check(getattr(self._lib, entry)(
-                *args, n, out["_ply_stride"], out["_tile_stride"], self.seed, self.env_base, self._ply, nat.ptr(self._ply_dev), T,
-                *sp["policies"], *sides, sp["explore"], sp["sample_plies"], self.illegal_mode,
-                self._counters.data_ptr() if count else None, nat.ptr(self.turn),
-                *(() if tp is None else (tp["inventory"], tp["aux"], tp["table"], tp["mode"], tp["count"],
-                                         *(nat.ptr(f.get(k)) if judged else None for k in ("tb_outcomes", "tb_value", "tb_played")))),
-                *(() if cap is None or tp is not None else (*cap["fast_iterations"], *cap["share"])),
-                *(() if gum is None else (*gum["considered"], gum["noise"], gum["visit_offset"], gum["scale"])),
-                self._stream()), entry)
+            # the trajectory arrays this member takes and the plan has not decided: the buffers' (NULL where the set has none)
+            takes = {name for name, _ in nat.SELFPLAY_ARGS[entry]}
+            traj = {a: nat.ptr(f.get(k)) for a, k in _selfplay.TRAJ_BUFFERS.items() if a in takes and a not in named}
+            # (plan.alive -- the evaluator structs behind ev0 / ev1 -- lives until this call has returned)
+            nat.check(nat.selfplay_call(
+                self._lib, entry, state=self.squares.data_ptr(), to_move=self.to_move.data_ptr(), done=self.done.data_ptr(), **traj, n=n,
+                ply_stride=out["_ply_stride"], tile_stride=out["_tile_stride"], seed=self.seed, env_base=self.env_base, ply0=self._ply,
+                ply_dev=nat.ptr(self._ply_dev), plies=T, illegal_mode=self.illegal_mode,
+                counters=self._counters.data_ptr() if count else None, turn=nat.ptr(self.turn), stream=self._stream(), **named), entry)
         elif policies is not None:
             try:
                 p0, p1 = (self.POLICIES[x] if isinstance(x, str) else int(x) for x in policies)
@@ -599,242 +573,6 @@ class BatchedGobblet:
         if self.observation is not None:
             self.observation.copy_(self._last_ply(out, "observation"))
         return out
-
-    @staticmethod
-    def _pair(v) -> list:
-        """A per-side setting of ``search=``: a value for both sides, or a pair."""
-        return list(v) if isinstance(v, (tuple, list)) else [v, v]
-
-    @staticmethod
-    def _is_random(x) -> bool:
-        return x == "random" or (not isinstance(x, str) and x == nat.POLICY_RANDOM)
-
-    @staticmethod
-    def _search_kw(defaults: dict, search, unknown_msg: str) -> dict:
-        """``defaults`` updated with ``search=``; a key it does not have is an error."""
-        unknown = set(search or ()) - set(defaults)
-        if unknown:
-            raise ValueError(unknown_msg % sorted(unknown))
-        return {**defaults, **(search or {})}
-
-    def _search_params(self, policies, search):
-        """The arguments of ``gbl_collect_search`` when a side of ``policies`` plays the tree search, else None."""
-        from .tree_policy import TreeSearchGobbletPolicy
-        if policies is None or isinstance(policies, str):
-            if search is not None:
-                raise ValueError("search= belongs to policies with a 'tree' side")
-            return None
-        sides = list(policies)
-        trees = [isinstance(x, TreeSearchGobbletPolicy) or x == "tree" or (not isinstance(x, str) and x == nat.POLICY_TREE) for x in sides]
-        if len(sides) != 2 or not any(trees):
-            if search is not None:
-                raise ValueError("search= belongs to policies with a 'tree' side")
-            return None
-        kw = self._search_kw(dict(iterations=256, playouts=16, max_plies=64, explore=16, sample_plies=0),  # TreeSearchGobbletPolicy's defaults
-                             search, "search: unknown keys %s")
-        its, pls = ([int(x) for x in self._pair(kw[k])] for k in ("iterations", "playouts"))
-        if len(its) != 2 or len(pls) != 2:
-            raise ValueError("search: iterations / playouts are a value or a pair, one value per side")
-        codes = []
-        for m, x in enumerate(sides):
-            if isinstance(x, TreeSearchGobbletPolicy):
-                its[m], pls[m] = x.iterations, x.playouts
-                if search is None or "max_plies" not in search:
-                    kw["max_plies"] = x.max_plies
-                if search is None or "explore" not in search:
-                    kw["explore"] = x.explore
-                codes.append(nat.POLICY_TREE)
-            elif trees[m]:
-                codes.append(nat.POLICY_TREE)
-            elif self._is_random(x):
-                codes.append(nat.POLICY_RANDOM)
-            else:
-                raise ValueError("policies: the tree search plays against 'tree' or 'random' (not %r)" % (x,))
-        for m in range(2):
-            if codes[m] == nat.POLICY_TREE and not (1 <= its[m] <= 1024 and 1 <= pls[m] <= 256):
-                raise ValueError("search: iterations must be in [1, 1024] and playouts in [1, 256]")
-        if not (0 <= int(kw["max_plies"]) <= 255 and 0 <= int(kw["explore"]) <= 1024 and int(kw["sample_plies"]) >= 0):
-            raise ValueError("search: max_plies must be in [0, 255], explore in [0, 1024], sample_plies >= 0")
-        return dict(policies=codes, iterations=its, playouts=pls, max_plies=int(kw["max_plies"]), explore=int(kw["explore"]),
-                    sample_plies=int(kw["sample_plies"]))
-
-    def _evaluator_params(self, policies, search):
-        """The arguments of ``gbl_collect_search_eval`` / ``_solve`` / ``_noise`` when a side of ``policies`` plays the evaluator-guided
-        search, else None."""
-        from .evaluator_policy import EvaluatorTreeSearchGobbletPolicy, GobbletEvaluator
-        from .tree_policy import TreeSearchGobbletPolicy
-        if policies is None or isinstance(policies, str):
-            return None
-        sides = list(policies)
-
-        def is_eval(x):
-            return isinstance(x, EvaluatorTreeSearchGobbletPolicy) or x == "evaluator" or \
-                (not isinstance(x, (str, TreeSearchGobbletPolicy)) and x == nat.POLICY_EVAL_TREE)
-        evs = [is_eval(x) for x in sides]
-        if len(sides) != 2 or not any(evs):
-            return None
-        from .evaluator_policy import noise_weight
-        kw = self._search_kw(dict(evaluator=None, iterations=256, explore=None, sample_plies=0, solve_depth=0, noise=0.0, cap=None,
-                                  gumbel=None),  # EvaluatorTreeSearchGobbletPolicy's defaults
-                             search, "search: unknown keys %s (an evaluator side takes evaluator / iterations / explore / sample_plies / "
-                             "solve_depth / noise / cap / gumbel)")
-        its, nets, deps, nzs = self._pair(kw["iterations"]), self._pair(kw["evaluator"]), self._pair(kw["solve_depth"]), self._pair(kw["noise"])
-        if len(its) != 2 or len(nets) != 2 or len(deps) != 2 or len(nzs) != 2:
-            raise ValueError("search: iterations / evaluator / solve_depth / noise are a value or a pair, one per side")
-        nzs = [noise_weight(x or 0.0) for x in nzs]  # (shares in [0, 1] -> the ABI's weights 0 .. 256)
-        codes, explores = [], []
-        for m, x in enumerate(sides):
-            if isinstance(x, EvaluatorTreeSearchGobbletPolicy):
-                if x.gumbel is not None:
-                    raise ValueError("a policy instance with gumbel= does not bring its rule into collect(): pass 'evaluator' sides and "
-                                     "search=dict(gumbel=...)")
-                its[m], nets[m], nzs[m] = x.iterations, x.evaluator, x.noise
-                explores.append(x.explore)
-                codes.append(nat.POLICY_EVAL_TREE)
-            elif evs[m]:
-                codes.append(nat.POLICY_EVAL_TREE)
-            elif self._is_random(x):
-                codes.append(nat.POLICY_RANDOM)
-                nets[m] = None
-            else:
-                raise ValueError("policies: the evaluator-guided search plays against 'evaluator' or 'random' inside one launch (not %r); "
-                                 "against the tree search or a greedy policy, compose the loop: the policy's "
-                                 "compute_actions_from_state + step_into per ply" % (x,))
-        if kw["explore"] is not None:
-            explore = int(kw["explore"])
-        elif explores:
-            if len(set(explores)) > 1:
-                raise ValueError("the two policy instances disagree on explore (%d, %d): one launch has one value; pass "
-                                 "search=dict(explore=...)" % tuple(explores))
-            explore = explores[0]
-        else:
-            explore = 16
-        for m in range(2):
-            if codes[m] != nat.POLICY_EVAL_TREE:
-                its[m] = deps[m] = nzs[m] = 0
-                continue
-            deps[m] = int(deps[m] or 0)
-            if not 0 <= deps[m] <= nat.SOLVE_MAX_DEPTH:
-                raise ValueError(f"search: solve_depth must be in [0, {nat.SOLVE_MAX_DEPTH}]")
-            if not isinstance(nets[m], GobbletEvaluator):
-                raise ValueError("search: an 'evaluator' side needs search=dict(evaluator=GobbletEvaluator ...)")
-            if nets[m].device != self.device:
-                raise ValueError("the evaluator lives on %s and the environment on %s: move it with evaluator.to(...)"
-                                 % (nets[m].device, self.device))
-            its[m] = int(its[m])
-            if not 1 <= its[m] <= 512:
-                raise ValueError("search: iterations must be in [1, 512]")
-        if not (0 <= explore <= 1024 and int(kw["sample_plies"]) >= 0):
-            raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
-        gumbel = self._gumbel_params(kw["gumbel"], codes)
-        if gumbel is not None and (any(deps) or any(nzs) or kw["cap"] is not None):
-            raise ValueError("search: gumbel does not go with solve_depth, noise or cap (gbl_collect_search_gumbel has none of them)")
-        return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
-                    solve_depth=deps, noise=nzs, cap=self._cap_params(kw["cap"], codes, its), gumbel=gumbel)
-
-    def _gumbel_params(self, gumbel, codes):
-        """``search=dict(gumbel=dict(considered=, noise=, visit_offset=, scale=))`` as ``gbl_collect_search_gumbel`` takes it --
-        ``considered`` per side (0: that side keeps the search above), the rest for both -- or None where no evaluator side follows
-        the rule (an absent ``gumbel``, ``considered=0``): the call keeps its entry point."""
-        from .evaluator_policy import gumbel_args
-        if gumbel is None:
-            return None
-        if not isinstance(gumbel, dict):
-            raise ValueError("search: gumbel is a dict of considered / noise / visit_offset / scale")
-        considered = self._pair(gumbel.get("considered", 16))
-        if len(considered) != 2:
-            raise ValueError("search: gumbel's considered is a value or a pair, one per side")
-        rest = gumbel_args(dict(gumbel, considered=1))
-        for m in range(2):
-            if codes[m] != nat.POLICY_EVAL_TREE:
-                considered[m] = 0
-            elif isinstance(considered[m], bool) or not 0 <= int(considered[m]) <= 54:
-                raise ValueError("search: gumbel's considered must be in [0, 54]")
-            considered[m] = int(considered[m])
-        if not any(considered):
-            return None
-        return dict(considered=considered, noise=rest["noise"], visit_offset=rest["visit_offset"], scale=rest["scale"])
-
-    def _cap_params(self, cap, codes, its):
-        """``search=dict(cap=dict(fast_iterations=, full=))`` as ``gbl_collect_search_cap`` takes it -- a fast budget and a share
-        0 .. 256 per side -- or None where no evaluator side is capped (an absent ``cap``, ``full=1``): the call keeps its entry point."""
-        from .evaluator_policy import cap_share
-        if cap is None:
-            return None
-        if not isinstance(cap, dict) or set(cap) - {"fast_iterations", "full"}:
-            raise ValueError("search: cap is a dict of fast_iterations / full")
-        fast, full = self._pair(cap.get("fast_iterations", 16)), self._pair(cap.get("full", 0.25))
-        if len(fast) != 2 or len(full) != 2:
-            raise ValueError("search: cap's fast_iterations / full are a value or a pair, one per side")
-        shares = [cap_share(x) for x in full]
-        for m in range(2):
-            if codes[m] != nat.POLICY_EVAL_TREE:
-                fast[m], shares[m] = 0, nat.CAP_FULL_SHARE
-            elif shares[m] < nat.CAP_FULL_SHARE:
-                fast[m] = int(fast[m])
-                if not 1 <= fast[m] <= its[m]:
-                    raise ValueError("search: cap's fast_iterations must be in [1, iterations]")
-            else:
-                fast[m] = 0
-        if all(x == nat.CAP_FULL_SHARE for x in shares):
-            return None
-        return dict(fast_iterations=fast, share=shares)
-
-    def _tablebase_params(self, policies, search):
-        """The table's arguments of ``gbl_collect_search_tb`` and, under "ep", the rest of the call as ``_evaluator_params`` returns it
-        (a table side stands there with its own policy code); None unless a side of ``policies`` plays from the table or
-        ``search=dict(judge=True)``."""
-        from .tablebase import Tablebase, TablebaseGobbletPolicy
-        if policies is None or isinstance(policies, str):
-            return None
-        sides = list(policies)
-
-        def is_tb(x):
-            return isinstance(x, TablebaseGobbletPolicy) or x == "tablebase" or \
-                (isinstance(x, int) and not isinstance(x, bool) and x == nat.POLICY_TABLEBASE)
-        tbs = [is_tb(x) for x in sides]
-        judge = bool((search or {}).get("judge", False))
-        if len(sides) != 2 or not (any(tbs) or judge):
-            if (search or {}).get("tablebase") is not None:
-                raise ValueError("search: tablebase= belongs to a pair of policies with a 'tablebase' side, or to judge=True")
-            return None
-        rest = {k: v for k, v in (search or {}).items() if k not in ("tablebase", "tb_mode", "tb_count", "judge", "allow_incomplete")}
-        kw = {**dict(tablebase=None, tb_mode="result", tb_count=1, allow_incomplete=False), **{k: v for k, v in (search or {}).items() if k not in rest}}
-        tb = kw["tablebase"]
-        for x in sides:
-            if isinstance(x, TablebaseGobbletPolicy):
-                if tb is not None and tb is not x.tb:
-                    raise ValueError("one launch reads one table: the policy instance's and search=dict(tablebase=...) differ")
-                tb = x.tb
-        if not isinstance(tb, Tablebase):
-            raise ValueError("search: a 'tablebase' side (or judge=True) needs search=dict(tablebase=Tablebase ...)")
-        if tb.device != self.device:
-            raise ValueError("the table lives on %s and the environment on %s" % (tb.device, self.device))
-        if not tb.complete and not kw["allow_incomplete"]:
-            raise ValueError("the table is not complete: a 0 would read 'not proven yet' (allow_incomplete=True to play from it anyway)")
-        if kw["tb_mode"] not in nat.TB_TARGET_MODES:
-            raise ValueError("search: tb_mode is 'result' or 'shortest'")
-        if not 1 <= int(kw["tb_count"]) <= nat.TB_TARGET_MAX_COUNT:
-            raise ValueError("search: tb_count must be in [1, %d]" % nat.TB_TARGET_MAX_COUNT)
-        if rest.get("cap") is not None:
-            raise ValueError("search: cap does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no playout cap)")
-        if rest.get("gumbel") is not None:
-            raise ValueError("search: gumbel does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no Gumbel rule)")
-        others = ["random" if t else x for t, x in zip(tbs, sides)]
-        ep = self._evaluator_params(others, rest or None)
-        if ep is None:  # no evaluator side: the table against itself or against "random"
-            if not all(self._is_random(x) for x in others):
-                raise ValueError("policies: the table plays against 'tablebase', 'evaluator' or 'random' inside one launch (not %r)" % (sides,))
-            unknown = set(rest) - {"sample_plies", "evaluator", "iterations", "explore", "solve_depth", "noise", "cap", "gumbel"}
-            if unknown:
-                raise ValueError("search: unknown keys %s" % sorted(unknown))
-            if int(rest.get("sample_plies", 0)) < 0:
-                raise ValueError("search: sample_plies >= 0")
-            ep = dict(policies=[nat.POLICY_RANDOM] * 2, evaluators=[None, None], iterations=[0, 0], explore=16,
-                      sample_plies=int(rest.get("sample_plies", 0)), solve_depth=[0, 0], noise=[0, 0], cap=None)
-        ep["policies"] = [nat.POLICY_TABLEBASE if t else c for t, c in zip(tbs, ep["policies"])]
-        return dict(ep=ep, judge=judge, tb=tb, inventory=tb._inv, aux=tb._aux.data_ptr(), table=tb.table.data_ptr(),
-                    mode=nat.TB_TARGET_MODES[kw["tb_mode"]], count=int(kw["tb_count"]))
 
     def outcome_targets(self, traj: dict) -> dict:
         """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128

@@ -17,21 +17,21 @@ sys.path.insert(0, ROOT)
 from gobblet_rl_amd import _native as nat  # noqa: E402
 
 K = 65536
-TRAJ = ("actions", "winner", "reward", "done_traj", "to_move_traj", "mask", "obs", "visits", "value", "nodes", "how", "mover")
-TRAJ_OF = {"collect_search": TRAJ, "collect_search_eval": TRAJ + ("root_value", "priors")}
-TRAJ_OF["collect_search_solve"] = TRAJ_OF["collect_search_noise"] = TRAJ_OF["collect_search_eval"] + ("outcome", "proven")
-WINDOW = ("n", "ply_stride", "tile_stride", "seed", "env_base", "ply0", "ply_dev", "plies", "policy0", "policy1")
-SIDES_OF = {"collect_search": ("iterations0", "iterations1", "playouts0", "playouts1", "max_plies", "explore"),
-            "collect_search_eval": ("ev0", "ev1", "iterations0", "iterations1", "explore"),
-            "collect_search_solve": ("ev0", "ev1", "iterations0", "iterations1", "solve_depth0", "solve_depth1", "explore"),
-            "collect_search_noise": ("ev0", "ev1", "iterations0", "iterations1", "solve_depth0", "solve_depth1", "noise0", "noise1",
-                                     "explore")}
-TAIL = ("sample_plies", "illegal_mode", "counters", "turn", "stream")
 GOOD_EV = [1 * K, 2 * K, 3 * K, 4 * K, 64, 4, 9, 9]
 
 
+def short(name):
+    """The ABI's parameter name as base() and the cases spell it: a trajectory array without its "_traj" (but done_traj / to_move_traj)."""
+    return name[:-5] if name.endswith("_traj") and name[:-5] not in ("done", "to_move") else name
+
+
 def names(fn):
-    return ("state", "to_move", "done") + TRAJ_OF[fn] + WINDOW + SIDES_OF[fn] + TAIL
+    """The arguments of gbl_`fn` in the ABI's order (nat.SELFPLAY_ARGS)."""
+    return tuple(short(k) for k, _ in nat.SELFPLAY_ARGS["gbl_" + fn])
+
+
+def traj_of(fn):
+    return tuple(short(k) for k, _ in nat.SELFPLAY_ARGS["gbl_" + fn] if k.endswith("_traj"))
 
 
 def base(fn):
@@ -41,7 +41,7 @@ def base(fn):
              plies=2, policy0=code, policy1=code, iterations0=8, iterations1=8, playouts0=2, playouts1=2, max_plies=8, explore=16,
              ev0=GOOD_EV, ev1=GOOD_EV, solve_depth0=2, solve_depth1=0, noise0=64, noise1=64, sample_plies=0, illegal_mode=0,
              counters=None, turn=None, stream=None)
-    b.update({k: (8 + i) * K for i, k in enumerate(TRAJ_OF[fn])})
+    b.update({k: (8 + i) * K for i, k in enumerate(traj_of(fn))})
     return {k: b[k] for k in names(fn)}
 
 
@@ -106,7 +106,7 @@ def cases(fn):
 
 
 def call(lib, prefix, fn, args, evs):
-    """One call as the table records it (tests/selfplay_harness.py's recorded_call replays it): "ev" is the next evaluator of `evs`."""
+    """One call as the table records it (tests/search_harness.py's recorded_call replays it): "ev" is the next evaluator of `evs`."""
     structs = [None if e is None else nat.Evaluator(*e) for e in evs]
     it = iter(structs)
     real = []

@@ -1,8 +1,7 @@
 """What the tests of gbl_tree_search_gumbel and gbl_collect_search_gumbel (either flavour) share, on top of tests/search_harness.py and
 tests/selfplay_harness.py: the single-decision entry point's line in the harness's table (so that `run` serves it, canaries and all),
-the self-play argument list (that of gbl_collect_search_eval, then the rule's five), one runner on host arrays and one on the device
-(every output filled with -7 / 99 first and, on the device, kept between canaries), and the boards.  A plain module: no fixtures."""
-import ctypes as C
+the self-play runner calls under the rule's own argument order and defaults (tests/selfplay_harness.py's one runner serves the entry
+point as "gumbel"), and the boards.  A plain module: no fixtures."""
 import math
 
 import numpy as np
@@ -15,8 +14,7 @@ from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import search_harness as SH
 from tests import solver_restatement as SR
-from tests.search_harness import DEV, PAD
-from tests.selfplay_harness import CODES, EVAL_NAMES, Compact, geometry
+from tests.selfplay_harness import device_collect, host_collect
 
 SH.ENTRIES.setdefault("tree_search_gumbel", (
     ("iterations", "explore", "considered", "gumbel_noise", "visit_offset", "scale", "seed", "env_base", "call"), True,
@@ -129,51 +127,19 @@ def winning_action_case(seed, env_base, n=512):
     return (np.repeat(s[None], n, 0), np.full(n, m, np.int8)), None, R.zero_net(64), (16, EDGE_EXPLORE, 16, 1, 50, 23, seed, env_base, 3), expect
 
 
-def call_args(ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, evs, its, X, sample_plies, illegal_mode, counters, tn,
-              considered, noise, visit_offset, scale, stream):
-    """The argument list of gbl(_cpu)_collect_search_gumbel."""
-    return [ptr(st), ptr(tm), ptr(dn), *[ptr(traj.get(k)) for k, _, _ in EVAL_NAMES], n, ps, ts, seed, env_base, ply0, ptr(pd), T,
-            CODES[pols[0]], CODES[pols[1]], *[None if e is None else C.addressof(e) for e in evs], its[0], its[1], X, sample_plies,
-            illegal_mode, ptr(counters), ptr(tn), int(considered[0]), int(considered[1]), int(noise), int(visit_offset), int(scale), stream]
-
-
-def _run(f, ok, put, get, ptr, pad, stream, st, tm, turn, T, pols, nets, its, considered, noise, visit_offset, scale, X, sample_plies,
-         illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters, strides=None, store=None):
-    n = len(st)
-    ps, ts, total, at = geometry(n, T, layout, strides)
-    store = Compact(put, get, pad) if store is None else store
-    keep = [k for k, _, _ in EVAL_NAMES] if keep is None else keep
-    traj = {k: store.array(k, dt, tail, total) for k, dt, tail in EVAL_NAMES if k in keep}
-    st, tm, dn = put(np.ascontiguousarray(st, np.int8)), put(np.ascontiguousarray(tm, np.int8)), put(np.full(n, 5, np.int8))
-    tn = None if turn is None else put(np.ascontiguousarray(turn, np.int32))
-    pd = None if ply_dev is None else put(np.array([ply_dev], np.int32))
-    evs = [None if net is None else net.struct() for net in nets]  # (alive until the call has returned)
-    ok(f(*call_args(ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, evs, its, X, sample_plies, illegal_mode, counters, tn,
-                    considered, noise, visit_offset, scale, stream)))
-    return store.cells(at, total), get(st), get(tm), get(dn), None if tn is None else get(tn)
-
-
 def host_collect_gumbel(st, tm, turn, T, pols, nets, its, considered, noise=1, visit_offset=50, scale=23, X=16, sample_plies=0,
-                        illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, keep=None, counters=None, strides=None, store=None):
-    """gbl_cpu_collect_search_gumbel on host arrays; nets: restatement Nets; only the outputs named in `keep` are given (None: all).
-    Returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
+                        illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, **kw):
+    """gbl_cpu_collect_search_gumbel on host arrays (tests.selfplay_harness's one runner, as "gumbel", under the rule's own argument order
+    and defaults); nets: restatement Nets; kw: ply_dev=, keep=, counters=, strides=, store=.  Returns ({name: (T, n, ...)}, state,
+    to_move, done, turn)."""
     L = nat.cpu_raw()
-
-    def ok(rc):
-        assert rc == 0, L.gbl_cpu_last_error()
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data
-    return _run(L.gbl_cpu_collect_search_gumbel, ok, np.array, lambda a: a, ptr, 0, None, st, tm, turn, T, pols, nets, its, considered, noise,
-                visit_offset, scale, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters, strides, store)
+    return host_collect("gumbel", L.gbl_cpu_collect_search_gumbel, L.gbl_cpu_last_error, st, tm, turn, T, pols, X, sample_plies, illegal_mode,
+                        layout, seed, env_base, ply0, nets=nets, its=its, considered=considered, gumbel_noise=noise, visit_offset=visit_offset,
+                        scale=scale, **kw)
 
 
 def device_collect_gumbel(st, tm, turn, T, pols, nets, its, considered, noise=1, visit_offset=50, scale=23, X=16, sample_plies=0,
-                          illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, ply_dev=None, keep=None, counters=None, strides=None, store=None):
+                          illegal_mode=nat.ILLEGAL_NOOP, layout="time", seed=1, env_base=0, ply0=0, **kw):
     """gbl_collect_search_gumbel on the device, every output between canaries; nets: DeviceNets."""
-    def get(t):
-        torch.cuda.synchronize()
-        return t.cpu().numpy()
-    return _run(nat.lib().gbl_collect_search_gumbel, lambda rc: nat.check(rc, "gbl_collect_search_gumbel"),
-                lambda a: torch.from_numpy(a).to(DEV), get, nat.ptr, PAD, nat.current_stream(DEV), st, tm, turn, T, pols, nets, its,
-                considered, noise, visit_offset, scale, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev, keep, counters, strides, store)
+    return device_collect("gumbel", st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, nets=nets, its=its,
+                          considered=considered, gumbel_noise=noise, visit_offset=visit_offset, scale=scale, **kw)

@@ -1,12 +1,14 @@
-"""What the tests of the four self-play entry points (gbl_collect_search, _eval, _solve, _noise; either flavour) share: the output
-tables, the trajectory geometry, ONE argument list, one runner on host arrays and one on the device (every output filled with -7 /
-99 first: nothing outside the cells may be written), the comparison, and the evaluator helpers.  A plain module: no fixtures."""
+"""What the tests of the seven self-play entry points (gbl_collect_search, _eval, _solve, _noise, _cap, _gumbel, _tb; either flavour)
+share: the output tables, the trajectory geometry, ONE argument list (by name, ordered by nat.SELFPLAY_ARGS), one runner on host arrays
+and one on the device (every output filled with -7 / 99 first: nothing outside the cells may be written), the comparison, and the
+evaluator helpers.  A plain module: no fixtures."""
 import ctypes as C
 
 import numpy as np
 
 import gobblet_rl_amd as G
 from gobblet_rl_amd import _native as nat
+from gobblet_rl_amd._selfplay import TRAJ_BUFFERS
 from tests.search_harness import DEV, PAD
 from tests.search_harness import same as same_arrays
 
@@ -15,8 +17,15 @@ SCALARS = (("actions", np.int32, ()), ("winner", np.int8, ()), ("rewards", np.in
            ("value", np.int32, ()), ("nodes", np.int32, ()), ("how", np.int8, ()), ("mover", np.int8, ()))
 EVAL_NAMES = SCALARS + (("root_value", np.int32, ()), ("priors", np.uint8, (54,)))
 SOLVE_NAMES = EVAL_NAMES + (("outcomes", np.int8, (54,)), ("proven", np.int8, ()))
-NAMES = {"search": SCALARS, "eval": EVAL_NAMES, "solve": SOLVE_NAMES, "noise": SOLVE_NAMES}  # entry point -> its outputs, in ABI order
-CODES = {"random": nat.POLICY_RANDOM, "tree": nat.POLICY_TREE, "eval": nat.POLICY_EVAL_TREE}
+JUDGE_NAMES = (("tb_outcomes", np.int8, (54,)), ("tb_value", np.int8, ()), ("tb_played", np.int8, ()))
+# entry point -> its outputs (name = the key of BatchedGobblet.trajectory_buffers, dtype, a cell's shape)
+NAMES = {"search": SCALARS, "eval": EVAL_NAMES, "solve": SOLVE_NAMES, "noise": SOLVE_NAMES, "cap": SOLVE_NAMES, "gumbel": EVAL_NAMES,
+         "tb": SOLVE_NAMES + JUDGE_NAMES}
+CODES = {"random": nat.POLICY_RANDOM, "tree": nat.POLICY_TREE, "eval": nat.POLICY_EVAL_TREE, "tb": nat.POLICY_TABLEBASE}
+
+
+def symbol(entry):
+    return "gbl_collect_search" + ("" if entry == "search" else "_" + entry)
 
 
 def strides(n, T, layout):
@@ -67,16 +76,23 @@ class Compact:
 
 
 def call_args(entry, ptr, st, tm, dn, traj, n, ps, ts, seed, env_base, ply0, pd, T, pols, X, sample_plies, illegal_mode, counters, tn, stream,
-              its=(0, 0), pls=(0, 0), M=0, evs=(None, None), deps=(0, 0), noise=(0, 0)):
-    """The argument list of gbl(_cpu)_collect_search ("search"), _eval, _solve or _noise; ptr(x) turns an array (or None) into a
-    pointer, evs are gbl_evaluator structs (or None)."""
-    if entry == "search":
-        sides = [its[0], its[1], pls[0], pls[1], M]
-    else:
-        sides = [*[None if e is None else C.addressof(e) for e in evs], its[0], its[1]] + \
-            ([deps[0], deps[1]] if entry != "eval" else []) + ([int(noise[0]), int(noise[1])] if entry == "noise" else [])
-    return [ptr(st), ptr(tm), ptr(dn), *[ptr(traj.get(k)) for k, _, _ in NAMES[entry]], n, ps, ts, seed, env_base, ply0, ptr(pd), T,
-            CODES[pols[0]], CODES[pols[1]], *sides, X, sample_plies, illegal_mode, ptr(counters), ptr(tn), stream]
+              its=(0, 0), pls=(0, 0), M=0, evs=(None, None), deps=(0, 0), noise=(0, 0), fast=(0, 0), share=(256, 256), considered=(0, 0),
+              gumbel_noise=0, visit_offset=0, scale=0, tb=None, mode=0, count=1):
+    """The argument list of gbl(_cpu)_collect_search ("search") or of its _`entry`: every value a member of the family may take, by
+    the ABI's name, of which nat.SELFPLAY_ARGS picks and orders the entry point's own.  ptr(x) turns an array (or None) into a pointer,
+    evs are gbl_evaluator structs (or None), tb a tests.selfplay_tb_harness.Table (or None: NULL for all three)."""
+    name = symbol(entry)
+    ev0, ev1 = (None if e is None else C.addressof(e) for e in evs)
+    every = dict(
+        state=ptr(st), to_move=ptr(tm), done=ptr(dn), **{arg: ptr(traj.get(k)) for arg, k in TRAJ_BUFFERS.items()}, n=n, ply_stride=ps,
+        tile_stride=ts, seed=seed, env_base=env_base, ply0=ply0, ply_dev=ptr(pd), plies=T, policy0=CODES[pols[0]], policy1=CODES[pols[1]],
+        ev0=ev0, ev1=ev1, iterations0=its[0], iterations1=its[1], playouts0=pls[0], playouts1=pls[1], max_plies=M, solve_depth0=deps[0],
+        solve_depth1=deps[1], noise0=int(noise[0]), noise1=int(noise[1]), explore=X, sample_plies=sample_plies, illegal_mode=illegal_mode,
+        counters=ptr(counters), turn=ptr(tn), fast_iterations0=int(fast[0]), fast_iterations1=int(fast[1]), full_share0=int(share[0]),
+        full_share1=int(share[1]), considered0=int(considered[0]), considered1=int(considered[1]), gumbel_noise=int(gumbel_noise),
+        visit_offset=int(visit_offset), scale=int(scale), inventory=None if tb is None else tb.inv, aux=None if tb is None else ptr(tb.aux),
+        table=None if tb is None else ptr(tb.table), tb_mode=mode, tb_count=count, stream=stream)
+    return nat.selfplay_args(name, **{k: every[k] for k, _ in nat.SELFPLAY_ARGS[name]})
 
 
 def _run(entry, f, ok, put, get, ptr, pad, stream, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0,
@@ -99,8 +115,9 @@ def _run(entry, f, ok, put, get, ptr, pad, stream, st, tm, turn, T, pols, X, sam
 
 def host_collect(entry, f, err, st, tm, turn, T, pols, X, sample_plies, illegal_mode, layout, seed, env_base, ply0, ply_dev=None, keep=None,
                  counters=None, nets=(None, None), **sides):
-    """`f` = gbl_cpu_collect_search* of `entry` on host arrays; only the outputs named in `keep` are given (None: all); sides: its=,
-    pls=, M=, deps=, noise=; nets: restatement Nets.  Returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
+    """`f` = gbl_cpu_collect_search* of `entry` on host arrays; only the outputs named in `keep` are given (None: all); sides: what
+    call_args takes by keyword (its=, pls=, M=, deps=, noise=, fast=, share=, considered=, ..., tb=, mode=, count=) and _run's
+    strides= / store=; nets: restatement Nets.  Returns ({name: (T, n, ...)}, state, to_move, done, turn)."""
     def ok(rc):
         assert rc == 0, err()
 
@@ -115,7 +132,7 @@ def device_collect(entry, st, tm, turn, T, pols, X, sample_plies, illegal_mode, 
     """gbl_collect_search* of `entry` on the device, every output between canaries; nets: DeviceNets; counters: a device tensor; the
     same return value as host_collect."""
     import torch
-    name = "gbl_collect_search" + ("" if entry == "search" else "_" + entry)
+    name = symbol(entry)
 
     def get(t):
         torch.cuda.synchronize()

@@ -26,6 +26,27 @@ def test_header_symbols_all_exported():
         assert getattr(L, name) is not None
 
 
+def test_selfplay_args_are_the_headers_declarations():
+    """nat.SELFPLAY_ARGS -- the one place the Python side takes the self-play family's argument order from -- against the seven
+    declarations of include/gobblet_hip.h, parameter by parameter: the name, and the ctype of its C type.  (gobblet_cpu.h is held
+    against gobblet_hip.h textually below, so all fourteen declarations are pinned.)"""
+    hdr = open(os.path.join(ROOT, "include", "gobblet_hip.h")).read()
+    ctype_of = {"int64_t": C.c_int64, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "int": C.c_int}
+    family = set(re.findall(r"^int (gbl_collect_search[a-z_]*)\(", hdr, re.M))
+    assert family == set(nat.SELFPLAY_ARGS) and len(family) == 7, family ^ set(nat.SELFPLAY_ARGS)
+    for name, table in nat.SELFPLAY_ARGS.items():
+        declared = []
+        for param in re.search(r"^int " + name + r"\(([^;]*)\);", hdr, re.M).group(1).split(","):
+            ctype, pointer, param_name = re.fullmatch(r"\s*(?:const )?(\w+) (\*?)(\w+)\s*", param).groups()
+            declared.append((param_name, C.c_void_p if pointer else ctype_of[ctype]))
+        assert declared == list(table), (name, [(d, t) for d, t in zip(declared, table) if d != t], len(declared), len(table))
+        assert nat.SIGNATURES[name] == (C.c_int, [t for _, t in table])
+    with pytest.raises(TypeError, match="'turn'"):
+        nat.selfplay_args("gbl_collect_search", **{k: None for k, _ in nat.SELFPLAY_ARGS["gbl_collect_search"] if k != "turn"})
+    with pytest.raises(TypeError, match="'ev0'"):
+        nat.selfplay_args("gbl_collect_search", **{k: None for k, _ in nat.SELFPLAY_ARGS["gbl_collect_search"]}, ev0=None)
+
+
 def kernel_metadata(lib_path=None):
     """{kernel symbol: {field: value}} from the AMDGPU metadata note of the gfx950 code object embedded in the library."""
     import shutil

@@ -11,11 +11,11 @@ import torch
 
 from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
-from tests.gumbel_harness import (LONG_PAIRS, call_args, device_collect_gumbel, host_collect_gumbel, root_value_edge_case, rule_boards,
-                                  sigma_edge_case, winning_action_case)
+from tests.gumbel_harness import (LONG_PAIRS, device_collect_gumbel, host_collect_gumbel, root_value_edge_case, rule_boards, sigma_edge_case,
+                                  winning_action_case)
 from tests.search_harness import DEV, ENTRIES, G, run  # noqa: F401  (G: the fixture)
 from tests.search_harness import same as same_arrays
-from tests.selfplay_harness import EVAL_NAMES, DeviceNet, same, strides
+from tests.selfplay_harness import EVAL_NAMES, DeviceNet, call_args, same, strides
 from tests.test_gumbel_search import SCHEDULE
 from tests.test_selfplay_solve import EXPLORE, fixture_boards, smoke_net
 
@@ -163,9 +163,10 @@ def test_k_collect_gumbel_more_boards_than_workgroups(G, boards, nets):
             for k, dt, tail in EVAL_NAMES}
     evs = [x.struct() for x in dn]
     kw = dict(noise=1, visit_offset=50, scale=23, X=EXPLORE, sample_plies=0, seed=SEED, ply0=3)
-    nat.check(nat.lib().gbl_collect_search_gumbel(*call_args(nat.ptr, st, tm, done, traj, n, ps, ts, SEED, ENV_BASE, 3, None, 1, ("eval", "eval"),
-                                                             evs, its, EXPLORE, 0, nat.ILLEGAL_NOOP, None, turn, considered, 1, 50, 23,
-                                                             nat.current_stream(DEV))), "gbl_collect_search_gumbel")
+    nat.check(nat.lib().gbl_collect_search_gumbel(*call_args("gumbel", nat.ptr, st, tm, done, traj, n, ps, ts, SEED, ENV_BASE, 3, None, 1,
+                                                             ("eval", "eval"), EXPLORE, 0, nat.ILLEGAL_NOOP, None, turn, nat.current_stream(DEV),
+                                                             evs=evs, its=its, considered=considered, gumbel_noise=1, visit_offset=50, scale=23)),
+              "gbl_collect_search_gumbel")
     torch.cuda.synchronize()
     for lo, hi in ((0, 64), (n - 130, n)):
         exp = host_collect_gumbel(*cycled(boards, lo, hi), 1, ("eval", "eval"), hn, its, considered, env_base=ENV_BASE + lo, **kw)

@@ -18,11 +18,11 @@ from gobblet_rl_amd import _native as nat
 from tests import evaluator_restatement as R
 from tests import gumbel_restatement as GR
 from tests import solver_restatement as SR
-from tests.gumbel_harness import (GUMBEL_NAMES, LONG_PAIRS, PAIRS, call_args, host_collect_gumbel, root_value_edge_case, rule_boards,
-                                  sigma_edge_case, winning_action_case)
+from tests.gumbel_harness import (GUMBEL_NAMES, LONG_PAIRS, PAIRS, host_collect_gumbel, root_value_edge_case, rule_boards, sigma_edge_case,
+                                  winning_action_case)
 from tests.search_harness import run
 from tests.search_harness import same as same_arrays
-from tests.selfplay_harness import _evaluator, host_collect, same
+from tests.selfplay_harness import _evaluator, call_args, host_collect, same
 from tests.test_selfplay_solve import EXPLORE, fixture_boards, smoke_net
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -457,8 +457,9 @@ def test_argument_errors(flavour):
         kw.update(over)
         evs = [net.struct() if p == "eval" else None for p in kw["pols"]]
         # n = 0: every check of the arguments runs, and nothing is read or launched
-        rc = f(*call_args(lambda a: a, None, None, None, {}, 0, 64, 64, 1, 0, 0, None, 4, kw["pols"], evs, kw["its"], 16, 0, nat.ILLEGAL_NOOP,
-                          None, None, kw["considered"], kw["noise"], kw["vo"], kw["scale"], None))
+        rc = f(*call_args("gumbel", lambda a: a, None, None, None, {}, 0, 64, 64, 1, 0, 0, None, 4, kw["pols"], 16, 0, nat.ILLEGAL_NOOP, None, None,
+                          None, evs=evs, its=kw["its"], considered=kw["considered"], gumbel_noise=kw["noise"], visit_offset=kw["vo"],
+                          scale=kw["scale"]))
         if msg is None:
             assert rc == nat.OK, (name, err())
         else:

@@ -13,8 +13,8 @@ from gobblet_rl_amd import _native as nat
 from tests import cap_restatement as CR
 from tests import evaluator_restatement as R
 from tests.search_harness import run
-from tests.selfplay_cap_harness import FULL, call_args, host_collect_cap
-from tests.selfplay_harness import _evaluator, same
+from tests.selfplay_cap_harness import FULL, host_collect_cap
+from tests.selfplay_harness import _evaluator, call_args, same
 from tests.test_selfplay_solve import EXPLORE, collect_solve, fixture_boards, smoke_net
 
 N_BOARDS, T = 130, 6
@@ -227,8 +227,8 @@ def test_argument_errors(flavour):
         kw.update(over)
         evs = [net.struct() if p == "eval" else None for p in kw["pols"]]
         # n = 0: every check of the arguments runs, and nothing is read or launched
-        rc = f(*call_args(lambda a: a, None, None, None, {}, 0, 64, 64, 1, 0, 0, None, 4, kw["pols"], evs, kw["its"], kw["deps"], kw["noise"], 16, 0,
-                          nat.ILLEGAL_NOOP, None, None, kw["fast"], kw["share"], None))
+        rc = f(*call_args("cap", lambda a: a, None, None, None, {}, 0, 64, 64, 1, 0, 0, None, 4, kw["pols"], 16, 0, nat.ILLEGAL_NOOP, None, None,
+                          None, evs=evs, its=kw["its"], deps=kw["deps"], noise=kw["noise"], fast=kw["fast"], share=kw["share"]))
         if msg is None:
             assert rc == nat.OK, (name, err())
         else:
