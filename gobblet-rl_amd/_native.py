@@ -91,12 +91,23 @@ SELFPLAY_ARGS = {
     "gbl_collect_search_tb": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_NOISE + _TAIL + _args(_vp, "inventory", "aux", "table") +
                              _args(_int, "tb_mode", "tb_count") + _args(_vp, "tb_outcome_traj", "tb_value_traj", "tb_played_traj") + _STREAM,
 }
+_GUMBEL = _args(_int, "considered0", "considered1", "gumbel_noise", "visit_offset", "scale")
+# ... and the self-play entry points outside the gbl_collect_search* names, from the same blocks: selfplay_args() / selfplay_call() look
+# in both tables; tests/test_gumbel_solve.py holds this one against both headers.
+SELFPLAY_ARGS_MORE = {
+    "gbl_collect_gumbel_solve": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_SOLVE + _TAIL + _GUMBEL + _STREAM,
+}
+
+
+def selfplay_table(entry: str) -> tuple:
+    """``entry``'s ((parameter name, ctype), ...) in the ABI's order, from whichever of the two tables has it."""
+    return SELFPLAY_ARGS[entry] if entry in SELFPLAY_ARGS else SELFPLAY_ARGS_MORE[entry]
 
 
 def selfplay_args(entry: str, **named) -> list:
-    """The values of ``named`` in the order ``entry`` takes them (``SELFPLAY_ARGS``).  A missing or an unknown name is a TypeError;
-    nothing is defaulted and nothing converted."""
-    names = [name for name, _ in SELFPLAY_ARGS[entry]]
+    """The values of ``named`` in the order ``entry`` takes them (``SELFPLAY_ARGS`` / ``SELFPLAY_ARGS_MORE``).  A missing or an
+    unknown name is a TypeError; nothing is defaulted and nothing converted."""
+    names = [name for name, _ in selfplay_table(entry)]
     for name in names:
         if name not in named:
             raise TypeError(f"{entry}: missing argument {name!r}")
@@ -152,7 +163,7 @@ SIGNATURES = {
                                 _int, _vp, _vp, _vp]),
     "gbl_collect_from_ex": (_int, [_vp] * 12 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _vp, _vp, _vp]),
     "gbl_collect_policy": (_int, [_vp] * 14 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _int, _int, _vp, _vp, _vp]),
-    **{entry: (_int, [ctype for _, ctype in args]) for entry, args in SELFPLAY_ARGS.items()},
+    **{entry: (_int, [ctype for _, ctype in args]) for entry, args in {**SELFPLAY_ARGS, **SELFPLAY_ARGS_MORE}.items()},
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_symmetry_apply": (_int, [_vp, _int, _vp] + [_vp] * 12 + [_i64, _vp]),
     "gbl_training_batch": (_int, [_vp] * 6 + [_i64, _u32, _i64, _i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),

@@ -1,6 +1,6 @@
 """``BatchedGobblet.collect``'s reading of ``policies=`` / ``search=`` for the self-play family (``gbl_collect_search`` and its
-``_eval``, ``_solve``, ``_noise``, ``_cap``, ``_gumbel`` and ``_tb``): which entry point a call takes, which trajectory buffers it
-needs and the arguments the parse decides, by the names of ``_native.SELFPLAY_ARGS``.  ``collect`` adds what belongs to the
+``_eval``, ``_solve``, ``_noise``, ``_cap``, ``_gumbel`` and ``_tb``, and ``gbl_collect_gumbel_solve``): which entry point a call takes, which trajectory buffers it
+needs and the arguments the parse decides, by the names of ``_native.SELFPLAY_ARGS`` / ``SELFPLAY_ARGS_MORE``.  ``collect`` adds what belongs to the
 environment (the boards, the buffers, the window, the counters, the stream) and calls.  What the keys mean: ``collect``'s docstring."""
 from __future__ import annotations
 
@@ -38,7 +38,7 @@ def plan(policies, search, device) -> Plan:
     if ep is None:
         return Plan("gbl_collect_search", outputs,
                     dict(named, playouts0=sp["playouts"][0], playouts1=sp["playouts"][1], max_plies=sp["max_plies"]), [])
-    # a table side or the judge -> _tb; the Gumbel root rule -> _gumbel; a playout cap -> _cap; else any noise weight -> _noise (the
+    # a table side or the judge -> _tb; the Gumbel root rule -> _gumbel, with a solve depth of its own -> gbl_collect_gumbel_solve; a playout cap -> _cap; else any noise weight -> _noise (the
     # guarded kernel, whatever the depths), else any solve depth -> _solve, else _eval
     cap, gum = ep.get("cap"), ep.get("gumbel")
     if tp is not None:
@@ -47,7 +47,7 @@ def plan(policies, search, device) -> Plan:
         if not judged:  # (the three verdict arrays are the judge's: without it NULL, whatever the buffers hold)
             named.update(tb_outcome_traj=None, tb_value_traj=None, tb_played_traj=None)
     elif gum is not None:
-        entry = "gbl_collect_search_gumbel"
+        entry = "gbl_collect_gumbel_solve" if guarded else "gbl_collect_search_gumbel"
         named.update(considered0=gum["considered"][0], considered1=gum["considered"][1], gumbel_noise=gum["noise"],
                      visit_offset=gum["visit_offset"], scale=gum["scale"])
     elif cap is not None:
@@ -60,7 +60,7 @@ def plan(policies, search, device) -> Plan:
     ev0, ev1 = (None if st is None else C.addressof(st) for st in structs)
     sides = dict(ev0=ev0, ev1=ev1, solve_depth0=ep["solve_depth"][0], solve_depth1=ep["solve_depth"][1], noise0=ep["noise"][0], noise1=ep["noise"][1])
     # (an entry point without the depths or the weights was chosen because they are all 0)
-    named.update({name: sides[name] for name, _ in nat.SELFPLAY_ARGS[entry] if name in sides})
+    named.update({name: sides[name] for name, _ in nat.selfplay_table(entry) if name in sides})
     return Plan(entry, outputs, named, structs)
 
 
@@ -193,33 +193,40 @@ def _evaluator_params(policies, search, device):
         raise ValueError("search: explore must be in [0, 1024], sample_plies >= 0")
     gumbel = _gumbel_params(kw["gumbel"], codes)
     if gumbel is not None and (any(deps) or any(nzs) or kw["cap"] is not None):
-        raise ValueError("search: gumbel does not go with solve_depth, noise or cap (gbl_collect_search_gumbel has none of them)")
+        raise ValueError("search: gumbel does not go with solve_depth, noise or cap beside it (the guard of a Gumbel side is "
+                         "gumbel=dict(solve_depth=...): gbl_collect_gumbel_solve; the rule has no root noise and no cap)")
+    if gumbel is not None:
+        deps = gumbel.pop("solve_depth")
     return dict(policies=codes, evaluators=nets, iterations=its, explore=explore, sample_plies=int(kw["sample_plies"]),
                 solve_depth=deps, noise=nzs, cap=_cap_params(kw["cap"], codes, its), gumbel=gumbel)
 
 
 def _gumbel_params(gumbel, codes):
-    """``search=dict(gumbel=dict(considered=, noise=, visit_offset=, scale=))`` as ``gbl_collect_search_gumbel`` takes it --
-    ``considered`` per side (0: that side keeps the search above), the rest for both -- or None where no evaluator side follows
-    the rule (an absent ``gumbel``, ``considered=0``): the call keeps its entry point."""
+    """``search=dict(gumbel=dict(considered=, noise=, visit_offset=, scale=, solve_depth=))`` as ``gbl_collect_search_gumbel`` and
+    ``gbl_collect_gumbel_solve`` take it -- ``considered`` (0: that side keeps the search above) and ``solve_depth`` (the guard in front
+    of that side's searches, 0: none) per side, the rest for both -- or None where no evaluator side follows the rule or is guarded
+    through it (an absent ``gumbel``, ``considered=0`` without a depth): the call keeps its entry point."""
     from .evaluator_policy import gumbel_args
     if gumbel is None:
         return None
     if not isinstance(gumbel, dict):
-        raise ValueError("search: gumbel is a dict of considered / noise / visit_offset / scale")
-    considered = _pair(gumbel.get("considered", 16))
-    if len(considered) != 2:
-        raise ValueError("search: gumbel's considered is a value or a pair, one per side")
-    rest = gumbel_args(dict(gumbel, considered=1))
+        raise ValueError("search: gumbel is a dict of considered / noise / visit_offset / scale / solve_depth")
+    considered, depths = _pair(gumbel.get("considered", 16)), _pair(gumbel.get("solve_depth", 0))
+    if len(considered) != 2 or len(depths) != 2:
+        raise ValueError("search: gumbel's considered / solve_depth are a value or a pair, one per side")
+    rest = gumbel_args({k: v for k, v in dict(gumbel, considered=1).items() if k != "solve_depth"})
     for m in range(2):
         if codes[m] != nat.POLICY_EVAL_TREE:
-            considered[m] = 0
-        elif isinstance(considered[m], bool) or not 0 <= int(considered[m]) <= 54:
+            considered[m] = depths[m] = 0
+            continue
+        if isinstance(considered[m], bool) or not 0 <= int(considered[m]) <= 54:
             raise ValueError("search: gumbel's considered must be in [0, 54]")
-        considered[m] = int(considered[m])
-    if not any(considered):
+        if isinstance(depths[m], bool) or int(depths[m]) != depths[m] or not 0 <= int(depths[m]) <= nat.SOLVE_MAX_DEPTH:
+            raise ValueError(f"search: gumbel's solve_depth must be in [0, {nat.SOLVE_MAX_DEPTH}]")
+        considered[m], depths[m] = int(considered[m]), int(depths[m])
+    if not any(considered) and not any(depths):
         return None
-    return dict(considered=considered, noise=rest["noise"], visit_offset=rest["visit_offset"], scale=rest["scale"])
+    return dict(considered=considered, noise=rest["noise"], visit_offset=rest["visit_offset"], scale=rest["scale"], solve_depth=depths)
 
 
 def _cap_params(cap, codes, its):

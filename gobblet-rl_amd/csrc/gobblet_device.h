@@ -2294,7 +2294,7 @@ constexpr uint32_t kStreamGumbel = 10u;  // generator stream of the Gumbel row
 constexpr int kGumbelMaxConsidered = 54, kGumbelMaxOffset = 255, kGumbelMaxScale = 64;
 constexpr int kHowGumbel = 10;  // GBL_HOW_GUMBEL
 
-struct GumbelArgs {  // considered == 0: the side searches by gbl_tree_search_eval's rule (gbl_collect_search_gumbel alone admits it)
+struct GumbelArgs {  // considered == 0: the side searches by gbl_tree_search_eval's rule (the self-play entry points with the rule alone admit it)
     uint32_t considered, noise, visit_offset, scale;
 };
 
@@ -2699,7 +2699,7 @@ inline const char *collect_solve_error(int illegal_mode, int policy0, int policy
     return nullptr;
 }
 
-// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise, _cap, _gumbel and _tb, and the checks both flavours make of them ----
+// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise, _cap, _gumbel and _tb and of gbl_collect_gumbel_solve, and the checks both flavours make of them ----
 // The 19 trajectory arrays (any may be NULL).
 struct SelfplayTraj {
     int32_t *actions;
@@ -2713,9 +2713,9 @@ struct SelfplayTraj {
     int8_t *tb_outcome, *tb_value, *tb_played;  // (the table's verdict of every ply: NULL but in gbl_collect_search_tb)
 };
 
-enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval and _gumbel; _solve, _noise and _cap; _tb
+enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval and _gumbel; _solve, _noise, _cap and gbl_collect_gumbel_solve; _tb
 
-// The union of the seven entry points' arguments; an entry point (gobblet_selfplay_entries.inc, one text for both flavours) fills it,
+// The union of the eight entry points' arguments; an entry point (gobblet_selfplay_entries.inc, one text for both flavours) fills it,
 // leaving 0 / NULL what it does not have, and calls its flavour's one runner.  [0] is player_1's, [1] player_2's.  Ev: gbl_evaluator.
 template <typename Ev>
 struct SelfplayCall {
@@ -2741,7 +2741,7 @@ struct SelfplayCall {
     // gbl_collect_search_cap's own (cap = 0 elsewhere: neither array is read)
     int cap;
     int fast[2], share[2];
-    // gbl_collect_search_gumbel's own (gumbel = 0 elsewhere: none is read)
+    // gbl_collect_search_gumbel's and gbl_collect_gumbel_solve's own (gumbel = 0 elsewhere: none is read)
     int gumbel;
     int considered[2];
     int gumbel_noise, visit_offset, scale;
@@ -2801,7 +2801,7 @@ inline const char *collect_tb_error(const SelfplayCall<Ev> &c)
 }
 
 // Everything both flavours look at, in the order they report it: n < 0, the entry point's *_error, the searching sides' noise
-// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) (gbl_collect_search_gumbel: their `considered`, then the
+// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) (gbl_collect_search_gumbel, gbl_collect_gumbel_solve: their `considered`, then the
 // rule's three where a side follows it,) n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
 // per searching side `side(m)` -- the flavour's own look at evaluator m
 // (its pointers; on the device their alignment too), which returns 0 or what its fail() returned.  Returns a flavour's error
@@ -2831,7 +2831,7 @@ inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, 
             if (c.policy[m] == searching && c.share[m] < kCapFullShare)
                 if (const char *bad = cap_fast_error(c.fast[m], c.iterations[m])) return fail(bad);
     }
-    if (c.gumbel) {  // gbl_collect_search_gumbel: the searching sides' considered, then the rule's three where a side follows it
+    if (c.gumbel) {  // gbl_collect_search_gumbel, gbl_collect_gumbel_solve: the searching sides' considered, then the rule's three where a side follows it
         for (int m = 0; m < 2; ++m)
             if (c.policy[m] == searching)
                 if (const char *bad = gumbel_error(c.considered[m], 0, 0, 0, 0)) return fail(bad);

@@ -3782,6 +3782,81 @@ __global__ __launch_bounds__(64) void k_collect_solve(int8_t *__restrict__ state
         });
 }
 
+// gbl_collect_gumbel_solve: k_collect_solve<false, false> with the Gumbel root rule on the unproven ply -- the kernel of a call that has
+// both a guarded side and a Gumbel side (selfplay_launch runs k_collect_eval<true> or k_collect_solve<false, false> for every other
+// call of the entry point, so neither of them carries the other's code).  A guarded ply is k_collect_solve's: solve_board on the live
+// planes, a proven root plays the solver's action and neither searches nor draws.  The ply that goes on searches over cand = C (the
+// actions of outcome 0; the legal mask of an unguarded side) exactly as k_collect_eval<true> does over the legal mask:
+// tree_eval_iterations<false, true>, and for a side with considered_m > 0 wave_gumbel_finish on the root's read-out -- ply q's search IS
+// gbl_tree_search_gumbel(mask = C, call = q).  A side with considered_m == 0 decides by search_decide, sample_plies honoured.  The
+// solver's registers are dead before the tree's come alive; its LDS stands beside the tree's, fenced by wave_lds_fence.  gum.G's
+// considered is not read: the two sides' own travel beside it.
+__global__ __launch_bounds__(64) void k_collect_gumbel_solve(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                             uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
+                                                             uint32_t plies, int8_t *__restrict__ done, int64_t ply_stride,
+                                                             int64_t tile_stride, SearchTraj T, int32_t *__restrict__ root_value_traj,
+                                                             uint8_t *__restrict__ priors_traj, int8_t *__restrict__ outcome_traj,
+                                                             int8_t *__restrict__ proven_traj, const EvalNet net0, const EvalNet net1,
+                                                             int policy0, int policy1, uint32_t iterations0, uint32_t iterations1,
+                                                             int solve_depth0, int solve_depth1, uint32_t most, uint32_t explore,
+                                                             int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
+                                                             int32_t *__restrict__ turn, const GumbelArgs gum, uint32_t considered0,
+                                                             uint32_t considered1)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    __shared__ SolveLds s_solve;
+    const uint32_t lane = threadIdx.x;
+    int my_c = kSolveNone, proven = 0;  // the ply's outcome byte of this lane and V, from the first lambda to the second
+    search_plies(
+        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            my_c = kSolveNone;
+            proven = 0;
+            if ((who ? policy1 : policy0) != kPolicyEvalTree) return false;
+            const uint32_t its = who ? iterations1 : iterations0;
+            const int depth = who ? solve_depth1 : solve_depth0;
+            uint64_t cand = legal;
+            if (depth > 0 && legal) {  // (wave-uniform)
+                const uint32_t best = solve_board<knob::kSolveDeal, false>(s_solve, B.p, who, legal, depth, lane, my_c);
+                if (depth > 2) solve_fence<false>();  // (before the next ply's solve rewrites the LDS arrays)
+                proven = uniform(solve_value_of(best));
+                if (proven) {
+                    const int a = uniform(solve_action_of(best));
+                    S.d = SearchDecision{a, kHowProven, (proven > 0 ? 128 : -128) * (int)its, lane == (uint32_t)a ? its : 0u};
+                    return true;
+                }
+                cand = (uint64_t)__ballot(my_c == 0);
+            }
+            uint32_t mixed;  // (no noise here: the network's byte)
+            WaveGumbel gb{GumbelArgs{who ? considered1 : considered0, gum.noise, gum.visit_offset, gum.scale}, seed, g, q, 0, 0, 0ull};
+            const WaveEval at_root = tree_eval_iterations<false, true>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its,
+                                                                       explore, lane, S.count, RootNoise{}, mixed, &gb);
+            S.pi = at_root.pi;
+            S.root_q = at_root.q;
+            const bool rule = gb.G.considered != 0u;  // (wave-uniform) a Gumbel side's ply
+            S.d = search_decide(nodes, lane, !rule && B.tabs < sample_plies, seed, g, q);
+            if (rule) {
+                GumbelOut out{-1, 0u};
+                if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), cand, at_root.q, lane);
+                S.d.action = out.action;
+                S.d.how = kHowGumbel;
+                S.d.my_n = out.target;
+            }
+            wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            return true;
+        },
+        [&](int64_t at, const SearchPly &S) {
+            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
+            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
+            if (outcome_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((int8_t)my_c, outcome_traj + at * kActions + lane);
+            if (proven_traj && lane == 0) proven_traj[at] = (int8_t)proven;
+        });
+}
+
 // gbl_collect_search_tb: k_collect_solve with the tablebase's probe in front of every ply that is judged or played from the table.
 // The probe is k_tb_probe's on the live planes: lane a < 54 takes action a, its successor's three look-ups go to `aux` in global
 // memory and one byte comes from anywhere in the table (a 64-bit offset); a butterfly gives V and a*.  A TABLEBASE mover's ply is done
@@ -5404,7 +5479,7 @@ int gbl_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int
     GBL_LAUNCHED("gbl_tree_search_gumbel");
 }
 
-// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb) between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
+// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb, and gbl_collect_gumbel_solve) between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
 // evaluators as the kernels take them, the trajectory's strides and alignments, the grid, the tree's LDS and the entry's own kernel.
 static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &c, void *stream)
 {
@@ -5429,7 +5504,19 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     // the tree: one node per iteration and the root; with an evaluator a prior row beside each (36.9 KB at 512 iterations, as
     // gbl_tree_search_eval; the solver's arrays are static LDS beside it)
     const size_t lds = (sizeof(TreeNode) + (uct ? 0 : kEvalOutputs)) * ((size_t)most + 1);
-    if (uct) {
+    // gbl_collect_gumbel_solve: a call with a Gumbel side and a guarded side runs its own kernel; with no Gumbel side it is
+    // gbl_collect_search_solve's launch below, and with no guarded side and neither of the guard's arrays to fill it is
+    // gbl_collect_search_gumbel's (k_collect_eval writes no outcome row: a call that wants the GBL_SOLVE_NONE rows keeps the kernel that does)
+    const bool guarded = (c.policy[0] == GBL_POLICY_EVAL_TREE && c.solve_depth[0] > 0) || (c.policy[1] == GBL_POLICY_EVAL_TREE && c.solve_depth[1] > 0);
+    const bool rule_side = selfplay_considered(c, 0) || selfplay_considered(c, 1);
+    const bool rule_unguarded = c.run == kRunSolve && rule_side && !guarded && !t.outcome && !t.proven;
+    if (c.run == kRunSolve && rule_side && !rule_unguarded) {
+        const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
+        hipLaunchKernelGGL(k_collect_gumbel_solve, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
+                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1], c.policy[0],
+                           c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies, c.illegal_mode,
+                           c.counters, c.turn, gum, (uint32_t)selfplay_considered(c, 0), (uint32_t)selfplay_considered(c, 1));
+    } else if (uct) {
         // the larger leaf of the sides that search
         const int wide = std::max(1, std::max(c.policy[0] == GBL_POLICY_TREE ? c.playouts[0] : 0, c.policy[1] == GBL_POLICY_TREE ? c.playouts[1] : 0));
 #define GBL_CS(W)                                                                                                                         \
@@ -5442,7 +5529,7 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
         default: GBL_CS(1); break;
         }
 #undef GBL_CS
-    } else if (c.run == kRunEval) {
+    } else if (c.run == kRunEval || rule_unguarded) {
         const uint32_t m0 = (uint32_t)selfplay_considered(c, 0), m1 = (uint32_t)selfplay_considered(c, 1);
         const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
         // (k_collect_eval<false> is the kernel without the rule's code: gbl_collect_search_eval, and gbl_collect_search_gumbel with no Gumbel side)
@@ -5498,7 +5585,7 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     GBL_LAUNCHED(name);
 }
 
-// the seven entry points themselves: one text for both flavours
+// the eight entry points themselves: one text for both flavours
 #define GBL_SELFPLAY_SYMBOL(fn) gbl_##fn
 #define GBL_SELFPLAY_RUN(name, call, stream) selfplay_launch(name, call, stream)
 #include "gobblet_selfplay_entries.inc"

@@ -377,6 +377,9 @@ GUMBEL_TABLE = tuple(int(x) for x in np.rint(-np.log(-np.log((np.arange(256) + 0
 def gumbel_args(gumbel: dict) -> dict:
     """``gumbel=dict(...)`` with the defaults filled in, as the ABI takes it: considered 1 .. 54, noise 0 / 1, visit_offset 0 .. 255,
     scale 0 .. 64."""
+    if isinstance(gumbel, dict) and "solve_depth" in gumbel:  # (collect()'s gumbel dict alone has the key: gbl_collect_gumbel_solve)
+        raise ValueError("gumbel: solve_depth belongs to collect(search=dict(gumbel=...)); a single decision is guarded by "
+                         "SolverGobbletPolicy(depth, fallback=this policy)")
     if not isinstance(gumbel, dict) or set(gumbel) - set(GUMBEL_DEFAULTS):
         raise ValueError("gumbel is a dict of considered / noise / visit_offset / scale")
     kw = {**GUMBEL_DEFAULTS, **gumbel}

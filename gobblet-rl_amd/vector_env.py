@@ -470,7 +470,13 @@ class BatchedGobblet:
         budget spent on them by sequential halving, and the completed-Q improved policy as the target -- "visits" holds that row (1 ..
         255 on the candidates), so EVERY ply of such a side is a policy target for ``training_batch`` / ``ReplayBuffer.append``.
         "how" is ``nat.HOW_GUMBEL``; ``sample_plies`` is not read for such a side (the noise is its exploration); ``gumbel_row``
-        recomputes the noise.  Not with ``solve_depth``, ``noise``, ``cap``, a "tablebase" side or ``judge=True``.
+        recomputes the noise.  Not with ``solve_depth``, ``noise`` or ``cap`` beside it, a "tablebase" side or ``judge=True``.
+
+        ``gumbel=dict(..., solve_depth=d)`` (an int, or a pair, one per side; 0 or absent: none) is the solver's guard of such a
+        window, still one launch (``gbl_collect_gumbel_solve``): a root the solver proves plays the solver's action (``nat.HOW_PROVEN``,
+        a one-hot row, no noise drawn), every other root runs the Gumbel search over its unproven actions only, and the buffers also
+        receive "outcomes" / "proven" as under ``solve_depth`` above.  A guarded side with ``considered=0`` searches as under
+        ``solve_depth`` above.  Kept rows are the cells with "how" 5 or 10.
 
         A side "tablebase" (or a ``TablebaseGobbletPolicy`` instance, which supplies its table) plays from the exact table INSIDE the
         launch (``gbl_collect_search_tb``), against "tablebase", "evaluator" or "random": ``search=dict(..., tablebase=tb,
@@ -529,7 +535,7 @@ class BatchedGobblet:
             if plan.outputs["tablebase_outputs"] and "tb_value" not in f:
                 raise ValueError("judge=True needs buffers from trajectory_buffers(tablebase_outputs=True)")
             # the trajectory arrays this member takes and the plan has not decided: the buffers' (NULL where the set has none)
-            takes = {name for name, _ in nat.SELFPLAY_ARGS[entry]}
+            takes = {name for name, _ in nat.selfplay_table(entry)}
             traj = {a: nat.ptr(f.get(k)) for a, k in _selfplay.TRAJ_BUFFERS.items() if a in takes and a not in named}
             # (plan.alive -- the evaluator structs behind ev0 / ev1 -- lives until this call has returned)
             nat.check(nat.selfplay_call(

@@ -746,8 +746,9 @@ int gbl_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t
  *   a root without a candidate: action -1, stepped per illegal_mode, the row zeros, how = GBL_HOW_GUMBEL.
  * The Gumbel row moves with *ply_dev as every other draw of the window does; a consumer recomputes it from (seed, g, q).  Errors are
  * gbl_collect_search_eval's in its order; after them (before the n == 0 return) GBL_ERR_ARG for a considered outside 0 .. 54 on an
- * EVAL_TREE side, then, where a side follows the rule, for gumbel_noise, visit_offset, scale out of range.  The solver guard, root
- * noise, the playout cap and the tablebase are not combined with the rule.  Allocates nothing; the LDS is gbl_collect_search_eval's. */
+ * EVAL_TREE side, then, where a side follows the rule, for gumbel_noise, visit_offset, scale out of range.  The solver guard goes
+ * with the rule in gbl_collect_gumbel_solve, below; root noise, the playout cap and the tablebase are not combined with it.  Allocates
+ * nothing; the LDS is gbl_collect_search_eval's. */
 #define GBL_HOW_GUMBEL 10
 int gbl_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
@@ -757,6 +758,45 @@ int gbl_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int3
                               int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1, int iterations0, int iterations1,
                               int explore, int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, int considered0,
                               int considered1, int gumbel_noise, int visit_offset, int scale, void *stream);
+
+/* Solver-guarded Gumbel self-play (no counterpart in the reference): gbl_collect_search_solve with the unproven ply's search replaced
+ * by the Gumbel root search, inside the same launch.  The arguments are gbl_collect_search_solve's, followed by
+ * gbl_collect_search_gumbel's five: considered0 / considered1 in 0 .. 54 for player_1 / player_2, and gumbel_noise / visit_offset /
+ * scale for both.  A side's depth and `considered` are ignored unless that side is EVAL_TREE.  The ply q of an EVAL_TREE mover m on
+ * board g = env_base + b:
+ *   solve_depth_m = d > 0 and the root has a candidate: (outcome, V, a*) = gbl_solve(state, to_move, mask = NULL, depth = d) of the
+ *   board's current position, as in gbl_collect_search_solve.
+ *     proven    V != 0: exactly gbl_collect_search_solve's proven ply -- the action is a*, how = GBL_HOW_PROVEN, the visits row holds
+ *               iterations_m at a* and 0 elsewhere, value = sign(V) * 128 * iterations_m, nodes = 0, root_value = 0, the prior row
+ *               zeros.  No search runs, nothing is drawn and no Gumbel row is made.
+ *     unproven  V == 0.  With C = the actions whose outcome is 0:
+ *               considered_m > 0   the search is gbl_tree_search_gumbel(state, to_move, mask = C, ev_m, iterations_m, explore,
+ *                                  considered_m, gumbel_noise, visit_offset, scale, seed, env_base, call = q): the rule considers
+ *                                  min(considered_m, |C|) actions of C.  The action is its action_out, how = GBL_HOW_GUMBEL, and
+ *                                  visits_traj holds its target_out -- 1 .. 255 on C, 0 elsewhere; value, nodes, root_value and priors
+ *                                  as gbl_collect_search_gumbel writes them.  sample_plies is not read for this side.
+ *               considered_m == 0  gbl_collect_search_solve's unproven ply: gbl_tree_search_eval(mask = C), the visit-proportional
+ *                                  draw while turn[b] < sample_plies.
+ *   solve_depth_m == 0: the side's ply is gbl_collect_search_gumbel's (over the legal mask); the outcome row is all GBL_SOLVE_NONE
+ *   and V is 0.
+ *   RANDOM sides, a root without a candidate, *ply_dev, the strides, counters and turn: as in gbl_collect_search_solve and
+ *   gbl_collect_search_gumbel, which agree on them.
+ * With both depths 0 every shared array is gbl_collect_search_gumbel's, bit for bit; with both `considered` 0 every array is
+ * gbl_collect_search_solve's, bit for bit.  A board's window depends on (seed, g, the ply indices) alone.  Errors are
+ * gbl_collect_search_solve's in its order (a depth outside 0 .. GBL_SOLVE_MAX_DEPTH on an EVAL_TREE side among them); after them,
+ * before the n == 0 return, GBL_ERR_ARG for a considered outside 0 .. 54 on an EVAL_TREE side, then, where a side follows the rule,
+ * for gumbel_noise, visit_offset, scale out of range; then the pointers.  Root noise, the playout cap and the tablebase are not
+ * combined with the rule.  gbl_outcome_targets, gbl_training_batch and gbl_replay_append work on these trajectories unchanged.
+ * Allocates nothing; the LDS is gbl_collect_search_solve's: the tree and the solver's 872 bytes. */
+int gbl_collect_gumbel_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                             int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                             int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
+                             int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj, int8_t *proven_traj, int64_t n,
+                             int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
+                             const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                             const gbl_evaluator *ev1, int iterations0, int iterations1, int solve_depth0, int solve_depth1, int explore,
+                             int sample_plies, int illegal_mode, int64_t *counters, int32_t *turn, int considered0, int considered1,
+                             int gumbel_noise, int visit_offset, int scale, void *stream);
 
 /* Outcome targets of a collected window of `plies` plies (the value target of a position is the result of the game it belongs
  * to).  For cell (t, b), with e the smallest t' >= t whose done_traj[cell(t', b)] is non-zero:
