@@ -15,6 +15,8 @@
                      ReplayBuffer.reanalyse / GobbletEvaluator.reanalyse: stored rows' visits from the current network's search
                      (gumbel=dict(...): the Gumbel root search's target rows, from 16 iterations)
     Tablebase        the game solved outright, one byte per position: retrograde sweeps and probes; TablebaseGobbletPolicy plays from it
+                     (BatchedGobblet.collect(search=dict(gumbel=dict(tablebase=tb, judge=True))): the table as a side and as the judge of
+                     every ply inside the Gumbel self-play window, one launch)
 
 The compute path is the hand-written HIP library ``csrc/libgobblet_hip.so`` (C-ABI in
 ``include/gobblet_hip.h``); there is no CPU fallback.  Importing this package needs torch;

@@ -78,6 +78,8 @@ _SIDES_SOLVE = _SIDES_EVAL + _args(_int, "solve_depth0", "solve_depth1")
 _SIDES_NOISE = _SIDES_SOLVE + _args(_int, "noise0", "noise1")
 _TAIL = _args(_int, "explore", "sample_plies", "illegal_mode") + _args(_vp, "counters", "turn")
 _STREAM = _args(_vp, "stream")
+_TABLE = _args(_vp, "inventory", "aux", "table") + _args(_int, "tb_mode", "tb_count") + \
+    _args(_vp, "tb_outcome_traj", "tb_value_traj", "tb_played_traj")  # (the table as gbl_tb_probe takes it, its mode and count, the judge's three)
 SELFPLAY_ARGS = {
     "gbl_collect_search": _BOARDS + _TRAJ + _WINDOW + _args(_int, "iterations0", "iterations1", "playouts0", "playouts1", "max_plies") +
                           _TAIL + _STREAM,
@@ -88,24 +90,32 @@ SELFPLAY_ARGS = {
                               _args(_int, "fast_iterations0", "fast_iterations1", "full_share0", "full_share1") + _STREAM,
     "gbl_collect_search_gumbel": _BOARDS + _TRAJ_EVAL + _WINDOW + _SIDES_EVAL + _TAIL +
                                  _args(_int, "considered0", "considered1", "gumbel_noise", "visit_offset", "scale") + _STREAM,
-    "gbl_collect_search_tb": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_NOISE + _TAIL + _args(_vp, "inventory", "aux", "table") +
-                             _args(_int, "tb_mode", "tb_count") + _args(_vp, "tb_outcome_traj", "tb_value_traj", "tb_played_traj") + _STREAM,
+    "gbl_collect_search_tb": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_NOISE + _TAIL + _TABLE + _STREAM,
 }
 _GUMBEL = _args(_int, "considered0", "considered1", "gumbel_noise", "visit_offset", "scale")
 # ... and the self-play entry points outside the gbl_collect_search* names, from the same blocks: selfplay_args() / selfplay_call() look
-# in both tables; tests/test_gumbel_solve.py holds this one against both headers.
+# in every table; tests/test_gumbel_solve.py holds this one against both headers.
 SELFPLAY_ARGS_MORE = {
     "gbl_collect_gumbel_solve": _BOARDS + _TRAJ_SOLVE + _WINDOW + _SIDES_SOLVE + _TAIL + _GUMBEL + _STREAM,
 }
+# ... and beside it the Gumbel window with the table: gbl_collect_search_gumbel's arguments up to `scale`, then gbl_collect_search_tb's
+# table block; tests/test_gumbel_tb.py holds it against both headers.
+SELFPLAY_ARGS_TABLE = {
+    "gbl_collect_gumbel_tb": _BOARDS + _TRAJ_EVAL + _WINDOW + _SIDES_EVAL + _TAIL + _GUMBEL + _TABLE + _STREAM,
+}
+_SELFPLAY_TABLES = (SELFPLAY_ARGS, SELFPLAY_ARGS_MORE, SELFPLAY_ARGS_TABLE)
 
 
 def selfplay_table(entry: str) -> tuple:
-    """``entry``'s ((parameter name, ctype), ...) in the ABI's order, from whichever of the two tables has it."""
-    return SELFPLAY_ARGS[entry] if entry in SELFPLAY_ARGS else SELFPLAY_ARGS_MORE[entry]
+    """``entry``'s ((parameter name, ctype), ...) in the ABI's order, from whichever of the tables has it."""
+    for table in _SELFPLAY_TABLES:
+        if entry in table:
+            return table[entry]
+    raise KeyError(entry)
 
 
 def selfplay_args(entry: str, **named) -> list:
-    """The values of ``named`` in the order ``entry`` takes them (``SELFPLAY_ARGS`` / ``SELFPLAY_ARGS_MORE``).  A missing or an
+    """The values of ``named`` in the order ``entry`` takes them (``SELFPLAY_ARGS`` / ``SELFPLAY_ARGS_MORE`` / ``SELFPLAY_ARGS_TABLE``).  A missing or an
     unknown name is a TypeError; nothing is defaulted and nothing converted."""
     names = [name for name, _ in selfplay_table(entry)]
     for name in names:
@@ -163,7 +173,7 @@ SIGNATURES = {
                                 _int, _vp, _vp, _vp]),
     "gbl_collect_from_ex": (_int, [_vp] * 12 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _vp, _vp, _vp]),
     "gbl_collect_policy": (_int, [_vp] * 14 + [_i64, _i64, _i64, _u64, _u64, _u32, _vp, _u32, _int, _int, _int, _int, _vp, _vp, _vp]),
-    **{entry: (_int, [ctype for _, ctype in args]) for entry, args in {**SELFPLAY_ARGS, **SELFPLAY_ARGS_MORE}.items()},
+    **{entry: (_int, [ctype for _, ctype in args]) for table in _SELFPLAY_TABLES for entry, args in table.items()},
     "gbl_outcome_targets": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _u32, _vp]),
     "gbl_symmetry_apply": (_int, [_vp, _int, _vp] + [_vp] * 12 + [_i64, _vp]),
     "gbl_training_batch": (_int, [_vp] * 6 + [_i64, _u32, _i64, _i64, _i64, _int, _u64, _u64, _u32] + [_vp] * 6 + [_vp]),

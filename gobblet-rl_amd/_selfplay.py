@@ -1,6 +1,6 @@
 """``BatchedGobblet.collect``'s reading of ``policies=`` / ``search=`` for the self-play family (``gbl_collect_search`` and its
-``_eval``, ``_solve``, ``_noise``, ``_cap``, ``_gumbel`` and ``_tb``, and ``gbl_collect_gumbel_solve``): which entry point a call takes, which trajectory buffers it
-needs and the arguments the parse decides, by the names of ``_native.SELFPLAY_ARGS`` / ``SELFPLAY_ARGS_MORE``.  ``collect`` adds what belongs to the
+``_eval``, ``_solve``, ``_noise``, ``_cap``, ``_gumbel`` and ``_tb``, ``gbl_collect_gumbel_solve`` and ``gbl_collect_gumbel_tb``): which entry point a call takes, which trajectory buffers it
+needs and the arguments the parse decides, by the names of ``_native.SELFPLAY_ARGS`` / ``SELFPLAY_ARGS_MORE`` / ``SELFPLAY_ARGS_TABLE``.  ``collect`` adds what belongs to the
 environment (the boards, the buffers, the window, the counters, the stream) and calls.  What the keys mean: ``collect``'s docstring."""
 from __future__ import annotations
 
@@ -38,11 +38,14 @@ def plan(policies, search, device) -> Plan:
     if ep is None:
         return Plan("gbl_collect_search", outputs,
                     dict(named, playouts0=sp["playouts"][0], playouts1=sp["playouts"][1], max_plies=sp["max_plies"]), [])
-    # a table side or the judge -> _tb; the Gumbel root rule -> _gumbel, with a solve depth of its own -> gbl_collect_gumbel_solve; a playout cap -> _cap; else any noise weight -> _noise (the
+    # the table inside the gumbel dict -> gbl_collect_gumbel_tb; a table side or the judge -> _tb; the Gumbel root rule -> _gumbel, with a solve depth of its own -> gbl_collect_gumbel_solve; a playout cap -> _cap; else any noise weight -> _noise (the
     # guarded kernel, whatever the depths), else any solve depth -> _solve, else _eval
     cap, gum = ep.get("cap"), ep.get("gumbel")
     if tp is not None:
-        entry = "gbl_collect_search_tb"
+        entry = "gbl_collect_gumbel_tb" if tp["inner"] else "gbl_collect_search_tb"
+        if tp["inner"]:
+            named.update(considered0=gum["considered"][0], considered1=gum["considered"][1], gumbel_noise=gum["noise"],
+                         visit_offset=gum["visit_offset"], scale=gum["scale"])
         named.update(inventory=tp["inventory"], aux=tp["aux"], table=tp["table"], tb_mode=tp["mode"], tb_count=tp["count"])
         if not judged:  # (the three verdict arrays are the judge's: without it NULL, whatever the buffers hold)
             named.update(tb_outcome_traj=None, tb_value_traj=None, tb_played_traj=None)
@@ -201,11 +204,12 @@ def _evaluator_params(policies, search, device):
                 solve_depth=deps, noise=nzs, cap=_cap_params(kw["cap"], codes, its), gumbel=gumbel)
 
 
-def _gumbel_params(gumbel, codes):
+def _gumbel_params(gumbel, codes, keep=False):
     """``search=dict(gumbel=dict(considered=, noise=, visit_offset=, scale=, solve_depth=))`` as ``gbl_collect_search_gumbel`` and
     ``gbl_collect_gumbel_solve`` take it -- ``considered`` (0: that side keeps the search above) and ``solve_depth`` (the guard in front
     of that side's searches, 0: none) per side, the rest for both -- or None where no evaluator side follows the rule or is guarded
-    through it (an absent ``gumbel``, ``considered=0`` without a depth): the call keeps its entry point."""
+    through it (an absent ``gumbel``, ``considered=0`` without a depth): the call keeps its entry point.  ``keep``: the dict even then
+    (``gbl_collect_gumbel_tb`` takes the rule's arguments whoever follows it)."""
     from .evaluator_policy import gumbel_args
     if gumbel is None:
         return None
@@ -224,7 +228,7 @@ def _gumbel_params(gumbel, codes):
         if isinstance(depths[m], bool) or int(depths[m]) != depths[m] or not 0 <= int(depths[m]) <= nat.SOLVE_MAX_DEPTH:
             raise ValueError(f"search: gumbel's solve_depth must be in [0, {nat.SOLVE_MAX_DEPTH}]")
         considered[m], depths[m] = int(considered[m]), int(depths[m])
-    if not any(considered) and not any(depths):
+    if not any(considered) and not any(depths) and not keep:
         return None
     return dict(considered=considered, noise=rest["noise"], visit_offset=rest["visit_offset"], scale=rest["scale"], solve_depth=depths)
 
@@ -256,9 +260,11 @@ def _cap_params(cap, codes, its):
 
 
 def _tablebase_params(policies, search, device):
-    """The table's arguments of ``gbl_collect_search_tb`` and, under "ep", the rest of the call as ``_evaluator_params`` returns it
-    (a table side stands there with its own policy code); None unless a side of ``policies`` plays from the table or
-    ``search=dict(judge=True)``."""
+    """The table's arguments of ``gbl_collect_search_tb`` / ``gbl_collect_gumbel_tb`` and, under "ep", the rest of the call as
+    ``_evaluator_params`` returns it (a table side stands there with its own policy code); None unless a side of ``policies`` plays
+    from the table, ``search=dict(judge=True)``, or the table travels inside ``search=dict(gumbel=dict(tablebase=, judge=, ...))``
+    ("inner": the Gumbel rule's entry point)."""
+    from .evaluator_policy import GUMBEL_TABLE_KEYS
     from .tablebase import Tablebase, TablebaseGobbletPolicy
     if policies is None or isinstance(policies, str):
         return None
@@ -268,13 +274,31 @@ def _tablebase_params(policies, search, device):
         return isinstance(x, TablebaseGobbletPolicy) or x == "tablebase" or \
             (isinstance(x, int) and not isinstance(x, bool) and x == nat.POLICY_TABLEBASE)
     tbs = [is_tb(x) for x in sides]
-    judge = bool((search or {}).get("judge", False))
-    if len(sides) != 2 or not (any(tbs) or judge):
-        if (search or {}).get("tablebase") is not None:
+    search = search or {}
+    gd = search.get("gumbel")
+    inner = isinstance(gd, dict) and any(k in gd for k in GUMBEL_TABLE_KEYS)
+    if inner:
+        if len(sides) != 2:
+            raise ValueError("search: gumbel's tablebase / judge belong to a pair of policies")
+        if any(k in search for k in GUMBEL_TABLE_KEYS):
+            raise ValueError("search: with the table inside gumbel=dict(...) (gbl_collect_gumbel_tb), tablebase / tb_mode / tb_count / "
+                             "judge / allow_incomplete go inside that dict, not beside it")
+        if any(_pair(gd.get("solve_depth", 0))):
+            raise ValueError("search: gumbel's solve_depth does not go with tablebase / judge inside the dict (gbl_collect_gumbel_tb has "
+                             "no solver guard)")
+        if any(_pair(search.get("solve_depth", 0))) or any(_pair(search.get("noise", 0.0))):
+            raise ValueError("search: gumbel does not go with solve_depth, noise or cap beside it (gbl_collect_gumbel_tb has none of them)")
+    src = gd if inner else search
+    judge = bool(src.get("judge", False))
+    if len(sides) != 2 or not (any(tbs) or judge or inner):
+        if search.get("tablebase") is not None:
             raise ValueError("search: tablebase= belongs to a pair of policies with a 'tablebase' side, or to judge=True")
         return None
-    rest = {k: v for k, v in (search or {}).items() if k not in ("tablebase", "tb_mode", "tb_count", "judge", "allow_incomplete")}
-    kw = {**dict(tablebase=None, tb_mode="result", tb_count=1, allow_incomplete=False), **{k: v for k, v in (search or {}).items() if k not in rest}}
+    rest = {k: v for k, v in search.items() if k not in GUMBEL_TABLE_KEYS}
+    if inner:  # (the rule's own keys stay for _gumbel_params)
+        rest["gumbel"] = {k: v for k, v in gd.items() if k not in GUMBEL_TABLE_KEYS and k != "solve_depth"}
+    kw = {**dict(tablebase=None, tb_mode="result", tb_count=1, allow_incomplete=False), **{k: v for k, v in src.items() if k in GUMBEL_TABLE_KEYS}}
+    where = "search=dict(gumbel=dict(tablebase=Tablebase ...))" if inner else "search=dict(tablebase=Tablebase ...)"
     tb = kw["tablebase"]
     for x in sides:
         if isinstance(x, TablebaseGobbletPolicy):
@@ -282,7 +306,7 @@ def _tablebase_params(policies, search, device):
                 raise ValueError("one launch reads one table: the policy instance's and search=dict(tablebase=...) differ")
             tb = x.tb
     if not isinstance(tb, Tablebase):
-        raise ValueError("search: a 'tablebase' side (or judge=True) needs search=dict(tablebase=Tablebase ...)")
+        raise ValueError("search: a 'tablebase' side (or judge=True) needs " + where)
     if tb.device != device:
         raise ValueError("the table lives on %s and the environment on %s" % (tb.device, device))
     if not tb.complete and not kw["allow_incomplete"]:
@@ -292,9 +316,11 @@ def _tablebase_params(policies, search, device):
     if not 1 <= int(kw["tb_count"]) <= nat.TB_TARGET_MAX_COUNT:
         raise ValueError("search: tb_count must be in [1, %d]" % nat.TB_TARGET_MAX_COUNT)
     if rest.get("cap") is not None:
-        raise ValueError("search: cap does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no playout cap)")
-    if rest.get("gumbel") is not None:
-        raise ValueError("search: gumbel does not go with a 'tablebase' side or judge=True (gbl_collect_search_tb has no Gumbel rule)")
+        raise ValueError("search: cap does not go with a 'tablebase' side or judge=True (neither gbl_collect_search_tb nor "
+                         "gbl_collect_gumbel_tb has a playout cap)")
+    if rest.get("gumbel") is not None and not inner:
+        raise ValueError("search: gumbel does not go with a 'tablebase' side or judge=True beside it (gbl_collect_search_tb has no Gumbel "
+                         "rule; the table of a Gumbel window travels inside the dict: gumbel=dict(tablebase=..., judge=...))")
     others = ["random" if t else x for t, x in zip(tbs, sides)]
     ep = _evaluator_params(others, rest or None, device)
     if ep is None:  # no evaluator side: the table against itself or against "random"
@@ -306,7 +332,10 @@ def _tablebase_params(policies, search, device):
         if int(rest.get("sample_plies", 0)) < 0:
             raise ValueError("search: sample_plies >= 0")
         ep = dict(policies=[nat.POLICY_RANDOM] * 2, evaluators=[None, None], iterations=[0, 0], explore=16,
-                  sample_plies=int(rest.get("sample_plies", 0)), solve_depth=[0, 0], noise=[0, 0], cap=None)
+                  sample_plies=int(rest.get("sample_plies", 0)), solve_depth=[0, 0], noise=[0, 0], cap=None, gumbel=None)
+    if inner and ep["gumbel"] is None:  # (no side follows the rule: its arguments travel all the same, checked)
+        ep["gumbel"] = _gumbel_params(rest["gumbel"], ep["policies"], keep=True)
+        ep["gumbel"].pop("solve_depth")
     ep["policies"] = [nat.POLICY_TABLEBASE if t else c for t, c in zip(tbs, ep["policies"])]
-    return dict(ep=ep, judge=judge, tb=tb, inventory=tb._inv, aux=tb._aux.data_ptr(), table=tb.table.data_ptr(),
+    return dict(ep=ep, judge=judge, inner=inner, tb=tb, inventory=tb._inv, aux=tb._aux.data_ptr(), table=tb.table.data_ptr(),
                 mode=nat.TB_TARGET_MODES[kw["tb_mode"]], count=int(kw["tb_count"]))

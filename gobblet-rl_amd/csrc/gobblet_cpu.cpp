@@ -1058,7 +1058,7 @@ struct SelfplaySearch {
     int8_t tb_outcome[kActions];
     // gbl_cpu_collect_search_cap: the ply is a fast one -- h holds the small search, whose visits row is not recorded
     bool fast;
-    // gbl_cpu_collect_search_gumbel / gbl_cpu_collect_gumbel_solve: the mover follows the Gumbel root rule -- gb holds its decision and the target row, which is recorded
+    // gbl_cpu_collect_search_gumbel / gbl_cpu_collect_gumbel_solve / gbl_cpu_collect_gumbel_tb: the mover follows the Gumbel root rule -- gb holds its decision and the target row, which is recorded
     // in the visits row's place; nothing is drawn from the visits
     bool gumbel;
     HostGumbel gb;
@@ -1164,9 +1164,10 @@ static void selfplay_boards(int64_t b0, int64_t b1, const SelfplayCall<gbl_evalu
 }
 }  // extern "C++"
 
-// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb, and gbl_collect_gumbel_solve) behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
+// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb, gbl_collect_gumbel_solve and gbl_collect_gumbel_tb) behind the C ABI: the checks both flavours share (selfplay_prologue), the strides, then the boards
 // over the threads.  gbl_cpu_collect_search_eval is the guarded loop with depths and weights 0 and no outcome / proven arrays;
-// gbl_cpu_collect_search_tb is it with the probe in front of every ply that is judged or played from the table.
+// gbl_cpu_collect_search_tb is it with the probe in front of every ply that is judged or played from the table, and
+// gbl_cpu_collect_gumbel_tb that with the Gumbel root rule on a searching side's ply (depths and weights 0).
 static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
 {
     EvalNet nets[2] = {};
@@ -1251,7 +1252,7 @@ static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
     return GBL_OK;
 }
 
-// the eight entry points themselves: one text for both flavours (the host flavour's calls are synchronous: `stream` is not read)
+// the nine entry points themselves: one text for both flavours (the host flavour's calls are synchronous: `stream` is not read)
 #define GBL_SELFPLAY_SYMBOL(fn) gbl_cpu_##fn
 #define GBL_SELFPLAY_RUN(name, call, stream) ((void)(stream), host_selfplay_run(call))
 #include "gobblet_selfplay_entries.inc"

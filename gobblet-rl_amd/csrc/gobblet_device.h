@@ -2699,7 +2699,7 @@ inline const char *collect_solve_error(int illegal_mode, int policy0, int policy
     return nullptr;
 }
 
-// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise, _cap, _gumbel and _tb and of gbl_collect_gumbel_solve, and the checks both flavours make of them ----
+// ---- one self-play call: the arguments of gbl_collect_search, _eval, _solve, _noise, _cap, _gumbel and _tb and of gbl_collect_gumbel_solve and gbl_collect_gumbel_tb, and the checks both flavours make of them ----
 // The 19 trajectory arrays (any may be NULL).
 struct SelfplayTraj {
     int32_t *actions;
@@ -2710,12 +2710,12 @@ struct SelfplayTraj {
     int32_t *root_value;  // (the evaluator search's two: NULL in gbl_collect_search)
     uint8_t *priors;
     int8_t *outcome, *proven;  // (the guard's two: NULL but in gbl_collect_search_solve / _noise / _cap / _tb)
-    int8_t *tb_outcome, *tb_value, *tb_played;  // (the table's verdict of every ply: NULL but in gbl_collect_search_tb)
+    int8_t *tb_outcome, *tb_value, *tb_played;  // (the table's verdict of every ply: NULL but in gbl_collect_search_tb / gbl_collect_gumbel_tb)
 };
 
-enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval and _gumbel; _solve, _noise, _cap and gbl_collect_gumbel_solve; _tb
+enum SelfplayRun { kRunSearch, kRunEval, kRunSolve, kRunTb };  // gbl_collect_search; _eval and _gumbel; _solve, _noise, _cap and gbl_collect_gumbel_solve; _tb and gbl_collect_gumbel_tb
 
-// The union of the eight entry points' arguments; an entry point (gobblet_selfplay_entries.inc, one text for both flavours) fills it,
+// The union of the nine entry points' arguments; an entry point (gobblet_selfplay_entries.inc, one text for both flavours) fills it,
 // leaving 0 / NULL what it does not have, and calls its flavour's one runner.  [0] is player_1's, [1] player_2's.  Ev: gbl_evaluator.
 template <typename Ev>
 struct SelfplayCall {
@@ -2733,7 +2733,7 @@ struct SelfplayCall {
     int max_plies, explore, sample_plies, illegal_mode;
     int64_t *counters;
     int32_t *turn;
-    // gbl_collect_search_tb's own (0 / NULL elsewhere): the table as gbl_tb_probe takes it, gbl_tb_targets' mode and count
+    // gbl_collect_search_tb's and gbl_collect_gumbel_tb's own (0 / NULL elsewhere): the table as gbl_tb_probe takes it, gbl_tb_targets' mode and count
     const int32_t *inventory;
     const void *aux;
     const int8_t *table;
@@ -2741,7 +2741,7 @@ struct SelfplayCall {
     // gbl_collect_search_cap's own (cap = 0 elsewhere: neither array is read)
     int cap;
     int fast[2], share[2];
-    // gbl_collect_search_gumbel's and gbl_collect_gumbel_solve's own (gumbel = 0 elsewhere: none is read)
+    // gbl_collect_search_gumbel's, gbl_collect_gumbel_solve's and gbl_collect_gumbel_tb's own (gumbel = 0 elsewhere: none is read)
     int gumbel;
     int considered[2];
     int gumbel_noise, visit_offset, scale;
@@ -2770,7 +2770,7 @@ inline const char *tb_inventory_error(const int32_t *inventory)
     return nullptr;
 }
 
-// whether a gbl_collect_search_tb call reads the table at all: a side plays from it, or a judge array is given
+// whether a gbl_collect_search_tb / gbl_collect_gumbel_tb call reads the table at all: a side plays from it, or a judge array is given
 template <typename Ev>
 inline bool selfplay_reads_table(const SelfplayCall<Ev> &c)
 {
@@ -2780,7 +2780,8 @@ inline bool selfplay_reads_table(const SelfplayCall<Ev> &c)
 
 // gbl_collect_search_tb, everything that is looked at before a pointer to boards is: the illegal mode, the policies (three here), then
 // collect_solve_error with a TABLEBASE side read as a RANDOM one (its evaluator, budget and depth are not read), then the table's
-// mode and count and, where the call reads the table, the inventory.  (n >= 0)
+// mode and count and, where the call reads the table, the inventory.  gbl_collect_gumbel_tb (c.gumbel; its depths and weights are 0)
+// looks at the mode and the count too only where the call reads the table.  (n >= 0)
 template <typename Ev>
 inline const char *collect_tb_error(const SelfplayCall<Ev> &c)
 {
@@ -2795,14 +2796,15 @@ inline const char *collect_tb_error(const SelfplayCall<Ev> &c)
                                               c.solve_depth[0], c.solve_depth[1], c.explore, c.sample_plies, c.turn != nullptr, c.ply0, c.plies,
                                               c.env_base, c.n))
         return why;
+    if (c.gumbel && !selfplay_reads_table(c)) return nullptr;
     if (c.tb_mode != kTbTargetResult && c.tb_mode != kTbTargetShortest) return "tb_mode must be GBL_TB_TARGET_RESULT or GBL_TB_TARGET_SHORTEST";
     if (c.tb_count < 1 || c.tb_count > kTbTargetMaxCount) return "tb_count must be in [1, 600]";
     return selfplay_reads_table(c) ? tb_inventory_error(c.inventory) : nullptr;
 }
 
 // Everything both flavours look at, in the order they report it: n < 0, the entry point's *_error, the searching sides' noise
-// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) (gbl_collect_search_gumbel, gbl_collect_gumbel_solve: their `considered`, then the
-// rule's three where a side follows it,) n == 0, the three board arrays, (gbl_collect_search_tb, where the call reads the table: aux, then table,) plies == 0, then
+// weights, (gbl_collect_search_cap: their shares, then their fast budgets,) (gbl_collect_search_gumbel, gbl_collect_gumbel_solve, gbl_collect_gumbel_tb: their `considered`, then the
+// rule's three where a side follows it,) n == 0, the three board arrays, (gbl_collect_search_tb, gbl_collect_gumbel_tb, where the call reads the table: aux, then table,) plies == 0, then
 // per searching side `side(m)` -- the flavour's own look at evaluator m
 // (its pointers; on the device their alignment too), which returns 0 or what its fail() returned.  Returns a flavour's error
 // code (< 0; fail(message) makes a GBL_ERR_ARG of a message), 0 where there is nothing to do (GBL_OK), or 1: the flavour goes on
@@ -2831,7 +2833,7 @@ inline int selfplay_prologue(const SelfplayCall<Ev> &c, int &most, Fail &&fail, 
             if (c.policy[m] == searching && c.share[m] < kCapFullShare)
                 if (const char *bad = cap_fast_error(c.fast[m], c.iterations[m])) return fail(bad);
     }
-    if (c.gumbel) {  // gbl_collect_search_gumbel, gbl_collect_gumbel_solve: the searching sides' considered, then the rule's three where a side follows it
+    if (c.gumbel) {  // gbl_collect_search_gumbel, gbl_collect_gumbel_solve, gbl_collect_gumbel_tb: the searching sides' considered, then the rule's three where a side follows it
         for (int m = 0; m < 2; ++m)
             if (c.policy[m] == searching)
                 if (const char *bad = gumbel_error(c.considered[m], 0, 0, 0, 0)) return fail(bad);

@@ -3874,6 +3874,52 @@ struct TbPlay {
     int8_t *outcome, *value, *played;
 };
 
+// The table's part of a self-play ply, for k_collect_tb and k_collect_gumbel_tb (every lane of the board's wavefront calls it): where
+// the ply is judged or its mover plays from the table, the verdict -- k_tb_probe of the live planes, no mask -- into tb_c (this lane's
+// outcome byte) and tb_v; a TABLEBASE mover on a board the table holds is decided here (S.d) and the call returns true: nothing else
+// runs for the ply.
+__device__ __forceinline__ bool wave_tb_ply(const TbPlay &tb, const SearchBoard &B, int who, uint64_t legal, int policy, int sample_plies,
+                                            uint64_t seed, uint64_t g, uint32_t q, uint32_t lane, int &tb_c, int &tb_v, SearchPly &S)
+{
+    if (tb.judge || policy == kPolicyTablebase) {  // (wave-uniform)
+        const TbAux A = tb_aux(tb.aux);
+        uint64_t cand = legal & tb_piece_actions(tb.S);
+        if (tb_board_index(A, tb.S, B.p, who) < 0) cand = 0;
+        const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
+        if (mine) tb_c = (int)(int8_t)tb_probe_action(A, tb.S, tb.table, B.p, who, lane);  // (the outcome byte: see tb_target_keeps)
+        const uint32_t best = wave_max(mine ? tb_action_key(tb_c, lane) : 0u);
+        tb_v = uniform(tb_value_of(best));
+        if (policy == kPolicyTablebase && best) {
+            const bool keep = mine && tb_target_keeps(tb_c, tb_v, tb.mode);
+            const uint64_t kept = (uint64_t)__ballot(keep);
+            const uint32_t sum = (uint32_t)tb.count * (uint32_t)__popcll(kept);
+            S.d = SearchDecision{uniform(tb_action_of(best)), kHowTable, tb_play_value(tb_v, (int)sum), keep ? (uint32_t)tb.count : 0u};
+            if (B.tabs < sample_plies) {
+                const uint32_t run = (uint32_t)tb.count * (uint32_t)__popcll(kept & ((2ull << lane) - 1ull));
+                const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), sum);
+                const uint64_t over = (uint64_t)__ballot(run > k);
+                S.d.action = over ? (int)__builtin_ctzll(over) : -1;
+                S.d.how = kHowTableSampled;
+            }
+            return true;
+        }
+    }
+    return false;
+}
+
+// The three judge arrays' cell of a ply, for the same two kernels: the lane's outcome byte, V, and the byte of the action the ply played
+// (from its lane by a shuffle).
+__device__ __forceinline__ void wave_tb_store(const TbPlay &tb, int64_t at, int tb_c, int tb_v, int action, uint32_t lane)
+{
+    if (tb.outcome && lane < (uint32_t)kActions) __builtin_nontemporal_store((int8_t)tb_c, tb.outcome + at * kActions + lane);
+    if (tb.value && lane == 0) tb.value[at] = (int8_t)tb_v;
+    if (tb.played) {
+        const int a = uniform(action);  // (the action the ply played: search_plies steps with the same)
+        const int c = __shfl(tb_c, a < 0 ? 0 : a);
+        if (lane == 0) tb.played[at] = (int8_t)(a < 0 ? kSolveNone : c);
+    }
+}
+
 template <bool NOISE, bool SEARCH>
 __global__ __launch_bounds__(64) void k_collect_tb(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                    uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
@@ -3902,29 +3948,7 @@ __global__ __launch_bounds__(64) void k_collect_tb(int8_t *__restrict__ state, i
             tb_c = kSolveNone;
             tb_v = 0;
             const int policy = who ? policy1 : policy0;
-            if (tb.judge || policy == kPolicyTablebase) {  // (wave-uniform) the verdict: k_tb_probe of the live planes, no mask
-                const TbAux A = tb_aux(tb.aux);
-                uint64_t cand = legal & tb_piece_actions(tb.S);
-                if (tb_board_index(A, tb.S, B.p, who) < 0) cand = 0;
-                const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
-                if (mine) tb_c = (int)(int8_t)tb_probe_action(A, tb.S, tb.table, B.p, who, lane);  // (the outcome byte: see tb_target_keeps)
-                const uint32_t best = wave_max(mine ? tb_action_key(tb_c, lane) : 0u);
-                tb_v = uniform(tb_value_of(best));
-                if (policy == kPolicyTablebase && best) {
-                    const bool keep = mine && tb_target_keeps(tb_c, tb_v, tb.mode);
-                    const uint64_t kept = (uint64_t)__ballot(keep);
-                    const uint32_t sum = (uint32_t)tb.count * (uint32_t)__popcll(kept);
-                    S.d = SearchDecision{uniform(tb_action_of(best)), kHowTable, tb_play_value(tb_v, (int)sum), keep ? (uint32_t)tb.count : 0u};
-                    if (B.tabs < sample_plies) {
-                        const uint32_t run = (uint32_t)tb.count * (uint32_t)__popcll(kept & ((2ull << lane) - 1ull));
-                        const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), sum);
-                        const uint64_t over = (uint64_t)__ballot(run > k);
-                        S.d.action = over ? (int)__builtin_ctzll(over) : -1;
-                        S.d.how = kHowTableSampled;
-                    }
-                    return true;
-                }
-            }
+            if (wave_tb_ply(tb, B, who, legal, policy, sample_plies, seed, g, q, lane, tb_c, tb_v, S)) return true;
             if (!SEARCH || policy != kPolicyEvalTree) return false;
             if constexpr (SEARCH) {
                 const uint32_t its = who ? iterations1 : iterations0;
@@ -3957,13 +3981,65 @@ __global__ __launch_bounds__(64) void k_collect_tb(int8_t *__restrict__ state, i
             if (priors_traj && act) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
             if (outcome_traj && act) __builtin_nontemporal_store((int8_t)my_c, outcome_traj + at * kActions + lane);
             if (proven_traj && lane == 0) proven_traj[at] = (int8_t)proven;
-            if (tb.outcome && act) __builtin_nontemporal_store((int8_t)tb_c, tb.outcome + at * kActions + lane);
-            if (tb.value && lane == 0) tb.value[at] = (int8_t)tb_v;
-            if (tb.played) {
-                const int a = uniform(S.d.action);  // (the action the ply played: search_plies steps with the same)
-                const int c = __shfl(tb_c, a < 0 ? 0 : a);
-                if (lane == 0) tb.played[at] = (int8_t)(a < 0 ? kSolveNone : c);
+            wave_tb_store(tb, at, tb_c, tb_v, S.d.action, lane);
+        });
+}
+
+// gbl_collect_gumbel_tb: k_collect_eval<true>'s ply with k_collect_tb's probe in front of it and the judge's stores behind it -- the
+// kernel of a call that has a Gumbel side and reads the table (selfplay_launch runs k_collect_eval<true> for a call that does not read
+// it and k_collect_tb for one without a Gumbel side, so neither carries the other's code).  A TABLEBASE mover's ply and the verdict
+// are wave_tb_ply's, exactly as in k_collect_tb; an EVAL_TREE mover's ply is tree_eval_iterations<false, true> over the legal mask and,
+// for a side with considered_m > 0, wave_gumbel_finish on the root's read-out -- ply q's search IS gbl_tree_search_gumbel(call = q); a
+// side with considered_m == 0 decides by search_decide, sample_plies honoured.  The probe's registers are dead before the tree's come
+// alive: only the lane's outcome byte and V live across the search.  No solver and no noise: neither has LDS or registers here.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_collect_gumbel_tb(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                          uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
+                                                          uint32_t plies, int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride,
+                                                          SearchTraj T, int32_t *__restrict__ root_value_traj,
+                                                          uint8_t *__restrict__ priors_traj, const EvalNet net0, const EvalNet net1,
+                                                          int policy0, int policy1, uint32_t iterations0, uint32_t iterations1, uint32_t most,
+                                                          uint32_t explore, int sample_plies, int illegal_mode,
+                                                          int64_t *__restrict__ counters, int32_t *__restrict__ turn, const GumbelArgs gum,
+                                                          uint32_t considered0, uint32_t considered1, const TbPlay tb)
+{
+    extern __shared__ uint4 s_tree[];
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    const uint32_t lane = threadIdx.x;
+    int tb_c = kSolveNone, tb_v = 0;  // the table's outcome byte of this lane and V, from the first lambda to the second
+    search_plies(
+        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            tb_c = kSolveNone;
+            tb_v = 0;
+            const int policy = who ? policy1 : policy0;
+            if (wave_tb_ply(tb, B, who, legal, policy, sample_plies, seed, g, q, lane, tb_c, tb_v, S)) return true;
+            if (policy != kPolicyEvalTree) return false;
+            uint32_t mixed;  // (no noise here: the network's byte)
+            WaveGumbel gb{GumbelArgs{who ? considered1 : considered0, gum.noise, gum.visit_offset, gum.scale}, seed, g, q, 0, 0, 0ull};
+            const WaveEval at_root = tree_eval_iterations<false, true>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
+                                                                       who ? iterations1 : iterations0, explore, lane, S.count, RootNoise{},
+                                                                       mixed, &gb);
+            S.pi = at_root.pi;
+            S.root_q = at_root.q;
+            const bool rule = gb.G.considered != 0u;  // (wave-uniform) a Gumbel side's ply
+            S.d = search_decide(nodes, lane, !rule && B.tabs < sample_plies, seed, g, q);
+            if (rule) {
+                GumbelOut out{-1, 0u};
+                if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), legal, at_root.q, lane);
+                S.d.action = out.action;
+                S.d.how = kHowGumbel;
+                S.d.my_n = out.target;
             }
+            wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            return true;
+        },
+        [&](int64_t at, const SearchPly &S) {
+            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
+            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
+            wave_tb_store(tb, at, tb_c, tb_v, S.d.action, lane);
         });
 }
 
@@ -5479,7 +5555,7 @@ int gbl_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int
     GBL_LAUNCHED("gbl_tree_search_gumbel");
 }
 
-// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb, and gbl_collect_gumbel_solve) between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
+// The self-play entry points (gbl_collect_search and its _eval, _solve, _noise, _cap, _gumbel and _tb, gbl_collect_gumbel_solve and gbl_collect_gumbel_tb) between the C ABI and the launch: the checks both flavours share (selfplay_prologue), the
 // evaluators as the kernels take them, the trajectory's strides and alignments, the grid, the tree's LDS and the entry's own kernel.
 static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &c, void *stream)
 {
@@ -5510,7 +5586,21 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     const bool guarded = (c.policy[0] == GBL_POLICY_EVAL_TREE && c.solve_depth[0] > 0) || (c.policy[1] == GBL_POLICY_EVAL_TREE && c.solve_depth[1] > 0);
     const bool rule_side = selfplay_considered(c, 0) || selfplay_considered(c, 1);
     const bool rule_unguarded = c.run == kRunSolve && rule_side && !guarded && !t.outcome && !t.proven;
-    if (c.run == kRunSolve && rule_side && !rule_unguarded) {
+    // gbl_collect_gumbel_tb likewise: a call with a Gumbel side that reads the table runs its own kernel; one that does not read it (no
+    // TABLEBASE side, no judge array) is gbl_collect_search_gumbel's launch, and one without a Gumbel side gbl_collect_search_tb's below
+    // (depths and weights 0) -- with no EVAL_TREE side at all its search-free instantiation
+    const bool rule_table = c.run == kRunTb && rule_side && reads_table;
+    const bool rule_untabled = c.run == kRunTb && rule_side && !reads_table;
+    // (a call that never reads the table passes an empty one: no ply probes)
+    const TbPlay tb{static_cast<const uint8_t *>(c.aux), c.table, reads_table ? tb_shape(c.inventory) : TbShape{}, c.tb_mode, c.tb_count,
+                    (t.tb_outcome || t.tb_value || t.tb_played) ? 1 : 0, t.tb_outcome, t.tb_value, t.tb_played};
+    if (rule_table) {
+        const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
+        hipLaunchKernelGGL(k_collect_gumbel_tb, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
+                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1], its0,
+                           its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn, gum,
+                           (uint32_t)selfplay_considered(c, 0), (uint32_t)selfplay_considered(c, 1), tb);
+    } else if (c.run == kRunSolve && rule_side && !rule_unguarded) {
         const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
         hipLaunchKernelGGL(k_collect_gumbel_solve, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
                            c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1], c.policy[0],
@@ -5529,7 +5619,7 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
         default: GBL_CS(1); break;
         }
 #undef GBL_CS
-    } else if (c.run == kRunEval || rule_unguarded) {
+    } else if (c.run == kRunEval || rule_unguarded || rule_untabled) {
         const uint32_t m0 = (uint32_t)selfplay_considered(c, 0), m1 = (uint32_t)selfplay_considered(c, 1);
         const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
         // (k_collect_eval<false> is the kernel without the rule's code: gbl_collect_search_eval, and gbl_collect_search_gumbel with no Gumbel side)
@@ -5545,9 +5635,6 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     } else if (c.run == kRunTb) {
         const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
                        w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
-        // (a call that never reads the table passes an empty one: no ply probes)
-        const TbPlay tb{static_cast<const uint8_t *>(c.aux), c.table, reads_table ? tb_shape(c.inventory) : TbShape{}, c.tb_mode, c.tb_count,
-                        (t.tb_outcome || t.tb_value || t.tb_played) ? 1 : 0, t.tb_outcome, t.tb_value, t.tb_played};
 #define GBL_CTB(NOISE, SEARCH)                                                                                                            \
     hipLaunchKernelGGL((k_collect_tb<NOISE, SEARCH>), grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,          \
                        c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1],       \
@@ -5585,7 +5672,7 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     GBL_LAUNCHED(name);
 }
 
-// the eight entry points themselves: one text for both flavours
+// the nine entry points themselves: one text for both flavours
 #define GBL_SELFPLAY_SYMBOL(fn) gbl_##fn
 #define GBL_SELFPLAY_RUN(name, call, stream) selfplay_launch(name, call, stream)
 #include "gobblet_selfplay_entries.inc"

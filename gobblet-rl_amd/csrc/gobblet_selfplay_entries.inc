@@ -1,5 +1,5 @@
-// gobblet_selfplay_entries.inc -- the eight self-play entry points of the C ABI (gbl_collect_search and its _eval, _solve, _noise,
-// _cap, _gumbel and _tb, and gbl_collect_gumbel_solve; include/gobblet_hip.h, include/gobblet_cpu.h), written once for both flavours.  gobblet_hip.hip and
+// gobblet_selfplay_entries.inc -- the nine self-play entry points of the C ABI (gbl_collect_search and its _eval, _solve, _noise,
+// _cap, _gumbel and _tb, gbl_collect_gumbel_solve and gbl_collect_gumbel_tb; include/gobblet_hip.h, include/gobblet_cpu.h), written once for both flavours.  gobblet_hip.hip and
 // gobblet_cpu.cpp include it inside their extern "C" block, after their runner, with
 //   GBL_SELFPLAY_SYMBOL(fn)              the flavour's symbol: gbl_##fn / gbl_cpu_##fn
 //   GBL_SELFPLAY_RUN(name, call, stream)  the flavour's runner on a filled SelfplayCall<gbl_evaluator>, under the entry point's name
@@ -207,4 +207,31 @@ int GBL_SELFPLAY_SYMBOL(collect_search_tb)(int8_t *state, int8_t *to_move, int8_
     c.inventory = inventory, c.aux = aux, c.table = table;
     c.tb_mode = tb_mode, c.tb_count = tb_count;
     return GBL_SELFPLAY_RUN("gbl_collect_search_tb", c, stream);
+}
+
+int GBL_SELFPLAY_SYMBOL(collect_gumbel_tb)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+                                           int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
+                                           int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj,
+                                           int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride,
+                                           int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev,
+                                           uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0, const gbl_evaluator *ev1,
+                                           int iterations0, int iterations1, int explore, int sample_plies, int illegal_mode,
+                                           int64_t *counters, int32_t *turn, int considered0, int considered1, int gumbel_noise,
+                                           int visit_offset, int scale, const int32_t *inventory, const void *aux, const int8_t *table,
+                                           int tb_mode, int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj,
+                                           void *stream)
+{
+    SelfplayCall<gbl_evaluator> c = selfplay_common(
+        kRunTb, state, to_move, done,
+        {actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj, obs_traj, visits_traj, value_traj, nodes_traj, how_traj,
+         mover_traj, root_value_traj, priors_traj, nullptr, nullptr, tb_outcome_traj, tb_value_traj, tb_played_traj},
+        n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, policy0, policy1, iterations0, iterations1, explore, sample_plies,
+        illegal_mode, counters, turn);
+    c.ev[0] = ev0, c.ev[1] = ev1;
+    c.gumbel = 1;
+    c.considered[0] = considered0, c.considered[1] = considered1;
+    c.gumbel_noise = gumbel_noise, c.visit_offset = visit_offset, c.scale = scale;
+    c.inventory = inventory, c.aux = aux, c.table = table;
+    c.tb_mode = tb_mode, c.tb_count = tb_count;
+    return GBL_SELFPLAY_RUN("gbl_collect_gumbel_tb", c, stream);
 }

@@ -370,6 +370,7 @@ def cap_full(seed: int, board_ids, ply_indices, full) -> torch.Tensor:
 
 # ---- the Gumbel root rule's arguments and its noise restated in torch (include/gobblet_hip.h, "Gumbel root search") ------------------
 GUMBEL_DEFAULTS = dict(considered=16, noise=True, visit_offset=50, scale=23)
+GUMBEL_TABLE_KEYS = ("tablebase", "tb_mode", "tb_count", "judge", "allow_incomplete")  # collect()'s gumbel dict alone: the table inside it
 # GT[k] = round(-ln(-ln((k + 1/2) / 256)) * 16 / ln 2): a standard Gumbel variate in 1/16 of an octave (csrc/gobblet_knobs.h holds the numbers)
 GUMBEL_TABLE = tuple(int(x) for x in np.rint(-np.log(-np.log((np.arange(256) + 0.5) / 256.0)) * 16.0 / math.log(2.0)))
 
@@ -380,6 +381,9 @@ def gumbel_args(gumbel: dict) -> dict:
     if isinstance(gumbel, dict) and "solve_depth" in gumbel:  # (collect()'s gumbel dict alone has the key: gbl_collect_gumbel_solve)
         raise ValueError("gumbel: solve_depth belongs to collect(search=dict(gumbel=...)); a single decision is guarded by "
                          "SolverGobbletPolicy(depth, fallback=this policy)")
+    if isinstance(gumbel, dict) and set(gumbel) & set(GUMBEL_TABLE_KEYS):  # (likewise: gbl_collect_gumbel_tb)
+        raise ValueError("gumbel: tablebase / tb_mode / tb_count / judge / allow_incomplete belong to collect(search=dict(gumbel=...)); "
+                         "a single decision plays from the table through TablebaseGobbletPolicy(tb, fallback=this policy)")
     if not isinstance(gumbel, dict) or set(gumbel) - set(GUMBEL_DEFAULTS):
         raise ValueError("gumbel is a dict of considered / noise / visit_offset / scale")
     kw = {**GUMBEL_DEFAULTS, **gumbel}

@@ -470,13 +470,21 @@ class BatchedGobblet:
         budget spent on them by sequential halving, and the completed-Q improved policy as the target -- "visits" holds that row (1 ..
         255 on the candidates), so EVERY ply of such a side is a policy target for ``training_batch`` / ``ReplayBuffer.append``.
         "how" is ``nat.HOW_GUMBEL``; ``sample_plies`` is not read for such a side (the noise is its exploration); ``gumbel_row``
-        recomputes the noise.  Not with ``solve_depth``, ``noise`` or ``cap`` beside it, a "tablebase" side or ``judge=True``.
+        recomputes the noise.  Not with ``solve_depth``, ``noise`` or ``cap`` beside it, nor with ``tablebase=`` / ``judge=True`` beside it
+        (the table of such a window travels inside the dict, below).
 
         ``gumbel=dict(..., solve_depth=d)`` (an int, or a pair, one per side; 0 or absent: none) is the solver's guard of such a
         window, still one launch (``gbl_collect_gumbel_solve``): a root the solver proves plays the solver's action (``nat.HOW_PROVEN``,
         a one-hot row, no noise drawn), every other root runs the Gumbel search over its unproven actions only, and the buffers also
         receive "outcomes" / "proven" as under ``solve_depth`` above.  A guarded side with ``considered=0`` searches as under
         ``solve_depth`` above.  Kept rows are the cells with "how" 5 or 10.
+
+        ``gumbel=dict(..., tablebase=tb, tb_mode="result" | "shortest", tb_count=1, judge=False, allow_incomplete=False)`` brings the
+        exact table into such a window, still one launch (``gbl_collect_gumbel_tb``): a side "tablebase" then plays from that table
+        and ``judge=True`` writes the table's verdict of every ply -- a Gumbel ply included -- exactly as described for
+        ``gbl_collect_search_tb`` below ("tb_outcomes" / "tb_value" / "tb_played"; ``Tablebase.judge`` and the regret-driven replay
+        priorities take the trajectory unchanged).  Not with ``solve_depth`` inside the dict.  Kept rows are the cells with "how" 6, 7
+        or 10.
 
         A side "tablebase" (or a ``TablebaseGobbletPolicy`` instance, which supplies its table) plays from the exact table INSIDE the
         launch (``gbl_collect_search_tb``), against "tablebase", "evaluator" or "random": ``search=dict(..., tablebase=tb,

@@ -179,6 +179,15 @@ int gbl_cpu_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int3
                               int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
                               int64_t *counters, int32_t *turn, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode,
                               int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *stream);
+int gbl_cpu_collect_gumbel_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                              int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                              int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                              uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base,
+                              uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                              const gbl_evaluator *ev1, int iterations0, int iterations1, int explore, int sample_plies, int illegal_mode,
+                              int64_t *counters, int32_t *turn, int considered0, int considered1, int gumbel_noise, int visit_offset,
+                              int scale, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode, int tb_count,
+                              int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *stream);
 int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
                             int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies,
                             void *stream);

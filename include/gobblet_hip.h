@@ -747,8 +747,8 @@ int gbl_collect_search_cap(int8_t *state, int8_t *to_move, int8_t *done, int32_t
  * The Gumbel row moves with *ply_dev as every other draw of the window does; a consumer recomputes it from (seed, g, q).  Errors are
  * gbl_collect_search_eval's in its order; after them (before the n == 0 return) GBL_ERR_ARG for a considered outside 0 .. 54 on an
  * EVAL_TREE side, then, where a side follows the rule, for gumbel_noise, visit_offset, scale out of range.  The solver guard goes
- * with the rule in gbl_collect_gumbel_solve, below; root noise, the playout cap and the tablebase are not combined with it.  Allocates
- * nothing; the LDS is gbl_collect_search_eval's. */
+ * with the rule in gbl_collect_gumbel_solve, below, and the tablebase in gbl_collect_gumbel_tb; root noise and the playout cap are not
+ * combined with it.  Allocates nothing; the LDS is gbl_collect_search_eval's. */
 #define GBL_HOW_GUMBEL 10
 int gbl_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
@@ -785,8 +785,8 @@ int gbl_collect_search_gumbel(int8_t *state, int8_t *to_move, int8_t *done, int3
  * gbl_collect_search_solve's, bit for bit.  A board's window depends on (seed, g, the ply indices) alone.  Errors are
  * gbl_collect_search_solve's in its order (a depth outside 0 .. GBL_SOLVE_MAX_DEPTH on an EVAL_TREE side among them); after them,
  * before the n == 0 return, GBL_ERR_ARG for a considered outside 0 .. 54 on an EVAL_TREE side, then, where a side follows the rule,
- * for gumbel_noise, visit_offset, scale out of range; then the pointers.  Root noise, the playout cap and the tablebase are not
- * combined with the rule.  gbl_outcome_targets, gbl_training_batch and gbl_replay_append work on these trajectories unchanged.
+ * for gumbel_noise, visit_offset, scale out of range; then the pointers.  Root noise and the playout cap are not combined with
+ * the rule; the tablebase is in gbl_collect_gumbel_tb, without the guard.  gbl_outcome_targets, gbl_training_batch and gbl_replay_append work on these trajectories unchanged.
  * Allocates nothing; the LDS is gbl_collect_search_solve's: the tree and the solver's 872 bytes. */
 int gbl_collect_gumbel_solve(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                              int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
@@ -1309,6 +1309,46 @@ int gbl_collect_search_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t 
                           int solve_depth0, int solve_depth1, int noise0, int noise1, int explore, int sample_plies, int illegal_mode,
                           int64_t *counters, int32_t *turn, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode,
                           int tb_count, int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *stream);
+
+/* Gumbel self-play with the tablebase (no counterpart in the reference): gbl_collect_search_gumbel with the exact table inside the
+ * launch, as a third policy for either side and as a judge of every ply.  The arguments are gbl_collect_search_gumbel's up to and
+ * including scale, then gbl_collect_search_tb's table block in its order: inventory / aux / table, tb_mode / tb_count, and the judge
+ * arrays tb_outcome_traj / tb_value_traj / tb_played_traj (each may be NULL, none needs an alignment).  There is no solver depth, no
+ * root noise and no playout cap.  A side's policy is GBL_POLICY_RANDOM, GBL_POLICY_EVAL_TREE or GBL_POLICY_TABLEBASE.  The rule is
+ * gbl_collect_search_gumbel's text with gbl_collect_search_tb's two additions, word for word:
+ *   The verdict of a ply.  Where a judge array is given or the ply's mover is TABLEBASE: gbl_tb_probe(mask = NULL) of the position
+ *     before the move, as its mover sees it; the three judge arrays are written exactly as gbl_collect_search_tb writes them -- the
+ *     GBL_SOLVE_NONE rows of a board outside the inventory or without a candidate included, and tb_played = outcome[action] of whatever
+ *     the ply played, so a Gumbel ply is judged like any other.
+ *   A TABLEBASE mover.  a* >= 0: gbl_collect_search_tb's ply to the byte -- the visits row holds tb_count on O, how = GBL_HOW_TABLE or,
+ *     while turn[b] < sample_plies, GBL_HOW_TABLE_SAMPLED with the stream-4 draw; nodes = 0, root_value = 0, the prior row zeros.
+ *     a* == -1: a RANDOM side's ply.  Its considered, iterations and evaluator are not read.
+ * An EVAL_TREE mover with considered_m > 0 plays gbl_collect_search_gumbel's ply (how = GBL_HOW_GUMBEL, the target row in visits_traj,
+ * sample_plies not read); one with considered_m == 0 plays gbl_collect_search_eval's ply, the visit-proportional draw while
+ * turn[b] < sample_plies, as in both parents.
+ * Two identities hold bit for bit.  With no TABLEBASE side and the three judge arrays NULL every array is gbl_collect_search_gumbel's,
+ * and inventory / aux / table may be NULL (tb_mode and tb_count are then not read either).  With both considered 0 every shared array
+ * is gbl_collect_search_tb's at depths (0, 0) and noise (0, 0).
+ * Errors, all GBL_ERR_ARG, in this order: n < 0; illegal_mode; a policy outside the three; per EVAL_TREE side, player_1 first, its
+ * evaluator (NULL, hidden, shifts) and then its iterations / explore; the window (sample_plies < 0, sample_plies > 0 without turn,
+ * ply0 + plies > 2^24, env_base + n); then -- only where a side is TABLEBASE or a judge array is given -- tb_mode, tb_count, the
+ * inventory (NULL, an entry outside 0 .. 2); a considered outside 0 .. 54 on an EVAL_TREE side; where a side follows the rule,
+ * gumbel_noise, visit_offset, scale out of range; n == 0 returns GBL_OK here; state, to_move, done NULL; where the call reads the
+ * table a missing aux, then a missing table; plies == 0 returns GBL_OK here; an EVAL_TREE side's weight pointers; the strides.  The
+ * device flavour then has its alignment rules (GBL_ERR_ALIGN): gbl_collect_search_gumbel's, among them, after the trajectory's, aux
+ * 16-byte aligned where the call reads the table.  A RANDOM or TABLEBASE side's considered, iterations and evaluator are never
+ * looked at.  Nothing about the table's completeness is checked.  Every offset into the table is 64-bit.  gbl_outcome_targets,
+ * gbl_training_batch and gbl_replay_append work on these trajectories unchanged.  Allocates nothing; the LDS is
+ * gbl_collect_search_eval's.  The solver guard is not combined with the table here. */
+int gbl_collect_gumbel_tb(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
+                          int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int16_t *visits_traj,
+                          int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj,
+                          uint8_t *priors_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base,
+                          uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, const gbl_evaluator *ev0,
+                          const gbl_evaluator *ev1, int iterations0, int iterations1, int explore, int sample_plies, int illegal_mode,
+                          int64_t *counters, int32_t *turn, int considered0, int considered1, int gumbel_noise, int visit_offset,
+                          int scale, const int32_t *inventory, const void *aux, const int8_t *table, int tb_mode, int tb_count,
+                          int8_t *tb_outcome_traj, int8_t *tb_value_traj, int8_t *tb_played_traj, void *stream);
 
 /* Which kernel a gbl_collect call of this shape runs (no launch; >= 0, or GBL_ERR_ARG): benchmarks and profiles label
  * their records with it instead of re-deriving the library's dispatch rule.
