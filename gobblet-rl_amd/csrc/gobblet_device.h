@@ -2633,7 +2633,7 @@ inline const char *env_range_error(uint64_t env_base, int64_t n)  // (n >= 0)
     return env_base > (1ull << 42) || (uint64_t)n > (1ull << 42) - env_base ? "env_base + n must not exceed 2^42" : nullptr;
 }
 
-// what the two self-play entry points (gbl_collect_search, gbl_collect_search_eval) ask of the window: after the policies' own checks
+// what the nine self-play entry points ask of the window: after the policies' own checks
 inline const char *selfplay_window_error(int sample_plies, bool has_turn, uint32_t ply0, uint32_t plies, uint64_t env_base, int64_t n)
 {
     if (sample_plies < 0) return "sample_plies < 0";

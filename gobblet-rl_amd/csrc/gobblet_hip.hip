@@ -2035,6 +2035,14 @@ __device__ __forceinline__ GumbelOut wave_gumbel_finish(const WaveGumbel &gb, co
     return GumbelOut{gumbel_action_of(key), in ? eval_prior(e, sum) : 0u};
 }
 
+// ... and the read-out of a finished search: action -1 and a zero row where the rule did not run (gb.A == 0: a root without candidates)
+__device__ __forceinline__ GumbelOut wave_gumbel_out(const WaveGumbel &gb, const TreeNode *nodes, uint64_t cand, int32_t q_root, uint32_t lane)
+{
+    GumbelOut out{-1, 0u};
+    if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), cand, q_root, lane);
+    return out;
+}
+
 template <bool NOISE, bool GUMBEL = false>
 __device__ __forceinline__ WaveEval tree_eval_iterations(TreeNode *const nodes, uint8_t *const pri, uint32_t *const s_h, const EvalNet &net,
                                                          const Planes &root, const int mover, const uint64_t cand, const uint32_t iterations,
@@ -2168,8 +2176,7 @@ __global__ __launch_bounds__(64) void k_tree_eval(const int8_t *__restrict__ sta
         const uint64_t key = tree_root_out(nodes, lane, b, visits_out, wins_out, losses_out);
         int action = GUMBEL ? -1 : tree_action_of(key);
         if constexpr (GUMBEL) {
-            GumbelOut out{-1, 0u};
-            if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), cand, at_root.q, lane);
+            const GumbelOut out = wave_gumbel_out(gb, nodes, cand, at_root.q, lane);
             action = out.action;
             if (lane < (uint32_t)kActions) {
                 if (gum.target) gum.target[b * kActions + lane] = (uint8_t)out.target;
@@ -2208,7 +2215,7 @@ struct SearchTraj {
     int8_t *how, *mover;
 };
 
-// What the two self-play kernels (k_collect_search, k_collect_eval) do between a search and the next one; wavefront 0's lanes call
+// What the self-play kernels (k_collect_search and the evaluator family of five) do between a search and the next one; wavefront 0's lanes call
 // search_decide and store_search_ply, every thread of the board's workgroup the other two.
 //
 // decide: lane a reads the root's child of action a; butterflies give the decision's key and the value sum; `sampled` (a game's
@@ -2327,7 +2334,7 @@ struct SearchPly {
     int root_q;
 };
 
-// The boards and plies of a self-play launch, for k_collect_search and k_collect_eval (every thread of the workgroup calls it; the
+// The boards and plies of a self-play launch, for k_collect_search and the evaluator family (every thread of the workgroup calls it; the
 // host flavour's selfplay_boards is the same loop).  search(B, who, legal, g, q, S): the mover's search of call q on board B -- false
 // where the masked-random sampler moves, else it fills S (the decision by search_decide) and returns after whatever keeps the next
 // search's writes to the tree behind this one's reads.  stored(at, S): wavefront 0, after the ply's cell `at` is written -- a
@@ -2396,67 +2403,11 @@ __global__ __launch_bounds__(64 * W) void k_collect_search(int8_t *__restrict__ 
         [](int64_t, const SearchPly &) {});
 }
 
-// gbl_collect_search_eval: k_collect_search with the evaluator-guided search: one wavefront per board (a grid-stride loop over
-// boards), the ply loop inside (search_plies), the tree rebuilt from an empty root on every ply -- ply q's search IS
-// gbl_tree_search_eval of the position, because both kernels run tree_eval_iterations.  Dynamic LDS: (most + 1) nodes, then (most + 1)
-// prior rows, most = the larger budget of the sides that search; beside it s_h and the two row images.  One wavefront: no workgroup
-// barrier anywhere, wave_lds_fence instead.  The mover picks its network and budget wave-uniformly (field by field: the two structs
-// stay in SGPRs).  The root's q and its prior row -- a byte in every lane -- go out beside the ply's cell, from this kernel's own
-// second lambda.
+// the mover's network, picked wave-uniformly field by field: the two structs stay in SGPRs
 __device__ __forceinline__ EvalNet eval_net_pick(const EvalNet &a, const EvalNet &b, int second)
 {
     return EvalNet{second ? b.w1 : a.w1, second ? b.b1 : a.b1, second ? b.w2 : a.w2, second ? b.b2 : a.b2, second ? b.hidden : a.hidden,
                    second ? b.shift1 : a.shift1, second ? b.shift_p : a.shift_p, second ? b.shift_v : a.shift_v};
-}
-
-// GUMBEL: gbl_collect_search_gumbel -- a side with considered_m > 0 searches by the Gumbel root rule with call = the ply index: its
-// action is the rule's decision (never the visit-proportional draw), how = GBL_HOW_GUMBEL and the visits row holds the target bytes.
-// gum.G's considered is not read: the two sides' own travel beside it.
-template <bool GUMBEL>
-__global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
-                                                     uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
-                                                     int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
-                                                     int32_t *__restrict__ root_value_traj, uint8_t *__restrict__ priors_traj,
-                                                     const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
-                                                     uint32_t iterations1, uint32_t most, uint32_t explore, int sample_plies, int illegal_mode,
-                                                     int64_t *__restrict__ counters, int32_t *__restrict__ turn, const GumbelArgs gum,
-                                                     uint32_t considered0, uint32_t considered1)
-{
-    extern __shared__ uint4 s_tree[];
-    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
-    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
-    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
-    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
-    const uint32_t lane = threadIdx.x;
-    search_plies(
-        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
-        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
-            if ((who ? policy1 : policy0) != kPolicyEvalTree) return false;
-            uint32_t mixed;  // (no noise here: the network's byte)
-            WaveGumbel gb{GumbelArgs{who ? considered1 : considered0, gum.noise, gum.visit_offset, gum.scale}, seed, g, q, 0, 0, 0ull};
-            const WaveEval at_root = tree_eval_iterations<false, GUMBEL>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
-                                                                         who ? iterations1 : iterations0, explore, lane, S.count, RootNoise{},
-                                                                         mixed, &gb);
-            S.pi = at_root.pi;
-            S.root_q = at_root.q;
-            const bool rule = GUMBEL && gb.G.considered != 0u;  // (wave-uniform) a Gumbel side's ply
-            S.d = search_decide(nodes, lane, !rule && B.tabs < sample_plies, seed, g, q);
-            if constexpr (GUMBEL) {
-                if (rule) {
-                    GumbelOut out{-1, 0u};
-                    if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), legal, at_root.q, lane);
-                    S.d.action = out.action;
-                    S.d.how = kHowGumbel;
-                    S.d.my_n = out.target;
-                }
-            }
-            wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
-            return true;
-        },
-        [&](int64_t at, const SearchPly &S) {
-            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
-            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
-        });
 }
 
 // gbl_outcome_targets: one reverse pass over the plies per board, a lane per board and a wavefront per tile of 64 boards -- in both
@@ -3274,8 +3225,7 @@ __global__ __launch_bounds__(64) void k_reanalyse(const std::conditional_t<GUMBE
                 WaveGumbel gb{a.G, a.seed, a.env_base + (uint64_t)r, a.call, 0, 0, 0ull};
                 at_root = tree_eval_iterations<false, true>(nodes, pri, s_h, a.net, root, mover, cand, a.iterations, a.explore, lane, count,
                                                             RootNoise{}, mixed, &gb);
-                GumbelOut out{-1, 0u};
-                if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), cand, at_root.q, lane);
+                const GumbelOut out = wave_gumbel_out(gb, nodes, cand, at_root.q, lane);
                 now = out.target;
                 action = out.action;
                 gum = gb.gum;
@@ -3706,6 +3656,194 @@ __global__ __launch_bounds__(64) void k_solve(const int8_t *__restrict__ state, 
     }
 }
 
+// The tablebase in a self-play launch (gbl_collect_search_tb, gbl_collect_gumbel_tb): the probe in front of every ply that is judged
+// or played from the table.  The probe is k_tb_probe's on the live planes: lane a < 54 takes action a, its successor's three look-ups go to `aux` in global
+// memory and one byte comes from anywhere in the table (a 64-bit offset); a butterfly gives V and a*.  A TABLEBASE mover's ply is done
+// there -- the set O is a ballot, its visits row a count in O's lanes, the sampled draw search_decide's rule on that row (the running
+// sum through lane a is count times the members of O up to a) -- and neither the solver nor the tree runs; on a board the table does
+// not hold the masked-random sampler moves.  The lane's outcome byte and V stay for the second lambda, which stores the three judge
+// arrays (the played action's byte comes from its lane by a shuffle).
+struct TbPlay {
+    const uint8_t *aux;
+    const int8_t *table;
+    TbShape S;
+    int mode, count, judge;  // judge: a judge array is given, every ply is probed
+    int8_t *outcome, *value, *played;
+};
+
+// The table's part of a self-play ply, for k_collect_tb and k_collect_gumbel_tb (every lane of the board's wavefront calls it): where
+// the ply is judged or its mover plays from the table, the verdict -- k_tb_probe of the live planes, no mask -- into tb_c (this lane's
+// outcome byte) and tb_v; a TABLEBASE mover on a board the table holds is decided here (S.d) and the call returns true: nothing else
+// runs for the ply.
+__device__ __forceinline__ bool wave_tb_ply(const TbPlay &tb, const SearchBoard &B, int who, uint64_t legal, int policy, int sample_plies,
+                                            uint64_t seed, uint64_t g, uint32_t q, uint32_t lane, int &tb_c, int &tb_v, SearchPly &S)
+{
+    if (tb.judge || policy == kPolicyTablebase) {  // (wave-uniform)
+        const TbAux A = tb_aux(tb.aux);
+        uint64_t cand = legal & tb_piece_actions(tb.S);
+        if (tb_board_index(A, tb.S, B.p, who) < 0) cand = 0;
+        const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
+        if (mine) tb_c = (int)(int8_t)tb_probe_action(A, tb.S, tb.table, B.p, who, lane);  // (the outcome byte: see tb_target_keeps)
+        const uint32_t best = wave_max(mine ? tb_action_key(tb_c, lane) : 0u);
+        tb_v = uniform(tb_value_of(best));
+        if (policy == kPolicyTablebase && best) {
+            const bool keep = mine && tb_target_keeps(tb_c, tb_v, tb.mode);
+            const uint64_t kept = (uint64_t)__ballot(keep);
+            const uint32_t sum = (uint32_t)tb.count * (uint32_t)__popcll(kept);
+            S.d = SearchDecision{uniform(tb_action_of(best)), kHowTable, tb_play_value(tb_v, (int)sum), keep ? (uint32_t)tb.count : 0u};
+            if (B.tabs < sample_plies) {
+                const uint32_t run = (uint32_t)tb.count * (uint32_t)__popcll(kept & ((2ull << lane) - 1ull));
+                const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), sum);
+                const uint64_t over = (uint64_t)__ballot(run > k);
+                S.d.action = over ? (int)__builtin_ctzll(over) : -1;
+                S.d.how = kHowTableSampled;
+            }
+            return true;
+        }
+    }
+    return false;
+}
+
+// The three judge arrays' cell of a ply, for the same two kernels: the lane's outcome byte, V, and the byte of the action the ply played
+// (from its lane by a shuffle).
+__device__ __forceinline__ void wave_tb_store(const TbPlay &tb, int64_t at, int tb_c, int tb_v, int action, uint32_t lane)
+{
+    if (tb.outcome && lane < (uint32_t)kActions) __builtin_nontemporal_store((int8_t)tb_c, tb.outcome + at * kActions + lane);
+    if (tb.value && lane == 0) tb.value[at] = (int8_t)tb_v;
+    if (tb.played) {
+        const int a = uniform(action);  // (the action the ply played: search_plies steps with the same)
+        const int c = __shfl(tb_c, a < 0 ? 0 : a);
+        if (lane == 0) tb.played[at] = (int8_t)(a < 0 ? kSolveNone : c);
+    }
+}
+
+// ---- the evaluator self-play family: k_collect_eval, k_collect_tb and k_collect_gumbel_tb are compositions of the
+// pieces below in the order host_selfplay_run's lambda has them -- probe (wave_tb_ply), guard, search, the ply's stores;
+// k_collect_solve and k_collect_gumbel_solve keep their own text and argument lists: from the pieces they measured slower.
+// SelfplayArgs: what a kernel takes after `done` (the nine arguments before it stay plain, in this order: they fill the 16 preloaded
+// dwords).  The two sides' values are spelt out, not arrays: the mover picks wave-uniformly, field by field, all in SGPRs.
+struct SelfplayArgs {
+    int64_t ply_stride, tile_stride;
+    SearchTraj T;
+    int32_t *root_value;  // the root's q and the network's prior row of every searched ply,
+    uint8_t *priors;
+    int8_t *outcome, *proven;  // ... and the guard's outcome row and V
+    EvalNet net0, net1;
+    int policy0, policy1;
+    uint32_t iterations0, iterations1;
+    int solve_depth0, solve_depth1;
+    uint32_t noise0, noise1, considered0, considered1, most, explore;
+    int sample_plies, illegal_mode;
+    int64_t *counters;
+    int32_t *turn;
+    GumbelArgs gum;  // (considered is not read: the two sides' own stand above)
+    TbPlay tb;
+};
+
+// The family's LDS: (most + 1) nodes, then as many prior rows (dynamic); s_h, the ply's two row images, the solver's: what a kernel touches
+struct PlyLds {
+    TreeNode *nodes;
+    uint8_t *pri;
+    uint32_t *h, *obs, *mask;
+    SolveLds *solve;
+};
+
+__device__ __forceinline__ PlyLds ply_lds(uint32_t most)
+{
+    extern __shared__ uint4 s_tree[];
+    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
+    __shared__ uint32_t s_obs[32], s_mask[16];
+    __shared__ SolveLds s_solve;
+    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
+    return PlyLds{nodes, reinterpret_cast<uint8_t *>(nodes + most + 1), s_h, s_obs, s_mask, &s_solve};
+}
+
+// The solver's guard of a ply (every lane calls it): on a guarded side (solve_depth_m > 0) solve_board on the live planes.  A proven
+// root (V != 0) plays the solver's action -- S.d is filled -- and searches nothing; an unproven one narrows the search to C.
+struct GuardPly {
+    uint64_t cand;     // what the ply's search may play: C, or the legal mask of an unguarded ply
+    int proven, my_c;  // V, and this lane's outcome byte (GBL_SOLVE_NONE on an unguarded ply)
+};
+
+__device__ __forceinline__ GuardPly wave_guard_ply(const SelfplayArgs &a, SolveLds &s_solve, const SearchBoard &B, int who, uint64_t legal,
+                                                   uint32_t lane, SearchPly &S)
+{
+    GuardPly G{legal, 0, kSolveNone};
+    const int depth = who ? a.solve_depth1 : a.solve_depth0;
+    if (depth > 0 && legal) {  // (wave-uniform)
+        const uint32_t best = solve_board<knob::kSolveDeal, false>(s_solve, B.p, who, legal, depth, lane, G.my_c);
+        if (depth > 2) solve_fence<false>();  // (before the next ply's solve rewrites the LDS arrays)
+        G.proven = uniform(solve_value_of(best));
+        if (G.proven) {
+            const uint32_t its = who ? a.iterations1 : a.iterations0;
+            const int act = uniform(solve_action_of(best));
+            S.d = SearchDecision{act, kHowProven, (G.proven > 0 ? 128 : -128) * (int)its, lane == (uint32_t)act ? its : 0u};
+        } else {
+            G.cand = (uint64_t)__ballot(G.my_c == 0);
+        }
+    }
+    return G;
+}
+
+// The search-and-decide ply of an EVAL_TREE mover over cand (every lane calls it; S is filled).  A feature is compiled out where its
+// flag is false; no kernel has both.  NOISE: the side's root noise.  GUMBEL: a side with considered_m > 0 searches by the Gumbel root
+// rule with call = the ply index: the rule decides (never the visit-proportional draw), how = GBL_HOW_GUMBEL, the visits row = the target.
+template <bool NOISE, bool GUMBEL>
+__device__ __forceinline__ void wave_search_ply(const SelfplayArgs &a, const PlyLds &L, const SearchBoard &B, int who, uint64_t cand,
+                                                uint64_t seed, uint64_t g, uint32_t q, uint32_t lane, SearchPly &S)
+{
+    uint32_t mixed;  // (the root's own row; the trajectory keeps the network's)
+    WaveGumbel gb{GumbelArgs{who ? a.considered1 : a.considered0, a.gum.noise, a.gum.visit_offset, a.gum.scale}, seed, g, q, 0, 0, 0ull};
+    const WaveEval at_root = tree_eval_iterations<NOISE, GUMBEL>(L.nodes, L.pri, L.h, eval_net_pick(a.net0, a.net1, who), B.p, who, cand,
+                                                                 who ? a.iterations1 : a.iterations0, a.explore, lane, S.count,
+                                                                 RootNoise{who ? a.noise1 : a.noise0, seed, g, q}, mixed, &gb);
+    S.pi = at_root.pi;
+    S.root_q = at_root.q;
+    const bool rule = GUMBEL && gb.G.considered != 0u;  // (wave-uniform) a Gumbel side's ply
+    S.d = search_decide(L.nodes, lane, !rule && B.tabs < a.sample_plies, seed, g, q);
+    if constexpr (GUMBEL) {
+        if (rule) {
+            const GumbelOut out = wave_gumbel_out(gb, L.nodes, cand, at_root.q, lane);
+            S.d.action = out.action;
+            S.d.how = kHowGumbel;
+            S.d.my_n = out.target;
+        }
+    }
+    wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+}
+
+// A ply's cell of the family's own trajectory arrays (wavefront 0): the root's q and the prior byte; the guard's outcome byte and V.
+__device__ __forceinline__ void store_root_ply(const SelfplayArgs &a, int64_t at, const SearchPly &S, uint32_t lane)
+{
+    if (a.root_value && lane == 0) a.root_value[at] = S.root_q;
+    if (a.priors && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, a.priors + at * kActions + lane);
+}
+
+__device__ __forceinline__ void store_guard_ply(const SelfplayArgs &a, int64_t at, int my_c, int proven, uint32_t lane)
+{
+    if (a.outcome && lane < (uint32_t)kActions) __builtin_nontemporal_store((int8_t)my_c, a.outcome + at * kActions + lane);
+    if (a.proven && lane == 0) a.proven[at] = (int8_t)proven;
+}
+
+// gbl_collect_search_eval, and (GUMBEL) gbl_collect_search_gumbel with a Gumbel side: the search alone.
+template <bool GUMBEL>
+__global__ __launch_bounds__(64) void k_collect_eval(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
+                                                     uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
+                                                     int8_t *__restrict__ done, const SelfplayArgs a)
+{
+    const PlyLds L = ply_lds(a.most);
+    const uint32_t lane = threadIdx.x;
+    search_plies(
+        state, to_move, done, a.turn, a.counters, n, seed, env_base, ply_dev, ply0, plies, a.ply_stride, a.tile_stride, a.T, a.illegal_mode,
+        L.mask, L.obs,
+        [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
+            if ((who ? a.policy1 : a.policy0) != kPolicyEvalTree) return false;
+            wave_search_ply<false, GUMBEL>(a, L, B, who, legal, seed, g, q, lane, S);
+            return true;
+        },
+        [&](int64_t at, const SearchPly &S) { store_root_ply(a, at, S, lane); });
+}
+
 // gbl_collect_search_solve: k_collect_eval with the exact solver in front of every search of a guarded side (solve_depth_m > 0).
 // One wavefront per board (a grid-stride loop over boards), the ply loop inside (search_plies).  A guarded ply runs solve_board
 // on the live planes.  A proven root (V != 0) plays the solver's action and searches nothing; an unproven root searches exactly as
@@ -3857,189 +3995,68 @@ __global__ __launch_bounds__(64) void k_collect_gumbel_solve(int8_t *__restrict_
         });
 }
 
-// gbl_collect_search_tb: k_collect_solve with the tablebase's probe in front of every ply that is judged or played from the table.
-// The probe is k_tb_probe's on the live planes: lane a < 54 takes action a, its successor's three look-ups go to `aux` in global
-// memory and one byte comes from anywhere in the table (a 64-bit offset); a butterfly gives V and a*.  A TABLEBASE mover's ply is done
-// there -- the set O is a ballot, its visits row a count in O's lanes, the sampled draw search_decide's rule on that row (the running
-// sum through lane a is count times the members of O up to a) -- and neither the solver nor the tree runs; on a board the table does
-// not hold the masked-random sampler moves.  The lane's outcome byte and V stay for the second lambda, which stores the three judge
-// arrays beside k_collect_solve's four (the played action's byte comes from its lane by a shuffle).  SEARCH = false is the launch
-// without an EVAL_TREE side: the solver and the tree are compiled out, and with them their registers -- such a ply is a chain of
-// dependent look-ups that only more resident wavefronts hide.
-struct TbPlay {
-    const uint8_t *aux;
-    const int8_t *table;
-    TbShape S;
-    int mode, count, judge;  // judge: a judge array is given, every ply is probed
-    int8_t *outcome, *value, *played;
-};
-
-// The table's part of a self-play ply, for k_collect_tb and k_collect_gumbel_tb (every lane of the board's wavefront calls it): where
-// the ply is judged or its mover plays from the table, the verdict -- k_tb_probe of the live planes, no mask -- into tb_c (this lane's
-// outcome byte) and tb_v; a TABLEBASE mover on a board the table holds is decided here (S.d) and the call returns true: nothing else
-// runs for the ply.
-__device__ __forceinline__ bool wave_tb_ply(const TbPlay &tb, const SearchBoard &B, int who, uint64_t legal, int policy, int sample_plies,
-                                            uint64_t seed, uint64_t g, uint32_t q, uint32_t lane, int &tb_c, int &tb_v, SearchPly &S)
-{
-    if (tb.judge || policy == kPolicyTablebase) {  // (wave-uniform)
-        const TbAux A = tb_aux(tb.aux);
-        uint64_t cand = legal & tb_piece_actions(tb.S);
-        if (tb_board_index(A, tb.S, B.p, who) < 0) cand = 0;
-        const bool mine = lane < (uint32_t)kActions && ((cand >> lane) & 1ull);
-        if (mine) tb_c = (int)(int8_t)tb_probe_action(A, tb.S, tb.table, B.p, who, lane);  // (the outcome byte: see tb_target_keeps)
-        const uint32_t best = wave_max(mine ? tb_action_key(tb_c, lane) : 0u);
-        tb_v = uniform(tb_value_of(best));
-        if (policy == kPolicyTablebase && best) {
-            const bool keep = mine && tb_target_keeps(tb_c, tb_v, tb.mode);
-            const uint64_t kept = (uint64_t)__ballot(keep);
-            const uint32_t sum = (uint32_t)tb.count * (uint32_t)__popcll(kept);
-            S.d = SearchDecision{uniform(tb_action_of(best)), kHowTable, tb_play_value(tb_v, (int)sum), keep ? (uint32_t)tb.count : 0u};
-            if (B.tabs < sample_plies) {
-                const uint32_t run = (uint32_t)tb.count * (uint32_t)__popcll(kept & ((2ull << lane) - 1ull));
-                const uint32_t k = __umulhi(draw32(seed, g, q, kStreamVisit), sum);
-                const uint64_t over = (uint64_t)__ballot(run > k);
-                S.d.action = over ? (int)__builtin_ctzll(over) : -1;
-                S.d.how = kHowTableSampled;
-            }
-            return true;
-        }
-    }
-    return false;
-}
-
-// The three judge arrays' cell of a ply, for the same two kernels: the lane's outcome byte, V, and the byte of the action the ply played
-// (from its lane by a shuffle).
-__device__ __forceinline__ void wave_tb_store(const TbPlay &tb, int64_t at, int tb_c, int tb_v, int action, uint32_t lane)
-{
-    if (tb.outcome && lane < (uint32_t)kActions) __builtin_nontemporal_store((int8_t)tb_c, tb.outcome + at * kActions + lane);
-    if (tb.value && lane == 0) tb.value[at] = (int8_t)tb_v;
-    if (tb.played) {
-        const int a = uniform(action);  // (the action the ply played: search_plies steps with the same)
-        const int c = __shfl(tb_c, a < 0 ? 0 : a);
-        if (lane == 0) tb.played[at] = (int8_t)(a < 0 ? kSolveNone : c);
-    }
-}
-
+// gbl_collect_search_tb: the table's probe in front of every ply that is judged or played from it, the judge's arrays behind the guard's.
+// SEARCH = false is the launch without an EVAL_TREE side: the solver and the tree are compiled out, and with them their registers and
+// LDS -- such a ply is a chain of dependent look-ups that only more resident wavefronts hide.
 template <bool NOISE, bool SEARCH>
 __global__ __launch_bounds__(64) void k_collect_tb(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
                                                    uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies,
-                                                   int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride, SearchTraj T,
-                                                   int32_t *__restrict__ root_value_traj, uint8_t *__restrict__ priors_traj,
-                                                   int8_t *__restrict__ outcome_traj, int8_t *__restrict__ proven_traj,
-                                                   const EvalNet net0, const EvalNet net1, int policy0, int policy1, uint32_t iterations0,
-                                                   uint32_t iterations1, int solve_depth0, int solve_depth1, uint32_t most, uint32_t explore,
-                                                   int sample_plies, int illegal_mode, int64_t *__restrict__ counters,
-                                                   int32_t *__restrict__ turn, uint32_t noise0, uint32_t noise1, const TbPlay tb)
+                                                   int8_t *__restrict__ done, const SelfplayArgs a)
 {
-    extern __shared__ uint4 s_tree[];
-    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
-    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
-    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
-    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
-    __shared__ SolveLds s_solve;
+    const PlyLds L = ply_lds(a.most);
     const uint32_t lane = threadIdx.x;
     int my_c = kSolveNone, proven = 0;  // the ply's outcome byte of this lane and V, from the first lambda to the second
-    int tb_c = kSolveNone, tb_v = 0;    // ... and the table's
+    int tb_c = kSolveNone, tb_v = 0;  // the table's outcome byte of this lane and V, from the first lambda to the second
     search_plies(
-        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        state, to_move, done, a.turn, a.counters, n, seed, env_base, ply_dev, ply0, plies, a.ply_stride, a.tile_stride, a.T, a.illegal_mode,
+        L.mask, L.obs,
         [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
             my_c = kSolveNone;
             proven = 0;
             tb_c = kSolveNone;
             tb_v = 0;
-            const int policy = who ? policy1 : policy0;
-            if (wave_tb_ply(tb, B, who, legal, policy, sample_plies, seed, g, q, lane, tb_c, tb_v, S)) return true;
+            const int policy = who ? a.policy1 : a.policy0;
+            if (wave_tb_ply(a.tb, B, who, legal, policy, a.sample_plies, seed, g, q, lane, tb_c, tb_v, S)) return true;
             if (!SEARCH || policy != kPolicyEvalTree) return false;
             if constexpr (SEARCH) {
-                const uint32_t its = who ? iterations1 : iterations0;
-                const int depth = who ? solve_depth1 : solve_depth0;
-                uint64_t cand = legal;
-                if (depth > 0 && legal) {  // (wave-uniform)
-                    const uint32_t best = solve_board<knob::kSolveDeal, false>(s_solve, B.p, who, legal, depth, lane, my_c);
-                    if (depth > 2) solve_fence<false>();  // (before the next ply's solve rewrites the LDS arrays)
-                    proven = uniform(solve_value_of(best));
-                    if (proven) {
-                        const int a = uniform(solve_action_of(best));
-                        S.d = SearchDecision{a, kHowProven, (proven > 0 ? 128 : -128) * (int)its, lane == (uint32_t)a ? its : 0u};
-                        return true;
-                    }
-                    cand = (uint64_t)__ballot(my_c == 0);
-                }
-                uint32_t mixed;  // (the root's own row; the trajectory keeps the network's)
-                const WaveEval at_root = tree_eval_iterations<NOISE>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, cand, its,
-                                                                     explore, lane, S.count, RootNoise{who ? noise1 : noise0, seed, g, q}, mixed);
-                S.pi = at_root.pi;
-                S.root_q = at_root.q;
-                S.d = search_decide(nodes, lane, B.tabs < sample_plies, seed, g, q);
-                wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+                const GuardPly G = wave_guard_ply(a, *L.solve, B, who, legal, lane, S);
+                my_c = G.my_c;
+                proven = G.proven;
+                if (!proven) wave_search_ply<NOISE, false>(a, L, B, who, G.cand, seed, g, q, lane, S);
             }
             return true;
         },
         [&](int64_t at, const SearchPly &S) {
-            const bool act = lane < (uint32_t)kActions;
-            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
-            if (priors_traj && act) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
-            if (outcome_traj && act) __builtin_nontemporal_store((int8_t)my_c, outcome_traj + at * kActions + lane);
-            if (proven_traj && lane == 0) proven_traj[at] = (int8_t)proven;
-            wave_tb_store(tb, at, tb_c, tb_v, S.d.action, lane);
+            store_root_ply(a, at, S, lane);
+            store_guard_ply(a, at, my_c, proven, lane);
+            wave_tb_store(a.tb, at, tb_c, tb_v, S.d.action, lane);
         });
 }
 
-// gbl_collect_gumbel_tb: k_collect_eval<true>'s ply with k_collect_tb's probe in front of it and the judge's stores behind it -- the
-// kernel of a call that has a Gumbel side and reads the table (selfplay_launch runs k_collect_eval<true> for a call that does not read
-// it and k_collect_tb for one without a Gumbel side, so neither carries the other's code).  A TABLEBASE mover's ply and the verdict
-// are wave_tb_ply's, exactly as in k_collect_tb; an EVAL_TREE mover's ply is tree_eval_iterations<false, true> over the legal mask and,
-// for a side with considered_m > 0, wave_gumbel_finish on the root's read-out -- ply q's search IS gbl_tree_search_gumbel(call = q); a
-// side with considered_m == 0 decides by search_decide, sample_plies honoured.  The probe's registers are dead before the tree's come
-// alive: only the lane's outcome byte and V live across the search.  No solver and no noise: neither has LDS or registers here.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_collect_gumbel_tb(int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed,
-                                                          uint64_t env_base, const uint32_t *__restrict__ ply_dev, uint32_t ply0,
-                                                          uint32_t plies, int8_t *__restrict__ done, int64_t ply_stride, int64_t tile_stride,
-                                                          SearchTraj T, int32_t *__restrict__ root_value_traj,
-                                                          uint8_t *__restrict__ priors_traj, const EvalNet net0, const EvalNet net1,
-                                                          int policy0, int policy1, uint32_t iterations0, uint32_t iterations1, uint32_t most,
-                                                          uint32_t explore, int sample_plies, int illegal_mode,
-                                                          int64_t *__restrict__ counters, int32_t *__restrict__ turn, const GumbelArgs gum,
-                                                          uint32_t considered0, uint32_t considered1, const TbPlay tb)
+// gbl_collect_gumbel_tb: the kernel of a call that has a Gumbel side and reads the table (every other call of the entry point runs
+// k_collect_eval<true> or k_collect_tb).  Only the lane's outcome byte and V live across the search; no solver and no noise here.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_collect_gumbel_tb(
+    int8_t *__restrict__ state, int8_t *__restrict__ to_move, int64_t n, uint64_t seed, uint64_t env_base,
+    const uint32_t *__restrict__ ply_dev, uint32_t ply0, uint32_t plies, int8_t *__restrict__ done, const SelfplayArgs a)
 {
-    extern __shared__ uint4 s_tree[];
-    TreeNode *const nodes = reinterpret_cast<TreeNode *>(s_tree);
-    uint8_t *const pri = reinterpret_cast<uint8_t *>(nodes + most + 1);
-    __shared__ uint32_t s_h[kEvalMaxHidden / 4];
-    __shared__ uint32_t s_obs[32], s_mask[16];  // the ply's observation row (117 bytes) and mask row (54)
+    const PlyLds L = ply_lds(a.most);
     const uint32_t lane = threadIdx.x;
     int tb_c = kSolveNone, tb_v = 0;  // the table's outcome byte of this lane and V, from the first lambda to the second
     search_plies(
-        state, to_move, done, turn, counters, n, seed, env_base, ply_dev, ply0, plies, ply_stride, tile_stride, T, illegal_mode, s_mask, s_obs,
+        state, to_move, done, a.turn, a.counters, n, seed, env_base, ply_dev, ply0, plies, a.ply_stride, a.tile_stride, a.T, a.illegal_mode,
+        L.mask, L.obs,
         [&](const SearchBoard &B, int who, uint64_t legal, uint64_t g, uint32_t q, SearchPly &S) {
             tb_c = kSolveNone;
             tb_v = 0;
-            const int policy = who ? policy1 : policy0;
-            if (wave_tb_ply(tb, B, who, legal, policy, sample_plies, seed, g, q, lane, tb_c, tb_v, S)) return true;
+            const int policy = who ? a.policy1 : a.policy0;
+            if (wave_tb_ply(a.tb, B, who, legal, policy, a.sample_plies, seed, g, q, lane, tb_c, tb_v, S)) return true;
             if (policy != kPolicyEvalTree) return false;
-            uint32_t mixed;  // (no noise here: the network's byte)
-            WaveGumbel gb{GumbelArgs{who ? considered1 : considered0, gum.noise, gum.visit_offset, gum.scale}, seed, g, q, 0, 0, 0ull};
-            const WaveEval at_root = tree_eval_iterations<false, true>(nodes, pri, s_h, eval_net_pick(net0, net1, who), B.p, who, legal,
-                                                                       who ? iterations1 : iterations0, explore, lane, S.count, RootNoise{},
-                                                                       mixed, &gb);
-            S.pi = at_root.pi;
-            S.root_q = at_root.q;
-            const bool rule = gb.G.considered != 0u;  // (wave-uniform) a Gumbel side's ply
-            S.d = search_decide(nodes, lane, !rule && B.tabs < sample_plies, seed, g, q);
-            if (rule) {
-                GumbelOut out{-1, 0u};
-                if (gb.A) out = wave_gumbel_finish(gb, tree_lane_child(nodes, nodes[0].child, lane), legal, at_root.q, lane);
-                S.d.action = out.action;
-                S.d.how = kHowGumbel;
-                S.d.my_n = out.target;
-            }
-            wave_lds_fence();  // (the root's children are read before the next search rewrites the tree)
+            wave_search_ply<false, true>(a, L, B, who, legal, seed, g, q, lane, S);
             return true;
         },
         [&](int64_t at, const SearchPly &S) {
-            if (root_value_traj && lane == 0) root_value_traj[at] = S.root_q;
-            if (priors_traj && lane < (uint32_t)kActions) __builtin_nontemporal_store((uint8_t)S.pi, priors_traj + at * kActions + lane);
-            wave_tb_store(tb, at, tb_c, tb_v, S.d.action, lane);
+            store_root_ply(a, at, S, lane);
+            wave_tb_store(a.tb, at, tb_c, tb_v, S.d.action, lane);
         });
 }
 
@@ -4788,7 +4805,7 @@ static int check_traj(int64_t n, uint32_t plies, int64_t ply_stride, int64_t til
     return GBL_OK;
 }
 
-// The tail the two self-play entry points (gbl_collect_search, gbl_collect_search_eval) share, after their own checks: the
+// The tail the nine self-play entry points share (selfplay_launch calls it once), after their own checks: the
 // trajectory's strides and alignments.  T: the kernel's SearchTraj, built by the entry point from its arguments; more_words /
 // words_msg: the entry's own further 4-byte arrays (check_traj's `words`) and the message that names its whole list.
 static int check_search_traj(const SearchTraj &T, uintptr_t more_words, const char *words_msg, int64_t n, uint32_t plies, int64_t ply_stride,
@@ -5594,19 +5611,7 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     // (a call that never reads the table passes an empty one: no ply probes)
     const TbPlay tb{static_cast<const uint8_t *>(c.aux), c.table, reads_table ? tb_shape(c.inventory) : TbShape{}, c.tb_mode, c.tb_count,
                     (t.tb_outcome || t.tb_value || t.tb_played) ? 1 : 0, t.tb_outcome, t.tb_value, t.tb_played};
-    if (rule_table) {
-        const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
-        hipLaunchKernelGGL(k_collect_gumbel_tb, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
-                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1], its0,
-                           its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn, gum,
-                           (uint32_t)selfplay_considered(c, 0), (uint32_t)selfplay_considered(c, 1), tb);
-    } else if (c.run == kRunSolve && rule_side && !rule_unguarded) {
-        const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
-        hipLaunchKernelGGL(k_collect_gumbel_solve, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
-                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1], c.policy[0],
-                           c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies, c.illegal_mode,
-                           c.counters, c.turn, gum, (uint32_t)selfplay_considered(c, 0), (uint32_t)selfplay_considered(c, 1));
-    } else if (uct) {
+    if (uct) {
         // the larger leaf of the sides that search
         const int wide = std::max(1, std::max(c.policy[0] == GBL_POLICY_TREE ? c.playouts[0] : 0, c.policy[1] == GBL_POLICY_TREE ? c.playouts[1] : 0));
 #define GBL_CS(W)                                                                                                                         \
@@ -5619,56 +5624,50 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
         default: GBL_CS(1); break;
         }
 #undef GBL_CS
-    } else if (c.run == kRunEval || rule_unguarded || rule_untabled) {
-        const uint32_t m0 = (uint32_t)selfplay_considered(c, 0), m1 = (uint32_t)selfplay_considered(c, 1);
-        const GumbelArgs gum{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale};
-        // (k_collect_eval<false> is the kernel without the rule's code: gbl_collect_search_eval, and gbl_collect_search_gumbel with no Gumbel side)
-#define GBL_CE(GUMBEL)                                                                                                                    \
-    hipLaunchKernelGGL(k_collect_eval<GUMBEL>, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,       \
-                       c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, nets[0], nets[1], c.policy[0], c.policy[1],  \
-                       its0, its1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn, gum, m0, m1)
-        if (m0 | m1)
-            GBL_CE(true);
-        else
-            GBL_CE(false);
-#undef GBL_CE
-    } else if (c.run == kRunTb) {
-        const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
-                       w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
-#define GBL_CTB(NOISE, SEARCH)                                                                                                            \
-    hipLaunchKernelGGL((k_collect_tb<NOISE, SEARCH>), grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0,          \
-                       c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1],       \
-                       c.policy[0], c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies,    \
-                       c.illegal_mode, c.counters, c.turn, w0, w1, tb)
-        if (most == 0)  // (no side searches: the instantiation without the solver and the tree)
-            GBL_CTB(false, false);
-        else if (w0 | w1)
-            GBL_CTB(true, true);
-        else
-            GBL_CTB(false, true);
-#undef GBL_CTB
-    } else {
-        const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
-                       w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
-        const uint32_t sh0 = (uint32_t)selfplay_share(c, 0), sh1 = (uint32_t)selfplay_share(c, 1);
-        // (k_collect_solve<false, ...> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked; and
-        // <..., false> the one without the cap's: both shares 256 run it)
+        GBL_LAUNCHED(name);
+    }
+    // the evaluator family: one argument struct for the kernels that take it (a side that does not search has weight 0, share 256, considered 0)
+    const uint32_t w0 = c.policy[0] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[0] : 0u,
+                   w1 = c.policy[1] == GBL_POLICY_EVAL_TREE ? (uint32_t)c.noise[1] : 0u;
+    const uint32_t sh0 = (uint32_t)selfplay_share(c, 0), sh1 = (uint32_t)selfplay_share(c, 1);
+    const uint32_t m0 = (uint32_t)selfplay_considered(c, 0), m1 = (uint32_t)selfplay_considered(c, 1);
+    const SelfplayArgs a{c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1], c.policy[0], c.policy[1],
+                         its0, its1, c.solve_depth[0], c.solve_depth[1], w0, w1, m0, m1, (uint32_t)most, explore, c.sample_plies, c.illegal_mode, c.counters, c.turn,
+                         GumbelArgs{0u, (uint32_t)c.gumbel_noise, (uint32_t)c.visit_offset, (uint32_t)c.scale}, tb};
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies, c.done, a);
+    };
 #define GBL_CSV(NOISE, CAP)                                                                                                               \
     hipLaunchKernelGGL((k_collect_solve<NOISE, CAP>), grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, \
                        c.plies, c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1],       \
                        c.policy[0], c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies,    \
                        c.illegal_mode, c.counters, c.turn, w0, w1, (uint32_t)c.fast[0], (uint32_t)c.fast[1], sh0, sh1)
-        const bool cap = sh0 < (uint32_t)kCapFullShare || sh1 < (uint32_t)kCapFullShare;
-        if (cap && (w0 | w1))
-            GBL_CSV(true, true);
-        else if (cap)
-            GBL_CSV(false, true);
-        else if (w0 | w1)
-            GBL_CSV(true, false);
-        else
-            GBL_CSV(false, false);
+    const bool cap = sh0 < (uint32_t)kCapFullShare || sh1 < (uint32_t)kCapFullShare;
+    if (rule_table)
+        launch(k_collect_gumbel_tb);
+    else if (c.run == kRunSolve && rule_side && !rule_unguarded)
+        hipLaunchKernelGGL(k_collect_gumbel_solve, grid, dim3(64), lds, s, c.state, c.to_move, c.n, c.seed, c.env_base, c.ply_dev, c.ply0, c.plies,
+                           c.done, c.ply_stride, c.tile_stride, T, t.root_value, t.priors, t.outcome, t.proven, nets[0], nets[1], c.policy[0],
+                           c.policy[1], its0, its1, c.solve_depth[0], c.solve_depth[1], (uint32_t)most, explore, c.sample_plies, c.illegal_mode,
+                           c.counters, c.turn, a.gum, m0, m1);
+    else if (c.run == kRunEval || rule_unguarded || rule_untabled)
+        // (k_collect_eval<false> is the kernel without the rule's code: gbl_collect_search_eval, and gbl_collect_search_gumbel with no Gumbel side)
+        (m0 | m1) ? launch(k_collect_eval<true>) : launch(k_collect_eval<false>);
+    else if (c.run == kRunTb && most == 0)  // (no side searches: the instantiation without the solver and the tree)
+        launch(k_collect_tb<false, false>);
+    else if (c.run == kRunTb)
+        (w0 | w1) ? launch(k_collect_tb<true, true>) : launch(k_collect_tb<false, true>);
+    // (k_collect_solve<false, ...> is the kernel without the noise's code: both weights 0 run it, whichever entry point asked; and
+    // <..., false> the one without the cap's: both shares 256 run it)
+    else if (cap && (w0 | w1))
+        GBL_CSV(true, true);
+    else if (cap)
+        GBL_CSV(false, true);
+    else if (w0 | w1)
+        GBL_CSV(true, false);
+    else
+        GBL_CSV(false, false);
 #undef GBL_CSV
-    }
     GBL_LAUNCHED(name);
 }
 

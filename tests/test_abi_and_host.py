@@ -86,6 +86,34 @@ def test_no_kernel_uses_scratch():
         assert int(v["group_segment_fixed_size"]) <= 160 * 1024, k
 
 
+def test_evaluator_selfplay_kernels_keep_their_wavefronts():
+    """The evaluator self-play family sits at the edge of its register bands: each instantiation keeps at least the wavefronts per
+    SIMD (by VGPRs, in allocation units of 8) it had when its text was folded into shared pieces, and exactly its static LDS.  A change
+    that gains a wavefront passes; one that loses a wavefront fails."""
+    import subprocess
+    floors = {  # demangled name: (wavefronts per SIMD at least, static LDS bytes)
+        "k_collect_eval<false>": (4, 448), "k_collect_eval<true>": (4, 448),
+        "k_collect_solve<false, false>": (4, 1328), "k_collect_solve<false, true>": (4, 1328),
+        "k_collect_solve<true, false>": (4, 1328), "k_collect_solve<true, true>": (4, 1328),
+        "k_collect_gumbel_solve": (3, 1328),
+        "k_collect_tb<false, false>": (8, 192), "k_collect_tb<false, true>": (3, 1328), "k_collect_tb<true, true>": (3, 1328),
+        "k_collect_gumbel_tb": (4, 448),
+        "k_tree_eval<false, true>": (4, 256), "k_reanalyse<true>": (4, 256),
+    }
+    meta = kernel_metadata()
+    names = sorted(meta)
+    demangled = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.splitlines()
+    seen = {}
+    for k, d in zip(names, demangled):
+        d = d.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
+        if d in floors:
+            seen[d] = (512 // (-(-int(meta[k]["vgpr_count"]) // 8) * 8), int(meta[k]["group_segment_fixed_size"]), meta[k]["vgpr_count"])
+    assert sorted(seen) == sorted(floors), sorted(set(floors) - set(seen))
+    for d, (waves, lds) in floors.items():
+        assert seen[d][0] >= waves, (d, "vgpr", seen[d][2], "wavefronts per SIMD", seen[d][0], "floor", waves)
+        assert seen[d][1] == lds, (d, "lds", seen[d][1], lds)
+
+
 def test_layout_info_and_host_side_argument_errors():
     L = nat.lib()
     info = (C.c_int32 * 6)()
