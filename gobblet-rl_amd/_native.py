@@ -311,6 +311,16 @@ def ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def device(spec) -> torch.device:
+    """``torch.device(spec)`` in the spelling a tensor reports: an unindexed GPU ("cuda") becomes the current one with its index --
+    ``torch.device("cuda") != torch.device("cuda:0")``, and every class compares its tensors' devices with its own.  Everything else
+    passes through."""
+    dev = torch.device(spec)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
 def current_stream(device):
     """The caller's HIP stream on `device` as a plain pointer (None on the host flavour: its calls are synchronous)."""
     device = torch.device(device)

@@ -1,7 +1,8 @@
 """What the policy classes share (private: the public names are the policies themselves).
 
 ``_ReferenceAdapters``: the three reference-shaped entry points over a class's own batched ``compute_actions(obs, mask)``.
-``_OnDevice``: the stream, the device context and the (state, to_move, mask) canonicalisation of an object with a ``device``.
+``_OnDevice``: the stream, the device context and the (state, to_move, mask) canonicalisation of an object with a ``device`` -- every
+class of the package that launches, the boards and the environment included; ``_launches`` puts a whole method inside that context.
 ``_SearchPolicy``: a policy whose decision is one launch on (state, to_move, mask) -- a subclass supplies ``_run`` (the launch, on
 inputs already in the library's form) and gets the batched entry points; ``device`` and ``_lib`` are the subclass's attributes.
 ``_TreeSearchPolicy``: the targets a tree search leaves in ``last_visits`` / ``last_wins`` / ``last_losses``.
@@ -9,6 +10,7 @@ inputs already in the library's form) and gets the batched entry points; ``devic
 from __future__ import annotations
 
 import contextlib
+import functools
 
 import numpy as np
 import torch
@@ -33,6 +35,15 @@ class _ReferenceAdapters:
         mask = ob["mask"] if isinstance(ob, dict) else ob.mask
         act = self.compute_actions(obs, torch.as_tensor(mask).to(torch.int8))
         return {"act": act.to(torch.int64).cpu().numpy()}
+
+
+def _launches(method):
+    """A method of an ``_OnDevice`` class that launches: its whole body runs inside ``_on_device()``."""
+    @functools.wraps(method)
+    def on_device(self, *args, **kwargs):
+        with self._on_device():
+            return method(self, *args, **kwargs)
+    return on_device
 
 
 class _OnDevice:

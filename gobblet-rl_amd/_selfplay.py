@@ -186,7 +186,7 @@ def _evaluator_params(policies, search, device):
             raise ValueError(f"search: solve_depth must be in [0, {nat.SOLVE_MAX_DEPTH}]")
         if not isinstance(nets[m], GobbletEvaluator):
             raise ValueError("search: an 'evaluator' side needs search=dict(evaluator=GobbletEvaluator ...)")
-        if nets[m].device != device:
+        if nat.device(nets[m].device) != nat.device(device):
             raise ValueError("the evaluator lives on %s and the environment on %s: move it with evaluator.to(...)"
                              % (nets[m].device, device))
         its[m] = int(its[m])
@@ -307,7 +307,7 @@ def _tablebase_params(policies, search, device):
             tb = x.tb
     if not isinstance(tb, Tablebase):
         raise ValueError("search: a 'tablebase' side (or judge=True) needs " + where)
-    if tb.device != device:
+    if nat.device(tb.device) != nat.device(device):
         raise ValueError("the table lives on %s and the environment on %s" % (tb.device, device))
     if not tb.complete and not kw["allow_incomplete"]:
         raise ValueError("the table is not complete: a 0 would read 'not proven yet' (allow_incomplete=True to play from it anyway)")

@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _native as nat
+from ._policy_base import _launches, _OnDevice
 
 
 def _as_i8(x, n, device, name):
@@ -38,13 +39,13 @@ def _as_i32(x, n, device, name):
     return t.contiguous()
 
 
-class BatchedBoard:
+class BatchedBoard(_OnDevice):
     """N Gobblet boards on one MI355X.  Mirrors ``Board`` (board.py:4-242)."""
 
     def __init__(self, num_envs: int, device="cuda:0", squares: torch.Tensor | None = None):
         if num_envs < 1:
             raise ValueError("num_envs must be >= 1")
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         # "cuda": the HIP library (it raises if it cannot be built or loaded: no fallback); "cpu": the host flavour of the same
         # ABI (include/gobblet_cpu.h), which a caller has to ask for
         self.num_envs = int(num_envs)
@@ -64,9 +65,6 @@ class BatchedBoard:
     def squares(self, value):
         v = torch.as_tensor(value, device=self.device).to(torch.int8).reshape(self.num_envs, nat.CELLS)
         self._squares = v.contiguous().clone() if v.data_ptr() % 16 else v.contiguous()
-
-    def _stream(self):
-        return nat.current_stream(self.device)
 
     # -- board.py:135-153 ------------------------------------------------------------------------
     def calculate_winners(self):
@@ -102,6 +100,7 @@ class BatchedBoard:
         return cls.get_pos_from_action(action) + 9 * (cls.get_piece_size_from_action(action) - 1)
 
     # -- board.py:82-115 -----------------------------------------------------------------------------
+    @_launches
     def is_legal(self, action, agent_index=0) -> torch.Tensor:
         """bool (N,): is ``action[b]`` legal for ``agent_index[b]`` on board b (scalars broadcast)."""
         n = self.num_envs
@@ -112,6 +111,7 @@ class BatchedBoard:
                                          self._stream()), "gbl_is_legal")
         return out.bool()
 
+    @_launches
     def legal_mask(self, agent_index) -> torch.Tensor:
         """int8 (N, 54): ``[is_legal(a, agent_index) for a in range(54)]`` (gobblet.py:223-228, 211-213)."""
         n = self.num_envs
@@ -122,6 +122,7 @@ class BatchedBoard:
         return out
 
     # -- board.py:118-132 -----------------------------------------------------------------------------
+    @_launches
     def play_turn(self, agent_index, action) -> None:
         n = self.num_envs
         a = _as_i32(action, n, self.device, "action")
@@ -142,6 +143,7 @@ class BatchedBoard:
         return torch.where(l1, a1, torch.where(l2, a2, torch.full_like(a1, -1)))
 
     # -- board.py:159-177 -------------------------------------------------------------------------------
+    @_launches
     def get_flatboard(self) -> torch.Tensor:
         n = self.num_envs
         out = torch.empty((n, 9), dtype=torch.int8, device=self.device)
@@ -149,6 +151,7 @@ class BatchedBoard:
         return out
 
     # -- board.py:183-201 -------------------------------------------------------------------------------
+    @_launches
     def check_for_winner(self) -> torch.Tensor:
         n = self.num_envs
         out = torch.empty(n, dtype=torch.int8, device=self.device)
@@ -159,6 +162,7 @@ class BatchedBoard:
         return self.check_for_winner() != 0
 
     # -- board.py:203-220 -------------------------------------------------------------------------------
+    @_launches
     def check_covered(self) -> torch.Tensor:
         n = self.num_envs
         out = torch.empty((n, nat.CELLS), dtype=torch.int8, device=self.device)
@@ -166,6 +170,7 @@ class BatchedBoard:
         return out
 
     # -- everything the reference derives from a position, in one launch ---------------------------------
+    @_launches
     def evaluate(self, agent_index=None, action=None, out: torch.Tensor | None = None) -> dict:
         """``gbl_board_eval``: optionally ``play_turn(agent_index, action)`` first, then per board the winner,
         flat board, covered cells, both agents' legal masks and both observations -- one launch instead of seven.
@@ -186,6 +191,7 @@ class BatchedBoard:
         return views
 
     # -- state contract (for callers that assign ``squares``) --------------------------------------------
+    @_launches
     def validate(self, raise_on_error: bool = True) -> torch.Tensor:
         """int8 (N,) flags: bit 0 = a cell holds a value its level cannot hold, bit 1 = a piece number
         occurs twice.  With ``raise_on_error`` a duplicate raises what the reference's ``is_legal`` raises
@@ -202,6 +208,7 @@ class BatchedBoard:
         return out
 
     # -- gobblet.py:179-208 (the observation planes are a pure function of the board) -------------------
+    @_launches
     def observation(self, agent_index) -> torch.Tensor:
         """int8 (N, 3, 3, 13) as seen by ``agent_index`` (scalar 0/1 or an (N,) tensor)."""
         n = self.num_envs

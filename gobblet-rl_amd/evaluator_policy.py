@@ -37,7 +37,7 @@ class GobbletEvaluator(_OnDevice):
     element [j // 4, k, j % 4] = the weight of hidden unit j for output k, b2 int32 (56,), and the three shifts."""
 
     def __init__(self, w1, b1, w2, b2, shift1: int, shift_p: int, shift_v: int, device="cpu") -> None:
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         w1, b1, w2, b2 = (torch.as_tensor(t) for t in (w1, b1, w2, b2))
         hidden = int(w1.shape[-1])
         if hidden not in HIDDEN_SIZES:
@@ -239,7 +239,7 @@ class EvaluatorTreeSearchGobbletPolicy(_TreeSearchPolicy):
         if self.gumbel is not None and self.noise:
             raise ValueError("gumbel does not go with noise: the Gumbel row is the search's exploration")
         self.seed, self.env_base, self.call = int(seed), int(env_base), 0
-        self.device = torch.device(evaluator.device if device is None else device)
+        self.device = nat.device(evaluator.device if device is None else device)
         self.evaluator = evaluator if evaluator.device == self.device else evaluator.to(self.device)
         self._lib = nat.lib_for(self.device)
         # outputs of the last call (tensors on the device): int32 (N, 54) visits / wins / losses of the root's children from the

@@ -143,7 +143,7 @@ class _HipBoardEngine:
     _STATE, _ACTION, _AGENT, _BYTES = 448, 432, 436, 512  # offsets in the block; the record is at 0
 
     def __init__(self, device):
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         if self.device.type != "cuda":
             raise nat.GobbletHipError("gobblet_v1 needs a GPU device (there is no CPU fallback)")
         self._lib = nat.lib()
@@ -227,7 +227,7 @@ _ENGINES: dict = {}
 def _new_backend(device):
     """The engine of a ``Board``: the HIP library for a GPU device, the host flavour of the same ABI for "cpu" -- one per
     device.  (Module-level so that the host-logic tests can monkeypatch it; nothing in the package does.)"""
-    key = str(torch.device(device))
+    key = str(nat.device(device))  # ("cuda" and "cuda:0" share the engine -- and its lock)
     if key not in _ENGINES:
         _ENGINES[key] = _HipBoardEngine(device) if torch.device(device).type == "cuda" else _HostBoardEngine(device)
     return _ENGINES[key]

@@ -21,10 +21,10 @@ from typing import Any, Optional
 import torch
 
 from . import _native as nat
-from ._policy_base import _ReferenceAdapters
+from ._policy_base import _launches, _OnDevice, _ReferenceAdapters
 
 
-class GreedyGobbletPolicy(_ReferenceAdapters):
+class GreedyGobbletPolicy(_OnDevice, _ReferenceAdapters):
     def __init__(self, depth: Optional[int] = 2, seed: Optional[int] = 0, device="cuda:0", env_base: int = 0,
                  **kwargs: Any) -> None:
         """env_base: global index of board 0 of the batches this policy is handed (a shard of a larger batch passes
@@ -35,15 +35,12 @@ class GreedyGobbletPolicy(_ReferenceAdapters):
         self.depth = depth
         self.seed = int(seed or 0)
         self.env_base = int(env_base)
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         self._lib = nat.lib_for(self.device)  # ("cpu": the host flavour of the ABI, asked for -- never a fallback)
         self.prev_actions = None  # int8 (N, 2, 3) on device: last three own actions per agent, -1 = none
         self._calls, self._calls_dev = 0, None  # call index (keys the fallback draw); see device_calls()
         # outputs of the last call (device tensors): chosen-or--1, candidate set, fallback flag
         self.last_chosen = self.last_candidates = self.last_fallback = None
-
-    def _stream(self):
-        return nat.current_stream(self.device)
 
     def _ensure(self, n):
         if self.prev_actions is None or self.prev_actions.shape[0] != n:
@@ -61,12 +58,14 @@ class GreedyGobbletPolicy(_ReferenceAdapters):
         elif not enable and self._calls_dev is not None:
             self._calls, self._calls_dev = self._calls + int(self._calls_dev.item()), None
 
+    @_launches
     def advance_calls(self) -> None:
         if self._calls_dev is not None and self._calls:
             nat.check(self._lib.gbl_counter_add(self._calls_dev.data_ptr(), self._calls, self._stream()),
                       "gbl_counter_add")
             self._calls = 0
 
+    @_launches
     def compute_actions(self, obs, mask=None) -> torch.Tensor:
         """obs: int8 (N,3,3,13); mask: int8 (N,54) or None (derive the legal mask from the board)."""
         obs = torch.as_tensor(obs).to(device=self.device, dtype=torch.int8).reshape(-1, 3, 3, 13).contiguous()
@@ -79,6 +78,7 @@ class GreedyGobbletPolicy(_ReferenceAdapters):
                   "gbl_decode_obs")  # greedy_policy.py:43-71
         return self.compute_actions_from_state(state, who, mask)
 
+    @_launches
     def compute_actions_from_state(self, state: torch.Tensor, to_move: torch.Tensor, mask=None) -> torch.Tensor:
         """The same decision from ``squares`` (N,27) + ``to_move`` (N,) directly (no observation round trip)."""
         n = state.shape[0]

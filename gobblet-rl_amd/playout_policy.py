@@ -31,7 +31,7 @@ class MonteCarloGobbletPolicy(_SearchPolicy):
         self.playouts, self.max_plies = int(playouts), int(max_plies)
         self.seed = int(seed or 0)
         self.env_base = int(env_base)
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         self._lib = nat.lib_for(self.device)  # ("cpu": the host flavour of the ABI, asked for -- never a fallback)
         self._calls = 0  # call index (keys the playouts' draws); +1 per call
         # outputs of the last call (tensors on the device): int32 (N, 54) wins / losses of the mover, int32 (N,) plies played

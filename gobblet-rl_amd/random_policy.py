@@ -7,12 +7,13 @@ from __future__ import annotations
 import torch
 
 from . import _native as nat
+from ._policy_base import _launches, _OnDevice
 
 
-class RandomAdmissiblePolicy:
+class RandomAdmissiblePolicy(_OnDevice):
     def __init__(self, seed: int = 0, device="cuda:0", env_base: int = 0):
         self.seed, self.env_base = int(seed), int(env_base)
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         self._lib = nat.lib_for(self.device)  # ("cpu": the host flavour of the ABI, asked for -- never a fallback)
         self._calls, self._calls_dev = 0, None
 
@@ -24,12 +25,14 @@ class RandomAdmissiblePolicy:
         elif not enable and self._calls_dev is not None:
             self._calls, self._calls_dev = self._calls + int(self._calls_dev.item()), None
 
+    @_launches
     def advance_calls(self) -> None:
         if self._calls_dev is not None and self._calls:
-            nat.check(self._lib.gbl_counter_add(self._calls_dev.data_ptr(), self._calls,
-                                                nat.current_stream(self.device)), "gbl_counter_add")
+            nat.check(self._lib.gbl_counter_add(self._calls_dev.data_ptr(), self._calls, self._stream()),
+                      "gbl_counter_add")
             self._calls = 0
 
+    @_launches
     def compute_actions(self, obs_batch, **kwargs) -> torch.Tensor:
         """obs_batch: {"action_mask": (N,54) int8, ...} (RLlib-style) or the mask tensor itself -> int32 (N,)."""
         mask = obs_batch["action_mask"] if isinstance(obs_batch, dict) else obs_batch
@@ -37,6 +40,6 @@ class RandomAdmissiblePolicy:
         n = mask.shape[0]
         out = torch.empty(n, dtype=torch.int32, device=self.device)
         nat.check(self._lib.gbl_sample_at(mask.data_ptr(), out.data_ptr(), n, self.seed, self.env_base, self._calls,
-                                          nat.ptr(self._calls_dev), nat.current_stream(self.device)), "gbl_sample")
+                                          nat.ptr(self._calls_dev), self._stream()), "gbl_sample")
         self._calls += 1
         return out

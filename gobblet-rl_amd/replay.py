@@ -33,7 +33,7 @@ class ReplayBuffer(_OnDevice):
         capacity = int(capacity)
         if not 1 <= capacity <= MAX_CAPACITY:
             raise ValueError("capacity must be in [1, 2^31 - 1]")
-        self.capacity, self.device, self.observations = capacity, torch.device(device), bool(observations)
+        self.capacity, self.device, self.observations = capacity, nat.device(device), bool(observations)
         self._lib = nat.lib_for(self.device)
         dev = self.device
         self._obs = _lines(capacity * nat.REPLAY_OBS_PITCH, dev).view(torch.int8).view(capacity, nat.REPLAY_OBS_PITCH) if observations else None
@@ -259,7 +259,7 @@ class ReplayBuffer(_OnDevice):
         (live rows,) in slot order, when asked.  Reads ``total`` from the device."""
         if self._obs is None:
             raise ValueError("relabel needs a buffer with observations")
-        if tb.device != self.device:
+        if nat.device(tb.device) != self.device:
             raise ValueError("relabel: the table lives on %s and the buffer on %s" % (tb.device, self.device))
         return tb._targets(self.size, self._obs.data_ptr(), nat.REPLAY_OBS_PITCH, self._meta.data_ptr(), nat.REPLAY_META_PITCH,
                            self._visits.data_ptr(), nat.REPLAY_VISITS_PITCH, self._meta.data_ptr() + nat.REPLAY_META_Z, nat.REPLAY_META_PITCH,
@@ -281,7 +281,7 @@ class ReplayBuffer(_OnDevice):
         if self._obs is None:
             raise ValueError("reanalyse needs a buffer with observations")
         rule = None if gumbel is None else gumbel_args(gumbel)
-        if torch.device(evaluator.device) != self.device:
+        if nat.device(evaluator.device) != self.device:
             raise ValueError("reanalyse: the evaluator lives on %s and the buffer on %s" % (evaluator.device, self.device))
         if prioritize is not None:
             self._need_priorities("reanalyse(prioritize=...)")
@@ -324,7 +324,7 @@ class ReplayBuffer(_OnDevice):
         because the search commutes with the symmetries -- with ``gbl_symmetry_apply``'s caveat: check_for_winner's last-line-decides
         rule is not symmetric on boards where a move leaves lines of both colours, so under the squares' symmetries a search that
         reaches such a board may differ from the image of the stored row's search (``symmetries=None`` avoids it)."""
-        if torch.device(trainer.device) != self.device:
+        if nat.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the buffer on %s" % (trainer.device, self.device))
         if (beta is not None or priority is not None) and not prioritized:
             raise ValueError("fit: beta= and priority= need prioritized=True")
@@ -335,7 +335,7 @@ class ReplayBuffer(_OnDevice):
             if unknown or "evaluator" not in reanalyse or ("seed" in reanalyse and reanalyse.get("gumbel") is None):
                 raise ValueError("fit: reanalyse=dict(evaluator=, iterations=64, explore=16, gumbel=None, seed=0) (seed goes with gumbel)")
             rule = None if reanalyse.get("gumbel") is None else gumbel_args(reanalyse["gumbel"])
-            if torch.device(reanalyse["evaluator"].device) != self.device:
+            if nat.device(reanalyse["evaluator"].device) != self.device:
                 raise ValueError("fit: the evaluator lives on %s and the buffer on %s" % (reanalyse["evaluator"].device, self.device))
             fresh = torch.zeros((int(batch), nat.ACTIONS), dtype=torch.int16, device=self.device)  # (reused: a skipped row counts for nothing)
 

@@ -29,8 +29,8 @@ class SolverGobbletPolicy(_SearchPolicy):
         if not 1 <= int(depth) <= nat.SOLVE_MAX_DEPTH:
             raise ValueError(f"depth must be in [1, {nat.SOLVE_MAX_DEPTH}]")
         self.depth = int(depth)
-        self.device = torch.device(device)
-        if fallback is not None and torch.device(fallback.device) != self.device:
+        self.device = nat.device(device)
+        if fallback is not None and nat.device(fallback.device) != self.device:
             raise ValueError("the fallback policy must live on the solver's device")
         self.fallback = fallback
         self._lib = nat.lib_for(self.device)  # ("cpu": the host flavour of the ABI, asked for -- never a fallback)

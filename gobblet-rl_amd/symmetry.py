@@ -90,7 +90,7 @@ def apply(sym, agent=None, state=None, observation=None, action_mask=None, visit
     if not given:
         raise ValueError("apply: no rows given")
     first = next(iter(given.values()))[0]
-    device, n = first.device, first.shape[0]
+    device, n = nat.device(first.device), first.shape[0]
     ins = {}
     for k, (t, dtype, tail) in given.items():
         if k == "observation":

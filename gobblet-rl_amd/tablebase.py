@@ -24,7 +24,7 @@ class Tablebase(_OnDevice):
         inventory = tuple(int(c) for c in inventory)
         if len(inventory) != 3 or not all(0 <= c <= 2 for c in inventory):
             raise ValueError("inventory: three piece counts, each in [0, 2]")
-        self.inventory, self.device = inventory, torch.device(device)
+        self.inventory, self.device = inventory, nat.device(device)
         self._lib = nat.lib_for(self.device)
         self._inv = (nat.C.c_int32 * 3)(*inventory)
         layout = (nat.C.c_int64 * 5)()
@@ -217,7 +217,7 @@ class TablebaseGobbletPolicy(_SearchPolicy):
         fallback: a policy of this package on the table's device that decides among the 0 actions of a root whose value is 0 (the
         table by itself plays the lowest of them)."""
         self.tb, self.device, self._lib = tb, tb.device, tb._lib
-        if fallback is not None and torch.device(fallback.device) != self.device:
+        if fallback is not None and nat.device(fallback.device) != self.device:
             raise ValueError("the fallback policy must live on the table's device")
         self.fallback = fallback
         self.last_outcomes = self.last_value = self.last_action = None

@@ -29,7 +29,7 @@ class GobbletTrainer(_OnDevice):
         with L2 weight decay."""
         if hidden not in HIDDEN_SIZES:
             raise ValueError("hidden must be 64, 128, 192 or 256")
-        self.hidden, self.device = int(hidden), torch.device(device)
+        self.hidden, self.device = int(hidden), nat.device(device)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.weight_decay, self.value_reg = float(weight_decay), float(value_reg)
         self._lib = nat.lib_for(self.device)

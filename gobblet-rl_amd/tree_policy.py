@@ -34,7 +34,7 @@ class TreeSearchGobbletPolicy(_TreeSearchPolicy):
         self._games_per_visit = self.playouts  # (a leaf is `playouts` games)
         self.seed = int(seed or 0)
         self.env_base = int(env_base)
-        self.device = torch.device(device)
+        self.device = nat.device(device)
         self._lib = nat.lib_for(self.device)  # ("cpu": the host flavour of the ABI, asked for -- never a fallback)
         self._calls = 0  # call index (keys the search's draws); +1 per call
         # outputs of the last call (tensors on the device): int32 (N, 54) visits / wins / losses of the root's children from the

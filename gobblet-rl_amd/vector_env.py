@@ -17,17 +17,16 @@ Tensors (attributes, all on ``device``)
 """
 from __future__ import annotations
 
-import contextlib
-
 import torch
 
 from . import _native as nat
 from . import _selfplay
 from . import placement as _placement
+from ._policy_base import _launches, _OnDevice
 from .board import BatchedBoard, _as_i32
 
 
-class BatchedGobblet:
+class BatchedGobblet(_OnDevice):
     SLOT_PAD_BOARDS = 0  # see trajectory_buffers
     STAGING_SETS = 2     # collect()'s own buffer sets kept at most (least recently used dropped first)
 
@@ -109,6 +108,7 @@ class BatchedGobblet:
         elif not enable and self._ply_dev is not None:
             self._ply, self._ply_dev = self.ply, None
 
+    @_launches
     def advance_ply(self) -> None:
         if self._ply_dev is not None and self._ply:
             nat.check(self._lib.gbl_counter_add(self._ply_dev.data_ptr(), self._ply, self._stream()), "gbl_counter_add")
@@ -120,10 +120,8 @@ class BatchedGobblet:
         ``rollout(..., count=True)`` calls."""
         return self._counters.sum(0)[:4]
 
-    def _stream(self):
-        return nat.current_stream(self.device)
-
     # -- gobblet.py:275-290 --------------------------------------------------------------------------
+    @_launches
     def reset(self, seed=None, options=None):
         """All boards empty, player_1 to move.  Like the reference, ``seed`` does not affect the
         (deterministic) environment; if given it re-keys the action sampler."""
@@ -141,6 +139,7 @@ class BatchedGobblet:
         self.refresh()
         return self.observe()
 
+    @_launches
     def refresh(self):
         """Recompute action_mask / observation from squares + to_move (after assigning state)."""
         n = self.num_envs
@@ -226,6 +225,7 @@ class BatchedGobblet:
             raise ValueError("%s: a contiguous int32 (N,) tensor on the environment's device" % name)
         return t
 
+    @_launches
     def step(self, actions, status=None, next_actions=None):
         """Apply ``actions`` (int (N,)) for the agents to move.  Returns
         (obs dict, rewards (N,2), done (N,), winner (N,)) -- views of the attribute tensors.
@@ -391,6 +391,7 @@ class BatchedGobblet:
         v = out[key][:, T - 1]  # (tiles, 64, ...)
         return v.reshape((v.shape[0] * 64,) + tuple(v.shape[2:]))[:n]
 
+    @_launches
     def collect(self, plies: int, out: dict | None = None, count: bool = False, refresh: bool = True,
                 layout: str = "time", policies=None, opening_plies: int = 0, first_actions=None, first_status=None,
                 search: dict | None = None) -> dict:
@@ -588,6 +589,7 @@ class BatchedGobblet:
             self.observation.copy_(self._last_ply(out, "observation"))
         return out
 
+    @_launches
     def outcome_targets(self, traj: dict) -> dict:
         """Adds "z" (int8: the reward, at the end of the game a ply belongs to, of the agent who played it; ``nat.Z_OPEN`` = -128
         where the game does not end inside the window) and "plies_left" (int16: plies until that end, -1 likewise) to a
@@ -618,7 +620,7 @@ class BatchedGobblet:
         out = {"outcome": torch.empty((n, nat.ACTIONS), dtype=torch.int8, device=self.device),
                "value": torch.empty(n, dtype=torch.int8, device=self.device),
                "action": torch.empty(n, dtype=torch.int32, device=self.device)}
-        with torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext():  # (whichever device is current)
+        with self._on_device():
             nat.check(self._lib.gbl_solve(self.squares.data_ptr(), self.to_move.data_ptr(), None, depth, out["outcome"].data_ptr(),
                                           out["value"].data_ptr(), out["action"].data_ptr(), n, self._stream()), "gbl_solve")
         return out
@@ -626,7 +628,7 @@ class BatchedGobblet:
     def tablebase(self, tb) -> dict:
         """The true verdict on the current boards from a ``Tablebase`` on this device (one launch of ``gbl_tb_probe``): ``solve``'s dict
         without a depth bound -- on a complete table 0 is a draw.  The boards are not touched."""
-        if tb.device != self.device:
+        if nat.device(tb.device) != self.device:
             raise ValueError("tablebase: the table lives on %s and the boards on %s" % (tb.device, self.device))
         return tb.probe(self.squares, self.to_move)
 
@@ -666,7 +668,7 @@ class BatchedGobblet:
         elif set(out) != set(spec) or any(tuple(out[k].shape) != shape or out[k].dtype != dtype or out[k].device != dev
                                           or not out[k].is_contiguous() for k, (shape, dtype) in spec.items()):
             raise ValueError("out: the dict of an earlier training_batch call of this batch size on this window's device")
-        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():  # (whichever device is current)
+        with self._on_device():
             nat.check(self._lib.gbl_training_batch(
                 nat.ptr(f.get("observation")), f["action_mask"].data_ptr(), f["visits"].data_ptr(), f["z"].data_ptr(),
                 f["done"].data_ptr(), f["mover"].data_ptr(), self.num_envs, traj["_plies"], traj["_ply_stride"], traj["_tile_stride"],
@@ -682,7 +684,7 @@ class BatchedGobblet:
         maximum), nothing crosses to the host.  ``targets``: a ``Tablebase`` on this device -- every drawn batch goes through
         ``targets.targets`` first (one more launch per step: the fit learns from the exact labels).  Returns the steps'
         statistics, float32 (steps, 4) on the device (see ``GobbletTrainer.step``)."""
-        if torch.device(trainer.device) != self.device:
+        if nat.device(trainer.device) != self.device:
             raise ValueError("fit: the trainer lives on %s and the environment on %s" % (trainer.device, self.device))
         buf, stats = None, []
         for i in range(int(steps)):
@@ -733,6 +735,7 @@ class BatchedGobblet:
         out["_placement"] = rec
         return rec
 
+    @_launches
     def step_into(self, actions, out: dict, t: int, status=None, next_actions=None):
         """``step(actions)`` with this ply's outputs written straight into slot ``t`` of time-major trajectory buffers
         (``trajectory_buffers``) -- the collector loop of a policy that lives outside the library (the reference's
@@ -765,6 +768,7 @@ class BatchedGobblet:
         return (out["observation"][t] if obs_t is not None else None), out["action_mask"][t]
 
     # -- masked-uniform sampling (examples/example_basic.py:58-61) ----------------------------------------
+    @_launches
     def sample_actions(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """One uniformly random legal action per board from the current action_mask, keyed by
         (seed, env_base + b, ply)."""
@@ -774,6 +778,7 @@ class BatchedGobblet:
                   "gbl_sample")
         return out
 
+    @_launches
     def rollout(self, plies: int = 1, count: bool = False):
         """``plies`` masked-random plies with auto-reset in ONE kernel launch (sample + step fused;
         the boards stay in registers between plies).  The attribute tensors hold the outputs of

@@ -13,6 +13,12 @@
  *   - the gbl_cpu_tb_* entry points take `aux`, `table` and `decided` in host memory;
  *   - gbl_cpu_replay_append checks its workspace like the device flavour and does not use it; ring_state is host memory;
  *   - gbl_cpu_set_threads(t): boards are dealt over t std::threads (0 = the hardware's; the library reads no environment).
+ * Threading and devices (gobblet_hip.h has the same paragraph): the library is re-entrant and holds no global state but the one number
+ * gbl_cpu_set_threads stores, which is read once per call and changes how many workers a call starts, never a result; any number of
+ * host threads may call at the same time, each on buffers of its own.  The error text is per thread: gbl_cpu_last_error() returns what
+ * the CALLING thread's last failing call left, "" on a thread that has had none.  There is no device to make current and no stream: a
+ * call has finished when it returns.  One object of a caller (boards, a ring and its workspace, a network and its moments) must not be
+ * driven from two threads at once.  tests/test_host_threads.py runs two workloads from two threads against the serial run.
  * It is a flavour a caller ASKS for (device="cpu" in the Python layer; BASELINE config 1 "on CPU"), never a fallback of the HIP
  * path, and it is test-independent of oracle/: tests/test_cpu_twin.py compares it with the oracle like the GPU tests do. */
 #ifndef GOBBLET_CPU_H

@@ -26,6 +26,26 @@
  *     action (handled per `illegal_mode`) and is flagged in the status byte of
  *     gbl_step_ex / gbl_collect_from_ex (GBL_STATUS_OUT_OF_RANGE).
  *
+ * Threading and devices
+ *   - The library is re-entrant and holds no global state: any number of host
+ *     threads may call any entry points at the same time, each on buffers and
+ *     a stream of its own.  The error text is per thread: gbl_last_error()
+ *     returns what the CALLING thread's last failing call left, "" on a
+ *     thread that has had none.
+ *   - A call lands on the device that owns `stream` (NULL: the current
+ *     device's default stream), and every launch and memset of a call --
+ *     the multi-launch entry points included -- goes to that one stream, so
+ *     any call can be captured into a hipGraph.  The CALLER makes that
+ *     device current (hipSetDevice) before the call; the pointers must be
+ *     that device's memory.  The Python classes do this themselves: an
+ *     object launches on its own device whichever device is current, on the
+ *     calling thread's current stream of that device.
+ *   - One OBJECT of a caller -- a set of boards, a replay ring with its
+ *     workspace, a network with its moments, a trainer's or a collector's
+ *     staging buffers -- must not be driven from two threads at once: the
+ *     calls are independent, the memory they are handed is not.
+ *   (tests/test_host_threads.py, tests/test_gpu_devices_threads.py)
+ *
  * Data layout in HBM (env-major, int8)
  *   state   int8 [n][27]      Board.squares per board: squares[9*level + pos]
  *                             (board.py:6-33); 0 empty, +piece player_1,
