@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(CSRC, "libgobblet_hip.so")
 _FOREIGN = False  # use_library() was called: LIB_PATH is somebody's own build, never rebuilt from here
 SOURCES = [os.path.join(CSRC, "gobblet_hip.hip"), os.path.join(CSRC, "gobblet_device.h"), os.path.join(CSRC, "gobblet_diag.h"),
            os.path.join(CSRC, "gobblet_knobs.h"), os.path.join(CSRC, "gobblet_selfplay_entries.inc"),
-           os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
+           os.path.join(CSRC, "gobblet_env_entries.inc"), os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
 # -amdgpu-kernarg-preload-count: the first 16 dwords of a kernel's arguments arrive in SGPRs with the wave
 # launch (the kernels order their arguments for that), so a wavefront's first loads do not wait for a
 # kernel-argument fetch; firmware without the feature runs the compiler's fallback prologue
@@ -334,8 +334,8 @@ def current_stream(device):
 # path: a "cuda" device without the HIP library still raises.  Built with g++ from the same device header.
 CPU_LIB_PATH = os.path.join(CSRC, "libgobblet_cpu.so")
 CPU_SOURCES = [os.path.join(CSRC, "gobblet_cpu.cpp"), os.path.join(CSRC, "gobblet_device.h"), os.path.join(CSRC, "gobblet_knobs.h"),
-               os.path.join(CSRC, "gobblet_selfplay_entries.inc"), os.path.join(_HERE, "..", "include", "gobblet_cpu.h"),
-               os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
+               os.path.join(CSRC, "gobblet_selfplay_entries.inc"), os.path.join(CSRC, "gobblet_env_entries.inc"),
+               os.path.join(_HERE, "..", "include", "gobblet_cpu.h"), os.path.join(_HERE, "..", "include", "gobblet_hip.h")]
 # -ffp-contract=off: gbl_cpu_train_step's float rule is single IEEE operations (include/gobblet_hip.h); everything else here is integer code
 CPU_CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"] + \
                 (["-mpopcnt"] if platform.machine() in ("x86_64", "AMD64") else [])

@@ -151,16 +151,6 @@ inline uint32_t hist_prev3(const int8_t *hist, int64_t b, int me)
 
 }  // namespace
 
-#define GBL_CHECK_N(n)                                      \
-    do {                                                    \
-        if ((n) < 0) return fail(GBL_ERR_ARG, "n < 0");     \
-        if ((n) == 0) return GBL_OK;                        \
-    } while (0)
-#define GBL_NEED(p, name)                                                 \
-    do {                                                                  \
-        if (!(p)) return fail(GBL_ERR_ARG, name " must not be NULL");     \
-    } while (0)
-
 extern "C" {
 
 const char *gbl_cpu_last_error(void) { return g_err; }
@@ -181,8 +171,8 @@ int gbl_cpu_layout_info(int32_t out[6])
 
 int gbl_cpu_reset(int8_t *state, int8_t *to_move, int8_t *done, int8_t *winner, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (const char *why = reset_error(n, state, to_move, done)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     memset(state, 0, (size_t)n * kCells);
     memset(to_move, 0, (size_t)n);
     memset(done, 0, (size_t)n);
@@ -192,8 +182,8 @@ int gbl_cpu_reset(int8_t *state, int8_t *to_move, int8_t *done, int8_t *winner, 
 
 int gbl_cpu_legal_mask(const int8_t *state, const int8_t *to_move, int8_t *mask, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(mask, "mask");
+    if (const char *why = legal_mask_error(n, state, to_move, mask)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) {
             uint32_t r[7];
@@ -206,8 +196,8 @@ int gbl_cpu_legal_mask(const int8_t *state, const int8_t *to_move, int8_t *mask,
 
 int gbl_cpu_is_legal(const int8_t *state, const int8_t *agent_index, const int32_t *actions, int8_t *out, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(agent_index, "agent_index"); GBL_NEED(actions, "actions"); GBL_NEED(out, "out");
+    if (const char *why = is_legal_error(n, state, agent_index, actions, out)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7];
         load_row(state, b, r);
@@ -220,8 +210,8 @@ int gbl_cpu_is_legal(const int8_t *state, const int8_t *agent_index, const int32
 
 int gbl_cpu_play_turn(int8_t *state, const int8_t *agent_index, const int32_t *actions, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(agent_index, "agent_index"); GBL_NEED(actions, "actions");
+    if (const char *why = play_turn_error(n, state, agent_index, actions)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7];
         load_row(state, b, r);
@@ -238,8 +228,8 @@ int gbl_cpu_play_turn(int8_t *state, const int8_t *agent_index, const int32_t *a
 
 int gbl_cpu_winner(const int8_t *state, int8_t *winner, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(winner, "winner");
+    if (const char *why = winner_error(n, state, winner)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7];
         load_row(state, b, r);
@@ -250,8 +240,8 @@ int gbl_cpu_winner(const int8_t *state, int8_t *winner, int64_t n, void *)
 
 int gbl_cpu_flatboard(const int8_t *state, int8_t *flat, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(flat, "flat");
+    if (const char *why = flatboard_error(n, state, flat)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7], d[3];
         load_row(state, b, r);
@@ -263,8 +253,8 @@ int gbl_cpu_flatboard(const int8_t *state, int8_t *flat, int64_t n, void *)
 
 int gbl_cpu_covered(const int8_t *state, int8_t *cov, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(cov, "cov");
+    if (const char *why = covered_error(n, state, cov)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7], d[7];
         load_row(state, b, r);
@@ -276,8 +266,8 @@ int gbl_cpu_covered(const int8_t *state, int8_t *cov, int64_t n, void *)
 
 int gbl_cpu_validate(const int8_t *state, int8_t *flags, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(flags, "flags");
+    if (const char *why = validate_error(n, state, flags)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7];
         load_row(state, b, r);
@@ -288,10 +278,8 @@ int gbl_cpu_validate(const int8_t *state, int8_t *flags, int64_t n, void *)
 
 int gbl_cpu_observe(const int8_t *state, const int8_t *to_move, int agent_sel, int8_t *obs, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(obs, "obs");
-    if (agent_sel < -1 || agent_sel > 1) return fail(GBL_ERR_ARG, "agent_sel must be -1, 0 or 1");
-    if (agent_sel < 0) GBL_NEED(to_move, "to_move (agent_sel == -1)");
+    if (const char *why = observe_error(n, state, to_move, agent_sel, obs)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) {
             uint32_t r[7];
@@ -305,9 +293,8 @@ int gbl_cpu_observe(const int8_t *state, const int8_t *to_move, int agent_sel, i
 
 int gbl_cpu_board_eval(int8_t *state, const int8_t *agent_index, const int32_t *actions, int8_t *record_out, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(record_out, "record_out");
-    if (actions) GBL_NEED(agent_index, "agent_index (with actions)");
+    if (const char *why = board_eval_error(n, state, agent_index, actions, record_out)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t r[7];
         load_row(state, b, r);
@@ -340,10 +327,8 @@ int gbl_cpu_step_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t 
                     int8_t *status_out, int32_t *next_actions_out, uint64_t seed, uint64_t env_base, uint32_t ply,
                     const uint32_t *ply_dev, int64_t n, int illegal_mode, int auto_reset, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done"); GBL_NEED(actions, "actions");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
+    if (const char *why = step_error(n, state, to_move, done, actions, illegal_mode)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     auto_reset = auto_reset != 0;
     if (ply_dev) ply += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
@@ -374,26 +359,11 @@ int gbl_cpu_step_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t 
     return GBL_OK;
 }
 
-int gbl_cpu_step_into(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *actions, int8_t *winner_out, int8_t *reward_out,
-                      int8_t *mask_out, int8_t *obs_out, int32_t *turn, int32_t *actions_out, int8_t *done_out,
-                      int8_t *to_move_out, int64_t n, int illegal_mode, int auto_reset, void *stream)
-{
-    return gbl_cpu_step_ex(state, to_move, done, actions, winner_out, reward_out, mask_out, obs_out, turn, actions_out, done_out,
-                           to_move_out, nullptr, nullptr, 0, 0, 0, nullptr, n, illegal_mode, auto_reset, stream);
-}
-
-int gbl_cpu_step(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *actions, int8_t *winner_out, int8_t *reward_out,
-                 int8_t *mask_out, int8_t *obs_out, int32_t *turn, int64_t n, int illegal_mode, int auto_reset, void *stream)
-{
-    return gbl_cpu_step_ex(state, to_move, done, actions, winner_out, reward_out, mask_out, obs_out, turn, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, 0, 0, 0, nullptr, n, illegal_mode, auto_reset, stream);
-}
-
 int gbl_cpu_sample_at(const int8_t *mask, int32_t *actions, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply,
                       const uint32_t *ply_dev, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(mask, "mask"); GBL_NEED(actions, "actions");
+    if (const char *why = sample_error(n, mask, actions)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     if (ply_dev) ply += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) actions[b] = sample54(read_mask(mask + b * kActions), seed, env_base + (uint64_t)b, ply);
@@ -401,14 +371,9 @@ int gbl_cpu_sample_at(const int8_t *mask, int32_t *actions, int64_t n, uint64_t 
     return GBL_OK;
 }
 
-int gbl_cpu_sample(const int8_t *mask, int32_t *actions, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply, void *stream)
-{
-    return gbl_cpu_sample_at(mask, actions, n, seed, env_base, ply, nullptr, stream);
-}
-
 int gbl_cpu_counter_add(uint32_t *counter, uint32_t by, void *)
 {
-    GBL_NEED(counter, "counter");
+    if (!counter) return fail(GBL_ERR_ARG, "counter must not be NULL");
     *counter += by;
     return GBL_OK;
 }
@@ -433,11 +398,8 @@ int gbl_cpu_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
                        int8_t *mask_out, int8_t *obs_out, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply0,
                        const uint32_t *ply_dev, uint32_t plies, int illegal_mode, int64_t *counters, int32_t *turn, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
-    if (plies == 0) return GBL_OK;
+    if (const char *why = rollout_error(n, state, to_move, done, illegal_mode)) return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
     if (ply_dev) ply0 += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         Tally tl;
@@ -471,38 +433,15 @@ int gbl_cpu_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *ac
     return GBL_OK;
 }
 
-int gbl_cpu_rollout(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_out, int8_t *winner_out, int8_t *reward_out,
-                    int8_t *mask_out, int8_t *obs_out, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply0, uint32_t plies,
-                    int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
-{
-    return gbl_cpu_rollout_at(state, to_move, done, actions_out, winner_out, reward_out, mask_out, obs_out, n, seed, env_base, ply0,
-                              nullptr, plies, illegal_mode, counters, turn, stream);
-}
-
-int gbl_cpu_collect_from(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *first_actions, int32_t *actions_traj,
-                         int8_t *winner_traj, int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
-                         int8_t *obs_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base,
-                         uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int illegal_mode, int64_t *counters, int32_t *turn,
-                         void *stream)
-{
-    return gbl_cpu_collect_from_ex(state, to_move, done, first_actions, nullptr, actions_traj, winner_traj, reward_traj, done_traj,
-                                   to_move_traj, mask_traj, obs_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies,
-                                   illegal_mode, counters, turn, stream);
-}
-
 int gbl_cpu_collect_from_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *first_actions, int8_t *first_status,
                             int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj,
                             int8_t *mask_traj, int8_t *obs_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed,
                             uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int illegal_mode,
                             int64_t *counters, int32_t *turn, void *)
 {
-    GBL_CHECK_N(n);
-    if (first_status && !first_actions) return fail(GBL_ERR_ARG, "first_status without first_actions");
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
-    if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    if (const char *why = collect_error(n, first_actions, first_status, state, to_move, done, illegal_mode, plies, ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
     if (ply_dev) ply0 += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         Tally tl;
@@ -541,20 +480,10 @@ int gbl_cpu_collect_from_ex(int8_t *state, int8_t *to_move, int8_t *done, const 
     return GBL_OK;
 }
 
-int gbl_cpu_collect(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj,
-                    int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj, int64_t n, int64_t ply_stride,
-                    int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies,
-                    int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
-{
-    return gbl_cpu_collect_from(state, to_move, done, nullptr, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj, mask_traj,
-                                obs_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies, illegal_mode, counters, turn,
-                                stream);
-}
-
 int gbl_cpu_decode_obs(const int8_t *obs, int8_t *state, int8_t *to_move, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(obs, "obs"); GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    if (const char *why = decode_obs_error(n, obs, state, to_move)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     for (int64_t b = 0; b < n; ++b) {
         uint32_t d[30], r[7];
         d[29] = 0;
@@ -600,9 +529,8 @@ static int greedy_run(const int8_t *state, const int8_t *to_move, const int8_t *
 int gbl_cpu_greedy(const int8_t *state, const int8_t *to_move, const int8_t *mask, const int8_t *hist, int depth, int32_t *action_out,
                    int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(action_out, "action_out");
-    if (depth < 1 || depth > 3) return fail(GBL_ERR_ARG, "depth must be 1, 2 or 3");
+    if (const char *why = greedy_error(n, state, to_move, action_out, depth)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     return greedy_run(state, to_move, mask, hist, depth, action_out, cand_mask_out, fallback_out, n, nullptr, nullptr, 0, 0, 0);
 }
 
@@ -610,20 +538,11 @@ int gbl_cpu_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8
                           uint64_t env_base, uint32_t call, const uint32_t *call_dev, int32_t *action_out, int32_t *chosen_out,
                           int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(hist, "hist"); GBL_NEED(action_out, "action_out");
-    if (depth < 1 || depth > 3) return fail(GBL_ERR_ARG, "depth must be 1, 2 or 3");
+    if (const char *why = greedy_act_error(n, state, to_move, hist, action_out, depth)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     if (call_dev) call += *call_dev;
     return greedy_run(state, to_move, mask, nullptr, depth, chosen_out, cand_mask_out, fallback_out, n, hist, action_out, seed, env_base,
                       call);
-}
-
-int gbl_cpu_greedy_act(const int8_t *state, const int8_t *to_move, const int8_t *mask, int8_t *hist, int depth, uint64_t seed,
-                       uint64_t env_base, uint32_t call, int32_t *action_out, int32_t *chosen_out, int8_t *cand_mask_out,
-                       int8_t *fallback_out, int64_t n, void *stream)
-{
-    return gbl_cpu_greedy_act_at(state, to_move, mask, hist, depth, seed, env_base, call, nullptr, action_out, chosen_out, cand_mask_out,
-                                 fallback_out, n, stream);
 }
 
 // Board b as the search entry points (gbl_cpu_playout_values, _tree_search, _evaluate, _tree_search_eval) take it: its planes, the
@@ -968,16 +887,10 @@ int gbl_cpu_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t 
                            uint32_t plies, int policy0, int policy1, int opening_plies, int illegal_mode, int64_t *counters,
                            int32_t *turn, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
-    if (policy0 < GBL_POLICY_RANDOM || policy0 > GBL_POLICY_GREEDY3 || policy1 < GBL_POLICY_RANDOM || policy1 > GBL_POLICY_GREEDY3)
-        return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM, GBL_POLICY_GREEDY1, _GREEDY2 or _GREEDY3");
-    if (opening_plies < 0) return fail(GBL_ERR_ARG, "opening_plies < 0");
-    if (opening_plies > 0 && !turn) return fail(GBL_ERR_ARG, "opening_plies > 0 needs the per-board turn counter (turn must not be NULL)");
-    if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    if (const char *why = collect_policy_error(n, state, to_move, done, illegal_mode, policy0, policy1, opening_plies, turn != nullptr, plies,
+                                                 ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
     if (ply_dev) ply0 += *ply_dev;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         Tally tl;
@@ -1253,20 +1166,19 @@ static int host_selfplay_run(const SelfplayCall<gbl_evaluator> &c)
 }
 
 // the nine entry points themselves: one text for both flavours (the host flavour's calls are synchronous: `stream` is not read)
-#define GBL_SELFPLAY_SYMBOL(fn) gbl_cpu_##fn
+#define GBL_SYMBOL(fn) gbl_cpu_##fn
 #define GBL_SELFPLAY_RUN(name, call, stream) ((void)(stream), host_selfplay_run(call))
 #include "gobblet_selfplay_entries.inc"
-#undef GBL_SELFPLAY_SYMBOL
+#include "gobblet_env_entries.inc"  // (gbl_cpu_step, _step_into, _sample, _rollout, _collect, _collect_from, _greedy_act: they only forward)
+#undef GBL_SYMBOL
 #undef GBL_SELFPLAY_RUN
 
 int gbl_cpu_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
                             int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(done_traj, "done_traj"); GBL_NEED(reward_traj, "reward_traj"); GBL_NEED(mover_traj, "mover_traj"); GBL_NEED(z_traj, "z_traj");
-    if (plies > 32767u) return fail(GBL_ERR_ARG, "plies must not exceed 32767");
-    if (plies == 0) return GBL_OK;
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    if (const char *why = outcome_targets_error(n, done_traj, reward_traj, mover_traj, z_traj, plies, ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
     parallel_for(n, [=](int64_t b0, int64_t b1) {
         for (int64_t b = b0; b < b1; ++b) {
             int r0 = 0, r1 = 0, left = -1;  // the rewards of the nearest game end at or after t, and how far it is

@@ -2949,6 +2949,107 @@ inline const char *tree_search_gumbel_error(const Ev *ev, int iterations, int ex
     return tree_search_eval_error(ev, iterations, explore, n, state, to_move);
 }
 
+// The (ply, tile) cells of 64 boards of a trajectory must start 16-byte aligned and must not overlap.
+inline bool strides_ok(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
+{
+    const int64_t tiles = (n + kTile - 1) / kTile;
+    const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
+    const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
+    const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
+    return aligned && (time_major || tile_major);
+}
+constexpr const char *kStridesMessage = "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart";
+
+// ---- argument checks of the env, collect and greedy entry points (gbl_reset ... gbl_greedy_act_at): host code, for both flavours ------
+// One *_error per entry point that checks anything (gbl_step, _step_into, _sample, _rollout, _collect, _collect_from and _greedy_act
+// forward: gobblet_env_entries.inc): every rule BOTH flavours have, in the order they report it, every one a GBL_ERR_ARG.  n == 0 (and,
+// where there are plies, plies == 0 once the rules in front of it hold) passes whatever comes after it: the caller returns GBL_OK
+// before using anything.  The device flavour's alignment rules follow there, after these.  tests/golden/env_arg_errors.json
+// (scripts/record_env_arg_errors.py) pins every rule alone, every adjacent pair and the early returns, on both flavours.
+#define GBL_N(n) if ((n) <= 0) return (n) < 0 ? "n < 0" : nullptr
+#define GBL_PTR(p) if (!(p)) return #p " must not be NULL"  // (the parameter bears the ABI's name)
+inline const char *reset_error(int64_t n, const void *state, const void *to_move, const void *done) { GBL_N(n); GBL_PTR(state); GBL_PTR(to_move); GBL_PTR(done); return nullptr; }
+inline const char *legal_mask_error(int64_t n, const void *state, const void *to_move, const void *mask) { GBL_N(n); GBL_PTR(state); GBL_PTR(to_move); GBL_PTR(mask); return nullptr; }
+inline const char *is_legal_error(int64_t n, const void *state, const void *agent_index, const void *actions, const void *out) { GBL_N(n); GBL_PTR(state); GBL_PTR(agent_index); GBL_PTR(actions); GBL_PTR(out); return nullptr; }
+inline const char *play_turn_error(int64_t n, const void *state, const void *agent_index, const void *actions) { GBL_N(n); GBL_PTR(state); GBL_PTR(agent_index); GBL_PTR(actions); return nullptr; }
+inline const char *winner_error(int64_t n, const void *state, const void *winner) { GBL_N(n); GBL_PTR(state); GBL_PTR(winner); return nullptr; }
+inline const char *flatboard_error(int64_t n, const void *state, const void *flat) { GBL_N(n); GBL_PTR(state); GBL_PTR(flat); return nullptr; }
+inline const char *covered_error(int64_t n, const void *state, const void *cov) { GBL_N(n); GBL_PTR(state); GBL_PTR(cov); return nullptr; }
+inline const char *validate_error(int64_t n, const void *state, const void *flags) { GBL_N(n); GBL_PTR(state); GBL_PTR(flags); return nullptr; }
+inline const char *sample_error(int64_t n, const void *mask, const void *actions) { GBL_N(n); GBL_PTR(mask); GBL_PTR(actions); return nullptr; }
+inline const char *decode_obs_error(int64_t n, const void *obs, const void *state, const void *to_move) { GBL_N(n); GBL_PTR(obs); GBL_PTR(state); GBL_PTR(to_move); return nullptr; }
+
+inline const char *observe_error(int64_t n, const void *state, const void *to_move, int agent_sel, const void *obs)
+{
+    GBL_N(n); GBL_PTR(state); GBL_PTR(obs);
+    if (agent_sel < -1 || agent_sel > 1) return "agent_sel must be -1, 0 or 1";
+    return agent_sel < 0 && !to_move ? "to_move (agent_sel == -1) must not be NULL" : nullptr;
+}
+
+inline const char *board_eval_error(int64_t n, const void *state, const void *agent_index, const void *actions, const void *record_out)
+{
+    GBL_N(n); GBL_PTR(state); GBL_PTR(record_out);
+    return actions && !agent_index ? "agent_index (with actions) must not be NULL" : nullptr;
+}
+
+// the boards a ply is played on, and how an illegal action is taken: gbl_step_ex (which needs its actions), gbl_rollout_at and, in
+// collect_error / collect_policy_error, the collectors
+inline const char *step_error(int64_t n, const void *state, const void *to_move, const void *done, const void *actions, int illegal_mode)
+{
+    GBL_N(n); GBL_PTR(state); GBL_PTR(to_move); GBL_PTR(done); GBL_PTR(actions);
+    return illegal_mode_error(illegal_mode);
+}
+
+inline const char *rollout_error(int64_t n, const void *state, const void *to_move, const void *done, int illegal_mode)
+{
+    GBL_N(n); GBL_PTR(state); GBL_PTR(to_move); GBL_PTR(done);
+    return illegal_mode_error(illegal_mode);
+}
+
+// (the device flavour looks at first_actions' alignment in front of these)
+inline const char *collect_error(int64_t n, const void *first_actions, const void *first_status, const void *state, const void *to_move,
+                                 const void *done, int illegal_mode, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
+{
+    GBL_N(n);
+    if (first_status && !first_actions) return "first_status without first_actions";
+    if (const char *why = rollout_error(n, state, to_move, done, illegal_mode)) return why;
+    return plies == 0 || strides_ok(n, plies, ply_stride, tile_stride) ? nullptr : kStridesMessage;
+}
+
+inline const char *collect_policy_error(int64_t n, const void *state, const void *to_move, const void *done, int illegal_mode, int policy0,
+                                        int policy1, int opening_plies, bool has_turn, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
+{
+    if (const char *why = rollout_error(n, state, to_move, done, illegal_mode)) return why;
+    if (n == 0) return nullptr;
+    if (policy0 < 0 || policy0 > 3 || policy1 < 0 || policy1 > 3) return "policy0 / policy1: GBL_POLICY_RANDOM, GBL_POLICY_GREEDY1, _GREEDY2 or _GREEDY3";
+    if (opening_plies < 0) return "opening_plies < 0";
+    if (opening_plies > 0 && !has_turn) return "opening_plies > 0 needs the per-board turn counter (turn must not be NULL)";
+    return plies == 0 || strides_ok(n, plies, ply_stride, tile_stride) ? nullptr : kStridesMessage;
+}
+
+// gbl_greedy, and gbl_greedy_act_at, which also needs the history it appends to
+inline const char *greedy_error(int64_t n, const void *state, const void *to_move, const void *action_out, int depth)
+{
+    GBL_N(n); GBL_PTR(state); GBL_PTR(to_move); GBL_PTR(action_out);
+    return depth < 1 || depth > 3 ? "depth must be 1, 2 or 3" : nullptr;
+}
+
+inline const char *greedy_act_error(int64_t n, const void *state, const void *to_move, const void *hist, const void *action_out, int depth)
+{
+    GBL_N(n); GBL_PTR(state); GBL_PTR(to_move); GBL_PTR(hist);
+    return greedy_error(n, state, to_move, action_out, depth);
+}
+
+inline const char *outcome_targets_error(int64_t n, const void *done_traj, const void *reward_traj, const void *mover_traj, const void *z_traj,
+                                         uint32_t plies, int64_t ply_stride, int64_t tile_stride)
+{
+    GBL_N(n); GBL_PTR(done_traj); GBL_PTR(reward_traj); GBL_PTR(mover_traj); GBL_PTR(z_traj);
+    if (plies > 32767u) return "plies must not exceed 32767";
+    return plies == 0 || strides_ok(n, plies, ply_stride, tile_stride) ? nullptr : kStridesMessage;
+}
+#undef GBL_N
+#undef GBL_PTR
+
 // ---- board symmetries (include/gobblet_hip.h, "Board symmetries"): gbl_symmetry_apply and gbl_training_batch ------------------------
 // One statement of the rule for the kernels and the host flavour.  Everything is in GATHER form -- "which input element lands in
 // output element k" -- so that a lane that owns a whole row runs it with constant k (the divisions fold away) and a wavefront that
@@ -3069,17 +3170,6 @@ __device__ __forceinline__ bool batch_valid(const int8_t *z, const int8_t *done,
 #endif
     return sum > 0;
 }
-
-// The (ply, tile) cells of 64 boards of a trajectory must start 16-byte aligned and must not overlap.
-inline bool strides_ok(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride)
-{
-    const int64_t tiles = (n + kTile - 1) / kTile;
-    const bool aligned = ply_stride > 0 && tile_stride > 0 && !(ply_stride & 15) && !(tile_stride & 15);
-    const bool time_major = tile_stride >= kTile && (plies == 1 || ply_stride >= (tiles - 1) * tile_stride + kTile);
-    const bool tile_major = ply_stride >= kTile && (tiles == 1 || tile_stride >= ((int64_t)plies - 1) * ply_stride + kTile);
-    return aligned && (time_major || tile_major);
-}
-constexpr const char *kStridesMessage = "ply_stride / tile_stride: multiples of 16 boards that keep the (ply, tile) cells apart";
 
 // Argument checks of gbl_symmetry_apply, shared by both flavours (the device entry adds its alignment rules).  ok_zero: n == 0.
 struct SymRowsArg {

@@ -31,7 +31,9 @@ int hip_fail(hipError_t e, const char *what)
     return GBL_ERR_HIP;
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// whether any of the pointers is off a `bytes`-byte boundary (a power of two); NULL adds nothing
+template <typename... P>
+inline bool off(uintptr_t bytes, const P *...p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & (bytes - 1)) != 0; }
 
 struct Geometry {
     int64_t ntiles;
@@ -4768,65 +4770,53 @@ int policy_shape(int depth, int64_t n);
 // ===========================================================================================
 // C-ABI
 
-#define GBL_CHECK_N(n)                                      \
-    do {                                                    \
-        if ((n) < 0) return fail(GBL_ERR_ARG, "n < 0");     \
-        if ((n) == 0) return GBL_OK;                        \
-    } while (0)
 #define GBL_NEED(p, name)                                                 \
     do {                                                                  \
         if (!(p)) return fail(GBL_ERR_ARG, name " must not be NULL");     \
     } while (0)
 #define GBL_ALIGNED(p, name)                                                                   \
     do {                                                                                       \
-        if ((p) && !aligned16(p)) return fail(GBL_ERR_ALIGN, name " must be 16-byte aligned"); \
+        if (off(16, p)) return fail(GBL_ERR_ALIGN, name " must be 16-byte aligned");           \
     } while (0)
-#define GBL_LAUNCHED(name)                                   \
-    do {                                                     \
-        hipError_t e_ = hipGetLastError();                   \
-        if (e_ != hipSuccess) return hip_fail(e_, name);     \
-        return GBL_OK;                                       \
+#define GBL_LAUNCH_CHECK(name) /* between the launches of one entry point */                             \
+    do {                                                                                                  \
+        if (const hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return hip_fail(e_, name);         \
+    } while (0)
+#define GBL_LAUNCHED(name)     \
+    do {                       \
+        GBL_LAUNCH_CHECK(name); \
+        return GBL_OK;         \
     } while (0)
 
-// The trajectory arguments of gbl_collect_from_ex and gbl_collect_policy.  words: the addresses of the 4-byte element arrays OR-ed
-// together (a null one adds nothing), words_msg: the error that names them.
-static int check_traj(int64_t n, uint32_t plies, int64_t ply_stride, int64_t tile_stride, const int8_t *state, const int8_t *mask_traj,
-                      const int8_t *obs_traj, const int8_t *reward_traj, uintptr_t words, const char *words_msg, const int32_t *turn,
-                      const int64_t *counters)
+// The alignment rules of the trajectory arguments of gbl_collect_from_ex and gbl_collect_policy (after collect_error's strides).
+// words_off: whether one of the 4-byte element arrays is off a 4-byte boundary, words_msg: the error that names them.
+static int check_traj(const int8_t *state, const int8_t *mask_traj, const int8_t *obs_traj, const int8_t *reward_traj, bool words_off,
+                      const char *words_msg, const int32_t *turn, const int64_t *counters)
 {
-    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(obs_traj, "obs_traj");
-    if (reward_traj && (reinterpret_cast<uintptr_t>(reward_traj) & 1u))
-        return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
-    if (words & 3u) return fail(GBL_ERR_ALIGN, words_msg);
-    if (turn && (reinterpret_cast<uintptr_t>(turn) & 3u)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
-    if (counters && (reinterpret_cast<uintptr_t>(counters) & 127u))
-        return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
+    if (off(2, reward_traj)) return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
+    if (words_off) return fail(GBL_ERR_ALIGN, words_msg);
+    if (off(4, turn)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
+    if (off(128, counters)) return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
     return GBL_OK;
 }
 
 // The tail the nine self-play entry points share (selfplay_launch calls it once), after their own checks: the
 // trajectory's strides and alignments.  T: the kernel's SearchTraj, built by the entry point from its arguments; more_words /
-// words_msg: the entry's own further 4-byte arrays (check_traj's `words`) and the message that names its whole list.
-static int check_search_traj(const SearchTraj &T, uintptr_t more_words, const char *words_msg, int64_t n, uint32_t plies, int64_t ply_stride,
+// words_msg: the entry's own further 4-byte array (check_traj's words) and the message that names its whole list.
+static int check_search_traj(const SearchTraj &T, const int32_t *more_words, const char *words_msg, int64_t n, uint32_t plies, int64_t ply_stride,
                              int64_t tile_stride, const int8_t *state, const int32_t *turn, const int64_t *counters)
 {
-    const uintptr_t words = more_words | reinterpret_cast<uintptr_t>(T.actions) | reinterpret_cast<uintptr_t>(T.value) |
-                            reinterpret_cast<uintptr_t>(T.nodes);
-    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, T.mask, T.obs, T.reward, words, words_msg, turn, counters)) return e;
-    if (reinterpret_cast<uintptr_t>(T.visits) & 1u) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
+    if (!strides_ok(n, plies, ply_stride, tile_stride)) return fail(GBL_ERR_ARG, kStridesMessage);
+    if (const int e = check_traj(state, T.mask, T.obs, T.reward, off(4, more_words, T.actions, T.value, T.nodes), words_msg, turn, counters)) return e;
+    if (off(2, T.visits)) return fail(GBL_ERR_ALIGN, "visits_traj must be 2-byte aligned");
     return GBL_OK;
 }
 
 // the grid of the one-workgroup-a-board kernels: they stride over what is beyond the cap
 static inline dim3 board_grid(int64_t n) { return dim3((uint32_t)std::min<int64_t>(n, 1 << 20)); }
 
-// whether any of the pointers (NULL included) is off a 4-byte boundary
-template <typename... P>
-static inline bool off_dword(const P *...p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 3u) != 0; }
-
 extern "C" {
-
 
 const char *gbl_last_error(void) { return g_err; }
 
@@ -4839,8 +4829,8 @@ int gbl_layout_info(int32_t out[6])
 
 int gbl_reset(int8_t *state, int8_t *to_move, int8_t *done, int8_t *winner, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
+    if (const char *why = reset_error(n, state, to_move, done)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
     if ((e = hipMemsetAsync(state, 0, (size_t)n * kCells, s)) != hipSuccess) return hip_fail(e, "gbl_reset");
@@ -4852,8 +4842,8 @@ int gbl_reset(int8_t *state, int8_t *to_move, int8_t *done, int8_t *winner, int6
 
 int gbl_legal_mask(const int8_t *state, const int8_t *to_move, int8_t *mask, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(mask, "mask");
+    if (const char *why = legal_mask_error(n, state, to_move, mask)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask, "mask");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_legal_mask, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, to_move, mask, n, g.ntiles);
@@ -4863,8 +4853,8 @@ int gbl_legal_mask(const int8_t *state, const int8_t *to_move, int8_t *mask, int
 int gbl_is_legal(const int8_t *state, const int8_t *agent_index, const int32_t *actions, int8_t *out, int64_t n,
                  void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(agent_index, "agent_index"); GBL_NEED(actions, "actions"); GBL_NEED(out, "out");
+    if (const char *why = is_legal_error(n, state, agent_index, actions, out)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_is_legal, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, agent_index, actions, out, n,
@@ -4874,8 +4864,8 @@ int gbl_is_legal(const int8_t *state, const int8_t *agent_index, const int32_t *
 
 int gbl_play_turn(int8_t *state, const int8_t *agent_index, const int32_t *actions, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(agent_index, "agent_index"); GBL_NEED(actions, "actions");
+    if (const char *why = play_turn_error(n, state, agent_index, actions)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_play_turn, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, agent_index, actions, n,
@@ -4885,8 +4875,8 @@ int gbl_play_turn(int8_t *state, const int8_t *agent_index, const int32_t *actio
 
 int gbl_winner(const int8_t *state, int8_t *winner, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(winner, "winner");
+    if (const char *why = winner_error(n, state, winner)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_winner, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, winner, n, g.ntiles);
@@ -4895,8 +4885,8 @@ int gbl_winner(const int8_t *state, int8_t *winner, int64_t n, void *stream)
 
 int gbl_flatboard(const int8_t *state, int8_t *flat, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(flat, "flat");
+    if (const char *why = flatboard_error(n, state, flat)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(flat, "flat");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_flatboard, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, flat, n, g.ntiles);
@@ -4905,8 +4895,8 @@ int gbl_flatboard(const int8_t *state, int8_t *flat, int64_t n, void *stream)
 
 int gbl_covered(const int8_t *state, int8_t *cov, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(cov, "cov");
+    if (const char *why = covered_error(n, state, cov)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(cov, "cov");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_covered, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, cov, n, g.ntiles);
@@ -4915,10 +4905,8 @@ int gbl_covered(const int8_t *state, int8_t *cov, int64_t n, void *stream)
 
 int gbl_observe(const int8_t *state, const int8_t *to_move, int agent_sel, int8_t *obs, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(obs, "obs");
-    if (agent_sel < -1 || agent_sel > 1) return fail(GBL_ERR_ARG, "agent_sel must be -1, 0 or 1");
-    if (agent_sel < 0) GBL_NEED(to_move, "to_move (agent_sel == -1)");
+    if (const char *why = observe_error(n, state, to_move, agent_sel, obs)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(obs, "obs");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_observe, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, to_move, agent_sel, obs, n,
@@ -4985,31 +4973,14 @@ int gbl_device_memory(int64_t *free_bytes, int64_t *total_bytes)
 int gbl_board_eval(int8_t *state, const int8_t *agent_index, const int32_t *actions, int8_t *record_out, int64_t n,
                    void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(record_out, "record_out");
-    if (actions) GBL_NEED(agent_index, "agent_index (with actions)");
+    if (const char *why = board_eval_error(n, state, agent_index, actions, record_out)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(record_out, "record_out");
-    if (actions && (reinterpret_cast<uintptr_t>(actions) & 3u)) return fail(GBL_ERR_ALIGN, "actions must be 4-byte aligned");
+    if (off(4, actions)) return fail(GBL_ERR_ALIGN, "actions must be 4-byte aligned");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_board_eval, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, agent_index, actions,
                        record_out, n, g.ntiles);
     GBL_LAUNCHED("gbl_board_eval");
-}
-
-int gbl_step(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *actions, int8_t *winner_out,
-             int8_t *reward_out, int8_t *mask_out, int8_t *obs_out, int32_t *turn, int64_t n, int illegal_mode,
-             int auto_reset, void *stream)
-{
-    return gbl_step_ex(state, to_move, done, actions, winner_out, reward_out, mask_out, obs_out, turn, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, 0, 0, 0, nullptr, n, illegal_mode, auto_reset, stream);
-}
-
-int gbl_step_into(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *actions, int8_t *winner_out,
-                  int8_t *reward_out, int8_t *mask_out, int8_t *obs_out, int32_t *turn, int32_t *actions_out,
-                  int8_t *done_out, int8_t *to_move_out, int64_t n, int illegal_mode, int auto_reset, void *stream)
-{
-    return gbl_step_ex(state, to_move, done, actions, winner_out, reward_out, mask_out, obs_out, turn, actions_out, done_out,
-                       to_move_out, nullptr, nullptr, 0, 0, 0, nullptr, n, illegal_mode, auto_reset, stream);
 }
 
 int gbl_step_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *actions, int8_t *winner_out,
@@ -5018,19 +4989,14 @@ int gbl_step_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *act
                 uint64_t env_base, uint32_t ply, const uint32_t *ply_dev, int64_t n, int illegal_mode, int auto_reset,
                 void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done"); GBL_NEED(actions, "actions");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
+    if (const char *why = step_error(n, state, to_move, done, actions, illegal_mode)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(obs_out, "obs_out");
-    if (reward_out && (reinterpret_cast<uintptr_t>(reward_out) & 1u))
-        return fail(GBL_ERR_ALIGN, "reward_out must be 2-byte aligned");
-    if (turn && (reinterpret_cast<uintptr_t>(turn) & 3u)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(actions) & 3u) return fail(GBL_ERR_ALIGN, "actions must be 4-byte aligned");
-    if (actions_out && (reinterpret_cast<uintptr_t>(actions_out) & 3u))
-        return fail(GBL_ERR_ALIGN, "actions_out must be 4-byte aligned");
-    if (next_actions_out && (reinterpret_cast<uintptr_t>(next_actions_out) & 3u))
-        return fail(GBL_ERR_ALIGN, "next_actions_out must be 4-byte aligned");
+    if (off(2, reward_out)) return fail(GBL_ERR_ALIGN, "reward_out must be 2-byte aligned");
+    if (off(4, turn)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
+    if (off(4, actions)) return fail(GBL_ERR_ALIGN, "actions must be 4-byte aligned");
+    if (off(4, actions_out)) return fail(GBL_ERR_ALIGN, "actions_out must be 4-byte aligned");
+    if (off(4, next_actions_out)) return fail(GBL_ERR_ALIGN, "next_actions_out must be 4-byte aligned");
     Geometry g = geometry(n, kStepWaves);
     hipStream_t s = (hipStream_t)stream;
     auto_reset = auto_reset != 0;
@@ -5047,8 +5013,8 @@ int gbl_step_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *act
 int gbl_sample_at(const int8_t *mask, int32_t *actions, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply,
                   const uint32_t *ply_dev, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(mask, "mask"); GBL_NEED(actions, "actions");
+    if (const char *why = sample_error(n, mask, actions)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(mask, "mask");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_sample, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, mask, actions, n, g.ntiles, seed,
@@ -5056,25 +5022,11 @@ int gbl_sample_at(const int8_t *mask, int32_t *actions, int64_t n, uint64_t seed
     GBL_LAUNCHED("gbl_sample");
 }
 
-int gbl_sample(const int8_t *mask, int32_t *actions, int64_t n, uint64_t seed, uint64_t env_base, uint32_t ply,
-               void *stream)
-{
-    return gbl_sample_at(mask, actions, n, seed, env_base, ply, nullptr, stream);
-}
-
 int gbl_counter_add(uint32_t *counter, uint32_t by, void *stream)
 {
-    GBL_NEED(counter, "counter");
+    if (!counter) return fail(GBL_ERR_ARG, "counter must not be NULL");
     hipLaunchKernelGGL(k_counter_add, dim3(1), dim3(1), 0, (hipStream_t)stream, counter, by);
     GBL_LAUNCHED("gbl_counter_add");
-}
-
-int gbl_rollout(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_out, int8_t *winner_out,
-                int8_t *reward_out, int8_t *mask_out, int8_t *obs_out, int64_t n, uint64_t seed, uint64_t env_base,
-                uint32_t ply0, uint32_t plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
-{
-    return gbl_rollout_at(state, to_move, done, actions_out, winner_out, reward_out, mask_out, obs_out, n, seed, env_base,
-                          ply0, nullptr, plies, illegal_mode, counters, turn, stream);
 }
 
 int gbl_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_out, int8_t *winner_out,
@@ -5082,19 +5034,13 @@ int gbl_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *action
                    uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int illegal_mode, int64_t *counters,
                    int32_t *turn, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
-    if (plies == 0) return GBL_OK;
+    if (const char *why = rollout_error(n, state, to_move, done, illegal_mode)) return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(obs_out, "obs_out");
-    if (reward_out && (reinterpret_cast<uintptr_t>(reward_out) & 1u))
-        return fail(GBL_ERR_ALIGN, "reward_out must be 2-byte aligned");
-    if (counters && (reinterpret_cast<uintptr_t>(counters) & 127u))
-        return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
-    if (turn && (reinterpret_cast<uintptr_t>(turn) & 3u)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
-    if (actions_out && (reinterpret_cast<uintptr_t>(actions_out) & 3u))
-        return fail(GBL_ERR_ALIGN, "actions_out must be 4-byte aligned");
+    if (off(2, reward_out)) return fail(GBL_ERR_ALIGN, "reward_out must be 2-byte aligned");
+    if (off(128, counters)) return fail(GBL_ERR_ALIGN, "counters must be 128-byte aligned");
+    if (off(4, turn)) return fail(GBL_ERR_ALIGN, "turn must be 4-byte aligned");
+    if (off(4, actions_out)) return fail(GBL_ERR_ALIGN, "actions_out must be 4-byte aligned");
     Geometry g = geometry(n, kStepWaves);
     hipStream_t s = (hipStream_t)stream;
     const int nt = nt_policy(n);
@@ -5106,43 +5052,17 @@ int gbl_rollout_at(int8_t *state, int8_t *to_move, int8_t *done, int32_t *action
     GBL_LAUNCHED("gbl_rollout");  // (also gbl_rollout_at)
 }
 
-int gbl_collect(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
-                int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
-                int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
-                const uint32_t *ply_dev, uint32_t plies, int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
-{
-    return gbl_collect_from(state, to_move, done, nullptr, actions_traj, winner_traj, reward_traj, done_traj, to_move_traj,
-                            mask_traj, obs_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies,
-                            illegal_mode, counters, turn, stream);
-}
-
-int gbl_collect_from(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *first_actions, int32_t *actions_traj,
-                     int8_t *winner_traj, int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
-                     int8_t *obs_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed,
-                     uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int illegal_mode,
-                     int64_t *counters, int32_t *turn, void *stream)
-{
-    return gbl_collect_from_ex(state, to_move, done, first_actions, nullptr, actions_traj, winner_traj, reward_traj, done_traj,
-                               to_move_traj, mask_traj, obs_traj, n, ply_stride, tile_stride, seed, env_base, ply0, ply_dev, plies,
-                               illegal_mode, counters, turn, stream);
-}
-
 int gbl_collect_from_ex(int8_t *state, int8_t *to_move, int8_t *done, const int32_t *first_actions, int8_t *first_status,
                         int32_t *actions_traj, int8_t *winner_traj, int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj,
                         int8_t *mask_traj, int8_t *obs_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed,
                         uint64_t env_base, uint32_t ply0, const uint32_t *ply_dev, uint32_t plies, int illegal_mode,
                         int64_t *counters, int32_t *turn, void *stream)
 {
-    GBL_CHECK_N(n);
-    if (first_actions && (reinterpret_cast<uintptr_t>(first_actions) & 3u))
-        return fail(GBL_ERR_ALIGN, "first_actions must be 4-byte aligned");
-    if (first_status && !first_actions) return fail(GBL_ERR_ARG, "first_status without first_actions");
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
-    if (plies == 0) return GBL_OK;
-    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
-                                 reinterpret_cast<uintptr_t>(actions_traj), "actions_traj must be 4-byte aligned", turn, counters))
+    if (n > 0 && off(4, first_actions)) return fail(GBL_ERR_ALIGN, "first_actions must be 4-byte aligned");  // (in front of every rule but n's)
+    if (const char *why = collect_error(n, first_actions, first_status, state, to_move, done, illegal_mode, plies, ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
+    if (const int e = check_traj(state, mask_traj, obs_traj, reward_traj, off(4, actions_traj), "actions_traj must be 4-byte aligned", turn, counters))
         return e;
     const Geometry g = geometry(n);
     const hipStream_t s = (hipStream_t)stream;
@@ -5182,21 +5102,15 @@ int gbl_collect_policy(int8_t *state, int8_t *to_move, int8_t *done, int8_t *his
                        const uint32_t *ply_dev, uint32_t plies, int policy0, int policy1, int opening_plies,
                        int illegal_mode, int64_t *counters, int32_t *turn, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(done, "done");
-    if (illegal_mode != GBL_ILLEGAL_NOOP && illegal_mode != GBL_ILLEGAL_TERMINATE)
-        return fail(GBL_ERR_ARG, "illegal_mode must be GBL_ILLEGAL_NOOP or GBL_ILLEGAL_TERMINATE");
-    if (policy0 < GBL_POLICY_RANDOM || policy0 > GBL_POLICY_GREEDY3 || policy1 < GBL_POLICY_RANDOM || policy1 > GBL_POLICY_GREEDY3)
-        return fail(GBL_ERR_ARG, "policy0 / policy1: GBL_POLICY_RANDOM, GBL_POLICY_GREEDY1, _GREEDY2 or _GREEDY3");
-    if (opening_plies < 0) return fail(GBL_ERR_ARG, "opening_plies < 0");
-    if (opening_plies > 0 && !turn) return fail(GBL_ERR_ARG, "opening_plies > 0 needs the per-board turn counter (turn must not be NULL)");
-    if (plies == 0) return GBL_OK;
-    if (const int e = check_traj(n, plies, ply_stride, tile_stride, state, mask_traj, obs_traj, reward_traj,
-                                 reinterpret_cast<uintptr_t>(actions_traj) | reinterpret_cast<uintptr_t>(chosen_traj),
+    if (const char *why = collect_policy_error(n, state, to_move, done, illegal_mode, policy0, policy1, opening_plies, turn != nullptr, plies,
+                                               ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
+    if (const int e = check_traj(state, mask_traj, obs_traj, reward_traj, off(4, actions_traj, chosen_traj),
                                  "actions_traj / chosen_traj must be 4-byte aligned", turn, counters))
         return e;
     GBL_ALIGNED(cand_traj, "cand_traj");
-    if (hist && (reinterpret_cast<uintptr_t>(hist) & 1u)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
+    if (off(2, hist)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int depth = policy0 > policy1 ? policy0 : policy1;
     const int shape = policy_shape(depth, n);
@@ -5229,8 +5143,7 @@ int gbl_placement_probe(void *a, int64_t a_bytes, void *b, int64_t b_bytes, int6
                         float *us_a, float *us_b, void *stream)
 {
     GBL_NEED(a, "a"); GBL_NEED(b, "b"); GBL_NEED(us_both, "us_both"); GBL_NEED(us_a, "us_a"); GBL_NEED(us_b, "us_b");
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 127u)
-        return fail(GBL_ERR_ALIGN, "a and b must be 128-byte aligned");
+    if (off(128, a, b)) return fail(GBL_ERR_ALIGN, "a and b must be 128-byte aligned");
     int kPlies = 4;
     int64_t tiles;
     if (slot_boards > 0) {  // the geometry of a time-major trajectory: `plies` slots of slot_boards boards
@@ -5286,8 +5199,8 @@ int gbl_placement_probe(void *a, int64_t a_bytes, void *b, int64_t b_bytes, int6
 
 int gbl_decode_obs(const int8_t *obs, int8_t *state, int8_t *to_move, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(obs, "obs"); GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move");
+    if (const char *why = decode_obs_error(n, obs, state, to_move)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(obs, "obs"); GBL_ALIGNED(state, "state");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_decode_obs, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, obs, state, to_move, n, g.ntiles);
@@ -5296,8 +5209,8 @@ int gbl_decode_obs(const int8_t *obs, int8_t *state, int8_t *to_move, int64_t n,
 
 int gbl_validate(const int8_t *state, int8_t *flags, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(flags, "flags");
+    if (const char *why = validate_error(n, state, flags)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state");
     Geometry g = geometry(n);
     hipLaunchKernelGGL(k_validate, dim3(g.grid), dim3(64), 0, (hipStream_t)stream, state, flags, n, g.ntiles);
@@ -5385,33 +5298,23 @@ void launch_greedy(int shape, int64_t n, hipStream_t stream, const int8_t *state
 int gbl_greedy(const int8_t *state, const int8_t *to_move, const int8_t *mask, const int8_t *hist, int depth,
                int32_t *action_out, int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(action_out, "action_out");
-    if (depth < 1 || depth > 3) return fail(GBL_ERR_ARG, "depth must be 1, 2 or 3");
+    if (const char *why = greedy_error(n, state, to_move, action_out, depth)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(cand_mask_out, "cand_mask_out");
-    if (hist && (reinterpret_cast<uintptr_t>(hist) & 1u)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
+    if (off(2, hist)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
     launch_greedy(greedy_shape(depth, n), n, (hipStream_t)stream, state, to_move, mask, hist, depth, action_out,
                   cand_mask_out, fallback_out, nullptr, nullptr, 0, 0, 0);
     GBL_LAUNCHED("gbl_greedy");
-}
-
-int gbl_greedy_act(const int8_t *state, const int8_t *to_move, const int8_t *mask, int8_t *hist, int depth,
-                   uint64_t seed, uint64_t env_base, uint32_t call, int32_t *action_out, int32_t *chosen_out,
-                   int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *stream)
-{
-    return gbl_greedy_act_at(state, to_move, mask, hist, depth, seed, env_base, call, nullptr, action_out, chosen_out,
-                             cand_mask_out, fallback_out, n, stream);
 }
 
 int gbl_greedy_act_at(const int8_t *state, const int8_t *to_move, const int8_t *mask, int8_t *hist, int depth,
                       uint64_t seed, uint64_t env_base, uint32_t call, const uint32_t *call_dev, int32_t *action_out,
                       int32_t *chosen_out, int8_t *cand_mask_out, int8_t *fallback_out, int64_t n, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(state, "state"); GBL_NEED(to_move, "to_move"); GBL_NEED(hist, "hist"); GBL_NEED(action_out, "action_out");
-    if (depth < 1 || depth > 3) return fail(GBL_ERR_ARG, "depth must be 1, 2 or 3");
+    if (const char *why = greedy_act_error(n, state, to_move, hist, action_out, depth)) return fail(GBL_ERR_ARG, why);
+    if (n == 0) return GBL_OK;
     GBL_ALIGNED(state, "state"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(cand_mask_out, "cand_mask_out");
-    if (hist && (reinterpret_cast<uintptr_t>(hist) & 1u)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
+    if (off(2, hist)) return fail(GBL_ERR_ALIGN, "hist must be 2-byte aligned");
     launch_greedy(greedy_shape(depth, n), n, (hipStream_t)stream, state, to_move, mask, nullptr, depth, chosen_out,
                   cand_mask_out, fallback_out, hist, action_out, seed, env_base, call, call_dev);
     GBL_LAUNCHED("gbl_greedy_act");
@@ -5423,7 +5326,7 @@ int gbl_playout_values(const int8_t *state, const int8_t *to_move, const int8_t 
 {
     if (const char *why = playout_values_error(playouts, max_plies, call, env_base, n, state, to_move)) return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    if (off_dword(wins_out, losses_out, action_out, plies_out))
+    if (off(4, wins_out, losses_out, action_out, plies_out))
         return fail(GBL_ERR_ALIGN, "wins_out / losses_out / action_out / plies_out must be 4-byte aligned");
     const uint32_t K = (uint32_t)playouts;
     const uint64_t kinv = ((1ull << 32) + K - 1) / K;
@@ -5449,7 +5352,7 @@ int gbl_tree_search(const int8_t *state, const int8_t *to_move, const int8_t *ma
     if (const char *why = tree_search_error(iterations, playouts, max_plies, explore, call, env_base, n, state, to_move))
         return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
-    if (off_dword(visits_out, wins_out, losses_out, action_out, nodes_out, plies_out))
+    if (off(4, visits_out, wins_out, losses_out, action_out, nodes_out, plies_out))
         return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / plies_out must be 4-byte aligned");
     const dim3 grid = board_grid(n);
     const size_t lds = sizeof(TreeNode) * ((size_t)iterations + 1);  // the tree: one node per iteration and the root
@@ -5482,8 +5385,7 @@ int gbl_solve(const int8_t *state, const int8_t *to_move, const int8_t *mask, in
 static int eval_net_of(const gbl_evaluator *ev, EvalNet &net)
 {
     if (const char *why = evaluator_pointers_error(ev)) return fail(GBL_ERR_ARG, why);
-    if (!aligned16(ev->w1) || !aligned16(ev->b1) || !aligned16(ev->w2) || !aligned16(ev->b2))
-        return fail(GBL_ERR_ALIGN, "the evaluator's w1 / b1 / w2 / b2 must be 16-byte aligned");
+    if (off(16, ev->w1, ev->b1, ev->w2, ev->b2)) return fail(GBL_ERR_ALIGN, "the evaluator's w1 / b1 / w2 / b2 must be 16-byte aligned");
     net = EvalNet{ev->w1, ev->b1, ev->w2, ev->b2, ev->hidden, ev->shift1, ev->shift_p, ev->shift_v};
     return GBL_OK;
 }
@@ -5495,7 +5397,7 @@ int gbl_evaluate(const int8_t *state, const int8_t *to_move, const int8_t *mask,
     if (n == 0) return GBL_OK;
     EvalNet net;
     if (const int e = eval_net_of(ev, net)) return e;
-    if (off_dword(value_out, logits_out)) return fail(GBL_ERR_ALIGN, "value_out / logits_out must be 4-byte aligned");
+    if (off(4, value_out, logits_out)) return fail(GBL_ERR_ALIGN, "value_out / logits_out must be 4-byte aligned");
     hipLaunchKernelGGL(k_evaluate, board_grid(n), dim3(64), 0, (hipStream_t)stream, state, to_move, mask, net, priors_out, value_out,
                        logits_out, n);
     GBL_LAUNCHED("gbl_evaluate");
@@ -5511,7 +5413,7 @@ static int tree_search_eval_launch(const char *name, const int8_t *state, const 
     if (n == 0) return GBL_OK;
     EvalNet net;
     if (const int e = eval_net_of(ev, net)) return e;
-    if (off_dword(visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out))
+    if (off(4, visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out))
         return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / root_value_out must be 4-byte aligned");
     // the tree: a node and a prior row per iteration, and the root's (36.9 KB at 512 iterations: below the 64 KB a kernel gets unasked)
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);
@@ -5560,9 +5462,9 @@ int gbl_tree_search_gumbel(const int8_t *state, const int8_t *to_move, const int
     if (n == 0) return GBL_OK;
     EvalNet net;
     if (const int e = eval_net_of(ev, net)) return e;
-    if (off_dword(visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out))
+    if (off(4, visits_out, wins_out, losses_out, action_out, nodes_out, root_value_out))
         return fail(GBL_ERR_ALIGN, "visits_out / wins_out / losses_out / action_out / nodes_out / root_value_out must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(gumbel_out) & 1u) return fail(GBL_ERR_ALIGN, "gumbel_out must be 2-byte aligned");
+    if (off(2, gumbel_out)) return fail(GBL_ERR_ALIGN, "gumbel_out must be 2-byte aligned");
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)iterations + 1);  // (the tree of gbl_tree_search_eval: the rule adds none)
     hipLaunchKernelGGL((k_tree_eval<false, true>), board_grid(n), dim3(64), lds, (hipStream_t)stream, state, to_move, mask, net, visits_out,
                        wins_out, losses_out, action_out, nodes_out, root_value_out, root_priors_out, n, (uint32_t)iterations,
@@ -5584,7 +5486,7 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
     const bool uct = c.run == kRunSearch;
     const SelfplayTraj &t = c.traj;
     const SearchTraj T{t.actions, t.winner, t.reward, t.done, t.to_move, t.mask, t.obs, t.visits, t.value, t.nodes, t.how, t.mover};
-    if (const int e = check_search_traj(T, reinterpret_cast<uintptr_t>(t.root_value),
+    if (const int e = check_search_traj(T, t.root_value,
                                         uct ? "actions_traj / value_traj / nodes_traj must be 4-byte aligned"
                                             : "actions_traj / value_traj / nodes_traj / root_value_traj must be 4-byte aligned",
                                         c.n, c.plies, c.ply_stride, c.tile_stride, c.state, c.turn, c.counters))
@@ -5672,21 +5574,21 @@ static int selfplay_launch(const char *name, const SelfplayCall<gbl_evaluator> &
 }
 
 // the nine entry points themselves: one text for both flavours
-#define GBL_SELFPLAY_SYMBOL(fn) gbl_##fn
+#define GBL_SYMBOL(fn) gbl_##fn
 #define GBL_SELFPLAY_RUN(name, call, stream) selfplay_launch(name, call, stream)
 #include "gobblet_selfplay_entries.inc"
-#undef GBL_SELFPLAY_SYMBOL
+#include "gobblet_env_entries.inc"  // (gbl_step, _step_into, _sample, _rollout, _collect, _collect_from, _greedy_act: they only forward)
+#undef GBL_SYMBOL
 #undef GBL_SELFPLAY_RUN
 
 int gbl_outcome_targets(const int8_t *done_traj, const int8_t *reward_traj, const int8_t *mover_traj, int8_t *z_traj,
                         int16_t *plies_left_traj, int64_t n, int64_t ply_stride, int64_t tile_stride, uint32_t plies, void *stream)
 {
-    GBL_CHECK_N(n);
-    GBL_NEED(done_traj, "done_traj"); GBL_NEED(reward_traj, "reward_traj"); GBL_NEED(mover_traj, "mover_traj"); GBL_NEED(z_traj, "z_traj");
-    if (plies > 32767u) return fail(GBL_ERR_ARG, "plies must not exceed 32767");
-    if (plies == 0) return GBL_OK;
-    if (const int e = check_traj(n, plies, ply_stride, tile_stride, nullptr, nullptr, nullptr, reward_traj, 0, "", nullptr, nullptr)) return e;
-    if (reinterpret_cast<uintptr_t>(plies_left_traj) & 1u) return fail(GBL_ERR_ALIGN, "plies_left_traj must be 2-byte aligned");
+    if (const char *why = outcome_targets_error(n, done_traj, reward_traj, mover_traj, z_traj, plies, ply_stride, tile_stride))
+        return fail(GBL_ERR_ARG, why);
+    if (n == 0 || plies == 0) return GBL_OK;
+    if (off(2, reward_traj)) return fail(GBL_ERR_ALIGN, "reward_traj must be 2-byte aligned");
+    if (off(2, plies_left_traj)) return fail(GBL_ERR_ALIGN, "plies_left_traj must be 2-byte aligned");
     const int64_t ntiles = (n + kTile - 1) / kTile;
     hipLaunchKernelGGL(k_outcome_targets, dim3((uint32_t)std::min<int64_t>(ntiles, 1 << 20)), dim3(64), 0, (hipStream_t)stream, done_traj,
                        reward_traj, mover_traj, z_traj, plies_left_traj, n, ntiles, ply_stride, tile_stride, plies);
@@ -5705,9 +5607,8 @@ int gbl_symmetry_apply(const int16_t *sym, int sym_all, const int8_t *agent, con
     GBL_ALIGNED(state_in, "state_in"); GBL_ALIGNED(state_out, "state_out"); GBL_ALIGNED(obs_in, "obs_in"); GBL_ALIGNED(obs_out, "obs_out");
     GBL_ALIGNED(mask_in, "mask_in"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_in, "visits_in");
     GBL_ALIGNED(visits_out, "visits_out"); GBL_ALIGNED(priors_in, "priors_in"); GBL_ALIGNED(priors_out, "priors_out");
-    if ((reinterpret_cast<uintptr_t>(actions_in) | reinterpret_cast<uintptr_t>(actions_out)) & 3u)
-        return fail(GBL_ERR_ALIGN, "actions_in / actions_out must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(sym) & 1u) return fail(GBL_ERR_ALIGN, "sym must be 2-byte aligned");
+    if (off(4, actions_in, actions_out)) return fail(GBL_ERR_ALIGN, "actions_in / actions_out must be 4-byte aligned");
+    if (off(2, sym)) return fail(GBL_ERR_ALIGN, "sym must be 2-byte aligned");
     const Geometry g = geometry(n);
     const SymRows R{state_in,  obs_in,  mask_in,  visits_in,  priors_in, actions_in,
                     state_out, obs_out, mask_out, visits_out, priors_out, actions_out};
@@ -5726,9 +5627,8 @@ int gbl_training_batch(const int8_t *obs_traj, const int8_t *mask_traj, const in
         return fail(GBL_ERR_ARG, why);
     if (batch == 0) return GBL_OK;
     GBL_ALIGNED(obs_out, "obs_out"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_out, "visits_out");
-    if ((reinterpret_cast<uintptr_t>(visits_traj) | reinterpret_cast<uintptr_t>(index_out)) & 3u)
-        return fail(GBL_ERR_ALIGN, "visits_traj / index_out must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(sym_out) & 1u) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
+    if (off(4, visits_traj, index_out)) return fail(GBL_ERR_ALIGN, "visits_traj / index_out must be 4-byte aligned");
+    if (off(2, sym_out)) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
     const Geometry g = geometry(batch);
     const BatchArgs A{obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, obs_out, mask_out, visits_out, z_out, index_out, sym_out,
                       n, ply_stride, tile_stride, batch, g.ntiles, seed, sample_base, plies, call, (uint32_t)sym_mask};
@@ -5746,8 +5646,7 @@ int gbl_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int
     if (const char *why = replay_append_error(obs_traj, mask_traj, visits_traj, z_traj, done_traj, mover_traj, n, plies, ply_stride,
                                               tile_stride, ring_obs, ring_visits, ring_meta, capacity, ring_state, workspace, workspace_bytes))
         return fail(GBL_ERR_ARG, why);
-    if ((reinterpret_cast<uintptr_t>(ring_obs) | reinterpret_cast<uintptr_t>(ring_visits) | reinterpret_cast<uintptr_t>(ring_meta)) & 127u)
-        return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
+    if (off(128, ring_obs, ring_visits, ring_meta)) return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
     GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(workspace, "workspace");
     GBL_ALIGNED(obs_traj, "obs_traj"); GBL_ALIGNED(mask_traj, "mask_traj"); GBL_ALIGNED(visits_traj, "visits_traj");
     const int64_t ntiles = (n + kTile - 1) / kTile, chunks = replay_chunks(n, plies);
@@ -5756,9 +5655,9 @@ int gbl_replay_append(const int8_t *obs_traj, const int8_t *mask_traj, const int
     const dim3 grid((uint32_t)std::min<int64_t>(chunks, kReplayMaxGrid));
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_replay_count, grid, dim3(64), 0, s, A);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_append");
+    GBL_LAUNCH_CHECK("gbl_replay_append");
     hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(kReplayScanThreads), 0, s, A);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_append");
+    GBL_LAUNCH_CHECK("gbl_replay_append");
     hipLaunchKernelGGL(k_replay_scatter, grid, dim3(64), 0, s, A);
     GBL_LAUNCHED("gbl_replay_append");
 }
@@ -5772,12 +5671,11 @@ int gbl_replay_batch(const int8_t *ring_obs, const int16_t *ring_visits, const i
                                              index_out))
         return fail(GBL_ERR_ARG, why);
     if (batch == 0) return GBL_OK;
-    if ((reinterpret_cast<uintptr_t>(ring_obs) | reinterpret_cast<uintptr_t>(ring_visits) | reinterpret_cast<uintptr_t>(ring_meta)) & 127u)
-        return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
+    if (off(128, ring_obs, ring_visits, ring_meta)) return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
     GBL_ALIGNED(ring_state, "ring_state");
     GBL_ALIGNED(obs_out, "obs_out"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_out, "visits_out");
-    if (reinterpret_cast<uintptr_t>(index_out) & 3u) return fail(GBL_ERR_ALIGN, "index_out must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(sym_out) & 1u) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
+    if (off(4, index_out)) return fail(GBL_ERR_ALIGN, "index_out must be 4-byte aligned");
+    if (off(2, sym_out)) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
     const Geometry g = geometry(batch);
     const ReplayBatchArgs A{ring_obs, ring_visits, ring_meta, ring_state, obs_out, mask_out, visits_out, z_out, index_out, sym_out,
                             batch, g.ntiles, recent, (uint64_t)capacity, seed, sample_base, call, (uint32_t)sym_mask};
@@ -5794,9 +5692,9 @@ int gbl_replay_prio_append(const int16_t *visits_traj, const int8_t *z_traj, con
     if (const char *why = replay_prio_append_error(visits_traj, z_traj, done_traj, n, plies, ply_stride, tile_stride, ring_prio, capacity,
                                                    ring_state, workspace, workspace_bytes))
         return fail(GBL_ERR_ARG, why);
-    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    if (off(128, ring_prio)) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
     GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(workspace, "workspace");
-    if (reinterpret_cast<uintptr_t>(prio_traj) & 3u) return fail(GBL_ERR_ALIGN, "prio_traj must be 4-byte aligned");
+    if (off(4, prio_traj)) return fail(GBL_ERR_ALIGN, "prio_traj must be 4-byte aligned");
     const int64_t ntiles = (n + kTile - 1) / kTile, chunks = replay_chunks(n, plies);
     const ReplayPrioAppendArgs A{prio_traj, ring_prio, static_cast<const uint64_t *>(workspace), ply_stride, tile_stride, ntiles, chunks,
                                  (uint64_t)capacity, value};
@@ -5808,13 +5706,12 @@ int gbl_replay_prio_update(const int32_t *index, const int32_t *values, int64_t 
 {
     if (const char *why = replay_prio_update_error(index, values, batch, ring_prio, capacity)) return fail(GBL_ERR_ARG, why);
     if (batch == 0) return GBL_OK;
-    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(values)) & 3u)
-        return fail(GBL_ERR_ALIGN, "index / values must be 4-byte aligned");
+    if (off(128, ring_prio)) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    if (off(4, index, values)) return fail(GBL_ERR_ALIGN, "index / values must be 4-byte aligned");
     const dim3 grid((uint32_t)std::min<int64_t>((batch + 255) / 256, kReplayMaxGrid));
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_replay_prio_update<0>, grid, dim3(256), 0, s, index, values, batch, ring_prio, capacity);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_prio_update");
+    GBL_LAUNCH_CHECK("gbl_replay_prio_update");
     hipLaunchKernelGGL(k_replay_prio_update<1>, grid, dim3(256), 0, s, index, values, batch, ring_prio, capacity);
     GBL_LAUNCHED("gbl_replay_prio_update");
 }
@@ -5823,13 +5720,13 @@ int gbl_replay_prio_index(const int32_t *ring_prio, int64_t capacity, const uint
                           void *stream)
 {
     if (const char *why = replay_prio_index_error(ring_prio, capacity, ring_state, prio_index, index_bytes)) return fail(GBL_ERR_ARG, why);
-    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    if (off(128, ring_prio)) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
     GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(prio_index, "prio_index");
     const uint64_t leaves = replay_prio_leaves((uint64_t)capacity), blocks = replay_prio_blocks((uint64_t)capacity);
     const ReplayPrioIndexArgs A{ring_prio, ring_state, static_cast<uint64_t *>(prio_index), (uint64_t)capacity, leaves, blocks};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_replay_prio_leaves, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 16)), dim3(kReplayLeafThreads), 0, s, A);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_replay_prio_index");
+    GBL_LAUNCH_CHECK("gbl_replay_prio_index");
     hipLaunchKernelGGL(k_replay_prio_scan, dim3(1), dim3(kReplayScanThreads), 0, s, A);
     GBL_LAUNCHED("gbl_replay_prio_index");
 }
@@ -5843,15 +5740,13 @@ int gbl_replay_batch_prio(const int8_t *ring_obs, const int16_t *ring_visits, co
                                                   sym_mask, call, obs_out, index_out))
         return fail(GBL_ERR_ARG, why);
     if (batch == 0) return GBL_OK;
-    if ((reinterpret_cast<uintptr_t>(ring_obs) | reinterpret_cast<uintptr_t>(ring_visits) | reinterpret_cast<uintptr_t>(ring_meta)) & 127u)
-        return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
-    if (reinterpret_cast<uintptr_t>(ring_prio) & 127u) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
+    if (off(128, ring_obs, ring_visits, ring_meta)) return fail(GBL_ERR_ALIGN, "ring_obs / ring_visits / ring_meta must be 128-byte aligned");
+    if (off(128, ring_prio)) return fail(GBL_ERR_ALIGN, "ring_prio must be 128-byte aligned");
     GBL_ALIGNED(ring_state, "ring_state"); GBL_ALIGNED(prio_index, "prio_index");
     GBL_ALIGNED(obs_out, "obs_out"); GBL_ALIGNED(mask_out, "mask_out"); GBL_ALIGNED(visits_out, "visits_out");
-    if ((reinterpret_cast<uintptr_t>(index_out) | reinterpret_cast<uintptr_t>(prio_out)) & 3u)
-        return fail(GBL_ERR_ALIGN, "index_out / prio_out must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(total_out) & 7u) return fail(GBL_ERR_ALIGN, "total_out must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(sym_out) & 1u) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
+    if (off(4, index_out, prio_out)) return fail(GBL_ERR_ALIGN, "index_out / prio_out must be 4-byte aligned");
+    if (off(8, total_out)) return fail(GBL_ERR_ALIGN, "total_out must be 8-byte aligned");
+    if (off(2, sym_out)) return fail(GBL_ERR_ALIGN, "sym_out must be 2-byte aligned");
     const Geometry g = geometry(batch);
     const ReplayBatchPrioArgs A{{ring_obs, ring_visits, ring_meta, ring_state, obs_out, mask_out, visits_out, z_out, index_out, sym_out,
                                  batch, g.ntiles, recent, (uint64_t)capacity, seed, sample_base, call, (uint32_t)sym_mask},
@@ -5874,7 +5769,7 @@ int gbl_tb_layout(const int32_t *inventory, int64_t *out)
 int gbl_tb_prepare(const int32_t *inventory, void *aux, void *stream)
 {
     if (const char *why = tb_inventory_error(inventory)) return fail(GBL_ERR_ARG, why);
-    GBL_NEED(aux, "aux");
+    if (!aux) return fail(GBL_ERR_ARG, "aux must not be NULL");
     GBL_ALIGNED(aux, "aux");
     hipLaunchKernelGGL(k_tb_prepare, dim3(1), dim3(kTbThreads), 0, (hipStream_t)stream, static_cast<uint8_t *>(aux));
     GBL_LAUNCHED("gbl_tb_prepare");
@@ -5886,7 +5781,7 @@ int gbl_tb_sweep(const int32_t *inventory, const void *aux, const int8_t *table,
     if (const char *why = tb_sweep_error(inventory, aux, table, out, first, count, k, decided)) return fail(GBL_ERR_ARG, why);
     if (count == 0) return GBL_OK;
     GBL_ALIGNED(aux, "aux");
-    if (reinterpret_cast<uintptr_t>(decided) & 7u) return fail(GBL_ERR_ALIGN, "decided must be 8-byte aligned");
+    if (off(8, decided)) return fail(GBL_ERR_ALIGN, "decided must be 8-byte aligned");
     const TbSweepArgs A{static_cast<const uint32_t *>(aux), table, out, reinterpret_cast<unsigned long long *>(decided), (uint64_t)first,
                         (uint64_t)count, tb_shape(inventory), k};
     // two workgroups per compute unit hold their tables at once (61.6 KB each of 160 KB): no more workgroups than that on 256 CUs, each striding
@@ -5903,7 +5798,7 @@ int gbl_tb_index(const int32_t *inventory, const void *aux, const int8_t *state,
         return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_ALIGNED(aux, "aux");
-    if (reinterpret_cast<uintptr_t>(index_out) & 7u) return fail(GBL_ERR_ALIGN, "index_out must be 8-byte aligned");
+    if (off(8, index_out)) return fail(GBL_ERR_ALIGN, "index_out must be 8-byte aligned");
     const int64_t groups = std::min<int64_t>((n + 255) / 256, (int64_t)1 << 20);
     hipLaunchKernelGGL(k_tb_index, dim3((uint32_t)groups), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), state, to_move,
                        index_out, n, tb_shape(inventory));
@@ -5916,7 +5811,7 @@ int gbl_tb_position(const int32_t *inventory, const void *aux, const int64_t *in
         return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_ALIGNED(aux, "aux");
-    if (reinterpret_cast<uintptr_t>(index) & 7u) return fail(GBL_ERR_ALIGN, "index must be 8-byte aligned");
+    if (off(8, index)) return fail(GBL_ERR_ALIGN, "index must be 8-byte aligned");
     const int64_t groups = std::min<int64_t>((n + 255) / 256, (int64_t)1 << 20);
     hipLaunchKernelGGL(k_tb_position, dim3((uint32_t)groups), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), index,
                        state_out, n, tb_shape(inventory));
@@ -5931,7 +5826,7 @@ int gbl_tb_probe(const int32_t *inventory, const void *aux, const int8_t *table,
         return fail(GBL_ERR_ARG, why);
     if (n == 0) return GBL_OK;
     GBL_ALIGNED(aux, "aux");
-    if (reinterpret_cast<uintptr_t>(action_out) & 3u) return fail(GBL_ERR_ALIGN, "action_out must be 4-byte aligned");
+    if (off(4, action_out)) return fail(GBL_ERR_ALIGN, "action_out must be 4-byte aligned");
     const int64_t groups = std::min<int64_t>(n, (int64_t)1 << 20);
     hipLaunchKernelGGL(k_tb_probe, dim3((uint32_t)groups), dim3(64), 0, (hipStream_t)stream, static_cast<const uint8_t *>(aux), table, state, to_move,
                        mask, outcome_out, value_out, action_out, n, tb_shape(inventory));
@@ -5948,8 +5843,8 @@ int gbl_tb_targets(const int32_t *inventory, const void *aux, const int8_t *tabl
         return fail(GBL_ERR_ARG, why);
     if (empty) return GBL_OK;
     GBL_ALIGNED(aux, "aux");
-    if (reinterpret_cast<uintptr_t>(visits_in) & 1u) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(visits_out) & 1u) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
+    if (off(2, visits_in)) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
+    if (off(2, visits_out)) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
     const TbTargetArgs A{static_cast<const uint8_t *>(aux), table, obs, mask, visits_in, visits_out, z_in, z_out, value_out, outcome_out,
                          census_out, obs_pitch, mask_pitch, visits_pitch, z_pitch, n, tb_shape(inventory), mode, count};
     const int64_t groups = std::min<int64_t>((n + kTbTargetWaves - 1) / kTbTargetWaves, kTbTargetGroups);
@@ -5964,17 +5859,60 @@ template <bool GUMBEL, typename Args>
 static int reanalyse_launch(const gbl_evaluator *ev, Args A, void *stream, const char *what)
 {
     if (const int e = eval_net_of(ev, A.net)) return e;
-    if (reinterpret_cast<uintptr_t>(A.visits_in) & 1u) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(A.visits_out) & 1u) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
-    if (off_dword(A.root_value_out, A.action_out, A.nodes_out, A.drift_out))
+    if (off(2, A.visits_in)) return fail(GBL_ERR_ALIGN, "visits_in must be 2-byte aligned");
+    if (off(2, A.visits_out)) return fail(GBL_ERR_ALIGN, "visits_out must be 2-byte aligned");
+    if (off(4, A.root_value_out, A.action_out, A.nodes_out, A.drift_out))
         return fail(GBL_ERR_ALIGN, "root_value_out / action_out / nodes_out / drift_out must be 4-byte aligned");
     if constexpr (GUMBEL)
-        if (reinterpret_cast<uintptr_t>(A.gumbel_out) & 1u) return fail(GBL_ERR_ALIGN, "gumbel_out must be 2-byte aligned");
+        if (off(2, A.gumbel_out)) return fail(GBL_ERR_ALIGN, "gumbel_out must be 2-byte aligned");
     // the tree as gbl_tree_search_eval's: a node and a prior row per iteration, and the root's (the rule keeps no LDS)
     const size_t lds = (sizeof(TreeNode) + kEvalOutputs) * ((size_t)A.iterations + 1);
     const int64_t groups = std::min<int64_t>(A.n, knob::kReanalyseGroups);
     hipLaunchKernelGGL(k_reanalyse<GUMBEL>, dim3((uint32_t)groups), dim3(64), lds, (hipStream_t)stream, A);
     GBL_LAUNCHED(what);
+}
+
+// gbl_train_step (EX = false: the weighted step's six arguments are not read) and gbl_train_step_weighted under their own names: the
+// checks, the kernels' arguments, the launch shape, the rows kernel of hidden / 64 units and the reduction
+template <bool EX>
+static int train_launch(const char *name, const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
+                        float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, const float *row_weight, float *row_loss_out,
+                        int32_t *prio_out, float prio_scale, int32_t prio_floor, int32_t prio_cap, float *grad_out, float *stats_out,
+                        void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
+        return fail(GBL_ERR_ARG, why);
+    GBL_ALIGNED(obs, "obs"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(visits, "visits"); GBL_ALIGNED(params, "params");
+    GBL_ALIGNED(adam_m, "adam_m"); GBL_ALIGNED(adam_v, "adam_v"); GBL_ALIGNED(grad_out, "grad_out"); GBL_ALIGNED(stats_out, "stats_out");
+    GBL_ALIGNED(workspace, "workspace");
+    if constexpr (EX) {
+        if (const char *why = train_weighted_error(prio_out, prio_scale, prio_floor, prio_cap)) return fail(GBL_ERR_ARG, why);
+        if (off(4, row_weight, row_loss_out, prio_out)) return fail(GBL_ERR_ALIGN, "row_weight / row_loss_out / prio_out must be 4-byte aligned");
+    }
+    float *ws = static_cast<float *>(workspace);
+    const TrainExArgs X{{obs, mask, visits, z, params, adam_m, adam_v, grad_out, stats_out,
+                         ws, ws + batch * hidden, ws + 2 * batch * hidden, ws + 2 * batch * hidden + batch * kTrainDoStride, batch, hidden,
+                         TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
+                                    hyper->bias2}},
+                        row_weight, row_loss_out, prio_out, prio_scale, prio_floor, prio_cap};
+    const std::conditional_t<EX, TrainExArgs, TrainArgs> &A = X;  // (the rows kernel's own argument type)
+    // as many workgroups as stay resident on 256 CUs, at most one per four rows: 4 / 4 / 3 / 2 per CU at H = 64 / 128 / 192 / 256, the
+    // smaller of what the registers allow (127 / 127 / 168 / 212 VGPRs: 4 / 4 / 3 / 2 wavefronts per SIMD, a workgroup being one wavefront on
+    // each SIMD) and what the LDS allows (w2 and four rows' scratch: 18 / 33 / 48 / 63 KB of 160); the weighted instantiations' registers
+    // allow 4 / 4 / 2 / 2
+    const int units = hidden / 64;
+    const int64_t resident = 256 * (int64_t)(units <= 2 ? 4 : units == 3 && !EX ? 3 : 2);
+    const dim3 rows_grid((uint32_t)std::min<int64_t>((batch + kTrainRowWaves - 1) / kTrainRowWaves, resident)), rows_block(64 * kTrainRowWaves);
+    const size_t lds = train_rows_lds(hidden);
+    hipStream_t s = (hipStream_t)stream;
+    if (units == 1) hipLaunchKernelGGL((k_train_rows<1, EX>), rows_grid, rows_block, lds, s, A);
+    else if (units == 2) hipLaunchKernelGGL((k_train_rows<2, EX>), rows_grid, rows_block, lds, s, A);
+    else if (units == 3) hipLaunchKernelGGL((k_train_rows<3, EX>), rows_grid, rows_block, lds, s, A);
+    else hipLaunchKernelGGL((k_train_rows<4, EX>), rows_grid, rows_block, lds, s, A);
+    GBL_LAUNCH_CHECK(name);
+    const uint32_t tiles = (uint32_t)((train_param_count(hidden) + 3 + 63) / 64);  // (+ 3: the statistics' lanes)
+    hipLaunchKernelGGL(k_train_reduce_adam, dim3(tiles), dim3(64 * kTrainReduceWaves), 0, s, static_cast<const TrainArgs &>(X));
+    GBL_LAUNCHED(name);
 }
 
 extern "C" {
@@ -6022,32 +5960,8 @@ int gbl_train_step(const int8_t *obs, const int8_t *mask, const int16_t *visits,
                    float *params, float *adam_m, float *adam_v, const gbl_train_hyper *hyper, float *grad_out, float *stats_out,
                    void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
-        return fail(GBL_ERR_ARG, why);
-    GBL_ALIGNED(obs, "obs"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(visits, "visits"); GBL_ALIGNED(params, "params");
-    GBL_ALIGNED(adam_m, "adam_m"); GBL_ALIGNED(adam_v, "adam_v"); GBL_ALIGNED(grad_out, "grad_out"); GBL_ALIGNED(stats_out, "stats_out");
-    GBL_ALIGNED(workspace, "workspace");
-    float *ws = static_cast<float *>(workspace);
-    const TrainArgs A{obs, mask, visits, z, params, adam_m, adam_v, grad_out, stats_out,
-                      ws, ws + batch * hidden, ws + 2 * batch * hidden, ws + 2 * batch * hidden + batch * kTrainDoStride, batch, hidden,
-                      TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
-                                 hyper->bias2}};
-    // as many workgroups as stay resident on 256 CUs, at most one per four rows: 4 / 4 / 3 / 2 per CU at H = 64 / 128 / 192 / 256, the
-    // smaller of what the registers allow (127 / 127 / 168 / 212 VGPRs: 4 / 4 / 3 / 2 wavefronts per SIMD, a workgroup being one wavefront on
-    // each SIMD) and what the LDS allows (w2 and four rows' scratch: 18 / 33 / 48 / 63 KB of 160)
-    const int units = hidden / 64;
-    const int64_t resident = 256 * (int64_t)(units <= 2 ? 4 : units == 3 ? 3 : 2);
-    const dim3 rows_grid((uint32_t)std::min<int64_t>((batch + kTrainRowWaves - 1) / kTrainRowWaves, resident)), rows_block(64 * kTrainRowWaves);
-    const size_t lds = train_rows_lds(hidden);
-    hipStream_t s = (hipStream_t)stream;
-    if (units == 1) hipLaunchKernelGGL(k_train_rows<1>, rows_grid, rows_block, lds, s, A);
-    else if (units == 2) hipLaunchKernelGGL(k_train_rows<2>, rows_grid, rows_block, lds, s, A);
-    else if (units == 3) hipLaunchKernelGGL(k_train_rows<3>, rows_grid, rows_block, lds, s, A);
-    else hipLaunchKernelGGL(k_train_rows<4>, rows_grid, rows_block, lds, s, A);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_train_step");
-    const uint32_t tiles = (uint32_t)((train_param_count(hidden) + 3 + 63) / 64);  // (+ 3: the statistics' lanes)
-    hipLaunchKernelGGL(k_train_reduce_adam, dim3(tiles), dim3(64 * kTrainReduceWaves), 0, s, A);
-    GBL_LAUNCHED("gbl_train_step");
+    return train_launch<false>("gbl_train_step", obs, mask, visits, z, batch, hidden, params, adam_m, adam_v, hyper, nullptr, nullptr, nullptr, 0.f,
+                               0, 0, grad_out, stats_out, workspace, workspace_bytes, stream);
 }
 
 int gbl_train_step_weighted(const int8_t *obs, const int8_t *mask, const int16_t *visits, const int8_t *z, int64_t batch, int hidden,
@@ -6055,41 +5969,14 @@ int gbl_train_step_weighted(const int8_t *obs, const int8_t *mask, const int16_t
                             float *row_loss_out, int32_t *prio_out, float prio_scale, int32_t prio_floor, int32_t prio_cap, float *grad_out,
                             float *stats_out, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (const char *why = train_error(obs, visits, z, batch, hidden, params, adam_m, adam_v, hyper, stats_out, workspace, workspace_bytes))
-        return fail(GBL_ERR_ARG, why);
-    GBL_ALIGNED(obs, "obs"); GBL_ALIGNED(mask, "mask"); GBL_ALIGNED(visits, "visits"); GBL_ALIGNED(params, "params");
-    GBL_ALIGNED(adam_m, "adam_m"); GBL_ALIGNED(adam_v, "adam_v"); GBL_ALIGNED(grad_out, "grad_out"); GBL_ALIGNED(stats_out, "stats_out");
-    GBL_ALIGNED(workspace, "workspace");
-    if (const char *why = train_weighted_error(prio_out, prio_scale, prio_floor, prio_cap)) return fail(GBL_ERR_ARG, why);
-    if ((reinterpret_cast<uintptr_t>(row_weight) | reinterpret_cast<uintptr_t>(row_loss_out) | reinterpret_cast<uintptr_t>(prio_out)) & 3u)
-        return fail(GBL_ERR_ALIGN, "row_weight / row_loss_out / prio_out must be 4-byte aligned");
-    float *ws = static_cast<float *>(workspace);
-    const TrainExArgs X{{obs, mask, visits, z, params, adam_m, adam_v, grad_out, stats_out,
-                         ws, ws + batch * hidden, ws + 2 * batch * hidden, ws + 2 * batch * hidden + batch * kTrainDoStride, batch, hidden,
-                         TrainHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->weight_decay, hyper->value_reg, hyper->bias1,
-                                    hyper->bias2}},
-                        row_weight, row_loss_out, prio_out, prio_scale, prio_floor, prio_cap};
-    // gbl_train_step's launch shape, with the weighted instantiations' 4 / 4 / 2 / 2 wavefronts per SIMD
-    const int units = hidden / 64;
-    const int64_t resident = 256 * (int64_t)(units <= 2 ? 4 : 2);
-    const dim3 rows_grid((uint32_t)std::min<int64_t>((batch + kTrainRowWaves - 1) / kTrainRowWaves, resident)), rows_block(64 * kTrainRowWaves);
-    const size_t lds = train_rows_lds(hidden);
-    hipStream_t s = (hipStream_t)stream;
-    if (units == 1) hipLaunchKernelGGL((k_train_rows<1, true>), rows_grid, rows_block, lds, s, X);
-    else if (units == 2) hipLaunchKernelGGL((k_train_rows<2, true>), rows_grid, rows_block, lds, s, X);
-    else if (units == 3) hipLaunchKernelGGL((k_train_rows<3, true>), rows_grid, rows_block, lds, s, X);
-    else hipLaunchKernelGGL((k_train_rows<4, true>), rows_grid, rows_block, lds, s, X);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gbl_train_step_weighted");
-    const uint32_t tiles = (uint32_t)((train_param_count(hidden) + 3 + 63) / 64);  // (+ 3: the statistics' lanes)
-    hipLaunchKernelGGL(k_train_reduce_adam, dim3(tiles), dim3(64 * kTrainReduceWaves), 0, s, static_cast<const TrainArgs &>(X));
-    GBL_LAUNCHED("gbl_train_step_weighted");
+    return train_launch<true>("gbl_train_step_weighted", obs, mask, visits, z, batch, hidden, params, adam_m, adam_v, hyper, row_weight,
+                              row_loss_out, prio_out, prio_scale, prio_floor, prio_cap, grad_out, stats_out, workspace, workspace_bytes, stream);
 }
 
 int gbl_replay_importance(const int32_t *prio, int64_t batch, float beta, float *weights_out, void *stream)
 {
     if (const char *why = replay_importance_error(prio, batch, beta, weights_out)) return fail(GBL_ERR_ARG, why);
-    if ((reinterpret_cast<uintptr_t>(prio) | reinterpret_cast<uintptr_t>(weights_out)) & 3u)
-        return fail(GBL_ERR_ALIGN, "prio / weights_out must be 4-byte aligned");
+    if (off(4, prio, weights_out)) return fail(GBL_ERR_ALIGN, "prio / weights_out must be 4-byte aligned");
     // (the kernel's loops stride by the grid: one workgroup that walks the batch twice is the same kernel on a grid of 1, the experiment
     // builds' other form -- measured slower from batch 1 024 on: DESIGN.md 5.24)
     const dim3 grid(knob::kImportanceOneGroup ? 1u : (uint32_t)((batch + kImportanceThreads - 1) / kImportanceThreads));

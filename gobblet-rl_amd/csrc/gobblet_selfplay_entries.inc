@@ -1,7 +1,7 @@
 // gobblet_selfplay_entries.inc -- the nine self-play entry points of the C ABI (gbl_collect_search and its _eval, _solve, _noise,
 // _cap, _gumbel and _tb, gbl_collect_gumbel_solve and gbl_collect_gumbel_tb; include/gobblet_hip.h, include/gobblet_cpu.h), written once for both flavours.  gobblet_hip.hip and
 // gobblet_cpu.cpp include it inside their extern "C" block, after their runner, with
-//   GBL_SELFPLAY_SYMBOL(fn)              the flavour's symbol: gbl_##fn / gbl_cpu_##fn
+//   GBL_SYMBOL(fn)              the flavour's symbol: gbl_##fn / gbl_cpu_##fn
 //   GBL_SELFPLAY_RUN(name, call, stream)  the flavour's runner on a filled SelfplayCall<gbl_evaluator>, under the entry point's name
 // A wrapper fills what every member has through selfplay_common and then names, field by field, what its member adds; whatever it does
 // not name stays 0 / NULL (gobblet_device.h: SelfplayCall).
@@ -28,7 +28,7 @@ static inline SelfplayCall<gbl_evaluator> selfplay_common(SelfplayRun run, int8_
     return c;
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                         int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                                         int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj, int8_t *mover_traj,
                                         int64_t n, int64_t ply_stride, int64_t tile_stride, uint64_t seed, uint64_t env_base, uint32_t ply0,
@@ -47,7 +47,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search)(int8_t *state, int8_t *to_move, int8_t *
     return GBL_SELFPLAY_RUN("gbl_collect_search", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search_eval)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search_eval)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                              int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
                                              int8_t *obs_traj, int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj,
                                              int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj, int64_t n,
@@ -66,7 +66,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search_eval)(int8_t *state, int8_t *to_move, int
     return GBL_SELFPLAY_RUN("gbl_collect_search_eval", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search_gumbel)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search_gumbel)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                                int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
                                                int8_t *obs_traj, int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj,
                                                int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj,
@@ -89,7 +89,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search_gumbel)(int8_t *state, int8_t *to_move, i
     return GBL_SELFPLAY_RUN("gbl_collect_search_gumbel", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search_solve)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search_solve)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
                                               int8_t *obs_traj, int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj,
                                               int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj,
@@ -110,7 +110,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search_solve)(int8_t *state, int8_t *to_move, in
     return GBL_SELFPLAY_RUN("gbl_collect_search_solve", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_gumbel_solve)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_gumbel_solve)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
                                               int8_t *obs_traj, int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj,
                                               int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj,
@@ -135,7 +135,7 @@ int GBL_SELFPLAY_SYMBOL(collect_gumbel_solve)(int8_t *state, int8_t *to_move, in
     return GBL_SELFPLAY_RUN("gbl_collect_gumbel_solve", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search_noise)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search_noise)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                               int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj,
                                               int8_t *obs_traj, int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj,
                                               int8_t *how_traj, int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj,
@@ -157,7 +157,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search_noise)(int8_t *state, int8_t *to_move, in
     return GBL_SELFPLAY_RUN("gbl_collect_search_noise", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search_cap)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search_cap)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                             int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                                             int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj,
                                             int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj,
@@ -183,7 +183,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search_cap)(int8_t *state, int8_t *to_move, int8
     return GBL_SELFPLAY_RUN("gbl_collect_search_cap", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_search_tb)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_search_tb)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                            int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                                            int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj,
                                            int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj, int8_t *outcome_traj,
@@ -209,7 +209,7 @@ int GBL_SELFPLAY_SYMBOL(collect_search_tb)(int8_t *state, int8_t *to_move, int8_
     return GBL_SELFPLAY_RUN("gbl_collect_search_tb", c, stream);
 }
 
-int GBL_SELFPLAY_SYMBOL(collect_gumbel_tb)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
+int GBL_SYMBOL(collect_gumbel_tb)(int8_t *state, int8_t *to_move, int8_t *done, int32_t *actions_traj, int8_t *winner_traj,
                                            int8_t *reward_traj, int8_t *done_traj, int8_t *to_move_traj, int8_t *mask_traj, int8_t *obs_traj,
                                            int16_t *visits_traj, int32_t *value_traj, int32_t *nodes_traj, int8_t *how_traj,
                                            int8_t *mover_traj, int32_t *root_value_traj, uint8_t *priors_traj, int64_t n, int64_t ply_stride,

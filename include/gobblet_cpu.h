@@ -13,6 +13,8 @@
  *   - the gbl_cpu_tb_* entry points take `aux`, `table` and `decided` in host memory;
  *   - gbl_cpu_replay_append checks its workspace like the device flavour and does not use it; ring_state is host memory;
  *   - gbl_cpu_set_threads(t): boards are dealt over t std::threads (0 = the hardware's; the library reads no environment).
+ * The argument checks are the device flavour's own, less its alignment rules: both call the same <name>_error() of
+ * gobblet-rl_amd/csrc/gobblet_device.h, and tests/golden/env_arg_errors.json (with the other *_arg_errors.json tables) pins them on both.
  * Threading and devices (gobblet_hip.h has the same paragraph): the library is re-entrant and holds no global state but the one number
  * gbl_cpu_set_threads stores, which is read once per call and changes how many workers a call starts, never a result; any number of
  * host threads may call at the same time, each on buffers of its own.  The error text is per thread: gbl_cpu_last_error() returns what

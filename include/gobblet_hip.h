@@ -80,6 +80,11 @@ extern "C" {
 #define GBL_ERR_ARG (-1)   /* null / negative / out-of-range argument */
 #define GBL_ERR_ALIGN (-2) /* a row buffer is not 16-byte aligned */
 #define GBL_ERR_HIP (-3)   /* a HIP runtime call failed; see gbl_last_error() */
+/* Where an entry point's argument contract lives: its rules that both flavours have are one <name>_error() in
+ * gobblet-rl_amd/csrc/gobblet_device.h, in the order they are reported; the device flavour's alignment rules follow in gobblet_hip.hip.
+ * For gbl_reset ... gbl_greedy_act_at and the device-memory helpers tests/golden/env_arg_errors.json pins every rule, the order and
+ * the early returns on both flavours (tests/test_abi_and_host.py replays it), as the other tests/golden/ *_arg_errors.json tables do
+ * for the later families. */
 
 #define GBL_CELLS 27
 #define GBL_ACTIONS 54

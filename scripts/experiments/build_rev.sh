@@ -8,8 +8,8 @@ mkdir -p $tmp/gobblet-rl_amd/csrc $tmp/include build
 for f in gobblet-rl_amd/csrc/gobblet_hip.hip gobblet-rl_amd/csrc/gobblet_device.h gobblet-rl_amd/csrc/gobblet_diag.h include/gobblet_hip.h; do
   git show $rev:$f > $tmp/$f
 done
-# (revisions since round 6 have the first two, revisions with the folded self-play entry points the third)
-for f in gobblet-rl_amd/csrc/gobblet_knobs.h gobblet-rl_amd/csrc/gobblet_ab.h gobblet-rl_amd/csrc/gobblet_selfplay_entries.inc; do
+# (revisions since round 6 have the first two, revisions with the folded self-play entry points the third, with the folded forwarding ones the fourth)
+for f in gobblet-rl_amd/csrc/gobblet_knobs.h gobblet-rl_amd/csrc/gobblet_ab.h gobblet-rl_amd/csrc/gobblet_selfplay_entries.inc gobblet-rl_amd/csrc/gobblet_env_entries.inc; do
   git show $rev:$f > $tmp/$f 2> /dev/null || rm -f $tmp/$f
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -mcode-object-version=5 \

@@ -29,8 +29,8 @@ def capture(fn, *a):
 
 
 def kernel_source_hash():
-    # (bench.py's kernel_source_hash, which compares against what is recorded here: the same three files.  The library's fourth
-    # source, gobblet_selfplay_entries.inc, is host code between the C ABI and the launch and holds no kernel.)
+    # (bench.py's kernel_source_hash, which compares against what is recorded here: the same three files.  The library's other
+    # sources, gobblet_selfplay_entries.inc and gobblet_env_entries.inc, are host code between the C ABI and the launch and hold no kernel.)
     h = hashlib.sha256()
     for f in ("gobblet_hip.hip", "gobblet_device.h", "gobblet_knobs.h"):
         h.update(open(os.path.join(ROOT, "gobblet-rl_amd", "csrc", f), "rb").read())

@@ -160,16 +160,21 @@ def midgame_boards(n=65536, device=DEV, turn=False, planted=False):
 def recorded_call(lib, prefix, case):
     """One case of a tests/golden/*_arg_errors.json table: every "ev" in its argument list is an evaluator, given as its eight fields
     (or null) in case["ev"] (one for the whole list) or case["evs"] (one after the other); a table without evaluators has neither.
-    Every pointer is a number that is never read (all calls return before any work).  Returns the return code."""
+    Every pointer is a number that is never read (all calls return before any work); where the ABI has a typed pointer (an int32_t *out)
+    the number is cast to it.  Returns the return code."""
     evs = [None if e is None else nat.Evaluator(*e) for e in case.get("evs", [case.get("ev")])]
     it = iter(evs) if "evs" in case else itertools.repeat(evs[0])
+    fn = getattr(lib, prefix + case["fn"])
     args = []
-    for x in case["args"]:
+    for x, ctype in zip(case["args"], fn.argtypes):
         if x == "ev":
             e = next(it)
             x = None if e is None else C.addressof(e)
+        elif isinstance(x, int) and isinstance(ctype, type) and issubclass(ctype, C._Pointer):
+            x = C.cast(x, ctype)
         args.append(x)
-    return getattr(lib, prefix + case["fn"])(*args)
+    assert len(args) == len(case["args"]), case["fn"]
+    return fn(*args)
 
 
 def replay_arg_errors(table, flavours=("device", "host")):

@@ -132,6 +132,23 @@ def test_layout_info_and_host_side_argument_errors():
         nat.check(nat.ERR_ARG, "x")
 
 
+def test_env_entry_points_recorded_argument_errors():
+    """tests/golden/env_arg_errors.json (scripts/record_env_arg_errors.py): for the env, collect and greedy entry points and the four
+    helpers without a host flavour, every check alone, every adjacent pair broken together and the n == 0 / plies == 0 early returns,
+    with the return code and the last-error text of either flavour as recorded BEFORE the checks were written once in
+    csrc/gobblet_device.h.  Every call returns before any work: no GPU needed."""
+    from tests.search_harness import replay_arg_errors
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "env_arg_errors.json")))
+    covered = {c["fn"] for c in table}
+    assert len(table) > 500 and len(covered) == 31 and {"step", "collect_from_ex", "greedy_act_at", "placement_probe"} <= covered
+    for fn in covered:  # (every function has a case of each flavour it has; a function with n has both early-return cases)
+        mine = [c for c in table if c["fn"] == fn]
+        assert any(c["device"][0] for c in mine), fn
+        assert ("gbl_" + fn in nat._NO_HOST_FLAVOUR) == all(c["host"] is None for c in mine), fn
+    assert sum(c["device"][0] == nat.ERR_ALIGN for c in table) > 150 and sum(c["device"][0] == 0 for c in table) > 60
+    replay_arg_errors(table)
+
+
 def test_the_host_flavour_is_asked_for_never_fallen_back_to():
     """A GPU device without a GPU is an error -- nothing routes it to the host flavour; "cpu" asks for the host flavour of the
     ABI (include/gobblet_cpu.h) by name; any other device has no flavour."""

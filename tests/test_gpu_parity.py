@@ -1456,3 +1456,78 @@ def test_step_into_trajectory_slots(G, n, illegal, auto_reset):
         a.step_into(acts, out, T)
     with pytest.raises(ValueError):
         a.step_into(acts, a.trajectory_buffers(2, layout="tile"), 0)
+
+
+# ---- the seven forwarding entry points (csrc/gobblet_env_entries.inc) against the long forms they forward to ----------------------
+# wrapper: (the long form, the arguments the long form adds, at the defaults the wrapper passes)
+_STEP_DEFAULTS = dict(status_out=None, next_actions_out=None, seed=0, env_base=0, ply=0, ply_dev=None)
+FORWARDS = {
+    "step": ("step_ex", dict(_STEP_DEFAULTS, actions_out=None, done_out=None, to_move_out=None)),
+    "step_into": ("step_ex", _STEP_DEFAULTS),
+    "sample": ("sample_at", dict(ply_dev=None)),
+    "rollout": ("rollout_at", dict(ply_dev=None)),
+    "collect": ("collect_from_ex", dict(first_actions=None, first_status=None)),
+    "collect_from": ("collect_from_ex", dict(first_status=None)),
+    "greedy_act": ("greedy_act_at", dict(call_dev=None)),
+}
+
+
+@pytest.mark.parametrize("flavour", ["device", "host"])
+@pytest.mark.parametrize("wrapper", sorted(FORWARDS))
+def test_forwarding_entry_points_are_their_long_forms(G, wrapper, flavour):
+    """Each wrapper against its _ex / _at form called with the defaulted arguments spelt out, on 65 boards (one whole tile and a
+    one-board ragged tile) and 3 plies where there are plies: every array either call can write, the boards' end state and the
+    counters' totals are equal bit for bit, on both flavours.  The argument order is the header's."""
+    import re
+    from gobblet_rl_amd import _native as nat
+    n, plies, slot = 65, 3, 128
+    cells = (plies - 1) * slot + n
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gobblet_hip.h")).read()
+
+    def order(fn):
+        return [re.fullmatch(r"\s*(?:const )?\w+ \*?(\w+)\s*", p).group(1)
+                for p in re.search(r"^int gbl_" + fn + r"\(([^;]*)\);", hdr, re.M).group(1).split(",")]
+
+    state, tm, dn = selfplay(n, 12, seed=5)
+    legal = oracle.batch_legal_mask(state, tm)
+    acts = oracle.batch_sample(legal, 9, 0, 0).astype(np.int32)
+
+    def out(count, dtype=np.int8):
+        return np.full(count, 0x5A, dtype=dtype)
+    start = dict(state=state, to_move=tm, done=dn, actions=acts, first_actions=acts, mask=legal.astype(np.int8),
+                 turn=np.zeros(n, np.int32), counters=np.zeros(nat.COUNTER_STRIPES * nat.COUNTER_STRIDE, np.int64),
+                 hist=np.full(6 * n, -1, np.int8), winner_out=out(n), reward_out=out(2 * n), mask_out=out(54 * n), obs_out=out(117 * n),
+                 actions_out=out(n, np.int32), done_out=out(n), to_move_out=out(n), action_out=out(n, np.int32),
+                 chosen_out=out(n, np.int32), cand_mask_out=out(54 * n), fallback_out=out(n), actions_traj=out(cells, np.int32),
+                 winner_traj=out(cells), reward_traj=out(2 * cells), done_traj=out(cells), to_move_traj=out(cells),
+                 mask_traj=out(54 * cells), obs_traj=out(117 * cells))
+    scalars = dict(n=n, illegal_mode=0, auto_reset=1, seed=7, env_base=3, ply=5, ply0=5, plies=plies, ply_stride=slot, tile_stride=64,
+                   depth=2, call=3, ply_dev=None, stream=None)
+    if wrapper == "greedy_act":
+        start["mask"] = None  # (optional there: the legal moves)
+    elif wrapper == "sample":
+        start["actions"] = out(n, np.int32)  # (its output)
+
+    def run(fn, more):
+        given = dict(scalars, **more)
+        if flavour == "device":
+            arrays = {k: None if v is None else t(v) for k, v in start.items()}
+            lib, prefix, where = nat.lib(), "gbl_", lambda x: x.data_ptr()
+        else:
+            arrays = {k: None if v is None else np.ascontiguousarray(v).copy() for k, v in start.items()}
+            lib, prefix, where = nat.cpu_raw(), "gbl_cpu_", lambda x: x.ctypes.data
+        args = [given[k] if k in given else None if arrays[k] is None else where(arrays[k]) for k in order(fn)]
+        assert getattr(lib, prefix + fn)(*args) == 0, getattr(lib, prefix + "last_error")()
+        if flavour == "device":
+            torch.cuda.synchronize()
+            arrays = {k: None if v is None else npy(v) for k, v in arrays.items()}
+        arrays["counters"] = arrays["counters"].reshape(nat.COUNTER_STRIPES, nat.COUNTER_STRIDE).sum(0)  # (the totals are the contract)
+        return arrays
+
+    long_form, defaults = FORWARDS[wrapper]
+    assert set(order(long_form)) - set(order(wrapper)) == set(defaults)
+    short, spelt = run(wrapper, {}), run(long_form, defaults)
+    written = [k for k in short if k != "counters" and short[k] is not None and not np.array_equal(short[k], start[k])]
+    assert written, wrapper  # (the call did something)
+    for k in short:
+        assert (short[k] is None and spelt[k] is None) or np.array_equal(short[k], spelt[k]), (wrapper, flavour, k)
